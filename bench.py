@@ -30,6 +30,10 @@ while the step runs back to back AFTER the timed region, and the dominant kernel
 after-the-fact probes (the profiling passes of scripts/profile_all.sh use it: their per-kernel averages then hold the timed steps only).
 `--workload cups512` = BASELINE configs[3] (config/cups.json: K = 4 maps, four objects per frame, 64 frames per GPU, the all-gather
 payload [64 N, 4, cap, 4]); the default N = 1 line carries one rank's share of it as the `cups64` object.
+`--dump-outputs DIR` writes what the headline's last timed step returned - the network's heat / depth / centre maps and every output of
+the post-processing (peaks, 3D points, objects, the overflow word; of the NaN-padded points and k-means centres the entries in use) - as
+DIR/<name>.npy in float32 / float64, at most 64 MB (dump_outputs); N > 1: rank 0's share.
+The inputs are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -68,7 +72,11 @@ def parse(argv=None):
     ap.add_argument("--no-cups", action="store_true", help="N=1: skip the configs[3] object (`cups64`)")
     ap.add_argument("--no-host-fed", action="store_true", help="N=1: skip the `host_fed` object (the batch-64 step with its frames starting in pinned host memory)")
     ap.add_argument("--no-probes", action="store_true", help="skip the power / operand / collective probes behind the timed region (profiling passes)")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the headline's last timed step returned as DIR/<name>.npy (rank 0)")
+    args = ap.parse_args(argv)
+    if args.dump_outputs and args.workload == "stream8":
+        ap.error("--dump-outputs needs a batch workload (the headline): --workload stream8 has none")
+    return args
 
 
 # --------------------------------------------------------------------------------------------------
@@ -394,8 +402,9 @@ def bump_maps(start, count, dev, wl):
     return to("heat"), to("depth"), to("centers"), n_peaks
 
 
-def run_precision(name, ctx, steps, warmup, workload="batch64"):
-    """Timed steps of the hot path at one precision on this rank.  Returns (result dict, heat maps of the error sample)."""
+def run_precision(name, ctx, steps, warmup, workload="batch64", dump_dir=None):
+    """Timed steps of the hot path at one precision on this rank.  Returns (result dict, heat maps of the error sample).
+    dump_dir: the outputs of the last timed step are written there (dump_outputs)."""
     import torch
     from object_keypoints_amd import distributed as dist_, ops
     from object_keypoints_amd.perception.pipeline import BatchedKeypointPipeline
@@ -424,13 +433,13 @@ def run_precision(name, ctx, steps, warmup, workload="batch64"):
     def step(i=0):
         # split-product configurations: the network's fp16-range flag is folded into the step's `overflow` word on the device (no host read
         # in the timed loop; asserted clear behind it)
-        net.deployed(pool[i % len(pool)], check_range=False)          # heat / depth / centre maps of the network (in full)
+        maps = net.deployed(pool[i % len(pool)], check_range=False)   # heat / depth / centre maps of the network (in full)
         out = pipe.postprocess_device(b_heat, b_depth, b_centers, range_flag=net.range_flag(dev))     # peaks -> 3D -> objects on the injected scenes
-        return out, dist_.all_gather_keypoints(out["points"], total_frames=batch * world)
+        return maps, out, dist_.all_gather_keypoints(out["points"], total_frames=batch * world)
 
     with torch.no_grad():
         for i in range(warmup):
-            out, gathered = step(i)
+            maps, out, gathered = step(i)
         m0 = ops.COUNTERS["macs"]
         net.deployed(frames)
         gflop_per_frame = 2.0 * (ops.COUNTERS["macs"] - m0) / batch / 1e9       # what this network's launches multiply (K = 3: GFLOP_PER_FRAME)
@@ -439,7 +448,7 @@ def run_precision(name, ctx, steps, warmup, workload="batch64"):
         t0 = time.perf_counter()
         for i in range(steps):
             timer.step = i
-            out, gathered = step(i)
+            maps, out, gathered = step(i)
         dist_.barrier(); torch.cuda.synchronize()
         elapsed = time.perf_counter() - t0
         timer.enabled = False
@@ -449,6 +458,13 @@ def run_precision(name, ctx, steps, warmup, workload="batch64"):
         assert not bool(out["overflow"]), "peak / object capacity exceeded, or an activation left the fp16 range (split-product configurations), in the timed step"
         found = int(out["count"].sum())
         assert batch <= found <= n_peaks, (found, n_peaks)      # at least the centre of every frame; bumps closer than the 5x5 window merge
+        if dump_dir:
+            # the network's maps and everything the pipeline computed from the injected scenes (whose maps are inputs, not outputs);
+            # of the NaN-padded fixed-capacity outputs, the entries a caller reads
+            arrays = dict(zip(("heat", "depth", "centers"), maps))
+            arrays.update((k, v) for k, v in out.items() if k not in arrays)
+            arrays["points"], arrays["reduced"] = used_entries(out, wl["keypoint_config"])
+            dump_outputs(dump_dir, arrays)
         sample = None
         if ctx["err_frames"] is not None:
             # the error sample through the product path: maps, peak indices (okp_peak_nms) and per-peak 3D points (okp_lift_peaks)
@@ -522,6 +538,53 @@ def run_precision(name, ctx, steps, warmup, workload="batch64"):
     del pipe, net
     torch.cuda.empty_cache()
     return res, sample
+
+
+DUMP_BYTES = 64 << 20     # --dump-outputs: at most this much in all
+
+
+def used_entries(out, keypoint_config):
+    """The entries of the fixed-capacity outputs of BatchedKeypointPipeline.postprocess_device that a caller reads (objects()); the
+    other slots hold NaN.  points[n, k, :count[n, k]] -> [peaks, 4] and, for the objects o < n_obj[n] whose multi-instance type i
+    received more votes than its keypoint_config[i] instances, reduced[n, o, i, :keypoint_config[i]] -> [centres, 2]; both in index order."""
+    import torch
+    points, reduced, votes = out["points"], out["reduced"], out["n_votes"]
+    dev = points.device
+    used = torch.arange(points.shape[2], device=dev) < out["count"].unsqueeze(-1)
+    cfg = torch.tensor(list(keypoint_config), device=dev)
+    surplus = (torch.arange(votes.shape[1], device=dev)[:, None] < out["n_obj"][:, None, None]) & (cfg > 1) & (votes > cfg)
+    centres = surplus.unsqueeze(-1) & (torch.arange(reduced.shape[3], device=dev) < cfg[:, None])
+    return points[used], reduced[centres]
+
+
+def dump_outputs(path, arrays, budget=DUMP_BYTES):
+    """Write each tensor of `arrays` as path/<name>.npy: float32 (float64 stays float64; integers and flags as float64, exact).  Every
+    value must be finite (unused slots are left out by the caller, see used_entries); an empty array is not written.  When they exceed
+    `budget` in all, every array keeps the same fraction of its rows (leading axis), chosen with a fixed seed and listed in
+    path/<name>.rows.npy, so that two runs with the same arguments write the same rows."""
+    import numpy as np
+    import torch
+    host = {}
+    for name, t in arrays.items():
+        if t.numel() == 0:                           # (e.g. no k-means centres in this step: n_votes says so)
+            continue
+        t = t.detach().cpu()
+        if t.dtype not in (torch.float32, torch.float64):
+            t = t.float() if t.is_floating_point() else t.double()
+        host[name] = t.numpy()
+        if not np.isfinite(host[name]).all():
+            raise ValueError(f"dump_outputs: {name} holds values that are not finite")
+    total = sum(a.nbytes for a in host.values())
+    if total > budget:
+        frac = 0.9 * budget / total                  # (the headroom holds the row lists)
+        for name, a in list(host.items()):
+            if a.ndim and a.shape[0] > 1:
+                rows = np.sort(np.random.default_rng(0).choice(a.shape[0], max(1, int(a.shape[0] * frac)), replace=False))
+                host[name], host[name + ".rows"] = a[rows], rows.astype(np.float64)
+    assert sum(a.nbytes for a in host.values()) <= budget, "dump_outputs: over the size budget"
+    os.makedirs(path, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def power_probe(step, seconds=3.0, smi="rocm-smi", sync=None):
@@ -932,7 +995,7 @@ def rank_main(args):
             torch.distributed.destroy_process_group()
         return
     workload = args.workload                      # batch64 (configs[2], the headline) or cups512 (configs[3])
-    head, head_heat = run_precision(args.dtype, ctx, args.steps, args.warmup, workload)
+    head, head_heat = run_precision(args.dtype, ctx, args.steps, args.warmup, workload, args.dump_outputs if rank == 0 else None)
     result = {
         "metric": "frames/sec keypoint inference (511x511 -> heatmaps+3D)",
         "value": head["value"], "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,

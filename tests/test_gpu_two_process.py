@@ -121,40 +121,54 @@ def test_two_ranks_on_one_gpu_gather_what_one_process_computes():
     assert np.isfinite(gathered[:, :, 0, :]).all()                   # every map of every frame holds at least one peak
 
 
-# ---- the rehearsal of the driver's 8-GPU run: EIGHT ranks (one process each, all on this box's one GPU), config/cups.json (K = 4 maps),
-# ---- an uneven total: 61 frames -> blocks of 8, 8, 8, 8, 8, 7, 7, 7, padded for the collective and trimmed after it ----------------------
-TOTAL8, WORLD8 = 61, 8
+# ---- the rehearsal of the driver's 8-GPU run: EIGHT ranks, config/cups.json (K = 4 maps), an uneven total: 61 frames -> blocks of
+# ---- 8, 8, 8, 8, 8, 7, 7, 7, padded for the collective and trimmed after it.  Every block goes through the HIP path at its own batch size in
+# ---- a process of its own (a pool of BLOCK_PROCS, all on this box's one GPU); the eight gloo ranks that gather them never open the device,
+# ---- so at most BLOCK_PROCS + 1 processes hold it at once (a shared box caps the processes per GPU) ----------------------------------------
+TOTAL8, WORLD8, BLOCK_PROCS = 61, 8, 4
 
 
-def _rank8(rank, world, port, q):
-    os.environ.update(RANK=str(rank), LOCAL_RANK="0", WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
-    os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-    from object_keypoints_amd import distributed as d
-    r, _, w = d.init(backend="gloo")
+def _block8(start, count):
+    """One rank's block of frames through the HIP path: its [count, 4, cap, 4] points and whether a map overflowed the capacity."""
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
-    start, count = d.shard(TOTAL8, r, w)
     pipe = _pipeline(dev, k=4, config=(1, 1, 1))
     points, cnt = _points(pipe, _frames(start, count, dev))
-    torch.cuda.synchronize()
+    return points.cpu().numpy(), bool((cnt > CAP).any())
+
+
+def _rank8(rank, world, port, block, q):
+    os.environ.update(RANK=str(rank), LOCAL_RANK="0", WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
+    from object_keypoints_amd import distributed as d
+    r, _, w = d.init(backend="gloo")                     # (CPU only: no HIP call in this process)
+    start, count = d.shard(TOTAL8, r, w)
+    points, overflow = block
+    assert points.shape[0] == count
     d.barrier()
-    gathered = d.all_gather_keypoints(points.cpu(), total_frames=TOTAL8)
+    gathered = d.all_gather_keypoints(torch.from_numpy(points), total_frames=TOTAL8)
     slowest = d.max_over_ranks(float(rank), torch.device("cpu"))
-    q.put((rank, start, count, gathered.numpy() if rank == 0 else tuple(gathered.shape), slowest, bool((cnt > CAP).any())))
+    q.put((rank, start, count, gathered.numpy() if rank == 0 else tuple(gathered.shape), slowest, overflow))
     d.barrier()
 
 
 def test_eight_ranks_cups_uneven_total_gather_what_one_process_computes():
+    from object_keypoints_amd import distributed as d
     ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    port = _free_port()
-    procs = [ctx.Process(target=_rank8, args=(r, WORLD8, port, q)) for r in range(WORLD8)]
-    for p in procs:
-        p.start()
-    try:
+    with ctx.Pool(BLOCK_PROCS) as pool:
+        pending = pool.starmap_async(_block8, [d.shard(TOTAL8, r, WORLD8) for r in range(WORLD8)])
+        # meanwhile, the single-process result in this process: the 61 frames as one batch
         dev = torch.device("cuda", 0)
         pipe = _pipeline(dev, k=4, config=(1, 1, 1))
         single = _points(pipe, _frames(0, TOTAL8, dev))[0].cpu().numpy()
+        blocks = pending.get(timeout=900)
+        pool.close()
+        pool.join()
+    q = ctx.Queue()
+    port = _free_port()
+    procs = [ctx.Process(target=_rank8, args=(r, WORLD8, port, blocks[r], q)) for r in range(WORLD8)]
+    for p in procs:
+        p.start()
+    try:
         results, waited = [], 0
         while len(results) < WORLD8:
             try:

@@ -534,6 +534,60 @@ def test_mixed_plan_loaded_without_an_audit_says_so():
         pp.load_keypoint_net({}, on_overflow="sometimes", device="cpu")
 
 
+def test_bench_dump_outputs_writes_float_arrays_within_the_budget(tmp_path):
+    """bench.py --dump-outputs: every output as <name>.npy in float32 / float64 (16-bit maps widened, integers and flags exact in float64);
+    over the size budget every array keeps the same seeded rows, listed next to it, and two dumps of the same outputs are identical."""
+    import bench
+    assert bench.parse(["--dump-outputs", str(tmp_path)]).dump_outputs == str(tmp_path) and bench.parse([]).dump_outputs is None
+    g = torch.Generator().manual_seed(0)
+    arrays = {"heat": torch.rand((64, 3, 64, 64), generator=g).to(torch.bfloat16), "points": torch.rand((64, 3, 8, 4), generator=g, dtype=torch.float64),
+              "count": torch.randint(0, 9, (64, 3), generator=g, dtype=torch.int32), "overflow": torch.zeros((1,), dtype=torch.int32)}
+    bench.dump_outputs(str(tmp_path / "all"), arrays)
+    got = {f[:-4]: np.load(tmp_path / "all" / f) for f in os.listdir(tmp_path / "all")}
+    assert sorted(got) == ["count", "heat", "overflow", "points"]
+    assert got["heat"].dtype == np.float32 and got["points"].dtype == np.float64 and got["count"].dtype == np.float64
+    assert np.array_equal(got["heat"], arrays["heat"].float().numpy()) and np.array_equal(got["count"], arrays["count"].numpy())
+    budget = 256 << 10                                                 # heat alone is 3 MB in float32
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), arrays, budget=budget)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == sorted(os.listdir(tmp_path / "b")) and "heat.rows.npy" in files and "overflow.rows.npy" not in files
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= budget + 128 * len(files)          # (+ the .npy headers)
+    for f in files:
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f))
+    rows = np.load(tmp_path / "a" / "heat.rows.npy").astype(np.int64)
+    assert np.array_equal(rows, np.load(tmp_path / "a" / "count.rows.npy")) and np.all(np.diff(rows) > 0)
+    assert np.array_equal(np.load(tmp_path / "a" / "heat.npy"), arrays["heat"].float().numpy()[rows])
+    bench.dump_outputs(str(tmp_path / "empty"), {"heat": arrays["heat"], "reduced": torch.zeros((0, 2))})
+    assert os.listdir(tmp_path / "empty") == ["heat.npy"]             # an empty output is left out
+    with pytest.raises(ValueError, match="points"):                   # a NaN is refused, not written
+        bench.dump_outputs(str(tmp_path / "nan"), {"points": torch.tensor([[0.0, float("nan")]])})
+
+
+def test_bench_used_entries_are_the_slots_a_caller_reads():
+    """bench.used_entries: of the NaN-padded outputs, points[n, k, :count[n, k]] and the k-means centres reduced[n, o, i, :cfg[i]] of the
+    objects o < n_obj[n] whose multi-instance type i has more votes than instances (BatchedKeypointPipeline.objects), in index order."""
+    import bench
+    n, k, cap, max_obj, max_sel, cfg = 2, 3, 4, 3, 4, (1, 3)
+    points = torch.full((n, k, cap, 4), float("nan"), dtype=torch.float64)
+    count = torch.tensor([[2, 0, 4], [1, 3, 0]], dtype=torch.int32)
+    for f in range(n):
+        for m in range(k):
+            points[f, m, :count[f, m]] = torch.arange(int(count[f, m]), dtype=torch.float64)[:, None] + 100 * f + 10 * m
+    reduced = torch.full((n, max_obj, k - 1, max_sel, 2), float("nan"))
+    votes = torch.zeros((n, max_obj, k - 1), dtype=torch.int32)
+    votes[0, 0] = torch.tensor([5, 4])        # type 0 has one instance (never reduced); type 1: 4 votes > 3 instances
+    votes[0, 2, 1] = 6                        # object 2 of frame 0 is past n_obj = 2: not read
+    votes[1, 0, 1] = 3                        # 3 votes for 3 instances: no reduction
+    reduced[0, 0, 1, :3] = torch.tensor([[1.0, 2.0], [3.0, 4.0], [5.0, 6.0]])
+    out = {"points": points, "count": count, "reduced": reduced, "n_votes": votes, "n_obj": torch.tensor([2, 1], dtype=torch.int32)}
+    pts, centres = bench.used_entries(out, cfg)
+    want = [[100 * f + 10 * m + j] * 4 for f in range(n) for m in range(k) for j in range(int(count[f, m]))]
+    assert pts.shape == (int(count.sum()), 4) and pts.tolist() == want
+    assert centres.tolist() == [[1.0, 2.0], [3.0, 4.0], [5.0, 6.0]]
+    assert torch.isfinite(pts).all() and torch.isfinite(centres).all()
+
+
 def test_bench_parity_fields_report_point_error_quantiles(tmp_path):
     """bench.parity_fields: `p_C_err_m` (the maximum) comes with median / p99 / n_over_1e-4, so that one flipped depth pixel under one
     peak (a 1.5 m outlier on a noise-like random-weight depth map) reads as an outlier and not as a bias."""
