@@ -33,7 +33,9 @@ extern "C" {
                                  7: okp_conv_patch_applies; okp_group_objects: `reduced_dev` (device k-means reduction of surplus votes);
                                     okp_conv_set_range_flag / okp_stem_set_range_flag (fp16-range guard of split-product plans), `range_flag_dev` of
                                     okp_capacity_overflow, okp_cast and okp_add_f16_f32; views of 2 GiB and more as the output of an OKP_F32X3
-                                    stem and as sources of OKP_F32X3 plans on the patch-resident kernel */
+                                    stem and as sources of OKP_F32X3 plans on the patch-resident kernel
+                                 additions at 7 (new entry points only; no struct or existing signature changed): okp_stereo_match,
+                                    okp_stereo_triangulate */
 
 /* OKP_F16: IEEE half activations / weights, fp32 accumulate (BASELINE configs[4]).
  * OKP_F32X3 (okp_conv plans only): fp32 activations, weights and results like OKP_F32 - every tensor argument of such a plan is an
@@ -408,6 +410,33 @@ int okp_triangulate_dlt(const okp_camera* left, const okp_camera* right, const d
                         const double* F, int correct_matches,
                         const float* left_xy_dev, const float* right_xy_dev, int32_t m,
                         double* out_dev, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * Stereo association and triangulation of a whole TICK on the device (BASELINE configs[4]: 2P frames = P stereo pairs, the left
+ * frame of pair p at index 2p, the right one at 2p + 1).  Both consume the okp_peak_nms outputs of the tick in place:
+ *   count [2P][K] int32, xyc [2P][K][cap][3] fp32; the peaks of map (f, k) are xyc[f][k][0 .. min(count[f][k], cap) - 1].
+ *
+ * okp_stereo_match: left/right key-point association (the reference tree has no implementation; the contract is its test,
+ * test/test_pipeline.py:208-261).  For every pair p and type k, between the peaks of left map (2p, k) and right map (2p + 1, k):
+ * undistort both views (P = K, each camera's model) -> symmetric epipolar distance against F (row-major 3 x 3, HOST) in fp64 ->
+ * entries above `max_distance` gated to 1e6 -> exact minimum-cost rectangular assignment (shortest augmenting paths) -> matches
+ * above the gate dropped.  Equivalently: the largest number of matches within the gate, of least summed cost among those - which
+ * requires cap * max_distance < 1e6 (refused otherwise).  cap <= 256.
+ *   match [P][K][cap] int32: the right-peak index of left peak i, or -1; slots i >= min(count, cap) are -1.
+ *   overflow (1 int32, may be NULL): WRITTEN (not ORed) with bit 0 = some map of the tick has count > cap (its first cap peaks are
+ *   matched), bit 1 = *range_flag_dev != 0 (the fp16-range flag of a split-product network, may be NULL; see okp_capacity_overflow).
+ * One wave per (pair, type).  No sync. */
+int okp_stereo_match(const okp_camera* left, const okp_camera* right, const double* F, double max_distance,
+                     const int32_t* count_dev, const float* xyc_dev, int32_t n_pairs, int32_t K, int32_t cap,
+                     const int32_t* range_flag_dev, int32_t* match_dev, int32_t* overflow_dev, void* stream);
+
+/* okp_stereo_triangulate: StereoCamera.triangulate (utils/camera_utils.py:92-110) of every matched slot of a tick, by the per-pair
+ * code of okp_triangulate_dlt (same T_RL / F / correct_matches conventions; F may be NULL only without the correction).
+ *   match [P][K][cap] int32 (okp_stereo_match) -> points [P][K][cap][4] fp64: (X, Y, Z, left-peak confidence) in the left camera
+ *   frame at slot = left-peak index; rows of unmatched slots are NaN (the okp_lift_peaks payload convention).  cap <= 256. */
+int okp_stereo_triangulate(const okp_camera* left, const okp_camera* right, const double* T_RL, const double* F, int correct_matches,
+                           const int32_t* count_dev, const float* xyc_dev, const int32_t* match_dev, int32_t n_pairs, int32_t K,
+                           int32_t cap, double* points_dev, void* stream);
 
 /* Undistort only (FisheyeCamera.undistort, camera_utils.py:75-81 / RadTanPinholeCamera.undistort, :57-62, by cam->model):
  * xy [m][2] fp32 -> out [m][2] fp64.  okp_fisheye_undistort is the same entry point under its round-1 name. */

@@ -578,11 +578,19 @@ __device__ int poly6_roots_oct(const double (&gc)[7], int g, double& re) {
   int deg = 6;
   double scale = 0;
   for (int i = 0; i <= 6; ++i) scale = fmax(scale, fabs(gc[i]));
-  while (deg > 0 && fabs(gc[deg]) <= 1e-14 * scale) --deg;            // (uniform over the octet)
+  // the degree and its coefficient by a fully unrolled descent (a dynamic index gc[deg] would put the array in scratch memory)
+  double lead = 1.0;
+  bool found = false;
+#pragma unroll
+  for (int i = 6; i >= 1; --i) {
+    if (!found) {
+      if (fabs(gc[i]) <= 1e-14 * scale) deg = i - 1;
+      else { found = true; lead = gc[i]; }
+    }
+  }                                                                    // (uniform over the octet)
   re = 0.0;
   if (__all(deg == 0)) return deg;
   double a[7];
-  const double lead = deg > 0 ? gc[deg] : 1.0;
   for (int i = 0; i <= 6; ++i) a[i] = i <= deg ? gc[i] / lead : 0.0;
   double radius = 0;
   for (int i = 0; i < deg; ++i) radius = fmax(radius, fabs(a[i]));
@@ -752,16 +760,13 @@ __device__ void null_vector4_oct(int g, double a0, double a1, double a2, double 
   for (int k = 0; k < 4; ++k) nv[k] = oct_bcast(mine, k);
 }
 
-__global__ __launch_bounds__(64) void okp_triangulate_kernel(TriParams tp, const float* __restrict__ lxy, const float* __restrict__ rxy, int m,
-                                                           double* __restrict__ out) {
-  const int lane = threadIdx.x & 63;
-  const int g = lane & 7;
-  const int pair = blockIdx.x * 8 + (lane >> 3);
-  const bool live = pair < m;
-  const int i = live ? pair : 0;                  // idle octets of the last wave work on pair 0 (the wave-wide votes need every lane) and store nothing
+// The per-pair work of okp_triangulate_kernel, by the octet (g = lane within it): lanes 0 / 1 undistort the left point lp[0..1] / the right
+// point rp[0..1], the octet corrects the pair (Hartley-Sturm, when tp.correct) and solves the DLT; every lane returns the dehomogenised point.
+// Shared with okp_stereo_triangulate_kernel.  Every lane of the wave must call it (wave-wide votes inside).
+__device__ __forceinline__ void triangulate_pair_oct(const TriParams& tp, int g, const float* lp, const float* rp, double& X, double& Y, double& Z) {
   double ux = 0.0, uy = 0.0;
-  if (g == 0) camera_undistort(tp.left, (double)lxy[2 * i], (double)lxy[2 * i + 1], ux, uy);
-  else if (g == 1) camera_undistort(tp.right, (double)rxy[2 * i], (double)rxy[2 * i + 1], ux, uy);
+  if (g == 0) camera_undistort(tp.left, (double)lp[0], (double)lp[1], ux, uy);
+  else if (g == 1) camera_undistort(tp.right, (double)rp[0], (double)rp[1], ux, uy);
   // cv2 hands float32 back for float32 input (camera_utils.py:93-97)
   double xl = (double)(float)oct_bcast(ux, 0), yl = (double)(float)oct_bcast(uy, 0);
   double xr = (double)(float)oct_bcast(ux, 1), yr = (double)(float)oct_bcast(uy, 1);
@@ -783,10 +788,219 @@ __global__ __launch_bounds__(64) void okp_triangulate_kernel(TriParams tp, const
   }
   double v[4];
   null_vector4_oct(g, a[0], a[1], a[2], a[3], v);
+  X = v[0] / v[3];
+  Y = v[1] / v[3];
+  Z = v[2] / v[3];
+}
+
+__global__ __launch_bounds__(64) void okp_triangulate_kernel(TriParams tp, const float* __restrict__ lxy, const float* __restrict__ rxy, int m,
+                                                           double* __restrict__ out) {
+  const int lane = threadIdx.x & 63;
+  const int g = lane & 7;
+  const int pair = blockIdx.x * 8 + (lane >> 3);
+  const bool live = pair < m;
+  const int i = live ? pair : 0;                  // idle octets of the last wave work on pair 0 (the wave-wide votes need every lane) and store nothing
+  double X, Y, Z;
+  triangulate_pair_oct(tp, g, lxy + 2 * i, rxy + 2 * i, X, Y, Z);
   if (live && g == 0) {
-    out[3 * pair + 0] = v[0] / v[3];
-    out[3 * pair + 1] = v[1] / v[3];
-    out[3 * pair + 2] = v[2] / v[3];
+    out[3 * pair + 0] = X;
+    out[3 * pair + 1] = Y;
+    out[3 * pair + 2] = Z;
+  }
+}
+
+// ------------------------------------------------------------------------------------------------------------------------
+// Stereo association of a tick on the device: the loop of StereoStreamPipeline.tick (perception/pipeline.py) and AssociationComponent
+// (the reference's association contract, test/test_pipeline.py:208-261) for every stereo pair p and key-point type k at once.  Left map
+// (2p, k), right map (2p + 1, k) of the okp_peak_nms outputs; both views undistorted with P = K by the camera's model; cost = the symmetric
+// epipolar distance against F in fp64; entries above the gate cost OKP_STEREO_BIG (the host's np.where(cost <= max_distance, cost, 1e6)),
+// the rectangular minimum-cost assignment is solved exactly and matches above the gate are dropped.  With min(n, m) * gate < 1e6 (checked
+// on the host) this maximises the number of admissible matches, then minimises their summed cost.
+// Solver: shortest augmenting paths with dual variables (Jonker-Volgenant / Hungarian, in the form of scipy's linear_sum_assignment:
+// one Dijkstra search over the columns per row), on the smaller side (rows = the fewer peaks).  One wave per (pair, type): the columns
+// are spread over the lanes (column c on lane c % 64), the per-step argmin is a butterfly over the wave (value, then a free column, then
+// the lowest index: every lane ends with the same choice, so the result is deterministic).  Costs are recomputed on the fly from a
+// per-left-peak epipolar line and a per-right-peak point kept in LDS.
+// ------------------------------------------------------------------------------------------------------------------------
+constexpr int OKP_STEREO_MAX_CAP = 256;
+constexpr double OKP_STEREO_BIG = 1e6;
+
+struct StereoParams {
+  okp_camera left, right;
+  double F[9];
+  double gate;
+  const int* count; const float* xyc; const int* range_flag;
+  int n_pairs, K, cap;
+  int* match; int* flag;
+};
+
+struct StereoLds {
+  double line[OKP_STEREO_MAX_CAP][4];     // left peak i: l = F (xu, yu, 1)^T and max(|l[0:2]|, 1e-300)
+  double pt[OKP_STEREO_MAX_CAP][3];       // right peak j: xu, yu and max(|((xu, yu, 1) F)[0:2]|, 1e-300)
+  double u[OKP_STEREO_MAX_CAP], v[OKP_STEREO_MAX_CAP], spc[OKP_STEREO_MAX_CAP];    // row / column duals, shortest path costs
+  int path[OKP_STEREO_MAX_CAP], row4col[OKP_STEREO_MAX_CAP], col4row[OKP_STEREO_MAX_CAP];
+};
+
+// AssociationComponent.cost of left peak i and right peak j
+__device__ __forceinline__ double epipolar_cost(const StereoLds& s, int i, int j) {
+  const double num = fabs(s.line[i][0] * s.pt[j][0] + s.line[i][1] * s.pt[j][1] + s.line[i][2]);
+  return 0.5 * (num / s.line[i][3] + num / s.pt[j][2]);
+}
+
+__global__ __launch_bounds__(64) void okp_stereo_match_kernel(const StereoParams p) {
+  __shared__ StereoLds s;
+  const int lane = threadIdx.x;
+  if (blockIdx.x == 0) {        // the tick's overflow word: WRITTEN, not ORed (a replayed graph must not carry an earlier tick's flag)
+    int bad = 0;
+    for (int i = lane; i < 2 * p.n_pairs * p.K; i += 64) bad |= p.count[i] > p.cap;
+    const bool any = __ballot(bad) != 0ull;
+    if (lane == 0 && p.flag) *p.flag = (any ? 1 : 0) | ((p.range_flag && *p.range_flag) ? 2 : 0);
+  }
+  const int pair = blockIdx.x / p.K, k = blockIdx.x - pair * p.K;
+  const int ml = 2 * pair * p.K + k, mr = ml + p.K;                 // maps (2p, k) and (2p + 1, k)
+  const int n = min(p.count[ml], p.cap), m = min(p.count[mr], p.cap);
+  int* out = p.match + (size_t)blockIdx.x * p.cap;
+  if (n <= 0 || m <= 0) {
+    for (int i = lane; i < p.cap; i += 64) out[i] = -1;
+    return;
+  }
+  const float* xl = p.xyc + (size_t)ml * p.cap * 3;
+  const float* xr = p.xyc + (size_t)mr * p.cap * 3;
+  const double* F = p.F;
+  for (int i = lane; i < n; i += 64) {
+    double xu, yu;
+    camera_undistort(p.left, (double)xl[3 * i], (double)xl[3 * i + 1], xu, yu);
+    const double l0 = F[0] * xu + F[1] * yu + F[2], l1 = F[3] * xu + F[4] * yu + F[5], l2 = F[6] * xu + F[7] * yu + F[8];
+    s.line[i][0] = l0; s.line[i][1] = l1; s.line[i][2] = l2;
+    s.line[i][3] = fmax(sqrt(l0 * l0 + l1 * l1), 1e-300);
+  }
+  for (int j = lane; j < m; j += 64) {
+    double xu, yu;
+    camera_undistort(p.right, (double)xr[3 * j], (double)xr[3 * j + 1], xu, yu);
+    const double c0 = xu * F[0] + yu * F[3] + F[6], c1 = xu * F[1] + yu * F[4] + F[7];
+    s.pt[j][0] = xu; s.pt[j][1] = yu;
+    s.pt[j][2] = fmax(sqrt(c0 * c0 + c1 * c1), 1e-300);
+  }
+  const bool tr = n > m;                                            // rows = right peaks, columns = left peaks
+  const int nr = tr ? m : n, nc = tr ? n : m;
+  for (int r = lane; r < nr; r += 64) { s.u[r] = 0.0; s.col4row[r] = -1; }
+  for (int c = lane; c < nc; c += 64) { s.v[c] = 0.0; s.row4col[c] = -1; }
+  __syncthreads();
+  const double gate = p.gate, inf = __builtin_inf();
+  auto cost = [&](int r, int c) {
+    const double x = tr ? epipolar_cost(s, c, r) : epipolar_cost(s, r, c);
+    return x <= gate ? x : OKP_STEREO_BIG;                          // (NaN: inadmissible, as on the host)
+  };
+  for (int cur = 0; cur < nr; ++cur) {
+    unsigned seen = 0u;                                             // bit t: column lane + 64 t has been scanned (SC)
+#pragma unroll
+    for (int t = 0; t < OKP_STEREO_MAX_CAP / 64; ++t)
+      if (lane + 64 * t < nc) s.spc[lane + 64 * t] = inf;
+    double minv = 0.0;
+    int row = cur, sink = -1;
+    while (sink < 0) {
+      const double ur = s.u[row];
+      double best = inf;
+      int bc = 0x7fffffff, bfree = 0;
+#pragma unroll
+      for (int t = 0; t < OKP_STEREO_MAX_CAP / 64; ++t) {
+        const int c = lane + 64 * t;
+        if (c < nc && !((seen >> t) & 1u)) {
+          const double r = minv + cost(row, c) - ur - s.v[c];
+          double sp = s.spc[c];
+          if (r < sp) { sp = r; s.spc[c] = r; s.path[c] = row; }
+          const int fr = s.row4col[c] < 0;
+          if (sp < best || (sp == best && fr > bfree)) { best = sp; bc = c; bfree = fr; }      // (columns ascend with t)
+        }
+      }
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) {
+        const double b2 = __shfl_xor(best, off);
+        const int c2 = __shfl_xor(bc, off), f2 = __shfl_xor(bfree, off);
+        if (b2 < best || (b2 == best && (f2 > bfree || (f2 == bfree && c2 < bc)))) { best = b2; bc = c2; bfree = f2; }
+      }
+      if (bc == 0x7fffffff) break;                                  // (no column left: cannot happen with nr <= nc and finite costs)
+      minv = best;
+      if ((bc & 63) == lane) seen |= 1u << (bc >> 6);
+      const int owner = s.row4col[bc];
+      if (owner < 0) sink = bc;
+      else row = owner;
+    }
+    if (sink < 0) break;
+    // duals: u[cur] += minv; u[row4col[c]] += minv - spc[c] and v[c] -= minv - spc[c] for the scanned columns c
+    if (lane == 0) s.u[cur] += minv;
+#pragma unroll
+    for (int t = 0; t < OKP_STEREO_MAX_CAP / 64; ++t) {
+      const int c = lane + 64 * t;
+      if (c < nc && ((seen >> t) & 1u)) {
+        const double d = minv - s.spc[c];
+        if (c != sink) s.u[s.row4col[c]] += d;
+        s.v[c] -= d;
+      }
+    }
+    __syncthreads();
+    if (lane == 0) {                                                // augment along the path back to `cur`
+      int c = sink;
+      for (;;) {
+        const int r = s.path[c];
+        s.row4col[c] = r;
+        const int next = s.col4row[r];
+        s.col4row[r] = c;
+        c = next;
+        if (r == cur) break;
+      }
+    }
+    __syncthreads();
+  }
+  for (int i = lane; i < p.cap; i += 64) {
+    int j = -1;
+    if (i < n) {
+      j = tr ? s.row4col[i] : s.col4row[i];
+      if (j >= 0 && !(epipolar_cost(s, i, j) <= gate)) j = -1;     // drop the matches above the gate
+    }
+    out[i] = j;
+  }
+}
+
+struct StereoTriParams {
+  TriParams tp;
+  const int* count; const float* xyc; const int* match;
+  int n_pairs, K, cap;
+  double* points;
+};
+
+// Every slot (pair, type, left peak i) of a tick: (X, Y, Z, left confidence) of the matched pair by the per-pair code of
+// okp_triangulate_kernel (an octet per slot, eight slots per wave), NaN rows for unmatched slots.
+__global__ __launch_bounds__(64) void okp_stereo_triangulate_kernel(const StereoTriParams p) {
+  const int lane = threadIdx.x & 63, g = lane & 7;
+  const int total = p.n_pairs * p.K * p.cap;
+  const int slot = blockIdx.x * 8 + (lane >> 3);
+  bool live = false;
+  int lo = 0, ro = 0;                                               // element offsets of the left / right peak in xyc
+  if (slot < total) {
+    const int pk = slot / p.cap, i = slot - pk * p.cap;
+    const int pair = pk / p.K, k = pk - pair * p.K;
+    const int ml = 2 * pair * p.K + k, mr = ml + p.K;
+    const int j = p.match[slot];
+    live = i < min(p.count[ml], p.cap) && j >= 0 && j < min(p.count[mr], p.cap);
+    lo = (ml * p.cap + i) * 3;
+    ro = (mr * p.cap + (live ? j : 0)) * 3;
+  }
+  const unsigned long long lv = __ballot(live);
+  const double nan = __builtin_nan("");
+  double* o = p.points + (size_t)slot * 4;
+  if (lv == 0ull) {                                                 // (wave-uniform)
+    if (slot < total && g == 0) { o[0] = nan; o[1] = nan; o[2] = nan; o[3] = nan; }
+    return;
+  }
+  const int src = __ffsll((long long)lv) - 1;                       // idle octets work on a live slot's pair and store nothing
+  const int slo = __shfl(lo, src), sro = __shfl(ro, src);
+  const int wlo = live ? lo : slo, wro = live ? ro : sro;
+  double X, Y, Z;
+  triangulate_pair_oct(p.tp, g, p.xyc + wlo, p.xyc + wro, X, Y, Z);
+  if (slot < total && g == 0) {
+    if (live) { o[0] = X; o[1] = Y; o[2] = Z; o[3] = (double)p.xyc[lo + 2]; }
+    else { o[0] = nan; o[1] = nan; o[2] = nan; o[3] = nan; }
   }
 }
 
@@ -882,4 +1096,60 @@ extern "C" int okp_triangulate_dlt(const okp_camera* left, const okp_camera* rig
   if (m <= OKP_TRI_OCTET_MAX) hipLaunchKernelGGL(okp_triangulate_kernel, dim3((m + 7) / 8), dim3(64), 0, (hipStream_t)stream, tp, lxy, rxy, m, out);     // eight pairs per wave
   else hipLaunchKernelGGL(okp_triangulate_thread_kernel, dim3((m + 63) / 64), dim3(64), 0, (hipStream_t)stream, tp, lxy, rxy, m, out);
   return okp_check_hip(hipGetLastError(), "okp_triangulate_dlt launch");
+}
+
+static int stereo_check_shape(const char* fn, int32_t n_pairs, int32_t K, int32_t cap) {
+  if (n_pairs <= 0) { okp_set_error("%s: n_pairs = %d; a tick holds at least one stereo pair", fn, n_pairs); return OKP_EINVAL; }
+  if (K < 1) { okp_set_error("%s: K = %d key-point types", fn, K); return OKP_EINVAL; }
+  if (cap < 1 || cap > OKP_STEREO_MAX_CAP) { okp_set_error("%s: cap = %d outside [1, %d]", fn, cap, OKP_STEREO_MAX_CAP); return OKP_EINVAL; }
+  if ((int64_t)2 * n_pairs * K * cap * 4 > INT32_MAX) { okp_set_error("%s: %d pairs x %d types x %d peaks is too large", fn, n_pairs, K, cap); return OKP_EINVAL; }
+  return OKP_OK;
+}
+
+static int stereo_check_cameras(const char* fn, const okp_camera* left, const okp_camera* right) {
+  if (!left || !right) { okp_set_error("%s: null camera", fn); return OKP_EINVAL; }
+  for (const okp_camera* c : {left, right})
+    if (c->model != OKP_CAM_EQUIDISTANT && c->model != OKP_CAM_RADTAN) { okp_set_error("%s: unknown camera model %d", fn, c->model); return OKP_EINVAL; }
+  return OKP_OK;
+}
+
+extern "C" int okp_stereo_match(const okp_camera* left, const okp_camera* right, const double* F, double max_distance,
+                                const int32_t* count, const float* xyc, int32_t n_pairs, int32_t K, int32_t cap,
+                                const int32_t* range_flag, int32_t* match, int32_t* overflow, void* stream) {
+  int rc = stereo_check_shape("okp_stereo_match", n_pairs, K, cap);
+  if (rc) return rc;
+  if (!(max_distance >= 0.0) || !(max_distance < 1e300)) { okp_set_error("okp_stereo_match: max_distance = %g", max_distance); return OKP_EINVAL; }
+  if ((double)cap * max_distance >= OKP_STEREO_BIG) {
+    okp_set_error("okp_stereo_match: cap * max_distance = %g is not below %g: the gated assignment would no longer maximise the number of matches",
+                  (double)cap * max_distance, OKP_STEREO_BIG);
+    return OKP_EINVAL;
+  }
+  if ((rc = stereo_check_cameras("okp_stereo_match", left, right))) return rc;
+  if (!F || !count || !xyc || !match) { okp_set_error("okp_stereo_match: null argument"); return OKP_EINVAL; }
+  StereoParams p;
+  p.left = *left; p.right = *right;
+  for (int i = 0; i < 9; ++i) p.F[i] = F[i];
+  p.gate = max_distance; p.count = count; p.xyc = xyc; p.range_flag = range_flag;
+  p.n_pairs = n_pairs; p.K = K; p.cap = cap; p.match = match; p.flag = overflow;
+  hipLaunchKernelGGL(okp_stereo_match_kernel, dim3(n_pairs * K), dim3(64), 0, (hipStream_t)stream, p);
+  return okp_check_hip(hipGetLastError(), "okp_stereo_match launch");
+}
+
+extern "C" int okp_stereo_triangulate(const okp_camera* left, const okp_camera* right, const double* T_RL, const double* F, int correct_matches,
+                                      const int32_t* count, const float* xyc, const int32_t* match, int32_t n_pairs, int32_t K, int32_t cap,
+                                      double* points, void* stream) {
+  int rc = stereo_check_shape("okp_stereo_triangulate", n_pairs, K, cap);
+  if (rc) return rc;
+  if (correct_matches && !F) { okp_set_error("okp_stereo_triangulate: the Hartley-Sturm correction needs F"); return OKP_EINVAL; }
+  if ((rc = stereo_check_cameras("okp_stereo_triangulate", left, right))) return rc;
+  if (!T_RL || !count || !xyc || !match || !points) { okp_set_error("okp_stereo_triangulate: null argument"); return OKP_EINVAL; }
+  StereoTriParams p;
+  p.tp.left = *left; p.tp.right = *right;
+  for (int i = 0; i < 12; ++i) p.tp.T[i] = T_RL[i];
+  for (int i = 0; i < 9; ++i) p.tp.F[i] = F ? F[i] : 0.0;
+  p.tp.correct = correct_matches ? 1 : 0;
+  p.count = count; p.xyc = xyc; p.match = match; p.n_pairs = n_pairs; p.K = K; p.cap = cap; p.points = points;
+  const int total = n_pairs * K * cap;
+  hipLaunchKernelGGL(okp_stereo_triangulate_kernel, dim3((total + 7) / 8), dim3(64), 0, (hipStream_t)stream, p);
+  return okp_check_hip(hipGetLastError(), "okp_stereo_triangulate launch");
 }

@@ -458,6 +458,42 @@ void triangulate_dlt(at::ArrayRef<double> left, at::ArrayRef<double> right, at::
                                (int32_t)left_xy.size(0), out.data_ptr<double>(), sp(stream)), "okp_triangulate_dlt");
 }
 
+// A tick's okp_peak_nms outputs: count [2P,K] int32, xyc [2P,K,cap,3] float32 (device); returns P
+inline int64_t stereo_tick_pairs(const Tensor& count, const Tensor& xyc) {
+  check_dev(count, at::kInt, "count"); check_dev(xyc, at::kFloat, "xyc");
+  TORCH_CHECK(xyc.dim() == 4 && xyc.size(3) == 3 && count.dim() == 2 && count.size(0) == xyc.size(0) && count.size(1) == xyc.size(1),
+              "okp: a tick's peaks are count [2P,K] int32 and xyc [2P,K,cap,3] float32");
+  TORCH_CHECK(xyc.size(0) % 2 == 0, "okp: a tick holds the left and right maps of every stereo pair: an even number of frames");
+  return xyc.size(0) / 2;
+}
+
+// F: 9 doubles (row-major 3 x 3); match [P,K,cap] int32 and overflow (1 int32) are written
+void stereo_match(at::ArrayRef<double> left, at::ArrayRef<double> right, at::ArrayRef<double> F, double max_distance, const Tensor& count, const Tensor& xyc,
+                  const Tensor& match, const Tensor& overflow, int64_t stream, const optional<Tensor>& range_flag) {
+  const int64_t P = stereo_tick_pairs(count, xyc);
+  check_dev(match, at::kInt, "match"); check_dev(overflow, at::kInt, "overflow");
+  if (range_flag.has_value()) check_dev(*range_flag, at::kInt, "range_flag");
+  TORCH_CHECK(F.size() == 9, "okp: F is row-major 3 x 3");
+  TORCH_CHECK(match.numel() == P * xyc.size(1) * xyc.size(2) && overflow.numel() >= 1, "okp: match is [P,K,cap] int32, overflow one int32");
+  const okp_camera cl = camera_of(left), cr = camera_of(right);
+  check_rc(okp_stereo_match(&cl, &cr, F.data(), max_distance, count.data_ptr<int32_t>(), xyc.data_ptr<float>(), (int32_t)P, (int32_t)xyc.size(1), (int32_t)xyc.size(2),
+                            range_flag.has_value() ? range_flag->data_ptr<int32_t>() : nullptr, match.data_ptr<int32_t>(), overflow.data_ptr<int32_t>(), sp(stream)),
+           "okp_stereo_match");
+}
+
+// T_RL: 12 doubles (row-major 3 x 4); F: 9 doubles = Hartley-Sturm correction on, empty = off; points [P,K,cap,4] float64 is written
+void stereo_triangulate(at::ArrayRef<double> left, at::ArrayRef<double> right, at::ArrayRef<double> T_RL, at::ArrayRef<double> F, const Tensor& count,
+                        const Tensor& xyc, const Tensor& match, const Tensor& points, int64_t stream) {
+  const int64_t P = stereo_tick_pairs(count, xyc);
+  check_dev(match, at::kInt, "match"); check_dev(points, at::kDouble, "points");
+  TORCH_CHECK(T_RL.size() == 12 && (F.empty() || F.size() == 9), "okp: T_RL is row-major 3 x 4, F row-major 3 x 3 (or empty)");
+  TORCH_CHECK(match.numel() == P * xyc.size(1) * xyc.size(2) && points.numel() == match.numel() * 4, "okp: match is [P,K,cap] int32, points [P,K,cap,4] float64");
+  const okp_camera cl = camera_of(left), cr = camera_of(right);
+  check_rc(okp_stereo_triangulate(&cl, &cr, T_RL.data(), F.empty() ? nullptr : F.data(), F.empty() ? 0 : 1, count.data_ptr<int32_t>(), xyc.data_ptr<float>(),
+                                  match.data_ptr<int32_t>(), (int32_t)P, (int32_t)xyc.size(1), (int32_t)xyc.size(2), points.data_ptr<double>(), sp(stream)),
+           "okp_stereo_triangulate");
+}
+
 void lift_peaks(at::ArrayRef<double> camera, const Tensor& count, const Tensor& xyc, const Tensor& depth, int64_t max_x, int64_t max_y, const Tensor& out, int64_t stream) {
   TORCH_CHECK(xyc.is_cuda() && xyc.dim() == 4 && xyc.scalar_type() == at::kFloat && depth.is_cuda() && depth.scalar_type() == at::kFloat && depth.dim() == 4 && depth.is_contiguous() &&
               depth.size(0) == xyc.size(0) && depth.size(1) == xyc.size(1) && count.scalar_type() == at::kInt && out.scalar_type() == at::kDouble &&
@@ -529,4 +565,8 @@ TORCH_LIBRARY(okp, m) {
   m.def("camera_undistort(float[] camera, Tensor xy, Tensor(a!) out, int stream) -> ()", camera_undistort);
   m.def("unproject_depth(float[] camera, Tensor xy, Tensor map_id, Tensor depth, int max_x, int max_y, Tensor(a!) out, int stream) -> ()", unproject_depth);
   m.def("triangulate_dlt(float[] left, float[] right, float[] T_RL, float[] F, Tensor left_xy, Tensor right_xy, Tensor(a!) out, int stream) -> ()", triangulate_dlt);
+  m.def("stereo_match(float[] left, float[] right, float[] F, float max_distance, Tensor count, Tensor xyc, Tensor(a!) match, Tensor(b!) overflow, int stream, "
+        "Tensor? range_flag=None) -> ()", stereo_match);
+  m.def("stereo_triangulate(float[] left, float[] right, float[] T_RL, float[] F, Tensor count, Tensor xyc, Tensor match, Tensor(a!) points, int stream) -> ()",
+        stereo_triangulate);
 }

@@ -990,3 +990,60 @@ def triangulate_dlt(cam_l, cam_r, T_RL, left_xy, right_xy, F=None):
                                               1 if F is not None else 0, left_xy.data_ptr(), right_xy.data_ptr(), left_xy.shape[0],
                                               out.data_ptr(), stream_handle()), "okp_triangulate_dlt")
     return out
+
+
+STEREO_MAX_CAPACITY = 256    # okp_stereo_match / okp_stereo_triangulate: peaks per map
+
+
+def _tick_pairs(count, xyc):
+    require_cuda(count, "count")
+    require_cuda(xyc, "xyc")
+    if count.dtype != torch.int32 or xyc.dtype != torch.float32 or xyc.dim() != 4 or xyc.shape[3] != 3 or tuple(count.shape) != tuple(xyc.shape[:2]):
+        raise OkpError("a tick's peaks are count [2P,K] int32 and xyc [2P,K,cap,3] float32 (peak_nms outputs)")
+    if xyc.shape[0] % 2:
+        raise OkpError("a tick holds the left and right maps of every stereo pair: an even number of frames")
+    return xyc.shape[0] // 2, xyc.shape[1], xyc.shape[2]
+
+
+def stereo_match(cam_l, cam_r, F, count, xyc, max_distance, range_flag=None):
+    """Left/right association of a whole tick on the device (okp_stereo_match): count [2P,K] int32, xyc [2P,K,cap,3] fp32 (peak_nms of
+    the 2P frames, left frame of pair p at 2p) -> match [P,K,cap] int32 (right-peak index of left peak i, -1 = unmatched) and overflow
+    (0-d int32, written: bit 0 some map has more than cap peaks, bit 1 (RANGE_OVERFLOW) `range_flag` was raised).  The minimum-cost
+    assignment on the symmetric epipolar distance against F, gated at `max_distance` - AssociationComponent's contract.  No host sync."""
+    n_pairs, k, cap = _tick_pairs(count, xyc)
+    count, xyc = count.contiguous(), xyc.contiguous()
+    Fl = [float(v) for v in np.asarray(F, dtype=np.float64).reshape(9)]
+    match = torch.empty((n_pairs, k, cap), dtype=torch.int32, device=xyc.device)
+    flag = torch.empty((1,), dtype=torch.int32, device=xyc.device)
+    T = _ops()
+    if T is not None:
+        _dispatch(T.stereo_match, _cam_list(cam_l), _cam_list(cam_r), Fl, float(max_distance), count, xyc, match, flag, stream_int(), range_flag)
+    else:
+        Fa = (ctypes.c_double * 9)(*Fl)
+        _lib.check(_lib.lib().okp_stereo_match(ctypes.byref(cam_l), ctypes.byref(cam_r), Fa, float(max_distance), count.data_ptr(), xyc.data_ptr(),
+                                               n_pairs, k, cap, range_flag.data_ptr() if range_flag is not None else None, match.data_ptr(),
+                                               flag.data_ptr(), stream_handle()), "okp_stereo_match")
+    return match, flag[0]
+
+
+def stereo_triangulate(cam_l, cam_r, T_RL, count, xyc, match, F=None):
+    """Every matched slot of a tick triangulated in place (okp_stereo_triangulate, the per-pair code of okp_triangulate_dlt; with F the
+    Hartley-Sturm correction): -> points [P,K,cap,4] fp64 (X, Y, Z, left confidence) in the left camera frame at slot = left-peak index,
+    NaN rows for unmatched slots (the lift_peaks payload convention)."""
+    n_pairs, k, cap = _tick_pairs(count, xyc)
+    require_cuda(match, "match")
+    if match.dtype != torch.int32 or tuple(match.shape) != (n_pairs, k, cap):
+        raise OkpError("match must be int32 [P,K,cap] (stereo_match)")
+    count, xyc, match = count.contiguous(), xyc.contiguous(), match.contiguous()
+    Tm = [float(v) for v in np.asarray(T_RL, dtype=np.float64)[:3, :4].reshape(12)]
+    Fl = [] if F is None else [float(v) for v in np.asarray(F, dtype=np.float64).reshape(9)]
+    points = torch.empty((n_pairs, k, cap, 4), dtype=torch.float64, device=xyc.device)
+    TO = _ops()
+    if TO is not None:
+        _dispatch(TO.stereo_triangulate, _cam_list(cam_l), _cam_list(cam_r), Tm, Fl, count, xyc, match, points, stream_int())
+    else:
+        Ta = (ctypes.c_double * 12)(*Tm)
+        Fa = (ctypes.c_double * 9)(*Fl) if Fl else None
+        _lib.check(_lib.lib().okp_stereo_triangulate(ctypes.byref(cam_l), ctypes.byref(cam_r), Ta, Fa, 1 if Fl else 0, count.data_ptr(), xyc.data_ptr(),
+                                                     match.data_ptr(), n_pairs, k, cap, points.data_ptr(), stream_handle()), "okp_stereo_triangulate")
+    return points

@@ -557,6 +557,22 @@ class CapturedStep:
         return iter((self, self.static_in, self.static_out))
 
 
+class CapturedTick(CapturedStep):
+    """StereoStreamPipeline.capture_device: the whole device tick as one hipGraph.  heat_override, when captured, is the static input
+    `static_heat` next to `static_in` (the frames)."""
+
+    def __init__(self, net, graph, static_in, static_out, static_heat=None):
+        super().__init__(net, graph, static_in, static_out)
+        self.static_heat = static_heat
+
+    def replay(self, frames=None, heat_override=None):
+        if heat_override is not None:
+            if self.static_heat is None:
+                raise OkpError("this tick was captured without heat_override: it has no heat input")
+            self.static_heat.copy_(heat_override)
+        return super().replay(frames)
+
+
 class BatchedKeypointPipeline:
     """Frames -> heat/depth/centre maps -> peaks -> per-peak 3D points for a whole batch, device-resident.
 
@@ -869,3 +885,107 @@ class StereoStreamPipeline:
             for (p, k), X in zip(owner, pts):
                 result[p][k] = np.concatenate([result[p][k], X[None]])
         return result
+
+    # ---- the device-resident tick (no host wait between the frames and the 3D points) ------------------------------------------------
+    def _check_device_tick(self, frames):
+        if self.capacity > ops.STEREO_MAX_CAPACITY:
+            raise OkpError(f"capacity = {self.capacity}: the device association holds at most {ops.STEREO_MAX_CAPACITY} peaks per map")
+        if frames.shape[0] % 2:
+            raise OkpError("a tick holds the left and right frame of every stereo pair: an even number of frames")
+
+    def tick_device(self, frames, heat_override=None):
+        """The whole tick on the device, with no host wait anywhere: network -> peak-NMS -> left/right association (okp_stereo_match) ->
+        triangulation of every matched slot (okp_stereo_triangulate).  Same frames as tick().  Returns a dict of device tensors
+            heat, depth [2P,K,H,W], count [2P,K] int32, xyc [2P,K,cap,3] fp32, match [P,K,cap] int32,
+            points [P,K,cap,4] fp64 (X, Y, Z, left confidence; NaN rows = unmatched slots), overflow (0-d int32: bit 0 some map of the tick
+            holds more than `capacity` peaks, bit 1 ops.RANGE_OVERFLOW the split-product network's fp16-range flag)
+        results(out) turns it into tick()'s return value.  `points` is the fixed-capacity payload all_gather_keypoints carries
+        (tick_sharded)."""
+        self._check_device_tick(frames)
+        with torch.no_grad():
+            # split-product networks: the fp16-range flag is folded into `overflow` on the device instead of being read here (as
+            # BatchedKeypointPipeline.forward_device does), except with on_overflow = "float32", where the pass is judged on the host
+            defer = getattr(self.net, "on_overflow", "raise") != "float32"
+            heat, depth, _ = self.net.deployed(frames, check_range=not defer)
+            range_flag = self.net.range_flag(frames.device) if defer and hasattr(self.net, "range_flag") else None
+            if heat_override is not None:
+                heat = heat_override
+            count, _, xyc = ops.peak_nms(heat, cap=self.capacity)
+            match, overflow = ops.stereo_match(self.cam_l, self.cam_r, self.stereo.F, count, xyc, self.assoc.max_distance, range_flag=range_flag)
+            points = ops.stereo_triangulate(self.cam_l, self.cam_r, self.stereo.T_RL, count, xyc, match, F=self.stereo.F)
+        return {"heat": heat, "depth": depth, "count": count, "xyc": xyc, "match": match, "points": points, "overflow": overflow}
+
+    def capture_device(self, frames, heat_override=None):
+        """Capture the WHOLE tick_device (network, NMS, association, triangulation, overflow word) for this frame shape into one hipGraph;
+        that the capture succeeds is itself the check that nothing in the tick waits on the host.  Returns a CapturedTick: replay with
+        step.replay(new_frames[, new_heat]) or by copying into step.static_in / step.static_heat (heat_override, when given, is a static
+        input of the graph like the frames) and step.replay(); the outputs are step.static_out (tick_device's dict)."""
+        self._check_device_tick(frames)
+        static_in = frames.clone()
+        static_heat = heat_override.clone() if heat_override is not None else None
+        for _ in range(2):                                   # warm-up: plans, allocator pools, kernel attributes
+            self.tick_device(static_in, heat_override=static_heat)
+        torch.cuda.synchronize()
+        graph = torch.cuda.CUDAGraph()
+        keep, ops.SIDE_STREAMS = ops.SIDE_STREAMS, ops.SIDE_STREAMS and GRAPH_SIDE_STREAMS
+        try:
+            with torch.cuda.graph(graph):
+                static_out = self.tick_device(static_in, heat_override=static_heat)
+        finally:
+            ops.SIDE_STREAMS = keep
+        return CapturedTick(self.net, graph, static_in, static_out, static_heat)
+
+    def results(self, out):
+        """A device tick (tick_device, a CapturedTick's outputs, or tick_sharded's gathered payload) as tick() returns it: a list over
+        pairs of {type k: (n_k, 3) float64 points in the left camera frame}, in ascending left-peak order.  Reads `points` (a NaN row =
+        unmatched slot) and `overflow` only, in ONE device -> host copy; raises OkpError like tick() when the overflow word is set."""
+        pts = out["points"]
+        flat = torch.cat([out["overflow"].reshape(1).to(torch.float64), pts.reshape(-1)]).cpu().numpy()        # the one D2H copy
+        flag = int(flat[0])
+        if flag & 1:
+            raise OkpError("peak capacity exceeded in a tick; raise `capacity`")
+        if flag & ops.RANGE_OVERFLOW:
+            raise OkpError("an activation of the split-product network left the fp16 range in this tick: its maps are not fp32-grade "
+                           "(load the network with on_overflow='float32', or run it in torch.float32)")
+        pts = flat[1:].reshape(tuple(pts.shape))
+        result = []
+        for p in range(pts.shape[0]):
+            per = {}
+            for k in range(pts.shape[1]):
+                rows = pts[p, k]
+                per[k] = np.ascontiguousarray(rows[~np.isnan(rows[:, 3]), :3])       # (column 3, the confidence, is NaN exactly in unused slots)
+            result.append(per)
+        return result
+
+    def tick_sharded(self, frames_local, n_pairs_total, heat_override=None):
+        """The rig's pairs sharded over the ranks of the process group (both views of a pair on one GPU): this rank holds the frames of
+        pairs distributed.shard(n_pairs_total, rank, world) (2 per pair, left first).  Runs tick_device on them and returns
+            {"points": [n_pairs_total, K, cap, 4] fp64 - ONE all_gather_keypoints of the per-rank payloads, ordered by pair,
+             "overflow": 0-d int32 - the overflow words folded over the ranks on the device (one all_reduce, MAX: set on one rank = set
+                         on every rank), "local": this rank's tick_device dict (None for a rank without pairs)}
+        which results() reads.  A rank without pairs (world > n_pairs_total) joins both collectives with an empty block.  Without a
+        process group it is tick_device on the whole rig."""
+        import torch.distributed as dist
+        from .. import distributed
+        if int(n_pairs_total) < 1:
+            raise OkpError(f"n_pairs_total = {n_pairs_total}: a rig has at least one stereo pair")
+        self._check_device_tick(frames_local)
+        if not dist.is_initialized():
+            if frames_local.shape[0] != 2 * n_pairs_total:
+                raise OkpError(f"{frames_local.shape[0]} frames for {n_pairs_total} stereo pairs")
+            out = self.tick_device(frames_local, heat_override=heat_override)
+            return {"points": out["points"], "overflow": out["overflow"], "local": out}
+        _, n_local = distributed.shard(int(n_pairs_total), dist.get_rank(), dist.get_world_size())
+        if frames_local.shape[0] != 2 * n_local:
+            raise OkpError(f"rank {dist.get_rank()} holds {frames_local.shape[0]} frames; shard({n_pairs_total}, {dist.get_rank()}, "
+                           f"{dist.get_world_size()}) gives it {n_local} stereo pairs = {2 * n_local} frames")
+        if n_local:
+            local = self.tick_device(frames_local, heat_override=heat_override)
+            points, flag = local["points"], local["overflow"].reshape(1).clone()
+        else:
+            local, dev = None, frames_local.device
+            points = torch.empty((0, len(self.config), self.capacity, 4), dtype=torch.float64, device=dev)
+            flag = torch.zeros((1,), dtype=torch.int32, device=dev)
+        gathered = distributed.all_gather_keypoints(points, total_frames=int(n_pairs_total))
+        dist.all_reduce(flag, op=dist.ReduceOp.MAX)
+        return {"points": gathered, "overflow": flag[0], "local": local}
