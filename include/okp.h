@@ -31,7 +31,7 @@ extern "C" {
                                  5: OKP_F32X3 in okp_stem_create_dtype / okp_stem_forward_nchw (fp32 NHWC output) and okp_fire_forward; tile 13 for OKP_F32X3 plans; tile 14
                                  6: okp_conv_args.src_pairs / out_pairs (pair-format tensors between split-product 3x3 convolutions), okp_stem_forward_nchw_pairs
                                  7: okp_conv_patch_applies; okp_group_objects: `reduced_dev` (device k-means reduction of surplus votes);
-                                    okp_conv_set_range_flag / okp_stem_set_range_flag (fp16-range guard of split-product plans), `range_flag_dev` of
+                                    okp_conv_set_range_flag / okp_stem_set_range_flag (fp16-range guard of split-product and float16 plans), `range_flag_dev` of
                                     okp_capacity_overflow, okp_cast and okp_add_f16_f32; views of 2 GiB and more as the output of an OKP_F32X3
                                     stem and as sources of OKP_F32X3 plans on the patch-resident kernel
                                  additions at 7 (new entry points only; no struct or existing signature changed): okp_stereo_match,
@@ -95,14 +95,22 @@ okp_conv* okp_conv_create(int dtype, int n_src, const int32_t* cin, const int32_
  * weights.  tap_terms == NULL: all taps three terms (= okp_conv_create(OKP_F32X3, ...)). */
 okp_conv* okp_conv_create_x3(int n_src, const int32_t* cin, const int32_t* conv_stride, int32_t cout, int32_t n_taps,
                              const okp_tap* taps, const uint8_t* tap_terms, const float* bias, int act);
-/* OKP_F32X3 range guard (ABI 7).  A split-product plan halves its fp32 operands into fp16: a value beyond +-65504 (or a non-finite one)
+/* OKP_F32X3 / OKP_F16 range guard (ABI 7).  A split-product plan halves its fp32 operands into fp16: a value beyond +-65504 (or a non-finite one)
  * becomes (inf, -inf), its products NaN, and the next ReLU turns the NaN into 0 - silently, where the reference's fp32 arithmetic
  * (py_utils/utils.py:143-156) returns numbers.  With a flag attached, every launch of the plan (okp_conv_forward on any tile, and
  * okp_fire_forward / okp_heads_forward through their squeeze / first-layer plan) ORs 1 into *flag_dev when the magnitude of one of its
  * RESULTS - a value the next split-product layer will halve, including the squeeze tile of the one-launch fire module and the hidden layer
  * of the heads - passes 65504 (a running maximum; with every input in range no NaN can arise, so infinity is the only way out);
  * okp_stem_set_range_flag does the same for the stem and checks the frames it reads exactly (NaN included), as okp_cast / okp_add_f16_f32
- * do for the fp16 data they hand to split-product consumers.  The
+ * do for the fp16 data they hand to split-product consumers.
+ * OKP_F16 plans take a flag too (the 16-bit storage guard): fp16 rounds a result beyond 65504 to inf, and the next layer's sums make NaN of it,
+ * which the next ReLU turns into 0.  With a flag attached, the plan's launches - okp_conv_forward on every tile, okp_fire_forward (the
+ * squeeze plan's flag: squeeze tile and both outputs), okp_fire_chain_forward (the first squeeze plan's flag: every module's squeeze tile
+ * and output inside the chain), okp_heads_forward (l1's flag: both hidden layers) - run separate range-guarded instantiations (okp_fire_forward: only where the output
+ * width is a multiple of 16 at stride 1 / of 8 at stride 2, else OKP_EINVAL - run the squeeze plan and the fused tail) that OR 1 into
+ * *flag_dev when a value they store in fp16 is not finite (exact, on the packed words); an OKP_F16 stem (okp_stem_set_range_flag) checks
+ * its results and the frames it reads the same way (okp_stem_forward: the packed frames as they are in LDS; okp_pack_frames has no flag).  Without a flag the fp16 kernels are the unguarded ones, unchanged.  OKP_BF16 and
+ * OKP_F32 plans have fp32's range and are refused (OKP_EINVAL).  okp_dwconv3x3_forward takes no flag: the network does not launch it.  The
  * flag is never cleared by the library: the caller zeroes it before a pass and reads it after (or hands it to okp_capacity_overflow).
  * flag_dev: DEVICE int32, NULL = off (the default).  Set once, before the plan is used from several threads or captured in a graph. */
 int okp_conv_set_range_flag(okp_conv* plan, int32_t* flag_dev);
@@ -274,7 +282,7 @@ typedef struct okp_stem okp_stem;
 okp_stem* okp_stem_create(const float* w_host, const float* bias_host);                       /* bf16 */
 okp_stem* okp_stem_create_dtype(int dtype, const float* w_host, const float* bias_host);    /* OKP_BF16, OKP_F16, or OKP_F32X3: the split-product
                                                                                                form (fp32 NHWC output; okp_stem_forward_nchw only) */
-int okp_stem_set_range_flag(okp_stem* stem, int32_t* flag_dev);   /* OKP_F32X3 stems: see okp_conv_set_range_flag */
+int okp_stem_set_range_flag(okp_stem* stem, int32_t* flag_dev);   /* OKP_F32X3 and OKP_F16 stems: see okp_conv_set_range_flag */
 void okp_stem_destroy(okp_stem* stem);
 int okp_stem_forward(const okp_stem* stem, int32_t n, int32_t h, int32_t w, const okp_tensor* packed, const okp_tensor* out, void* stream);
 /* Same layer straight from the reference's input layout, fp32 NCHW frames (n,3,h,w): the bf16 rounding and the zero

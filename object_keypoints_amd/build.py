@@ -6,7 +6,9 @@ hipcc cross-compiles without a GPU; each .hip is compiled to build/*.o in parall
 into object_keypoints_amd/lib/libokp_hip.so.
 """
 import concurrent.futures
+import json
 import os
+import re
 import subprocess
 import sys
 
@@ -25,6 +27,9 @@ CFLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-I" + os.path
 # AGPRs and copies all of them to and from VGPRs around every K-step (v_accvgpr_write/read x 128).
 VGPR_FORM = ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]
 AGPR_FILES = set()
+# per-kernel register / scratch report of the device compile (remarks only: the code is the same): build() checks that no range-guarded
+# float16 instantiation (the `bool G` kernels, include/okp.h okp_conv_set_range_flag) spills
+RESOURCE_REMARKS = ["-Rpass-analysis=kernel-resource-usage"]
 
 
 def _sources():
@@ -43,10 +48,74 @@ def _stale(target, deps):
     return any(os.path.getmtime(d) > t for d in deps)
 
 
+def _parse_resources(stderr):
+    """-Rpass-analysis=kernel-resource-usage remarks -> {kernel symbol: {"vgprs", "agprs", "scratch", "vgpr_spill", "sgpr_spill"}}."""
+    out, cur = {}, None
+    keys = {"VGPRs": "vgprs", "AGPRs": "agprs", "ScratchSize [bytes/lane]": "scratch", "VGPRs Spill": "vgpr_spill", "SGPRs Spill": "sgpr_spill"}
+    for line in stderr.splitlines():
+        m = re.search(r"remark: .*?Function Name: (\S+)", line)
+        if m:
+            cur = out.setdefault(m.group(1), {})
+            continue
+        m = re.search(r"remark: +([A-Za-z][A-Za-z \[\]/]*?): (\d+)(?: \[-Rpass[^\]]*\])?\s*$", line)
+        if m and cur is not None and m.group(1) in keys:
+            cur[keys[m.group(1)]] = int(m.group(2))
+    return out
+
+
+def _without_remarks(stderr):
+    """The compiler's console output without the resource remarks (they go to the report) and the source excerpts printed under them."""
+    keep, held, in_remark = [], [], False
+    for line in stderr.splitlines():
+        if line.startswith("In file included from"):
+            held.append(line)                  # (kept only if what follows is not a remark)
+            continue
+        if "remark:" in line:
+            in_remark, held = True, []
+            continue
+        if in_remark and re.match(r"^\s*(\d+ )?\|", line):
+            continue
+        in_remark = False
+        keep += held + [line]
+        held = []
+    return "\n".join(keep)
+
+
+def _guarded_f16(symbol):
+    """A range-guarded float16 instantiation: an fp16 kernel whose last template argument is the guard, true."""
+    return "DF16_" in symbol and "Lb1EEEv" in symbol
+
+
+def kernel_resources():
+    """{kernel symbol: resources} of every kernel of the last build (from the compile remarks)."""
+    res = {}
+    for f in sorted(os.listdir(OBJ_DIR)) if os.path.isdir(OBJ_DIR) else []:
+        if f.endswith(".o.res.json"):
+            with open(os.path.join(OBJ_DIR, f)) as fh:
+                res.update(json.load(fh))
+    return res
+
+
+def guarded_resources():
+    """{kernel symbol: resources} of every range-guarded float16 instantiation of the last build."""
+    return {k: v for k, v in kernel_resources().items() if _guarded_f16(k)}
+
+
+def guarded_spills():
+    """[(guarded symbol, its VGPR spills, its unguarded sibling's VGPR spills or None)] of the guarded instances that spill VGPRs."""
+    res = kernel_resources()
+    out = []
+    for k, v in sorted(res.items()):
+        if _guarded_f16(k) and v.get("vgpr_spill", 0):
+            sib = res.get(k.replace("Lb1EEEv", "Lb0EEEv"))
+            out.append((k, v["vgpr_spill"], sib.get("vgpr_spill", 0) if sib is not None else None))
+    return out
+
+
 def _compile(src):
     obj = os.path.join(OBJ_DIR, os.path.basename(src)[:-4] + ".o")
     extra = [] if os.path.basename(src) in AGPR_FILES else VGPR_FORM
-    flags = CFLAGS + extra + os.environ.get("OKP_EXTRA_CFLAGS", "").split()
+    flags = CFLAGS + extra + RESOURCE_REMARKS + os.environ.get("OKP_EXTRA_CFLAGS", "").split()
     stamp = obj + ".flags"                      # an object built with other flags (experiment switches) is stale
     same_flags = os.path.exists(stamp) and open(stamp).read() == " ".join(flags)
     if not same_flags or _stale(obj, [src] + _deps()):
@@ -56,7 +125,9 @@ def _compile(src):
             raise RuntimeError(f"hipcc failed for {src}:\n{r.stdout}\n{r.stderr}")
         with open(stamp, "w") as f:
             f.write(" ".join(flags))
-        return obj, True, r.stderr
+        with open(obj + ".res.json", "w") as f:
+            json.dump(_parse_resources(r.stderr), f)
+        return obj, True, _without_remarks(r.stderr)
     return obj, False, ""
 
 
@@ -93,7 +164,7 @@ def build(force=False, verbose=False):
     objs = [o for o, _, _ in results]
     rebuilt = any(r for _, r, _ in results)
     for f in os.listdir(OBJ_DIR):                 # objects (and flag stamps) of sources that no longer exist
-        if f.endswith((".o", ".o.flags")) and os.path.join(OBJ_DIR, f.split(".o")[0] + ".o") not in objs:
+        if f.endswith((".o", ".o.flags", ".o.res.json")) and os.path.join(OBJ_DIR, f.split(".o")[0] + ".o") not in objs:
             os.remove(os.path.join(OBJ_DIR, f))
     if verbose:
         for _, _, err in results:
@@ -104,6 +175,17 @@ def build(force=False, verbose=False):
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:
             raise RuntimeError(f"link failed:\n{r.stdout}\n{r.stderr}")
+    guarded = guarded_resources()
+    # (VGPR spills go to scratch memory; SGPR spills land in VGPR lanes, as in the unguarded instances.)  A guarded instance whose
+    # unguarded sibling does not spill is a regression of this build; one whose sibling already spills (the 32x32 A/B tiles, the stem) is listed
+    spills = guarded_spills()
+    new = [f"{k} ({n})" for k, n, sib in spills if not sib]
+    if new:
+        print("warning: range-guarded float16 instantiations that spill VGPRs where the unguarded one does not: " + ", ".join(new), file=sys.stderr)
+    if verbose and guarded:
+        old = ", ".join(f"{k} ({n}; unguarded {sib})" for k, n, sib in spills if sib)
+        print(f"range-guarded float16 instantiations: {len(guarded)}, {len(new)} spilling where the unguarded sibling does not"
+              + (f"; spilling as their unguarded siblings do: {old}" if old else ""), file=sys.stderr)
     try:
         build_torch_ops(verbose)
     except Exception as e:        # the dispatcher shim is optional: the ctypes binding serves every launch without it

@@ -376,7 +376,7 @@ static okp_conv* conv_create(int dtype, int n_src, const int32_t* cin, const int
 }
 
 extern "C" int okp_conv_set_range_flag(okp_conv* plan, int32_t* flag_dev) {
-  if (!plan || plan->dtype != OKP_F32X3) { okp_set_error("okp_conv_set_range_flag: a split-product (OKP_F32X3) plan"); return OKP_EINVAL; }
+  if (!plan || (plan->dtype != OKP_F32X3 && plan->dtype != OKP_F16)) { okp_set_error("okp_conv_set_range_flag: a split-product (OKP_F32X3) or float16 (OKP_F16) plan"); return OKP_EINVAL; }
   plan->range_flag = flag_dev;
   return OKP_OK;
 }

@@ -36,10 +36,14 @@
 // x requests of every tile but a workgroup's first, OKP_F2_ABL_NOSKIP the skip values, OKP_F2_ABL_NODW the depth-wise branch's MFMAs and reads,
 // OKP_F2_ABL_NOWEIGHTS the weight stream.
 #ifdef OKP_F2_ABL_NOSTORE
-#define F2_STORE(v, rs, off) do { if ((off) == 0x7ffffff0u) __builtin_amdgcn_raw_buffer_store_b128(v, rs, (int)(off), 0, 0); } while (0)
+#define F2_STORE_(v, rs, off) do { if ((off) == 0x7ffffff0u) __builtin_amdgcn_raw_buffer_store_b128(v, rs, (int)(off), 0, 0); } while (0)
 #else
-#define F2_STORE(v, rs, off) __builtin_amdgcn_raw_buffer_store_b128(v, rs, (int)(off), 0, 0)
+#define F2_STORE_(v, rs, off) __builtin_amdgcn_raw_buffer_store_b128(v, rs, (int)(off), 0, 0)
 #endif
+// every output store; the range-guarded instances (G) fold what they store into range_h (pixels outside the map - offset kInvalid - are not stored)
+#define F2_STORE(v, rs, off) do { \
+    if constexpr (G) { if ((uint32_t)(off) < kInvalid) range_h = okp_range_max_h8(range_h, v); } \
+    F2_STORE_(v, rs, off); } while (0)
 
 
 namespace {
@@ -138,9 +142,11 @@ __device__ __forceinline__ void wait_vm(int n) {   // s_waitcnt vmcnt(n) for a w
 // out as the expand GEMM's do: eight adjacent channels of a pixel per lane, one 16-byte store).  The tap weights are rounded to the
 // activation type T on this path (the VALU path multiplies by fp32 weights): one more rounding point of the 16-bit configurations, inside
 // their bounds (tests/precision/bounds.py); the products are exact in the fp32 accumulators either way.
-template <typename T, int CIN, int MID, int STR, bool DWM = false>
+// G: the range-guarded fp16 instantiation (okp_internal.h: OKP_F16 range guard) - the squeeze tile and both outputs are checked to be finite
+template <typename T, int CIN, int MID, int STR, bool DWM = false, bool G = false>
 __global__ __launch_bounds__(MID * 2, MID == 128 ? 2 : 1) void okp_fire2_kernel(const OkpFire2Params p) {
   static_assert(STR == 1 || STR == 2, "stride of both branches");
+  static_assert(!G || std::is_same<T, _Float16>::value, "the 16-bit storage guard is an fp16 instantiation");
   // DWM at stride 2 (round 6, last): tiles of 3 x 8 OUTPUT pixels, pixel block = 2 rows x 8 columns (lane l16 -> row 2 pb + (l16 >> 3), column
   // l16 & 7; the fourth row does not exist), squeeze tile 7 x 17.  Nothing in the matrix-pipe form needs the 16 pixels of a fragment to be a row:
   // every lane reads its own 16-byte chunk at its own address.  Nine taps x two blocks: 18 fragment reads, 36 MFMAs - where the vector-ALU form
@@ -391,6 +397,7 @@ __global__ __launch_bounds__(MID * 2, MID == 128 ? 2 : 1) void okp_fire2_kernel(
   __syncthreads();
   F2_STAMP_ANY(6);
 
+  uint32_t range_h = 0u;                           // G: largest |fp16| bits this thread stored, over all its tiles (okp_range_max_h2)
   for (; tile < p.n_tiles; tile += gridDim.x) {
     int n, y0, x0;
     tile_origin(tile, n, y0, x0);
@@ -557,6 +564,7 @@ __global__ __launch_bounds__(MID * 2, MID == 128 ? 2 : 1) void okp_fire2_kernel(
           v[2 * b] = ok ? p0 : 0u;
           v[2 * b + 1] = ok ? p1 : 0u;
         }
+        if constexpr (G) range_h = okp_range_max_h8(range_h, v);       // the squeeze tile: phase 2 reads it from LDS
         *reinterpret_cast<u32x4*>(smem + s_dst + pb * 16 * (MID * 2)) = v;
       }
     }
@@ -952,6 +960,7 @@ __global__ __launch_bounds__(MID * 2, MID == 128 ? 2 : 1) void okp_fire2_kernel(
     F2_STAMP(4);
     // no barrier here: phase 2 does not read what the next tile's phase 1 writes before its own barriers
   }
+  if constexpr (G) okp_raise_range_flag(p.range_flag, okp_range_exceeded_h2(range_h));
   F2_STAMP_ANY(7);
 }
 
@@ -969,7 +978,7 @@ bool okp_fire2_supported(int cin, int mid, int half, int stride) {
   return stride == 2 && ((cin == 256 && mid == 128) || (cin == 384 && mid == 192) || (cin == 384 && mid == 256) || (cin == 256 && mid == 192));
 }
 
-template <typename T>
+template <typename T, bool G = false>
 static int launch_fire2_t(OkpFire2Params p, int cin, int mid, int stride, hipStream_t stream) {
   // interior rectangle IH x IW: halo'd footprint <= 128 squeeze pixels, <= 96 interior pixels.  First the rounds of the persistent grid; then,
   // with several rounds, the fewest tiles (least halo), ties -> wider rows - and with ONE round the smallest tile, because the launch then takes one
@@ -1057,32 +1066,48 @@ static int launch_fire2_t(OkpFire2Params p, int cin, int mid, int stride, hipStr
     if (c2) printf("whole kernel: prologue (first requests + constants -> LDS + barrier) %.0f clocks, entry to exit %.0f clocks\n", pro / c2, all / c2);
   } } print_at_exit{p, mid, stream, dbg};
 #endif
-  if (stride == 1) {
-    if (dwm && cin == 256 && mid == 128) hipLaunchKernelGGL((okp_fire2_kernel<T, 256, 128, 1, true>), grid, block, 0, stream, p);
-    else if (dwm && cin == 384 && mid == 192) hipLaunchKernelGGL((okp_fire2_kernel<T, 384, 192, 1, true>), grid, block, 0, stream, p);
-    else if (dwm && cin == 512 && mid == 256) hipLaunchKernelGGL((okp_fire2_kernel<T, 512, 256, 1, true>), grid, block, 0, stream, p);
-    else if (dwm && cin == 384 && mid == 128) hipLaunchKernelGGL((okp_fire2_kernel<T, 384, 128, 1, true>), grid, block, 0, stream, p);
-    else if (dwm && cin == 512 && mid == 192) hipLaunchKernelGGL((okp_fire2_kernel<T, 512, 192, 1, true>), grid, block, 0, stream, p);
-    else if (cin == 256 && mid == 128) hipLaunchKernelGGL((okp_fire2_kernel<T, 256, 128, 1>), grid, block, 0, stream, p);
+  bool launched = true;
+  if (stride == 1 && dwm) {
+    if (cin == 256 && mid == 128) hipLaunchKernelGGL((okp_fire2_kernel<T, 256, 128, 1, true, G>), grid, block, 0, stream, p);
+    else if (cin == 384 && mid == 192) hipLaunchKernelGGL((okp_fire2_kernel<T, 384, 192, 1, true, G>), grid, block, 0, stream, p);
+    else if (cin == 512 && mid == 256) hipLaunchKernelGGL((okp_fire2_kernel<T, 512, 256, 1, true, G>), grid, block, 0, stream, p);
+    else if (cin == 384 && mid == 128) hipLaunchKernelGGL((okp_fire2_kernel<T, 384, 128, 1, true, G>), grid, block, 0, stream, p);
+    else if (cin == 512 && mid == 192) hipLaunchKernelGGL((okp_fire2_kernel<T, 512, 192, 1, true, G>), grid, block, 0, stream, p);
+    else launched = false;
+  } else if (stride == 2 && dwm2) {
+    if (cin == 256 && mid == 128) hipLaunchKernelGGL((okp_fire2_kernel<T, 256, 128, 2, true, G>), grid, block, 0, stream, p);
+    else if (cin == 384 && mid == 192) hipLaunchKernelGGL((okp_fire2_kernel<T, 384, 192, 2, true, G>), grid, block, 0, stream, p);
+    else if (cin == 384 && mid == 256) hipLaunchKernelGGL((okp_fire2_kernel<T, 384, 256, 2, true, G>), grid, block, 0, stream, p);
+    else if (cin == 256 && mid == 192) hipLaunchKernelGGL((okp_fire2_kernel<T, 256, 192, 2, true, G>), grid, block, 0, stream, p);
+    else launched = false;
+  } else if constexpr (G) {
+    // the vector-ALU forms (output maps whose width is not a multiple of 16 / 8 at stride 1 / 2, or OKP_F2_DWM=0) have no range-guarded
+    // instances: with the guard they spill (66-144 VGPRs).  A guarded pass runs such a module as the squeeze plan + fused tail
+    // (ops.fire_fusable(..., guarded=True) says which modules take this launch).
+    okp_set_error("okp_fire_forward: the range-guarded fp16 one-launch kernel takes output maps %d wide at stride %d only on its matrix-pipe form "
+                  "(width a multiple of %d); run the squeeze plan and the fused tail", p.Wo, stride, stride == 1 ? 16 : 8);
+    return OKP_EINVAL;
+  } else if (stride == 1) {
+    if (cin == 256 && mid == 128) hipLaunchKernelGGL((okp_fire2_kernel<T, 256, 128, 1>), grid, block, 0, stream, p);
     else if (cin == 384 && mid == 192) hipLaunchKernelGGL((okp_fire2_kernel<T, 384, 192, 1>), grid, block, 0, stream, p);
     else if (cin == 512 && mid == 256) hipLaunchKernelGGL((okp_fire2_kernel<T, 512, 256, 1>), grid, block, 0, stream, p);
     else if (cin == 384 && mid == 128) hipLaunchKernelGGL((okp_fire2_kernel<T, 384, 128, 1>), grid, block, 0, stream, p);
     else if (cin == 512 && mid == 192) hipLaunchKernelGGL((okp_fire2_kernel<T, 512, 192, 1>), grid, block, 0, stream, p);
-    else { okp_set_error("okp_fire_forward: no streaming kernel for %d -> %d", cin, mid); return OKP_EINVAL; }
-  } else if (dwm2 && cin == 256 && mid == 128) hipLaunchKernelGGL((okp_fire2_kernel<T, 256, 128, 2, true>), grid, block, 0, stream, p);
-  else if (dwm2 && cin == 384 && mid == 192) hipLaunchKernelGGL((okp_fire2_kernel<T, 384, 192, 2, true>), grid, block, 0, stream, p);
-  else if (dwm2 && cin == 384 && mid == 256) hipLaunchKernelGGL((okp_fire2_kernel<T, 384, 256, 2, true>), grid, block, 0, stream, p);
-  else if (dwm2 && cin == 256 && mid == 192) hipLaunchKernelGGL((okp_fire2_kernel<T, 256, 192, 2, true>), grid, block, 0, stream, p);
-  else if (cin == 256 && mid == 192) hipLaunchKernelGGL((okp_fire2_kernel<T, 256, 192, 2>), grid, block, 0, stream, p);
-  else if (cin == 256 && mid == 128) hipLaunchKernelGGL((okp_fire2_kernel<T, 256, 128, 2>), grid, block, 0, stream, p);
-  else if (cin == 384 && mid == 192) hipLaunchKernelGGL((okp_fire2_kernel<T, 384, 192, 2>), grid, block, 0, stream, p);
-  else if (cin == 384 && mid == 256) hipLaunchKernelGGL((okp_fire2_kernel<T, 384, 256, 2>), grid, block, 0, stream, p);
-  else { okp_set_error("okp_fire_forward: no streaming kernel for %d -> %d stride %d", cin, mid, stride); return OKP_EINVAL; }
+    else launched = false;
+  } else {
+    if (cin == 256 && mid == 192) hipLaunchKernelGGL((okp_fire2_kernel<T, 256, 192, 2>), grid, block, 0, stream, p);
+    else if (cin == 256 && mid == 128) hipLaunchKernelGGL((okp_fire2_kernel<T, 256, 128, 2>), grid, block, 0, stream, p);
+    else if (cin == 384 && mid == 192) hipLaunchKernelGGL((okp_fire2_kernel<T, 384, 192, 2>), grid, block, 0, stream, p);
+    else if (cin == 384 && mid == 256) hipLaunchKernelGGL((okp_fire2_kernel<T, 384, 256, 2>), grid, block, 0, stream, p);
+    else launched = false;
+  }
+  if (!launched) { okp_set_error("okp_fire_forward: no streaming kernel for %d -> %d stride %d", cin, mid, stride); return OKP_EINVAL; }
   return okp_check_hip(hipGetLastError(), "okp_fire2 launch");
 }
 
 int okp_launch_fire2(int dtype, const OkpFire2Params& p, int cin, int mid, int stride, hipStream_t stream) {
   if (dtype == OKP_BF16) return launch_fire2_t<__bf16>(p, cin, mid, stride, stream);
+  if (p.range_flag) return launch_fire2_t<_Float16, true>(p, cin, mid, stride, stream);       // the range-guarded instances
   return launch_fire2_t<_Float16>(p, cin, mid, stride, stream);
 }
 
@@ -1142,6 +1167,7 @@ extern "C" int okp_fire_forward(const okp_conv* squeeze, const okp_conv* expand,
     q.w1 = squeeze->fragT_dev; q.w1_cout_pad = squeeze->cout_pad; q.b1 = squeeze->bias_dev;
     q.wa = expand->fragT_dev; q.wa_cout_pad = expand->cout_pad; q.ba = expand->bias_dev;
     q.wd = dw_w_dev; q.bd = dw_bias_dev;
+    q.range_flag = squeeze->dtype == OKP_F16 ? squeeze->range_flag : nullptr;
     return okp_launch_fire2(squeeze->dtype, q, cin, mid, a->stride, (hipStream_t)stream);
   }
 }

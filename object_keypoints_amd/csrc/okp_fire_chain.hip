@@ -71,11 +71,17 @@ __device__ __forceinline__ uint32_t xoff(int row, int chunk, int rowbytes) { ret
 #define FC_STAMP(cond, i) do {} while (0)
 #endif
 
-template <typename T, int CIN, int PXB, bool EE>
+// G: the range-guarded fp16 instantiation (okp_internal.h: OKP_F16 range guard) - every module's squeeze tile and output, inside the chain as
+// well as at its end, is checked to be finite where it is written to LDS
+template <typename T, int CIN, int PXB, bool EE, bool G = false>
 __global__ __launch_bounds__((ChainCfg<CIN, PXB, EE>::NT)) void okp_fire_chain_kernel(const OkpFireChainParams p) {
   using C = ChainCfg<CIN, PXB, EE>;
   using x2_t = typename H16<T>::x2;
   using x8_t = typename H16<T>::x8;
+  static_assert(!G || std::is_same<T, _Float16>::value, "the 16-bit storage guard is an fp16 instantiation");
+  uint32_t range_h = 0u;                           // G: largest |fp16| bits this thread wrote (okp_range_max_h2)
+  auto guard2 = [&](const x2_t& v) { if constexpr (G) range_h = okp_range_max_h2(range_h, __builtin_bit_cast(uint32_t, v)); };
+  auto guard8 = [&](const x8_t& v) { if constexpr (G) range_h = okp_range_max_h8(range_h, __builtin_bit_cast(u32x4, v)); };
   constexpr int MID = C::MID, NT = C::NT, KS1 = C::KS1, KS2 = C::KS2, XROW = C::XROW, SROW = C::SROW, NPX = C::NPX;
   constexpr int XK = C::XKEY, SK = C::SKEY;
   // Weight fragments stream through ONE register ring of PF = KS2 k-steps that never drains: the last PF squeeze steps fetch the
@@ -210,6 +216,7 @@ __global__ __launch_bounds__((ChainCfg<CIN, PXB, EE>::NT)) void okp_fire_chain_k
           if (px < HWe) {
             x2_t v;
             v[0] = (T)acc0[pb][r]; v[1] = (T)acc1[pb][r];
+            guard2(v);
             const int py = px / p.We;
             const int row = (py + 1) * SWe + (px - py * p.We) + 1;
             *reinterpret_cast<x2_t*>(smem + C::OFF_S + xoff<SK>(row, (ch0 * 2) >> 4, SROW) + ((ch0 * 2) & 15)) = v;
@@ -242,6 +249,7 @@ __global__ __launch_bounds__((ChainCfg<CIN, PXB, EE>::NT)) void okp_fire_chain_k
         x2_t v;
         v[0] = (T)fmaxf(acc0[r], 0.f); v[1] = (T)fmaxf(acc1[r], 0.f);
         if (px >= HW) { v[0] = (T)0.f; v[1] = (T)0.f; }
+        guard2(v);
         *reinterpret_cast<x2_t*>(xn + xoff<XK>(px, (ch0 * 2) >> 4, XROW) + ((ch0 * 2) & 15)) = v;
       }
     }
@@ -266,6 +274,7 @@ __global__ __launch_bounds__((ChainCfg<CIN, PXB, EE>::NT)) void okp_fire_chain_k
       x8_t out;
 #pragma unroll
       for (int e = 0; e < 8; ++e) out[e] = (T)(dpx < HW ? fmaxf(v[e], 0.f) : 0.f);
+      guard8(out);
       *reinterpret_cast<x8_t*>(xn + xoff<XK>(dpx, (MID * 2) / 16 + cg, XROW)) = out;
     }
     __syncthreads();                                          // every reader of s8 is through
@@ -330,6 +339,7 @@ __global__ __launch_bounds__((ChainCfg<CIN, PXB, EE>::NT)) void okp_fire_chain_k
           if (px < HW) {
             x2_t v;
             v[0] = (T)acc0[pb][r]; v[1] = (T)acc1[pb][r];
+            guard2(v);
             const int row = srow(px);
             *reinterpret_cast<x2_t*>(smem + C::OFF_S + xoff<SK>(row, (ch0 * 2) >> 4, SROW) + ((ch0 * 2) & 15)) = v;
           }
@@ -377,6 +387,7 @@ __global__ __launch_bounds__((ChainCfg<CIN, PXB, EE>::NT)) void okp_fire_chain_k
           v[0] = (T)fmaxf(acc0[pb][r] + (float)xv[0], 0.f);
           v[1] = (T)fmaxf(acc1[pb][r] + (float)xv[1], 0.f);
           if (px >= HW) { v[0] = (T)0.f; v[1] = (T)0.f; }
+          guard2(v);
           *reinterpret_cast<x2_t*>(xn + o) = v;
         }
     }
@@ -425,6 +436,7 @@ __global__ __launch_bounds__((ChainCfg<CIN, PXB, EE>::NT)) void okp_fire_chain_k
         x8_t out;
 #pragma unroll
         for (int e = 0; e < 8; ++e) out[e] = (T)(dpx < HW ? fmaxf(v[i][e] + (float)xv[e], 0.f) : 0.f);
+        guard8(out);
         *reinterpret_cast<x8_t*>(xn + o) = out;
       }
     }
@@ -476,6 +488,7 @@ __global__ __launch_bounds__((ChainCfg<CIN, PXB, EE>::NT)) void okp_fire_chain_k
         if (px < HW) {
           x2_t v;
           v[0] = (T)acc0[r]; v[1] = (T)acc1[r];
+          guard2(v);
           *reinterpret_cast<x2_t*>(smem + C::OFF_S + xoff<SK>(srow(px), (ch0 * 2) >> 4, SROW) + ((ch0 * 2) & 15)) = v;
         }
       }
@@ -496,6 +509,7 @@ __global__ __launch_bounds__((ChainCfg<CIN, PXB, EE>::NT)) void okp_fire_chain_k
         const int px = 4 * q + r;
         x2_t v;
         v[0] = (T)fmaxf(acc0[r], 0.f); v[1] = (T)fmaxf(acc1[r], 0.f);
+        guard2(v);
         *reinterpret_cast<x2_t*>(xn + xoff<XK>(px, (ch0 * 2) >> 4, XROW) + ((ch0 * 2) & 15)) = v;
       }
     }
@@ -520,6 +534,7 @@ __global__ __launch_bounds__((ChainCfg<CIN, PXB, EE>::NT)) void okp_fire_chain_k
       x8_t out;
 #pragma unroll
       for (int e = 0; e < 8; ++e) out[e] = (T)fmaxf(v[e], 0.f);
+      guard8(out);
       *reinterpret_cast<x8_t*>(xn + xoff<XK>(dpx, (XMID * 2) / 16 + cg, XROW)) = out;
     }
     __syncthreads();
@@ -536,6 +551,7 @@ __global__ __launch_bounds__((ChainCfg<CIN, PXB, EE>::NT)) void okp_fire_chain_k
       *reinterpret_cast<u32x4*>(dst + (size_t)px * p.out_ps * 2 + c * 16) = *reinterpret_cast<const u32x4*>(xc + xoff<XK>(px, c, XROW));
     }
   }
+  if constexpr (G) okp_raise_range_flag(p.range_flag, okp_range_exceeded_h2(range_h));
 }
 
 }  // namespace
@@ -609,6 +625,7 @@ extern "C" int okp_fire_chain_forward(int32_t n_modules, okp_conv* const* squeez
     p.mod[m].wd = dw_w_dev[m]; p.mod[m].bd = dw_bias_dev[m];
   }
   const bool bf = squeeze[0]->dtype == OKP_BF16;
+  p.range_flag = squeeze[0]->dtype == OKP_F16 ? squeeze[0]->range_flag : nullptr;      // (a guarded pass gives every plan the same flag)
   if (ee) {
     const int ho = (x->h - 1) / 2 + 1, wo = (x->w - 1) / 2 + 1;
     if (cin != 512 || x->h < 1 || x->w < 1 || x->h > 8 || x->w > 8 || out->h != ho || out->w != wo) {
@@ -625,6 +642,7 @@ extern "C" int okp_fire_chain_forward(int32_t n_modules, okp_conv* const* squeez
     }
     p.n_modules = n_modules; p.x = x->data; p.out = out->data; p.x_ps = x->pix_stride; p.out_ps = out->pix_stride; p.H = ho; p.W = wo; p.He = x->h; p.We = x->w;
     if (bf) hipLaunchKernelGGL((okp_fire_chain_kernel<__bf16, 512, 1, true>), dim3(n), dim3(ChainCfg<512, 1, true>::NT), 0, (hipStream_t)stream, p);
+    else if (p.range_flag) hipLaunchKernelGGL((okp_fire_chain_kernel<_Float16, 512, 1, true, true>), dim3(n), dim3(ChainCfg<512, 1, true>::NT), 0, (hipStream_t)stream, p);
     else hipLaunchKernelGGL((okp_fire_chain_kernel<_Float16, 512, 1, true>), dim3(n), dim3(ChainCfg<512, 1, true>::NT), 0, (hipStream_t)stream, p);
     CHAIN_STAMPS_PRINT("512-wide entry / exit form", 8);
     return okp_check_hip(hipGetLastError(), "okp_fire_chain launch");
@@ -645,12 +663,15 @@ extern "C" int okp_fire_chain_forward(int32_t n_modules, okp_conv* const* squeez
   p.n_modules = n_modules; p.x = x->data; p.out = out->data; p.x_ps = x->pix_stride; p.out_ps = out->pix_stride; p.H = x->h; p.W = x->w;
   if (cin == 512) {
     if (bf) hipLaunchKernelGGL((okp_fire_chain_kernel<__bf16, 512, 1, false>), dim3(n), dim3(ChainCfg<512, 1>::NT), 0, (hipStream_t)stream, p);
+    else if (p.range_flag) hipLaunchKernelGGL((okp_fire_chain_kernel<_Float16, 512, 1, false, true>), dim3(n), dim3(ChainCfg<512, 1>::NT), 0, (hipStream_t)stream, p);
     else hipLaunchKernelGGL((okp_fire_chain_kernel<_Float16, 512, 1, false>), dim3(n), dim3(ChainCfg<512, 1>::NT), 0, (hipStream_t)stream, p);
   } else if (small) {
     if (bf) hipLaunchKernelGGL((okp_fire_chain_kernel<__bf16, 384, 1, false>), dim3(n), dim3(ChainCfg<384, 1>::NT), 0, (hipStream_t)stream, p);
+    else if (p.range_flag) hipLaunchKernelGGL((okp_fire_chain_kernel<_Float16, 384, 1, false, true>), dim3(n), dim3(ChainCfg<384, 1>::NT), 0, (hipStream_t)stream, p);
     else hipLaunchKernelGGL((okp_fire_chain_kernel<_Float16, 384, 1, false>), dim3(n), dim3(ChainCfg<384, 1>::NT), 0, (hipStream_t)stream, p);
   } else {
     if (bf) hipLaunchKernelGGL((okp_fire_chain_kernel<__bf16, 384, 4, false>), dim3(n), dim3(ChainCfg<384, 4>::NT), 0, (hipStream_t)stream, p);
+    else if (p.range_flag) hipLaunchKernelGGL((okp_fire_chain_kernel<_Float16, 384, 4, false, true>), dim3(n), dim3(ChainCfg<384, 4>::NT), 0, (hipStream_t)stream, p);
     else hipLaunchKernelGGL((okp_fire_chain_kernel<_Float16, 384, 4, false>), dim3(n), dim3(ChainCfg<384, 4>::NT), 0, (hipStream_t)stream, p);
   }
   CHAIN_STAMPS_PRINT(cin == 512 ? "512-wide" : "384-wide", cin / 64);

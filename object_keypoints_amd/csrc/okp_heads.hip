@@ -49,11 +49,18 @@ struct HeadsParams {
   int64_t out_n_stride[OKP_HEAD_MAX_OUT];
   int32_t n_tiles;
 };
+struct HeadsParamsG : HeadsParams {       // the range-guarded instance's parameters (the unguarded instances keep their kernel arguments as they were)
+  int32_t* range_flag;                    // plan l1's range flag (okp_conv_set_range_flag)
+};
 
 __device__ __forceinline__ uint32_t xoff(int row, int chunk, int rowbytes) { return (uint32_t)row * rowbytes + (uint32_t)((chunk ^ (row & 15)) << 4); }
 
-template <typename T>
-__global__ __launch_bounds__(256, 2) void okp_heads_kernel(const HeadsParams p) {
+// G: the range-guarded fp16 instantiation (okp_internal.h: OKP_F16 range guard) - both hidden layers, handed on in fp16 through LDS and
+// rounded to fp16 for the last layer, are checked to be finite
+template <typename T, bool G = false>
+__global__ __launch_bounds__(256, 2) void okp_heads_kernel(const typename std::conditional<G, HeadsParamsG, HeadsParams>::type p) {
+  static_assert(!G || std::is_same<T, _Float16>::value, "the 16-bit storage guard is an fp16 instantiation");
+  uint32_t range_h = 0u;                  // G: largest |fp16| bits of the hidden values this thread wrote (okp_range_max_h2)
   __shared__ __attribute__((aligned(16))) char smem[LDS_BYTES];
   const int tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -131,6 +138,7 @@ __global__ __launch_bounds__(256, 2) void okp_heads_kernel(const HeadsParams p) 
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             const uint32_t v = okp_pack2<T>(fmaxf(acc[pb][0][r], 0.f), fmaxf(acc[pb][1][r], 0.f));
+            if constexpr (G) range_h = okp_range_max_h2(range_h, v);
             const int px = 16 * pb + 4 * q + r;
             *reinterpret_cast<uint32_t*>(smem + OFF_H1 + xoff(px, (ch0 * 2) >> 4, F * 2) + ((ch0 * 2) & 15)) = v;
           }
@@ -153,6 +161,7 @@ __global__ __launch_bounds__(256, 2) void okp_heads_kernel(const HeadsParams p) 
           // rounded to bf16 like the stored activation of the unfused path, kept as fp32 for the dot products
           h2[px * H2_PITCH + 2 * l16] = (float)(T)fmaxf(acc0[r], 0.f);
           h2[px * H2_PITCH + 2 * l16 + 1] = (float)(T)fmaxf(acc1[r], 0.f);
+          if constexpr (G) range_h = okp_range_max_h2(range_h, okp_pack2<T>(fmaxf(acc0[r], 0.f), fmaxf(acc1[r], 0.f)));
         }
       }
       __syncthreads();
@@ -177,6 +186,7 @@ __global__ __launch_bounds__(256, 2) void okp_heads_kernel(const HeadsParams p) 
       }
     }
   }
+  if constexpr (G) okp_raise_range_flag(p.range_flag, okp_range_exceeded_h2(range_h));
 }
 
 // ---- the same three heads for split-product plans (OKP_F32X3): fp32 tensors, every product as x_hi w_hi + x_lo w_hi + x_hi w_lo on the
@@ -433,6 +443,12 @@ extern "C" int okp_heads_forward(const okp_conv* l1, const okp_conv* l2, const o
   p.n_tiles = (int)tiles;
   const long groups = tiles < 168 ? tiles : 168;            // 3 x 168 = 504 = 24 x 21 workgroups: two per CU, whole head triples per XCD
   if (l1->dtype == OKP_BF16) hipLaunchKernelGGL(okp_heads_kernel<__bf16>, dim3((unsigned)(3 * groups)), dim3(256), 0, (hipStream_t)stream, p);
+  else if (l1->range_flag) {
+    HeadsParamsG pg;
+    static_cast<HeadsParams&>(pg) = p;
+    pg.range_flag = l1->range_flag;
+    hipLaunchKernelGGL((okp_heads_kernel<_Float16, true>), dim3((unsigned)(3 * groups)), dim3(256), 0, (hipStream_t)stream, pg);
+  }
   else hipLaunchKernelGGL(okp_heads_kernel<_Float16>, dim3((unsigned)(3 * groups)), dim3(256), 0, (hipStream_t)stream, p);
   return okp_check_hip(hipGetLastError(), "okp_heads launch");
 }

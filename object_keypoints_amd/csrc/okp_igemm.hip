@@ -3,15 +3,15 @@
 
 namespace {
 
-template <typename T>
+template <typename T, bool G = false>      // G: the range-guarded fp16 instances (an OKP_F16 plan with a range flag)
 int launch_tile(const okp_conv* plan, const OkpIgemmParams& p, int tile, hipStream_t stream) {
   switch (tile) {
-    case 8: return launch_cfg<T, 64, 64, 2, 2, 4, 128, 16>(plan, p, stream);   // 64x64 on 16x16 MFMA tiles
-    case 6: return launch_cfg<T, 256, 256, 4, 2, 2, 128, 16>(plan, p, stream); // 256x256 on 16x16 MFMA tiles
-    case 4: return launch_cfg<T, 128, 256, 2, 2, 3, 64>(plan, p, stream);     // 2 workgroups per CU, half-slice ring
-    case 3: return launch_cfg<T, 256, 256, 4, 2, 2, 128>(plan, p, stream);
-    case 2: return launch_cfg<T, 128, 128, 2, 2, 2, 128>(plan, p, stream);
-    default: return launch_cfg<T, 64, 64, 2, 2, 4, 128>(plan, p, stream);
+    case 8: return launch_cfg<T, 64, 64, 2, 2, 4, 128, 16, G>(plan, p, stream);   // 64x64 on 16x16 MFMA tiles
+    case 6: return launch_cfg<T, 256, 256, 4, 2, 2, 128, 16, G>(plan, p, stream); // 256x256 on 16x16 MFMA tiles
+    case 4: return launch_cfg<T, 128, 256, 2, 2, 3, 64, 32, G>(plan, p, stream);     // 2 workgroups per CU, half-slice ring
+    case 3: return launch_cfg<T, 256, 256, 4, 2, 2, 128, 32, G>(plan, p, stream);
+    case 2: return launch_cfg<T, 128, 128, 2, 2, 2, 128, 32, G>(plan, p, stream);
+    default: return launch_cfg<T, 64, 64, 2, 2, 4, 128, 32, G>(plan, p, stream);
   }
 }
 
@@ -47,7 +47,7 @@ int okp_launch_igemm(const okp_conv* plan, const OkpIgemmParams& p, int tile, hi
   }
   if (tile == 0) tile = okp_select_tile(plan->dtype, p.cout_pad, (long)p.N * p.Ho * p.Wo);
   if (plan->dtype == OKP_BF16) return launch_tile<__bf16>(plan, p, tile, stream);
-  if (plan->dtype == OKP_F16) return launch_tile<_Float16>(plan, p, tile, stream);
+  if (plan->dtype == OKP_F16) return p.range_flag ? launch_tile<_Float16, true>(plan, p, tile, stream) : launch_tile<_Float16>(plan, p, tile, stream);
   if (plan->dtype == OKP_F32X3) return launch_tile_x3(plan, p, tile, stream);
   return launch_tile<float>(plan, p, tile, stream);
 }

@@ -185,7 +185,8 @@ struct SliceMeta {            // per-slice gather constants, built once per work
 constexpr int kMetaMax = 256;
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
 
-template <typename T, int BCO, int BPX, int WCO, int WPX, int NS, int KB, int MT, int NSRC>
+// RG: the range-guarded fp16 instantiation (okp_internal.h: OKP_F16 range guard) - every value written in fp16 is checked to be finite
+template <typename T, int BCO, int BPX, int WCO, int WPX, int NS, int KB, int MT, int NSRC, bool RG>
 __global__ __launch_bounds__(64 * WCO * WPX, (std::is_same<T, F32S>::value ? 2 : 1)) void okp_igemm_kernel(const OkpIgemmParams p) {     // split-product tiles: two waves per SIMD (<= 256 registers)
   constexpr int NT = 64 * WCO * WPX;
   constexpr int ESZ = (int)sizeof(T);
@@ -218,6 +219,7 @@ __global__ __launch_bounds__(64 * WCO * WPX, (std::is_same<T, F32S>::value ? 2 :
 
   // ONE LDS object (a second __shared__ array makes hipcc drain LDS-DMA before unrelated ds_reads)
   constexpr bool X3 = std::is_same<T, F32S>::value;      // split-product plans (OKP_F32X3): see struct F32S
+  static_assert(!RG || std::is_same<T, _Float16>::value, "the 16-bit storage guard is an fp16 instantiation");
   __shared__ __attribute__((aligned(16))) char smem[LDS_BYTES + kMetaMax * (int)sizeof(SliceMeta) + (X3 ? 2048 : 1024)];
   SliceMeta* const meta = reinterpret_cast<SliceMeta*>(smem + LDS_BYTES);
   char* const bias_lds = smem + LDS_BYTES + kMetaMax * (int)sizeof(SliceMeta);     // this tile's BCO biases (fp32); X3: + BCO output scales
@@ -622,6 +624,7 @@ __global__ __launch_bounds__(64 * WCO * WPX, (std::is_same<T, F32S>::value ? 2 :
     constexpr int UH = U >= 16 ? U / 4 : (U >= 8 ? U / 2 : U);
     float range_m = 0.f;                           // split-product plans: largest |result| of this pass (okp_range_max); local to the epilogue, so that
                                                    // nothing of the guard is live across the K loop
+    uint32_t range_h = 0u;                         // RG: largest |fp16| bits of the packed words this pass stores (okp_range_max_h2)
 #pragma unroll 1
     for (int ub = 0; ub < U; ub += UH) {
     u32x4 rres[UH][CH8];
@@ -700,6 +703,7 @@ __global__ __launch_bounds__(64 * WCO * WPX, (std::is_same<T, F32S>::value ? 2 :
               const s16x8 z = {0, 0, 0, 0, 0, 0, 0, 0};
               w = __builtin_bit_cast(u32x4, __builtin_elementwise_max(__builtin_bit_cast(s16x8, w), z));
             }
+            if constexpr (RG) range_h = okp_range_max_h8(range_h, w);
             *reinterpret_cast<u32x4*>(op) = w;
           } else {
             float v[8];
@@ -731,7 +735,7 @@ __global__ __launch_bounds__(64 * WCO * WPX, (std::is_same<T, F32S>::value ? 2 :
 #pragma unroll
               for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], 0.f);
             }
-            if constexpr (X3) {
+            if constexpr (X3 || RG) {
 #pragma unroll
               for (int e = 0; e < 8; ++e) range_m = okp_range_max(range_m, v[e]);
             }
@@ -750,6 +754,7 @@ __global__ __launch_bounds__(64 * WCO * WPX, (std::is_same<T, F32S>::value ? 2 :
     }
     }  // ub
     if constexpr (X3) okp_raise_range_flag(p.range_flag, okp_range_exceeded(range_m));
+    if constexpr (RG) okp_raise_range_flag(p.range_flag, okp_range_exceeded(range_m) || okp_range_exceeded_h2(range_h));
     __syncthreads();       // staging is free again (next pass, or the next tile's LDS-DMA)
   }
   }
@@ -807,7 +812,7 @@ __global__ __launch_bounds__(64 * WCO * WPX, (std::is_same<T, F32S>::value ? 2 :
 #pragma unroll
           for (int e = 0; e < VN; ++e) v[e] = fmaxf(v[e], 0.f);
         }
-        if constexpr (X3) {
+        if constexpr (X3 || RG) {
 #pragma unroll
           for (int e = 0; e < VN; ++e) dw_range_m = okp_range_max(dw_range_m, v[e]);
         }
@@ -880,12 +885,12 @@ __global__ __launch_bounds__(64 * WCO * WPX, (std::is_same<T, F32S>::value ? 2 :
         }
       }
     }
-    if constexpr (X3) okp_raise_range_flag(p.range_flag, okp_range_exceeded(dw_range_m));
+    if constexpr (X3 || RG) okp_raise_range_flag(p.range_flag, okp_range_exceeded(dw_range_m));
   }
   }  // tile loop
 }
 
-template <typename T, int BCO, int BPX, int WCO, int WPX, int NS, int KB, int MT = 32>
+template <typename T, int BCO, int BPX, int WCO, int WPX, int NS, int KB, int MT = 32, bool G = false>
 int launch_cfg(const okp_conv* plan, OkpIgemmParams p, hipStream_t stream) {
   const int P = p.N * p.Ho * p.Wo;
   p.n_co_tiles = (p.cout_pad + BCO - 1) / BCO;
@@ -898,9 +903,9 @@ int launch_cfg(const okp_conv* plan, OkpIgemmParams p, hipStream_t stream) {
   const dim3 grid((unsigned)(p.n_tiles < resident ? p.n_tiles : resident));
   const dim3 block(64 * WCO * WPX);
   if (plan->n_src == 1)
-    hipLaunchKernelGGL((okp_igemm_kernel<T, BCO, BPX, WCO, WPX, NS, KB, MT, 1>), grid, block, 0, stream, p);
+    hipLaunchKernelGGL((okp_igemm_kernel<T, BCO, BPX, WCO, WPX, NS, KB, MT, 1, G>), grid, block, 0, stream, p);
   else
-    hipLaunchKernelGGL((okp_igemm_kernel<T, BCO, BPX, WCO, WPX, NS, KB, MT, 2>), grid, block, 0, stream, p);
+    hipLaunchKernelGGL((okp_igemm_kernel<T, BCO, BPX, WCO, WPX, NS, KB, MT, 2, G>), grid, block, 0, stream, p);
   return okp_check_hip(hipGetLastError(), "okp_igemm launch");
 }
 

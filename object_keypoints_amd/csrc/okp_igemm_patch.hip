@@ -75,8 +75,10 @@ static_assert(sizeof(OkpPatchStep) == 16, "step table entries are read as one 16
 static_assert(256 * 512 <= kLdsSteps, "epilogue staging (256 px x 256 ch bf16) must not reach the step table");
 static_assert(kLdsTotal <= 160 * 1024, "one workgroup's LDS is at most the CU's 160 KiB");
 
-template <typename T, int MT = 16>
+// RG: the range-guarded fp16 instantiation (okp_internal.h: OKP_F16 range guard) - every value written in fp16 is checked to be finite
+template <typename T, int MT = 16, bool RG = false>
 __global__ __launch_bounds__(512) void okp_igemm_patch_kernel(const OkpPatchParams p) {
+  static_assert(!RG || std::is_same<T, _Float16>::value, "the 16-bit storage guard is an fp16 instantiation");
   using x4_t = typename H16<T>::x4;
   using x8_t = typename H16<T>::x8;
   static_assert(MT == 16 || MT == 32, "MFMA tile");
@@ -367,6 +369,7 @@ __global__ __launch_bounds__(512) void okp_igemm_patch_kernel(const OkpPatchPara
     constexpr int U = 256 * 32 / 512;              // 16-byte items (8 channels of one pixel) per thread
     constexpr int UH = 8;                          // residual vectors in flight together (4: -1 %, 16: spills, +12 %)
     const bool relu = p.act == OKP_ACT_RELU;
+    uint32_t range_h = 0u;                         // RG: largest |fp16| bits of what this tile stores (okp_range_max_h2; local to the epilogue)
 #pragma unroll 1
     for (int ub = 0; ub < U; ub += UH) {
       u32x4 rres[UH];
@@ -401,6 +404,7 @@ __global__ __launch_bounds__(512) void okp_igemm_patch_kernel(const OkpPatchPara
             const s16x8 z = {0, 0, 0, 0, 0, 0, 0, 0};
             w = __builtin_bit_cast(u32x4, __builtin_elementwise_max(__builtin_bit_cast(s16x8, w), z));
           }
+          if constexpr (RG) range_h = okp_range_max_h8(range_h, w);
           *reinterpret_cast<u32x4*>(op) = w;
         } else {
           const x8_t s8 = __builtin_bit_cast(x8_t, w), r8 = __builtin_bit_cast(x8_t, rres[u]);
@@ -411,10 +415,12 @@ __global__ __launch_bounds__(512) void okp_igemm_patch_kernel(const OkpPatchPara
             if (relu) v = fmaxf(v, 0.f);
             o[e] = (T)v;
           }
+          if constexpr (RG) range_h = okp_range_max_h8(range_h, __builtin_bit_cast(u32x4, o));
           *reinterpret_cast<x8_t*>(op) = o;
         }
       }
     }
+    if constexpr (RG) okp_raise_range_flag(p.range_flag, okp_range_exceeded_h2(range_h));
     __syncthreads();                               // staging is free again: the next tile's LDS-DMA may overwrite it
   }
 }
@@ -493,8 +499,10 @@ int okp_launch_igemm_patch(const okp_conv* plan, const OkpIgemmParams& q, hipStr
   const dim3 grid((unsigned)(p.n_tiles < 256 ? p.n_tiles : 256)), block(512);
   if (q.mfma32) {         // tile 14: the 32x32x16 instantiation (same wave tile; kept for the MFMA-shape A/B, never the heuristic's choice)
     if (plan->dtype == OKP_BF16) hipLaunchKernelGGL((okp_igemm_patch_kernel<__bf16, 32>), grid, block, 0, stream, p);
+    else if (p.range_flag) hipLaunchKernelGGL((okp_igemm_patch_kernel<_Float16, 32, true>), grid, block, 0, stream, p);
     else hipLaunchKernelGGL((okp_igemm_patch_kernel<_Float16, 32>), grid, block, 0, stream, p);
   } else if (plan->dtype == OKP_BF16) hipLaunchKernelGGL((okp_igemm_patch_kernel<__bf16, 16>), grid, block, 0, stream, p);
+  else if (p.range_flag) hipLaunchKernelGGL((okp_igemm_patch_kernel<_Float16, 16, true>), grid, block, 0, stream, p);     // the range-guarded instance
   else hipLaunchKernelGGL((okp_igemm_patch_kernel<_Float16, 16>), grid, block, 0, stream, p);
 #ifdef OKP_PATCH_STAMPS
   if (getenv("OKP_PATCH_STAMPS_PRINT")) {

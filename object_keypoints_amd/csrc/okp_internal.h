@@ -102,6 +102,28 @@ static __device__ __forceinline__ bool okp_unsplittable(float v) { return !(__bu
 static __device__ __forceinline__ float okp_range_max(float m, float v) { return __builtin_fmaxf(m, __builtin_fabsf(v)); }
 #endif
 static __device__ __forceinline__ bool okp_range_exceeded(float m) { return !(m <= 65504.f); }
+
+// OKP_F16 range guard (the `bool G` instantiations of the 16-bit kernels, chosen where an OKP_F16 plan has a flag): every value a float16
+// kernel hands on in fp16 - to HBM, or to a later phase / module through LDS - must be finite.  fp16 rounds a result beyond 65504 to inf; the
+// next layer's sums with mixed-sign weights make NaN of it and the next ReLU (fmaxf) makes 0 of the NaN: the silent failure of the split
+// products, one type earlier.  With every stored operand finite a layer's fp32 sums are finite, so the induction above holds as it is.  Where a
+// kernel stores packed fp16 words it folds them into a running maximum of their magnitude BITS (okp_range_max_h2: one v_and + one
+// v_pk_max_u16 per dword): |h| >= 0x7c00 is inf or NaN, exact.  Where it still holds the fp32 value it uses okp_range_max (|v| <= 65504).
+// The unguarded fp16 and all bf16 instantiations compile none of it (if constexpr).
+typedef unsigned short okp_u16x2 __attribute__((ext_vector_type(2)));
+#ifdef OKP_NO_RANGE_GUARD
+static __device__ __forceinline__ uint32_t okp_range_max_h2(uint32_t m, uint32_t) { return m; }
+#else
+static __device__ __forceinline__ uint32_t okp_range_max_h2(uint32_t m, uint32_t w) {
+  return __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(okp_u16x2, m), __builtin_bit_cast(okp_u16x2, w & 0x7fff7fffu)));
+}
+#endif
+static __device__ __forceinline__ uint32_t okp_range_max_h8(uint32_t m, const u32x4& w) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) m = okp_range_max_h2(m, w[i]);
+  return m;
+}
+static __device__ __forceinline__ bool okp_range_exceeded_h2(uint32_t m) { return (m & 0xffffu) >= 0x7c00u || (m >> 16) >= 0x7c00u; }
 static __device__ __forceinline__ void okp_raise_range_flag(int32_t* flag, bool bad) {
 #if defined(__HIP_DEVICE_COMPILE__)
   if (flag != nullptr && bad) atomicOr(flag, 1);     // (no lane takes this branch in a healthy launch)
@@ -179,7 +201,7 @@ struct OkpIgemmParams {
   int32_t src_pairs, out_pairs;      // OKP_F32X3 on the patch-resident kernel: sources (bit s) / output in pair format (okp_conv_args.src_pairs / out_pairs)
   int32_t out_sub2, OH2, OW2;        // OKP_F32X3: the fp32 output keeps even rows / columns only (tensor of OH2 x OW2 pixels); out16 is full size
   int32_t mfma32;                    // tile 14: the patch-resident 16-bit kernel on 32x32x16 MFMAs (experiment)
-  int32_t* range_flag;               // OKP_F32X3: the plan's range flag (okp_conv_set_range_flag) or NULL
+  int32_t* range_flag;               // OKP_F32X3 / OKP_F16: the plan's range flag (okp_conv_set_range_flag) or NULL
   int64_t src_bytes64[2];            // the sources' byte spans in full (src_bytes is clamped to 32 bits): a source of the split-product patch kernel may pass 2 GiB
   OkpTapDev taps[OKP_MAX_TAPS];
 };
@@ -222,7 +244,7 @@ struct OkpPatchParams {
   const void* res; uint32_t res_bytes; int32_t res_pix_stride;
   int32_t act, n_co_tiles, n_tiles;
   uint32_t pairs;              // okp_igemm_patch_x3.hip: bit s = source s arrives in pair format (its patches are not split), bit 2 = out is written in pair format
-  int32_t* range_flag;         // okp_igemm_patch_x3.hip: the plan's range flag or NULL
+  int32_t* range_flag;         // the plan's range flag or NULL (okp_igemm_patch_x3.hip; the guarded fp16 instance of okp_igemm_patch.hip)
   int64_t src_total_bytes[2];  // okp_igemm_patch_x3.hip: a source's whole byte span (may pass 2 GiB) and the bytes of one frame of it: the kernel builds
   int64_t src_frame_bytes[2];  // its buffer resources per tile from the tile's frame, offsets are frame-relative
 #ifdef OKP_PATCH_STAMPS
@@ -238,7 +260,7 @@ struct OkpFire2Params {       // okp_fire2.hip: streaming fire module, 256 -> 12
   const void* wa; int32_t wa_cout_pad; const float* ba;     // expand plan
   const float* wd; const float* bd;                         // depth-wise [9][128] fp32, bias [128]
   const float* s1; const float* sa;                         // okp_fire_x3.hip (split-product plans): output scales of the squeeze / expand plan
-  int32_t* range_flag;                                      // okp_fire_x3.hip: the squeeze plan's range flag or NULL
+  int32_t* range_flag;                                      // the squeeze plan's range flag or NULL (okp_fire_x3.hip; guarded fp16 okp_fire2)
   int32_t SH, SW, IH, IW, IP, RPR, tiles_y, tiles_x, n_tiles;
   OkpFastDiv div_tiles_frame, div_tiles_x, div_sw, div_iw, div_rpr;
 #ifdef OKP_FIRE_STAMPS
@@ -255,6 +277,7 @@ struct OkpFireChainParams {
   const void* x; void* out; int32_t x_ps, out_ps, H, W, n_modules;
   int32_t He, We;               // EE form (entry + exit modules): size of the map the stride-2 entry module reads
   OkpFireChainModule mod[OKP_FIRE_CHAIN_MAX];
+  int32_t* range_flag;          // OKP_F16: the first squeeze plan's range flag (read by the guarded instances only) or NULL
 #ifdef OKP_FIRE_STAMPS
   uint32_t* dbg;                // debug build: shader-clock stamps at the phase boundaries of the chain's second module
 #endif
@@ -281,7 +304,7 @@ struct okp_conv {
   int32_t patch_n_geom;
   int32_t patch_src[OKP_PATCH_MAX_GEOM], patch_PW[OKP_PATCH_MAX_GEOM], patch_PH[OKP_PATCH_MAX_GEOM], patch_oy[OKP_PATCH_MAX_GEOM], patch_ox[OKP_PATCH_MAX_GEOM], patch_step[OKP_PATCH_MAX_GEOM];
   void* frag_dev;          // single-tap 16-bit plans: weights re-laid in MFMA-fragment order (built by okp_conv_create; NULL otherwise)
-  int32_t* range_flag;     // OKP_F32X3 plans: device flag raised by this plan's launches when a result leaves the fp16 range (okp_conv_set_range_flag); NULL = off
+  int32_t* range_flag;     // OKP_F32X3 / OKP_F16 plans: device flag raised by this plan's launches when a result leaves the fp16 range (okp_conv_set_range_flag); NULL = off
   void* fragT_dev;         // the same with the channel-as-ROW order of okp_fire2 (row i of block b = channel 32 w + 8 (i >> 2) + 4 b + (i & 3));
                            // single-tap OKP_F32X3 plans: [cout / 16][hi | lo][cin / 32][lane][8 fp16], row i of wave w = channel 16 w + i (okp_fire_x3.hip)
 };

@@ -53,7 +53,7 @@ struct StemParams {
   int32_t N, Ho, Wo, out_pix_stride;
   int32_t tiles_x, tiles_y, n_tiles;
   OkpFastDiv div_tiles_frame, div_tiles_x;
-  int32_t* range_flag;      // split-product plan: raised when a frame value or a result leaves the fp16 range (okp_stem_set_range_flag), or NULL
+  int32_t* range_flag;      // split-product / guarded fp16 stem: raised when a frame value or a result leaves the fp16 range (okp_stem_set_range_flag), or NULL
   int64_t out_total_bytes;  // split-product plan: bytes of the whole output view (it may pass 2 GiB: the kernel addresses frame by frame)
   int64_t out_frame_bytes;  // ... and of one frame of it
 };
@@ -66,9 +66,14 @@ __device__ __forceinline__ int fastdiv(int x, const OkpFastDiv& f) {
 
 // NCHW = true: the patch is read straight from the caller's fp32 NCHW frames (zero padding by range checks), rounded to
 // bf16 and written to LDS by the threads themselves - the packing pass (okp_pack_frames) and its 138 MB round trip go away.
-template <typename T, bool NCHW>
+// G: the range-guarded fp16 instantiation (okp_internal.h: OKP_F16 range guard): the frames it reads and the results it writes are checked
+// for being finite in fp16 - exactly, NaN included, on the packed words (the frames as rounded to fp16: a value beyond the range is inf) -
+// NCHW: where the kernel rounds them; packed frames (okp_pack_frames rounded them): each tile's patch once it is in LDS
+template <typename T, bool NCHW, bool G = false>
 __global__ __launch_bounds__(256, 2) void okp_stem_kernel(const StemParams p) {
+  static_assert(!G || std::is_same<T, _Float16>::value, "the 16-bit storage guard is an fp16 instantiation");
   __shared__ __attribute__((aligned(16))) char smem[2 * PATCH_BYTES];
+  uint32_t range_h = 0u;                        // G: largest |fp16| bits of the frame values / results this thread handled (okp_range_max_h2)
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -150,6 +155,7 @@ __global__ __launch_bounds__(256, 2) void okp_stem_kernel(const StemParams p) {
         if (idx < PATCH_BYTES / 8) {
           typename H16<T>::x4 o;
           o[0] = (T)pv[i][0]; o[1] = (T)pv[i][1]; o[2] = (T)pv[i][2]; o[3] = (T)0.f;
+          if constexpr (G) { const u32x2 o2 = __builtin_bit_cast(u32x2, o); range_h = okp_range_max_h2(okp_range_max_h2(range_h, o2[0]), o2[1]); }
           *reinterpret_cast<typename H16<T>::x4*>(smem + buf * PATCH_BYTES + idx * 8) = o;
         }
       }
@@ -170,6 +176,10 @@ __global__ __launch_bounds__(256, 2) void okp_stem_kernel(const StemParams p) {
     int n, oy0, ox0;
     tile_coords(tile, n, oy0, ox0);
     const char* patch = smem + buf * PATCH_BYTES;
+    if constexpr (G && !NCHW) {                   // packed frames (okp_pack_frames*: no flag of their own): the tile's patch, once, from LDS
+#pragma unroll
+      for (int i = 0; i < PATCH_BYTES / 16 / 256; ++i) range_h = okp_range_max_h8(range_h, reinterpret_cast<const u32x4*>(patch)[tid + 256 * i]);
+    }
     // byte address of this lane's B chunk for (row ry of the tile, ky, kx0): ((2 ry + ky) * PC + 2 j + kx0 + 2 h) * 8
     const int lane_off = (2 * j + 2 * h) * 8;
 #pragma unroll 1
@@ -204,8 +214,10 @@ __global__ __launch_bounds__(256, 2) void okp_stem_kernel(const StemParams p) {
           for (int e = 0; e < 16; ++e) {
             const int i0 = 8 * (e >> 2) + (e & 3);                  // pixel (MFMA row) of register e is i0 + 4 h
             const uint32_t v = okp_pack2<T>(fmaxf(acc[r][0][e], 0.f), fmaxf(acc[r][1][e], 0.f));
-            if (full || ox0 + i0 + 4 * h < p.Wo)
+            if (full || ox0 + i0 + 4 * h < p.Wo) {
+              if constexpr (G) range_h = okp_range_max_h2(range_h, v);
               __builtin_amdgcn_raw_buffer_store_b32(v, rs_o, (int)st_lane, (int)(row_off + (uint32_t)i0 * ps2), 0);
+            }
           }
         }
       }
@@ -214,6 +226,7 @@ __global__ __launch_bounds__(256, 2) void okp_stem_kernel(const StemParams p) {
     __syncthreads();            // every wave's part of the next patch is in LDS; this patch is free
     buf ^= 1;
   }
+  if constexpr (G) okp_raise_range_flag(p.range_flag, okp_range_exceeded_h2(range_h));
 }
 
 // ---- split-product form (OKP_F32X3): fp32 NHWC output, every product as x_hi w_hi + x_lo w_hi + x_hi w_lo on the fp16 matrix pipe ----
@@ -380,7 +393,7 @@ struct okp_stem {
   float* bias_dev;
   int dtype;
   float* oscale_dev;        // OKP_F32X3 only
-  int32_t* range_flag;      // OKP_F32X3 only: okp_stem_set_range_flag
+  int32_t* range_flag;      // OKP_F32X3 / OKP_F16: okp_stem_set_range_flag
 };
 
 
@@ -461,7 +474,7 @@ extern "C" okp_stem* okp_stem_create_dtype(int dtype, const float* w, const floa
 }
 
 extern "C" int okp_stem_set_range_flag(okp_stem* st, int32_t* flag_dev) {
-  if (!st || st->dtype != OKP_F32X3) { okp_set_error("okp_stem_set_range_flag: a split-product (OKP_F32X3) stem"); return OKP_EINVAL; }
+  if (!st || (st->dtype != OKP_F32X3 && st->dtype != OKP_F16)) { okp_set_error("okp_stem_set_range_flag: a split-product (OKP_F32X3) or float16 (OKP_F16) stem"); return OKP_EINVAL; }
   st->range_flag = flag_dev;
   return OKP_OK;
 }
@@ -493,7 +506,7 @@ extern "C" int okp_stem_forward(const okp_stem* st, int32_t n, int32_t h, int32_
   StemParams p;
   std::memset(&p, 0, sizeof(p));
   p.src = packed->data; p.src_bytes = (uint32_t)packed->bytes; p.Hp = packed->h; p.Wp = packed->w;
-  p.wfrag = st->wfrag_dev; p.bias = st->bias_dev;
+  p.wfrag = st->wfrag_dev; p.bias = st->bias_dev; p.range_flag = st->range_flag;
   p.out = out->data; p.out_bytes = (uint32_t)out->bytes; p.N = n; p.Ho = ho; p.Wo = wo; p.out_pix_stride = out->pix_stride;
   p.tiles_x = (wo + TW - 1) / TW; p.tiles_y = (ho + TH - 1) / TH;
   const long tiles = (long)n * p.tiles_x * p.tiles_y;
@@ -504,6 +517,7 @@ extern "C" int okp_stem_forward(const okp_stem* st, int32_t n, int32_t h, int32_
   const int resident = 256 * 2;        // two workgroups per CU: one computes while the other's stores drain
   const int grid = p.n_tiles < resident ? p.n_tiles : resident;
   if (st->dtype == OKP_BF16) hipLaunchKernelGGL((okp_stem_kernel<__bf16, false>), dim3(grid), dim3(256), 0, (hipStream_t)stream, p);
+  else if (p.range_flag) hipLaunchKernelGGL((okp_stem_kernel<_Float16, false, true>), dim3(grid), dim3(256), 0, (hipStream_t)stream, p);
   else hipLaunchKernelGGL((okp_stem_kernel<_Float16, false>), dim3(grid), dim3(256), 0, (hipStream_t)stream, p);
   return okp_check_hip(hipGetLastError(), "okp_stem launch");
 }
@@ -543,6 +557,7 @@ static int stem_forward_nchw(const okp_stem* st, int32_t n, int32_t h, int32_t w
   if (st->dtype == OKP_F32X3 && pairs) hipLaunchKernelGGL(okp_stem_x3_kernel<true>, dim3(grid), dim3(256), 0, (hipStream_t)stream, p);
   else if (st->dtype == OKP_F32X3) hipLaunchKernelGGL(okp_stem_x3_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, p);
   else if (st->dtype == OKP_BF16) hipLaunchKernelGGL((okp_stem_kernel<__bf16, true>), dim3(grid), dim3(256), 0, (hipStream_t)stream, p);
+  else if (p.range_flag) hipLaunchKernelGGL((okp_stem_kernel<_Float16, true, true>), dim3(grid), dim3(256), 0, (hipStream_t)stream, p);
   else hipLaunchKernelGGL((okp_stem_kernel<_Float16, true>), dim3(grid), dim3(256), 0, (hipStream_t)stream, p);
   return okp_check_hip(hipGetLastError(), "okp_stem launch");
 }

@@ -41,6 +41,8 @@ def __getattr__(name):
         return getattr(_MODE, "split", False)
     if name == "F32_MIX":
         return getattr(_MODE, "mix", False)
+    if name == "RANGE_GUARDED":
+        return getattr(_MODE, "range_flag", None) is not None
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 MIX_FP16_LEVELS = int(os.environ.get("OKP_MIX_FP16_LEVELS", "2"))    # hg_module levels n <= this run in fp16 (n = 2: the 16 x 16 level)
@@ -62,11 +64,13 @@ class f32_split:
     """Context manager: convolution plans built inside are split-product plans (KeypointNet(compute_dtype=ops.F32X3 / ops.F32MIX) wraps
     its passes in it).  range_flag (int32 device tensor of one element, optional): every split-product plan and stem BUILT inside gets it as
     its fp16-range flag (okp_conv_set_range_flag: a launch ORs 1 into it when one of its results would not survive the next layer's split
-    into fp16 halves - |x| > 65504 or not finite)."""
+    into fp16 halves - |x| > 65504 or not finite), and so does every float16 plan and stem built inside (the fp16 sub-networks of the
+    mixed configuration; a launch ORs 1 when a value it stores in fp16 is not finite).  guard16: keep the flag although the pass is not
+    split - a torch.float16 network with range_guard=True (its plans are float16: they get the flag, nothing else changes)."""
 
-    def __init__(self, enabled=True, mixed=False, range_flag=None):
+    def __init__(self, enabled=True, mixed=False, range_flag=None, guard16=False):
         self.enabled, self.mixed = bool(enabled), bool(enabled and mixed)
-        self.range_flag = range_flag if self.enabled else None
+        self.range_flag = range_flag if (self.enabled or guard16) else None
 
     def __enter__(self):
         self.prev = (getattr(_MODE, "split", False), getattr(_MODE, "mix", False), getattr(_MODE, "range_flag", None))
@@ -77,10 +81,11 @@ class f32_split:
 
 
 def _attach_range_flag(plan, setter_name):
-    """Give a freshly built split-product plan the range flag of the enclosing f32_split context, if there is one."""
+    """Give a freshly built split-product or float16 plan the range flag of the enclosing f32_split context, if there is one (the float16
+    plan's launches then run the range-guarded fp16 kernels)."""
     flag = getattr(_MODE, "range_flag", None)
     plan._range_flag = None
-    if flag is None or not plan.split:
+    if flag is None or not (plan.split or plan.dtype == torch.float16):
         return
     require_cuda(flag, "range_flag")
     if flag.dtype != torch.int32 or flag.numel() != 1:
@@ -510,10 +515,24 @@ if os.environ.get("OKP_FIRE2_S2_256_192", "1") == "0":      # A/B switch (script
 FUSE_FIRE_S2 = True
 
 
-def fire_fusable(inp_dim, mid, stride, h, w):
+# okp_fire2's matrix-pipe forms (the launcher's choice, csrc/okp_fire2.hip launch_fire2_t): output width a multiple of 16 at stride 1 / of 8 at
+# stride 2, the squeeze width at most OKP_F2_DWM_MID; the environment switches are the launcher's A/B switches, read the same way
+_F2_DWM = os.environ.get("OKP_F2_DWM", "1")[:1] != "0"
+_F2_DWM_S2 = os.environ.get("OKP_F2_DWM_S2", "1")[:1] != "0"
+_F2_DWM_MID = int(os.environ.get("OKP_F2_DWM_MID", "256")) if os.environ.get("OKP_F2_DWM_MID", "256").strip().isdigit() else 0
+
+
+def fire_fusable(inp_dim, mid, stride, h, w, guarded=False):
+    """guarded: the module's plans are float16 plans with a range flag.  The range-guarded one-launch kernel exists in the matrix-pipe forms
+    only (its vector-ALU forms would spill); other geometries run as the squeeze plan + fused tail on the guarded gather tiles."""
     if stride == 2 and not FUSE_FIRE_S2:
         return False
-    return FUSE_FIRE and (inp_dim, mid) in _FIRE2_CONFIGS.get(stride, ()) and min(h, w) // stride >= FUSE_FIRE_MIN_HW
+    if not (FUSE_FIRE and (inp_dim, mid) in _FIRE2_CONFIGS.get(stride, ()) and min(h, w) // stride >= FUSE_FIRE_MIN_HW):
+        return False
+    if guarded:
+        wo = (w - 1) // stride + 1
+        return _F2_DWM and mid <= _F2_DWM_MID and (wo % 16 == 0 if stride == 1 else (_F2_DWM_S2 and wo % 8 == 0))
+    return True
 
 
 FUSE_FIRE_X3 = True     # split-product plans: the one-launch fire module okp_fire_x3.hip (256 -> 128 -> 256 with skip, stride 1)

@@ -89,6 +89,7 @@ class _HipModule(nn.Module):
         if self.training:
             raise OkpError("the HIP path implements eval-mode inference only; call .eval()")
         key = (key, ops.F32_SPLIT, ops.F32_MIX)   # fp32 plans exist in three forms: exact fp32 MFMAs / split products (ops.F32X3) / mixed
+        key += (ops.RANGE_GUARDED,)               # ... and float16 plans two: built with the range flag of a guarded pass (ops.f32_split) or without
         p = self._plans.get(key)
         if p is None:
             p = build()
@@ -350,7 +351,8 @@ class fire_module(_HipModule):
         squeeze, expand, wd, bd = self._plan(("p", x.dtype), lambda: self._build(x.dtype, x.t.device))
         half = self.out_dim // 2
         ho, wo = conv_out_size(x.h, 3, self.stride, 1), conv_out_size(x.w, 3, self.stride, 1)
-        if (x.dtype in ops.HALF_DTYPES and ops.fire_fusable(self.inp_dim, self.mid, self.stride, x.h, x.w)) or \
+        guarded = x.dtype == torch.float16 and squeeze._range_flag is not None
+        if (x.dtype in ops.HALF_DTYPES and ops.fire_fusable(self.inp_dim, self.mid, self.stride, x.h, x.w, guarded=guarded)) or \
                 (squeeze.split and expand.split and ops.fire_fusable_x3(self.inp_dim, self.mid, self.stride, self.skip, x.h, x.w)):
             out = Act.empty(x.n, ho, wo, self.out_dim, x.dtype, x.t.device)
             ops.fire_fused(squeeze, expand, wd, bd, x, out, self.stride, self.skip)

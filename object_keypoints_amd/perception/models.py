@@ -89,7 +89,7 @@ class KeypointNet(_HipModule):
     branches, fp16 inner hourglass levels): heat error 4e-4 on the test networks, still inside the 1e-3 bar.
     """
 
-    def __init__(self, output_size=None, features=128, heatmaps_out=2, dropout=0.1, compute_dtype=torch.float32):
+    def __init__(self, output_size=None, features=128, heatmaps_out=2, dropout=0.1, compute_dtype=torch.float32, range_guard=None):
         super().__init__()
         self.backbone = hg()
         self.heatmap_head = HeatmapHead(features, heatmaps_out)
@@ -109,9 +109,14 @@ class KeypointNet(_HipModule):
         #   "float32" ... and run the pass again with the exact fp32 kernels (slow, always right), with a RuntimeWarning the first time
         #   "defer"   nothing is read: the caller asks range_overflow() or folds range_flag() into okp_capacity_overflow's word
         #             (BatchedKeypointPipeline.forward_device does; captured graphs cannot branch on the host anyway)
+        # torch.float16 stores every activation in the same 16-bit range: a result beyond 65504 is rounded to inf, and the same NaN -> ReLU -> 0
+        # follows one layer later.  range_guard=True runs its passes on the range-guarded fp16 kernels (the same flag, the same on_overflow);
+        # None (default) = each configuration's own: on for float32x3 / float32mix, off for float16 (see the range_guard property)
         self.on_overflow = "raise"
         self._range_flag = None
         self._warned_overflow = False
+        self._range_guard = None
+        self.range_guard = range_guard
 
     # ---- fused three-head plan for one stack ------------------------------------------------
     def _build_heads(self, stack, dtype, device):
@@ -130,10 +135,33 @@ class KeypointNet(_HipModule):
         b3 = np.concatenate([_np(pm[2].bias) for pm in heads], 0)
         return l1, l2, torch.from_numpy(w3).to(device), torch.from_numpy(b3).to(device)
 
+    @property
+    def range_guard(self):
+        """True if this network's passes run under the fp16-range guard: always for the split-product configurations (float32x3,
+        float32mix), for torch.float16 when it was asked for (range_guard=True), never for torch.bfloat16 / torch.float32."""
+        return bool(self.mfma_split or (self.compute_dtype == torch.float16 and self._range_guard))
+
+    @range_guard.setter
+    def range_guard(self, value):
+        """None: the configuration's default; True: guard a torch.float16 network (refused for bfloat16 / float32, whose range is fp32's:
+        there is nothing to guard); False: refused for the split-product configurations, whose guard is not optional."""
+        if value is not None and not isinstance(value, bool):
+            raise OkpError("range_guard is None, True or False")
+        if value is False and self.mfma_split:
+            raise OkpError(f"{self.configuration()}: the fp16-range guard of a split-product configuration cannot be switched off")
+        if value is True and not self.mfma_split and self.compute_dtype != torch.float16:
+            raise OkpError(f"range_guard=True: {self.configuration()} has the range of fp32 - the guard belongs to torch.float16 (and is always on "
+                           "for float32x3 / float32mix)")
+        before = self.range_guard
+        self._range_guard = value
+        if self.range_guard != before:
+            self._drop_all_plans()               # fp16 plans carry the flag (or not) from when they were built
+
     def range_flag(self, device=None):
-        """The network's fp16-range flag (int32 device tensor of one element; split-product configurations only, else None).  Every
-        split-product plan built by this network's passes raises it; the passes zero it when they start."""
-        if not self.mfma_split:
+        """The network's fp16-range flag (int32 device tensor of one element; guarded configurations only - the split-product ones and
+        torch.float16 with range_guard=True - else None).  Every plan built by this network's guarded passes raises it; the passes zero it
+        when they start."""
+        if not self.range_guard:
             return None
         if self._range_flag is None or (device is not None and self._range_flag.device != torch.device(device)):
             dev = device if device is not None else next(self.parameters()).device
@@ -147,12 +175,12 @@ class KeypointNet(_HipModule):
                 m._drop_plans()
 
     def range_overflow(self):
-        """True if a value left the fp16 range in a split-product pass since the last pass started (reads one word from the device)."""
-        return bool(self.mfma_split and self._range_flag is not None and int(self._range_flag) != 0)
+        """True if a value left the fp16 range in a guarded pass since the last pass started (reads one word from the device)."""
+        return bool(self.range_guard and self._range_flag is not None and int(self._range_flag) != 0)
 
     def _guarded(self, x, run, check):
         """One pass under the range guard: zero the flag, run, then act on `on_overflow` (see __init__).  check=False: never read the flag."""
-        if not self.mfma_split:
+        if not self.range_guard:
             return run()
         if self.on_overflow not in ("raise", "float32", "defer"):
             raise OkpError("on_overflow is 'raise', 'float32' or 'defer'")
@@ -163,8 +191,10 @@ class KeypointNet(_HipModule):
         if int(self._range_flag) == 0:
             return out
         if self.on_overflow == "raise":
-            raise OkpError(f"{self.configuration()}: an activation left the fp16 range (|x| > 65504 or not finite); the split products of this pass are "
-                           "not fp32-grade.  Run these weights with compute_dtype=torch.float32, or load with on_overflow='float32'")
+            what = ("the split products of this pass are not fp32-grade" if self.mfma_split else
+                    "float16 rounded it to inf, and the next layers turn that into NaN and then 0: the maps of this pass are wrong")
+            raise OkpError(f"{self.configuration()}: an activation left the fp16 range (|x| > 65504 or not finite); {what}.  "
+                           "Run these weights with compute_dtype=torch.float32, or load with on_overflow='float32'")
         if not self._warned_overflow:
             import warnings
             warnings.warn(f"{self.configuration()}: an activation left the fp16 range; passes that do are re-run with the exact float32 kernels", RuntimeWarning, stacklevel=3)
@@ -177,8 +207,9 @@ class KeypointNet(_HipModule):
             self.compute_dtype, self.mfma_split, self.mixed = mine
 
     def _run_heads(self, stack, cnv, sigmoid):
-        with ops.f32_split(self.mfma_split, self.mixed, self.range_flag(cnv.t.device)):      # (allocated here if no guarded pass has run yet: a plan
-            return self._run_heads_(stack, cnv, sigmoid)                                     #  built without the flag would be cached without it)
+        flag = self.range_flag(cnv.t.device)                   # (allocated here if no guarded pass has run yet: a plan built without the flag
+        with ops.f32_split(self.mfma_split, self.mixed, flag, guard16=flag is not None):     #  would be cached without it)
+            return self._run_heads_(stack, cnv, sigmoid)
 
     def _run_heads_(self, stack, cnv, sigmoid):
         l1, l2, w3, b3 = self._plan(("heads", stack, cnv.dtype), lambda: self._build_heads(stack, cnv.dtype, cnv.t.device))
@@ -203,7 +234,8 @@ class KeypointNet(_HipModule):
         return heat, depth, centers.reshape(n, K - 1, 2, h, w)
 
     def _features(self, x):
-        with ops.f32_split(self.mfma_split, self.mixed, self.range_flag(x.device) if isinstance(x, torch.Tensor) and x.is_cuda else None):
+        flag = self.range_flag(x.device) if isinstance(x, torch.Tensor) and x.is_cuda else None
+        with ops.f32_split(self.mfma_split, self.mixed, flag, guard16=flag is not None):
             return self._features_(x)
 
     def _features_(self, x):

@@ -185,7 +185,7 @@ def _audited(net, audit_frames, heat_bar, _source=None):
     return net
 
 
-def load_keypoint_net(model, compute_dtype=torch.float32, device=None, audit_frames=AUDIT_AUTO, heat_bar=HEAT_BAR, on_overflow="raise"):
+def load_keypoint_net(model, compute_dtype=torch.float32, device=None, audit_frames=AUDIT_AUTO, heat_bar=HEAT_BAR, on_overflow="raise", range_guard=None):
     """Accepts a KeypointNet, a state_dict, or a path to a torch.save'd state_dict / Lightning checkpoint /
     TorchScript file produced by the reference's scripts/package_model.py, and returns an eval KeypointNet.
     Entries of the file that are not KeypointNet parameters (loss buffers, metrics of the Lightning module) are ignored;
@@ -194,12 +194,16 @@ def load_keypoint_net(model, compute_dtype=torch.float32, device=None, audit_fra
     fall back to float32x3 when it misses `heat_bar` (see _audited; the result is in `net.audit`).  Default: a split-product configuration
     ("float32x3", "float32mix") is audited on synthetic frames; None skips the audit (with a RuntimeWarning for a mixed configuration).
     on_overflow ("raise" | "float32" | "defer"): what a pass of a split-product configuration does when an activation leaves the fp16
-    range (KeypointNet.on_overflow): raise OkpError, re-run the pass with the exact float32 kernels, or leave the flag to the caller."""
+    range (KeypointNet.on_overflow): raise OkpError, re-run the pass with the exact float32 kernels, or leave the flag to the caller.
+    range_guard (KeypointNet.range_guard): True runs a torch.float16 network under the same guard (on_overflow then applies to it); None
+    keeps each configuration's default (a KeypointNet passed in keeps its own)."""
     device = device or _device()
     if on_overflow not in ("raise", "float32", "defer"):
         raise OkpError("on_overflow is 'raise', 'float32' or 'defer'")
     if isinstance(model, models.KeypointNet):
         model.on_overflow = on_overflow
+        if range_guard is not None:
+            model.range_guard = range_guard
         return _audited(model.to(device).eval(), audit_frames, heat_bar)
     if isinstance(model, (str, bytes)) or hasattr(model, "__fspath__"):
         clean = read_checkpoint_state_dict(model)
@@ -212,7 +216,7 @@ def load_keypoint_net(model, compute_dtype=torch.float32, device=None, audit_fra
             raise OkpError(f"model file holds no KeypointNet: '{need}' is missing")
     heat_out = clean["heatmap_head.output_head2.2.weight"].shape[0]
     features = clean["heatmap_head.output_head2.0.conv.weight"].shape[0]
-    net = models.KeypointNet(features=features, heatmaps_out=heat_out, compute_dtype=compute_dtype)
+    net = models.KeypointNet(features=features, heatmaps_out=heat_out, compute_dtype=compute_dtype, range_guard=range_guard)
     own = net.state_dict()
     missing = [k for k in own if k not in clean]
     if missing:
@@ -250,14 +254,14 @@ def load_cornernet_backbone(net, pretrained):
 class InferenceComponent:
     name = "inference"
 
-    def __init__(self, model, cuda=True, compute_dtype=torch.float32, on_overflow="float32"):
+    def __init__(self, model, cuda=True, compute_dtype=torch.float32, on_overflow="float32", range_guard=None):
         """on_overflow (split-product compute dtypes only): the reference's fp32 model returns numbers for any input; the drop-in does too -
         a pass whose activations leave the fp16 range is re-run with the exact float32 kernels ("float32", with a RuntimeWarning the first
-        time) - unless the caller prefers an OkpError ("raise")."""
+        time) - unless the caller prefers an OkpError ("raise").  range_guard=True extends that to torch.float16 (KeypointNet.range_guard)."""
         if not cuda:
             raise OkpError("InferenceComponent(cuda=False): this build has no CPU path (the CPU restatement is oracle/, test-only)")
         self.cuda = cuda
-        self.model = load_keypoint_net(model, compute_dtype, on_overflow=on_overflow)
+        self.model = load_keypoint_net(model, compute_dtype, on_overflow=on_overflow, range_guard=range_guard)
 
     def __call__(self, frames):
         frames = frames.to(_device())
@@ -447,8 +451,9 @@ class LearnedKeypointTrackingPipeline(ObjectKeypointPipeline):
     def __init__(self, model, cuda=True, *args, **kwargs):
         compute_dtype = kwargs.pop("compute_dtype", torch.float32)
         on_overflow = kwargs.pop("on_overflow", "float32")
+        range_guard = kwargs.pop("range_guard", None)
         super().__init__(*args, **kwargs)
-        self.inference = InferenceComponent(model, cuda, compute_dtype=compute_dtype, on_overflow=on_overflow)
+        self.inference = InferenceComponent(model, cuda, compute_dtype=compute_dtype, on_overflow=on_overflow, range_guard=range_guard)
 
     def __call__(self, frame):
         heatmap, depth, centers = self.inference(frame)
@@ -654,7 +659,7 @@ class BatchedKeypointPipeline:
             raise OkpError("peak / object capacity exceeded; raise `capacity` / `max_objects`")
         if int(out["overflow"]) & ops.RANGE_OVERFLOW:
             raise OkpError("an activation of the split-product network left the fp16 range in this batch: its maps are not fp32-grade "
-                           "(load the network with on_overflow='float32', or run it in torch.float32)")
+                           "(load the network with on_overflow='float32', or run it in torch.float32; a guarded float16 network sets the same bit)")
         if any(c > self.max_per_type for c in cfg):
             raise OkpError(f"a keypoint type has {max(cfg)} instances, above max_per_type = {self.max_per_type}")
         sel = out["sel"][n].cpu().numpy()
