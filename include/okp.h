@@ -35,7 +35,7 @@ extern "C" {
                                     okp_capacity_overflow, okp_cast and okp_add_f16_f32; views of 2 GiB and more as the output of an OKP_F32X3
                                     stem and as sources of OKP_F32X3 plans on the patch-resident kernel
                                  additions at 7 (new entry points only; no struct or existing signature changed): okp_stereo_match,
-                                    okp_stereo_triangulate */
+                                    okp_stereo_triangulate; the struct okp_stereo_pair, okp_stereo_match_rig, okp_stereo_triangulate_rig */
 
 /* OKP_F16: IEEE half activations / weights, fp32 accumulate (BASELINE configs[4]).
  * OKP_F32X3 (okp_conv plans only): fp32 activations, weights and results like OKP_F32 - every tensor argument of such a plan is an
@@ -445,6 +445,31 @@ int okp_stereo_match(const okp_camera* left, const okp_camera* right, const doub
 int okp_stereo_triangulate(const okp_camera* left, const okp_camera* right, const double* T_RL, const double* F, int correct_matches,
                            const int32_t* count_dev, const float* xyc_dev, const int32_t* match_dev, int32_t n_pairs, int32_t K,
                            int32_t cap, double* points_dev, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * The same two jobs for a RIG whose stereo pairs are calibrated one by one (a real 8-camera rig is four physical pairs, each with its own
+ * intrinsics, distortion and baseline: one StereoCamera.from_file per Kalibr calibration, utils/camera_utils.py:84-117).
+ * okp_stereo_pair: the calibration of one pair, fp64 - left / right camera, T_RL (row-major 3 x 4: left-camera coordinates -> right
+ * camera's) and F (row-major 3 x 3, the pair's fundamental matrix).  The table is an array of them in DEVICE memory: a captured graph
+ * reads it on every replay.  Pair p of the tick (maps 2p, 2p + 1) uses table_dev[first_pair + p] - first_pair being the rig-wide index of
+ * the tick's first pair (a shard of the rig) - and a table of ONE entry is used for every pair (first_pair is then ignored); a longer
+ * table must cover first_pair + n_pairs <= n_table.  The kernels cannot check a device table: the caller validates the calibration
+ * (finite, fx, fy > 0, a known camera model) before it uploads it.
+ * Semantics, outputs and the remaining arguments are those of okp_stereo_match / okp_stereo_triangulate, per pair; the results of a
+ * pair equal, bit for bit, what the by-value entry points compute with that pair's calibration (one kernel body each). */
+typedef struct okp_stereo_pair {
+  okp_camera left, right;
+  double T_RL[12];
+  double F[9];
+} okp_stereo_pair;
+
+int okp_stereo_match_rig(const okp_stereo_pair* table_dev, int32_t n_table, int32_t first_pair, double max_distance,
+                         const int32_t* count_dev, const float* xyc_dev, int32_t n_pairs, int32_t K, int32_t cap,
+                         const int32_t* range_flag_dev, int32_t* match_dev, int32_t* overflow_dev, void* stream);
+/* correct_matches != 0: the Hartley-Sturm correction against each pair's F. */
+int okp_stereo_triangulate_rig(const okp_stereo_pair* table_dev, int32_t n_table, int32_t first_pair, int correct_matches,
+                               const int32_t* count_dev, const float* xyc_dev, const int32_t* match_dev, int32_t n_pairs, int32_t K,
+                               int32_t cap, double* points_dev, void* stream);
 
 /* Undistort only (FisheyeCamera.undistort, camera_utils.py:75-81 / RadTanPinholeCamera.undistort, :57-62, by cam->model):
  * xy [m][2] fp32 -> out [m][2] fp64.  okp_fisheye_undistort is the same entry point under its round-1 name. */

@@ -54,6 +54,10 @@ class okp_camera(Structure):
                 ("model", c_int32), ("reserved", c_int32)]
 
 
+class okp_stereo_pair(Structure):
+    _fields_ = [("left", okp_camera), ("right", okp_camera), ("T_RL", c_double * 12), ("F", c_double * 9)]
+
+
 # every symbol include/okp.h declares: (name, restype, argtypes)
 SIGNATURES = [
     ("okp_last_error", c_char_p, []),
@@ -99,6 +103,8 @@ SIGNATURES = [
                                  c_void_p, c_void_p, c_void_p, c_void_p]),
     ("okp_stereo_triangulate", c_int, [POINTER(okp_camera), POINTER(okp_camera), POINTER(c_double), POINTER(c_double), c_int, c_void_p, c_void_p, c_void_p,
                                        c_int32, c_int32, c_int32, c_void_p, c_void_p]),
+    ("okp_stereo_match_rig", c_int, [c_void_p, c_int32, c_int32, c_double, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    ("okp_stereo_triangulate_rig", c_int, [c_void_p, c_int32, c_int32, c_int, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
     ("okp_fisheye_undistort", c_int, [POINTER(okp_camera), c_void_p, c_int32, c_void_p, c_void_p]),
     ("okp_camera_undistort", c_int, [POINTER(okp_camera), c_void_p, c_int32, c_void_p, c_void_p]),
 ]

@@ -828,6 +828,7 @@ constexpr double OKP_STEREO_BIG = 1e6;
 struct StereoParams {
   okp_camera left, right;
   double F[9];
+  const okp_stereo_pair* table; int n_table, first_pair;           // the rig form (okp_stereo_match_rig); unused by okp_stereo_match
   double gate;
   const int* count; const float* xyc; const int* range_flag;
   int n_pairs, K, cap;
@@ -847,16 +848,39 @@ __device__ __forceinline__ double epipolar_cost(const StereoLds& s, int i, int j
   return 0.5 * (num / s.line[i][3] + num / s.pt[j][2]);
 }
 
+// The calibration of the tick's pair `pair`: the kernel argument (the by-value entry points), or - p.table set (the rig form) - table entry
+// first_pair + pair, or the one entry of a broadcast table.  One kernel for both: a uniform branch on p.table picks where the values come
+// from and everything after it is the same instructions, so the two forms give the same bits for the same calibration.  `pair` comes from
+// blockIdx, so the table address is wave-uniform; read before the kernel's first store, the entry is loaded with scalar loads into SGPRs,
+// as the kernel argument is.
+template <typename Params>
+__device__ __forceinline__ void pair_calibration(const Params& p, const okp_camera& left_arg, const okp_camera& right_arg, const double* T_arg,
+                                                 const double* F_arg, int pair, okp_camera& left, okp_camera& right, double (&T)[12], double (&F)[9]) {
+  if (p.table) {
+    const okp_stereo_pair& e = p.table[p.n_table == 1 ? 0 : p.first_pair + pair];
+    left = e.left; right = e.right;
+    for (int i = 0; i < 12; ++i) T[i] = e.T_RL[i];
+    for (int i = 0; i < 9; ++i) F[i] = e.F[i];
+  } else {
+    left = left_arg; right = right_arg;
+    for (int i = 0; i < 12; ++i) T[i] = T_arg ? T_arg[i] : 0.0;
+    for (int i = 0; i < 9; ++i) F[i] = F_arg[i];
+  }
+}
+
 __global__ __launch_bounds__(64) void okp_stereo_match_kernel(const StereoParams p) {
   __shared__ StereoLds s;
   const int lane = threadIdx.x;
+  const int pair = blockIdx.x / p.K, k = blockIdx.x - pair * p.K;
+  okp_camera left, right;
+  double T_unused[12], F[9];
+  pair_calibration(p, p.left, p.right, nullptr, p.F, pair, left, right, T_unused, F);
   if (blockIdx.x == 0) {        // the tick's overflow word: WRITTEN, not ORed (a replayed graph must not carry an earlier tick's flag)
     int bad = 0;
     for (int i = lane; i < 2 * p.n_pairs * p.K; i += 64) bad |= p.count[i] > p.cap;
     const bool any = __ballot(bad) != 0ull;
     if (lane == 0 && p.flag) *p.flag = (any ? 1 : 0) | ((p.range_flag && *p.range_flag) ? 2 : 0);
   }
-  const int pair = blockIdx.x / p.K, k = blockIdx.x - pair * p.K;
   const int ml = 2 * pair * p.K + k, mr = ml + p.K;                 // maps (2p, k) and (2p + 1, k)
   const int n = min(p.count[ml], p.cap), m = min(p.count[mr], p.cap);
   int* out = p.match + (size_t)blockIdx.x * p.cap;
@@ -866,17 +890,16 @@ __global__ __launch_bounds__(64) void okp_stereo_match_kernel(const StereoParams
   }
   const float* xl = p.xyc + (size_t)ml * p.cap * 3;
   const float* xr = p.xyc + (size_t)mr * p.cap * 3;
-  const double* F = p.F;
   for (int i = lane; i < n; i += 64) {
     double xu, yu;
-    camera_undistort(p.left, (double)xl[3 * i], (double)xl[3 * i + 1], xu, yu);
+    camera_undistort(left, (double)xl[3 * i], (double)xl[3 * i + 1], xu, yu);
     const double l0 = F[0] * xu + F[1] * yu + F[2], l1 = F[3] * xu + F[4] * yu + F[5], l2 = F[6] * xu + F[7] * yu + F[8];
     s.line[i][0] = l0; s.line[i][1] = l1; s.line[i][2] = l2;
     s.line[i][3] = fmax(sqrt(l0 * l0 + l1 * l1), 1e-300);
   }
   for (int j = lane; j < m; j += 64) {
     double xu, yu;
-    camera_undistort(p.right, (double)xr[3 * j], (double)xr[3 * j + 1], xu, yu);
+    camera_undistort(right, (double)xr[3 * j], (double)xr[3 * j + 1], xu, yu);
     const double c0 = xu * F[0] + yu * F[3] + F[6], c1 = xu * F[1] + yu * F[4] + F[7];
     s.pt[j][0] = xu; s.pt[j][1] = yu;
     s.pt[j][2] = fmax(sqrt(c0 * c0 + c1 * c1), 1e-300);
@@ -963,23 +986,31 @@ __global__ __launch_bounds__(64) void okp_stereo_match_kernel(const StereoParams
 }
 
 struct StereoTriParams {
-  TriParams tp;
+  TriParams tp;                                                     // okp_stereo_triangulate_rig: only tp.correct is read
+  const okp_stereo_pair* table; int n_table, first_pair;
   const int* count; const float* xyc; const int* match;
   int n_pairs, K, cap;
   double* points;
 };
 
 // Every slot (pair, type, left peak i) of a tick: (X, Y, Z, left confidence) of the matched pair by the per-pair code of
-// okp_triangulate_kernel (an octet per slot, eight slots per wave), NaN rows for unmatched slots.
+// okp_triangulate_kernel (an octet per slot, eight slots per wave), NaN rows for unmatched slots.  The grid is laid out per pair:
+// ceil(K cap / 8) waves for each, so that no wave straddles two pairs (it would whenever K cap % 8 != 0) and the pair's calibration is
+// wave-uniform - kernel argument (okp_stereo_triangulate) or table entry (okp_stereo_triangulate_rig) in SGPRs (pair_calibration).
 __global__ __launch_bounds__(64) void okp_stereo_triangulate_kernel(const StereoTriParams p) {
   const int lane = threadIdx.x & 63, g = lane & 7;
-  const int total = p.n_pairs * p.K * p.cap;
-  const int slot = blockIdx.x * 8 + (lane >> 3);
+  const int per_pair = p.K * p.cap, waves = (per_pair + 7) / 8;
+  const int pair = blockIdx.x / waves;
+  const int local = (blockIdx.x - pair * waves) * 8 + (lane >> 3);  // slot within the pair; >= per_pair: an idle octet
+  const int slot = pair * per_pair + local;
+  TriParams tp;
+  pair_calibration(p, p.tp.left, p.tp.right, p.tp.T, p.tp.F, pair, tp.left, tp.right, tp.T, tp.F);
+  tp.correct = p.tp.correct;
+  const bool in = local < per_pair;
   bool live = false;
   int lo = 0, ro = 0;                                               // element offsets of the left / right peak in xyc
-  if (slot < total) {
-    const int pk = slot / p.cap, i = slot - pk * p.cap;
-    const int pair = pk / p.K, k = pk - pair * p.K;
+  if (in) {
+    const int k = local / p.cap, i = local - k * p.cap;
     const int ml = 2 * pair * p.K + k, mr = ml + p.K;
     const int j = p.match[slot];
     live = i < min(p.count[ml], p.cap) && j >= 0 && j < min(p.count[mr], p.cap);
@@ -990,15 +1021,15 @@ __global__ __launch_bounds__(64) void okp_stereo_triangulate_kernel(const Stereo
   const double nan = __builtin_nan("");
   double* o = p.points + (size_t)slot * 4;
   if (lv == 0ull) {                                                 // (wave-uniform)
-    if (slot < total && g == 0) { o[0] = nan; o[1] = nan; o[2] = nan; o[3] = nan; }
+    if (in && g == 0) { o[0] = nan; o[1] = nan; o[2] = nan; o[3] = nan; }
     return;
   }
   const int src = __ffsll((long long)lv) - 1;                       // idle octets work on a live slot's pair and store nothing
   const int slo = __shfl(lo, src), sro = __shfl(ro, src);
   const int wlo = live ? lo : slo, wro = live ? ro : sro;
   double X, Y, Z;
-  triangulate_pair_oct(p.tp, g, p.xyc + wlo, p.xyc + wro, X, Y, Z);
-  if (slot < total && g == 0) {
+  triangulate_pair_oct(tp, g, p.xyc + wlo, p.xyc + wro, X, Y, Z);
+  if (in && g == 0) {
     if (live) { o[0] = X; o[1] = Y; o[2] = Z; o[3] = (double)p.xyc[lo + 2]; }
     else { o[0] = nan; o[1] = nan; o[2] = nan; o[3] = nan; }
   }
@@ -1113,26 +1144,70 @@ static int stereo_check_cameras(const char* fn, const okp_camera* left, const ok
   return OKP_OK;
 }
 
+static int stereo_check_gate(const char* fn, double max_distance, int32_t cap) {
+  if (!(max_distance >= 0.0) || !(max_distance < 1e300)) { okp_set_error("%s: max_distance = %g", fn, max_distance); return OKP_EINVAL; }
+  if ((double)cap * max_distance >= OKP_STEREO_BIG) {
+    okp_set_error("%s: cap * max_distance = %g is not below %g: the gated assignment would no longer maximise the number of matches",
+                  fn, (double)cap * max_distance, OKP_STEREO_BIG);
+    return OKP_EINVAL;
+  }
+  return OKP_OK;
+}
+
+// The rig form's table arguments (okp_stereo_match_rig / okp_stereo_triangulate_rig): a one-entry table is broadcast, a longer one covers
+// the tick's pairs first_pair .. first_pair + n_pairs - 1.
+static int stereo_check_table(const char* fn, const okp_stereo_pair* table, int32_t n_table, int32_t first_pair, int32_t n_pairs) {
+  if (n_table < 1) { okp_set_error("%s: n_table = %d; a calibration table holds at least one stereo pair", fn, n_table); return OKP_EINVAL; }
+  if (first_pair < 0) { okp_set_error("%s: first_pair = %d is negative", fn, first_pair); return OKP_EINVAL; }
+  if (n_table > 1 && (int64_t)first_pair + n_pairs > n_table) {
+    okp_set_error("%s: pairs %d .. %lld of the rig, but n_table = %d calibrations", fn, first_pair, (long long)first_pair + n_pairs - 1, n_table);
+    return OKP_EINVAL;
+  }
+  if (!table) { okp_set_error("%s: null calibration table", fn); return OKP_EINVAL; }
+  return OKP_OK;
+}
+
+static int stereo_match_launch(const char* fn, const StereoParams& p, void* stream) {
+  hipLaunchKernelGGL(okp_stereo_match_kernel, dim3(p.n_pairs * p.K), dim3(64), 0, (hipStream_t)stream, p);
+  return okp_check_hip(hipGetLastError(), fn);
+}
+
 extern "C" int okp_stereo_match(const okp_camera* left, const okp_camera* right, const double* F, double max_distance,
                                 const int32_t* count, const float* xyc, int32_t n_pairs, int32_t K, int32_t cap,
                                 const int32_t* range_flag, int32_t* match, int32_t* overflow, void* stream) {
   int rc = stereo_check_shape("okp_stereo_match", n_pairs, K, cap);
   if (rc) return rc;
-  if (!(max_distance >= 0.0) || !(max_distance < 1e300)) { okp_set_error("okp_stereo_match: max_distance = %g", max_distance); return OKP_EINVAL; }
-  if ((double)cap * max_distance >= OKP_STEREO_BIG) {
-    okp_set_error("okp_stereo_match: cap * max_distance = %g is not below %g: the gated assignment would no longer maximise the number of matches",
-                  (double)cap * max_distance, OKP_STEREO_BIG);
-    return OKP_EINVAL;
-  }
+  if ((rc = stereo_check_gate("okp_stereo_match", max_distance, cap))) return rc;
   if ((rc = stereo_check_cameras("okp_stereo_match", left, right))) return rc;
   if (!F || !count || !xyc || !match) { okp_set_error("okp_stereo_match: null argument"); return OKP_EINVAL; }
-  StereoParams p;
+  StereoParams p = {};
   p.left = *left; p.right = *right;
   for (int i = 0; i < 9; ++i) p.F[i] = F[i];
   p.gate = max_distance; p.count = count; p.xyc = xyc; p.range_flag = range_flag;
   p.n_pairs = n_pairs; p.K = K; p.cap = cap; p.match = match; p.flag = overflow;
-  hipLaunchKernelGGL(okp_stereo_match_kernel, dim3(n_pairs * K), dim3(64), 0, (hipStream_t)stream, p);
-  return okp_check_hip(hipGetLastError(), "okp_stereo_match launch");
+  return stereo_match_launch("okp_stereo_match launch", p, stream);
+}
+
+extern "C" int okp_stereo_match_rig(const okp_stereo_pair* table, int32_t n_table, int32_t first_pair, double max_distance,
+                                    const int32_t* count, const float* xyc, int32_t n_pairs, int32_t K, int32_t cap,
+                                    const int32_t* range_flag, int32_t* match, int32_t* overflow, void* stream) {
+  int rc = stereo_check_shape("okp_stereo_match_rig", n_pairs, K, cap);
+  if (rc) return rc;
+  if ((rc = stereo_check_gate("okp_stereo_match_rig", max_distance, cap))) return rc;
+  if ((rc = stereo_check_table("okp_stereo_match_rig", table, n_table, first_pair, n_pairs))) return rc;
+  if (!count || !xyc || !match) { okp_set_error("okp_stereo_match_rig: null argument"); return OKP_EINVAL; }
+  StereoParams p = {};
+  p.table = table; p.n_table = n_table; p.first_pair = first_pair;
+  p.gate = max_distance; p.count = count; p.xyc = xyc; p.range_flag = range_flag;
+  p.n_pairs = n_pairs; p.K = K; p.cap = cap; p.match = match; p.flag = overflow;
+  return stereo_match_launch("okp_stereo_match_rig launch", p, stream);
+}
+
+// ceil(K cap / 8) waves per pair (okp_stereo_triangulate_kernel)
+static int stereo_triangulate_launch(const char* fn, const StereoTriParams& p, void* stream) {
+  const dim3 grid(p.n_pairs * ((p.K * p.cap + 7) / 8));
+  hipLaunchKernelGGL(okp_stereo_triangulate_kernel, grid, dim3(64), 0, (hipStream_t)stream, p);
+  return okp_check_hip(hipGetLastError(), fn);
 }
 
 extern "C" int okp_stereo_triangulate(const okp_camera* left, const okp_camera* right, const double* T_RL, const double* F, int correct_matches,
@@ -1143,13 +1218,25 @@ extern "C" int okp_stereo_triangulate(const okp_camera* left, const okp_camera* 
   if (correct_matches && !F) { okp_set_error("okp_stereo_triangulate: the Hartley-Sturm correction needs F"); return OKP_EINVAL; }
   if ((rc = stereo_check_cameras("okp_stereo_triangulate", left, right))) return rc;
   if (!T_RL || !count || !xyc || !match || !points) { okp_set_error("okp_stereo_triangulate: null argument"); return OKP_EINVAL; }
-  StereoTriParams p;
+  StereoTriParams p = {};
   p.tp.left = *left; p.tp.right = *right;
   for (int i = 0; i < 12; ++i) p.tp.T[i] = T_RL[i];
   for (int i = 0; i < 9; ++i) p.tp.F[i] = F ? F[i] : 0.0;
   p.tp.correct = correct_matches ? 1 : 0;
   p.count = count; p.xyc = xyc; p.match = match; p.n_pairs = n_pairs; p.K = K; p.cap = cap; p.points = points;
-  const int total = n_pairs * K * cap;
-  hipLaunchKernelGGL(okp_stereo_triangulate_kernel, dim3((total + 7) / 8), dim3(64), 0, (hipStream_t)stream, p);
-  return okp_check_hip(hipGetLastError(), "okp_stereo_triangulate launch");
+  return stereo_triangulate_launch("okp_stereo_triangulate launch", p, stream);
+}
+
+extern "C" int okp_stereo_triangulate_rig(const okp_stereo_pair* table, int32_t n_table, int32_t first_pair, int correct_matches,
+                                          const int32_t* count, const float* xyc, const int32_t* match, int32_t n_pairs, int32_t K, int32_t cap,
+                                          double* points, void* stream) {
+  int rc = stereo_check_shape("okp_stereo_triangulate_rig", n_pairs, K, cap);
+  if (rc) return rc;
+  if ((rc = stereo_check_table("okp_stereo_triangulate_rig", table, n_table, first_pair, n_pairs))) return rc;
+  if (!count || !xyc || !match || !points) { okp_set_error("okp_stereo_triangulate_rig: null argument"); return OKP_EINVAL; }
+  StereoTriParams p = {};
+  p.tp.correct = correct_matches ? 1 : 0;
+  p.table = table; p.n_table = n_table; p.first_pair = first_pair;
+  p.count = count; p.xyc = xyc; p.match = match; p.n_pairs = n_pairs; p.K = K; p.cap = cap; p.points = points;
+  return stereo_triangulate_launch("okp_stereo_triangulate_rig launch", p, stream);
 }

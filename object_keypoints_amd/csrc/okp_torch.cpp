@@ -494,6 +494,42 @@ void stereo_triangulate(at::ArrayRef<double> left, at::ArrayRef<double> right, a
            "okp_stereo_triangulate");
 }
 
+// A rig's calibration table: the packed okp_stereo_pair entries (ops.stereo_rig) as a contiguous uint8 [n_table, sizeof(okp_stereo_pair)]
+// device tensor; returns n_table
+inline int32_t stereo_table_size(const Tensor& table) {
+  check_dev(table, at::kByte, "table");
+  TORCH_CHECK(table.dim() == 2 && table.size(0) >= 1 && table.size(1) == (int64_t)sizeof(okp_stereo_pair),
+              "okp: a rig's calibration table is uint8 [n_table, ", sizeof(okp_stereo_pair), "] (ops.stereo_rig)");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(table.data_ptr()) % alignof(okp_stereo_pair) == 0, "okp: the calibration table must be 8-byte aligned");
+  return (int32_t)table.size(0);
+}
+
+// The rig form of stereo_match: pair p of the tick uses table[first_pair + p] (a one-entry table: every pair)
+void stereo_match_rig(const Tensor& table, int64_t first_pair, double max_distance, const Tensor& count, const Tensor& xyc, const Tensor& match,
+                      const Tensor& overflow, int64_t stream, const optional<Tensor>& range_flag) {
+  const int64_t P = stereo_tick_pairs(count, xyc);
+  const int32_t n_table = stereo_table_size(table);
+  check_dev(match, at::kInt, "match"); check_dev(overflow, at::kInt, "overflow");
+  if (range_flag.has_value()) check_dev(*range_flag, at::kInt, "range_flag");
+  TORCH_CHECK(match.numel() == P * xyc.size(1) * xyc.size(2) && overflow.numel() >= 1, "okp: match is [P,K,cap] int32, overflow one int32");
+  check_rc(okp_stereo_match_rig(reinterpret_cast<const okp_stereo_pair*>(table.data_ptr()), n_table, (int32_t)first_pair, max_distance,
+                                count.data_ptr<int32_t>(), xyc.data_ptr<float>(), (int32_t)P, (int32_t)xyc.size(1), (int32_t)xyc.size(2),
+                                range_flag.has_value() ? range_flag->data_ptr<int32_t>() : nullptr, match.data_ptr<int32_t>(), overflow.data_ptr<int32_t>(),
+                                sp(stream)), "okp_stereo_match_rig");
+}
+
+// The rig form of stereo_triangulate: correct_matches = the Hartley-Sturm correction against each pair's F
+void stereo_triangulate_rig(const Tensor& table, int64_t first_pair, bool correct_matches, const Tensor& count, const Tensor& xyc, const Tensor& match,
+                            const Tensor& points, int64_t stream) {
+  const int64_t P = stereo_tick_pairs(count, xyc);
+  const int32_t n_table = stereo_table_size(table);
+  check_dev(match, at::kInt, "match"); check_dev(points, at::kDouble, "points");
+  TORCH_CHECK(match.numel() == P * xyc.size(1) * xyc.size(2) && points.numel() == match.numel() * 4, "okp: match is [P,K,cap] int32, points [P,K,cap,4] float64");
+  check_rc(okp_stereo_triangulate_rig(reinterpret_cast<const okp_stereo_pair*>(table.data_ptr()), n_table, (int32_t)first_pair, correct_matches ? 1 : 0,
+                                      count.data_ptr<int32_t>(), xyc.data_ptr<float>(), match.data_ptr<int32_t>(), (int32_t)P, (int32_t)xyc.size(1),
+                                      (int32_t)xyc.size(2), points.data_ptr<double>(), sp(stream)), "okp_stereo_triangulate_rig");
+}
+
 void lift_peaks(at::ArrayRef<double> camera, const Tensor& count, const Tensor& xyc, const Tensor& depth, int64_t max_x, int64_t max_y, const Tensor& out, int64_t stream) {
   TORCH_CHECK(xyc.is_cuda() && xyc.dim() == 4 && xyc.scalar_type() == at::kFloat && depth.is_cuda() && depth.scalar_type() == at::kFloat && depth.dim() == 4 && depth.is_contiguous() &&
               depth.size(0) == xyc.size(0) && depth.size(1) == xyc.size(1) && count.scalar_type() == at::kInt && out.scalar_type() == at::kDouble &&
@@ -569,4 +605,8 @@ TORCH_LIBRARY(okp, m) {
         "Tensor? range_flag=None) -> ()", stereo_match);
   m.def("stereo_triangulate(float[] left, float[] right, float[] T_RL, float[] F, Tensor count, Tensor xyc, Tensor match, Tensor(a!) points, int stream) -> ()",
         stereo_triangulate);
+  m.def("stereo_match_rig(Tensor table, int first_pair, float max_distance, Tensor count, Tensor xyc, Tensor(a!) match, Tensor(b!) overflow, int stream, "
+        "Tensor? range_flag=None) -> ()", stereo_match_rig);
+  m.def("stereo_triangulate_rig(Tensor table, int first_pair, bool correct_matches, Tensor count, Tensor xyc, Tensor match, Tensor(a!) points, int stream) -> ()",
+        stereo_triangulate_rig);
 }

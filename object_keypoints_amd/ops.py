@@ -1066,3 +1066,87 @@ def stereo_triangulate(cam_l, cam_r, T_RL, count, xyc, match, F=None):
         _lib.check(_lib.lib().okp_stereo_triangulate(ctypes.byref(cam_l), ctypes.byref(cam_r), Ta, Fa, 1 if Fl else 0, count.data_ptr(), xyc.data_ptr(),
                                                      match.data_ptr(), n_pairs, k, cap, points.data_ptr(), stream_handle()), "okp_stereo_triangulate")
     return points
+
+
+# ---- a rig of individually calibrated stereo pairs (okp_stereo_match_rig / okp_stereo_triangulate_rig) -------------------------------------
+STEREO_PAIR_BYTES = ctypes.sizeof(_lib.okp_stereo_pair)
+
+
+def stereo_rig(stereo_cameras):
+    """The calibration table of a rig: a sequence of P StereoCameras, pair p = frames 2p (left) and 2p + 1 (right) of a tick ->
+    uint8 HOST tensor [P, STEREO_PAIR_BYTES] of packed okp_stereo_pair entries (left / right camera, T_RL, F; fp64), which the caller
+    moves to the device once.  Each camera is the equidistant model from its own K and D (make_camera), as StereoStreamPipeline and the
+    reference's StereoCamera.triangulate use it.  The kernels cannot check a device table, so a bad calibration is refused here: non-finite
+    entries, fx or fy <= 0, skew, a T_RL whose last row is not [0, 0, 0, 1], an empty rig."""
+    cams = list(stereo_cameras)
+    if not cams:
+        raise OkpError("a rig has at least one stereo pair")
+    table = (_lib.okp_stereo_pair * len(cams))()
+    for p, st in enumerate(cams):
+        e = table[p]
+        for side, cam in (("left", st.left_camera), ("right", st.right_camera)):
+            K, D = np.asarray(cam.K, dtype=np.float64), np.asarray(cam.D, dtype=np.float64).reshape(-1)
+            if K.shape != (3, 3) or not np.isfinite(K).all() or not np.isfinite(D).all():
+                raise OkpError(f"stereo pair {p}: the {side} camera's K must be a finite 3 x 3 matrix and D finite")
+            if not (K[0, 0] > 0 and K[1, 1] > 0):
+                raise OkpError(f"stereo pair {p}: the {side} camera has fx = {K[0, 0]}, fy = {K[1, 1]}; both must be positive")
+            try:
+                setattr(e, side, make_camera(K, D))
+            except OkpError as err:
+                raise OkpError(f"stereo pair {p}: the {side} camera: {err}") from None
+        T = np.asarray(st.T_RL, dtype=np.float64)
+        if T.shape != (4, 4) or not np.isfinite(T).all():
+            raise OkpError(f"stereo pair {p}: T_RL must be a finite 4 x 4 transform")
+        if not np.array_equal(T[3], [0.0, 0.0, 0.0, 1.0]):
+            raise OkpError(f"stereo pair {p}: T_RL's last row is {T[3].tolist()}, not [0, 0, 0, 1]")
+        F = np.asarray(st.F, dtype=np.float64)
+        if F.shape != (3, 3) or not np.isfinite(F).all():
+            raise OkpError(f"stereo pair {p}: F must be a finite 3 x 3 matrix")
+        e.T_RL[:] = [float(v) for v in T[:3].reshape(12)]
+        e.F[:] = [float(v) for v in F.reshape(9)]
+    return torch.frombuffer(bytearray(table), dtype=torch.uint8).reshape(len(cams), STEREO_PAIR_BYTES).clone()
+
+
+def _rig_table(table):
+    require_cuda(table, "table")
+    if table.dtype != torch.uint8 or table.dim() != 2 or table.shape[0] < 1 or table.shape[1] != STEREO_PAIR_BYTES or not table.is_contiguous():
+        raise OkpError(f"a rig's calibration table is a contiguous uint8 [n_table, {STEREO_PAIR_BYTES}] device tensor (stereo_rig)")
+    return table.shape[0]
+
+
+def stereo_match_rig(table, count, xyc, max_distance, first_pair=0, range_flag=None):
+    """stereo_match for a rig: pair p of the tick is associated against the epipolar geometry of table[first_pair + p] (the table of
+    stereo_rig on the device; a one-entry table serves every pair), with that pair's cameras.  -> match [P,K,cap] int32, overflow (0-d int32)."""
+    n_pairs, k, cap = _tick_pairs(count, xyc)
+    n_table = _rig_table(table)
+    count, xyc = count.contiguous(), xyc.contiguous()
+    match = torch.empty((n_pairs, k, cap), dtype=torch.int32, device=xyc.device)
+    flag = torch.empty((1,), dtype=torch.int32, device=xyc.device)
+    T = _ops()
+    if T is not None:
+        _dispatch(T.stereo_match_rig, table, int(first_pair), float(max_distance), count, xyc, match, flag, stream_int(), range_flag)
+    else:
+        _lib.check(_lib.lib().okp_stereo_match_rig(table.data_ptr(), n_table, int(first_pair), float(max_distance), count.data_ptr(), xyc.data_ptr(),
+                                                   n_pairs, k, cap, range_flag.data_ptr() if range_flag is not None else None, match.data_ptr(),
+                                                   flag.data_ptr(), stream_handle()), "okp_stereo_match_rig")
+    return match, flag[0]
+
+
+def stereo_triangulate_rig(table, count, xyc, match, first_pair=0, correct_matches=True):
+    """stereo_triangulate for a rig: the matched slots of pair p triangulated with the cameras and T_RL of table[first_pair + p] (with the
+    Hartley-Sturm correction against its F unless correct_matches=False).  -> points [P,K,cap,4] fp64 in each pair's left camera frame."""
+    n_pairs, k, cap = _tick_pairs(count, xyc)
+    n_table = _rig_table(table)
+    require_cuda(match, "match")
+    if match.dtype != torch.int32 or tuple(match.shape) != (n_pairs, k, cap):
+        raise OkpError("match must be int32 [P,K,cap] (stereo_match_rig)")
+    count, xyc, match = count.contiguous(), xyc.contiguous(), match.contiguous()
+    points = torch.empty((n_pairs, k, cap, 4), dtype=torch.float64, device=xyc.device)
+    TO = _ops()
+    if TO is not None:
+        _dispatch(TO.stereo_triangulate_rig, table, int(first_pair), bool(correct_matches), count, xyc, match, points, stream_int())
+    else:
+        _lib.check(_lib.lib().okp_stereo_triangulate_rig(table.data_ptr(), n_table, int(first_pair), 1 if correct_matches else 0, count.data_ptr(),
+                                                         xyc.data_ptr(), match.data_ptr(), n_pairs, k, cap, points.data_ptr(), stream_handle()),
+                   "okp_stereo_triangulate_rig")
+    return points

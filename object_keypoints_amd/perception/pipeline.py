@@ -793,18 +793,46 @@ class StereoStreamPipeline:
     three small device -> host copies per tick (peaks, undistorted peaks, 3D points).
     `frames`: fp32 NCHW crops [2P, 3, 511, 511] in HBM, or raw camera frames uint8 [2P, H, W, 3] (resized, cropped and normalised on the
     device, okp_preprocess_u8).  Host-fed operation: stream(host_ticks) uploads the raw frames of tick t + 1 on a copy stream while tick t
-    is computed (HostFrameFeed) and yields the same results, bit for bit, as tick() on resident frames."""
+    is computed (HostFrameFeed) and yields the same results, bit for bit, as tick() on resident frames.
+
+    stereo_camera: one StereoCamera, used for every pair of a tick of any size, or a RIG - a sequence of P StereoCameras, each pair
+    calibrated on its own (pair p = frames 2p and 2p + 1, its points in its own left camera frame); a rig's ticks hold exactly its 2P
+    frames (tick_device / tick_sharded: a shard of them, first_pair = the shard's first pair).  The calibration is validated and packed
+    at construction (ops.stereo_rig: a bad one fails here, before any device work) and uploaded to the frames' device on the first
+    device tick; the device copy lives as long as the pipeline, since captured ticks read it on every replay."""
 
     def __init__(self, net, stereo_camera, keypoint_config, capacity=16, max_distance=3.0):
         self.net = net
-        self.stereo = stereo_camera
+        self.rig = None if hasattr(stereo_camera, "left_camera") else list(stereo_camera)       # one StereoCamera, or a sequence of them
+        self.stereo_cameras = self.rig if self.rig is not None else [stereo_camera]
+        self._table_host = ops.stereo_rig(self.stereo_cameras)         # (refuses an empty rig)
+        self._tables = {}                                               # device -> the uploaded table
+        self.stereo = self.stereo_cameras[0]
         self.config = [1] + list(keypoint_config["keypoint_config"])
         self.capacity = capacity
         self.assoc = AssociationComponent(max_distance=max_distance)
-        self.assoc.reset(stereo_camera)
-        self.cam_l = ops.make_camera(stereo_camera.left_camera.K, stereo_camera.left_camera.D)      # fisheye model, as the reference
-        self.cam_r = ops.make_camera(stereo_camera.right_camera.K, stereo_camera.right_camera.D)
+        self.assoc.reset(self.stereo)
+        # fisheye model, as the reference; one (left, right) pair per calibration
+        self._cams = [(ops.make_camera(st.left_camera.K, st.left_camera.D), ops.make_camera(st.right_camera.K, st.right_camera.D))
+                      for st in self.stereo_cameras]
+        self.cam_l, self.cam_r = self._cams[0]
         self._graph = None
+
+    def _check_rig_frames(self, frames, first_pair=0):
+        """A rig's tick holds 2 frames for each of its pairs first_pair .. first_pair + P - 1 (a single calibration: any P)."""
+        if frames.shape[0] % 2:
+            raise OkpError("a tick holds the left and right frame of every stereo pair: an even number of frames")
+        first_pair = int(first_pair)
+        if self.rig is not None and (first_pair < 0 or first_pair + frames.shape[0] // 2 > len(self.rig)):
+            raise OkpError(f"{frames.shape[0]} frames from pair {first_pair} on: the rig has {len(self.rig)} stereo pairs "
+                           f"(pairs {first_pair} .. {first_pair + frames.shape[0] // 2 - 1} asked for)")
+        return first_pair
+
+    def _table(self, device):
+        t = self._tables.get(device)
+        if t is None:
+            t = self._tables[device] = self._table_host.to(device)
+        return t
 
     def capture(self, frames):
         """Capture the network pass of a tick for this frame shape into a hipGraph (one graph launch instead of ~66)."""
@@ -842,8 +870,9 @@ class StereoStreamPipeline:
             slot = nxt
 
     def tick(self, frames, heat_override=None, use_graph=False):
-        if frames.shape[0] % 2:
-            raise OkpError("a tick holds the left and right frame of every stereo pair: an even number of frames")
+        self._check_rig_frames(frames)
+        if self.rig is not None and frames.shape[0] != 2 * len(self.rig):
+            raise OkpError(f"{frames.shape[0]} frames for a rig of {len(self.rig)} stereo pairs: a tick holds {2 * len(self.rig)}")
         with torch.no_grad():
             if use_graph:
                 if self._graph is None:
@@ -858,16 +887,22 @@ class StereoStreamPipeline:
             if int(count_h.max(initial=0)) > self.capacity:
                 raise OkpError("peak capacity exceeded in a tick; raise `capacity`")
             n_pairs, K = frames.shape[0] // 2, heat.shape[1]
-            # undistort every left and every right peak of the tick in two launches (the cost of the assignment needs them)
+            # undistort every left and every right peak of the tick, two launches per calibration (the cost of the assignment needs them)
             xy = xyc[..., :2].reshape(n_pairs, 2, K, self.capacity, 2)
-            ul = ops.camera_undistort(self.cam_l, xy[:, 0].reshape(-1, 2))
-            ur = ops.camera_undistort(self.cam_r, xy[:, 1].reshape(-1, 2))
-            und = torch.stack([ul, ur]).cpu().numpy().reshape(2, n_pairs, K, self.capacity, 2)      # D2H 2
+            groups = [slice(None)] if self.rig is None else [slice(p, p + 1) for p in range(n_pairs)]      # the pairs of calibration c
+            und = []
+            for c, pairs in enumerate(groups):
+                cam_l, cam_r = self._cams[c]
+                ul = ops.camera_undistort(cam_l, xy[pairs, 0].reshape(-1, 2))
+                ur = ops.camera_undistort(cam_r, xy[pairs, 1].reshape(-1, 2))
+                und.append(torch.stack([ul, ur]).reshape(2, -1, K, self.capacity, 2))
+            und = (und[0] if len(und) == 1 else torch.cat(und, dim=1)).cpu().numpy()                # D2H 2
             raw = xy.cpu().numpy()
-        F = self.stereo.F
-        left_sel, right_sel, owner = [], [], []
+        left_sel, right_sel, owner = [[] for _ in groups], [[] for _ in groups], [[] for _ in groups]
         from scipy.optimize import linear_sum_assignment
         for p in range(n_pairs):
+            c = 0 if self.rig is None else p
+            F = self.stereo_cameras[c].F
             for k in range(K):
                 cl, cr = int(count_h[2 * p, k]), int(count_h[2 * p + 1, k])
                 if cl == 0 or cr == 0:
@@ -881,32 +916,35 @@ class StereoStreamPipeline:
                 rows, cols = linear_sum_assignment(np.where(cost <= self.assoc.max_distance, cost, 1e6))
                 keep = cost[rows, cols] <= self.assoc.max_distance
                 for i, j in zip(rows[keep], cols[keep]):
-                    left_sel.append(raw[p, 0, k, i]); right_sel.append(raw[p, 1, k, j]); owner.append((p, k))
+                    left_sel[c].append(raw[p, 0, k, i]); right_sel[c].append(raw[p, 1, k, j]); owner[c].append((p, k))
         result = [{k: np.zeros((0, 3)) for k in range(K)} for _ in range(n_pairs)]
-        if left_sel:
-            dev = frames.device
-            pts = ops.triangulate_dlt(self.cam_l, self.cam_r, self.stereo.T_RL, torch.from_numpy(np.stack(left_sel)).to(dev),
-                                      torch.from_numpy(np.stack(right_sel)).to(dev), F=F).cpu().numpy()          # D2H 3
-            for (p, k), X in zip(owner, pts):
+        dev = frames.device
+        for c in range(len(groups)):                                   # one triangulation launch per calibration
+            if not left_sel[c]:
+                continue
+            st = self.stereo_cameras[c]
+            pts = ops.triangulate_dlt(*self._cams[c], st.T_RL, torch.from_numpy(np.stack(left_sel[c])).to(dev),
+                                      torch.from_numpy(np.stack(right_sel[c])).to(dev), F=st.F).cpu().numpy()          # D2H 3
+            for (p, k), X in zip(owner[c], pts):
                 result[p][k] = np.concatenate([result[p][k], X[None]])
         return result
 
     # ---- the device-resident tick (no host wait between the frames and the 3D points) ------------------------------------------------
-    def _check_device_tick(self, frames):
+    def _check_device_tick(self, frames, first_pair=0):
         if self.capacity > ops.STEREO_MAX_CAPACITY:
             raise OkpError(f"capacity = {self.capacity}: the device association holds at most {ops.STEREO_MAX_CAPACITY} peaks per map")
-        if frames.shape[0] % 2:
-            raise OkpError("a tick holds the left and right frame of every stereo pair: an even number of frames")
+        return self._check_rig_frames(frames, first_pair)
 
-    def tick_device(self, frames, heat_override=None):
+    def tick_device(self, frames, heat_override=None, first_pair=0):
         """The whole tick on the device, with no host wait anywhere: network -> peak-NMS -> left/right association (okp_stereo_match) ->
         triangulation of every matched slot (okp_stereo_triangulate).  Same frames as tick().  Returns a dict of device tensors
             heat, depth [2P,K,H,W], count [2P,K] int32, xyc [2P,K,cap,3] fp32, match [P,K,cap] int32,
             points [P,K,cap,4] fp64 (X, Y, Z, left confidence; NaN rows = unmatched slots), overflow (0-d int32: bit 0 some map of the tick
             holds more than `capacity` peaks, bit 1 ops.RANGE_OVERFLOW the split-product network's fp16-range flag)
         results(out) turns it into tick()'s return value.  `points` is the fixed-capacity payload all_gather_keypoints carries
-        (tick_sharded)."""
-        self._check_device_tick(frames)
+        (tick_sharded).  first_pair: the rig-wide index of the frames' first pair (a rig: pair p of the frames is calibrated as the
+        rig's pair first_pair + p; a single calibration: no effect)."""
+        first_pair = self._check_device_tick(frames, first_pair)
         with torch.no_grad():
             # split-product networks: the fp16-range flag is folded into `overflow` on the device instead of being read here (as
             # BatchedKeypointPipeline.forward_device does), except with on_overflow = "float32", where the pass is judged on the host
@@ -916,29 +954,33 @@ class StereoStreamPipeline:
             if heat_override is not None:
                 heat = heat_override
             count, _, xyc = ops.peak_nms(heat, cap=self.capacity)
-            match, overflow = ops.stereo_match(self.cam_l, self.cam_r, self.stereo.F, count, xyc, self.assoc.max_distance, range_flag=range_flag)
-            points = ops.stereo_triangulate(self.cam_l, self.cam_r, self.stereo.T_RL, count, xyc, match, F=self.stereo.F)
+            table = self._table(frames.device)                 # (a single calibration: the one-entry table, broadcast to every pair)
+            match, overflow = ops.stereo_match_rig(table, count, xyc, self.assoc.max_distance, first_pair=first_pair, range_flag=range_flag)
+            points = ops.stereo_triangulate_rig(table, count, xyc, match, first_pair=first_pair)
         return {"heat": heat, "depth": depth, "count": count, "xyc": xyc, "match": match, "points": points, "overflow": overflow}
 
-    def capture_device(self, frames, heat_override=None):
+    def capture_device(self, frames, heat_override=None, first_pair=0):
         """Capture the WHOLE tick_device (network, NMS, association, triangulation, overflow word) for this frame shape into one hipGraph;
         that the capture succeeds is itself the check that nothing in the tick waits on the host.  Returns a CapturedTick: replay with
         step.replay(new_frames[, new_heat]) or by copying into step.static_in / step.static_heat (heat_override, when given, is a static
-        input of the graph like the frames) and step.replay(); the outputs are step.static_out (tick_device's dict)."""
-        self._check_device_tick(frames)
+        input of the graph like the frames) and step.replay(); the outputs are step.static_out (tick_device's dict).  first_pair: as for
+        tick_device; the warm-up ticks upload the calibration table before the capture begins."""
+        first_pair = self._check_device_tick(frames, first_pair)
         static_in = frames.clone()
         static_heat = heat_override.clone() if heat_override is not None else None
-        for _ in range(2):                                   # warm-up: plans, allocator pools, kernel attributes
-            self.tick_device(static_in, heat_override=static_heat)
+        for _ in range(2):                                   # warm-up: plans, allocator pools, kernel attributes, calibration table
+            self.tick_device(static_in, heat_override=static_heat, first_pair=first_pair)
         torch.cuda.synchronize()
         graph = torch.cuda.CUDAGraph()
         keep, ops.SIDE_STREAMS = ops.SIDE_STREAMS, ops.SIDE_STREAMS and GRAPH_SIDE_STREAMS
         try:
             with torch.cuda.graph(graph):
-                static_out = self.tick_device(static_in, heat_override=static_heat)
+                static_out = self.tick_device(static_in, heat_override=static_heat, first_pair=first_pair)
         finally:
             ops.SIDE_STREAMS = keep
-        return CapturedTick(self.net, graph, static_in, static_out, static_heat)
+        step = CapturedTick(self.net, graph, static_in, static_out, static_heat)
+        step._table = self._table(frames.device)               # (the graph reads it on every replay)
+        return step
 
     def results(self, out):
         """A device tick (tick_device, a CapturedTick's outputs, or tick_sharded's gathered payload) as tick() returns it: a list over
@@ -969,23 +1011,26 @@ class StereoStreamPipeline:
              "overflow": 0-d int32 - the overflow words folded over the ranks on the device (one all_reduce, MAX: set on one rank = set
                          on every rank), "local": this rank's tick_device dict (None for a rank without pairs)}
         which results() reads.  A rank without pairs (world > n_pairs_total) joins both collectives with an empty block.  Without a
-        process group it is tick_device on the whole rig."""
+        process group it is tick_device on the whole rig.  A rig of individually calibrated pairs: n_pairs_total == len(rig), and each
+        rank's pairs are calibrated by their rig-wide index (first_pair = the shard's start)."""
         import torch.distributed as dist
         from .. import distributed
         if int(n_pairs_total) < 1:
             raise OkpError(f"n_pairs_total = {n_pairs_total}: a rig has at least one stereo pair")
+        if self.rig is not None and int(n_pairs_total) != len(self.rig):
+            raise OkpError(f"n_pairs_total = {n_pairs_total}, but the rig has {len(self.rig)} stereo pairs")
         self._check_device_tick(frames_local)
         if not dist.is_initialized():
             if frames_local.shape[0] != 2 * n_pairs_total:
                 raise OkpError(f"{frames_local.shape[0]} frames for {n_pairs_total} stereo pairs")
             out = self.tick_device(frames_local, heat_override=heat_override)
             return {"points": out["points"], "overflow": out["overflow"], "local": out}
-        _, n_local = distributed.shard(int(n_pairs_total), dist.get_rank(), dist.get_world_size())
+        start, n_local = distributed.shard(int(n_pairs_total), dist.get_rank(), dist.get_world_size())
         if frames_local.shape[0] != 2 * n_local:
             raise OkpError(f"rank {dist.get_rank()} holds {frames_local.shape[0]} frames; shard({n_pairs_total}, {dist.get_rank()}, "
                            f"{dist.get_world_size()}) gives it {n_local} stereo pairs = {2 * n_local} frames")
         if n_local:
-            local = self.tick_device(frames_local, heat_override=heat_override)
+            local = self.tick_device(frames_local, heat_override=heat_override, first_pair=start)
             points, flag = local["points"], local["overflow"].reshape(1).clone()
         else:
             local, dev = None, frames_local.device

@@ -194,3 +194,76 @@ def add_double_detections(scene, k, offset=(4.0, 3.0), size=64, length_scale=2.0
             centers[k - 1, 1][near] = (cy - (ys + 0.5))[near]
     heat[k] = np.clip(heat[k] + extra, 0.0, 1.0).astype(np.float32)
     return {"heat": heat, "depth": depth, "centers": centers, "objects": scene["objects"]}
+
+
+# ----------------------------------------------------------------------------
+# a synthetic rig of individually calibrated stereo pairs (StereoStreamPipeline with a sequence of StereoCameras)
+# ----------------------------------------------------------------------------
+
+RIG_BASELINES = (0.06, 0.12, 0.20, 0.30)          # metres, pair by pair
+# per pair: (fx, fy, cx, cy) factors of the left and of the right camera (cx only 1.5-2 %: PinholeCamera's centring check of the crop),
+# a factor on the distortion coefficients, and a relative rotation of the right camera (axis, degrees)
+_RIG_PAIRS = (
+    ((1.00, 1.00, 1.00, 1.00), (1.00, 1.00, 1.00, 1.00), 1.00, (1, 0.0)),
+    ((1.08, 1.10, 1.02, 1.06), (0.93, 0.92, 0.98, 0.94), 0.70, (1, 2.5)),
+    ((0.90, 0.88, 0.985, 0.91), (1.12, 1.14, 1.02, 1.10), 1.25, (0, -3.0)),
+    ((1.15, 1.13, 1.015, 1.12), (0.87, 0.86, 0.98, 0.89), 0.50, (2, 4.0)),
+)
+# per pair of a rig scene: 1 centre (type 0), 1 point of type 1, 3 points of type 2 (bench.py run_stream8's scene), pushed back and
+# shifted by half the baseline as the pair's baseline grows, so that every point stays inside both views' 64 x 64 maps
+RIG_SCENE = {0: [[0.00, 0.00, 0.55]], 1: [[0.12, -0.10, 0.60]], 2: [[-0.16, 0.12, 0.50], [0.14, 0.04, 0.65], [-0.12, -0.16, 0.70]]}
+
+
+def stereo_rig(params, n_pairs=4, size=64):
+    """n_pairs (<= 4) clearly different StereoCameras derived from one calibration (camera_utils.load_calibration_params): baselines
+    RIG_BASELINES, focal lengths and principal points 5-15 % apart (cx 1.5-2 %), distortion scaled by 0.5-1.25, a few degrees of relative
+    rotation; every camera resampled to the size x size prediction space of a 720 x 1280 camera (resize to 511 rows, centre crop 511,
+    scale), as the stereo tests and bench.py do."""
+    from .perception.utils import camera_utils as cu
+    offset = np.array([(511 / 720 * 1280 - 511.0) / 2.0, 0.0])
+    T0 = np.asarray(params["T_RL"], dtype=np.float64)
+    rig = []
+    for q in range(n_pairs):
+        fl, fr, dscale, (axis, deg) = _RIG_PAIRS[q]
+        cams = []
+        for K, D, f in ((params["K"], params["D"], fl), (params["Kp"], params["Dp"], fr)):
+            K = np.array(K, dtype=np.float64)
+            K[0, 0] *= f[0]; K[1, 1] *= f[1]; K[0, 2] *= f[2]; K[1, 2] *= f[3]
+            cam = cu.FisheyeCamera(K, np.asarray(D, dtype=np.float64) * dscale, params["image_size"])
+            cams.append(cam.scale(511 / 720).cut(offset).scale(size / 511))
+        a = np.deg2rad(deg)
+        c, s = np.cos(a), np.sin(a)
+        i, j = [(1, 2), (0, 2), (0, 1)][axis]
+        R = np.eye(3)
+        R[i, i], R[i, j], R[j, i], R[j, j] = c, -s, s, c
+        T = np.eye(4)
+        T[:3, :3] = R @ T0[:3, :3]
+        T[:3, 3] = T0[:3, 3] / np.linalg.norm(T0[:3, 3]) * RIG_BASELINES[q]
+        rig.append(cu.StereoCamera(cams[0], cams[1], T))
+    return rig
+
+
+def rig_scene_points(q, shift=0.0):
+    """{type: (n, 3) points in pair q's left camera frame} of the rig scene."""
+    b = RIG_BASELINES[q]
+    depth = max(1.0, b / RIG_BASELINES[0]) ** 0.5
+    return {k: np.array(pts) * depth + np.array([b / 2 + shift, 0.0, 0.0]) for k, pts in RIG_SCENE.items()}
+
+
+def render_rig_heat(rig, pairs=None, shift=0.0, crowd=None, size=64):
+    """Heat maps [2 len(pairs), K, size, size] float32 (NumPy) of the rig scene: pair q's points rendered through pair q's OWN left and
+    right camera (Gaussian bumps exp(-d^2 / 4), clipped to [0, 1]).  crowd = (pair q, side, type): twelve extra bumps in that map."""
+    pairs = list(range(len(rig))) if pairs is None else list(pairs)
+    ys, xs = np.meshgrid(np.arange(size, dtype=np.float32), np.arange(size, dtype=np.float32), indexing="ij")
+    heat = np.zeros((2 * len(pairs), len(RIG_SCENE), size, size), np.float32)
+    for i, q in enumerate(pairs):
+        st = rig[q]
+        for k, X in rig_scene_points(q, shift).items():
+            for side, (cam, T) in enumerate(((st.left_camera, np.eye(4)), (st.right_camera, st.T_RL))):
+                for px, py in cam.project(X, T):
+                    heat[2 * i + side, k] += np.exp(-((xs - px) ** 2 + (ys - py) ** 2) / 4.0)
+        if crowd is not None and crowd[0] == q:
+            for a in range(4):
+                for c in range(3):
+                    heat[2 * i + crowd[1], crowd[2]] += np.exp(-((xs - 8 - 12 * a) ** 2 + (ys - 50 - 5 * c) ** 2) / 2.0)
+    return np.clip(heat, 0.0, 1.0)
