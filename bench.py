@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the keypoint-inference hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
 
 N > 1 without a torchrun environment: this process never touches the GPU; it starts
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...` as a child (one rank
@@ -18,8 +18,11 @@ injected Gaussian-bump scenes (`synth.bump_scene`, 1-2 objects
 frame); the network itself runs in full on the frames in every step.
 
 Prints ONE JSON line (rank 0).  `roofline` = the dominant kernel (the patch-resident 3x3 implicit-GEMM kernel), timed
-live with HIP events on the launch stream during the timed steps; `cpu_baseline` = the oracle (torch-CPU fp32
-restatement + NumPy post-processing) on the host cores, N=1 only, bounded sample.  At N=1 the line also carries `f32mix`,
+live with HIP events on the launch stream during the timed steps.  A plain run does only what the headline needs: it sets up,
+warms up, times the steps, writes --dump-outputs and prints the line (`collective` and `power` null).  All else described below -
+the objects of other precisions and workloads, the CPU baseline, parity with the oracle, the probes after the timed region - is
+measured with `--full` only (the --no-* options and --extra-dtypes select among them there).  `cpu_baseline` = the oracle (torch-CPU fp32
+restatement + NumPy post-processing) on the host cores, N=1 only, bounded sample.  At N=1 a --full line also carries `f32mix`,
 `f32x3`, `fp32` (BASELINE configs[1] precision) and `fp16` (configs[4] precision) objects, each {value, ms_per_step, roofline,
 collective, heat_err_vs_oracle, depth_err_vs_oracle, peak_jaccard, p_C_err_m, meets}: every north_star tolerance of that
 precision measured on the cpu_baseline's frames against the oracle (parity_fields).  `collective` describes the one
@@ -29,7 +32,8 @@ while the step runs back to back AFTER the timed region, and the dominant kernel
 (the same instructions at different power: the kernel runs at the board's power limit); `--no-probes` skips these
 after-the-fact probes (the profiling passes of scripts/profile_all.sh use it: their per-kernel averages then hold the timed steps only).
 `--workload cups512` = BASELINE configs[3] (config/cups.json: K = 4 maps, four objects per frame, 64 frames per GPU, the all-gather
-payload [64 N, 4, cap, 4]); the default N = 1 line carries one rank's share of it as the `cups64` object.
+payload [64 N, 4, cap, 4]); a --full N = 1 line carries one rank's share of it as the `cups64` object.  `--workload stream8` prints
+only the configs[4] object (`stream8`, run_stream8), with or without --full.
 `--dump-outputs DIR` writes what the headline's last timed step returned - the network's heat / depth / centre maps and every output of
 the post-processing (peaks, 3D points, objects, the overflow word; of the NaN-padded points and k-means centres the entries in use) - as
 DIR/<name>.npy in float32 / float64, at most 64 MB (dump_outputs); N > 1: rank 0's share.
@@ -61,22 +65,36 @@ def parse(argv=None):
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=64, help="frames per GPU per step")
     ap.add_argument("--dtype", choices=["bf16", "f16", "f32", "f32x3", "f32mix"], default="bf16", help="precision of the headline line")
-    ap.add_argument("--extra-dtypes", default="f32mix,f32x3,f32,f16", help="N=1: further precisions reported as extra objects ('' = none)")
+    ap.add_argument("--extra-dtypes", default="f32mix,f32x3,f32,f16", help="--full, N=1: further precisions reported as extra objects ('' = none)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--spawn", action="store_true", help="go through the launcher even for --gpus 1 (tests)")
     ap.add_argument("--workload", choices=["batch64", "cups512", "stream8"], default="batch64",
                     help="cups512: BASELINE configs[3] (K = 4, config/cups.json, four objects per frame) as the headline, at any N; "
-                         "stream8: print only the BASELINE configs[4] object (the default run carries both as `cups64` / `stream8` next to the headline)")
-    ap.add_argument("--no-stream8", action="store_true", help="N=1: skip the configs[4] object")
-    ap.add_argument("--no-cups", action="store_true", help="N=1: skip the configs[3] object (`cups64`)")
-    ap.add_argument("--no-host-fed", action="store_true", help="N=1: skip the `host_fed` object (the batch-64 step with its frames starting in pinned host memory)")
-    ap.add_argument("--no-probes", action="store_true", help="skip the power / operand / collective probes behind the timed region (profiling passes)")
+                         "stream8: print only the BASELINE configs[4] object (a --full run carries both as `cups64` / `stream8` next to the headline)")
+    ap.add_argument("--no-stream8", action="store_true", help="--full, N=1: skip the configs[4] object")
+    ap.add_argument("--no-cups", action="store_true", help="--full, N=1: skip the configs[3] object (`cups64`)")
+    ap.add_argument("--no-host-fed", action="store_true", help="--full, N=1: skip the `host_fed` object (the batch-64 step with its frames starting in pinned host memory)")
+    ap.add_argument("--no-probes", action="store_true", help="--full: skip the power / operand / collective probes behind the timed region (profiling passes)")
     ap.add_argument("--dump-outputs", metavar="DIR", help="write what the headline's last timed step returned as DIR/<name>.npy (rank 0)")
+    ap.add_argument("--full", action="store_true", help="measure everything besides the headline too: the extra precisions, cups64, stream8, "
+                                                       "host_fed, CPU baseline, parity with the oracle and the probes (a plain run times the headline only)")
     args = ap.parse_args(argv)
     if args.dump_outputs and args.workload == "stream8":
         ap.error("--dump-outputs needs a batch workload (the headline): --workload stream8 has none")
     return args
+
+
+def extras(args, world, rank=0):
+    """What a run of a batch workload measures besides its headline on this rank: nothing without --full; with it, what the --no-*
+    options and --extra-dtypes leave on (the extra objects and the probes at N = 1 only, the all-gather timing at every N)."""
+    full = args.full
+    one = full and world == 1
+    batch64 = one and args.workload == "batch64"
+    return {"extra_dtypes": [d for d in args.extra_dtypes.split(",") if d and d != args.dtype] if batch64 else [],
+            "cups": batch64 and not args.no_cups, "stream8": batch64 and not args.no_stream8, "host_fed": batch64 and not args.no_host_fed,
+            "cpu_baseline": one and rank == 0 and not args.no_cpu_baseline,
+            "probes": one and not args.no_probes, "collective": full}
 
 
 # --------------------------------------------------------------------------------------------------
@@ -472,8 +490,8 @@ def run_precision(name, ctx, steps, warmup, workload="batch64", dump_dir=None):
             cnt, yx, xyc = ops.peak_nms(h, cap=SAMPLE_CAP)
             pts = ops.lift_peaks(pipe.cam, cnt, xyc, d, int(pipe.max_index[0]), int(pipe.max_index[1]))
             sample = {k: v.cpu().numpy() for k, v in (("heat", h), ("depth", d), ("count", cnt), ("yx", yx), ("points", pts))}
-        probes = world == 1 and not ctx.get("no_probes", False)
-        coll = collective_probe(out["points"], batch, world, dev, own_group=probes and ctx.get("probe_collective", False)) if (probes or world > 1) else None
+        probes = ctx["probes"]                    # (extras(): --full, N = 1, not --no-probes)
+        coll = collective_probe(out["points"], batch, world, dev, own_group=probes and ctx.get("probe_collective", False)) if (probes or (world > 1 and ctx["collective"])) else None
         power = power_probe(step) if probes and ctx.get("probe_power", False) else None
         if power is not None and name in ("bf16", "f16"):
             power["dominant_kernel_alone"] = operand_probe(dtype, dev)
@@ -984,9 +1002,10 @@ def rank_main(args):
     # the timed steps do not re-run ONE resident batch: a 64-frame batch is 201 MB, less than the 256 MB of Infinity Cache, so a batch that is
     # read again every 5 ms could be served from there.  FRAME_BATCHES different batches (seeded per batch) are walked round robin.
     pool = [frames] + [torch.randn((args.batch, 3, 511, 511), generator=gen, device=dev, dtype=torch.float32) for _ in range(FRAME_BATCHES - 1)]
-    with_cpu = rank == 0 and world == 1 and not args.no_cpu_baseline
+    ex = extras(args, world, rank)
+    with_cpu = ex["cpu_baseline"]
     ctx = {"dev": dev, "world": world, "batch": args.batch, "camera": camera, "frames": frames, "frames_pool": pool, "probe_collective": True, "probe_power": True,
-           "no_probes": args.no_probes, "start": start, "bumps": {},
+           "probes": ex["probes"], "collective": ex["collective"], "start": start, "bumps": {},
            "err_frames": torch.from_numpy(synth.frames(ERR_FRAMES, seed=1)).to(dev) if with_cpu else None}
 
     if args.workload == "stream8":
@@ -1011,26 +1030,25 @@ def rank_main(args):
     }
     extra_heat = {}
     cups_heat = None
-    if world == 1 and workload == "batch64":
-        for name in [d for d in args.extra_dtypes.split(",") if d and d != args.dtype]:
-            # fp32 runs ~12x longer per step (157 TFLOP/s MFMA peak): fewer steps keep the default run within minutes
-            # (with the driver's --steps 20 every precision still times at least 10 steps)
-            steps = max(10, args.steps // 10) if name == "f32" else max(10, args.steps // (4 if name in ("f32x3", "f32mix") else 2))
-            res, extra_heat[name] = run_precision(name, ctx, steps, min(args.warmup, 2))
-            res["workload"] = workload_string(args.batch, name, world)
-            res.pop("power", None)               # (probed once, on the headline precision)
-            result[OBJECT_KEY[name]] = res
-        if not args.no_cups:
-            # BASELINE configs[3], one rank's share (64 frames of the 512): the workload a `--workload cups512 --gpus 8` run weak-scales
-            ctx["probe_collective"] = True       # its payload ([64, 4, cap, 4]) through a one-rank RCCL group of its own
-            res, cups_heat = run_precision(args.dtype, ctx, max(10, args.steps // 2), min(args.warmup, 2), "cups512")
-            res["workload"] = workload_string(args.batch, args.dtype, world, "cups512")
-            res["dtype"] = args.dtype
-            res.pop("power", None)
-            result["cups64"] = res
-    if world == 1 and not args.no_stream8 and workload == "batch64":
+    for name in ex["extra_dtypes"]:
+        # fp32 runs ~12x longer per step (157 TFLOP/s MFMA peak): fewer steps keep a --full run within minutes
+        # (with the driver's --steps 20 every precision still times at least 10 steps)
+        steps = max(10, args.steps // 10) if name == "f32" else max(10, args.steps // (4 if name in ("f32x3", "f32mix") else 2))
+        res, extra_heat[name] = run_precision(name, ctx, steps, min(args.warmup, 2))
+        res["workload"] = workload_string(args.batch, name, world)
+        res.pop("power", None)               # (probed once, on the headline precision)
+        result[OBJECT_KEY[name]] = res
+    if ex["cups"]:
+        # BASELINE configs[3], one rank's share (64 frames of the 512): the workload a `--workload cups512 --gpus 8` run weak-scales
+        ctx["probe_collective"] = True       # its payload ([64, 4, cap, 4]) through a one-rank RCCL group of its own
+        res, cups_heat = run_precision(args.dtype, ctx, max(10, args.steps // 2), min(args.warmup, 2), "cups512")
+        res["workload"] = workload_string(args.batch, args.dtype, world, "cups512")
+        res["dtype"] = args.dtype
+        res.pop("power", None)
+        result["cups64"] = res
+    if ex["stream8"]:
         result["stream8"] = run_stream8(ctx)
-    if world == 1 and not args.no_host_fed and workload == "batch64":
+    if ex["host_fed"]:
         result["host_fed"] = run_host_fed(ctx, args.dtype if args.dtype in ("bf16", "f16") else "bf16")
     if with_cpu:
         cal = os.path.join(REPO, "config", "calibration.yaml")

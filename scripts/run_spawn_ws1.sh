@@ -8,7 +8,7 @@ tag=$1
 out=$GRAFT_REPO_ROOT/gpurun_out/$tag
 mkdir -p $out
 cd $GRAFT_REPO_ROOT
-NCCL_DEBUG=VERSION timeout 600 python3 bench.py --gpus 1 --spawn --steps 20 --warmup 5 --no-cpu-baseline --no-stream8 --extra-dtypes= > $out/bench_spawn_ws1.json 2> $out/bench_spawn_ws1.err
+NCCL_DEBUG=VERSION timeout 600 python3 bench.py --gpus 1 --spawn --steps 20 --warmup 5 --full --no-cpu-baseline --no-stream8 --extra-dtypes= > $out/bench_spawn_ws1.json 2> $out/bench_spawn_ws1.err
 echo "rc=$?" | tee -a $out/bench_spawn_ws1.err
 cut -c1-400 $out/bench_spawn_ws1.json
 grep -i -m3 "rccl\|nccl version" $out/bench_spawn_ws1.err

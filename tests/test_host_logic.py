@@ -264,6 +264,33 @@ def test_bench_launcher_starts_ranks_and_relays_one_json_line():
     assert bench.self_launch(args3, argv3, device_count=7, popen=FakeProc, out=io.StringIO(), err=err) == 2 and "needs 8 devices, 7 visible" in err.getvalue() and not seen
 
 
+def test_bench_plain_run_measures_the_headline_only():
+    """A plain `bench.py --gpus 1 --steps N --warmup W` times the headline and nothing else; `--full` adds every other object and probe,
+    which the --no-* options and --extra-dtypes then select among.  The launcher hands --full on to its ranks."""
+    import bench
+    nothing = {"extra_dtypes": [], "cups": False, "stream8": False, "host_fed": False, "cpu_baseline": False, "probes": False, "collective": False}
+    plain = bench.parse(["--gpus", "1", "--steps", "20", "--warmup", "5"])
+    assert not plain.full
+    for world in (1, 8):
+        assert bench.extras(plain, world) == nothing
+    assert bench.extras(bench.parse(["--workload", "cups512"]), 1) == nothing
+    assert bench.extras(bench.parse(["--dtype", "f32x3", "--no-probes"]), 1) == nothing
+
+    full = bench.parse(["--gpus", "1", "--steps", "20", "--warmup", "5", "--full"])
+    assert bench.extras(full, 1) == {"extra_dtypes": ["f32mix", "f32x3", "f32", "f16"], "cups": True, "stream8": True, "host_fed": True,
+                                     "cpu_baseline": True, "probes": True, "collective": True}
+    assert bench.extras(full, 1, rank=1)["cpu_baseline"] is False
+    assert bench.extras(bench.parse(["--full", "--dtype", "f16"]), 1)["extra_dtypes"] == ["f32mix", "f32x3", "f32"]
+    # N > 1: the all-gather is timed, the one-GPU objects and probes are not
+    assert bench.extras(bench.parse(["--gpus", "8", "--full"]), 8) == dict(nothing, collective=True)
+    # configs[3] as the headline: parity with the oracle and the probes, no objects of the batch-64 workload
+    assert bench.extras(bench.parse(["--full", "--workload", "cups512"]), 1) == dict(nothing, cpu_baseline=True, probes=True, collective=True)
+    sel = bench.extras(bench.parse(["--full", "--extra-dtypes=", "--no-cups", "--no-stream8", "--no-host-fed", "--no-cpu-baseline", "--no-probes"]), 1)
+    assert sel == dict(nothing, collective=True)
+    argv = ["--gpus", "8", "--full"]
+    assert bench.launcher_command(bench.parse(argv), argv, 29513)[-3:] == argv
+
+
 def test_launcher_counts_gpus_without_the_hip_runtime(tmp_path):
     """The launcher parent must not initialise the GPU before it starts torchrun: devices are counted from the KFD topology
     (nodes with SIMDs), with /dev/dri/renderD* as fall-back and the *_VISIBLE_DEVICES lists as caps."""
