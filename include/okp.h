@@ -35,7 +35,8 @@ extern "C" {
                                     okp_capacity_overflow, okp_cast and okp_add_f16_f32; views of 2 GiB and more as the output of an OKP_F32X3
                                     stem and as sources of OKP_F32X3 plans on the patch-resident kernel
                                  additions at 7 (new entry points only; no struct or existing signature changed): okp_stereo_match,
-                                    okp_stereo_triangulate; the struct okp_stereo_pair, okp_stereo_match_rig, okp_stereo_triangulate_rig */
+                                    okp_stereo_triangulate; the struct okp_stereo_pair, okp_stereo_match_rig, okp_stereo_triangulate_rig;
+                                    OKP_YUV_I420 / OKP_YUV_NV12 / OKP_YUV_BT601 / OKP_YUV_BT709, okp_preprocess_yuv420 */
 
 /* OKP_F16: IEEE half activations / weights, fp32 accumulate (BASELINE configs[4]).
  * OKP_F32X3 (okp_conv plans only): fp32 activations, weights and results like OKP_F32 - every tensor argument of such a plan is an
@@ -269,6 +270,29 @@ int okp_pack_frames_u8(int dtype, const uint8_t* frames_nhwc_dev, int32_t n, int
 int okp_preprocess_u8(int dtype, const uint8_t* frames_nhwc_dev, int32_t n, int32_t src_h, int32_t src_w,
                       int32_t resized_h, int32_t resized_w, int32_t crop_y, int32_t crop_x, int32_t h, int32_t w,
                       const float* mean3, const float* std3, void* out_dev, int32_t out_w, void* stream);
+
+/* The same pre-processing from 4:2:0 YUV decoder output (the reference decodes H.264 video, whose frames are 4:2:0, and has
+ * ffmpeg convert them to RGB on the host: perception/datasets/video.py:178).  One frame is 3*src_h/2 rows of src_pitch bytes
+ * (src_h, src_w even; src_pitch even and >= src_w), frames 3*src_h/2*src_pitch bytes apart:
+ *   OKP_YUV_NV12  Y: src_h rows, then src_h/2 rows of interleaved U,V pairs (hardware decoders)
+ *   OKP_YUV_I420  Y: src_h rows, then U: src_h/2 rows of src_pitch/2 bytes, packed, then V alike (yuv420p, software H.264)
+ * Pixel (y, x) takes chroma sample (y >> 1, x >> 1) (nearest, no interpolation) and converts in integers, int32 arithmetic shift:
+ *   c = max(0, Y - y0), u = U - 128, v = V - 128      y0 = 16 (limited range, full_range = 0) or 0 (full range)
+ *   R = clamp8((CY*c + 2^19 + CVR*v) >> 20)   G = clamp8((CY*c + 2^19 + CVG*v + CUG*u) >> 20)   B = clamp8((CY*c + 2^19 + CUB*u) >> 20)
+ * with each constant round(k * 2^20):          CY          CVR          CUG          CVG          CUB
+ *   OKP_YUV_BT601, limited                  1.164        1.596       -0.391       -0.813        2.018
+ *   OKP_YUV_BT709, limited                  1.164        1.793       -0.213       -0.533        2.112
+ *   OKP_YUV_BT601, full (JPEG)              1.0          1.402       -0.344       -0.714        1.772
+ *   OKP_YUV_BT709, full                     1.0          1.575       -0.187       -0.468        1.856
+ * Each tap of the bilinear resize converts its own sample: the output equals okp_preprocess_u8 of the converted frames, bit for
+ * bit.  The conversion is its own specification: parity with OpenCV's cvtColor (YUV2RGB_NV12 / _I420, believed to be the BT.601
+ * limited row) and with ffmpeg's swscale is not pinned. */
+enum { OKP_YUV_I420 = 0, OKP_YUV_NV12 = 1 };
+enum { OKP_YUV_BT601 = 0, OKP_YUV_BT709 = 1 };
+int okp_preprocess_yuv420(int dtype, const uint8_t* frames_dev, int32_t n, int32_t src_h, int32_t src_w, int32_t src_pitch,
+                          int32_t layout, int32_t matrix, int32_t full_range, int32_t resized_h, int32_t resized_w,
+                          int32_t crop_y, int32_t crop_x, int32_t h, int32_t w, const float* mean3, const float* std3,
+                          void* out_dev, int32_t out_w, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * The 7x7 / stride-2 / pad-3 stem convolution 3 -> 128 + folded BatchNorm + ReLU in bf16 as its own kernel

@@ -13,6 +13,8 @@ LIB_PATH = os.environ.get("OKP_LIB") or os.path.join(os.path.dirname(os.path.abs
 OKP_F32, OKP_BF16, OKP_F16, OKP_F32X3 = 0, 1, 2, 3
 OKP_ABI = 7
 CAM_EQUIDISTANT, CAM_RADTAN = 0, 1
+YUV_I420, YUV_NV12 = 0, 1
+YUV_BT601, YUV_BT709 = 0, 1
 ACT_NONE, ACT_RELU, ACT_SIGMOID = 0, 1, 2
 HEAD_MAX_OUT = 32
 
@@ -84,6 +86,8 @@ SIGNATURES = [
     ("okp_pack_frames_u8", c_int, [c_int, c_void_p, c_int32, c_int32, c_int32, POINTER(c_float), POINTER(c_float), c_void_p, c_int32, c_void_p]),
     ("okp_preprocess_u8", c_int, [c_int, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
                                   POINTER(c_float), POINTER(c_float), c_void_p, c_int32, c_void_p]),
+    ("okp_preprocess_yuv420", c_int, [c_int, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
+                                      c_int32, c_int32, c_int32, POINTER(c_float), POINTER(c_float), c_void_p, c_int32, c_void_p]),
     ("okp_stem_create", c_void_p, [POINTER(c_float), POINTER(c_float)]),
     ("okp_stem_create_dtype", c_void_p, [c_int, POINTER(c_float), POINTER(c_float)]),
     ("okp_stem_destroy", None, [c_void_p]),

@@ -241,6 +241,17 @@ __device__ __forceinline__ void resize_coeff(int d, double scale, int ssize, int
   w1 = __float2int_rn(__fmul_rn(f, 2048.f));
 }
 
+// the vertical pass of the fixed-point resize on two horizontal results (rows sy0, sy1), saturated to 8 bits
+__device__ __forceinline__ int resize_vertical(int h0, int h1, int b0, int b1) {
+  const int u = (((b0 * (h0 >> 4)) >> 16) + ((b1 * (h1 >> 4)) >> 16) + 2) >> 2;
+  return u < 0 ? 0 : (u > 255 ? 255 : u);
+}
+
+// (u8 / 255 - mean) / std, one IEEE rounding per operation as NumPy float32 does
+__device__ __forceinline__ float normalise_u8(int u8, const NormParams& np, int c) {
+  return __fdiv_rn(__fsub_rn(__fdiv_rn((float)u8, 255.0f), np.mean[c]), np.stdv[c]);
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void okp_preprocess_u8_kernel(const uint8_t* __restrict__ in, int N, ResizeParams rp,
                                                                  T* __restrict__ out, int OHt, int OWt) {
@@ -262,9 +273,84 @@ __global__ __launch_bounds__(256) void okp_preprocess_u8_kernel(const uint8_t* _
       for (int c = 0; c < 3; ++c) {
         const int h0 = (int)r0[sx0 * 3 + c] * a0 + (int)r0[sx1 * 3 + c] * a1;
         const int h1 = (int)r1[sx0 * 3 + c] * a0 + (int)r1[sx1 * 3 + c] * a1;
-        const int u = (((b0 * (h0 >> 4)) >> 16) + ((b1 * (h1 >> 4)) >> 16) + 2) >> 2;
-        const int u8 = u < 0 ? 0 : (u > 255 ? 255 : u);
-        v[c] = __fdiv_rn(__fsub_rn(__fdiv_rn((float)u8, 255.0f), rp.np.mean[c]), rp.np.stdv[c]);
+        v[c] = normalise_u8(resize_vertical(h0, h1, b0, b1), rp.np, c);
+      }
+    }
+    T* o = out + idx * 4;
+    o[0] = (T)v[0]; o[1] = (T)v[1]; o[2] = (T)v[2]; o[3] = (T)0.f;
+  }
+}
+
+// ---- the same pre-processing from 4:2:0 YUV decoder output (NV12 / I420) -------------------------------------------------------
+// A frame is 3H/2 rows of `pitch` bytes: Y (H rows), then NV12: H/2 rows of interleaved U,V; I420: U (H/2 rows of pitch/2 bytes, packed),
+// then V alike.  Chroma is taken at the nearest sample (y >> 1, x >> 1).  Integer conversion (include/okp.h, okp_preprocess_yuv420):
+//   c = max(0, Y - y0), u = U - 128, v = V - 128;  R = clamp8((CY*c + 2^19 + CVR*v) >> 20), G = ... CVG*v + CUG*u, B = ... CUB*u.
+// Every tap of the bilinear resize converts its own sample, so the result equals converting the whole frame and running
+// okp_preprocess_u8 on it, bit for bit.  All terms stay below 2^31: |CY*c| < 2^29, each chroma term < 2^29.
+struct YuvParams {
+  int32_t pitch, y0;
+  int32_t cy, cvr, cug, cvg, cub;       // coefficients * 2^20
+  size_t frame_bytes;                   // 3H/2 * pitch
+};
+
+__device__ __forceinline__ int clamp8(int x) { return x < 0 ? 0 : (x > 255 ? 255 : x); }
+
+// one source row's samples: Y, and the chroma row of (y >> 1) (NV12: the interleaved U,V row; I420: the U and V rows)
+struct YuvRow { const uint8_t* y; const uint8_t* u; const uint8_t* v; };
+
+template <int LAYOUT>
+__device__ __forceinline__ YuvRow yuv_row(const uint8_t* __restrict__ f, int H, const YuvParams& yp, int y) {
+  const uint8_t* chroma = f + (size_t)H * yp.pitch;
+  YuvRow r;
+  r.y = f + (size_t)y * yp.pitch;
+  if constexpr (LAYOUT == OKP_YUV_NV12) {
+    r.u = chroma + (size_t)(y >> 1) * yp.pitch;
+    r.v = r.u + 1;
+  } else {
+    const size_t cw = (size_t)(yp.pitch >> 1);
+    r.u = chroma + (size_t)(y >> 1) * cw;
+    r.v = r.u + (size_t)(H >> 1) * cw;
+  }
+  return r;
+}
+
+template <int LAYOUT>
+__device__ __forceinline__ void yuv_tap(const YuvRow& r, const YuvParams& yp, int x, int (&rgb)[3]) {
+  const int cx = LAYOUT == OKP_YUV_NV12 ? (x & ~1) : (x >> 1);
+  const int c = max((int)r.y[x] - yp.y0, 0) * yp.cy + (1 << 19);
+  const int u = (int)r.u[cx] - 128, v = (int)r.v[cx] - 128;
+  rgb[0] = clamp8((c + yp.cvr * v) >> 20);
+  rgb[1] = clamp8((c + yp.cvg * v + yp.cug * u) >> 20);
+  rgb[2] = clamp8((c + yp.cub * u) >> 20);
+}
+
+template <typename T, int LAYOUT>
+__global__ __launch_bounds__(256) void okp_preprocess_yuv420_kernel(const uint8_t* __restrict__ in, int N, ResizeParams rp, YuvParams yp,
+                                                                     T* __restrict__ out, int OHt, int OWt) {
+  const long total = (long)N * OHt * OWt;
+  for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
+    const int x = (int)(idx % OWt);
+    const long t = idx / OWt;
+    const int y = (int)(t % OHt);
+    const int n = (int)(t / OHt);
+    const int cy = y - 3, cx = x - 3;               // position inside the cropped frame
+    float v[3] = {0.f, 0.f, 0.f};
+    if (cy >= 0 && cy < rp.H && cx >= 0 && cx < rp.W) {
+      int sy0, sy1, b0, b1, sx0, sx1, a0, a1;
+      resize_coeff(cy + rp.cropY, rp.scaleY, rp.srcH, sy0, sy1, b0, b1);
+      resize_coeff(cx + rp.cropX, rp.scaleX, rp.srcW, sx0, sx1, a0, a1);
+      const uint8_t* f = in + (size_t)n * yp.frame_bytes;
+      const YuvRow r0 = yuv_row<LAYOUT>(f, rp.srcH, yp, sy0), r1 = yuv_row<LAYOUT>(f, rp.srcH, yp, sy1);
+      int p00[3], p01[3], p10[3], p11[3];
+      yuv_tap<LAYOUT>(r0, yp, sx0, p00);
+      yuv_tap<LAYOUT>(r0, yp, sx1, p01);
+      yuv_tap<LAYOUT>(r1, yp, sx0, p10);
+      yuv_tap<LAYOUT>(r1, yp, sx1, p11);
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const int h0 = p00[c] * a0 + p01[c] * a1;
+        const int h1 = p10[c] * a0 + p11[c] * a1;
+        v[c] = normalise_u8(resize_vertical(h0, h1, b0, b1), rp.np, c);
       }
     }
     T* o = out + idx * 4;
@@ -488,6 +574,62 @@ extern "C" int okp_preprocess_u8(int dtype, const uint8_t* frames, int32_t n, in
   else if (dtype == OKP_F16) hipLaunchKernelGGL(okp_preprocess_u8_kernel<_Float16>, dim3(grid), dim3(256), 0, (hipStream_t)stream, frames, n, rp, (_Float16*)out, h + 6, out_w);
   else hipLaunchKernelGGL(okp_preprocess_u8_kernel<float>, dim3(grid), dim3(256), 0, (hipStream_t)stream, frames, n, rp, (float*)out, h + 6, out_w);
   return okp_check_hip(hipGetLastError(), "okp_preprocess_u8 launch");
+}
+
+namespace {
+// the coefficients of include/okp.h (okp_preprocess_yuv420): round(k * 2^20) of CY, CVR, CUG, CVG, CUB; [matrix][full_range]
+constexpr int32_t kYuvCoeffs[2][2][5] = {
+    {{1220542, 1673527, -409993, -852492, 2116026}, {1048576, 1470104, -360710, -748683, 1858077}},    // BT.601 limited, full
+    {{1220542, 1880097, -223347, -558891, 2214593}, {1048576, 1651507, -196084, -490734, 1946157}},    // BT.709 limited, full
+};
+
+template <typename T>
+void launch_yuv420(int layout, int grid, hipStream_t stream, const uint8_t* frames, int n, const ResizeParams& rp, const YuvParams& yp, void* out,
+                   int OHt, int OWt) {
+  if (layout == OKP_YUV_NV12)
+    hipLaunchKernelGGL((okp_preprocess_yuv420_kernel<T, OKP_YUV_NV12>), dim3(grid), dim3(256), 0, stream, frames, n, rp, yp, (T*)out, OHt, OWt);
+  else
+    hipLaunchKernelGGL((okp_preprocess_yuv420_kernel<T, OKP_YUV_I420>), dim3(grid), dim3(256), 0, stream, frames, n, rp, yp, (T*)out, OHt, OWt);
+}
+}  // namespace
+
+extern "C" int okp_preprocess_yuv420(int dtype, const uint8_t* frames, int32_t n, int32_t src_h, int32_t src_w, int32_t src_pitch, int32_t layout,
+                                     int32_t matrix, int32_t full_range, int32_t resized_h, int32_t resized_w, int32_t crop_y, int32_t crop_x,
+                                     int32_t h, int32_t w, const float* mean3, const float* std3, void* out, int32_t out_w, void* stream) {
+  if (!frames || !out || !mean3 || !std3) { okp_set_error("okp_preprocess_yuv420: null argument"); return OKP_EINVAL; }
+  if (dtype != OKP_F32 && !okp_is16(dtype)) { okp_set_error("okp_preprocess_yuv420: bad dtype %d", dtype); return OKP_EINVAL; }
+  if (n < 1 || src_h < 2 || src_w < 2 || (src_h & 1) || (src_w & 1)) {
+    okp_set_error("okp_preprocess_yuv420: %d frames of %dx%d: 4:2:0 frames have an even height and width", n, src_h, src_w);
+    return OKP_EINVAL;
+  }
+  if (src_pitch < src_w || (src_pitch & 1)) {
+    okp_set_error("okp_preprocess_yuv420: pitch %d: an even number of bytes, at least the width %d", src_pitch, src_w);
+    return OKP_EINVAL;
+  }
+  if (layout != OKP_YUV_I420 && layout != OKP_YUV_NV12) { okp_set_error("okp_preprocess_yuv420: unknown layout %d", layout); return OKP_EINVAL; }
+  if (matrix != OKP_YUV_BT601 && matrix != OKP_YUV_BT709) { okp_set_error("okp_preprocess_yuv420: unknown matrix %d", matrix); return OKP_EINVAL; }
+  if (full_range != 0 && full_range != 1) { okp_set_error("okp_preprocess_yuv420: full_range %d is 0 or 1", full_range); return OKP_EINVAL; }
+  if (resized_h < 1 || resized_w < 1 || h < 1 || w < 1 || crop_y < 0 || crop_x < 0 || crop_y + h > resized_h || crop_x + w > resized_w) {
+    okp_set_error("okp_preprocess_yuv420: crop %dx%d at (%d,%d) does not fit the resized frame %dx%d", h, w, crop_y, crop_x, resized_h, resized_w);
+    return OKP_EINVAL;
+  }
+  if (out_w < w + 6) { okp_set_error("okp_preprocess_yuv420: out_w %d < w+6", out_w); return OKP_EINVAL; }
+  ResizeParams rp;
+  rp.srcH = src_h; rp.srcW = src_w; rp.rsH = resized_h; rp.rsW = resized_w; rp.cropY = crop_y; rp.cropX = crop_x; rp.H = h; rp.W = w;
+  rp.scaleY = 1.0 / ((double)resized_h / (double)src_h);
+  rp.scaleX = 1.0 / ((double)resized_w / (double)src_w);
+  for (int c = 0; c < 3; ++c) { rp.np.mean[c] = mean3[c]; rp.np.stdv[c] = std3[c]; }
+  YuvParams yp;
+  const int32_t* k = kYuvCoeffs[matrix][full_range];
+  yp.pitch = src_pitch; yp.y0 = full_range ? 0 : 16;
+  yp.cy = k[0]; yp.cvr = k[1]; yp.cug = k[2]; yp.cvg = k[3]; yp.cub = k[4];
+  yp.frame_bytes = (size_t)(src_h / 2 * 3) * (size_t)src_pitch;
+  const long total = (long)n * (h + 6) * out_w;
+  const int grid = grid_for(total, 256);
+  if (dtype == OKP_BF16) launch_yuv420<__bf16>(layout, grid, (hipStream_t)stream, frames, n, rp, yp, out, h + 6, out_w);
+  else if (dtype == OKP_F16) launch_yuv420<_Float16>(layout, grid, (hipStream_t)stream, frames, n, rp, yp, out, h + 6, out_w);
+  else launch_yuv420<float>(layout, grid, (hipStream_t)stream, frames, n, rp, yp, out, h + 6, out_w);
+  return okp_check_hip(hipGetLastError(), "okp_preprocess_yuv420 launch");
 }
 
 extern "C" int okp_head_out_forward(int dtype, const okp_head_out_args* a, void* stream) {

@@ -371,6 +371,24 @@ void preprocess_u8(const Tensor& frames, int64_t resized_h, int64_t resized_w, i
            "okp_preprocess_u8");
 }
 
+// frames: uint8 [N, 3H/2, W] with stride(2) == 1, pitch = stride(1), frames stride(0) = 3H/2 * pitch bytes apart (a view [..., :W] of
+// pitched decoder surfaces needs no copy)
+void preprocess_yuv420(const Tensor& frames, int64_t layout, int64_t matrix, bool full_range, int64_t resized_h, int64_t resized_w, int64_t crop_y,
+                       int64_t crop_x, int64_t h, int64_t w, at::ArrayRef<double> mean, at::ArrayRef<double> std_, const Tensor& out, int64_t stream) {
+  TORCH_CHECK(frames.is_cuda(), "okp: frames must be a device tensor: the HIP path has no CPU fallback");
+  TORCH_CHECK(frames.scalar_type() == at::kByte && frames.dim() == 3 && frames.size(1) % 3 == 0 && frames.stride(2) == 1,
+              "okp: frames must be uint8 [N, 3H/2, W] with unit inner stride");
+  const int64_t rows = frames.size(1), pitch = frames.stride(1);
+  TORCH_CHECK(frames.size(0) == 1 || frames.stride(0) == rows * pitch, "okp: frames must be 3H/2 * pitch bytes apart (stride(0) == size(1) * stride(1))");
+  TORCH_CHECK(out.is_cuda() && out.dim() == 4 && out.is_contiguous() && out.size(0) == frames.size(0) && out.size(1) == h + 6 && out.size(3) == 4,
+              "okp: frames [N,3H/2,W] uint8 -> out [N,h+6,wp,4]");
+  float m[3], sd[3]; three(mean, m, "mean"); three(std_, sd, "std");
+  check_rc(okp_preprocess_yuv420(dtype_of(out), frames.data_ptr<uint8_t>(), (int32_t)frames.size(0), (int32_t)(rows / 3 * 2), (int32_t)frames.size(2),
+                                 (int32_t)pitch, (int32_t)layout, (int32_t)matrix, full_range ? 1 : 0, (int32_t)resized_h, (int32_t)resized_w,
+                                 (int32_t)crop_y, (int32_t)crop_x, (int32_t)h, (int32_t)w, m, sd, out.data_ptr(), (int32_t)out.size(2), sp(stream)),
+           "okp_preprocess_yuv420");
+}
+
 inline int32_t* flag_ptr(const optional<Tensor>& f) {
   if (!f.has_value()) return nullptr;
   TORCH_CHECK(f->is_cuda() && f->scalar_type() == at::kInt && f->numel() >= 1, "okp: range_flag is an int32 device tensor");
@@ -590,6 +608,8 @@ TORCH_LIBRARY(okp, m) {
   m.def("pack_frames(Tensor frames, Tensor(a!) out, int stream) -> ()", pack_frames);
   m.def("pack_frames_u8(Tensor frames, float[] mean, float[] std, Tensor(a!) out, int stream) -> ()", pack_frames_u8);
   m.def("preprocess_u8(Tensor frames, int resized_h, int resized_w, int crop_y, int crop_x, int h, int w, float[] mean, float[] std, Tensor(a!) out, int stream) -> ()", preprocess_u8);
+  m.def("preprocess_yuv420(Tensor frames, int layout, int matrix, bool full_range, int resized_h, int resized_w, int crop_y, int crop_x, int h, int w, "
+        "float[] mean, float[] std, Tensor(a!) out, int stream) -> ()", preprocess_yuv420);
   m.def("cast(Tensor src, Tensor(a!) dst, int stream, Tensor(b!)? range_flag=None) -> ()", cast);
   m.def("add_f16_f32(Tensor a, Tensor b, Tensor(a!) out, int act, int stream, Tensor(b!)? range_flag=None) -> ()", add_f16_f32);
   m.def("dwconv3x3_forward(Tensor src, int src_c0, int c, int conv_stride, Tensor w, Tensor bias, Tensor? res, int res_c0, Tensor(a!) out, int out_c0, int act, int stream) -> ()", dwconv3x3_forward);

@@ -4,6 +4,7 @@ torch is used for device memory and streams only: every computation below is a c
 libokp_hip.so on `torch.cuda.current_stream()`.  Nothing here has a CPU path.
 """
 import ctypes
+import dataclasses
 import os
 
 import numpy as np
@@ -787,6 +788,92 @@ def preprocess_u8(frames, dtype, size=511, mean=RGB_MEAN, std=RGB_STD):
     sd = (ctypes.c_float * 3)(*std)
     _lib.check(_lib.lib().okp_preprocess_u8(okp_dtype(dtype), frames.data_ptr(), n, sh, sw, rh, rw, cy, cx, size, size, m, sd,
                                             out.data_ptr(), wp, stream_handle()), "okp_preprocess_u8")
+    COUNTERS["launches"] += 1
+    act = Act(out)
+    act.orig_hw = (size, size)
+    return act
+
+
+@dataclasses.dataclass(frozen=True)
+class YUV420Format:
+    """4:2:0 decoder output (include/okp.h, okp_preprocess_yuv420): layout "nv12" (Y, then interleaved U,V rows: hardware decoders) or
+    "i420" (Y, U, V planes: yuv420p, software H.264); matrix "bt601" or "bt709"; full_range False = limited range (Y from 16)."""
+    layout: str = "nv12"
+    matrix: str = "bt601"
+    full_range: bool = False
+
+    def __post_init__(self):
+        if self.layout not in _YUV_LAYOUTS:
+            raise OkpError(f"unknown YUV layout {self.layout!r}: 'nv12' or 'i420'")
+        if self.matrix not in _YUV_MATRICES:
+            raise OkpError(f"unknown YUV matrix {self.matrix!r}: 'bt601' or 'bt709'")
+        if not isinstance(self.full_range, bool):
+            raise OkpError(f"full_range is a bool, not {self.full_range!r}")
+
+
+_YUV_LAYOUTS = {"i420": _lib.YUV_I420, "nv12": _lib.YUV_NV12}
+_YUV_MATRICES = {"bt601": _lib.YUV_BT601, "bt709": _lib.YUV_BT709}
+# (matrix, full_range) -> (CY, CVR, CUG, CVG, CUB) = round(k * 2^20) of the three-decimal coefficients (include/okp.h)
+YUV_COEFFS = {
+    ("bt601", False): (1220542, 1673527, -409993, -852492, 2116026),
+    ("bt709", False): (1220542, 1880097, -223347, -558891, 2214593),
+    ("bt601", True): (1048576, 1470104, -360710, -748683, 1858077),
+    ("bt709", True): (1048576, 1651507, -196084, -490734, 1946157),
+}
+
+
+def check_yuv420_frames(frames):
+    """Shape, dtype and stride checks of 4:2:0 frames (no device work) -> (n, H, W, pitch)."""
+    if not isinstance(frames, torch.Tensor):
+        raise OkpError("frames must be a uint8 tensor [N, 3H/2, W]")
+    if frames.dtype != torch.uint8:
+        raise OkpError(f"4:2:0 frames are uint8, not {frames.dtype}")
+    if frames.dim() != 3:
+        raise OkpError(f"4:2:0 frames are [N, 3H/2, W] (3-D), not {frames.dim()}-D: RGB frames [N,H,W,3] go through preprocess_u8")
+    n, rows, w = frames.shape
+    if rows % 3:
+        raise OkpError(f"4:2:0 frames have 3H/2 rows for an even height H: shape[1] = {rows} is not a multiple of 3")
+    h = rows // 3 * 2
+    if h % 2 or w % 2 or h < 2 or w < 2:
+        raise OkpError(f"4:2:0 frames of {h}x{w}: the height and width must be even")
+    if frames.stride(2) != 1:
+        raise OkpError(f"4:2:0 frames need a unit inner stride (stride(2) = {frames.stride(2)})")
+    pitch = frames.stride(1)
+    if pitch < w or pitch % 2:
+        raise OkpError(f"pitch (stride(1)) = {pitch}: an even number of bytes, at least the width {w}")
+    if n > 1 and frames.stride(0) != rows * pitch:
+        raise OkpError(f"frames must be 3H/2 * pitch = {rows * pitch} bytes apart, not stride(0) = {frames.stride(0)}")
+    # the kernel reads whole pitched rows of the last frame (the I420 chroma planes run to the end of a row): the storage must hold them
+    if n and frames.untyped_storage().nbytes() < frames.storage_offset() + (n - 1) * rows * pitch + rows * pitch:
+        raise OkpError("the frames' storage ends before the last frame's last pitched row")
+    return n, h, w, pitch
+
+
+def preprocess_yuv420(frames, dtype, fmt, size=511, mean=RGB_MEAN, std=RGB_STD):
+    """4:2:0 decoder output uint8 [N, 3H/2, W] (device; NV12 or I420 as `fmt`, a YUV420Format; pitch = stride(1), so a view [..., :W] of
+    pitched surfaces is taken as it is) -> the packed stem input that preprocess_u8 makes of the same frames converted to RGB, bit for bit
+    (okp_preprocess_yuv420: conversion, resize, centre crop and normalisation in one kernel)."""
+    if not isinstance(fmt, YUV420Format):
+        raise OkpError(f"fmt must be a YUV420Format, not {type(fmt).__name__}")
+    n, sh, sw, pitch = check_yuv420_frames(frames)
+    rh, rw = smallest_max_size(sh, sw, size) if size >= 1 else (0, 0)
+    if size < 1 or rh < size or rw < size:
+        raise OkpError(f"the {size}x{size} crop does not fit the resized frame {rh}x{rw}")
+    okp_dtype(dtype)
+    require_cuda(frames, "frames")
+    cy, cx = (rh - size) // 2, (rw - size) // 2
+    layout, matrix = _YUV_LAYOUTS[fmt.layout], _YUV_MATRICES[fmt.matrix]
+    wp = stem_packed_width(size)
+    out = torch.empty((n, size + 6, wp, 4), dtype=dtype, device=frames.device)
+    T = _ops()
+    if T is not None:
+        _dispatch(T.preprocess_yuv420, frames, layout, matrix, fmt.full_range, rh, rw, cy, cx, size, size, [float(np.float32(v)) for v in mean],
+                  [float(np.float32(v)) for v in std], out, stream_int())
+    else:
+        m = (ctypes.c_float * 3)(*mean)
+        sd = (ctypes.c_float * 3)(*std)
+        _lib.check(_lib.lib().okp_preprocess_yuv420(okp_dtype(dtype), frames.data_ptr(), n, sh, sw, pitch, layout, matrix, int(fmt.full_range), rh, rw,
+                                                    cy, cx, size, size, m, sd, out.data_ptr(), wp, stream_handle()), "okp_preprocess_yuv420")
     COUNTERS["launches"] += 1
     act = Act(out)
     act.orig_hw = (size, size)

@@ -89,7 +89,8 @@ class KeypointNet(_HipModule):
     branches, fp16 inner hourglass levels): heat error 4e-4 on the test networks, still inside the 1e-3 bar.
     """
 
-    def __init__(self, output_size=None, features=128, heatmaps_out=2, dropout=0.1, compute_dtype=torch.float32, range_guard=None):
+    def __init__(self, output_size=None, features=128, heatmaps_out=2, dropout=0.1, compute_dtype=torch.float32, range_guard=None,
+                 frame_format=None):
         super().__init__()
         self.backbone = hg()
         self.heatmap_head = HeatmapHead(features, heatmaps_out)
@@ -102,6 +103,10 @@ class KeypointNet(_HipModule):
         # uint8 frames of any other size are resized (shortest side) and centre-cropped to this size on the device, as the
         # reference's data path does (perception/datasets/video.py:63-69,95-96); None = uint8 frames are taken as they are
         self.raw_frame_size = 511
+        # ops.YUV420Format: a 3-D uint8 tensor [N, 3H/2, W] is taken as 4:2:0 decoder output (NV12 / I420) and converted to RGB on the
+        # device by the same pre-processing kernel (ops.preprocess_yuv420, to raw_frame_size); None = 4:2:0 frames are refused.
+        # 4-D uint8 frames are RGB either way.
+        self.frame_format = frame_format
         # Split-product configurations halve fp32 values into fp16: a value beyond +-65504 has no halves (inf, -inf -> NaN products, which the
         # next ReLU turns into 0 without a trace), where the reference's fp32 arithmetic returns numbers.  The kernels raise a device flag
         # (okp_conv_set_range_flag) whenever a value they hand on leaves that range; what a pass does about it:
@@ -245,6 +250,9 @@ class KeypointNet(_HipModule):
         # split-product configuration: the last stack's `cnv` has one reader, the heads - in pair format where its 3x3 convolution can write
         # that, the three heads are one launch (ops.heads_fused; _run_heads_ looks at Act.pairs)
         cnv_pairs = bool(ops.FUSE_HEADS_X3 and self.mfma_split and self.features == 128)      # (the mixed configuration's heads are three-term plans too)
+        if x.dtype == torch.uint8 and x.dim() == 3:      # 4:2:0 [N,3H/2,W]: colour conversion fused into the pre-processing kernel too
+            self._frame_hw(x)
+            return self.backbone(ops.preprocess_yuv420(x, self.compute_dtype, self.frame_format, size=self.raw_frame_size), cnv_pairs=cnv_pairs)
         if x.dtype == torch.uint8:      # raw RGB [N,H,W,3]: normalisation (and resize + centre crop) fused into the packing kernel
             if self.raw_frame_size is not None and tuple(x.shape[1:3]) != (self.raw_frame_size, self.raw_frame_size):
                 return self.backbone(ops.preprocess_u8(x, self.compute_dtype, size=self.raw_frame_size), cnv_pairs=cnv_pairs)
@@ -261,10 +269,22 @@ class KeypointNet(_HipModule):
         per_frame = max(h2 * w2 * 128 * 2, ((h2 + 1) // 2) * ((w2 + 1) // 2) * 256 * esz)
         return max(1, (0x7FFF0000 - 1) // per_frame)
 
-    def _chunks(self, x):
+    def _frame_hw(self, x):
+        """(H, W) of the frames the network sees: the crop for uint8 frames (raw_frame_size), the frame itself otherwise."""
+        if x.dtype == torch.uint8 and x.dim() == 3:
+            if self.frame_format is None:
+                raise OkpError("a 3-D uint8 tensor is 4:2:0 (YUV) frames [N, 3H/2, W]: set frame_format (ops.YUV420Format) to take them; "
+                               "RGB frames are [N, H, W, 3]")
+            if self.raw_frame_size is None:
+                raise OkpError("4:2:0 frames are resized and cropped to raw_frame_size: it cannot be None with frame_format set")
+            return self.raw_frame_size, self.raw_frame_size
         h, w = (x.shape[1], x.shape[2]) if x.dtype == torch.uint8 else (x.shape[2], x.shape[3])
         if x.dtype == torch.uint8 and self.raw_frame_size is not None:
             h = w = self.raw_frame_size
+        return h, w
+
+    def _chunks(self, x):
+        h, w = self._frame_hw(x)
         step = self.max_frames_per_pass(h, w)
         return [x[i:i + step] for i in range(0, x.shape[0], step)]
 

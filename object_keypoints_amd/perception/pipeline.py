@@ -185,7 +185,8 @@ def _audited(net, audit_frames, heat_bar, _source=None):
     return net
 
 
-def load_keypoint_net(model, compute_dtype=torch.float32, device=None, audit_frames=AUDIT_AUTO, heat_bar=HEAT_BAR, on_overflow="raise", range_guard=None):
+def load_keypoint_net(model, compute_dtype=torch.float32, device=None, audit_frames=AUDIT_AUTO, heat_bar=HEAT_BAR, on_overflow="raise", range_guard=None,
+                      frame_format=None):
     """Accepts a KeypointNet, a state_dict, or a path to a torch.save'd state_dict / Lightning checkpoint /
     TorchScript file produced by the reference's scripts/package_model.py, and returns an eval KeypointNet.
     Entries of the file that are not KeypointNet parameters (loss buffers, metrics of the Lightning module) are ignored;
@@ -196,7 +197,9 @@ def load_keypoint_net(model, compute_dtype=torch.float32, device=None, audit_fra
     on_overflow ("raise" | "float32" | "defer"): what a pass of a split-product configuration does when an activation leaves the fp16
     range (KeypointNet.on_overflow): raise OkpError, re-run the pass with the exact float32 kernels, or leave the flag to the caller.
     range_guard (KeypointNet.range_guard): True runs a torch.float16 network under the same guard (on_overflow then applies to it); None
-    keeps each configuration's default (a KeypointNet passed in keeps its own)."""
+    keeps each configuration's default (a KeypointNet passed in keeps its own).
+    frame_format (KeypointNet.frame_format, an ops.YUV420Format): take 3-D uint8 tensors as 4:2:0 decoder output (NV12 / I420); None
+    keeps a KeypointNet's own (a new one refuses them)."""
     device = device or _device()
     if on_overflow not in ("raise", "float32", "defer"):
         raise OkpError("on_overflow is 'raise', 'float32' or 'defer'")
@@ -204,6 +207,8 @@ def load_keypoint_net(model, compute_dtype=torch.float32, device=None, audit_fra
         model.on_overflow = on_overflow
         if range_guard is not None:
             model.range_guard = range_guard
+        if frame_format is not None:
+            model.frame_format = frame_format
         return _audited(model.to(device).eval(), audit_frames, heat_bar)
     if isinstance(model, (str, bytes)) or hasattr(model, "__fspath__"):
         clean = read_checkpoint_state_dict(model)
@@ -216,7 +221,7 @@ def load_keypoint_net(model, compute_dtype=torch.float32, device=None, audit_fra
             raise OkpError(f"model file holds no KeypointNet: '{need}' is missing")
     heat_out = clean["heatmap_head.output_head2.2.weight"].shape[0]
     features = clean["heatmap_head.output_head2.0.conv.weight"].shape[0]
-    net = models.KeypointNet(features=features, heatmaps_out=heat_out, compute_dtype=compute_dtype, range_guard=range_guard)
+    net = models.KeypointNet(features=features, heatmaps_out=heat_out, compute_dtype=compute_dtype, range_guard=range_guard, frame_format=frame_format)
     own = net.state_dict()
     missing = [k for k in own if k not in clean]
     if missing:
@@ -254,14 +259,15 @@ def load_cornernet_backbone(net, pretrained):
 class InferenceComponent:
     name = "inference"
 
-    def __init__(self, model, cuda=True, compute_dtype=torch.float32, on_overflow="float32", range_guard=None):
+    def __init__(self, model, cuda=True, compute_dtype=torch.float32, on_overflow="float32", range_guard=None, frame_format=None):
         """on_overflow (split-product compute dtypes only): the reference's fp32 model returns numbers for any input; the drop-in does too -
         a pass whose activations leave the fp16 range is re-run with the exact float32 kernels ("float32", with a RuntimeWarning the first
-        time) - unless the caller prefers an OkpError ("raise").  range_guard=True extends that to torch.float16 (KeypointNet.range_guard)."""
+        time) - unless the caller prefers an OkpError ("raise").  range_guard=True extends that to torch.float16 (KeypointNet.range_guard).
+        frame_format (an ops.YUV420Format): frames may be 4:2:0 decoder output [N, 3H/2, W] uint8 (KeypointNet.frame_format)."""
         if not cuda:
             raise OkpError("InferenceComponent(cuda=False): this build has no CPU path (the CPU restatement is oracle/, test-only)")
         self.cuda = cuda
-        self.model = load_keypoint_net(model, compute_dtype, on_overflow=on_overflow, range_guard=range_guard)
+        self.model = load_keypoint_net(model, compute_dtype, on_overflow=on_overflow, range_guard=range_guard, frame_format=frame_format)
 
     def __call__(self, frames):
         frames = frames.to(_device())
@@ -452,8 +458,10 @@ class LearnedKeypointTrackingPipeline(ObjectKeypointPipeline):
         compute_dtype = kwargs.pop("compute_dtype", torch.float32)
         on_overflow = kwargs.pop("on_overflow", "float32")
         range_guard = kwargs.pop("range_guard", None)
+        frame_format = kwargs.pop("frame_format", None)
         super().__init__(*args, **kwargs)
-        self.inference = InferenceComponent(model, cuda, compute_dtype=compute_dtype, on_overflow=on_overflow, range_guard=range_guard)
+        self.inference = InferenceComponent(model, cuda, compute_dtype=compute_dtype, on_overflow=on_overflow, range_guard=range_guard,
+                                            frame_format=frame_format)
 
     def __call__(self, frame):
         heatmap, depth, centers = self.inference(frame)
