@@ -36,7 +36,8 @@ extern "C" {
                                     stem and as sources of OKP_F32X3 plans on the patch-resident kernel
                                  additions at 7 (new entry points only; no struct or existing signature changed): okp_stereo_match,
                                     okp_stereo_triangulate; the struct okp_stereo_pair, okp_stereo_match_rig, okp_stereo_triangulate_rig;
-                                    OKP_YUV_I420 / OKP_YUV_NV12 / OKP_YUV_BT601 / OKP_YUV_BT709, okp_preprocess_yuv420 */
+                                    OKP_YUV_I420 / OKP_YUV_NV12 / OKP_YUV_BT601 / OKP_YUV_BT709, okp_preprocess_yuv420;
+                                    okp_project_labels, okp_render_targets, okp_keypoint_loss (scoring labelled scenes) */
 
 /* OKP_F16: IEEE half activations / weights, fp32 accumulate (BASELINE configs[4]).
  * OKP_F32X3 (okp_conv plans only): fp32 activations, weights and results like OKP_F32 - every tensor argument of such a plan is an
@@ -499,6 +500,53 @@ int okp_stereo_triangulate_rig(const okp_stereo_pair* table_dev, int32_t n_table
  * xy [m][2] fp32 -> out [m][2] fp64.  okp_fisheye_undistort is the same entry point under its round-1 name. */
 int okp_camera_undistort(const okp_camera* cam, const float* xy_dev, int32_t m, double* out_dev, void* stream);
 int okp_fisheye_undistort(const okp_camera* cam, const float* xy_dev, int32_t m, double* out_dev, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * Scoring labelled scenes: the forward halves of the reference's target rendering and KeypointLoss (csrc/okp_targets.hip).
+ *
+ * Labels of one frame: [max_obj * nk][3] fp64 rows (x, y, z), nk = sum(type_count); x, y in pixels of the 511 x 511 network input, z the
+ * depth in the camera frame.  Rows are object-major; within an object the centre comes first, then the key points type by type
+ * (SceneDataset._init_points, perception/datasets/video.py:108-125).  n_obj [n] int32 gives the objects of each frame, 0 .. max_obj
+ * (clamped to that range); max_obj <= 64 as in okp_group_objects.  type_count [K] int32 is SceneDataset.keypoint_config: [1] + the
+ * configuration file's list (video.py:70), 2 <= K <= 16, type_count[k] * max_obj <= 512.
+ *
+ * okp_project_labels: world points [p][3] fp64 and camera poses T_WC [n][4][4] fp64 (row-major) -> labels [n][p][3], one lane per
+ * point, all fp64: inv_transform(T_WC) (perception/utils/linalg.py:4-10), the camera-frame point, camera.project by cam->model
+ * (perception/utils/camera_utils.py:93-118 as restated by the product's host FisheyeCamera / RadTanPinholeCamera.project), then the raw-to-input
+ * map x * scale - crop_x, y * scale - crop_y (video.py:188-196: what SmallestMaxSize + CenterCrop do to key points; 511/720 and (198, 0)
+ * for 720 x 1280 frames, the geometry of okp_preprocess_u8).
+ *
+ * okp_render_targets: labels -> heat [n][K][64][64], depth [n][K][64][64], centers [n][K-1][2][64][64] fp32, what the dataset yields:
+ *   heat     _set_keypoints (video.py:33-44) as called at :201-209 and the normalisation at :214-215: positions * 64/511; int_x, int_y
+ *            truncate toward zero; window [int - 8, int + 8] clipped to the map; exp(-((px - j)^2 + (py - i)^2) / 2.0^2) at the INTEGER
+ *            pixel (j, i), in fp64, summed into the fp32 map of the type in label order; then / max(map maximum, 0.5), clipped to [0, 1].
+ *            Off-frame key points render what part of their window is inside; a frame without objects gives zero maps.
+ *   depth    _compute_depth (video.py:247-263): discs ||key point - (j + 0.5, i + 0.5)|| < 4.0 on pixel CENTRES hold the point's z
+ *   centers  _compute_centers (video.py:226-245): the same discs of map k >= 1 hold, in map k - 1, (the object's centre key point -
+ *            pixel centre) in x and y.  Where discs overlap the LAST key point in label order wins (the reference overwrites).
+ *
+ * okp_keypoint_loss: KeypointLoss.forward (perception/loss.py:20-48) for n_stacks <= 4 stacks of predictions laid out as
+ * KeypointNet.forward returns them (fp32 NCHW; centers [n][K-1][2][64][64]); p_*_dev are HOST arrays of n_stacks device pointers.
+ * Targets are EITHER labels (labels_dev, n_obj_dev, max_obj, type_count; rendered in registers, never stored; t_*_dev NULL) OR dense
+ * tensors of the whole batch (t_heat_dev, t_depth_dev, t_centers_dev as okp_render_targets writes them; labels_dev NULL).
+ * The call covers frames [n_first, n_first + n) of a batch of n_total: predictions hold these n frames, labels / targets / outputs the
+ * whole batch; the call with n_first + n == n_total folds the batch, so a batch scored in chunks gives the bits of one call.  Outputs:
+ *   partial    [n_total][K][n_stacks][3] fp64  scratch: per-map sums (no floating-point atomics: a second kernel folds them in a fixed order)
+ *   terms      [n_total][n_stacks][3] fp64     per-frame sums of the heat (BCE with logits), depth (L1 over target heat > 0.01) and
+ *                                              centre (smooth L1, beta 1, same mask of maps 1.., both components) terms
+ *   mask_count [n_total][K] int32              pixels with target heat > 0.01
+ *   out        [1 + 3 n_stacks] fp64           total, heat[s], depth[s], center[s]: heat[s] = mean over frames, depth[s] / center[s] the
+ *              raw sums, total = sum_s heat[s] + depth_weight * depth[s] / n_total + center_weight * center[s] / n_total (loss.py:28-48)
+ * Per-pixel terms are fp32 as in the reference, their sums fp64. */
+int okp_project_labels(const okp_camera* cam, const double* world_dev, int32_t p, const double* T_WC_dev, int32_t n, double scale,
+                       double crop_x, double crop_y, double* labels_dev, void* stream);
+int okp_render_targets(const double* labels_dev, const int32_t* n_obj_dev, int32_t n, int32_t max_obj, const int32_t* type_count, int32_t K,
+                       float* heat_dev, float* depth_dev, float* centers_dev, void* stream);
+int okp_keypoint_loss(const float* const* p_heat_dev, const float* const* p_depth_dev, const float* const* p_centers_dev, int32_t n_stacks,
+                      int32_t n_first, int32_t n, int32_t n_total, int32_t K, const double* labels_dev, const int32_t* n_obj_dev,
+                      int32_t max_obj, const int32_t* type_count, const float* t_heat_dev, const float* t_depth_dev,
+                      const float* t_centers_dev, double depth_weight, double center_weight, double* partial_dev, double* terms_dev,
+                      int32_t* mask_count_dev, double* out_dev, void* stream);
 
 #ifdef __cplusplus
 }

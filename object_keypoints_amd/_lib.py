@@ -111,6 +111,10 @@ SIGNATURES = [
     ("okp_stereo_triangulate_rig", c_int, [c_void_p, c_int32, c_int32, c_int, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
     ("okp_fisheye_undistort", c_int, [POINTER(okp_camera), c_void_p, c_int32, c_void_p, c_void_p]),
     ("okp_camera_undistort", c_int, [POINTER(okp_camera), c_void_p, c_int32, c_void_p, c_void_p]),
+    ("okp_project_labels", c_int, [POINTER(okp_camera), c_void_p, c_int32, c_void_p, c_int32, c_double, c_double, c_double, c_void_p, c_void_p]),
+    ("okp_render_targets", c_int, [c_void_p, c_void_p, c_int32, c_int32, POINTER(c_int32), c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    ("okp_keypoint_loss", c_int, [POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p), c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p,
+                                  c_int32, POINTER(c_int32), c_void_p, c_void_p, c_void_p, c_double, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
 ]
 
 _lib = None

@@ -576,6 +576,80 @@ void group_objects(const Tensor& count, const Tensor& xyc, const Tensor& centers
                              red, reinterpret_cast<void*>(stream)), "okp_group_objects");
 }
 
+// ---- scoring labelled scenes (csrc/okp_targets.hip) --------------------------------------------------------------------------------
+
+void project_labels(at::ArrayRef<double> camera, const Tensor& world, const Tensor& T_WC, double scale, double crop_x, double crop_y, const Tensor& labels,
+                    int64_t stream) {
+  check_dev(world, at::kDouble, "world_points"); check_dev(T_WC, at::kDouble, "T_WC"); check_dev(labels, at::kDouble, "labels");
+  TORCH_CHECK(world.dim() == 2 && world.size(1) == 3, "okp: world_points is [P,3]");
+  TORCH_CHECK(T_WC.dim() == 3 && T_WC.size(1) == 4 && T_WC.size(2) == 4, "okp: T_WC is [N,4,4]");
+  TORCH_CHECK(labels.dim() == 3 && labels.size(0) == T_WC.size(0) && labels.size(1) == world.size(0) && labels.size(2) == 3, "okp: labels is [N,P,3]");
+  const okp_camera cam = camera_of(camera);
+  check_rc(okp_project_labels(&cam, world.data_ptr<double>(), (int32_t)world.size(0), T_WC.data_ptr<double>(), (int32_t)T_WC.size(0), scale, crop_x, crop_y,
+                              labels.data_ptr<double>(), sp(stream)), "okp_project_labels");
+}
+
+// labels [N, max_obj * nk, 3] fp64, n_obj [N] int32: the checks both label consumers share -> max_obj
+inline int64_t check_labels(const Tensor& labels, const Tensor& n_obj, at::IntArrayRef type_count, int64_t n) {
+  check_dev(labels, at::kDouble, "labels"); check_dev(n_obj, at::kInt, "n_obj");
+  int64_t nk = 0;
+  for (auto c : type_count) nk += c;
+  TORCH_CHECK(nk > 0 && labels.dim() == 3 && labels.size(0) == n && labels.size(2) == 3 && labels.size(1) > 0 && labels.size(1) % nk == 0,
+              "okp: labels is [N, max_obj * sum(type_count), 3]");
+  TORCH_CHECK(n_obj.dim() == 1 && n_obj.size(0) == n, "okp: n_obj is [N]");
+  return labels.size(1) / nk;
+}
+
+inline void check_targets(const Tensor& heat, const Tensor& depth, const Tensor& centers, int64_t n, int64_t K) {
+  check_dev(heat, at::kFloat, "heat"); check_dev(depth, at::kFloat, "depth"); check_dev(centers, at::kFloat, "centers");
+  TORCH_CHECK(heat.sizes() == at::IntArrayRef({n, K, 64, 64}) && depth.sizes() == heat.sizes(), "okp: heat and depth are [N,K,64,64]");
+  TORCH_CHECK(centers.sizes() == at::IntArrayRef({n, K - 1, 2, 64, 64}), "okp: centers is [N,K-1,2,64,64]");
+}
+
+void render_targets(const Tensor& labels, const Tensor& n_obj, at::IntArrayRef type_count, const Tensor& heat, const Tensor& depth, const Tensor& centers,
+                    int64_t stream) {
+  const int64_t n = heat.dim() ? heat.size(0) : 0, K = (int64_t)type_count.size();
+  const int64_t max_obj = check_labels(labels, n_obj, type_count, n);
+  check_targets(heat, depth, centers, n, K);
+  std::vector<int32_t> tc(type_count.begin(), type_count.end());
+  check_rc(okp_render_targets(labels.data_ptr<double>(), n_obj.data_ptr<int32_t>(), (int32_t)n, (int32_t)max_obj, tc.data(), (int32_t)K, heat.data_ptr<float>(),
+                              depth.data_ptr<float>(), centers.data_ptr<float>(), sp(stream)), "okp_render_targets");
+}
+
+void keypoint_loss(at::TensorList p_heat, at::TensorList p_depth, at::TensorList p_centers, int64_t n_first, int64_t n_total, const optional<Tensor>& labels,
+                   const optional<Tensor>& n_obj, at::IntArrayRef type_count, const optional<Tensor>& t_heat, const optional<Tensor>& t_depth,
+                   const optional<Tensor>& t_centers, double depth_weight, double center_weight, const Tensor& partial, const Tensor& terms,
+                   const Tensor& mask_count, const Tensor& out, int64_t stream) {
+  const int64_t S = (int64_t)p_heat.size(), K = (int64_t)type_count.size();
+  TORCH_CHECK(S >= 1 && (int64_t)p_depth.size() == S && (int64_t)p_centers.size() == S, "okp: one heat, depth and centre prediction per stack");
+  TORCH_CHECK(p_heat[0].dim() == 4, "okp: p_heatmaps are [N,K,64,64]");
+  const int64_t n = p_heat[0].size(0);
+  std::vector<const float*> ph, pd, pc;
+  for (int64_t s = 0; s < S; ++s) {
+    check_targets(p_heat[s], p_depth[s], p_centers[s], n, K);
+    ph.push_back(p_heat[s].data_ptr<float>()); pd.push_back(p_depth[s].data_ptr<float>()); pc.push_back(p_centers[s].data_ptr<float>());
+  }
+  TORCH_CHECK(n_first >= 0 && n_first + n <= n_total, "okp: frames outside the batch");
+  check_dev(partial, at::kDouble, "partial"); check_dev(terms, at::kDouble, "terms"); check_dev(mask_count, at::kInt, "mask_count"); check_dev(out, at::kDouble, "out");
+  TORCH_CHECK(partial.numel() == n_total * K * S * 3 && terms.numel() == n_total * S * 3 && mask_count.numel() == n_total * K && out.numel() == 1 + 3 * S,
+              "okp: keypoint_loss outputs are partial [N,K,S,3], terms [N,S,3], mask_count [N,K], out [1 + 3 S]");
+  std::vector<int32_t> tc(type_count.begin(), type_count.end());
+  const double* lab = nullptr; const int32_t* no = nullptr; int64_t max_obj = 0;
+  const float *th = nullptr, *td = nullptr, *tcn = nullptr;
+  if (labels.has_value()) {
+    TORCH_CHECK(n_obj.has_value() && !t_heat.has_value() && !t_depth.has_value() && !t_centers.has_value(), "okp: give either labels with n_obj or dense targets");
+    max_obj = check_labels(*labels, *n_obj, type_count, n_total);
+    lab = labels->data_ptr<double>(); no = n_obj->data_ptr<int32_t>();
+  } else {
+    TORCH_CHECK(t_heat.has_value() && t_depth.has_value() && t_centers.has_value(), "okp: give either labels with n_obj or dense targets");
+    check_targets(*t_heat, *t_depth, *t_centers, n_total, K);
+    th = t_heat->data_ptr<float>(); td = t_depth->data_ptr<float>(); tcn = t_centers->data_ptr<float>();
+  }
+  check_rc(okp_keypoint_loss(ph.data(), pd.data(), pc.data(), (int32_t)S, (int32_t)n_first, (int32_t)n, (int32_t)n_total, (int32_t)K, lab, no, (int32_t)max_obj,
+                             tc.data(), th, td, tcn, depth_weight, center_weight, partial.data_ptr<double>(), terms.data_ptr<double>(),
+                             mask_count.data_ptr<int32_t>(), out.data_ptr<double>(), sp(stream)), "okp_keypoint_loss");
+}
+
 }  // namespace
 
 TORCH_LIBRARY(okp, m) {
@@ -629,4 +703,9 @@ TORCH_LIBRARY(okp, m) {
         "Tensor? range_flag=None) -> ()", stereo_match_rig);
   m.def("stereo_triangulate_rig(Tensor table, int first_pair, bool correct_matches, Tensor count, Tensor xyc, Tensor match, Tensor(a!) points, int stream) -> ()",
         stereo_triangulate_rig);
+  m.def("project_labels(float[] camera, Tensor world_points, Tensor T_WC, float scale, float crop_x, float crop_y, Tensor(a!) labels, int stream) -> ()", project_labels);
+  m.def("render_targets(Tensor labels, Tensor n_obj, int[] type_count, Tensor(a!) heat, Tensor(b!) depth, Tensor(c!) centers, int stream) -> ()", render_targets);
+  m.def("keypoint_loss(Tensor[] p_heat, Tensor[] p_depth, Tensor[] p_centers, int n_first, int n_total, Tensor? labels, Tensor? n_obj, int[] type_count, "
+        "Tensor? t_heat, Tensor? t_depth, Tensor? t_centers, float depth_weight, float center_weight, Tensor(a!) partial, Tensor(b!) terms, Tensor(c!) mask_count, "
+        "Tensor(d!) out, int stream) -> ()", keypoint_loss);
 }

@@ -1237,3 +1237,207 @@ def stereo_triangulate_rig(table, count, xyc, match, first_pair=0, correct_match
                                                          xyc.data_ptr(), match.data_ptr(), n_pairs, k, cap, points.data_ptr(), stream_handle()),
                    "okp_stereo_triangulate_rig")
     return points
+
+
+# ---- scoring labelled scenes (csrc/okp_targets.hip) ---------------------------------------------------------------------------------
+TARGET_SIZE = 64             # SceneDataset.prediction_size
+TARGET_MAX_MAPS = 16         # K
+TARGET_MAX_STACKS = 4        # S
+TARGET_MAX_OBJ = 64          # objects per frame, as okp_group_objects
+TARGET_MAX_MAP_POINTS = 512  # max_obj * type_count[k]
+
+
+def raw_to_input(raw_size, size=511):
+    """(scale, crop_x, crop_y) of the key point half of SmallestMaxSize(size) + CenterCrop(size, size) on raw_size = (H, W) frames: the geometry
+    preprocess_u8 applies to the pixels.  (720, 1280) -> (511/720, 198, 0)."""
+    h, w = int(raw_size[0]), int(raw_size[1])
+    if h < 1 or w < 1 or size < 1:
+        raise OkpError(f"raw_size {h}x{w} and size {size} must be positive")
+    rh, rw = smallest_max_size(h, w, size)
+    if rh < size or rw < size:
+        raise OkpError(f"raw_size: the {size}x{size} crop does not fit the resized frame {rh}x{rw}")
+    return size / min(h, w), float((rw - size) // 2), float((rh - size) // 2)
+
+
+def check_type_count(type_count, max_obj=1):
+    """type_count = [1] + the configuration file's keypoint_config (SceneDataset.keypoint_config) -> (list of K ints, nk)."""
+    try:
+        tc = [int(c) for c in type_count]
+    except (TypeError, ValueError):
+        raise OkpError("type_count must be a list of integers: [1] + keypoint_config") from None
+    if not 2 <= len(tc) <= TARGET_MAX_MAPS:
+        raise OkpError(f"type_count has {len(tc)} maps: 2 to {TARGET_MAX_MAPS} are supported")
+    if tc[0] != 1:
+        raise OkpError(f"type_count[0] = {tc[0]}: map 0 is the centre map, one point per object")
+    if min(tc) < 1:
+        raise OkpError(f"type_count {tc}: every map has at least one key point")
+    if not 1 <= max_obj <= TARGET_MAX_OBJ:
+        raise OkpError(f"labels hold {max_obj} objects per frame: the capacity is 1 to {TARGET_MAX_OBJ}")
+    if max(tc) * max_obj > TARGET_MAX_MAP_POINTS:
+        raise OkpError(f"type_count {tc} with {max_obj} objects per frame: at most {TARGET_MAX_MAP_POINTS} key points per map")
+    return tc, sum(tc)
+
+
+def check_labels(labels, n_obj, type_count, n=None):
+    """Shape, dtype and capacity checks of a batch of labels (no device work) -> (type_count list, N, max_obj)."""
+    if not isinstance(labels, torch.Tensor) or labels.dtype != torch.float64:
+        raise OkpError("labels must be a float64 tensor [N, max_obj * sum(type_count), 3]")
+    if not isinstance(n_obj, torch.Tensor) or n_obj.dtype != torch.int32:
+        raise OkpError("n_obj must be an int32 tensor [N]")
+    nk = sum(check_type_count(type_count)[0])
+    if labels.dim() != 3 or labels.shape[2] != 3 or labels.shape[1] == 0 or labels.shape[1] % nk:
+        raise OkpError(f"labels must be [N, max_obj * {nk}, 3] rows (x, y, z), not {tuple(labels.shape)}")
+    max_obj = labels.shape[1] // nk
+    tc, _ = check_type_count(type_count, max_obj)
+    if n_obj.dim() != 1 or n_obj.shape[0] != labels.shape[0]:
+        raise OkpError(f"n_obj must be [N] = [{labels.shape[0]}], not {tuple(n_obj.shape)}")
+    if n is not None and labels.shape[0] != n:
+        raise OkpError(f"labels hold {labels.shape[0]} frames, the batch has {n}")
+    if not labels.is_contiguous() or not n_obj.is_contiguous():
+        raise OkpError("labels and n_obj must be contiguous")
+    if labels.device != n_obj.device:
+        raise OkpError("labels and n_obj must be on the same device")
+    return tc, labels.shape[0], max_obj
+
+
+def _check_maps(name, heat, depth, centers, n, k, device=None):
+    for what, t, shape in ((f"{name}heat", heat, (n, k, TARGET_SIZE, TARGET_SIZE)), (f"{name}depth", depth, (n, k, TARGET_SIZE, TARGET_SIZE)),
+                           (f"{name}centers", centers, (n, k - 1, 2, TARGET_SIZE, TARGET_SIZE))):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+            raise OkpError(f"{what} must be a float32 tensor")
+        if tuple(t.shape) != shape:
+            raise OkpError(f"{what} must be {list(shape)}, not {list(t.shape)}")
+        if not t.is_contiguous():
+            raise OkpError(f"{what} must be contiguous")
+        if device is not None and t.device != device:
+            raise OkpError(f"{what} is on {t.device}, not on {device}")
+
+
+def project_labels(cam, world_points, T_WC, scale=511.0 / 720.0, crop=(198.0, 0.0)):
+    """world_points [P,3] fp64, camera poses T_WC [N,4,4] fp64 (device) -> labels [N,P,3] fp64: (x, y) in pixels of the network input, z in the
+    camera frame (okp_project_labels).  scale / crop: raw_to_input(raw_size)."""
+    if not isinstance(cam, _lib.okp_camera):
+        raise OkpError(f"cam must be an okp_camera (make_camera), not {type(cam).__name__}")
+    if cam.model not in (_lib.CAM_EQUIDISTANT, _lib.CAM_RADTAN):
+        raise OkpError(f"cam: unknown camera model {cam.model}")
+    if not isinstance(world_points, torch.Tensor) or world_points.dtype != torch.float64 or world_points.dim() != 2 or world_points.shape[1] != 3:
+        raise OkpError("world_points must be a float64 tensor [P, 3]")
+    if not isinstance(T_WC, torch.Tensor) or T_WC.dtype != torch.float64 or T_WC.dim() != 3 or tuple(T_WC.shape[1:]) != (4, 4):
+        raise OkpError("T_WC must be a float64 tensor [N, 4, 4]")
+    if not world_points.is_contiguous() or not T_WC.is_contiguous():
+        raise OkpError("world_points and T_WC must be contiguous")
+    if not float(scale) > 0.0:
+        raise OkpError(f"scale must be positive, not {scale}")
+    if len(crop) != 2:
+        raise OkpError("crop must be (crop_x, crop_y)")
+    if world_points.device != T_WC.device:
+        raise OkpError("world_points and T_WC must be on the same device")
+    require_cuda(world_points, "world_points")
+    n, p = T_WC.shape[0], world_points.shape[0]
+    labels = torch.empty((n, p, 3), dtype=torch.float64, device=T_WC.device)
+    if n == 0 or p == 0:
+        return labels
+    T = _ops()
+    if T is not None:
+        _dispatch(T.project_labels, _cam_list(cam), world_points, T_WC, float(scale), float(crop[0]), float(crop[1]), labels, stream_int())
+    else:
+        _lib.check(_lib.lib().okp_project_labels(ctypes.byref(cam), world_points.data_ptr(), p, T_WC.data_ptr(), n, float(scale), float(crop[0]),
+                                                 float(crop[1]), labels.data_ptr(), stream_handle()), "okp_project_labels")
+    COUNTERS["launches"] += 1
+    return labels
+
+
+def render_targets(labels, n_obj, type_count):
+    """labels [N, max_obj * nk, 3] fp64, n_obj [N] int32 (device), type_count = [1] + keypoint_config -> (heat [N,K,64,64], depth [N,K,64,64],
+    centers [N,K-1,2,64,64]) fp32: what the reference's SceneDataset yields for these key points (okp_render_targets)."""
+    tc, n, max_obj = check_labels(labels, n_obj, type_count)
+    require_cuda(labels, "labels")
+    k, dev = len(tc), labels.device
+    heat = torch.empty((n, k, TARGET_SIZE, TARGET_SIZE), dtype=torch.float32, device=dev)
+    depth = torch.empty_like(heat)
+    centers = torch.empty((n, k - 1, 2, TARGET_SIZE, TARGET_SIZE), dtype=torch.float32, device=dev)
+    if n == 0:
+        return heat, depth, centers
+    T = _ops()
+    if T is not None:
+        _dispatch(T.render_targets, labels, n_obj, tc, heat, depth, centers, stream_int())
+    else:
+        _lib.check(_lib.lib().okp_render_targets(labels.data_ptr(), n_obj.data_ptr(), n, max_obj, (ctypes.c_int32 * k)(*tc), k, heat.data_ptr(),
+                                                 depth.data_ptr(), centers.data_ptr(), stream_handle()), "okp_render_targets")
+    COUNTERS["launches"] += 1
+    return heat, depth, centers
+
+
+def keypoint_loss(p_heatmaps, p_depth, p_centers, type_count, labels=None, n_obj=None, targets=None, depth_weight=10.0, center_weight=1.0,
+                  first=0, total=None, state=None):
+    """The reference's KeypointLoss.forward (perception/loss.py:20-48) in one device pass (okp_keypoint_loss), without a host synchronisation.
+
+    p_heatmaps / p_depth / p_centers: one fp32 tensor per stack, as KeypointNet.forward returns them ([n,K,64,64], [n,K,64,64],
+    [n,K-1,2,64,64]).  The targets are EITHER labels [N, max_obj * nk, 3] fp64 with n_obj [N] int32 (rendered in registers) OR
+    targets = (heat, depth, centers), dense fp32 tensors of the batch.  A batch of `total` frames may be scored in chunks: the predictions of
+    a call are frames [first, first + n) and `state` is the result of the previous chunk; the chunk that ends the batch folds it, and the
+    result has the bits of one call.  Returns device tensors: loss [], heat [S], depth [S], center [S] (fp64; the reference's 4-tuple),
+    terms [N,S,3] fp64 (per-frame heat / depth / centre sums), mask_count [N,K] int32."""
+    lists = []
+    for name, lst in (("p_heatmaps", p_heatmaps), ("p_depth", p_depth), ("p_centers", p_centers)):
+        if isinstance(lst, torch.Tensor) or not isinstance(lst, (list, tuple)) or not lst or not all(isinstance(t, torch.Tensor) for t in lst):
+            raise OkpError(f"{name} must be a list of tensors, one per stack")
+        lists.append(list(lst))
+    s = len(lists[0])
+    if len(lists[1]) != s or len(lists[2]) != s:
+        raise OkpError(f"p_heatmaps, p_depth and p_centers must have one tensor per stack: {s}, {len(lists[1])}, {len(lists[2])}")
+    if s > TARGET_MAX_STACKS:
+        raise OkpError(f"p_heatmaps has {s} stacks: at most {TARGET_MAX_STACKS} are supported")
+    tc, _ = check_type_count(type_count)
+    k = len(tc)
+    if lists[0][0].dim() != 4:
+        raise OkpError(f"p_heatmaps[0] must be [n, {k}, 64, 64], not {list(lists[0][0].shape)}")
+    n, dev = lists[0][0].shape[0], lists[0][0].device
+    for i in range(s):
+        _check_maps(f"p_[{i}] ", lists[0][i], lists[1][i], lists[2][i], n, k, dev)
+    first = int(first)
+    total = n + first if total is None else int(total)
+    if first < 0 or total < 1 or first + n > total:
+        raise OkpError(f"first = {first}, total = {total}: the {n} frames of this call must lie inside the batch")
+    if (labels is None) == (targets is None):
+        raise OkpError("give either labels (with n_obj) or targets = (heat, depth, centers)")
+    max_obj = 0
+    if labels is not None:
+        tc, _, max_obj = check_labels(labels, n_obj, tc, total)
+        if labels.device != dev:
+            raise OkpError(f"labels are on {labels.device}, the predictions on {dev}")
+    else:
+        if n_obj is not None:
+            raise OkpError("n_obj goes with labels, not with dense targets")
+        if not isinstance(targets, (list, tuple)) or len(targets) != 3:
+            raise OkpError("targets must be (heat, depth, centers)")
+        _check_maps("target ", targets[0], targets[1], targets[2], total, k, dev)
+    if state is None:
+        if first != 0:
+            raise OkpError(f"first = {first} without the state of the chunks before it")
+    else:
+        for key, shape in (("partial", (total, k, s, 3)), ("terms", (total, s, 3)), ("mask_count", (total, k)), ("out", (1 + 3 * s,))):
+            if key not in state or tuple(state[key].shape) != shape or state[key].device != dev:
+                raise OkpError(f"state[{key!r}] must be the {list(shape)} tensor an earlier chunk of this batch returned")
+    require_cuda(lists[0][0], "p_heatmaps")
+    if state is None:
+        state = {"partial": torch.empty((total, k, s, 3), dtype=torch.float64, device=dev),
+                 "terms": torch.empty((total, s, 3), dtype=torch.float64, device=dev),
+                 "mask_count": torch.empty((total, k), dtype=torch.int32, device=dev),
+                 "out": torch.empty((1 + 3 * s,), dtype=torch.float64, device=dev)}
+    partial, terms, mask_count, out = state["partial"], state["terms"], state["mask_count"], state["out"]
+    T = _ops()
+    if T is not None:
+        th, td, tcn = targets if targets is not None else (None, None, None)
+        _dispatch(T.keypoint_loss, lists[0], lists[1], lists[2], first, total, labels, n_obj, tc, th, td, tcn, float(depth_weight), float(center_weight),
+                  partial, terms, mask_count, out, stream_int())
+    else:
+        ptrs = [(ctypes.c_void_p * s)(*[t.data_ptr() for t in lst]) for lst in lists]
+        tp = [t.data_ptr() for t in targets] if targets is not None else [None, None, None]
+        _lib.check(_lib.lib().okp_keypoint_loss(ptrs[0], ptrs[1], ptrs[2], s, first, n, total, k, labels.data_ptr() if labels is not None else None,
+                                                n_obj.data_ptr() if labels is not None else None, max_obj, (ctypes.c_int32 * k)(*tc), tp[0], tp[1], tp[2],
+                                                float(depth_weight), float(center_weight), partial.data_ptr(), terms.data_ptr(), mask_count.data_ptr(),
+                                                out.data_ptr(), stream_handle()), "okp_keypoint_loss")
+    COUNTERS["launches"] += 2 if first + n == total else 1
+    return {"loss": out[0], "heat": out[1:1 + s], "depth": out[1 + s:1 + 2 * s], "center": out[1 + 2 * s:], "terms": terms, "mask_count": mask_count,
+            "partial": partial, "out": out}

@@ -745,6 +745,63 @@ class BatchedKeypointPipeline:
         return objects
 
 
+class SceneScorer:
+    """Score labelled frames on the device: net.forward (raw logits of both stacks) plus the fused KeypointLoss against targets rendered
+    from the labels in registers (ops.keypoint_loss).  Nothing synchronises with the host, so a step can be captured.
+
+    score(frames, labels) -> {"loss" [], "heat" [S], "depth" [S], "center" [S] (the reference's 4-tuple, perception/loss.py:48, fp64),
+    "terms" [N,S,3] fp64 per-frame sums, "mask_count" [N,K] int32, "range_overflow" 0-d int32 (non-zero: a guarded configuration left
+    the fp16 range in this pass - the score is not to be trusted; always 0 for float32 / bfloat16)}.  labels: SceneTargets.labels."""
+
+    def __init__(self, net, keypoint_config, depth_weight=10.0, center_weight=1.0):
+        from .loss import KeypointLoss
+        cfg = keypoint_config['keypoint_config'] if isinstance(keypoint_config, dict) else keypoint_config
+        self.net = net
+        self.loss = KeypointLoss(cfg, depth_weight=depth_weight, center_weight=center_weight)
+
+    def score(self, frames, labels):
+        heat, depth, centers = self.net.forward(frames, check_range=False)      # the flag is folded in below, not read here
+        self.loss.from_labels(list(heat), list(depth), list(centers), labels)
+        r = self.loss.last
+        flag = self.net.range_flag(frames.device)
+        overflow = (flag != 0).to(torch.int32).reshape(()) if flag is not None else torch.zeros((), dtype=torch.int32, device=frames.device)
+        return {"loss": r["loss"], "heat": r["heat"], "depth": r["depth"], "center": r["center"], "terms": r["terms"],
+                "mask_count": r["mask_count"], "range_overflow": overflow}
+
+    def capture(self, frames, labels):
+        """score() for this frame and label shape as one hipGraph -> CapturedStep (static_in: the frames; static_labels: the labels, to be
+        overwritten in place with .copy_()); replay(frames) returns the static result dict."""
+        static_in = frames.clone()
+        static_labels = {"points": labels["points"].clone(), "n_obj": labels["n_obj"].clone()}
+        for _ in range(2):
+            self.score(static_in, static_labels)
+        torch.cuda.synchronize()
+        graph = torch.cuda.CUDAGraph()
+        keep, ops.SIDE_STREAMS = ops.SIDE_STREAMS, ops.SIDE_STREAMS and GRAPH_SIDE_STREAMS
+        try:
+            with torch.cuda.graph(graph):
+                static_out = self.score(static_in, static_labels)
+        finally:
+            ops.SIDE_STREAMS = keep
+        step = CapturedStep(self.net, graph, static_in, static_out)
+        step.static_labels = static_labels
+        return step
+
+    def compare(self, frames, labels, configurations):
+        """{configuration name: score} of several compute configurations on the same weights, frames and labels (set_compute_dtype);
+        the network is left in the configuration it had."""
+        mine = (self.net.compute_dtype, self.net.mfma_split, self.net.mixed)
+        out = {}
+        try:
+            for c in configurations:
+                self.net.set_compute_dtype(c)
+                r = self.score(frames, labels)
+                out[self.net.configuration()] = {k: v.clone() for k, v in r.items()}
+        finally:
+            self.net.compute_dtype, self.net.mfma_split, self.net.mixed = mine
+        return out
+
+
 class HostFrameFeed:
     """Host -> HBM upload of camera frames on a COPY stream, double-buffered, so that the frames of tick t + 1 cross PCIe while tick t is
     computed (the reference feeds its model from a DataLoader on the host, one frame per call: scripts/eval_model.py:274-293; raw frames
