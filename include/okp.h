@@ -37,7 +37,8 @@ extern "C" {
                                  additions at 7 (new entry points only; no struct or existing signature changed): okp_stereo_match,
                                     okp_stereo_triangulate; the struct okp_stereo_pair, okp_stereo_match_rig, okp_stereo_triangulate_rig;
                                     OKP_YUV_I420 / OKP_YUV_NV12 / OKP_YUV_BT601 / OKP_YUV_BT709, okp_preprocess_yuv420;
-                                    okp_project_labels, okp_render_targets, okp_keypoint_loss (scoring labelled scenes) */
+                                    okp_project_labels, okp_render_targets, okp_keypoint_loss (scoring labelled scenes);
+                                    okp_rig_fuse (a rig's stereo pairs fused into one object list in the rig frame) */
 
 /* OKP_F16: IEEE half activations / weights, fp32 accumulate (BASELINE configs[4]).
  * OKP_F32X3 (okp_conv plans only): fp32 activations, weights and results like OKP_F32 - every tensor argument of such a plan is an
@@ -495,6 +496,55 @@ int okp_stereo_match_rig(const okp_stereo_pair* table_dev, int32_t n_table, int3
 int okp_stereo_triangulate_rig(const okp_stereo_pair* table_dev, int32_t n_table, int32_t first_pair, int correct_matches,
                                const int32_t* count_dev, const float* xyc_dev, const int32_t* match_dev, int32_t n_pairs, int32_t K,
                                int32_t cap, double* points_dev, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * Rig fusion (csrc/okp_rig.hip): the per-pair 3D points of a stereo tick -> ONE list of objects in the rig (body) frame.  The reference
+ * has no rig; its tools work in one frame throughout (scripts/label.py:285-305 triangulates, then transforms to the world;
+ * scripts/eval_model.py:137-187) and group key points around centres with a distance gate and a per-type count
+ * (perception/pipeline.py:104-153, in the image).  This is the 3D counterpart, and the specification is this comment:
+ *   points [P][K][cap][4] fp64   the payload of okp_stereo_triangulate(_rig): (X, Y, Z, confidence) in pair p's left-camera frame; a row
+ *                                whose confidence is NaN is an empty slot, every other row is a candidate
+ *   poses  [P][12] fp64, DEVICE  row p = T_BL[p][:3] row-major = [R_p | t_p]: pair p's left-camera coordinates -> rig coordinates.  A
+ *                                captured graph reads the table on every replay.  The kernels cannot check a device table: the caller
+ *                                validates it (finite, R_p orthonormal with determinant +1) before the upload.
+ *   type_count HOST [K-1]        as for okp_group_objects: clusters of type k >= 1 kept per object, each >= 1
+ * 1. Transform.  X_B = R_p X + t_p for every candidate, fp64.
+ * 2. Cluster, type by type, across the pairs.  The candidates of type k are taken in the order confidence descending, then pair ascending,
+ *    then slot ascending.  Clusters are tried in creation order; a candidate joins the FIRST cluster whose seed (its first member, X_B)
+ *    lies within merge_radius - squared Euclidean distance <= merge_radius^2 - and which has no member from the candidate's pair yet.
+ *    Otherwise it founds the next cluster; when cap_f clusters exist it is dropped instead and bit OKP_RIG_FUSE_OVERFLOW is raised.
+ *    (The gate is against the seed, not a running mean: membership does not depend on the order of any arithmetic.)
+ * 3. Fuse.  A cluster's position is sum(c_i X_B,i) / sum(c_i) over its members, both sums accumulated in join order in fp64; its
+ *    confidence is its seed's (the largest); `views` has bit p set for every contributing pair p.
+ * 4. Group.  The clusters of type 0 are the objects, object index = cluster index.  A cluster of type k >= 1 belongs to the object whose
+ *    centre (fused position) is nearest to its fused position, a tie going to the lower index, if that distance is within
+ *    object_radius (squared distance <= object_radius^2); otherwise to none.  Per object and type the type_count[k-1] best clusters stay,
+ *    ranked by number of views descending, then confidence descending, then cluster index ascending; the others get object -1.
+ *    (Nearest centre, gate, count limit: pipeline.py:119-148.  Membership by the left view's centre-offset votes would need the centre
+ *    maps in the payload, and is not offered.)
+ * Outputs (fixed capacity, all written by every call):
+ *   fused   [K][cap_f][4] fp64   (X, Y, Z, confidence) of cluster c of type k in the rig frame; NaN rows from n_fused[k] on
+ *   n_fused [K] int32            clusters of type k (<= cap_f)
+ *   views   [K][cap_f] int32     bit mask of contributing pairs (0 beyond the count)
+ *   object  [K][cap_f] int32     object index of the cluster, or -1 (type 0: its own index; -1 beyond the count)
+ *   member  [P][K][cap] int32    cluster of its type the input row joined, -1 = none (empty slot, or dropped at cap_f)
+ *   n_obj   1 int32              = n_fused[0]
+ *   overflow 1 int32             (*overflow_in, or 0 when overflow_in is NULL) | OKP_RIG_FUSE_OVERFLOW if some type had more than cap_f
+ *                                clusters; the first cap_f clusters of that type are the ones an unbounded run would have found first.
+ *                                overflow_in may be the same address.
+ * Limits, refused on the host before any launch: P <= 32 (the `views` mask), K <= 8, cap <= 256, P * cap <= 1024 (the candidates of one
+ * type are sorted in LDS), cap_f <= 64 (one lane per cluster); radii positive and finite.  Two launches (one workgroup per type, then one
+ * workgroup for the grouping), no host wait, no floating-point atomics: the same bits on every run.
+ * ---------------------------------------------------------------------------------- */
+#define OKP_RIG_MAX_PAIRS 32
+#define OKP_RIG_MAX_TYPES 8
+#define OKP_RIG_MAX_ROWS 1024
+#define OKP_RIG_MAX_FUSED 64
+#define OKP_RIG_FUSE_OVERFLOW 4
+int okp_rig_fuse(const double* points_dev, const double* poses_dev, int32_t n_pairs, int32_t K, int32_t cap,
+                 const int32_t* type_count /* HOST [K-1] */, double merge_radius, double object_radius, int32_t cap_f,
+                 const int32_t* overflow_in_dev, double* fused_dev, int32_t* n_fused_dev, int32_t* views_dev, int32_t* object_dev,
+                 int32_t* member_dev, int32_t* n_obj_dev, int32_t* overflow_dev, void* stream);
 
 /* Undistort only (FisheyeCamera.undistort, camera_utils.py:75-81 / RadTanPinholeCamera.undistort, :57-62, by cam->model):
  * xy [m][2] fp32 -> out [m][2] fp64.  okp_fisheye_undistort is the same entry point under its round-1 name. */

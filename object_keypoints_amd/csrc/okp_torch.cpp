@@ -548,6 +548,30 @@ void stereo_triangulate_rig(const Tensor& table, int64_t first_pair, bool correc
                                       (int32_t)xyc.size(2), points.data_ptr<double>(), sp(stream)), "okp_stereo_triangulate_rig");
 }
 
+// Rig fusion: points [P,K,cap,4] float64 and poses [P,12] float64 (device) -> the seven outputs of okp_rig_fuse, all written
+void rig_fuse(const Tensor& points, const Tensor& poses, at::IntArrayRef type_count, double merge_radius, double object_radius, const Tensor& fused,
+              const Tensor& n_fused, const Tensor& views, const Tensor& object, const Tensor& member, const Tensor& n_obj, const Tensor& overflow, int64_t stream,
+              const optional<Tensor>& overflow_in) {
+  check_dev(points, at::kDouble, "points"); check_dev(poses, at::kDouble, "poses"); check_dev(fused, at::kDouble, "fused");
+  check_dev(n_fused, at::kInt, "n_fused"); check_dev(views, at::kInt, "views"); check_dev(object, at::kInt, "object"); check_dev(member, at::kInt, "member");
+  check_dev(n_obj, at::kInt, "n_obj"); check_dev(overflow, at::kInt, "overflow");
+  if (overflow_in.has_value()) check_dev(*overflow_in, at::kInt, "overflow_in");
+  TORCH_CHECK(points.dim() == 4 && points.size(3) == 4, "okp: points is [P,K,cap,4] float64 (the stereo tick's payload)");
+  const int64_t P = points.size(0), K = points.size(1), cap = points.size(2);
+  TORCH_CHECK(poses.dim() == 2 && poses.size(0) == P && poses.size(1) == 12, "okp: poses is [P,12] float64 (ops.rig_poses), one row per pair of points");
+  TORCH_CHECK((int64_t)type_count.size() == K - 1, "okp: type_count has K-1 entries");
+  TORCH_CHECK(fused.dim() == 3 && fused.size(0) == K && fused.size(2) == 4, "okp: fused is [K,cap_f,4] float64");
+  const int64_t cap_f = fused.size(1);
+  TORCH_CHECK(n_fused.numel() == K && views.numel() == K * cap_f && object.numel() == K * cap_f && member.numel() == P * K * cap && n_obj.numel() == 1 &&
+              overflow.numel() == 1 && (!overflow_in.has_value() || overflow_in->numel() == 1),
+              "okp: rig_fuse outputs are n_fused [K], views / object [K,cap_f], member [P,K,cap] int32, n_obj and overflow one int32 each");
+  std::vector<int32_t> tc(type_count.begin(), type_count.end());
+  check_rc(okp_rig_fuse(points.data_ptr<double>(), poses.data_ptr<double>(), (int32_t)P, (int32_t)K, (int32_t)cap, tc.data(), merge_radius, object_radius, (int32_t)cap_f,
+                        overflow_in.has_value() ? overflow_in->data_ptr<int32_t>() : nullptr, fused.data_ptr<double>(), n_fused.data_ptr<int32_t>(),
+                        views.data_ptr<int32_t>(), object.data_ptr<int32_t>(), member.data_ptr<int32_t>(), n_obj.data_ptr<int32_t>(), overflow.data_ptr<int32_t>(),
+                        sp(stream)), "okp_rig_fuse");
+}
+
 void lift_peaks(at::ArrayRef<double> camera, const Tensor& count, const Tensor& xyc, const Tensor& depth, int64_t max_x, int64_t max_y, const Tensor& out, int64_t stream) {
   TORCH_CHECK(xyc.is_cuda() && xyc.dim() == 4 && xyc.scalar_type() == at::kFloat && depth.is_cuda() && depth.scalar_type() == at::kFloat && depth.dim() == 4 && depth.is_contiguous() &&
               depth.size(0) == xyc.size(0) && depth.size(1) == xyc.size(1) && count.scalar_type() == at::kInt && out.scalar_type() == at::kDouble &&
@@ -703,6 +727,8 @@ TORCH_LIBRARY(okp, m) {
         "Tensor? range_flag=None) -> ()", stereo_match_rig);
   m.def("stereo_triangulate_rig(Tensor table, int first_pair, bool correct_matches, Tensor count, Tensor xyc, Tensor match, Tensor(a!) points, int stream) -> ()",
         stereo_triangulate_rig);
+  m.def("rig_fuse(Tensor points, Tensor poses, int[] type_count, float merge_radius, float object_radius, Tensor(a!) fused, Tensor(b!) n_fused, Tensor(c!) views, "
+        "Tensor(d!) object, Tensor(e!) member, Tensor(f!) n_obj, Tensor(g!) overflow, int stream, Tensor? overflow_in=None) -> ()", rig_fuse);
   m.def("project_labels(float[] camera, Tensor world_points, Tensor T_WC, float scale, float crop_x, float crop_y, Tensor(a!) labels, int stream) -> ()", project_labels);
   m.def("render_targets(Tensor labels, Tensor n_obj, int[] type_count, Tensor(a!) heat, Tensor(b!) depth, Tensor(c!) centers, int stream) -> ()", render_targets);
   m.def("keypoint_loss(Tensor[] p_heat, Tensor[] p_depth, Tensor[] p_centers, int n_first, int n_total, Tensor? labels, Tensor? n_obj, int[] type_count, "

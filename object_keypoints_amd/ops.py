@@ -1239,6 +1239,99 @@ def stereo_triangulate_rig(table, count, xyc, match, first_pair=0, correct_match
     return points
 
 
+# ---- a rig's pairs fused into one object list in the rig frame (okp_rig_fuse, csrc/okp_rig.hip) ----------------------------------------
+FUSE_OVERFLOW = 4            # bit of rig_fuse()'s overflow word: a key-point type had more than cap_f fused clusters
+RIG_MAX_PAIRS, RIG_MAX_TYPES, RIG_MAX_ROWS, RIG_MAX_FUSED = 32, 8, 1024, 64      # include/okp.h OKP_RIG_MAX_*
+RIG_POSE_TOLERANCE = 1e-9    # |R R^T - I| and |det R - 1| allowed in a pose (a calibration file's rounding)
+
+
+def rig_poses(T_BL_list):
+    """The pose table of a rig: a sequence of P transforms T_BL (4 x 4: pair p's left-camera coordinates -> rig coordinates) -> float64
+    HOST tensor [P, 12], row p = T_BL[p][:3] row-major, which the caller moves to the device once (as stereo_rig's table).  The kernel
+    cannot check a device table, so a bad pose is refused here: non-finite entries, a last row other than [0, 0, 0, 1], a rotation block
+    that is not orthonormal with determinant +1 (to RIG_POSE_TOLERANCE), an empty list."""
+    poses = list(T_BL_list)
+    if not poses:
+        raise OkpError("a rig has at least one stereo pair: no poses given")
+    if len(poses) > RIG_MAX_PAIRS:
+        raise OkpError(f"{len(poses)} poses: a fused rig has at most {RIG_MAX_PAIRS} stereo pairs")
+    out = np.empty((len(poses), 12), dtype=np.float64)
+    for p, T in enumerate(poses):
+        T = np.asarray(T, dtype=np.float64)
+        if T.shape != (4, 4) or not np.isfinite(T).all():
+            raise OkpError(f"pose {p}: T_BL must be a finite 4 x 4 transform")
+        if not np.array_equal(T[3], [0.0, 0.0, 0.0, 1.0]):
+            raise OkpError(f"pose {p}: T_BL's last row is {T[3].tolist()}, not [0, 0, 0, 1]")
+        R = T[:3, :3]
+        if np.abs(R @ R.T - np.eye(3)).max() > RIG_POSE_TOLERANCE:
+            raise OkpError(f"pose {p}: the rotation block of T_BL is not orthonormal (|R R^T - I| = {np.abs(R @ R.T - np.eye(3)).max():.3g})")
+        if abs(np.linalg.det(R) - 1.0) > RIG_POSE_TOLERANCE:
+            raise OkpError(f"pose {p}: the rotation block of T_BL has determinant {np.linalg.det(R):.6g}, not +1 (a reflection)")
+        out[p] = T[:3].reshape(12)
+    return torch.from_numpy(out)
+
+
+def check_fuse_radii(merge_radius, object_radius):
+    for name, r in (("merge_radius", merge_radius), ("object_radius", object_radius)):
+        try:
+            ok = bool(np.isfinite(float(r))) and float(r) > 0.0
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            raise OkpError(f"{name} = {r!r}: a positive, finite length in metres")
+    return float(merge_radius), float(object_radius)
+
+
+def rig_fuse(points, poses, type_count, merge_radius, object_radius, cap_f, overflow=None):
+    """A tick's per-pair 3D points fused into one object list in the rig frame (okp_rig_fuse; the four steps - transform, cluster each
+    type across the pairs, fuse, group around the centres - are specified in include/okp.h).
+        points [P,K,cap,4] float64 (device): the payload of stereo_triangulate(_rig) / tick_sharded's gather, NaN confidence = empty slot
+        poses  [P,12] float64 (device): rig_poses(...) moved to the device
+        type_count: K-1 ints, clusters of type k >= 1 kept per object; merge_radius, object_radius: metres; cap_f: clusters kept per type
+        overflow: the tick's overflow word (0-d or 1-element int32 device tensor) to fold into the result, or None
+    -> {"fused" [K,cap_f,4] float64, "n_fused" [K], "views" [K,cap_f], "object" [K,cap_f], "member" [P,K,cap] int32, "n_obj" 0-d int32,
+        "overflow" 0-d int32 = overflow | FUSE_OVERFLOW where a type had more than cap_f clusters}.  Two launches, no host sync."""
+    require_cuda(points, "points")
+    require_cuda(poses, "poses")
+    if points.dtype != torch.float64 or points.dim() != 4 or points.shape[3] != 4:
+        raise OkpError("points must be float64 [P,K,cap,4] (the stereo tick's payload)")
+    n_pairs, k, cap = (int(v) for v in points.shape[:3])
+    if poses.dtype != torch.float64 or tuple(poses.shape) != (n_pairs, 12) or poses.device != points.device:
+        raise OkpError(f"poses must be float64 [{n_pairs},12] on the points' device (rig_poses): one row for each of the {n_pairs} pairs of points")
+    tc = [int(c) for c in type_count]
+    if len(tc) != k - 1 or any(c < 1 for c in tc):
+        raise OkpError(f"type_count {tc}: {k - 1} positive counts, one for each key-point type after the centre")
+    merge_radius, object_radius = check_fuse_radii(merge_radius, object_radius)
+    cap_f = int(cap_f)
+    if not 1 <= n_pairs <= RIG_MAX_PAIRS or not 1 <= k <= RIG_MAX_TYPES or not 1 <= cap <= STEREO_MAX_CAPACITY or n_pairs * cap > RIG_MAX_ROWS:
+        raise OkpError(f"points [{n_pairs},{k},{cap},4]: at most {RIG_MAX_PAIRS} pairs, {RIG_MAX_TYPES} types, {STEREO_MAX_CAPACITY} slots and "
+                       f"{RIG_MAX_ROWS} rows (pairs x slots) per type")
+    if not 1 <= cap_f <= RIG_MAX_FUSED:
+        raise OkpError(f"cap_f = {cap_f} outside [1, {RIG_MAX_FUSED}]")
+    if overflow is not None:
+        require_cuda(overflow, "overflow")
+        if overflow.dtype != torch.int32 or overflow.numel() != 1 or overflow.device != points.device:
+            raise OkpError("overflow must be one int32 on the points' device (a tick's overflow word)")
+        overflow = overflow.reshape(1)
+    points, poses = points.contiguous(), poses.contiguous()
+    dev = points.device
+    fused = torch.empty((k, cap_f, 4), dtype=torch.float64, device=dev)
+    n_fused = torch.empty((k,), dtype=torch.int32, device=dev)
+    views = torch.empty((k, cap_f), dtype=torch.int32, device=dev)
+    obj = torch.empty((k, cap_f), dtype=torch.int32, device=dev)
+    member = torch.empty((n_pairs, k, cap), dtype=torch.int32, device=dev)
+    words = torch.empty((2,), dtype=torch.int32, device=dev)        # n_obj, overflow
+    T = _ops()
+    if T is not None:
+        _dispatch(T.rig_fuse, points, poses, tc, merge_radius, object_radius, fused, n_fused, views, obj, member, words[0:1], words[1:2], stream_int(), overflow)
+    else:
+        tca = (ctypes.c_int32 * max(1, k - 1))(*tc)
+        _lib.check(_lib.lib().okp_rig_fuse(points.data_ptr(), poses.data_ptr(), n_pairs, k, cap, tca, merge_radius, object_radius, cap_f,
+                                           overflow.data_ptr() if overflow is not None else None, fused.data_ptr(), n_fused.data_ptr(), views.data_ptr(),
+                                           obj.data_ptr(), member.data_ptr(), words[0:1].data_ptr(), words[1:2].data_ptr(), stream_handle()), "okp_rig_fuse")
+    return {"fused": fused, "n_fused": n_fused, "views": views, "object": obj, "member": member, "n_obj": words[0], "overflow": words[1]}
+
+
 # ---- scoring labelled scenes (csrc/okp_targets.hip) ---------------------------------------------------------------------------------
 TARGET_SIZE = 64             # SceneDataset.prediction_size
 TARGET_MAX_MAPS = 16         # K

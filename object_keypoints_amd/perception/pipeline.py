@@ -864,9 +864,18 @@ class StereoStreamPipeline:
     calibrated on its own (pair p = frames 2p and 2p + 1, its points in its own left camera frame); a rig's ticks hold exactly its 2P
     frames (tick_device / tick_sharded: a shard of them, first_pair = the shard's first pair).  The calibration is validated and packed
     at construction (ops.stereo_rig: a bad one fails here, before any device work) and uploaded to the frames' device on the first
-    device tick; the device copy lives as long as the pipeline, since captured ticks read it on every replay."""
+    device tick; the device copy lives as long as the pipeline, since captured ticks read it on every replay.
 
-    def __init__(self, net, stereo_camera, keypoint_config, capacity=16, max_distance=3.0):
+    Fusion (optional): rig_poses = one 4 x 4 transform T_BL per pair (the pair's left-camera coordinates -> rig coordinates) with
+    merge_radius and object_radius in metres - the three are given together or not at all.  A rig needs one pose per StereoCamera; with
+    a single StereoCamera the number of poses fixes the number of pairs of a tick.  The device ticks (tick_device, capture_device - inside
+    the graph -, tick_sharded - after the gather, on every rank) then end with okp_rig_fuse and carry the key "fused" (ops.rig_fuse's dict:
+    one list of clusters per type in the rig frame, grouped into objects), and their "overflow" word carries ops.FUSE_OVERFLOW;
+    rig_objects(out) reads it.  fuse_capacity: fused clusters kept per type (default: the kernel's limit, ops.RIG_MAX_FUSED).  Poses and
+    radii are validated at construction (ops.rig_poses).  tick(), the host tick, is unchanged and does not fuse."""
+
+    def __init__(self, net, stereo_camera, keypoint_config, capacity=16, max_distance=3.0, rig_poses=None, merge_radius=None, object_radius=None,
+                 fuse_capacity=None):
         self.net = net
         self.rig = None if hasattr(stereo_camera, "left_camera") else list(stereo_camera)       # one StereoCamera, or a sequence of them
         self.stereo_cameras = self.rig if self.rig is not None else [stereo_camera]
@@ -882,6 +891,38 @@ class StereoStreamPipeline:
                       for st in self.stereo_cameras]
         self.cam_l, self.cam_r = self._cams[0]
         self._graph = None
+        self._poses_host = None                                         # fusion off
+        given = [n for n, v in (("rig_poses", rig_poses), ("merge_radius", merge_radius), ("object_radius", object_radius)) if v is not None]
+        if given and len(given) != 3:
+            raise OkpError(f"fusion takes rig_poses, merge_radius and object_radius together: only {', '.join(given)} given")
+        if not given and fuse_capacity is not None:
+            raise OkpError("fuse_capacity without rig_poses, merge_radius and object_radius")
+        if given:
+            self._poses_host = ops.rig_poses(rig_poses)
+            self._poses = {}                                            # device -> the uploaded pose table
+            self.n_fused_pairs = int(self._poses_host.shape[0])
+            if self.rig is not None and self.n_fused_pairs != len(self.rig):
+                raise OkpError(f"{self.n_fused_pairs} rig poses for a rig of {len(self.rig)} stereo pairs: one pose per pair")
+            self.merge_radius, self.object_radius = ops.check_fuse_radii(merge_radius, object_radius)
+            self.fuse_capacity = ops.RIG_MAX_FUSED if fuse_capacity is None else int(fuse_capacity)
+            if not 1 <= self.fuse_capacity <= ops.RIG_MAX_FUSED:
+                raise OkpError(f"fuse_capacity = {fuse_capacity} outside [1, {ops.RIG_MAX_FUSED}]")
+            if len(self.config) > ops.RIG_MAX_TYPES or self.n_fused_pairs * self.capacity > ops.RIG_MAX_ROWS:
+                raise OkpError(f"fusion holds at most {ops.RIG_MAX_TYPES} key-point types and {ops.RIG_MAX_ROWS} rows (pairs x capacity) per type: "
+                               f"{len(self.config)} types, {self.n_fused_pairs} x {self.capacity} rows asked for")
+
+    def _check_fused_tick(self, n_pairs, first_pair=0):
+        """A fused tick holds every pair of the rig: the clusters are formed across all of them."""
+        if self._poses_host is not None and (n_pairs != self.n_fused_pairs or first_pair != 0):
+            raise OkpError(f"a fused tick holds the {2 * self.n_fused_pairs} frames of all {self.n_fused_pairs} posed stereo pairs, from pair 0 on "
+                           f"({2 * n_pairs} frames from pair {first_pair} on given; a shard of the rig goes through tick_sharded)")
+
+    def _fuse(self, points, overflow):
+        dev = points.device
+        poses = self._poses.get(dev)
+        if poses is None:
+            poses = self._poses[dev] = self._poses_host.to(dev)
+        return ops.rig_fuse(points, poses, self.config[1:], self.merge_radius, self.object_radius, self.fuse_capacity, overflow=overflow)
 
     def _check_rig_frames(self, frames, first_pair=0):
         """A rig's tick holds 2 frames for each of its pairs first_pair .. first_pair + P - 1 (a single calibration: any P)."""
@@ -1000,7 +1041,7 @@ class StereoStreamPipeline:
             raise OkpError(f"capacity = {self.capacity}: the device association holds at most {ops.STEREO_MAX_CAPACITY} peaks per map")
         return self._check_rig_frames(frames, first_pair)
 
-    def tick_device(self, frames, heat_override=None, first_pair=0):
+    def tick_device(self, frames, heat_override=None, first_pair=0, _fuse=True):
         """The whole tick on the device, with no host wait anywhere: network -> peak-NMS -> left/right association (okp_stereo_match) ->
         triangulation of every matched slot (okp_stereo_triangulate).  Same frames as tick().  Returns a dict of device tensors
             heat, depth [2P,K,H,W], count [2P,K] int32, xyc [2P,K,cap,3] fp32, match [P,K,cap] int32,
@@ -1008,8 +1049,12 @@ class StereoStreamPipeline:
             holds more than `capacity` peaks, bit 1 ops.RANGE_OVERFLOW the split-product network's fp16-range flag)
         results(out) turns it into tick()'s return value.  `points` is the fixed-capacity payload all_gather_keypoints carries
         (tick_sharded).  first_pair: the rig-wide index of the frames' first pair (a rig: pair p of the frames is calibrated as the
-        rig's pair first_pair + p; a single calibration: no effect)."""
+        rig's pair first_pair + p; a single calibration: no effect).  With rig_poses (see the class) the tick ends with okp_rig_fuse: the
+        dict gains "fused" and its overflow word the bit ops.FUSE_OVERFLOW; such a tick holds all the posed pairs."""
         first_pair = self._check_device_tick(frames, first_pair)
+        fuse = _fuse and self._poses_host is not None           # (tick_sharded fuses after the gather instead)
+        if fuse:
+            self._check_fused_tick(frames.shape[0] // 2, first_pair)
         with torch.no_grad():
             # split-product networks: the fp16-range flag is folded into `overflow` on the device instead of being read here (as
             # BatchedKeypointPipeline.forward_device does), except with on_overflow = "float32", where the pass is judged on the host
@@ -1022,7 +1067,11 @@ class StereoStreamPipeline:
             table = self._table(frames.device)                 # (a single calibration: the one-entry table, broadcast to every pair)
             match, overflow = ops.stereo_match_rig(table, count, xyc, self.assoc.max_distance, first_pair=first_pair, range_flag=range_flag)
             points = ops.stereo_triangulate_rig(table, count, xyc, match, first_pair=first_pair)
-        return {"heat": heat, "depth": depth, "count": count, "xyc": xyc, "match": match, "points": points, "overflow": overflow}
+            out = {"heat": heat, "depth": depth, "count": count, "xyc": xyc, "match": match, "points": points, "overflow": overflow}
+            if fuse:
+                out["fused"] = self._fuse(points, overflow)
+                out["overflow"] = out["fused"]["overflow"]
+        return out
 
     def capture_device(self, frames, heat_override=None, first_pair=0):
         """Capture the WHOLE tick_device (network, NMS, association, triangulation, overflow word) for this frame shape into one hipGraph;
@@ -1031,6 +1080,7 @@ class StereoStreamPipeline:
         input of the graph like the frames) and step.replay(); the outputs are step.static_out (tick_device's dict).  first_pair: as for
         tick_device; the warm-up ticks upload the calibration table before the capture begins."""
         first_pair = self._check_device_tick(frames, first_pair)
+        self._check_fused_tick(frames.shape[0] // 2, first_pair)
         static_in = frames.clone()
         static_heat = heat_override.clone() if heat_override is not None else None
         for _ in range(2):                                   # warm-up: plans, allocator pools, kernel attributes, calibration table
@@ -1045,6 +1095,7 @@ class StereoStreamPipeline:
             ops.SIDE_STREAMS = keep
         step = CapturedTick(self.net, graph, static_in, static_out, static_heat)
         step._table = self._table(frames.device)               # (the graph reads it on every replay)
+        step._poses = self._poses.get(frames.device) if self._poses_host is not None else None       # (and the pose table)
         return step
 
     def results(self, out):
@@ -1075,7 +1126,8 @@ class StereoStreamPipeline:
             {"points": [n_pairs_total, K, cap, 4] fp64 - ONE all_gather_keypoints of the per-rank payloads, ordered by pair,
              "overflow": 0-d int32 - the overflow words folded over the ranks on the device (one all_reduce, MAX: set on one rank = set
                          on every rank), "local": this rank's tick_device dict (None for a rank without pairs)}
-        which results() reads.  A rank without pairs (world > n_pairs_total) joins both collectives with an empty block.  Without a
+        which results() reads; with rig_poses also "fused": okp_rig_fuse of the gathered payload, run on every rank (the same bits on each),
+        and "overflow" then carries ops.FUSE_OVERFLOW as well.  A rank without pairs (world > n_pairs_total) joins both collectives with an empty block.  Without a
         process group it is tick_device on the whole rig.  A rig of individually calibrated pairs: n_pairs_total == len(rig), and each
         rank's pairs are calibrated by their rig-wide index (first_pair = the shard's start)."""
         import torch.distributed as dist
@@ -1085,17 +1137,22 @@ class StereoStreamPipeline:
         if self.rig is not None and int(n_pairs_total) != len(self.rig):
             raise OkpError(f"n_pairs_total = {n_pairs_total}, but the rig has {len(self.rig)} stereo pairs")
         self._check_device_tick(frames_local)
+        if self._poses_host is not None and int(n_pairs_total) != self.n_fused_pairs:
+            raise OkpError(f"n_pairs_total = {n_pairs_total}, but {self.n_fused_pairs} rig poses were given")
         if not dist.is_initialized():
             if frames_local.shape[0] != 2 * n_pairs_total:
                 raise OkpError(f"{frames_local.shape[0]} frames for {n_pairs_total} stereo pairs")
             out = self.tick_device(frames_local, heat_override=heat_override)
-            return {"points": out["points"], "overflow": out["overflow"], "local": out}
+            whole = {"points": out["points"], "overflow": out["overflow"], "local": out}
+            if "fused" in out:
+                whole["fused"] = out["fused"]
+            return whole
         start, n_local = distributed.shard(int(n_pairs_total), dist.get_rank(), dist.get_world_size())
         if frames_local.shape[0] != 2 * n_local:
             raise OkpError(f"rank {dist.get_rank()} holds {frames_local.shape[0]} frames; shard({n_pairs_total}, {dist.get_rank()}, "
                            f"{dist.get_world_size()}) gives it {n_local} stereo pairs = {2 * n_local} frames")
         if n_local:
-            local = self.tick_device(frames_local, heat_override=heat_override, first_pair=start)
+            local = self.tick_device(frames_local, heat_override=heat_override, first_pair=start, _fuse=False)
             points, flag = local["points"], local["overflow"].reshape(1).clone()
         else:
             local, dev = None, frames_local.device
@@ -1103,4 +1160,48 @@ class StereoStreamPipeline:
             flag = torch.zeros((1,), dtype=torch.int32, device=dev)
         gathered = distributed.all_gather_keypoints(points, total_frames=int(n_pairs_total))
         dist.all_reduce(flag, op=dist.ReduceOp.MAX)
-        return {"points": gathered, "overflow": flag[0], "local": local}
+        out = {"points": gathered, "overflow": flag[0], "local": local}
+        if self._poses_host is not None:
+            with torch.no_grad():
+                out["fused"] = self._fuse(gathered, flag)
+            out["overflow"] = out["fused"]["overflow"]
+        return out
+
+    def rig_objects(self, out):
+        """The objects of a fused device tick (tick_device, a CapturedTick's outputs or tick_sharded's dict, of a pipeline built with
+        rig_poses) in the rig frame: a list over objects of
+            {"p_B": [(1, 3) centre, (n_1, 3), ..., (n_{K-1}, 3)] float64 points in rig coordinates - the nesting of
+                    ObjectKeypointPipeline's 'p_C', one array per key-point type, n_k <= the type's count, in cluster order,
+             "confidence": [(1,), (n_1,), ...] float64, "views": [(1,), (n_1,), ...] int32 bit masks of the contributing pairs}
+        read in ONE device -> host copy.  Raises OkpError when the tick's overflow word is set, as results() does (bit ops.FUSE_OVERFLOW:
+        a type had more than fuse_capacity clusters).  tick(), the host tick, does not fuse: its return value is not accepted here."""
+        if not isinstance(out, dict) or "fused" not in out:
+            raise OkpError("rig_objects reads a fused device tick: the dict of tick_device / capture_device / tick_sharded of a pipeline "
+                           "built with rig_poses (the host tick() does not fuse)")
+        f = out["fused"]
+        K, cap_f = f["views"].shape
+        parts = [out["overflow"].reshape(1), f["n_obj"].reshape(1), f["n_fused"], f["views"].reshape(-1), f["object"].reshape(-1)]
+        flat = torch.cat([t.to(torch.float64) for t in parts] + [f["fused"].reshape(-1)]).cpu().numpy()          # the one D2H copy (int32 is exact in fp64)
+        flag, n_obj = int(flat[0]), int(flat[1])
+        if flag & 1:
+            raise OkpError("peak capacity exceeded in a tick; raise `capacity`")
+        if flag & ops.RANGE_OVERFLOW:
+            raise OkpError("an activation of the split-product network left the fp16 range in this tick: its maps are not fp32-grade "
+                           "(load the network with on_overflow='float32', or run it in torch.float32)")
+        if flag & ops.FUSE_OVERFLOW:
+            raise OkpError("a key-point type had more fused clusters than fit in a tick; raise `fuse_capacity`")
+        n_fused = flat[2:2 + K].astype(np.int64)
+        at = 2 + K
+        views = flat[at:at + K * cap_f].astype(np.int32).reshape(K, cap_f)
+        obj = flat[at + K * cap_f:at + 2 * K * cap_f].astype(np.int64).reshape(K, cap_f)
+        rows = flat[at + 2 * K * cap_f:].reshape(K, cap_f, 4)
+        objects = []
+        for o in range(n_obj):
+            p_B, conf, seen = [], [], []
+            for k in range(K):
+                sel = np.nonzero(obj[k, :n_fused[k]] == o)[0]
+                p_B.append(np.ascontiguousarray(rows[k, sel, :3]))
+                conf.append(np.ascontiguousarray(rows[k, sel, 3]))
+                seen.append(views[k, sel])
+            objects.append({"p_B": p_B, "confidence": conf, "views": seen})
+        return objects

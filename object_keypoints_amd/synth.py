@@ -267,3 +267,66 @@ def render_rig_heat(rig, pairs=None, shift=0.0, crowd=None, size=64):
                 for c in range(3):
                     heat[2 * i + crowd[1], crowd[2]] += np.exp(-((xs - 8 - 12 * a) ** 2 + (ys - 50 - 5 * c) ** 2) / 2.0)
     return np.clip(heat, 0.0, 1.0)
+
+
+# ----------------------------------------------------------------------------
+# the same rig with a pose per pair, and one scene in rig coordinates (StereoStreamPipeline with rig_poses: okp_rig_fuse)
+# ----------------------------------------------------------------------------
+
+# two objects in the rig (body) frame: per object 1 centre (type 0), 1 point of type 1, 3 points of type 2 - RIG_SCENE's object and a
+# second one beside and behind it, far enough apart that every key point is nearer to its own centre than to the other
+RIG_FUSE_SCENE = (
+    {0: [[-0.12, -0.03, 0.00]], 1: [[-0.06, -0.10, 0.03]], 2: [[-0.12, 0.09, -0.03], [-0.224, -0.08, 0.04], [-0.05, -0.135, 0.03]]},
+    {0: [[0.14, 0.05, 0.16]], 1: [[0.20, -0.02, 0.19]], 2: [[0.14, -0.03, 0.13], [0.22, 0.14, 0.18], [0.036, 0.03, 0.21]]},
+)
+# metres.  Points of one type are at least 0.14 m apart - and 0.05 m apart in height, more than the epipolar gate of the stereo tests in
+# every pair's maps, so that each pair's left / right association is unambiguous -; with views that miss the truth by e < 0.03 a merge
+# radius between 2 e and 0.14 - 2 e joins the views of one point and nothing else; a key point lies within 0.13 m of its own centre and at
+# least 0.13 m farther from the other one, so the object radius holds the former plus 2 e.  (The tests assert these conditions on the
+# tick's own payload.)
+RIG_FUSE_MERGE_RADIUS = 0.08
+RIG_FUSE_OBJECT_RADIUS = 0.18
+# per pair: the yaw (about the rig's y axis, degrees) from which it looks at the rig frame's origin, its height above it and its distance
+# to it - growing with the baseline, so that each pair works in a depth range its baseline resolves on 64 x 64 maps
+_RIG_FUSE_YAW = (0.0, 9.0, -8.0, 14.0)
+_RIG_FUSE_HEIGHT = (0.0, 0.03, -0.02, 0.04)
+_RIG_FUSE_DISTANCE = (0.50, 0.62, 0.75, 0.90)
+
+
+def rig_poses(n_pairs=4):
+    """T_BL (4 x 4: pair q's left-camera coordinates -> rig coordinates) of stereo_rig's pairs: pair q looks at the rig frame's origin
+    - where RIG_FUSE_SCENE lies - from a yaw of its own, at the distance rig_scene_points gives its baseline, offset by half the baseline
+    so that the scene sits between its two cameras."""
+    poses = []
+    for q in range(n_pairs):
+        b = RIG_BASELINES[q]
+        a = np.deg2rad(_RIG_FUSE_YAW[q])
+        c, s = np.cos(a), np.sin(a)
+        R = np.array([[c, 0.0, s], [0.0, 1.0, 0.0], [-s, 0.0, c]])                 # camera axes in rig coordinates
+        in_camera = np.array([b / 2, _RIG_FUSE_HEIGHT[q], _RIG_FUSE_DISTANCE[q]])     # the rig's origin, seen by the left camera
+        T = np.eye(4)
+        T[:3, :3] = R
+        T[:3, 3] = -R @ in_camera
+        poses.append(T)
+    return poses
+
+
+def rig_fuse_scene(shift=0.0):
+    """[{type: (n, 3) points in rig coordinates}] per object of the fused rig scene (shift: metres along the rig's x axis)."""
+    return [{k: np.array(pts) + np.array([shift, 0.0, 0.0]) for k, pts in obj.items()} for obj in RIG_FUSE_SCENE]
+
+
+def render_rig_fuse_heat(rig, poses, shift=0.0, size=64):
+    """Heat maps [2 len(rig), K, size, size] float32 (NumPy) of rig_fuse_scene: every object's points taken into pair q's left-camera
+    frame by inv(poses[q]) and rendered through pair q's OWN left and right camera, as render_rig_heat does."""
+    ys, xs = np.meshgrid(np.arange(size, dtype=np.float32), np.arange(size, dtype=np.float32), indexing="ij")
+    heat = np.zeros((2 * len(rig), len(RIG_FUSE_SCENE[0]), size, size), np.float32)
+    for q, st in enumerate(rig):
+        T_LB = np.linalg.inv(np.asarray(poses[q], dtype=np.float64))
+        for obj in rig_fuse_scene(shift):
+            for k, X_B in obj.items():
+                X = X_B @ T_LB[:3, :3].T + T_LB[:3, 3]
+                for side, (cam, T) in enumerate(((st.left_camera, np.eye(4)), (st.right_camera, st.T_RL))):
+                    for px, py in cam.project(X, T):
+                        heat[2 * q + side, k] += np.exp(-((xs - px) ** 2 + (ys - py) ** 2) / 4.0)
+    return np.clip(heat, 0.0, 1.0)
