@@ -2,6 +2,9 @@
 
 torch is used for device memory and streams only: every computation below is a call into
 libokp_hip.so on `torch.cuda.current_stream()`.  Nothing here has a CPU path.
+
+Every wrapper checks its arguments and makes ONE call, `_dispatch(_ops().<entry point>, ...)`, with the signature of the dispatcher schema
+(csrc/okp_torch.cpp): _ops() is torch.ops.okp or, where the shim is not in force, the ctypes binding of the same signatures (_ctypes_ops.py).
 """
 import ctypes
 import dataclasses
@@ -10,10 +13,10 @@ import os
 import numpy as np
 import torch
 
-from . import _lib
+from . import _ctypes_ops, _lib
+from ._ctypes_ops import _DTYPES, _okp_dtype as okp_dtype      # (torch dtype -> OKP_* code: the adapter marshals with the same table)
 from ._lib import OKP_BF16, OKP_F16, OKP_F32, OKP_F32X3, ACT_NONE, ACT_RELU, ACT_SIGMOID, OkpError
 
-_DTYPES = {torch.float32: OKP_F32, torch.bfloat16: OKP_BF16, torch.float16: OKP_F16}
 HALF_DTYPES = (torch.bfloat16, torch.float16)     # 16-bit activations / weights, fp32 accumulate: the MFMA throughput precisions
 
 
@@ -81,7 +84,7 @@ class f32_split:
         _MODE.split, _MODE.mix, _MODE.range_flag = self.prev
 
 
-def _attach_range_flag(plan, setter_name):
+def _attach_range_flag(plan):
     """Give a freshly built split-product or float16 plan the range flag of the enclosing f32_split context, if there is one (the float16
     plan's launches then run the range-guarded fp16 kernels)."""
     flag = getattr(_MODE, "range_flag", None)
@@ -91,11 +94,8 @@ def _attach_range_flag(plan, setter_name):
     require_cuda(flag, "range_flag")
     if flag.dtype != torch.int32 or flag.numel() != 1:
         raise OkpError("range_flag is an int32 device tensor of one element")
-    T = _ops()
-    if T is not None:
-        _dispatch(getattr(T, setter_name), plan._h, flag)
-    else:
-        _lib.check(getattr(_lib.lib(), "okp_" + setter_name)(plan._h, flag.data_ptr()), "okp_" + setter_name)
+    B = _ops()
+    _dispatch(B.stem_set_range_flag if isinstance(plan, StemPlan) else B.conv_set_range_flag, plan._h, flag)
     plan._range_flag = flag              # (the plan's launches write through this pointer: keep the tensor alive with the plan)
 
 
@@ -112,13 +112,6 @@ def parse_compute_dtype(compute_dtype):
     return compute_dtype, False, False
 
 
-def okp_dtype(torch_dtype):
-    try:
-        return _DTYPES[torch_dtype]
-    except KeyError:
-        raise OkpError(f"unsupported activation dtype {torch_dtype}; use torch.float32, torch.bfloat16 or torch.float16")
-
-
 # torch.cuda.current_stream() builds a Stream object through four Python layers (8 us under a profiler, ~75 calls per network pass);
 # the raw handle of the current stream of the current device is one C call
 _RAW_STREAM = getattr(torch._C, "_cuda_getCurrentRawStream", None)
@@ -130,24 +123,25 @@ def stream_int():
     return torch.cuda.current_stream().cuda_stream
 
 
-def stream_handle():
-    return ctypes.c_void_p(stream_int())
-
-
 def _dispatch(fn, *args):
-    """Call a torch.ops.okp entry point; its TORCH_CHECK failures surface as OkpError like the ctypes path's error codes."""
+    """Call an entry point of the binding in force; the shim's TORCH_CHECK failures surface as OkpError like the ctypes binding's error codes
+    (an OkpError of the ctypes binding passes through as it is)."""
     try:
         return fn(*args)
+    except OkpError:
+        raise
     except RuntimeError as e:
         raise OkpError(str(e).split("\n")[0]) from None
 
 
 def _ops():
-    """torch.ops.okp, or None with the ctypes call that follows counted (COUNTERS["ctypes_launches"])."""
-    T = _lib.torch_ops()
-    if T is None:
+    """The binding of the call that follows: torch.ops.okp, or - where _lib.torch_ops() has none - its ctypes twin _ctypes_ops (the same
+    entry points with the same signatures), that call counted in COUNTERS["ctypes_launches"].  Looked up per call."""
+    B = _lib.torch_ops()
+    if B is None:
         COUNTERS["ctypes_launches"] += 1
-    return T
+        return _ctypes_ops
+    return B
 
 
 def _cam_list(cam):
@@ -235,9 +229,6 @@ class Act:
         return a
 
 
-_NULL_TENSOR = _lib.okp_tensor(None, 0, 0, 0, 0)
-
-
 def _refuse_pairs(*acts):
     for a in acts:
         if a is not None and getattr(a, "pairs", False):
@@ -249,7 +240,6 @@ class ConvPlan:
 
     def __init__(self, dtype, cins, strides, cout, taps, bias=None, relu=False, alg_k=None, tap_terms=None):
         """tap_terms (split-product plans only): per tap 3 (three-term product, the default) or 1 (single fp16 term)."""
-        L = _lib.lib()
         self.dtype = dtype
         self.split = bool(getattr(_MODE, "split", False) and dtype == torch.float32)      # OKP_F32X3: fp32 tensors, products on the fp16 matrix pipe
         self.allow_compact = False       # set by the one consumer that knows how to read an even-pixels-only source (residual's skip plan)
@@ -259,7 +249,6 @@ class ConvPlan:
         self.cins = list(cins)
         self._strides = (list(strides) + [1])[:2]
         self._tap_srcs = [t[0] for t in taps]
-        n_taps = len(taps)
         keep = []
         k = 0
         for i, (src, dy, dx, w) in enumerate(taps):
@@ -274,30 +263,14 @@ class ConvPlan:
             b = np.ascontiguousarray(bias, dtype=np.float32)
             if b.shape != (cout,):
                 raise OkpError("bias shape")
-        if self.tap_terms is not None and len(self.tap_terms) != n_taps:
+        if self.tap_terms is not None and len(self.tap_terms) != len(taps):
             raise OkpError("tap_terms: one entry per tap")
         code = OKP_F32X3 if self.split else okp_dtype(dtype)
         act = ACT_RELU if relu else ACT_NONE
-        T = _ops()
-        if T is not None:       # torch.ops.okp.conv_create: host tensors in, opaque handle out
-            self._h = _dispatch(T.conv_create, code, list(cins), (list(strides) + [1] * len(cins))[:len(cins)], cout, [t[0] for t in taps], [t[1] for t in taps], [t[2] for t in taps],
-                                [torch.from_numpy(w) for w in keep], torch.from_numpy(b) if b is not None else None, act, self.tap_terms or [])
-            _attach_range_flag(self, "conv_set_range_flag")
-            return
-        arr_t = (_lib.okp_tap * n_taps)()
-        for i, (src, dy, dx, _) in enumerate(taps):
-            arr_t[i] = _lib.okp_tap(src, dy, dx, keep[i].ctypes.data_as(ctypes.POINTER(ctypes.c_float)))
-        cin_arr = (ctypes.c_int32 * 2)(*(list(cins) + [0])[:2])
-        st_arr = (ctypes.c_int32 * 2)(*(list(strides) + [1])[:2])
-        bp = b.ctypes.data_as(ctypes.POINTER(ctypes.c_float)) if b is not None else None
-        if self.tap_terms is not None:
-            terms = (ctypes.c_uint8 * n_taps)(*self.tap_terms)
-            self._h = L.okp_conv_create_x3(self.n_src, cin_arr, st_arr, cout, n_taps, arr_t, terms, bp, act)
-        else:
-            self._h = L.okp_conv_create(code, self.n_src, cin_arr, st_arr, cout, n_taps, arr_t, bp, act)
-        if not self._h:
-            raise OkpError("okp_conv_create: " + L.okp_last_error().decode())
-        _attach_range_flag(self, "conv_set_range_flag")
+        # conv_create: host tensors in, opaque handle out
+        self._h = _dispatch(_ops().conv_create, code, list(cins), (list(strides) + [1] * len(cins))[:len(cins)], cout, [t[0] for t in taps], [t[1] for t in taps],
+                            [t[2] for t in taps], [torch.from_numpy(w) for w in keep], torch.from_numpy(b) if b is not None else None, act, self.tap_terms or [])
+        _attach_range_flag(self)
 
     def __del__(self):
         h, self._h = getattr(self, "_h", None), None
@@ -311,19 +284,7 @@ class ConvPlan:
         """True if a launch of this shape (dense output of ho*out_step x wo*out_step pixels, no depth-wise branch / fp16 side output) runs
         on the patch-resident kernel (tile 13 of okp_conv_forward's heuristic, okp_conv_select_tile) - the one kernel that reads and
         writes pair-format activations."""
-        tile = tile or FORCE_TILE
-        T = _ops()
-        if T is not None:
-            return bool(_dispatch(T.conv_picks_patch, self._h, n, ho, wo, list(src_pix_strides), self.cout, out_step, n_classes, tile))
-        a = _lib.okp_conv_args()
-        a.n, a.ho, a.wo = n, ho, wo
-        for i, ps in enumerate(src_pix_strides):
-            a.src[i] = _lib.okp_tensor(1, 1, 1, ps, 1)          # (the heuristic reads pixel strides and the output grid only)
-        a.out = _lib.okp_tensor(1, ho * out_step, wo * out_step, self.cout, 1)
-        a.out_step, a.n_classes = out_step, n_classes
-        if tile:                                                # a forced tile 13 on a shape the kernel refuses is not a "yes" (the launch would end in EINVAL)
-            return tile == 13 and bool(_lib.lib().okp_conv_patch_applies(self._h, ctypes.byref(a)))
-        return _lib.lib().okp_conv_select_tile(self._h, ctypes.byref(a)) == 13
+        return bool(_dispatch(_ops().conv_picks_patch, self._h, n, ho, wo, list(src_pix_strides), self.cout, out_step, n_classes, tile or FORCE_TILE))
 
     def _algorithmic_bytes(self, srcs, out, ho, wo, res, out_step, n_classes, dw, out16, write_out, out_subsample):
         """Compulsory HBM bytes of one launch (bench.py's roofline of HBM-bound launches): every source pixel the taps sample once,
@@ -378,6 +339,7 @@ class ConvPlan:
             raise OkpError("pair-format activations belong to split-product (ops.F32X3) plans")
         if (res is not None and res.pairs) or (dw is not None and (src_pairs or out_pairs)):
             raise OkpError("pair format: the residual stays float32, and the depth-wise branch does not take it")
+        _refuse_pairs(out16, dw[3] if dw is not None else None)
         if out_pairs and (out.c0 % 8 or out.t.shape[3] % 8):
             raise OkpError("pair format: the output window starts on a whole 8-channel group of its tensor")
         extended = out16 is not None or res16 or out_subsample == 2 or not write_out      # (what keeps a split-product launch off the patch-resident kernel)
@@ -385,58 +347,26 @@ class ConvPlan:
         macs_dw = out.n * ho * wo * self.cout * 9 if dw is not None else 0
         tile = tile or FORCE_TILE
         out.pairs = False                # whatever this Act held before, the launch overwrites it with ordinary values - or pairs, set below
-        T = _ops()
+        B = _ops()
         hook = LAUNCH_HOOK
-        if T is not None:
-            s1 = srcs[1] if len(srcs) > 1 else None
-            if hook is not None:
-                self.last_launch = (out.n, ho, wo, dw is not None, res is not None, n_classes)
-                self.last_bytes = self._algorithmic_bytes(srcs, out, ho, wo, res, out_step, n_classes, dw, out16, write_out, out_subsample)
-                tile = _dispatch(T.conv_select_tile, self._h, srcs[0].t, srcs[0].c0, s1.t if s1 else None, s1.c0 if s1 else 0, out.t, out.c0, ho, wo,
-                                 out_step, oy, ox, tile, n_classes, dw is not None, extended)
-                token = hook.before(self, tile, macs)
-            if dw is not None:
-                dw_w, dw_b, dw_out, dw_res = dw
-                dw_out.pairs = False
-                dwa = (dw_w, dw_b, dw_out.t, dw_out.c0, dw_res.t if dw_res is not None else None, dw_res.c0 if dw_res is not None else 0)
-            else:
-                dwa = (None, None, None, 0, None, 0)
-            _dispatch(T.conv_forward, self._h, srcs[0].t, srcs[0].c0, s1.t if s1 else None, s1.c0 if s1 else 0, out.t, out.c0, ho, wo,
-                      res.t if res is not None else None, res.c0 if res is not None else 0, out_step, oy, ox, tile, n_classes, *dwa, stream_int(),
-                      out16.t if out16 is not None else None, out16.c0 if out16 is not None else 0, bool(write_out), out_subsample, src_pairs, bool(out_pairs))
-            if hook is not None:
-                hook.after(token)
+        s1 = srcs[1] if len(srcs) > 1 else None
+        if hook is not None:
+            self.last_launch = (out.n, ho, wo, dw is not None, res is not None, n_classes)
+            self.last_bytes = self._algorithmic_bytes(srcs, out, ho, wo, res, out_step, n_classes, dw, out16, write_out, out_subsample)
+            tile = _dispatch(B.conv_select_tile, self._h, srcs[0].t, srcs[0].c0, s1.t if s1 else None, s1.c0 if s1 else 0, out.t, out.c0, ho, wo,
+                             out_step, oy, ox, tile, n_classes, dw is not None, extended)
+            token = hook.before(self, tile, macs)
+        if dw is not None:
+            dw_w, dw_b, dw_out, dw_res = dw
+            dw_out.pairs = False
+            dwa = (dw_w, dw_b, dw_out.t, dw_out.c0, dw_res.t if dw_res is not None else None, dw_res.c0 if dw_res is not None else 0)
         else:
-            a = _lib.okp_conv_args()
-            a.n, a.ho, a.wo = out.n, ho, wo
-            for i, s in enumerate(srcs):
-                a.src[i] = s.view(pairs_ok=True)
-            a.src_pairs, a.out_pairs = src_pairs, 1 if out_pairs else 0
-            a.out = out.view()
-            if not write_out:
-                a.out.data = None
-            if out16 is not None:
-                a.out16 = out16.view()
-            a.res_is_f16 = 1 if res16 else 0
-            a.out_subsample = out_subsample
-            a.out_step, a.out_oy, a.out_ox = out_step, oy, ox
-            a.res = res.view() if res is not None else _NULL_TENSOR
-            a.tile = tile
-            a.n_classes = n_classes
-            if dw is not None:
-                dw_w, dw_b, dw_out, dw_res = dw
-                dw_out.pairs = False
-                a.dw_w_dev, a.dw_bias_dev = dw_w.data_ptr(), dw_b.data_ptr()
-                a.dw_out = dw_out.view()
-                a.dw_res = dw_res.view() if dw_res is not None else _NULL_TENSOR
-            if hook is not None:
-                self.last_launch = (out.n, ho, wo, dw is not None, res is not None, n_classes)
-                self.last_bytes = self._algorithmic_bytes(srcs, out, ho, wo, res, out_step, n_classes, dw, out16, write_out, out_subsample)
-                a.tile = _lib.lib().okp_conv_select_tile(self._h, ctypes.byref(a))
-                token = hook.before(self, a.tile, macs)
-            _lib.check(_lib.lib().okp_conv_forward(self._h, ctypes.byref(a), stream_handle()), "okp_conv_forward")
-            if hook is not None:
-                hook.after(token)
+            dwa = (None, None, None, 0, None, 0)
+        _dispatch(B.conv_forward, self._h, srcs[0].t, srcs[0].c0, s1.t if s1 else None, s1.c0 if s1 else 0, out.t, out.c0, ho, wo,
+                  res.t if res is not None else None, res.c0 if res is not None else 0, out_step, oy, ox, tile, n_classes, *dwa, stream_int(),
+                  out16.t if out16 is not None else None, out16.c0 if out16 is not None else 0, bool(write_out), out_subsample, src_pairs, bool(out_pairs))
+        if hook is not None:
+            hook.after(token)
         out.pairs = bool(out_pairs)
         COUNTERS["pair_outputs"] += 1 if out_pairs else 0
         COUNTERS["macs"] += macs + macs_dw
@@ -454,16 +384,7 @@ def fire_fused(squeeze, expand, wd_dev, bd_dev, x, out, stride, skip):
     """One-launch fire module (16-bit plans: okp_fire2.hip; split-product plans: okp_fire_x3.hip): see okp_fire_forward in include/okp.h."""
     _refuse_pairs(x)
     out.pairs = False
-    T = _ops()
-    if T is not None:
-        _dispatch(T.fire_forward, squeeze._h, expand._h, wd_dev, bd_dev, x.t, x.c0, out.t, out.c0, stride, bool(skip), stream_int())
-    else:
-        a = _lib.okp_fire_args()
-        a.n = x.n
-        a.x, a.out = x.view(), out.view()
-        a.stride, a.skip = stride, 1 if skip else 0
-        _lib.check(_lib.lib().okp_fire_forward(squeeze._h, expand._h, wd_dev.data_ptr(), bd_dev.data_ptr(), ctypes.byref(a), stream_handle()),
-                   "okp_fire_forward")
+    _dispatch(_ops().fire_forward, squeeze._h, expand._h, wd_dev, bd_dev, x.t, x.c0, out.t, out.c0, stride, bool(skip), stream_int())
     half = expand.cout
     COUNTERS["macs"] += x.n * x.h * x.w * squeeze.cout * squeeze.cins[0] + out.n * out.h * out.w * half * (expand.cins[0] + 9)
     COUNTERS["launches"] += 1
@@ -481,19 +402,9 @@ FUSE_FIRE_CHAIN = True          # consecutive 512-channel fire modules on <= 4x4
 def fire_chain(modules, x, out):
     """modules: list of (squeeze plan, expand plan, dw weights, dw bias) of consecutive fire(512, 512) modules; x, out: Acts."""
     _refuse_pairs(x)
-    n = len(modules)
     out.pairs = False
-    T = _ops()
-    if T is not None:
-        _dispatch(T.fire_chain_forward, [m[0]._h for m in modules], [m[1]._h for m in modules], [m[2] for m in modules], [m[3] for m in modules],
-                  x.t, x.c0, out.t, out.c0, stream_int())
-    else:
-        sq = (ctypes.c_void_p * n)(*[m[0]._h for m in modules])
-        ex = (ctypes.c_void_p * n)(*[m[1]._h for m in modules])
-        wd = (ctypes.c_void_p * n)(*[m[2].data_ptr() for m in modules])
-        bd = (ctypes.c_void_p * n)(*[m[3].data_ptr() for m in modules])
-        xv, ov = x.view(), out.view()
-        _lib.check(_lib.lib().okp_fire_chain_forward(n, sq, ex, wd, bd, x.n, ctypes.byref(xv), ctypes.byref(ov), stream_handle()), "okp_fire_chain_forward")
+    _dispatch(_ops().fire_chain_forward, [m[0]._h for m in modules], [m[1]._h for m in modules], [m[2] for m in modules], [m[3] for m in modules],
+              x.t, x.c0, out.t, out.c0, stream_int())
     for i, m in enumerate(modules):
         half = m[1].cout
         sq_px = x.h * x.w if i == 0 else out.h * out.w          # (entry / exit form: the entry module squeezes at the input resolution)
@@ -557,11 +468,7 @@ LIGHT_EVENTS = True     # forks / joins through okp_stream_wait_stream (events w
 def stream_wait(waiter, signaller):
     """`waiter` (torch.cuda.Stream) waits for the work enqueued on `signaller` so far."""
     if LIGHT_EVENTS:
-        T = _ops()
-        if T is not None:
-            _dispatch(T.stream_wait_stream, waiter.cuda_stream, signaller.cuda_stream)
-        else:
-            _lib.check(_lib.lib().okp_stream_wait_stream(ctypes.c_void_p(waiter.cuda_stream), ctypes.c_void_p(signaller.cuda_stream)), "okp_stream_wait_stream")
+        _dispatch(_ops().stream_wait_stream, waiter.cuda_stream, signaller.cuda_stream)
     else:
         waiter.wait_stream(signaller)
 
@@ -575,12 +482,7 @@ def cast(src, dtype):
     okp_dtype(dtype)
     # to fp32 inside a split-product pass: what the fp16 sub-network made is about to be halved again - its range is checked here, exactly
     flag = getattr(_MODE, "range_flag", None) if dtype == torch.float32 else None
-    T = _ops()
-    if T is not None:
-        _dispatch(T.cast, src.t, out.t, stream_int(), flag)
-    else:
-        _lib.check(_lib.lib().okp_cast(okp_dtype(src.dtype), src.t.data_ptr(), okp_dtype(dtype), out.t.data_ptr(), src.t.numel(),
-                                       flag.data_ptr() if flag is not None else None, stream_handle()), "okp_cast")
+    _dispatch(_ops().cast, src.t, out.t, stream_int(), flag)
     COUNTERS["launches"] += 1
     return out
 
@@ -592,32 +494,17 @@ def add_f16_f32(a16, b32, relu=True):
         raise OkpError("add_f16_f32 takes whole float16 / float32 tensors of one shape")
     out = Act(torch.empty_like(b32.t))
     flag = getattr(_MODE, "range_flag", None)
-    T = _ops()
-    if T is not None:
-        _dispatch(T.add_f16_f32, a16.t, b32.t, out.t, ACT_RELU if relu else ACT_NONE, stream_int(), flag)
-    else:
-        _lib.check(_lib.lib().okp_add_f16_f32(a16.t.data_ptr(), b32.t.data_ptr(), out.t.data_ptr(), out.t.numel(), ACT_RELU if relu else ACT_NONE,
-                                              flag.data_ptr() if flag is not None else None, stream_handle()), "okp_add_f16_f32")
+    _dispatch(_ops().add_f16_f32, a16.t, b32.t, out.t, ACT_RELU if relu else ACT_NONE, stream_int(), flag)
     COUNTERS["launches"] += 1
     return out
 
 
 def dwconv3x3(src, w_dev, bias_dev, out, stride, res=None, relu=True):
     _refuse_pairs(src, res)
-    dt = okp_dtype(src.dtype)
+    okp_dtype(src.dtype)
     out.pairs = False
-    T = _ops()
-    if T is not None:
-        _dispatch(T.dwconv3x3_forward, src.t, src.c0, src.c, stride, w_dev, bias_dev, res.t if res is not None else None, res.c0 if res is not None else 0,
-                  out.t, out.c0, ACT_RELU if relu else ACT_NONE, stream_int())
-        COUNTERS["macs"] += out.n * out.h * out.w * src.c * 9
-        COUNTERS["launches"] += 1
-        return
-    sv, ov = src.view(), out.view()
-    rv = res.view() if res is not None else None
-    _lib.check(_lib.lib().okp_dwconv3x3_forward(dt, src.n, src.c, stride, ctypes.byref(sv), w_dev.data_ptr(), bias_dev.data_ptr(),
-                                                ctypes.byref(rv) if rv is not None else None, ctypes.byref(ov),
-                                                ACT_RELU if relu else ACT_NONE, stream_handle()), "okp_dwconv3x3_forward")
+    _dispatch(_ops().dwconv3x3_forward, src.t, src.c0, src.c, stride, w_dev, bias_dev, res.t if res is not None else None, res.c0 if res is not None else 0,
+              out.t, out.c0, ACT_RELU if relu else ACT_NONE, stream_int())
     COUNTERS["macs"] += out.n * out.h * out.w * src.c * 9
     COUNTERS["launches"] += 1
 
@@ -638,11 +525,12 @@ def pack_frames(frames, dtype):
     wp = stem_packed_width(w)
     out = torch.empty((n, h + 6, wp, 4), dtype=dtype, device=frames.device)
     okp_dtype(dtype)
-    T = _ops()
-    if T is not None:
-        _dispatch(T.pack_frames, frames, out, stream_int())
-    else:
-        _lib.check(_lib.lib().okp_pack_frames(okp_dtype(dtype), frames.data_ptr(), n, h, w, out.data_ptr(), wp, stream_handle()), "okp_pack_frames")
+    _dispatch(_ops().pack_frames, frames, out, stream_int())
+    return _packed(out, h, w)
+
+
+def _packed(out, h, w):
+    """The packed stem input a pack / preprocess launch has just written, as an Act that remembers the un-padded frame size."""
     COUNTERS["launches"] += 1
     act = Act(out)
     act.orig_hw = (h, w)
@@ -663,16 +551,8 @@ class StemPlan:
         if dtype not in HALF_DTYPES and not self.split:
             raise OkpError("the stem kernel computes in bfloat16, float16 or (float32 inside ops.f32_split()) split products")
         self.dtype = dtype
-        L = _lib.lib()
-        T = _ops()
-        if T is not None:
-            self._h = _dispatch(T.stem_create, OKP_F32X3 if self.split else okp_dtype(dtype), torch.from_numpy(w), torch.from_numpy(b))
-            _attach_range_flag(self, "stem_set_range_flag")
-            return
-        self._h = L.okp_stem_create_dtype(OKP_F32X3 if self.split else okp_dtype(dtype), w.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), b.ctypes.data_as(ctypes.POINTER(ctypes.c_float)))
-        if not self._h:
-            raise OkpError("okp_stem_create: " + L.okp_last_error().decode())
-        _attach_range_flag(self, "stem_set_range_flag")
+        self._h = _dispatch(_ops().stem_create, OKP_F32X3 if self.split else okp_dtype(dtype), torch.from_numpy(w), torch.from_numpy(b))
+        _attach_range_flag(self)
 
     def __del__(self):
         h, self._h = getattr(self, "_h", None), None
@@ -690,23 +570,16 @@ class StemPlan:
             raise OkpError("frames must be float32 [N,3,H,W] and the output of the plan's element type")
         frames = frames.contiguous()
         n, _, h, w = frames.shape
-        T = _ops()
+        B = _ops()
         out.pairs = False
         if out_pairs:
             if not self.split:
                 raise OkpError("pair-format output belongs to the split-product stem")
-            if T is not None:
-                _dispatch(T.stem_forward_nchw_pairs, self._h, frames, out.t, out.c0, stream_int())
-            else:
-                ov = out.view()
-                _lib.check(_lib.lib().okp_stem_forward_nchw_pairs(self._h, n, h, w, frames.data_ptr(), ctypes.byref(ov), stream_handle()), "okp_stem_forward_nchw_pairs")
+            _dispatch(B.stem_forward_nchw_pairs, self._h, frames, out.t, out.c0, stream_int())
             out.pairs = True
             COUNTERS["pair_outputs"] += 1
-        elif T is not None:
-            _dispatch(T.stem_forward_nchw, self._h, frames, out.t, out.c0, stream_int())
         else:
-            ov = out.view()
-            _lib.check(_lib.lib().okp_stem_forward_nchw(self._h, n, h, w, frames.data_ptr(), ctypes.byref(ov), stream_handle()), "okp_stem_forward_nchw")
+            _dispatch(B.stem_forward_nchw, self._h, frames, out.t, out.c0, stream_int())
         COUNTERS["macs"] += out.n * out.h * out.w * 128 * 147
         COUNTERS["launches"] += 1
 
@@ -715,12 +588,7 @@ class StemPlan:
             raise OkpError("stem input must be the output of ops.pack_frames in the plan's 16-bit type (the split-product stem reads NCHW frames: from_nchw)")
         h, w = packed.orig_hw
         out.pairs = False
-        T = _ops()
-        if T is not None:
-            _dispatch(T.stem_forward, self._h, packed.t, h, w, out.t, out.c0, stream_int())
-        else:
-            pv, ov = packed.view(), out.view()
-            _lib.check(_lib.lib().okp_stem_forward(self._h, packed.n, h, w, ctypes.byref(pv), ctypes.byref(ov), stream_handle()), "okp_stem_forward")
+        _dispatch(_ops().stem_forward, self._h, packed.t, h, w, out.t, out.c0, stream_int())
         COUNTERS["macs"] += out.n * out.h * out.w * 128 * 147
         COUNTERS["launches"] += 1
 
@@ -728,6 +596,11 @@ class StemPlan:
 # normalisation constants of the reference's data loader (perception/datasets/video.py:55-56)
 RGB_MEAN = (0.40789654, 0.44719302, 0.47026115)
 RGB_STD = (0.28863828, 0.27408164, 0.27809835)
+
+
+def _f32_list(v):
+    """Normalisation constants as the kernels take them: rounded to float32."""
+    return [float(np.float32(x)) for x in v]
 
 
 def pack_frames_u8(frames, dtype, mean=RGB_MEAN, std=RGB_STD):
@@ -740,20 +613,8 @@ def pack_frames_u8(frames, dtype, mean=RGB_MEAN, std=RGB_STD):
     wp = stem_packed_width(w)
     out = torch.empty((n, h + 6, wp, 4), dtype=dtype, device=frames.device)
     okp_dtype(dtype)
-    T = _ops()
-    if T is not None:
-        _dispatch(T.pack_frames_u8, frames, [float(np.float32(v)) for v in mean], [float(np.float32(v)) for v in std], out, stream_int())
-        COUNTERS["launches"] += 1
-        act = Act(out)
-        act.orig_hw = (h, w)
-        return act
-    m = (ctypes.c_float * 3)(*mean)
-    sd = (ctypes.c_float * 3)(*std)
-    _lib.check(_lib.lib().okp_pack_frames_u8(okp_dtype(dtype), frames.data_ptr(), n, h, w, m, sd, out.data_ptr(), wp, stream_handle()), "okp_pack_frames_u8")
-    COUNTERS["launches"] += 1
-    act = Act(out)
-    act.orig_hw = (h, w)
-    return act
+    _dispatch(_ops().pack_frames_u8, frames, _f32_list(mean), _f32_list(std), out, stream_int())
+    return _packed(out, h, w)
 
 
 def smallest_max_size(h, w, max_size):
@@ -777,21 +638,8 @@ def preprocess_u8(frames, dtype, size=511, mean=RGB_MEAN, std=RGB_STD):
     wp = stem_packed_width(size)
     out = torch.empty((n, size + 6, wp, 4), dtype=dtype, device=frames.device)
     okp_dtype(dtype)
-    T = _ops()
-    if T is not None:
-        _dispatch(T.preprocess_u8, frames, rh, rw, cy, cx, size, size, [float(np.float32(v)) for v in mean], [float(np.float32(v)) for v in std], out, stream_int())
-        COUNTERS["launches"] += 1
-        act = Act(out)
-        act.orig_hw = (size, size)
-        return act
-    m = (ctypes.c_float * 3)(*mean)
-    sd = (ctypes.c_float * 3)(*std)
-    _lib.check(_lib.lib().okp_preprocess_u8(okp_dtype(dtype), frames.data_ptr(), n, sh, sw, rh, rw, cy, cx, size, size, m, sd,
-                                            out.data_ptr(), wp, stream_handle()), "okp_preprocess_u8")
-    COUNTERS["launches"] += 1
-    act = Act(out)
-    act.orig_hw = (size, size)
-    return act
+    _dispatch(_ops().preprocess_u8, frames, rh, rw, cy, cx, size, size, _f32_list(mean), _f32_list(std), out, stream_int())
+    return _packed(out, size, size)
 
 
 @dataclasses.dataclass(frozen=True)
@@ -865,45 +713,15 @@ def preprocess_yuv420(frames, dtype, fmt, size=511, mean=RGB_MEAN, std=RGB_STD):
     layout, matrix = _YUV_LAYOUTS[fmt.layout], _YUV_MATRICES[fmt.matrix]
     wp = stem_packed_width(size)
     out = torch.empty((n, size + 6, wp, 4), dtype=dtype, device=frames.device)
-    T = _ops()
-    if T is not None:
-        _dispatch(T.preprocess_yuv420, frames, layout, matrix, fmt.full_range, rh, rw, cy, cx, size, size, [float(np.float32(v)) for v in mean],
-                  [float(np.float32(v)) for v in std], out, stream_int())
-    else:
-        m = (ctypes.c_float * 3)(*mean)
-        sd = (ctypes.c_float * 3)(*std)
-        _lib.check(_lib.lib().okp_preprocess_yuv420(okp_dtype(dtype), frames.data_ptr(), n, sh, sw, pitch, layout, matrix, int(fmt.full_range), rh, rw,
-                                                    cy, cx, size, size, m, sd, out.data_ptr(), wp, stream_handle()), "okp_preprocess_yuv420")
-    COUNTERS["launches"] += 1
-    act = Act(out)
-    act.orig_hw = (size, size)
-    return act
-
-
-def _head_out_args(n, h, w, outputs, w_dev, bias_dev):
-    a = _lib.okp_head_out_args()
-    a.n, a.h, a.w = n, h, w
-    a.n_out = len(outputs)
-    for i, (off, act, t, ch) in enumerate(outputs):
-        a.in_c_off[i] = off
-        a.act[i] = act
-        a.out_ptr[i] = t.data_ptr() + ch * t.shape[2] * t.shape[3] * 4
-        a.out_n_stride[i] = t.shape[1] * t.shape[2] * t.shape[3]
-    a.w_dev, a.bias_dev = w_dev.data_ptr(), bias_dev.data_ptr()
-    return a
+    _dispatch(_ops().preprocess_yuv420, frames, layout, matrix, fmt.full_range, rh, rw, cy, cx, size, size, _f32_list(mean), _f32_list(std), out, stream_int())
+    return _packed(out, size, size)
 
 
 def head_out(src, outputs, w_dev, bias_dev):
     """outputs: list of (in_c_off, act, out_tensor[N,Cx,H,W] fp32, channel index)."""
     _refuse_pairs(src)
-    T = _ops()
-    if T is not None:
-        _dispatch(T.head_out_forward, src.t, src.c0, [o[0] for o in outputs], [o[1] for o in outputs], [o[2] for o in outputs], [o[3] for o in outputs],
-                  w_dev, bias_dev, stream_int())
-    else:
-        a = _head_out_args(src.n, src.h, src.w, outputs, w_dev, bias_dev)
-        a.src = src.view()
-        _lib.check(_lib.lib().okp_head_out_forward(okp_dtype(src.dtype), ctypes.byref(a), stream_handle()), "okp_head_out_forward")
+    _dispatch(_ops().head_out_forward, src.t, src.c0, [o[0] for o in outputs], [o[1] for o in outputs], [o[2] for o in outputs], [o[3] for o in outputs],
+              w_dev, bias_dev, stream_int())
     COUNTERS["macs"] += src.n * src.h * src.w * 32 * len(outputs)
     COUNTERS["launches"] += 1
 
@@ -917,14 +735,8 @@ def heads_fused(l1, l2, x, outputs, w_dev, bias_dev):
     Split-product plans: x is a pair-format activation (Act.pairs; written by the 3x3 `cnvs` convolution in front of the heads)."""
     if l1.split != bool(x.pairs):
         raise OkpError("heads_fused: split-product plans read a pair-format activation, the 16-bit plans an ordinary one")
-    T = _ops()
-    if T is not None:
-        _dispatch(T.heads_forward, l1._h, l2._h, x.t, x.c0, [o[0] for o in outputs], [o[1] for o in outputs], [o[2] for o in outputs], [o[3] for o in outputs],
-                  w_dev, bias_dev, stream_int())
-    else:
-        a = _head_out_args(x.n, x.h, x.w, outputs, w_dev, bias_dev)
-        xv = x.view(pairs_ok=True)
-        _lib.check(_lib.lib().okp_heads_forward(l1._h, l2._h, ctypes.byref(a), ctypes.byref(xv), stream_handle()), "okp_heads_forward")
+    _dispatch(_ops().heads_forward, l1._h, l2._h, x.t, x.c0, [o[0] for o in outputs], [o[1] for o in outputs], [o[2] for o in outputs], [o[3] for o in outputs],
+              w_dev, bias_dev, stream_int())
     COUNTERS["macs"] += x.n * x.h * x.w * (l1.cout * l1.alg_k + l2.cout * l2.alg_k + 32 * len(outputs))
     COUNTERS["launches"] += 1
 
@@ -940,11 +752,7 @@ def peak_nms(heat, cap=64):
     count = torch.empty((n, k), dtype=torch.int32, device=heat.device)
     yx = torch.empty((n, k, cap, 2), dtype=torch.int32, device=heat.device)
     xyc = torch.empty((n, k, cap, 3), dtype=torch.float32, device=heat.device)
-    T = _ops()
-    if T is not None:
-        _dispatch(T.peak_nms, heat, cap, count, yx, xyc, stream_int())
-    else:
-        _lib.check(_lib.lib().okp_peak_nms(heat.data_ptr(), n * k, h, w, cap, count.data_ptr(), yx.data_ptr(), xyc.data_ptr(), stream_handle()), "okp_peak_nms")
+    _dispatch(_ops().peak_nms, heat, cap, count, yx, xyc, stream_int())
     return count, yx, xyc
 
 
@@ -955,12 +763,7 @@ def nms_maxpool(x, size=5):
         raise OkpError("nms expects float32 [N,C,H,W]")
     x = x.contiguous()
     out = torch.empty_like(x)
-    n, c, h, w = x.shape
-    T = _ops()
-    if T is not None:
-        _dispatch(T.nms_maxpool, x, size, out, stream_int())
-    else:
-        _lib.check(_lib.lib().okp_nms_maxpool(x.data_ptr(), n * c, h, w, size, out.data_ptr(), stream_handle()), "okp_nms_maxpool")
+    _dispatch(_ops().nms_maxpool, x, size, out, stream_int())
     return out
 
 
@@ -981,11 +784,7 @@ def camera_undistort(cam, xy):
     require_cuda(xy, "xy")
     xy = xy.to(torch.float32).contiguous()
     out = torch.empty((xy.shape[0], 2), dtype=torch.float64, device=xy.device)
-    T = _ops()
-    if T is not None:
-        _dispatch(T.camera_undistort, _cam_list(cam), xy, out, stream_int())
-    else:
-        _lib.check(_lib.lib().okp_camera_undistort(ctypes.byref(cam), xy.data_ptr(), xy.shape[0], out.data_ptr(), stream_handle()), "okp_camera_undistort")
+    _dispatch(_ops().camera_undistort, _cam_list(cam), xy, out, stream_int())
     return out
 
 
@@ -1001,12 +800,7 @@ def unproject_depth(cam, xy, map_id, depth, max_x, max_y):
     if depth.dtype != torch.float32 or depth.dim() != 3:
         raise OkpError("depth must be float32 [maps,H,W]")
     out = torch.empty((xy.shape[0], 3), dtype=torch.float64, device=xy.device)
-    T = _ops()
-    if T is not None:
-        _dispatch(T.unproject_depth, _cam_list(cam), xy, map_id, depth, max_x, max_y, out, stream_int())
-    else:
-        _lib.check(_lib.lib().okp_unproject_depth(ctypes.byref(cam), xy.data_ptr(), map_id.data_ptr(), xy.shape[0], depth.data_ptr(),
-                                                  depth.shape[1], depth.shape[2], max_x, max_y, out.data_ptr(), stream_handle()), "okp_unproject_depth")
+    _dispatch(_ops().unproject_depth, _cam_list(cam), xy, map_id, depth, max_x, max_y, out, stream_int())
     return out
 
 
@@ -1018,12 +812,7 @@ def lift_peaks(cam, count, xyc, depth, max_x, max_y):
     if depth.dtype != torch.float32 or depth.shape[:2] != (n, k):
         raise OkpError("depth must be float32 [N,K,H,W] matching the peak tensors")
     out = torch.empty((n, k, cap, 4), dtype=torch.float64, device=xyc.device)
-    T = _ops()
-    if T is not None:
-        _dispatch(T.lift_peaks, _cam_list(cam), count, xyc, depth, max_x, max_y, out, stream_int())
-    else:
-        _lib.check(_lib.lib().okp_lift_peaks(ctypes.byref(cam), count.data_ptr(), xyc.data_ptr(), n * k, cap, depth.data_ptr(),
-                                             depth.shape[2], depth.shape[3], max_x, max_y, out.data_ptr(), stream_handle()), "okp_lift_peaks")
+    _dispatch(_ops().lift_peaks, _cam_list(cam), count, xyc, depth, max_x, max_y, out, stream_int())
     return out
 
 
@@ -1044,14 +833,7 @@ def group_objects(count, xyc, centers, type_count, max_obj=16, max_sel=4, max_di
     assign = torch.empty((n, k, cap), dtype=torch.int32, device=dev)
     pred = torch.empty((n, k, cap, 2), dtype=torch.float64, device=dev)      # (the kernel zeroes the unused slots)
     reduced = torch.empty((n, max_obj, k - 1, max_sel, 2), dtype=torch.float32, device=dev)     # (NaN where no reduction took place)
-    T = _ops()
-    if T is not None:
-        _dispatch(T.group_objects, count, xyc, centers, [int(c) for c in type_count], float(max_dist), max_obj, max_sel, n_obj, sel, votes, assign, pred, stream_int(), reduced)
-    else:
-        tc = (ctypes.c_int32 * (k - 1))(*[int(c) for c in type_count])
-        _lib.check(_lib.lib().okp_group_objects(count.data_ptr(), xyc.data_ptr(), centers.data_ptr(), n, k, cap, centers.shape[3], centers.shape[4],
-                                                tc, float(max_dist), max_obj, max_sel, n_obj.data_ptr(), sel.data_ptr(), votes.data_ptr(),
-                                                assign.data_ptr(), pred.data_ptr(), reduced.data_ptr(), stream_handle()), "okp_group_objects")
+    _dispatch(_ops().group_objects, count, xyc, centers, [int(c) for c in type_count], float(max_dist), max_obj, max_sel, n_obj, sel, votes, assign, pred, stream_int(), reduced)
     return {"n_obj": n_obj, "sel": sel, "n_votes": votes, "assign": assign, "pred": pred, "reduced": reduced}
 
 
@@ -1064,13 +846,8 @@ def capacity_overflow(count, cap, max_obj, range_flag=None):
     when that flag is raised (bit 1, RANGE_OVERFLOW).  `bool(flag)` on the host.  One small launch, no host sync, no torch kernel."""
     require_cuda(count, "count")
     flag = torch.empty((1,), dtype=torch.int32, device=count.device)
-    n, k = count.shape
-    T = _ops()
-    if T is not None:
-        _dispatch(T.capacity_overflow, count.contiguous(), k, cap, max_obj, flag, stream_int(), range_flag)
-    else:
-        _lib.check(_lib.lib().okp_capacity_overflow(count.data_ptr(), n * k, k, cap, max_obj, range_flag.data_ptr() if range_flag is not None else None,
-                                                    flag.data_ptr(), stream_handle()), "okp_capacity_overflow")
+    k = count.shape[1]
+    _dispatch(_ops().capacity_overflow, count.contiguous(), k, cap, max_obj, flag, stream_int(), range_flag)
     return flag[0]
 
 
@@ -1081,20 +858,9 @@ def triangulate_dlt(cam_l, cam_r, T_RL, left_xy, right_xy, F=None):
     if left_xy.shape != right_xy.shape:
         raise OkpError("left/right point counts differ")
     T = np.ascontiguousarray(np.asarray(T_RL, dtype=np.float64)[:3, :4])
-    TO = _ops()
-    if TO is not None:
-        out = torch.empty((left_xy.shape[0], 3), dtype=torch.float64, device=left_xy.device)
-        Fl = [] if F is None else [float(v) for v in np.asarray(F, dtype=np.float64).reshape(9)]
-        _dispatch(TO.triangulate_dlt, _cam_list(cam_l), _cam_list(cam_r), [float(v) for v in T.reshape(12)], Fl, left_xy, right_xy, out, stream_int())
-        return out
-    Fp = None
-    if F is not None:
-        Fa = np.ascontiguousarray(np.asarray(F, dtype=np.float64).reshape(3, 3))
-        Fp = Fa.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+    Fl = [] if F is None else [float(v) for v in np.asarray(F, dtype=np.float64).reshape(9)]
     out = torch.empty((left_xy.shape[0], 3), dtype=torch.float64, device=left_xy.device)
-    _lib.check(_lib.lib().okp_triangulate_dlt(ctypes.byref(cam_l), ctypes.byref(cam_r), T.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), Fp,
-                                              1 if F is not None else 0, left_xy.data_ptr(), right_xy.data_ptr(), left_xy.shape[0],
-                                              out.data_ptr(), stream_handle()), "okp_triangulate_dlt")
+    _dispatch(_ops().triangulate_dlt, _cam_list(cam_l), _cam_list(cam_r), [float(v) for v in T.reshape(12)], Fl, left_xy, right_xy, out, stream_int())
     return out
 
 
@@ -1121,14 +887,7 @@ def stereo_match(cam_l, cam_r, F, count, xyc, max_distance, range_flag=None):
     Fl = [float(v) for v in np.asarray(F, dtype=np.float64).reshape(9)]
     match = torch.empty((n_pairs, k, cap), dtype=torch.int32, device=xyc.device)
     flag = torch.empty((1,), dtype=torch.int32, device=xyc.device)
-    T = _ops()
-    if T is not None:
-        _dispatch(T.stereo_match, _cam_list(cam_l), _cam_list(cam_r), Fl, float(max_distance), count, xyc, match, flag, stream_int(), range_flag)
-    else:
-        Fa = (ctypes.c_double * 9)(*Fl)
-        _lib.check(_lib.lib().okp_stereo_match(ctypes.byref(cam_l), ctypes.byref(cam_r), Fa, float(max_distance), count.data_ptr(), xyc.data_ptr(),
-                                               n_pairs, k, cap, range_flag.data_ptr() if range_flag is not None else None, match.data_ptr(),
-                                               flag.data_ptr(), stream_handle()), "okp_stereo_match")
+    _dispatch(_ops().stereo_match, _cam_list(cam_l), _cam_list(cam_r), Fl, float(max_distance), count, xyc, match, flag, stream_int(), range_flag)
     return match, flag[0]
 
 
@@ -1144,14 +903,7 @@ def stereo_triangulate(cam_l, cam_r, T_RL, count, xyc, match, F=None):
     Tm = [float(v) for v in np.asarray(T_RL, dtype=np.float64)[:3, :4].reshape(12)]
     Fl = [] if F is None else [float(v) for v in np.asarray(F, dtype=np.float64).reshape(9)]
     points = torch.empty((n_pairs, k, cap, 4), dtype=torch.float64, device=xyc.device)
-    TO = _ops()
-    if TO is not None:
-        _dispatch(TO.stereo_triangulate, _cam_list(cam_l), _cam_list(cam_r), Tm, Fl, count, xyc, match, points, stream_int())
-    else:
-        Ta = (ctypes.c_double * 12)(*Tm)
-        Fa = (ctypes.c_double * 9)(*Fl) if Fl else None
-        _lib.check(_lib.lib().okp_stereo_triangulate(ctypes.byref(cam_l), ctypes.byref(cam_r), Ta, Fa, 1 if Fl else 0, count.data_ptr(), xyc.data_ptr(),
-                                                     match.data_ptr(), n_pairs, k, cap, points.data_ptr(), stream_handle()), "okp_stereo_triangulate")
+    _dispatch(_ops().stereo_triangulate, _cam_list(cam_l), _cam_list(cam_r), Tm, Fl, count, xyc, match, points, stream_int())
     return points
 
 
@@ -1205,17 +957,11 @@ def stereo_match_rig(table, count, xyc, max_distance, first_pair=0, range_flag=N
     """stereo_match for a rig: pair p of the tick is associated against the epipolar geometry of table[first_pair + p] (the table of
     stereo_rig on the device; a one-entry table serves every pair), with that pair's cameras.  -> match [P,K,cap] int32, overflow (0-d int32)."""
     n_pairs, k, cap = _tick_pairs(count, xyc)
-    n_table = _rig_table(table)
+    _rig_table(table)
     count, xyc = count.contiguous(), xyc.contiguous()
     match = torch.empty((n_pairs, k, cap), dtype=torch.int32, device=xyc.device)
     flag = torch.empty((1,), dtype=torch.int32, device=xyc.device)
-    T = _ops()
-    if T is not None:
-        _dispatch(T.stereo_match_rig, table, int(first_pair), float(max_distance), count, xyc, match, flag, stream_int(), range_flag)
-    else:
-        _lib.check(_lib.lib().okp_stereo_match_rig(table.data_ptr(), n_table, int(first_pair), float(max_distance), count.data_ptr(), xyc.data_ptr(),
-                                                   n_pairs, k, cap, range_flag.data_ptr() if range_flag is not None else None, match.data_ptr(),
-                                                   flag.data_ptr(), stream_handle()), "okp_stereo_match_rig")
+    _dispatch(_ops().stereo_match_rig, table, int(first_pair), float(max_distance), count, xyc, match, flag, stream_int(), range_flag)
     return match, flag[0]
 
 
@@ -1223,19 +969,13 @@ def stereo_triangulate_rig(table, count, xyc, match, first_pair=0, correct_match
     """stereo_triangulate for a rig: the matched slots of pair p triangulated with the cameras and T_RL of table[first_pair + p] (with the
     Hartley-Sturm correction against its F unless correct_matches=False).  -> points [P,K,cap,4] fp64 in each pair's left camera frame."""
     n_pairs, k, cap = _tick_pairs(count, xyc)
-    n_table = _rig_table(table)
+    _rig_table(table)
     require_cuda(match, "match")
     if match.dtype != torch.int32 or tuple(match.shape) != (n_pairs, k, cap):
         raise OkpError("match must be int32 [P,K,cap] (stereo_match_rig)")
     count, xyc, match = count.contiguous(), xyc.contiguous(), match.contiguous()
     points = torch.empty((n_pairs, k, cap, 4), dtype=torch.float64, device=xyc.device)
-    TO = _ops()
-    if TO is not None:
-        _dispatch(TO.stereo_triangulate_rig, table, int(first_pair), bool(correct_matches), count, xyc, match, points, stream_int())
-    else:
-        _lib.check(_lib.lib().okp_stereo_triangulate_rig(table.data_ptr(), n_table, int(first_pair), 1 if correct_matches else 0, count.data_ptr(),
-                                                         xyc.data_ptr(), match.data_ptr(), n_pairs, k, cap, points.data_ptr(), stream_handle()),
-                   "okp_stereo_triangulate_rig")
+    _dispatch(_ops().stereo_triangulate_rig, table, int(first_pair), bool(correct_matches), count, xyc, match, points, stream_int())
     return points
 
 
@@ -1321,14 +1061,7 @@ def rig_fuse(points, poses, type_count, merge_radius, object_radius, cap_f, over
     obj = torch.empty((k, cap_f), dtype=torch.int32, device=dev)
     member = torch.empty((n_pairs, k, cap), dtype=torch.int32, device=dev)
     words = torch.empty((2,), dtype=torch.int32, device=dev)        # n_obj, overflow
-    T = _ops()
-    if T is not None:
-        _dispatch(T.rig_fuse, points, poses, tc, merge_radius, object_radius, fused, n_fused, views, obj, member, words[0:1], words[1:2], stream_int(), overflow)
-    else:
-        tca = (ctypes.c_int32 * max(1, k - 1))(*tc)
-        _lib.check(_lib.lib().okp_rig_fuse(points.data_ptr(), poses.data_ptr(), n_pairs, k, cap, tca, merge_radius, object_radius, cap_f,
-                                           overflow.data_ptr() if overflow is not None else None, fused.data_ptr(), n_fused.data_ptr(), views.data_ptr(),
-                                           obj.data_ptr(), member.data_ptr(), words[0:1].data_ptr(), words[1:2].data_ptr(), stream_handle()), "okp_rig_fuse")
+    _dispatch(_ops().rig_fuse, points, poses, tc, merge_radius, object_radius, fused, n_fused, views, obj, member, words[0:1], words[1:2], stream_int(), overflow)
     return {"fused": fused, "n_fused": n_fused, "views": views, "object": obj, "member": member, "n_obj": words[0], "overflow": words[1]}
 
 
@@ -1430,12 +1163,7 @@ def project_labels(cam, world_points, T_WC, scale=511.0 / 720.0, crop=(198.0, 0.
     labels = torch.empty((n, p, 3), dtype=torch.float64, device=T_WC.device)
     if n == 0 or p == 0:
         return labels
-    T = _ops()
-    if T is not None:
-        _dispatch(T.project_labels, _cam_list(cam), world_points, T_WC, float(scale), float(crop[0]), float(crop[1]), labels, stream_int())
-    else:
-        _lib.check(_lib.lib().okp_project_labels(ctypes.byref(cam), world_points.data_ptr(), p, T_WC.data_ptr(), n, float(scale), float(crop[0]),
-                                                 float(crop[1]), labels.data_ptr(), stream_handle()), "okp_project_labels")
+    _dispatch(_ops().project_labels, _cam_list(cam), world_points, T_WC, float(scale), float(crop[0]), float(crop[1]), labels, stream_int())
     COUNTERS["launches"] += 1
     return labels
 
@@ -1443,7 +1171,7 @@ def project_labels(cam, world_points, T_WC, scale=511.0 / 720.0, crop=(198.0, 0.
 def render_targets(labels, n_obj, type_count):
     """labels [N, max_obj * nk, 3] fp64, n_obj [N] int32 (device), type_count = [1] + keypoint_config -> (heat [N,K,64,64], depth [N,K,64,64],
     centers [N,K-1,2,64,64]) fp32: what the reference's SceneDataset yields for these key points (okp_render_targets)."""
-    tc, n, max_obj = check_labels(labels, n_obj, type_count)
+    tc, n, _ = check_labels(labels, n_obj, type_count)
     require_cuda(labels, "labels")
     k, dev = len(tc), labels.device
     heat = torch.empty((n, k, TARGET_SIZE, TARGET_SIZE), dtype=torch.float32, device=dev)
@@ -1451,12 +1179,7 @@ def render_targets(labels, n_obj, type_count):
     centers = torch.empty((n, k - 1, 2, TARGET_SIZE, TARGET_SIZE), dtype=torch.float32, device=dev)
     if n == 0:
         return heat, depth, centers
-    T = _ops()
-    if T is not None:
-        _dispatch(T.render_targets, labels, n_obj, tc, heat, depth, centers, stream_int())
-    else:
-        _lib.check(_lib.lib().okp_render_targets(labels.data_ptr(), n_obj.data_ptr(), n, max_obj, (ctypes.c_int32 * k)(*tc), k, heat.data_ptr(),
-                                                 depth.data_ptr(), centers.data_ptr(), stream_handle()), "okp_render_targets")
+    _dispatch(_ops().render_targets, labels, n_obj, tc, heat, depth, centers, stream_int())
     COUNTERS["launches"] += 1
     return heat, depth, centers
 
@@ -1494,9 +1217,8 @@ def keypoint_loss(p_heatmaps, p_depth, p_centers, type_count, labels=None, n_obj
         raise OkpError(f"first = {first}, total = {total}: the {n} frames of this call must lie inside the batch")
     if (labels is None) == (targets is None):
         raise OkpError("give either labels (with n_obj) or targets = (heat, depth, centers)")
-    max_obj = 0
     if labels is not None:
-        tc, _, max_obj = check_labels(labels, n_obj, tc, total)
+        tc = check_labels(labels, n_obj, tc, total)[0]
         if labels.device != dev:
             raise OkpError(f"labels are on {labels.device}, the predictions on {dev}")
     else:
@@ -1519,18 +1241,9 @@ def keypoint_loss(p_heatmaps, p_depth, p_centers, type_count, labels=None, n_obj
                  "mask_count": torch.empty((total, k), dtype=torch.int32, device=dev),
                  "out": torch.empty((1 + 3 * s,), dtype=torch.float64, device=dev)}
     partial, terms, mask_count, out = state["partial"], state["terms"], state["mask_count"], state["out"]
-    T = _ops()
-    if T is not None:
-        th, td, tcn = targets if targets is not None else (None, None, None)
-        _dispatch(T.keypoint_loss, lists[0], lists[1], lists[2], first, total, labels, n_obj, tc, th, td, tcn, float(depth_weight), float(center_weight),
-                  partial, terms, mask_count, out, stream_int())
-    else:
-        ptrs = [(ctypes.c_void_p * s)(*[t.data_ptr() for t in lst]) for lst in lists]
-        tp = [t.data_ptr() for t in targets] if targets is not None else [None, None, None]
-        _lib.check(_lib.lib().okp_keypoint_loss(ptrs[0], ptrs[1], ptrs[2], s, first, n, total, k, labels.data_ptr() if labels is not None else None,
-                                                n_obj.data_ptr() if labels is not None else None, max_obj, (ctypes.c_int32 * k)(*tc), tp[0], tp[1], tp[2],
-                                                float(depth_weight), float(center_weight), partial.data_ptr(), terms.data_ptr(), mask_count.data_ptr(),
-                                                out.data_ptr(), stream_handle()), "okp_keypoint_loss")
+    th, td, tcn = targets if targets is not None else (None, None, None)
+    _dispatch(_ops().keypoint_loss, lists[0], lists[1], lists[2], first, total, labels, n_obj, tc, th, td, tcn, float(depth_weight), float(center_weight),
+              partial, terms, mask_count, out, stream_int())
     COUNTERS["launches"] += 2 if first + n == total else 1
     return {"loss": out[0], "heat": out[1:1 + s], "depth": out[1 + s:1 + 2 * s], "center": out[1 + 2 * s:], "terms": terms, "mask_count": mask_count,
             "partial": partial, "out": out}

@@ -523,6 +523,32 @@ class AssociationComponent:
 GRAPH_SIDE_STREAMS = True
 
 
+def _capture(step):
+    """`step` (a callable without arguments, reading static device tensors) as a hipGraph -> (graph, the static outputs of the captured call)."""
+    for _ in range(2):                                       # warm-up: plans, allocator pools, kernel attributes, calibration tables
+        step()
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    keep, ops.SIDE_STREAMS = ops.SIDE_STREAMS, ops.SIDE_STREAMS and GRAPH_SIDE_STREAMS
+    try:
+        with torch.cuda.graph(graph):
+            static_out = step()
+    finally:
+        ops.SIDE_STREAMS = keep
+    return graph, static_out
+
+
+def _raise_on_overflow(flag, fused=False):
+    """A tick's overflow word (host int) as the OkpError it stands for; fused: the word of a fused tick, ops.FUSE_OVERFLOW read as well."""
+    if flag & 1:
+        raise OkpError("peak capacity exceeded in a tick; raise `capacity`")
+    if flag & ops.RANGE_OVERFLOW:
+        raise OkpError("an activation of the split-product network left the fp16 range in this tick: its maps are not fp32-grade "
+                       "(load the network with on_overflow='float32', or run it in torch.float32)")
+    if fused and flag & ops.FUSE_OVERFLOW:
+        raise OkpError("a key-point type had more fused clusters than fit in a tick; raise `fuse_capacity`")
+
+
 def _live_plans(net):
     """Every device plan object currently cached by the modules of `net` (ConvPlan / StemPlan / tuples of them)."""
     found = []
@@ -625,16 +651,7 @@ class BatchedKeypointPipeline:
         batches (batch 8: 2.7 -> 2.2 ms per step).  Returns a CapturedStep; it also unpacks as
         (step, static_input, static_outputs): replay with step.replay(new_frames) or static_input.copy_(...); step.replay()."""
         static_in = frames.clone()
-        for _ in range(2):                                   # warm-up: plans, allocator pools, kernel attributes
-            self.forward_device(static_in)
-        torch.cuda.synchronize()
-        graph = torch.cuda.CUDAGraph()
-        keep, ops.SIDE_STREAMS = ops.SIDE_STREAMS, ops.SIDE_STREAMS and GRAPH_SIDE_STREAMS
-        try:
-            with torch.cuda.graph(graph):
-                static_out = self.forward_device(static_in)
-        finally:
-            ops.SIDE_STREAMS = keep
+        graph, static_out = _capture(lambda: self.forward_device(static_in))
         return CapturedStep(self.net, graph, static_in, static_out)
 
     def postprocess_device(self, heat, depth, centers, range_flag=None):
@@ -773,16 +790,7 @@ class SceneScorer:
         overwritten in place with .copy_()); replay(frames) returns the static result dict."""
         static_in = frames.clone()
         static_labels = {"points": labels["points"].clone(), "n_obj": labels["n_obj"].clone()}
-        for _ in range(2):
-            self.score(static_in, static_labels)
-        torch.cuda.synchronize()
-        graph = torch.cuda.CUDAGraph()
-        keep, ops.SIDE_STREAMS = ops.SIDE_STREAMS, ops.SIDE_STREAMS and GRAPH_SIDE_STREAMS
-        try:
-            with torch.cuda.graph(graph):
-                static_out = self.score(static_in, static_labels)
-        finally:
-            ops.SIDE_STREAMS = keep
+        graph, static_out = _capture(lambda: self.score(static_in, static_labels))
         step = CapturedStep(self.net, graph, static_in, static_out)
         step.static_labels = static_labels
         return step
@@ -943,16 +951,7 @@ class StereoStreamPipeline:
     def capture(self, frames):
         """Capture the network pass of a tick for this frame shape into a hipGraph (one graph launch instead of ~66)."""
         static_in = frames.clone()
-        for _ in range(2):
-            self.net.deployed(static_in)
-        torch.cuda.synchronize()
-        graph = torch.cuda.CUDAGraph()
-        keep, ops.SIDE_STREAMS = ops.SIDE_STREAMS, ops.SIDE_STREAMS and GRAPH_SIDE_STREAMS
-        try:
-            with torch.cuda.graph(graph):
-                static_out = self.net.deployed(static_in)
-        finally:
-            ops.SIDE_STREAMS = keep
+        graph, static_out = _capture(lambda: self.net.deployed(static_in))
         self._graph = CapturedStep(self.net, graph, static_in, static_out)
         return self._graph
 
@@ -1083,16 +1082,7 @@ class StereoStreamPipeline:
         self._check_fused_tick(frames.shape[0] // 2, first_pair)
         static_in = frames.clone()
         static_heat = heat_override.clone() if heat_override is not None else None
-        for _ in range(2):                                   # warm-up: plans, allocator pools, kernel attributes, calibration table
-            self.tick_device(static_in, heat_override=static_heat, first_pair=first_pair)
-        torch.cuda.synchronize()
-        graph = torch.cuda.CUDAGraph()
-        keep, ops.SIDE_STREAMS = ops.SIDE_STREAMS, ops.SIDE_STREAMS and GRAPH_SIDE_STREAMS
-        try:
-            with torch.cuda.graph(graph):
-                static_out = self.tick_device(static_in, heat_override=static_heat, first_pair=first_pair)
-        finally:
-            ops.SIDE_STREAMS = keep
+        graph, static_out = _capture(lambda: self.tick_device(static_in, heat_override=static_heat, first_pair=first_pair))
         step = CapturedTick(self.net, graph, static_in, static_out, static_heat)
         step._table = self._table(frames.device)               # (the graph reads it on every replay)
         step._poses = self._poses.get(frames.device) if self._poses_host is not None else None       # (and the pose table)
@@ -1104,12 +1094,7 @@ class StereoStreamPipeline:
         unmatched slot) and `overflow` only, in ONE device -> host copy; raises OkpError like tick() when the overflow word is set."""
         pts = out["points"]
         flat = torch.cat([out["overflow"].reshape(1).to(torch.float64), pts.reshape(-1)]).cpu().numpy()        # the one D2H copy
-        flag = int(flat[0])
-        if flag & 1:
-            raise OkpError("peak capacity exceeded in a tick; raise `capacity`")
-        if flag & ops.RANGE_OVERFLOW:
-            raise OkpError("an activation of the split-product network left the fp16 range in this tick: its maps are not fp32-grade "
-                           "(load the network with on_overflow='float32', or run it in torch.float32)")
+        _raise_on_overflow(int(flat[0]))
         pts = flat[1:].reshape(tuple(pts.shape))
         result = []
         for p in range(pts.shape[0]):
@@ -1182,14 +1167,8 @@ class StereoStreamPipeline:
         K, cap_f = f["views"].shape
         parts = [out["overflow"].reshape(1), f["n_obj"].reshape(1), f["n_fused"], f["views"].reshape(-1), f["object"].reshape(-1)]
         flat = torch.cat([t.to(torch.float64) for t in parts] + [f["fused"].reshape(-1)]).cpu().numpy()          # the one D2H copy (int32 is exact in fp64)
-        flag, n_obj = int(flat[0]), int(flat[1])
-        if flag & 1:
-            raise OkpError("peak capacity exceeded in a tick; raise `capacity`")
-        if flag & ops.RANGE_OVERFLOW:
-            raise OkpError("an activation of the split-product network left the fp16 range in this tick: its maps are not fp32-grade "
-                           "(load the network with on_overflow='float32', or run it in torch.float32)")
-        if flag & ops.FUSE_OVERFLOW:
-            raise OkpError("a key-point type had more fused clusters than fit in a tick; raise `fuse_capacity`")
+        _raise_on_overflow(int(flat[0]), fused=True)
+        n_obj = int(flat[1])
         n_fused = flat[2:2 + K].astype(np.int64)
         at = 2 + K
         views = flat[at:at + K * cap_f].astype(np.int32).reshape(K, cap_f)

@@ -366,6 +366,31 @@ def test_torch_ops_are_registered_over_the_c_abi():
         ops.peak_nms(torch.zeros(1, 1, 8, 8))
 
 
+def test_ctypes_adapter_speaks_the_dispatcher_signatures():
+    """_ctypes_ops is the ctypes binding behind the signatures of torch.ops.okp: every function it defines is a schema of csrc/okp_torch.cpp
+    with the same positional parameters (names, order, defaults), and every entry point ops.py calls exists in both - ops.py has one call
+    site per entry point, so this is what keeps the two bindings from drifting."""
+    import inspect
+    import re
+    from object_keypoints_amd import _ctypes_ops, _lib, ops
+    T = _lib.torch_ops()
+    assert T is not None, "libokp_torch.so is built by object_keypoints_amd.build alongside libokp_hip.so"
+    adapter = {n: f for n, f in vars(_ctypes_ops).items() if inspect.isfunction(f) and f.__module__ == _ctypes_ops.__name__ and not n.startswith("_")}
+    called = set(re.findall(r"\b(?:_ops\(\)|B)\.([a-z0-9_]+)", inspect.getsource(ops)))
+    assert len(called) >= 38 and {"conv_forward", "conv_create", "stem_set_range_flag", "keypoint_loss", "rig_fuse"} <= called, sorted(called)
+    assert called <= set(adapter), f"ops.py calls {sorted(called - set(adapter))}, which the ctypes adapter does not define"
+    for name, fn in sorted(adapter.items()):
+        assert hasattr(T, name), f"_ctypes_ops.{name} is not a schema of okp_torch.cpp"
+        want = getattr(T, name).default._schema.arguments
+        got = list(inspect.signature(fn).parameters.values())
+        assert all(p.kind is p.POSITIONAL_OR_KEYWORD for p in got), name
+        assert [p.name for p in got] == [a.name for a in want], f"{name}: {[p.name for p in got]} != {[a.name for a in want]}"
+        for p, a in zip(got, want):
+            assert (p.default is not p.empty) == a.has_default_value(), f"{name}({p.name}): a default on one side only"
+            if a.has_default_value():
+                assert p.default == a.default_value and type(p.default) is type(a.default_value), f"{name}({p.name}): default {p.default!r} != {a.default_value!r}"
+
+
 def test_from_calibration_picks_the_camera_model(tmp_path):
     """camera_utils.from_calibration (reference :131-144): equidistant -> FisheyeCamera, radtan -> RadTanPinholeCamera,
     anything else -> ValueError."""
