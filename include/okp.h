@@ -357,7 +357,8 @@ int okp_heads_forward(const okp_conv* l1, const okp_conv* l2, const okp_head_out
  *   peak = box == maxpool5x5(box) (padding ignored)  and  box > 0.5      [bit-exact contract]
  *   per peak (row-major order): confidence = sum of p over the clipped 5x5 window,
  *   (x, y) = sum(p * (x, y)) / confidence.
- * heat: [n_maps][h][w] fp32 (any height; w <= 2340: the map is walked in LDS-resident strips).  Outputs per map, capacity `cap` peaks:
+ * heat: [n_maps][h][w] fp32 (any height; w <= 2336: the map is walked in LDS-resident strips of R rows,
+ *   (2 R + 12) rows of w + 4 floats in 128 KiB, R = min(h, (32768 / (w + 4) - 12) / 2) >= 1).  Outputs per map, capacity `cap` peaks:
  *   count[n_maps]        total peaks found (may exceed cap; only the first cap are stored)
  *   yx[n_maps][cap][2]   int32 (y, x)
  *   xyc[n_maps][cap][3]  fp32 (x, y, confidence)
@@ -413,15 +414,22 @@ int okp_lift_peaks(const okp_camera* cam, const int32_t* count_dev, const float*
  * received MORE votes than the type has instances the reference's k-means reduction (pipeline.py:143-148: unseeded sklearn KMeans,
  * reproducible as a set only) is done here as a deterministic Lloyd iteration - one lane per vote (the object's first 64), fp64,
  * farthest-point initialisation seeded by each of the four most confident votes in turn, least inertia wins - into `reduced`.
+ * The reduction is deterministic: votes ranked by confidence descending, then peak order; the farthest vote with the lowest index on a tie;
+ * a vote joins the nearest centre, the lower cluster on a tie; an empty cluster keeps its centre; the iteration stops when no centre moves
+ * or after 32 iterations; a run's inertia is that of its last assignment step; the earlier seed wins equal inertia; centres rounded to fp32.
+ * A vote whose predicted centre is not finite (a NaN or an infinity in the centre-offset map) is for no object (assign -1; `pred` holds it).
  *   count [n][K] int32, xyc [n][K][cap][3] fp32 (okp_peak_nms outputs), centers [n][K-1][2][h][w] fp32
- *   n_obj   [n] int32                         objects per frame (= min(count[n][0], max_obj)); max_obj <= 64
+ *   n_obj   [n] int32                         objects per frame (= min(count[n][0], cap, max_obj)); 1 <= max_obj <= 64
  *   sel     [n][max_obj][K-1][max_sel] int32  selected peak indices into map k, -1 = empty slot
  *   n_votes [n][max_obj][K-1] int32           votes the object received for that type (before the cut)
  *   assign  [n][K][cap] int32                 object index each peak voted for (-1: none / dropped / map 0)
  *   pred    [n][K][cap][2] fp64               the predicted centre (x, y) each peak voted with
  *   reduced [n][max_obj][K-1][max_sel][2] fp32 (ABI 7; may be NULL = no reduction): for a type with type_count > 1 (<= max_sel) and
  *           n_votes > type_count the type_count cluster centres (x, y), NaN everywhere else
- * One wave per frame; K <= 8, max_sel <= 8.
+ * Slots beyond min(count, cap) of `assign` / `pred` are -1 / 0, unused `sel` -1, unused `n_votes` 0; a frame without a centre peak has no
+ * votes: all of its outputs are at these values.
+ * One wave per frame; 2 <= K <= 8, 1 <= max_sel <= 8, cap >= 1, h >= 1, w >= 1, every type_count[k] >= 1 (a type with more
+ * instances than max_sel keeps its first max_sel votes and is not reduced); anything else is refused (OKP_EINVAL) before any launch.
  * ---------------------------------------------------------------------------------- */
 int okp_group_objects(const int32_t* count_dev, const float* xyc_dev, const float* centers_dev, int32_t n, int32_t K,
                       int32_t cap, int32_t h, int32_t w, const int32_t* type_count /* HOST [K-1] */, float max_dist,

@@ -1099,8 +1099,16 @@ extern "C" int okp_capacity_overflow(const int32_t* count, int32_t n_maps, int32
 extern "C" int okp_group_objects(const int32_t* count, const float* xyc, const float* centers, int32_t n, int32_t K, int32_t cap,
                                  int32_t h, int32_t w, const int32_t* type_count, float max_dist, int32_t max_obj, int32_t max_sel,
                                  int32_t* n_obj, int32_t* sel, int32_t* n_votes, int32_t* assign, double* pred, float* reduced, void* stream) {
-  if (!count || !xyc || !centers || !type_count || !n_obj || !sel || !n_votes || !assign || !pred) { okp_set_error("okp_group_objects: null argument"); return OKP_EINVAL; }
-  if (K < 2 || K > 8 || max_sel < 1 || max_sel > 8 || max_obj < 1 || max_obj > 64 || cap < 1) { okp_set_error("okp_group_objects: K in [2,8], max_sel in [1,8], max_obj in [1,64] required"); return OKP_EINVAL; }
+  const char* fn = "okp_group_objects";
+  if (K < 2 || K > 8) { okp_set_error("%s: K = %d outside [2, 8] (the centre map and one to seven key-point types)", fn, K); return OKP_EINVAL; }
+  if (max_sel < 1 || max_sel > 8) { okp_set_error("%s: max_sel = %d outside [1, 8]", fn, max_sel); return OKP_EINVAL; }
+  if (max_obj < 1 || max_obj > 64) { okp_set_error("%s: max_obj = %d outside [1, 64] (one lane per object)", fn, max_obj); return OKP_EINVAL; }
+  if (cap < 1) { okp_set_error("%s: cap = %d; a map holds at least one peak", fn, cap); return OKP_EINVAL; }
+  if (h < 1 || w < 1) { okp_set_error("%s: h = %d, w = %d; the centre maps have at least one pixel", fn, h, w); return OKP_EINVAL; }
+  if (!type_count) { okp_set_error("%s: null type_count", fn); return OKP_EINVAL; }
+  for (int k = 0; k < K - 1; ++k)
+    if (type_count[k] < 1) { okp_set_error("%s: type_count[%d] = %d; every type keeps at least one key point per object", fn, k, type_count[k]); return OKP_EINVAL; }
+  if (!count || !xyc || !centers || !n_obj || !sel || !n_votes || !assign || !pred) { okp_set_error("%s: null argument", fn); return OKP_EINVAL; }   // (reduced may be NULL: no reduction)
   if (n <= 0) return OKP_OK;
   GroupParams p;
   p.count = count; p.xyc = xyc; p.centers = centers; p.n = n; p.K = K; p.cap = cap; p.H = h; p.W = w;

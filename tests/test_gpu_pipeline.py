@@ -491,3 +491,240 @@ def test_peak_nms_on_large_maps_matches_oracle(h, w):
         pts, conf = op.refine_peaks(maps[k], idx)
         np.testing.assert_allclose(xyc[0, k, :n, :2], np.stack(pts), rtol=2e-6, atol=1e-4)
         np.testing.assert_allclose(xyc[0, k, :n, 2], np.array(conf), rtol=1e-6, atol=1e-6)
+
+
+# ---- the capacity edges of the post-network kernels ------------------------------------------------------------------------------------
+
+def _strip_rows(h, w):
+    """The strip height of okp_peak_nms from the rule in include/okp.h: (2 R + 12) rows of w + 4 floats in 128 KiB of LDS."""
+    return min(h, (32768 // (w + 4) - 12) // 2)
+
+
+def _nms_against_oracle(maps, cap=4096):
+    from object_keypoints_amd import ops
+    count, yx, xyc = [t.cpu().numpy() for t in ops.peak_nms(torch.from_numpy(maps[None]).cuda(), cap=cap)]
+    found = []
+    for k in range(maps.shape[0]):
+        idx = op.peak_indices(maps[k])
+        n = idx.shape[0]
+        assert int(count[0, k]) == n and n <= cap
+        assert yx[0, k, :n].tolist() == idx.tolist()
+        assert not yx[0, k, n:].any() and not xyc[0, k, n:].any()               # unused slots are zero
+        if n:
+            pts, conf = op.refine_peaks(maps[k], idx)
+            np.testing.assert_allclose(xyc[0, k, :n, :2], np.stack(pts), rtol=2e-6, atol=1e-4)
+            np.testing.assert_allclose(xyc[0, k, :n, 2], np.array(conf), rtol=1e-6, atol=1e-6)
+        found.append(idx)
+    return found
+
+
+@pytest.mark.parametrize("h,w", [(22, 1023), (22, 1024), (22, 1025), (7, 2336), (18, 1024)])
+def test_peak_nms_on_wide_maps_and_at_strip_boundaries(h, w):
+    """W >= 1024, where the division-free row walk has sy = 0 (and sx = 0 at W == 1024), up to the widest map, 2336 pixels, whose strips
+    are one row high (R = 1, H = 7: every row a strip boundary); H = 22 leaves a partial last strip of R = 9, H = 18 none.  Map 0: Gaussian
+    bumps.  Map 1: isolated hot pixels - each a 5x5 plateau of 25 tied box sums - centred on rows r0 - 2 .. r0 + 2 of every strip boundary
+    r0, so that plateaus straddle the boundaries.  Map 2: the same on the first and last two columns.  Against the oracle's peak_indices /
+    refine_peaks with the tolerances of the large-map test above."""
+    R = _strip_rows(h, w)
+    assert R == (1 if w == 2336 else 9) and (h % R != 0) == (h == 22)
+    rng = np.random.default_rng(h * 10000 + w)
+    maps = np.zeros((3, h, w), np.float32)
+    ys, xs = np.meshgrid(np.arange(h, dtype=np.float32), np.arange(w, dtype=np.float32), indexing="ij")
+    for _ in range(12):
+        cy, cx = rng.uniform(0, h - 1), rng.uniform(0, w - 1)
+        maps[0] += np.exp(-((xs - cx) ** 2 + (ys - cy) ** 2) / 4.0).astype(np.float32)
+    col = 9
+    boundaries = list(range(R, h, R))
+    for r0 in boundaries:
+        for dy in (-2, -1, 0, 1, 2):
+            if 0 <= r0 + dy < h:
+                maps[1, r0 + dy, col % w] = 0.9
+                col += 37
+    assert col < w, "every hot pixel in a column of its own"
+    for j, r0 in enumerate([0] + boundaries):
+        for x in ((0, w - 1) if j % 2 == 0 else (1, w - 2)):
+            maps[2, min(r0 + j % 3, h - 1), x] = 0.9
+    maps = np.clip(maps, 0, 1).astype(np.float32)
+    found = _nms_against_oracle(maps)
+    assert len(found[0]) >= 8 and len(found[1]) >= 25 * len(boundaries) and len(found[2]) >= 4 and found[2][:, 1].min() <= 1 and found[2][:, 1].max() >= w - 2
+    rows = set(found[1][:, 0].tolist())
+    assert all({r0 - 1, r0} <= rows for r0 in boundaries), "peaks on both sides of every strip boundary"
+
+
+def test_peak_nms_on_a_single_pixel_and_a_single_row():
+    """A 1x1 map (one peak, or none) and a 1xW map."""
+    for v, n in ((0.7, 1), (0.3, 0)):
+        found = _nms_against_oracle(np.full((1, 1, 1), v, np.float32), cap=4)
+        assert len(found[0]) == n
+    row = np.zeros((2, 1, 50), np.float32)
+    row[0, 0, [0, 7, 8, 30, 49]] = (0.9, 0.6, 0.6, 0.55, 0.8)
+    row[1, 0, 20:24] = 0.2
+    found = _nms_against_oracle(row, cap=64)
+    assert len(found[0]) >= 5 and len(found[1]) >= 1
+
+
+def test_peak_nms_capacity_cut_inside_a_step():
+    """The map is classified 1024 pixels at a time; `cap` is chosen so that the cap-th peak falls inside the second step with further peaks
+    after it in the same step and in later ones: count is the total, the first cap peaks are stored; with room to spare the unused slots are zero."""
+    from object_keypoints_amd import ops
+    rng = np.random.default_rng(77)
+    heat = (rng.random((64, 64)) < 0.004).astype(np.float32) * 0.9
+    idx = op.peak_indices(heat)
+    lin = idx[:, 0].astype(np.int64) * 64 + idx[:, 1]
+    before, inside = int((lin < 1024).sum()), int(((lin >= 1024) & (lin < 2048)).sum())
+    assert inside >= 4 and int((lin >= 2048).sum()) > 0
+    cap = before + inside // 2
+    assert lin[cap - 1] >= 1024 and lin[cap] < 2048
+    dev = torch.from_numpy(heat[None, None]).cuda()
+    count, yx, xyc = [t.cpu().numpy() for t in ops.peak_nms(dev, cap=cap)]
+    assert int(count[0, 0]) == len(idx) > cap and yx[0, 0].tolist() == idx[:cap].tolist()
+    pts, conf = op.refine_peaks(heat, idx[:cap])
+    np.testing.assert_allclose(xyc[0, 0, :, :2], np.stack(pts), rtol=2e-6, atol=2e-5)
+    np.testing.assert_allclose(xyc[0, 0, :, 2], np.array(conf), rtol=1e-6, atol=1e-6)
+    roomy = len(idx) + 5
+    count, yx, xyc = [t.cpu().numpy() for t in ops.peak_nms(dev, cap=roomy)]
+    assert int(count[0, 0]) == len(idx) and yx[0, 0, :len(idx)].tolist() == idx.tolist() and not yx[0, 0, len(idx):].any() and not xyc[0, 0, len(idx):].any()
+
+
+@pytest.mark.parametrize("size", [1, 3, 5, 7, 15])
+def test_nms_maxpool_sizes_and_small_maps(size):
+    """okp_nms_maxpool against the oracle's nms, bit for bit: every odd size class (1, the default 5, the largest 15), on maps smaller than the
+    window (2x3, 7x5) and on 64x64; values on a coarse grid, so that ties with the window maximum are common."""
+    from object_keypoints_amd import ops
+    from oracle import net as onet
+    rng = np.random.default_rng(size)
+    for shape in ((3, 2, 2, 3), (2, 3, 7, 5), (2, 2, 64, 64)):
+        x = torch.from_numpy((rng.integers(0, 9, shape) / 8.0).astype(np.float32))
+        assert torch.equal(ops.nms_maxpool(x.cuda(), size=size).cpu(), onet.nms(x, size=size)), shape
+
+
+def test_nms_maxpool_runs_its_grid_stride_loop_a_second_time():
+    """The grid is capped at 4096 blocks of 256 threads = 64 * 4 * 64 * 64 elements: a [64, 5, 64, 64] batch (K = 5) needs a second pass of
+    the grid-stride loop for its last fifth."""
+    from object_keypoints_amd import ops
+    from oracle import net as onet
+    x = torch.from_numpy((np.random.default_rng(5).integers(0, 17, (64, 5, 64, 64)) / 16.0).astype(np.float32))
+    assert x.numel() > 4096 * 256
+    got = ops.nms_maxpool(x.cuda(), size=5).cpu()
+    want = onet.nms(x, size=5)
+    assert torch.equal(got, want) and int((want[:, 4] > 0).sum()) > 0
+
+
+def _lift_spec(undistort, fx, fy, cx, cy, xy, depth, max_x, max_y):
+    """The formula of include/okp.h in NumPy: undistort (P = K) -> float32 -> round half to even -> clip to [0, max_x] x [0, max_y] ->
+    z = depth[y][x] -> K^-1 [xu, yu, 1]^T z, in fp64."""
+    u = undistort(xy.astype(np.float32).astype(np.float64)).astype(np.float32)
+    xi = np.clip(np.rint(u[:, 0]).astype(np.int64), 0, max_x)
+    yi = np.clip(np.rint(u[:, 1]).astype(np.int64), 0, max_y)
+    z = depth[yi, xi].astype(np.float64)
+    return np.stack([(u[:, 0].astype(np.float64) - cx) / fx * z, (u[:, 1].astype(np.float64) - cy) / fy * z, z], axis=1), xi, yi
+
+
+@pytest.mark.parametrize("model", ["equidistant", "radtan"])
+@pytest.mark.parametrize("max_x,max_y", [(79, 47), (60, 30)])
+def test_lifting_on_a_map_that_is_not_square(model, max_x, max_y):
+    """okp_lift_peaks / okp_unproject_depth on 48x80 depth maps, the clip box at the map edge and inside it, both camera models, points
+    that undistort outside the box (clipped), map_id < 0 rows (NaN), and count > cap in okp_lift_peaks: all cap rows are filled and nothing
+    behind the output is written (a guard region).  The 1e-6 m bound of the calibrated-camera tests above."""
+    from object_keypoints_amd import ops
+    from object_keypoints_amd.perception.utils import camera_utils as cu
+    H, W, cap, K = 48, 80, 8, 3
+    if model == "equidistant":
+        K_, D = np.array([[38.0, 0.0, 41.0], [0.0, 37.5, 23.0], [0.0, 0.0, 1.0]]), np.array([-0.02, 0.004, -0.001, 0.0002])
+        cam = cu.FisheyeCamera(K_, D, [H, W])
+        undistort = lambda xy: og.fisheye_undistort(xy, K_, D, P=K_)
+    else:
+        K_, D = np.array([[42.0, 0.0, 40.0], [0.0, 41.5, 24.0], [0.0, 0.0, 1.0]]), np.array([-0.28, 0.07, 0.0006, -0.0002])
+        cam = cu.RadTanPinholeCamera(K_, D, [H, W])
+        undistort = lambda xy: og.radtan_undistort(xy, K_, D, P=K_)
+    rng = np.random.default_rng(max_x * 100 + max_y)
+    depth = rng.uniform(0.3, 1.5, (2, K, H, W)).astype(np.float32)
+    xyc = np.zeros((2, K, cap, 3), np.float32)
+    xyc[..., 0] = rng.uniform(-6.0, W + 6.0, (2, K, cap))
+    xyc[..., 1] = rng.uniform(-6.0, H + 6.0, (2, K, cap))
+    xyc[..., 2] = rng.uniform(0.5, 2.0, (2, K, cap))
+    count = np.array([[3, 0, cap], [cap, 5, cap + 3]], np.int32)                  # the last map holds more peaks than were stored
+    n_rows = 2 * K * cap
+    buf = torch.full((n_rows * 4 + 64,), -7.0, dtype=torch.float64, device="cuda")
+    out = buf[:n_rows * 4].view(2, K, cap, 4)
+    ops._dispatch(ops._ops().lift_peaks, ops._cam_list(cam.okp()), torch.from_numpy(count).cuda(), torch.from_numpy(xyc).cuda(), torch.from_numpy(depth).cuda(),
+                  max_x, max_y, out, ops.stream_int())
+    torch.cuda.synchronize()
+    assert bool((buf[n_rows * 4:] == -7.0).all()), "okp_lift_peaks wrote behind its output"
+    got = out.cpu().numpy()
+    outside = 0
+    for n in range(2):
+        for k in range(K):
+            c = min(int(count[n, k]), cap)
+            assert np.isnan(got[n, k, c:]).all()
+            if c:
+                want, xi, yi = _lift_spec(undistort, K_[0, 0], K_[1, 1], K_[0, 2], K_[1, 2], xyc[n, k, :c, :2], depth[n, k], max_x, max_y)
+                assert np.abs(got[n, k, :c, :3] - want).max() < 1e-6
+                assert np.array_equal(got[n, k, :c, 3], xyc[n, k, :c, 2].astype(np.float64))
+                outside += int(((xi == 0) | (xi == max_x) | (yi == 0) | (yi == max_y)).sum())
+    assert outside >= 4, "some points undistort outside the clip box"
+    # the one-call form on the same points, with rows that are skipped
+    flat = xyc.reshape(-1, cap, 3)[:, :, :2].reshape(-1, 2)
+    ids = np.repeat(np.arange(2 * K, dtype=np.int32), cap)
+    ids[::5] = -1
+    ids[7] = -3
+    one = ops.unproject_depth(cam.okp(), torch.from_numpy(flat).cuda(), torch.from_numpy(ids).cuda(), torch.from_numpy(depth.reshape(-1, H, W)).cuda(), max_x, max_y).cpu().numpy()
+    assert np.isnan(one[ids < 0]).all() and not np.isnan(one[ids >= 0]).any()
+    for m in range(2 * K):
+        rows = np.nonzero(ids == m)[0]
+        want, _, _ = _lift_spec(undistort, K_[0, 0], K_[1, 1], K_[0, 2], K_[1, 2], flat[rows], depth.reshape(-1, H, W)[m], max_x, max_y)
+        assert np.abs(one[rows] - want).max() < 1e-6
+
+
+def test_lifting_reads_the_half_even_pixel_exactly():
+    """A radtan camera without distortion and with fx = fy = 1, cx = cy = 0 undistorts a point to itself exactly (every correction term is a
+    product with zero, the scale 1 / (1 + 0)), so the pixel read is round-half-even of the input and the 3D point is (x z, y z, z) with x, y, z
+    fp32 values multiplied in fp64: exact products (24 + 24 bits), compared with ==.  Coordinates x.5 in both axes, and clipping on both sides."""
+    from object_keypoints_amd import _lib, ops
+    H, W = 48, 80
+    okp_cam = ops.make_camera(np.eye(3), np.zeros(4), model=_lib.CAM_RADTAN)
+    depth = (1.0 + np.arange(H * W, dtype=np.float32).reshape(1, H, W) / 4096.0).astype(np.float32)        # a value of its own per pixel
+    xs = [0.5, 1.5, 2.5, 10.5, 11.5, 78.5, 79.5, -0.5, -3.2, W + 7.0, 30.25, 30.75]
+    ys = [0.5, 1.5, 2.5, 10.5, 11.5, 46.5, 47.5, -0.5, -3.2, H + 7.0, 20.25, 20.75]
+    xy = np.array([(x, y) for x in xs for y in ys], np.float32)
+    expect_x = dict(zip(np.float32(xs).tolist(), [0, 2, 2, 10, 12, 78, 79, 0, 0, 79, 30, 31]))
+    expect_y = dict(zip(np.float32(ys).tolist(), [0, 2, 2, 10, 12, 46, 47, 0, 0, 47, 20, 21]))
+    got = ops.unproject_depth(okp_cam, torch.from_numpy(xy).cuda(), torch.zeros(len(xy), dtype=torch.int32).cuda(), torch.from_numpy(depth).cuda(), W - 1, H - 1).cpu().numpy()
+    for (x, y), g in zip(xy, got):
+        z = float(depth[0, expect_y[float(y)], expect_x[float(x)]])
+        assert g.tolist() == [float(x) * z, float(y) * z, z], (x, y)
+    count = torch.tensor([[len(xy)]], dtype=torch.int32).cuda()
+    xyc = torch.from_numpy(np.concatenate([xy, np.ones((len(xy), 1), np.float32)], axis=1)[None, None]).cuda()
+    lifted = ops.lift_peaks(okp_cam, count, xyc, torch.from_numpy(depth[None]).cuda(), W - 1, H - 1).cpu().numpy()
+    assert np.array_equal(lifted[0, 0, :, :3], got) and (lifted[0, 0, :, 3] == 1.0).all()
+
+
+@pytest.mark.parametrize("K", [2, 5, 8])
+def test_capacity_overflow_over_many_maps(K):
+    """More than 256 maps (the kernel's one workgroup strides over them): the single offending map at flat index 300; a count above max_obj
+    on a non-centre map only leaves bit 0 clear, the same count on a centre map (i % K == 0) sets it; the range flag sets bit 1 alone."""
+    from object_keypoints_amd import ops
+    cap, max_obj = 32, 4
+    N = -(-512 // K)
+    assert N * K >= 512
+    base = np.random.default_rng(K).integers(0, max_obj + 1, (N, K)).astype(np.int32)
+
+    def flag(count, range_flag=None):
+        return int(ops.capacity_overflow(torch.from_numpy(count).cuda(), cap, max_obj, range_flag=range_flag))
+
+    assert flag(base) == 0
+    at = base.copy().reshape(-1)
+    at[300] = cap                                                               # exactly full: no overflow (a centre map when 300 % K == 0: then above max_obj)
+    assert flag(at.reshape(N, K)) == (1 if 300 % K == 0 else 0)
+    at[300] = cap + 1
+    assert flag(at.reshape(N, K)) == 1
+    i = 300 + (1 if 300 % K == 0 else 0)                                        # a non-centre map beyond the first 256
+    assert i % K != 0
+    side = base.copy().reshape(-1)
+    side[i] = max_obj + 1
+    assert flag(side.reshape(N, K)) == 0
+    centre = base.copy().reshape(-1)
+    centre[i - i % K] = max_obj + 1
+    assert i - i % K >= 256 and flag(centre.reshape(N, K)) == 1
+    raised = torch.ones(1, dtype=torch.int32).cuda()
+    assert flag(base, raised) == 2 and flag(centre.reshape(N, K), raised) == 3 and flag(base, torch.zeros(1, dtype=torch.int32).cuda()) == 0
