@@ -38,7 +38,8 @@ extern "C" {
                                     okp_stereo_triangulate; the struct okp_stereo_pair, okp_stereo_match_rig, okp_stereo_triangulate_rig;
                                     OKP_YUV_I420 / OKP_YUV_NV12 / OKP_YUV_BT601 / OKP_YUV_BT709, okp_preprocess_yuv420;
                                     okp_project_labels, okp_render_targets, okp_keypoint_loss (scoring labelled scenes);
-                                    okp_rig_fuse (a rig's stereo pairs fused into one object list in the rig frame) */
+                                    okp_rig_fuse (a rig's stereo pairs fused into one object list in the rig frame);
+                                    okp_object_points, okp_rig_object_points, okp_object_pose (each object's 6-DoF pose from its 3D key points) */
 
 /* OKP_F16: IEEE half activations / weights, fp32 accumulate (BASELINE configs[4]).
  * OKP_F32X3 (okp_conv plans only): fp32 activations, weights and results like OKP_F32 - every tensor argument of such a plan is an
@@ -553,6 +554,82 @@ int okp_rig_fuse(const double* points_dev, const double* poses_dev, int32_t n_pa
                  const int32_t* type_count /* HOST [K-1] */, double merge_radius, double object_radius, int32_t cap_f,
                  const int32_t* overflow_in_dev, double* fused_dev, int32_t* n_fused_dev, int32_t* views_dev, int32_t* object_dev,
                  int32_t* member_dev, int32_t* n_obj_dev, int32_t* overflow_dev, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * Object pose (csrc/okp_pose.hip): the loose 3D key points of every object -> the object's 6-DoF pose, the rigid transform that carries
+ * the object model onto them.  The reference stops short of this step: ObjectKeypointPipeline takes the model `points_3d` and ignores it
+ * (perception/pipeline.py:174-178), perception/utils/ros.py turns a 4 x 4 transform into a pose message, notebooks/keypoint_debug.ipynb
+ * solves a PnP on the host.  There is no reference implementation: the specification is this comment (tests/object_pose_spec.py restates
+ * it in NumPy).
+ *
+ * The model: [S][3] fp64, S = 1 + sum(type_count) <= OKP_POSE_MAX_POINTS.  Rows 1.. are the object's key points in type order, type k >= 1
+ * with type_count[k-1] = c_k instances in c_k consecutive rows; row 0 is their mean, the centre point (perception/datasets/video.py:121-129).
+ * The object point table `tab` [B][max_obj][S][4] fp64 has the same slots: slot 0 the detected centre, then c_k slots per type; a row is
+ * (X, Y, Z, confidence), and a slot is FILLED when its four values are finite - any other row (all NaN by convention) is an empty slot.
+ *
+ * okp_object_points: the batched grouping -> tab [n][max_obj][S][4].
+ *   points [n][K][cap][4] fp64 (okp_lift_peaks), sel [n][max_obj][K-1][max_sel], n_obj [n], n_votes [n][max_obj][K-1] int32 and reduced
+ *   [n][max_obj][K-1][max_sel][2] fp32 (okp_group_objects; reduced may be NULL), depth [n][K][h][w] fp32.
+ *   Object o < min(n_obj[f], max_obj) of frame f: slot 0 = points[f][0][o] (centre peak o); slot j < c_k of type k = points[f][k][sel[f][o][k-1][j]],
+ *   empty where that index is negative or not below cap.  Where the type was reduced - reduced given, c_k > 1, n_votes[f][o][k-1] > c_k - slot j
+ *   is the cluster centre reduced[f][o][k-1][j] lifted through depth map (f, k) by exactly the arithmetic of okp_lift_peaks /
+ *   okp_unproject_depth (one device function: the three agree bit for bit), with confidence 1.0 (a cluster centre has none of its own);
+ *   empty where the centre is NaN.  Objects from n_obj[f] on: all NaN.  Every row of tab is written.
+ *   Refused: K outside [2, 16], a type_count below 1 or above max_sel, S > OKP_POSE_MAX_POINTS, n, cap, max_obj, max_sel < 1; with reduced
+ *   given also a null cam / depth, an unknown camera model, h, w < 1 or a clip box (max_x, max_y) outside the depth map.
+ *
+ * okp_rig_object_points: the same table [1][cap_f][S][4] from okp_rig_fuse outputs, in the rig frame.  fused [K][cap_f][4] fp64, n_fused [K],
+ *   object [K][cap_f] int32.  Object o < min(n_fused[0], cap_f): slot 0 = fused[0][o]; slot j of type k = the j-th cluster c < n_fused[k] of
+ *   type k, in cluster order, with object[k][c] == o (at most c_k of them, by the fusion's own cut; further ones are ignored).  Objects beyond:
+ *   all NaN.  Refused: K outside [2, OKP_RIG_MAX_TYPES], cap_f outside [1, OKP_RIG_MAX_FUSED], a type_count below 1, S > OKP_POSE_MAX_POINTS.
+ *
+ * okp_object_pose: tab [B][max_obj][S][4], n_obj [B] int32, model [S][3] fp64 in DEVICE memory (a captured graph reads it on every replay;
+ *   the kernel cannot check it: the caller validates it - finite, row 0 the mean, not collinear - before the upload), type_count HOST [K-1].
+ *   For every object o < n_obj[b] (objects from n_obj[b] on: NaN pose and fit, assignment -1, used 0, status 0):
+ *   0. used = the number of filled slots.  used < 3: status OKP_POSE_FEW, pose and fit NaN, assignment -1.  Otherwise the detected points are
+ *      centred on their mean p_bar; when the second-largest eigenvalue of their 3 x 3 scatter sum (p - p_bar)(p - p_bar)^T is
+ *      <= OKP_POSE_DEGENERACY * its trace (collinear points: the rotation is not determined) the status is OKP_POSE_DEGENERATE, pose and fit
+ *      NaN, assignment -1, and no hypothesis is tried.
+ *   1. Hypotheses.  The filled slots of type k (n_k <= c_k of them, compacted in slot order) are mapped injectively onto the c_k model rows of
+ *      that type: a map is (a_0, ..., a_{n_k - 1}), a_j the instance the j-th filled slot takes.  Per type the maps are listed in
+ *      lexicographic order; the hypothesis index is mixed radix over the types with type 1 the slowest digit.  A filled slot 0 maps to model
+ *      row 0.  H = prod_k c_k! / (c_k - n_k)! <= prod_k c_k! <= OKP_POSE_MAX_HYPOTHESES (refused otherwise): [1,3] has 6, [1,1,1] has 1.
+ *   2. Cost.  A hypothesis costs  min over rotations R of  sum_i |R (m_i - m_bar) - (p_i - p_bar)|^2  over its `used` point pairs, uniform
+ *      weights, both means over the pairs in use.  (Found as sum |p'|^2 + sum |m'|^2 - 2 lambda_max of Horn's 4 x 4 matrix, by Jacobi
+ *      rotations, one hypothesis per lane; how the minimum is found is not part of the contract.)  The least cost wins; on exactly equal
+ *      cost the lowest index.  The runner-up is the least-cost hypothesis among the others, again the lowest index on equal cost.
+ *   3. Pose.  R is the minimising rotation of the winner, proper (det +1); t = p_bar - R m_bar;  X = R m + t  takes model coordinates to the
+ *      table's frame (the camera frame for okp_object_points, the rig frame for okp_rig_object_points).  When the second-largest eigenvalue
+ *      of the scatter of the winner's matched MODEL points is <= OKP_POSE_DEGENERACY * its trace: OKP_POSE_DEGENERATE, pose and fit NaN, the
+ *      winner's assignment is kept.
+ *   4. Outputs, all written by every call:
+ *      pose [B][max_obj][12] fp64     row-major [R | t] (3 x 4)
+ *      fit [B][max_obj][2] fp64       rmse = sqrt(sum_i |R m_i + t - p_i|^2 / used) of the winner and of the runner-up (its own best R), both
+ *                                     from the residuals, not from the eigenvalue identity (which cancels to ~1e-8 m on a perfect fit).  The
+ *                                     runner-up's is NaN when H = 1; it measures the symmetry ambiguity: close to the winner's, the data
+ *                                     cannot tell the two assignments apart
+ *      assignment [B][max_obj][S] int32   the model row of each table slot, -1 for an empty slot
+ *      used [B][max_obj] int32
+ *      status [B][max_obj] int32      0, OKP_POSE_FEW, OKP_POSE_DEGENERATE, or OKP_POSE_POOR: rmse > max_rmse (the pose is still written;
+ *                                     max_rmse > 0, may be +infinity; NaN or <= 0 is refused)
+ *   Refused: B, max_obj < 1, K outside [2, 16], a type_count below 1, S > OKP_POSE_MAX_POINTS, prod c_k! > OKP_POSE_MAX_HYPOTHESES.
+ * All three: fp64, one wave per object, no atomics, no host wait, the same bits on every run, capturable in a hipGraph; arguments are
+ * checked on the host before any launch (OKP_EINVAL, the message names the argument).
+ * ---------------------------------------------------------------------------------- */
+#define OKP_POSE_MAX_POINTS 16
+#define OKP_POSE_MAX_HYPOTHESES 1024
+#define OKP_POSE_DEGENERACY 1e-12
+#define OKP_POSE_FEW 1
+#define OKP_POSE_DEGENERATE 2
+#define OKP_POSE_POOR 4
+int okp_object_points(const okp_camera* cam, const double* points_dev, const int32_t* sel_dev, const int32_t* n_obj_dev, const int32_t* n_votes_dev,
+                      const float* reduced_dev, const float* depth_dev, int32_t n, int32_t K, int32_t cap, int32_t h, int32_t w, int32_t max_x,
+                      int32_t max_y, const int32_t* type_count /* HOST [K-1] */, int32_t max_obj, int32_t max_sel, double* tab_dev, void* stream);
+int okp_rig_object_points(const double* fused_dev, const int32_t* n_fused_dev, const int32_t* object_dev, int32_t K, int32_t cap_f,
+                          const int32_t* type_count /* HOST [K-1] */, double* tab_dev, void* stream);
+int okp_object_pose(const double* tab_dev, const int32_t* n_obj_dev, int32_t B, int32_t max_obj, const double* model_dev,
+                    const int32_t* type_count /* HOST [K-1] */, int32_t K, double max_rmse, double* pose_dev, double* fit_dev,
+                    int32_t* assignment_dev, int32_t* used_dev, int32_t* status_dev, void* stream);
 
 /* Undistort only (FisheyeCamera.undistort, camera_utils.py:75-81 / RadTanPinholeCamera.undistort, :57-62, by cam->model):
  * xy [m][2] fp32 -> out [m][2] fp64.  okp_fisheye_undistort is the same entry point under its round-1 name. */

@@ -318,6 +318,26 @@ def rig_fuse(points, poses, type_count, merge_radius, object_radius, fused, n_fu
                                        member.data_ptr(), n_obj.data_ptr(), overflow.data_ptr(), stream), "okp_rig_fuse")
 
 
+# ---- object pose: point tables and the fit (csrc/okp_pose.hip) -------------------------------------------------------------------------------
+def object_points(camera, points, sel, n_obj, n_votes, depth, max_x, max_y, type_count, tab, stream, reduced=None):
+    n, k, cap, _ = points.shape
+    _lib.check(_lib.lib().okp_object_points(_camera(camera), points.data_ptr(), sel.data_ptr(), n_obj.data_ptr(), n_votes.data_ptr(), _ptr(reduced), depth.data_ptr(),
+                                            n, k, cap, depth.shape[2], depth.shape[3], max_x, max_y, _int32s(type_count, k - 1), sel.shape[1], sel.shape[3],
+                                            tab.data_ptr(), stream), "okp_object_points")
+
+
+def rig_object_points(fused, n_fused, object, type_count, tab, stream):
+    k, cap_f, _ = fused.shape
+    _lib.check(_lib.lib().okp_rig_object_points(fused.data_ptr(), n_fused.data_ptr(), object.data_ptr(), k, cap_f, _int32s(type_count, max(1, k - 1)), tab.data_ptr(), stream),
+               "okp_rig_object_points")
+
+
+def object_pose(tab, n_obj, model, type_count, max_rmse, pose, fit, assignment, used, status, stream):
+    b, max_obj = tab.shape[0], tab.shape[1]
+    _lib.check(_lib.lib().okp_object_pose(tab.data_ptr(), n_obj.data_ptr(), b, max_obj, model.data_ptr(), _int32s(type_count), len(type_count) + 1, max_rmse,
+                                          pose.data_ptr(), fit.data_ptr(), assignment.data_ptr(), used.data_ptr(), status.data_ptr(), stream), "okp_object_pose")
+
+
 # ---- scoring labelled scenes -----------------------------------------------------------------------------------------------------------------
 def project_labels(camera, world_points, T_WC, scale, crop_x, crop_y, labels, stream):
     _lib.check(_lib.lib().okp_project_labels(_camera(camera), world_points.data_ptr(), world_points.shape[0], T_WC.data_ptr(), T_WC.shape[0], scale, crop_x, crop_y,

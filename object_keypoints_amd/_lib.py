@@ -111,6 +111,11 @@ SIGNATURES = [
     ("okp_stereo_triangulate_rig", c_int, [c_void_p, c_int32, c_int32, c_int, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
     ("okp_rig_fuse", c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, POINTER(c_int32), c_double, c_double, c_int32, c_void_p, c_void_p, c_void_p,
                              c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    ("okp_object_points", c_int, [POINTER(okp_camera), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32,
+                                  c_int32, c_int32, POINTER(c_int32), c_int32, c_int32, c_void_p, c_void_p]),
+    ("okp_rig_object_points", c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, POINTER(c_int32), c_void_p, c_void_p]),
+    ("okp_object_pose", c_int, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, POINTER(c_int32), c_int32, c_double, c_void_p, c_void_p, c_void_p, c_void_p,
+                                c_void_p, c_void_p]),
     ("okp_fisheye_undistort", c_int, [POINTER(okp_camera), c_void_p, c_int32, c_void_p, c_void_p]),
     ("okp_camera_undistort", c_int, [POINTER(okp_camera), c_void_p, c_int32, c_void_p, c_void_p]),
     ("okp_project_labels", c_int, [POINTER(okp_camera), c_void_p, c_int32, c_void_p, c_int32, c_double, c_double, c_double, c_void_p, c_void_p]),

@@ -14,52 +14,11 @@
 
 namespace {
 
-__device__ __forceinline__ void fisheye_undistort(const okp_camera& cam, double x, double y, double& xu, double& yu) {
-  const double pwx = (x - cam.cx) / cam.fx, pwy = (y - cam.cy) / cam.fy;
-  double theta_d = sqrt(pwx * pwx + pwy * pwy);
-  const double half_pi = 1.5707963267948966;
-  theta_d = fmin(fmax(-half_pi, theta_d), half_pi);
-  double scale = 1.0;
-  if (theta_d > 1e-8) {
-    double theta = theta_d;
-    for (int j = 0; j < 10; ++j) {
-      const double t2 = theta * theta, t4 = t2 * t2, t6 = t4 * t2, t8 = t6 * t2;
-      theta = theta_d / (1.0 + cam.d[0] * t2 + cam.d[1] * t4 + cam.d[2] * t6 + cam.d[3] * t8);
-    }
-    scale = tan(theta) / theta_d;
-  }
-  xu = cam.fx * (pwx * scale) + cam.cx;   // R = I, P = K
-  yu = cam.fy * (pwy * scale) + cam.cy;
-}
-
-// cv2.undistortPoints(xy, K, D, P=K) of OpenCV 3.4 for the plumb-bob model with D = (k1, k2, p1, p2): five fixed-point iterations
-//   x <- (x0 - (2 p1 x y + p2 (r^2 + 2 x^2))) / (1 + k1 r^2 + k2 r^4),  y likewise with p1 (r^2 + 2 y^2) + 2 p2 x y
-__device__ __forceinline__ void radtan_undistort(const okp_camera& cam, double u, double v, double& xu, double& yu) {
-  const double x0 = (u - cam.cx) / cam.fx, y0 = (v - cam.cy) / cam.fy;
-  const double k1 = cam.d[0], k2 = cam.d[1], p1 = cam.d[2], p2 = cam.d[3];
-  double x = x0, y = y0;
-  for (int j = 0; j < 5; ++j) {
-    const double r2 = x * x + y * y;
-    const double icdist = 1.0 / (1.0 + (k2 * r2 + k1) * r2);
-    const double dx = 2.0 * p1 * x * y + p2 * (r2 + 2.0 * x * x);
-    const double dy = p1 * (r2 + 2.0 * y * y) + 2.0 * p2 * x * y;
-    x = (x0 - dx) * icdist;
-    y = (y0 - dy) * icdist;
-  }
-  xu = cam.fx * x + cam.cx;
-  yu = cam.fy * y + cam.cy;
-}
-
-__device__ __forceinline__ void camera_undistort(const okp_camera& cam, double x, double y, double& xu, double& yu) {
-  if (cam.model == OKP_CAM_RADTAN) radtan_undistort(cam, x, y, xu, yu);
-  else fisheye_undistort(cam, x, y, xu, yu);
-}
-
 __global__ void okp_undistort_kernel(okp_camera cam, const float* __restrict__ xy, int m, double* __restrict__ out) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= m) return;
   double xu, yu;
-  camera_undistort(cam, (double)xy[2 * i], (double)xy[2 * i + 1], xu, yu);
+  okp_undistort_point(cam, (double)xy[2 * i], (double)xy[2 * i + 1], xu, yu);
   out[2 * i] = xu;
   out[2 * i + 1] = yu;
 }
@@ -75,19 +34,7 @@ __global__ void okp_unproject_kernel(okp_camera cam, const float* __restrict__ x
     out[3 * i] = nan; out[3 * i + 1] = nan; out[3 * i + 2] = nan;
     return;
   }
-  // cv2 returns the dtype it was given: the reference passes float32 peaks, so the undistorted
-  // point is rounded to float32 before it is used (pipeline.py:167-171).
-  double xu, yu;
-  camera_undistort(cam, (double)xy[2 * i], (double)xy[2 * i + 1], xu, yu);
-  const float xf = (float)xu, yf = (float)yu;
-  int xi = (int)rintf(xf), yi = (int)rintf(yf);        // numpy round = half to even
-  xi = min(max(xi, 0), max_x);
-  yi = min(max(yi, 0), max_y);
-  const double z = (double)depth[((size_t)map * H + yi) * W + xi];
-  // K^-1 [x y 1]^T * z for an upper-triangular K without skew
-  out[3 * i + 0] = ((double)xf - cam.cx) / cam.fx * z;
-  out[3 * i + 1] = ((double)yf - cam.cy) / cam.fy * z;
-  out[3 * i + 2] = z;
+  okp_lift_pixel(cam, xy[2 * i], xy[2 * i + 1], depth + (size_t)map * H * W, W, max_x, max_y, out[3 * i], out[3 * i + 1], out[3 * i + 2]);
 }
 
 __global__ void okp_lift_peaks_kernel(okp_camera cam, const int* __restrict__ count, const float* __restrict__ xyc, int n_maps,
@@ -103,16 +50,7 @@ __global__ void okp_lift_peaks_kernel(okp_camera cam, const int* __restrict__ co
     return;
   }
   const float* pk = xyc + (size_t)i * 3;
-  double xu, yu;
-  camera_undistort(cam, (double)pk[0], (double)pk[1], xu, yu);
-  const float xf = (float)xu, yf = (float)yu;
-  int xi = (int)rintf(xf), yi = (int)rintf(yf);
-  xi = min(max(xi, 0), max_x);
-  yi = min(max(yi, 0), max_y);
-  const double z = (double)depth[((size_t)map * H + yi) * W + xi];
-  o[0] = ((double)xf - cam.cx) / cam.fx * z;
-  o[1] = ((double)yf - cam.cy) / cam.fy * z;
-  o[2] = z;
+  okp_lift_pixel(cam, pk[0], pk[1], depth + (size_t)map * H * W, W, max_x, max_y, o[0], o[1], o[2]);
   o[3] = (double)pk[2];
 }
 
@@ -516,8 +454,8 @@ __global__ void okp_triangulate_thread_kernel(TriParams tp, const float* __restr
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= m) return;
   double xl, yl, xr, yr;
-  camera_undistort(tp.left, (double)lxy[2 * i], (double)lxy[2 * i + 1], xl, yl);
-  camera_undistort(tp.right, (double)rxy[2 * i], (double)rxy[2 * i + 1], xr, yr);
+  okp_undistort_point(tp.left, (double)lxy[2 * i], (double)lxy[2 * i + 1], xl, yl);
+  okp_undistort_point(tp.right, (double)rxy[2 * i], (double)rxy[2 * i + 1], xr, yr);
   // cv2 hands float32 back for float32 input (camera_utils.py:93-97)
   xl = (double)(float)xl; yl = (double)(float)yl; xr = (double)(float)xr; yr = (double)(float)yr;
   if (tp.correct) {
@@ -765,8 +703,8 @@ __device__ void null_vector4_oct(int g, double a0, double a1, double a2, double 
 // Shared with okp_stereo_triangulate_kernel.  Every lane of the wave must call it (wave-wide votes inside).
 __device__ __forceinline__ void triangulate_pair_oct(const TriParams& tp, int g, const float* lp, const float* rp, double& X, double& Y, double& Z) {
   double ux = 0.0, uy = 0.0;
-  if (g == 0) camera_undistort(tp.left, (double)lp[0], (double)lp[1], ux, uy);
-  else if (g == 1) camera_undistort(tp.right, (double)rp[0], (double)rp[1], ux, uy);
+  if (g == 0) okp_undistort_point(tp.left, (double)lp[0], (double)lp[1], ux, uy);
+  else if (g == 1) okp_undistort_point(tp.right, (double)rp[0], (double)rp[1], ux, uy);
   // cv2 hands float32 back for float32 input (camera_utils.py:93-97)
   double xl = (double)(float)oct_bcast(ux, 0), yl = (double)(float)oct_bcast(uy, 0);
   double xr = (double)(float)oct_bcast(ux, 1), yr = (double)(float)oct_bcast(uy, 1);
@@ -892,14 +830,14 @@ __global__ __launch_bounds__(64) void okp_stereo_match_kernel(const StereoParams
   const float* xr = p.xyc + (size_t)mr * p.cap * 3;
   for (int i = lane; i < n; i += 64) {
     double xu, yu;
-    camera_undistort(left, (double)xl[3 * i], (double)xl[3 * i + 1], xu, yu);
+    okp_undistort_point(left, (double)xl[3 * i], (double)xl[3 * i + 1], xu, yu);
     const double l0 = F[0] * xu + F[1] * yu + F[2], l1 = F[3] * xu + F[4] * yu + F[5], l2 = F[6] * xu + F[7] * yu + F[8];
     s.line[i][0] = l0; s.line[i][1] = l1; s.line[i][2] = l2;
     s.line[i][3] = fmax(sqrt(l0 * l0 + l1 * l1), 1e-300);
   }
   for (int j = lane; j < m; j += 64) {
     double xu, yu;
-    camera_undistort(right, (double)xr[3 * j], (double)xr[3 * j + 1], xu, yu);
+    okp_undistort_point(right, (double)xr[3 * j], (double)xr[3 * j + 1], xu, yu);
     const double c0 = xu * F[0] + yu * F[3] + F[6], c1 = xu * F[1] + yu * F[4] + F[7];
     s.pt[j][0] = xu; s.pt[j][1] = yu;
     s.pt[j][2] = fmax(sqrt(c0 * c0 + c1 * c1), 1e-300);

@@ -309,6 +309,66 @@ struct okp_conv {
                            // single-tap OKP_F32X3 plans: [cout / 16][hi | lo][cin / 32][lane][8 fp16], row i of wave w = channel 16 w + i (okp_fire_x3.hip)
 };
 
+// Camera models on the device (fp64), shared by the geometry kernels (okp_geom.hip) and the object point tables (okp_pose.hip).
+static __device__ __forceinline__ void okp_fisheye_undistort_point(const okp_camera& cam, double x, double y, double& xu, double& yu) {
+  const double pwx = (x - cam.cx) / cam.fx, pwy = (y - cam.cy) / cam.fy;
+  double theta_d = sqrt(pwx * pwx + pwy * pwy);
+  const double half_pi = 1.5707963267948966;
+  theta_d = fmin(fmax(-half_pi, theta_d), half_pi);
+  double scale = 1.0;
+  if (theta_d > 1e-8) {
+    double theta = theta_d;
+    for (int j = 0; j < 10; ++j) {
+      const double t2 = theta * theta, t4 = t2 * t2, t6 = t4 * t2, t8 = t6 * t2;
+      theta = theta_d / (1.0 + cam.d[0] * t2 + cam.d[1] * t4 + cam.d[2] * t6 + cam.d[3] * t8);
+    }
+    scale = tan(theta) / theta_d;
+  }
+  xu = cam.fx * (pwx * scale) + cam.cx;   // R = I, P = K
+  yu = cam.fy * (pwy * scale) + cam.cy;
+}
+
+// cv2.undistortPoints(xy, K, D, P=K) of OpenCV 3.4 for the plumb-bob model with D = (k1, k2, p1, p2): five fixed-point iterations
+//   x <- (x0 - (2 p1 x y + p2 (r^2 + 2 x^2))) / (1 + k1 r^2 + k2 r^4),  y likewise with p1 (r^2 + 2 y^2) + 2 p2 x y
+static __device__ __forceinline__ void okp_radtan_undistort_point(const okp_camera& cam, double u, double v, double& xu, double& yu) {
+  const double x0 = (u - cam.cx) / cam.fx, y0 = (v - cam.cy) / cam.fy;
+  const double k1 = cam.d[0], k2 = cam.d[1], p1 = cam.d[2], p2 = cam.d[3];
+  double x = x0, y = y0;
+  for (int j = 0; j < 5; ++j) {
+    const double r2 = x * x + y * y;
+    const double icdist = 1.0 / (1.0 + (k2 * r2 + k1) * r2);
+    const double dx = 2.0 * p1 * x * y + p2 * (r2 + 2.0 * x * x);
+    const double dy = p1 * (r2 + 2.0 * y * y) + 2.0 * p2 * x * y;
+    x = (x0 - dx) * icdist;
+    y = (y0 - dy) * icdist;
+  }
+  xu = cam.fx * x + cam.cx;
+  yu = cam.fy * y + cam.cy;
+}
+
+static __device__ __forceinline__ void okp_undistort_point(const okp_camera& cam, double x, double y, double& xu, double& yu) {
+  if (cam.model == OKP_CAM_RADTAN) okp_radtan_undistort_point(cam, x, y, xu, yu);
+  else okp_fisheye_undistort_point(cam, x, y, xu, yu);
+}
+
+// The lifting of one pixel position to a camera-frame point, the arithmetic of DetectionToPoint.__call__ (perception/pipeline.py:164-171) that
+// okp_unproject_depth, okp_lift_peaks and okp_object_points share (one body: their results agree bit for bit): undistort (P = K) -> the
+// undistorted point rounded to fp32 (cv2 returns the dtype it was given, and the reference passes float32 peaks) -> round half to even, clip
+// to [0, max_x] x [0, max_y] -> z = depth[y][x] of the W-wide map `depth` -> K^-1 [x y 1]^T * z for an upper-triangular K without skew.
+static __device__ __forceinline__ void okp_lift_pixel(const okp_camera& cam, float x, float y, const float* __restrict__ depth, int W, int max_x, int max_y,
+                                                      double& X, double& Y, double& Z) {
+  double xu, yu;
+  okp_undistort_point(cam, (double)x, (double)y, xu, yu);
+  const float xf = (float)xu, yf = (float)yu;
+  int xi = (int)rintf(xf), yi = (int)rintf(yf);        // numpy round = half to even
+  xi = min(max(xi, 0), max_x);
+  yi = min(max(yi, 0), max_y);
+  const double z = (double)depth[(size_t)yi * W + xi];
+  X = ((double)xf - cam.cx) / cam.fx * z;
+  Y = ((double)yf - cam.cy) / cam.fy * z;
+  Z = z;
+}
+
 void okp_set_error(const char* fmt, ...);
 uint16_t okp_f32_to_16(int dtype, float f);          // host: fp32 -> bf16 / fp16 bits, round to nearest even
 int okp_check_hip(hipError_t e, const char* what);

@@ -572,6 +572,60 @@ void rig_fuse(const Tensor& points, const Tensor& poses, at::IntArrayRef type_co
                         sp(stream)), "okp_rig_fuse");
 }
 
+// Object pose (csrc/okp_pose.hip).  object_points: the batched grouping -> tab [N,max_obj,S,4] float64; rig_object_points: rig_fuse outputs ->
+// tab [1,cap_f,S,4]; object_pose: tab, n_obj [B], model [S,3] (device) -> pose [B,max_obj,12], fit [B,max_obj,2], assignment [B,max_obj,S], used, status
+void object_points(at::ArrayRef<double> camera, const Tensor& points, const Tensor& sel, const Tensor& n_obj, const Tensor& n_votes, const Tensor& depth,
+                   int64_t max_x, int64_t max_y, at::IntArrayRef type_count, const Tensor& tab, int64_t stream, const optional<Tensor>& reduced) {
+  check_dev(points, at::kDouble, "points"); check_dev(sel, at::kInt, "sel"); check_dev(n_obj, at::kInt, "n_obj"); check_dev(n_votes, at::kInt, "n_votes");
+  check_dev(depth, at::kFloat, "depth"); check_dev(tab, at::kDouble, "tab");
+  if (reduced.has_value()) check_dev(*reduced, at::kFloat, "reduced");
+  TORCH_CHECK(points.dim() == 4 && points.size(3) == 4 && sel.dim() == 4 && depth.dim() == 4, "okp: points is [N,K,cap,4] float64, sel [N,max_obj,K-1,max_sel] int32, depth [N,K,H,W]");
+  const int64_t n = points.size(0), K = points.size(1), cap = points.size(2), max_obj = sel.size(1), max_sel = sel.size(3);
+  int64_t S = 1;
+  for (auto c : type_count) S += c;
+  TORCH_CHECK((int64_t)type_count.size() == K - 1, "okp: type_count has K-1 entries");
+  TORCH_CHECK(sel.size(0) == n && sel.size(2) == K - 1 && n_obj.numel() == n && n_votes.numel() == n * max_obj * (K - 1) && depth.size(0) == n && depth.size(1) == K &&
+              (!reduced.has_value() || reduced->numel() == sel.numel() * 2) && tab.numel() == n * max_obj * S * 4, "okp: object_points buffers do not match");
+  const okp_camera cam = camera_of(camera);
+  std::vector<int32_t> tc(type_count.begin(), type_count.end());
+  check_rc(okp_object_points(&cam, points.data_ptr<double>(), sel.data_ptr<int32_t>(), n_obj.data_ptr<int32_t>(), n_votes.data_ptr<int32_t>(),
+                             reduced.has_value() ? reduced->data_ptr<float>() : nullptr, depth.data_ptr<float>(), (int32_t)n, (int32_t)K, (int32_t)cap,
+                             (int32_t)depth.size(2), (int32_t)depth.size(3), (int32_t)max_x, (int32_t)max_y, tc.data(), (int32_t)max_obj, (int32_t)max_sel,
+                             tab.data_ptr<double>(), sp(stream)), "okp_object_points");
+}
+
+void rig_object_points(const Tensor& fused, const Tensor& n_fused, const Tensor& object, at::IntArrayRef type_count, const Tensor& tab, int64_t stream) {
+  check_dev(fused, at::kDouble, "fused"); check_dev(n_fused, at::kInt, "n_fused"); check_dev(object, at::kInt, "object"); check_dev(tab, at::kDouble, "tab");
+  TORCH_CHECK(fused.dim() == 3 && fused.size(2) == 4, "okp: fused is [K,cap_f,4] float64");
+  const int64_t K = fused.size(0), cap_f = fused.size(1);
+  int64_t S = 1;
+  for (auto c : type_count) S += c;
+  TORCH_CHECK((int64_t)type_count.size() == K - 1, "okp: type_count has K-1 entries");
+  TORCH_CHECK(n_fused.numel() == K && object.numel() == K * cap_f && tab.numel() == cap_f * S * 4, "okp: rig_object_points buffers do not match");
+  std::vector<int32_t> tc(type_count.begin(), type_count.end());
+  tc.push_back(0);                                  // (K = 1: a non-null pointer for the entry point to refuse K with)
+  check_rc(okp_rig_object_points(fused.data_ptr<double>(), n_fused.data_ptr<int32_t>(), object.data_ptr<int32_t>(), (int32_t)K, (int32_t)cap_f, tc.data(),
+                                 tab.data_ptr<double>(), sp(stream)), "okp_rig_object_points");
+}
+
+void object_pose(const Tensor& tab, const Tensor& n_obj, const Tensor& model, at::IntArrayRef type_count, double max_rmse, const Tensor& pose, const Tensor& fit,
+                 const Tensor& assignment, const Tensor& used, const Tensor& status, int64_t stream) {
+  check_dev(tab, at::kDouble, "tab"); check_dev(n_obj, at::kInt, "n_obj"); check_dev(model, at::kDouble, "model"); check_dev(pose, at::kDouble, "pose");
+  check_dev(fit, at::kDouble, "fit"); check_dev(assignment, at::kInt, "assignment"); check_dev(used, at::kInt, "used"); check_dev(status, at::kInt, "status");
+  TORCH_CHECK(tab.dim() == 4 && tab.size(3) == 4, "okp: tab is [B,max_obj,S,4] float64");
+  const int64_t B = tab.size(0), max_obj = tab.size(1), S = tab.size(2);
+  int64_t want = 1;
+  for (auto c : type_count) want += c;
+  TORCH_CHECK(want == S && model.numel() == S * 3, "okp: tab has S = 1 + sum(type_count) slots and model is [S,3] float64");
+  TORCH_CHECK(n_obj.numel() == B && pose.numel() == B * max_obj * 12 && fit.numel() == B * max_obj * 2 && assignment.numel() == B * max_obj * S &&
+              used.numel() == B * max_obj && status.numel() == B * max_obj, "okp: object_pose outputs are pose [B,max_obj,12], fit [B,max_obj,2], assignment [B,max_obj,S], used and status [B,max_obj]");
+  std::vector<int32_t> tc(type_count.begin(), type_count.end());
+  tc.push_back(0);
+  check_rc(okp_object_pose(tab.data_ptr<double>(), n_obj.data_ptr<int32_t>(), (int32_t)B, (int32_t)max_obj, model.data_ptr<double>(), tc.data(), (int32_t)type_count.size() + 1,
+                           max_rmse, pose.data_ptr<double>(), fit.data_ptr<double>(), assignment.data_ptr<int32_t>(), used.data_ptr<int32_t>(), status.data_ptr<int32_t>(),
+                           sp(stream)), "okp_object_pose");
+}
+
 void lift_peaks(at::ArrayRef<double> camera, const Tensor& count, const Tensor& xyc, const Tensor& depth, int64_t max_x, int64_t max_y, const Tensor& out, int64_t stream) {
   TORCH_CHECK(xyc.is_cuda() && xyc.dim() == 4 && xyc.scalar_type() == at::kFloat && depth.is_cuda() && depth.scalar_type() == at::kFloat && depth.dim() == 4 && depth.is_contiguous() &&
               depth.size(0) == xyc.size(0) && depth.size(1) == xyc.size(1) && count.scalar_type() == at::kInt && out.scalar_type() == at::kDouble &&
@@ -727,6 +781,11 @@ TORCH_LIBRARY(okp, m) {
         "Tensor? range_flag=None) -> ()", stereo_match_rig);
   m.def("stereo_triangulate_rig(Tensor table, int first_pair, bool correct_matches, Tensor count, Tensor xyc, Tensor match, Tensor(a!) points, int stream) -> ()",
         stereo_triangulate_rig);
+  m.def("object_points(float[] camera, Tensor points, Tensor sel, Tensor n_obj, Tensor n_votes, Tensor depth, int max_x, int max_y, int[] type_count, Tensor(a!) tab, "
+        "int stream, Tensor? reduced=None) -> ()", object_points);
+  m.def("rig_object_points(Tensor fused, Tensor n_fused, Tensor object, int[] type_count, Tensor(a!) tab, int stream) -> ()", rig_object_points);
+  m.def("object_pose(Tensor tab, Tensor n_obj, Tensor model, int[] type_count, float max_rmse, Tensor(a!) pose, Tensor(b!) fit, Tensor(c!) assignment, "
+        "Tensor(d!) used, Tensor(e!) status, int stream) -> ()", object_pose);
   m.def("rig_fuse(Tensor points, Tensor poses, int[] type_count, float merge_radius, float object_radius, Tensor(a!) fused, Tensor(b!) n_fused, Tensor(c!) views, "
         "Tensor(d!) object, Tensor(e!) member, Tensor(f!) n_obj, Tensor(g!) overflow, int stream, Tensor? overflow_in=None) -> ()", rig_fuse);
   m.def("project_labels(float[] camera, Tensor world_points, Tensor T_WC, float scale, float crop_x, float crop_y, Tensor(a!) labels, int stream) -> ()", project_labels);

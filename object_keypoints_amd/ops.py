@@ -1065,6 +1065,147 @@ def rig_fuse(points, poses, type_count, merge_radius, object_radius, cap_f, over
     return {"fused": fused, "n_fused": n_fused, "views": views, "object": obj, "member": member, "n_obj": words[0], "overflow": words[1]}
 
 
+# ---- each object's 6-DoF pose from its 3D key points (csrc/okp_pose.hip; no reference counterpart: the specification is include/okp.h) -------
+POSE_MAX_POINTS, POSE_MAX_HYPOTHESES, POSE_DEGENERACY = 16, 1024, 1e-12          # include/okp.h OKP_POSE_*
+POSE_FEW, POSE_DEGENERATE, POSE_POOR = 1, 2, 4                                   # status words of object_pose()
+
+
+def _pose_type_count(keypoint_config, what="keypoint_config"):
+    try:
+        tc = [int(c) for c in keypoint_config]
+    except (TypeError, ValueError):
+        tc = None
+    if not tc or any(c < 1 for c in tc):
+        raise OkpError(f"{what} {keypoint_config!r}: one positive count for each key-point type after the centre")
+    s = 1 + sum(tc)
+    if s > POSE_MAX_POINTS:
+        raise OkpError(f"{what} {tc}: S = 1 + sum = {s} model points, above {POSE_MAX_POINTS}")
+    return tc, s
+
+
+def scatter_is_degenerate(points):
+    """The degeneracy test of okp_object_pose on a set of points [n,3]: the second-largest eigenvalue of the scatter of the centred points
+    is <= POSE_DEGENERACY x its trace (collinear points: a rotation about their line changes nothing)."""
+    p = np.asarray(points, dtype=np.float64)
+    p = p - p.mean(axis=0)
+    e = np.linalg.eigvalsh(p.T @ p)
+    return not e[1] > POSE_DEGENERACY * (p * p).sum()
+
+
+def object_model(points_3d, keypoint_config):
+    """The object model of okp_object_pose: points_3d [sum(keypoint_config), 3], the object's key points in model coordinates in type order
+    (type k >= 1 with count c_k in c_k consecutive rows: the layout of the reference's `points_3d`), -> float64 HOST tensor [S, 3],
+    S = 1 + sum(keypoint_config), row 0 their mean (the centre point, perception/datasets/video.py:121-129), which the caller moves to the
+    device once.  The kernel cannot check a device table, so a bad model is refused here: non-finite entries, a wrong row count, S above
+    POSE_MAX_POINTS, more than POSE_MAX_HYPOTHESES assignments (prod c_k!), key points that are collinear (scatter_is_degenerate)."""
+    tc, s = _pose_type_count(keypoint_config)
+    pts = np.asarray(points_3d, dtype=np.float64)
+    if pts.ndim != 2 or pts.shape[1] != 3 or pts.shape[0] != s - 1:
+        raise OkpError(f"points_3d has shape {tuple(pts.shape)}: keypoint_config {tc} asks for [{s - 1}, 3], one row per key point in type order")
+    if not np.isfinite(pts).all():
+        raise OkpError("points_3d must be finite")
+    h = 1
+    for c in tc:
+        h *= int(np.prod(np.arange(1, c + 1)))
+    if h > POSE_MAX_HYPOTHESES:
+        raise OkpError(f"keypoint_config {tc}: prod(c_k!) = {h} assignments of detected key points to model instances per object, above {POSE_MAX_HYPOTHESES}")
+    model = np.concatenate([pts.mean(axis=0)[None], pts])
+    if scatter_is_degenerate(model):
+        raise OkpError("points_3d: the model's points are collinear (the second eigenvalue of their scatter is not above "
+                       f"{POSE_DEGENERACY:g} x its trace): no rotation is determined by them")
+    return torch.from_numpy(model)
+
+
+def check_max_rmse(max_rmse):
+    """None -> +infinity (never POSE_POOR); otherwise a positive number of metres."""
+    if max_rmse is None:
+        return float("inf")
+    try:
+        v = float(max_rmse)
+    except (TypeError, ValueError):
+        v = float("nan")
+    if not v > 0.0:
+        raise OkpError(f"max_rmse = {max_rmse!r}: a positive length in metres (None or inf: no bound)")
+    return v
+
+
+def object_points(cam, out, type_count, max_x, max_y):
+    """The object point table of a batch (okp_object_points): `out` is the dict of BatchedKeypointPipeline.postprocess_device (points, sel,
+    n_obj, n_votes, reduced, depth), type_count the K-1 counts the grouping ran with -> tab [N, max_obj, S, 4] float64 (device): per object
+    slot 0 the centre, then c_k slots per type, rows (X, Y, Z, confidence), NaN rows = empty.  A reduced type (more votes than instances)
+    takes its cluster centres lifted as lift_peaks lifts a peak.  One launch, no host sync."""
+    points, sel, n_obj, n_votes, reduced, depth = (out[k] for k in ("points", "sel", "n_obj", "n_votes", "reduced", "depth"))
+    for name, t in (("points", points), ("sel", sel), ("n_obj", n_obj), ("n_votes", n_votes), ("depth", depth)):
+        require_cuda(t, name)
+    tc, s = _pose_type_count(type_count, "type_count")
+    if points.dtype != torch.float64 or points.dim() != 4 or points.shape[3] != 4:
+        raise OkpError("points must be float64 [N,K,cap,4] (lift_peaks)")
+    n, k, cap = (int(v) for v in points.shape[:3])
+    if len(tc) != k - 1:
+        raise OkpError(f"type_count {tc}: {k - 1} counts, one for each key-point type after the centre")
+    if sel.dtype != torch.int32 or sel.dim() != 4 or sel.shape[0] != n or sel.shape[2] != k - 1:
+        raise OkpError("sel must be int32 [N,max_obj,K-1,max_sel] (group_objects)")
+    max_obj, max_sel = int(sel.shape[1]), int(sel.shape[3])
+    if max(tc) > max_sel:
+        raise OkpError(f"type_count {tc}: a type has more instances than max_sel = {max_sel}, the peaks `sel` holds per type")
+    if n_obj.dtype != torch.int32 or tuple(n_obj.shape) != (n,) or n_votes.dtype != torch.int32 or tuple(n_votes.shape) != (n, max_obj, k - 1):
+        raise OkpError("n_obj must be int32 [N] and n_votes int32 [N,max_obj,K-1] (group_objects)")
+    if depth.dtype != torch.float32 or depth.dim() != 4 or tuple(depth.shape[:2]) != (n, k):
+        raise OkpError("depth must be float32 [N,K,H,W] matching the points")
+    if reduced is not None and (not reduced.is_cuda or reduced.dtype != torch.float32 or tuple(reduced.shape) != (n, max_obj, k - 1, max_sel, 2)):
+        raise OkpError("reduced must be float32 [N,max_obj,K-1,max_sel,2] on the device (group_objects)")
+    tab = torch.empty((n, max_obj, s, 4), dtype=torch.float64, device=points.device)
+    _dispatch(_ops().object_points, _cam_list(cam), points.contiguous(), sel.contiguous(), n_obj.contiguous(), n_votes.contiguous(), depth.contiguous(),
+              int(max_x), int(max_y), tc, tab, stream_int(), reduced.contiguous() if reduced is not None else None)
+    return tab
+
+
+def rig_object_points(fused, type_count):
+    """The object point table of a fused tick (okp_rig_object_points): `fused` is rig_fuse()'s dict -> tab [1, cap_f, S, 4] float64 (device),
+    in the rig frame: per object its centre cluster, then per type its clusters in cluster order.  One launch, no host sync."""
+    f, n_fused, obj = fused["fused"], fused["n_fused"], fused["object"]
+    for name, t in (("fused", f), ("n_fused", n_fused), ("object", obj)):
+        require_cuda(t, name)
+    tc, s = _pose_type_count(type_count, "type_count")
+    if f.dtype != torch.float64 or f.dim() != 3 or f.shape[2] != 4 or len(tc) != f.shape[0] - 1:
+        raise OkpError(f"fused must be float64 [K,cap_f,4] with K - 1 = {len(tc)} key-point types (rig_fuse)")
+    k, cap_f = int(f.shape[0]), int(f.shape[1])
+    if n_fused.dtype != torch.int32 or tuple(n_fused.shape) != (k,) or obj.dtype != torch.int32 or tuple(obj.shape) != (k, cap_f):
+        raise OkpError("n_fused must be int32 [K] and object int32 [K,cap_f] (rig_fuse)")
+    tab = torch.empty((1, cap_f, s, 4), dtype=torch.float64, device=f.device)
+    _dispatch(_ops().rig_object_points, f.contiguous(), n_fused.contiguous(), obj.contiguous(), tc, tab, stream_int())
+    return tab
+
+
+def object_pose(tab, n_obj, model, type_count, max_rmse=None):
+    """The pose of every object of a point table (okp_object_pose; hypotheses, cost, pose and outputs are specified in include/okp.h).
+        tab [B,max_obj,S,4] float64 (device): object_points / rig_object_points; n_obj: int32 [B] (0-d for B = 1), objects per frame
+        model [S,3] float64 (device): object_model(...) moved to the device; type_count: the K-1 counts; max_rmse: metres, None = no bound
+    -> {"pose" [B,max_obj,12] float64 (row-major [R | t]: X = R m + t takes model coordinates to the table's frame), "fit" [B,max_obj,2]
+        float64 (rmse of the winning assignment and of the runner-up, the measure of symmetry ambiguity; NaN without a second hypothesis),
+        "assignment" [B,max_obj,S] int32 (model row of each slot, -1 = empty), "used" [B,max_obj] int32 (point pairs), "status" [B,max_obj]
+        int32 (0, POSE_FEW, POSE_DEGENERATE - both with a NaN pose - or POSE_POOR)}.  One launch, no host sync."""
+    require_cuda(tab, "tab")
+    require_cuda(n_obj, "n_obj")
+    require_cuda(model, "model")
+    tc, s = _pose_type_count(type_count, "type_count")
+    if tab.dtype != torch.float64 or tab.dim() != 4 or tab.shape[3] != 4 or tab.shape[2] != s:
+        raise OkpError(f"tab must be float64 [B,max_obj,{s},4]: S = 1 + sum(type_count) slots per object")
+    b, max_obj = int(tab.shape[0]), int(tab.shape[1])
+    if n_obj.dtype != torch.int32 or n_obj.numel() != b or n_obj.device != tab.device:
+        raise OkpError(f"n_obj must be int32 [{b}] on the table's device: the objects of each frame")
+    if model.dtype != torch.float64 or tuple(model.shape) != (s, 3) or model.device != tab.device:
+        raise OkpError(f"model must be float64 [{s},3] on the table's device (object_model)")
+    max_rmse = check_max_rmse(max_rmse)
+    dev = tab.device
+    pose = torch.empty((b, max_obj, 12), dtype=torch.float64, device=dev)
+    fit = torch.empty((b, max_obj, 2), dtype=torch.float64, device=dev)
+    assignment = torch.empty((b, max_obj, s), dtype=torch.int32, device=dev)
+    words = torch.empty((2, b, max_obj), dtype=torch.int32, device=dev)      # used, status
+    _dispatch(_ops().object_pose, tab.contiguous(), n_obj.reshape(b).contiguous(), model.contiguous(), tc, max_rmse, pose, fit, assignment, words[0], words[1], stream_int())
+    return {"pose": pose, "fit": fit, "assignment": assignment, "used": words[0], "status": words[1]}
+
+
 # ---- scoring labelled scenes (csrc/okp_targets.hip) ---------------------------------------------------------------------------------
 TARGET_SIZE = 64             # SceneDataset.prediction_size
 TARGET_MAX_MAPS = 16         # K

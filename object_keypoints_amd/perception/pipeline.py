@@ -566,6 +566,23 @@ def _live_plans(net):
     return found
 
 
+def _host_poses(pose, n):
+    """Frame n of an ops.object_pose dict on the host, in ONE device -> host copy: (pose [max_obj,12], fit [max_obj,2], status [max_obj])."""
+    max_obj = pose["status"].shape[1]
+    flat = torch.cat([pose["pose"][n].reshape(-1), pose["fit"][n].reshape(-1), pose["status"][n].to(torch.float64)]).cpu().numpy()
+    return flat[:12 * max_obj].reshape(max_obj, 12), flat[12 * max_obj:14 * max_obj].reshape(max_obj, 2), flat[14 * max_obj:].astype(np.int64)
+
+
+def _pose_entries(poses, o, key):
+    """Object o's pose as the entries objects() / rig_objects() add: the 4 x 4 transform under `key` (None where the status refuses a pose)."""
+    pose, fit, status = poses
+    T = None
+    if not int(status[o]) & (ops.POSE_FEW | ops.POSE_DEGENERATE):
+        T = np.eye(4)
+        T[:3] = pose[o].reshape(3, 4)
+    return {key: T, 'rmse': float(fit[o, 0]), 'ambiguity': float(fit[o, 1]), 'pose_status': int(status[o])}
+
+
 class CapturedStep:
     """A captured hipGraph of BatchedKeypointPipeline.forward_device plus everything its kernel nodes point at.
 
@@ -622,10 +639,18 @@ class BatchedKeypointPipeline:
     `points` is the fixed-capacity payload that is all-gathered across ranks (object_keypoints_amd.distributed).
     objects(...) groups one frame's peaks exactly as ObjectKeypointPipeline does, reusing the lifted points (surplus votes of a
     multi-instance type reduced by the device k-means of okp_group_objects).
+
+    Pose (optional): points_3d = the object model, [sum(keypoint_config), 3] key points in model coordinates in type order (the argument
+    ObjectKeypointPipeline takes and ignores); it is validated at construction (ops.object_model) and uploaded once per device.  The
+    device step then ends with okp_object_points and okp_object_pose, inside a captured step too, and its dict gains "pose": {"tab"
+    [N,max_objects,S,4], "pose" [N,max_objects,12], "fit", "assignment", "used", "status"} (ops.object_pose); objects() adds to every object
+    'T_CO' (4 x 4 float64, model -> camera coordinates; None where the status is ops.POSE_FEW or ops.POSE_DEGENERATE), 'rmse', 'ambiguity' (the
+    runner-up assignment's rmse: close to 'rmse' = the data cannot tell the two apart) and 'pose_status'.  max_rmse (metres, optional):
+    objects that fit worse carry ops.POSE_POOR.  Without points_3d no launch, key or value differs.
     """
 
     def __init__(self, net, keypoint_config, camera, prediction_size=(64, 64), capacity=DEFAULT_PEAK_CAPACITY,
-                 max_objects=16, max_per_type=4):
+                 max_objects=16, max_per_type=4, points_3d=None, max_rmse=None):
         self.net = net
         self.max_objects = max_objects
         self.max_per_type = max_per_type
@@ -636,6 +661,22 @@ class BatchedKeypointPipeline:
         self.camera = camera
         self.cam = camera.okp()
         self.max_index = camera.image_size.astype(int) - 1
+        self._model_host = None                                         # pose off
+        if points_3d is None and max_rmse is not None:
+            raise OkpError("max_rmse without points_3d: the pose needs the object model")
+        if points_3d is not None:
+            cfg = keypoint_config['keypoint_config']
+            self._model_host = ops.object_model(points_3d, cfg)
+            self._models = {}                                           # device -> the uploaded model
+            self.max_rmse = ops.check_max_rmse(max_rmse)
+            if max(cfg) > max_per_type:
+                raise OkpError(f"a keypoint type has {max(cfg)} instances, above max_per_type = {max_per_type}")
+
+    def _model(self, device):
+        m = self._models.get(device)
+        if m is None:
+            m = self._models[device] = self._model_host.to(device)
+        return m
 
     def forward_device(self, frames):
         """Split-product configurations: the network's fp16-range flag is not read here (no host sync in the batch loop) but folded into
@@ -652,7 +693,10 @@ class BatchedKeypointPipeline:
         (step, static_input, static_outputs): replay with step.replay(new_frames) or static_input.copy_(...); step.replay()."""
         static_in = frames.clone()
         graph, static_out = _capture(lambda: self.forward_device(static_in))
-        return CapturedStep(self.net, graph, static_in, static_out)
+        step = CapturedStep(self.net, graph, static_in, static_out)
+        if self._model_host is not None:                       # the graph reads the model on every replay: the step keeps the very tensor the
+            step._model = self._model(static_out["pose"]["tab"].device)     # captured launch took, looked up by the device that launch ran on
+        return step
 
     def postprocess_device(self, heat, depth, centers, range_flag=None):
         """Peaks, per-peak 3D points and the object grouping from (post-sigmoid) heat, depth and centre maps, all on
@@ -666,6 +710,10 @@ class BatchedKeypointPipeline:
         # device-side flag (no sync here): a map with more peaks than `capacity`, or more centre peaks than `max_objects`,
         # means `points` / the grouping are truncated - callers check it (objects() raises, bench.py asserts).
         out["overflow"] = ops.capacity_overflow(count, self.capacity, self.max_objects, range_flag=range_flag)
+        if self._model_host is not None:
+            cfg = self.config['keypoint_config']
+            tab = ops.object_points(self.cam, out, cfg, int(self.max_index[0]), int(self.max_index[1]))
+            out["pose"] = dict(ops.object_pose(tab, out["n_obj"], self._model(tab.device), cfg, self.max_rmse), tab=tab)
         return out
 
     def objects(self, out, n):
@@ -705,6 +753,7 @@ class BatchedKeypointPipeline:
             for o, i in surplus:
                 lifted[(o, i)] = world[at:at + cfg[i]]
                 at += cfg[i]
+        poses = _host_poses(out["pose"], n) if "pose" in out else None
         objects = []
         for o in range(n_obj):
             keypoints = [xyc[0, o, :2].copy()[None]]
@@ -723,6 +772,8 @@ class BatchedKeypointPipeline:
                     world.append(None)
             p_centers = [pred[k, j] for k in range(1, count.shape[0]) for j in range(int(count[k])) if assign[k, j] == o]
             objects.append({'p_centers': p_centers, 'keypoints': keypoints, 'p_C': world})
+            if poses is not None:
+                objects[-1].update(_pose_entries(poses, o, 'T_CO'))
         return objects
 
     def objects_reference(self, out, n):
@@ -880,10 +931,15 @@ class StereoStreamPipeline:
     the graph -, tick_sharded - after the gather, on every rank) then end with okp_rig_fuse and carry the key "fused" (ops.rig_fuse's dict:
     one list of clusters per type in the rig frame, grouped into objects), and their "overflow" word carries ops.FUSE_OVERFLOW;
     rig_objects(out) reads it.  fuse_capacity: fused clusters kept per type (default: the kernel's limit, ops.RIG_MAX_FUSED).  Poses and
-    radii are validated at construction (ops.rig_poses).  tick(), the host tick, is unchanged and does not fuse."""
+    radii are validated at construction (ops.rig_poses).  tick(), the host tick, is unchanged and does not fuse.
+
+    Pose (optional, needs the fusion): points_3d = the object model as for BatchedKeypointPipeline, max_rmse optional.  The fused device
+    ticks then end with okp_rig_object_points and okp_object_pose - the pose of every fused object in the RIG frame, inside the captured
+    graph, after the gather on every rank - under the key "pose" (ops.object_pose's dict plus "tab"), and rig_objects(out) adds 'T_BO'
+    (4 x 4, model -> rig coordinates, or None), 'rmse', 'ambiguity' and 'pose_status' to every object."""
 
     def __init__(self, net, stereo_camera, keypoint_config, capacity=16, max_distance=3.0, rig_poses=None, merge_radius=None, object_radius=None,
-                 fuse_capacity=None):
+                 fuse_capacity=None, points_3d=None, max_rmse=None):
         self.net = net
         self.rig = None if hasattr(stereo_camera, "left_camera") else list(stereo_camera)       # one StereoCamera, or a sequence of them
         self.stereo_cameras = self.rig if self.rig is not None else [stereo_camera]
@@ -918,6 +974,15 @@ class StereoStreamPipeline:
             if len(self.config) > ops.RIG_MAX_TYPES or self.n_fused_pairs * self.capacity > ops.RIG_MAX_ROWS:
                 raise OkpError(f"fusion holds at most {ops.RIG_MAX_TYPES} key-point types and {ops.RIG_MAX_ROWS} rows (pairs x capacity) per type: "
                                f"{len(self.config)} types, {self.n_fused_pairs} x {self.capacity} rows asked for")
+        self._model_host = None                                         # pose off
+        if points_3d is None and max_rmse is not None:
+            raise OkpError("max_rmse without points_3d: the pose needs the object model")
+        if points_3d is not None:
+            if not given:
+                raise OkpError("points_3d without rig_poses, merge_radius and object_radius: the pose is fitted to the fused objects of the rig")
+            self._model_host = ops.object_model(points_3d, self.config[1:])
+            self._models = {}                                           # device -> the uploaded model
+            self.max_rmse = ops.check_max_rmse(max_rmse)
 
     def _check_fused_tick(self, n_pairs, first_pair=0):
         """A fused tick holds every pair of the rig: the clusters are formed across all of them."""
@@ -931,6 +996,17 @@ class StereoStreamPipeline:
         if poses is None:
             poses = self._poses[dev] = self._poses_host.to(dev)
         return ops.rig_fuse(points, poses, self.config[1:], self.merge_radius, self.object_radius, self.fuse_capacity, overflow=overflow)
+
+    def _pose(self, fused):
+        """The pose of every fused object, in the rig frame: two launches behind okp_rig_fuse."""
+        tab = ops.rig_object_points(fused, self.config[1:])
+        return dict(ops.object_pose(tab, fused["n_obj"], self._model(tab.device), self.config[1:], self.max_rmse), tab=tab)
+
+    def _model(self, device):
+        m = self._models.get(device)
+        if m is None:
+            m = self._models[device] = self._model_host.to(device)
+        return m
 
     def _check_rig_frames(self, frames, first_pair=0):
         """A rig's tick holds 2 frames for each of its pairs first_pair .. first_pair + P - 1 (a single calibration: any P)."""
@@ -1070,6 +1146,8 @@ class StereoStreamPipeline:
             if fuse:
                 out["fused"] = self._fuse(points, overflow)
                 out["overflow"] = out["fused"]["overflow"]
+                if self._model_host is not None:
+                    out["pose"] = self._pose(out["fused"])
         return out
 
     def capture_device(self, frames, heat_override=None, first_pair=0):
@@ -1086,6 +1164,8 @@ class StereoStreamPipeline:
         step = CapturedTick(self.net, graph, static_in, static_out, static_heat)
         step._table = self._table(frames.device)               # (the graph reads it on every replay)
         step._poses = self._poses.get(frames.device) if self._poses_host is not None else None       # (and the pose table)
+        if self._model_host is not None and "pose" in static_out:       # (and the object model: the tensor the captured launch took)
+            step._model = self._model(static_out["pose"]["tab"].device)
         return step
 
     def results(self, out):
@@ -1131,6 +1211,8 @@ class StereoStreamPipeline:
             whole = {"points": out["points"], "overflow": out["overflow"], "local": out}
             if "fused" in out:
                 whole["fused"] = out["fused"]
+            if "pose" in out:
+                whole["pose"] = out["pose"]
             return whole
         start, n_local = distributed.shard(int(n_pairs_total), dist.get_rank(), dist.get_world_size())
         if frames_local.shape[0] != 2 * n_local:
@@ -1149,6 +1231,8 @@ class StereoStreamPipeline:
         if self._poses_host is not None:
             with torch.no_grad():
                 out["fused"] = self._fuse(gathered, flag)
+                if self._model_host is not None:
+                    out["pose"] = self._pose(out["fused"])
             out["overflow"] = out["fused"]["overflow"]
         return out
 
@@ -1158,6 +1242,8 @@ class StereoStreamPipeline:
             {"p_B": [(1, 3) centre, (n_1, 3), ..., (n_{K-1}, 3)] float64 points in rig coordinates - the nesting of
                     ObjectKeypointPipeline's 'p_C', one array per key-point type, n_k <= the type's count, in cluster order,
              "confidence": [(1,), (n_1,), ...] float64, "views": [(1,), (n_1,), ...] int32 bit masks of the contributing pairs}
+        plus, for a pipeline built with points_3d, 'T_BO' (4 x 4 float64: model -> rig coordinates; None where the status is ops.POSE_FEW or
+        ops.POSE_DEGENERATE), 'rmse', 'ambiguity' (the runner-up assignment's rmse) and 'pose_status' -
         read in ONE device -> host copy.  Raises OkpError when the tick's overflow word is set, as results() does (bit ops.FUSE_OVERFLOW:
         a type had more than fuse_capacity clusters).  tick(), the host tick, does not fuse: its return value is not accepted here."""
         if not isinstance(out, dict) or "fused" not in out:
@@ -1166,14 +1252,22 @@ class StereoStreamPipeline:
         f = out["fused"]
         K, cap_f = f["views"].shape
         parts = [out["overflow"].reshape(1), f["n_obj"].reshape(1), f["n_fused"], f["views"].reshape(-1), f["object"].reshape(-1)]
-        flat = torch.cat([t.to(torch.float64) for t in parts] + [f["fused"].reshape(-1)]).cpu().numpy()          # the one D2H copy (int32 is exact in fp64)
+        tail = [f["fused"].reshape(-1)]
+        if "pose" in out:
+            ps = out["pose"]
+            tail += [ps["pose"].reshape(-1), ps["fit"].reshape(-1), ps["status"].reshape(-1).to(torch.float64)]
+        flat = torch.cat([t.to(torch.float64) for t in parts] + tail).cpu().numpy()          # the one D2H copy (int32 is exact in fp64)
         _raise_on_overflow(int(flat[0]), fused=True)
         n_obj = int(flat[1])
         n_fused = flat[2:2 + K].astype(np.int64)
         at = 2 + K
         views = flat[at:at + K * cap_f].astype(np.int32).reshape(K, cap_f)
         obj = flat[at + K * cap_f:at + 2 * K * cap_f].astype(np.int64).reshape(K, cap_f)
-        rows = flat[at + 2 * K * cap_f:].reshape(K, cap_f, 4)
+        rows = flat[at + 2 * K * cap_f:at + 2 * K * cap_f + K * cap_f * 4].reshape(K, cap_f, 4)
+        poses = None
+        if "pose" in out:
+            rest = flat[at + 2 * K * cap_f + K * cap_f * 4:]
+            poses = (rest[:12 * cap_f].reshape(cap_f, 12), rest[12 * cap_f:14 * cap_f].reshape(cap_f, 2), rest[14 * cap_f:].astype(np.int64))
         objects = []
         for o in range(n_obj):
             p_B, conf, seen = [], [], []
@@ -1183,4 +1277,6 @@ class StereoStreamPipeline:
                 conf.append(np.ascontiguousarray(rows[k, sel, 3]))
                 seen.append(views[k, sel])
             objects.append({"p_B": p_B, "confidence": conf, "views": seen})
+            if poses is not None:
+                objects[-1].update(_pose_entries(poses, o, "T_BO"))
         return objects
