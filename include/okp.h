@@ -39,7 +39,8 @@ extern "C" {
                                     OKP_YUV_I420 / OKP_YUV_NV12 / OKP_YUV_BT601 / OKP_YUV_BT709, okp_preprocess_yuv420;
                                     okp_project_labels, okp_render_targets, okp_keypoint_loss (scoring labelled scenes);
                                     okp_rig_fuse (a rig's stereo pairs fused into one object list in the rig frame);
-                                    okp_object_points, okp_rig_object_points, okp_object_pose (each object's 6-DoF pose from its 3D key points) */
+                                    okp_object_points, okp_rig_object_points, okp_object_pose (each object's 6-DoF pose from its 3D key points);
+                                    okp_track_objects, OKP_TRACK_* (objects tracked across ticks: stable ids, filtered poses) */
 
 /* OKP_F16: IEEE half activations / weights, fp32 accumulate (BASELINE configs[4]).
  * OKP_F32X3 (okp_conv plans only): fp32 activations, weights and results like OKP_F32 - every tensor argument of such a plan is an
@@ -630,6 +631,64 @@ int okp_rig_object_points(const double* fused_dev, const int32_t* n_fused_dev, c
 int okp_object_pose(const double* tab_dev, const int32_t* n_obj_dev, int32_t B, int32_t max_obj, const double* model_dev,
                     const int32_t* type_count /* HOST [K-1] */, int32_t K, double max_rmse, double* pose_dev, double* fit_dev,
                     int32_t* assignment_dev, int32_t* used_dev, int32_t* status_dev, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * Tracking across ticks (csrc/okp_track.hip): the poses of one tick's objects -> tracks with stable ids and filtered poses.  Object o of tick
+ * t and object o of tick t + 1 are unrelated - the index is the order the centre peaks or fused clusters came out in -, a missed detection
+ * makes the object vanish and the pose jitters with the depth map.  The reference names the step (LearnedKeypointTrackingPipeline,
+ * perception/pipeline.py) and never takes it.  There is no reference implementation: the specification is this comment
+ * (tests/track_spec.py restates it in NumPy).
+ *
+ * okp_track_objects: one launch, one wave per stream b, fp64, no atomics, no host wait, capturable; the same bits on every run.
+ * Inputs, all in device memory and all outputs of the pose stage:
+ *   tab [B][max_obj][S][4] fp64, pose [B][max_obj][12] fp64, status [B][max_obj] int32, n_obj [B] int32,
+ *   model [S][3] fp64 - only row 0 is used, the centre point m0 -, overflow_in 0-d int32 (may be NULL; may be the address of `overflow`).
+ * Host scalars: B, max_obj, S, T (track capacity), gate (metres), dt (seconds, a fixed tick period), alpha, beta, alpha_R, min_hits, max_misses.
+ * State, in device memory, updated in place; all zeros is a valid empty tracker:
+ *   track_f [B][T][16] fp64     centre c (3), velocity v (3), rotation R (9, row-major), one spare kept 0
+ *   track_i [B][T][4] int32     id (0 = free slot), hits, misses, age
+ *   next_id [B] int32
+ * Outputs, all written by every call:
+ *   track_pose [B][T][12] fp64  [R | c - R m0] for live slots, NaN for free ones
+ *   track_of [B][max_obj] int32 the slot the measurement went to, or -1
+ *   meas_of [B][T] int32        the object that updated or founded the track in this call, or -1
+ *   n_tracks [B] int32          live slots after the call
+ *   overflow 0-d int32
+ * Per stream, in this order:
+ *   0. Measurements.  For object o < min(n_obj[b], max_obj): FULL if status == 0 and all 12 pose values are finite; then z = t + R m0 and
+ *      R_meas = R.  POSITION-ONLY if not full and the four values of tab[b][o][0] are finite; then z = that row's xyz.  Otherwise no
+ *      measurement.  Objects from n_obj[b] on are never read as measurements, whatever their rows hold.
+ *   1. Predict every live track: p = c + dt*v.  Multiply, then add, no contraction.
+ *   2. Candidates.  The pairs (live track i, measurement o) with d2 = (dx*dx + dy*dy) + dz*dz <= gate*gate, where (dx, dy, dz) = z - p,
+ *      no contraction; gate*gate is formed once on the host in fp64.
+ *   3. Greedy association.  Repeatedly take the candidate of least d2 whose track and measurement are both unassigned.  On equal d2 take
+ *      the lower track slot, then the lower object index.  Stop when none is left.
+ *   4. Matched track.  r = z - p; c = p + alpha*r; v = v + (beta/dt)*r (beta/dt is formed once on the host).  hits and age +1, misses = 0.
+ *      Full, alpha_R == 1: R = R_meas, copied bit for bit.  Full, otherwise: Q = R^T R_meas; w = (Q32-Q23, Q13-Q31, Q21-Q12), s = |w|;
+ *      theta = atan2(s/2, (trace Q - 1)/2).  If s <= 1e-9 - the rotations agree, or differ by a half turn whose axis the data do not
+ *      give -: R = R_meas.  Else u = w/s, phi = alpha_R*theta, R = R (I + sin(phi)[u]x + (1 - cos(phi))[u]x^2).
+ *      Position-only: R keeps its bits.
+ *   5. Unmatched live track.  c = p, v kept, misses and age +1.  When misses > max_misses the slot is freed: both rows zeroed.
+ *   6. Births.  The unmatched full measurements, in ascending o, each take the lowest free slot; slots freed in step 5 count.
+ *      id = ++next_id[b], c = z, v = 0, R = R_meas, hits = age = 1, misses = 0.  With no free slot the measurement is dropped:
+ *      track_of = -1, and bit OKP_TRACK_OVERFLOW is raised (bits 1, 2 and 4 are taken: capacity, fp16 range, OKP_RIG_FUSE_OVERFLOW).
+ *      An unmatched position-only measurement founds nothing.
+ *   7. overflow = (*overflow_in or 0) | bit.  hits, misses and age saturate at INT32_MAX.
+ * A track is CONFIRMED when hits >= min_hits; that is computed by the reader and is not state.
+ * Limits.  R is not re-orthonormalised: with alpha_R < 1 the drift of the repeated products is a few ulp per tick.  next_id is a plain
+ * int32 count of births (2^31 of them wrap).  One tick period for every call; tracks are not exchanged between streams or ranks.
+ * Refused on the host before any launch (OKP_EINVAL, the message names the argument): T outside [1, OKP_TRACK_MAX_TRACKS], max_obj
+ * outside [1, OKP_TRACK_MAX_OBJECTS] (one lane per track and per measurement), B < 1, S outside [1, OKP_POSE_MAX_POINTS], gate or dt not
+ * positive and finite, alpha or alpha_R outside (0, 1], beta negative or not finite, min_hits < 1, max_misses < 0, a null required pointer.
+ * ---------------------------------------------------------------------------------- */
+#define OKP_TRACK_MAX_TRACKS 64
+#define OKP_TRACK_MAX_OBJECTS 64
+#define OKP_TRACK_OVERFLOW 8
+int okp_track_objects(const double* tab_dev, const double* pose_dev, const int32_t* status_dev, const int32_t* n_obj_dev, const double* model_dev,
+                      int32_t B, int32_t max_obj, int32_t S, int32_t T, double gate, double dt, double alpha, double beta, double alpha_R,
+                      int32_t min_hits, int32_t max_misses, const int32_t* overflow_in_dev, double* track_f_dev, int32_t* track_i_dev,
+                      int32_t* next_id_dev, double* track_pose_dev, int32_t* track_of_dev, int32_t* meas_of_dev, int32_t* n_tracks_dev,
+                      int32_t* overflow_dev, void* stream);
 
 /* Undistort only (FisheyeCamera.undistort, camera_utils.py:75-81 / RadTanPinholeCamera.undistort, :57-62, by cam->model):
  * xy [m][2] fp32 -> out [m][2] fp64.  okp_fisheye_undistort is the same entry point under its round-1 name. */

@@ -338,6 +338,16 @@ def object_pose(tab, n_obj, model, type_count, max_rmse, pose, fit, assignment, 
                                           pose.data_ptr(), fit.data_ptr(), assignment.data_ptr(), used.data_ptr(), status.data_ptr(), stream), "okp_object_pose")
 
 
+# ---- tracking across ticks (csrc/okp_track.hip): tab [B,max_obj,S,4], track_f [B,T,16] ----------------------------------------------------------
+def track_objects(tab, pose, status, n_obj, model, gate, dt, alpha, beta, alpha_R, min_hits, max_misses, track_f, track_i, next_id, track_pose, track_of,
+                  meas_of, n_tracks, overflow, stream, overflow_in=None):
+    b, max_obj, s, _ = tab.shape
+    _lib.check(_lib.lib().okp_track_objects(tab.data_ptr(), pose.data_ptr(), status.data_ptr(), n_obj.data_ptr(), model.data_ptr(), b, max_obj, s, track_f.shape[1],
+                                            gate, dt, alpha, beta, alpha_R, min_hits, max_misses, _ptr(overflow_in), track_f.data_ptr(), track_i.data_ptr(),
+                                            next_id.data_ptr(), track_pose.data_ptr(), track_of.data_ptr(), meas_of.data_ptr(), n_tracks.data_ptr(),
+                                            overflow.data_ptr(), stream), "okp_track_objects")
+
+
 # ---- scoring labelled scenes -----------------------------------------------------------------------------------------------------------------
 def project_labels(camera, world_points, T_WC, scale, crop_x, crop_y, labels, stream):
     _lib.check(_lib.lib().okp_project_labels(_camera(camera), world_points.data_ptr(), world_points.shape[0], T_WC.data_ptr(), T_WC.shape[0], scale, crop_x, crop_y,

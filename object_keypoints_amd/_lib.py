@@ -116,6 +116,8 @@ SIGNATURES = [
     ("okp_rig_object_points", c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, POINTER(c_int32), c_void_p, c_void_p]),
     ("okp_object_pose", c_int, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, POINTER(c_int32), c_int32, c_double, c_void_p, c_void_p, c_void_p, c_void_p,
                                 c_void_p, c_void_p]),
+    ("okp_track_objects", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_double, c_double, c_double, c_double,
+                                  c_double, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     ("okp_fisheye_undistort", c_int, [POINTER(okp_camera), c_void_p, c_int32, c_void_p, c_void_p]),
     ("okp_camera_undistort", c_int, [POINTER(okp_camera), c_void_p, c_int32, c_void_p, c_void_p]),
     ("okp_project_labels", c_int, [POINTER(okp_camera), c_void_p, c_int32, c_void_p, c_int32, c_double, c_double, c_double, c_void_p, c_void_p]),

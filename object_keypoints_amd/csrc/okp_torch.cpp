@@ -626,6 +626,32 @@ void object_pose(const Tensor& tab, const Tensor& n_obj, const Tensor& model, at
                            sp(stream)), "okp_object_pose");
 }
 
+// Tracking across ticks (csrc/okp_track.hip): the pose stage's tab / pose / status / n_obj and the model -> the tracker's state (track_f [B,T,16],
+// track_i [B,T,4], next_id [B]) stepped in place, and track_pose [B,T,12], track_of [B,max_obj], meas_of [B,T], n_tracks [B], overflow
+void track_objects(const Tensor& tab, const Tensor& pose, const Tensor& status, const Tensor& n_obj, const Tensor& model, double gate, double dt, double alpha,
+                   double beta, double alpha_R, int64_t min_hits, int64_t max_misses, const Tensor& track_f, const Tensor& track_i, const Tensor& next_id,
+                   const Tensor& track_pose, const Tensor& track_of, const Tensor& meas_of, const Tensor& n_tracks, const Tensor& overflow, int64_t stream,
+                   const optional<Tensor>& overflow_in) {
+  check_dev(tab, at::kDouble, "tab"); check_dev(pose, at::kDouble, "pose"); check_dev(status, at::kInt, "status"); check_dev(n_obj, at::kInt, "n_obj");
+  check_dev(model, at::kDouble, "model"); check_dev(track_f, at::kDouble, "track_f"); check_dev(track_i, at::kInt, "track_i"); check_dev(next_id, at::kInt, "next_id");
+  check_dev(track_pose, at::kDouble, "track_pose"); check_dev(track_of, at::kInt, "track_of"); check_dev(meas_of, at::kInt, "meas_of");
+  check_dev(n_tracks, at::kInt, "n_tracks"); check_dev(overflow, at::kInt, "overflow");
+  if (overflow_in.has_value()) check_dev(*overflow_in, at::kInt, "overflow_in");
+  TORCH_CHECK(tab.dim() == 4 && tab.size(3) == 4, "okp: tab is [B,max_obj,S,4] float64");
+  TORCH_CHECK(track_f.dim() == 3 && track_f.size(2) == 16, "okp: track_f is [B,T,16] float64 (ops.track_state)");
+  const int64_t B = tab.size(0), max_obj = tab.size(1), S = tab.size(2), T = track_f.size(1);
+  TORCH_CHECK(track_f.size(0) == B && pose.numel() == B * max_obj * 12 && status.numel() == B * max_obj && n_obj.numel() == B && model.numel() == S * 3,
+              "okp: track_objects inputs are pose [B,max_obj,12], status [B,max_obj], n_obj [B], model [S,3] and track_f [B,T,16]");
+  TORCH_CHECK(track_i.numel() == B * T * 4 && next_id.numel() == B && track_pose.numel() == B * T * 12 && track_of.numel() == B * max_obj && meas_of.numel() == B * T &&
+              n_tracks.numel() == B && overflow.numel() == 1 && (!overflow_in.has_value() || overflow_in->numel() == 1),
+              "okp: track_objects buffers are track_i [B,T,4], next_id [B], track_pose [B,T,12], track_of [B,max_obj], meas_of [B,T], n_tracks [B], overflow one int32");
+  check_rc(okp_track_objects(tab.data_ptr<double>(), pose.data_ptr<double>(), status.data_ptr<int32_t>(), n_obj.data_ptr<int32_t>(), model.data_ptr<double>(),
+                             (int32_t)B, (int32_t)max_obj, (int32_t)S, (int32_t)T, gate, dt, alpha, beta, alpha_R, (int32_t)min_hits, (int32_t)max_misses,
+                             overflow_in.has_value() ? overflow_in->data_ptr<int32_t>() : nullptr, track_f.data_ptr<double>(), track_i.data_ptr<int32_t>(),
+                             next_id.data_ptr<int32_t>(), track_pose.data_ptr<double>(), track_of.data_ptr<int32_t>(), meas_of.data_ptr<int32_t>(),
+                             n_tracks.data_ptr<int32_t>(), overflow.data_ptr<int32_t>(), sp(stream)), "okp_track_objects");
+}
+
 void lift_peaks(at::ArrayRef<double> camera, const Tensor& count, const Tensor& xyc, const Tensor& depth, int64_t max_x, int64_t max_y, const Tensor& out, int64_t stream) {
   TORCH_CHECK(xyc.is_cuda() && xyc.dim() == 4 && xyc.scalar_type() == at::kFloat && depth.is_cuda() && depth.scalar_type() == at::kFloat && depth.dim() == 4 && depth.is_contiguous() &&
               depth.size(0) == xyc.size(0) && depth.size(1) == xyc.size(1) && count.scalar_type() == at::kInt && out.scalar_type() == at::kDouble &&
@@ -786,6 +812,9 @@ TORCH_LIBRARY(okp, m) {
   m.def("rig_object_points(Tensor fused, Tensor n_fused, Tensor object, int[] type_count, Tensor(a!) tab, int stream) -> ()", rig_object_points);
   m.def("object_pose(Tensor tab, Tensor n_obj, Tensor model, int[] type_count, float max_rmse, Tensor(a!) pose, Tensor(b!) fit, Tensor(c!) assignment, "
         "Tensor(d!) used, Tensor(e!) status, int stream) -> ()", object_pose);
+  m.def("track_objects(Tensor tab, Tensor pose, Tensor status, Tensor n_obj, Tensor model, float gate, float dt, float alpha, float beta, float alpha_R, "
+        "int min_hits, int max_misses, Tensor(a!) track_f, Tensor(b!) track_i, Tensor(c!) next_id, Tensor(d!) track_pose, Tensor(e!) track_of, "
+        "Tensor(f!) meas_of, Tensor(g!) n_tracks, Tensor(h!) overflow, int stream, Tensor? overflow_in=None) -> ()", track_objects);
   m.def("rig_fuse(Tensor points, Tensor poses, int[] type_count, float merge_radius, float object_radius, Tensor(a!) fused, Tensor(b!) n_fused, Tensor(c!) views, "
         "Tensor(d!) object, Tensor(e!) member, Tensor(f!) n_obj, Tensor(g!) overflow, int stream, Tensor? overflow_in=None) -> ()", rig_fuse);
   m.def("project_labels(float[] camera, Tensor world_points, Tensor T_WC, float scale, float crop_x, float crop_y, Tensor(a!) labels, int stream) -> ()", project_labels);

@@ -1206,6 +1206,114 @@ def object_pose(tab, n_obj, model, type_count, max_rmse=None):
     return {"pose": pose, "fit": fit, "assignment": assignment, "used": words[0], "status": words[1]}
 
 
+# ---- objects tracked across ticks (okp_track_objects, csrc/okp_track.hip; no reference counterpart: the specification is include/okp.h) ------
+TRACK_OVERFLOW = 8           # bit of track_objects()'s overflow word: an unmatched full measurement found no free track slot
+TRACK_MAX_TRACKS, TRACK_MAX_OBJECTS = 64, 64                                     # include/okp.h OKP_TRACK_*
+
+
+class TrackConfig:
+    """The tracker's parameters (okp_track_objects), validated here - an OkpError names the field:
+        gate      metres: a measurement farther than this from a track's predicted centre is no candidate for it
+        dt        seconds: the fixed tick period
+        alpha, beta   the position and velocity gains of the alpha-beta filter (alpha in (0, 1], beta >= 0; 1 and 0: the track's centre is the
+                  measurement's, no velocity)
+        alpha_R   the fraction of the rotation between the track's and the measured orientation taken per tick, in (0, 1]
+        min_hits  a track is `confirmed` from this many updates on (computed by the reader); max_misses: ticks a track coasts unseen before
+                  its slot is freed; max_tracks: track slots per stream, at most TRACK_MAX_TRACKS."""
+
+    def __init__(self, gate, dt, alpha=1.0, beta=0.0, alpha_R=1.0, min_hits=2, max_misses=5, max_tracks=16):
+        def number(name, v):
+            try:
+                return float(v)
+            except (TypeError, ValueError):
+                raise OkpError(f"TrackConfig: {name} = {v!r} is not a number") from None
+
+        def integer(name, v, lo, hi=2 ** 31 - 1):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
+                raise OkpError(f"TrackConfig: {name} = {v!r}: an integer in [{lo}, {hi}]")
+            return int(v)
+
+        self.gate, self.dt = number("gate", gate), number("dt", dt)
+        for name, v in (("gate", self.gate), ("dt", self.dt)):
+            if not (v > 0.0 and np.isfinite(v)):
+                raise OkpError(f"TrackConfig: {name} = {v!r} must be positive and finite")
+        self.alpha, self.alpha_R = number("alpha", alpha), number("alpha_R", alpha_R)
+        for name, v in (("alpha", self.alpha), ("alpha_R", self.alpha_R)):
+            if not 0.0 < v <= 1.0:
+                raise OkpError(f"TrackConfig: {name} = {v!r} outside (0, 1]")
+        self.beta = number("beta", beta)
+        if not (self.beta >= 0.0 and np.isfinite(self.beta)):
+            raise OkpError(f"TrackConfig: beta = {beta!r} must be finite and not negative")
+        self.min_hits = integer("min_hits", min_hits, 1)
+        self.max_misses = integer("max_misses", max_misses, 0)
+        self.max_tracks = integer("max_tracks", max_tracks, 1, TRACK_MAX_TRACKS)
+
+    def __repr__(self):
+        return (f"TrackConfig(gate={self.gate}, dt={self.dt}, alpha={self.alpha}, beta={self.beta}, alpha_R={self.alpha_R}, min_hits={self.min_hits}, "
+                f"max_misses={self.max_misses}, max_tracks={self.max_tracks})")
+
+
+def track_state(B, max_tracks, device):
+    """An empty tracker of B streams: {"track_f" [B,T,16] float64 (centre, velocity, rotation, one spare), "track_i" [B,T,4] int32 (id - 0 = free
+    slot -, hits, misses, age), "next_id" [B] int32}, all zeros, on `device`.  track_objects() steps it in place."""
+    B, T = int(B), int(max_tracks)
+    if B < 1 or not 1 <= T <= TRACK_MAX_TRACKS:
+        raise OkpError(f"track_state: B = {B} streams (at least 1) of max_tracks = {T} slots (1 .. {TRACK_MAX_TRACKS})")
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise OkpError("track_state: the tracker's state lives in device memory: the HIP path has no CPU fallback")
+    return {"track_f": torch.zeros((B, T, 16), dtype=torch.float64, device=device), "track_i": torch.zeros((B, T, 4), dtype=torch.int32, device=device),
+            "next_id": torch.zeros((B,), dtype=torch.int32, device=device)}
+
+
+def track_objects(state, tab, pose, status, n_obj, model, cfg, overflow=None):
+    """One tick of the tracker (okp_track_objects; measurements, gate, greedy association, filter, births and deaths are specified in
+    include/okp.h).  state: track_state(...), stepped in place; tab [B,max_obj,S,4], pose [B,max_obj,12] float64, status [B,max_obj] int32,
+    n_obj int32 [B] (0-d for B = 1): the pose stage's outputs (object_points / rig_object_points, object_pose); model [S,3] float64 (device);
+    cfg: a TrackConfig; overflow: the tick's overflow word to fold into the result, or None
+    -> {"track_pose" [B,T,12] float64 (row-major [R | t] of every live slot, NaN for free ones), "track_of" [B,max_obj] int32 (the slot each
+        object went to, -1 = none), "meas_of" [B,T] int32 (the object that updated or founded each track in this call, -1 = none),
+        "n_tracks" [B] int32, "overflow" 0-d int32 = overflow | TRACK_OVERFLOW where a new object found no free slot}.  One launch, no host sync."""
+    if not isinstance(cfg, TrackConfig):
+        raise OkpError("cfg must be an ops.TrackConfig")
+    for name, t in (("tab", tab), ("pose", pose), ("status", status), ("n_obj", n_obj), ("model", model)):
+        require_cuda(t, name)
+    if tab.dtype != torch.float64 or tab.dim() != 4 or tab.shape[3] != 4:
+        raise OkpError("tab must be float64 [B,max_obj,S,4] (object_points / rig_object_points)")
+    b, max_obj, s = (int(v) for v in tab.shape[:3])
+    dev = tab.device
+    if not 1 <= max_obj <= TRACK_MAX_OBJECTS or not 1 <= s <= POSE_MAX_POINTS:
+        raise OkpError(f"tab [{b},{max_obj},{s},4]: at most {TRACK_MAX_OBJECTS} objects per stream and {POSE_MAX_POINTS} model points")
+    if pose.dtype != torch.float64 or tuple(pose.shape) != (b, max_obj, 12) or status.dtype != torch.int32 or tuple(status.shape) != (b, max_obj) or \
+            pose.device != dev or status.device != dev:
+        raise OkpError(f"pose must be float64 [{b},{max_obj},12] and status int32 [{b},{max_obj}] on the table's device (object_pose)")
+    if n_obj.dtype != torch.int32 or n_obj.numel() != b or n_obj.device != dev:
+        raise OkpError(f"n_obj must be int32 [{b}] on the table's device: the objects of each stream")
+    if model.dtype != torch.float64 or tuple(model.shape) != (s, 3) or model.device != dev:
+        raise OkpError(f"model must be float64 [{s},3] on the table's device (object_model)")
+    try:
+        tf, ti, nid = state["track_f"], state["track_i"], state["next_id"]
+    except (TypeError, KeyError):
+        raise OkpError("state must be the dict of ops.track_state") from None
+    t = cfg.max_tracks
+    for name, x, dtype, shape in (("track_f", tf, torch.float64, (b, t, 16)), ("track_i", ti, torch.int32, (b, t, 4)), ("next_id", nid, torch.int32, (b,))):
+        require_cuda(x, name)
+        if x.dtype != dtype or tuple(x.shape) != shape or x.device != dev or not x.is_contiguous():
+            raise OkpError(f"state[{name!r}] must be a contiguous {dtype} tensor {list(shape)} on the table's device: track_state({b}, cfg.max_tracks = {t}, device)")
+    if overflow is not None:
+        require_cuda(overflow, "overflow")
+        if overflow.dtype != torch.int32 or overflow.numel() != 1 or overflow.device != dev:
+            raise OkpError("overflow must be one int32 on the table's device (a tick's overflow word)")
+        overflow = overflow.reshape(1)
+    track_pose = torch.empty((b, t, 12), dtype=torch.float64, device=dev)
+    words = torch.empty((b * max_obj + b * t + b + 1,), dtype=torch.int32, device=dev)      # track_of, meas_of, n_tracks, overflow
+    track_of, meas_of = words[:b * max_obj].view(b, max_obj), words[b * max_obj:b * max_obj + b * t].view(b, t)
+    n_tracks, word = words[b * max_obj + b * t:-1], words[-1:]
+    _dispatch(_ops().track_objects, tab.contiguous(), pose.contiguous(), status.contiguous(), n_obj.reshape(b).contiguous(), model.contiguous(), cfg.gate, cfg.dt,
+              cfg.alpha, cfg.beta, cfg.alpha_R, cfg.min_hits, cfg.max_misses, tf, ti, nid, track_pose, track_of, meas_of, n_tracks, word, stream_int(), overflow)
+    return {"track_pose": track_pose, "track_of": track_of, "meas_of": meas_of, "n_tracks": n_tracks, "overflow": word[0]}
+
+
 # ---- scoring labelled scenes (csrc/okp_targets.hip) ---------------------------------------------------------------------------------
 TARGET_SIZE = 64             # SceneDataset.prediction_size
 TARGET_MAX_MAPS = 16         # K

@@ -583,6 +583,79 @@ def _pose_entries(poses, o, key):
     return {key: T, 'rmse': float(fit[o, 0]), 'ambiguity': float(fit[o, 1]), 'pose_status': int(status[o])}
 
 
+def _check_track(track, has_model, max_obj, what):
+    """The `track` argument of both device pipelines: None, or an ops.TrackConfig next to an object model."""
+    if track is None:
+        return None
+    if not isinstance(track, ops.TrackConfig):
+        raise OkpError("track must be an ops.TrackConfig")
+    if not has_model:
+        raise OkpError("track without points_3d: the tracker follows the poses of the object model")
+    if max_obj > ops.TRACK_MAX_OBJECTS:
+        raise OkpError(f"{what} = {max_obj}: the tracker takes at most {ops.TRACK_MAX_OBJECTS} objects per stream")
+    return track
+
+
+class _Tracker:
+    """The device state of a pipeline's tracker, one ops.track_state per (device, streams), created on first use and kept for the pipeline's
+    life: captured steps hold these very tensors, so reset() zeroes them in place."""
+
+    def __init__(self, cfg):
+        self.cfg, self.states = cfg, {}
+
+    def state(self, device, streams):
+        st = self.states.get((device, streams))
+        if st is None:
+            st = self.states[(device, streams)] = ops.track_state(streams, self.cfg.max_tracks, device)
+        return st
+
+    def step(self, pose, n_obj, model, overflow):
+        """ops.track_objects behind ops.object_pose's dict (with "tab") -> its outputs plus the state tensors."""
+        st = self.state(pose["tab"].device, int(pose["tab"].shape[0]))
+        return dict(ops.track_objects(st, pose["tab"], pose["pose"], pose["status"], n_obj, model, self.cfg, overflow=overflow), **st)
+
+    def reset(self):
+        for st in self.states.values():
+            for t in st.values():
+                t.zero_()
+
+
+def _host_tracks(track, n):
+    """Stream n of a tick's "track" dict on the host, in ONE device -> host copy: (track_pose [T,12], track_f [T,16], track_i [T,4],
+    track_of [max_obj], meas_of [T])."""
+    T, max_obj = track["meas_of"].shape[1], track["track_of"].shape[1]
+    flat = torch.cat([track["track_pose"][n].reshape(-1), track["track_f"][n].reshape(-1), track["track_i"][n].reshape(-1).to(torch.float64),
+                      track["track_of"][n].to(torch.float64), track["meas_of"][n].to(torch.float64)]).cpu().numpy()         # (int32 is exact in fp64)
+    a, b, c, d = 12 * T, 28 * T, 32 * T, 32 * T + max_obj
+    return flat[:a].reshape(T, 12), flat[a:b].reshape(T, 16), flat[b:c].astype(np.int64).reshape(T, 4), flat[c:d].astype(np.int64), flat[d:].astype(np.int64)
+
+
+def _track_transform(row):
+    T = np.eye(4)
+    T[:3] = row.reshape(3, 4)
+    return T
+
+
+def _track_entries(host, o, key, min_hits):
+    """Object o's track as the entries objects() / rig_objects() add: 'track_id' (None: the object went to no track - a position-only or
+    dropped measurement), the filtered pose under `key`, 'velocity', 'track_hits', 'confirmed'."""
+    track_pose, track_f, track_i, track_of, _ = host
+    slot = int(track_of[o])
+    if slot < 0:
+        return {'track_id': None, key: None, 'velocity': None, 'track_hits': 0, 'confirmed': False}
+    hits = int(track_i[slot, 1])
+    return {'track_id': int(track_i[slot, 0]), key: _track_transform(track_pose[slot]), 'velocity': track_f[slot, 3:6].copy(), 'track_hits': hits,
+            'confirmed': hits >= min_hits}
+
+
+def _track_list(host, key, min_hits):
+    """Every live track, coasting ones included, in slot order."""
+    track_pose, track_f, track_i, _, meas_of = host
+    return [{'track_id': int(track_i[i, 0]), key: _track_transform(track_pose[i]), 'velocity': track_f[i, 3:6].copy(), 'hits': int(track_i[i, 1]),
+             'misses': int(track_i[i, 2]), 'age': int(track_i[i, 3]), 'confirmed': int(track_i[i, 1]) >= min_hits,
+             'object': int(meas_of[i]) if meas_of[i] >= 0 else None} for i in range(track_i.shape[0]) if track_i[i, 0] != 0]
+
+
 class CapturedStep:
     """A captured hipGraph of BatchedKeypointPipeline.forward_device plus everything its kernel nodes point at.
 
@@ -647,10 +720,17 @@ class BatchedKeypointPipeline:
     'T_CO' (4 x 4 float64, model -> camera coordinates; None where the status is ops.POSE_FEW or ops.POSE_DEGENERATE), 'rmse', 'ambiguity' (the
     runner-up assignment's rmse: close to 'rmse' = the data cannot tell the two apart) and 'pose_status'.  max_rmse (metres, optional):
     objects that fit worse carry ops.POSE_POOR.  Without points_3d no launch, key or value differs.
+
+    Tracking (optional, needs the pose): track = ops.TrackConfig(...).  Batch index = stream: frame n of every step is the next tick of
+    stream n.  The device step then ends with okp_track_objects, inside a captured step too, and its dict gains "track": ops.track_objects'
+    outputs plus the state tensors "track_f", "track_i", "next_id" (one state per device and batch size, kept for the pipeline's life).
+    objects() adds 'track_id' (None where the object went to no track), 'T_CO_track' (the filtered pose), 'velocity', 'track_hits' and
+    'confirmed'; tracks(out, n) lists every live track of stream n, coasting ones included; reset_tracks() empties the tracker.  The tick's
+    own "overflow" word is unchanged; "track"["overflow"] is that word | ops.TRACK_OVERFLOW.  Without track no launch, key or value differs.
     """
 
     def __init__(self, net, keypoint_config, camera, prediction_size=(64, 64), capacity=DEFAULT_PEAK_CAPACITY,
-                 max_objects=16, max_per_type=4, points_3d=None, max_rmse=None):
+                 max_objects=16, max_per_type=4, points_3d=None, max_rmse=None, track=None):
         self.net = net
         self.max_objects = max_objects
         self.max_per_type = max_per_type
@@ -671,6 +751,22 @@ class BatchedKeypointPipeline:
             self.max_rmse = ops.check_max_rmse(max_rmse)
             if max(cfg) > max_per_type:
                 raise OkpError(f"a keypoint type has {max(cfg)} instances, above max_per_type = {max_per_type}")
+        track = _check_track(track, points_3d is not None, max_objects, "max_objects")
+        self._tracker = _Tracker(track) if track is not None else None
+
+    def reset_tracks(self):
+        """Empty the tracker: its state tensors are zeroed in place on the current stream, so a captured step keeps working."""
+        if self._tracker is None:
+            raise OkpError("this pipeline was built without track")
+        self._tracker.reset()
+
+    def tracks(self, out, n):
+        """Every live track of stream n after the step `out`, coasting ones included, in slot order: a list of {'track_id', 'T_CO_track'
+        (4 x 4, model -> camera coordinates, filtered), 'velocity' (m/s), 'hits', 'misses', 'age', 'confirmed' (hits >= min_hits), 'object'
+        (the index into objects(out, n) that updated or founded it in this step, or None)} - ONE device -> host copy."""
+        if "track" not in out:
+            raise OkpError("tracks reads the step of a pipeline built with track")
+        return _track_list(_host_tracks(out["track"], n), 'T_CO_track', self._tracker.cfg.min_hits)
 
     def _model(self, device):
         m = self._models.get(device)
@@ -690,12 +786,17 @@ class BatchedKeypointPipeline:
         """Capture forward_device for this frame shape into a hipGraph (HIP stream capture through torch): the ~75
         launches of a step become one graph launch, which removes the host launch cost that dominates small
         batches (batch 8: 2.7 -> 2.2 ms per step).  Returns a CapturedStep; it also unpacks as
-        (step, static_input, static_outputs): replay with step.replay(new_frames) or static_input.copy_(...); step.replay()."""
+        (step, static_input, static_outputs): replay with step.replay(new_frames) or static_input.copy_(...); step.replay().
+        With track: the graph steps the tracker's state of this batch size in place, the state eager steps of the same batch size use; the
+        warm-up passes and the capture advance it, so capture() ends with reset_tracks() - every track alive before it is gone."""
         static_in = frames.clone()
         graph, static_out = _capture(lambda: self.forward_device(static_in))
         step = CapturedStep(self.net, graph, static_in, static_out)
         if self._model_host is not None:                       # the graph reads the model on every replay: the step keeps the very tensor the
             step._model = self._model(static_out["pose"]["tab"].device)     # captured launch took, looked up by the device that launch ran on
+        if self._tracker is not None:                          # (and the tracker's state, which it also writes)
+            step._track_state = [static_out["track"][k] for k in ("track_f", "track_i", "next_id")]
+            self.reset_tracks()
         return step
 
     def postprocess_device(self, heat, depth, centers, range_flag=None):
@@ -714,6 +815,8 @@ class BatchedKeypointPipeline:
             cfg = self.config['keypoint_config']
             tab = ops.object_points(self.cam, out, cfg, int(self.max_index[0]), int(self.max_index[1]))
             out["pose"] = dict(ops.object_pose(tab, out["n_obj"], self._model(tab.device), cfg, self.max_rmse), tab=tab)
+            if self._tracker is not None:
+                out["track"] = self._tracker.step(out["pose"], out["n_obj"], self._model(tab.device), out["overflow"])
         return out
 
     def objects(self, out, n):
@@ -754,6 +857,7 @@ class BatchedKeypointPipeline:
                 lifted[(o, i)] = world[at:at + cfg[i]]
                 at += cfg[i]
         poses = _host_poses(out["pose"], n) if "pose" in out else None
+        tracked = _host_tracks(out["track"], n) if "track" in out else None
         objects = []
         for o in range(n_obj):
             keypoints = [xyc[0, o, :2].copy()[None]]
@@ -774,6 +878,8 @@ class BatchedKeypointPipeline:
             objects.append({'p_centers': p_centers, 'keypoints': keypoints, 'p_C': world})
             if poses is not None:
                 objects[-1].update(_pose_entries(poses, o, 'T_CO'))
+            if tracked is not None:
+                objects[-1].update(_track_entries(tracked, o, 'T_CO_track', self._tracker.cfg.min_hits))
         return objects
 
     def objects_reference(self, out, n):
@@ -936,10 +1042,16 @@ class StereoStreamPipeline:
     Pose (optional, needs the fusion): points_3d = the object model as for BatchedKeypointPipeline, max_rmse optional.  The fused device
     ticks then end with okp_rig_object_points and okp_object_pose - the pose of every fused object in the RIG frame, inside the captured
     graph, after the gather on every rank - under the key "pose" (ops.object_pose's dict plus "tab"), and rig_objects(out) adds 'T_BO'
-    (4 x 4, model -> rig coordinates, or None), 'rmse', 'ambiguity' and 'pose_status' to every object."""
+    (4 x 4, model -> rig coordinates, or None), 'rmse', 'ambiguity' and 'pose_status' to every object.
+
+    Tracking (optional, needs the pose): track = ops.TrackConfig(...).  The fused device ticks then end with okp_track_objects - one stream,
+    in the rig frame, inside the captured graph, after the gather on every rank with no further collective (every rank keeps the same
+    tracker) - under the key "track" (ops.track_objects' outputs plus the state tensors); rig_objects(out) adds 'track_id', 'T_BO_track',
+    'velocity', 'track_hits' and 'confirmed', rig_tracks(out) lists the live tracks, reset_tracks() empties the tracker.  The tick's
+    "overflow" word is unchanged; "track"["overflow"] carries ops.TRACK_OVERFLOW on top of it."""
 
     def __init__(self, net, stereo_camera, keypoint_config, capacity=16, max_distance=3.0, rig_poses=None, merge_radius=None, object_radius=None,
-                 fuse_capacity=None, points_3d=None, max_rmse=None):
+                 fuse_capacity=None, points_3d=None, max_rmse=None, track=None):
         self.net = net
         self.rig = None if hasattr(stereo_camera, "left_camera") else list(stereo_camera)       # one StereoCamera, or a sequence of them
         self.stereo_cameras = self.rig if self.rig is not None else [stereo_camera]
@@ -983,6 +1095,26 @@ class StereoStreamPipeline:
             self._model_host = ops.object_model(points_3d, self.config[1:])
             self._models = {}                                           # device -> the uploaded model
             self.max_rmse = ops.check_max_rmse(max_rmse)
+        track = _check_track(track, points_3d is not None, self.fuse_capacity if given else 0, "fuse_capacity")
+        self._tracker = _Tracker(track) if track is not None else None
+
+    def reset_tracks(self):
+        """Empty the tracker: its state tensors are zeroed in place on the current stream, so a captured tick keeps working."""
+        if self._tracker is None:
+            raise OkpError("this pipeline was built without track")
+        self._tracker.reset()
+
+    def _track(self, out):
+        """The tracker stepped by a fused tick's poses: one launch behind okp_object_pose."""
+        return self._tracker.step(out["pose"], out["fused"]["n_obj"], self._model(out["pose"]["tab"].device), out["fused"]["overflow"])
+
+    def rig_tracks(self, out):
+        """Every live track after the fused tick `out`, coasting ones included, in slot order: a list of {'track_id', 'T_BO_track' (4 x 4,
+        model -> rig coordinates, filtered), 'velocity' (m/s), 'hits', 'misses', 'age', 'confirmed', 'object' (the index into
+        rig_objects(out), or None)} - ONE device -> host copy."""
+        if not isinstance(out, dict) or "track" not in out:
+            raise OkpError("rig_tracks reads the fused device tick of a pipeline built with track")
+        return _track_list(_host_tracks(out["track"], 0), 'T_BO_track', self._tracker.cfg.min_hits)
 
     def _check_fused_tick(self, n_pairs, first_pair=0):
         """A fused tick holds every pair of the rig: the clusters are formed across all of them."""
@@ -1148,6 +1280,8 @@ class StereoStreamPipeline:
                 out["overflow"] = out["fused"]["overflow"]
                 if self._model_host is not None:
                     out["pose"] = self._pose(out["fused"])
+                    if self._tracker is not None:
+                        out["track"] = self._track(out)
         return out
 
     def capture_device(self, frames, heat_override=None, first_pair=0):
@@ -1155,7 +1289,9 @@ class StereoStreamPipeline:
         that the capture succeeds is itself the check that nothing in the tick waits on the host.  Returns a CapturedTick: replay with
         step.replay(new_frames[, new_heat]) or by copying into step.static_in / step.static_heat (heat_override, when given, is a static
         input of the graph like the frames) and step.replay(); the outputs are step.static_out (tick_device's dict).  first_pair: as for
-        tick_device; the warm-up ticks upload the calibration table before the capture begins."""
+        tick_device; the warm-up ticks upload the calibration table before the capture begins.  With track: the graph steps the tracker's
+        state in place, the state eager ticks use; the warm-up ticks and the capture advance it, so capture_device() ends with
+        reset_tracks() - every track alive before it is gone."""
         first_pair = self._check_device_tick(frames, first_pair)
         self._check_fused_tick(frames.shape[0] // 2, first_pair)
         static_in = frames.clone()
@@ -1166,6 +1302,9 @@ class StereoStreamPipeline:
         step._poses = self._poses.get(frames.device) if self._poses_host is not None else None       # (and the pose table)
         if self._model_host is not None and "pose" in static_out:       # (and the object model: the tensor the captured launch took)
             step._model = self._model(static_out["pose"]["tab"].device)
+        if "track" in static_out:                                       # (and the tracker's state, which the graph also writes)
+            step._track_state = [static_out["track"][k] for k in ("track_f", "track_i", "next_id")]
+            self.reset_tracks()
         return step
 
     def results(self, out):
@@ -1213,6 +1352,8 @@ class StereoStreamPipeline:
                 whole["fused"] = out["fused"]
             if "pose" in out:
                 whole["pose"] = out["pose"]
+            if "track" in out:
+                whole["track"] = out["track"]
             return whole
         start, n_local = distributed.shard(int(n_pairs_total), dist.get_rank(), dist.get_world_size())
         if frames_local.shape[0] != 2 * n_local:
@@ -1233,6 +1374,8 @@ class StereoStreamPipeline:
                 out["fused"] = self._fuse(gathered, flag)
                 if self._model_host is not None:
                     out["pose"] = self._pose(out["fused"])
+                    if self._tracker is not None:
+                        out["track"] = self._track(out)
             out["overflow"] = out["fused"]["overflow"]
         return out
 
@@ -1243,7 +1386,8 @@ class StereoStreamPipeline:
                     ObjectKeypointPipeline's 'p_C', one array per key-point type, n_k <= the type's count, in cluster order,
              "confidence": [(1,), (n_1,), ...] float64, "views": [(1,), (n_1,), ...] int32 bit masks of the contributing pairs}
         plus, for a pipeline built with points_3d, 'T_BO' (4 x 4 float64: model -> rig coordinates; None where the status is ops.POSE_FEW or
-        ops.POSE_DEGENERATE), 'rmse', 'ambiguity' (the runner-up assignment's rmse) and 'pose_status' -
+        ops.POSE_DEGENERATE), 'rmse', 'ambiguity' (the runner-up assignment's rmse) and 'pose_status', and, for one built with track,
+        'track_id' (None where the object went to no track), 'T_BO_track' (the filtered pose), 'velocity', 'track_hits' and 'confirmed' -
         read in ONE device -> host copy.  Raises OkpError when the tick's overflow word is set, as results() does (bit ops.FUSE_OVERFLOW:
         a type had more than fuse_capacity clusters).  tick(), the host tick, does not fuse: its return value is not accepted here."""
         if not isinstance(out, dict) or "fused" not in out:
@@ -1256,6 +1400,11 @@ class StereoStreamPipeline:
         if "pose" in out:
             ps = out["pose"]
             tail += [ps["pose"].reshape(-1), ps["fit"].reshape(-1), ps["status"].reshape(-1).to(torch.float64)]
+        if "track" in out:
+            tr = out["track"]
+            n_slots = tr["meas_of"].shape[1]
+            tail += [tr["track_pose"].reshape(-1), tr["track_f"].reshape(-1), tr["track_i"].reshape(-1).to(torch.float64), tr["track_of"].reshape(-1).to(torch.float64),
+                     tr["meas_of"].reshape(-1).to(torch.float64)]
         flat = torch.cat([t.to(torch.float64) for t in parts] + tail).cpu().numpy()          # the one D2H copy (int32 is exact in fp64)
         _raise_on_overflow(int(flat[0]), fused=True)
         n_obj = int(flat[1])
@@ -1267,7 +1416,13 @@ class StereoStreamPipeline:
         poses = None
         if "pose" in out:
             rest = flat[at + 2 * K * cap_f + K * cap_f * 4:]
-            poses = (rest[:12 * cap_f].reshape(cap_f, 12), rest[12 * cap_f:14 * cap_f].reshape(cap_f, 2), rest[14 * cap_f:].astype(np.int64))
+            poses = (rest[:12 * cap_f].reshape(cap_f, 12), rest[12 * cap_f:14 * cap_f].reshape(cap_f, 2), rest[14 * cap_f:15 * cap_f].astype(np.int64))
+        tracked = None
+        if "track" in out:
+            rest = rest[15 * cap_f:]
+            a, b, c, d = 12 * n_slots, 28 * n_slots, 32 * n_slots, 32 * n_slots + cap_f
+            tracked = (rest[:a].reshape(n_slots, 12), rest[a:b].reshape(n_slots, 16), rest[b:c].astype(np.int64).reshape(n_slots, 4), rest[c:d].astype(np.int64),
+                       rest[d:].astype(np.int64))
         objects = []
         for o in range(n_obj):
             p_B, conf, seen = [], [], []
@@ -1279,4 +1434,6 @@ class StereoStreamPipeline:
             objects.append({"p_B": p_B, "confidence": conf, "views": seen})
             if poses is not None:
                 objects[-1].update(_pose_entries(poses, o, "T_BO"))
+            if tracked is not None:
+                objects[-1].update(_track_entries(tracked, o, "T_BO_track", self._tracker.cfg.min_hits))
         return objects
