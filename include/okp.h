@@ -40,7 +40,8 @@ extern "C" {
                                     okp_project_labels, okp_render_targets, okp_keypoint_loss (scoring labelled scenes);
                                     okp_rig_fuse (a rig's stereo pairs fused into one object list in the rig frame);
                                     okp_object_points, okp_rig_object_points, okp_object_pose (each object's 6-DoF pose from its 3D key points);
-                                    okp_track_objects, OKP_TRACK_* (objects tracked across ticks: stable ids, filtered poses) */
+                                    okp_track_objects, OKP_TRACK_* (objects tracked across ticks: stable ids, filtered poses);
+                                    okp_change_frame, OKP_FRAME_MISSING (points, tables and poses in a fixed world frame under a moving camera) */
 
 /* OKP_F16: IEEE half activations / weights, fp32 accumulate (BASELINE configs[4]).
  * OKP_F32X3 (okp_conv plans only): fp32 activations, weights and results like OKP_F32 - every tensor argument of such a plan is an
@@ -689,6 +690,44 @@ int okp_track_objects(const double* tab_dev, const double* pose_dev, const int32
                       int32_t min_hits, int32_t max_misses, const int32_t* overflow_in_dev, double* track_f_dev, int32_t* track_i_dev,
                       int32_t* next_id_dev, double* track_pose_dev, int32_t* track_of_dev, int32_t* meas_of_dev, int32_t* n_tracks_dev,
                       int32_t* overflow_dev, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * Change of frame (csrc/okp_frame.hip): everything above is expressed in the frame of the camera (okp_object_points: T_CO) or of the rig
+ * (okp_rig_fuse: T_BO), and a camera on an arm or in a hand moves.  The host hands the step one pose per stream and tick, T_WC (or T_WB),
+ * in device memory - replaceable between replays of a captured graph, like the frames -, and the step re-expresses its lifted points, its
+ * object tables and its poses in the world frame, runs the tracker there and takes the filtered track poses back into the current camera
+ * frame.  Fed this way, the tracker's gate, its velocity and its coasting over max_misses ticks are world-frame quantities: a static
+ * object under a moving camera stays inside its gate, has zero velocity and coasts in place.  There is no reference implementation: the
+ * specification is this comment (tests/frame_spec.py restates it in NumPy).
+ *
+ * okp_change_frame: one launch, one lane per output row, fp64, no atomics, no host wait, capturable; the same bits on every run.
+ *   T [B][12] fp64, row-major [R | t] (3 x 4) of stream b: for a camera pose, camera coordinates -> world.  R is taken as a rotation; the
+ *   kernel cannot check that: the caller does, before the upload.
+ *   points_in / points_out [B][n_points][4] fp64 rows (X, Y, Z, c): okp_lift_peaks' points, the rows of an object table, okp_rig_fuse's
+ *   clusters.  pose_in / pose_out [B][n_pose][12] fp64 rows [Rp | tp].  Either table may be absent (NULL with a count of 0), not both.
+ *   Every product and sum below is rounded on its own (no contraction), in exactly this association.
+ *   Forward (inverse == 0):
+ *     point  X'_i = ((R[i][0]*X + R[i][1]*Y) + R[i][2]*Z) + t[i];  c is copied bit for bit
+ *     pose   R'[i][j] = (R[i][0]*Rp[0][j] + R[i][1]*Rp[1][j]) + R[i][2]*Rp[2][j]
+ *            t'[i] = ((R[i][0]*tp[0] + R[i][1]*tp[1]) + R[i][2]*tp[2]) + t[i]
+ *   Inverse (inverse != 0: the transform by T^-1 = [R^T | -R^T t]):
+ *     d = p - t, p the point's (X, Y, Z) or the pose's tp;  result_i = (R[0][i]*d[0] + R[1][i]*d[1]) + R[2][i]*d[2];  c is copied
+ *     R'[i][j] = (R[0][i]*Rp[0][j] + R[1][i]*Rp[1][j]) + R[2][i]*Rp[2][j]
+ *   Missing pose: when any of the 12 values of T[b] is not finite, EVERY output value of stream b is NaN - all 4 of each point row, all
+ *   12 of each pose row: in the table convention an empty slot, and a pose the tracker refuses, so the tick yields no measurement and
+ *   the tracks coast - and bit OKP_FRAME_MISSING is raised (bits 1, 2, 4 and 8 are taken: capacity, fp16 range, OKP_RIG_FUSE_OVERFLOW,
+ *   OKP_TRACK_OVERFLOW).  overflow = (*overflow_in or 0) | bit, written by every call; overflow_in may be NULL and may be the address of
+ *   `overflow`.
+ *   Non-finite INPUT rows are not special-cased: they go through the same arithmetic, so a NaN row stays NaN (empty slots stay empty).
+ *   A lane reads its whole input row before it writes: points_out == points_in and pose_out == pose_in are allowed and give the bits of
+ *   the out-of-place call.
+ * Refused on the host before any launch (OKP_EINVAL, the message names the argument): B < 1, a negative count, a count > 0 with a null
+ * pointer, both counts 0, a null T or overflow.
+ * ---------------------------------------------------------------------------------- */
+#define OKP_FRAME_MISSING 16
+int okp_change_frame(const double* T_dev, int32_t B, int inverse, const double* points_in_dev, int32_t n_points, double* points_out_dev,
+                     const double* pose_in_dev, int32_t n_pose, double* pose_out_dev, const int32_t* overflow_in_dev, int32_t* overflow_dev,
+                     void* stream);
 
 /* Undistort only (FisheyeCamera.undistort, camera_utils.py:75-81 / RadTanPinholeCamera.undistort, :57-62, by cam->model):
  * xy [m][2] fp32 -> out [m][2] fp64.  okp_fisheye_undistort is the same entry point under its round-1 name. */

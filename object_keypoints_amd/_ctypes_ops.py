@@ -348,6 +348,13 @@ def track_objects(tab, pose, status, n_obj, model, gate, dt, alpha, beta, alpha_
                                             overflow.data_ptr(), stream), "okp_track_objects")
 
 
+# ---- change of frame (csrc/okp_frame.hip): T [B,12], points [B,n_points,4], poses [B,n_pose,12]; either table may be None ------------------------
+def change_frame(T, inverse, points, out_points, poses, out_poses, overflow, stream, overflow_in=None):
+    _lib.check(_lib.lib().okp_change_frame(T.data_ptr(), T.shape[0], 1 if inverse else 0, _ptr(points), points.shape[1] if points is not None else 0, _ptr(out_points),
+                                           _ptr(poses), poses.shape[1] if poses is not None else 0, _ptr(out_poses), _ptr(overflow_in), overflow.data_ptr(), stream),
+               "okp_change_frame")
+
+
 # ---- scoring labelled scenes -----------------------------------------------------------------------------------------------------------------
 def project_labels(camera, world_points, T_WC, scale, crop_x, crop_y, labels, stream):
     _lib.check(_lib.lib().okp_project_labels(_camera(camera), world_points.data_ptr(), world_points.shape[0], T_WC.data_ptr(), T_WC.shape[0], scale, crop_x, crop_y,

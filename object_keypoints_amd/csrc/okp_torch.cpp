@@ -652,6 +652,33 @@ void track_objects(const Tensor& tab, const Tensor& pose, const Tensor& status, 
                              n_tracks.data_ptr<int32_t>(), overflow.data_ptr<int32_t>(), sp(stream)), "okp_track_objects");
 }
 
+// Change of frame (csrc/okp_frame.hip): T [B,12], points [B,n_points,4] and poses [B,n_pose,12] (either may be absent) through every stream's
+// rigid transform or its inverse; out_points / out_poses may be the inputs themselves; overflow = (overflow_in or 0) | OKP_FRAME_MISSING
+void change_frame(const Tensor& T, bool inverse, const optional<Tensor>& points, const optional<Tensor>& out_points, const optional<Tensor>& poses,
+                  const optional<Tensor>& out_poses, const Tensor& overflow, int64_t stream, const optional<Tensor>& overflow_in) {
+  check_dev(T, at::kDouble, "T"); check_dev(overflow, at::kInt, "overflow");
+  if (overflow_in.has_value()) check_dev(*overflow_in, at::kInt, "overflow_in");
+  TORCH_CHECK(T.dim() == 2 && T.size(1) == 12, "okp: T is [B,12] float64 (ops.frame_poses)");
+  const int64_t B = T.size(0);
+  TORCH_CHECK(points.has_value() == out_points.has_value() && poses.has_value() == out_poses.has_value(), "okp: change_frame takes points with out_points and poses with out_poses");
+  int64_t n_points = 0, n_pose = 0;
+  if (points.has_value()) {
+    check_dev(*points, at::kDouble, "points"); check_dev(*out_points, at::kDouble, "out_points");
+    TORCH_CHECK(points->dim() == 3 && points->size(0) == B && points->size(2) == 4 && out_points->numel() == points->numel(), "okp: points and out_points are [B,n_points,4] float64");
+    n_points = points->size(1);
+  }
+  if (poses.has_value()) {
+    check_dev(*poses, at::kDouble, "poses"); check_dev(*out_poses, at::kDouble, "out_poses");
+    TORCH_CHECK(poses->dim() == 3 && poses->size(0) == B && poses->size(2) == 12 && out_poses->numel() == poses->numel(), "okp: poses and out_poses are [B,n_pose,12] float64");
+    n_pose = poses->size(1);
+  }
+  TORCH_CHECK(overflow.numel() == 1 && (!overflow_in.has_value() || overflow_in->numel() == 1), "okp: overflow and overflow_in are one int32 each");
+  check_rc(okp_change_frame(T.data_ptr<double>(), (int32_t)B, inverse ? 1 : 0, points.has_value() ? points->data_ptr<double>() : nullptr, (int32_t)n_points,
+                            out_points.has_value() ? out_points->data_ptr<double>() : nullptr, poses.has_value() ? poses->data_ptr<double>() : nullptr, (int32_t)n_pose,
+                            out_poses.has_value() ? out_poses->data_ptr<double>() : nullptr, overflow_in.has_value() ? overflow_in->data_ptr<int32_t>() : nullptr,
+                            overflow.data_ptr<int32_t>(), sp(stream)), "okp_change_frame");
+}
+
 void lift_peaks(at::ArrayRef<double> camera, const Tensor& count, const Tensor& xyc, const Tensor& depth, int64_t max_x, int64_t max_y, const Tensor& out, int64_t stream) {
   TORCH_CHECK(xyc.is_cuda() && xyc.dim() == 4 && xyc.scalar_type() == at::kFloat && depth.is_cuda() && depth.scalar_type() == at::kFloat && depth.dim() == 4 && depth.is_contiguous() &&
               depth.size(0) == xyc.size(0) && depth.size(1) == xyc.size(1) && count.scalar_type() == at::kInt && out.scalar_type() == at::kDouble &&
@@ -815,6 +842,8 @@ TORCH_LIBRARY(okp, m) {
   m.def("track_objects(Tensor tab, Tensor pose, Tensor status, Tensor n_obj, Tensor model, float gate, float dt, float alpha, float beta, float alpha_R, "
         "int min_hits, int max_misses, Tensor(a!) track_f, Tensor(b!) track_i, Tensor(c!) next_id, Tensor(d!) track_pose, Tensor(e!) track_of, "
         "Tensor(f!) meas_of, Tensor(g!) n_tracks, Tensor(h!) overflow, int stream, Tensor? overflow_in=None) -> ()", track_objects);
+  m.def("change_frame(Tensor T, bool inverse, Tensor? points, Tensor(a!)? out_points, Tensor? poses, Tensor(b!)? out_poses, Tensor(c!) overflow, int stream, "
+        "Tensor? overflow_in=None) -> ()", change_frame);
   m.def("rig_fuse(Tensor points, Tensor poses, int[] type_count, float merge_radius, float object_radius, Tensor(a!) fused, Tensor(b!) n_fused, Tensor(c!) views, "
         "Tensor(d!) object, Tensor(e!) member, Tensor(f!) n_obj, Tensor(g!) overflow, int stream, Tensor? overflow_in=None) -> ()", rig_fuse);
   m.def("project_labels(float[] camera, Tensor world_points, Tensor T_WC, float scale, float crop_x, float crop_y, Tensor(a!) labels, int stream) -> ()", project_labels);

@@ -1314,6 +1314,102 @@ def track_objects(state, tab, pose, status, n_obj, model, cfg, overflow=None):
     return {"track_pose": track_pose, "track_of": track_of, "meas_of": meas_of, "n_tracks": n_tracks, "overflow": word[0]}
 
 
+# ---- a fixed world frame under a moving camera (okp_change_frame, csrc/okp_frame.hip; no reference counterpart: the specification is include/okp.h) ----
+FRAME_MISSING = 16           # bit of change_frame()'s overflow word: a stream's pose was missing (NaN) in this tick, its outputs are NaN
+FRAME_POSE_TOLERANCE = 1e-9  # |R^T R - I|_max of a camera / rig pose: rejects scaled and reflected matrices, passes any product of fp64 rotations
+
+
+def frame_poses(T, allow_missing=True):
+    """The per-stream poses of one tick: [B,4,4] or [B,3,4] array-likes (or one [4,4] / [3,4]), T_WC (camera coordinates -> world) or T_WB
+    -> float64 HOST tensor [B,12], row b = T[b][:3] row-major, which the caller moves to the frames' device (`.to(device)`).  The kernel cannot
+    check a device table, so a bad pose is refused here, with its stream named: each pose is either entirely NaN (a MISSING pose: the stream's
+    tick yields no measurements and its tracks coast; only with allow_missing) or finite with |R^T R - I|_max <= FRAME_POSE_TOLERANCE and
+    det R > 0; a 4th row, when given, is 0, 0, 0, 1."""
+    try:
+        a = np.array(T.detach().cpu().numpy() if isinstance(T, torch.Tensor) else T, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise OkpError("T: poses must be numbers, [B,4,4] or [B,3,4] (or one [4,4])") from None
+    if a.ndim == 2:
+        a = a[None]
+    if a.ndim != 3 or a.shape[0] < 1 or tuple(a.shape[1:]) not in ((4, 4), (3, 4)):
+        raise OkpError(f"T has shape {tuple(np.shape(T))}: one pose per stream, [B,4,4] or [B,3,4] (or one [4,4])")
+    out = np.empty((a.shape[0], 12), dtype=np.float64)
+    for b, M in enumerate(a):
+        top = M[:3]
+        if np.isnan(top).all() and (M.shape[0] == 3 or np.isnan(M[3]).all() or np.array_equal(M[3], [0.0, 0.0, 0.0, 1.0])):
+            if not allow_missing:
+                raise OkpError(f"T: stream {b}: the pose is missing (NaN) and allow_missing is off")
+            out[b] = np.nan
+            continue
+        if not np.isfinite(top).all():
+            raise OkpError(f"T: stream {b}: the pose is neither finite nor entirely NaN (a missing pose is NaN in every entry)")
+        if M.shape[0] == 4 and not np.array_equal(M[3], [0.0, 0.0, 0.0, 1.0]):
+            raise OkpError(f"T: stream {b}: the last row is {M[3].tolist()}, not [0, 0, 0, 1]")
+        R = top[:, :3]
+        err = float(np.abs(R.T @ R - np.eye(3)).max())
+        if err > FRAME_POSE_TOLERANCE:
+            raise OkpError(f"T: stream {b}: the rotation block is not orthonormal (|R^T R - I| = {err:.3g}, above {FRAME_POSE_TOLERANCE:g}: scaled or sheared)")
+        if not np.linalg.det(R) > 0.0:
+            raise OkpError(f"T: stream {b}: the rotation block has determinant {np.linalg.det(R):.6g}, not +1 (a reflection)")
+        out[b] = top.reshape(12)
+    return torch.from_numpy(out)
+
+
+def change_frame(T, points=None, poses=None, inverse=False, overflow=None, out_points=None, out_poses=None):
+    """Points and poses of every stream through that stream's rigid transform (okp_change_frame; the arithmetic is specified in include/okp.h).
+        T [B,12] float64 (device): frame_poses(...) moved to the device - row-major [R | t], camera (or rig) coordinates -> world
+        points [B,...,4] float64 rows (X, Y, Z, c) - lift_peaks' points, an object table, rig_fuse's clusters with a leading 1 -, poses [B,...,12]
+        float64 rows [R | t]; at least one of the two.  inverse: transform by T^-1 (world -> camera) instead
+        overflow: the tick's overflow word to fold into the result, or None; out_points / out_poses: where to write (the inputs themselves
+        are allowed: in place), or None for new tensors
+    -> {"points", "poses" (None where not given), "overflow" 0-d int32 = overflow | FRAME_MISSING where a stream's pose is not finite - every
+        output value of that stream is then NaN}.  One launch, no host sync."""
+    # (dtype and shape before the device: a wrong table is named for what is wrong with it wherever it lives)
+    if not isinstance(T, torch.Tensor) or T.dtype != torch.float64 or T.dim() != 2 or T.shape[1] != 12 or T.shape[0] < 1 or not T.is_contiguous():
+        raise OkpError("T must be a contiguous float64 [B,12] tensor: frame_poses(...).to(device)")
+    require_cuda(T, "T")
+    b, dev = int(T.shape[0]), T.device
+    if points is None and poses is None:
+        raise OkpError("change_frame: neither points nor poses given: nothing to transform")
+
+    def table(name, x, out, width):
+        if x is None:
+            if out is not None:
+                raise OkpError(f"out_{name} without {name}")
+            return None, None
+        if not isinstance(x, torch.Tensor) or x.dtype != torch.float64 or x.dim() < 2 or x.shape[0] != b or x.shape[-1] != width:
+            raise OkpError(f"{name} must be float64 [{b},...,{width}]: one block of rows per stream of T")
+        if x.numel() == 0:
+            raise OkpError(f"{name} has shape {list(x.shape)}: no rows")
+        require_cuda(x, name)
+        if x.device != dev:
+            raise OkpError(f"{name} is on {x.device}, T on {dev}")
+        x = x.contiguous()
+        if out is None:
+            out = torch.empty_like(x)
+        else:
+            if not isinstance(out, torch.Tensor) or out.dtype != torch.float64 or tuple(out.shape) != tuple(x.shape) or not out.is_contiguous():
+                raise OkpError(f"out_{name} must be a contiguous float64 tensor {list(x.shape)}")
+            require_cuda(out, f"out_{name}")
+            if out.device != dev:
+                raise OkpError(f"out_{name} is on {out.device}, T on {dev}")
+        return x, out
+
+    points, out_points = table("points", points, out_points, 4)
+    poses, out_poses = table("poses", poses, out_poses, 12)
+    if overflow is not None:
+        if not isinstance(overflow, torch.Tensor) or overflow.dtype != torch.int32 or overflow.numel() != 1:
+            raise OkpError("overflow must be one int32 (a tick's overflow word)")
+        require_cuda(overflow, "overflow")
+        if overflow.device != dev:
+            raise OkpError(f"overflow is on {overflow.device}, T on {dev}")
+        overflow = overflow.reshape(1)
+    word = torch.empty((1,), dtype=torch.int32, device=dev)
+    flat = lambda x, width: x.view(b, -1, width) if x is not None else None
+    _dispatch(_ops().change_frame, T, bool(inverse), flat(points, 4), flat(out_points, 4), flat(poses, 12), flat(out_poses, 12), word, stream_int(), overflow)
+    return {"points": out_points, "poses": out_poses, "overflow": word[0]}
+
+
 # ---- scoring labelled scenes (csrc/okp_targets.hip) ---------------------------------------------------------------------------------
 TARGET_SIZE = 64             # SceneDataset.prediction_size
 TARGET_MAX_MAPS = 16         # K

@@ -622,38 +622,91 @@ class _Tracker:
 
 def _host_tracks(track, n):
     """Stream n of a tick's "track" dict on the host, in ONE device -> host copy: (track_pose [T,12], track_f [T,16], track_i [T,4],
-    track_of [max_obj], meas_of [T])."""
+    track_of [max_obj], meas_of [T], track_pose_C [T,12] or None - the track poses back in the camera / rig frame of a world-frame tick)."""
     T, max_obj = track["meas_of"].shape[1], track["track_of"].shape[1]
+    local = [track["track_pose_C"][n].reshape(-1)] if "track_pose_C" in track else []
     flat = torch.cat([track["track_pose"][n].reshape(-1), track["track_f"][n].reshape(-1), track["track_i"][n].reshape(-1).to(torch.float64),
-                      track["track_of"][n].to(torch.float64), track["meas_of"][n].to(torch.float64)]).cpu().numpy()         # (int32 is exact in fp64)
-    a, b, c, d = 12 * T, 28 * T, 32 * T, 32 * T + max_obj
-    return flat[:a].reshape(T, 12), flat[a:b].reshape(T, 16), flat[b:c].astype(np.int64).reshape(T, 4), flat[c:d].astype(np.int64), flat[d:].astype(np.int64)
+                      track["track_of"][n].to(torch.float64), track["meas_of"][n].to(torch.float64)] + local).cpu().numpy()  # (int32 is exact in fp64)
+    a, b, c, d, e = 12 * T, 28 * T, 32 * T, 32 * T + max_obj, 33 * T + max_obj
+    return (flat[:a].reshape(T, 12), flat[a:b].reshape(T, 16), flat[b:c].astype(np.int64).reshape(T, 4), flat[c:d].astype(np.int64), flat[d:e].astype(np.int64),
+            flat[e:].reshape(T, 12) if local else None)
 
 
 def _track_transform(row):
+    if not np.isfinite(row).all():           # (a world-frame track seen from a tick whose camera pose is missing)
+        return None
     T = np.eye(4)
     T[:3] = row.reshape(3, 4)
     return T
 
 
-def _track_entries(host, o, key, min_hits):
+def _track_poses(host, slot, key, world_key):
+    """The filtered pose of a track slot under `key` (the camera or rig frame) and, for a world-frame tick, under `world_key` as well: the
+    tracker's own pose is then the world one and `key` is read from the inverse transform."""
+    if host[5] is None:
+        return {key: _track_transform(host[0][slot])}
+    return {world_key: _track_transform(host[0][slot]), key: _track_transform(host[5][slot])}
+
+
+def _track_entries(host, o, key, min_hits, world_key=None):
     """Object o's track as the entries objects() / rig_objects() add: 'track_id' (None: the object went to no track - a position-only or
     dropped measurement), the filtered pose under `key`, 'velocity', 'track_hits', 'confirmed'."""
-    track_pose, track_f, track_i, track_of, _ = host
+    track_pose, track_f, track_i, track_of = host[:4]
     slot = int(track_of[o])
     if slot < 0:
-        return {'track_id': None, key: None, 'velocity': None, 'track_hits': 0, 'confirmed': False}
+        none = {key: None} if host[5] is None else {world_key: None, key: None}
+        return dict({'track_id': None, 'velocity': None, 'track_hits': 0, 'confirmed': False}, **none)
     hits = int(track_i[slot, 1])
-    return {'track_id': int(track_i[slot, 0]), key: _track_transform(track_pose[slot]), 'velocity': track_f[slot, 3:6].copy(), 'track_hits': hits,
-            'confirmed': hits >= min_hits}
+    return dict({'track_id': int(track_i[slot, 0]), 'velocity': track_f[slot, 3:6].copy(), 'track_hits': hits, 'confirmed': hits >= min_hits},
+                **_track_poses(host, slot, key, world_key))
 
 
-def _track_list(host, key, min_hits):
+def _track_list(host, key, min_hits, world_key=None):
     """Every live track, coasting ones included, in slot order."""
-    track_pose, track_f, track_i, _, meas_of = host
-    return [{'track_id': int(track_i[i, 0]), key: _track_transform(track_pose[i]), 'velocity': track_f[i, 3:6].copy(), 'hits': int(track_i[i, 1]),
-             'misses': int(track_i[i, 2]), 'age': int(track_i[i, 3]), 'confirmed': int(track_i[i, 1]) >= min_hits,
-             'object': int(meas_of[i]) if meas_of[i] >= 0 else None} for i in range(track_i.shape[0]) if track_i[i, 0] != 0]
+    track_pose, track_f, track_i, _, meas_of = host[:5]
+    return [dict({'track_id': int(track_i[i, 0]), 'velocity': track_f[i, 3:6].copy(), 'hits': int(track_i[i, 1]),
+                  'misses': int(track_i[i, 2]), 'age': int(track_i[i, 3]), 'confirmed': int(track_i[i, 1]) >= min_hits,
+                  'object': int(meas_of[i]) if meas_of[i] >= 0 else None}, **_track_poses(host, i, key, world_key))
+            for i in range(track_i.shape[0]) if track_i[i, 0] != 0]
+
+
+def _check_frame_pose(pose, world_frame, streams, device, name, what):
+    """The per-tick pose argument of both device pipelines against their world_frame switch: both or neither."""
+    if not world_frame:
+        if pose is not None:
+            raise OkpError(f"{name} given to a pipeline built without world_frame")
+        return None
+    if pose is None:
+        raise OkpError(f"{name} is required by a pipeline built with world_frame: ops.frame_poses(...).to(device), {what}")
+    if not isinstance(pose, torch.Tensor) or pose.dtype != torch.float64 or tuple(pose.shape) != (streams, 12) or pose.device != device or not pose.is_contiguous():
+        raise OkpError(f"{name} must be a float64 [{streams},12] tensor on the frames' device ({device}): ops.frame_poses(...).to(device), {what}")
+    return pose
+
+
+def _world(T, points, pose, overflow):
+    """The world-frame view of a tick (two okp_change_frame launches at the most): the lifted / fused `points`, and - with an object model -
+    the pose stage's table and poses, through the tick's poses T [B,12]; "overflow" = the tick's word | ops.FRAME_MISSING."""
+    B = T.shape[0]
+    first = ops.change_frame(T, points=points.reshape((B, -1, 4)), overflow=overflow)
+    world = {"T": T, "points": first["points"].view(points.shape), "overflow": first["overflow"]}
+    if pose is not None:
+        second = ops.change_frame(T, points=pose["tab"], poses=pose["pose"], overflow=overflow)
+        world.update(tab=second["points"], pose=second["poses"])
+    return world
+
+
+def _track_world(tracker, world, pose, n_obj, model):
+    """The tracker stepped in the world frame, and its filtered poses taken back into the tick's camera / rig frame ("track_pose_C")."""
+    track = tracker.step(dict(pose, tab=world["tab"], pose=world["pose"]), n_obj, model, world["overflow"])
+    track["track_pose_C"] = ops.change_frame(world["T"], poses=track["track_pose"], inverse=True)["poses"]
+    return track
+
+
+def _frame_point(T, p, missing):
+    """One host-lifted point [3] into the world frame by the formula of okp_change_frame (a row of T [3,4]: ((a + b) + c) + t)."""
+    if missing:
+        return None
+    return np.array([((T[i, 0] * p[0] + T[i, 1] * p[1]) + T[i, 2] * p[2]) + T[i, 3] for i in range(3)])
 
 
 class CapturedStep:
@@ -666,6 +719,7 @@ class CapturedStep:
 
     def __init__(self, net, graph, static_in, static_out):
         self.net, self.graph, self.static_in, self.static_out = net, graph, static_in, static_out
+        self.static_pose = None                  # world_frame: the static camera / rig pose tensor next to static_in
         self._pinned = _live_plans(net)
         # every module that caches plans, with its plan epoch at capture time: the per-replay staleness test is ~150 integer
         # compares (walking and comparing the plan objects themselves cost a replay ~0.4 ms of host time)
@@ -674,9 +728,13 @@ class CapturedStep:
     def stale(self):
         return any(m._plan_epoch != e for m, e in self._epochs)
 
-    def replay(self, frames=None):
+    def replay(self, frames=None, camera_pose=None):
         if self.stale():
             raise OkpError("the network's weights / plans changed after capture(): capture the step again")
+        if camera_pose is not None:
+            if self.static_pose is None:
+                raise OkpError("this step was captured without a pose (a pipeline built without world_frame): it has no pose input")
+            self.static_pose.copy_(camera_pose)
         if frames is not None:
             self.static_in.copy_(frames)
         self.graph.replay()
@@ -694,12 +752,12 @@ class CapturedTick(CapturedStep):
         super().__init__(net, graph, static_in, static_out)
         self.static_heat = static_heat
 
-    def replay(self, frames=None, heat_override=None):
+    def replay(self, frames=None, heat_override=None, rig_pose=None):
         if heat_override is not None:
             if self.static_heat is None:
                 raise OkpError("this tick was captured without heat_override: it has no heat input")
             self.static_heat.copy_(heat_override)
-        return super().replay(frames)
+        return super().replay(frames, camera_pose=rig_pose)
 
 
 class BatchedKeypointPipeline:
@@ -727,11 +785,22 @@ class BatchedKeypointPipeline:
     objects() adds 'track_id' (None where the object went to no track), 'T_CO_track' (the filtered pose), 'velocity', 'track_hits' and
     'confirmed'; tracks(out, n) lists every live track of stream n, coasting ones included; reset_tracks() empties the tracker.  The tick's
     own "overflow" word is unchanged; "track"["overflow"] is that word | ops.TRACK_OVERFLOW.  Without track no launch, key or value differs.
+
+    World frame (optional): world_frame=True, for a camera that moves.  Every step then takes camera_pose, a float64 [N,12] tensor on the
+    frames' device (ops.frame_poses(T_WC).to(device): camera coordinates -> world, one pose per stream and tick; an all-NaN row = the pose of
+    that stream is missing in this tick), and its dict gains "world": {"T", "points" [N,K,cap,4] (out["points"] in the world frame),
+    "overflow" (the tick's word | ops.FRAME_MISSING)} and, with points_3d, "tab" and "pose" (out["pose"]'s in the world frame) - at most
+    three okp_change_frame launches, inside a captured step too.  With track the tracker runs on the world table and poses: gate, velocity and
+    coasting are world-frame quantities, out["track"] is in the world frame and gains "track_pose_C" [N,T,12], the filtered poses back in the
+    tick's camera frame.  objects() adds 'p_W' next to 'p_C', 'T_WO' and 'T_WO_track' ('T_CO_track' then comes from track_pose_C; all None
+    where the pose is missing); tracks() lists both.  out["points"], out["pose"] and every earlier key keep their bits.  Without world_frame
+    no launch, key or value differs, and a camera_pose is refused.
     """
 
     def __init__(self, net, keypoint_config, camera, prediction_size=(64, 64), capacity=DEFAULT_PEAK_CAPACITY,
-                 max_objects=16, max_per_type=4, points_3d=None, max_rmse=None, track=None):
+                 max_objects=16, max_per_type=4, points_3d=None, max_rmse=None, track=None, world_frame=False):
         self.net = net
+        self.world_frame = bool(world_frame)
         self.max_objects = max_objects
         self.max_per_type = max_per_type
         self.config = keypoint_config
@@ -766,7 +835,7 @@ class BatchedKeypointPipeline:
         (the index into objects(out, n) that updated or founded it in this step, or None)} - ONE device -> host copy."""
         if "track" not in out:
             raise OkpError("tracks reads the step of a pipeline built with track")
-        return _track_list(_host_tracks(out["track"], n), 'T_CO_track', self._tracker.cfg.min_hits)
+        return _track_list(_host_tracks(out["track"], n), 'T_CO_track', self._tracker.cfg.min_hits, 'T_WO_track')
 
     def _model(self, device):
         m = self._models.get(device)
@@ -774,24 +843,30 @@ class BatchedKeypointPipeline:
             m = self._models[device] = self._model_host.to(device)
         return m
 
-    def forward_device(self, frames):
+    def forward_device(self, frames, camera_pose=None):
         """Split-product configurations: the network's fp16-range flag is not read here (no host sync in the batch loop) but folded into
         `overflow` on the device (bit ops.RANGE_OVERFLOW), which objects() checks - except with on_overflow = "float32", where the pass has
         to be judged on the host before it can be re-run."""
+        _check_frame_pose(camera_pose, self.world_frame, frames.shape[0], frames.device, "camera_pose", "one T_WC per frame")
         defer = getattr(self.net, "on_overflow", "raise") != "float32"
         heat, depth, centers = self.net.deployed(frames, check_range=not defer)
-        return self.postprocess_device(heat, depth, centers, range_flag=self.net.range_flag(frames.device) if defer else None)
+        return self.postprocess_device(heat, depth, centers, range_flag=self.net.range_flag(frames.device) if defer else None, camera_pose=camera_pose)
 
-    def capture(self, frames):
+    def capture(self, frames, camera_pose=None):
         """Capture forward_device for this frame shape into a hipGraph (HIP stream capture through torch): the ~75
         launches of a step become one graph launch, which removes the host launch cost that dominates small
         batches (batch 8: 2.7 -> 2.2 ms per step).  Returns a CapturedStep; it also unpacks as
         (step, static_input, static_outputs): replay with step.replay(new_frames) or static_input.copy_(...); step.replay().
         With track: the graph steps the tracker's state of this batch size in place, the state eager steps of the same batch size use; the
-        warm-up passes and the capture advance it, so capture() ends with reset_tracks() - every track alive before it is gone."""
+        warm-up passes and the capture advance it, so capture() ends with reset_tracks() - every track alive before it is gone.
+        With world_frame: camera_pose is a static input of the graph like the frames - step.replay(frames, camera_pose=...) copies a new one
+        into step.static_pose before the replay."""
+        _check_frame_pose(camera_pose, self.world_frame, frames.shape[0], frames.device, "camera_pose", "one T_WC per frame")
         static_in = frames.clone()
-        graph, static_out = _capture(lambda: self.forward_device(static_in))
+        static_pose = camera_pose.clone() if camera_pose is not None else None
+        graph, static_out = _capture(lambda: self.forward_device(static_in, static_pose))
         step = CapturedStep(self.net, graph, static_in, static_out)
+        step.static_pose = static_pose
         if self._model_host is not None:                       # the graph reads the model on every replay: the step keeps the very tensor the
             step._model = self._model(static_out["pose"]["tab"].device)     # captured launch took, looked up by the device that launch ran on
         if self._tracker is not None:                          # (and the tracker's state, which it also writes)
@@ -799,9 +874,10 @@ class BatchedKeypointPipeline:
             self.reset_tracks()
         return step
 
-    def postprocess_device(self, heat, depth, centers, range_flag=None):
+    def postprocess_device(self, heat, depth, centers, range_flag=None, camera_pose=None):
         """Peaks, per-peak 3D points and the object grouping from (post-sigmoid) heat, depth and centre maps, all on
         the device: three small launches, nothing crosses PCIe."""
+        camera_pose = _check_frame_pose(camera_pose, self.world_frame, heat.shape[0], heat.device, "camera_pose", "one T_WC per frame")
         count, yx, xyc = ops.peak_nms(heat, cap=self.capacity)
         points = ops.lift_peaks(self.cam, count, xyc, depth, int(self.max_index[0]), int(self.max_index[1]))
         out = {"heat": heat, "depth": depth, "centers": centers, "count": count, "yx": yx, "xyc": xyc, "points": points}
@@ -815,8 +891,12 @@ class BatchedKeypointPipeline:
             cfg = self.config['keypoint_config']
             tab = ops.object_points(self.cam, out, cfg, int(self.max_index[0]), int(self.max_index[1]))
             out["pose"] = dict(ops.object_pose(tab, out["n_obj"], self._model(tab.device), cfg, self.max_rmse), tab=tab)
-            if self._tracker is not None:
+            if self._tracker is not None and camera_pose is None:
                 out["track"] = self._tracker.step(out["pose"], out["n_obj"], self._model(tab.device), out["overflow"])
+        if camera_pose is not None:
+            out["world"] = _world(camera_pose, points, out.get("pose"), out["overflow"])
+            if self._tracker is not None:
+                out["track"] = _track_world(self._tracker, out["world"], out["pose"], out["n_obj"], self._model(points.device))
         return out
 
     def objects(self, out, n):
@@ -858,28 +938,45 @@ class BatchedKeypointPipeline:
                 at += cfg[i]
         poses = _host_poses(out["pose"], n) if "pose" in out else None
         tracked = _host_tracks(out["track"], n) if "track" in out else None
+        in_world = "world" in out
+        if in_world:                                               # 'p_W' parallel to 'p_C': the device's world points, row for row
+            T_WC = out["world"]["T"][n].cpu().numpy().reshape(3, 4)
+            missing = not np.isfinite(T_WC).all()
+            pts3_w = out["world"]["points"][n].cpu().numpy()
+            poses_w = _host_poses(dict(out["pose"], pose=out["world"]["pose"]), n) if poses is not None else None
         objects = []
         for o in range(n_obj):
             keypoints = [xyc[0, o, :2].copy()[None]]
             world = [pts3[0, o, :3][None]]
+            p_W = [None if missing else pts3_w[0, o, :3][None]] if in_world else None
             for i in range(len(cfg)):
                 if (o, i) in centres:
                     keypoints.append(centres[(o, i)])
                     world.append(lifted[(o, i)])
+                    if in_world:                                   # lifted on the host just above: transformed here, by the same formula
+                        p_W.append(None if missing else np.stack([_frame_point(T_WC, p, False) for p in lifted[(o, i)]]))
                     continue
                 idx = [int(j) for j in sel[o, i] if j >= 0][:max(cfg[i], 1)]
                 if idx:
                     keypoints.append(xyc[i + 1, idx, :2].copy())
                     world.append(pts3[i + 1, idx, :3])
+                    if in_world:
+                        p_W.append(None if missing else pts3_w[i + 1, idx, :3])
                 else:
                     keypoints.append(np.array([]))
                     world.append(None)
+                    if in_world:
+                        p_W.append(None)
             p_centers = [pred[k, j] for k in range(1, count.shape[0]) for j in range(int(count[k])) if assign[k, j] == o]
             objects.append({'p_centers': p_centers, 'keypoints': keypoints, 'p_C': world})
+            if in_world:
+                objects[-1]['p_W'] = p_W
             if poses is not None:
                 objects[-1].update(_pose_entries(poses, o, 'T_CO'))
+                if in_world:
+                    objects[-1]['T_WO'] = None if missing else _pose_entries(poses_w, o, 'T_WO')['T_WO']
             if tracked is not None:
-                objects[-1].update(_track_entries(tracked, o, 'T_CO_track', self._tracker.cfg.min_hits))
+                objects[-1].update(_track_entries(tracked, o, 'T_CO_track', self._tracker.cfg.min_hits, 'T_WO_track'))
         return objects
 
     def objects_reference(self, out, n):
@@ -1048,11 +1145,22 @@ class StereoStreamPipeline:
     in the rig frame, inside the captured graph, after the gather on every rank with no further collective (every rank keeps the same
     tracker) - under the key "track" (ops.track_objects' outputs plus the state tensors); rig_objects(out) adds 'track_id', 'T_BO_track',
     'velocity', 'track_hits' and 'confirmed', rig_tracks(out) lists the live tracks, reset_tracks() empties the tracker.  The tick's
-    "overflow" word is unchanged; "track"["overflow"] carries ops.TRACK_OVERFLOW on top of it."""
+    "overflow" word is unchanged; "track"["overflow"] carries ops.TRACK_OVERFLOW on top of it.
+
+    World frame (optional, needs the fusion - the fused tick is what has ONE frame): world_frame=True, for a rig that moves.  tick_device,
+    capture_device / CapturedTick.replay and tick_sharded then take rig_pose, a float64 [1,12] tensor on the frames' device
+    (ops.frame_poses(T_WB).to(device): rig coordinates -> world; the same on every rank of a sharded tick; all NaN = missing in this tick).
+    It is applied after okp_rig_fuse: the dict gains "world": {"T", "points" [K,cap_f,4] (the fused clusters), "overflow" (the tick's word |
+    ops.FRAME_MISSING)} and, with points_3d, "tab" and "pose" - at most three okp_change_frame launches.  With track the tracker runs in the
+    world frame and out["track"] gains "track_pose_C", its poses back in the rig frame; rig_objects() adds 'T_WO' and 'T_WO_track' next to
+    'T_BO' and 'T_BO_track', rig_tracks() lists both.  Every earlier key keeps its bits; without world_frame a rig_pose is refused."""
 
     def __init__(self, net, stereo_camera, keypoint_config, capacity=16, max_distance=3.0, rig_poses=None, merge_radius=None, object_radius=None,
-                 fuse_capacity=None, points_3d=None, max_rmse=None, track=None):
+                 fuse_capacity=None, points_3d=None, max_rmse=None, track=None, world_frame=False):
         self.net = net
+        self.world_frame = bool(world_frame)
+        if self.world_frame and rig_poses is None:
+            raise OkpError("world_frame without rig_poses, merge_radius and object_radius: the fused tick is what has one frame to pose")
         self.rig = None if hasattr(stereo_camera, "left_camera") else list(stereo_camera)       # one StereoCamera, or a sequence of them
         self.stereo_cameras = self.rig if self.rig is not None else [stereo_camera]
         self._table_host = ops.stereo_rig(self.stereo_cameras)         # (refuses an empty rig)
@@ -1108,13 +1216,25 @@ class StereoStreamPipeline:
         """The tracker stepped by a fused tick's poses: one launch behind okp_object_pose."""
         return self._tracker.step(out["pose"], out["fused"]["n_obj"], self._model(out["pose"]["tab"].device), out["fused"]["overflow"])
 
+    def _finish(self, out, rig_pose):
+        """What follows okp_rig_fuse in a fused device tick: the pose, the world frame, the tracker (in the world frame where there is one)."""
+        if self._model_host is not None:
+            out["pose"] = self._pose(out["fused"])
+        if rig_pose is not None:
+            out["world"] = _world(rig_pose, out["fused"]["fused"], out.get("pose"), out["fused"]["overflow"])
+        if self._tracker is not None:
+            if rig_pose is None:
+                out["track"] = self._track(out)
+            else:
+                out["track"] = _track_world(self._tracker, out["world"], out["pose"], out["fused"]["n_obj"], self._model(out["pose"]["tab"].device))
+
     def rig_tracks(self, out):
         """Every live track after the fused tick `out`, coasting ones included, in slot order: a list of {'track_id', 'T_BO_track' (4 x 4,
         model -> rig coordinates, filtered), 'velocity' (m/s), 'hits', 'misses', 'age', 'confirmed', 'object' (the index into
         rig_objects(out), or None)} - ONE device -> host copy."""
         if not isinstance(out, dict) or "track" not in out:
             raise OkpError("rig_tracks reads the fused device tick of a pipeline built with track")
-        return _track_list(_host_tracks(out["track"], 0), 'T_BO_track', self._tracker.cfg.min_hits)
+        return _track_list(_host_tracks(out["track"], 0), 'T_BO_track', self._tracker.cfg.min_hits, 'T_WO_track')
 
     def _check_fused_tick(self, n_pairs, first_pair=0):
         """A fused tick holds every pair of the rig: the clusters are formed across all of them."""
@@ -1248,7 +1368,7 @@ class StereoStreamPipeline:
             raise OkpError(f"capacity = {self.capacity}: the device association holds at most {ops.STEREO_MAX_CAPACITY} peaks per map")
         return self._check_rig_frames(frames, first_pair)
 
-    def tick_device(self, frames, heat_override=None, first_pair=0, _fuse=True):
+    def tick_device(self, frames, heat_override=None, first_pair=0, _fuse=True, rig_pose=None):
         """The whole tick on the device, with no host wait anywhere: network -> peak-NMS -> left/right association (okp_stereo_match) ->
         triangulation of every matched slot (okp_stereo_triangulate).  Same frames as tick().  Returns a dict of device tensors
             heat, depth [2P,K,H,W], count [2P,K] int32, xyc [2P,K,cap,3] fp32, match [P,K,cap] int32,
@@ -1262,6 +1382,8 @@ class StereoStreamPipeline:
         fuse = _fuse and self._poses_host is not None           # (tick_sharded fuses after the gather instead)
         if fuse:
             self._check_fused_tick(frames.shape[0] // 2, first_pair)
+        if _fuse:
+            rig_pose = _check_frame_pose(rig_pose, self.world_frame, 1, frames.device, "rig_pose", "the one T_WB of the tick")
         with torch.no_grad():
             # split-product networks: the fp16-range flag is folded into `overflow` on the device instead of being read here (as
             # BatchedKeypointPipeline.forward_device does), except with on_overflow = "float32", where the pass is judged on the host
@@ -1278,26 +1400,27 @@ class StereoStreamPipeline:
             if fuse:
                 out["fused"] = self._fuse(points, overflow)
                 out["overflow"] = out["fused"]["overflow"]
-                if self._model_host is not None:
-                    out["pose"] = self._pose(out["fused"])
-                    if self._tracker is not None:
-                        out["track"] = self._track(out)
+                self._finish(out, rig_pose)
         return out
 
-    def capture_device(self, frames, heat_override=None, first_pair=0):
+    def capture_device(self, frames, heat_override=None, first_pair=0, rig_pose=None):
         """Capture the WHOLE tick_device (network, NMS, association, triangulation, overflow word) for this frame shape into one hipGraph;
         that the capture succeeds is itself the check that nothing in the tick waits on the host.  Returns a CapturedTick: replay with
         step.replay(new_frames[, new_heat]) or by copying into step.static_in / step.static_heat (heat_override, when given, is a static
         input of the graph like the frames) and step.replay(); the outputs are step.static_out (tick_device's dict).  first_pair: as for
         tick_device; the warm-up ticks upload the calibration table before the capture begins.  With track: the graph steps the tracker's
         state in place, the state eager ticks use; the warm-up ticks and the capture advance it, so capture_device() ends with
-        reset_tracks() - every track alive before it is gone."""
+        reset_tracks() - every track alive before it is gone.  With world_frame: rig_pose is a static input of the graph as well -
+        step.replay(frames, rig_pose=...) copies a new one into step.static_pose before the replay."""
         first_pair = self._check_device_tick(frames, first_pair)
         self._check_fused_tick(frames.shape[0] // 2, first_pair)
+        _check_frame_pose(rig_pose, self.world_frame, 1, frames.device, "rig_pose", "the one T_WB of the tick")
         static_in = frames.clone()
         static_heat = heat_override.clone() if heat_override is not None else None
-        graph, static_out = _capture(lambda: self.tick_device(static_in, heat_override=static_heat, first_pair=first_pair))
+        static_pose = rig_pose.clone() if rig_pose is not None else None
+        graph, static_out = _capture(lambda: self.tick_device(static_in, heat_override=static_heat, first_pair=first_pair, rig_pose=static_pose))
         step = CapturedTick(self.net, graph, static_in, static_out, static_heat)
+        step.static_pose = static_pose
         step._table = self._table(frames.device)               # (the graph reads it on every replay)
         step._poses = self._poses.get(frames.device) if self._poses_host is not None else None       # (and the pose table)
         if self._model_host is not None and "pose" in static_out:       # (and the object model: the tensor the captured launch took)
@@ -1324,7 +1447,7 @@ class StereoStreamPipeline:
             result.append(per)
         return result
 
-    def tick_sharded(self, frames_local, n_pairs_total, heat_override=None):
+    def tick_sharded(self, frames_local, n_pairs_total, heat_override=None, rig_pose=None):
         """The rig's pairs sharded over the ranks of the process group (both views of a pair on one GPU): this rank holds the frames of
         pairs distributed.shard(n_pairs_total, rank, world) (2 per pair, left first).  Runs tick_device on them and returns
             {"points": [n_pairs_total, K, cap, 4] fp64 - ONE all_gather_keypoints of the per-rank payloads, ordered by pair,
@@ -1343,17 +1466,15 @@ class StereoStreamPipeline:
         self._check_device_tick(frames_local)
         if self._poses_host is not None and int(n_pairs_total) != self.n_fused_pairs:
             raise OkpError(f"n_pairs_total = {n_pairs_total}, but {self.n_fused_pairs} rig poses were given")
+        rig_pose = _check_frame_pose(rig_pose, self.world_frame, 1, frames_local.device, "rig_pose", "the one T_WB of the tick, the same on every rank")
         if not dist.is_initialized():
             if frames_local.shape[0] != 2 * n_pairs_total:
                 raise OkpError(f"{frames_local.shape[0]} frames for {n_pairs_total} stereo pairs")
-            out = self.tick_device(frames_local, heat_override=heat_override)
+            out = self.tick_device(frames_local, heat_override=heat_override, rig_pose=rig_pose)
             whole = {"points": out["points"], "overflow": out["overflow"], "local": out}
-            if "fused" in out:
-                whole["fused"] = out["fused"]
-            if "pose" in out:
-                whole["pose"] = out["pose"]
-            if "track" in out:
-                whole["track"] = out["track"]
+            for key in ("fused", "pose", "world", "track"):
+                if key in out:
+                    whole[key] = out[key]
             return whole
         start, n_local = distributed.shard(int(n_pairs_total), dist.get_rank(), dist.get_world_size())
         if frames_local.shape[0] != 2 * n_local:
@@ -1372,10 +1493,7 @@ class StereoStreamPipeline:
         if self._poses_host is not None:
             with torch.no_grad():
                 out["fused"] = self._fuse(gathered, flag)
-                if self._model_host is not None:
-                    out["pose"] = self._pose(out["fused"])
-                    if self._tracker is not None:
-                        out["track"] = self._track(out)
+                self._finish(out, rig_pose)
             out["overflow"] = out["fused"]["overflow"]
         return out
 
@@ -1405,6 +1523,10 @@ class StereoStreamPipeline:
             n_slots = tr["meas_of"].shape[1]
             tail += [tr["track_pose"].reshape(-1), tr["track_f"].reshape(-1), tr["track_i"].reshape(-1).to(torch.float64), tr["track_of"].reshape(-1).to(torch.float64),
                      tr["meas_of"].reshape(-1).to(torch.float64)]
+        in_world = "world" in out                                  # (behind everything else: the offsets above it are today's)
+        if in_world:
+            tail += [out["world"]["T"].reshape(-1)] + ([out["world"]["pose"].reshape(-1)] if "pose" in out else []) + \
+                    ([out["track"]["track_pose_C"].reshape(-1)] if "track" in out else [])
         flat = torch.cat([t.to(torch.float64) for t in parts] + tail).cpu().numpy()          # the one D2H copy (int32 is exact in fp64)
         _raise_on_overflow(int(flat[0]), fused=True)
         n_obj = int(flat[1])
@@ -1422,7 +1544,14 @@ class StereoStreamPipeline:
             rest = rest[15 * cap_f:]
             a, b, c, d = 12 * n_slots, 28 * n_slots, 32 * n_slots, 32 * n_slots + cap_f
             tracked = (rest[:a].reshape(n_slots, 12), rest[a:b].reshape(n_slots, 16), rest[b:c].astype(np.int64).reshape(n_slots, 4), rest[c:d].astype(np.int64),
-                       rest[d:].astype(np.int64))
+                       rest[d:d + n_slots].astype(np.int64), None)
+        if in_world:
+            w = flat[-(12 + (12 * cap_f if poses is not None else 0) + (12 * n_slots if tracked is not None else 0)):]
+            missing = not np.isfinite(w[:12]).all()
+            if poses is not None:
+                poses_w = (w[12:12 + 12 * cap_f].reshape(cap_f, 12),) + poses[1:]
+            if tracked is not None:
+                tracked = tracked[:5] + (w[len(w) - 12 * n_slots:].reshape(n_slots, 12),)
         objects = []
         for o in range(n_obj):
             p_B, conf, seen = [], [], []
@@ -1434,6 +1563,8 @@ class StereoStreamPipeline:
             objects.append({"p_B": p_B, "confidence": conf, "views": seen})
             if poses is not None:
                 objects[-1].update(_pose_entries(poses, o, "T_BO"))
+                if in_world:
+                    objects[-1]["T_WO"] = None if missing else _pose_entries(poses_w, o, "T_WO")["T_WO"]
             if tracked is not None:
-                objects[-1].update(_track_entries(tracked, o, "T_BO_track", self._tracker.cfg.min_hits))
+                objects[-1].update(_track_entries(tracked, o, "T_BO_track", self._tracker.cfg.min_hits, "T_WO_track"))
         return objects
