@@ -41,7 +41,8 @@ extern "C" {
                                     okp_rig_fuse (a rig's stereo pairs fused into one object list in the rig frame);
                                     okp_object_points, okp_rig_object_points, okp_object_pose (each object's 6-DoF pose from its 3D key points);
                                     okp_track_objects, OKP_TRACK_* (objects tracked across ticks: stable ids, filtered poses);
-                                    okp_change_frame, OKP_FRAME_MISSING (points, tables and poses in a fixed world frame under a moving camera) */
+                                    okp_change_frame, OKP_FRAME_MISSING (points, tables and poses in a fixed world frame under a moving camera);
+                                    okp_refine_pose, OKP_REFINE_* (each object's pose refined against its key points' bearings) */
 
 /* OKP_F16: IEEE half activations / weights, fp32 accumulate (BASELINE configs[4]).
  * OKP_F32X3 (okp_conv plans only): fp32 activations, weights and results like OKP_F32 - every tensor argument of such a plan is an
@@ -728,6 +729,71 @@ int okp_track_objects(const double* tab_dev, const double* pose_dev, const int32
 int okp_change_frame(const double* T_dev, int32_t B, int inverse, const double* points_in_dev, int32_t n_points, double* points_out_dev,
                      const double* pose_in_dev, int32_t n_pose, double* pose_out_dev, const int32_t* overflow_in_dev, int32_t* overflow_dev,
                      void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * Pose refinement (csrc/okp_refine.hip): okp_object_pose fits a rigid transform to key points that were lifted to 3D through the depth
+ * head, and weights the three coordinates of a lifted point equally - yet the depth of a key point is good to centimetres at a metre while
+ * its pixel is good to a fraction of a map pixel, a millimetre or two at that range.  This stage takes the fitted pose as the start and
+ * minimises the reprojection error of the same point pairs, with the measured depth as a weak prior.  The reference solves a PnP on the
+ * host (notebooks/keypoint_debug.ipynb).  There is no reference implementation: the specification is this comment (tests/refine_spec.py
+ * restates it in NumPy).
+ *
+ * okp_refine_pose: one launch, sixteen lanes per object, fp64, no atomics, no host wait, capturable; the same bits on every run.
+ * Inputs, all in device memory and all outputs of the pose stage:
+ *   tab [B][max_obj][S][4] fp64, pose [B][max_obj][12] fp64, assignment [B][max_obj][S] int32, n_obj [B] int32, model [S][3] fp64.
+ * Host arguments: cam (only fx and fy are read: the table's points are already undistorted), sigma_px (map pixels), sigma_z (metres;
+ *   +infinity: no depth term), iters, damping (mu), B, max_obj, S.
+ * The table holds the bearings: okp_lift_pixel writes X = K^-1 [xu, yu, 1] z, so u = X/Z and v = Y/Z are the undistorted normalised image
+ * coordinates of the key point and Z its measured depth.
+ * Per object o < min(n_obj[b], max_obj).  The point pairs are the slots s with 0 <= assignment[s] < S (any other value: no pair); pair i has
+ * the model point m_i = model[assignment[s]] and (u_i, v_i, Z_i) from tab[s].
+ *   Cost.  With p_i = R m_i and q_i = p_i + t:
+ *     e_u = fx (q_x/q_z - u_i) / sigma_px,  e_v = fy (q_y/q_z - v_i) / sigma_px,  e_z = (q_z - Z_i) / sigma_z  (0 for an infinite sigma_z)
+ *     J(R, t) = sum_i (e_u^2 + e_v^2 + e_z^2)
+ *   One step.  The 6 parameters are (w, d): R <- C(w) R, t <- t + d.  The Jacobian rows follow from dq_i/dw = -[p_i]x and dq_i/dd = I:
+ *     a row is (p_i x a, a) with a = de/dq:  a_u = (fx/sigma_px) (1/q_z, 0, -q_x/q_z^2),  a_v = (fy/sigma_px) (0, 1/q_z, -q_y/q_z^2),
+ *     a_z = (0, 0, 1/sigma_z).  H = sum j^T j (6 x 6), g = sum j^T e.  (H + mu diag H) x = -g is solved by Cholesky (lower triangle,
+ *     column by column; pivot c = H_cc + mu H_cc - sum_{q<c} L_cq^2), x = (w, d).
+ *     C(w) is the rotation matrix of the unit quaternion (1, w/2) / |(1, w/2)|, written out in products, sums, one division and one square
+ *     root: no trigonometric function is evaluated anywhere in the stage.  R is not re-orthonormalised: C is orthonormal to rounding.
+ *   Iteration.  Exactly `iters` steps from the input pose; no line search, no early exit.  The cost, H and g are then evaluated once more
+ *     at the final iterate.
+ *   Status, the first of these to occur in the order of evaluation (0 when none does):
+ *     OKP_REFINE_SKIPPED   before the first step: one of the 12 values of the input pose is not finite, fewer than 3 pairs, or a pair with
+ *                          Z = 0 or a non-finite u or v
+ *     OKP_REFINE_BEHIND    q_z <= 0 for some pair at an iterate (the start, every intermediate one and the final one; tested before that
+ *                          iterate's solve)
+ *     OKP_REFINE_SINGULAR  a Cholesky pivot that is <= 1e-12 x its diagonal entry of H (the undamped H_cc), or not finite
+ *     OKP_REFINE_REJECTED  after the last step: J_final is not finite, or J_final > J_initial + 1e-12 x pairs
+ *   Outputs, all written by every call:
+ *     pose_out [B][max_obj][12] fp64     row-major [R | t] at the final iterate; for ANY non-zero status the input pose copied bit for bit
+ *                                        (NaN poses and poses with OKP_POSE_POOR included)
+ *     fit [B][max_obj][4] fp64           sqrt(sum_i ((fx (q_x/q_z - u_i))^2 + (fy (q_y/q_z - v_i))^2) / pairs) at the input pose and at the
+ *                                        final iterate (map pixels), then sqrt(sum_i (q_z - Z_i)^2 / pairs) at the two (metres; measured
+ *                                        also when sigma_z is infinite); NaN for a non-zero status
+ *     information [B][max_obj][36] fp64  H at the final iterate, undamped, row-major 6 x 6 and exactly symmetric, in the parameter order
+ *                                        (w, d) - the inverse covariance of the refined pose under the two sigmas, what a filter that
+ *                                        consumes the pose needs; the device does not invert it.  NaN for a non-zero status
+ *     status [B][max_obj] int32
+ *   Objects from n_obj[b] on follow the pose stage's convention: NaN pose_out, fit and information, status OKP_REFINE_SKIPPED.
+ *   The order in which the sums over the pairs are formed and products are associated is not part of the contract: the device adds the
+ *   pairs' terms in a fixed butterfly (the same bits on every run and from every binding) and agrees with a NumPy evaluation to rounding
+ *   (tests/test_gpu_refine.py: 1e-9 on R and t).  pose_out must not overlap pose.
+ * Limits.  Uniform weights: the confidences of the table are not used.  A symmetric model's assignment is taken from okp_object_pose as it
+ * is.  The points of a rig (okp_rig_object_points) come from stereo triangulation, not from one camera's bearings: they are not refined.
+ * Refused on the host before any launch (OKP_EINVAL, the message names the argument): a null pointer, B or max_obj < 1, S outside
+ * [1, OKP_POSE_MAX_POINTS], iters outside [1, OKP_REFINE_MAX_ITERS], sigma_px not positive and finite, sigma_z not positive (NaN included),
+ * damping negative or not finite, cam->fx or cam->fy not positive and finite.
+ * ---------------------------------------------------------------------------------- */
+#define OKP_REFINE_MAX_ITERS 16
+#define OKP_REFINE_SKIPPED 1
+#define OKP_REFINE_SINGULAR 2
+#define OKP_REFINE_BEHIND 4
+#define OKP_REFINE_REJECTED 8
+int okp_refine_pose(const double* tab_dev, const double* pose_dev, const int32_t* assignment_dev, const int32_t* n_obj_dev,
+                    const double* model_dev, const okp_camera* cam, double sigma_px, double sigma_z, int32_t iters, double damping, int32_t B,
+                    int32_t max_obj, int32_t S, double* pose_out_dev, double* fit_dev, double* information_dev, int32_t* status_dev,
+                    void* stream);
 
 /* Undistort only (FisheyeCamera.undistort, camera_utils.py:75-81 / RadTanPinholeCamera.undistort, :57-62, by cam->model):
  * xy [m][2] fp32 -> out [m][2] fp64.  okp_fisheye_undistort is the same entry point under its round-1 name. */

@@ -355,6 +355,14 @@ def change_frame(T, inverse, points, out_points, poses, out_poses, overflow, str
                "okp_change_frame")
 
 
+# ---- pose refinement (csrc/okp_refine.hip): tab [B,max_obj,S,4], pose [B,max_obj,12], assignment [B,max_obj,S] ------------------------------------
+def refine_pose(camera, tab, pose, assignment, n_obj, model, sigma_px, sigma_z, iters, damping, pose_out, fit, information, status, stream):
+    b, max_obj, s, _ = tab.shape
+    _lib.check(_lib.lib().okp_refine_pose(tab.data_ptr(), pose.data_ptr(), assignment.data_ptr(), n_obj.data_ptr(), model.data_ptr(), _camera(camera), sigma_px, sigma_z,
+                                          iters, damping, b, max_obj, s, pose_out.data_ptr(), fit.data_ptr(), information.data_ptr(), status.data_ptr(), stream),
+               "okp_refine_pose")
+
+
 # ---- scoring labelled scenes -----------------------------------------------------------------------------------------------------------------
 def project_labels(camera, world_points, T_WC, scale, crop_x, crop_y, labels, stream):
     _lib.check(_lib.lib().okp_project_labels(_camera(camera), world_points.data_ptr(), world_points.shape[0], T_WC.data_ptr(), T_WC.shape[0], scale, crop_x, crop_y,

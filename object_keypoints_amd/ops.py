@@ -1410,6 +1410,84 @@ def change_frame(T, points=None, poses=None, inverse=False, overflow=None, out_p
     return {"points": out_points, "poses": out_poses, "overflow": word[0]}
 
 
+# ---- each object's pose refined against its key points' bearings (okp_refine_pose, csrc/okp_refine.hip; the specification is include/okp.h) ----
+REFINE_SKIPPED, REFINE_SINGULAR, REFINE_BEHIND, REFINE_REJECTED = 1, 2, 4, 8      # status words of refine_pose()
+REFINE_MAX_ITERS = 16                                                            # include/okp.h OKP_REFINE_MAX_ITERS
+
+
+class RefineConfig:
+    """The parameters of the pose refinement (okp_refine_pose), validated here - an OkpError names the field:
+        sigma_px  map pixels: the standard deviation of a key point's pixel position (positive, finite)
+        sigma_z   metres: the standard deviation of a key point's measured depth (positive; inf: the depth is not used at all)
+        iters     Gauss-Newton steps, 1 .. REFINE_MAX_ITERS: always exactly this many
+        damping   mu >= 0 of (H + mu diag H) d = -g."""
+
+    def __init__(self, sigma_px=0.25, sigma_z=0.05, iters=6, damping=1e-9):
+        def number(name, v):
+            if isinstance(v, bool):
+                raise OkpError(f"RefineConfig: {name} = {v!r} is not a number")
+            try:
+                return float(v)
+            except (TypeError, ValueError):
+                raise OkpError(f"RefineConfig: {name} = {v!r} is not a number") from None
+
+        self.sigma_px, self.sigma_z, self.damping = number("sigma_px", sigma_px), number("sigma_z", sigma_z), number("damping", damping)
+        if not (self.sigma_px > 0.0 and np.isfinite(self.sigma_px)):
+            raise OkpError(f"RefineConfig: sigma_px = {sigma_px!r} must be positive and finite (map pixels)")
+        if not self.sigma_z > 0.0:
+            raise OkpError(f"RefineConfig: sigma_z = {sigma_z!r} must be positive (metres; inf: no depth term)")
+        if not (self.damping >= 0.0 and np.isfinite(self.damping)):
+            raise OkpError(f"RefineConfig: damping = {damping!r} must be finite and not negative")
+        if isinstance(iters, bool) or not isinstance(iters, (int, np.integer)) or not 1 <= int(iters) <= REFINE_MAX_ITERS:
+            raise OkpError(f"RefineConfig: iters = {iters!r}: an integer in [1, {REFINE_MAX_ITERS}]")
+        self.iters = int(iters)
+
+    def __repr__(self):
+        return f"RefineConfig(sigma_px={self.sigma_px}, sigma_z={self.sigma_z}, iters={self.iters}, damping={self.damping})"
+
+
+def refine_pose(tab, pose, n_obj, model, cam, cfg):
+    """Every object's fitted pose refined against the bearings of its key points (okp_refine_pose; cost, step, statuses and outputs are
+    specified in include/okp.h).  tab [B,max_obj,S,4] float64 (object_points); pose: object_pose()'s dict (its "pose" [B,max_obj,12] and
+    "assignment" [B,max_obj,S] are read); n_obj int32 [B] (0-d for B = 1); model [S,3] float64 (device); cam: the okp_camera the table was
+    lifted through (only fx and fy are read); cfg: a RefineConfig
+    -> {"pose" [B,max_obj,12] float64 (the refined [R | t]; the input pose bit for bit where the status is not 0), "fit" [B,max_obj,4]
+        float64 (reprojection rmse in map pixels before and after, depth rmse in metres before and after; NaN where the status is not 0),
+        "information" [B,max_obj,36] float64 (H = J^T J at the refined pose, row-major 6 x 6 over (rotation, translation): the inverse
+        covariance under the two sigmas; NaN where the status is not 0), "status" [B,max_obj] int32 (0, REFINE_SKIPPED, REFINE_SINGULAR,
+        REFINE_BEHIND or REFINE_REJECTED)}.  One launch, no host sync."""
+    if not isinstance(cfg, RefineConfig):
+        raise OkpError("cfg must be an ops.RefineConfig")
+    if not isinstance(cam, _lib.okp_camera):
+        raise OkpError(f"cam must be an okp_camera (make_camera), not {type(cam).__name__}")
+    try:
+        fitted, assignment = pose["pose"], pose["assignment"]
+    except (TypeError, KeyError, IndexError):
+        raise OkpError("pose must be the dict of ops.object_pose (its \"pose\" and \"assignment\")") from None
+    for name, t in (("tab", tab), ("pose", fitted), ("assignment", assignment), ("n_obj", n_obj), ("model", model)):
+        require_cuda(t, name)
+    if tab.dtype != torch.float64 or tab.dim() != 4 or tab.shape[3] != 4:
+        raise OkpError("tab must be float64 [B,max_obj,S,4] (object_points)")
+    b, max_obj, s = (int(v) for v in tab.shape[:3])
+    dev = tab.device
+    if not 1 <= s <= POSE_MAX_POINTS:
+        raise OkpError(f"tab [{b},{max_obj},{s},4]: at most {POSE_MAX_POINTS} model points")
+    if fitted.dtype != torch.float64 or tuple(fitted.shape) != (b, max_obj, 12) or assignment.dtype != torch.int32 or tuple(assignment.shape) != (b, max_obj, s) or \
+            fitted.device != dev or assignment.device != dev:
+        raise OkpError(f"pose must be float64 [{b},{max_obj},12] and assignment int32 [{b},{max_obj},{s}] on the table's device (object_pose)")
+    if n_obj.dtype != torch.int32 or n_obj.numel() != b or n_obj.device != dev:
+        raise OkpError(f"n_obj must be int32 [{b}] on the table's device: the objects of each frame")
+    if model.dtype != torch.float64 or tuple(model.shape) != (s, 3) or model.device != dev:
+        raise OkpError(f"model must be float64 [{s},3] on the table's device (object_model)")
+    pose_out = torch.empty((b, max_obj, 12), dtype=torch.float64, device=dev)
+    fit = torch.empty((b, max_obj, 4), dtype=torch.float64, device=dev)
+    information = torch.empty((b, max_obj, 36), dtype=torch.float64, device=dev)
+    status = torch.empty((b, max_obj), dtype=torch.int32, device=dev)
+    _dispatch(_ops().refine_pose, _cam_list(cam), tab.contiguous(), fitted.contiguous(), assignment.contiguous(), n_obj.reshape(b).contiguous(), model.contiguous(),
+              cfg.sigma_px, cfg.sigma_z, cfg.iters, cfg.damping, pose_out, fit, information, status, stream_int())
+    return {"pose": pose_out, "fit": fit, "information": information, "status": status}
+
+
 # ---- scoring labelled scenes (csrc/okp_targets.hip) ---------------------------------------------------------------------------------
 TARGET_SIZE = 64             # SceneDataset.prediction_size
 TARGET_MAX_MAPS = 16         # K

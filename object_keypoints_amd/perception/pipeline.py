@@ -566,16 +566,35 @@ def _live_plans(net):
     return found
 
 
-def _host_poses(pose, n):
-    """Frame n of an ops.object_pose dict on the host, in ONE device -> host copy: (pose [max_obj,12], fit [max_obj,2], status [max_obj])."""
+def _host_poses(pose, n, refine=None):
+    """Frame n of an ops.object_pose dict on the host, in ONE device -> host copy: (pose [max_obj,12], fit [max_obj,2], status [max_obj]);
+    with an ops.refine_pose dict the same copy also carries (refined pose [max_obj,12], fit [max_obj,4], information [max_obj,6,6], status)."""
     max_obj = pose["status"].shape[1]
-    flat = torch.cat([pose["pose"][n].reshape(-1), pose["fit"][n].reshape(-1), pose["status"][n].to(torch.float64)]).cpu().numpy()
-    return flat[:12 * max_obj].reshape(max_obj, 12), flat[12 * max_obj:14 * max_obj].reshape(max_obj, 2), flat[14 * max_obj:].astype(np.int64)
+    more = [refine["pose"][n].reshape(-1), refine["fit"][n].reshape(-1), refine["information"][n].reshape(-1), refine["status"][n].to(torch.float64)] if refine is not None else []
+    flat = torch.cat([pose["pose"][n].reshape(-1), pose["fit"][n].reshape(-1), pose["status"][n].to(torch.float64)] + more).cpu().numpy()
+    host = (flat[:12 * max_obj].reshape(max_obj, 12), flat[12 * max_obj:14 * max_obj].reshape(max_obj, 2), flat[14 * max_obj:15 * max_obj].astype(np.int64))
+    if refine is None:
+        return host
+    r = flat[15 * max_obj:]
+    return host + (r[:12 * max_obj].reshape(max_obj, 12), r[12 * max_obj:16 * max_obj].reshape(max_obj, 4), r[16 * max_obj:52 * max_obj].reshape(max_obj, 6, 6),
+                   r[52 * max_obj:].astype(np.int64))
+
+
+def _refine_entries(poses, o, T_CO):
+    """Object o's refined pose as the entries objects() adds: 'T_CO_refined' (None where 'T_CO' is; the fitted pose where the refinement's
+    status is not 0), 'reprojection_rmse' and 'depth_rmse' (before, after), 'pose_information' (6 x 6) and 'refine_status'."""
+    pose, fit, information, status = poses[3:]
+    T = None
+    if T_CO is not None:
+        T = np.eye(4)
+        T[:3] = pose[o].reshape(3, 4)
+    return {'T_CO_refined': T, 'reprojection_rmse': (float(fit[o, 0]), float(fit[o, 1])), 'depth_rmse': (float(fit[o, 2]), float(fit[o, 3])),
+            'pose_information': information[o].copy(), 'refine_status': int(status[o])}
 
 
 def _pose_entries(poses, o, key):
     """Object o's pose as the entries objects() / rig_objects() add: the 4 x 4 transform under `key` (None where the status refuses a pose)."""
-    pose, fit, status = poses
+    pose, fit, status = poses[:3]
     T = None
     if not int(status[o]) & (ops.POSE_FEW | ops.POSE_DEGENERATE):
         T = np.eye(4)
@@ -795,10 +814,21 @@ class BatchedKeypointPipeline:
     tick's camera frame.  objects() adds 'p_W' next to 'p_C', 'T_WO' and 'T_WO_track' ('T_CO_track' then comes from track_pose_C; all None
     where the pose is missing); tracks() lists both.  out["points"], out["pose"] and every earlier key keep their bits.  Without world_frame
     no launch, key or value differs, and a camera_pose is refused.
+
+    Refinement (optional, needs the pose): refine = ops.RefineConfig(...).  The fitted pose rests on key points lifted through the depth
+    head, the weakest measurement of the step; the device step then gains one launch after okp_object_pose (okp_refine_pose, inside a
+    captured step too) that minimises the reprojection error of the same key points' bearings with the depth as a weak prior, and its dict
+    gains "refine": {"pose" [N,max_objects,12], "fit" [N,max_objects,4], "information" [N,max_objects,36], "status"} (ops.refine_pose).
+    out["pose"] and every earlier key keep their bits; the world-frame change and the tracker are fed the refined pose - the fitted one
+    where the refinement's status is not 0 - so 'T_WO', 'T_CO_track', 'T_WO_track' and 'velocity' come from it.  objects() adds
+    'T_CO_refined' (None where 'T_CO' is), 'reprojection_rmse' and 'depth_rmse' ((before, after): map pixels, metres), 'pose_information'
+    (6 x 6, the inverse covariance over (rotation, translation)) and 'refine_status', still in one device -> host copy.  Without refine no
+    launch, key or value differs.  The fused rig tick (StereoStreamPipeline) has no such stage: its points come from stereo triangulation,
+    not from one camera's bearings.
     """
 
     def __init__(self, net, keypoint_config, camera, prediction_size=(64, 64), capacity=DEFAULT_PEAK_CAPACITY,
-                 max_objects=16, max_per_type=4, points_3d=None, max_rmse=None, track=None, world_frame=False):
+                 max_objects=16, max_per_type=4, points_3d=None, max_rmse=None, track=None, world_frame=False, refine=None):
         self.net = net
         self.world_frame = bool(world_frame)
         self.max_objects = max_objects
@@ -822,6 +852,12 @@ class BatchedKeypointPipeline:
                 raise OkpError(f"a keypoint type has {max(cfg)} instances, above max_per_type = {max_per_type}")
         track = _check_track(track, points_3d is not None, max_objects, "max_objects")
         self._tracker = _Tracker(track) if track is not None else None
+        if refine is not None:
+            if not isinstance(refine, ops.RefineConfig):
+                raise OkpError("refine must be an ops.RefineConfig")
+            if points_3d is None:
+                raise OkpError("refine without points_3d: the refinement starts from the pose of the object model")
+        self.refine = refine
 
     def reset_tracks(self):
         """Empty the tracker: its state tensors are zeroed in place on the current stream, so a captured step keeps working."""
@@ -891,12 +927,16 @@ class BatchedKeypointPipeline:
             cfg = self.config['keypoint_config']
             tab = ops.object_points(self.cam, out, cfg, int(self.max_index[0]), int(self.max_index[1]))
             out["pose"] = dict(ops.object_pose(tab, out["n_obj"], self._model(tab.device), cfg, self.max_rmse), tab=tab)
+            fed = out["pose"]                                      # what the world-frame change and the tracker take: the refined pose when there is one
+            if self.refine is not None:
+                out["refine"] = ops.refine_pose(tab, out["pose"], out["n_obj"], self._model(tab.device), self.cam, self.refine)
+                fed = dict(out["pose"], pose=out["refine"]["pose"])
             if self._tracker is not None and camera_pose is None:
-                out["track"] = self._tracker.step(out["pose"], out["n_obj"], self._model(tab.device), out["overflow"])
+                out["track"] = self._tracker.step(fed, out["n_obj"], self._model(tab.device), out["overflow"])
         if camera_pose is not None:
-            out["world"] = _world(camera_pose, points, out.get("pose"), out["overflow"])
+            out["world"] = _world(camera_pose, points, fed if self._model_host is not None else None, out["overflow"])
             if self._tracker is not None:
-                out["track"] = _track_world(self._tracker, out["world"], out["pose"], out["n_obj"], self._model(points.device))
+                out["track"] = _track_world(self._tracker, out["world"], fed, out["n_obj"], self._model(points.device))
         return out
 
     def objects(self, out, n):
@@ -936,7 +976,7 @@ class BatchedKeypointPipeline:
             for o, i in surplus:
                 lifted[(o, i)] = world[at:at + cfg[i]]
                 at += cfg[i]
-        poses = _host_poses(out["pose"], n) if "pose" in out else None
+        poses = _host_poses(out["pose"], n, out.get("refine")) if "pose" in out else None
         tracked = _host_tracks(out["track"], n) if "track" in out else None
         in_world = "world" in out
         if in_world:                                               # 'p_W' parallel to 'p_C': the device's world points, row for row
@@ -973,6 +1013,8 @@ class BatchedKeypointPipeline:
                 objects[-1]['p_W'] = p_W
             if poses is not None:
                 objects[-1].update(_pose_entries(poses, o, 'T_CO'))
+                if len(poses) > 3:
+                    objects[-1].update(_refine_entries(poses, o, objects[-1]['T_CO']))
                 if in_world:
                     objects[-1]['T_WO'] = None if missing else _pose_entries(poses_w, o, 'T_WO')['T_WO']
             if tracked is not None:
@@ -1139,7 +1181,8 @@ class StereoStreamPipeline:
     Pose (optional, needs the fusion): points_3d = the object model as for BatchedKeypointPipeline, max_rmse optional.  The fused device
     ticks then end with okp_rig_object_points and okp_object_pose - the pose of every fused object in the RIG frame, inside the captured
     graph, after the gather on every rank - under the key "pose" (ops.object_pose's dict plus "tab"), and rig_objects(out) adds 'T_BO'
-    (4 x 4, model -> rig coordinates, or None), 'rmse', 'ambiguity' and 'pose_status' to every object.
+    (4 x 4, model -> rig coordinates, or None), 'rmse', 'ambiguity' and 'pose_status' to every object.  There is no `refine` here
+    (BatchedKeypointPipeline has one): the fused points come from stereo triangulation, not from one camera's bearings and depth map.
 
     Tracking (optional, needs the pose): track = ops.TrackConfig(...).  The fused device ticks then end with okp_track_objects - one stream,
     in the rig frame, inside the captured graph, after the gather on every rank with no further collective (every rank keeps the same
