@@ -566,53 +566,115 @@ def _live_plans(net):
     return found
 
 
+def _to_host(fields):
+    """The one unpacker of the host readers: an ordered {name: device tensor} (float64, float32 or int32, all on one device) -> {name: ndarray of
+    the same shape}, through ONE device -> host copy of their concatenation as float64 (int32 and float32 are exact in it); integer fields come
+    back as int32."""
+    flat = torch.cat([t.reshape(-1).to(torch.float64) for t in fields.values()]).cpu().numpy()
+    host, at = {}, 0
+    for name, t in fields.items():
+        a = flat[at:at + t.numel()].reshape(tuple(t.shape))
+        host[name] = a if t.dtype.is_floating_point else a.astype(np.int32)
+        at += t.numel()
+    return host
+
+
+def _pose_fields(pose, n, refine=None):
+    """What the readers take of frame n of an ops.object_pose dict: "pose" [max_obj,12], "fit" [max_obj,2], "status" [max_obj]; with an
+    ops.refine_pose dict also "refine" (the refined pose [max_obj,12]), "refine_fit" [max_obj,4], "information" [max_obj,36], "refine_status"."""
+    fields = {"pose": pose["pose"][n], "fit": pose["fit"][n], "status": pose["status"][n]}
+    if refine is not None:
+        fields.update(refine=refine["pose"][n], refine_fit=refine["fit"][n], information=refine["information"][n], refine_status=refine["status"][n])
+    return fields
+
+
+def _track_fields(track, n):
+    """What the readers take of stream n of a tick's "track" dict: "track_pose" [T,12], "track_f" [T,16], "track_i" [T,4], "track_of" [max_obj],
+    "meas_of" [T] and, of a world-frame tick, "track_pose_C" [T,12] - the track poses back in the camera / rig frame."""
+    return {k: track[k][n] for k in ("track_pose", "track_f", "track_i", "track_of", "meas_of", "track_pose_C") if k in track}
+
+
 def _host_poses(pose, n, refine=None):
-    """Frame n of an ops.object_pose dict on the host, in ONE device -> host copy: (pose [max_obj,12], fit [max_obj,2], status [max_obj]);
-    with an ops.refine_pose dict the same copy also carries (refined pose [max_obj,12], fit [max_obj,4], information [max_obj,6,6], status)."""
-    max_obj = pose["status"].shape[1]
-    more = [refine["pose"][n].reshape(-1), refine["fit"][n].reshape(-1), refine["information"][n].reshape(-1), refine["status"][n].to(torch.float64)] if refine is not None else []
-    flat = torch.cat([pose["pose"][n].reshape(-1), pose["fit"][n].reshape(-1), pose["status"][n].to(torch.float64)] + more).cpu().numpy()
-    host = (flat[:12 * max_obj].reshape(max_obj, 12), flat[12 * max_obj:14 * max_obj].reshape(max_obj, 2), flat[14 * max_obj:15 * max_obj].astype(np.int64))
-    if refine is None:
-        return host
-    r = flat[15 * max_obj:]
-    return host + (r[:12 * max_obj].reshape(max_obj, 12), r[12 * max_obj:16 * max_obj].reshape(max_obj, 4), r[16 * max_obj:52 * max_obj].reshape(max_obj, 6, 6),
-                   r[52 * max_obj:].astype(np.int64))
+    """_pose_fields on the host, in ONE device -> host copy."""
+    return _to_host(_pose_fields(pose, n, refine))
 
 
-def _refine_entries(poses, o, T_CO):
+def _host_tracks(track, n):
+    """_track_fields on the host, in ONE device -> host copy."""
+    return _to_host(_track_fields(track, n))
+
+
+def _refine_entries(rec, o, T_CO):
     """Object o's refined pose as the entries objects() adds: 'T_CO_refined' (None where 'T_CO' is; the fitted pose where the refinement's
     status is not 0), 'reprojection_rmse' and 'depth_rmse' (before, after), 'pose_information' (6 x 6) and 'refine_status'."""
-    pose, fit, information, status = poses[3:]
+    fit = rec["refine_fit"]
     T = None
     if T_CO is not None:
         T = np.eye(4)
-        T[:3] = pose[o].reshape(3, 4)
+        T[:3] = rec["refine"][o].reshape(3, 4)
     return {'T_CO_refined': T, 'reprojection_rmse': (float(fit[o, 0]), float(fit[o, 1])), 'depth_rmse': (float(fit[o, 2]), float(fit[o, 3])),
-            'pose_information': information[o].copy(), 'refine_status': int(status[o])}
+            'pose_information': rec["information"][o].reshape(6, 6).copy(), 'refine_status': int(rec["refine_status"][o])}
 
 
-def _pose_entries(poses, o, key):
+def _pose_entries(rec, o, key):
     """Object o's pose as the entries objects() / rig_objects() add: the 4 x 4 transform under `key` (None where the status refuses a pose)."""
-    pose, fit, status = poses[:3]
+    fit, status = rec["fit"], int(rec["status"][o])
     T = None
-    if not int(status[o]) & (ops.POSE_FEW | ops.POSE_DEGENERATE):
+    if not status & (ops.POSE_FEW | ops.POSE_DEGENERATE):
         T = np.eye(4)
-        T[:3] = pose[o].reshape(3, 4)
-    return {key: T, 'rmse': float(fit[o, 0]), 'ambiguity': float(fit[o, 1]), 'pose_status': int(status[o])}
+        T[:3] = rec["pose"][o].reshape(3, 4)
+    return {key: T, 'rmse': float(fit[o, 0]), 'ambiguity': float(fit[o, 1]), 'pose_status': status}
 
 
-def _check_track(track, has_model, max_obj, what):
-    """The `track` argument of both device pipelines: None, or an ops.TrackConfig next to an object model."""
-    if track is None:
+def _track_transform(row):
+    if not np.isfinite(row).all():           # (a world-frame track seen from a tick whose camera pose is missing)
         return None
-    if not isinstance(track, ops.TrackConfig):
-        raise OkpError("track must be an ops.TrackConfig")
-    if not has_model:
-        raise OkpError("track without points_3d: the tracker follows the poses of the object model")
-    if max_obj > ops.TRACK_MAX_OBJECTS:
-        raise OkpError(f"{what} = {max_obj}: the tracker takes at most {ops.TRACK_MAX_OBJECTS} objects per stream")
-    return track
+    T = np.eye(4)
+    T[:3] = row.reshape(3, 4)
+    return T
+
+
+def _track_poses(rec, slot, key, world_key):
+    """The filtered pose of a track slot under `key` (the camera or rig frame) and, for a world-frame tick, under `world_key` as well: the
+    tracker's own pose is then the world one and `key` is read from the inverse transform."""
+    if "track_pose_C" not in rec:
+        return {key: _track_transform(rec["track_pose"][slot])}
+    return {world_key: _track_transform(rec["track_pose"][slot]), key: _track_transform(rec["track_pose_C"][slot])}
+
+
+def _track_entries(rec, o, key, min_hits, world_key=None):
+    """Object o's track as the entries objects() / rig_objects() add: 'track_id' (None: the object went to no track - a position-only or
+    dropped measurement), the filtered pose under `key`, 'velocity', 'track_hits', 'confirmed'."""
+    slot = int(rec["track_of"][o])
+    if slot < 0:
+        none = {key: None} if "track_pose_C" not in rec else {world_key: None, key: None}
+        return dict({'track_id': None, 'velocity': None, 'track_hits': 0, 'confirmed': False}, **none)
+    hits = int(rec["track_i"][slot, 1])
+    return dict({'track_id': int(rec["track_i"][slot, 0]), 'velocity': rec["track_f"][slot, 3:6].copy(), 'track_hits': hits, 'confirmed': hits >= min_hits},
+                **_track_poses(rec, slot, key, world_key))
+
+
+def _track_list(rec, key, min_hits, world_key=None):
+    """Every live track, coasting ones included, in slot order."""
+    track_f, track_i, meas_of = rec["track_f"], rec["track_i"], rec["meas_of"]
+    return [dict({'track_id': int(track_i[i, 0]), 'velocity': track_f[i, 3:6].copy(), 'hits': int(track_i[i, 1]),
+                  'misses': int(track_i[i, 2]), 'age': int(track_i[i, 3]), 'confirmed': int(track_i[i, 1]) >= min_hits,
+                  'object': int(meas_of[i]) if meas_of[i] >= 0 else None}, **_track_poses(rec, i, key, world_key))
+            for i in range(track_i.shape[0]) if track_i[i, 0] != 0]
+
+
+class _PerDevice:
+    """A host tensor, uploaded once per device and kept for the pipeline's life - captured steps read the device copy on every replay:
+    cache(device) -> that copy; cache.host: the host tensor (None: the feature it serves is off); cache.on: {device: copy}."""
+
+    def __init__(self, host):
+        self.host, self.on = host, {}
+
+    def __call__(self, device):
+        t = self.on.get(device)
+        if t is None:
+            t = self.on[device] = self.host.to(device)
+        return t
 
 
 class _Tracker:
@@ -628,65 +690,15 @@ class _Tracker:
             st = self.states[(device, streams)] = ops.track_state(streams, self.cfg.max_tracks, device)
         return st
 
-    def step(self, pose, n_obj, model, overflow):
-        """ops.track_objects behind ops.object_pose's dict (with "tab") -> its outputs plus the state tensors."""
-        st = self.state(pose["tab"].device, int(pose["tab"].shape[0]))
-        return dict(ops.track_objects(st, pose["tab"], pose["pose"], pose["status"], n_obj, model, self.cfg, overflow=overflow), **st)
+    def step(self, tab, pose, status, n_obj, model, overflow):
+        """ops.track_objects on the state of the table's device and streams -> its outputs plus the state tensors."""
+        st = self.state(tab.device, int(tab.shape[0]))
+        return dict(ops.track_objects(st, tab, pose, status, n_obj, model, self.cfg, overflow=overflow), **st)
 
     def reset(self):
         for st in self.states.values():
             for t in st.values():
                 t.zero_()
-
-
-def _host_tracks(track, n):
-    """Stream n of a tick's "track" dict on the host, in ONE device -> host copy: (track_pose [T,12], track_f [T,16], track_i [T,4],
-    track_of [max_obj], meas_of [T], track_pose_C [T,12] or None - the track poses back in the camera / rig frame of a world-frame tick)."""
-    T, max_obj = track["meas_of"].shape[1], track["track_of"].shape[1]
-    local = [track["track_pose_C"][n].reshape(-1)] if "track_pose_C" in track else []
-    flat = torch.cat([track["track_pose"][n].reshape(-1), track["track_f"][n].reshape(-1), track["track_i"][n].reshape(-1).to(torch.float64),
-                      track["track_of"][n].to(torch.float64), track["meas_of"][n].to(torch.float64)] + local).cpu().numpy()  # (int32 is exact in fp64)
-    a, b, c, d, e = 12 * T, 28 * T, 32 * T, 32 * T + max_obj, 33 * T + max_obj
-    return (flat[:a].reshape(T, 12), flat[a:b].reshape(T, 16), flat[b:c].astype(np.int64).reshape(T, 4), flat[c:d].astype(np.int64), flat[d:e].astype(np.int64),
-            flat[e:].reshape(T, 12) if local else None)
-
-
-def _track_transform(row):
-    if not np.isfinite(row).all():           # (a world-frame track seen from a tick whose camera pose is missing)
-        return None
-    T = np.eye(4)
-    T[:3] = row.reshape(3, 4)
-    return T
-
-
-def _track_poses(host, slot, key, world_key):
-    """The filtered pose of a track slot under `key` (the camera or rig frame) and, for a world-frame tick, under `world_key` as well: the
-    tracker's own pose is then the world one and `key` is read from the inverse transform."""
-    if host[5] is None:
-        return {key: _track_transform(host[0][slot])}
-    return {world_key: _track_transform(host[0][slot]), key: _track_transform(host[5][slot])}
-
-
-def _track_entries(host, o, key, min_hits, world_key=None):
-    """Object o's track as the entries objects() / rig_objects() add: 'track_id' (None: the object went to no track - a position-only or
-    dropped measurement), the filtered pose under `key`, 'velocity', 'track_hits', 'confirmed'."""
-    track_pose, track_f, track_i, track_of = host[:4]
-    slot = int(track_of[o])
-    if slot < 0:
-        none = {key: None} if host[5] is None else {world_key: None, key: None}
-        return dict({'track_id': None, 'velocity': None, 'track_hits': 0, 'confirmed': False}, **none)
-    hits = int(track_i[slot, 1])
-    return dict({'track_id': int(track_i[slot, 0]), 'velocity': track_f[slot, 3:6].copy(), 'track_hits': hits, 'confirmed': hits >= min_hits},
-                **_track_poses(host, slot, key, world_key))
-
-
-def _track_list(host, key, min_hits, world_key=None):
-    """Every live track, coasting ones included, in slot order."""
-    track_pose, track_f, track_i, _, meas_of = host[:5]
-    return [dict({'track_id': int(track_i[i, 0]), 'velocity': track_f[i, 3:6].copy(), 'hits': int(track_i[i, 1]),
-                  'misses': int(track_i[i, 2]), 'age': int(track_i[i, 3]), 'confirmed': int(track_i[i, 1]) >= min_hits,
-                  'object': int(meas_of[i]) if meas_of[i] >= 0 else None}, **_track_poses(host, i, key, world_key))
-            for i in range(track_i.shape[0]) if track_i[i, 0] != 0]
 
 
 def _check_frame_pose(pose, world_frame, streams, device, name, what):
@@ -702,23 +714,105 @@ def _check_frame_pose(pose, world_frame, streams, device, name, what):
     return pose
 
 
-def _world(T, points, pose, overflow):
-    """The world-frame view of a tick (two okp_change_frame launches at the most): the lifted / fused `points`, and - with an object model -
-    the pose stage's table and poses, through the tick's poses T [B,12]; "overflow" = the tick's word | ops.FRAME_MISSING."""
-    B = T.shape[0]
-    first = ops.change_frame(T, points=points.reshape((B, -1, 4)), overflow=overflow)
-    world = {"T": T, "points": first["points"].view(points.shape), "overflow": first["overflow"]}
-    if pose is not None:
-        second = ops.change_frame(T, points=pose["tab"], poses=pose["pose"], overflow=overflow)
-        world.update(tab=second["points"], pose=second["poses"])
-    return world
+class _ObjectStage:
+    """Everything that follows the object point table in a device step, for both device pipelines - each makes its table its own way
+    (okp_object_points from a camera's lifted peaks, okp_rig_object_points from a rig's fused clusters) and names the frame ('T_CO' / 'T_BO'):
+
+    Pose (points_3d, the object model: [sum(type_count), 3] key points in model coordinates in type order, validated here by ops.object_model
+    and uploaded once per device): okp_object_pose -> "pose", ops.object_pose's dict plus "tab".  max_rmse (metres, optional): objects that
+    fit worse carry ops.POSE_POOR.
+    Refinement (refine = ops.RefineConfig(...), needs the pose and the camera the table was lifted through): okp_refine_pose -> "refine",
+    ops.refine_pose's dict.  "pose" keeps its bits; the world-frame change and the tracker are fed the refined pose from here on.
+    World frame (world_frame=True; the step's frame_pose [B,12] takes the table's frame to the world, an all-NaN row = missing in this tick):
+    okp_change_frame on the step's points and, with the pose, on the table and the poses -> "world": {"T", "points", "overflow" (the
+    step's word | ops.FRAME_MISSING)} and "tab", "pose".
+    Tracking (track = ops.TrackConfig(...), needs the pose): okp_track_objects - in the world frame where there is one, on "world"'s table,
+    poses and overflow word - -> "track": ops.track_objects' outputs plus the state tensors "track_f", "track_i", "next_id" (one state per
+    device and number of streams, kept for the pipeline's life) and, in the world frame, "track_pose_C": the filtered poses back in the table's
+    frame (okp_change_frame, inverse).  "track"["overflow"] is the word it was given | ops.TRACK_OVERFLOW.
+
+    Every launch is captured with the step it ends.  Without any of the four no launch, key or value of the step differs."""
+
+    def __init__(self, type_count, points_3d, max_rmse, track, max_obj, what, world_frame, refine=None):
+        self.type_count, self.world_frame = type_count, bool(world_frame)
+        if points_3d is None and max_rmse is not None:
+            raise OkpError("max_rmse without points_3d: the pose needs the object model")
+        self.model = _PerDevice(ops.object_model(points_3d, type_count) if points_3d is not None else None)       # (.host None: pose off)
+        self.max_rmse = ops.check_max_rmse(max_rmse) if points_3d is not None else None
+        if track is not None:
+            if not isinstance(track, ops.TrackConfig):
+                raise OkpError("track must be an ops.TrackConfig")
+            if points_3d is None:
+                raise OkpError("track without points_3d: the tracker follows the poses of the object model")
+            if max_obj > ops.TRACK_MAX_OBJECTS:
+                raise OkpError(f"{what} = {max_obj}: the tracker takes at most {ops.TRACK_MAX_OBJECTS} objects per stream")
+        self.tracker = _Tracker(track) if track is not None else None
+        if refine is not None:
+            if not isinstance(refine, ops.RefineConfig):
+                raise OkpError("refine must be an ops.RefineConfig")
+            if points_3d is None:
+                raise OkpError("refine without points_3d: the refinement starts from the pose of the object model")
+        self.refine = refine
+
+    def run(self, tab, n_obj, points, overflow, frame_pose, cam=None):
+        """The stage behind a step: tab = the object point table (None without a model), n_obj, points (what the world frame shows besides the
+        objects) and overflow = the step's own; frame_pose: the checked per-step pose, or None; cam: the camera of a refined table
+        -> the entries the step's dict gains, in order: "pose", "refine", "world", "track"."""
+        out, fed = {}, None
+        if self.model.host is not None:
+            model = self.model(tab.device)
+            fed = out["pose"] = dict(ops.object_pose(tab, n_obj, model, self.type_count, self.max_rmse), tab=tab)
+            if self.refine is not None:
+                out["refine"] = ops.refine_pose(tab, fed, n_obj, model, cam, self.refine)
+                fed = dict(fed, pose=out["refine"]["pose"])          # what the world-frame change and the tracker take
+        if frame_pose is not None:
+            first = ops.change_frame(frame_pose, points=points.reshape((frame_pose.shape[0], -1, 4)), overflow=overflow)
+            out["world"] = {"T": frame_pose, "points": first["points"].view(points.shape), "overflow": first["overflow"]}
+            if fed is not None:
+                second = ops.change_frame(frame_pose, points=tab, poses=fed["pose"], overflow=overflow)
+                out["world"].update(tab=second["points"], pose=second["poses"])
+                fed, overflow = dict(fed, tab=second["points"], pose=second["poses"]), first["overflow"]
+        if self.tracker is not None:
+            out["track"] = self.tracker.step(fed["tab"], fed["pose"], fed["status"], n_obj, model, overflow)
+            if frame_pose is not None:
+                out["track"]["track_pose_C"] = ops.change_frame(frame_pose, poses=out["track"]["track_pose"], inverse=True)["poses"]
+        return out
+
+    def reset_tracks(self):
+        if self.tracker is None:
+            raise OkpError("this pipeline was built without track")
+        self.tracker.reset()
+
+    def tracks(self, track, n, key):
+        """Every live track of stream n of a step's "track" dict, `key` naming its pose in the table's frame - ONE device -> host copy."""
+        return _track_list(_host_tracks(track, n), key, self.tracker.cfg.min_hits, 'T_WO_track')
+
+    def pin(self, step, static_out):
+        """What a captured graph reads on every replay besides its inputs, kept on `step`: the object model - the very tensor the captured launch
+        took, looked up by the device that launch ran on - and the tracker's state, which the graph also writes.  The warm-up passes and the
+        capture advanced that state: it is reset."""
+        if "pose" in static_out:
+            step._model = self.model(static_out["pose"]["tab"].device)
+        if "track" in static_out:
+            step._track_state = [static_out["track"][k] for k in ("track_f", "track_i", "next_id")]
+            self.reset_tracks()
 
 
-def _track_world(tracker, world, pose, n_obj, model):
-    """The tracker stepped in the world frame, and its filtered poses taken back into the tick's camera / rig frame ("track_pose_C")."""
-    track = tracker.step(dict(pose, tab=world["tab"], pose=world["pose"]), n_obj, model, world["overflow"])
-    track["track_pose_C"] = ops.change_frame(world["T"], poses=track["track_pose"], inverse=True)["poses"]
-    return track
+class _ObjectStagePipeline:
+    """What both device pipelines show of their _ObjectStage (self._stage)."""
+    world_frame = property(lambda self: self._stage.world_frame)
+    max_rmse = property(lambda self: self._stage.max_rmse)
+    refine = property(lambda self: self._stage.refine)
+    _tracker = property(lambda self: self._stage.tracker)
+    _model_host = property(lambda self: self._stage.model.host)
+    _models = property(lambda self: self._stage.model.on)
+
+    def _model(self, device):
+        return self._stage.model(device)
+
+    def reset_tracks(self):
+        """Empty the tracker: its state tensors are zeroed in place on the current stream, so a captured step keeps working."""
+        self._stage.reset_tracks()
 
 
 def _frame_point(T, p, missing):
@@ -779,7 +873,7 @@ class CapturedTick(CapturedStep):
         return super().replay(frames, camera_pose=rig_pose)
 
 
-class BatchedKeypointPipeline:
+class BatchedKeypointPipeline(_ObjectStagePipeline):
     """Frames -> heat/depth/centre maps -> peaks -> per-peak 3D points for a whole batch, device-resident.
 
     forward_device(frames) returns device tensors
@@ -790,47 +884,29 @@ class BatchedKeypointPipeline:
     objects(...) groups one frame's peaks exactly as ObjectKeypointPipeline does, reusing the lifted points (surplus votes of a
     multi-instance type reduced by the device k-means of okp_group_objects).
 
-    Pose (optional): points_3d = the object model, [sum(keypoint_config), 3] key points in model coordinates in type order (the argument
-    ObjectKeypointPipeline takes and ignores); it is validated at construction (ops.object_model) and uploaded once per device.  The
-    device step then ends with okp_object_points and okp_object_pose, inside a captured step too, and its dict gains "pose": {"tab"
-    [N,max_objects,S,4], "pose" [N,max_objects,12], "fit", "assignment", "used", "status"} (ops.object_pose); objects() adds to every object
-    'T_CO' (4 x 4 float64, model -> camera coordinates; None where the status is ops.POSE_FEW or ops.POSE_DEGENERATE), 'rmse', 'ambiguity' (the
-    runner-up assignment's rmse: close to 'rmse' = the data cannot tell the two apart) and 'pose_status'.  max_rmse (metres, optional):
-    objects that fit worse carry ops.POSE_POOR.  Without points_3d no launch, key or value differs.
-
-    Tracking (optional, needs the pose): track = ops.TrackConfig(...).  Batch index = stream: frame n of every step is the next tick of
-    stream n.  The device step then ends with okp_track_objects, inside a captured step too, and its dict gains "track": ops.track_objects'
-    outputs plus the state tensors "track_f", "track_i", "next_id" (one state per device and batch size, kept for the pipeline's life).
-    objects() adds 'track_id' (None where the object went to no track), 'T_CO_track' (the filtered pose), 'velocity', 'track_hits' and
-    'confirmed'; tracks(out, n) lists every live track of stream n, coasting ones included; reset_tracks() empties the tracker.  The tick's
-    own "overflow" word is unchanged; "track"["overflow"] is that word | ops.TRACK_OVERFLOW.  Without track no launch, key or value differs.
-
-    World frame (optional): world_frame=True, for a camera that moves.  Every step then takes camera_pose, a float64 [N,12] tensor on the
-    frames' device (ops.frame_poses(T_WC).to(device): camera coordinates -> world, one pose per stream and tick; an all-NaN row = the pose of
-    that stream is missing in this tick), and its dict gains "world": {"T", "points" [N,K,cap,4] (out["points"] in the world frame),
-    "overflow" (the tick's word | ops.FRAME_MISSING)} and, with points_3d, "tab" and "pose" (out["pose"]'s in the world frame) - at most
-    three okp_change_frame launches, inside a captured step too.  With track the tracker runs on the world table and poses: gate, velocity and
-    coasting are world-frame quantities, out["track"] is in the world frame and gains "track_pose_C" [N,T,12], the filtered poses back in the
-    tick's camera frame.  objects() adds 'p_W' next to 'p_C', 'T_WO' and 'T_WO_track' ('T_CO_track' then comes from track_pose_C; all None
-    where the pose is missing); tracks() lists both.  out["points"], out["pose"] and every earlier key keep their bits.  Without world_frame
-    no launch, key or value differs, and a camera_pose is refused.
-
-    Refinement (optional, needs the pose): refine = ops.RefineConfig(...).  The fitted pose rests on key points lifted through the depth
-    head, the weakest measurement of the step; the device step then gains one launch after okp_object_pose (okp_refine_pose, inside a
-    captured step too) that minimises the reprojection error of the same key points' bearings with the depth as a weak prior, and its dict
-    gains "refine": {"pose" [N,max_objects,12], "fit" [N,max_objects,4], "information" [N,max_objects,36], "status"} (ops.refine_pose).
-    out["pose"] and every earlier key keep their bits; the world-frame change and the tracker are fed the refined pose - the fitted one
-    where the refinement's status is not 0 - so 'T_WO', 'T_CO_track', 'T_WO_track' and 'velocity' come from it.  objects() adds
-    'T_CO_refined' (None where 'T_CO' is), 'reprojection_rmse' and 'depth_rmse' ((before, after): map pixels, metres), 'pose_information'
-    (6 x 6, the inverse covariance over (rotation, translation)) and 'refine_status', still in one device -> host copy.  Without refine no
-    launch, key or value differs.  The fused rig tick (StereoStreamPipeline) has no such stage: its points come from stereo triangulation,
-    not from one camera's bearings.
+    Pose, refinement, world frame and tracking (all optional) end the device step, inside a captured step too: _ObjectStage describes the
+    launches and the keys "pose", "refine", "world" and "track" they add to the step's dict, in the CAMERA frame of each frame.  Here:
+    points_3d is the argument ObjectKeypointPipeline takes and ignores; the table is okp_object_points' [N,max_objects,S,4].  objects() adds to
+    every object 'T_CO' (4 x 4 float64, model -> camera coordinates; None where the status is ops.POSE_FEW or ops.POSE_DEGENERATE), 'rmse',
+    'ambiguity' (the runner-up assignment's rmse: close to 'rmse' = the data cannot tell the two apart) and 'pose_status'.
+    refine: the fitted pose rests on key points lifted through the depth head, the weakest measurement of the step; okp_refine_pose minimises
+    the reprojection error of the same key points' bearings with the depth as a weak prior.  'T_WO', 'T_CO_track', 'T_WO_track' and 'velocity'
+    then come from the refined pose - the fitted one where the refinement's status is not 0.  objects() adds 'T_CO_refined' (None where 'T_CO'
+    is), 'reprojection_rmse' and 'depth_rmse' ((before, after): map pixels, metres), 'pose_information' (6 x 6, the inverse covariance over
+    (rotation, translation)) and 'refine_status', still in one device -> host copy.
+    world_frame=True, for a camera that moves: every step takes camera_pose, a float64 [N,12] tensor on the frames' device
+    (ops.frame_poses(T_WC).to(device): camera coordinates -> world, one pose per stream and tick; an all-NaN row = the pose of that stream
+    is missing in this tick); "world"["points"] is out["points"] in the world frame.  objects() adds 'p_W' next to 'p_C', 'T_WO' and
+    'T_WO_track' ('T_CO_track' then comes from track_pose_C; all None where the pose is missing); tracks() lists both.  Without world_frame a
+    camera_pose is refused.
+    track: batch index = stream - frame n of every step is the next tick of stream n.  objects() adds 'track_id' (None where the object went
+    to no track), 'T_CO_track' (the filtered pose), 'velocity', 'track_hits' and 'confirmed'; tracks(out, n) lists every live track of stream
+    n, coasting ones included; reset_tracks() empties the tracker.  The step's own "overflow" word is unchanged.
     """
 
     def __init__(self, net, keypoint_config, camera, prediction_size=(64, 64), capacity=DEFAULT_PEAK_CAPACITY,
                  max_objects=16, max_per_type=4, points_3d=None, max_rmse=None, track=None, world_frame=False, refine=None):
         self.net = net
-        self.world_frame = bool(world_frame)
         self.max_objects = max_objects
         self.max_per_type = max_per_type
         self.config = keypoint_config
@@ -840,30 +916,10 @@ class BatchedKeypointPipeline:
         self.camera = camera
         self.cam = camera.okp()
         self.max_index = camera.image_size.astype(int) - 1
-        self._model_host = None                                         # pose off
-        if points_3d is None and max_rmse is not None:
-            raise OkpError("max_rmse without points_3d: the pose needs the object model")
-        if points_3d is not None:
-            cfg = keypoint_config['keypoint_config']
-            self._model_host = ops.object_model(points_3d, cfg)
-            self._models = {}                                           # device -> the uploaded model
-            self.max_rmse = ops.check_max_rmse(max_rmse)
-            if max(cfg) > max_per_type:
-                raise OkpError(f"a keypoint type has {max(cfg)} instances, above max_per_type = {max_per_type}")
-        track = _check_track(track, points_3d is not None, max_objects, "max_objects")
-        self._tracker = _Tracker(track) if track is not None else None
-        if refine is not None:
-            if not isinstance(refine, ops.RefineConfig):
-                raise OkpError("refine must be an ops.RefineConfig")
-            if points_3d is None:
-                raise OkpError("refine without points_3d: the refinement starts from the pose of the object model")
-        self.refine = refine
-
-    def reset_tracks(self):
-        """Empty the tracker: its state tensors are zeroed in place on the current stream, so a captured step keeps working."""
-        if self._tracker is None:
-            raise OkpError("this pipeline was built without track")
-        self._tracker.reset()
+        cfg = keypoint_config['keypoint_config']
+        self._stage = _ObjectStage(cfg, points_3d, max_rmse, track, max_objects, "max_objects", world_frame, refine)
+        if points_3d is not None and max(cfg) > max_per_type:
+            raise OkpError(f"a keypoint type has {max(cfg)} instances, above max_per_type = {max_per_type}")
 
     def tracks(self, out, n):
         """Every live track of stream n after the step `out`, coasting ones included, in slot order: a list of {'track_id', 'T_CO_track'
@@ -871,13 +927,7 @@ class BatchedKeypointPipeline:
         (the index into objects(out, n) that updated or founded it in this step, or None)} - ONE device -> host copy."""
         if "track" not in out:
             raise OkpError("tracks reads the step of a pipeline built with track")
-        return _track_list(_host_tracks(out["track"], n), 'T_CO_track', self._tracker.cfg.min_hits, 'T_WO_track')
-
-    def _model(self, device):
-        m = self._models.get(device)
-        if m is None:
-            m = self._models[device] = self._model_host.to(device)
-        return m
+        return self._stage.tracks(out["track"], n, 'T_CO_track')
 
     def forward_device(self, frames, camera_pose=None):
         """Split-product configurations: the network's fp16-range flag is not read here (no host sync in the batch loop) but folded into
@@ -903,11 +953,7 @@ class BatchedKeypointPipeline:
         graph, static_out = _capture(lambda: self.forward_device(static_in, static_pose))
         step = CapturedStep(self.net, graph, static_in, static_out)
         step.static_pose = static_pose
-        if self._model_host is not None:                       # the graph reads the model on every replay: the step keeps the very tensor the
-            step._model = self._model(static_out["pose"]["tab"].device)     # captured launch took, looked up by the device that launch ran on
-        if self._tracker is not None:                          # (and the tracker's state, which it also writes)
-            step._track_state = [static_out["track"][k] for k in ("track_f", "track_i", "next_id")]
-            self.reset_tracks()
+        self._stage.pin(step, static_out)
         return step
 
     def postprocess_device(self, heat, depth, centers, range_flag=None, camera_pose=None):
@@ -923,20 +969,8 @@ class BatchedKeypointPipeline:
         # device-side flag (no sync here): a map with more peaks than `capacity`, or more centre peaks than `max_objects`,
         # means `points` / the grouping are truncated - callers check it (objects() raises, bench.py asserts).
         out["overflow"] = ops.capacity_overflow(count, self.capacity, self.max_objects, range_flag=range_flag)
-        if self._model_host is not None:
-            cfg = self.config['keypoint_config']
-            tab = ops.object_points(self.cam, out, cfg, int(self.max_index[0]), int(self.max_index[1]))
-            out["pose"] = dict(ops.object_pose(tab, out["n_obj"], self._model(tab.device), cfg, self.max_rmse), tab=tab)
-            fed = out["pose"]                                      # what the world-frame change and the tracker take: the refined pose when there is one
-            if self.refine is not None:
-                out["refine"] = ops.refine_pose(tab, out["pose"], out["n_obj"], self._model(tab.device), self.cam, self.refine)
-                fed = dict(out["pose"], pose=out["refine"]["pose"])
-            if self._tracker is not None and camera_pose is None:
-                out["track"] = self._tracker.step(fed, out["n_obj"], self._model(tab.device), out["overflow"])
-        if camera_pose is not None:
-            out["world"] = _world(camera_pose, points, fed if self._model_host is not None else None, out["overflow"])
-            if self._tracker is not None:
-                out["track"] = _track_world(self._tracker, out["world"], fed, out["n_obj"], self._model(points.device))
+        tab = ops.object_points(self.cam, out, self.config['keypoint_config'], int(self.max_index[0]), int(self.max_index[1])) if self._model_host is not None else None
+        out.update(self._stage.run(tab, out["n_obj"], points, out["overflow"], camera_pose, self.cam))
         return out
 
     def objects(self, out, n):
@@ -1013,7 +1047,7 @@ class BatchedKeypointPipeline:
                 objects[-1]['p_W'] = p_W
             if poses is not None:
                 objects[-1].update(_pose_entries(poses, o, 'T_CO'))
-                if len(poses) > 3:
+                if "refine" in poses:
                     objects[-1].update(_refine_entries(poses, o, objects[-1]['T_CO']))
                 if in_world:
                     objects[-1]['T_WO'] = None if missing else _pose_entries(poses_w, o, 'T_WO')['T_WO']
@@ -1149,7 +1183,7 @@ class HostFrameFeed:
         self.done[slot] = ev
 
 
-class StereoStreamPipeline:
+class StereoStreamPipeline(_ObjectStagePipeline):
     """BASELINE configs[4] / SURVEY 8(d) config 5: a rig of stereo cameras streamed frame-synchronously.  One TICK takes the 2P
     frames of P stereo pairs (left frame of pair p at index 2p, right at 2p + 1) through the network as ONE batch, finds the heat-map
     peaks of all 2P x K maps in one launch, matches left and right peaks per pair and key-point type (AssociationComponent's
@@ -1178,36 +1212,26 @@ class StereoStreamPipeline:
     rig_objects(out) reads it.  fuse_capacity: fused clusters kept per type (default: the kernel's limit, ops.RIG_MAX_FUSED).  Poses and
     radii are validated at construction (ops.rig_poses).  tick(), the host tick, is unchanged and does not fuse.
 
-    Pose (optional, needs the fusion): points_3d = the object model as for BatchedKeypointPipeline, max_rmse optional.  The fused device
-    ticks then end with okp_rig_object_points and okp_object_pose - the pose of every fused object in the RIG frame, inside the captured
-    graph, after the gather on every rank - under the key "pose" (ops.object_pose's dict plus "tab"), and rig_objects(out) adds 'T_BO'
-    (4 x 4, model -> rig coordinates, or None), 'rmse', 'ambiguity' and 'pose_status' to every object.  There is no `refine` here
+    Pose, world frame and tracking (all optional, all need the fusion - the fused tick is what has ONE frame) end the fused device ticks, inside
+    the captured graph and after the gather on every rank with no further collective (every rank keeps the same tracker): _ObjectStage describes
+    the launches and the keys "pose", "world" and "track" they add to the tick's dict, for ONE stream in the RIG frame.  Here: the table is
+    okp_rig_object_points' [1,fuse_capacity,S,4]; "world"["points"] is the fused clusters [K,cap_f,4] in the world frame.  There is no `refine`
     (BatchedKeypointPipeline has one): the fused points come from stereo triangulation, not from one camera's bearings and depth map.
-
-    Tracking (optional, needs the pose): track = ops.TrackConfig(...).  The fused device ticks then end with okp_track_objects - one stream,
-    in the rig frame, inside the captured graph, after the gather on every rank with no further collective (every rank keeps the same
-    tracker) - under the key "track" (ops.track_objects' outputs plus the state tensors); rig_objects(out) adds 'track_id', 'T_BO_track',
-    'velocity', 'track_hits' and 'confirmed', rig_tracks(out) lists the live tracks, reset_tracks() empties the tracker.  The tick's
-    "overflow" word is unchanged; "track"["overflow"] carries ops.TRACK_OVERFLOW on top of it.
-
-    World frame (optional, needs the fusion - the fused tick is what has ONE frame): world_frame=True, for a rig that moves.  tick_device,
-    capture_device / CapturedTick.replay and tick_sharded then take rig_pose, a float64 [1,12] tensor on the frames' device
-    (ops.frame_poses(T_WB).to(device): rig coordinates -> world; the same on every rank of a sharded tick; all NaN = missing in this tick).
-    It is applied after okp_rig_fuse: the dict gains "world": {"T", "points" [K,cap_f,4] (the fused clusters), "overflow" (the tick's word |
-    ops.FRAME_MISSING)} and, with points_3d, "tab" and "pose" - at most three okp_change_frame launches.  With track the tracker runs in the
-    world frame and out["track"] gains "track_pose_C", its poses back in the rig frame; rig_objects() adds 'T_WO' and 'T_WO_track' next to
-    'T_BO' and 'T_BO_track', rig_tracks() lists both.  Every earlier key keeps its bits; without world_frame a rig_pose is refused."""
+    rig_objects(out) adds 'T_BO' (4 x 4, model -> rig coordinates, or None), 'rmse', 'ambiguity' and 'pose_status' to every object; with track
+    'track_id', 'T_BO_track', 'velocity', 'track_hits' and 'confirmed'; with world_frame 'T_WO' and 'T_WO_track' next to them.  rig_tracks(out)
+    lists the live tracks, reset_tracks() empties the tracker.
+    world_frame=True, for a rig that moves: tick_device, capture_device / CapturedTick.replay and tick_sharded take rig_pose, a float64 [1,12]
+    tensor on the frames' device (ops.frame_poses(T_WB).to(device): rig coordinates -> world; the same on every rank of a sharded tick; all NaN
+    = missing in this tick).  Without world_frame a rig_pose is refused."""
 
     def __init__(self, net, stereo_camera, keypoint_config, capacity=16, max_distance=3.0, rig_poses=None, merge_radius=None, object_radius=None,
                  fuse_capacity=None, points_3d=None, max_rmse=None, track=None, world_frame=False):
         self.net = net
-        self.world_frame = bool(world_frame)
-        if self.world_frame and rig_poses is None:
+        if world_frame and rig_poses is None:
             raise OkpError("world_frame without rig_poses, merge_radius and object_radius: the fused tick is what has one frame to pose")
         self.rig = None if hasattr(stereo_camera, "left_camera") else list(stereo_camera)       # one StereoCamera, or a sequence of them
         self.stereo_cameras = self.rig if self.rig is not None else [stereo_camera]
-        self._table_host = ops.stereo_rig(self.stereo_cameras)         # (refuses an empty rig)
-        self._tables = {}                                               # device -> the uploaded table
+        self._table = _PerDevice(ops.stereo_rig(self.stereo_cameras))  # (refuses an empty rig)
         self.stereo = self.stereo_cameras[0]
         self.config = [1] + list(keypoint_config["keypoint_config"])
         self.capacity = capacity
@@ -1218,15 +1242,13 @@ class StereoStreamPipeline:
                       for st in self.stereo_cameras]
         self.cam_l, self.cam_r = self._cams[0]
         self._graph = None
-        self._poses_host = None                                         # fusion off
         given = [n for n, v in (("rig_poses", rig_poses), ("merge_radius", merge_radius), ("object_radius", object_radius)) if v is not None]
         if given and len(given) != 3:
             raise OkpError(f"fusion takes rig_poses, merge_radius and object_radius together: only {', '.join(given)} given")
         if not given and fuse_capacity is not None:
             raise OkpError("fuse_capacity without rig_poses, merge_radius and object_radius")
+        self._poses = _PerDevice(ops.rig_poses(rig_poses) if given else None)          # (.host None: fusion off)
         if given:
-            self._poses_host = ops.rig_poses(rig_poses)
-            self._poses = {}                                            # device -> the uploaded pose table
             self.n_fused_pairs = int(self._poses_host.shape[0])
             if self.rig is not None and self.n_fused_pairs != len(self.rig):
                 raise OkpError(f"{self.n_fused_pairs} rig poses for a rig of {len(self.rig)} stereo pairs: one pose per pair")
@@ -1237,39 +1259,18 @@ class StereoStreamPipeline:
             if len(self.config) > ops.RIG_MAX_TYPES or self.n_fused_pairs * self.capacity > ops.RIG_MAX_ROWS:
                 raise OkpError(f"fusion holds at most {ops.RIG_MAX_TYPES} key-point types and {ops.RIG_MAX_ROWS} rows (pairs x capacity) per type: "
                                f"{len(self.config)} types, {self.n_fused_pairs} x {self.capacity} rows asked for")
-        self._model_host = None                                         # pose off
-        if points_3d is None and max_rmse is not None:
-            raise OkpError("max_rmse without points_3d: the pose needs the object model")
-        if points_3d is not None:
-            if not given:
-                raise OkpError("points_3d without rig_poses, merge_radius and object_radius: the pose is fitted to the fused objects of the rig")
-            self._model_host = ops.object_model(points_3d, self.config[1:])
-            self._models = {}                                           # device -> the uploaded model
-            self.max_rmse = ops.check_max_rmse(max_rmse)
-        track = _check_track(track, points_3d is not None, self.fuse_capacity if given else 0, "fuse_capacity")
-        self._tracker = _Tracker(track) if track is not None else None
+        if points_3d is not None and not given:
+            raise OkpError("points_3d without rig_poses, merge_radius and object_radius: the pose is fitted to the fused objects of the rig")
+        self._stage = _ObjectStage(self.config[1:], points_3d, max_rmse, track, self.fuse_capacity if given else 0, "fuse_capacity", world_frame)
 
-    def reset_tracks(self):
-        """Empty the tracker: its state tensors are zeroed in place on the current stream, so a captured tick keeps working."""
-        if self._tracker is None:
-            raise OkpError("this pipeline was built without track")
-        self._tracker.reset()
-
-    def _track(self, out):
-        """The tracker stepped by a fused tick's poses: one launch behind okp_object_pose."""
-        return self._tracker.step(out["pose"], out["fused"]["n_obj"], self._model(out["pose"]["tab"].device), out["fused"]["overflow"])
+    _table_host = property(lambda self: self._table.host)
+    _poses_host = property(lambda self: self._poses.host)
 
     def _finish(self, out, rig_pose):
-        """What follows okp_rig_fuse in a fused device tick: the pose, the world frame, the tracker (in the world frame where there is one)."""
-        if self._model_host is not None:
-            out["pose"] = self._pose(out["fused"])
-        if rig_pose is not None:
-            out["world"] = _world(rig_pose, out["fused"]["fused"], out.get("pose"), out["fused"]["overflow"])
-        if self._tracker is not None:
-            if rig_pose is None:
-                out["track"] = self._track(out)
-            else:
-                out["track"] = _track_world(self._tracker, out["world"], out["pose"], out["fused"]["n_obj"], self._model(out["pose"]["tab"].device))
+        """What follows okp_rig_fuse in a fused device tick: the table of the fused objects (with a model), then the object stage."""
+        fused = out["fused"]
+        tab = ops.rig_object_points(fused, self.config[1:]) if self._model_host is not None else None
+        out.update(self._stage.run(tab, fused["n_obj"], fused["fused"], fused["overflow"], rig_pose))
 
     def rig_tracks(self, out):
         """Every live track after the fused tick `out`, coasting ones included, in slot order: a list of {'track_id', 'T_BO_track' (4 x 4,
@@ -1277,7 +1278,7 @@ class StereoStreamPipeline:
         rig_objects(out), or None)} - ONE device -> host copy."""
         if not isinstance(out, dict) or "track" not in out:
             raise OkpError("rig_tracks reads the fused device tick of a pipeline built with track")
-        return _track_list(_host_tracks(out["track"], 0), 'T_BO_track', self._tracker.cfg.min_hits, 'T_WO_track')
+        return self._stage.tracks(out["track"], 0, 'T_BO_track')
 
     def _check_fused_tick(self, n_pairs, first_pair=0):
         """A fused tick holds every pair of the rig: the clusters are formed across all of them."""
@@ -1286,22 +1287,7 @@ class StereoStreamPipeline:
                            f"({2 * n_pairs} frames from pair {first_pair} on given; a shard of the rig goes through tick_sharded)")
 
     def _fuse(self, points, overflow):
-        dev = points.device
-        poses = self._poses.get(dev)
-        if poses is None:
-            poses = self._poses[dev] = self._poses_host.to(dev)
-        return ops.rig_fuse(points, poses, self.config[1:], self.merge_radius, self.object_radius, self.fuse_capacity, overflow=overflow)
-
-    def _pose(self, fused):
-        """The pose of every fused object, in the rig frame: two launches behind okp_rig_fuse."""
-        tab = ops.rig_object_points(fused, self.config[1:])
-        return dict(ops.object_pose(tab, fused["n_obj"], self._model(tab.device), self.config[1:], self.max_rmse), tab=tab)
-
-    def _model(self, device):
-        m = self._models.get(device)
-        if m is None:
-            m = self._models[device] = self._model_host.to(device)
-        return m
+        return ops.rig_fuse(points, self._poses(points.device), self.config[1:], self.merge_radius, self.object_radius, self.fuse_capacity, overflow=overflow)
 
     def _check_rig_frames(self, frames, first_pair=0):
         """A rig's tick holds 2 frames for each of its pairs first_pair .. first_pair + P - 1 (a single calibration: any P)."""
@@ -1312,12 +1298,6 @@ class StereoStreamPipeline:
             raise OkpError(f"{frames.shape[0]} frames from pair {first_pair} on: the rig has {len(self.rig)} stereo pairs "
                            f"(pairs {first_pair} .. {first_pair + frames.shape[0] // 2 - 1} asked for)")
         return first_pair
-
-    def _table(self, device):
-        t = self._tables.get(device)
-        if t is None:
-            t = self._tables[device] = self._table_host.to(device)
-        return t
 
     def capture(self, frames):
         """Capture the network pass of a tick for this frame shape into a hipGraph (one graph launch instead of ~66)."""
@@ -1465,22 +1445,17 @@ class StereoStreamPipeline:
         step = CapturedTick(self.net, graph, static_in, static_out, static_heat)
         step.static_pose = static_pose
         step._table = self._table(frames.device)               # (the graph reads it on every replay)
-        step._poses = self._poses.get(frames.device) if self._poses_host is not None else None       # (and the pose table)
-        if self._model_host is not None and "pose" in static_out:       # (and the object model: the tensor the captured launch took)
-            step._model = self._model(static_out["pose"]["tab"].device)
-        if "track" in static_out:                                       # (and the tracker's state, which the graph also writes)
-            step._track_state = [static_out["track"][k] for k in ("track_f", "track_i", "next_id")]
-            self.reset_tracks()
+        step._poses = self._poses.on.get(frames.device)        # (and the pose table)
+        self._stage.pin(step, static_out)
         return step
 
     def results(self, out):
         """A device tick (tick_device, a CapturedTick's outputs, or tick_sharded's gathered payload) as tick() returns it: a list over
         pairs of {type k: (n_k, 3) float64 points in the left camera frame}, in ascending left-peak order.  Reads `points` (a NaN row =
         unmatched slot) and `overflow` only, in ONE device -> host copy; raises OkpError like tick() when the overflow word is set."""
-        pts = out["points"]
-        flat = torch.cat([out["overflow"].reshape(1).to(torch.float64), pts.reshape(-1)]).cpu().numpy()        # the one D2H copy
-        _raise_on_overflow(int(flat[0]))
-        pts = flat[1:].reshape(tuple(pts.shape))
+        host = _to_host({"overflow": out["overflow"], "points": out["points"]})        # the one D2H copy
+        _raise_on_overflow(int(host["overflow"]))
+        pts = host["points"]
         result = []
         for p in range(pts.shape[0]):
             per = {}
@@ -1555,59 +1530,33 @@ class StereoStreamPipeline:
             raise OkpError("rig_objects reads a fused device tick: the dict of tick_device / capture_device / tick_sharded of a pipeline "
                            "built with rig_poses (the host tick() does not fuse)")
         f = out["fused"]
-        K, cap_f = f["views"].shape
-        parts = [out["overflow"].reshape(1), f["n_obj"].reshape(1), f["n_fused"], f["views"].reshape(-1), f["object"].reshape(-1)]
-        tail = [f["fused"].reshape(-1)]
+        fields = {"overflow": out["overflow"], "n_obj": f["n_obj"], "n_fused": f["n_fused"], "views": f["views"], "object": f["object"], "fused": f["fused"]}
         if "pose" in out:
-            ps = out["pose"]
-            tail += [ps["pose"].reshape(-1), ps["fit"].reshape(-1), ps["status"].reshape(-1).to(torch.float64)]
+            fields.update(_pose_fields(out["pose"], 0))
         if "track" in out:
-            tr = out["track"]
-            n_slots = tr["meas_of"].shape[1]
-            tail += [tr["track_pose"].reshape(-1), tr["track_f"].reshape(-1), tr["track_i"].reshape(-1).to(torch.float64), tr["track_of"].reshape(-1).to(torch.float64),
-                     tr["meas_of"].reshape(-1).to(torch.float64)]
-        in_world = "world" in out                                  # (behind everything else: the offsets above it are today's)
+            fields.update(_track_fields(out["track"], 0))
+        in_world = "world" in out
         if in_world:
-            tail += [out["world"]["T"].reshape(-1)] + ([out["world"]["pose"].reshape(-1)] if "pose" in out else []) + \
-                    ([out["track"]["track_pose_C"].reshape(-1)] if "track" in out else [])
-        flat = torch.cat([t.to(torch.float64) for t in parts] + tail).cpu().numpy()          # the one D2H copy (int32 is exact in fp64)
-        _raise_on_overflow(int(flat[0]), fused=True)
-        n_obj = int(flat[1])
-        n_fused = flat[2:2 + K].astype(np.int64)
-        at = 2 + K
-        views = flat[at:at + K * cap_f].astype(np.int32).reshape(K, cap_f)
-        obj = flat[at + K * cap_f:at + 2 * K * cap_f].astype(np.int64).reshape(K, cap_f)
-        rows = flat[at + 2 * K * cap_f:at + 2 * K * cap_f + K * cap_f * 4].reshape(K, cap_f, 4)
-        poses = None
-        if "pose" in out:
-            rest = flat[at + 2 * K * cap_f + K * cap_f * 4:]
-            poses = (rest[:12 * cap_f].reshape(cap_f, 12), rest[12 * cap_f:14 * cap_f].reshape(cap_f, 2), rest[14 * cap_f:15 * cap_f].astype(np.int64))
-        tracked = None
-        if "track" in out:
-            rest = rest[15 * cap_f:]
-            a, b, c, d = 12 * n_slots, 28 * n_slots, 32 * n_slots, 32 * n_slots + cap_f
-            tracked = (rest[:a].reshape(n_slots, 12), rest[a:b].reshape(n_slots, 16), rest[b:c].astype(np.int64).reshape(n_slots, 4), rest[c:d].astype(np.int64),
-                       rest[d:d + n_slots].astype(np.int64), None)
-        if in_world:
-            w = flat[-(12 + (12 * cap_f if poses is not None else 0) + (12 * n_slots if tracked is not None else 0)):]
-            missing = not np.isfinite(w[:12]).all()
-            if poses is not None:
-                poses_w = (w[12:12 + 12 * cap_f].reshape(cap_f, 12),) + poses[1:]
-            if tracked is not None:
-                tracked = tracked[:5] + (w[len(w) - 12 * n_slots:].reshape(n_slots, 12),)
+            fields["T_WB"] = out["world"]["T"]
+            if "pose" in out:
+                fields["world_pose"] = out["world"]["pose"][0]
+        host = _to_host(fields)                                    # the one D2H copy
+        _raise_on_overflow(int(host["overflow"]), fused=True)
+        n_obj, n_fused, views, obj, rows = int(host["n_obj"]), host["n_fused"], host["views"], host["object"], host["fused"]
+        missing = in_world and not np.isfinite(host["T_WB"]).all()
         objects = []
         for o in range(n_obj):
             p_B, conf, seen = [], [], []
-            for k in range(K):
+            for k in range(views.shape[0]):
                 sel = np.nonzero(obj[k, :n_fused[k]] == o)[0]
                 p_B.append(np.ascontiguousarray(rows[k, sel, :3]))
                 conf.append(np.ascontiguousarray(rows[k, sel, 3]))
                 seen.append(views[k, sel])
             objects.append({"p_B": p_B, "confidence": conf, "views": seen})
-            if poses is not None:
-                objects[-1].update(_pose_entries(poses, o, "T_BO"))
+            if "pose" in out:
+                objects[-1].update(_pose_entries(host, o, "T_BO"))
                 if in_world:
-                    objects[-1]["T_WO"] = None if missing else _pose_entries(poses_w, o, "T_WO")["T_WO"]
-            if tracked is not None:
-                objects[-1].update(_track_entries(tracked, o, "T_BO_track", self._tracker.cfg.min_hits, "T_WO_track"))
+                    objects[-1]["T_WO"] = None if missing else _pose_entries(dict(host, pose=host["world_pose"]), o, "T_WO")["T_WO"]
+            if "track" in out:
+                objects[-1].update(_track_entries(host, o, "T_BO_track", self._tracker.cfg.min_hits, "T_WO_track"))
         return objects
