@@ -42,7 +42,9 @@ extern "C" {
                                     okp_object_points, okp_rig_object_points, okp_object_pose (each object's 6-DoF pose from its 3D key points);
                                     okp_track_objects, OKP_TRACK_* (objects tracked across ticks: stable ids, filtered poses);
                                     okp_change_frame, OKP_FRAME_MISSING (points, tables and poses in a fixed world frame under a moving camera);
-                                    okp_refine_pose, OKP_REFINE_* (each object's pose refined against its key points' bearings) */
+                                    okp_refine_pose, OKP_REFINE_* (each object's pose refined against its key points' bearings);
+                                    okp_refine_assignments, OKP_REFINE_NONE, OKP_REFINE_MAX_HYPOTHESES (interchangeable key points resolved by
+                                    refining every assignment) */
 
 /* OKP_F16: IEEE half activations / weights, fp32 accumulate (BASELINE configs[4]).
  * OKP_F32X3 (okp_conv plans only): fp32 activations, weights and results like OKP_F32 - every tensor argument of such a plan is an
@@ -794,6 +796,63 @@ int okp_refine_pose(const double* tab_dev, const double* pose_dev, const int32_t
                     const double* model_dev, const okp_camera* cam, double sigma_px, double sigma_z, int32_t iters, double damping, int32_t B,
                     int32_t max_obj, int32_t S, double* pose_out_dev, double* fit_dev, double* information_dev, int32_t* status_dev,
                     void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * Resolving interchangeable key points (csrc/okp_refine_assign.hip): okp_object_pose picks the assignment of an object's key points to the
+ * interchangeable instances of a type by a rigid fit to the lifted points, and okp_refine_pose takes that assignment as it is.  With
+ * centimetres of depth noise the fit picks a wrong assignment for a valve ([1, 3]: one stem, three handle points) about once in six, a pose
+ * 120 degrees off that no local refinement repairs.  The bearings, good to a fraction of a map pixel, tell the assignments apart where the
+ * depths cannot: this stage refines EVERY assignment, each from its own rigid fit, and keeps the one with the least final cost.  There is
+ * no reference implementation: the specification is this comment (tests/refine_assign_spec.py restates it in NumPy).
+ *
+ * okp_refine_assignments: one launch, one wave per object - each of its four 16-lane groups runs one hypothesis at a time, over ceil(H / 4)
+ * rounds -, fp64, no atomics, no host wait, capturable; the same bits on every run.
+ * Inputs: those of okp_refine_pose - tab [B][max_obj][S][4], pose [B][max_obj][12], assignment [B][max_obj][S] int32, n_obj [B] int32,
+ *   model [S][3] in device memory; cam, sigma_px, sigma_z, iters, damping, B, max_obj on the host - and type_count HOST [K-1] and K as
+ *   okp_object_pose takes them, S = 1 + sum(type_count).  pose and assignment are the pose stage's outputs: the fallback, not the start.
+ * Per object o < min(n_obj[b], max_obj):
+ *   1. Precheck, as in okp_refine_pose, on the filled slots (a slot is filled when its four values are finite): OKP_REFINE_SKIPPED when one
+ *      of the 12 values of the input pose is not finite (which covers the pose stage's OKP_POSE_FEW and OKP_POSE_DEGENERATE), when fewer
+ *      than 3 slots are filled, or when a filled slot has Z = 0 or a non-finite u = X/Z or v = Y/Z.
+ *   2. Hypotheses: exactly the enumeration of okp_object_pose, step 1 - the filled slots of a type mapped injectively onto that type's
+ *      model rows, the maps of a type in lexicographic order, mixed radix over the types with type 1 the slowest digit, a filled slot 0
+ *      mapped to model row 0.  H = prod_k c_k! / (c_k - n_k)! <= prod_k c_k! <= OKP_REFINE_MAX_HYPOTHESES.
+ *   3. Per hypothesis h, whose point pairs are the filled slots with the model rows it gives them:
+ *      the start is the rigid fit of okp_object_pose, steps 2 and 3: R minimising sum_i |R (m_i - m_bar) - (p_i - p_bar)|^2 (uniform
+ *      weights), t = p_bar - R m_bar; how the minimum is found is not part of the contract.  When the second-largest eigenvalue of the scatter
+ *      of the matched MODEL points is <= OKP_POSE_DEGENERACY * its trace, the hypothesis is out with the per-hypothesis status
+ *      OKP_REFINE_SINGULAR.  Otherwise exactly `iters` Gauss-Newton steps of okp_refine_pose from that start - the same cost, step,
+ *      Cholesky and C(w), the same statuses OKP_REFINE_BEHIND / OKP_REFINE_SINGULAR / OKP_REFINE_REJECTED - and the evaluation at the final
+ *      iterate, J_final.
+ *   4. Selection.  Among the hypotheses whose status is 0 the least J_final wins; on exactly equal cost the lowest index.  The runner-up is
+ *      the least among the others, by the same rule.
+ *   5. Outputs, all written by every call:
+ *      pose_out [B][max_obj][12], fit [B][max_obj][4], information [B][max_obj][36] fp64   the winner's, defined as in okp_refine_pose;
+ *                                           fit[0] and fit[2] are taken at the winner's own start
+ *      assignment_out [B][max_obj][S] int32 the winner's model row of each slot, -1 for an empty slot
+ *      hypothesis [B][max_obj][2] int32     the indices of the winner and of the runner-up, -1 where there is none
+ *      cost [B][max_obj][2] fp64            J_final of the winner and of the runner-up, NaN where there is none
+ *      status [B][max_obj] int32            0 when there is a winner; OKP_REFINE_SKIPPED from the precheck; OKP_REFINE_NONE when every
+ *                                           hypothesis ended out
+ *      For ANY non-zero status pose_out is the input pose bit for bit and assignment_out the input assignment bit for bit; fit,
+ *      information and cost are NaN, hypothesis is -1.
+ *   6. Objects from n_obj[b] on: NaN pose_out, fit, information and cost, assignment_out and hypothesis -1, status OKP_REFINE_SKIPPED;
+ *      whatever their table rows hold is ignored.
+ *   As for okp_refine_pose the order of the sums over the pairs is not part of the contract (tests/test_gpu_refine_assign.py: 1e-9 on R, t).
+ * Limits.  Uniform weights.  An exactly symmetric model gives equal costs by construction: the lowest index wins and cost[1] ~ cost[0]
+ * tells the reader so.  With a quarter of a map pixel of pixel noise on top of 3 % depth noise about one valve in eleven still ends on a
+ * wrong assignment (23 of 256 in the specification).  The objects of a rig are not refined, as before.
+ * Refused on the host before any launch (OKP_EINVAL, the message names the argument): everything okp_refine_pose refuses, K outside
+ * [2, 16], a type_count below 1, S > OKP_POSE_MAX_POINTS, prod c_k! > OKP_REFINE_MAX_HYPOTHESES, pose_out overlapping pose,
+ * assignment_out overlapping assignment.
+ * ---------------------------------------------------------------------------------- */
+#define OKP_REFINE_MAX_HYPOTHESES 24
+#define OKP_REFINE_NONE 16
+int okp_refine_assignments(const double* tab_dev, const double* pose_dev, const int32_t* assignment_dev, const int32_t* n_obj_dev,
+                           const double* model_dev, const int32_t* type_count /* HOST [K-1] */, int32_t K, const okp_camera* cam,
+                           double sigma_px, double sigma_z, int32_t iters, double damping, int32_t B, int32_t max_obj, double* pose_out_dev,
+                           double* fit_dev, double* information_dev, int32_t* status_dev, int32_t* assignment_out_dev,
+                           int32_t* hypothesis_dev, double* cost_dev, void* stream);
 
 /* Undistort only (FisheyeCamera.undistort, camera_utils.py:75-81 / RadTanPinholeCamera.undistort, :57-62, by cam->model):
  * xy [m][2] fp32 -> out [m][2] fp64.  okp_fisheye_undistort is the same entry point under its round-1 name. */

@@ -363,6 +363,16 @@ def refine_pose(camera, tab, pose, assignment, n_obj, model, sigma_px, sigma_z, 
                "okp_refine_pose")
 
 
+# ---- resolving interchangeable key points (csrc/okp_refine_assign.hip): refine_pose's tensors, type_count, and assignment_out [B,max_obj,S] ----
+def refine_assignments(camera, tab, pose, assignment, n_obj, model, type_count, sigma_px, sigma_z, iters, damping, pose_out, fit, information, status,
+                       assignment_out, hypothesis, cost, stream):
+    b, max_obj = tab.shape[0], tab.shape[1]
+    _lib.check(_lib.lib().okp_refine_assignments(tab.data_ptr(), pose.data_ptr(), assignment.data_ptr(), n_obj.data_ptr(), model.data_ptr(), _int32s(type_count),
+                                                 len(type_count) + 1, _camera(camera), sigma_px, sigma_z, iters, damping, b, max_obj, pose_out.data_ptr(), fit.data_ptr(),
+                                                 information.data_ptr(), status.data_ptr(), assignment_out.data_ptr(), hypothesis.data_ptr(), cost.data_ptr(), stream),
+               "okp_refine_assignments")
+
+
 # ---- scoring labelled scenes -----------------------------------------------------------------------------------------------------------------
 def project_labels(camera, world_points, T_WC, scale, crop_x, crop_y, labels, stream):
     _lib.check(_lib.lib().okp_project_labels(_camera(camera), world_points.data_ptr(), world_points.shape[0], T_WC.data_ptr(), T_WC.shape[0], scale, crop_x, crop_y,

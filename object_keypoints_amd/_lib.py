@@ -121,6 +121,8 @@ SIGNATURES = [
     ("okp_change_frame", c_int, [c_void_p, c_int32, c_int, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     ("okp_refine_pose", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(okp_camera), c_double, c_double, c_int32, c_double, c_int32, c_int32,
                                 c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    ("okp_refine_assignments", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_int32), c_int32, POINTER(okp_camera), c_double, c_double, c_int32,
+                                       c_double, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     ("okp_fisheye_undistort", c_int, [POINTER(okp_camera), c_void_p, c_int32, c_void_p, c_void_p]),
     ("okp_camera_undistort", c_int, [POINTER(okp_camera), c_void_p, c_int32, c_void_p, c_void_p]),
     ("okp_project_labels", c_int, [POINTER(okp_camera), c_void_p, c_int32, c_void_p, c_int32, c_double, c_double, c_double, c_void_p, c_void_p]),

@@ -12,19 +12,12 @@
 //                                 all in registers; (3) two butterflies pick the winner and the runner-up by (cost, index); (4) lane 0 solves
 //                                 the winner and lane 1 the runner-up for the rotation (the same code with the eigenvectors accumulated) and
 //                                 measures the residuals; (5) lane s writes slot s of the assignment, lane 0 the rest.
-#include "okp_internal.h"
+#include "okp_pose_math.h"           // PoseTypes, pose_types, jacobi_sym, scatter_degenerate, horn_matrix
 
-#define OKP_POSE_MAX_TYPES 16        // K: the centre and up to fifteen key-point types (S <= 16 rows)
 static_assert(OKP_POSE_MAX_POINTS == 16, "a hypothesis' assignment is packed four bits per point pair into 64 bits");
 static_assert(OKP_POSE_MAX_POINTS <= 64, "one lane per table slot");
 
 namespace {
-
-struct PoseTypes {
-  int32_t K, S;
-  int32_t count[OKP_POSE_MAX_TYPES];   // [k]: model instances of type k (count[0] = 1: the centre)
-  int32_t base[OKP_POSE_MAX_TYPES];    // [k]: first model row / table slot of type k
-};
 
 // slot -> (type, index within the type)
 __device__ __forceinline__ void slot_type(const PoseTypes& t, int s, int& k, int& j) {
@@ -104,65 +97,6 @@ __global__ __launch_bounds__(64) void okp_rig_object_points_kernel(const RigPoin
   row[0] = src[0]; row[1] = src[1]; row[2] = src[2]; row[3] = src[3];
 }
 
-// Cyclic Jacobi on a symmetric N x N matrix held in registers: on return the diagonal of `a` holds the eigenvalues and, with V, the columns
-// of `v` the eigenvectors.  Converges quadratically; a 4 x 4 matrix is diagonal to rounding after five or six sweeps.
-template <int N, bool V>
-__device__ void jacobi_sym(double (&a)[N][N], double (&v)[N][N]) {
-  if (V) {
-#pragma unroll
-    for (int i = 0; i < N; ++i)
-#pragma unroll
-      for (int j = 0; j < N; ++j) v[i][j] = i == j ? 1.0 : 0.0;
-  }
-  for (int sweep = 0; sweep < 30; ++sweep) {
-    double off = 0.0, diag = 0.0;
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-      diag += a[i][i] * a[i][i];
-#pragma unroll
-      for (int j = i + 1; j < N; ++j) off += a[i][j] * a[i][j];
-    }
-    if (!(off > 1e-36 * (diag + off))) break;          // off-diagonal norm below 1e-18 of the matrix norm (or all zero)
-#pragma unroll
-    for (int p = 0; p < N - 1; ++p) {
-#pragma unroll
-      for (int q = p + 1; q < N; ++q) {
-        const double apq = a[p][q];
-        if (apq == 0.0) continue;
-        const double theta = (a[q][q] - a[p][p]) / (2.0 * apq);
-        const double t = copysign(1.0, theta) / (fabs(theta) + sqrt(theta * theta + 1.0));     // (theta^2 = inf: t = 0)
-        const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-        a[p][p] -= t * apq;
-        a[q][q] += t * apq;
-        a[p][q] = 0.0; a[q][p] = 0.0;
-#pragma unroll
-        for (int r = 0; r < N; ++r) {
-          if (r != p && r != q) {
-            const double arp = a[r][p], arq = a[r][q];
-            a[r][p] = c * arp - s * arq; a[p][r] = a[r][p];
-            a[r][q] = s * arp + c * arq; a[q][r] = a[r][q];
-          }
-          if (V) {
-            const double vrp = v[r][p], vrq = v[r][q];
-            v[r][p] = c * vrp - s * vrq;
-            v[r][q] = s * vrp + c * vrq;
-          }
-        }
-      }
-    }
-  }
-}
-
-// collinear points: the second-largest eigenvalue of their scatter is <= OKP_POSE_DEGENERACY * trace
-__device__ bool scatter_degenerate(double (&A)[3][3]) {
-  double none[3][3];
-  const double trace = A[0][0] + A[1][1] + A[2][2];
-  jacobi_sym<3, false>(A, none);
-  const double e0 = A[0][0], e1 = A[1][1], e2 = A[2][2];
-  const double mid = fmax(fmin(e0, e1), fmin(fmax(e0, e1), e2));     // the median of the three
-  return !(mid > OKP_POSE_DEGENERACY * trace);
-}
-
 struct PoseLds {
   double p[OKP_POSE_MAX_POINTS][3];    // by point pair t (the filled slots in slot order): the detected point, then centred on their mean
   double m[OKP_POSE_MAX_POINTS][3];    // by model row: the model point minus model row 0
@@ -208,21 +142,6 @@ __device__ void hypothesis_sums(const PoseLds& L, const PoseTypes& T, int h, dou
       ++t;
     }
   }
-}
-
-// Horn's matrix of the correlation M = sum m p^T: its largest eigenvalue's eigenvector is the unit quaternion (w, x, y, z) of the rotation
-// that best carries m onto p
-__device__ __forceinline__ void horn_matrix(const double (&M)[3][3], double (&N)[4][4]) {
-  N[0][0] = M[0][0] + M[1][1] + M[2][2];
-  N[1][1] = M[0][0] - M[1][1] - M[2][2];
-  N[2][2] = -M[0][0] + M[1][1] - M[2][2];
-  N[3][3] = -M[0][0] - M[1][1] + M[2][2];
-  N[0][1] = N[1][0] = M[1][2] - M[2][1];
-  N[0][2] = N[2][0] = M[2][0] - M[0][2];
-  N[0][3] = N[3][0] = M[0][1] - M[1][0];
-  N[1][2] = N[2][1] = M[0][1] + M[1][0];
-  N[1][3] = N[3][1] = M[2][0] + M[0][2];
-  N[2][3] = N[3][2] = M[1][2] + M[2][1];
 }
 
 struct PoseParams {
@@ -391,27 +310,6 @@ __global__ __launch_bounds__(64) void okp_object_pose_kernel(const PoseParams P)
     P.used[blockIdx.x] = live ? n : 0;
     P.status[blockIdx.x] = status;
   }
-}
-
-// type_count [K-1] -> the slot layout; 0 on success (the message names what is wrong)
-int pose_types(const char* fn, const int32_t* type_count, int K, int K_max, PoseTypes& t, long long* hypotheses) {
-  if (K < 2 || K > K_max) { okp_set_error("%s: K = %d outside [2, %d] (the centre and the key-point types)", fn, K, K_max); return OKP_EINVAL; }
-  if (!type_count) { okp_set_error("%s: null type_count", fn); return OKP_EINVAL; }
-  t = PoseTypes{};
-  t.K = K; t.count[0] = 1; t.base[0] = 0;
-  int S = 1;
-  long long H = 1;
-  for (int k = 1; k < K; ++k) {
-    const int c = type_count[k - 1];
-    if (c < 1) { okp_set_error("%s: type_count[%d] = %d; every type has at least one key point per object", fn, k - 1, c); return OKP_EINVAL; }
-    t.count[k] = c; t.base[k] = S;
-    S += c;
-    if (S > OKP_POSE_MAX_POINTS) { okp_set_error("%s: type_count gives S = 1 + sum(type_count) > %d model points", fn, OKP_POSE_MAX_POINTS); return OKP_EINVAL; }
-    for (int i = 2; i <= c; ++i) H *= i;                          // (S <= 16 rows: at most 15! = 1.3e12, no overflow)
-  }
-  t.S = S;
-  if (hypotheses) *hypotheses = H;
-  return OKP_OK;
 }
 
 }  // namespace

@@ -12,14 +12,9 @@
 //   the information matrix.  A status, once set, sticks; the arithmetic runs on regardless (no early exit: the four objects of a wave stay
 //   in step) and its results are dropped at the end.
 // No sin, cos or atan2: the step's rotation is the matrix of the unit quaternion (1, w/2) / |(1, w/2)|.
-#include "okp_internal.h"
+#include "okp_pose_math.h"           // finite64, refine_pair_terms, refine_butterfly, refine_step
 
 #pragma clang fp contract(off)
-
-#define OKP_REFINE_LANES 16
-#define OKP_REFINE_SUMS 30           // H (21, upper triangle by rows), g (6), sum(e_u^2 + e_v^2), sum e_z^2, sum (q_z - Z)^2
-static_assert(OKP_POSE_MAX_POINTS <= OKP_REFINE_LANES, "one lane per table slot");
-static_assert(64 % OKP_REFINE_LANES == 0, "whole objects per wave");
 
 namespace {
 
@@ -29,8 +24,6 @@ struct RefineParams {
   double kx, ky, kz, sigma_px, damping;          // fx / sigma_px, fy / sigma_px, 1 / sigma_z (0: no depth term), formed once on the host
   double* pose_out; double* fit; double* information; int32_t* status;
 };
-
-__device__ __forceinline__ bool finite64(double x) { return fabs(x) < __builtin_inf(); }      // (false for NaN)
 
 __global__ __launch_bounds__(64) void okp_refine_pose_kernel(const RefineParams P) {
   const int lane = threadIdx.x, sub = lane & (OKP_REFINE_LANES - 1), grp = lane / OKP_REFINE_LANES;
@@ -69,104 +62,16 @@ __global__ __launch_bounds__(64) void okp_refine_pose_kernel(const RefineParams 
   double acc[OKP_REFINE_SUMS];
   double J0 = nan, px0 = nan, dz0 = nan;
   for (int k = 0;; ++k) {
-    // this lane's pair at the iterate (R, t): residuals e and Jacobian rows j = (p x a, a), a = de/dq
-    const double p0 = (R[0] * m0 + R[1] * m1) + R[2] * m2, p1 = (R[3] * m0 + R[4] * m1) + R[5] * m2, p2 = (R[6] * m0 + R[7] * m1) + R[8] * m2;
-    const double q0 = p0 + t[0], q1 = p1 + t[1], q2 = p2 + t[2];
+    // this lane's terms at the iterate (R, t), summed over the object's lanes
+    const double q2 = refine_pair_terms(R, t, pair, m0, m1, m2, u, v, Z, kx, ky, kz, acc);
     const bool behind = pair && q2 <= 0.0;
     const bool any_behind = ((__ballot(behind) >> shift) & 0xffffull) != 0ull;
     if (status == 0 && any_behind) status = OKP_REFINE_BEHIND;
-    const double iz = 1.0 / q2, xn = q0 * iz, yn = q1 * iz, dz = q2 - Z;
-    double e[3] = {kx * (xn - u), ky * (yn - v), kz * dz};
-    const double au0 = kx * iz, au2 = -(au0 * xn), av1 = ky * iz, av2 = -(av1 * yn);
-    double j[3][6] = {{p1 * au2, p2 * au0 - p0 * au2, -(p1 * au0), au0, 0.0, au2},
-                      {p1 * av2 - p2 * av1, -(p0 * av2), p0 * av1, 0.0, av1, av2},
-                      {p1 * kz, -(p0 * kz), 0.0, 0.0, 0.0, kz}};
-    double dz_own = dz;
-    if (!pair) {
-      dz_own = 0.0;
-#pragma unroll
-      for (int r = 0; r < 3; ++r) {
-        e[r] = 0.0;
-#pragma unroll
-        for (int c = 0; c < 6; ++c) j[r][c] = 0.0;
-      }
-    }
-    {
-      int idx = 0;
-#pragma unroll
-      for (int r = 0; r < 6; ++r)
-#pragma unroll
-        for (int c = r; c < 6; ++c) acc[idx++] = (j[0][r] * j[0][c] + j[1][r] * j[1][c]) + j[2][r] * j[2][c];
-#pragma unroll
-      for (int r = 0; r < 6; ++r) acc[21 + r] = (j[0][r] * e[0] + j[1][r] * e[1]) + j[2][r] * e[2];
-      acc[27] = e[0] * e[0] + e[1] * e[1];
-      acc[28] = e[2] * e[2];
-      acc[29] = dz_own * dz_own;
-    }
-#pragma unroll
-    for (int off = OKP_REFINE_LANES / 2; off > 0; off >>= 1)
-#pragma unroll
-      for (int i = 0; i < OKP_REFINE_SUMS; ++i) acc[i] += __shfl_xor(acc[i], off);
+    refine_butterfly(acc);
     if (k == 0) { J0 = acc[27] + acc[28]; px0 = acc[27]; dz0 = acc[29]; }
     if (k == P.iters) break;                                      // acc holds the sums at the final iterate
-
-    // (H + mu diag H) d = -g by Cholesky; the same numbers, so the same decision, in every lane of the object
-    double L[6][6], d[6];
-    {
-      int idx = 0;
-#pragma unroll
-      for (int r = 0; r < 6; ++r)
-#pragma unroll
-        for (int c = r; c < 6; ++c) L[c][r] = acc[idx++];         // the lower triangle of H
-    }
-    bool singular = false;
-#pragma unroll
-    for (int c = 0; c < 6; ++c) {
-      const double h = L[c][c];
-      double piv = h + P.damping * h;
-#pragma unroll
-      for (int q = 0; q < c; ++q) piv -= L[c][q] * L[c][q];
-      singular = singular || !(piv > 1e-12 * h) || !(piv < inf);
-      const double inv = 1.0 / sqrt(piv);
-      L[c][c] = inv;                                              // (the reciprocal of the diagonal entry)
-#pragma unroll
-      for (int r = c + 1; r < 6; ++r) {
-        double s = L[r][c];
-#pragma unroll
-        for (int q = 0; q < c; ++q) s -= L[r][q] * L[c][q];
-        L[r][c] = s * inv;
-      }
-    }
+    const bool singular = refine_step(acc, P.damping, R, t);
     if (status == 0 && singular) status = OKP_REFINE_SINGULAR;
-#pragma unroll
-    for (int r = 0; r < 6; ++r) {                                 // L y = -g
-      double s = -acc[21 + r];
-#pragma unroll
-      for (int q = 0; q < r; ++q) s -= L[r][q] * d[q];
-      d[r] = s * L[r][r];
-    }
-#pragma unroll
-    for (int r = 5; r >= 0; --r) {                                // L^T d = y
-      double s = d[r];
-#pragma unroll
-      for (int q = r + 1; q < 6; ++q) s -= L[q][r] * d[q];
-      d[r] = s * L[r][r];
-    }
-    // R <- C(d_w) R, t <- t + d_t; C is the matrix of the unit quaternion (1, d_w / 2) / |(1, d_w / 2)|
-    const double h0 = 0.5 * d[0], h1 = 0.5 * d[1], h2 = 0.5 * d[2];
-    const double w = 1.0 / sqrt(1.0 + ((h0 * h0 + h1 * h1) + h2 * h2)), x = h0 * w, y = h1 * w, z = h2 * w;
-    double C[9];
-    C[0] = w * w + x * x - y * y - z * z; C[1] = 2.0 * (x * y - w * z);         C[2] = 2.0 * (x * z + w * y);
-    C[3] = 2.0 * (y * x + w * z);         C[4] = w * w - x * x + y * y - z * z; C[5] = 2.0 * (y * z - w * x);
-    C[6] = 2.0 * (z * x - w * y);         C[7] = 2.0 * (z * y + w * x);         C[8] = w * w - x * x - y * y + z * z;
-    double Rn[9];
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-#pragma unroll
-      for (int c = 0; c < 3; ++c) Rn[3 * r + c] = (C[3 * r] * R[c] + C[3 * r + 1] * R[3 + c]) + C[3 * r + 2] * R[6 + c];
-#pragma unroll
-    for (int i = 0; i < 9; ++i) R[i] = Rn[i];
-    t[0] += d[3]; t[1] += d[4]; t[2] += d[5];
   }
   const double J1 = acc[27] + acc[28];
   if (status == 0 && (!(J1 < inf) || J1 > J0 + 1e-12 * n_pairs)) status = OKP_REFINE_REJECTED;

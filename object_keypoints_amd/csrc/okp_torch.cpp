@@ -699,6 +699,35 @@ void refine_pose(at::ArrayRef<double> camera, const Tensor& tab, const Tensor& p
                            information.data_ptr<double>(), status.data_ptr<int32_t>(), sp(stream)), "okp_refine_pose");
 }
 
+// Resolving interchangeable key points (csrc/okp_refine_assign.hip): refine_pose's inputs and type_count -> the winner's pose_out, fit, information,
+// status and assignment_out [B,max_obj,S], hypothesis [B,max_obj,2] (winner, runner-up), cost [B,max_obj,2]
+void refine_assignments(at::ArrayRef<double> camera, const Tensor& tab, const Tensor& pose, const Tensor& assignment, const Tensor& n_obj, const Tensor& model,
+                        at::IntArrayRef type_count, double sigma_px, double sigma_z, int64_t iters, double damping, const Tensor& pose_out, const Tensor& fit,
+                        const Tensor& information, const Tensor& status, const Tensor& assignment_out, const Tensor& hypothesis, const Tensor& cost, int64_t stream) {
+  check_dev(tab, at::kDouble, "tab"); check_dev(pose, at::kDouble, "pose"); check_dev(assignment, at::kInt, "assignment"); check_dev(n_obj, at::kInt, "n_obj");
+  check_dev(model, at::kDouble, "model"); check_dev(pose_out, at::kDouble, "pose_out"); check_dev(fit, at::kDouble, "fit"); check_dev(information, at::kDouble, "information");
+  check_dev(status, at::kInt, "status"); check_dev(assignment_out, at::kInt, "assignment_out"); check_dev(hypothesis, at::kInt, "hypothesis"); check_dev(cost, at::kDouble, "cost");
+  TORCH_CHECK(tab.dim() == 4 && tab.size(3) == 4, "okp: tab is [B,max_obj,S,4] float64");
+  const int64_t B = tab.size(0), max_obj = tab.size(1), S = tab.size(2);
+  int64_t want = 1;
+  for (auto c : type_count) want += c;
+  TORCH_CHECK(want == S && model.numel() == S * 3, "okp: tab has S = 1 + sum(type_count) slots and model is [S,3] float64");
+  TORCH_CHECK(pose.numel() == B * max_obj * 12 && assignment.numel() == B * max_obj * S && n_obj.numel() == B,
+              "okp: refine_assignments inputs are pose [B,max_obj,12], assignment [B,max_obj,S], n_obj [B] and model [S,3]");
+  TORCH_CHECK(pose_out.numel() == B * max_obj * 12 && fit.numel() == B * max_obj * 4 && information.numel() == B * max_obj * 36 && status.numel() == B * max_obj &&
+              assignment_out.numel() == B * max_obj * S && hypothesis.numel() == B * max_obj * 2 && cost.numel() == B * max_obj * 2,
+              "okp: refine_assignments outputs are pose_out [B,max_obj,12], fit [B,max_obj,4], information [B,max_obj,36], status [B,max_obj], assignment_out [B,max_obj,S], "
+              "hypothesis and cost [B,max_obj,2]");
+  TORCH_CHECK(iters >= INT32_MIN && iters <= INT32_MAX, "okp: iters does not fit an int32");
+  const okp_camera cam = camera_of(camera);
+  std::vector<int32_t> tc(type_count.begin(), type_count.end());
+  tc.push_back(0);
+  check_rc(okp_refine_assignments(tab.data_ptr<double>(), pose.data_ptr<double>(), assignment.data_ptr<int32_t>(), n_obj.data_ptr<int32_t>(), model.data_ptr<double>(),
+                                  tc.data(), (int32_t)type_count.size() + 1, &cam, sigma_px, sigma_z, (int32_t)iters, damping, (int32_t)B, (int32_t)max_obj,
+                                  pose_out.data_ptr<double>(), fit.data_ptr<double>(), information.data_ptr<double>(), status.data_ptr<int32_t>(),
+                                  assignment_out.data_ptr<int32_t>(), hypothesis.data_ptr<int32_t>(), cost.data_ptr<double>(), sp(stream)), "okp_refine_assignments");
+}
+
 void lift_peaks(at::ArrayRef<double> camera, const Tensor& count, const Tensor& xyc, const Tensor& depth, int64_t max_x, int64_t max_y, const Tensor& out, int64_t stream) {
   TORCH_CHECK(xyc.is_cuda() && xyc.dim() == 4 && xyc.scalar_type() == at::kFloat && depth.is_cuda() && depth.scalar_type() == at::kFloat && depth.dim() == 4 && depth.is_contiguous() &&
               depth.size(0) == xyc.size(0) && depth.size(1) == xyc.size(1) && count.scalar_type() == at::kInt && out.scalar_type() == at::kDouble &&
@@ -866,6 +895,9 @@ TORCH_LIBRARY(okp, m) {
         "Tensor? overflow_in=None) -> ()", change_frame);
   m.def("refine_pose(float[] camera, Tensor tab, Tensor pose, Tensor assignment, Tensor n_obj, Tensor model, float sigma_px, float sigma_z, int iters, float damping, "
         "Tensor(a!) pose_out, Tensor(b!) fit, Tensor(c!) information, Tensor(d!) status, int stream) -> ()", refine_pose);
+  m.def("refine_assignments(float[] camera, Tensor tab, Tensor pose, Tensor assignment, Tensor n_obj, Tensor model, int[] type_count, float sigma_px, float sigma_z, int iters, "
+        "float damping, Tensor(a!) pose_out, Tensor(b!) fit, Tensor(c!) information, Tensor(d!) status, Tensor(e!) assignment_out, Tensor(f!) hypothesis, Tensor(g!) cost, "
+        "int stream) -> ()", refine_assignments);
   m.def("rig_fuse(Tensor points, Tensor poses, int[] type_count, float merge_radius, float object_radius, Tensor(a!) fused, Tensor(b!) n_fused, Tensor(c!) views, "
         "Tensor(d!) object, Tensor(e!) member, Tensor(f!) n_obj, Tensor(g!) overflow, int stream, Tensor? overflow_in=None) -> ()", rig_fuse);
   m.def("project_labels(float[] camera, Tensor world_points, Tensor T_WC, float scale, float crop_x, float crop_y, Tensor(a!) labels, int stream) -> ()", project_labels);

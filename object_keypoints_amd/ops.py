@@ -1413,6 +1413,8 @@ def change_frame(T, points=None, poses=None, inverse=False, overflow=None, out_p
 # ---- each object's pose refined against its key points' bearings (okp_refine_pose, csrc/okp_refine.hip; the specification is include/okp.h) ----
 REFINE_SKIPPED, REFINE_SINGULAR, REFINE_BEHIND, REFINE_REJECTED = 1, 2, 4, 8      # status words of refine_pose()
 REFINE_MAX_ITERS = 16                                                            # include/okp.h OKP_REFINE_MAX_ITERS
+REFINE_NONE = 16                                                                 # refine_assignments(): every assignment ended with a status
+REFINE_MAX_HYPOTHESES = 24                                                       # include/okp.h OKP_REFINE_MAX_HYPOTHESES
 
 
 class RefineConfig:
@@ -1420,9 +1422,11 @@ class RefineConfig:
         sigma_px  map pixels: the standard deviation of a key point's pixel position (positive, finite)
         sigma_z   metres: the standard deviation of a key point's measured depth (positive; inf: the depth is not used at all)
         iters     Gauss-Newton steps, 1 .. REFINE_MAX_ITERS: always exactly this many
-        damping   mu >= 0 of (H + mu diag H) d = -g."""
+        damping   mu >= 0 of (H + mu diag H) d = -g
+        resolve_assignment   (keyword, default False) a pipeline then refines every assignment of the interchangeable key points, each from
+                  its own rigid fit, and keeps the one of least final cost (okp_refine_assignments) instead of refining the fit's own."""
 
-    def __init__(self, sigma_px=0.25, sigma_z=0.05, iters=6, damping=1e-9):
+    def __init__(self, sigma_px=0.25, sigma_z=0.05, iters=6, damping=1e-9, *, resolve_assignment=False):
         def number(name, v):
             if isinstance(v, bool):
                 raise OkpError(f"RefineConfig: {name} = {v!r} is not a number")
@@ -1441,21 +1445,17 @@ class RefineConfig:
         if isinstance(iters, bool) or not isinstance(iters, (int, np.integer)) or not 1 <= int(iters) <= REFINE_MAX_ITERS:
             raise OkpError(f"RefineConfig: iters = {iters!r}: an integer in [1, {REFINE_MAX_ITERS}]")
         self.iters = int(iters)
+        if not isinstance(resolve_assignment, (bool, np.bool_)):
+            raise OkpError(f"RefineConfig: resolve_assignment = {resolve_assignment!r} must be True or False")
+        self.resolve_assignment = bool(resolve_assignment)
 
     def __repr__(self):
-        return f"RefineConfig(sigma_px={self.sigma_px}, sigma_z={self.sigma_z}, iters={self.iters}, damping={self.damping})"
+        flag = ", resolve_assignment=True" if self.resolve_assignment else ""
+        return f"RefineConfig(sigma_px={self.sigma_px}, sigma_z={self.sigma_z}, iters={self.iters}, damping={self.damping}{flag})"
 
 
-def refine_pose(tab, pose, n_obj, model, cam, cfg):
-    """Every object's fitted pose refined against the bearings of its key points (okp_refine_pose; cost, step, statuses and outputs are
-    specified in include/okp.h).  tab [B,max_obj,S,4] float64 (object_points); pose: object_pose()'s dict (its "pose" [B,max_obj,12] and
-    "assignment" [B,max_obj,S] are read); n_obj int32 [B] (0-d for B = 1); model [S,3] float64 (device); cam: the okp_camera the table was
-    lifted through (only fx and fy are read); cfg: a RefineConfig
-    -> {"pose" [B,max_obj,12] float64 (the refined [R | t]; the input pose bit for bit where the status is not 0), "fit" [B,max_obj,4]
-        float64 (reprojection rmse in map pixels before and after, depth rmse in metres before and after; NaN where the status is not 0),
-        "information" [B,max_obj,36] float64 (H = J^T J at the refined pose, row-major 6 x 6 over (rotation, translation): the inverse
-        covariance under the two sigmas; NaN where the status is not 0), "status" [B,max_obj] int32 (0, REFINE_SKIPPED, REFINE_SINGULAR,
-        REFINE_BEHIND or REFINE_REJECTED)}.  One launch, no host sync."""
+def _refine_inputs(tab, pose, n_obj, model, cam, cfg):
+    """The argument checks refine_pose and refine_assignments share -> (fitted, assignment, b, max_obj, s, dev)."""
     if not isinstance(cfg, RefineConfig):
         raise OkpError("cfg must be an ops.RefineConfig")
     if not isinstance(cam, _lib.okp_camera):
@@ -1479,6 +1479,20 @@ def refine_pose(tab, pose, n_obj, model, cam, cfg):
         raise OkpError(f"n_obj must be int32 [{b}] on the table's device: the objects of each frame")
     if model.dtype != torch.float64 or tuple(model.shape) != (s, 3) or model.device != dev:
         raise OkpError(f"model must be float64 [{s},3] on the table's device (object_model)")
+    return fitted, assignment, b, max_obj, s, dev
+
+
+def refine_pose(tab, pose, n_obj, model, cam, cfg):
+    """Every object's fitted pose refined against the bearings of its key points (okp_refine_pose; cost, step, statuses and outputs are
+    specified in include/okp.h).  tab [B,max_obj,S,4] float64 (object_points); pose: object_pose()'s dict (its "pose" [B,max_obj,12] and
+    "assignment" [B,max_obj,S] are read); n_obj int32 [B] (0-d for B = 1); model [S,3] float64 (device); cam: the okp_camera the table was
+    lifted through (only fx and fy are read); cfg: a RefineConfig
+    -> {"pose" [B,max_obj,12] float64 (the refined [R | t]; the input pose bit for bit where the status is not 0), "fit" [B,max_obj,4]
+        float64 (reprojection rmse in map pixels before and after, depth rmse in metres before and after; NaN where the status is not 0),
+        "information" [B,max_obj,36] float64 (H = J^T J at the refined pose, row-major 6 x 6 over (rotation, translation): the inverse
+        covariance under the two sigmas; NaN where the status is not 0), "status" [B,max_obj] int32 (0, REFINE_SKIPPED, REFINE_SINGULAR,
+        REFINE_BEHIND or REFINE_REJECTED)}.  One launch, no host sync."""
+    fitted, assignment, b, max_obj, s, dev = _refine_inputs(tab, pose, n_obj, model, cam, cfg)
     pose_out = torch.empty((b, max_obj, 12), dtype=torch.float64, device=dev)
     fit = torch.empty((b, max_obj, 4), dtype=torch.float64, device=dev)
     information = torch.empty((b, max_obj, 36), dtype=torch.float64, device=dev)
@@ -1486,6 +1500,43 @@ def refine_pose(tab, pose, n_obj, model, cam, cfg):
     _dispatch(_ops().refine_pose, _cam_list(cam), tab.contiguous(), fitted.contiguous(), assignment.contiguous(), n_obj.reshape(b).contiguous(), model.contiguous(),
               cfg.sigma_px, cfg.sigma_z, cfg.iters, cfg.damping, pose_out, fit, information, status, stream_int())
     return {"pose": pose_out, "fit": fit, "information": information, "status": status}
+
+
+def refine_assignments(tab, pose, n_obj, model, type_count, cam, cfg):
+    """Every assignment of every object's interchangeable key points refined, each from its own rigid fit, and the one of least final cost
+    kept (okp_refine_assignments; hypotheses, selection and outputs are specified in include/okp.h).  The arguments of refine_pose plus
+    type_count, the K-1 counts of object_pose; pose (object_pose()'s dict) is the fallback, not the start.
+    -> refine_pose's "pose", "fit", "information" and "status" (0, REFINE_SKIPPED or REFINE_NONE: every assignment ended with a status) of the
+        winner, "assignment" [B,max_obj,S] int32 (the winner's model row of each slot, -1 = empty; the input assignment where the status is
+        not 0), "hypothesis" [B,max_obj,2] int32 (the indices of the winner and the runner-up, -1 = none), "cost" [B,max_obj,2] float64 (their
+        final costs, NaN = none: a runner-up close to the winner means the data cannot tell the two apart).  One launch, no host sync."""
+    fitted, assignment, b, max_obj, s, dev = _refine_inputs(tab, pose, n_obj, model, cam, cfg)
+    tc, want = _pose_type_count(type_count, "type_count")
+    if want != s:
+        raise OkpError(f"tab has {s} slots per object, type_count gives S = 1 + sum(type_count) = {want}")
+    check_refine_hypotheses(tc)
+    pose_out = torch.empty((b, max_obj, 12), dtype=torch.float64, device=dev)
+    fit = torch.empty((b, max_obj, 4), dtype=torch.float64, device=dev)
+    information = torch.empty((b, max_obj, 36), dtype=torch.float64, device=dev)
+    cost = torch.empty((b, max_obj, 2), dtype=torch.float64, device=dev)
+    status = torch.empty((b, max_obj), dtype=torch.int32, device=dev)
+    assignment_out = torch.empty((b, max_obj, s), dtype=torch.int32, device=dev)
+    hypothesis = torch.empty((b, max_obj, 2), dtype=torch.int32, device=dev)
+    _dispatch(_ops().refine_assignments, _cam_list(cam), tab.contiguous(), fitted.contiguous(), assignment.contiguous(), n_obj.reshape(b).contiguous(), model.contiguous(),
+              tc, cfg.sigma_px, cfg.sigma_z, cfg.iters, cfg.damping, pose_out, fit, information, status, assignment_out, hypothesis, cost, stream_int())
+    return {"pose": pose_out, "fit": fit, "information": information, "status": status, "assignment": assignment_out, "hypothesis": hypothesis, "cost": cost}
+
+
+def check_refine_hypotheses(type_count):
+    """prod c_k! of an object model's type counts, refused above REFINE_MAX_HYPOTHESES: what refine_assignments can enumerate."""
+    hyps = 1
+    for c in type_count:
+        for i in range(2, int(c) + 1):
+            hyps *= i
+    if hyps > REFINE_MAX_HYPOTHESES:
+        raise OkpError(f"type_count = {list(type_count)} gives prod(c_k!) = {hyps} assignments per object, above {REFINE_MAX_HYPOTHESES}: "
+                       "resolve_assignment cannot enumerate them (resolve_assignment=False keeps working)")
+    return hyps
 
 
 # ---- scoring labelled scenes (csrc/okp_targets.hip) ---------------------------------------------------------------------------------

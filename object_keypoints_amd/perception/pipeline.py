@@ -581,10 +581,13 @@ def _to_host(fields):
 
 def _pose_fields(pose, n, refine=None):
     """What the readers take of frame n of an ops.object_pose dict: "pose" [max_obj,12], "fit" [max_obj,2], "status" [max_obj]; with an
-    ops.refine_pose dict also "refine" (the refined pose [max_obj,12]), "refine_fit" [max_obj,4], "information" [max_obj,36], "refine_status"."""
+    ops.refine_pose dict also "refine" (the refined pose [max_obj,12]), "refine_fit" [max_obj,4], "information" [max_obj,36], "refine_status";
+    with an ops.refine_assignments dict also "refine_assignment" [max_obj,S], "refine_hypothesis" [max_obj,2] and "refine_cost" [max_obj,2]."""
     fields = {"pose": pose["pose"][n], "fit": pose["fit"][n], "status": pose["status"][n]}
     if refine is not None:
         fields.update(refine=refine["pose"][n], refine_fit=refine["fit"][n], information=refine["information"][n], refine_status=refine["status"][n])
+        if "hypothesis" in refine:
+            fields.update(refine_assignment=refine["assignment"][n], refine_hypothesis=refine["hypothesis"][n], refine_cost=refine["cost"][n])
     return fields
 
 
@@ -612,8 +615,12 @@ def _refine_entries(rec, o, T_CO):
     if T_CO is not None:
         T = np.eye(4)
         T[:3] = rec["refine"][o].reshape(3, 4)
-    return {'T_CO_refined': T, 'reprojection_rmse': (float(fit[o, 0]), float(fit[o, 1])), 'depth_rmse': (float(fit[o, 2]), float(fit[o, 3])),
-            'pose_information': rec["information"][o].reshape(6, 6).copy(), 'refine_status': int(rec["refine_status"][o])}
+    entries = {'T_CO_refined': T, 'reprojection_rmse': (float(fit[o, 0]), float(fit[o, 1])), 'depth_rmse': (float(fit[o, 2]), float(fit[o, 3])),
+               'pose_information': rec["information"][o].reshape(6, 6).copy(), 'refine_status': int(rec["refine_status"][o])}
+    if "refine_hypothesis" in rec:           # resolve_assignment: the winning assignment (model row per slot), (winner, runner-up) indices and costs
+        entries.update(assignment_refined=rec["refine_assignment"][o].copy(), refine_hypothesis=tuple(int(h) for h in rec["refine_hypothesis"][o]),
+                       refine_cost=tuple(float(c) for c in rec["refine_cost"][o]))
+    return entries
 
 
 def _pose_entries(rec, o, key):
@@ -722,7 +729,10 @@ class _ObjectStage:
     and uploaded once per device): okp_object_pose -> "pose", ops.object_pose's dict plus "tab".  max_rmse (metres, optional): objects that
     fit worse carry ops.POSE_POOR.
     Refinement (refine = ops.RefineConfig(...), needs the pose and the camera the table was lifted through): okp_refine_pose -> "refine",
-    ops.refine_pose's dict.  "pose" keeps its bits; the world-frame change and the tracker are fed the refined pose from here on.
+    ops.refine_pose's dict.  "pose" keeps its bits; the world-frame change and the tracker are fed the refined pose from here on.  With
+    RefineConfig(..., resolve_assignment=True) the one launch is okp_refine_assignments instead - every assignment of the interchangeable key
+    points refined, the one of least final cost kept - and "refine" is ops.refine_assignments' dict ("assignment", "hypothesis", "cost" too);
+    a model with more than ops.REFINE_MAX_HYPOTHESES assignments is refused at construction.
     World frame (world_frame=True; the step's frame_pose [B,12] takes the table's frame to the world, an all-NaN row = missing in this tick):
     okp_change_frame on the step's points and, with the pose, on the table and the poses -> "world": {"T", "points", "overflow" (the
     step's word | ops.FRAME_MISSING)} and "tab", "pose".
@@ -752,6 +762,8 @@ class _ObjectStage:
                 raise OkpError("refine must be an ops.RefineConfig")
             if points_3d is None:
                 raise OkpError("refine without points_3d: the refinement starts from the pose of the object model")
+            if refine.resolve_assignment:
+                ops.check_refine_hypotheses(type_count)
         self.refine = refine
 
     def run(self, tab, n_obj, points, overflow, frame_pose, cam=None):
@@ -763,7 +775,10 @@ class _ObjectStage:
             model = self.model(tab.device)
             fed = out["pose"] = dict(ops.object_pose(tab, n_obj, model, self.type_count, self.max_rmse), tab=tab)
             if self.refine is not None:
-                out["refine"] = ops.refine_pose(tab, fed, n_obj, model, cam, self.refine)
+                if self.refine.resolve_assignment:
+                    out["refine"] = ops.refine_assignments(tab, fed, n_obj, model, self.type_count, cam, self.refine)
+                else:
+                    out["refine"] = ops.refine_pose(tab, fed, n_obj, model, cam, self.refine)
                 fed = dict(fed, pose=out["refine"]["pose"])          # what the world-frame change and the tracker take
         if frame_pose is not None:
             first = ops.change_frame(frame_pose, points=points.reshape((frame_pose.shape[0], -1, 4)), overflow=overflow)
@@ -893,7 +908,9 @@ class BatchedKeypointPipeline(_ObjectStagePipeline):
     the reprojection error of the same key points' bearings with the depth as a weak prior.  'T_WO', 'T_CO_track', 'T_WO_track' and 'velocity'
     then come from the refined pose - the fitted one where the refinement's status is not 0.  objects() adds 'T_CO_refined' (None where 'T_CO'
     is), 'reprojection_rmse' and 'depth_rmse' ((before, after): map pixels, metres), 'pose_information' (6 x 6, the inverse covariance over
-    (rotation, translation)) and 'refine_status', still in one device -> host copy.
+    (rotation, translation)) and 'refine_status', still in one device -> host copy.  With resolve_assignment=True the refinement also resolves
+    which interchangeable key point is which (okp_refine_assignments): objects() further adds 'assignment_refined' (the model row of each table
+    slot, -1 = empty), 'refine_hypothesis' (winner, runner-up; -1 = none) and 'refine_cost' (their final costs; NaN = none).
     world_frame=True, for a camera that moves: every step takes camera_pose, a float64 [N,12] tensor on the frames' device
     (ops.frame_poses(T_WC).to(device): camera coordinates -> world, one pose per stream and tick; an all-NaN row = the pose of that stream
     is missing in this tick); "world"["points"] is out["points"] in the world frame.  objects() adds 'p_W' next to 'p_C', 'T_WO' and
