@@ -44,7 +44,9 @@ extern "C" {
                                     okp_change_frame, OKP_FRAME_MISSING (points, tables and poses in a fixed world frame under a moving camera);
                                     okp_refine_pose, OKP_REFINE_* (each object's pose refined against its key points' bearings);
                                     okp_refine_assignments, OKP_REFINE_NONE, OKP_REFINE_MAX_HYPOTHESES (interchangeable key points resolved by
-                                    refining every assignment) */
+                                    refining every assignment);
+                                    okp_rig_bearings, okp_refine_pose_views, OKP_REFINE_MAX_VIEWS (a rig's object poses refined against every
+                                    camera's bearings) */
 
 /* OKP_F16: IEEE half activations / weights, fp32 accumulate (BASELINE configs[4]).
  * OKP_F32X3 (okp_conv plans only): fp32 activations, weights and results like OKP_F32 - every tensor argument of such a plan is an
@@ -782,7 +784,8 @@ int okp_change_frame(const double* T_dev, int32_t B, int inverse, const double* 
  *   pairs' terms in a fixed butterfly (the same bits on every run and from every binding) and agrees with a NumPy evaluation to rounding
  *   (tests/test_gpu_refine.py: 1e-9 on R and t).  pose_out must not overlap pose.
  * Limits.  Uniform weights: the confidences of the table are not used.  A symmetric model's assignment is taken from okp_object_pose as it
- * is.  The points of a rig (okp_rig_object_points) come from stereo triangulation, not from one camera's bearings: they are not refined.
+ * is.  The points of a rig (okp_rig_object_points) come from stereo triangulation, not from one camera's bearings and depth map: this entry point
+ * does not take them - a rig's poses are refined against the bearings of all its cameras by okp_refine_pose_views, below.
  * Refused on the host before any launch (OKP_EINVAL, the message names the argument): a null pointer, B or max_obj < 1, S outside
  * [1, OKP_POSE_MAX_POINTS], iters outside [1, OKP_REFINE_MAX_ITERS], sigma_px not positive and finite, sigma_z not positive (NaN included),
  * damping negative or not finite, cam->fx or cam->fy not positive and finite.
@@ -841,7 +844,8 @@ int okp_refine_pose(const double* tab_dev, const double* pose_dev, const int32_t
  *   As for okp_refine_pose the order of the sums over the pairs is not part of the contract (tests/test_gpu_refine_assign.py: 1e-9 on R, t).
  * Limits.  Uniform weights.  An exactly symmetric model gives equal costs by construction: the lowest index wins and cost[1] ~ cost[0]
  * tells the reader so.  With a quarter of a map pixel of pixel noise on top of 3 % depth noise about one valve in eleven still ends on a
- * wrong assignment (23 of 256 in the specification).  The objects of a rig are not refined, as before.
+ * wrong assignment (23 of 256 in the specification).  The objects of a rig have their own refinement, okp_refine_pose_views; their
+ * assignments are not resolved.
  * Refused on the host before any launch (OKP_EINVAL, the message names the argument): everything okp_refine_pose refuses, K outside
  * [2, 16], a type_count below 1, S > OKP_POSE_MAX_POINTS, prod c_k! > OKP_REFINE_MAX_HYPOTHESES, pose_out overlapping pose,
  * assignment_out overlapping assignment.
@@ -853,6 +857,92 @@ int okp_refine_assignments(const double* tab_dev, const double* pose_dev, const 
                            double sigma_px, double sigma_z, int32_t iters, double damping, int32_t B, int32_t max_obj, double* pose_out_dev,
                            double* fit_dev, double* information_dev, int32_t* status_dev, int32_t* assignment_out_dev,
                            int32_t* hypothesis_dev, double* cost_dev, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * Refining a rig's poses against every camera's bearings (csrc/okp_refine_views.hip).  okp_object_pose fits a rig's objects to FUSED points:
+ * a fused cluster is a confidence-weighted mean of per-pair two-view triangulations, each with the depth noise of a short baseline
+ * (z^2 / (f b) per pixel of disparity error), and the fit puts that noise straight into the rotation.  The measurements without it are the
+ * peaks themselves: an object seen by P pairs has up to 2P bearings per key point, and the pose that minimises their reprojection error in
+ * all 2P cameras at once is the maximum-likelihood estimate under pixel noise - a mean of triangulations is not.  Two entry points:
+ * the first collects the bearings of a fused tick, the second refines against a table of bearings and knows nothing of stereo.  There is no
+ * reference implementation: the specification is this comment (tests/refine_views_spec.py restates it in NumPy).
+ *
+ * okp_rig_bearings: the measurements of a fused tick -> obs [cap_f][S][2P][2] fp64, one bearing per object, table slot and camera; camera
+ * 2p is the left one of pair p, 2p + 1 its right one.  EVERY word is written by every call; (NaN, NaN) = no observation.
+ *   Inputs, all in device memory: count [2P][K] int32 and xyc [2P][K][cap][3] fp32 (okp_peak_nms), match [P][K][cap] int32 (okp_stereo_match),
+ *   member [P][K][cap], object [K][cap_f] and n_fused [K] int32 (okp_rig_fuse), and the calibration table of okp_stereo_triangulate_rig:
+ *   table[p] calibrates pair p, and a table of ONE entry is used for every pair; a longer one must hold n_table >= P entries.  The kernel
+ *   cannot check a device table: the caller validates the calibration before the upload.  type_count HOST [K-1], S = 1 + sum(type_count).
+ *   Objects are o < min(n_fused[0], cap_f); the rows of every other o are NaN.
+ *   For pair p, type k and left peak i < min(count[2p][k], cap) with c = member[p][k][i] >= 0 and o = object[k][c] >= 0 (type 0: o = c, a
+ *   centre cluster is its own object; object[0] is not read):
+ *     the table slot s of cluster c is the one okp_rig_object_points gives it - slot 0 for type 0 (where c = o); for type k >= 1 the first slot
+ *     of the type plus the rank of c among the clusters c' < min(n_fused[k], cap_f) of type k with object[k][c'] == o, in cluster order;
+ *     clusters of rank >= type_count[k-1] have no slot and are ignored, as they are there;
+ *     obs[o][s][2p] is the left peak xyc[2p][k][i], obs[o][s][2p+1] the right peak xyc[2p+1][k][j] with j = match[p][k][i].  (A member of a
+ *     cluster is a triangulated slot, so 0 <= j < min(count[2p+1][k], cap); a slot for which that does not hold gives neither entry.)
+ *   A peak (x, y) is undistorted by its OWN camera - the model and arithmetic of okp_camera_undistort, P = K, in fp64, NOT rounded to fp32 -
+ *   to (xu, yu) and written as the bearing ((xu - cx) / fx, (yu - cy) / fy): divisions.  The Hartley-Sturm correction is not applied: these
+ *   are the raw measurements.
+ *   A cluster holds at most one member per pair (okp_rig_fuse, step 2), so no entry has two sources and none is written twice; on a member
+ *   table that breaks that rule the lowest i counts.
+ *   One launch, one workgroup per object, no atomics, no host wait, capturable; the same bits on every run.
+ *   Refused on the host before any launch (OKP_EINVAL, the message names the argument): n_pairs outside [1, OKP_RIG_MAX_PAIRS], K outside
+ *   [2, OKP_RIG_MAX_TYPES], cap outside [1, 256], cap_f outside [1, OKP_RIG_MAX_FUSED], a type_count below 1, S > OKP_POSE_MAX_POINTS,
+ *   n_table < 1 or 1 < n_table < n_pairs, a null pointer.
+ *
+ * okp_refine_pose_views: one launch, one wave per object, its lanes split over the views and the table slots; fp64, no atomics, no host
+ * wait, capturable; the same bits on every run.
+ * Inputs, in device memory:
+ *   obs [B][max_obj][S][V][2] fp64   the bearing (u, v) of table slot s in view v, undistorted normalised image coordinates of that view;
+ *                                    an entry is FILLED when both halves are finite and EMPTY when both are NaN
+ *   views [V][14] fp64               row v = [R_v | t_v] row-major 3 x 4, taking coordinates of the table's frame (the rig frame) to camera
+ *                                    v's, then fx_v, fy_v (map pixels).  A captured graph reads it on every replay; the kernel cannot check
+ *                                    it: the caller validates it (finite, focal lengths positive) before the upload
+ *   pose [B][max_obj][12] fp64, assignment [B][max_obj][S] int32, n_obj [B] int32 (okp_object_pose), model [S][3] fp64.
+ * Host arguments: sigma_px (map pixels), iters, damping (mu), B, max_obj, S, V.
+ * Per object o < min(n_obj[b], max_obj).  Slot s has a model row when a = assignment[s] is in [0, S): m_a = model[a].  The observations are
+ * the filled entries (s, v) of the slots with a model row; n_obs counts them.
+ *   Cost.  With p = R m_a, X = p + t (the table's frame) and q = R_v X + t_v (camera v's):
+ *     e_u = fx_v (q_x/q_z - u) / sigma_px,  e_v = fy_v (q_y/q_z - v) / sigma_px;   J(R, t) = sum over the observations of (e_u^2 + e_v^2).
+ *     There is no depth term.
+ *   One step.  The parameters, the update R <- C(w) R, t <- t + d, the damped normal equations, the Cholesky factorisation with its pivot rule
+ *     and C(w) are those of okp_refine_pose.  The Jacobian rows follow from dX/dw = -[p]x and dX/dd = I: a row is (p x b, b) with
+ *     b = R_v^T a and a = de/dq:  a_u = (fx_v/sigma_px) (1/q_z, 0, -q_x/q_z^2),  a_v = (fy_v/sigma_px) (0, 1/q_z, -q_y/q_z^2).
+ *   Iteration.  Exactly `iters` steps from the input pose; no line search, no early exit; cost, H and g are evaluated once more at the final
+ *     iterate.
+ *   Status, the first of these to occur in the order of evaluation (0 when none does), with okp_refine_pose's words:
+ *     OKP_REFINE_SKIPPED   before the first step: one of the 12 values of the input pose is not finite; one of the object's S x V entries has
+ *                          exactly one NaN half, or an infinite half; or fewer than 3 slots have a model row and at least one observation
+ *     OKP_REFINE_BEHIND    q_z <= 0 for some observation at an iterate (the start, every intermediate one and the final one; tested before
+ *                          that iterate's solve)
+ *     OKP_REFINE_SINGULAR  a Cholesky pivot that is <= 1e-12 x its diagonal entry of H, or not finite
+ *     OKP_REFINE_REJECTED  after the last step: J_final is not finite, or J_final > J_initial + 1e-12 x n_obs
+ *   Outputs, all written by every call:
+ *     pose_out [B][max_obj][12] fp64     [R | t] at the final iterate; for ANY non-zero status the input pose copied bit for bit
+ *     fit [B][max_obj][2] fp64           the reprojection rmse sqrt(J / n_obs) * sigma_px at the input pose and at the final iterate, in map
+ *                                        pixels; NaN for a non-zero status
+ *     n_obs [B][max_obj] int32           the observations, for every live object whatever its status
+ *     information [B][max_obj][36] fp64  H at the final iterate, undamped, row-major 6 x 6 and exactly symmetric, parameter order (w, d);
+ *                                        NaN for a non-zero status
+ *     status [B][max_obj] int32
+ *   Objects from n_obj[b] on: NaN pose_out, fit and information, n_obs 0, status OKP_REFINE_SKIPPED; their rows of obs are not used.
+ *   As for okp_refine_pose the order of the sums is not part of the contract: a lane adds the terms of its view over its slots in ascending
+ *   order and one butterfly adds the lanes (tests/test_gpu_refine_views.py: 1e-9 on R and t against a NumPy evaluation).  pose_out must not
+ *   overlap pose.
+ * Limits.  Uniform weights over the observations: the peaks' confidences are not used.  The assignment is okp_object_pose's, as it is.
+ * Refused on the host before any launch (OKP_EINVAL, the message names the argument): a null pointer, B or max_obj < 1, S outside
+ * [1, OKP_POSE_MAX_POINTS], V outside [1, OKP_REFINE_MAX_VIEWS], iters outside [1, OKP_REFINE_MAX_ITERS], sigma_px not positive and finite,
+ * damping negative or not finite, pose_out overlapping pose.
+ * ---------------------------------------------------------------------------------- */
+#define OKP_REFINE_MAX_VIEWS 64
+int okp_rig_bearings(const int32_t* count_dev, const float* xyc_dev, const int32_t* match_dev, const int32_t* member_dev,
+                     const int32_t* object_dev, const int32_t* n_fused_dev, const okp_stereo_pair* table_dev, int32_t n_table, int32_t n_pairs,
+                     int32_t K, int32_t cap, int32_t cap_f, const int32_t* type_count /* HOST [K-1] */, double* obs_dev, void* stream);
+int okp_refine_pose_views(const double* obs_dev, const double* views_dev, const double* pose_dev, const int32_t* assignment_dev,
+                          const int32_t* n_obj_dev, const double* model_dev, double sigma_px, int32_t iters, double damping, int32_t B,
+                          int32_t max_obj, int32_t S, int32_t V, double* pose_out_dev, double* fit_dev, int32_t* n_obs_dev,
+                          double* information_dev, int32_t* status_dev, void* stream);
 
 /* Undistort only (FisheyeCamera.undistort, camera_utils.py:75-81 / RadTanPinholeCamera.undistort, :57-62, by cam->model):
  * xy [m][2] fp32 -> out [m][2] fp64.  okp_fisheye_undistort is the same entry point under its round-1 name. */

@@ -373,6 +373,21 @@ def refine_assignments(camera, tab, pose, assignment, n_obj, model, type_count, 
                "okp_refine_assignments")
 
 
+# ---- a rig's poses refined against every camera's bearings (csrc/okp_refine_views.hip): obs [B,max_obj,S,V,2], views [V,14] ----------------------
+def rig_bearings(table, count, xyc, match, member, object, n_fused, type_count, obs, stream):
+    n, k, cap, _ = xyc.shape
+    _lib.check(_lib.lib().okp_rig_bearings(count.data_ptr(), xyc.data_ptr(), match.data_ptr(), member.data_ptr(), object.data_ptr(), n_fused.data_ptr(),
+                                           table.data_ptr(), table.shape[0], n // 2, k, cap, object.shape[1], _int32s(type_count, max(1, k - 1)), obs.data_ptr(), stream),
+               "okp_rig_bearings")
+
+
+def refine_pose_views(obs, views, pose, assignment, n_obj, model, sigma_px, iters, damping, pose_out, fit, n_obs, information, status, stream):
+    b, max_obj, s, v, _ = obs.shape
+    _lib.check(_lib.lib().okp_refine_pose_views(obs.data_ptr(), views.data_ptr(), pose.data_ptr(), assignment.data_ptr(), n_obj.data_ptr(), model.data_ptr(), sigma_px,
+                                                iters, damping, b, max_obj, s, v, pose_out.data_ptr(), fit.data_ptr(), n_obs.data_ptr(), information.data_ptr(),
+                                                status.data_ptr(), stream), "okp_refine_pose_views")
+
+
 # ---- scoring labelled scenes -----------------------------------------------------------------------------------------------------------------
 def project_labels(camera, world_points, T_WC, scale, crop_x, crop_y, labels, stream):
     _lib.check(_lib.lib().okp_project_labels(_camera(camera), world_points.data_ptr(), world_points.shape[0], T_WC.data_ptr(), T_WC.shape[0], scale, crop_x, crop_y,

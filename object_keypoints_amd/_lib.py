@@ -23,6 +23,11 @@ class OkpError(RuntimeError):
     pass
 
 
+class OkpNotOffered(OkpError, TypeError):
+    """An argument the receiver knows but does not offer in this form.  Also a TypeError: before the receiver took the keyword at all the call
+    ended in one, and a caller that caught that keeps working."""
+
+
 class okp_tap(Structure):
     _fields_ = [("src", c_int32), ("dy", c_int32), ("dx", c_int32), ("w", POINTER(c_float))]
 
@@ -123,6 +128,10 @@ SIGNATURES = [
                                 c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     ("okp_refine_assignments", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_int32), c_int32, POINTER(okp_camera), c_double, c_double, c_int32,
                                        c_double, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    ("okp_rig_bearings", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32,
+                                 POINTER(c_int32), c_void_p, c_void_p]),
+    ("okp_refine_pose_views", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_int32, c_double, c_int32, c_int32, c_int32,
+                                      c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     ("okp_fisheye_undistort", c_int, [POINTER(okp_camera), c_void_p, c_int32, c_void_p, c_void_p]),
     ("okp_camera_undistort", c_int, [POINTER(okp_camera), c_void_p, c_int32, c_void_p, c_void_p]),
     ("okp_project_labels", c_int, [POINTER(okp_camera), c_void_p, c_int32, c_void_p, c_int32, c_double, c_double, c_double, c_void_p, c_void_p]),

@@ -1,0 +1,318 @@
+// Pose refinement of a rig's objects against every camera's bearings (okp_rig_bearings, okp_refine_pose_views; contract in include/okp.h).
+// okp_object_pose fits a rig's pose to FUSED points, confidence-weighted means of two-view triangulations that carry the depth noise of a
+// short baseline; the peaks those points came from do not.  okp_rig_bearings collects them, per object and table slot, as one bearing per
+// camera; okp_refine_pose_views minimises the reprojection error of the object model in all cameras at once, from the fitted pose.
+//
+//   okp_rig_bearings_kernel        one workgroup of 1024 per object (a rig of 32 pairs has 16 x 32 (slot, pair) items: 32 per wave).  Phase 1, a
+//                                  wave per (slot, pair): the slot's cluster is the j-th set bit
+//                                  of a ballot over the type's clusters, the pair's member of it a ballot over the pair's left peaks; the two
+//                                  peak indices go to LDS.  Phase 2, a lane per (slot, camera): undistort the peak, store the bearing - or
+//                                  NaN, so every word of the table is written, once, with no atomics.
+//   okp_refine_pose_views_kernel   one wave per object.  With Vp the power of two that holds the V views the wave is G = 64 / Vp groups of Vp
+//                                  lanes: lane (g, v) is camera v and takes the slots g, g + G, g + 2 G, ... - a rig of 4 pairs (Vp = 8) has
+//                                  eight groups and walks a five-point model in ONE pass, a table of 64 views has one group and walks it
+//                                  slot by slot.  The lane keeps its row of `views`, its bearings and their model rows in registers over the
+//                                  whole iteration.  Per iterate it adds the terms of its own slots in ascending order, then one
+//                                  xor-butterfly over the 64 lanes makes the sums of H, g and the cost - after it every lane holds the
+//                                  same bits - and every lane solves the same 6 x 6 system (refine_step), so nothing is broadcast.  The
+//                                  loop over a lane's slots is unrolled to the 16 a model can have; a pass in which no lane's slot has a
+//                                  model row is skipped on a scalar branch.
+// fp64, no atomics, no host wait; the summation order is fixed, so the bits are the same on every run.
+#include "okp_pose_math.h"           // PoseTypes, pose_types, finite64, refine_step, the sums layout
+
+#pragma clang fp contract(off)
+
+namespace {
+
+#define OKP_BEARINGS_THREADS 1024
+
+struct BearingsParams {
+  const int32_t* count; const float* xyc; const int32_t* match; const int32_t* member; const int32_t* object; const int32_t* n_fused;
+  const okp_stereo_pair* table; int32_t n_table;
+  int32_t n_pairs, cap, cap_f;
+  PoseTypes types;
+  double* obs;
+};
+
+__global__ __launch_bounds__(OKP_BEARINGS_THREADS) void okp_rig_bearings_kernel(const BearingsParams p) {
+  __shared__ int32_t peak[OKP_POSE_MAX_POINTS][2 * OKP_RIG_MAX_PAIRS];      // [s][v]: the peak of camera v that slot s saw, or -1
+  const int o = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int S = p.types.S, K = p.types.K, P = p.n_pairs, V = 2 * P, cap = p.cap, cap_f = p.cap_f;
+  const bool live = o < min(p.n_fused[0], cap_f);
+  for (int e = tid; e < S * V; e += OKP_BEARINGS_THREADS) peak[e / V][e - (e / V) * V] = -1;
+  __syncthreads();
+  if (live) {                                                     // (block-uniform)
+    for (int item = wave; item < S * P; item += OKP_BEARINGS_THREADS / 64) {              // (wave-uniform)
+      const int s = item / P, pair = item - s * P;
+      int k = 0;
+      while (k + 1 < K && s >= p.types.base[k + 1]) ++k;
+      const int j = s - p.types.base[k];
+      int cluster = o;                                            // type 0: the object's own centre cluster
+      if (k >= 1) {
+        const int n = min(p.n_fused[k], cap_f);
+        unsigned long long mine = __ballot(lane < n && p.object[k * cap_f + lane] == o);
+        for (int q = 0; q < j; ++q) mine &= mine - 1ull;          // the j-th cluster of the object, in cluster order
+        cluster = mine ? __ffsll((long long)mine) - 1 : -1;
+      }
+      if (cluster < 0) continue;
+      const int ml = 2 * pair * K + k, mr = ml + K;
+      const int nl = min(p.count[ml], cap), nr = min(p.count[mr], cap);
+      const int32_t* mem = p.member + ((size_t)pair * K + k) * cap;
+      int found = -1;
+      for (int i0 = 0; i0 < nl && found < 0; i0 += 64) {
+        const int i = i0 + lane;
+        const unsigned long long hit = __ballot(i < nl && mem[i] == cluster);
+        if (hit) found = i0 + __ffsll((long long)hit) - 1;
+      }
+      if (found < 0) continue;
+      const int right = p.match[((size_t)pair * K + k) * cap + found];
+      if (right < 0 || right >= nr) continue;                     // (no member of a cluster is unmatched: a table the fusion did not write)
+      if (lane == 0) { peak[s][2 * pair] = found; peak[s][2 * pair + 1] = right; }
+    }
+  }
+  __syncthreads();
+  const double nan = __builtin_nan("");
+  for (int e = tid; e < S * V; e += OKP_BEARINGS_THREADS) {
+    const int s = e / V, v = e - s * V;
+    const int idx = peak[s][v];
+    double bx = nan, by = nan;
+    if (idx >= 0) {
+      int k = 0;
+      while (k + 1 < K && s >= p.types.base[k + 1]) ++k;
+      const okp_stereo_pair& entry = p.table[p.n_table == 1 ? 0 : (v >> 1)];
+      const okp_camera cam = (v & 1) ? entry.right : entry.left;
+      const float* src = p.xyc + (((size_t)v * K + k) * cap + idx) * 3;
+      double xu, yu;
+      okp_undistort_point(cam, (double)src[0], (double)src[1], xu, yu);
+      bx = (xu - cam.cx) / cam.fx;
+      by = (yu - cam.cy) / cam.fy;
+    }
+    double* dst = p.obs + ((size_t)o * S * V + e) * 2;
+    dst[0] = bx; dst[1] = by;
+  }
+}
+
+struct ViewsParams {
+  const double* obs; const double* views; const double* pose; const int32_t* assignment; const int32_t* n_obj; const double* model;
+  int32_t max_obj, S, V, iters, vshift;           // Vp = 1 << vshift >= V lanes per group
+  double sigma_px, damping;
+  double* pose_out; double* fit; int32_t* n_obs; double* information; int32_t* status;
+};
+
+// The sums over the wave's 64 lanes (H, g and the cost: the depth sums of the layout are not used here)
+__device__ __forceinline__ void views_butterfly(double (&acc)[OKP_REFINE_SUMS]) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1)
+#pragma unroll
+    for (int i = 0; i < 28; ++i) acc[i] += __shfl_xor(acc[i], off);
+}
+
+__global__ __launch_bounds__(64) void okp_refine_pose_views_kernel(const ViewsParams P) {
+  const int lane = threadIdx.x;
+  const size_t oi = blockIdx.x;
+  const int b = (int)(oi / P.max_obj), o = (int)(oi - (size_t)b * P.max_obj);
+  const bool live = o < P.n_obj[b];                               // (wave-uniform, like everything that is not a lane's own view)
+  const int S = P.S, V = P.V;
+  const int G = 64 >> P.vshift, grp = lane >> P.vshift, cam = lane & ((1 << P.vshift) - 1);
+  const int passes = (S + G - 1) / G;                             // slots per lane: slot grp + G i in pass i
+  const bool view = cam < V;
+  const double nan = __builtin_nan(""), inf = __builtin_inf();
+
+  double R[9], t[3];
+  bool pose_finite = true;
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    const double* row = P.pose + oi * 12 + 4 * i;
+    R[3 * i + 0] = row[0]; R[3 * i + 1] = row[1]; R[3 * i + 2] = row[2]; t[i] = row[3];
+    pose_finite = pose_finite && finite64(row[0]) && finite64(row[1]) && finite64(row[2]) && finite64(row[3]);
+  }
+  // this lane's camera: [R_v | t_v] and k_v = (fx_v, fy_v) / sigma_px (the lanes past V: an identity that observes nothing)
+  double rv[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0}, tv[3] = {0.0, 0.0, 0.0}, kx = 1.0, ky = 1.0;
+  if (view) {
+    const double* row = P.views + (size_t)cam * 14;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) { rv[3 * i + 0] = row[4 * i + 0]; rv[3 * i + 1] = row[4 * i + 1]; rv[3 * i + 2] = row[4 * i + 2]; tv[i] = row[4 * i + 3]; }
+    kx = row[12] / P.sigma_px; ky = row[13] / P.sigma_px;
+  }
+  // the object's bearings and model rows, slot by slot
+  double ou[OKP_POSE_MAX_POINTS], ov[OKP_POSE_MAX_POINTS], m[OKP_POSE_MAX_POINTS][3];
+  unsigned seen = 0u, rows = 0u;                                  // bit i: this lane observed its slot of pass i; some lane's slot of pass i has a model row
+  int n_obs = 0, n_rows = 0;
+  bool bad = false;
+  unsigned long long first = 0ull;                                // the first lane of every group
+  for (int g = 0; g < G; ++g) first |= 1ull << (g << P.vshift);
+#pragma unroll
+  for (int i = 0; i < OKP_POSE_MAX_POINTS; ++i) {
+    ou[i] = 0.0; ov[i] = 0.0; m[i][0] = 0.0; m[i][1] = 0.0; m[i][2] = 0.0;
+    if (i < passes) {                                             // (wave-uniform)
+      const int s = grp + G * i;
+      const bool slot = live && s < S;
+      const int a = slot ? P.assignment[oi * S + s] : -1;
+      const bool row = a >= 0 && a < S;
+      double u = nan, v = nan;
+      if (slot && view) {
+        const double* e = P.obs + ((oi * S + s) * V + cam) * 2;
+        u = e[0]; v = e[1];
+      }
+      bad = bad || ((u != u) != (v != v)) || fabs(u) == inf || fabs(v) == inf;
+      const bool mine = row && finite64(u) && finite64(v);
+      unsigned long long who = __ballot(mine);
+      n_obs += __popcll(who);
+      for (int sh = 1; sh < (1 << P.vshift); sh <<= 1) who |= who >> sh;          // a group's first lane: some lane of the group observed the slot
+      n_rows += __popcll(who & first);
+      if (mine) { ou[i] = u; ov[i] = v; seen |= 1u << i; }
+      if (row) { m[i][0] = P.model[a * 3 + 0]; m[i][1] = P.model[a * 3 + 1]; m[i][2] = P.model[a * 3 + 2]; }
+      if (__ballot(row) != 0ull) rows |= 1u << i;
+    }
+  }
+  const bool any_bad = __ballot(bad) != 0ull;
+  int status = (!live || !pose_finite || any_bad || n_rows < 3) ? OKP_REFINE_SKIPPED : 0;
+
+  double acc[OKP_REFINE_SUMS];
+  double J0 = nan;
+  if (status == 0) {                                              // (a skipped object has nothing to iterate on; its outputs do not depend on it)
+    for (int k = 0;; ++k) {
+#pragma unroll
+      for (int i = 0; i < OKP_REFINE_SUMS; ++i) acc[i] = 0.0;
+      bool behind = false;
+#pragma unroll
+      for (int s = 0; s < OKP_POSE_MAX_POINTS; ++s) {             // (s: the pass; the lane's slot of it)
+        if (!((rows >> s) & 1u)) continue;                        // (wave-uniform)
+        const bool mine = (seen >> s) & 1u;
+        const double p0 = (R[0] * m[s][0] + R[1] * m[s][1]) + R[2] * m[s][2], p1 = (R[3] * m[s][0] + R[4] * m[s][1]) + R[5] * m[s][2],
+                     p2 = (R[6] * m[s][0] + R[7] * m[s][1]) + R[8] * m[s][2];
+        const double X0 = p0 + t[0], X1 = p1 + t[1], X2 = p2 + t[2];
+        const double q0 = ((rv[0] * X0 + rv[1] * X1) + rv[2] * X2) + tv[0], q1 = ((rv[3] * X0 + rv[4] * X1) + rv[5] * X2) + tv[1],
+                     q2 = ((rv[6] * X0 + rv[7] * X1) + rv[8] * X2) + tv[2];
+        behind = behind || (mine && q2 <= 0.0);
+        const double iz = 1.0 / q2, xn = q0 * iz, yn = q1 * iz;
+        const double au0 = kx * iz, au2 = -(au0 * xn), av1 = ky * iz, av2 = -(av1 * yn);
+        // b = R_v^T a, the gradient in the table's frame; a Jacobian row is (p x b, b)
+        const double bu0 = rv[0] * au0 + rv[6] * au2, bu1 = rv[1] * au0 + rv[7] * au2, bu2 = rv[2] * au0 + rv[8] * au2;
+        const double bv0 = rv[3] * av1 + rv[6] * av2, bv1 = rv[4] * av1 + rv[7] * av2, bv2 = rv[5] * av1 + rv[8] * av2;
+        double e[2] = {kx * (xn - ou[s]), ky * (yn - ov[s])};
+        double j[2][6] = {{p1 * bu2 - p2 * bu1, p2 * bu0 - p0 * bu2, p0 * bu1 - p1 * bu0, bu0, bu1, bu2},
+                          {p1 * bv2 - p2 * bv1, p2 * bv0 - p0 * bv2, p0 * bv1 - p1 * bv0, bv0, bv1, bv2}};
+        if (!mine) {
+          e[0] = 0.0; e[1] = 0.0;
+#pragma unroll
+          for (int c = 0; c < 6; ++c) { j[0][c] = 0.0; j[1][c] = 0.0; }
+        }
+        int idx = 0;
+#pragma unroll
+        for (int r = 0; r < 6; ++r)
+#pragma unroll
+          for (int c = r; c < 6; ++c) { acc[idx] += j[0][r] * j[0][c] + j[1][r] * j[1][c]; ++idx; }
+#pragma unroll
+        for (int r = 0; r < 6; ++r) acc[21 + r] += j[0][r] * e[0] + j[1][r] * e[1];
+        acc[27] += e[0] * e[0] + e[1] * e[1];
+      }
+      if (status == 0 && __ballot(behind) != 0ull) status = OKP_REFINE_BEHIND;
+      views_butterfly(acc);
+      if (k == 0) J0 = acc[27];
+      if (k == P.iters) break;                                    // acc holds the sums at the final iterate
+      const bool singular = refine_step(acc, P.damping, R, t);
+      if (status == 0 && singular) status = OKP_REFINE_SINGULAR;
+    }
+    const double J1 = acc[27];
+    if (status == 0 && (!(J1 < inf) || J1 > J0 + 1e-12 * n_obs)) status = OKP_REFINE_REJECTED;
+  }
+
+  // outputs: every word is written by every call, by the object's first lane
+  if (lane != 0) return;
+  double* pose_out = P.pose_out + oi * 12;
+  double* fit = P.fit + oi * 2;
+  double* info = P.information + oi * 36;
+  const bool ok = status == 0;
+  if (ok) {
+#pragma unroll
+    for (int i = 0; i < 3; ++i) { pose_out[4 * i + 0] = R[3 * i + 0]; pose_out[4 * i + 1] = R[3 * i + 1]; pose_out[4 * i + 2] = R[3 * i + 2]; pose_out[4 * i + 3] = t[i]; }
+  } else if (live) {                                              // the input pose, bit for bit (NaN payloads included)
+    const unsigned long long* src = reinterpret_cast<const unsigned long long*>(P.pose + oi * 12);
+    unsigned long long* dst = reinterpret_cast<unsigned long long*>(pose_out);
+    unsigned long long bits[12];
+#pragma unroll
+    for (int i = 0; i < 12; ++i) bits[i] = src[i];
+#pragma unroll
+    for (int i = 0; i < 12; ++i) dst[i] = bits[i];
+  } else {
+#pragma unroll
+    for (int i = 0; i < 12; ++i) pose_out[i] = nan;
+  }
+  fit[0] = ok ? sqrt(J0 / n_obs) * P.sigma_px : nan;
+  fit[1] = ok ? sqrt(acc[27] / n_obs) * P.sigma_px : nan;
+  {
+    int idx = 0;
+#pragma unroll
+    for (int r = 0; r < 6; ++r)
+#pragma unroll
+      for (int c = r; c < 6; ++c) {
+        const double hv = ok ? acc[idx] : nan;
+        ++idx;
+        info[6 * r + c] = hv; info[6 * c + r] = hv;
+      }
+  }
+  P.n_obs[oi] = n_obs;
+  P.status[oi] = status;
+}
+
+// [a, a + na) and [b, b + nb) share a byte
+bool views_overlap(const void* a, size_t na, const void* b, size_t nb) {
+  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+  return x < y + nb && y < x + na;
+}
+
+}  // namespace
+
+extern "C" int okp_rig_bearings(const int32_t* count, const float* xyc, const int32_t* match, const int32_t* member, const int32_t* object,
+                                const int32_t* n_fused, const okp_stereo_pair* table, int32_t n_table, int32_t n_pairs, int32_t K, int32_t cap,
+                                int32_t cap_f, const int32_t* type_count, double* obs, void* stream) {
+  const char* fn = "okp_rig_bearings";
+  BearingsParams p = {};
+  if (n_pairs < 1 || n_pairs > OKP_RIG_MAX_PAIRS) { okp_set_error("%s: n_pairs = %d outside [1, %d]", fn, n_pairs, OKP_RIG_MAX_PAIRS); return OKP_EINVAL; }
+  int rc = pose_types(fn, type_count, K, OKP_RIG_MAX_TYPES, p.types, nullptr);
+  if (rc) return rc;
+  if (cap < 1 || cap > 256) { okp_set_error("%s: cap = %d outside [1, 256]", fn, cap); return OKP_EINVAL; }
+  if (cap_f < 1 || cap_f > OKP_RIG_MAX_FUSED) { okp_set_error("%s: cap_f = %d outside [1, %d]", fn, cap_f, OKP_RIG_MAX_FUSED); return OKP_EINVAL; }
+  if (n_table < 1) { okp_set_error("%s: n_table = %d; a calibration table holds at least one stereo pair", fn, n_table); return OKP_EINVAL; }
+  if (n_table > 1 && n_table < n_pairs) { okp_set_error("%s: n_table = %d calibrations for n_pairs = %d pairs (one entry serves every pair)", fn, n_table, n_pairs); return OKP_EINVAL; }
+  const struct { const void* ptr; const char* name; } required[] = {
+      {count, "count"}, {xyc, "xyc"}, {match, "match"}, {member, "member"}, {object, "object"}, {n_fused, "n_fused"}, {table, "table"}, {obs, "obs"}};
+  for (const auto& r : required)
+    if (!r.ptr) { okp_set_error("%s: null %s", fn, r.name); return OKP_EINVAL; }
+  p.count = count; p.xyc = xyc; p.match = match; p.member = member; p.object = object; p.n_fused = n_fused;
+  p.table = table; p.n_table = n_table; p.n_pairs = n_pairs; p.cap = cap; p.cap_f = cap_f; p.obs = obs;
+  hipLaunchKernelGGL(okp_rig_bearings_kernel, dim3(cap_f), dim3(OKP_BEARINGS_THREADS), 0, (hipStream_t)stream, p);
+  return okp_check_hip(hipGetLastError(), "okp_rig_bearings launch");
+}
+
+extern "C" int okp_refine_pose_views(const double* obs, const double* views, const double* pose, const int32_t* assignment, const int32_t* n_obj,
+                                     const double* model, double sigma_px, int32_t iters, double damping, int32_t B, int32_t max_obj, int32_t S,
+                                     int32_t V, double* pose_out, double* fit, int32_t* n_obs, double* information, int32_t* status, void* stream) {
+  const char* fn = "okp_refine_pose_views";
+  if (B < 1) { okp_set_error("%s: B = %d; a batch holds at least one frame", fn, B); return OKP_EINVAL; }
+  if (max_obj < 1) { okp_set_error("%s: max_obj = %d; a frame holds at least one object", fn, max_obj); return OKP_EINVAL; }
+  if ((long long)B * max_obj > 0x7fffffffll) { okp_set_error("%s: B * max_obj = %lld objects do not fit one launch", fn, (long long)B * max_obj); return OKP_EINVAL; }
+  if (S < 1 || S > OKP_POSE_MAX_POINTS) { okp_set_error("%s: S = %d outside [1, %d] model points", fn, S, OKP_POSE_MAX_POINTS); return OKP_EINVAL; }
+  if (V < 1 || V > OKP_REFINE_MAX_VIEWS) { okp_set_error("%s: V = %d outside [1, %d] views", fn, V, OKP_REFINE_MAX_VIEWS); return OKP_EINVAL; }
+  if (iters < 1 || iters > OKP_REFINE_MAX_ITERS) { okp_set_error("%s: iters = %d outside [1, %d]", fn, iters, OKP_REFINE_MAX_ITERS); return OKP_EINVAL; }
+  if (!(sigma_px > 0.0 && sigma_px < __builtin_inf())) { okp_set_error("%s: sigma_px = %g must be a positive, finite number of map pixels", fn, sigma_px); return OKP_EINVAL; }
+  if (!(damping >= 0.0 && damping < __builtin_inf())) { okp_set_error("%s: damping = %g must be finite and not negative", fn, damping); return OKP_EINVAL; }
+  const struct { const void* ptr; const char* name; } required[] = {
+      {obs, "obs"}, {views, "views"}, {pose, "pose"}, {assignment, "assignment"}, {n_obj, "n_obj"}, {model, "model"},
+      {pose_out, "pose_out"}, {fit, "fit"}, {n_obs, "n_obs"}, {information, "information"}, {status, "status"}};
+  for (const auto& r : required)
+    if (!r.ptr) { okp_set_error("%s: null %s", fn, r.name); return OKP_EINVAL; }
+  const size_t n_total = (size_t)B * max_obj;
+  if (views_overlap(pose_out, n_total * 12 * sizeof(double), pose, n_total * 12 * sizeof(double))) {
+    okp_set_error("%s: pose_out overlaps pose: the input pose is the fallback and is read after other objects are written", fn);
+    return OKP_EINVAL;
+  }
+  ViewsParams p = {};
+  p.obs = obs; p.views = views; p.pose = pose; p.assignment = assignment; p.n_obj = n_obj; p.model = model;
+  p.max_obj = max_obj; p.S = S; p.V = V; p.iters = iters; p.sigma_px = sigma_px; p.damping = damping;
+  while ((1 << p.vshift) < V) ++p.vshift;
+  p.pose_out = pose_out; p.fit = fit; p.n_obs = n_obs; p.information = information; p.status = status;
+  hipLaunchKernelGGL(okp_refine_pose_views_kernel, dim3((unsigned)n_total), dim3(64), 0, (hipStream_t)stream, p);
+  return okp_check_hip(hipGetLastError(), "okp_refine_pose_views launch");
+}

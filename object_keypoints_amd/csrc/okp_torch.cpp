@@ -728,6 +728,51 @@ void refine_assignments(at::ArrayRef<double> camera, const Tensor& tab, const Te
                                   assignment_out.data_ptr<int32_t>(), hypothesis.data_ptr<int32_t>(), cost.data_ptr<double>(), sp(stream)), "okp_refine_assignments");
 }
 
+// A rig's poses refined against every camera's bearings (csrc/okp_refine_views.hip).  rig_bearings: the fused tick's count / xyc / match / member /
+// object / n_fused and the calibration table -> obs [cap_f,S,2P,2] float64; refine_pose_views: obs [B,max_obj,S,V,2], views [V,14] and the pose
+// stage's pose / assignment / n_obj and the model -> pose_out [B,max_obj,12], fit [B,max_obj,2], n_obs [B,max_obj], information [B,max_obj,36], status
+void rig_bearings(const Tensor& table, const Tensor& count, const Tensor& xyc, const Tensor& match, const Tensor& member, const Tensor& object, const Tensor& n_fused,
+                  at::IntArrayRef type_count, const Tensor& obs, int64_t stream) {
+  const int64_t P = stereo_tick_pairs(count, xyc);
+  const int32_t n_table = stereo_table_size(table);
+  check_dev(match, at::kInt, "match"); check_dev(member, at::kInt, "member"); check_dev(object, at::kInt, "object"); check_dev(n_fused, at::kInt, "n_fused");
+  check_dev(obs, at::kDouble, "obs");
+  const int64_t K = xyc.size(1), cap = xyc.size(2);
+  TORCH_CHECK(object.dim() == 2 && object.size(0) == K, "okp: object is [K,cap_f] int32 (rig_fuse)");
+  const int64_t cap_f = object.size(1);
+  int64_t S = 1;
+  for (auto c : type_count) S += c;
+  TORCH_CHECK((int64_t)type_count.size() == K - 1, "okp: type_count has K-1 entries");
+  TORCH_CHECK(match.numel() == P * K * cap && member.numel() == P * K * cap && n_fused.numel() == K && obs.numel() == cap_f * S * 2 * P * 2,
+              "okp: rig_bearings buffers are match and member [P,K,cap], n_fused [K] int32 and obs [cap_f,S,2P,2] float64");
+  std::vector<int32_t> tc(type_count.begin(), type_count.end());
+  tc.push_back(0);                                  // (K = 1: a non-null pointer for the entry point to refuse K with)
+  check_rc(okp_rig_bearings(count.data_ptr<int32_t>(), xyc.data_ptr<float>(), match.data_ptr<int32_t>(), member.data_ptr<int32_t>(), object.data_ptr<int32_t>(),
+                            n_fused.data_ptr<int32_t>(), reinterpret_cast<const okp_stereo_pair*>(table.data_ptr()), n_table, (int32_t)P, (int32_t)K, (int32_t)cap,
+                            (int32_t)cap_f, tc.data(), obs.data_ptr<double>(), sp(stream)), "okp_rig_bearings");
+}
+
+void refine_pose_views(const Tensor& obs, const Tensor& views, const Tensor& pose, const Tensor& assignment, const Tensor& n_obj, const Tensor& model, double sigma_px,
+                       int64_t iters, double damping, const Tensor& pose_out, const Tensor& fit, const Tensor& n_obs, const Tensor& information, const Tensor& status,
+                       int64_t stream) {
+  check_dev(obs, at::kDouble, "obs"); check_dev(views, at::kDouble, "views"); check_dev(pose, at::kDouble, "pose"); check_dev(assignment, at::kInt, "assignment");
+  check_dev(n_obj, at::kInt, "n_obj"); check_dev(model, at::kDouble, "model"); check_dev(pose_out, at::kDouble, "pose_out"); check_dev(fit, at::kDouble, "fit");
+  check_dev(n_obs, at::kInt, "n_obs"); check_dev(information, at::kDouble, "information"); check_dev(status, at::kInt, "status");
+  TORCH_CHECK(obs.dim() == 5 && obs.size(4) == 2, "okp: obs is [B,max_obj,S,V,2] float64");
+  const int64_t B = obs.size(0), max_obj = obs.size(1), S = obs.size(2), V = obs.size(3);
+  TORCH_CHECK(views.numel() == V * 14 && pose.numel() == B * max_obj * 12 && assignment.numel() == B * max_obj * S && n_obj.numel() == B && model.numel() == S * 3,
+              "okp: refine_pose_views inputs are views [V,14], pose [B,max_obj,12], assignment [B,max_obj,S], n_obj [B] and model [S,3]");
+  TORCH_CHECK(pose_out.numel() == B * max_obj * 12 && fit.numel() == B * max_obj * 2 && n_obs.numel() == B * max_obj && information.numel() == B * max_obj * 36 &&
+              status.numel() == B * max_obj,
+              "okp: refine_pose_views outputs are pose_out [B,max_obj,12], fit [B,max_obj,2], n_obs [B,max_obj], information [B,max_obj,36] and status [B,max_obj]");
+  TORCH_CHECK(iters >= INT32_MIN && iters <= INT32_MAX, "okp: iters does not fit an int32");
+  TORCH_CHECK(B <= INT32_MAX && max_obj <= INT32_MAX && S <= INT32_MAX && V <= INT32_MAX, "okp: obs is too large");
+  check_rc(okp_refine_pose_views(obs.data_ptr<double>(), views.data_ptr<double>(), pose.data_ptr<double>(), assignment.data_ptr<int32_t>(), n_obj.data_ptr<int32_t>(),
+                                 model.data_ptr<double>(), sigma_px, (int32_t)iters, damping, (int32_t)B, (int32_t)max_obj, (int32_t)S, (int32_t)V,
+                                 pose_out.data_ptr<double>(), fit.data_ptr<double>(), n_obs.data_ptr<int32_t>(), information.data_ptr<double>(),
+                                 status.data_ptr<int32_t>(), sp(stream)), "okp_refine_pose_views");
+}
+
 void lift_peaks(at::ArrayRef<double> camera, const Tensor& count, const Tensor& xyc, const Tensor& depth, int64_t max_x, int64_t max_y, const Tensor& out, int64_t stream) {
   TORCH_CHECK(xyc.is_cuda() && xyc.dim() == 4 && xyc.scalar_type() == at::kFloat && depth.is_cuda() && depth.scalar_type() == at::kFloat && depth.dim() == 4 && depth.is_contiguous() &&
               depth.size(0) == xyc.size(0) && depth.size(1) == xyc.size(1) && count.scalar_type() == at::kInt && out.scalar_type() == at::kDouble &&
@@ -895,6 +940,10 @@ TORCH_LIBRARY(okp, m) {
         "Tensor? overflow_in=None) -> ()", change_frame);
   m.def("refine_pose(float[] camera, Tensor tab, Tensor pose, Tensor assignment, Tensor n_obj, Tensor model, float sigma_px, float sigma_z, int iters, float damping, "
         "Tensor(a!) pose_out, Tensor(b!) fit, Tensor(c!) information, Tensor(d!) status, int stream) -> ()", refine_pose);
+  m.def("rig_bearings(Tensor table, Tensor count, Tensor xyc, Tensor match, Tensor member, Tensor object, Tensor n_fused, int[] type_count, Tensor(a!) obs, int stream) -> ()",
+        rig_bearings);
+  m.def("refine_pose_views(Tensor obs, Tensor views, Tensor pose, Tensor assignment, Tensor n_obj, Tensor model, float sigma_px, int iters, float damping, "
+        "Tensor(a!) pose_out, Tensor(b!) fit, Tensor(c!) n_obs, Tensor(d!) information, Tensor(e!) status, int stream) -> ()", refine_pose_views);
   m.def("refine_assignments(float[] camera, Tensor tab, Tensor pose, Tensor assignment, Tensor n_obj, Tensor model, int[] type_count, float sigma_px, float sigma_z, int iters, "
         "float damping, Tensor(a!) pose_out, Tensor(b!) fit, Tensor(c!) information, Tensor(d!) status, Tensor(e!) assignment_out, Tensor(f!) hypothesis, Tensor(g!) cost, "
         "int stream) -> ()", refine_assignments);

@@ -15,7 +15,7 @@ import torch
 
 from . import _ctypes_ops, _lib
 from ._ctypes_ops import _DTYPES, _okp_dtype as okp_dtype      # (torch dtype -> OKP_* code: the adapter marshals with the same table)
-from ._lib import OKP_BF16, OKP_F16, OKP_F32, OKP_F32X3, ACT_NONE, ACT_RELU, ACT_SIGMOID, OkpError
+from ._lib import OKP_BF16, OKP_F16, OKP_F32, OKP_F32X3, ACT_NONE, ACT_RELU, ACT_SIGMOID, OkpError, OkpNotOffered
 
 HALF_DTYPES = (torch.bfloat16, torch.float16)     # 16-bit activations / weights, fp32 accumulate: the MFMA throughput precisions
 
@@ -1011,6 +1011,9 @@ def rig_poses(T_BL_list):
     return torch.from_numpy(out)
 
 
+_rig_poses = rig_poses       # (for rig_views, whose argument has the function's name)
+
+
 def check_fuse_radii(merge_radius, object_radius):
     for name, r in (("merge_radius", merge_radius), ("object_radius", object_radius)):
         try:
@@ -1424,7 +1427,10 @@ class RefineConfig:
         iters     Gauss-Newton steps, 1 .. REFINE_MAX_ITERS: always exactly this many
         damping   mu >= 0 of (H + mu diag H) d = -g
         resolve_assignment   (keyword, default False) a pipeline then refines every assignment of the interchangeable key points, each from
-                  its own rigid fit, and keeps the one of least final cost (okp_refine_assignments) instead of refining the fit's own."""
+                  its own rigid fit, and keeps the one of least final cost (okp_refine_assignments) instead of refining the fit's own.
+    refine_pose_views - the refinement of a rig's poses against every camera's bearings, StereoStreamPipeline's - reads sigma_px, iters and
+    damping only: its cost has no depth term, so sigma_z is not used, and it does not resolve assignments (a rig pipeline refuses
+    resolve_assignment=True)."""
 
     def __init__(self, sigma_px=0.25, sigma_z=0.05, iters=6, damping=1e-9, *, resolve_assignment=False):
         def number(name, v):
@@ -1537,6 +1543,135 @@ def check_refine_hypotheses(type_count):
         raise OkpError(f"type_count = {list(type_count)} gives prod(c_k!) = {hyps} assignments per object, above {REFINE_MAX_HYPOTHESES}: "
                        "resolve_assignment cannot enumerate them (resolve_assignment=False keeps working)")
     return hyps
+
+
+# ---- a rig's poses refined against every camera's bearings (okp_rig_bearings, okp_refine_pose_views; csrc/okp_refine_views.hip) ----------------
+REFINE_MAX_VIEWS = 64                                                            # include/okp.h OKP_REFINE_MAX_VIEWS
+
+
+def check_views(views):
+    """A views table [V,14] float64 (rig_views' layout) as a finite array with positive focal lengths, 1 <= V <= REFINE_MAX_VIEWS."""
+    v = np.asarray(views, dtype=np.float64)
+    if v.ndim != 2 or v.shape[1] != 14 or not 1 <= v.shape[0] <= REFINE_MAX_VIEWS:
+        raise OkpError(f"views has shape {tuple(v.shape)}: [V,14] with 1 <= V <= {REFINE_MAX_VIEWS}, row v = [R_v | t_v] row-major, fx_v, fy_v")
+    if not np.isfinite(v).all():
+        raise OkpError("views must be finite")
+    if not (v[:, 12:] > 0.0).all():
+        raise OkpError("views: the focal lengths fx_v, fy_v (columns 12 and 13) must be positive")
+    return v
+
+
+def rig_views(stereo_cameras, rig_poses):
+    """The views table of a rig for refine_pose_views: its 2P cameras as seen from the rig frame -> float64 HOST tensor [2P, 14], which the
+    caller moves to the device once.  Row v = [R_v | t_v] row-major 3 x 4 - rig coordinates -> camera v's - then the camera's fx, fy.
+        stereo_cameras: a sequence of P StereoCameras, or ONE StereoCamera whose calibration every pair repeats
+        rig_poses: P transforms T_BL (4 x 4: pair p's left-camera coordinates -> rig coordinates), validated as ops.rig_poses validates them
+    The left camera of pair p (row 2p) is the inverse of T_BL[p]: R = R_p^T, t = -(R_p^T t_p).  The right camera (row 2p + 1) is T_RL[p]
+    composed with it: R = R_RL R_p^T, t = R_RL (-(R_p^T t_p)) + t_RL.  Plain NumPy matrix products in fp64, in exactly this order."""
+    poses = _rig_poses(rig_poses).numpy().reshape(-1, 3, 4)
+    cams = [stereo_cameras] if hasattr(stereo_cameras, "left_camera") else list(stereo_cameras)
+    if len(cams) == 1 and hasattr(stereo_cameras, "left_camera"):
+        cams = cams * len(poses)
+    if len(cams) != len(poses):
+        raise OkpError(f"{len(poses)} rig poses for {len(cams)} stereo pairs: one pose per pair")
+    out = np.empty((2 * len(poses), 14), dtype=np.float64)
+    for p, (st, T_BL) in enumerate(zip(cams, poses)):
+        T_RL = np.asarray(st.T_RL, dtype=np.float64)
+        if T_RL.shape != (4, 4) or not np.isfinite(T_RL).all() or not np.array_equal(T_RL[3], [0.0, 0.0, 0.0, 1.0]):
+            raise OkpError(f"stereo pair {p}: T_RL must be a finite 4 x 4 transform with the last row [0, 0, 0, 1]")
+        R_LB = T_BL[:, :3].T
+        t_LB = -(R_LB @ T_BL[:, 3])
+        R_RB = T_RL[:3, :3] @ R_LB
+        t_RB = T_RL[:3, :3] @ t_LB + T_RL[:3, 3]
+        for row, R, t, cam, side in ((2 * p, R_LB, t_LB, st.left_camera, "left"), (2 * p + 1, R_RB, t_RB, st.right_camera, "right")):
+            K = np.asarray(cam.K, dtype=np.float64)
+            if K.shape != (3, 3) or not np.isfinite(K).all() or not (K[0, 0] > 0 and K[1, 1] > 0):
+                raise OkpError(f"stereo pair {p}: the {side} camera's K must be a finite 3 x 3 matrix with fx, fy > 0")
+            out[row, :12] = np.concatenate([R, t[:, None]], axis=1).reshape(12)
+            out[row, 12:] = K[0, 0], K[1, 1]
+    return torch.from_numpy(check_views(out))
+
+
+def rig_bearings(table, count, xyc, match, fused, type_count):
+    """The bearings of a fused tick's objects in every camera of the rig (okp_rig_bearings, specified in include/okp.h): table - the rig's
+    calibration table on the device (stereo_rig; one entry serves every pair) -, count [2P,K] int32 and xyc [2P,K,cap,3] fp32 (peak_nms),
+    match [P,K,cap] int32 (stereo_match_rig), fused: rig_fuse()'s dict ("member", "object" and "n_fused" are read), type_count: the K-1 counts
+    -> obs [1, cap_f, S, 2P, 2] float64 (device): the undistorted normalised image coordinates of slot s of object o in camera v (2p: the left
+    camera of pair p), (NaN, NaN) where the camera did not see it.  Every word is written.  One launch, no host sync."""
+    n_pairs, k, cap = _tick_pairs(count, xyc)
+    n_table = _rig_table(table)
+    tc, s = _pose_type_count(type_count, "type_count")
+    if len(tc) != k - 1:
+        raise OkpError(f"type_count {tc}: {k - 1} counts, one for each key-point type after the centre")
+    if not 1 <= n_pairs <= RIG_MAX_PAIRS or not 2 <= k <= RIG_MAX_TYPES or not 1 <= cap <= STEREO_MAX_CAPACITY:
+        raise OkpError(f"xyc [{2 * n_pairs},{k},{cap},3]: at most {RIG_MAX_PAIRS} pairs, 2 .. {RIG_MAX_TYPES} types and {STEREO_MAX_CAPACITY} slots")
+    if n_table != 1 and n_table < n_pairs:
+        raise OkpError(f"table holds {n_table} calibrations for {n_pairs} stereo pairs (one entry serves every pair)")
+    try:
+        member, obj, n_fused = fused["member"], fused["object"], fused["n_fused"]
+    except (TypeError, KeyError, IndexError):
+        raise OkpError("fused must be the dict of ops.rig_fuse (its \"member\", \"object\" and \"n_fused\")") from None
+    for name, t in (("match", match), ("member", member), ("object", obj), ("n_fused", n_fused)):
+        require_cuda(t, name)
+    dev = xyc.device
+    if match.dtype != torch.int32 or tuple(match.shape) != (n_pairs, k, cap) or match.device != dev:
+        raise OkpError(f"match must be int32 [{n_pairs},{k},{cap}] on the peaks' device (stereo_match_rig)")
+    if member.dtype != torch.int32 or tuple(member.shape) != (n_pairs, k, cap) or member.device != dev:
+        raise OkpError(f"member must be int32 [{n_pairs},{k},{cap}] on the peaks' device (rig_fuse)")
+    if obj.dtype != torch.int32 or obj.dim() != 2 or obj.shape[0] != k or not 1 <= obj.shape[1] <= RIG_MAX_FUSED or obj.device != dev:
+        raise OkpError(f"object must be int32 [{k},cap_f] with cap_f in [1, {RIG_MAX_FUSED}] on the peaks' device (rig_fuse)")
+    if n_fused.dtype != torch.int32 or tuple(n_fused.shape) != (k,) or n_fused.device != dev:
+        raise OkpError(f"n_fused must be int32 [{k}] on the peaks' device (rig_fuse)")
+    if table.device != dev:
+        raise OkpError(f"table is on {table.device}, the peaks on {dev}")
+    cap_f = int(obj.shape[1])
+    obs = torch.empty((1, cap_f, s, 2 * n_pairs, 2), dtype=torch.float64, device=dev)
+    _dispatch(_ops().rig_bearings, table, count.contiguous(), xyc.contiguous(), match.contiguous(), member.contiguous(), obj.contiguous(), n_fused.contiguous(), tc, obs,
+              stream_int())
+    return obs
+
+
+def refine_pose_views(obs, views, pose, n_obj, model, cfg):
+    """Every object's fitted pose refined against its bearings in all views at once (okp_refine_pose_views; cost, step, statuses and outputs
+    are specified in include/okp.h).  obs [B,max_obj,S,V,2] float64 (device; rig_bearings, or any table of bearings: (NaN, NaN) = not seen);
+    views [V,14] float64 (device): rig_views(...) moved to the device; pose: object_pose()'s dict (its "pose" [B,max_obj,12] and "assignment"
+    [B,max_obj,S] are read); n_obj int32 [B] (0-d for B = 1); model [S,3] float64 (device); cfg: a RefineConfig, of which sigma_px, iters and
+    damping are read (no depth term, no assignments resolved)
+    -> {"pose" [B,max_obj,12] float64 (the refined [R | t]; the input pose bit for bit where the status is not 0), "fit" [B,max_obj,2] float64
+        (reprojection rmse in map pixels before and after; NaN where the status is not 0), "n_obs" [B,max_obj] int32 (bearings used),
+        "information" [B,max_obj,36] float64 (H at the refined pose, 6 x 6 over (rotation, translation); NaN where the status is not 0),
+        "status" [B,max_obj] int32 (0, REFINE_SKIPPED, REFINE_SINGULAR, REFINE_BEHIND or REFINE_REJECTED)}.  One launch, no host sync."""
+    if not isinstance(cfg, RefineConfig):
+        raise OkpError("cfg must be an ops.RefineConfig")
+    try:
+        fitted, assignment = pose["pose"], pose["assignment"]
+    except (TypeError, KeyError, IndexError):
+        raise OkpError("pose must be the dict of ops.object_pose (its \"pose\" and \"assignment\")") from None
+    for name, t in (("obs", obs), ("views", views), ("pose", fitted), ("assignment", assignment), ("n_obj", n_obj), ("model", model)):
+        require_cuda(t, name)
+    if obs.dtype != torch.float64 or obs.dim() != 5 or obs.shape[4] != 2:
+        raise OkpError("obs must be float64 [B,max_obj,S,V,2] (rig_bearings)")
+    b, max_obj, s, v = (int(x) for x in obs.shape[:4])
+    dev = obs.device
+    if b < 1 or max_obj < 1 or not 1 <= s <= POSE_MAX_POINTS or not 1 <= v <= REFINE_MAX_VIEWS:
+        raise OkpError(f"obs [{b},{max_obj},{s},{v},2]: at least one frame and object, at most {POSE_MAX_POINTS} model points and {REFINE_MAX_VIEWS} views")
+    if views.dtype != torch.float64 or tuple(views.shape) != (v, 14) or views.device != dev:
+        raise OkpError(f"views must be float64 [{v},14] on the bearings' device (rig_views): one row for each of the {v} views of obs")
+    if fitted.dtype != torch.float64 or tuple(fitted.shape) != (b, max_obj, 12) or assignment.dtype != torch.int32 or tuple(assignment.shape) != (b, max_obj, s) or \
+            fitted.device != dev or assignment.device != dev:
+        raise OkpError(f"pose must be float64 [{b},{max_obj},12] and assignment int32 [{b},{max_obj},{s}] on the bearings' device (object_pose)")
+    if n_obj.dtype != torch.int32 or n_obj.numel() != b or n_obj.device != dev:
+        raise OkpError(f"n_obj must be int32 [{b}] on the bearings' device: the objects of each frame")
+    if model.dtype != torch.float64 or tuple(model.shape) != (s, 3) or model.device != dev:
+        raise OkpError(f"model must be float64 [{s},3] on the bearings' device (object_model)")
+    pose_out = torch.empty((b, max_obj, 12), dtype=torch.float64, device=dev)
+    fit = torch.empty((b, max_obj, 2), dtype=torch.float64, device=dev)
+    n_obs = torch.empty((b, max_obj), dtype=torch.int32, device=dev)
+    information = torch.empty((b, max_obj, 36), dtype=torch.float64, device=dev)
+    status = torch.empty((b, max_obj), dtype=torch.int32, device=dev)
+    _dispatch(_ops().refine_pose_views, obs.contiguous(), views.contiguous(), fitted.contiguous(), assignment.contiguous(), n_obj.reshape(b).contiguous(), model.contiguous(),
+              cfg.sigma_px, cfg.iters, cfg.damping, pose_out, fit, n_obs, information, status, stream_int())
+    return {"pose": pose_out, "fit": fit, "n_obs": n_obs, "information": information, "status": status}
 
 
 # ---- scoring labelled scenes (csrc/okp_targets.hip) ---------------------------------------------------------------------------------

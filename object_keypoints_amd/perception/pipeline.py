@@ -14,7 +14,7 @@ import numpy as np
 import torch
 
 from .. import ops
-from ..ops import OkpError
+from ..ops import OkpError, OkpNotOffered
 from . import models
 from .utils import camera_utils  # noqa: F401  (re-exported like the reference module does)
 
@@ -586,6 +586,8 @@ def _pose_fields(pose, n, refine=None):
     fields = {"pose": pose["pose"][n], "fit": pose["fit"][n], "status": pose["status"][n]}
     if refine is not None:
         fields.update(refine=refine["pose"][n], refine_fit=refine["fit"][n], information=refine["information"][n], refine_status=refine["status"][n])
+        if "n_obs" in refine:                    # an ops.refine_pose_views dict (a rig): "refine_fit" is [max_obj,2], and "refine_n_obs" [max_obj]
+            fields.update(refine_n_obs=refine["n_obs"][n])
         if "hypothesis" in refine:
             fields.update(refine_assignment=refine["assignment"][n], refine_hypothesis=refine["hypothesis"][n], refine_cost=refine["cost"][n])
     return fields
@@ -621,6 +623,18 @@ def _refine_entries(rec, o, T_CO):
         entries.update(assignment_refined=rec["refine_assignment"][o].copy(), refine_hypothesis=tuple(int(h) for h in rec["refine_hypothesis"][o]),
                        refine_cost=tuple(float(c) for c in rec["refine_cost"][o]))
     return entries
+
+
+def _rig_refine_entries(rec, o, T_BO):
+    """Object o's refined pose as the entries rig_objects() adds: 'T_BO_refined' (None where 'T_BO' is; the fitted pose where the refinement's
+    status is not 0), 'reprojection_rmse' (before, after), 'refine_observations', 'pose_information' (6 x 6) and 'refine_status'."""
+    fit = rec["refine_fit"]
+    T = None
+    if T_BO is not None:
+        T = np.eye(4)
+        T[:3] = rec["refine"][o].reshape(3, 4)
+    return {'T_BO_refined': T, 'reprojection_rmse': (float(fit[o, 0]), float(fit[o, 1])), 'refine_observations': int(rec["refine_n_obs"][o]),
+            'pose_information': rec["information"][o].reshape(6, 6).copy(), 'refine_status': int(rec["refine_status"][o])}
 
 
 def _pose_entries(rec, o, key):
@@ -732,7 +746,9 @@ class _ObjectStage:
     ops.refine_pose's dict.  "pose" keeps its bits; the world-frame change and the tracker are fed the refined pose from here on.  With
     RefineConfig(..., resolve_assignment=True) the one launch is okp_refine_assignments instead - every assignment of the interchangeable key
     points refined, the one of least final cost kept - and "refine" is ops.refine_assignments' dict ("assignment", "hypothesis", "cost" too);
-    a model with more than ops.REFINE_MAX_HYPOTHESES assignments is refused at construction.
+    a model with more than ops.REFINE_MAX_HYPOTHESES assignments is refused at construction.  A rig's table holds fused points, not one camera's
+    bearings: its step hands run() `rig` - the tick's peaks, matches, fusion, calibration table and views table - and the refinement is
+    okp_rig_bearings, then okp_refine_pose_views against the bearings of every camera; "refine" is ops.refine_pose_views' dict plus "obs".
     World frame (world_frame=True; the step's frame_pose [B,12] takes the table's frame to the world, an all-NaN row = missing in this tick):
     okp_change_frame on the step's points and, with the pose, on the table and the poses -> "world": {"T", "points", "overflow" (the
     step's word | ops.FRAME_MISSING)} and "tab", "pose".
@@ -766,16 +782,20 @@ class _ObjectStage:
                 ops.check_refine_hypotheses(type_count)
         self.refine = refine
 
-    def run(self, tab, n_obj, points, overflow, frame_pose, cam=None):
+    def run(self, tab, n_obj, points, overflow, frame_pose, cam=None, rig=None):
         """The stage behind a step: tab = the object point table (None without a model), n_obj, points (what the world frame shows besides the
-        objects) and overflow = the step's own; frame_pose: the checked per-step pose, or None; cam: the camera of a refined table
+        objects) and overflow = the step's own; frame_pose: the checked per-step pose, or None; cam: the camera of a refined table; rig: what
+        a refined rig tick observes with - {"table", "count", "xyc", "match", "fused", "views"}
         -> the entries the step's dict gains, in order: "pose", "refine", "world", "track"."""
         out, fed = {}, None
         if self.model.host is not None:
             model = self.model(tab.device)
             fed = out["pose"] = dict(ops.object_pose(tab, n_obj, model, self.type_count, self.max_rmse), tab=tab)
             if self.refine is not None:
-                if self.refine.resolve_assignment:
+                if rig is not None:
+                    obs = ops.rig_bearings(rig["table"], rig["count"], rig["xyc"], rig["match"], rig["fused"], self.type_count)
+                    out["refine"] = dict(ops.refine_pose_views(obs, rig["views"], fed, n_obj, model, self.refine), obs=obs)
+                elif self.refine.resolve_assignment:
                     out["refine"] = ops.refine_assignments(tab, fed, n_obj, model, self.type_count, cam, self.refine)
                 else:
                     out["refine"] = ops.refine_pose(tab, fed, n_obj, model, cam, self.refine)
@@ -1232,8 +1252,17 @@ class StereoStreamPipeline(_ObjectStagePipeline):
     Pose, world frame and tracking (all optional, all need the fusion - the fused tick is what has ONE frame) end the fused device ticks, inside
     the captured graph and after the gather on every rank with no further collective (every rank keeps the same tracker): _ObjectStage describes
     the launches and the keys "pose", "world" and "track" they add to the tick's dict, for ONE stream in the RIG frame.  Here: the table is
-    okp_rig_object_points' [1,fuse_capacity,S,4]; "world"["points"] is the fused clusters [K,cap_f,4] in the world frame.  There is no `refine`
-    (BatchedKeypointPipeline has one): the fused points come from stereo triangulation, not from one camera's bearings and depth map.
+    okp_rig_object_points' [1,fuse_capacity,S,4]; "world"["points"] is the fused clusters [K,cap_f,4] in the world frame.
+    refine = ops.RefineConfig(...) (needs points_3d): the fitted pose rests on fused points, means of two-view triangulations with the depth
+    noise of a short baseline; the peaks they came from do not carry it.  okp_rig_bearings collects them as one bearing per object, table slot
+    and camera, and okp_refine_pose_views minimises their reprojection error in all 2P cameras at once, from the fitted pose (sigma_px, iters
+    and damping of the config; no depth term, so sigma_z is not used; resolve_assignment=True is refused with ops.OkpNotOffered, an OkpError that is also the TypeError
+    the call raised while the rig took no `refine`: not offered for a rig).  The tick's
+    dict gains "refine" - ops.refine_pose_views' dict plus "obs" -, "pose" keeps its bits, and the world-frame change and the tracker take the
+    refined pose (the fitted one where the refinement's status is not 0).  The views table (ops.rig_views) is built at construction and
+    uploaded once per device, like the calibration and the poses.  rig_objects(out) then adds 'T_BO_refined' (None where 'T_BO' is),
+    'reprojection_rmse' (before, after; map pixels), 'refine_observations', 'pose_information' (6 x 6) and 'refine_status'.  Under an
+    initialised process group tick_sharded refuses a refinement: the other ranks' peaks are not in the gathered payload.
     rig_objects(out) adds 'T_BO' (4 x 4, model -> rig coordinates, or None), 'rmse', 'ambiguity' and 'pose_status' to every object; with track
     'track_id', 'T_BO_track', 'velocity', 'track_hits' and 'confirmed'; with world_frame 'T_WO' and 'T_WO_track' next to them.  rig_tracks(out)
     lists the live tracks, reset_tracks() empties the tracker.
@@ -1242,8 +1271,10 @@ class StereoStreamPipeline(_ObjectStagePipeline):
     = missing in this tick).  Without world_frame a rig_pose is refused."""
 
     def __init__(self, net, stereo_camera, keypoint_config, capacity=16, max_distance=3.0, rig_poses=None, merge_radius=None, object_radius=None,
-                 fuse_capacity=None, points_3d=None, max_rmse=None, track=None, world_frame=False):
+                 fuse_capacity=None, points_3d=None, max_rmse=None, track=None, world_frame=False, refine=None):
         self.net = net
+        if isinstance(refine, ops.RefineConfig) and refine.resolve_assignment:
+            raise OkpNotOffered("refine with resolve_assignment=True: not offered for a rig (its refinement keeps the assignment of the fit)")
         if world_frame and rig_poses is None:
             raise OkpError("world_frame without rig_poses, merge_radius and object_radius: the fused tick is what has one frame to pose")
         self.rig = None if hasattr(stereo_camera, "left_camera") else list(stereo_camera)       # one StereoCamera, or a sequence of them
@@ -1278,7 +1309,9 @@ class StereoStreamPipeline(_ObjectStagePipeline):
                                f"{len(self.config)} types, {self.n_fused_pairs} x {self.capacity} rows asked for")
         if points_3d is not None and not given:
             raise OkpError("points_3d without rig_poses, merge_radius and object_radius: the pose is fitted to the fused objects of the rig")
-        self._stage = _ObjectStage(self.config[1:], points_3d, max_rmse, track, self.fuse_capacity if given else 0, "fuse_capacity", world_frame)
+        self._stage = _ObjectStage(self.config[1:], points_3d, max_rmse, track, self.fuse_capacity if given else 0, "fuse_capacity", world_frame, refine)
+        on = refine is not None                 # (_ObjectStage refused a refinement without points_3d, and points_3d without the fusion)
+        self._views = _PerDevice(ops.rig_views(stereo_camera if self.rig is None else self.rig, rig_poses) if on else None)      # (.host None: refinement off)
 
     _table_host = property(lambda self: self._table.host)
     _poses_host = property(lambda self: self._poses.host)
@@ -1287,7 +1320,11 @@ class StereoStreamPipeline(_ObjectStagePipeline):
         """What follows okp_rig_fuse in a fused device tick: the table of the fused objects (with a model), then the object stage."""
         fused = out["fused"]
         tab = ops.rig_object_points(fused, self.config[1:]) if self._model_host is not None else None
-        out.update(self._stage.run(tab, fused["n_obj"], fused["fused"], fused["overflow"], rig_pose))
+        rig = None
+        if self._views.host is not None:        # what the refinement observes with: this tick's own peaks (the whole rig's)
+            dev = fused["fused"].device
+            rig = {"table": self._table(dev), "views": self._views(dev), "fused": fused, **{k: out[k] for k in ("count", "xyc", "match")}}
+        out.update(self._stage.run(tab, fused["n_obj"], fused["fused"], fused["overflow"], rig_pose, rig=rig))
 
     def rig_tracks(self, out):
         """Every live track after the fused tick `out`, coasting ones included, in slot order: a list of {'track_id', 'T_BO_track' (4 x 4,
@@ -1463,6 +1500,7 @@ class StereoStreamPipeline(_ObjectStagePipeline):
         step.static_pose = static_pose
         step._table = self._table(frames.device)               # (the graph reads it on every replay)
         step._poses = self._poses.on.get(frames.device)        # (and the pose table)
+        step._views = self._views.on.get(frames.device)        # (and, with refine, the views table)
         self._stage.pin(step, static_out)
         return step
 
@@ -1507,10 +1545,13 @@ class StereoStreamPipeline(_ObjectStagePipeline):
                 raise OkpError(f"{frames_local.shape[0]} frames for {n_pairs_total} stereo pairs")
             out = self.tick_device(frames_local, heat_override=heat_override, rig_pose=rig_pose)
             whole = {"points": out["points"], "overflow": out["overflow"], "local": out}
-            for key in ("fused", "pose", "world", "track"):
+            for key in ("fused", "pose", "refine", "world", "track"):
                 if key in out:
                     whole[key] = out[key]
             return whole
+        if self.refine is not None:
+            raise OkpError("tick_sharded with refine under a process group: the refinement reads every pair's peaks and matches, and the gathered "
+                           "payload holds the other ranks' 3D points only")
         start, n_local = distributed.shard(int(n_pairs_total), dist.get_rank(), dist.get_world_size())
         if frames_local.shape[0] != 2 * n_local:
             raise OkpError(f"rank {dist.get_rank()} holds {frames_local.shape[0]} frames; shard({n_pairs_total}, {dist.get_rank()}, "
@@ -1540,8 +1581,10 @@ class StereoStreamPipeline(_ObjectStagePipeline):
              "confidence": [(1,), (n_1,), ...] float64, "views": [(1,), (n_1,), ...] int32 bit masks of the contributing pairs}
         plus, for a pipeline built with points_3d, 'T_BO' (4 x 4 float64: model -> rig coordinates; None where the status is ops.POSE_FEW or
         ops.POSE_DEGENERATE), 'rmse', 'ambiguity' (the runner-up assignment's rmse) and 'pose_status', and, for one built with track,
-        'track_id' (None where the object went to no track), 'T_BO_track' (the filtered pose), 'velocity', 'track_hits' and 'confirmed' -
-        read in ONE device -> host copy.  Raises OkpError when the tick's overflow word is set, as results() does (bit ops.FUSE_OVERFLOW:
+        'track_id' (None where the object went to no track), 'T_BO_track' (the filtered pose), 'velocity', 'track_hits' and 'confirmed', and,
+        for one built with refine, 'T_BO_refined' (None where 'T_BO' is; the fitted pose where 'refine_status' is not 0), 'reprojection_rmse'
+        (before, after), 'refine_observations', 'pose_information' (6 x 6) and 'refine_status'; with world_frame 'T_WO' then comes from the
+        refined pose - read in ONE device -> host copy.  Raises OkpError when the tick's overflow word is set, as results() does (bit ops.FUSE_OVERFLOW:
         a type had more than fuse_capacity clusters).  tick(), the host tick, does not fuse: its return value is not accepted here."""
         if not isinstance(out, dict) or "fused" not in out:
             raise OkpError("rig_objects reads a fused device tick: the dict of tick_device / capture_device / tick_sharded of a pipeline "
@@ -1549,7 +1592,7 @@ class StereoStreamPipeline(_ObjectStagePipeline):
         f = out["fused"]
         fields = {"overflow": out["overflow"], "n_obj": f["n_obj"], "n_fused": f["n_fused"], "views": f["views"], "object": f["object"], "fused": f["fused"]}
         if "pose" in out:
-            fields.update(_pose_fields(out["pose"], 0))
+            fields.update(_pose_fields(out["pose"], 0, out.get("refine")))
         if "track" in out:
             fields.update(_track_fields(out["track"], 0))
         in_world = "world" in out
@@ -1572,6 +1615,8 @@ class StereoStreamPipeline(_ObjectStagePipeline):
             objects.append({"p_B": p_B, "confidence": conf, "views": seen})
             if "pose" in out:
                 objects[-1].update(_pose_entries(host, o, "T_BO"))
+                if "refine" in out:
+                    objects[-1].update(_rig_refine_entries(host, o, objects[-1]["T_BO"]))
                 if in_world:
                     objects[-1]["T_WO"] = None if missing else _pose_entries(dict(host, pose=host["world_pose"]), o, "T_WO")["T_WO"]
             if "track" in out:
