@@ -46,7 +46,9 @@ extern "C" {
                                     okp_refine_assignments, OKP_REFINE_NONE, OKP_REFINE_MAX_HYPOTHESES (interchangeable key points resolved by
                                     refining every assignment);
                                     okp_rig_bearings, okp_refine_pose_views, OKP_REFINE_MAX_VIEWS (a rig's object poses refined against every
-                                    camera's bearings) */
+                                    camera's bearings);
+                                    okp_window_push, okp_refine_pose_views_each (tracked objects refined against a sliding window of ticks'
+                                    bearings) */
 
 /* OKP_F16: IEEE half activations / weights, fp32 accumulate (BASELINE configs[4]).
  * OKP_F32X3 (okp_conv plans only): fp32 activations, weights and results like OKP_F32 - every tensor argument of such a plan is an
@@ -943,6 +945,67 @@ int okp_refine_pose_views(const double* obs_dev, const double* views_dev, const 
                           const int32_t* n_obj_dev, const double* model_dev, double sigma_px, int32_t iters, double damping, int32_t B,
                           int32_t max_obj, int32_t S, int32_t V, double* pose_out_dev, double* fit_dev, int32_t* n_obs_dev,
                           double* information_dev, int32_t* status_dev, void* stream);
+/* okp_refine_pose_views_each: okp_refine_pose_views with one views table per object - views [B][max_obj][V][14] fp64, object (b, o) reads
+ * its own V rows.  Everything else is that entry point's: cost, step, Cholesky, statuses, outputs, refusals; it is the same kernel,
+ * instantiated with a per-object offset on the table (okp_refine_pose_views' instance and bits are unchanged), so with one table
+ * replicated per object the two give the same bits.  A view none of whose S entries is filled contributes nothing, WHATEVER its row holds - zeros, NaN: the masking of
+ * unobserved entries covers it, and q_z <= 0 counts for observations only - so a table may carry unused rows. */
+int okp_refine_pose_views_each(const double* obs_dev, const double* views_dev, const double* pose_dev, const int32_t* assignment_dev,
+                               const int32_t* n_obj_dev, const double* model_dev, double sigma_px, int32_t iters, double damping, int32_t B,
+                               int32_t max_obj, int32_t S, int32_t V, double* pose_out_dev, double* fit_dev, int32_t* n_obs_dev,
+                               double* information_dev, int32_t* status_dev, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * A sliding window of ticks' bearings per track (csrc/okp_window.hip).  Every pose above is a single-tick estimate: okp_refine_pose fits one
+ * camera's bearings with the depth head as a weak prior, okp_refine_pose_views the cameras of one rig tick, and the tracker smooths with
+ * fixed gains.  A camera on an arm or in a hand that moves past a STATIC object sees it from many viewpoints, and in the world frame the
+ * step has the camera pose T_WC of every tick: the key points' bearings over W ticks are then a multi-view triangulation that does not
+ * use the depth head at all.  okp_window_push keeps the last W ticks' observations of every track slot; okp_refine_pose_views_each, called
+ * on that state (obs = win_obs, views = win_views, pose = start, an identity assignment, n_obj = T, B x T "objects", V = W), refines the
+ * track's world pose T_WO against them.  The gain comes from the BASELINE the camera travelled, not from averaging: a standing camera
+ * gathers W bearings along one ray and leaves the depth as undetermined as one tick does.  There is no reference implementation: the
+ * specification is this comment (tests/window_spec.py restates it in NumPy, and the device agrees with it BIT FOR BIT).
+ *
+ * okp_window_push: one launch, one wave per (stream, track slot), fp64, no atomics, no host wait, capturable; the same bits on every run.
+ * State, in device memory, updated in place, kept across calls (and graph replays) like the tracker's:
+ *   win_obs [B][T][S][W][2] fp64   the bearing (u, v) of MODEL ROW r in the camera of ring column w; (NaN, NaN) = none.  Indexed by model
+ *                                  row, not table slot: a later change of the assignment does not matter
+ *   win_views [B][T][W][14] fp64   column w's camera: [R | t] row-major 3 x 4 taking WORLD coordinates to that tick's camera, then fx, fy;
+ *                                  zeros when empty
+ *   win_i [B][T][4] int32          owner id, head (the column the next push writes), filled, one spare kept 0
+ *   The empty state is all-NaN win_obs with zero win_views and win_i.
+ * Inputs, all in device memory: the CAMERA-frame table tab [B][max_obj][S][4] fp64 (okp_object_points); assignment [B][max_obj][S] int32 -
+ *   okp_refine_assignments' where it ran, otherwise okp_object_pose's -; status [B][max_obj] int32, the pose status the tracker was given;
+ *   the tracker's meas_of [B][T] int32, track_i [B][T][4] int32, track_f [B][T][16] fp64 and track_pose [B][T][12] fp64 (world frame);
+ *   T_WC [B][12] fp64 (okp_change_frame's T).  Host: cam (only fx and fy are read), B, max_obj, S, T, W, min_views, max_speed (metres per
+ *   second; its square is formed once on the host in fp64; +infinity: never).
+ * Per slot i of stream b, in this order ("empty the ring": NaN to every word of win_obs[b][i], 0 to every word of win_views[b][i]):
+ *   1. id = track_i[b][i][0].  id == 0 (a free slot): empty the ring, win_i = (0, 0, 0, 0); steps 2 - 4 are skipped.
+ *   2. Otherwise, when id != the owner - or head is outside [0, W) or filled outside [0, W], a state that no call leaves -: empty the ring,
+ *      win_i = (id, 0, 0, 0).
+ *   3. With v = track_f[b][i][3..5], the track's velocity: when (vx*vx + vy*vy) + vz*vz > max_speed^2 (no contraction; false for NaN):
+ *      empty the ring, head = filled = 0.  The window assumes a static object.
+ *   4. Push, only when o = meas_of[b][i] is in [0, max_obj), status[b][o] == 0 and all 12 values of T_WC[b] are finite; the column is
+ *      w = head.  First every model row's entry of column w becomes (NaN, NaN).  Then, over the slots s of tab[b][o] in ASCENDING order: the
+ *      slot counts when a = assignment[b][o][s] is in [0, S), its four values (X, Y, Z, c) are finite and Z != 0; then
+ *      win_obs[b][i][a][w] = (X / Z, Y / Z) - divisions; of two slots with the same a the later one stays.  The views row is the inverse of
+ *      T_WC[b] = [R | t] in okp_change_frame's inverse association: R'[i][j] = R[j][i] copied, t'[i] = (R[0][i]*d0 + R[1][i]*d1) + R[2][i]*d2
+ *      with d = -t (no contraction), then cam->fx, cam->fy.  head = (head + 1) mod W, filled = min(filled + 1, W).
+ * Outputs, all written by every call:
+ *   n_views [B][T] int32 = filled
+ *   start [B][T][12] fp64 = track_pose[b][i] bit for bit when filled >= min_views, otherwise NaN: okp_refine_pose_views_each then leaves
+ *   free slots and short windows as OKP_REFINE_SKIPPED
+ * Limits.  Static objects only: the window does not model motion, max_speed is a guard, not a model.  No robust loss and uniform weights
+ * in the refinement: one wrong peak in one tick pulls the pose.  The error of the camera poses goes straight into the result: the
+ * refinement takes T_WC as exact.  The window of a rig (2 P cameras x W ticks) would exceed OKP_REFINE_MAX_VIEWS: it is not offered.
+ * Refused on the host before any launch (OKP_EINVAL, the message names the argument): W outside [1, OKP_REFINE_MAX_VIEWS], T outside
+ * [1, OKP_TRACK_MAX_TRACKS], S outside [1, OKP_POSE_MAX_POINTS], B or max_obj < 1, min_views outside [1, W], max_speed not positive (NaN
+ * included), cam->fx or cam->fy not positive and finite, a null pointer.
+ * ---------------------------------------------------------------------------------- */
+int okp_window_push(const double* tab_dev, const int32_t* assignment_dev, const int32_t* status_dev, const int32_t* meas_of_dev,
+                    const int32_t* track_i_dev, const double* track_f_dev, const double* track_pose_dev, const double* T_WC_dev,
+                    const okp_camera* cam, int32_t B, int32_t max_obj, int32_t S, int32_t T, int32_t W, int32_t min_views, double max_speed,
+                    double* win_obs_dev, double* win_views_dev, int32_t* win_i_dev, int32_t* n_views_dev, double* start_dev, void* stream);
 
 /* Undistort only (FisheyeCamera.undistort, camera_utils.py:75-81 / RadTanPinholeCamera.undistort, :57-62, by cam->model):
  * xy [m][2] fp32 -> out [m][2] fp64.  okp_fisheye_undistort is the same entry point under its round-1 name. */

@@ -388,6 +388,21 @@ def refine_pose_views(obs, views, pose, assignment, n_obj, model, sigma_px, iter
                                                 status.data_ptr(), stream), "okp_refine_pose_views")
 
 
+def refine_pose_views_each(obs, views, pose, assignment, n_obj, model, sigma_px, iters, damping, pose_out, fit, n_obs, information, status, stream):
+    b, max_obj, s, v, _ = obs.shape
+    _lib.check(_lib.lib().okp_refine_pose_views_each(obs.data_ptr(), views.data_ptr(), pose.data_ptr(), assignment.data_ptr(), n_obj.data_ptr(), model.data_ptr(),
+                                                     sigma_px, iters, damping, b, max_obj, s, v, pose_out.data_ptr(), fit.data_ptr(), n_obs.data_ptr(),
+                                                     information.data_ptr(), status.data_ptr(), stream), "okp_refine_pose_views_each")
+
+
+# ---- a sliding window of ticks' bearings per track (csrc/okp_window.hip): win_obs [B,T,S,W,2], win_views [B,T,W,14], win_i [B,T,4] ------------------
+def window_push(camera, tab, assignment, status, meas_of, track_i, track_f, track_pose, T_WC, min_views, max_speed, win_obs, win_views, win_i, n_views, start, stream):
+    b, max_obj, s, _ = tab.shape
+    _lib.check(_lib.lib().okp_window_push(tab.data_ptr(), assignment.data_ptr(), status.data_ptr(), meas_of.data_ptr(), track_i.data_ptr(), track_f.data_ptr(),
+                                          track_pose.data_ptr(), T_WC.data_ptr(), _camera(camera), b, max_obj, s, win_obs.shape[1], win_obs.shape[3], min_views, max_speed,
+                                          win_obs.data_ptr(), win_views.data_ptr(), win_i.data_ptr(), n_views.data_ptr(), start.data_ptr(), stream), "okp_window_push")
+
+
 # ---- scoring labelled scenes -----------------------------------------------------------------------------------------------------------------
 def project_labels(camera, world_points, T_WC, scale, crop_x, crop_y, labels, stream):
     _lib.check(_lib.lib().okp_project_labels(_camera(camera), world_points.data_ptr(), world_points.shape[0], T_WC.data_ptr(), T_WC.shape[0], scale, crop_x, crop_y,

@@ -16,7 +16,9 @@
 //                                  xor-butterfly over the 64 lanes makes the sums of H, g and the cost - after it every lane holds the
 //                                  same bits - and every lane solves the same 6 x 6 system (refine_step), so nothing is broadcast.  The
 //                                  loop over a lane's slots is unrolled to the 16 a model can have; a pass in which no lane's slot has a
-//                                  model row is skipped on a scalar branch.
+//                                  model row is skipped on a scalar branch.  A template on where the lane's row of `views` lies: one
+//                                  table for every object (okp_refine_pose_views), or one per object (okp_refine_pose_views_each: the
+//                                  sliding window of csrc/okp_window.hip, whose views are the ticks of each track's own ring).
 // fp64, no atomics, no host wait; the summation order is fixed, so the bits are the same on every run.
 #include "okp_pose_math.h"           // PoseTypes, pose_types, finite64, refine_step, the sums layout
 
@@ -107,6 +109,9 @@ __device__ __forceinline__ void views_butterfly(double (&acc)[OKP_REFINE_SUMS]) 
     for (int i = 0; i < 28; ++i) acc[i] += __shfl_xor(acc[i], off);
 }
 
+// EACH: `views` holds one table of V rows per object (okp_refine_pose_views_each) instead of one for all; the only line that differs is the
+// address of the lane's row, so the shared-table instance is the code it was
+template <bool EACH>
 __global__ __launch_bounds__(64) void okp_refine_pose_views_kernel(const ViewsParams P) {
   const int lane = threadIdx.x;
   const size_t oi = blockIdx.x;
@@ -129,7 +134,7 @@ __global__ __launch_bounds__(64) void okp_refine_pose_views_kernel(const ViewsPa
   // this lane's camera: [R_v | t_v] and k_v = (fx_v, fy_v) / sigma_px (the lanes past V: an identity that observes nothing)
   double rv[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0}, tv[3] = {0.0, 0.0, 0.0}, kx = 1.0, ky = 1.0;
   if (view) {
-    const double* row = P.views + (size_t)cam * 14;
+    const double* row = P.views + (EACH ? oi * (size_t)V * 14 : (size_t)0) + (size_t)cam * 14;
 #pragma unroll
     for (int i = 0; i < 3; ++i) { rv[3 * i + 0] = row[4 * i + 0]; rv[3 * i + 1] = row[4 * i + 1]; rv[3 * i + 2] = row[4 * i + 2]; tv[i] = row[4 * i + 3]; }
     kx = row[12] / P.sigma_px; ky = row[13] / P.sigma_px;
@@ -286,10 +291,10 @@ extern "C" int okp_rig_bearings(const int32_t* count, const float* xyc, const in
   return okp_check_hip(hipGetLastError(), "okp_rig_bearings launch");
 }
 
-extern "C" int okp_refine_pose_views(const double* obs, const double* views, const double* pose, const int32_t* assignment, const int32_t* n_obj,
-                                     const double* model, double sigma_px, int32_t iters, double damping, int32_t B, int32_t max_obj, int32_t S,
-                                     int32_t V, double* pose_out, double* fit, int32_t* n_obs, double* information, int32_t* status, void* stream) {
-  const char* fn = "okp_refine_pose_views";
+// the two entry points: one views table for every object, or one per object
+static int refine_views_launch(const char* fn, bool each, const double* obs, const double* views, const double* pose, const int32_t* assignment, const int32_t* n_obj,
+                               const double* model, double sigma_px, int32_t iters, double damping, int32_t B, int32_t max_obj, int32_t S, int32_t V,
+                               double* pose_out, double* fit, int32_t* n_obs, double* information, int32_t* status, void* stream) {
   if (B < 1) { okp_set_error("%s: B = %d; a batch holds at least one frame", fn, B); return OKP_EINVAL; }
   if (max_obj < 1) { okp_set_error("%s: max_obj = %d; a frame holds at least one object", fn, max_obj); return OKP_EINVAL; }
   if ((long long)B * max_obj > 0x7fffffffll) { okp_set_error("%s: B * max_obj = %lld objects do not fit one launch", fn, (long long)B * max_obj); return OKP_EINVAL; }
@@ -313,6 +318,21 @@ extern "C" int okp_refine_pose_views(const double* obs, const double* views, con
   p.max_obj = max_obj; p.S = S; p.V = V; p.iters = iters; p.sigma_px = sigma_px; p.damping = damping;
   while ((1 << p.vshift) < V) ++p.vshift;
   p.pose_out = pose_out; p.fit = fit; p.n_obs = n_obs; p.information = information; p.status = status;
-  hipLaunchKernelGGL(okp_refine_pose_views_kernel, dim3((unsigned)n_total), dim3(64), 0, (hipStream_t)stream, p);
-  return okp_check_hip(hipGetLastError(), "okp_refine_pose_views launch");
+  if (each) hipLaunchKernelGGL(okp_refine_pose_views_kernel<true>, dim3((unsigned)n_total), dim3(64), 0, (hipStream_t)stream, p);
+  else hipLaunchKernelGGL(okp_refine_pose_views_kernel<false>, dim3((unsigned)n_total), dim3(64), 0, (hipStream_t)stream, p);
+  return okp_check_hip(hipGetLastError(), each ? "okp_refine_pose_views_each launch" : "okp_refine_pose_views launch");
+}
+
+extern "C" int okp_refine_pose_views(const double* obs, const double* views, const double* pose, const int32_t* assignment, const int32_t* n_obj,
+                                     const double* model, double sigma_px, int32_t iters, double damping, int32_t B, int32_t max_obj, int32_t S,
+                                     int32_t V, double* pose_out, double* fit, int32_t* n_obs, double* information, int32_t* status, void* stream) {
+  return refine_views_launch("okp_refine_pose_views", false, obs, views, pose, assignment, n_obj, model, sigma_px, iters, damping, B, max_obj, S, V, pose_out, fit,
+                             n_obs, information, status, stream);
+}
+
+extern "C" int okp_refine_pose_views_each(const double* obs, const double* views, const double* pose, const int32_t* assignment, const int32_t* n_obj,
+                                          const double* model, double sigma_px, int32_t iters, double damping, int32_t B, int32_t max_obj, int32_t S,
+                                          int32_t V, double* pose_out, double* fit, int32_t* n_obs, double* information, int32_t* status, void* stream) {
+  return refine_views_launch("okp_refine_pose_views_each", true, obs, views, pose, assignment, n_obj, model, sigma_px, iters, damping, B, max_obj, S, V, pose_out,
+                             fit, n_obs, information, status, stream);
 }

@@ -752,25 +752,68 @@ void rig_bearings(const Tensor& table, const Tensor& count, const Tensor& xyc, c
                             (int32_t)cap_f, tc.data(), obs.data_ptr<double>(), sp(stream)), "okp_rig_bearings");
 }
 
-void refine_pose_views(const Tensor& obs, const Tensor& views, const Tensor& pose, const Tensor& assignment, const Tensor& n_obj, const Tensor& model, double sigma_px,
-                       int64_t iters, double damping, const Tensor& pose_out, const Tensor& fit, const Tensor& n_obs, const Tensor& information, const Tensor& status,
-                       int64_t stream) {
+// each = false: views [V,14], one table for every object (okp_refine_pose_views); each = true: views [B,max_obj,V,14] (okp_refine_pose_views_each)
+void refine_views(bool each, const Tensor& obs, const Tensor& views, const Tensor& pose, const Tensor& assignment, const Tensor& n_obj, const Tensor& model, double sigma_px,
+                  int64_t iters, double damping, const Tensor& pose_out, const Tensor& fit, const Tensor& n_obs, const Tensor& information, const Tensor& status,
+                  int64_t stream) {
   check_dev(obs, at::kDouble, "obs"); check_dev(views, at::kDouble, "views"); check_dev(pose, at::kDouble, "pose"); check_dev(assignment, at::kInt, "assignment");
   check_dev(n_obj, at::kInt, "n_obj"); check_dev(model, at::kDouble, "model"); check_dev(pose_out, at::kDouble, "pose_out"); check_dev(fit, at::kDouble, "fit");
   check_dev(n_obs, at::kInt, "n_obs"); check_dev(information, at::kDouble, "information"); check_dev(status, at::kInt, "status");
   TORCH_CHECK(obs.dim() == 5 && obs.size(4) == 2, "okp: obs is [B,max_obj,S,V,2] float64");
   const int64_t B = obs.size(0), max_obj = obs.size(1), S = obs.size(2), V = obs.size(3);
-  TORCH_CHECK(views.numel() == V * 14 && pose.numel() == B * max_obj * 12 && assignment.numel() == B * max_obj * S && n_obj.numel() == B && model.numel() == S * 3,
+  TORCH_CHECK(views.numel() == (each ? B * max_obj : 1) * V * 14, each ? "okp: refine_pose_views_each takes views [B,max_obj,V,14]: one table per object" :
+                                                                           "okp: refine_pose_views inputs are views [V,14], pose [B,max_obj,12], assignment [B,max_obj,S], n_obj [B] and model [S,3]");
+  TORCH_CHECK(pose.numel() == B * max_obj * 12 && assignment.numel() == B * max_obj * S && n_obj.numel() == B && model.numel() == S * 3,
               "okp: refine_pose_views inputs are views [V,14], pose [B,max_obj,12], assignment [B,max_obj,S], n_obj [B] and model [S,3]");
   TORCH_CHECK(pose_out.numel() == B * max_obj * 12 && fit.numel() == B * max_obj * 2 && n_obs.numel() == B * max_obj && information.numel() == B * max_obj * 36 &&
               status.numel() == B * max_obj,
               "okp: refine_pose_views outputs are pose_out [B,max_obj,12], fit [B,max_obj,2], n_obs [B,max_obj], information [B,max_obj,36] and status [B,max_obj]");
   TORCH_CHECK(iters >= INT32_MIN && iters <= INT32_MAX, "okp: iters does not fit an int32");
   TORCH_CHECK(B <= INT32_MAX && max_obj <= INT32_MAX && S <= INT32_MAX && V <= INT32_MAX, "okp: obs is too large");
-  check_rc(okp_refine_pose_views(obs.data_ptr<double>(), views.data_ptr<double>(), pose.data_ptr<double>(), assignment.data_ptr<int32_t>(), n_obj.data_ptr<int32_t>(),
-                                 model.data_ptr<double>(), sigma_px, (int32_t)iters, damping, (int32_t)B, (int32_t)max_obj, (int32_t)S, (int32_t)V,
-                                 pose_out.data_ptr<double>(), fit.data_ptr<double>(), n_obs.data_ptr<int32_t>(), information.data_ptr<double>(),
-                                 status.data_ptr<int32_t>(), sp(stream)), "okp_refine_pose_views");
+  check_rc((each ? okp_refine_pose_views_each : okp_refine_pose_views)(
+               obs.data_ptr<double>(), views.data_ptr<double>(), pose.data_ptr<double>(), assignment.data_ptr<int32_t>(), n_obj.data_ptr<int32_t>(),
+               model.data_ptr<double>(), sigma_px, (int32_t)iters, damping, (int32_t)B, (int32_t)max_obj, (int32_t)S, (int32_t)V,
+               pose_out.data_ptr<double>(), fit.data_ptr<double>(), n_obs.data_ptr<int32_t>(), information.data_ptr<double>(),
+               status.data_ptr<int32_t>(), sp(stream)), each ? "okp_refine_pose_views_each" : "okp_refine_pose_views");
+}
+
+void refine_pose_views(const Tensor& obs, const Tensor& views, const Tensor& pose, const Tensor& assignment, const Tensor& n_obj, const Tensor& model, double sigma_px,
+                       int64_t iters, double damping, const Tensor& pose_out, const Tensor& fit, const Tensor& n_obs, const Tensor& information, const Tensor& status,
+                       int64_t stream) {
+  refine_views(false, obs, views, pose, assignment, n_obj, model, sigma_px, iters, damping, pose_out, fit, n_obs, information, status, stream);
+}
+
+void refine_pose_views_each(const Tensor& obs, const Tensor& views, const Tensor& pose, const Tensor& assignment, const Tensor& n_obj, const Tensor& model, double sigma_px,
+                            int64_t iters, double damping, const Tensor& pose_out, const Tensor& fit, const Tensor& n_obs, const Tensor& information, const Tensor& status,
+                            int64_t stream) {
+  refine_views(true, obs, views, pose, assignment, n_obj, model, sigma_px, iters, damping, pose_out, fit, n_obs, information, status, stream);
+}
+
+// A sliding window of ticks' bearings per track slot (csrc/okp_window.hip): the camera-frame table, the assignment and status the tracker's tick had, the tracker's
+// meas_of / track_i / track_f / track_pose and T_WC -> the state win_obs [B,T,S,W,2], win_views [B,T,W,14], win_i [B,T,4] stepped in place, n_views [B,T], start [B,T,12]
+void window_push(at::ArrayRef<double> camera, const Tensor& tab, const Tensor& assignment, const Tensor& status, const Tensor& meas_of, const Tensor& track_i,
+                 const Tensor& track_f, const Tensor& track_pose, const Tensor& T_WC, int64_t min_views, double max_speed, const Tensor& win_obs, const Tensor& win_views,
+                 const Tensor& win_i, const Tensor& n_views, const Tensor& start, int64_t stream) {
+  check_dev(tab, at::kDouble, "tab"); check_dev(assignment, at::kInt, "assignment"); check_dev(status, at::kInt, "status"); check_dev(meas_of, at::kInt, "meas_of");
+  check_dev(track_i, at::kInt, "track_i"); check_dev(track_f, at::kDouble, "track_f"); check_dev(track_pose, at::kDouble, "track_pose"); check_dev(T_WC, at::kDouble, "T_WC");
+  check_dev(win_obs, at::kDouble, "win_obs"); check_dev(win_views, at::kDouble, "win_views"); check_dev(win_i, at::kInt, "win_i"); check_dev(n_views, at::kInt, "n_views");
+  check_dev(start, at::kDouble, "start");
+  TORCH_CHECK(tab.dim() == 4 && tab.size(3) == 4, "okp: tab is [B,max_obj,S,4] float64");
+  TORCH_CHECK(win_obs.dim() == 5 && win_obs.size(4) == 2, "okp: win_obs is [B,T,S,W,2] float64");
+  const int64_t B = tab.size(0), max_obj = tab.size(1), S = tab.size(2), T = win_obs.size(1), W = win_obs.size(3);
+  TORCH_CHECK(win_obs.size(0) == B && win_obs.size(2) == S && win_views.numel() == B * T * W * 14 && win_i.numel() == B * T * 4,
+              "okp: the window state is win_obs [B,T,S,W,2], win_views [B,T,W,14] and win_i [B,T,4] for the table's B and S");
+  TORCH_CHECK(assignment.numel() == B * max_obj * S && status.numel() == B * max_obj && meas_of.numel() == B * T && track_i.numel() == B * T * 4 &&
+              track_f.numel() == B * T * 16 && track_pose.numel() == B * T * 12 && T_WC.numel() == B * 12,
+              "okp: window_push inputs are assignment [B,max_obj,S], status [B,max_obj], meas_of [B,T], track_i [B,T,4], track_f [B,T,16], track_pose [B,T,12] and T_WC [B,12]");
+  TORCH_CHECK(n_views.numel() == B * T && start.numel() == B * T * 12, "okp: window_push outputs are n_views [B,T] and start [B,T,12]");
+  TORCH_CHECK(min_views >= INT32_MIN && min_views <= INT32_MAX, "okp: min_views does not fit an int32");
+  TORCH_CHECK(B <= INT32_MAX && max_obj <= INT32_MAX && S <= INT32_MAX && T <= INT32_MAX && W <= INT32_MAX, "okp: tab or win_obs is too large");
+  const okp_camera cam = camera_of(camera);
+  check_rc(okp_window_push(tab.data_ptr<double>(), assignment.data_ptr<int32_t>(), status.data_ptr<int32_t>(), meas_of.data_ptr<int32_t>(), track_i.data_ptr<int32_t>(),
+                           track_f.data_ptr<double>(), track_pose.data_ptr<double>(), T_WC.data_ptr<double>(), &cam, (int32_t)B, (int32_t)max_obj, (int32_t)S, (int32_t)T,
+                           (int32_t)W, (int32_t)min_views, max_speed, win_obs.data_ptr<double>(), win_views.data_ptr<double>(), win_i.data_ptr<int32_t>(),
+                           n_views.data_ptr<int32_t>(), start.data_ptr<double>(), sp(stream)), "okp_window_push");
 }
 
 void lift_peaks(at::ArrayRef<double> camera, const Tensor& count, const Tensor& xyc, const Tensor& depth, int64_t max_x, int64_t max_y, const Tensor& out, int64_t stream) {
@@ -944,6 +987,10 @@ TORCH_LIBRARY(okp, m) {
         rig_bearings);
   m.def("refine_pose_views(Tensor obs, Tensor views, Tensor pose, Tensor assignment, Tensor n_obj, Tensor model, float sigma_px, int iters, float damping, "
         "Tensor(a!) pose_out, Tensor(b!) fit, Tensor(c!) n_obs, Tensor(d!) information, Tensor(e!) status, int stream) -> ()", refine_pose_views);
+  m.def("refine_pose_views_each(Tensor obs, Tensor views, Tensor pose, Tensor assignment, Tensor n_obj, Tensor model, float sigma_px, int iters, float damping, "
+        "Tensor(a!) pose_out, Tensor(b!) fit, Tensor(c!) n_obs, Tensor(d!) information, Tensor(e!) status, int stream) -> ()", refine_pose_views_each);
+  m.def("window_push(float[] camera, Tensor tab, Tensor assignment, Tensor status, Tensor meas_of, Tensor track_i, Tensor track_f, Tensor track_pose, Tensor T_WC, "
+        "int min_views, float max_speed, Tensor(a!) win_obs, Tensor(b!) win_views, Tensor(c!) win_i, Tensor(d!) n_views, Tensor(e!) start, int stream) -> ()", window_push);
   m.def("refine_assignments(float[] camera, Tensor tab, Tensor pose, Tensor assignment, Tensor n_obj, Tensor model, int[] type_count, float sigma_px, float sigma_z, int iters, "
         "float damping, Tensor(a!) pose_out, Tensor(b!) fit, Tensor(c!) information, Tensor(d!) status, Tensor(e!) assignment_out, Tensor(f!) hypothesis, Tensor(g!) cost, "
         "int stream) -> ()", refine_assignments);

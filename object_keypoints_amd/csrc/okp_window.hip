@@ -1,0 +1,147 @@
+// A sliding window of ticks' bearings per track slot (okp_window_push; contract in include/okp.h).  Every pose of the object stage is a
+// single-tick estimate; a camera that moves past a static object sees it from many viewpoints, and with the camera pose of every tick known
+// the key points' bearings over several ticks are a multi-view triangulation.  This launch keeps, per track slot, a ring of the last W
+// ticks' bearings (by MODEL ROW) and camera-from-world views; okp_refine_pose_views_each then refines the track pose against the ring.
+//
+//   okp_window_push_kernel   one wave per (stream, track slot).  Every lane takes the slot's few control words (id, owner, head, filled, the
+//                            velocity, the measurement and its status, the camera pose) - the same addresses for all 64 - and decides the
+//                            same thing.  Lane s loads table slot s, the lanes store their bearings into a 16-row LDS column in ascending
+//                            slot order (a later slot with the same model row wins), lanes 0 .. 13 form the views row.  Then one pass over
+//                            the ring: an element is the new column's, or NaN / 0 when the ring is emptied, or left alone - so no word is
+//                            written twice.  Rings are a few KiB: the launch is latency-bound.
+// fp64, no atomics, no host wait, contraction off; the same bits on every run and as tests/window_spec.py.
+#include "okp_pose_math.h"           // finite64
+
+#pragma clang fp contract(off)
+
+namespace {
+
+struct WindowParams {
+  const double* tab; const int32_t* assignment; const int32_t* status; const int32_t* meas_of; const int32_t* track_i; const double* track_f;
+  const double* track_pose; const double* T_WC;
+  double fx, fy, max_speed2;
+  int32_t max_obj, S, T, W, min_views;
+  double* win_obs; double* win_views; int32_t* win_i; int32_t* n_views; double* start;
+};
+
+__global__ __launch_bounds__(64) void okp_window_push_kernel(const WindowParams P) {
+  __shared__ double row[OKP_POSE_MAX_POINTS][2];                  // the new column: the bearing of every model row, or NaN
+  __shared__ double view[14];
+  const int lane = threadIdx.x;
+  const size_t bi = blockIdx.x;                                   // b * T + i
+  const size_t b = bi / P.T;
+  const int S = P.S, W = P.W;
+  const double nan = __builtin_nan("");
+  int32_t* wi = P.win_i + bi * 4;
+
+  // 1 - 3: whose ring this is, and whether it is emptied (wave-uniform: every lane reads the same words)
+  const int id = P.track_i[bi * 4];
+  int owner = wi[0], head = wi[1], filled = wi[2];
+  bool clear = false, push = false;
+  int o = -1;
+  if (id == 0) {
+    clear = true; owner = 0; head = 0; filled = 0;
+  } else {
+    if (id != owner || head < 0 || head >= W || filled < 0 || filled > W) { clear = true; owner = id; head = 0; filled = 0; }
+    const double* f = P.track_f + bi * 16;
+    const double vx = f[3], vy = f[4], vz = f[5];
+    if ((vx * vx + vy * vy) + vz * vz > P.max_speed2) { clear = true; head = 0; filled = 0; }
+    // 4: is there a column to push
+    o = P.meas_of[bi];
+    if (o >= 0 && o < P.max_obj && P.status[b * P.max_obj + o] == 0) {
+      push = true;
+#pragma unroll
+      for (int k = 0; k < 12; ++k) push = push && finite64(P.T_WC[b * 12 + k]);
+    }
+  }
+
+  if (push) {                                                     // (wave-uniform)
+    if (lane < OKP_POSE_MAX_POINTS) { row[lane][0] = nan; row[lane][1] = nan; }
+    int a = -1;
+    double u = nan, v = nan;
+    if (lane < S) {
+      const size_t slot = (b * P.max_obj + o) * S + lane;
+      const double* p = P.tab + slot * 4;
+      const double X = p[0], Y = p[1], Z = p[2], c = p[3];
+      const int as = P.assignment[slot];
+      if (as >= 0 && as < S && finite64(X) && finite64(Y) && finite64(Z) && finite64(c) && Z != 0.0) { a = as; u = X / Z; v = Y / Z; }
+    }
+    __syncthreads();
+    for (int s = 0; s < S; ++s) {                                 // ascending slots: a later slot with the same model row wins
+      if (lane == s && a >= 0) { row[a][0] = u; row[a][1] = v; }
+      __syncthreads();
+    }
+    if (lane < 14) {                                              // camera-from-world: [R^T | R^T (-t)], then fx, fy
+      const double* Tb = P.T_WC + b * 12;
+      double x = lane == 12 ? P.fx : P.fy;
+      if (lane < 12) {
+        const int i = lane >> 2, j = lane & 3;
+        if (j < 3) x = Tb[4 * j + i];
+        else {
+          const double d0 = -Tb[3], d1 = -Tb[7], d2 = -Tb[11];
+          x = (Tb[i] * d0 + Tb[4 + i] * d1) + Tb[8 + i] * d2;
+        }
+      }
+      view[lane] = x;
+    }
+    __syncthreads();
+  }
+
+  // the ring: every element is the new column's, or emptied, or kept - written at most once
+  double* obs = P.win_obs + bi * S * W * 2;
+  for (int e = lane; e < S * W; e += 64) {
+    const int r = e / W, c = e - r * W;
+    if (push && c == head) { obs[2 * e] = row[r][0]; obs[2 * e + 1] = row[r][1]; }
+    else if (clear) { obs[2 * e] = nan; obs[2 * e + 1] = nan; }
+  }
+  double* vw = P.win_views + bi * W * 14;
+  for (int e = lane; e < W * 14; e += 64) {
+    const int c = e / 14, k = e - c * 14;
+    if (push && c == head) vw[e] = view[k];
+    else if (clear) vw[e] = 0.0;
+  }
+  if (push) { head = head + 1 == W ? 0 : head + 1; filled = filled < W ? filled + 1 : W; }
+
+  if (lane == 0) { wi[0] = owner; wi[1] = head; wi[2] = filled; wi[3] = 0; P.n_views[bi] = filled; }
+  if (lane < 12) {                                                // the start of the refinement: the track pose bit for bit, or NaN
+    const unsigned long long bits = reinterpret_cast<const unsigned long long*>(P.track_pose)[bi * 12 + lane];
+    if (filled >= P.min_views) reinterpret_cast<unsigned long long*>(P.start)[bi * 12 + lane] = bits;
+    else P.start[bi * 12 + lane] = nan;
+  }
+}
+
+}  // namespace
+
+extern "C" int okp_window_push(const double* tab, const int32_t* assignment, const int32_t* status, const int32_t* meas_of, const int32_t* track_i,
+                               const double* track_f, const double* track_pose, const double* T_WC, const okp_camera* cam, int32_t B, int32_t max_obj,
+                               int32_t S, int32_t T, int32_t W, int32_t min_views, double max_speed, double* win_obs, double* win_views,
+                               int32_t* win_i, int32_t* n_views, double* start, void* stream) {
+  const char* fn = "okp_window_push";
+  if (B < 1) { okp_set_error("%s: B = %d; at least one stream", fn, B); return OKP_EINVAL; }
+  if (max_obj < 1) { okp_set_error("%s: max_obj = %d; a stream holds at least one object", fn, max_obj); return OKP_EINVAL; }
+  if (S < 1 || S > OKP_POSE_MAX_POINTS) { okp_set_error("%s: S = %d outside [1, %d] model points", fn, S, OKP_POSE_MAX_POINTS); return OKP_EINVAL; }
+  if (T < 1 || T > OKP_TRACK_MAX_TRACKS) { okp_set_error("%s: T = %d outside [1, %d] track slots", fn, T, OKP_TRACK_MAX_TRACKS); return OKP_EINVAL; }
+  if (W < 1 || W > OKP_REFINE_MAX_VIEWS) { okp_set_error("%s: W = %d outside [1, %d] ticks", fn, W, OKP_REFINE_MAX_VIEWS); return OKP_EINVAL; }
+  if (min_views < 1 || min_views > W) { okp_set_error("%s: min_views = %d outside [1, W = %d]", fn, min_views, W); return OKP_EINVAL; }
+  if (!(max_speed > 0.0)) { okp_set_error("%s: max_speed = %g must be positive (metres per second; +inf: never reset)", fn, max_speed); return OKP_EINVAL; }
+  if ((long long)B * T > 0x7fffffffll) { okp_set_error("%s: B * T = %lld track slots do not fit one launch", fn, (long long)B * T); return OKP_EINVAL; }
+  if (!cam) { okp_set_error("%s: null cam", fn); return OKP_EINVAL; }
+  if (!(cam->fx > 0.0 && cam->fx < __builtin_inf() && cam->fy > 0.0 && cam->fy < __builtin_inf())) {
+    okp_set_error("%s: cam fx = %g, fy = %g must be positive and finite", fn, (double)cam->fx, (double)cam->fy);
+    return OKP_EINVAL;
+  }
+  const struct { const void* ptr; const char* name; } required[] = {
+      {tab, "tab"}, {assignment, "assignment"}, {status, "status"}, {meas_of, "meas_of"}, {track_i, "track_i"}, {track_f, "track_f"},
+      {track_pose, "track_pose"}, {T_WC, "T_WC"}, {win_obs, "win_obs"}, {win_views, "win_views"}, {win_i, "win_i"}, {n_views, "n_views"},
+      {start, "start"}};
+  for (const auto& r : required)
+    if (!r.ptr) { okp_set_error("%s: null %s", fn, r.name); return OKP_EINVAL; }
+  WindowParams p = {};
+  p.tab = tab; p.assignment = assignment; p.status = status; p.meas_of = meas_of; p.track_i = track_i; p.track_f = track_f;
+  p.track_pose = track_pose; p.T_WC = T_WC;
+  p.fx = cam->fx; p.fy = cam->fy; p.max_speed2 = max_speed * max_speed;
+  p.max_obj = max_obj; p.S = S; p.T = T; p.W = W; p.min_views = min_views;
+  p.win_obs = win_obs; p.win_views = win_views; p.win_i = win_i; p.n_views = n_views; p.start = start;
+  hipLaunchKernelGGL(okp_window_push_kernel, dim3((unsigned)((size_t)B * T)), dim3(64), 0, (hipStream_t)stream, p);
+  return okp_check_hip(hipGetLastError(), "okp_window_push launch");
+}

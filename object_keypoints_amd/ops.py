@@ -1641,8 +1641,20 @@ def refine_pose_views(obs, views, pose, n_obj, model, cfg):
         (reprojection rmse in map pixels before and after; NaN where the status is not 0), "n_obs" [B,max_obj] int32 (bearings used),
         "information" [B,max_obj,36] float64 (H at the refined pose, 6 x 6 over (rotation, translation); NaN where the status is not 0),
         "status" [B,max_obj] int32 (0, REFINE_SKIPPED, REFINE_SINGULAR, REFINE_BEHIND or REFINE_REJECTED)}.  One launch, no host sync."""
-    if not isinstance(cfg, RefineConfig):
-        raise OkpError("cfg must be an ops.RefineConfig")
+    return _refine_views(False, obs, views, pose, n_obj, model, cfg)
+
+
+def refine_pose_views_each(obs, views, pose, n_obj, model, cfg):
+    """refine_pose_views with one views table per object (okp_refine_pose_views_each): views [B,max_obj,V,14] float64 (device), object (b, o)
+    reads its own V rows; everything else - the other arguments, the cost, the statuses, the returned dict - is refine_pose_views'.  cfg: a
+    RefineConfig or a WindowConfig (sigma_px, iters and damping are read).  A view none of whose entries is filled contributes nothing,
+    whatever its row holds.  With one table replicated per object the result has the bits of refine_pose_views.  One launch, no host sync."""
+    return _refine_views(True, obs, views, pose, n_obj, model, cfg)
+
+
+def _refine_views(each, obs, views, pose, n_obj, model, cfg):
+    if not isinstance(cfg, (RefineConfig, WindowConfig) if each else RefineConfig):
+        raise OkpError("cfg must be an ops.RefineConfig" + (" or an ops.WindowConfig" if each else ""))
     try:
         fitted, assignment = pose["pose"], pose["assignment"]
     except (TypeError, KeyError, IndexError):
@@ -1655,7 +1667,9 @@ def refine_pose_views(obs, views, pose, n_obj, model, cfg):
     dev = obs.device
     if b < 1 or max_obj < 1 or not 1 <= s <= POSE_MAX_POINTS or not 1 <= v <= REFINE_MAX_VIEWS:
         raise OkpError(f"obs [{b},{max_obj},{s},{v},2]: at least one frame and object, at most {POSE_MAX_POINTS} model points and {REFINE_MAX_VIEWS} views")
-    if views.dtype != torch.float64 or tuple(views.shape) != (v, 14) or views.device != dev:
+    if each and (views.dtype != torch.float64 or tuple(views.shape) != (b, max_obj, v, 14) or views.device != dev):
+        raise OkpError(f"views must be float64 [{b},{max_obj},{v},14] on the bearings' device: one table of {v} rows for each object of obs")
+    if not each and (views.dtype != torch.float64 or tuple(views.shape) != (v, 14) or views.device != dev):
         raise OkpError(f"views must be float64 [{v},14] on the bearings' device (rig_views): one row for each of the {v} views of obs")
     if fitted.dtype != torch.float64 or tuple(fitted.shape) != (b, max_obj, 12) or assignment.dtype != torch.int32 or tuple(assignment.shape) != (b, max_obj, s) or \
             fitted.device != dev or assignment.device != dev:
@@ -1669,9 +1683,122 @@ def refine_pose_views(obs, views, pose, n_obj, model, cfg):
     n_obs = torch.empty((b, max_obj), dtype=torch.int32, device=dev)
     information = torch.empty((b, max_obj, 36), dtype=torch.float64, device=dev)
     status = torch.empty((b, max_obj), dtype=torch.int32, device=dev)
-    _dispatch(_ops().refine_pose_views, obs.contiguous(), views.contiguous(), fitted.contiguous(), assignment.contiguous(), n_obj.reshape(b).contiguous(), model.contiguous(),
-              cfg.sigma_px, cfg.iters, cfg.damping, pose_out, fit, n_obs, information, status, stream_int())
+    B = _ops()
+    _dispatch(B.refine_pose_views_each if each else B.refine_pose_views, obs.contiguous(), views.contiguous(), fitted.contiguous(), assignment.contiguous(),
+              n_obj.reshape(b).contiguous(), model.contiguous(), cfg.sigma_px, cfg.iters, cfg.damping, pose_out, fit, n_obs, information, status, stream_int())
     return {"pose": pose_out, "fit": fit, "n_obs": n_obs, "information": information, "status": status}
+
+
+# ---- tracked objects refined against a sliding window of ticks' bearings (okp_window_push, okp_refine_pose_views_each; csrc/okp_window.hip) ----
+class WindowConfig:
+    """The parameters of the sliding window (okp_window_push, then okp_refine_pose_views_each on its state), validated here - an OkpError names
+    the field:
+        ticks      W, the ring's columns: the last W ticks in which the track was measured, 1 .. REFINE_MAX_VIEWS
+        min_views  the refinement runs from this many filled columns on, 1 .. ticks (fewer: the status is REFINE_SKIPPED)
+        max_speed  metres per second: a track whose filtered speed exceeds it has its ring emptied - the window assumes a STATIC object
+                   (positive; inf: never)
+        sigma_px, iters, damping   as in RefineConfig (there is no depth term)."""
+
+    def __init__(self, ticks, min_views=2, max_speed=float("inf"), sigma_px=0.25, iters=6, damping=1e-9):
+        def number(name, v):
+            if isinstance(v, bool):
+                raise OkpError(f"WindowConfig: {name} = {v!r} is not a number")
+            try:
+                return float(v)
+            except (TypeError, ValueError):
+                raise OkpError(f"WindowConfig: {name} = {v!r} is not a number") from None
+
+        def integer(name, v, lo, hi):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
+                raise OkpError(f"WindowConfig: {name} = {v!r}: an integer in [{lo}, {hi}]")
+            return int(v)
+
+        self.ticks = integer("ticks", ticks, 1, REFINE_MAX_VIEWS)
+        self.min_views = integer("min_views", min_views, 1, self.ticks)
+        self.max_speed, self.sigma_px, self.damping = number("max_speed", max_speed), number("sigma_px", sigma_px), number("damping", damping)
+        if not self.max_speed > 0.0:
+            raise OkpError(f"WindowConfig: max_speed = {max_speed!r} must be positive (metres per second; inf: never reset)")
+        if not (self.sigma_px > 0.0 and np.isfinite(self.sigma_px)):
+            raise OkpError(f"WindowConfig: sigma_px = {sigma_px!r} must be positive and finite (map pixels)")
+        if not (self.damping >= 0.0 and np.isfinite(self.damping)):
+            raise OkpError(f"WindowConfig: damping = {damping!r} must be finite and not negative")
+        self.iters = integer("iters", iters, 1, REFINE_MAX_ITERS)
+
+    def __repr__(self):
+        return (f"WindowConfig(ticks={self.ticks}, min_views={self.min_views}, max_speed={self.max_speed}, sigma_px={self.sigma_px}, iters={self.iters}, "
+                f"damping={self.damping})")
+
+
+def window_state(B, max_tracks, S, ticks, device):
+    """An empty window of B streams x max_tracks slots x S model rows x ticks columns: {"win_obs" [B,T,S,W,2] float64, all NaN, "win_views"
+    [B,T,W,14] float64 and "win_i" [B,T,4] int32 (owner id, head, filled, one spare), zeros} on `device` - window_push() steps it in place -
+    plus what the refinement of the window reads next to it on every call: "win_assignment" [B,T,S] int32, the identity (ring rows are model
+    rows), and "win_n" [B] int32 filled with T (every slot is an "object"; free ones arrive with a NaN pose)."""
+    B, T, S, W = int(B), int(max_tracks), int(S), int(ticks)
+    if B < 1 or not 1 <= T <= TRACK_MAX_TRACKS or not 1 <= S <= POSE_MAX_POINTS or not 1 <= W <= REFINE_MAX_VIEWS:
+        raise OkpError(f"window_state: B = {B} streams (at least 1) of max_tracks = {T} slots (1 .. {TRACK_MAX_TRACKS}), S = {S} model rows (1 .. {POSE_MAX_POINTS}), "
+                       f"ticks = {W} (1 .. {REFINE_MAX_VIEWS})")
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise OkpError("window_state: the window's state lives in device memory: the HIP path has no CPU fallback")
+    return {"win_obs": torch.full((B, T, S, W, 2), float("nan"), dtype=torch.float64, device=device),
+            "win_views": torch.zeros((B, T, W, 14), dtype=torch.float64, device=device), "win_i": torch.zeros((B, T, 4), dtype=torch.int32, device=device),
+            "win_assignment": torch.arange(S, dtype=torch.int32, device=device).repeat(B, T, 1).contiguous(),
+            "win_n": torch.full((B,), T, dtype=torch.int32, device=device)}
+
+
+def window_push(state, tab, assignment, status, track, T_WC, cam, cfg):
+    """One tick of the sliding window (okp_window_push; the ring, its resets and the push are specified in include/okp.h).  state:
+    window_state(...), stepped in place; tab [B,max_obj,S,4] float64: the CAMERA-frame table (object_points); assignment [B,max_obj,S] int32
+    (refine_assignments' where it ran, otherwise object_pose's) and status [B,max_obj] int32, the pose status the tracker was given; track:
+    the dict of this tick's track_objects() plus its state (its "meas_of", "track_i", "track_f" and "track_pose" are read: world frame);
+    T_WC [B,12] float64 (device), this tick's camera poses; cam: the okp_camera the table was lifted through (only fx and fy are read);
+    cfg: a WindowConfig
+    -> {"n_views" [B,T] int32 (filled columns), "start" [B,T,12] float64 (the track pose bit for bit from cfg.min_views columns on, otherwise
+        NaN)}.  One launch, no host sync."""
+    if not isinstance(cfg, WindowConfig):
+        raise OkpError("cfg must be an ops.WindowConfig")
+    if not isinstance(cam, _lib.okp_camera):
+        raise OkpError(f"cam must be an okp_camera (make_camera), not {type(cam).__name__}")
+    try:
+        meas_of, track_i, track_f, track_pose = track["meas_of"], track["track_i"], track["track_f"], track["track_pose"]
+    except (TypeError, KeyError, IndexError):
+        raise OkpError("track must be the dict of ops.track_objects with the tracker's state (its \"meas_of\", \"track_i\", \"track_f\" and \"track_pose\")") from None
+    try:
+        win_obs, win_views, win_i = state["win_obs"], state["win_views"], state["win_i"]
+    except (TypeError, KeyError, IndexError):
+        raise OkpError("state must be the dict of ops.window_state") from None
+    for name, t in (("tab", tab), ("assignment", assignment), ("status", status), ("meas_of", meas_of), ("track_i", track_i), ("track_f", track_f),
+                    ("track_pose", track_pose), ("T_WC", T_WC), ("win_obs", win_obs), ("win_views", win_views), ("win_i", win_i)):
+        require_cuda(t, name)
+    if tab.dtype != torch.float64 or tab.dim() != 4 or tab.shape[3] != 4:
+        raise OkpError("tab must be float64 [B,max_obj,S,4] (object_points)")
+    b, max_obj, s = (int(v) for v in tab.shape[:3])
+    dev = tab.device
+    if not 1 <= s <= POSE_MAX_POINTS:
+        raise OkpError(f"tab [{b},{max_obj},{s},4]: at most {POSE_MAX_POINTS} model points")
+    if assignment.dtype != torch.int32 or tuple(assignment.shape) != (b, max_obj, s) or status.dtype != torch.int32 or tuple(status.shape) != (b, max_obj) or \
+            assignment.device != dev or status.device != dev:
+        raise OkpError(f"assignment must be int32 [{b},{max_obj},{s}] and status int32 [{b},{max_obj}] on the table's device (object_pose)")
+    if track_i.dtype != torch.int32 or track_i.dim() != 3 or track_i.shape[0] != b or track_i.shape[2] != 4 or not 1 <= track_i.shape[1] <= TRACK_MAX_TRACKS:
+        raise OkpError(f"track_i must be int32 [{b},T,4] with T in [1, {TRACK_MAX_TRACKS}] (track_state)")
+    t = int(track_i.shape[1])
+    w = cfg.ticks
+    for name, x, dtype, shape in (("meas_of", meas_of, torch.int32, (b, t)), ("track_f", track_f, torch.float64, (b, t, 16)), ("track_pose", track_pose, torch.float64, (b, t, 12)),
+                                  ("T_WC", T_WC, torch.float64, (b, 12))):
+        if x.dtype != dtype or tuple(x.shape) != shape or x.device != dev:
+            raise OkpError(f"{name} must be a {dtype} tensor {list(shape)} on the table's device")
+    if track_i.device != dev:
+        raise OkpError(f"track_i is on {track_i.device}, the table on {dev}")
+    for name, x, dtype, shape in (("win_obs", win_obs, torch.float64, (b, t, s, w, 2)), ("win_views", win_views, torch.float64, (b, t, w, 14)),
+                                  ("win_i", win_i, torch.int32, (b, t, 4))):
+        if x.dtype != dtype or tuple(x.shape) != shape or x.device != dev or not x.is_contiguous():
+            raise OkpError(f"state[{name!r}] must be a contiguous {dtype} tensor {list(shape)} on the table's device: window_state({b}, {t}, {s}, cfg.ticks = {w}, device)")
+    n_views = torch.empty((b, t), dtype=torch.int32, device=dev)
+    start = torch.empty((b, t, 12), dtype=torch.float64, device=dev)
+    _dispatch(_ops().window_push, _cam_list(cam), tab.contiguous(), assignment.contiguous(), status.contiguous(), meas_of.contiguous(), track_i.contiguous(),
+              track_f.contiguous(), track_pose.contiguous(), T_WC.contiguous(), cfg.min_views, cfg.max_speed, win_obs, win_views, win_i, n_views, start, stream_int())
+    return {"n_views": n_views, "start": start}
 
 
 # ---- scoring labelled scenes (csrc/okp_targets.hip) ---------------------------------------------------------------------------------

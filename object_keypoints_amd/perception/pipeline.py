@@ -593,10 +593,14 @@ def _pose_fields(pose, n, refine=None):
     return fields
 
 
-def _track_fields(track, n):
+def _track_fields(track, n, window=None):
     """What the readers take of stream n of a tick's "track" dict: "track_pose" [T,12], "track_f" [T,16], "track_i" [T,4], "track_of" [max_obj],
-    "meas_of" [T] and, of a world-frame tick, "track_pose_C" [T,12] - the track poses back in the camera / rig frame."""
-    return {k: track[k][n] for k in ("track_pose", "track_f", "track_i", "track_of", "meas_of", "track_pose_C") if k in track}
+    "meas_of" [T] and, of a world-frame tick, "track_pose_C" [T,12] - the track poses back in the camera / rig frame; with the step's "window"
+    dict also "window_pose" and "window_pose_C" [T,12], "window_fit" [T,2], "window_n_views" [T], "window_information" [T,36], "window_status" [T]."""
+    fields = {k: track[k][n] for k in ("track_pose", "track_f", "track_i", "track_of", "meas_of", "track_pose_C") if k in track}
+    if window is not None:
+        fields.update({"window_" + k: window[k][n] for k in ("pose", "pose_C", "fit", "n_views", "information", "status")})
+    return fields
 
 
 def _host_poses(pose, n, refine=None):
@@ -604,9 +608,21 @@ def _host_poses(pose, n, refine=None):
     return _to_host(_pose_fields(pose, n, refine))
 
 
-def _host_tracks(track, n):
+def _host_tracks(track, n, window=None):
     """_track_fields on the host, in ONE device -> host copy."""
-    return _to_host(_track_fields(track, n))
+    return _to_host(_track_fields(track, n, window))
+
+
+def _window_entries(rec, slot):
+    """A track slot's windowed pose as the entries tracks() adds: 'T_WO_window' and 'T_CO_window' (4 x 4; None where 'window_status' is not 0 -
+    a short window, a free slot, a refused refinement - or, for 'T_CO_window', the camera pose is missing: the caller falls back to the
+    track pose), 'window_views' (filled ring columns), 'window_rmse' (reprojection rmse before, after; map pixels), 'window_information'
+    (6 x 6) and 'window_status'."""
+    ok = int(rec["window_status"][slot]) == 0
+    fit = rec["window_fit"][slot]
+    return {'T_WO_window': _track_transform(rec["window_pose"][slot]) if ok else None, 'T_CO_window': _track_transform(rec["window_pose_C"][slot]) if ok else None,
+            'window_views': int(rec["window_n_views"][slot]), 'window_rmse': (float(fit[0]), float(fit[1])),
+            'window_information': rec["window_information"][slot].reshape(6, 6).copy(), 'window_status': int(rec["window_status"][slot])}
 
 
 def _refine_entries(rec, o, T_CO):
@@ -667,12 +683,19 @@ def _track_entries(rec, o, key, min_hits, world_key=None):
     """Object o's track as the entries objects() / rig_objects() add: 'track_id' (None: the object went to no track - a position-only or
     dropped measurement), the filtered pose under `key`, 'velocity', 'track_hits', 'confirmed'."""
     slot = int(rec["track_of"][o])
+    windowed = "window_status" in rec        # the window segment: 'T_CO_window' and 'window_views' of the object's track
     if slot < 0:
         none = {key: None} if "track_pose_C" not in rec else {world_key: None, key: None}
+        if windowed:
+            none.update(T_CO_window=None, window_views=0)
         return dict({'track_id': None, 'velocity': None, 'track_hits': 0, 'confirmed': False}, **none)
     hits = int(rec["track_i"][slot, 1])
-    return dict({'track_id': int(rec["track_i"][slot, 0]), 'velocity': rec["track_f"][slot, 3:6].copy(), 'track_hits': hits, 'confirmed': hits >= min_hits},
-                **_track_poses(rec, slot, key, world_key))
+    entries = dict({'track_id': int(rec["track_i"][slot, 0]), 'velocity': rec["track_f"][slot, 3:6].copy(), 'track_hits': hits, 'confirmed': hits >= min_hits},
+                   **_track_poses(rec, slot, key, world_key))
+    if windowed:
+        w = _window_entries(rec, slot)
+        entries.update(T_CO_window=w['T_CO_window'], window_views=w['window_views'])
+    return entries
 
 
 def _track_list(rec, key, min_hits, world_key=None):
@@ -680,7 +703,7 @@ def _track_list(rec, key, min_hits, world_key=None):
     track_f, track_i, meas_of = rec["track_f"], rec["track_i"], rec["meas_of"]
     return [dict({'track_id': int(track_i[i, 0]), 'velocity': track_f[i, 3:6].copy(), 'hits': int(track_i[i, 1]),
                   'misses': int(track_i[i, 2]), 'age': int(track_i[i, 3]), 'confirmed': int(track_i[i, 1]) >= min_hits,
-                  'object': int(meas_of[i]) if meas_of[i] >= 0 else None}, **_track_poses(rec, i, key, world_key))
+                  'object': int(meas_of[i]) if meas_of[i] >= 0 else None}, **_track_poses(rec, i, key, world_key), **(_window_entries(rec, i) if "window_status" in rec else {}))
             for i in range(track_i.shape[0]) if track_i[i, 0] != 0]
 
 
@@ -722,6 +745,36 @@ class _Tracker:
                 t.zero_()
 
 
+class _Window:
+    """The device state of a pipeline's sliding window, one ops.window_state per (device, streams), created on first use and kept for the
+    pipeline's life like the tracker's: captured steps hold these very tensors, so reset() empties them in place."""
+
+    def __init__(self, cfg, max_tracks):
+        self.cfg, self.max_tracks, self.states = cfg, max_tracks, {}
+
+    def state(self, device, streams, rows):
+        st = self.states.get((device, streams))
+        if st is None:
+            st = self.states[(device, streams)] = ops.window_state(streams, self.max_tracks, rows, self.cfg.ticks, device)
+        return st
+
+    def step(self, tab, assignment, status, track, T_WC, cam, model):
+        """ops.window_push on the state of the table's device and streams, ops.refine_pose_views_each on that state from the pushed start, and
+        the refined poses back in the camera frame -> the entries of the step's "window" dict."""
+        st = self.state(tab.device, int(tab.shape[0]), int(tab.shape[2]))
+        pushed = ops.window_push(st, tab, assignment, status, track, T_WC, cam, self.cfg)
+        refined = ops.refine_pose_views_each(st["win_obs"], st["win_views"], {"pose": pushed["start"], "assignment": st["win_assignment"]}, st["win_n"], model, self.cfg)
+        pose_C = ops.change_frame(T_WC, poses=refined["pose"], inverse=True)["poses"]
+        return {"pose": refined["pose"], "fit": refined["fit"], "n_obs": refined["n_obs"], "n_views": pushed["n_views"], "information": refined["information"],
+                "status": refined["status"], "pose_C": pose_C, "win_obs": st["win_obs"], "win_views": st["win_views"], "win_i": st["win_i"]}
+
+    def reset(self):
+        for st in self.states.values():
+            st["win_obs"].fill_(float("nan"))
+            st["win_views"].zero_()
+            st["win_i"].zero_()
+
+
 def _check_frame_pose(pose, world_frame, streams, device, name, what):
     """The per-tick pose argument of both device pipelines against their world_frame switch: both or neither."""
     if not world_frame:
@@ -756,10 +809,16 @@ class _ObjectStage:
     poses and overflow word - -> "track": ops.track_objects' outputs plus the state tensors "track_f", "track_i", "next_id" (one state per
     device and number of streams, kept for the pipeline's life) and, in the world frame, "track_pose_C": the filtered poses back in the table's
     frame (okp_change_frame, inverse).  "track"["overflow"] is the word it was given | ops.TRACK_OVERFLOW.
+    Window (window = ops.WindowConfig(...), the camera pipeline only; needs the pose, the tracker and the world frame): okp_window_push keeps a
+    ring of the last `ticks` measured ticks per track slot - the CAMERA-frame table's bearings by model row (under the refined assignment where
+    resolve_assignment produced one) and each tick's camera-from-world pose -, okp_refine_pose_views_each refines every track's world pose
+    against its ring, and okp_change_frame (inverse) takes the result back into the camera frame -> "window": {"pose" (T_WO [B,T,12]), "fit",
+    "n_obs", "n_views", "information", "status", "pose_C", and the state "win_obs", "win_views", "win_i"} (one state per device and number of
+    streams, kept for the pipeline's life; reset_tracks() empties it too).  Static objects only: the ring does not model motion.
 
-    Every launch is captured with the step it ends.  Without any of the four no launch, key or value of the step differs."""
+    Every launch is captured with the step it ends.  Without any of the five no launch, key or value of the step differs."""
 
-    def __init__(self, type_count, points_3d, max_rmse, track, max_obj, what, world_frame, refine=None):
+    def __init__(self, type_count, points_3d, max_rmse, track, max_obj, what, world_frame, refine=None, window=None):
         self.type_count, self.world_frame = type_count, bool(world_frame)
         if points_3d is None and max_rmse is not None:
             raise OkpError("max_rmse without points_3d: the pose needs the object model")
@@ -781,12 +840,20 @@ class _ObjectStage:
             if refine.resolve_assignment:
                 ops.check_refine_hypotheses(type_count)
         self.refine = refine
+        if window is not None:
+            if not isinstance(window, ops.WindowConfig):
+                raise OkpError("window must be an ops.WindowConfig")
+            for missing, why in ((points_3d is None, "points_3d: the window refines the pose of the object model"), (track is None, "track: a window belongs to a track"),
+                                 (not world_frame, "world_frame=True: the ticks of a window share the world frame, through each tick's camera_pose")):
+                if missing:
+                    raise OkpError(f"window without {why}")
+        self.window = _Window(window, track.max_tracks) if window is not None else None
 
     def run(self, tab, n_obj, points, overflow, frame_pose, cam=None, rig=None):
         """The stage behind a step: tab = the object point table (None without a model), n_obj, points (what the world frame shows besides the
         objects) and overflow = the step's own; frame_pose: the checked per-step pose, or None; cam: the camera of a refined table; rig: what
         a refined rig tick observes with - {"table", "count", "xyc", "match", "fused", "views"}
-        -> the entries the step's dict gains, in order: "pose", "refine", "world", "track"."""
+        -> the entries the step's dict gains, in order: "pose", "refine", "world", "track", "window"."""
         out, fed = {}, None
         if self.model.host is not None:
             model = self.model(tab.device)
@@ -811,16 +878,22 @@ class _ObjectStage:
             out["track"] = self.tracker.step(fed["tab"], fed["pose"], fed["status"], n_obj, model, overflow)
             if frame_pose is not None:
                 out["track"]["track_pose_C"] = ops.change_frame(frame_pose, poses=out["track"]["track_pose"], inverse=True)["poses"]
+        if self.window is not None:
+            resolved = out.get("refine", {}).get("assignment")       # the refined assignment where resolve_assignment produced one
+            out["window"] = self.window.step(tab, resolved if resolved is not None else out["pose"]["assignment"], out["pose"]["status"], out["track"], frame_pose, cam, model)
         return out
 
     def reset_tracks(self):
         if self.tracker is None:
             raise OkpError("this pipeline was built without track")
         self.tracker.reset()
+        if self.window is not None:
+            self.window.reset()
 
-    def tracks(self, track, n, key):
-        """Every live track of stream n of a step's "track" dict, `key` naming its pose in the table's frame - ONE device -> host copy."""
-        return _track_list(_host_tracks(track, n), key, self.tracker.cfg.min_hits, 'T_WO_track')
+    def tracks(self, track, n, key, window=None):
+        """Every live track of stream n of a step's "track" dict, `key` naming its pose in the table's frame, with the entries of the step's
+        "window" dict where there is one - ONE device -> host copy."""
+        return _track_list(_host_tracks(track, n, window), key, self.tracker.cfg.min_hits, 'T_WO_track')
 
     def pin(self, step, static_out):
         """What a captured graph reads on every replay besides its inputs, kept on `step`: the object model - the very tensor the captured launch
@@ -830,6 +903,8 @@ class _ObjectStage:
             step._model = self.model(static_out["pose"]["tab"].device)
         if "track" in static_out:
             step._track_state = [static_out["track"][k] for k in ("track_f", "track_i", "next_id")]
+            if "window" in static_out:
+                step._window_state = [static_out["window"][k] for k in ("win_obs", "win_views", "win_i")]
             self.reset_tracks()
 
 
@@ -838,6 +913,7 @@ class _ObjectStagePipeline:
     world_frame = property(lambda self: self._stage.world_frame)
     max_rmse = property(lambda self: self._stage.max_rmse)
     refine = property(lambda self: self._stage.refine)
+    window = property(lambda self: self._stage.window.cfg if self._stage.window is not None else None)
     _tracker = property(lambda self: self._stage.tracker)
     _model_host = property(lambda self: self._stage.model.host)
     _models = property(lambda self: self._stage.model.on)
@@ -939,10 +1015,17 @@ class BatchedKeypointPipeline(_ObjectStagePipeline):
     track: batch index = stream - frame n of every step is the next tick of stream n.  objects() adds 'track_id' (None where the object went
     to no track), 'T_CO_track' (the filtered pose), 'velocity', 'track_hits' and 'confirmed'; tracks(out, n) lists every live track of stream
     n, coasting ones included; reset_tracks() empties the tracker.  The step's own "overflow" word is unchanged.
+    window = ops.WindowConfig(ticks, ...) (needs points_3d, track and world_frame=True; each is refused by name when missing): every track's
+    world pose refined against the bearings of its last `ticks` measured ticks, each seen from that tick's camera pose - a multi-view
+    triangulation that does not use the depth head, whose gain comes from the baseline the camera travels (a standing camera gains nothing in
+    depth).  tracks() adds 'T_WO_window', 'T_CO_window' (None where 'window_status' is not 0 - a short window, a refused refinement -: fall back
+    to the track pose), 'window_views', 'window_rmse', 'window_information' and 'window_status'; objects() adds 'T_CO_window' and
+    'window_views' of the object's track - still one device -> host copy each.  Static objects only, no robust loss, uniform weights, and the
+    error of camera_pose goes straight into the result.  StereoStreamPipeline has no window: 2 P cameras x ticks exceed the kernel's 64 views.
     """
 
     def __init__(self, net, keypoint_config, camera, prediction_size=(64, 64), capacity=DEFAULT_PEAK_CAPACITY,
-                 max_objects=16, max_per_type=4, points_3d=None, max_rmse=None, track=None, world_frame=False, refine=None):
+                 max_objects=16, max_per_type=4, points_3d=None, max_rmse=None, track=None, world_frame=False, refine=None, window=None):
         self.net = net
         self.max_objects = max_objects
         self.max_per_type = max_per_type
@@ -954,7 +1037,7 @@ class BatchedKeypointPipeline(_ObjectStagePipeline):
         self.cam = camera.okp()
         self.max_index = camera.image_size.astype(int) - 1
         cfg = keypoint_config['keypoint_config']
-        self._stage = _ObjectStage(cfg, points_3d, max_rmse, track, max_objects, "max_objects", world_frame, refine)
+        self._stage = _ObjectStage(cfg, points_3d, max_rmse, track, max_objects, "max_objects", world_frame, refine, window)
         if points_3d is not None and max(cfg) > max_per_type:
             raise OkpError(f"a keypoint type has {max(cfg)} instances, above max_per_type = {max_per_type}")
 
@@ -964,7 +1047,7 @@ class BatchedKeypointPipeline(_ObjectStagePipeline):
         (the index into objects(out, n) that updated or founded it in this step, or None)} - ONE device -> host copy."""
         if "track" not in out:
             raise OkpError("tracks reads the step of a pipeline built with track")
-        return self._stage.tracks(out["track"], n, 'T_CO_track')
+        return self._stage.tracks(out["track"], n, 'T_CO_track', out.get("window"))
 
     def forward_device(self, frames, camera_pose=None):
         """Split-product configurations: the network's fp16-range flag is not read here (no host sync in the batch loop) but folded into
@@ -1048,7 +1131,7 @@ class BatchedKeypointPipeline(_ObjectStagePipeline):
                 lifted[(o, i)] = world[at:at + cfg[i]]
                 at += cfg[i]
         poses = _host_poses(out["pose"], n, out.get("refine")) if "pose" in out else None
-        tracked = _host_tracks(out["track"], n) if "track" in out else None
+        tracked = _host_tracks(out["track"], n, out.get("window")) if "track" in out else None
         in_world = "world" in out
         if in_world:                                               # 'p_W' parallel to 'p_C': the device's world points, row for row
             T_WC = out["world"]["T"][n].cpu().numpy().reshape(3, 4)

@@ -1,0 +1,401 @@
+"""CPU-side checks of the sliding window (okp_window_push, okp_refine_pose_views_each; ops.WindowConfig / window_state / window_push /
+refine_pose_views_each; the window argument of BatchedKeypointPipeline): the names exist in the header, the ctypes table and the op registry;
+every refusal is raised by the C entry point, with its argument named, before any device pointer is touched; WindowConfig and the pipeline
+name what they refuse; the step launches the segment after the tracker, on the right tensors (recording stubs, as
+tests/test_object_stage_wiring.py); the sequences of the GPU test (tests/window_cases.py) contain every event the contract names; its
+refinement cases are away from every decision; and the accuracy statement of the stage under a moving camera.  No GPU needed."""
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+import refine_views_spec as views_spec
+import test_object_stage_wiring as wiring
+import window_cases as wc
+import window_spec as spec
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+FAKE = 64                # a non-NULL "device" address the host never dereferences: the checks that follow must stop at the NULL buffers
+PUSH_POINTERS = ("tab", "assignment", "status", "meas_of", "track_i", "track_f", "track_pose", "T_WC", "win_obs", "win_views", "win_i", "n_views", "start")
+VIEW_POINTERS = ("obs", "views", "pose", "assignment", "n_obj", "model", "pose_out", "fit", "n_obs", "information", "status")
+SEQUENCES = wc.sequences()
+EACH = wc.each_cases()
+
+
+def _lib():
+    from object_keypoints_amd import _lib, build
+    build.build()
+    return _lib
+
+
+def test_header_ctypes_table_and_op_registry_agree_on_the_names():
+    lib = _lib()
+    text = open(os.path.join(REPO, "include", "okp.h")).read()
+    declared = set(re.findall(r"\b(okp_[a-z0-9_]+)\s*\(", re.sub(r"/\*.*?\*/", "", text, flags=re.S)))
+    additions = text[text.index("additions at 7"):text.index("*/", text.index("additions at 7"))]
+    T = lib.torch_ops()
+    assert T is not None
+    from object_keypoints_amd import _ctypes_ops, ops
+    for name in ("okp_window_push", "okp_refine_pose_views_each"):
+        assert name in declared and name in {n for n, _, _ in lib.SIGNATURES} and hasattr(lib.lib(), name) and name in additions
+        assert callable(getattr(_ctypes_ops, name[4:])) and callable(getattr(ops, name[4:]))
+    assert lib.lib().okp_abi_version() == 7 and re.search(r"#define OKP_ABI_VERSION 7\b", text)
+    schema = str(T.refine_pose_views_each.default._schema)
+    assert schema.startswith("okp::refine_pose_views_each(")
+    for name, mark in zip(("pose_out", "fit", "n_obs", "information", "status"), "abcde"):
+        assert f"Tensor({mark}!) {name}" in schema, (name, schema)
+    schema = str(T.window_push.default._schema)
+    for name, mark in zip(("win_obs", "win_views", "win_i", "n_views", "start"), "abcde"):
+        assert f"Tensor({mark}!) {name}" in schema, (name, schema)
+    assert (spec.MAX_VIEWS, spec.MAX_TRACKS, spec.MAX_POINTS) == (ops.REFINE_MAX_VIEWS, ops.TRACK_MAX_TRACKS, ops.POSE_MAX_POINTS)
+    source = open(os.path.join(REPO, "object_keypoints_amd", "csrc", "okp_window.hip")).read()
+    assert "#pragma clang fp contract(off)" in source and "atomic" not in re.sub(r"//.*", "", source)
+    flat = " ".join(text.replace("\n *", " ").split())
+    for word in ("WHATEVER its row holds", "Static objects only", "No robust loss", "uniform weights", "camera poses goes straight into the result", "BASELINE"):
+        assert word in flat, word
+
+
+def _push_call(L, B=2, max_obj=4, S=4, T=8, W=16, min_views=2, max_speed=0.5, fx=62.0, fy=62.0, null=None, cam=True):
+    from object_keypoints_amd import _lib as lib
+    import ctypes
+    p = {name: (None if name == null else FAKE * (1 + i) * 4096) for i, name in enumerate(PUSH_POINTERS)}
+    camera = ctypes.byref(lib.okp_camera(fx, fy, 32.0, 32.0, (0.0, 0.0, 0.0, 0.0), 0)) if cam else None
+    return L.okp_window_push(p["tab"], p["assignment"], p["status"], p["meas_of"], p["track_i"], p["track_f"], p["track_pose"], p["T_WC"], camera, B, max_obj, S, T, W,
+                             min_views, max_speed, p["win_obs"], p["win_views"], p["win_i"], p["n_views"], p["start"], None)
+
+
+def test_window_push_checks_its_arguments_before_any_device_call():
+    """Every call here carries a null required pointer, so none can reach the launch: a scalar is refused under its own name, and with good
+    scalars the first null pointer is."""
+    L = _lib().lib()
+    err = L.okp_last_error
+    nan, inf = float("nan"), float("inf")
+    bad = lambda **kw: _push_call(L, null="start", **kw)
+    assert bad() == -1 and b"null start" in err()
+    assert bad(B=1, max_obj=1, S=1, T=1, W=1, min_views=1, max_speed=inf) == -1 and b"null start" in err()           # the edges are allowed
+    assert bad(S=16, T=64, W=64, min_views=64, max_speed=1e-300) == -1 and b"null start" in err()
+    for v in (0, 65, -1):
+        assert bad(W=v) == -1 and f"W = {v} ".encode() in err()
+        assert bad(T=v) == -1 and f"T = {v} ".encode() in err()
+    for v in (0, 17, -3):
+        assert bad(S=v) == -1 and f"S = {v} ".encode() in err()
+    for v in (0, -1):
+        assert bad(B=v) == -1 and f"B = {v}".encode() in err()
+        assert bad(max_obj=v) == -1 and f"max_obj = {v}".encode() in err()
+    for v in (0, 17, -1):
+        assert bad(min_views=v) == -1 and f"min_views = {v} ".encode() in err()
+    for v in (0.0, -0.5, nan, -inf):
+        assert bad(max_speed=v) == -1 and b"max_speed = " in err()
+    for v in (0.0, -62.0, nan, inf):
+        assert bad(fx=v) == -1 and b"fx = " in err()
+        assert bad(fy=v) == -1 and b"fy = " in err()
+    assert bad(cam=False) == -1 and b"null cam" in err()
+    for name in PUSH_POINTERS:
+        assert _push_call(L, null=name) == -1 and f"null {name}".encode() in err() and b"okp_window_push" in err()
+
+
+def _each_call(L, sigma_px=0.25, iters=6, damping=1e-9, B=2, max_obj=4, S=4, V=8, null=None, overlap=False):
+    p = {name: (None if name == null else FAKE * (1 + i) * 4096) for i, name in enumerate(VIEW_POINTERS)}
+    if overlap:
+        p["pose_out"] = p["pose"] + 8
+    return L.okp_refine_pose_views_each(p["obs"], p["views"], p["pose"], p["assignment"], p["n_obj"], p["model"], sigma_px, iters, damping, B, max_obj, S, V,
+                                        p["pose_out"], p["fit"], p["n_obs"], p["information"], p["status"], None)
+
+
+def test_refine_pose_views_each_refuses_what_refine_pose_views_refuses():
+    L = _lib().lib()
+    err = L.okp_last_error
+    nan, inf = float("nan"), float("inf")
+    bad = lambda **kw: _each_call(L, null="status", **kw)
+    assert bad() == -1 and b"null status" in err() and b"okp_refine_pose_views_each" in err()
+    assert bad(iters=1, damping=0.0, S=16, V=64, B=1, max_obj=1) == -1 and b"null status" in err()
+    for v in (0, -1):
+        assert bad(B=v) == -1 and f"B = {v}".encode() in err()
+        assert bad(max_obj=v) == -1 and f"max_obj = {v}".encode() in err()
+    for v in (0, 17, -3):
+        assert bad(S=v) == -1 and f"S = {v} ".encode() in err()
+        assert bad(iters=v) == -1 and f"iters = {v} ".encode() in err()
+    for v in (0, 65, -2):
+        assert bad(V=v) == -1 and f"V = {v} ".encode() in err()
+    for v in (0.0, -0.25, nan, inf):
+        assert bad(sigma_px=v) == -1 and b"sigma_px = " in err()
+    for v in (-1e-12, nan, inf):
+        assert bad(damping=v) == -1 and b"damping = " in err()
+    for name in VIEW_POINTERS:
+        assert _each_call(L, null=name) == -1 and f"null {name}".encode() in err() and b"okp_refine_pose_views_each" in err()
+    assert _each_call(L, overlap=True) == -1 and b"pose_out overlaps pose" in err()
+
+
+# ---- ops and the pipeline -----------------------------------------------------------------------------------------------------------------------
+
+def test_window_config_names_what_it_refuses():
+    from object_keypoints_amd import ops
+    cfg = ops.WindowConfig(16)
+    assert (cfg.ticks, cfg.min_views, cfg.max_speed, cfg.sigma_px, cfg.iters, cfg.damping) == (16, 2, float("inf"), 0.25, 6, 1e-9)
+    assert repr(ops.WindowConfig(8, 3, 0.2)) == "WindowConfig(ticks=8, min_views=3, max_speed=0.2, sigma_px=0.25, iters=6, damping=1e-09)"
+    assert ops.WindowConfig(1, min_views=1).ticks == 1 and ops.WindowConfig(64, min_views=64, iters=16).min_views == 64
+    for kw, field in ((dict(ticks=0), "ticks"), (dict(ticks=65), "ticks"), (dict(ticks=8.0), "ticks"), (dict(ticks=True), "ticks"), (dict(ticks=8, min_views=0), "min_views"),
+                      (dict(ticks=8, min_views=9), "min_views"), (dict(ticks=8, max_speed=0.0), "max_speed"), (dict(ticks=8, max_speed=float("nan")), "max_speed"),
+                      (dict(ticks=8, max_speed="fast"), "max_speed"), (dict(ticks=8, sigma_px=0.0), "sigma_px"), (dict(ticks=8, sigma_px=float("inf")), "sigma_px"),
+                      (dict(ticks=8, iters=0), "iters"), (dict(ticks=8, iters=17), "iters"), (dict(ticks=8, damping=-1.0), "damping"), (dict(ticks=8, damping=float("nan")), "damping")):
+        with pytest.raises(ops.OkpError, match=f"WindowConfig: {field} = "):
+            ops.WindowConfig(**kw)
+
+
+def test_the_wrappers_name_what_they_refuse():
+    from object_keypoints_amd import ops
+    cfg = ops.WindowConfig(4)
+    with pytest.raises(ops.OkpError, match="window_state: the window's state lives in device memory"):
+        ops.window_state(1, 2, 3, 4, "cpu")
+    for args in ((0, 2, 3, 4), (1, 65, 3, 4), (1, 2, 17, 4), (1, 2, 3, 65)):
+        with pytest.raises(ops.OkpError, match="window_state: B = "):
+            ops.window_state(*args, "cuda")
+    cam = ops.make_camera(np.array([[62.0, 0, 32], [0, 62.0, 32], [0, 0, 1]]), np.zeros(4))
+    tab, assignment, status = torch.zeros(1, 2, 3, 4, dtype=torch.float64), torch.zeros(1, 2, 3, dtype=torch.int32), torch.zeros(1, 2, dtype=torch.int32)
+    with pytest.raises(ops.OkpError, match="ops.WindowConfig"):
+        ops.window_push({}, tab, assignment, status, {}, torch.zeros(1, 12, dtype=torch.float64), cam, ops.RefineConfig())
+    with pytest.raises(ops.OkpError, match="okp_camera"):
+        ops.window_push({}, tab, assignment, status, {}, torch.zeros(1, 12, dtype=torch.float64), [62.0, 62.0], cfg)
+    with pytest.raises(ops.OkpError, match="track must be the dict of ops.track_objects"):
+        ops.window_push({}, tab, assignment, status, {}, torch.zeros(1, 12, dtype=torch.float64), cam, cfg)
+    track = {"meas_of": torch.zeros(1, 5, dtype=torch.int32), "track_i": torch.zeros(1, 5, 4, dtype=torch.int32), "track_f": torch.zeros(1, 5, 16, dtype=torch.float64),
+             "track_pose": torch.zeros(1, 5, 12, dtype=torch.float64)}
+    with pytest.raises(ops.OkpError, match="state must be the dict of ops.window_state"):
+        ops.window_push({}, tab, assignment, status, track, torch.zeros(1, 12, dtype=torch.float64), cam, cfg)
+    state = {"win_obs": torch.zeros(1, 5, 3, 4, 2, dtype=torch.float64), "win_views": torch.zeros(1, 5, 4, 14, dtype=torch.float64), "win_i": torch.zeros(1, 5, 4, dtype=torch.int32)}
+    with pytest.raises(ops.OkpError, match="tab must be a device tensor"):
+        ops.window_push(state, tab, assignment, status, track, torch.zeros(1, 12, dtype=torch.float64), cam, cfg)
+    obs = torch.zeros(1, 2, 4, 6, 2, dtype=torch.float64)
+    pose = {"pose": torch.zeros(1, 2, 12, dtype=torch.float64), "assignment": torch.zeros(1, 2, 4, dtype=torch.int32)}
+    with pytest.raises(ops.OkpError, match="RefineConfig or an ops.WindowConfig"):
+        ops.refine_pose_views_each(obs, torch.zeros(1, 2, 6, 14, dtype=torch.float64), pose, torch.zeros(1, dtype=torch.int32), torch.zeros(4, 3, dtype=torch.float64), dict(iters=6))
+    with pytest.raises(ops.OkpError, match="cfg must be an ops.RefineConfig$"):                  # the shared-table entry point keeps its own words
+        ops.refine_pose_views(obs, torch.zeros(6, 14, dtype=torch.float64), pose, torch.zeros(1, dtype=torch.int32), torch.zeros(4, 3, dtype=torch.float64), cfg)
+    with pytest.raises(ops.OkpError, match="obs must be a device tensor"):
+        ops.refine_pose_views_each(obs, torch.zeros(1, 2, 6, 14, dtype=torch.float64), pose, torch.zeros(1, dtype=torch.int32), torch.zeros(4, 3, dtype=torch.float64), cfg)
+    T = _lib().torch_ops()
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        T.refine_pose_views_each(obs, torch.zeros(1, 2, 6, 14, dtype=torch.float64), pose["pose"], pose["assignment"], torch.zeros(1, dtype=torch.int32),
+                                 torch.zeros(4, 3, dtype=torch.float64), 0.25, 6, 1e-9, torch.zeros(1, 2, 12, dtype=torch.float64), torch.zeros(1, 2, 2, dtype=torch.float64),
+                                 torch.zeros(1, 2, dtype=torch.int32), torch.zeros(1, 2, 36, dtype=torch.float64), torch.zeros(1, 2, dtype=torch.int32), 0)
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        T.window_push([62.0, 62.0, 32.0, 32.0, 0.0, 0.0, 0.0, 0.0, 0.0], tab, assignment, status, track["meas_of"], track["track_i"], track["track_f"], track["track_pose"],
+                      torch.zeros(1, 12, dtype=torch.float64), 2, 0.5, state["win_obs"], state["win_views"], state["win_i"], torch.zeros(1, 5, dtype=torch.int32),
+                      torch.zeros(1, 5, 12, dtype=torch.float64), 0)
+
+
+def _pipeline(**kw):
+    from object_keypoints_amd import ops
+    from object_keypoints_amd.perception import pipeline as pp
+    from object_keypoints_amd.perception.utils import camera_utils as cu
+    cam = cu.FisheyeCamera(np.array([[300.0, 0, 32], [0, 300.0, 32], [0, 0, 1]]), np.zeros(4), np.array([64, 64]))
+    full = dict(points_3d=wiring.MODEL, track=ops.TrackConfig(0.5, 0.1, max_tracks=wiring.TRACKS), world_frame=True, window=ops.WindowConfig(4))
+    full.update(kw)
+    return pp.BatchedKeypointPipeline(None, {"keypoint_config": wiring.CFG}, cam, capacity=wiring.CAP, max_objects=wiring.MAX_OBJ, max_per_type=wiring.MAX_SEL, **full)
+
+
+def test_the_pipeline_refuses_a_window_without_what_it_rests_on():
+    import inspect
+    from object_keypoints_amd import ops
+    from object_keypoints_amd.perception import pipeline as pp
+    with pytest.raises(ops.OkpError, match="window without points_3d"):
+        _pipeline(points_3d=None, track=None)
+    with pytest.raises(ops.OkpError, match="window without track"):
+        _pipeline(track=None)
+    with pytest.raises(ops.OkpError, match="window without world_frame=True"):
+        _pipeline(world_frame=False)
+    with pytest.raises(ops.OkpError, match="ops.WindowConfig"):
+        _pipeline(window=dict(ticks=4))
+    pipe = _pipeline()
+    assert pipe.window.ticks == 4 and _pipeline(window=None).window is None
+    assert "window" not in inspect.signature(pp.StereoStreamPipeline.__init__).parameters       # a rig's 2 P W views exceed the kernel's 64: not offered
+
+
+# ---- the wiring, against recording stubs ----------------------------------------------------------------------------------------------------------
+
+class Recorder(wiring.Recorder):
+    def __init__(self, monkeypatch):
+        super().__init__(monkeypatch)
+        from object_keypoints_amd import ops
+        for name in ("window_state", "window_push", "refine_pose_views_each", "refine_assignments"):
+            monkeypatch.setattr(ops, name, getattr(self, name))
+
+    def label(self, v):
+        from object_keypoints_amd import ops
+        return "WindowConfig" if isinstance(v, ops.WindowConfig) else super().label(v)
+
+    def window_state(self, B, max_tracks, S, ticks, device):
+        self.call("window_state", B=B, max_tracks=max_tracks, S=S, ticks=ticks)
+        return {"win_obs": self.new("win_obs", (B, max_tracks, S, ticks, 2)), "win_views": self.new("win_views", (B, max_tracks, ticks, 14)),
+                "win_i": self.new("win_i", (B, max_tracks, 4), torch.int32), "win_assignment": self.new("win_assignment", (B, max_tracks, S), torch.int32),
+                "win_n": self.new("win_n", (B,), torch.int32)}
+
+    def window_push(self, state, tab, assignment, status, track, T_WC, cam, cfg):
+        self.call("window_push", state=list(state), win_obs=state["win_obs"], tab=tab, assignment=assignment, status=status, meas_of=track["meas_of"], track_i=track["track_i"],
+                  track_f=track["track_f"], track_pose=track["track_pose"], T_WC=T_WC, cam=cam, cfg=cfg)
+        b, t = track["meas_of"].shape
+        return {"n_views": self.new("window.n_views", (b, t), torch.int32), "start": self.new("window.start", (b, t, 12))}
+
+    def refine_pose_views_each(self, obs, views, pose, n_obj, model, cfg):
+        self.call("refine_pose_views_each", obs=obs, views=views, pose=pose["pose"], assignment=pose["assignment"], n_obj=n_obj, model=model, cfg=cfg)
+        b, t = obs.shape[:2]
+        return {"pose": self.new("window.pose", (b, t, 12)), "fit": self.new("window.fit", (b, t, 2)), "n_obs": self.new("window.n_obs", (b, t), torch.int32),
+                "information": self.new("window.information", (b, t, 36)), "status": self.new("window.status", (b, t), torch.int32)}
+
+    def refine_assignments(self, tab, pose, n_obj, model, type_count, cam, cfg):
+        out = self.refine_pose(tab, pose, n_obj, model, cam, cfg)
+        self.trace[-1] = self.trace[-1].replace("refine_pose(", "refine_assignments(")
+        b, max_obj, s = tab.shape[:3]
+        return dict(out, assignment=self.new("refine.assignment", (b, max_obj, s), torch.int32), hypothesis=self.new("refine.hypothesis", (b, max_obj, 2), torch.int32),
+                    cost=self.new("refine.cost", (b, max_obj, 2)))
+
+
+WINDOW_TAIL = [
+    "window_state(B=2, max_tracks=7, S=5, ticks=4)",
+    "window_push(state=['win_obs', 'win_views', 'win_i', 'win_assignment', 'win_n'], win_obs=win_obs, tab=tab, assignment={assignment}, status=pose.status, meas_of=meas_of, "
+    "track_i=track_i, track_f=track_f, track_pose=track_pose, T_WC=camera_pose, cam=cam, cfg=WindowConfig)",
+    "refine_pose_views_each(obs=win_obs, views=win_views, pose=window.start, assignment=win_assignment, n_obj=win_n, model=model, cfg=WindowConfig)",
+    "change_frame(T=camera_pose, points=None, poses=window.pose, inverse=True, overflow=None)",
+]
+
+
+@pytest.mark.parametrize("refine", (None, "refine", "resolve"))
+def test_the_step_ends_with_the_window_segment_on_the_right_tensors(monkeypatch, refine):
+    from object_keypoints_amd import ops
+    rec = Recorder(monkeypatch)
+    c = dict(pose=1, refine=1 if refine else 0, track=1, world=1)
+    cfg = {None: None, "refine": ops.RefineConfig(), "resolve": ops.RefineConfig(resolve_assignment=True)}[refine]
+    pipe = _pipeline(max_rmse=0.25, refine=cfg)
+    off = _pipeline(max_rmse=0.25, refine=cfg, window=None)
+    rec.name("model", pipe._model_host)
+    rec.name("model", off._model_host)
+    maps = [rec.new("heat", (wiring.N, 1 + len(wiring.CFG), wiring.HW, wiring.HW), torch.float32), rec.new("depth", (wiring.N, 1 + len(wiring.CFG), wiring.HW, wiring.HW), torch.float32),
+            rec.new("centers", (wiring.N, len(wiring.CFG), 2, wiring.HW, wiring.HW), torch.float32)]
+    flag, camera_pose = rec.new("range_flag", (1,), torch.int32), rec.new("camera_pose", (wiring.N, 12))
+    # with the segment off: the trace and the keys of tests/test_object_stage_wiring.py
+    plain = off.postprocess_device(*maps, range_flag=flag, camera_pose=camera_pose)
+    base = wiring.BATCHED_PLAIN + wiring.BATCHED_POSE + ([line.replace("refine_pose(", "refine_assignments(" if refine == "resolve" else "refine_pose(") for line in wiring.BATCHED_REFINE] if refine else []) \
+        + wiring.stage_tail(c, "camera_pose", "points", "n_obj", "overflow", wiring.N)
+    assert rec.trace == base, "\n" + "\n".join(rec.trace)
+    assert list(plain)[-len(wiring.stage_keys(c)):] == wiring.stage_keys(c) and "window" not in plain
+    del rec.trace[:]
+    out = pipe.postprocess_device(*maps, range_flag=flag, camera_pose=camera_pose)
+    tail = [line.format(assignment="refine.assignment" if refine == "resolve" else "pose.assignment") for line in WINDOW_TAIL]
+    assert rec.trace == base + tail, "\n" + "\n".join(rec.trace)
+    assert list(out) == list(plain) + ["window"]
+    w = out["window"]
+    assert [(k, rec.label(v)) for k, v in w.items()] == [("pose", "window.pose"), ("fit", "window.fit"), ("n_obs", "window.n_obs"), ("n_views", "window.n_views"),
+                                                        ("information", "window.information"), ("status", "window.status"), ("pose_C", "local(window.pose)"),
+                                                        ("win_obs", "win_obs"), ("win_views", "win_views"), ("win_i", "win_i")]
+    if refine != "resolve":                                           # (the helper knows refine_pose's four keys)
+        wiring.check_stage_values(rec, c, out, camera_pose, "points")
+    # the second step finds the window's state where the first left it
+    del rec.trace[:]
+    again = pipe.postprocess_device(*maps, range_flag=flag, camera_pose=camera_pose)
+    assert rec.trace == [line for line in base + tail if not line.startswith(("track_state(", "window_state("))]
+    assert all(again["window"][k] is w[k] for k in ("win_obs", "win_views", "win_i"))
+    # reset_tracks() empties the windows too, in place
+    w["win_obs"].zero_()
+    w["win_views"].fill_(1.0)
+    w["win_i"].fill_(3)
+    pipe.reset_tracks()
+    assert torch.isnan(w["win_obs"]).all() and not w["win_views"].any() and not w["win_i"].any()
+
+
+# ---- the conditions of the GPU cases --------------------------------------------------------------------------------------------------------------
+
+def test_the_sequences_contain_every_event_the_contract_names():
+    assert [s["name"] for s in SEQUENCES] == ["b1_t1_s3_w1", "w2_five_pushes", "b3_t64_s16_w64"]
+    assert [s["shape"] for s in SEQUENCES] == [(1, 1, 3, 1, 1), (2, 3, 4, 2, 3), (3, 64, 16, 64, 16)] and len(SEQUENCES[1]["ticks"]) == 5
+    seen = {}
+    for seq in SEQUENCES:
+        events = set()
+        snaps = wc.run_spec(seq, events)
+        seen[seq["name"]] = events
+        for state, out in snaps:
+            halves = np.isnan(state["win_obs"])
+            assert np.array_equal(halves[..., 0], halves[..., 1]) and not np.isinf(state["win_obs"]).any()
+            filled = state["win_i"][..., 2]
+            assert np.array_equal(out["n_views"], filled) and (filled >= 0).all() and (filled <= seq["shape"][3]).all()
+            assert np.array_equal(np.isfinite(out["start"]).all(axis=2), (filled >= seq["min_views"]) & (state["win_i"][..., 0] != 0))
+            assert (np.count_nonzero(state["win_views"][..., 12], axis=2) == filled).all()           # a filled column has its focal length, an empty one is zero
+    print({k: sorted(v) for k, v in seen.items()})
+    want = {"freed", "refounded", "new_owner", "meas_none", "meas_above", "bad_status", "nan_T", "unassigned", "z0", "speed_reset", "short", "started", "same_row_twice"}
+    assert want <= seen["b3_t64_s16_w64"] and "wrapped" in seen["w2_five_pushes"] and "wrapped" in seen["b1_t1_s3_w1"]
+    assert {"meas_none", "started", "speed_reset"} <= seen["w2_five_pushes"]
+    steady = [int(state["win_i"][1, 2, 1]) for state, _ in wc.run_spec(SEQUENCES[1])]
+    assert steady == [1, 0, 1, 0, 1], steady                                                     # five pushes into a ring of two columns
+
+
+@pytest.mark.parametrize("case", EACH, ids=[c["name"] for c in EACH])
+def test_the_refinement_cases_are_away_from_every_decision(case):
+    diags = {}
+    out = spec.refine_pose_views_each(case["obs"], case["views"], case["pose"], case["assignment"], case["n_obj"], case["model"], diags=diags, **case["params"])
+    compared = 0
+    for (b, o), d in diags.items():
+        status = int(out["status"][b, o])
+        assert out["n_obs"][b, o] == d["n_obs"]
+        if status == views_spec.SKIPPED:
+            assert "pivot" not in d and (d["rows"] < 3 or np.isnan(case["pose"][b, o]).all())
+            continue
+        assert status == 0 and d["rows"] >= 3
+        assert d["pivot"] > 1e-6 and d["min_qz"] >= 1e-3
+        slack = views_spec.SLACK * d["n_obs"]
+        assert abs(d["J_final"] - d["J_initial"] - slack) > 1e-6 * (d["J_initial"] + slack), (b, o, d)
+        assert d["cond"] <= 1e8, (b, o, d["cond"])                    # the premise of the 1e-9 bar of tests/test_gpu_window.py
+        compared += 1
+    assert compared >= 1
+    ok = out["status"] == 0
+    assert (out["fit"][..., 1][ok] <= out["fit"][..., 0][ok]).all()
+
+
+def test_the_refinement_cases_cover_the_shapes_the_kernel_can_go_wrong_at():
+    by = {c["name"]: c for c in EACH}
+    assert [by[n]["obs"].shape[2:4] for n in ("s4_v2", "s5_v6", "s5_v14", "s16_v64")] == [(4, 2), (5, 6), (5, 14), (16, 64)]
+    c = by["b3_obj64_free_slots"]
+    assert c["obs"].shape[:2] == (3, 64) and c["n_obj"].tolist() == [64, 64, 64]
+    free = np.isnan(c["pose"]).all(axis=2)
+    assert 20 <= free.sum() <= 80 and np.isnan(c["obs"][free]).all() and not c["views"][free].any()
+    empty_view = np.isnan(c["obs"][..., 0]).all(axis=2) & ~free[..., None]                      # [B,max_obj,V]: a view no entry of which is filled, of a live object
+    assert empty_view.any() and not c["views"][empty_view].any()                                 # its row is zeros: what an unused ring column holds
+    tables = c["views"][~free].reshape(-1, 8 * 14)
+    assert len(np.unique(tables, axis=0)) == len(tables)                                         # every object has a table of its own
+
+
+# ---- the accuracy statement ---------------------------------------------------------------------------------------------------------------------
+
+ACCURACY_SEED, ACCURACY_OBJECTS, ACCURACY_TICKS = 7, 128, 16
+
+
+def accuracy(seed=ACCURACY_SEED, n=ACCURACY_OBJECTS, ticks=ACCURACY_TICKS, **kw):
+    s = wc.moving_camera_scene(n, ticks, seed, **kw)
+    out = spec.refine_window(s["state"], s["start"], s["model"], **wc.DEFAULTS)
+    rot, pos = np.zeros((n, 2)), np.zeros((n, 2))
+    for o, (R, t) in enumerate(s["truth"]):
+        for col, P in enumerate((s["single"][o].reshape(3, 4), out["pose"][o, 0].reshape(3, 4))):
+            rot[o, col] = views_spec.rotation_error_deg(P[:, :3], R)
+            pos[o, col] = np.linalg.norm(P[:, :3] @ s["model"][0] + P[:, 3] - (R @ s["model"][0] + t))
+    return rot, pos, out["status"][:, 0], out["n_obs"][:, 0]
+
+
+def test_the_window_beats_the_single_tick_estimate_under_a_moving_camera():
+    """The figures printed here are the ones README.md and DESIGN.md quote (seed 7, 128 valve-like objects at 0.6 - 1.4 m, 3 % depth noise and
+    0.1 map pixels on every peak, the camera 2 cm and 0.01 rad further every tick, 16 ticks)."""
+    rot, pos, status, n_obs = accuracy()
+    print(f"seed {ACCURACY_SEED}, {ACCURACY_OBJECTS} objects, {ACCURACY_TICKS} ticks: rotation error median {np.median(rot[:, 0]):.2f} -> {np.median(rot[:, 1]):.2f} deg, "
+          f"worst {rot[:, 0].max():.2f} -> {rot[:, 1].max():.2f} deg; centre error median {1e3 * np.median(pos[:, 0]):.2f} -> {1e3 * np.median(pos[:, 1]):.2f} mm, "
+          f"worst {1e3 * pos[:, 0].max():.1f} -> {1e3 * pos[:, 1].max():.1f} mm; statuses other than 0: {int((status != 0).sum())}")
+    assert (status == 0).all() and (n_obs == 5 * ACCURACY_TICKS).all()                # the centre and four key points in every tick
+    assert np.median(rot[:, 1]) < np.median(rot[:, 0]) and np.median(pos[:, 1]) < np.median(pos[:, 0])
+
+
+def test_a_standing_camera_gains_nothing_in_depth():
+    """The gain comes from baseline, not from averaging: with the camera at rest the 16 ticks' bearings lie along one ray per key point, and
+    the centre error along the viewing direction stays that of a single-view fit to bearings."""
+    rot_m, pos_m, status_m, _ = accuracy(n=32)
+    rot_s, pos_s, status_s, _ = accuracy(n=32, step=0.0, yaw=0.0)
+    print(f"32 objects, 16 ticks: centre error median moving {1e3 * np.median(pos_m[:, 1]):.2f} mm, standing {1e3 * np.median(pos_s[:, 1]):.2f} mm")
+    assert (status_m == 0).all() and (status_s == 0).all()
+    assert np.median(pos_m[:, 1]) < np.median(pos_s[:, 1])
