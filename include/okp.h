@@ -48,7 +48,8 @@ extern "C" {
                                     okp_rig_bearings, okp_refine_pose_views, OKP_REFINE_MAX_VIEWS (a rig's object poses refined against every
                                     camera's bearings);
                                     okp_window_push, okp_refine_pose_views_each (tracked objects refined against a sliding window of ticks'
-                                    bearings) */
+                                    bearings);
+                                    okp_refine_pose_views_robust (those two refinements under a Huber loss) */
 
 /* OKP_F16: IEEE half activations / weights, fp32 accumulate (BASELINE configs[4]).
  * OKP_F32X3 (okp_conv plans only): fp32 activations, weights and results like OKP_F32 - every tensor argument of such a plan is an
@@ -954,6 +955,44 @@ int okp_refine_pose_views_each(const double* obs_dev, const double* views_dev, c
                                const int32_t* n_obj_dev, const double* model_dev, double sigma_px, int32_t iters, double damping, int32_t B,
                                int32_t max_obj, int32_t S, int32_t V, double* pose_out_dev, double* fit_dev, int32_t* n_obs_dev,
                                double* information_dev, int32_t* status_dev, void* stream);
+/* okp_refine_pose_views_robust: okp_refine_pose_views under a Huber loss, by iteratively reweighted least squares.  A rig of four pairs has
+ * 40 bearings for 6 unknowns and a window of 16 ticks 80: a false peak, a key point grouped to the wrong object, a wrong stereo match or a
+ * stale camera pose is one gross error among them, and in plain least squares it pulls the pose by its full residual.  Here its pull is
+ * bounded.  One launch of a sibling of that kernel (the same wave per object, lanes, sums and solve, a weight per observation); the two
+ * plain entry points keep their instances and their bits.  There is no reference implementation: the specification is this comment
+ * (tests/refine_robust_spec.py restates it in NumPy).
+ *   views_each = 0: views [V][14], as okp_refine_pose_views takes it; views_each = 1: views [B][max_obj][V][14], as okp_refine_pose_views_each.
+ *   huber_px (map pixels): the residual length from which an observation is down-weighted.
+ * Everything said of okp_refine_pose_views holds - the inputs, which entries are observations, the parameters, the update, the damped solve
+ * with its pivot rule, the precheck - except:
+ *   Weights and cost.  c = huber_px / sigma_px and c2 = c * c are formed once on the host in fp64.  Per observation at an iterate, with e_u,
+ *     e_v as above: s = e_u*e_u + e_v*e_v (no contraction).  The observation is an INLIER when s <= c2.  w = 1 for an inlier, otherwise
+ *     c / sqrt(s) - a division.  rho = s for an inlier, otherwise (2 c) sqrt(s) - c2.
+ *   One step.  H = sum w j^T j, g = sum w j^T e, the robust cost J = sum rho and the plain cost Pl = sum s, all over the observations, with the
+ *     weights of the CURRENT iterate's residuals; the damped solve and the update are unchanged.  Exactly `iters` steps; all sums are
+ *     evaluated once more at the final iterate.
+ *   Status.  The same four, in the same order of evaluation; OKP_REFINE_REJECTED tests the ROBUST cost: J_final not finite, or
+ *     J_final > J_initial + 1e-12 x n_obs.  The plain cost may rise - that is what down-weighting an outlier does.
+ *   Outputs, all written by every call:
+ *     pose_out, n_obs, status            as okp_refine_pose_views writes them
+ *     information [B][max_obj][36]       the WEIGHTED H at the final iterate, undamped, exactly symmetric; NaN for a non-zero status
+ *     fit [B][max_obj][4] fp64           map pixels: sqrt(Pl / n_obs) * sigma_px at the input pose and at the final iterate - the two values of
+ *                                        okp_refine_pose_views' fit -, then sqrt(J / n_obs) * sigma_px at the input pose and at the final
+ *                                        iterate; all four NaN for a non-zero status
+ *     n_inlier [B][max_obj] int32        the inliers at the final iterate; 0 for a non-zero status
+ *     weight [B][max_obj][S][V] fp64     w of observation (s, v) at the final iterate, exactly 1.0 for an inlier; NaN for every entry that is
+ *                                        not an observation, and all NaN for a non-zero status
+ *   Objects from n_obj[b] on: as okp_refine_pose_views leaves them, n_inlier 0, weight all NaN.
+ *   A lane writes the weight words of its own (slot, view) entries, recomputed from the final iterate once the status is known.
+ * Limits.  The weights do not use the peaks' confidences.  Huber bounds an outlier's pull, it does not remove it: an outlier still adds
+ * c / sqrt(s) of its Jacobian rows.  With huber_px large enough that nothing is down-weighted the result is okp_refine_pose_views'.
+ * Refused on the host before any launch (OKP_EINVAL, the message names the argument): everything okp_refine_pose_views refuses, huber_px not
+ * positive and finite, views_each outside {0, 1}, a null n_inlier or weight. */
+int okp_refine_pose_views_robust(const double* obs_dev, const double* views_dev, int32_t views_each, const double* pose_dev,
+                                 const int32_t* assignment_dev, const int32_t* n_obj_dev, const double* model_dev, double sigma_px,
+                                 double huber_px, int32_t iters, double damping, int32_t B, int32_t max_obj, int32_t S, int32_t V,
+                                 double* pose_out_dev, double* fit_dev /* [B][max_obj][4] */, int32_t* n_obs_dev, int32_t* n_inlier_dev,
+                                 double* weight_dev /* [B][max_obj][S][V] */, double* information_dev, int32_t* status_dev, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * A sliding window of ticks' bearings per track (csrc/okp_window.hip).  Every pose above is a single-tick estimate: okp_refine_pose fits one
@@ -996,7 +1035,8 @@ int okp_refine_pose_views_each(const double* obs_dev, const double* views_dev, c
  *   start [B][T][12] fp64 = track_pose[b][i] bit for bit when filled >= min_views, otherwise NaN: okp_refine_pose_views_each then leaves
  *   free slots and short windows as OKP_REFINE_SKIPPED
  * Limits.  Static objects only: the window does not model motion, max_speed is a guard, not a model.  No robust loss and uniform weights
- * in the refinement: one wrong peak in one tick pulls the pose.  The error of the camera poses goes straight into the result: the
+ * in okp_refine_pose_views_each: there one wrong peak in one tick pulls the pose.  okp_refine_pose_views_robust (views_each = 1) on the same
+ * state bounds that pull with a Huber loss; it does not remove it, and its weights still do not use the peaks' confidences.  The error of the camera poses goes straight into the result: the
  * refinement takes T_WC as exact.  The window of a rig (2 P cameras x W ticks) would exceed OKP_REFINE_MAX_VIEWS: it is not offered.
  * Refused on the host before any launch (OKP_EINVAL, the message names the argument): W outside [1, OKP_REFINE_MAX_VIEWS], T outside
  * [1, OKP_TRACK_MAX_TRACKS], S outside [1, OKP_POSE_MAX_POINTS], B or max_obj < 1, min_views outside [1, W], max_speed not positive (NaN

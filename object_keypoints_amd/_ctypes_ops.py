@@ -395,6 +395,15 @@ def refine_pose_views_each(obs, views, pose, assignment, n_obj, model, sigma_px,
                                                      information.data_ptr(), status.data_ptr(), stream), "okp_refine_pose_views_each")
 
 
+def refine_pose_views_robust(obs, views, views_each, pose, assignment, n_obj, model, sigma_px, huber_px, iters, damping, pose_out, fit, n_obs, n_inlier, weight,
+                             information, status, stream):
+    b, max_obj, s, v, _ = obs.shape
+    _lib.check(_lib.lib().okp_refine_pose_views_robust(obs.data_ptr(), views.data_ptr(), views_each, pose.data_ptr(), assignment.data_ptr(), n_obj.data_ptr(),
+                                                       model.data_ptr(), sigma_px, huber_px, iters, damping, b, max_obj, s, v, pose_out.data_ptr(), fit.data_ptr(),
+                                                       n_obs.data_ptr(), n_inlier.data_ptr(), weight.data_ptr(), information.data_ptr(), status.data_ptr(), stream),
+               "okp_refine_pose_views_robust")
+
+
 # ---- a sliding window of ticks' bearings per track (csrc/okp_window.hip): win_obs [B,T,S,W,2], win_views [B,T,W,14], win_i [B,T,4] ------------------
 def window_push(camera, tab, assignment, status, meas_of, track_i, track_f, track_pose, T_WC, min_views, max_speed, win_obs, win_views, win_i, n_views, start, stream):
     b, max_obj, s, _ = tab.shape

@@ -19,6 +19,11 @@
 //                                  model row is skipped on a scalar branch.  A template on where the lane's row of `views` lies: one
 //                                  table for every object (okp_refine_pose_views), or one per object (okp_refine_pose_views_each: the
 //                                  sliding window of csrc/okp_window.hip, whose views are the ticks of each track's own ring).
+//   okp_refine_pose_views_robust_kernel   the same wave, lanes, registers, butterfly and solve under a Huber loss (okp_refine_pose_views_robust):
+//                                  a weight per observation from the current iterate's residuals, the robust cost where the plain kernel has
+//                                  its cost and the plain cost in a sum of its own, the inliers counted by ballot, and after the status is
+//                                  known a pass in which every lane writes the weights of its own (slot, view) entries.  A sibling, not a
+//                                  further template flag: the two plain instances stay the code they are.
 // fp64, no atomics, no host wait; the summation order is fixed, so the bits are the same on every run.
 #include "okp_pose_math.h"           // PoseTypes, pose_types, finite64, refine_step, the sums layout
 
@@ -261,6 +266,216 @@ __global__ __launch_bounds__(64) void okp_refine_pose_views_kernel(const ViewsPa
   P.status[oi] = status;
 }
 
+// ---- the robust sibling (okp_refine_pose_views_robust): the same wave, lanes and sums with a Huber weight per observation (IRLS) ----
+
+struct RobustParams {
+  ViewsParams v;                                  // (v.fit is [4] per object here)
+  double c, c2;                                   // huber_px / sigma_px and its square, formed on the host
+  int32_t* n_inlier; double* weight;
+};
+
+// H, g, the robust cost (slot 27, where the plain kernel keeps its cost) and the plain cost (slot 28)
+__device__ __forceinline__ void robust_butterfly(double (&acc)[OKP_REFINE_SUMS]) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1)
+#pragma unroll
+    for (int i = 0; i < 29; ++i) acc[i] += __shfl_xor(acc[i], off);
+}
+
+// One (slot, view) entry at the iterate (R, t): p = R m, the gradients b_u, b_v in the table's frame, the residual e and q_z.  The iteration
+// and the pass that writes the weights both call it, so a weight is the bits the final iterate's sums were made with.
+struct ViewTerm { double p0, p1, p2, bu0, bu1, bu2, bv0, bv1, bv2, e0, e1, qz; };
+__device__ __forceinline__ ViewTerm view_term(const double (&R)[9], const double (&t)[3], const double (&rv)[9], const double (&tv)[3], double kx, double ky,
+                                              double m0, double m1, double m2, double u, double v) {
+  ViewTerm o;
+  o.p0 = (R[0] * m0 + R[1] * m1) + R[2] * m2; o.p1 = (R[3] * m0 + R[4] * m1) + R[5] * m2; o.p2 = (R[6] * m0 + R[7] * m1) + R[8] * m2;
+  const double X0 = o.p0 + t[0], X1 = o.p1 + t[1], X2 = o.p2 + t[2];
+  const double q0 = ((rv[0] * X0 + rv[1] * X1) + rv[2] * X2) + tv[0], q1 = ((rv[3] * X0 + rv[4] * X1) + rv[5] * X2) + tv[1];
+  o.qz = ((rv[6] * X0 + rv[7] * X1) + rv[8] * X2) + tv[2];
+  const double iz = 1.0 / o.qz, xn = q0 * iz, yn = q1 * iz;
+  const double au0 = kx * iz, au2 = -(au0 * xn), av1 = ky * iz, av2 = -(av1 * yn);
+  o.bu0 = rv[0] * au0 + rv[6] * au2; o.bu1 = rv[1] * au0 + rv[7] * au2; o.bu2 = rv[2] * au0 + rv[8] * au2;
+  o.bv0 = rv[3] * av1 + rv[6] * av2; o.bv1 = rv[4] * av1 + rv[7] * av2; o.bv2 = rv[5] * av1 + rv[8] * av2;
+  o.e0 = kx * (xn - u); o.e1 = ky * (yn - v);
+  return o;
+}
+
+// the Huber weight of a squared residual s: 1 inside the threshold, c / sqrt(s) outside (NaN for a NaN s)
+__device__ __forceinline__ double huber_weight(double s, double c, double c2) { return s <= c2 ? 1.0 : c / sqrt(s); }
+
+template <bool EACH>
+__global__ __launch_bounds__(64) void okp_refine_pose_views_robust_kernel(const RobustParams Q) {
+  const ViewsParams& P = Q.v;
+  const int lane = threadIdx.x;
+  const size_t oi = blockIdx.x;
+  const int b = (int)(oi / P.max_obj), o = (int)(oi - (size_t)b * P.max_obj);
+  const bool live = o < P.n_obj[b];
+  const int S = P.S, V = P.V;
+  const int G = 64 >> P.vshift, grp = lane >> P.vshift, cam = lane & ((1 << P.vshift) - 1);
+  const int passes = (S + G - 1) / G;
+  const bool view = cam < V;
+  const double nan = __builtin_nan(""), inf = __builtin_inf();
+  const double c = Q.c, c2 = Q.c2, two_c = 2.0 * Q.c;
+
+  double R[9], t[3];
+  bool pose_finite = true;
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    const double* row = P.pose + oi * 12 + 4 * i;
+    R[3 * i + 0] = row[0]; R[3 * i + 1] = row[1]; R[3 * i + 2] = row[2]; t[i] = row[3];
+    pose_finite = pose_finite && finite64(row[0]) && finite64(row[1]) && finite64(row[2]) && finite64(row[3]);
+  }
+  double rv[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0}, tv[3] = {0.0, 0.0, 0.0}, kx = 1.0, ky = 1.0;
+  if (view) {
+    const double* row = P.views + (EACH ? oi * (size_t)V * 14 : (size_t)0) + (size_t)cam * 14;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) { rv[3 * i + 0] = row[4 * i + 0]; rv[3 * i + 1] = row[4 * i + 1]; rv[3 * i + 2] = row[4 * i + 2]; tv[i] = row[4 * i + 3]; }
+    kx = row[12] / P.sigma_px; ky = row[13] / P.sigma_px;
+  }
+  double ou[OKP_POSE_MAX_POINTS], ov[OKP_POSE_MAX_POINTS], m[OKP_POSE_MAX_POINTS][3];
+  unsigned seen = 0u, rows = 0u;
+  int n_obs = 0, n_rows = 0;
+  bool bad = false;
+  unsigned long long first = 0ull;
+  for (int g = 0; g < G; ++g) first |= 1ull << (g << P.vshift);
+#pragma unroll
+  for (int i = 0; i < OKP_POSE_MAX_POINTS; ++i) {
+    ou[i] = 0.0; ov[i] = 0.0; m[i][0] = 0.0; m[i][1] = 0.0; m[i][2] = 0.0;
+    if (i < passes) {
+      const int s = grp + G * i;
+      const bool slot = live && s < S;
+      const int a = slot ? P.assignment[oi * S + s] : -1;
+      const bool row = a >= 0 && a < S;
+      double u = nan, v = nan;
+      if (slot && view) {
+        const double* e = P.obs + ((oi * S + s) * V + cam) * 2;
+        u = e[0]; v = e[1];
+      }
+      bad = bad || ((u != u) != (v != v)) || fabs(u) == inf || fabs(v) == inf;
+      const bool mine = row && finite64(u) && finite64(v);
+      unsigned long long who = __ballot(mine);
+      n_obs += __popcll(who);
+      for (int sh = 1; sh < (1 << P.vshift); sh <<= 1) who |= who >> sh;
+      n_rows += __popcll(who & first);
+      if (mine) { ou[i] = u; ov[i] = v; seen |= 1u << i; }
+      if (row) { m[i][0] = P.model[a * 3 + 0]; m[i][1] = P.model[a * 3 + 1]; m[i][2] = P.model[a * 3 + 2]; }
+      if (__ballot(row) != 0ull) rows |= 1u << i;
+    }
+  }
+  const bool any_bad = __ballot(bad) != 0ull;
+  int status = (!live || !pose_finite || any_bad || n_rows < 3) ? OKP_REFINE_SKIPPED : 0;
+
+  double acc[OKP_REFINE_SUMS];
+  double J0 = nan, Pl0 = nan;
+  int n_inlier = 0;
+  if (status == 0) {
+    for (int k = 0;; ++k) {
+#pragma unroll
+      for (int i = 0; i < OKP_REFINE_SUMS; ++i) acc[i] = 0.0;
+      bool behind = false;
+      n_inlier = 0;
+#pragma unroll
+      for (int s = 0; s < OKP_POSE_MAX_POINTS; ++s) {
+        if (!((rows >> s) & 1u)) continue;                        // (wave-uniform)
+        const bool mine = (seen >> s) & 1u;
+        const ViewTerm T = view_term(R, t, rv, tv, kx, ky, m[s][0], m[s][1], m[s][2], ou[s], ov[s]);
+        behind = behind || (mine && T.qz <= 0.0);
+        double e[2] = {T.e0, T.e1};
+        double j[2][6] = {{T.p1 * T.bu2 - T.p2 * T.bu1, T.p2 * T.bu0 - T.p0 * T.bu2, T.p0 * T.bu1 - T.p1 * T.bu0, T.bu0, T.bu1, T.bu2},
+                          {T.p1 * T.bv2 - T.p2 * T.bv1, T.p2 * T.bv0 - T.p0 * T.bv2, T.p0 * T.bv1 - T.p1 * T.bv0, T.bv0, T.bv1, T.bv2}};
+        if (!mine) {
+          e[0] = 0.0; e[1] = 0.0;
+#pragma unroll
+          for (int q = 0; q < 6; ++q) { j[0][q] = 0.0; j[1][q] = 0.0; }
+        }
+        const double sq = e[0] * e[0] + e[1] * e[1];             // (0 for a lane without the observation: an inlier that adds nothing)
+        const bool inlier = sq <= c2;
+        const double w = huber_weight(sq, c, c2);
+        const double rho = inlier ? sq : two_c * sqrt(sq) - c2;
+        n_inlier += __popcll(__ballot(mine && inlier));
+        double wj[2][6];
+#pragma unroll
+        for (int q = 0; q < 6; ++q) { wj[0][q] = w * j[0][q]; wj[1][q] = w * j[1][q]; }
+        int idx = 0;
+#pragma unroll
+        for (int r = 0; r < 6; ++r)
+#pragma unroll
+          for (int q = r; q < 6; ++q) { acc[idx] += wj[0][r] * j[0][q] + wj[1][r] * j[1][q]; ++idx; }
+#pragma unroll
+        for (int r = 0; r < 6; ++r) acc[21 + r] += wj[0][r] * e[0] + wj[1][r] * e[1];
+        acc[27] += rho;
+        acc[28] += sq;
+      }
+      if (status == 0 && __ballot(behind) != 0ull) status = OKP_REFINE_BEHIND;
+      robust_butterfly(acc);
+      if (k == 0) { J0 = acc[27]; Pl0 = acc[28]; }
+      if (k == P.iters) break;
+      const bool singular = refine_step(acc, P.damping, R, t);
+      if (status == 0 && singular) status = OKP_REFINE_SINGULAR;
+    }
+    const double J1 = acc[27];
+    if (status == 0 && (!(J1 < inf) || J1 > J0 + 1e-12 * n_obs)) status = OKP_REFINE_REJECTED;
+  }
+  const bool ok = status == 0;
+
+  // the weights: a lane writes the words of its own (slot, view) entries - the lanes with cam < V and the passes cover the table - from the
+  // final iterate (R, t), after the status is known
+  if (view) {
+    double* wrow = Q.weight + oi * (size_t)S * V + cam;
+#pragma unroll
+    for (int i = 0; i < OKP_POSE_MAX_POINTS; ++i) {
+      const int s = grp + G * i;
+      if (i < passes && s < S) {
+        double w = nan;
+        if (ok && ((seen >> i) & 1u)) {
+          const ViewTerm T = view_term(R, t, rv, tv, kx, ky, m[i][0], m[i][1], m[i][2], ou[i], ov[i]);
+          w = huber_weight(T.e0 * T.e0 + T.e1 * T.e1, c, c2);
+        }
+        wrow[(size_t)s * V] = w;
+      }
+    }
+  }
+
+  // the other outputs: every word is written by every call, by the object's first lane
+  if (lane != 0) return;
+  double* pose_out = P.pose_out + oi * 12;
+  double* fit = P.fit + oi * 4;
+  double* info = P.information + oi * 36;
+  if (ok) {
+#pragma unroll
+    for (int i = 0; i < 3; ++i) { pose_out[4 * i + 0] = R[3 * i + 0]; pose_out[4 * i + 1] = R[3 * i + 1]; pose_out[4 * i + 2] = R[3 * i + 2]; pose_out[4 * i + 3] = t[i]; }
+  } else if (live) {                                              // the input pose, bit for bit (NaN payloads included)
+    const unsigned long long* src = reinterpret_cast<const unsigned long long*>(P.pose + oi * 12);
+    unsigned long long* dst = reinterpret_cast<unsigned long long*>(pose_out);
+    unsigned long long bits[12];
+#pragma unroll
+    for (int i = 0; i < 12; ++i) bits[i] = src[i];
+#pragma unroll
+    for (int i = 0; i < 12; ++i) dst[i] = bits[i];
+  } else {
+#pragma unroll
+    for (int i = 0; i < 12; ++i) pose_out[i] = nan;
+  }
+  fit[0] = ok ? sqrt(Pl0 / n_obs) * P.sigma_px : nan;
+  fit[1] = ok ? sqrt(acc[28] / n_obs) * P.sigma_px : nan;
+  fit[2] = ok ? sqrt(J0 / n_obs) * P.sigma_px : nan;
+  fit[3] = ok ? sqrt(acc[27] / n_obs) * P.sigma_px : nan;
+  {
+    int idx = 0;
+#pragma unroll
+    for (int r = 0; r < 6; ++r)
+#pragma unroll
+      for (int q = r; q < 6; ++q) {
+        const double hv = ok ? acc[idx] : nan;
+        ++idx;
+        info[6 * r + q] = hv; info[6 * q + r] = hv;
+      }
+  }
+  P.n_obs[oi] = n_obs;
+  Q.n_inlier[oi] = ok ? n_inlier : 0;
+  P.status[oi] = status;
+}
+
 // [a, a + na) and [b, b + nb) share a byte
 bool views_overlap(const void* a, size_t na, const void* b, size_t nb) {
   const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
@@ -291,10 +506,13 @@ extern "C" int okp_rig_bearings(const int32_t* count, const float* xyc, const in
   return okp_check_hip(hipGetLastError(), "okp_rig_bearings launch");
 }
 
-// the two entry points: one views table for every object, or one per object
-static int refine_views_launch(const char* fn, bool each, const double* obs, const double* views, const double* pose, const int32_t* assignment, const int32_t* n_obj,
-                               const double* model, double sigma_px, int32_t iters, double damping, int32_t B, int32_t max_obj, int32_t S, int32_t V,
-                               double* pose_out, double* fit, int32_t* n_obs, double* information, int32_t* status, void* stream) {
+// what every refinement against a table of views refuses (the message names the argument) -> the parameters of its launch.  huber_px and
+// views_each are null for the plain entry points; `extra` are the robust one's further outputs
+struct ViewsArg { const void* ptr; const char* name; };
+static int refine_views_params(const char* fn, const double* obs, const double* views, const double* pose, const int32_t* assignment, const int32_t* n_obj,
+                               const double* model, double sigma_px, const double* huber_px, const int32_t* views_each, int32_t iters, double damping, int32_t B,
+                               int32_t max_obj, int32_t S, int32_t V, double* pose_out, double* fit, int32_t* n_obs, double* information, int32_t* status,
+                               const ViewsArg* extra, int n_extra, ViewsParams& p) {
   if (B < 1) { okp_set_error("%s: B = %d; a batch holds at least one frame", fn, B); return OKP_EINVAL; }
   if (max_obj < 1) { okp_set_error("%s: max_obj = %d; a frame holds at least one object", fn, max_obj); return OKP_EINVAL; }
   if ((long long)B * max_obj > 0x7fffffffll) { okp_set_error("%s: B * max_obj = %lld objects do not fit one launch", fn, (long long)B * max_obj); return OKP_EINVAL; }
@@ -303,21 +521,43 @@ static int refine_views_launch(const char* fn, bool each, const double* obs, con
   if (iters < 1 || iters > OKP_REFINE_MAX_ITERS) { okp_set_error("%s: iters = %d outside [1, %d]", fn, iters, OKP_REFINE_MAX_ITERS); return OKP_EINVAL; }
   if (!(sigma_px > 0.0 && sigma_px < __builtin_inf())) { okp_set_error("%s: sigma_px = %g must be a positive, finite number of map pixels", fn, sigma_px); return OKP_EINVAL; }
   if (!(damping >= 0.0 && damping < __builtin_inf())) { okp_set_error("%s: damping = %g must be finite and not negative", fn, damping); return OKP_EINVAL; }
-  const struct { const void* ptr; const char* name; } required[] = {
+  if (huber_px && !(*huber_px > 0.0 && *huber_px < __builtin_inf())) {
+    okp_set_error("%s: huber_px = %g must be a positive, finite number of map pixels", fn, *huber_px);
+    return OKP_EINVAL;
+  }
+  if (views_each && *views_each != 0 && *views_each != 1) {
+    okp_set_error("%s: views_each = %d; 0 (views [V][14], one table for every object) or 1 (views [B][max_obj][V][14], one per object)", fn, *views_each);
+    return OKP_EINVAL;
+  }
+  const ViewsArg required[] = {
       {obs, "obs"}, {views, "views"}, {pose, "pose"}, {assignment, "assignment"}, {n_obj, "n_obj"}, {model, "model"},
       {pose_out, "pose_out"}, {fit, "fit"}, {n_obs, "n_obs"}, {information, "information"}, {status, "status"}};
   for (const auto& r : required)
     if (!r.ptr) { okp_set_error("%s: null %s", fn, r.name); return OKP_EINVAL; }
+  for (int i = 0; i < n_extra; ++i)
+    if (!extra[i].ptr) { okp_set_error("%s: null %s", fn, extra[i].name); return OKP_EINVAL; }
   const size_t n_total = (size_t)B * max_obj;
   if (views_overlap(pose_out, n_total * 12 * sizeof(double), pose, n_total * 12 * sizeof(double))) {
     okp_set_error("%s: pose_out overlaps pose: the input pose is the fallback and is read after other objects are written", fn);
     return OKP_EINVAL;
   }
-  ViewsParams p = {};
+  p = ViewsParams{};
   p.obs = obs; p.views = views; p.pose = pose; p.assignment = assignment; p.n_obj = n_obj; p.model = model;
   p.max_obj = max_obj; p.S = S; p.V = V; p.iters = iters; p.sigma_px = sigma_px; p.damping = damping;
   while ((1 << p.vshift) < V) ++p.vshift;
   p.pose_out = pose_out; p.fit = fit; p.n_obs = n_obs; p.information = information; p.status = status;
+  return OKP_OK;
+}
+
+// the two plain entry points: one views table for every object, or one per object
+static int refine_views_launch(const char* fn, bool each, const double* obs, const double* views, const double* pose, const int32_t* assignment, const int32_t* n_obj,
+                               const double* model, double sigma_px, int32_t iters, double damping, int32_t B, int32_t max_obj, int32_t S, int32_t V,
+                               double* pose_out, double* fit, int32_t* n_obs, double* information, int32_t* status, void* stream) {
+  ViewsParams p;
+  const int rc = refine_views_params(fn, obs, views, pose, assignment, n_obj, model, sigma_px, nullptr, nullptr, iters, damping, B, max_obj, S, V, pose_out, fit, n_obs,
+                                     information, status, nullptr, 0, p);
+  if (rc) return rc;
+  const size_t n_total = (size_t)B * max_obj;
   if (each) hipLaunchKernelGGL(okp_refine_pose_views_kernel<true>, dim3((unsigned)n_total), dim3(64), 0, (hipStream_t)stream, p);
   else hipLaunchKernelGGL(okp_refine_pose_views_kernel<false>, dim3((unsigned)n_total), dim3(64), 0, (hipStream_t)stream, p);
   return okp_check_hip(hipGetLastError(), each ? "okp_refine_pose_views_each launch" : "okp_refine_pose_views launch");
@@ -335,4 +575,23 @@ extern "C" int okp_refine_pose_views_each(const double* obs, const double* views
                                           int32_t V, double* pose_out, double* fit, int32_t* n_obs, double* information, int32_t* status, void* stream) {
   return refine_views_launch("okp_refine_pose_views_each", true, obs, views, pose, assignment, n_obj, model, sigma_px, iters, damping, B, max_obj, S, V, pose_out,
                              fit, n_obs, information, status, stream);
+}
+
+extern "C" int okp_refine_pose_views_robust(const double* obs, const double* views, int32_t views_each, const double* pose, const int32_t* assignment,
+                                            const int32_t* n_obj, const double* model, double sigma_px, double huber_px, int32_t iters, double damping, int32_t B,
+                                            int32_t max_obj, int32_t S, int32_t V, double* pose_out, double* fit, int32_t* n_obs, int32_t* n_inlier, double* weight,
+                                            double* information, int32_t* status, void* stream) {
+  const char* fn = "okp_refine_pose_views_robust";
+  const ViewsArg extra[] = {{n_inlier, "n_inlier"}, {weight, "weight"}};
+  RobustParams q = {};
+  const int rc = refine_views_params(fn, obs, views, pose, assignment, n_obj, model, sigma_px, &huber_px, &views_each, iters, damping, B, max_obj, S, V, pose_out, fit,
+                                     n_obs, information, status, extra, 2, q.v);
+  if (rc) return rc;
+  q.c = huber_px / sigma_px;                                      // the threshold in units of sigma_px, and its square: once, here
+  q.c2 = q.c * q.c;
+  q.n_inlier = n_inlier; q.weight = weight;
+  const unsigned n_total = (unsigned)((size_t)B * max_obj);
+  if (views_each) hipLaunchKernelGGL(okp_refine_pose_views_robust_kernel<true>, dim3(n_total), dim3(64), 0, (hipStream_t)stream, q);
+  else hipLaunchKernelGGL(okp_refine_pose_views_robust_kernel<false>, dim3(n_total), dim3(64), 0, (hipStream_t)stream, q);
+  return okp_check_hip(hipGetLastError(), "okp_refine_pose_views_robust launch");
 }

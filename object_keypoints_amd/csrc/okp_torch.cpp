@@ -789,6 +789,35 @@ void refine_pose_views_each(const Tensor& obs, const Tensor& views, const Tensor
   refine_views(true, obs, views, pose, assignment, n_obj, model, sigma_px, iters, damping, pose_out, fit, n_obs, information, status, stream);
 }
 
+// The two under a Huber loss (okp_refine_pose_views_robust): views [V,14] (views_each = 0) or [B,max_obj,V,14] (1); fit is [B,max_obj,4], and
+// n_inlier [B,max_obj] and weight [B,max_obj,S,V] are written next to the plain outputs
+void refine_pose_views_robust(const Tensor& obs, const Tensor& views, int64_t views_each, const Tensor& pose, const Tensor& assignment, const Tensor& n_obj,
+                              const Tensor& model, double sigma_px, double huber_px, int64_t iters, double damping, const Tensor& pose_out, const Tensor& fit,
+                              const Tensor& n_obs, const Tensor& n_inlier, const Tensor& weight, const Tensor& information, const Tensor& status, int64_t stream) {
+  check_dev(obs, at::kDouble, "obs"); check_dev(views, at::kDouble, "views"); check_dev(pose, at::kDouble, "pose"); check_dev(assignment, at::kInt, "assignment");
+  check_dev(n_obj, at::kInt, "n_obj"); check_dev(model, at::kDouble, "model"); check_dev(pose_out, at::kDouble, "pose_out"); check_dev(fit, at::kDouble, "fit");
+  check_dev(n_obs, at::kInt, "n_obs"); check_dev(n_inlier, at::kInt, "n_inlier"); check_dev(weight, at::kDouble, "weight");
+  check_dev(information, at::kDouble, "information"); check_dev(status, at::kInt, "status");
+  TORCH_CHECK(obs.dim() == 5 && obs.size(4) == 2, "okp: obs is [B,max_obj,S,V,2] float64");
+  const int64_t B = obs.size(0), max_obj = obs.size(1), S = obs.size(2), V = obs.size(3);
+  TORCH_CHECK(views_each >= INT32_MIN && views_each <= INT32_MAX, "okp: views_each does not fit an int32");
+  TORCH_CHECK((views_each != 0 && views_each != 1) || views.numel() == (views_each == 1 ? B * max_obj : 1) * V * 14,      // (any other value: the entry point refuses it)
+              "okp: refine_pose_views_robust takes views [V,14] (views_each = 0) or [B,max_obj,V,14] (views_each = 1)");
+  TORCH_CHECK(pose.numel() == B * max_obj * 12 && assignment.numel() == B * max_obj * S && n_obj.numel() == B && model.numel() == S * 3,
+              "okp: refine_pose_views_robust inputs are pose [B,max_obj,12], assignment [B,max_obj,S], n_obj [B] and model [S,3]");
+  TORCH_CHECK(pose_out.numel() == B * max_obj * 12 && fit.numel() == B * max_obj * 4 && n_obs.numel() == B * max_obj && n_inlier.numel() == B * max_obj &&
+              weight.numel() == B * max_obj * S * V && information.numel() == B * max_obj * 36 && status.numel() == B * max_obj,
+              "okp: refine_pose_views_robust outputs are pose_out [B,max_obj,12], fit [B,max_obj,4], n_obs and n_inlier [B,max_obj], weight [B,max_obj,S,V], "
+              "information [B,max_obj,36] and status [B,max_obj]");
+  TORCH_CHECK(iters >= INT32_MIN && iters <= INT32_MAX, "okp: iters does not fit an int32");
+  TORCH_CHECK(B <= INT32_MAX && max_obj <= INT32_MAX && S <= INT32_MAX && V <= INT32_MAX, "okp: obs is too large");
+  check_rc(okp_refine_pose_views_robust(obs.data_ptr<double>(), views.data_ptr<double>(), (int32_t)views_each, pose.data_ptr<double>(), assignment.data_ptr<int32_t>(),
+                                        n_obj.data_ptr<int32_t>(), model.data_ptr<double>(), sigma_px, huber_px, (int32_t)iters, damping, (int32_t)B, (int32_t)max_obj,
+                                        (int32_t)S, (int32_t)V, pose_out.data_ptr<double>(), fit.data_ptr<double>(), n_obs.data_ptr<int32_t>(),
+                                        n_inlier.data_ptr<int32_t>(), weight.data_ptr<double>(), information.data_ptr<double>(), status.data_ptr<int32_t>(), sp(stream)),
+           "okp_refine_pose_views_robust");
+}
+
 // A sliding window of ticks' bearings per track slot (csrc/okp_window.hip): the camera-frame table, the assignment and status the tracker's tick had, the tracker's
 // meas_of / track_i / track_f / track_pose and T_WC -> the state win_obs [B,T,S,W,2], win_views [B,T,W,14], win_i [B,T,4] stepped in place, n_views [B,T], start [B,T,12]
 void window_push(at::ArrayRef<double> camera, const Tensor& tab, const Tensor& assignment, const Tensor& status, const Tensor& meas_of, const Tensor& track_i,
@@ -989,6 +1018,9 @@ TORCH_LIBRARY(okp, m) {
         "Tensor(a!) pose_out, Tensor(b!) fit, Tensor(c!) n_obs, Tensor(d!) information, Tensor(e!) status, int stream) -> ()", refine_pose_views);
   m.def("refine_pose_views_each(Tensor obs, Tensor views, Tensor pose, Tensor assignment, Tensor n_obj, Tensor model, float sigma_px, int iters, float damping, "
         "Tensor(a!) pose_out, Tensor(b!) fit, Tensor(c!) n_obs, Tensor(d!) information, Tensor(e!) status, int stream) -> ()", refine_pose_views_each);
+  m.def("refine_pose_views_robust(Tensor obs, Tensor views, int views_each, Tensor pose, Tensor assignment, Tensor n_obj, Tensor model, float sigma_px, float huber_px, "
+        "int iters, float damping, Tensor(a!) pose_out, Tensor(b!) fit, Tensor(c!) n_obs, Tensor(d!) n_inlier, Tensor(e!) weight, Tensor(f!) information, "
+        "Tensor(g!) status, int stream) -> ()", refine_pose_views_robust);
   m.def("window_push(float[] camera, Tensor tab, Tensor assignment, Tensor status, Tensor meas_of, Tensor track_i, Tensor track_f, Tensor track_pose, Tensor T_WC, "
         "int min_views, float max_speed, Tensor(a!) win_obs, Tensor(b!) win_views, Tensor(c!) win_i, Tensor(d!) n_views, Tensor(e!) start, int stream) -> ()", window_push);
   m.def("refine_assignments(float[] camera, Tensor tab, Tensor pose, Tensor assignment, Tensor n_obj, Tensor model, int[] type_count, float sigma_px, float sigma_z, int iters, "

@@ -1430,9 +1430,11 @@ class RefineConfig:
                   its own rigid fit, and keeps the one of least final cost (okp_refine_assignments) instead of refining the fit's own.
     refine_pose_views - the refinement of a rig's poses against every camera's bearings, StereoStreamPipeline's - reads sigma_px, iters and
     damping only: its cost has no depth term, so sigma_z is not used, and it does not resolve assignments (a rig pipeline refuses
-    resolve_assignment=True)."""
+    resolve_assignment=True).
+        huber_px  (keyword, default None) map pixels, positive and finite: refine_pose_views / refine_pose_views_each then run under a Huber
+                  loss with this threshold (okp_refine_pose_views_robust).  The single-camera refinement does not offer it."""
 
-    def __init__(self, sigma_px=0.25, sigma_z=0.05, iters=6, damping=1e-9, *, resolve_assignment=False):
+    def __init__(self, sigma_px=0.25, sigma_z=0.05, iters=6, damping=1e-9, *, resolve_assignment=False, huber_px=None):
         def number(name, v):
             if isinstance(v, bool):
                 raise OkpError(f"RefineConfig: {name} = {v!r} is not a number")
@@ -1454,16 +1456,35 @@ class RefineConfig:
         if not isinstance(resolve_assignment, (bool, np.bool_)):
             raise OkpError(f"RefineConfig: resolve_assignment = {resolve_assignment!r} must be True or False")
         self.resolve_assignment = bool(resolve_assignment)
+        self.huber_px = _huber_px("RefineConfig", huber_px)
 
     def __repr__(self):
         flag = ", resolve_assignment=True" if self.resolve_assignment else ""
+        flag += f", huber_px={self.huber_px}" if self.huber_px is not None else ""
         return f"RefineConfig(sigma_px={self.sigma_px}, sigma_z={self.sigma_z}, iters={self.iters}, damping={self.damping}{flag})"
+
+
+def _huber_px(owner, v):
+    """huber_px of a RefineConfig / WindowConfig: None, or a positive finite number of map pixels."""
+    if v is None:
+        return None
+    if isinstance(v, (bool, np.bool_)):
+        raise OkpError(f"{owner}: huber_px = {v!r} is not a number (None: no robust loss)")
+    try:
+        h = float(v)
+    except (TypeError, ValueError):
+        raise OkpError(f"{owner}: huber_px = {v!r} is not a number (None: no robust loss)") from None
+    if not (h > 0.0 and np.isfinite(h)):
+        raise OkpError(f"{owner}: huber_px = {v!r} must be positive and finite (map pixels; None: no robust loss)")
+    return h
 
 
 def _refine_inputs(tab, pose, n_obj, model, cam, cfg):
     """The argument checks refine_pose and refine_assignments share -> (fitted, assignment, b, max_obj, s, dev)."""
     if not isinstance(cfg, RefineConfig):
         raise OkpError("cfg must be an ops.RefineConfig")
+    if cfg.huber_px is not None:                 # (not ignored quietly: okp_refine_pose and okp_refine_assignments have no robust form)
+        raise OkpNotOffered("cfg.huber_px: not offered for the single-camera refinement (refine_pose_views and refine_pose_views_each take it)")
     if not isinstance(cam, _lib.okp_camera):
         raise OkpError(f"cam must be an okp_camera (make_camera), not {type(cam).__name__}")
     try:
@@ -1640,7 +1661,11 @@ def refine_pose_views(obs, views, pose, n_obj, model, cfg):
     -> {"pose" [B,max_obj,12] float64 (the refined [R | t]; the input pose bit for bit where the status is not 0), "fit" [B,max_obj,2] float64
         (reprojection rmse in map pixels before and after; NaN where the status is not 0), "n_obs" [B,max_obj] int32 (bearings used),
         "information" [B,max_obj,36] float64 (H at the refined pose, 6 x 6 over (rotation, translation); NaN where the status is not 0),
-        "status" [B,max_obj] int32 (0, REFINE_SKIPPED, REFINE_SINGULAR, REFINE_BEHIND or REFINE_REJECTED)}.  One launch, no host sync."""
+        "status" [B,max_obj] int32 (0, REFINE_SKIPPED, REFINE_SINGULAR, REFINE_BEHIND or REFINE_REJECTED)}.  One launch, no host sync.
+    With cfg.huber_px set the one launch is okp_refine_pose_views_robust - the same refinement under a Huber loss with that threshold in map
+    pixels - and the dict has the same keys with "fit" as [B,max_obj,4] (the two values above, then the rmse of the robust cost before and
+    after), plus "n_inlier" [B,max_obj] int32 (bearings inside the threshold at the refined pose) and "weight" [B,max_obj,S,V] float64 (the
+    weight of every bearing there: exactly 1.0 for an inlier, NaN where there is no observation or the status is not 0)."""
     return _refine_views(False, obs, views, pose, n_obj, model, cfg)
 
 
@@ -1648,7 +1673,8 @@ def refine_pose_views_each(obs, views, pose, n_obj, model, cfg):
     """refine_pose_views with one views table per object (okp_refine_pose_views_each): views [B,max_obj,V,14] float64 (device), object (b, o)
     reads its own V rows; everything else - the other arguments, the cost, the statuses, the returned dict - is refine_pose_views'.  cfg: a
     RefineConfig or a WindowConfig (sigma_px, iters and damping are read).  A view none of whose entries is filled contributes nothing,
-    whatever its row holds.  With one table replicated per object the result has the bits of refine_pose_views.  One launch, no host sync."""
+    whatever its row holds.  With one table replicated per object the result has the bits of refine_pose_views.  One launch, no host sync.
+    cfg.huber_px selects the Huber sibling as it does there (views_each = 1)."""
     return _refine_views(True, obs, views, pose, n_obj, model, cfg)
 
 
@@ -1679,11 +1705,20 @@ def _refine_views(each, obs, views, pose, n_obj, model, cfg):
     if model.dtype != torch.float64 or tuple(model.shape) != (s, 3) or model.device != dev:
         raise OkpError(f"model must be float64 [{s},3] on the bearings' device (object_model)")
     pose_out = torch.empty((b, max_obj, 12), dtype=torch.float64, device=dev)
-    fit = torch.empty((b, max_obj, 2), dtype=torch.float64, device=dev)
     n_obs = torch.empty((b, max_obj), dtype=torch.int32, device=dev)
     information = torch.empty((b, max_obj, 36), dtype=torch.float64, device=dev)
     status = torch.empty((b, max_obj), dtype=torch.int32, device=dev)
     B = _ops()
+    huber_px = getattr(cfg, "huber_px", None)
+    if huber_px is not None:                     # the Huber sibling: one launch, today's keys (fit with four values) and the two it adds
+        fit = torch.empty((b, max_obj, 4), dtype=torch.float64, device=dev)
+        n_inlier = torch.empty((b, max_obj), dtype=torch.int32, device=dev)
+        weight = torch.empty((b, max_obj, s, v), dtype=torch.float64, device=dev)
+        _dispatch(B.refine_pose_views_robust, obs.contiguous(), views.contiguous(), 1 if each else 0, fitted.contiguous(), assignment.contiguous(),
+                  n_obj.reshape(b).contiguous(), model.contiguous(), cfg.sigma_px, huber_px, cfg.iters, cfg.damping, pose_out, fit, n_obs, n_inlier, weight, information,
+                  status, stream_int())
+        return {"pose": pose_out, "fit": fit, "n_obs": n_obs, "information": information, "status": status, "n_inlier": n_inlier, "weight": weight}
+    fit = torch.empty((b, max_obj, 2), dtype=torch.float64, device=dev)
     _dispatch(B.refine_pose_views_each if each else B.refine_pose_views, obs.contiguous(), views.contiguous(), fitted.contiguous(), assignment.contiguous(),
               n_obj.reshape(b).contiguous(), model.contiguous(), cfg.sigma_px, cfg.iters, cfg.damping, pose_out, fit, n_obs, information, status, stream_int())
     return {"pose": pose_out, "fit": fit, "n_obs": n_obs, "information": information, "status": status}
@@ -1697,9 +1732,11 @@ class WindowConfig:
         min_views  the refinement runs from this many filled columns on, 1 .. ticks (fewer: the status is REFINE_SKIPPED)
         max_speed  metres per second: a track whose filtered speed exceeds it has its ring emptied - the window assumes a STATIC object
                    (positive; inf: never)
-        sigma_px, iters, damping   as in RefineConfig (there is no depth term)."""
+        sigma_px, iters, damping   as in RefineConfig (there is no depth term)
+        huber_px   (keyword, default None) map pixels, positive and finite: the refinement of the ring then runs under a Huber loss with this
+                   threshold (okp_refine_pose_views_robust, views_each = 1)."""
 
-    def __init__(self, ticks, min_views=2, max_speed=float("inf"), sigma_px=0.25, iters=6, damping=1e-9):
+    def __init__(self, ticks, min_views=2, max_speed=float("inf"), sigma_px=0.25, iters=6, damping=1e-9, *, huber_px=None):
         def number(name, v):
             if isinstance(v, bool):
                 raise OkpError(f"WindowConfig: {name} = {v!r} is not a number")
@@ -1723,10 +1760,12 @@ class WindowConfig:
         if not (self.damping >= 0.0 and np.isfinite(self.damping)):
             raise OkpError(f"WindowConfig: damping = {damping!r} must be finite and not negative")
         self.iters = integer("iters", iters, 1, REFINE_MAX_ITERS)
+        self.huber_px = _huber_px("WindowConfig", huber_px)
 
     def __repr__(self):
+        flag = f", huber_px={self.huber_px}" if self.huber_px is not None else ""
         return (f"WindowConfig(ticks={self.ticks}, min_views={self.min_views}, max_speed={self.max_speed}, sigma_px={self.sigma_px}, iters={self.iters}, "
-                f"damping={self.damping})")
+                f"damping={self.damping}{flag})")
 
 
 def window_state(B, max_tracks, S, ticks, device):

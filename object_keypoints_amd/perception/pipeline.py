@@ -588,6 +588,8 @@ def _pose_fields(pose, n, refine=None):
         fields.update(refine=refine["pose"][n], refine_fit=refine["fit"][n], information=refine["information"][n], refine_status=refine["status"][n])
         if "n_obs" in refine:                    # an ops.refine_pose_views dict (a rig): "refine_fit" is [max_obj,2], and "refine_n_obs" [max_obj]
             fields.update(refine_n_obs=refine["n_obs"][n])
+        if "n_inlier" in refine:                 # under a Huber loss (RefineConfig.huber_px): "refine_fit" is [max_obj,4], "refine_weight" [max_obj,S,V]
+            fields.update(refine_n_inlier=refine["n_inlier"][n], refine_weight=refine["weight"][n])
         if "hypothesis" in refine:
             fields.update(refine_assignment=refine["assignment"][n], refine_hypothesis=refine["hypothesis"][n], refine_cost=refine["cost"][n])
     return fields
@@ -600,6 +602,8 @@ def _track_fields(track, n, window=None):
     fields = {k: track[k][n] for k in ("track_pose", "track_f", "track_i", "track_of", "meas_of", "track_pose_C") if k in track}
     if window is not None:
         fields.update({"window_" + k: window[k][n] for k in ("pose", "pose_C", "fit", "n_views", "information", "status")})
+        if "n_inlier" in window:                 # under a Huber loss (WindowConfig.huber_px): "window_fit" is [T,4], "window_weight" [T,S,W]
+            fields.update(window_n_inlier=window["n_inlier"][n], window_weight=window["weight"][n])
     return fields
 
 
@@ -617,12 +621,23 @@ def _window_entries(rec, slot):
     """A track slot's windowed pose as the entries tracks() adds: 'T_WO_window' and 'T_CO_window' (4 x 4; None where 'window_status' is not 0 -
     a short window, a free slot, a refused refinement - or, for 'T_CO_window', the camera pose is missing: the caller falls back to the
     track pose), 'window_views' (filled ring columns), 'window_rmse' (reprojection rmse before, after; map pixels), 'window_information'
-    (6 x 6) and 'window_status'."""
+    (6 x 6) and 'window_status'; under a Huber loss also 'window_inliers', 'window_robust_rmse' (the rmse of the robust cost before, after; map
+    pixels) and 'window_outliers', the (model row, ring column) entries the final iterate down-weighted."""
     ok = int(rec["window_status"][slot]) == 0
     fit = rec["window_fit"][slot]
-    return {'T_WO_window': _track_transform(rec["window_pose"][slot]) if ok else None, 'T_CO_window': _track_transform(rec["window_pose_C"][slot]) if ok else None,
-            'window_views': int(rec["window_n_views"][slot]), 'window_rmse': (float(fit[0]), float(fit[1])),
-            'window_information': rec["window_information"][slot].reshape(6, 6).copy(), 'window_status': int(rec["window_status"][slot])}
+    entries = {'T_WO_window': _track_transform(rec["window_pose"][slot]) if ok else None, 'T_CO_window': _track_transform(rec["window_pose_C"][slot]) if ok else None,
+               'window_views': int(rec["window_n_views"][slot]), 'window_rmse': (float(fit[0]), float(fit[1])),
+               'window_information': rec["window_information"][slot].reshape(6, 6).copy(), 'window_status': int(rec["window_status"][slot])}
+    if "window_n_inlier" in rec:
+        entries.update(window_inliers=int(rec["window_n_inlier"][slot]), window_robust_rmse=(float(fit[2]), float(fit[3])),
+                       window_outliers=_outliers(rec["window_weight"][slot]))
+    return entries
+
+
+def _outliers(weight):
+    """The (row, column) entries of one object's weight table [S,V] with weight < 1: what the Huber loss down-weighted (NaN: no observation)."""
+    with np.errstate(invalid="ignore"):
+        return [(int(s), int(v)) for s, v in zip(*np.nonzero(weight < 1.0))]
 
 
 def _refine_entries(rec, o, T_CO):
@@ -643,14 +658,19 @@ def _refine_entries(rec, o, T_CO):
 
 def _rig_refine_entries(rec, o, T_BO):
     """Object o's refined pose as the entries rig_objects() adds: 'T_BO_refined' (None where 'T_BO' is; the fitted pose where the refinement's
-    status is not 0), 'reprojection_rmse' (before, after), 'refine_observations', 'pose_information' (6 x 6) and 'refine_status'."""
+    status is not 0), 'reprojection_rmse' (before, after), 'refine_observations', 'pose_information' (6 x 6) and 'refine_status'; under a
+    Huber loss also 'refine_inliers', 'robust_rmse' (the rmse of the robust cost before, after; map pixels) and 'refine_outliers', the
+    (table slot, camera) entries the final iterate down-weighted."""
     fit = rec["refine_fit"]
     T = None
     if T_BO is not None:
         T = np.eye(4)
         T[:3] = rec["refine"][o].reshape(3, 4)
-    return {'T_BO_refined': T, 'reprojection_rmse': (float(fit[o, 0]), float(fit[o, 1])), 'refine_observations': int(rec["refine_n_obs"][o]),
-            'pose_information': rec["information"][o].reshape(6, 6).copy(), 'refine_status': int(rec["refine_status"][o])}
+    entries = {'T_BO_refined': T, 'reprojection_rmse': (float(fit[o, 0]), float(fit[o, 1])), 'refine_observations': int(rec["refine_n_obs"][o]),
+               'pose_information': rec["information"][o].reshape(6, 6).copy(), 'refine_status': int(rec["refine_status"][o])}
+    if "refine_n_inlier" in rec:
+        entries.update(refine_inliers=int(rec["refine_n_inlier"][o]), robust_rmse=(float(fit[o, 2]), float(fit[o, 3])), refine_outliers=_outliers(rec["refine_weight"][o]))
+    return entries
 
 
 def _pose_entries(rec, o, key):
@@ -765,8 +785,11 @@ class _Window:
         pushed = ops.window_push(st, tab, assignment, status, track, T_WC, cam, self.cfg)
         refined = ops.refine_pose_views_each(st["win_obs"], st["win_views"], {"pose": pushed["start"], "assignment": st["win_assignment"]}, st["win_n"], model, self.cfg)
         pose_C = ops.change_frame(T_WC, poses=refined["pose"], inverse=True)["poses"]
-        return {"pose": refined["pose"], "fit": refined["fit"], "n_obs": refined["n_obs"], "n_views": pushed["n_views"], "information": refined["information"],
-                "status": refined["status"], "pose_C": pose_C, "win_obs": st["win_obs"], "win_views": st["win_views"], "win_i": st["win_i"]}
+        out = {"pose": refined["pose"], "fit": refined["fit"], "n_obs": refined["n_obs"], "n_views": pushed["n_views"], "information": refined["information"],
+               "status": refined["status"], "pose_C": pose_C, "win_obs": st["win_obs"], "win_views": st["win_views"], "win_i": st["win_i"]}
+        if "n_inlier" in refined:                # cfg.huber_px: the refinement was okp_refine_pose_views_robust
+            out.update(n_inlier=refined["n_inlier"], weight=refined["weight"])
+        return out
 
     def reset(self):
         for st in self.states.values():
@@ -802,6 +825,8 @@ class _ObjectStage:
     a model with more than ops.REFINE_MAX_HYPOTHESES assignments is refused at construction.  A rig's table holds fused points, not one camera's
     bearings: its step hands run() `rig` - the tick's peaks, matches, fusion, calibration table and views table - and the refinement is
     okp_rig_bearings, then okp_refine_pose_views against the bearings of every camera; "refine" is ops.refine_pose_views' dict plus "obs".
+    With RefineConfig(..., huber_px=h) that second launch is okp_refine_pose_views_robust - the same refinement under a Huber loss - and
+    "refine" gains "n_inlier" and "weight" (WindowConfig(..., huber_px=h) does the same to the window's refinement and "window").
     World frame (world_frame=True; the step's frame_pose [B,12] takes the table's frame to the world, an all-NaN row = missing in this tick):
     okp_change_frame on the step's points and, with the pose, on the table and the poses -> "world": {"T", "points", "overflow" (the
     step's word | ops.FRAME_MISSING)} and "tab", "pose".
@@ -1020,13 +1045,21 @@ class BatchedKeypointPipeline(_ObjectStagePipeline):
     triangulation that does not use the depth head, whose gain comes from the baseline the camera travels (a standing camera gains nothing in
     depth).  tracks() adds 'T_WO_window', 'T_CO_window' (None where 'window_status' is not 0 - a short window, a refused refinement -: fall back
     to the track pose), 'window_views', 'window_rmse', 'window_information' and 'window_status'; objects() adds 'T_CO_window' and
-    'window_views' of the object's track - still one device -> host copy each.  Static objects only, no robust loss, uniform weights, and the
-    error of camera_pose goes straight into the result.  StereoStreamPipeline has no window: 2 P cameras x ticks exceed the kernel's 64 views.
+    'window_views' of the object's track - still one device -> host copy each.  Static objects only, and the error of camera_pose goes
+    straight into the result.  StereoStreamPipeline has no window: 2 P cameras x ticks exceed the kernel's 64 views.
+    window = ops.WindowConfig(..., huber_px=h): the ring is refined under a Huber loss (okp_refine_pose_views_robust, one launch in place of
+    okp_refine_pose_views_each), so one wrong peak in one tick no longer pulls the pose by its full residual; "window" gains "n_inlier" and
+    "weight", "fit" has four values, and tracks() adds 'window_inliers', 'window_robust_rmse' and 'window_outliers', the (model row, ring
+    column) entries that were down-weighted.  The weights do not use the peaks' confidences, and an outlier's pull is bounded, not removed.
+    refine = ops.RefineConfig(..., huber_px=h) is refused here (ops.OkpNotOffered): one camera's five points leave no redundancy to vote with.
     """
 
     def __init__(self, net, keypoint_config, camera, prediction_size=(64, 64), capacity=DEFAULT_PEAK_CAPACITY,
                  max_objects=16, max_per_type=4, points_3d=None, max_rmse=None, track=None, world_frame=False, refine=None, window=None):
         self.net = net
+        if isinstance(refine, ops.RefineConfig) and refine.huber_px is not None:
+            raise OkpNotOffered("refine with huber_px: not offered for one camera (five points against six unknowns and a depth prior leave a Huber loss "
+                                "nothing to vote with); window=ops.WindowConfig(..., huber_px=...) and a rig's refine take it")
         self.max_objects = max_objects
         self.max_per_type = max_per_type
         self.config = keypoint_config
@@ -1346,6 +1379,11 @@ class StereoStreamPipeline(_ObjectStagePipeline):
     uploaded once per device, like the calibration and the poses.  rig_objects(out) then adds 'T_BO_refined' (None where 'T_BO' is),
     'reprojection_rmse' (before, after; map pixels), 'refine_observations', 'pose_information' (6 x 6) and 'refine_status'.  Under an
     initialised process group tick_sharded refuses a refinement: the other ranks' peaks are not in the gathered payload.
+    refine = ops.RefineConfig(..., huber_px=h): the second launch is okp_refine_pose_views_robust, the same refinement under a Huber loss, so a
+    false peak or a wrong match among the 10 P bearings of an object no longer pulls the pose by its full residual (bounded, not removed; the
+    weights do not use the peaks' confidences).  "refine" gains "n_inlier" and "weight", its "fit" has four values, and rig_objects(out) adds
+    'refine_inliers', 'robust_rmse' (the rmse of the robust cost before, after) and 'refine_outliers', the (table slot, camera) entries that
+    were down-weighted; 'reprojection_rmse' stays the plain one.  The tracker and the world frame take the refined pose as before.
     rig_objects(out) adds 'T_BO' (4 x 4, model -> rig coordinates, or None), 'rmse', 'ambiguity' and 'pose_status' to every object; with track
     'track_id', 'T_BO_track', 'velocity', 'track_hits' and 'confirmed'; with world_frame 'T_WO' and 'T_WO_track' next to them.  rig_tracks(out)
     lists the live tracks, reset_tracks() empties the tracker.
