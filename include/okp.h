@@ -49,7 +49,9 @@ extern "C" {
                                     camera's bearings);
                                     okp_window_push, okp_refine_pose_views_each (tracked objects refined against a sliding window of ticks'
                                     bearings);
-                                    okp_refine_pose_views_robust (those two refinements under a Huber loss) */
+                                    okp_refine_pose_views_robust (those two refinements under a Huber loss);
+                                    okp_window_push_views, okp_refine_pose_views_wide, OKP_REFINE_WIDE_MAX_VIEWS (a rig's tracked objects refined
+                                    against a sliding window of ticks x cameras) */
 
 /* OKP_F16: IEEE half activations / weights, fp32 accumulate (BASELINE configs[4]).
  * OKP_F32X3 (okp_conv plans only): fp32 activations, weights and results like OKP_F32 - every tensor argument of such a plan is an
@@ -1037,7 +1039,8 @@ int okp_refine_pose_views_robust(const double* obs_dev, const double* views_dev,
  * Limits.  Static objects only: the window does not model motion, max_speed is a guard, not a model.  No robust loss and uniform weights
  * in okp_refine_pose_views_each: there one wrong peak in one tick pulls the pose.  okp_refine_pose_views_robust (views_each = 1) on the same
  * state bounds that pull with a Huber loss; it does not remove it, and its weights still do not use the peaks' confidences.  The error of the camera poses goes straight into the result: the
- * refinement takes T_WC as exact.  The window of a rig (2 P cameras x W ticks) would exceed OKP_REFINE_MAX_VIEWS: it is not offered.
+ * refinement takes T_WC as exact.  The window of a rig (2 P cameras x W ticks) exceeds OKP_REFINE_MAX_VIEWS: okp_window_push_views and
+ * okp_refine_pose_views_wide, below, are its ring and its refinement.
  * Refused on the host before any launch (OKP_EINVAL, the message names the argument): W outside [1, OKP_REFINE_MAX_VIEWS], T outside
  * [1, OKP_TRACK_MAX_TRACKS], S outside [1, OKP_POSE_MAX_POINTS], B or max_obj < 1, min_views outside [1, W], max_speed not positive (NaN
  * included), cam->fx or cam->fy not positive and finite, a null pointer.
@@ -1046,6 +1049,74 @@ int okp_window_push(const double* tab_dev, const int32_t* assignment_dev, const 
                     const int32_t* track_i_dev, const double* track_f_dev, const double* track_pose_dev, const double* T_WC_dev,
                     const okp_camera* cam, int32_t B, int32_t max_obj, int32_t S, int32_t T, int32_t W, int32_t min_views, double max_speed,
                     double* win_obs_dev, double* win_views_dev, int32_t* win_i_dev, int32_t* n_views_dev, double* start_dev, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * The sliding window of a rig: ticks x cameras (csrc/okp_window_views.hip, csrc/okp_refine_views_wide.hip).  A rig tick brings V = 2 P
+ * viewpoints instead of one, and the rig's motion widens a baseline that is otherwise the stereo pairs' 0.1 m.  okp_window_push_views keeps,
+ * per track slot, the last W ticks' bearings in every camera with every camera's camera-from-world view: W x V views, up to
+ * OKP_REFINE_WIDE_MAX_VIEWS.  okp_refine_pose_views_wide refines the track's world pose against them (obs = win_obs, views = win_views,
+ * views_each = 1, pose = start, an identity assignment, n_obj = T, V = W x V).  There is no reference implementation: the specification is
+ * this comment (tests/window_views_spec.py restates the push in NumPy, and the device agrees with it BIT FOR BIT).
+ *
+ * okp_window_push_views: okp_window_push for a table of bearings per camera.  One launch, one workgroup per (stream, track slot), fp64, no
+ * atomics, no host wait, capturable; the same bits on every run.
+ * State, in device memory, updated in place, kept across calls (and graph replays) like the tracker's:
+ *   win_obs [B][T][S][W*V][2] fp64   the bearing of MODEL ROW r in view c V + v: camera v in the tick of ring column c; (NaN, NaN) = none
+ *   win_views [B][T][W*V][14] fp64   view c V + v: [R | t] row-major 3 x 4 taking WORLD coordinates to camera v at that tick, then fx_v,
+ *                                    fy_v; zeros when empty
+ *   win_i [B][T][4] int32            owner id, head (the column the next push writes), filled (columns), one spare kept 0
+ *   The empty state is all-NaN win_obs with zero win_views and win_i.
+ * Inputs, all in device memory: obs [B][max_obj][S][V][2] fp64, the bearings by TABLE SLOT (okp_rig_bearings; a rig has B = 1);
+ *   assignment, status, meas_of, track_i, track_f, track_pose as okp_window_push takes them; T_WB [B][12] fp64, the rig's pose in the world
+ *   (okp_change_frame's T); views [V][14] fp64, camera-from-rig then fx, fy (okp_refine_pose_views' table: the caller validates it).
+ *   Host: B, max_obj, S, T, W, V, min_views, max_speed.
+ * Per slot i of stream b: steps 1 - 3 of okp_window_push word for word (owner, head and filled; the ring emptied on a free slot, a new id,
+ *   an inconsistent state or a speed above max_speed; "empty the ring" is NaN to every word of win_obs[b][i] and 0 to every word of
+ *   win_views[b][i]).  Then
+ *   4. Push, only when o = meas_of[b][i] is in [0, max_obj), status[b][o] == 0 and all 12 values of T_WB[b] are finite; the column is
+ *      c = head: the views c V .. c V + V - 1.  First every model row's V entries of the column become (NaN, NaN).  Then, over the slots s
+ *      of obs[b][o] in ASCENDING order: the slot counts when a = assignment[b][o][s] is in [0, S); then win_obs[b][i][a][c V + v] =
+ *      obs[b][o][s][v] for all v, copied bit for bit, NaNs included; of two slots with the same a the later one replaces the WHOLE row.
+ *      The view rows are camera-from-world.  First rig-from-world [R' | t'], the inverse of T_WB[b] = T (12 values, row-major 3 x 4) as
+ *      okp_window_push forms it: R'[i][j] = T[4j+i], t'[i] = (T[i]*d0 + T[4+i]*d1) + T[8+i]*d2 with d = -t.  Then, with [Rv | tv] camera v's
+ *      row of `views`:  R[i][j] = (Rv[i][0]*R'[0][j] + Rv[i][1]*R'[1][j]) + Rv[i][2]*R'[2][j],
+ *      t[i] = ((Rv[i][0]*t'[0] + Rv[i][1]*t'[1]) + Rv[i][2]*t'[2]) + tv[i] (no contraction); fx_v and fy_v are copied.
+ *      head = (head + 1) mod W, filled = min(filled + 1, W).
+ *   Every word of the state is written at most once per call.
+ * Outputs, all written by every call: n_views [B][T] int32 = filled (TICKS, not views); start [B][T][12] fp64 = track_pose[b][i] bit for bit
+ *   when filled >= min_views, otherwise NaN.
+ * Limits.  Those of okp_window_push: static objects only; the error of T_WB - and here of the rig's calibration in `views` - goes straight into
+ * the result; uniform weights unless the refinement is given a huber_px.
+ * Refused on the host before any launch (OKP_EINVAL, the message names the argument): V outside [1, 2 * OKP_RIG_MAX_PAIRS], W outside
+ * [1, OKP_REFINE_MAX_VIEWS], W * V > OKP_REFINE_WIDE_MAX_VIEWS, T outside [1, OKP_TRACK_MAX_TRACKS], S outside [1, OKP_POSE_MAX_POINTS], B or
+ * max_obj < 1, min_views outside [1, W], max_speed not positive (NaN included), a null pointer.
+ *
+ * okp_refine_pose_views_wide: the refinement against a table of views beyond one wave: V in [1, OKP_REFINE_WIDE_MAX_VIEWS].  One launch,
+ * one WORKGROUP of ceil(V / 64) waves per object; lane l of wave w is view 64 w + l.  fp64, no atomics, no host wait, capturable; the same
+ * bits on every run.
+ *   huber_px == 0: the cost, step, statuses, outputs and refusals of okp_refine_pose_views (views_each = 0) / okp_refine_pose_views_each
+ *     (views_each = 1): fit is [B][max_obj][2], n_inlier and weight are not written and may be null.
+ *   huber_px > 0: those of okp_refine_pose_views_robust: fit is [B][max_obj][4], n_inlier and weight are required.
+ *   Order of the sums (not part of the contract, as there): a lane adds the terms of its view over its slots in ascending order, a butterfly
+ *   adds the 64 lanes of a wave, and every lane adds the waves' sums in ascending wave order starting from wave 0's.  With one wave that is
+ *   the one-wave kernels' order at 64 lanes per group: for 32 < V <= 64 the outputs are BIT FOR BIT those of okp_refine_pose_views /
+ *   okp_refine_pose_views_each / okp_refine_pose_views_robust.  The slots with an observation are counted once however many waves see them.
+ *   A view none of whose S entries is filled contributes nothing, whatever its row holds.
+ * Refused on the host before any launch (OKP_EINVAL, the message names the argument): everything okp_refine_pose_views refuses, with V
+ * outside [1, OKP_REFINE_WIDE_MAX_VIEWS]; huber_px negative, NaN or infinite; views_each outside {0, 1}; with huber_px > 0 a null n_inlier or
+ * weight.
+ * ---------------------------------------------------------------------------------- */
+#define OKP_REFINE_WIDE_MAX_VIEWS 512
+int okp_window_push_views(const double* obs_dev, const int32_t* assignment_dev, const int32_t* status_dev, const int32_t* meas_of_dev,
+                          const int32_t* track_i_dev, const double* track_f_dev, const double* track_pose_dev, const double* T_WB_dev,
+                          const double* views_dev, int32_t B, int32_t max_obj, int32_t S, int32_t T, int32_t W, int32_t V, int32_t min_views,
+                          double max_speed, double* win_obs_dev, double* win_views_dev, int32_t* win_i_dev, int32_t* n_views_dev,
+                          double* start_dev, void* stream);
+int okp_refine_pose_views_wide(const double* obs_dev, const double* views_dev, int32_t views_each, const double* pose_dev,
+                               const int32_t* assignment_dev, const int32_t* n_obj_dev, const double* model_dev, double sigma_px,
+                               double huber_px, int32_t iters, double damping, int32_t B, int32_t max_obj, int32_t S, int32_t V,
+                               double* pose_out_dev, double* fit_dev /* [2], or [4] with huber_px > 0 */, int32_t* n_obs_dev,
+                               int32_t* n_inlier_dev, double* weight_dev, double* information_dev, int32_t* status_dev, void* stream);
 
 /* Undistort only (FisheyeCamera.undistort, camera_utils.py:75-81 / RadTanPinholeCamera.undistort, :57-62, by cam->model):
  * xy [m][2] fp32 -> out [m][2] fp64.  okp_fisheye_undistort is the same entry point under its round-1 name. */

@@ -412,6 +412,25 @@ def window_push(camera, tab, assignment, status, meas_of, track_i, track_f, trac
                                           win_obs.data_ptr(), win_views.data_ptr(), win_i.data_ptr(), n_views.data_ptr(), start.data_ptr(), stream), "okp_window_push")
 
 
+# ---- the sliding window of a rig (csrc/okp_window_views.hip, csrc/okp_refine_views_wide.hip): win_obs [B,T,S,W*V,2], win_views [B,T,W*V,14] --------
+def window_push_views(obs, assignment, status, meas_of, track_i, track_f, track_pose, T_WB, views, ticks, min_views, max_speed, win_obs, win_views, win_i, n_views,
+                      start, stream):
+    b, max_obj, s, v, _ = obs.shape
+    _lib.check(_lib.lib().okp_window_push_views(obs.data_ptr(), assignment.data_ptr(), status.data_ptr(), meas_of.data_ptr(), track_i.data_ptr(), track_f.data_ptr(),
+                                                track_pose.data_ptr(), T_WB.data_ptr(), views.data_ptr(), b, max_obj, s, win_obs.shape[1], ticks, v, min_views, max_speed,
+                                                win_obs.data_ptr(), win_views.data_ptr(), win_i.data_ptr(), n_views.data_ptr(), start.data_ptr(), stream),
+               "okp_window_push_views")
+
+
+def refine_pose_views_wide(obs, views, views_each, pose, assignment, n_obj, model, sigma_px, huber_px, iters, damping, pose_out, fit, n_obs, n_inlier, weight,
+                           information, status, stream):
+    b, max_obj, s, v, _ = obs.shape
+    _lib.check(_lib.lib().okp_refine_pose_views_wide(obs.data_ptr(), views.data_ptr(), views_each, pose.data_ptr(), assignment.data_ptr(), n_obj.data_ptr(),
+                                                     model.data_ptr(), sigma_px, huber_px, iters, damping, b, max_obj, s, v, pose_out.data_ptr(), fit.data_ptr(),
+                                                     n_obs.data_ptr(), _ptr(n_inlier), _ptr(weight), information.data_ptr(), status.data_ptr(), stream),
+               "okp_refine_pose_views_wide")
+
+
 # ---- scoring labelled scenes -----------------------------------------------------------------------------------------------------------------
 def project_labels(camera, world_points, T_WC, scale, crop_x, crop_y, labels, stream):
     _lib.check(_lib.lib().okp_project_labels(_camera(camera), world_points.data_ptr(), world_points.shape[0], T_WC.data_ptr(), T_WC.shape[0], scale, crop_x, crop_y,

@@ -1,7 +1,8 @@
 // The arithmetic the object pose stages share (csrc/okp_pose.hip, csrc/okp_refine.hip, csrc/okp_refine_assign.hip; contracts in
 // include/okp.h): the slot layout of an object model, Horn's closed-form rigid fit with cyclic Jacobi, the degeneracy rule, and the pieces of
 // one Gauss-Newton step of the refinement - a lane's residuals and Jacobian rows, the sixteen-lane butterfly, the 6 x 6 Cholesky solve and
-// the update by C(w).
+// the update by C(w) - and, for the refinements against a table of views (csrc/okp_refine_views.hip, csrc/okp_refine_views_wide.hip), the terms of
+// one (slot, view) entry and the Huber weight.
 //
 // Floating-point contraction.  The pose functions (first half) are compiled under the including file's setting at the point of inclusion:
 // okp_pose.hip includes this header under the compiler's default and keeps its bits.  The refinement functions (second half) turn
@@ -248,6 +249,30 @@ __device__ __forceinline__ bool refine_step(const double (&acc)[OKP_REFINE_SUMS]
   t[0] += d[3]; t[1] += d[4]; t[2] += d[5];
   return singular;
 }
+
+// ---- the refinements against a table of views (csrc/okp_refine_views.hip, csrc/okp_refine_views_wide.hip) ----
+
+// One (slot, view) entry at the iterate (R, t): p = R m, the gradients b_u, b_v in the table's frame, the residual e and q_z.  The iteration
+// and the pass that writes the weights both call it, so a weight is the bits the final iterate's sums were made with.
+struct ViewTerm { double p0, p1, p2, bu0, bu1, bu2, bv0, bv1, bv2, e0, e1, qz; };
+__device__ __forceinline__ ViewTerm view_term(const double (&R)[9], const double (&t)[3], const double (&rv)[9], const double (&tv)[3], double kx, double ky,
+                                              double m0, double m1, double m2, double u, double v) {
+#pragma clang fp contract(off)
+  ViewTerm o;
+  o.p0 = (R[0] * m0 + R[1] * m1) + R[2] * m2; o.p1 = (R[3] * m0 + R[4] * m1) + R[5] * m2; o.p2 = (R[6] * m0 + R[7] * m1) + R[8] * m2;
+  const double X0 = o.p0 + t[0], X1 = o.p1 + t[1], X2 = o.p2 + t[2];
+  const double q0 = ((rv[0] * X0 + rv[1] * X1) + rv[2] * X2) + tv[0], q1 = ((rv[3] * X0 + rv[4] * X1) + rv[5] * X2) + tv[1];
+  o.qz = ((rv[6] * X0 + rv[7] * X1) + rv[8] * X2) + tv[2];
+  const double iz = 1.0 / o.qz, xn = q0 * iz, yn = q1 * iz;
+  const double au0 = kx * iz, au2 = -(au0 * xn), av1 = ky * iz, av2 = -(av1 * yn);
+  o.bu0 = rv[0] * au0 + rv[6] * au2; o.bu1 = rv[1] * au0 + rv[7] * au2; o.bu2 = rv[2] * au0 + rv[8] * au2;
+  o.bv0 = rv[3] * av1 + rv[6] * av2; o.bv1 = rv[4] * av1 + rv[7] * av2; o.bv2 = rv[5] * av1 + rv[8] * av2;
+  o.e0 = kx * (xn - u); o.e1 = ky * (yn - v);
+  return o;
+}
+
+// the Huber weight of a squared residual s: 1 inside the threshold, c / sqrt(s) outside (NaN for a NaN s)
+__device__ __forceinline__ double huber_weight(double s, double c, double c2) { return s <= c2 ? 1.0 : c / sqrt(s); }
 
 }  // namespace
 #endif  // OKP_POSE_MATH_H

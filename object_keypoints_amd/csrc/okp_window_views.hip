@@ -1,0 +1,147 @@
+// The sliding window of a rig (okp_window_push_views; contract in include/okp.h): okp_window_push (csrc/okp_window.hip) for a table of
+// bearings per camera.  A rig tick brings V = 2 P viewpoints instead of one, and the rig's motion widens a baseline that is otherwise the
+// stereo pairs'; this launch keeps, per track slot, a ring of the last W ticks' bearings in all V cameras (by MODEL ROW) and the cameras'
+// camera-from-world views.  Column c of the ring is the views c V .. c V + V - 1; okp_refine_pose_views_wide then refines the track pose
+// against the W V views.
+//
+//   okp_window_push_views_kernel   one workgroup of 256 per (stream, track slot).  Every thread takes the slot's few control words (id, owner,
+//                                  head, filled, the velocity, the measurement and its status, the rig pose) - the same addresses for all -
+//                                  and decides the same thing.  Threads 0 .. S - 1 find, each for its model row, the LAST table slot assigned
+//                                  to it (ascending slots, a later one replaces the whole row) and leave it in LDS; after the one barrier -
+//                                  which every thread reaches, under no branch - one pass over the ring: an element is the new column's
+//                                  (copied from the table of bearings, NaNs included, or composed from the rig pose and the camera's row of
+//                                  `views`), or NaN / 0 when the ring is emptied, or left alone - so no word is written twice.
+// fp64, no atomics, no host wait, contraction off; the same bits on every run and as tests/window_views_spec.py.
+#include "okp_pose_math.h"           // finite64
+
+#pragma clang fp contract(off)
+
+namespace {
+
+#define OKP_WINDOW_VIEWS_THREADS 256
+
+struct WindowViewsParams {
+  const double* obs; const int32_t* assignment; const int32_t* status; const int32_t* meas_of; const int32_t* track_i; const double* track_f;
+  const double* track_pose; const double* T_WB; const double* views;
+  double max_speed2;
+  int32_t max_obj, S, T, W, V, min_views;
+  double* win_obs; double* win_views; int32_t* win_i; int32_t* n_views; double* start;
+};
+
+__global__ __launch_bounds__(OKP_WINDOW_VIEWS_THREADS) void okp_window_push_views_kernel(const WindowViewsParams P) {
+  __shared__ int32_t slot_of[OKP_POSE_MAX_POINTS];                // the table slot whose bearings model row r takes, or -1
+  const int tid = threadIdx.x;
+  const size_t bi = blockIdx.x;                                   // b * T + i
+  const size_t b = bi / P.T;
+  const int S = P.S, W = P.W, V = P.V, WV = W * V;
+  const double nan = __builtin_nan("");
+  int32_t* wi = P.win_i + bi * 4;
+
+  // 1 - 3: whose ring this is, and whether it is emptied (workgroup-uniform: every thread reads the same words)
+  const int id = P.track_i[bi * 4];
+  int owner = wi[0], head = wi[1], filled = wi[2];
+  bool clear = false, push = false;
+  int o = -1;
+  if (id == 0) {
+    clear = true; owner = 0; head = 0; filled = 0;
+  } else {
+    if (id != owner || head < 0 || head >= W || filled < 0 || filled > W) { clear = true; owner = id; head = 0; filled = 0; }
+    const double* f = P.track_f + bi * 16;
+    const double vx = f[3], vy = f[4], vz = f[5];
+    if ((vx * vx + vy * vy) + vz * vz > P.max_speed2) { clear = true; head = 0; filled = 0; }
+    // 4: is there a column to push
+    o = P.meas_of[bi];
+    if (o >= 0 && o < P.max_obj && P.status[b * P.max_obj + o] == 0) {
+      push = true;
+#pragma unroll
+      for (int k = 0; k < 12; ++k) push = push && finite64(P.T_WB[b * 12 + k]);
+    }
+  }
+
+  if (tid < OKP_POSE_MAX_POINTS) {
+    int src = -1;
+    if (push && tid < S) {
+      const int32_t* as = P.assignment + (b * P.max_obj + o) * S;
+      for (int s = 0; s < S; ++s) src = as[s] == tid ? s : src;   // ascending slots: a later slot with the same model row wins
+    }
+    slot_of[tid] = src;
+  }
+  __syncthreads();                                                // (the only barrier: under no branch; win_i is read above, written below)
+
+  // the ring: every element is the new column's, or emptied, or kept - written at most once
+  double* ring = P.win_obs + bi * (size_t)S * WV * 2;
+  const double* tab = P.obs + (b * P.max_obj + (size_t)(push ? o : 0)) * S * V * 2;
+  for (int e = tid; e < S * WV; e += OKP_WINDOW_VIEWS_THREADS) {
+    const int r = e / WV, cv = e - r * WV, c = cv / V, v = cv - c * V;
+    if (push && c == head) {
+      const int src = slot_of[r];
+      double x = nan, y = nan;
+      if (src >= 0) { x = tab[((size_t)src * V + v) * 2]; y = tab[((size_t)src * V + v) * 2 + 1]; }
+      ring[2 * (size_t)e] = x; ring[2 * (size_t)e + 1] = y;
+    } else if (clear) { ring[2 * (size_t)e] = nan; ring[2 * (size_t)e + 1] = nan; }
+  }
+  double* vw = P.win_views + bi * (size_t)WV * 14;
+  for (int e = tid; e < WV * 14; e += OKP_WINDOW_VIEWS_THREADS) {
+    const int cv = e / 14, k = e - cv * 14, c = cv / V, v = cv - c * V;
+    if (push && c == head) {                                      // camera-from-world: the camera's row of `views` composed with rig-from-world
+      const double* Tb = P.T_WB + b * 12;
+      const double* row = P.views + (size_t)v * 14;
+      double x = row[k];                                          // (fx, fy: copied)
+      if (k < 12) {
+        const int i = k >> 2, j = k & 3;
+        const double r0 = row[4 * i], r1 = row[4 * i + 1], r2 = row[4 * i + 2];
+        if (j < 3) x = (r0 * Tb[4 * j] + r1 * Tb[4 * j + 1]) + r2 * Tb[4 * j + 2];            // R'[q][j] = T[4 j + q]
+        else {
+          const double d0 = -Tb[3], d1 = -Tb[7], d2 = -Tb[11];
+          const double t0 = (Tb[0] * d0 + Tb[4] * d1) + Tb[8] * d2, t1 = (Tb[1] * d0 + Tb[5] * d1) + Tb[9] * d2, t2 = (Tb[2] * d0 + Tb[6] * d1) + Tb[10] * d2;
+          x = ((r0 * t0 + r1 * t1) + r2 * t2) + row[4 * i + 3];
+        }
+      }
+      vw[e] = x;
+    } else if (clear) vw[e] = 0.0;
+  }
+  if (push) { head = head + 1 == W ? 0 : head + 1; filled = filled < W ? filled + 1 : W; }
+
+  if (tid == 0) { wi[0] = owner; wi[1] = head; wi[2] = filled; wi[3] = 0; P.n_views[bi] = filled; }
+  if (tid < 12) {                                                 // the start of the refinement: the track pose bit for bit, or NaN
+    const unsigned long long bits = reinterpret_cast<const unsigned long long*>(P.track_pose)[bi * 12 + tid];
+    if (filled >= P.min_views) reinterpret_cast<unsigned long long*>(P.start)[bi * 12 + tid] = bits;
+    else P.start[bi * 12 + tid] = nan;
+  }
+}
+
+}  // namespace
+
+extern "C" int okp_window_push_views(const double* obs, const int32_t* assignment, const int32_t* status, const int32_t* meas_of, const int32_t* track_i,
+                                     const double* track_f, const double* track_pose, const double* T_WB, const double* views, int32_t B, int32_t max_obj,
+                                     int32_t S, int32_t T, int32_t W, int32_t V, int32_t min_views, double max_speed, double* win_obs, double* win_views,
+                                     int32_t* win_i, int32_t* n_views, double* start, void* stream) {
+  const char* fn = "okp_window_push_views";
+  if (B < 1) { okp_set_error("%s: B = %d; at least one stream", fn, B); return OKP_EINVAL; }
+  if (max_obj < 1) { okp_set_error("%s: max_obj = %d; a stream holds at least one object", fn, max_obj); return OKP_EINVAL; }
+  if (S < 1 || S > OKP_POSE_MAX_POINTS) { okp_set_error("%s: S = %d outside [1, %d] model points", fn, S, OKP_POSE_MAX_POINTS); return OKP_EINVAL; }
+  if (T < 1 || T > OKP_TRACK_MAX_TRACKS) { okp_set_error("%s: T = %d outside [1, %d] track slots", fn, T, OKP_TRACK_MAX_TRACKS); return OKP_EINVAL; }
+  if (V < 1 || V > 2 * OKP_RIG_MAX_PAIRS) { okp_set_error("%s: V = %d outside [1, %d] cameras", fn, V, 2 * OKP_RIG_MAX_PAIRS); return OKP_EINVAL; }
+  if (W < 1 || W > OKP_REFINE_MAX_VIEWS) { okp_set_error("%s: W = %d outside [1, %d] ticks", fn, W, OKP_REFINE_MAX_VIEWS); return OKP_EINVAL; }
+  if (W * V > OKP_REFINE_WIDE_MAX_VIEWS) {
+    okp_set_error("%s: W * V = %d x %d = %d views exceed the %d of okp_refine_pose_views_wide", fn, W, V, W * V, OKP_REFINE_WIDE_MAX_VIEWS);
+    return OKP_EINVAL;
+  }
+  if (min_views < 1 || min_views > W) { okp_set_error("%s: min_views = %d outside [1, W = %d]", fn, min_views, W); return OKP_EINVAL; }
+  if (!(max_speed > 0.0)) { okp_set_error("%s: max_speed = %g must be positive (metres per second; +inf: never reset)", fn, max_speed); return OKP_EINVAL; }
+  if ((long long)B * T > 0x7fffffffll) { okp_set_error("%s: B * T = %lld track slots do not fit one launch", fn, (long long)B * T); return OKP_EINVAL; }
+  const struct { const void* ptr; const char* name; } required[] = {
+      {obs, "obs"}, {assignment, "assignment"}, {status, "status"}, {meas_of, "meas_of"}, {track_i, "track_i"}, {track_f, "track_f"},
+      {track_pose, "track_pose"}, {T_WB, "T_WB"}, {views, "views"}, {win_obs, "win_obs"}, {win_views, "win_views"}, {win_i, "win_i"},
+      {n_views, "n_views"}, {start, "start"}};
+  for (const auto& r : required)
+    if (!r.ptr) { okp_set_error("%s: null %s", fn, r.name); return OKP_EINVAL; }
+  WindowViewsParams p = {};
+  p.obs = obs; p.assignment = assignment; p.status = status; p.meas_of = meas_of; p.track_i = track_i; p.track_f = track_f;
+  p.track_pose = track_pose; p.T_WB = T_WB; p.views = views;
+  p.max_speed2 = max_speed * max_speed;
+  p.max_obj = max_obj; p.S = S; p.T = T; p.W = W; p.V = V; p.min_views = min_views;
+  p.win_obs = win_obs; p.win_views = win_views; p.win_i = win_i; p.n_views = n_views; p.start = start;
+  hipLaunchKernelGGL(okp_window_push_views_kernel, dim3((unsigned)((size_t)B * T)), dim3(OKP_WINDOW_VIEWS_THREADS), 0, (hipStream_t)stream, p);
+  return okp_check_hip(hipGetLastError(), "okp_window_push_views launch");
+}

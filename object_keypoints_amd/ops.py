@@ -1840,6 +1840,132 @@ def window_push(state, tab, assignment, status, track, T_WC, cam, cfg):
     return {"n_views": n_views, "start": start}
 
 
+# ---- a rig's tracked objects refined against a sliding window of ticks x cameras (okp_window_push_views, okp_refine_pose_views_wide) ----------------
+REFINE_WIDE_MAX_VIEWS = 512                                                      # include/okp.h OKP_REFINE_WIDE_MAX_VIEWS
+
+
+def window_views_state(B, max_tracks, S, ticks, n_views, device):
+    """An empty window of B streams x max_tracks slots x S model rows x ticks columns of n_views cameras each: {"win_obs" [B,T,S,W*V,2]
+    float64, all NaN, "win_views" [B,T,W*V,14] float64 and "win_i" [B,T,4] int32 (owner id, head, filled, one spare), zeros} on `device` -
+    window_push_views() steps it in place - plus what the refinement of the window reads next to it on every call: "win_assignment" [B,T,S]
+    int32, the identity, and "win_n" [B] int32 filled with T."""
+    B, T, S, W, V = int(B), int(max_tracks), int(S), int(ticks), int(n_views)
+    if B < 1 or not 1 <= T <= TRACK_MAX_TRACKS or not 1 <= S <= POSE_MAX_POINTS or not 1 <= W <= REFINE_MAX_VIEWS or not 1 <= V <= 2 * RIG_MAX_PAIRS:
+        raise OkpError(f"window_views_state: B = {B} streams (at least 1) of max_tracks = {T} slots (1 .. {TRACK_MAX_TRACKS}), S = {S} model rows (1 .. {POSE_MAX_POINTS}), "
+                       f"ticks = {W} (1 .. {REFINE_MAX_VIEWS}), n_views = {V} cameras (1 .. {2 * RIG_MAX_PAIRS})")
+    if W * V > REFINE_WIDE_MAX_VIEWS:
+        raise OkpError(f"window_views_state: ticks x n_views = {W} x {V} = {W * V} views exceed the {REFINE_WIDE_MAX_VIEWS} of okp_refine_pose_views_wide")
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise OkpError("window_views_state: the window's state lives in device memory: the HIP path has no CPU fallback")
+    return {"win_obs": torch.full((B, T, S, W * V, 2), float("nan"), dtype=torch.float64, device=device),
+            "win_views": torch.zeros((B, T, W * V, 14), dtype=torch.float64, device=device), "win_i": torch.zeros((B, T, 4), dtype=torch.int32, device=device),
+            "win_assignment": torch.arange(S, dtype=torch.int32, device=device).repeat(B, T, 1).contiguous(),
+            "win_n": torch.full((B,), T, dtype=torch.int32, device=device)}
+
+
+def window_push_views(state, obs, assignment, status, track, T_WB, views, cfg):
+    """One tick of a rig's sliding window (okp_window_push_views; the ring, its resets and the push are specified in include/okp.h).  state:
+    window_views_state(...), stepped in place; obs [B,max_obj,S,V,2] float64: the tick's bearings by table slot (rig_bearings; a rig has
+    B = 1); assignment [B,max_obj,S] int32 and status [B,max_obj] int32, the pose stage's; track: the dict of this tick's track_objects()
+    plus its state (its "meas_of", "track_i", "track_f" and "track_pose" are read: world frame); T_WB [B,12] float64 (device), this tick's
+    rig pose; views [V,14] float64 (device): rig_views(...) moved to the device; cfg: a WindowConfig, whose ticks x V may not exceed
+    REFINE_WIDE_MAX_VIEWS
+    -> {"n_views" [B,T] int32 (filled columns: ticks), "start" [B,T,12] float64 (the track pose bit for bit from cfg.min_views columns on,
+        otherwise NaN)}.  One launch, no host sync."""
+    if not isinstance(cfg, WindowConfig):
+        raise OkpError("cfg must be an ops.WindowConfig")
+    try:
+        meas_of, track_i, track_f, track_pose = track["meas_of"], track["track_i"], track["track_f"], track["track_pose"]
+    except (TypeError, KeyError, IndexError):
+        raise OkpError("track must be the dict of ops.track_objects with the tracker's state (its \"meas_of\", \"track_i\", \"track_f\" and \"track_pose\")") from None
+    try:
+        win_obs, win_views, win_i = state["win_obs"], state["win_views"], state["win_i"]
+    except (TypeError, KeyError, IndexError):
+        raise OkpError("state must be the dict of ops.window_views_state") from None
+    for name, t in (("obs", obs), ("assignment", assignment), ("status", status), ("meas_of", meas_of), ("track_i", track_i), ("track_f", track_f),
+                    ("track_pose", track_pose), ("T_WB", T_WB), ("views", views), ("win_obs", win_obs), ("win_views", win_views), ("win_i", win_i)):
+        require_cuda(t, name)
+    if obs.dtype != torch.float64 or obs.dim() != 5 or obs.shape[4] != 2:
+        raise OkpError("obs must be float64 [B,max_obj,S,V,2] (rig_bearings)")
+    b, max_obj, s, v = (int(x) for x in obs.shape[:4])
+    dev = obs.device
+    w = cfg.ticks
+    if not 1 <= s <= POSE_MAX_POINTS or not 1 <= v <= 2 * RIG_MAX_PAIRS:
+        raise OkpError(f"obs [{b},{max_obj},{s},{v},2]: at most {POSE_MAX_POINTS} model points and {2 * RIG_MAX_PAIRS} cameras")
+    if w * v > REFINE_WIDE_MAX_VIEWS:
+        raise OkpError(f"cfg.ticks x V = {w} x {v} = {w * v} views exceed the {REFINE_WIDE_MAX_VIEWS} of okp_refine_pose_views_wide")
+    if assignment.dtype != torch.int32 or tuple(assignment.shape) != (b, max_obj, s) or status.dtype != torch.int32 or tuple(status.shape) != (b, max_obj) or \
+            assignment.device != dev or status.device != dev:
+        raise OkpError(f"assignment must be int32 [{b},{max_obj},{s}] and status int32 [{b},{max_obj}] on the bearings' device (object_pose)")
+    if track_i.dtype != torch.int32 or track_i.dim() != 3 or track_i.shape[0] != b or track_i.shape[2] != 4 or not 1 <= track_i.shape[1] <= TRACK_MAX_TRACKS:
+        raise OkpError(f"track_i must be int32 [{b},T,4] with T in [1, {TRACK_MAX_TRACKS}] (track_state)")
+    t = int(track_i.shape[1])
+    for name, x, dtype, shape in (("meas_of", meas_of, torch.int32, (b, t)), ("track_f", track_f, torch.float64, (b, t, 16)), ("track_pose", track_pose, torch.float64, (b, t, 12)),
+                                  ("T_WB", T_WB, torch.float64, (b, 12)), ("views", views, torch.float64, (v, 14))):
+        if x.dtype != dtype or tuple(x.shape) != shape or x.device != dev:
+            raise OkpError(f"{name} must be a {dtype} tensor {list(shape)} on the bearings' device")
+    if track_i.device != dev:
+        raise OkpError(f"track_i is on {track_i.device}, the bearings on {dev}")
+    for name, x, dtype, shape in (("win_obs", win_obs, torch.float64, (b, t, s, w * v, 2)), ("win_views", win_views, torch.float64, (b, t, w * v, 14)),
+                                  ("win_i", win_i, torch.int32, (b, t, 4))):
+        if x.dtype != dtype or tuple(x.shape) != shape or x.device != dev or not x.is_contiguous():
+            raise OkpError(f"state[{name!r}] must be a contiguous {dtype} tensor {list(shape)} on the bearings' device: "
+                           f"window_views_state({b}, {t}, {s}, cfg.ticks = {w}, {v}, device)")
+    n_views = torch.empty((b, t), dtype=torch.int32, device=dev)
+    start = torch.empty((b, t, 12), dtype=torch.float64, device=dev)
+    _dispatch(_ops().window_push_views, obs.contiguous(), assignment.contiguous(), status.contiguous(), meas_of.contiguous(), track_i.contiguous(), track_f.contiguous(),
+              track_pose.contiguous(), T_WB.contiguous(), views.contiguous(), w, cfg.min_views, cfg.max_speed, win_obs, win_views, win_i, n_views, start, stream_int())
+    return {"n_views": n_views, "start": start}
+
+
+def refine_pose_views_wide(obs, views, pose, n_obj, model, cfg, each=False):
+    """refine_pose_views (each=False: views [V,14]) or refine_pose_views_each (each=True: views [B,max_obj,V,14]) for up to
+    REFINE_WIDE_MAX_VIEWS views (okp_refine_pose_views_wide: one workgroup of ceil(V / 64) waves per object).  The other arguments, the cost,
+    the statuses and the returned dict are theirs; cfg: a RefineConfig or a WindowConfig, whose huber_px selects the Huber instance as it
+    does there ("fit" with four values, "n_inlier", "weight").  For 32 < V <= 64 the result has the bits of those entry points.  One launch,
+    no host sync."""
+    if not isinstance(cfg, (RefineConfig, WindowConfig)):
+        raise OkpError("cfg must be an ops.RefineConfig or an ops.WindowConfig")
+    if not isinstance(each, (bool, np.bool_)):
+        raise OkpError(f"each = {each!r} must be True (one views table per object) or False (one for all)")
+    try:
+        fitted, assignment = pose["pose"], pose["assignment"]
+    except (TypeError, KeyError, IndexError):
+        raise OkpError("pose must be the dict of ops.object_pose (its \"pose\" and \"assignment\")") from None
+    for name, t in (("obs", obs), ("views", views), ("pose", fitted), ("assignment", assignment), ("n_obj", n_obj), ("model", model)):
+        require_cuda(t, name)
+    if obs.dtype != torch.float64 or obs.dim() != 5 or obs.shape[4] != 2:
+        raise OkpError("obs must be float64 [B,max_obj,S,V,2] (rig_bearings, or the win_obs of window_views_state)")
+    b, max_obj, s, v = (int(x) for x in obs.shape[:4])
+    dev = obs.device
+    if b < 1 or max_obj < 1 or not 1 <= s <= POSE_MAX_POINTS or not 1 <= v <= REFINE_WIDE_MAX_VIEWS:
+        raise OkpError(f"obs [{b},{max_obj},{s},{v},2]: at least one frame and object, at most {POSE_MAX_POINTS} model points and {REFINE_WIDE_MAX_VIEWS} views")
+    if each and (views.dtype != torch.float64 or tuple(views.shape) != (b, max_obj, v, 14) or views.device != dev):
+        raise OkpError(f"views must be float64 [{b},{max_obj},{v},14] on the bearings' device: one table of {v} rows for each object of obs")
+    if not each and (views.dtype != torch.float64 or tuple(views.shape) != (v, 14) or views.device != dev):
+        raise OkpError(f"views must be float64 [{v},14] on the bearings' device: one row for each of the {v} views of obs")
+    if fitted.dtype != torch.float64 or tuple(fitted.shape) != (b, max_obj, 12) or assignment.dtype != torch.int32 or tuple(assignment.shape) != (b, max_obj, s) or \
+            fitted.device != dev or assignment.device != dev:
+        raise OkpError(f"pose must be float64 [{b},{max_obj},12] and assignment int32 [{b},{max_obj},{s}] on the bearings' device (object_pose)")
+    if n_obj.dtype != torch.int32 or n_obj.numel() != b or n_obj.device != dev:
+        raise OkpError(f"n_obj must be int32 [{b}] on the bearings' device: the objects of each frame")
+    if model.dtype != torch.float64 or tuple(model.shape) != (s, 3) or model.device != dev:
+        raise OkpError(f"model must be float64 [{s},3] on the bearings' device (object_model)")
+    huber_px = getattr(cfg, "huber_px", None)
+    out = {"pose": torch.empty((b, max_obj, 12), dtype=torch.float64, device=dev),
+           "fit": torch.empty((b, max_obj, 4 if huber_px is not None else 2), dtype=torch.float64, device=dev),
+           "n_obs": torch.empty((b, max_obj), dtype=torch.int32, device=dev), "information": torch.empty((b, max_obj, 36), dtype=torch.float64, device=dev),
+           "status": torch.empty((b, max_obj), dtype=torch.int32, device=dev)}
+    if huber_px is not None:
+        out["n_inlier"] = torch.empty((b, max_obj), dtype=torch.int32, device=dev)
+        out["weight"] = torch.empty((b, max_obj, s, v), dtype=torch.float64, device=dev)
+    _dispatch(_ops().refine_pose_views_wide, obs.contiguous(), views.contiguous(), 1 if each else 0, fitted.contiguous(), assignment.contiguous(),
+              n_obj.reshape(b).contiguous(), model.contiguous(), cfg.sigma_px, huber_px if huber_px is not None else 0.0, cfg.iters, cfg.damping, out["pose"], out["fit"],
+              out["n_obs"], out.get("n_inlier"), out.get("weight"), out["information"], out["status"], stream_int())
+    return out
+
+
 # ---- scoring labelled scenes (csrc/okp_targets.hip) ---------------------------------------------------------------------------------
 TARGET_SIZE = 64             # SceneDataset.prediction_size
 TARGET_MAX_MAPS = 16         # K

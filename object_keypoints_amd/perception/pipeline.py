@@ -601,7 +601,8 @@ def _track_fields(track, n, window=None):
     dict also "window_pose" and "window_pose_C" [T,12], "window_fit" [T,2], "window_n_views" [T], "window_information" [T,36], "window_status" [T]."""
     fields = {k: track[k][n] for k in ("track_pose", "track_f", "track_i", "track_of", "meas_of", "track_pose_C") if k in track}
     if window is not None:
-        fields.update({"window_" + k: window[k][n] for k in ("pose", "pose_C", "fit", "n_views", "information", "status")})
+        fields.update({"window_" + k: window[k][n] for k in ("pose", "fit", "n_views", "information", "status")})
+        fields["window_pose_C"] = window["pose_C" if "pose_C" in window else "pose_B"][n]       # (a rig's window: the rig frame, [T,S,W*V] weights)
         if "n_inlier" in window:                 # under a Huber loss (WindowConfig.huber_px): "window_fit" is [T,4], "window_weight" [T,S,W]
             fields.update(window_n_inlier=window["n_inlier"][n], window_weight=window["weight"][n])
     return fields
@@ -617,20 +618,23 @@ def _host_tracks(track, n, window=None):
     return _to_host(_track_fields(track, n, window))
 
 
-def _window_entries(rec, slot):
-    """A track slot's windowed pose as the entries tracks() adds: 'T_WO_window' and 'T_CO_window' (4 x 4; None where 'window_status' is not 0 -
+def _window_entries(rec, slot, key='T_CO_window', cameras=None):
+    """A track slot's windowed pose as the entries tracks() adds: 'T_WO_window' and `key`, 'T_CO_window' or a rig's 'T_BO_window' (4 x 4; None where 'window_status' is not 0 -
     a short window, a free slot, a refused refinement - or, for 'T_CO_window', the camera pose is missing: the caller falls back to the
     track pose), 'window_views' (filled ring columns), 'window_rmse' (reprojection rmse before, after; map pixels), 'window_information'
     (6 x 6) and 'window_status'; under a Huber loss also 'window_inliers', 'window_robust_rmse' (the rmse of the robust cost before, after; map
-    pixels) and 'window_outliers', the (model row, ring column) entries the final iterate down-weighted."""
+    pixels) and 'window_outliers', the (model row, ring column) entries the final iterate down-weighted - of a rig's window, whose ring
+    column holds `cameras` views, (model row, ring column, camera)."""
     ok = int(rec["window_status"][slot]) == 0
     fit = rec["window_fit"][slot]
-    entries = {'T_WO_window': _track_transform(rec["window_pose"][slot]) if ok else None, 'T_CO_window': _track_transform(rec["window_pose_C"][slot]) if ok else None,
+    entries = {'T_WO_window': _track_transform(rec["window_pose"][slot]) if ok else None, key: _track_transform(rec["window_pose_C"][slot]) if ok else None,
                'window_views': int(rec["window_n_views"][slot]), 'window_rmse': (float(fit[0]), float(fit[1])),
                'window_information': rec["window_information"][slot].reshape(6, 6).copy(), 'window_status': int(rec["window_status"][slot])}
     if "window_n_inlier" in rec:
-        entries.update(window_inliers=int(rec["window_n_inlier"][slot]), window_robust_rmse=(float(fit[2]), float(fit[3])),
-                       window_outliers=_outliers(rec["window_weight"][slot]))
+        outliers = _outliers(rec["window_weight"][slot])
+        if cameras is not None:
+            outliers = [(s, v // cameras, v % cameras) for s, v in outliers]
+        entries.update(window_inliers=int(rec["window_n_inlier"][slot]), window_robust_rmse=(float(fit[2]), float(fit[3])), window_outliers=outliers)
     return entries
 
 
@@ -699,31 +703,33 @@ def _track_poses(rec, slot, key, world_key):
     return {world_key: _track_transform(rec["track_pose"][slot]), key: _track_transform(rec["track_pose_C"][slot])}
 
 
-def _track_entries(rec, o, key, min_hits, world_key=None):
+def _track_entries(rec, o, key, min_hits, world_key=None, cameras=None):
     """Object o's track as the entries objects() / rig_objects() add: 'track_id' (None: the object went to no track - a position-only or
     dropped measurement), the filtered pose under `key`, 'velocity', 'track_hits', 'confirmed'."""
     slot = int(rec["track_of"][o])
-    windowed = "window_status" in rec        # the window segment: 'T_CO_window' and 'window_views' of the object's track
+    windowed = "window_status" in rec        # the window segment: 'T_CO_window' / 'T_BO_window' and 'window_views' of the object's track
+    window_key = key.replace("_track", "_window")
     if slot < 0:
         none = {key: None} if "track_pose_C" not in rec else {world_key: None, key: None}
         if windowed:
-            none.update(T_CO_window=None, window_views=0)
+            none.update({window_key: None, 'window_views': 0})
         return dict({'track_id': None, 'velocity': None, 'track_hits': 0, 'confirmed': False}, **none)
     hits = int(rec["track_i"][slot, 1])
     entries = dict({'track_id': int(rec["track_i"][slot, 0]), 'velocity': rec["track_f"][slot, 3:6].copy(), 'track_hits': hits, 'confirmed': hits >= min_hits},
                    **_track_poses(rec, slot, key, world_key))
     if windowed:
-        w = _window_entries(rec, slot)
-        entries.update(T_CO_window=w['T_CO_window'], window_views=w['window_views'])
+        w = _window_entries(rec, slot, window_key, cameras)
+        entries.update({window_key: w[window_key], 'window_views': w['window_views']})
     return entries
 
 
-def _track_list(rec, key, min_hits, world_key=None):
+def _track_list(rec, key, min_hits, world_key=None, cameras=None):
     """Every live track, coasting ones included, in slot order."""
     track_f, track_i, meas_of = rec["track_f"], rec["track_i"], rec["meas_of"]
     return [dict({'track_id': int(track_i[i, 0]), 'velocity': track_f[i, 3:6].copy(), 'hits': int(track_i[i, 1]),
                   'misses': int(track_i[i, 2]), 'age': int(track_i[i, 3]), 'confirmed': int(track_i[i, 1]) >= min_hits,
-                  'object': int(meas_of[i]) if meas_of[i] >= 0 else None}, **_track_poses(rec, i, key, world_key), **(_window_entries(rec, i) if "window_status" in rec else {}))
+                  'object': int(meas_of[i]) if meas_of[i] >= 0 else None}, **_track_poses(rec, i, key, world_key),
+                 **(_window_entries(rec, i, key.replace("_track", "_window"), cameras) if "window_status" in rec else {}))
             for i in range(track_i.shape[0]) if track_i[i, 0] != 0]
 
 
@@ -798,6 +804,35 @@ class _Window:
             st["win_i"].zero_()
 
 
+class _RigWindow(_Window):
+    """_Window for a rig: a ring column holds the tick's bearings in all `cameras` cameras (ops.window_views_state, ops.window_push_views) and
+    the refinement is the one beyond one wave (ops.refine_pose_views_wide, a views table per track)."""
+
+    def __init__(self, cfg, max_tracks, cameras):
+        super().__init__(cfg, max_tracks)
+        self.cameras = cameras
+
+    def state(self, device, streams, rows):
+        st = self.states.get((device, streams))
+        if st is None:
+            st = self.states[(device, streams)] = ops.window_views_state(streams, self.max_tracks, rows, self.cfg.ticks, self.cameras, device)
+        return st
+
+    def step(self, obs, assignment, status, track, T_WB, views, model):
+        """ops.window_push_views on the state of the bearings' device and streams, ops.refine_pose_views_wide on that state from the pushed
+        start, and the refined poses back in the rig frame -> the entries of the tick's "window" dict."""
+        st = self.state(obs.device, int(obs.shape[0]), int(obs.shape[2]))
+        pushed = ops.window_push_views(st, obs, assignment, status, track, T_WB, views, self.cfg)
+        refined = ops.refine_pose_views_wide(st["win_obs"], st["win_views"], {"pose": pushed["start"], "assignment": st["win_assignment"]}, st["win_n"], model, self.cfg,
+                                             each=True)
+        pose_B = ops.change_frame(T_WB, poses=refined["pose"], inverse=True)["poses"]
+        out = {"pose": refined["pose"], "fit": refined["fit"], "n_obs": refined["n_obs"], "n_views": pushed["n_views"], "information": refined["information"],
+               "status": refined["status"], "pose_B": pose_B, "tick_obs": obs, "win_obs": st["win_obs"], "win_views": st["win_views"], "win_i": st["win_i"]}
+        if "n_inlier" in refined:                # cfg.huber_px: the Huber instance
+            out.update(n_inlier=refined["n_inlier"], weight=refined["weight"])
+        return out
+
+
 def _check_frame_pose(pose, world_frame, streams, device, name, what):
     """The per-tick pose argument of both device pipelines against their world_frame switch: both or neither."""
     if not world_frame:
@@ -834,16 +869,22 @@ class _ObjectStage:
     poses and overflow word - -> "track": ops.track_objects' outputs plus the state tensors "track_f", "track_i", "next_id" (one state per
     device and number of streams, kept for the pipeline's life) and, in the world frame, "track_pose_C": the filtered poses back in the table's
     frame (okp_change_frame, inverse).  "track"["overflow"] is the word it was given | ops.TRACK_OVERFLOW.
-    Window (window = ops.WindowConfig(...), the camera pipeline only; needs the pose, the tracker and the world frame): okp_window_push keeps a
+    Window (window = ops.WindowConfig(...), the camera pipeline's; needs the pose, the tracker and the world frame): okp_window_push keeps a
     ring of the last `ticks` measured ticks per track slot - the CAMERA-frame table's bearings by model row (under the refined assignment where
     resolve_assignment produced one) and each tick's camera-from-world pose -, okp_refine_pose_views_each refines every track's world pose
     against its ring, and okp_change_frame (inverse) takes the result back into the camera frame -> "window": {"pose" (T_WO [B,T,12]), "fit",
     "n_obs", "n_views", "information", "status", "pose_C", and the state "win_obs", "win_views", "win_i"} (one state per device and number of
     streams, kept for the pipeline's life; reset_tracks() empties it too).  Static objects only: the ring does not model motion.
 
+    A rig's window (rig_cameras = 2 P, the rig pipeline's rig_window): a ring column holds one TICK of all 2 P cameras - okp_window_push_views
+    takes the tick's table of bearings (okp_rig_bearings: the refinement's where there is one, otherwise launched here) and composes every
+    camera's row of the views table with the tick's rig pose -, okp_refine_pose_views_wide refines every track's world pose against its
+    ticks x 2 P views, and okp_change_frame (inverse) takes the result back into the rig frame -> "window" with "pose_B" where the camera
+    window has "pose_C", plus "tick_obs", the tick's bearings.
+
     Every launch is captured with the step it ends.  Without any of the five no launch, key or value of the step differs."""
 
-    def __init__(self, type_count, points_3d, max_rmse, track, max_obj, what, world_frame, refine=None, window=None):
+    def __init__(self, type_count, points_3d, max_rmse, track, max_obj, what, world_frame, refine=None, window=None, rig_cameras=0):
         self.type_count, self.world_frame = type_count, bool(world_frame)
         if points_3d is None and max_rmse is not None:
             raise OkpError("max_rmse without points_3d: the pose needs the object model")
@@ -866,20 +907,23 @@ class _ObjectStage:
                 ops.check_refine_hypotheses(type_count)
         self.refine = refine
         if window is not None:
+            name, pose = ("rig_window", "rig_pose") if rig_cameras else ("window", "camera_pose")      # (a rig's keyword: its ring holds rig_cameras views per tick)
             if not isinstance(window, ops.WindowConfig):
-                raise OkpError("window must be an ops.WindowConfig")
+                raise OkpError(f"{name} must be an ops.WindowConfig")
             for missing, why in ((points_3d is None, "points_3d: the window refines the pose of the object model"), (track is None, "track: a window belongs to a track"),
-                                 (not world_frame, "world_frame=True: the ticks of a window share the world frame, through each tick's camera_pose")):
+                                 (not world_frame, f"world_frame=True: the ticks of a window share the world frame, through each tick's {pose}")):
                 if missing:
-                    raise OkpError(f"window without {why}")
-        self.window = _Window(window, track.max_tracks) if window is not None else None
+                    raise OkpError(f"{name} without {why}")
+        self.window = None
+        if window is not None:
+            self.window = _RigWindow(window, track.max_tracks, rig_cameras) if rig_cameras else _Window(window, track.max_tracks)
 
     def run(self, tab, n_obj, points, overflow, frame_pose, cam=None, rig=None):
         """The stage behind a step: tab = the object point table (None without a model), n_obj, points (what the world frame shows besides the
         objects) and overflow = the step's own; frame_pose: the checked per-step pose, or None; cam: the camera of a refined table; rig: what
         a refined rig tick observes with - {"table", "count", "xyc", "match", "fused", "views"}
         -> the entries the step's dict gains, in order: "pose", "refine", "world", "track", "window"."""
-        out, fed = {}, None
+        out, fed, obs = {}, None, None
         if self.model.host is not None:
             model = self.model(tab.device)
             fed = out["pose"] = dict(ops.object_pose(tab, n_obj, model, self.type_count, self.max_rmse), tab=tab)
@@ -903,7 +947,11 @@ class _ObjectStage:
             out["track"] = self.tracker.step(fed["tab"], fed["pose"], fed["status"], n_obj, model, overflow)
             if frame_pose is not None:
                 out["track"]["track_pose_C"] = ops.change_frame(frame_pose, poses=out["track"]["track_pose"], inverse=True)["poses"]
-        if self.window is not None:
+        if isinstance(self.window, _RigWindow):
+            if obs is None:                      # (no refinement: the one launch of the bearings is the window's)
+                obs = ops.rig_bearings(rig["table"], rig["count"], rig["xyc"], rig["match"], rig["fused"], self.type_count)
+            out["window"] = self.window.step(obs, out["pose"]["assignment"], out["pose"]["status"], out["track"], frame_pose, rig["views"], model)
+        elif self.window is not None:
             resolved = out.get("refine", {}).get("assignment")       # the refined assignment where resolve_assignment produced one
             out["window"] = self.window.step(tab, resolved if resolved is not None else out["pose"]["assignment"], out["pose"]["status"], out["track"], frame_pose, cam, model)
         return out
@@ -918,7 +966,7 @@ class _ObjectStage:
     def tracks(self, track, n, key, window=None):
         """Every live track of stream n of a step's "track" dict, `key` naming its pose in the table's frame, with the entries of the step's
         "window" dict where there is one - ONE device -> host copy."""
-        return _track_list(_host_tracks(track, n, window), key, self.tracker.cfg.min_hits, 'T_WO_track')
+        return _track_list(_host_tracks(track, n, window), key, self.tracker.cfg.min_hits, 'T_WO_track', getattr(self.window, "cameras", None))
 
     def pin(self, step, static_out):
         """What a captured graph reads on every replay besides its inputs, kept on `step`: the object model - the very tensor the captured launch
@@ -1046,7 +1094,7 @@ class BatchedKeypointPipeline(_ObjectStagePipeline):
     depth).  tracks() adds 'T_WO_window', 'T_CO_window' (None where 'window_status' is not 0 - a short window, a refused refinement -: fall back
     to the track pose), 'window_views', 'window_rmse', 'window_information' and 'window_status'; objects() adds 'T_CO_window' and
     'window_views' of the object's track - still one device -> host copy each.  Static objects only, and the error of camera_pose goes
-    straight into the result.  StereoStreamPipeline has no window: 2 P cameras x ticks exceed the kernel's 64 views.
+    straight into the result.  StereoStreamPipeline has no `window` (2 P cameras x ticks exceed this kernel's 64 views): it takes rig_window.
     window = ops.WindowConfig(..., huber_px=h): the ring is refined under a Huber loss (okp_refine_pose_views_robust, one launch in place of
     okp_refine_pose_views_each), so one wrong peak in one tick no longer pulls the pose by its full residual; "window" gains "n_inlier" and
     "weight", "fit" has four values, and tracks() adds 'window_inliers', 'window_robust_rmse' and 'window_outliers', the (model row, ring
@@ -1387,12 +1435,25 @@ class StereoStreamPipeline(_ObjectStagePipeline):
     rig_objects(out) adds 'T_BO' (4 x 4, model -> rig coordinates, or None), 'rmse', 'ambiguity' and 'pose_status' to every object; with track
     'track_id', 'T_BO_track', 'velocity', 'track_hits' and 'confirmed'; with world_frame 'T_WO' and 'T_WO_track' next to them.  rig_tracks(out)
     lists the live tracks, reset_tracks() empties the tracker.
+    rig_window = ops.WindowConfig(ticks, ...) (needs points_3d, track and world_frame=True - hence the fusion; each is refused by name when
+    missing; 2 x pairs x ticks above ops.REFINE_WIDE_MAX_VIEWS is refused with the numbers; it does not need refine): every track's world pose
+    refined against the last `ticks` measured ticks of ALL 2 P cameras.  The fused device tick ends, after the tracker, with
+    okp_window_push_views (a ring column = one tick: the bearings of okp_rig_bearings by model row - the refinement's table where there is one,
+    otherwise launched for the window alone - and every camera's camera-from-world view, its row of the views table composed with rig_pose),
+    okp_refine_pose_views_wide (one workgroup of up to eight waves per track, an identity assignment, from the track pose) and one
+    okp_change_frame (inverse) -> "window": the keys of the camera window with "pose_B" where that has "pose_C", plus "tick_obs"; under
+    huber_px also "n_inlier", "weight" and a four-value "fit".  rig_tracks(out) adds 'T_WO_window', 'T_BO_window' (None where 'window_status' is
+    not 0: fall back to the track pose), 'window_views' (filled TICKS), 'window_rmse', 'window_information' and 'window_status' - under huber_px
+    also 'window_inliers', 'window_robust_rmse' and 'window_outliers' as (model row, ring column, camera) -, rig_objects(out) 'T_BO_window' and
+    'window_views' of the object's track; one device -> host copy each as before.  capture_device pins the state, reset_tracks() empties it.
+    Under an initialised process group tick_sharded refuses rig_window as it refuses refine.  Static objects only; the error of rig_pose and of
+    the calibration goes straight into the result; uniform weights unless huber_px.
     world_frame=True, for a rig that moves: tick_device, capture_device / CapturedTick.replay and tick_sharded take rig_pose, a float64 [1,12]
     tensor on the frames' device (ops.frame_poses(T_WB).to(device): rig coordinates -> world; the same on every rank of a sharded tick; all NaN
     = missing in this tick).  Without world_frame a rig_pose is refused."""
 
     def __init__(self, net, stereo_camera, keypoint_config, capacity=16, max_distance=3.0, rig_poses=None, merge_radius=None, object_radius=None,
-                 fuse_capacity=None, points_3d=None, max_rmse=None, track=None, world_frame=False, refine=None):
+                 fuse_capacity=None, points_3d=None, max_rmse=None, track=None, world_frame=False, refine=None, rig_window=None):
         self.net = net
         if isinstance(refine, ops.RefineConfig) and refine.resolve_assignment:
             raise OkpNotOffered("refine with resolve_assignment=True: not offered for a rig (its refinement keeps the assignment of the fit)")
@@ -1430,11 +1491,18 @@ class StereoStreamPipeline(_ObjectStagePipeline):
                                f"{len(self.config)} types, {self.n_fused_pairs} x {self.capacity} rows asked for")
         if points_3d is not None and not given:
             raise OkpError("points_3d without rig_poses, merge_radius and object_radius: the pose is fitted to the fused objects of the rig")
-        self._stage = _ObjectStage(self.config[1:], points_3d, max_rmse, track, self.fuse_capacity if given else 0, "fuse_capacity", world_frame, refine)
-        on = refine is not None                 # (_ObjectStage refused a refinement without points_3d, and points_3d without the fusion)
+        cameras = 2 * self.n_fused_pairs if given else 2 * len(self.stereo_cameras)
+        if isinstance(rig_window, ops.WindowConfig) and cameras * rig_window.ticks > ops.REFINE_WIDE_MAX_VIEWS:
+            raise OkpError(f"rig_window: 2 x {cameras // 2} pairs x {rig_window.ticks} ticks = {cameras * rig_window.ticks} views exceed the "
+                           f"{ops.REFINE_WIDE_MAX_VIEWS} of okp_refine_pose_views_wide")
+        self._stage = _ObjectStage(self.config[1:], points_3d, max_rmse, track, self.fuse_capacity if given else 0, "fuse_capacity", world_frame, refine,
+                                   window=rig_window, rig_cameras=cameras if rig_window is not None else 0)
+        on = refine is not None or rig_window is not None       # (_ObjectStage refused either without points_3d, and points_3d without the fusion)
         self._views = _PerDevice(ops.rig_views(stereo_camera if self.rig is None else self.rig, rig_poses) if on else None)      # (.host None: refinement off)
 
     _table_host = property(lambda self: self._table.host)
+    window = None                                   # (the camera pipeline's keyword; a rig's is rig_window)
+    rig_window = property(lambda self: self._stage.window.cfg if self._stage.window is not None else None)
     _poses_host = property(lambda self: self._poses.host)
 
     def _finish(self, out, rig_pose):
@@ -1442,7 +1510,7 @@ class StereoStreamPipeline(_ObjectStagePipeline):
         fused = out["fused"]
         tab = ops.rig_object_points(fused, self.config[1:]) if self._model_host is not None else None
         rig = None
-        if self._views.host is not None:        # what the refinement observes with: this tick's own peaks (the whole rig's)
+        if self._views.host is not None:        # what the refinement and the window observe with: this tick's own peaks (the whole rig's)
             dev = fused["fused"].device
             rig = {"table": self._table(dev), "views": self._views(dev), "fused": fused, **{k: out[k] for k in ("count", "xyc", "match")}}
         out.update(self._stage.run(tab, fused["n_obj"], fused["fused"], fused["overflow"], rig_pose, rig=rig))
@@ -1450,10 +1518,11 @@ class StereoStreamPipeline(_ObjectStagePipeline):
     def rig_tracks(self, out):
         """Every live track after the fused tick `out`, coasting ones included, in slot order: a list of {'track_id', 'T_BO_track' (4 x 4,
         model -> rig coordinates, filtered), 'velocity' (m/s), 'hits', 'misses', 'age', 'confirmed', 'object' (the index into
-        rig_objects(out), or None)} - ONE device -> host copy."""
+        rig_objects(out), or None)}, with rig_window also 'T_WO_window', 'T_BO_window', 'window_views', 'window_rmse', 'window_information' and
+        'window_status' (see the class) - ONE device -> host copy."""
         if not isinstance(out, dict) or "track" not in out:
             raise OkpError("rig_tracks reads the fused device tick of a pipeline built with track")
-        return self._stage.tracks(out["track"], 0, 'T_BO_track')
+        return self._stage.tracks(out["track"], 0, 'T_BO_track', out.get("window"))
 
     def _check_fused_tick(self, n_pairs, first_pair=0):
         """A fused tick holds every pair of the rig: the clusters are formed across all of them."""
@@ -1666,12 +1735,15 @@ class StereoStreamPipeline(_ObjectStagePipeline):
                 raise OkpError(f"{frames_local.shape[0]} frames for {n_pairs_total} stereo pairs")
             out = self.tick_device(frames_local, heat_override=heat_override, rig_pose=rig_pose)
             whole = {"points": out["points"], "overflow": out["overflow"], "local": out}
-            for key in ("fused", "pose", "refine", "world", "track"):
+            for key in ("fused", "pose", "refine", "world", "track", "window"):
                 if key in out:
                     whole[key] = out[key]
             return whole
         if self.refine is not None:
             raise OkpError("tick_sharded with refine under a process group: the refinement reads every pair's peaks and matches, and the gathered "
+                           "payload holds the other ranks' 3D points only")
+        if self.rig_window is not None:
+            raise OkpError("tick_sharded with rig_window under a process group: the window reads every pair's peaks and matches, and the gathered "
                            "payload holds the other ranks' 3D points only")
         start, n_local = distributed.shard(int(n_pairs_total), dist.get_rank(), dist.get_world_size())
         if frames_local.shape[0] != 2 * n_local:
@@ -1705,7 +1777,8 @@ class StereoStreamPipeline(_ObjectStagePipeline):
         'track_id' (None where the object went to no track), 'T_BO_track' (the filtered pose), 'velocity', 'track_hits' and 'confirmed', and,
         for one built with refine, 'T_BO_refined' (None where 'T_BO' is; the fitted pose where 'refine_status' is not 0), 'reprojection_rmse'
         (before, after), 'refine_observations', 'pose_information' (6 x 6) and 'refine_status'; with world_frame 'T_WO' then comes from the
-        refined pose - read in ONE device -> host copy.  Raises OkpError when the tick's overflow word is set, as results() does (bit ops.FUSE_OVERFLOW:
+        refined pose; with rig_window 'T_BO_window' (None where the window's status is not 0) and 'window_views' of the object's track - read
+        in ONE device -> host copy.  Raises OkpError when the tick's overflow word is set, as results() does (bit ops.FUSE_OVERFLOW:
         a type had more than fuse_capacity clusters).  tick(), the host tick, does not fuse: its return value is not accepted here."""
         if not isinstance(out, dict) or "fused" not in out:
             raise OkpError("rig_objects reads a fused device tick: the dict of tick_device / capture_device / tick_sharded of a pipeline "
@@ -1715,7 +1788,7 @@ class StereoStreamPipeline(_ObjectStagePipeline):
         if "pose" in out:
             fields.update(_pose_fields(out["pose"], 0, out.get("refine")))
         if "track" in out:
-            fields.update(_track_fields(out["track"], 0))
+            fields.update(_track_fields(out["track"], 0, out.get("window")))
         in_world = "world" in out
         if in_world:
             fields["T_WB"] = out["world"]["T"]
@@ -1741,5 +1814,5 @@ class StereoStreamPipeline(_ObjectStagePipeline):
                 if in_world:
                     objects[-1]["T_WO"] = None if missing else _pose_entries(dict(host, pose=host["world_pose"]), o, "T_WO")["T_WO"]
             if "track" in out:
-                objects[-1].update(_track_entries(host, o, "T_BO_track", self._tracker.cfg.min_hits, "T_WO_track"))
+                objects[-1].update(_track_entries(host, o, "T_BO_track", self._tracker.cfg.min_hits, "T_WO_track", getattr(self._stage.window, "cameras", None)))
         return objects
