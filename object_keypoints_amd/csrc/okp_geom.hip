@@ -273,12 +273,14 @@ struct TriParams {
 
 // ---- Hartley-Sturm correction (cv2.correctMatches) -------------------------------------------
 __device__ void mat3_mul(const double (&A)[3][3], const double (&B)[3][3], double (&C)[3][3]) {
+#pragma clang fp contract(off)
   for (int i = 0; i < 3; ++i)
     for (int j = 0; j < 3; ++j) { double s = 0; for (int k = 0; k < 3; ++k) s += A[i][k] * B[k][j]; C[i][j] = s; }
 }
 
 // Right null vector of a 3x3 matrix (rank 2): the largest cross product of two rows.
 __device__ void null3(const double (&M)[3][3], double (&e)[3]) {
+#pragma clang fp contract(off)
   double best = -1;
   for (int a = 0; a < 3; ++a) {
     const int b = (a + 1) % 3;
@@ -291,6 +293,7 @@ __device__ void null3(const double (&M)[3][3], double (&e)[3]) {
 }
 
 __device__ double hs_cost(double t, double a, double b, double c, double d, double f1, double f2) {
+#pragma clang fp contract(off)
   const double u = a * t + b, v = c * t + d;
   return t * t / (1.0 + f1 * f1 * t * t) + v * v / (u * u + f2 * f2 * v * v);
 }
@@ -334,6 +337,7 @@ __device__ void null_vector4(double (&A)[4][4], double (&v)[4]) {
 }
 
 // Real roots of a degree-6 polynomial g[0] + g[1] t + ... + g[6] t^6 by Durand-Kerner in complex fp64.
+// (Degrees 4 to 6 against the oracle, and against the octet form's Jacobi-order stepping: tests/test_gpu_triangulation_rigs.py.)
 __device__ int poly6_roots(const double (&g)[7], double (&re)[6], double (&im)[6]) {
   int deg = 6;
   double scale = 0;
@@ -494,6 +498,8 @@ __global__ void okp_triangulate_thread_kernel(TriParams tp, const float* __restr
 //   * the degree-6 polynomial of Hartley-Sturm: lane k owns root k of a Durand-Kerner iteration (all roots stepped together from
 //     the previous iterate; the other roots arrive by shuffle), the cost of the seven candidates (six roots + t = infinity) is
 //     evaluated one per lane and the minimum taken by an octet reduction with OpenCV's order of preference (infinity, then root order);
+//     pinned at degrees 4, 5 and 6, in waves of mixed degree and with |f1| up to 0.9 by tests/test_gpu_triangulation_rigs.py (the committed
+//     calibration alone only ever gives a cubic: every f1^2 / f1^4 term falls below the 1e-14 cut);
 //   * the 4x4 null vector of the DLT system: one-sided Jacobi with the two disjoint column rotations of a round in parallel -
 //     lanes (rotation r, row i) - dot products by group reductions, rotated columns exchanged between the groups.
 // What is uniform per pair (3x3 algebra, polynomial coefficients, back-transformation) is computed redundantly by the eight lanes.
@@ -513,6 +519,7 @@ __device__ __forceinline__ double quad_sum(double v) {       // over the four la
 
 // Real parts of the roots of g[0] + ... + g[6] t^6: lane g (< degree) of the octet returns its root in `re`; returns the degree.
 __device__ int poly6_roots_oct(const double (&gc)[7], int g, double& re) {
+#pragma clang fp contract(off)
   int deg = 6;
   double scale = 0;
   for (int i = 0; i <= 6; ++i) scale = fmax(scale, fabs(gc[i]));
@@ -566,6 +573,7 @@ __device__ int poly6_roots_oct(const double (&gc)[7], int g, double& re) {
 
 // cv2.correctMatches for one pair, by the octet (g = lane within it)
 __device__ void hartley_sturm_oct(const double (&F)[9], int g, double& x1, double& y1, double& x2, double& y2) {
+#pragma clang fp contract(off)
   // translate both points to the origin: F' = T2^-T F T1^-1 with T^-1 = [[1,0,x],[0,1,y],[0,0,1]]
   double Fm[3][3], T1i[3][3] = {{1, 0, x1}, {0, 1, y1}, {0, 0, 1}}, T2it[3][3] = {{1, 0, 0}, {0, 1, 0}, {x2, y2, 1}};
   for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) Fm[i][j] = F[3 * i + j];
@@ -650,6 +658,7 @@ __device__ void hartley_sturm_oct(const double (&F)[9], int g, double& x1, doubl
 // Null vector of a 4x4 matrix (argmin |A v| over unit v) by one-sided (Hestenes) Jacobi, by the octet: lane (r = g >> 2, i = g & 3)
 // holds row i of A and of V (a0..a3, v0..v3; both groups hold every row) and rotates the r-th column pair of the round.
 __device__ void null_vector4_oct(int g, double a0, double a1, double a2, double a3, double (&nv)[4]) {
+#pragma clang fp contract(off)
   const int r = g >> 2, i = g & 3;
   double v0 = i == 0, v1 = i == 1, v2 = i == 2, v3 = i == 3;
   auto get = [&](int col, double c0, double c1, double c2, double c3) { return col == 0 ? c0 : col == 1 ? c1 : col == 2 ? c2 : c3; };
@@ -701,7 +710,12 @@ __device__ void null_vector4_oct(int g, double a0, double a1, double a2, double 
 // The per-pair work of okp_triangulate_kernel, by the octet (g = lane within it): lanes 0 / 1 undistort the left point lp[0..1] / the right
 // point rp[0..1], the octet corrects the pair (Hartley-Sturm, when tp.correct) and solves the DLT; every lane returns the dehomogenised point.
 // Shared with okp_stereo_triangulate_kernel.  Every lane of the wave must call it (wave-wide votes inside).
+// Contraction is off in this function and in everything it calls from this file: inlined into two kernels, the sums of two products in it
+// (3x3 products, cross products, the polynomial, the DLT rows) were fused into a * b + fma(c, d) one way in okp_triangulate_kernel and the
+// other way in okp_stereo_triangulate_kernel, and the same pair came out 1e-15 m apart.  Without fusion both kernels round the same
+// operations: okp_stereo_triangulate gives the bits of okp_triangulate_dlt (tests/test_gpu_triangulation_rigs.py).
 __device__ __forceinline__ void triangulate_pair_oct(const TriParams& tp, int g, const float* lp, const float* rp, double& X, double& Y, double& Z) {
+#pragma clang fp contract(off)
   double ux = 0.0, uy = 0.0;
   if (g == 0) okp_undistort_point(tp.left, (double)lp[0], (double)lp[1], ux, uy);
   else if (g == 1) okp_undistort_point(tp.right, (double)rp[0], (double)rp[1], ux, uy);
