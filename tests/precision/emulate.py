@@ -43,6 +43,13 @@ class Policy:
         where the branch runs on the fp16 kernels (mixed configuration)."""
         return rnd(y, self.branch_dtype) if getattr(self, "branch_dtype", None) is not None else y
 
+    def staged(self, name, y):
+        """acc + bias of a 16-bit implicit-GEMM launch that adds a residual (identity-skip residual blocks, the transposed convolution +
+        merge): both kernels stage it in the OUTPUT type before the residual is added in fp32 and the sum is rounded again
+        (csrc/okp_igemm_kernel.h:603 and :711-742, csrc/okp_igemm_patch.hip:363 and :410-419).  Rounded like the tensor `name` the launch
+        stores - part of that rounding point, not one of its own in the attribution tables; fp32-storage plans stage in fp32."""
+        return rnd(y, self.act_rule(name) if self.act_rule is not None else self.acts.get(name, self.default))
+
     def conv(self, x, w, b, fn=F.conv2d, **kw):
         mode = self.modes(self._last_weight) if self.modes is not None else ("x3" if self.x3 else "f32")
         if mode == "x3":
@@ -104,7 +111,7 @@ class EmuNet:
         w = p.weight(f"{name}.{conv}", w)
         y = p.conv(x, w, b, stride=stride, padding=(w.shape[2] - 1) // 2)
         if res is not None:
-            y = y + res
+            y = p.staged(name, y) + res
         return F.relu(y) if relu else y
 
     def _residual(self, p, name, x, stride, branch_in=None):
@@ -118,7 +125,7 @@ class EmuNet:
             ws, bs = _fold(sd[f"{name}.skip.0.weight"], f"{name}.skip.1", name, sd)
             y = y + p.conv(x, p.weight(f"{name}.skip", ws), bs, stride=stride)
         else:
-            y = y + x
+            y = p.staged(name, y) + x
         return p.act(name, F.relu(y))
 
     def _fire(self, p, name, x, stride, skip):
@@ -160,7 +167,7 @@ class EmuNet:
             low2 = self._fires(p, f"{name}.low2", low1, [(nxt, nxt)] * modules[1])
         low3 = self._fires(p, f"{name}.low3", low2, [(nxt, nxt)] * (modules[0] - 1) + [(nxt, cur)])
         w = p.weight(f"{name}.up2", self.sd[f"{name}.up2.weight"])
-        y = p.conv(low3, w, self.sd[f"{name}.up2.bias"], fn=F.conv_transpose2d, stride=2, padding=1) + up1
+        y = p.staged(name, p.conv(low3, w, self.sd[f"{name}.up2.bias"], fn=F.conv_transpose2d, stride=2, padding=1)) + up1
         return p.act(name, y)
 
     def _head(self, p, name, x, sigmoid):

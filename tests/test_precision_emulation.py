@@ -101,7 +101,7 @@ def test_float32mix_on_weight_families_it_was_not_derived_on():
       * on the family the plan was derived on (BatchNorm gains of 0.3 closing every branch; two seeds, and with logits twice as large)
         it stays inside the 1e-3 heat bar, worst 8.1e-4: the bound for this family is 9e-4 (tests/precision/bounds.py);
       * on families whose branches enter the stream with gain 1 (torch's default BatchNorm initialisation, or the synthetic gamma range
-        without the 0.3, running statistics calibrated so that activations stay O(10)) it MISSES the bar by 3-3.6x: the single-term
+        without the 0.3, running statistics calibrated so that activations stay O(10)) it MISSES the bar by 2.7-3.7x: the single-term
         fp16 branches are only cheap where a small BatchNorm gain attenuates them.  float32x3 holds everywhere (<= 1e-5).
     Hence load_keypoint_net(..., compute_dtype="float32mix", audit_frames=...) - an on-device audit with a fall-back to float32x3
     (tests/test_gpu_f32x3.py::test_audit_frames_falls_back_to_float32x3_on_unit_gain_weights)."""
