@@ -2,7 +2,10 @@
 // include/okp.h): the slot layout of an object model, Horn's closed-form rigid fit with cyclic Jacobi, the degeneracy rule, and the pieces of
 // one Gauss-Newton step of the refinement - a lane's residuals and Jacobian rows, the sixteen-lane butterfly, the 6 x 6 Cholesky solve and
 // the update by C(w) - and, for the refinements against a table of views (csrc/okp_refine_views.hip, csrc/okp_refine_views_wide.hip), the terms of
-// one (slot, view) entry and the Huber weight.
+// one (slot, view) entry and the Huber weight.  Then what the refinements repeat around their iteration and can share without a change to
+// their instructions - the pose load with its finite check and the writer of `information` - and, on the host, the argument checks of the
+// five entry-point families: the scalars, the camera, the table of required pointers, the overlap of pose_out with pose, and
+// refine_views_params, which checks and fills the launch parameters of every refinement against views, one wave or wide.
 //
 // Floating-point contraction.  The pose functions (first half) are compiled under the including file's setting at the point of inclusion:
 // okp_pose.hip includes this header under the compiler's default and keeps its bits.  The refinement functions (second half) turn
@@ -273,6 +276,133 @@ __device__ __forceinline__ ViewTerm view_term(const double (&R)[9], const double
 
 // the Huber weight of a squared residual s: 1 inside the threshold, c / sqrt(s) outside (NaN for a NaN s)
 __device__ __forceinline__ double huber_weight(double s, double c, double c2) { return s <= c2 ? 1.0 : c / sqrt(s); }
+
+// ---- what the refinement kernels do around their iteration: no barrier and no return in any of these ----
+
+// [R | t] of object oi's row-major 3 x 4 pose.  -> every entry is finite
+__device__ __forceinline__ bool load_pose(const double* pose, size_t oi, double (&R)[9], double (&t)[3]) {
+  bool finite = true;
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    const double* row = pose + oi * 12 + 4 * i;
+    R[3 * i + 0] = row[0]; R[3 * i + 1] = row[1]; R[3 * i + 2] = row[2]; t[i] = row[3];
+    finite = finite && finite64(row[0]) && finite64(row[1]) && finite64(row[2]) && finite64(row[3]);
+  }
+  return finite;
+}
+
+// The symmetric 6 x 6 `information` from the upper triangle by rows H[0 .. 20], or NaN
+template <int N>
+__device__ __forceinline__ void write_information(const double (&H)[N], bool ok, double* info) {
+  static_assert(N >= 21, "the upper triangle of a 6 x 6 matrix");
+  const double nan = __builtin_nan("");
+  int idx = 0;
+#pragma unroll
+  for (int r = 0; r < 6; ++r)
+#pragma unroll
+    for (int c = r; c < 6; ++c) {
+      const double hv = ok ? H[idx] : nan;
+      ++idx;
+      info[6 * r + c] = hv; info[6 * c + r] = hv;
+    }
+}
+
+// ---- what every refinement entry point refuses (the message names the entry point and the argument) ----
+
+// [a, a + na) and [b, b + nb) share a byte
+bool overlap(const void* a, size_t na, const void* b, size_t nb) {
+  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+  return x < y + nb && y < x + na;
+}
+
+// The table of an entry point's pointers: every one must be there, but for the last `optional` of the table
+struct NamedArg { const void* ptr; const char* name; };
+template <int N>
+int require_args(const char* fn, const NamedArg (&args)[N], int optional = 0) {
+  for (int i = 0; i < N - optional; ++i)
+    if (!args[i].ptr) { okp_set_error("%s: null %s", fn, args[i].name); return OKP_EINVAL; }
+  return OKP_OK;
+}
+
+int refuse_pose_overlap(const char* fn, const double* pose, const double* pose_out, size_t n_total) {
+  if (overlap(pose_out, n_total * 12 * sizeof(double), pose, n_total * 12 * sizeof(double))) {
+    okp_set_error("%s: pose_out overlaps pose: the input pose is the fallback and is read after other objects are written", fn);
+    return OKP_EINVAL;
+  }
+  return OKP_OK;
+}
+
+// The scalar arguments, in the order the entry points have always checked them.  v_max = 0: no views (V is not read); sigma_z = null: no
+// depth term
+int refine_scalars(const char* fn, int32_t B, int32_t max_obj, int32_t S, int32_t V, int32_t v_max, int32_t iters, double sigma_px, const double* sigma_z,
+                   double damping) {
+  if (B < 1) { okp_set_error("%s: B = %d; a batch holds at least one frame", fn, B); return OKP_EINVAL; }
+  if (max_obj < 1) { okp_set_error("%s: max_obj = %d; a frame holds at least one object", fn, max_obj); return OKP_EINVAL; }
+  if ((long long)B * max_obj > 0x7fffffffll) { okp_set_error("%s: B * max_obj = %lld objects do not fit one launch", fn, (long long)B * max_obj); return OKP_EINVAL; }
+  if (S < 1 || S > OKP_POSE_MAX_POINTS) { okp_set_error("%s: S = %d outside [1, %d] model points", fn, S, OKP_POSE_MAX_POINTS); return OKP_EINVAL; }
+  if (v_max && (V < 1 || V > v_max)) { okp_set_error("%s: V = %d outside [1, %d] views", fn, V, v_max); return OKP_EINVAL; }
+  if (iters < 1 || iters > OKP_REFINE_MAX_ITERS) { okp_set_error("%s: iters = %d outside [1, %d]", fn, iters, OKP_REFINE_MAX_ITERS); return OKP_EINVAL; }
+  if (!(sigma_px > 0.0 && sigma_px < __builtin_inf())) { okp_set_error("%s: sigma_px = %g must be a positive, finite number of map pixels", fn, sigma_px); return OKP_EINVAL; }
+  if (sigma_z && !(*sigma_z > 0.0)) { okp_set_error("%s: sigma_z = %g must be positive (metres; +infinity: no depth term)", fn, *sigma_z); return OKP_EINVAL; }
+  if (!(damping >= 0.0 && damping < __builtin_inf())) { okp_set_error("%s: damping = %g must be finite and not negative", fn, damping); return OKP_EINVAL; }
+  return OKP_OK;
+}
+
+// the camera of the single-camera refinements: only fx and fy are read
+int refine_camera(const char* fn, const okp_camera* cam) {
+  if (!cam) { okp_set_error("%s: null cam", fn); return OKP_EINVAL; }
+  if (!(cam->fx > 0.0 && cam->fx < __builtin_inf()) || !(cam->fy > 0.0 && cam->fy < __builtin_inf())) {
+    okp_set_error("%s: cam: fx = %g, fy = %g; both must be positive and finite", fn, cam->fx, cam->fy);
+    return OKP_EINVAL;
+  }
+  return OKP_OK;
+}
+
+// The launch parameters of every refinement against a table of views, one wave or wide
+struct ViewsParams {
+  const double* obs; const double* views; const double* pose; const int32_t* assignment; const int32_t* n_obj; const double* model;
+  int32_t max_obj, S, V, iters, vshift, each;     // Vp = 1 << vshift >= V lanes per group (one wave); each: one table of V rows per object (wide)
+  double sigma_px, damping;
+  double* pose_out; double* fit; int32_t* n_obs; double* information; int32_t* status;        // fit: [4] per object under a Huber loss, else [2]
+  double c, c2;                                   // huber_px / sigma_px and its square, formed once on the host (0 without a Huber loss)
+  int32_t* n_inlier; double* weight;              // the Huber instances' further outputs
+};
+
+// What a refinement against views refuses -> the parameters of its launch.  v_max: the entry point's limit on V; huber_px and views_each are
+// null for the plain entry points; zero_is_plain: huber_px = 0 is accepted and selects the plain cost, and n_inlier and weight are then not
+// required
+int refine_views_params(const char* fn, const double* obs, const double* views, const double* pose, const int32_t* assignment, const int32_t* n_obj,
+                        const double* model, double sigma_px, const double* huber_px, bool zero_is_plain, const int32_t* views_each, int32_t iters, double damping,
+                        int32_t B, int32_t max_obj, int32_t S, int32_t V, int32_t v_max, double* pose_out, double* fit, int32_t* n_obs, int32_t* n_inlier,
+                        double* weight, double* information, int32_t* status, ViewsParams& p) {
+  int rc = refine_scalars(fn, B, max_obj, S, V, v_max, iters, sigma_px, nullptr, damping);
+  if (rc) return rc;
+  if (huber_px && zero_is_plain && !(*huber_px >= 0.0 && *huber_px < __builtin_inf())) {
+    okp_set_error("%s: huber_px = %g must be finite and not negative (map pixels; 0: the plain cost)", fn, *huber_px);
+    return OKP_EINVAL;
+  }
+  if (huber_px && !zero_is_plain && !(*huber_px > 0.0 && *huber_px < __builtin_inf())) {
+    okp_set_error("%s: huber_px = %g must be a positive, finite number of map pixels", fn, *huber_px);
+    return OKP_EINVAL;
+  }
+  if (views_each && *views_each != 0 && *views_each != 1) {
+    okp_set_error("%s: views_each = %d; 0 (views [V][14], one table for every object) or 1 (views [B][max_obj][V][14], one per object)", fn, *views_each);
+    return OKP_EINVAL;
+  }
+  const bool robust = huber_px && *huber_px > 0.0;
+  const NamedArg required[] = {
+      {obs, "obs"}, {views, "views"}, {pose, "pose"}, {assignment, "assignment"}, {n_obj, "n_obj"}, {model, "model"},
+      {pose_out, "pose_out"}, {fit, "fit"}, {n_obs, "n_obs"}, {information, "information"}, {status, "status"}, {n_inlier, "n_inlier"}, {weight, "weight"}};
+  if ((rc = require_args(fn, required, robust ? 0 : 2))) return rc;              // (n_inlier and weight: the Huber instances' only)
+  if ((rc = refuse_pose_overlap(fn, pose, pose_out, (size_t)B * max_obj))) return rc;
+  p = ViewsParams{};
+  p.obs = obs; p.views = views; p.pose = pose; p.assignment = assignment; p.n_obj = n_obj; p.model = model;
+  p.max_obj = max_obj; p.S = S; p.V = V; p.iters = iters; p.each = views_each ? *views_each : 0; p.sigma_px = sigma_px; p.damping = damping;
+  while ((1 << p.vshift) < V) ++p.vshift;
+  if (huber_px) { p.c = *huber_px / sigma_px; p.c2 = p.c * p.c; }            // the threshold in units of sigma_px, and its square: once, here
+  p.pose_out = pose_out; p.fit = fit; p.n_obs = n_obs; p.n_inlier = n_inlier; p.weight = weight; p.information = information; p.status = status;
+  return OKP_OK;
+}
 
 }  // namespace
 #endif  // OKP_POSE_MATH_H

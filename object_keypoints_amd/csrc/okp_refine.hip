@@ -12,7 +12,7 @@
 //   the information matrix.  A status, once set, sticks; the arithmetic runs on regardless (no early exit: the four objects of a wave stay
 //   in step) and its results are dropped at the end.
 // No sin, cos or atan2: the step's rotation is the matrix of the unit quaternion (1, w/2) / |(1, w/2)|.
-#include "okp_pose_math.h"           // finite64, refine_pair_terms, refine_butterfly, refine_step
+#include "okp_pose_math.h"           // load_pose, refine_pair_terms, refine_butterfly, refine_step, the argument checks
 
 #pragma clang fp contract(off)
 
@@ -36,13 +36,7 @@ __global__ __launch_bounds__(64) void okp_refine_pose_kernel(const RefineParams 
   const double nan = __builtin_nan("");
 
   double R[9], t[3];
-  bool pose_finite = true;
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    const double* row = P.pose + oi * 12 + 4 * i;
-    R[3 * i + 0] = row[0]; R[3 * i + 1] = row[1]; R[3 * i + 2] = row[2]; t[i] = row[3];
-    pose_finite = pose_finite && finite64(row[0]) && finite64(row[1]) && finite64(row[2]) && finite64(row[3]);
-  }
+  const bool pose_finite = load_pose(P.pose, oi, R, t);
   const int a = (live && sub < S) ? P.assignment[oi * S + sub] : -1;
   const bool pair = a >= 0 && a < S;
   double X = 0.0, Y = 0.0, Z = 1.0, m0 = 0.0, m1 = 0.0, m2 = 0.0;
@@ -121,24 +115,13 @@ extern "C" int okp_refine_pose(const double* tab, const double* pose, const int3
                                const okp_camera* cam, double sigma_px, double sigma_z, int32_t iters, double damping, int32_t B, int32_t max_obj,
                                int32_t S, double* pose_out, double* fit, double* information, int32_t* status, void* stream) {
   const char* fn = "okp_refine_pose";
-  if (B < 1) { okp_set_error("%s: B = %d; a batch holds at least one frame", fn, B); return OKP_EINVAL; }
-  if (max_obj < 1) { okp_set_error("%s: max_obj = %d; a frame holds at least one object", fn, max_obj); return OKP_EINVAL; }
-  if ((long long)B * max_obj > 0x7fffffffll) { okp_set_error("%s: B * max_obj = %lld objects do not fit one launch", fn, (long long)B * max_obj); return OKP_EINVAL; }
-  if (S < 1 || S > OKP_POSE_MAX_POINTS) { okp_set_error("%s: S = %d outside [1, %d] model points", fn, S, OKP_POSE_MAX_POINTS); return OKP_EINVAL; }
-  if (iters < 1 || iters > OKP_REFINE_MAX_ITERS) { okp_set_error("%s: iters = %d outside [1, %d]", fn, iters, OKP_REFINE_MAX_ITERS); return OKP_EINVAL; }
-  if (!(sigma_px > 0.0 && sigma_px < __builtin_inf())) { okp_set_error("%s: sigma_px = %g must be a positive, finite number of map pixels", fn, sigma_px); return OKP_EINVAL; }
-  if (!(sigma_z > 0.0)) { okp_set_error("%s: sigma_z = %g must be positive (metres; +infinity: no depth term)", fn, sigma_z); return OKP_EINVAL; }
-  if (!(damping >= 0.0 && damping < __builtin_inf())) { okp_set_error("%s: damping = %g must be finite and not negative", fn, damping); return OKP_EINVAL; }
-  if (!cam) { okp_set_error("%s: null cam", fn); return OKP_EINVAL; }
-  if (!(cam->fx > 0.0 && cam->fx < __builtin_inf()) || !(cam->fy > 0.0 && cam->fy < __builtin_inf())) {
-    okp_set_error("%s: cam: fx = %g, fy = %g; both must be positive and finite", fn, cam->fx, cam->fy);
-    return OKP_EINVAL;
-  }
-  const struct { const void* p; const char* name; } required[] = {
+  int rc = refine_scalars(fn, B, max_obj, S, 0, 0, iters, sigma_px, &sigma_z, damping);
+  if (rc) return rc;
+  if ((rc = refine_camera(fn, cam))) return rc;
+  const NamedArg required[] = {
       {tab, "tab"}, {pose, "pose"}, {assignment, "assignment"}, {n_obj, "n_obj"}, {model, "model"},
       {pose_out, "pose_out"}, {fit, "fit"}, {information, "information"}, {status, "status"}};
-  for (const auto& r : required)
-    if (!r.p) { okp_set_error("%s: null %s", fn, r.name); return OKP_EINVAL; }
+  if ((rc = require_args(fn, required))) return rc;
   RefineParams p = {};
   p.tab = tab; p.pose = pose; p.assignment = assignment; p.n_obj = n_obj; p.model = model;
   p.max_obj = max_obj; p.S = S; p.iters = iters; p.n_total = B * max_obj;

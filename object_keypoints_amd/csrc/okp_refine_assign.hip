@@ -259,12 +259,6 @@ __global__ __launch_bounds__(64) void okp_refine_assignments_kernel(const Assign
   P.status[oi] = 0;
 }
 
-// [a, a + na) and [b, b + nb) share a byte
-bool overlap(const void* a, size_t na, const void* b, size_t nb) {
-  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-  return x < y + nb && y < x + na;
-}
-
 }  // namespace
 
 extern "C" int okp_refine_assignments(const double* tab, const double* pose, const int32_t* assignment, const int32_t* n_obj, const double* model,
@@ -280,28 +274,14 @@ extern "C" int okp_refine_assignments(const double* tab, const double* pose, con
     okp_set_error("%s: type_count gives prod(c_k!) = %lld hypotheses per object, above %d", fn, H, OKP_REFINE_MAX_HYPOTHESES);
     return OKP_EINVAL;
   }
-  if (B < 1) { okp_set_error("%s: B = %d; a batch holds at least one frame", fn, B); return OKP_EINVAL; }
-  if (max_obj < 1) { okp_set_error("%s: max_obj = %d; a frame holds at least one object", fn, max_obj); return OKP_EINVAL; }
-  if ((long long)B * max_obj > 0x7fffffffll) { okp_set_error("%s: B * max_obj = %lld objects do not fit one launch", fn, (long long)B * max_obj); return OKP_EINVAL; }
-  if (iters < 1 || iters > OKP_REFINE_MAX_ITERS) { okp_set_error("%s: iters = %d outside [1, %d]", fn, iters, OKP_REFINE_MAX_ITERS); return OKP_EINVAL; }
-  if (!(sigma_px > 0.0 && sigma_px < __builtin_inf())) { okp_set_error("%s: sigma_px = %g must be a positive, finite number of map pixels", fn, sigma_px); return OKP_EINVAL; }
-  if (!(sigma_z > 0.0)) { okp_set_error("%s: sigma_z = %g must be positive (metres; +infinity: no depth term)", fn, sigma_z); return OKP_EINVAL; }
-  if (!(damping >= 0.0 && damping < __builtin_inf())) { okp_set_error("%s: damping = %g must be finite and not negative", fn, damping); return OKP_EINVAL; }
-  if (!cam) { okp_set_error("%s: null cam", fn); return OKP_EINVAL; }
-  if (!(cam->fx > 0.0 && cam->fx < __builtin_inf()) || !(cam->fy > 0.0 && cam->fy < __builtin_inf())) {
-    okp_set_error("%s: cam: fx = %g, fy = %g; both must be positive and finite", fn, cam->fx, cam->fy);
-    return OKP_EINVAL;
-  }
-  const struct { const void* p; const char* name; } required[] = {
+  if ((rc = refine_scalars(fn, B, max_obj, p.types.S, 0, 0, iters, sigma_px, &sigma_z, damping))) return rc;      // (S: pose_types has checked it)
+  if ((rc = refine_camera(fn, cam))) return rc;
+  const NamedArg required[] = {
       {tab, "tab"}, {pose, "pose"}, {assignment, "assignment"}, {n_obj, "n_obj"}, {model, "model"}, {pose_out, "pose_out"}, {fit, "fit"},
       {information, "information"}, {status, "status"}, {assignment_out, "assignment_out"}, {hypothesis, "hypothesis"}, {cost, "cost"}};
-  for (const auto& r : required)
-    if (!r.p) { okp_set_error("%s: null %s", fn, r.name); return OKP_EINVAL; }
+  if ((rc = require_args(fn, required))) return rc;
   const size_t n_total = (size_t)B * max_obj;
-  if (overlap(pose_out, n_total * 12 * sizeof(double), pose, n_total * 12 * sizeof(double))) {
-    okp_set_error("%s: pose_out overlaps pose: the input pose is the fallback and is read after other objects are written", fn);
-    return OKP_EINVAL;
-  }
+  if ((rc = refuse_pose_overlap(fn, pose, pose_out, n_total))) return rc;
   if (overlap(assignment_out, n_total * p.types.S * sizeof(int32_t), assignment, n_total * p.types.S * sizeof(int32_t))) {
     okp_set_error("%s: assignment_out overlaps assignment: the input assignment is the fallback", fn);
     return OKP_EINVAL;

@@ -23,9 +23,12 @@
 //                                  a weight per observation from the current iterate's residuals, the robust cost where the plain kernel has
 //                                  its cost and the plain cost in a sum of its own, the inliers counted by ballot, and after the status is
 //                                  known a pass in which every lane writes the weights of its own (slot, view) entries.  A sibling, not a
-//                                  further template flag: the two plain instances stay the code they are.
+//                                  further template flag: the two plain instances stay the code they are.  Two bodies, because a merged
+//                                  one, or bodies built from more shared blocks than csrc/okp_pose_math.h's pose load (plain kernel) and
+//                                  `information` writer (both), changed the instances' instructions and their time (docs/EXPERIMENTS.md);
+//                                  the launch parameters and the argument checks of all four entry points are shared (refine_views_params).
 // fp64, no atomics, no host wait; the summation order is fixed, so the bits are the same on every run.
-#include "okp_pose_math.h"           // PoseTypes, pose_types, finite64, refine_step, the sums layout, ViewTerm / view_term / huber_weight
+#include "okp_pose_math.h"           // PoseTypes, pose_types, ViewsParams, load_pose, refine_step, view_term, huber_weight, write_information
 
 #pragma clang fp contract(off)
 
@@ -99,13 +102,6 @@ __global__ __launch_bounds__(OKP_BEARINGS_THREADS) void okp_rig_bearings_kernel(
   }
 }
 
-struct ViewsParams {
-  const double* obs; const double* views; const double* pose; const int32_t* assignment; const int32_t* n_obj; const double* model;
-  int32_t max_obj, S, V, iters, vshift;           // Vp = 1 << vshift >= V lanes per group
-  double sigma_px, damping;
-  double* pose_out; double* fit; int32_t* n_obs; double* information; int32_t* status;
-};
-
 // The sums over the wave's 64 lanes (H, g and the cost: the depth sums of the layout are not used here)
 __device__ __forceinline__ void views_butterfly(double (&acc)[OKP_REFINE_SUMS]) {
 #pragma unroll
@@ -129,13 +125,7 @@ __global__ __launch_bounds__(64) void okp_refine_pose_views_kernel(const ViewsPa
   const double nan = __builtin_nan(""), inf = __builtin_inf();
 
   double R[9], t[3];
-  bool pose_finite = true;
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    const double* row = P.pose + oi * 12 + 4 * i;
-    R[3 * i + 0] = row[0]; R[3 * i + 1] = row[1]; R[3 * i + 2] = row[2]; t[i] = row[3];
-    pose_finite = pose_finite && finite64(row[0]) && finite64(row[1]) && finite64(row[2]) && finite64(row[3]);
-  }
+  const bool pose_finite = load_pose(P.pose, oi, R, t);
   // this lane's camera: [R_v | t_v] and k_v = (fx_v, fy_v) / sigma_px (the lanes past V: an identity that observes nothing)
   double rv[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0}, tv[3] = {0.0, 0.0, 0.0}, kx = 1.0, ky = 1.0;
   if (view) {
@@ -251,28 +241,12 @@ __global__ __launch_bounds__(64) void okp_refine_pose_views_kernel(const ViewsPa
   }
   fit[0] = ok ? sqrt(J0 / n_obs) * P.sigma_px : nan;
   fit[1] = ok ? sqrt(acc[27] / n_obs) * P.sigma_px : nan;
-  {
-    int idx = 0;
-#pragma unroll
-    for (int r = 0; r < 6; ++r)
-#pragma unroll
-      for (int c = r; c < 6; ++c) {
-        const double hv = ok ? acc[idx] : nan;
-        ++idx;
-        info[6 * r + c] = hv; info[6 * c + r] = hv;
-      }
-  }
+  write_information(acc, ok, info);
   P.n_obs[oi] = n_obs;
   P.status[oi] = status;
 }
 
 // ---- the robust sibling (okp_refine_pose_views_robust): the same wave, lanes and sums with a Huber weight per observation (IRLS) ----
-
-struct RobustParams {
-  ViewsParams v;                                  // (v.fit is [4] per object here)
-  double c, c2;                                   // huber_px / sigma_px and its square, formed on the host
-  int32_t* n_inlier; double* weight;
-};
 
 // H, g, the robust cost (slot 27, where the plain kernel keeps its cost) and the plain cost (slot 28)
 __device__ __forceinline__ void robust_butterfly(double (&acc)[OKP_REFINE_SUMS]) {
@@ -283,8 +257,7 @@ __device__ __forceinline__ void robust_butterfly(double (&acc)[OKP_REFINE_SUMS])
 }
 
 template <bool EACH>
-__global__ __launch_bounds__(64) void okp_refine_pose_views_robust_kernel(const RobustParams Q) {
-  const ViewsParams& P = Q.v;
+__global__ __launch_bounds__(64) void okp_refine_pose_views_robust_kernel(const ViewsParams P) {
   const int lane = threadIdx.x;
   const size_t oi = blockIdx.x;
   const int b = (int)(oi / P.max_obj), o = (int)(oi - (size_t)b * P.max_obj);
@@ -294,7 +267,7 @@ __global__ __launch_bounds__(64) void okp_refine_pose_views_robust_kernel(const 
   const int passes = (S + G - 1) / G;
   const bool view = cam < V;
   const double nan = __builtin_nan(""), inf = __builtin_inf();
-  const double c = Q.c, c2 = Q.c2, two_c = 2.0 * Q.c;
+  const double c = P.c, c2 = P.c2, two_c = 2.0 * P.c;
 
   double R[9], t[3];
   bool pose_finite = true;
@@ -400,7 +373,7 @@ __global__ __launch_bounds__(64) void okp_refine_pose_views_robust_kernel(const 
   // the weights: a lane writes the words of its own (slot, view) entries - the lanes with cam < V and the passes cover the table - from the
   // final iterate (R, t), after the status is known
   if (view) {
-    double* wrow = Q.weight + oi * (size_t)S * V + cam;
+    double* wrow = P.weight + oi * (size_t)S * V + cam;
 #pragma unroll
     for (int i = 0; i < OKP_POSE_MAX_POINTS; ++i) {
       const int s = grp + G * i;
@@ -439,26 +412,10 @@ __global__ __launch_bounds__(64) void okp_refine_pose_views_robust_kernel(const 
   fit[1] = ok ? sqrt(acc[28] / n_obs) * P.sigma_px : nan;
   fit[2] = ok ? sqrt(J0 / n_obs) * P.sigma_px : nan;
   fit[3] = ok ? sqrt(acc[27] / n_obs) * P.sigma_px : nan;
-  {
-    int idx = 0;
-#pragma unroll
-    for (int r = 0; r < 6; ++r)
-#pragma unroll
-      for (int q = r; q < 6; ++q) {
-        const double hv = ok ? acc[idx] : nan;
-        ++idx;
-        info[6 * r + q] = hv; info[6 * q + r] = hv;
-      }
-  }
+  write_information(acc, ok, info);
   P.n_obs[oi] = n_obs;
-  Q.n_inlier[oi] = ok ? n_inlier : 0;
+  P.n_inlier[oi] = ok ? n_inlier : 0;
   P.status[oi] = status;
-}
-
-// [a, a + na) and [b, b + nb) share a byte
-bool views_overlap(const void* a, size_t na, const void* b, size_t nb) {
-  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-  return x < y + nb && y < x + na;
 }
 
 }  // namespace
@@ -485,92 +442,42 @@ extern "C" int okp_rig_bearings(const int32_t* count, const float* xyc, const in
   return okp_check_hip(hipGetLastError(), "okp_rig_bearings launch");
 }
 
-// what every refinement against a table of views refuses (the message names the argument) -> the parameters of its launch.  huber_px and
-// views_each are null for the plain entry points; `extra` are the robust one's further outputs
-struct ViewsArg { const void* ptr; const char* name; };
-static int refine_views_params(const char* fn, const double* obs, const double* views, const double* pose, const int32_t* assignment, const int32_t* n_obj,
-                               const double* model, double sigma_px, const double* huber_px, const int32_t* views_each, int32_t iters, double damping, int32_t B,
-                               int32_t max_obj, int32_t S, int32_t V, double* pose_out, double* fit, int32_t* n_obs, double* information, int32_t* status,
-                               const ViewsArg* extra, int n_extra, ViewsParams& p) {
-  if (B < 1) { okp_set_error("%s: B = %d; a batch holds at least one frame", fn, B); return OKP_EINVAL; }
-  if (max_obj < 1) { okp_set_error("%s: max_obj = %d; a frame holds at least one object", fn, max_obj); return OKP_EINVAL; }
-  if ((long long)B * max_obj > 0x7fffffffll) { okp_set_error("%s: B * max_obj = %lld objects do not fit one launch", fn, (long long)B * max_obj); return OKP_EINVAL; }
-  if (S < 1 || S > OKP_POSE_MAX_POINTS) { okp_set_error("%s: S = %d outside [1, %d] model points", fn, S, OKP_POSE_MAX_POINTS); return OKP_EINVAL; }
-  if (V < 1 || V > OKP_REFINE_MAX_VIEWS) { okp_set_error("%s: V = %d outside [1, %d] views", fn, V, OKP_REFINE_MAX_VIEWS); return OKP_EINVAL; }
-  if (iters < 1 || iters > OKP_REFINE_MAX_ITERS) { okp_set_error("%s: iters = %d outside [1, %d]", fn, iters, OKP_REFINE_MAX_ITERS); return OKP_EINVAL; }
-  if (!(sigma_px > 0.0 && sigma_px < __builtin_inf())) { okp_set_error("%s: sigma_px = %g must be a positive, finite number of map pixels", fn, sigma_px); return OKP_EINVAL; }
-  if (!(damping >= 0.0 && damping < __builtin_inf())) { okp_set_error("%s: damping = %g must be finite and not negative", fn, damping); return OKP_EINVAL; }
-  if (huber_px && !(*huber_px > 0.0 && *huber_px < __builtin_inf())) {
-    okp_set_error("%s: huber_px = %g must be a positive, finite number of map pixels", fn, *huber_px);
-    return OKP_EINVAL;
-  }
-  if (views_each && *views_each != 0 && *views_each != 1) {
-    okp_set_error("%s: views_each = %d; 0 (views [V][14], one table for every object) or 1 (views [B][max_obj][V][14], one per object)", fn, *views_each);
-    return OKP_EINVAL;
-  }
-  const ViewsArg required[] = {
-      {obs, "obs"}, {views, "views"}, {pose, "pose"}, {assignment, "assignment"}, {n_obj, "n_obj"}, {model, "model"},
-      {pose_out, "pose_out"}, {fit, "fit"}, {n_obs, "n_obs"}, {information, "information"}, {status, "status"}};
-  for (const auto& r : required)
-    if (!r.ptr) { okp_set_error("%s: null %s", fn, r.name); return OKP_EINVAL; }
-  for (int i = 0; i < n_extra; ++i)
-    if (!extra[i].ptr) { okp_set_error("%s: null %s", fn, extra[i].name); return OKP_EINVAL; }
-  const size_t n_total = (size_t)B * max_obj;
-  if (views_overlap(pose_out, n_total * 12 * sizeof(double), pose, n_total * 12 * sizeof(double))) {
-    okp_set_error("%s: pose_out overlaps pose: the input pose is the fallback and is read after other objects are written", fn);
-    return OKP_EINVAL;
-  }
-  p = ViewsParams{};
-  p.obs = obs; p.views = views; p.pose = pose; p.assignment = assignment; p.n_obj = n_obj; p.model = model;
-  p.max_obj = max_obj; p.S = S; p.V = V; p.iters = iters; p.sigma_px = sigma_px; p.damping = damping;
-  while ((1 << p.vshift) < V) ++p.vshift;
-  p.pose_out = pose_out; p.fit = fit; p.n_obs = n_obs; p.information = information; p.status = status;
-  return OKP_OK;
-}
-
-// the two plain entry points: one views table for every object, or one per object
-static int refine_views_launch(const char* fn, bool each, const double* obs, const double* views, const double* pose, const int32_t* assignment, const int32_t* n_obj,
-                               const double* model, double sigma_px, int32_t iters, double damping, int32_t B, int32_t max_obj, int32_t S, int32_t V,
-                               double* pose_out, double* fit, int32_t* n_obs, double* information, int32_t* status, void* stream) {
+// the four one-wave entry points: plain or Huber (huber_px), one views table for every object or one per object
+static int refine_views_launch(const char* fn, const char* what, const double* obs, const double* views, const int32_t* views_each, bool each, const double* pose,
+                               const int32_t* assignment, const int32_t* n_obj, const double* model, double sigma_px, const double* huber_px, int32_t iters,
+                               double damping, int32_t B, int32_t max_obj, int32_t S, int32_t V, double* pose_out, double* fit, int32_t* n_obs, int32_t* n_inlier,
+                               double* weight, double* information, int32_t* status, void* stream) {
   ViewsParams p;
-  const int rc = refine_views_params(fn, obs, views, pose, assignment, n_obj, model, sigma_px, nullptr, nullptr, iters, damping, B, max_obj, S, V, pose_out, fit, n_obs,
-                                     information, status, nullptr, 0, p);
+  const int rc = refine_views_params(fn, obs, views, pose, assignment, n_obj, model, sigma_px, huber_px, false, views_each, iters, damping, B, max_obj, S, V,
+                                     OKP_REFINE_MAX_VIEWS, pose_out, fit, n_obs, n_inlier, weight, information, status, p);
   if (rc) return rc;
-  const size_t n_total = (size_t)B * max_obj;
-  if (each) hipLaunchKernelGGL(okp_refine_pose_views_kernel<true>, dim3((unsigned)n_total), dim3(64), 0, (hipStream_t)stream, p);
-  else hipLaunchKernelGGL(okp_refine_pose_views_kernel<false>, dim3((unsigned)n_total), dim3(64), 0, (hipStream_t)stream, p);
-  return okp_check_hip(hipGetLastError(), each ? "okp_refine_pose_views_each launch" : "okp_refine_pose_views launch");
+  const dim3 grid((unsigned)((size_t)B * max_obj)), block(64);
+  const hipStream_t st = (hipStream_t)stream;
+  if (!huber_px && each) hipLaunchKernelGGL(okp_refine_pose_views_kernel<true>, grid, block, 0, st, p);
+  else if (!huber_px) hipLaunchKernelGGL(okp_refine_pose_views_kernel<false>, grid, block, 0, st, p);
+  else if (each) hipLaunchKernelGGL(okp_refine_pose_views_robust_kernel<true>, grid, block, 0, st, p);
+  else hipLaunchKernelGGL(okp_refine_pose_views_robust_kernel<false>, grid, block, 0, st, p);
+  return okp_check_hip(hipGetLastError(), what);
 }
 
 extern "C" int okp_refine_pose_views(const double* obs, const double* views, const double* pose, const int32_t* assignment, const int32_t* n_obj,
                                      const double* model, double sigma_px, int32_t iters, double damping, int32_t B, int32_t max_obj, int32_t S,
                                      int32_t V, double* pose_out, double* fit, int32_t* n_obs, double* information, int32_t* status, void* stream) {
-  return refine_views_launch("okp_refine_pose_views", false, obs, views, pose, assignment, n_obj, model, sigma_px, iters, damping, B, max_obj, S, V, pose_out, fit,
-                             n_obs, information, status, stream);
+  return refine_views_launch("okp_refine_pose_views", "okp_refine_pose_views launch", obs, views, nullptr, false, pose, assignment, n_obj, model, sigma_px, nullptr,
+                             iters, damping, B, max_obj, S, V, pose_out, fit, n_obs, nullptr, nullptr, information, status, stream);
 }
 
 extern "C" int okp_refine_pose_views_each(const double* obs, const double* views, const double* pose, const int32_t* assignment, const int32_t* n_obj,
                                           const double* model, double sigma_px, int32_t iters, double damping, int32_t B, int32_t max_obj, int32_t S,
                                           int32_t V, double* pose_out, double* fit, int32_t* n_obs, double* information, int32_t* status, void* stream) {
-  return refine_views_launch("okp_refine_pose_views_each", true, obs, views, pose, assignment, n_obj, model, sigma_px, iters, damping, B, max_obj, S, V, pose_out,
-                             fit, n_obs, information, status, stream);
+  return refine_views_launch("okp_refine_pose_views_each", "okp_refine_pose_views_each launch", obs, views, nullptr, true, pose, assignment, n_obj, model, sigma_px,
+                             nullptr, iters, damping, B, max_obj, S, V, pose_out, fit, n_obs, nullptr, nullptr, information, status, stream);
 }
 
 extern "C" int okp_refine_pose_views_robust(const double* obs, const double* views, int32_t views_each, const double* pose, const int32_t* assignment,
                                             const int32_t* n_obj, const double* model, double sigma_px, double huber_px, int32_t iters, double damping, int32_t B,
                                             int32_t max_obj, int32_t S, int32_t V, double* pose_out, double* fit, int32_t* n_obs, int32_t* n_inlier, double* weight,
                                             double* information, int32_t* status, void* stream) {
-  const char* fn = "okp_refine_pose_views_robust";
-  const ViewsArg extra[] = {{n_inlier, "n_inlier"}, {weight, "weight"}};
-  RobustParams q = {};
-  const int rc = refine_views_params(fn, obs, views, pose, assignment, n_obj, model, sigma_px, &huber_px, &views_each, iters, damping, B, max_obj, S, V, pose_out, fit,
-                                     n_obs, information, status, extra, 2, q.v);
-  if (rc) return rc;
-  q.c = huber_px / sigma_px;                                      // the threshold in units of sigma_px, and its square: once, here
-  q.c2 = q.c * q.c;
-  q.n_inlier = n_inlier; q.weight = weight;
-  const unsigned n_total = (unsigned)((size_t)B * max_obj);
-  if (views_each) hipLaunchKernelGGL(okp_refine_pose_views_robust_kernel<true>, dim3(n_total), dim3(64), 0, (hipStream_t)stream, q);
-  else hipLaunchKernelGGL(okp_refine_pose_views_robust_kernel<false>, dim3(n_total), dim3(64), 0, (hipStream_t)stream, q);
-  return okp_check_hip(hipGetLastError(), "okp_refine_pose_views_robust launch");
+  return refine_views_launch("okp_refine_pose_views_robust", "okp_refine_pose_views_robust launch", obs, views, &views_each, views_each != 0, pose, assignment, n_obj,
+                             model, sigma_px, &huber_px, iters, damping, B, max_obj, S, V, pose_out, fit, n_obs, n_inlier, weight, information, status, stream);
 }

@@ -11,6 +11,9 @@
 //                                  workgroup holds the same bits and solves the same 6 x 6 system (refine_step); nothing is broadcast.  With
 //                                  one wave (V <= 64) the sums are that wave's butterfly: at 32 < V <= 64 the bits are the one-wave kernels'.
 //                                  A template on the loss: plain (okp_refine_pose_views' cost) or Huber (okp_refine_pose_views_robust's).
+//                                  Of the blocks csrc/okp_pose_math.h shares, the kernel takes the writer of `information`; the others
+//                                  changed its instructions, and built from them the plain instance took 2 % longer at 512 views
+//                                  (docs/EXPERIMENTS.md).  The argument checks are the shared ones (refine_views_params).
 //
 // Barriers.  A barrier under a branch that two waves of a workgroup decide differently hangs the device, so every word that decides control
 // flow around a barrier is workgroup-wide BEFORE it is used: whether the object is live, its pose finite and its bearings well-formed, the
@@ -19,7 +22,7 @@
 // branch that encloses a barrier is `status == 0` before the loop, made of such words; the loop runs `iters` steps (a kernel argument) in
 // every wave, and no thread returns before the last barrier.
 // fp64, no atomics, no host wait, contraction off; the summation order is fixed, so the bits are the same on every run.
-#include "okp_pose_math.h"           // finite64, view_term, huber_weight, refine_step, the sums layout
+#include "okp_pose_math.h"           // finite64, view_term, huber_weight, refine_step, write_information, refine_views_params
 
 #pragma clang fp contract(off)
 
@@ -28,6 +31,8 @@ namespace {
 #define OKP_WIDE_WAVES (OKP_REFINE_WIDE_MAX_VIEWS / 64)
 static_assert(OKP_REFINE_WIDE_MAX_VIEWS % 64 == 0 && OKP_WIDE_WAVES * 64 <= 1024, "whole waves, one workgroup");
 
+// (the kernel's own order of the launch parameters: its scalar loads and spills follow the layout; refine_views_params fills the shared
+// ViewsParams and the entry point copies)
 struct WideParams {
   const double* obs; const double* views; const double* pose; const int32_t* assignment; const int32_t* n_obj; const double* model;
   int32_t max_obj, S, V, iters, each;             // each: views holds one table of V rows per object
@@ -257,25 +262,9 @@ __global__ __launch_bounds__(OKP_REFINE_WIDE_MAX_VIEWS) void okp_refine_pose_vie
     fit[0] = ok ? sqrt(J0 / n_obs) * P.sigma_px : nan;
     fit[1] = ok ? sqrt(acc[27] / n_obs) * P.sigma_px : nan;
   }
-  {
-    int idx = 0;
-#pragma unroll
-    for (int r = 0; r < 6; ++r)
-#pragma unroll
-      for (int q = r; q < 6; ++q) {
-        const double hv = ok ? acc[idx] : nan;
-        ++idx;
-        info[6 * r + q] = hv; info[6 * q + r] = hv;
-      }
-  }
+  write_information(acc, ok, info);
   P.n_obs[oi] = n_obs;
   P.status[oi] = status;
-}
-
-// [a, a + na) and [b, b + nb) share a byte
-bool wide_overlap(const void* a, size_t na, const void* b, size_t nb) {
-  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-  return x < y + nb && y < x + na;
 }
 
 }  // namespace
@@ -284,44 +273,16 @@ extern "C" int okp_refine_pose_views_wide(const double* obs, const double* views
                                           const int32_t* n_obj, const double* model, double sigma_px, double huber_px, int32_t iters, double damping, int32_t B,
                                           int32_t max_obj, int32_t S, int32_t V, double* pose_out, double* fit, int32_t* n_obs, int32_t* n_inlier, double* weight,
                                           double* information, int32_t* status, void* stream) {
-  const char* fn = "okp_refine_pose_views_wide";
-  const double inf = __builtin_inf();
-  if (B < 1) { okp_set_error("%s: B = %d; a batch holds at least one frame", fn, B); return OKP_EINVAL; }
-  if (max_obj < 1) { okp_set_error("%s: max_obj = %d; a frame holds at least one object", fn, max_obj); return OKP_EINVAL; }
-  if ((long long)B * max_obj > 0x7fffffffll) { okp_set_error("%s: B * max_obj = %lld objects do not fit one launch", fn, (long long)B * max_obj); return OKP_EINVAL; }
-  if (S < 1 || S > OKP_POSE_MAX_POINTS) { okp_set_error("%s: S = %d outside [1, %d] model points", fn, S, OKP_POSE_MAX_POINTS); return OKP_EINVAL; }
-  if (V < 1 || V > OKP_REFINE_WIDE_MAX_VIEWS) { okp_set_error("%s: V = %d outside [1, %d] views", fn, V, OKP_REFINE_WIDE_MAX_VIEWS); return OKP_EINVAL; }
-  if (iters < 1 || iters > OKP_REFINE_MAX_ITERS) { okp_set_error("%s: iters = %d outside [1, %d]", fn, iters, OKP_REFINE_MAX_ITERS); return OKP_EINVAL; }
-  if (!(sigma_px > 0.0 && sigma_px < inf)) { okp_set_error("%s: sigma_px = %g must be a positive, finite number of map pixels", fn, sigma_px); return OKP_EINVAL; }
-  if (!(damping >= 0.0 && damping < inf)) { okp_set_error("%s: damping = %g must be finite and not negative", fn, damping); return OKP_EINVAL; }
-  if (!(huber_px >= 0.0 && huber_px < inf)) {
-    okp_set_error("%s: huber_px = %g must be finite and not negative (map pixels; 0: the plain cost)", fn, huber_px);
-    return OKP_EINVAL;
-  }
-  if (views_each != 0 && views_each != 1) {
-    okp_set_error("%s: views_each = %d; 0 (views [V][14], one table for every object) or 1 (views [B][max_obj][V][14], one per object)", fn, views_each);
-    return OKP_EINVAL;
-  }
-  const bool robust = huber_px > 0.0;
-  const struct { const void* ptr; const char* name; bool needed; } required[] = {
-      {obs, "obs", true}, {views, "views", true}, {pose, "pose", true}, {assignment, "assignment", true}, {n_obj, "n_obj", true}, {model, "model", true},
-      {pose_out, "pose_out", true}, {fit, "fit", true}, {n_obs, "n_obs", true}, {information, "information", true}, {status, "status", true},
-      {n_inlier, "n_inlier", robust}, {weight, "weight", robust}};
-  for (const auto& r : required)
-    if (r.needed && !r.ptr) { okp_set_error("%s: null %s", fn, r.name); return OKP_EINVAL; }
-  const size_t n_total = (size_t)B * max_obj;
-  if (wide_overlap(pose_out, n_total * 12 * sizeof(double), pose, n_total * 12 * sizeof(double))) {
-    okp_set_error("%s: pose_out overlaps pose: the input pose is the fallback and is read after other objects are written", fn);
-    return OKP_EINVAL;
-  }
+  ViewsParams v;
+  const int rc = refine_views_params("okp_refine_pose_views_wide", obs, views, pose, assignment, n_obj, model, sigma_px, &huber_px, true, &views_each, iters, damping, B,
+                                     max_obj, S, V, OKP_REFINE_WIDE_MAX_VIEWS, pose_out, fit, n_obs, n_inlier, weight, information, status, v);
+  if (rc) return rc;
   WideParams p = {};
-  p.obs = obs; p.views = views; p.pose = pose; p.assignment = assignment; p.n_obj = n_obj; p.model = model;
-  p.max_obj = max_obj; p.S = S; p.V = V; p.iters = iters; p.each = views_each; p.sigma_px = sigma_px; p.damping = damping;
-  p.c = huber_px / sigma_px;                                      // the threshold in units of sigma_px, and its square: once, here
-  p.c2 = p.c * p.c;
-  p.pose_out = pose_out; p.fit = fit; p.n_obs = n_obs; p.n_inlier = n_inlier; p.weight = weight; p.information = information; p.status = status;
-  const dim3 grid((unsigned)n_total), block(64u * (unsigned)((V + 63) / 64));
-  if (robust) hipLaunchKernelGGL(okp_refine_pose_views_wide_kernel<true>, grid, block, 0, (hipStream_t)stream, p);
+  p.obs = v.obs; p.views = v.views; p.pose = v.pose; p.assignment = v.assignment; p.n_obj = v.n_obj; p.model = v.model;
+  p.max_obj = v.max_obj; p.S = v.S; p.V = v.V; p.iters = v.iters; p.each = v.each; p.sigma_px = v.sigma_px; p.damping = v.damping; p.c = v.c; p.c2 = v.c2;
+  p.pose_out = v.pose_out; p.fit = v.fit; p.n_obs = v.n_obs; p.n_inlier = v.n_inlier; p.weight = v.weight; p.information = v.information; p.status = v.status;
+  const dim3 grid((unsigned)((size_t)B * max_obj)), block(64u * (unsigned)((V + 63) / 64));
+  if (huber_px > 0.0) hipLaunchKernelGGL(okp_refine_pose_views_wide_kernel<true>, grid, block, 0, (hipStream_t)stream, p);
   else hipLaunchKernelGGL(okp_refine_pose_views_wide_kernel<false>, grid, block, 0, (hipStream_t)stream, p);
   return okp_check_hip(hipGetLastError(), "okp_refine_pose_views_wide launch");
 }

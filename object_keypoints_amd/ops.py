@@ -1678,9 +1678,14 @@ def refine_pose_views_each(obs, views, pose, n_obj, model, cfg):
     return _refine_views(True, obs, views, pose, n_obj, model, cfg)
 
 
-def _refine_views(each, obs, views, pose, n_obj, model, cfg):
-    if not isinstance(cfg, (RefineConfig, WindowConfig) if each else RefineConfig):
-        raise OkpError("cfg must be an ops.RefineConfig" + (" or an ops.WindowConfig" if each else ""))
+def _views_inputs(each, obs, views, pose, n_obj, model, cfg, cfg_types, cfg_text, max_views, obs_from, views_from):
+    """The argument checks every refinement against views shares -> (fitted, assignment, b, max_obj, s, v, dev).  cfg_types / cfg_text: the
+    config classes accepted and their names in the message; max_views: the entry point's limit on V; obs_from / views_from: where the message
+    says obs and a shared views table come from."""
+    if not isinstance(cfg, cfg_types):
+        raise OkpError(f"cfg must be {cfg_text}")
+    if not isinstance(each, (bool, np.bool_)):
+        raise OkpError(f"each = {each!r} must be True (one views table per object) or False (one for all)")
     try:
         fitted, assignment = pose["pose"], pose["assignment"]
     except (TypeError, KeyError, IndexError):
@@ -1688,15 +1693,15 @@ def _refine_views(each, obs, views, pose, n_obj, model, cfg):
     for name, t in (("obs", obs), ("views", views), ("pose", fitted), ("assignment", assignment), ("n_obj", n_obj), ("model", model)):
         require_cuda(t, name)
     if obs.dtype != torch.float64 or obs.dim() != 5 or obs.shape[4] != 2:
-        raise OkpError("obs must be float64 [B,max_obj,S,V,2] (rig_bearings)")
+        raise OkpError(f"obs must be float64 [B,max_obj,S,V,2] ({obs_from})")
     b, max_obj, s, v = (int(x) for x in obs.shape[:4])
     dev = obs.device
-    if b < 1 or max_obj < 1 or not 1 <= s <= POSE_MAX_POINTS or not 1 <= v <= REFINE_MAX_VIEWS:
-        raise OkpError(f"obs [{b},{max_obj},{s},{v},2]: at least one frame and object, at most {POSE_MAX_POINTS} model points and {REFINE_MAX_VIEWS} views")
+    if b < 1 or max_obj < 1 or not 1 <= s <= POSE_MAX_POINTS or not 1 <= v <= max_views:
+        raise OkpError(f"obs [{b},{max_obj},{s},{v},2]: at least one frame and object, at most {POSE_MAX_POINTS} model points and {max_views} views")
     if each and (views.dtype != torch.float64 or tuple(views.shape) != (b, max_obj, v, 14) or views.device != dev):
         raise OkpError(f"views must be float64 [{b},{max_obj},{v},14] on the bearings' device: one table of {v} rows for each object of obs")
     if not each and (views.dtype != torch.float64 or tuple(views.shape) != (v, 14) or views.device != dev):
-        raise OkpError(f"views must be float64 [{v},14] on the bearings' device (rig_views): one row for each of the {v} views of obs")
+        raise OkpError(f"views must be float64 [{v},14] on the bearings' device{views_from}: one row for each of the {v} views of obs")
     if fitted.dtype != torch.float64 or tuple(fitted.shape) != (b, max_obj, 12) or assignment.dtype != torch.int32 or tuple(assignment.shape) != (b, max_obj, s) or \
             fitted.device != dev or assignment.device != dev:
         raise OkpError(f"pose must be float64 [{b},{max_obj},12] and assignment int32 [{b},{max_obj},{s}] on the bearings' device (object_pose)")
@@ -1704,24 +1709,37 @@ def _refine_views(each, obs, views, pose, n_obj, model, cfg):
         raise OkpError(f"n_obj must be int32 [{b}] on the bearings' device: the objects of each frame")
     if model.dtype != torch.float64 or tuple(model.shape) != (s, 3) or model.device != dev:
         raise OkpError(f"model must be float64 [{s},3] on the bearings' device (object_model)")
-    pose_out = torch.empty((b, max_obj, 12), dtype=torch.float64, device=dev)
-    n_obs = torch.empty((b, max_obj), dtype=torch.int32, device=dev)
-    information = torch.empty((b, max_obj, 36), dtype=torch.float64, device=dev)
-    status = torch.empty((b, max_obj), dtype=torch.int32, device=dev)
+    return fitted, assignment, b, max_obj, s, v, dev
+
+
+def _views_outputs(b, max_obj, s, v, dev, robust):
+    """The dict a refinement against views returns, allocated: under a Huber loss "fit" has four values and "n_inlier" and "weight" are added."""
+    out = {"pose": torch.empty((b, max_obj, 12), dtype=torch.float64, device=dev),
+           "fit": torch.empty((b, max_obj, 4 if robust else 2), dtype=torch.float64, device=dev),
+           "n_obs": torch.empty((b, max_obj), dtype=torch.int32, device=dev), "information": torch.empty((b, max_obj, 36), dtype=torch.float64, device=dev),
+           "status": torch.empty((b, max_obj), dtype=torch.int32, device=dev)}
+    if robust:
+        out["n_inlier"] = torch.empty((b, max_obj), dtype=torch.int32, device=dev)
+        out["weight"] = torch.empty((b, max_obj, s, v), dtype=torch.float64, device=dev)
+    return out
+
+
+def _refine_views(each, obs, views, pose, n_obj, model, cfg):
+    fitted, assignment, b, max_obj, s, v, dev = _views_inputs(
+        each, obs, views, pose, n_obj, model, cfg, (RefineConfig, WindowConfig) if each else RefineConfig,
+        "an ops.RefineConfig" + (" or an ops.WindowConfig" if each else ""), REFINE_MAX_VIEWS, "rig_bearings", " (rig_views)")
     B = _ops()
     huber_px = getattr(cfg, "huber_px", None)
-    if huber_px is not None:                     # the Huber sibling: one launch, today's keys (fit with four values) and the two it adds
-        fit = torch.empty((b, max_obj, 4), dtype=torch.float64, device=dev)
-        n_inlier = torch.empty((b, max_obj), dtype=torch.int32, device=dev)
-        weight = torch.empty((b, max_obj, s, v), dtype=torch.float64, device=dev)
+    out = _views_outputs(b, max_obj, s, v, dev, huber_px is not None)
+    if huber_px is not None:                     # the Huber instance: one launch, the plain keys (fit with four values) and the two it adds
         _dispatch(B.refine_pose_views_robust, obs.contiguous(), views.contiguous(), 1 if each else 0, fitted.contiguous(), assignment.contiguous(),
-                  n_obj.reshape(b).contiguous(), model.contiguous(), cfg.sigma_px, huber_px, cfg.iters, cfg.damping, pose_out, fit, n_obs, n_inlier, weight, information,
-                  status, stream_int())
-        return {"pose": pose_out, "fit": fit, "n_obs": n_obs, "information": information, "status": status, "n_inlier": n_inlier, "weight": weight}
-    fit = torch.empty((b, max_obj, 2), dtype=torch.float64, device=dev)
-    _dispatch(B.refine_pose_views_each if each else B.refine_pose_views, obs.contiguous(), views.contiguous(), fitted.contiguous(), assignment.contiguous(),
-              n_obj.reshape(b).contiguous(), model.contiguous(), cfg.sigma_px, cfg.iters, cfg.damping, pose_out, fit, n_obs, information, status, stream_int())
-    return {"pose": pose_out, "fit": fit, "n_obs": n_obs, "information": information, "status": status}
+                  n_obj.reshape(b).contiguous(), model.contiguous(), cfg.sigma_px, huber_px, cfg.iters, cfg.damping, out["pose"], out["fit"], out["n_obs"], out["n_inlier"],
+                  out["weight"], out["information"], out["status"], stream_int())
+    else:
+        _dispatch(B.refine_pose_views_each if each else B.refine_pose_views, obs.contiguous(), views.contiguous(), fitted.contiguous(), assignment.contiguous(),
+                  n_obj.reshape(b).contiguous(), model.contiguous(), cfg.sigma_px, cfg.iters, cfg.damping, out["pose"], out["fit"], out["n_obs"], out["information"],
+                  out["status"], stream_int())
+    return out
 
 
 # ---- tracked objects refined against a sliding window of ticks' bearings (okp_window_push, okp_refine_pose_views_each; csrc/okp_window.hip) ----
@@ -1925,41 +1943,11 @@ def refine_pose_views_wide(obs, views, pose, n_obj, model, cfg, each=False):
     the statuses and the returned dict are theirs; cfg: a RefineConfig or a WindowConfig, whose huber_px selects the Huber instance as it
     does there ("fit" with four values, "n_inlier", "weight").  For 32 < V <= 64 the result has the bits of those entry points.  One launch,
     no host sync."""
-    if not isinstance(cfg, (RefineConfig, WindowConfig)):
-        raise OkpError("cfg must be an ops.RefineConfig or an ops.WindowConfig")
-    if not isinstance(each, (bool, np.bool_)):
-        raise OkpError(f"each = {each!r} must be True (one views table per object) or False (one for all)")
-    try:
-        fitted, assignment = pose["pose"], pose["assignment"]
-    except (TypeError, KeyError, IndexError):
-        raise OkpError("pose must be the dict of ops.object_pose (its \"pose\" and \"assignment\")") from None
-    for name, t in (("obs", obs), ("views", views), ("pose", fitted), ("assignment", assignment), ("n_obj", n_obj), ("model", model)):
-        require_cuda(t, name)
-    if obs.dtype != torch.float64 or obs.dim() != 5 or obs.shape[4] != 2:
-        raise OkpError("obs must be float64 [B,max_obj,S,V,2] (rig_bearings, or the win_obs of window_views_state)")
-    b, max_obj, s, v = (int(x) for x in obs.shape[:4])
-    dev = obs.device
-    if b < 1 or max_obj < 1 or not 1 <= s <= POSE_MAX_POINTS or not 1 <= v <= REFINE_WIDE_MAX_VIEWS:
-        raise OkpError(f"obs [{b},{max_obj},{s},{v},2]: at least one frame and object, at most {POSE_MAX_POINTS} model points and {REFINE_WIDE_MAX_VIEWS} views")
-    if each and (views.dtype != torch.float64 or tuple(views.shape) != (b, max_obj, v, 14) or views.device != dev):
-        raise OkpError(f"views must be float64 [{b},{max_obj},{v},14] on the bearings' device: one table of {v} rows for each object of obs")
-    if not each and (views.dtype != torch.float64 or tuple(views.shape) != (v, 14) or views.device != dev):
-        raise OkpError(f"views must be float64 [{v},14] on the bearings' device: one row for each of the {v} views of obs")
-    if fitted.dtype != torch.float64 or tuple(fitted.shape) != (b, max_obj, 12) or assignment.dtype != torch.int32 or tuple(assignment.shape) != (b, max_obj, s) or \
-            fitted.device != dev or assignment.device != dev:
-        raise OkpError(f"pose must be float64 [{b},{max_obj},12] and assignment int32 [{b},{max_obj},{s}] on the bearings' device (object_pose)")
-    if n_obj.dtype != torch.int32 or n_obj.numel() != b or n_obj.device != dev:
-        raise OkpError(f"n_obj must be int32 [{b}] on the bearings' device: the objects of each frame")
-    if model.dtype != torch.float64 or tuple(model.shape) != (s, 3) or model.device != dev:
-        raise OkpError(f"model must be float64 [{s},3] on the bearings' device (object_model)")
+    fitted, assignment, b, max_obj, s, v, dev = _views_inputs(
+        each, obs, views, pose, n_obj, model, cfg, (RefineConfig, WindowConfig), "an ops.RefineConfig or an ops.WindowConfig", REFINE_WIDE_MAX_VIEWS,
+        "rig_bearings, or the win_obs of window_views_state", "")
     huber_px = getattr(cfg, "huber_px", None)
-    out = {"pose": torch.empty((b, max_obj, 12), dtype=torch.float64, device=dev),
-           "fit": torch.empty((b, max_obj, 4 if huber_px is not None else 2), dtype=torch.float64, device=dev),
-           "n_obs": torch.empty((b, max_obj), dtype=torch.int32, device=dev), "information": torch.empty((b, max_obj, 36), dtype=torch.float64, device=dev),
-           "status": torch.empty((b, max_obj), dtype=torch.int32, device=dev)}
-    if huber_px is not None:
-        out["n_inlier"] = torch.empty((b, max_obj), dtype=torch.int32, device=dev)
-        out["weight"] = torch.empty((b, max_obj, s, v), dtype=torch.float64, device=dev)
+    out = _views_outputs(b, max_obj, s, v, dev, huber_px is not None)
     _dispatch(_ops().refine_pose_views_wide, obs.contiguous(), views.contiguous(), 1 if each else 0, fitted.contiguous(), assignment.contiguous(),
               n_obj.reshape(b).contiguous(), model.contiguous(), cfg.sigma_px, huber_px if huber_px is not None else 0.0, cfg.iters, cfg.damping, out["pose"], out["fit"],
               out["n_obs"], out.get("n_inlier"), out.get("weight"), out["information"], out["status"], stream_int())
