@@ -51,7 +51,10 @@ extern "C" {
                                     bearings);
                                     okp_refine_pose_views_robust (those two refinements under a Huber loss);
                                     okp_window_push_views, okp_refine_pose_views_wide, OKP_REFINE_WIDE_MAX_VIEWS (a rig's tracked objects refined
-                                    against a sliding window of ticks x cameras) */
+                                    against a sliding window of ticks x cameras);
+                                    okp_refine_pose_views_weighted, okp_rig_bearings_weighted, okp_window_push_weighted,
+                                    okp_window_push_views_weighted, okp_refine_pose_views_weighted_wide (those refinements weighted by the
+                                    peaks' confidences) */
 
 /* OKP_F16: IEEE half activations / weights, fp32 accumulate (BASELINE configs[4]).
  * OKP_F32X3 (okp_conv plans only): fp32 activations, weights and results like OKP_F32 - every tensor argument of such a plan is an
@@ -935,7 +938,8 @@ int okp_refine_assignments(const double* tab_dev, const double* pose_dev, const 
  *   As for okp_refine_pose the order of the sums is not part of the contract: a lane adds the terms of its view over its slots in ascending
  *   order and one butterfly adds the lanes (tests/test_gpu_refine_views.py: 1e-9 on R and t against a NumPy evaluation).  pose_out must not
  *   overlap pose.
- * Limits.  Uniform weights over the observations: the peaks' confidences are not used.  The assignment is okp_object_pose's, as it is.
+ * Limits.  Uniform weights over the observations: the peaks' confidences are not used unless the weighted entry points are called
+ * (okp_rig_bearings_weighted, okp_refine_pose_views_weighted, below).  The assignment is okp_object_pose's, as it is.
  * Refused on the host before any launch (OKP_EINVAL, the message names the argument): a null pointer, B or max_obj < 1, S outside
  * [1, OKP_POSE_MAX_POINTS], V outside [1, OKP_REFINE_MAX_VIEWS], iters outside [1, OKP_REFINE_MAX_ITERS], sigma_px not positive and finite,
  * damping negative or not finite, pose_out overlapping pose.
@@ -986,7 +990,7 @@ int okp_refine_pose_views_each(const double* obs_dev, const double* views_dev, c
  *                                        not an observation, and all NaN for a non-zero status
  *   Objects from n_obj[b] on: as okp_refine_pose_views leaves them, n_inlier 0, weight all NaN.
  *   A lane writes the weight words of its own (slot, view) entries, recomputed from the final iterate once the status is known.
- * Limits.  The weights do not use the peaks' confidences.  Huber bounds an outlier's pull, it does not remove it: an outlier still adds
+ * Limits.  The weights do not use the peaks' confidences unless okp_refine_pose_views_weighted is called with the same huber_px.  Huber bounds an outlier's pull, it does not remove it: an outlier still adds
  * c / sqrt(s) of its Jacobian rows.  With huber_px large enough that nothing is down-weighted the result is okp_refine_pose_views'.
  * Refused on the host before any launch (OKP_EINVAL, the message names the argument): everything okp_refine_pose_views refuses, huber_px not
  * positive and finite, views_each outside {0, 1}, a null n_inlier or weight. */
@@ -1038,7 +1042,8 @@ int okp_refine_pose_views_robust(const double* obs_dev, const double* views_dev,
  *   free slots and short windows as OKP_REFINE_SKIPPED
  * Limits.  Static objects only: the window does not model motion, max_speed is a guard, not a model.  No robust loss and uniform weights
  * in okp_refine_pose_views_each: there one wrong peak in one tick pulls the pose.  okp_refine_pose_views_robust (views_each = 1) on the same
- * state bounds that pull with a Huber loss; it does not remove it, and its weights still do not use the peaks' confidences.  The error of the camera poses goes straight into the result: the
+ * state bounds that pull with a Huber loss; it does not remove it, and its weights still do not use the peaks' confidences unless the ring
+ * is kept by okp_window_push_weighted and refined by okp_refine_pose_views_weighted.  The error of the camera poses goes straight into the result: the
  * refinement takes T_WC as exact.  The window of a rig (2 P cameras x W ticks) exceeds OKP_REFINE_MAX_VIEWS: okp_window_push_views and
  * okp_refine_pose_views_wide, below, are its ring and its refinement.
  * Refused on the host before any launch (OKP_EINVAL, the message names the argument): W outside [1, OKP_REFINE_MAX_VIEWS], T outside
@@ -1086,7 +1091,8 @@ int okp_window_push(const double* tab_dev, const int32_t* assignment_dev, const 
  * Outputs, all written by every call: n_views [B][T] int32 = filled (TICKS, not views); start [B][T][12] fp64 = track_pose[b][i] bit for bit
  *   when filled >= min_views, otherwise NaN.
  * Limits.  Those of okp_window_push: static objects only; the error of T_WB - and here of the rig's calibration in `views` - goes straight into
- * the result; uniform weights unless the refinement is given a huber_px.
+ * the result; uniform weights unless the refinement is given a huber_px, or the ring is kept by okp_window_push_views_weighted and refined by
+ * okp_refine_pose_views_weighted.
  * Refused on the host before any launch (OKP_EINVAL, the message names the argument): V outside [1, 2 * OKP_RIG_MAX_PAIRS], W outside
  * [1, OKP_REFINE_MAX_VIEWS], W * V > OKP_REFINE_WIDE_MAX_VIEWS, T outside [1, OKP_TRACK_MAX_TRACKS], S outside [1, OKP_POSE_MAX_POINTS], B or
  * max_obj < 1, min_views outside [1, W], max_speed not positive (NaN included), a null pointer.
@@ -1117,6 +1123,96 @@ int okp_refine_pose_views_wide(const double* obs_dev, const double* views_dev, i
                                double huber_px, int32_t iters, double damping, int32_t B, int32_t max_obj, int32_t S, int32_t V,
                                double* pose_out_dev, double* fit_dev /* [2], or [4] with huber_px > 0 */, int32_t* n_obs_dev,
                                int32_t* n_inlier_dev, double* weight_dev, double* information_dev, int32_t* status_dev, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * Weighting the views refinements by the peaks' confidences (csrc/okp_refine_views.hip, csrc/okp_refine_views_wide.hip, csrc/okp_window.hip,
+ * csrc/okp_window_views.hip).  The refinements above give every bearing the same weight, whether it came from a clean bump or from a faint,
+ * half-occluded peak; the Huber loss bounds a gross error after the fact, a per-observation variance is the other half of a maximum-
+ * likelihood refinement.  Here every observation carries a PRIOR a > 0 that scales its squared standardised residual: its sigma is
+ * sigma_px / sqrt(a).  The priors come from the confidences that are already on the device - okp_peak_nms' sum of p over the 5 x 5 window,
+ * the third value of xyc and the fourth of every row of the object table - through a STATED MODEL with two user parameters; how a real
+ * peak's localisation error depends on its confidence has not been measured.  Opt-in: entry points of their own next to the unweighted ones, which
+ * keep their signatures, their kernel instances and their bits.  There is no reference implementation: the specification is this comment
+ * (tests/refine_weighted_spec.py restates it in NumPy).
+ *
+ * The mapping, prior_of(c) for a confidence c with conf_ref and conf_floor: comparisons and one division in fp64,
+ *     c >= conf_ref ? 1.0 : ((c > conf_floor ? c : conf_floor) / conf_ref)
+ *   - a NaN c falls to the floor, a confidence at or above conf_ref gives exactly 1.0, and the result lies in [conf_floor / conf_ref, 1].
+ *
+ * okp_refine_pose_views_weighted: the refinement of okp_refine_pose_views_wide - V in [1, OKP_REFINE_WIDE_MAX_VIEWS], views_each 0 or 1,
+ * huber_px == 0 the plain cost and > 0 the Huber cost - with prior [B][max_obj][S][V] fp64, the prior of observation (table slot s, view v).
+ * Everything said there holds - the inputs, which entries are observations, the step, the damping, the pivot rule, the statuses, the
+ * REJECTED slack 1e-12 x n_obs, n_obs - except, with e_u, e_v as okp_refine_pose_views defines them and
+ *     s' = a * (e_u*e_u + e_v*e_v)    (no contraction):
+ *   Plain.  J = sum s', H = sum a j^T j, g = sum a j^T e over the observations: the factor scales the first j of every product.
+ *     fit = sqrt(J / n_obs) * sigma_px at the input pose and at the final iterate; information is the weighted H.
+ *   Huber.  The rule of okp_refine_pose_views_robust is applied to s', the whitened residual: an observation is an INLIER when s' <= c2;
+ *     w_h = 1 for an inlier, otherwise c / sqrt(s'); rho = s' for an inlier, otherwise (2 c) sqrt(s') - c2.  H = sum (a w_h) j^T j,
+ *     g = sum (a w_h) j^T e, J = sum rho, Pl = sum s'.  The `weight` output stays w_h alone - exactly 1.0 for an inlier -, and n_inlier and
+ *     the four values of fit are as there, computed on s'.
+ *   Precheck.  A FILLED entry of a slot with a model row - an observation - whose prior is NaN, infinite or <= 0 makes the object
+ *     OKP_REFINE_SKIPPED, like a half-NaN bearing.  The prior of an entry that is not an observation is not read, whatever it holds.
+ *   With every prior exactly 1.0 the outputs are BIT FOR BIT those of the unweighted entry point of the same shape and loss
+ *   (okp_refine_pose_views / _each / _robust for V <= OKP_REFINE_MAX_VIEWS, okp_refine_pose_views_wide above): multiplication by 1.0 is exact.
+ *   For V <= OKP_REFINE_MAX_VIEWS one wave per object, an instance of the one-wave kernels that keeps the lane's priors in registers; above,
+ *   an instance of the wide kernel that stages the object's priors in shared memory, a lane reading only what it wrote.
+ *   Refused on the host before any launch (OKP_EINVAL, the message names the argument): everything okp_refine_pose_views_wide refuses, and a
+ *   null prior.
+ * okp_refine_pose_views_weighted_wide: the same arguments, cost and refusals on the wide kernel's instance WHATEVER V is.  Up to 32 views the
+ *   one-wave kernels and the wide kernel add their sums in different orders (okp_refine_pose_views_wide), so there are two unweighted results
+ *   to be equal to: with every prior exactly 1.0 this entry point gives the bits of okp_refine_pose_views_wide for every V - it is what
+ *   refines the ring of okp_window_push_views_weighted, whose unweighted refinement is that one.  For V > 32 the two weighted entry points
+ *   give the same bits.
+ *
+ * okp_rig_bearings_weighted: okp_rig_bearings - the same kernel, obs written bit for bit as there - with conf_ref, conf_floor and
+ * prior [cap_f][S][2P] fp64.  EVERY word is written: prior[o][s][v] is NaN wherever obs[o][s][v] is (NaN, NaN), elsewhere
+ * prior_of(xyc[v][k][i][2]) of the peak the bearing came from, its fp32 confidence taken to fp64.
+ *   Refused: everything okp_rig_bearings refuses, conf_ref not positive and finite, conf_floor outside (0, conf_ref], a null prior.
+ *
+ * okp_window_push_weighted: okp_window_push with conf_ref, conf_floor and the state win_prior [B][T][S][W] fp64, kept next to win_obs and
+ * indexed like it (model row, ring column).  Wherever the push writes (NaN, NaN) to an entry of win_obs it writes NaN to the same entry of
+ * win_prior - "empty the ring" included -; wherever it writes the bearing of table slot s it writes prior_of(c) of that row's fourth value
+ * (finite there, by step 4).  The empty state is all NaN.  Every other word is okp_window_push's.
+ *   Refused: everything okp_window_push refuses, conf_ref not positive and finite, conf_floor outside (0, conf_ref], a null win_prior.
+ *
+ * okp_window_push_views_weighted: okp_window_push_views with the input prior [B][max_obj][S][V] fp64 (okp_rig_bearings_weighted's) and the
+ * state win_prior [B][T][S][W*V] fp64.  The prior rows are copied bit for bit alongside the bearing rows, NaNs included, under the same
+ * "a later slot replaces the whole row" rule; NaN wherever the push writes (NaN, NaN).  The empty state is all NaN.
+ *   Refused: everything okp_window_push_views refuses, a null prior or win_prior.
+ * Both pushes agree with tests/refine_weighted_spec.py BIT FOR BIT, as the unweighted ones do with their specifications.
+ *
+ * Limits.  The relation between a peak's confidence and its localisation error is ASSUMED (variance proportional to 1 / confidence below
+ * conf_ref, constant above, bounded at conf_floor), not measured on real data.  A slot that is a reduced cluster centre carries
+ * confidence 1.0 (okp_object_points), so in the camera window it sits at the floor unless conf_ref is chosen with that in mind; the sum of
+ * p of a clean bump of length scale 2 is about 15.8.  Priors do not detect outliers: huber_px does that.
+ * ---------------------------------------------------------------------------------- */
+int okp_refine_pose_views_weighted(const double* obs_dev, const double* prior_dev /* [B][max_obj][S][V] */, const double* views_dev,
+                                   int32_t views_each, const double* pose_dev, const int32_t* assignment_dev, const int32_t* n_obj_dev,
+                                   const double* model_dev, double sigma_px, double huber_px, int32_t iters, double damping, int32_t B,
+                                   int32_t max_obj, int32_t S, int32_t V, double* pose_out_dev,
+                                   double* fit_dev /* [2], or [4] with huber_px > 0 */, int32_t* n_obs_dev, int32_t* n_inlier_dev,
+                                   double* weight_dev, double* information_dev, int32_t* status_dev, void* stream);
+int okp_refine_pose_views_weighted_wide(const double* obs_dev, const double* prior_dev, const double* views_dev, int32_t views_each,
+                                        const double* pose_dev, const int32_t* assignment_dev, const int32_t* n_obj_dev, const double* model_dev,
+                                        double sigma_px, double huber_px, int32_t iters, double damping, int32_t B, int32_t max_obj, int32_t S,
+                                        int32_t V, double* pose_out_dev, double* fit_dev, int32_t* n_obs_dev, int32_t* n_inlier_dev,
+                                        double* weight_dev, double* information_dev, int32_t* status_dev, void* stream);
+int okp_rig_bearings_weighted(const int32_t* count_dev, const float* xyc_dev, const int32_t* match_dev, const int32_t* member_dev,
+                              const int32_t* object_dev, const int32_t* n_fused_dev, const okp_stereo_pair* table_dev, int32_t n_table,
+                              int32_t n_pairs, int32_t K, int32_t cap, int32_t cap_f, const int32_t* type_count /* HOST [K-1] */,
+                              double conf_ref, double conf_floor, double* obs_dev, double* prior_dev /* [cap_f][S][2P] */, void* stream);
+int okp_window_push_weighted(const double* tab_dev, const int32_t* assignment_dev, const int32_t* status_dev, const int32_t* meas_of_dev,
+                             const int32_t* track_i_dev, const double* track_f_dev, const double* track_pose_dev, const double* T_WC_dev,
+                             const okp_camera* cam, int32_t B, int32_t max_obj, int32_t S, int32_t T, int32_t W, int32_t min_views,
+                             double max_speed, double conf_ref, double conf_floor, double* win_obs_dev,
+                             double* win_prior_dev /* [B][T][S][W] */, double* win_views_dev, int32_t* win_i_dev, int32_t* n_views_dev,
+                             double* start_dev, void* stream);
+int okp_window_push_views_weighted(const double* obs_dev, const double* prior_dev /* [B][max_obj][S][V] */, const int32_t* assignment_dev,
+                                   const int32_t* status_dev, const int32_t* meas_of_dev, const int32_t* track_i_dev,
+                                   const double* track_f_dev, const double* track_pose_dev, const double* T_WB_dev, const double* views_dev,
+                                   int32_t B, int32_t max_obj, int32_t S, int32_t T, int32_t W, int32_t V, int32_t min_views,
+                                   double max_speed, double* win_obs_dev, double* win_prior_dev /* [B][T][S][W*V] */,
+                                   double* win_views_dev, int32_t* win_i_dev, int32_t* n_views_dev, double* start_dev, void* stream);
 
 /* Undistort only (FisheyeCamera.undistort, camera_utils.py:75-81 / RadTanPinholeCamera.undistort, :57-62, by cam->model):
  * xy [m][2] fp32 -> out [m][2] fp64.  okp_fisheye_undistort is the same entry point under its round-1 name. */

@@ -431,6 +431,51 @@ def refine_pose_views_wide(obs, views, views_each, pose, assignment, n_obj, mode
                "okp_refine_pose_views_wide")
 
 
+# ---- the views refinements weighted by the peaks' confidences: prior [B,max_obj,S,V], win_prior [B,T,S,W] / [B,T,S,W*V] -----------------------------
+def rig_bearings_weighted(table, count, xyc, match, member, object, n_fused, type_count, conf_ref, conf_floor, obs, prior, stream):
+    n, k, cap, _ = xyc.shape
+    _lib.check(_lib.lib().okp_rig_bearings_weighted(count.data_ptr(), xyc.data_ptr(), match.data_ptr(), member.data_ptr(), object.data_ptr(), n_fused.data_ptr(),
+                                                    table.data_ptr(), table.shape[0], n // 2, k, cap, object.shape[1], _int32s(type_count, max(1, k - 1)), conf_ref,
+                                                    conf_floor, obs.data_ptr(), prior.data_ptr(), stream), "okp_rig_bearings_weighted")
+
+
+def refine_pose_views_weighted(obs, prior, views, views_each, pose, assignment, n_obj, model, sigma_px, huber_px, iters, damping, pose_out, fit, n_obs, n_inlier,
+                               weight, information, status, stream):
+    b, max_obj, s, v, _ = obs.shape
+    _lib.check(_lib.lib().okp_refine_pose_views_weighted(obs.data_ptr(), prior.data_ptr(), views.data_ptr(), views_each, pose.data_ptr(), assignment.data_ptr(),
+                                                         n_obj.data_ptr(), model.data_ptr(), sigma_px, huber_px, iters, damping, b, max_obj, s, v, pose_out.data_ptr(),
+                                                         fit.data_ptr(), n_obs.data_ptr(), _ptr(n_inlier), _ptr(weight), information.data_ptr(), status.data_ptr(),
+                                                         stream), "okp_refine_pose_views_weighted")
+
+
+def refine_pose_views_weighted_wide(obs, prior, views, views_each, pose, assignment, n_obj, model, sigma_px, huber_px, iters, damping, pose_out, fit, n_obs, n_inlier,
+                                    weight, information, status, stream):
+    b, max_obj, s, v, _ = obs.shape
+    _lib.check(_lib.lib().okp_refine_pose_views_weighted_wide(obs.data_ptr(), prior.data_ptr(), views.data_ptr(), views_each, pose.data_ptr(), assignment.data_ptr(),
+                                                              n_obj.data_ptr(), model.data_ptr(), sigma_px, huber_px, iters, damping, b, max_obj, s, v, pose_out.data_ptr(),
+                                                              fit.data_ptr(), n_obs.data_ptr(), _ptr(n_inlier), _ptr(weight), information.data_ptr(), status.data_ptr(),
+                                                              stream), "okp_refine_pose_views_weighted_wide")
+
+
+def window_push_weighted(camera, tab, assignment, status, meas_of, track_i, track_f, track_pose, T_WC, min_views, max_speed, conf_ref, conf_floor, win_obs,
+                         win_prior, win_views, win_i, n_views, start, stream):
+    b, max_obj, s, _ = tab.shape
+    _lib.check(_lib.lib().okp_window_push_weighted(tab.data_ptr(), assignment.data_ptr(), status.data_ptr(), meas_of.data_ptr(), track_i.data_ptr(),
+                                                   track_f.data_ptr(), track_pose.data_ptr(), T_WC.data_ptr(), _camera(camera), b, max_obj, s, win_obs.shape[1],
+                                                   win_obs.shape[3], min_views, max_speed, conf_ref, conf_floor, win_obs.data_ptr(), win_prior.data_ptr(),
+                                                   win_views.data_ptr(), win_i.data_ptr(), n_views.data_ptr(), start.data_ptr(), stream), "okp_window_push_weighted")
+
+
+def window_push_views_weighted(obs, prior, assignment, status, meas_of, track_i, track_f, track_pose, T_WB, views, ticks, min_views, max_speed, win_obs,
+                               win_prior, win_views, win_i, n_views, start, stream):
+    b, max_obj, s, v, _ = obs.shape
+    _lib.check(_lib.lib().okp_window_push_views_weighted(obs.data_ptr(), prior.data_ptr(), assignment.data_ptr(), status.data_ptr(), meas_of.data_ptr(),
+                                                         track_i.data_ptr(), track_f.data_ptr(), track_pose.data_ptr(), T_WB.data_ptr(), views.data_ptr(), b, max_obj,
+                                                         s, win_obs.shape[1], ticks, v, min_views, max_speed, win_obs.data_ptr(), win_prior.data_ptr(),
+                                                         win_views.data_ptr(), win_i.data_ptr(), n_views.data_ptr(), start.data_ptr(), stream),
+               "okp_window_push_views_weighted")
+
+
 # ---- scoring labelled scenes -----------------------------------------------------------------------------------------------------------------
 def project_labels(camera, world_points, T_WC, scale, crop_x, crop_y, labels, stream):
     _lib.check(_lib.lib().okp_project_labels(_camera(camera), world_points.data_ptr(), world_points.shape[0], T_WC.data_ptr(), T_WC.shape[0], scale, crop_x, crop_y,

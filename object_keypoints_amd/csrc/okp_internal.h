@@ -385,3 +385,8 @@ bool okp_patch_supported(const okp_conv* plan, const OkpIgemmParams& p);   // ok
 int okp_launch_igemm_patch(const okp_conv* plan, const OkpIgemmParams& p, hipStream_t stream);
 int okp_fill_patch_params(const okp_conv* plan, const OkpIgemmParams& q, OkpPatchParams& p);             // okp_igemm_patch.hip (shared by both patch kernels)
 int okp_launch_igemm_patch_x3(const okp_conv* plan, const OkpPatchParams& p, hipStream_t stream);      // okp_igemm_patch_x3.hip
+// okp_refine_views_wide.hip: okp_refine_pose_views_weighted (okp_refine_views.hip) beyond one wave of views; fn names the entry point in messages
+int okp_refine_views_weighted_wide(const char* fn, const double* obs, const double* prior, const double* views, int32_t views_each, const double* pose,
+                                   const int32_t* assignment, const int32_t* n_obj, const double* model, double sigma_px, double huber_px, int32_t iters,
+                                   double damping, int32_t B, int32_t max_obj, int32_t S, int32_t V, double* pose_out, double* fit, int32_t* n_obs,
+                                   int32_t* n_inlier, double* weight, double* information, int32_t* status, void* stream);

@@ -366,6 +366,7 @@ struct ViewsParams {
   double* pose_out; double* fit; int32_t* n_obs; double* information; int32_t* status;        // fit: [4] per object under a Huber loss, else [2]
   double c, c2;                                   // huber_px / sigma_px and its square, formed once on the host (0 without a Huber loss)
   int32_t* n_inlier; double* weight;              // the Huber instances' further outputs
+  const double* prior;                            // [B][max_obj][S][V]: the PRIOR instances' scale of every observation's squared residual (last: the other offsets stay)
 };
 
 // What a refinement against views refuses -> the parameters of its launch.  v_max: the entry point's limit on V; huber_px and views_each are

@@ -27,6 +27,11 @@
 //                                  one, or bodies built from more shared blocks than csrc/okp_pose_math.h's pose load (plain kernel) and
 //                                  `information` writer (both), changed the instances' instructions and their time (docs/EXPERIMENTS.md);
 //                                  the launch parameters and the argument checks of all four entry points are shared (refine_views_params).
+//   PRIOR instances (okp_refine_pose_views_weighted, okp_rig_bearings_weighted; contract in include/okp.h): a template flag on the two
+//                                  refinement kernels - the lane keeps the priors of its observations in registers, 1.0 where it has none,
+//                                  and the factor scales the first j of every product (plain) or the Huber weight, so with all priors
+//                                  1.0 the bits are the instance's without the flag - and on the bearings kernel, whose phase 2 then also
+//                                  writes every entry's prior.  Under `if constexpr`: the instances without the flag are the code they were.
 // fp64, no atomics, no host wait; the summation order is fixed, so the bits are the same on every run.
 #include "okp_pose_math.h"           // PoseTypes, pose_types, ViewsParams, load_pose, refine_step, view_term, huber_weight, write_information
 
@@ -42,8 +47,11 @@ struct BearingsParams {
   int32_t n_pairs, cap, cap_f;
   PoseTypes types;
   double* obs;
+  double* prior; double conf_ref, conf_floor;    // the PRIOR instance's (okp_rig_bearings_weighted); last, so the other offsets stay
 };
 
+// PRIOR: phase 2 also writes every entry's prior from the peak's confidence (okp_rig_bearings_weighted); the plain instance is the code it was
+template <bool PRIOR>
 __global__ __launch_bounds__(OKP_BEARINGS_THREADS) void okp_rig_bearings_kernel(const BearingsParams p) {
   __shared__ int32_t peak[OKP_POSE_MAX_POINTS][2 * OKP_RIG_MAX_PAIRS];      // [s][v]: the peak of camera v that slot s saw, or -1
   const int o = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -86,6 +94,7 @@ __global__ __launch_bounds__(OKP_BEARINGS_THREADS) void okp_rig_bearings_kernel(
     const int s = e / V, v = e - s * V;
     const int idx = peak[s][v];
     double bx = nan, by = nan;
+    [[maybe_unused]] double a = nan;
     if (idx >= 0) {
       int k = 0;
       while (k + 1 < K && s >= p.types.base[k + 1]) ++k;
@@ -96,9 +105,15 @@ __global__ __launch_bounds__(OKP_BEARINGS_THREADS) void okp_rig_bearings_kernel(
       okp_undistort_point(cam, (double)src[0], (double)src[1], xu, yu);
       bx = (xu - cam.cx) / cam.fx;
       by = (yu - cam.cy) / cam.fy;
+      if constexpr (PRIOR) {                                      // comparisons and one division; a NaN confidence falls to the floor
+        const double c = (double)src[2];
+        a = c >= p.conf_ref ? 1.0 : ((c > p.conf_floor ? c : p.conf_floor) / p.conf_ref);
+        if (bx != bx && by != by) a = nan;
+      }
     }
     double* dst = p.obs + ((size_t)o * S * V + e) * 2;
     dst[0] = bx; dst[1] = by;
+    if constexpr (PRIOR) p.prior[(size_t)o * S * V + e] = a;
   }
 }
 
@@ -112,7 +127,9 @@ __device__ __forceinline__ void views_butterfly(double (&acc)[OKP_REFINE_SUMS]) 
 
 // EACH: `views` holds one table of V rows per object (okp_refine_pose_views_each) instead of one for all; the only line that differs is the
 // address of the lane's row, so the shared-table instance is the code it was
-template <bool EACH>
+// PRIOR: every observation's squared residual is scaled by its prior (okp_refine_pose_views_weighted): the lane keeps the priors of its slots
+// in registers and scales its Jacobian rows by them; under `if constexpr`, so the instances without it are the code they were
+template <bool EACH, bool PRIOR>
 __global__ __launch_bounds__(64) void okp_refine_pose_views_kernel(const ViewsParams P) {
   const int lane = threadIdx.x;
   const size_t oi = blockIdx.x;
@@ -136,6 +153,7 @@ __global__ __launch_bounds__(64) void okp_refine_pose_views_kernel(const ViewsPa
   }
   // the object's bearings and model rows, slot by slot
   double ou[OKP_POSE_MAX_POINTS], ov[OKP_POSE_MAX_POINTS], m[OKP_POSE_MAX_POINTS][3];
+  [[maybe_unused]] double pr[PRIOR ? OKP_POSE_MAX_POINTS : 1];    // the priors of this lane's observations (1.0 where it has none)
   unsigned seen = 0u, rows = 0u;                                  // bit i: this lane observed its slot of pass i; some lane's slot of pass i has a model row
   int n_obs = 0, n_rows = 0;
   bool bad = false;
@@ -144,6 +162,7 @@ __global__ __launch_bounds__(64) void okp_refine_pose_views_kernel(const ViewsPa
 #pragma unroll
   for (int i = 0; i < OKP_POSE_MAX_POINTS; ++i) {
     ou[i] = 0.0; ov[i] = 0.0; m[i][0] = 0.0; m[i][1] = 0.0; m[i][2] = 0.0;
+    if constexpr (PRIOR) pr[i] = 1.0;
     if (i < passes) {                                             // (wave-uniform)
       const int s = grp + G * i;
       const bool slot = live && s < S;
@@ -156,6 +175,13 @@ __global__ __launch_bounds__(64) void okp_refine_pose_views_kernel(const ViewsPa
       }
       bad = bad || ((u != u) != (v != v)) || fabs(u) == inf || fabs(v) == inf;
       const bool mine = row && finite64(u) && finite64(v);
+      if constexpr (PRIOR) {
+        if (mine) {                                               // (a prior is read, and judged, only where there is an observation)
+          const double a = P.prior[(oi * S + s) * V + cam];
+          bad = bad || !(a > 0.0 && a < inf);
+          pr[i] = a;
+        }
+      }
       unsigned long long who = __ballot(mine);
       n_obs += __popcll(who);
       for (int sh = 1; sh < (1 << P.vshift); sh <<= 1) who |= who >> sh;          // a group's first lane: some lane of the group observed the slot
@@ -198,14 +224,29 @@ __global__ __launch_bounds__(64) void okp_refine_pose_views_kernel(const ViewsPa
 #pragma unroll
           for (int c = 0; c < 6; ++c) { j[0][c] = 0.0; j[1][c] = 0.0; }
         }
-        int idx = 0;
+        if constexpr (PRIOR) {                                    // a j in the place of the first j of every product: 1.0 gives the bits below
+          const double a = pr[s];
+          double aj[2][6];
 #pragma unroll
-        for (int r = 0; r < 6; ++r)
+          for (int c = 0; c < 6; ++c) { aj[0][c] = a * j[0][c]; aj[1][c] = a * j[1][c]; }
+          int idx = 0;
 #pragma unroll
-          for (int c = r; c < 6; ++c) { acc[idx] += j[0][r] * j[0][c] + j[1][r] * j[1][c]; ++idx; }
+          for (int r = 0; r < 6; ++r)
 #pragma unroll
-        for (int r = 0; r < 6; ++r) acc[21 + r] += j[0][r] * e[0] + j[1][r] * e[1];
-        acc[27] += e[0] * e[0] + e[1] * e[1];
+            for (int c = r; c < 6; ++c) { acc[idx] += aj[0][r] * j[0][c] + aj[1][r] * j[1][c]; ++idx; }
+#pragma unroll
+          for (int r = 0; r < 6; ++r) acc[21 + r] += aj[0][r] * e[0] + aj[1][r] * e[1];
+          acc[27] += a * (e[0] * e[0] + e[1] * e[1]);
+        } else {
+          int idx = 0;
+#pragma unroll
+          for (int r = 0; r < 6; ++r)
+#pragma unroll
+            for (int c = r; c < 6; ++c) { acc[idx] += j[0][r] * j[0][c] + j[1][r] * j[1][c]; ++idx; }
+#pragma unroll
+          for (int r = 0; r < 6; ++r) acc[21 + r] += j[0][r] * e[0] + j[1][r] * e[1];
+          acc[27] += e[0] * e[0] + e[1] * e[1];
+        }
       }
       if (status == 0 && __ballot(behind) != 0ull) status = OKP_REFINE_BEHIND;
       views_butterfly(acc);
@@ -256,7 +297,7 @@ __device__ __forceinline__ void robust_butterfly(double (&acc)[OKP_REFINE_SUMS])
     for (int i = 0; i < 29; ++i) acc[i] += __shfl_xor(acc[i], off);
 }
 
-template <bool EACH>
+template <bool EACH, bool PRIOR>
 __global__ __launch_bounds__(64) void okp_refine_pose_views_robust_kernel(const ViewsParams P) {
   const int lane = threadIdx.x;
   const size_t oi = blockIdx.x;
@@ -285,6 +326,7 @@ __global__ __launch_bounds__(64) void okp_refine_pose_views_robust_kernel(const 
     kx = row[12] / P.sigma_px; ky = row[13] / P.sigma_px;
   }
   double ou[OKP_POSE_MAX_POINTS], ov[OKP_POSE_MAX_POINTS], m[OKP_POSE_MAX_POINTS][3];
+  [[maybe_unused]] double pr[PRIOR ? OKP_POSE_MAX_POINTS : 1];    // the priors of this lane's observations (1.0 where it has none)
   unsigned seen = 0u, rows = 0u;
   int n_obs = 0, n_rows = 0;
   bool bad = false;
@@ -293,6 +335,7 @@ __global__ __launch_bounds__(64) void okp_refine_pose_views_robust_kernel(const 
 #pragma unroll
   for (int i = 0; i < OKP_POSE_MAX_POINTS; ++i) {
     ou[i] = 0.0; ov[i] = 0.0; m[i][0] = 0.0; m[i][1] = 0.0; m[i][2] = 0.0;
+    if constexpr (PRIOR) pr[i] = 1.0;
     if (i < passes) {
       const int s = grp + G * i;
       const bool slot = live && s < S;
@@ -305,6 +348,13 @@ __global__ __launch_bounds__(64) void okp_refine_pose_views_robust_kernel(const 
       }
       bad = bad || ((u != u) != (v != v)) || fabs(u) == inf || fabs(v) == inf;
       const bool mine = row && finite64(u) && finite64(v);
+      if constexpr (PRIOR) {
+        if (mine) {                                               // (a prior is read, and judged, only where there is an observation)
+          const double a = P.prior[(oi * S + s) * V + cam];
+          bad = bad || !(a > 0.0 && a < inf);
+          pr[i] = a;
+        }
+      }
       unsigned long long who = __ballot(mine);
       n_obs += __popcll(who);
       for (int sh = 1; sh < (1 << P.vshift); sh <<= 1) who |= who >> sh;
@@ -340,11 +390,13 @@ __global__ __launch_bounds__(64) void okp_refine_pose_views_robust_kernel(const 
 #pragma unroll
           for (int q = 0; q < 6; ++q) { j[0][q] = 0.0; j[1][q] = 0.0; }
         }
-        const double sq = e[0] * e[0] + e[1] * e[1];             // (0 for a lane without the observation: an inlier that adds nothing)
+        double sq = e[0] * e[0] + e[1] * e[1];                   // (0 for a lane without the observation: an inlier that adds nothing)
+        if constexpr (PRIOR) sq = pr[s] * sq;                     // the whitened residual: the Huber rule is applied to it
         const bool inlier = sq <= c2;
-        const double w = huber_weight(sq, c, c2);
+        double w = huber_weight(sq, c, c2);
         const double rho = inlier ? sq : two_c * sqrt(sq) - c2;
         n_inlier += __popcll(__ballot(mine && inlier));
+        if constexpr (PRIOR) w = pr[s] * w;                       // the terms' weight is a w_h (the weight OUTPUT stays w_h)
         double wj[2][6];
 #pragma unroll
         for (int q = 0; q < 6; ++q) { wj[0][q] = w * j[0][q]; wj[1][q] = w * j[1][q]; }
@@ -381,7 +433,9 @@ __global__ __launch_bounds__(64) void okp_refine_pose_views_robust_kernel(const 
         double w = nan;
         if (ok && ((seen >> i) & 1u)) {
           const ViewTerm T = view_term(R, t, rv, tv, kx, ky, m[i][0], m[i][1], m[i][2], ou[i], ov[i]);
-          w = huber_weight(T.e0 * T.e0 + T.e1 * T.e1, c, c2);
+          double sq = T.e0 * T.e0 + T.e1 * T.e1;
+          if constexpr (PRIOR) sq = pr[i] * sq;
+          w = huber_weight(sq, c, c2);
         }
         wrow[(size_t)s * V] = w;
       }
@@ -420,10 +474,11 @@ __global__ __launch_bounds__(64) void okp_refine_pose_views_robust_kernel(const 
 
 }  // namespace
 
-extern "C" int okp_rig_bearings(const int32_t* count, const float* xyc, const int32_t* match, const int32_t* member, const int32_t* object,
-                                const int32_t* n_fused, const okp_stereo_pair* table, int32_t n_table, int32_t n_pairs, int32_t K, int32_t cap,
-                                int32_t cap_f, const int32_t* type_count, double* obs, void* stream) {
-  const char* fn = "okp_rig_bearings";
+// okp_rig_bearings and okp_rig_bearings_weighted: one kernel, the second instance also writes the priors
+static int rig_bearings_launch(const char* fn, const char* what, const int32_t* count, const float* xyc, const int32_t* match, const int32_t* member,
+                               const int32_t* object, const int32_t* n_fused, const okp_stereo_pair* table, int32_t n_table, int32_t n_pairs, int32_t K,
+                               int32_t cap, int32_t cap_f, const int32_t* type_count, bool weighted, double conf_ref, double conf_floor, double* obs,
+                               double* prior, void* stream) {
   BearingsParams p = {};
   if (n_pairs < 1 || n_pairs > OKP_RIG_MAX_PAIRS) { okp_set_error("%s: n_pairs = %d outside [1, %d]", fn, n_pairs, OKP_RIG_MAX_PAIRS); return OKP_EINVAL; }
   int rc = pose_types(fn, type_count, K, OKP_RIG_MAX_TYPES, p.types, nullptr);
@@ -432,14 +487,40 @@ extern "C" int okp_rig_bearings(const int32_t* count, const float* xyc, const in
   if (cap_f < 1 || cap_f > OKP_RIG_MAX_FUSED) { okp_set_error("%s: cap_f = %d outside [1, %d]", fn, cap_f, OKP_RIG_MAX_FUSED); return OKP_EINVAL; }
   if (n_table < 1) { okp_set_error("%s: n_table = %d; a calibration table holds at least one stereo pair", fn, n_table); return OKP_EINVAL; }
   if (n_table > 1 && n_table < n_pairs) { okp_set_error("%s: n_table = %d calibrations for n_pairs = %d pairs (one entry serves every pair)", fn, n_table, n_pairs); return OKP_EINVAL; }
+  if (weighted && !(conf_ref > 0.0 && conf_ref < __builtin_inf())) {
+    okp_set_error("%s: conf_ref = %g must be positive and finite (the confidence from which a peak has the full weight)", fn, conf_ref);
+    return OKP_EINVAL;
+  }
+  if (weighted && !(conf_floor > 0.0 && conf_floor <= conf_ref)) {
+    okp_set_error("%s: conf_floor = %g outside (0, conf_ref = %g]", fn, conf_floor, conf_ref);
+    return OKP_EINVAL;
+  }
   const struct { const void* ptr; const char* name; } required[] = {
       {count, "count"}, {xyc, "xyc"}, {match, "match"}, {member, "member"}, {object, "object"}, {n_fused, "n_fused"}, {table, "table"}, {obs, "obs"}};
   for (const auto& r : required)
     if (!r.ptr) { okp_set_error("%s: null %s", fn, r.name); return OKP_EINVAL; }
+  if (weighted && !prior) { okp_set_error("%s: null prior", fn); return OKP_EINVAL; }
   p.count = count; p.xyc = xyc; p.match = match; p.member = member; p.object = object; p.n_fused = n_fused;
   p.table = table; p.n_table = n_table; p.n_pairs = n_pairs; p.cap = cap; p.cap_f = cap_f; p.obs = obs;
-  hipLaunchKernelGGL(okp_rig_bearings_kernel, dim3(cap_f), dim3(OKP_BEARINGS_THREADS), 0, (hipStream_t)stream, p);
-  return okp_check_hip(hipGetLastError(), "okp_rig_bearings launch");
+  p.prior = prior; p.conf_ref = conf_ref; p.conf_floor = conf_floor;
+  if (weighted) hipLaunchKernelGGL(okp_rig_bearings_kernel<true>, dim3(cap_f), dim3(OKP_BEARINGS_THREADS), 0, (hipStream_t)stream, p);
+  else hipLaunchKernelGGL(okp_rig_bearings_kernel<false>, dim3(cap_f), dim3(OKP_BEARINGS_THREADS), 0, (hipStream_t)stream, p);
+  return okp_check_hip(hipGetLastError(), what);
+}
+
+extern "C" int okp_rig_bearings(const int32_t* count, const float* xyc, const int32_t* match, const int32_t* member, const int32_t* object,
+                                const int32_t* n_fused, const okp_stereo_pair* table, int32_t n_table, int32_t n_pairs, int32_t K, int32_t cap,
+                                int32_t cap_f, const int32_t* type_count, double* obs, void* stream) {
+  return rig_bearings_launch("okp_rig_bearings", "okp_rig_bearings launch", count, xyc, match, member, object, n_fused, table, n_table, n_pairs, K, cap, cap_f,
+                             type_count, false, 0.0, 0.0, obs, nullptr, stream);
+}
+
+extern "C" int okp_rig_bearings_weighted(const int32_t* count, const float* xyc, const int32_t* match, const int32_t* member, const int32_t* object,
+                                         const int32_t* n_fused, const okp_stereo_pair* table, int32_t n_table, int32_t n_pairs, int32_t K, int32_t cap,
+                                         int32_t cap_f, const int32_t* type_count, double conf_ref, double conf_floor, double* obs, double* prior,
+                                         void* stream) {
+  return rig_bearings_launch("okp_rig_bearings_weighted", "okp_rig_bearings_weighted launch", count, xyc, match, member, object, n_fused, table, n_table, n_pairs,
+                             K, cap, cap_f, type_count, true, conf_ref, conf_floor, obs, prior, stream);
 }
 
 // the four one-wave entry points: plain or Huber (huber_px), one views table for every object or one per object
@@ -453,10 +534,10 @@ static int refine_views_launch(const char* fn, const char* what, const double* o
   if (rc) return rc;
   const dim3 grid((unsigned)((size_t)B * max_obj)), block(64);
   const hipStream_t st = (hipStream_t)stream;
-  if (!huber_px && each) hipLaunchKernelGGL(okp_refine_pose_views_kernel<true>, grid, block, 0, st, p);
-  else if (!huber_px) hipLaunchKernelGGL(okp_refine_pose_views_kernel<false>, grid, block, 0, st, p);
-  else if (each) hipLaunchKernelGGL(okp_refine_pose_views_robust_kernel<true>, grid, block, 0, st, p);
-  else hipLaunchKernelGGL(okp_refine_pose_views_robust_kernel<false>, grid, block, 0, st, p);
+  if (!huber_px && each) hipLaunchKernelGGL((okp_refine_pose_views_kernel<true, false>), grid, block, 0, st, p);
+  else if (!huber_px) hipLaunchKernelGGL((okp_refine_pose_views_kernel<false, false>), grid, block, 0, st, p);
+  else if (each) hipLaunchKernelGGL((okp_refine_pose_views_robust_kernel<true, false>), grid, block, 0, st, p);
+  else hipLaunchKernelGGL((okp_refine_pose_views_robust_kernel<false, false>), grid, block, 0, st, p);
   return okp_check_hip(hipGetLastError(), what);
 }
 
@@ -480,4 +561,29 @@ extern "C" int okp_refine_pose_views_robust(const double* obs, const double* vie
                                             double* information, int32_t* status, void* stream) {
   return refine_views_launch("okp_refine_pose_views_robust", "okp_refine_pose_views_robust launch", obs, views, &views_each, views_each != 0, pose, assignment, n_obj,
                              model, sigma_px, &huber_px, iters, damping, B, max_obj, S, V, pose_out, fit, n_obs, n_inlier, weight, information, status, stream);
+}
+
+// The weighted refinement: up to one wave of views the PRIOR instances of the kernels above, beyond it the wide kernel's (csrc/okp_refine_views_wide.hip)
+extern "C" int okp_refine_pose_views_weighted(const double* obs, const double* prior, const double* views, int32_t views_each, const double* pose,
+                                              const int32_t* assignment, const int32_t* n_obj, const double* model, double sigma_px, double huber_px, int32_t iters,
+                                              double damping, int32_t B, int32_t max_obj, int32_t S, int32_t V, double* pose_out, double* fit, int32_t* n_obs,
+                                              int32_t* n_inlier, double* weight, double* information, int32_t* status, void* stream) {
+  const char* fn = "okp_refine_pose_views_weighted";
+  if (V > OKP_REFINE_MAX_VIEWS)
+    return okp_refine_views_weighted_wide(fn, obs, prior, views, views_each, pose, assignment, n_obj, model, sigma_px, huber_px, iters, damping, B, max_obj, S, V,
+                                          pose_out, fit, n_obs, n_inlier, weight, information, status, stream);
+  ViewsParams p;
+  const int rc = refine_views_params(fn, obs, views, pose, assignment, n_obj, model, sigma_px, &huber_px, true, &views_each, iters, damping, B, max_obj, S, V,
+                                     OKP_REFINE_WIDE_MAX_VIEWS, pose_out, fit, n_obs, n_inlier, weight, information, status, p);
+  if (rc) return rc;
+  if (!prior) { okp_set_error("%s: null prior", fn); return OKP_EINVAL; }
+  p.prior = prior;
+  const dim3 grid((unsigned)((size_t)B * max_obj)), block(64);
+  const hipStream_t st = (hipStream_t)stream;
+  const bool robust = huber_px > 0.0, each = views_each != 0;
+  if (!robust && each) hipLaunchKernelGGL((okp_refine_pose_views_kernel<true, true>), grid, block, 0, st, p);
+  else if (!robust) hipLaunchKernelGGL((okp_refine_pose_views_kernel<false, true>), grid, block, 0, st, p);
+  else if (each) hipLaunchKernelGGL((okp_refine_pose_views_robust_kernel<true, true>), grid, block, 0, st, p);
+  else hipLaunchKernelGGL((okp_refine_pose_views_robust_kernel<false, true>), grid, block, 0, st, p);
+  return okp_check_hip(hipGetLastError(), "okp_refine_pose_views_weighted launch");
 }

@@ -39,6 +39,7 @@ struct WideParams {
   double sigma_px, damping;
   double c, c2;                                   // huber_px / sigma_px and its square, formed on the host (the Huber instance)
   double* pose_out; double* fit; int32_t* n_obs; int32_t* n_inlier; double* weight; double* information; int32_t* status;
+  const double* prior;                            // [B][max_obj][S][V], the PRIOR instances' (last: the other offsets stay)
 };
 
 // x as a scalar: every lane of the workgroup holds the same bits of the iterate (R, t), so the wave's copy can live in scalar registers - the
@@ -49,7 +50,12 @@ __device__ __forceinline__ double wave_uniform(double x) {
   return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
 }
 
-template <bool ROBUST>
+// PRIOR: every observation's squared residual is scaled by its prior (okp_refine_pose_views_weighted).  Sixteen more fp64 values a lane do not
+// fit its 256 registers, so the object's priors are staged in LDS once, [slot][thread] (64 KB): a lane writes and reads only its own view's
+// entries, so they need no barrier, and the address is one register with the slot in the instruction's offset.  The precheck of the priors
+// joins the workgroup-wide OR of the bearings' precheck; nothing else that decides control flow depends on them.  Under `if constexpr`: the
+// other instances are the code they were
+template <bool ROBUST, bool PRIOR>
 __global__ __launch_bounds__(OKP_REFINE_WIDE_MAX_VIEWS) void okp_refine_pose_views_wide_kernel(const WideParams P) {
   constexpr int NS = ROBUST ? 29 : 28;            // H, g, the cost (and the plain cost next to the robust one)
   __shared__ double mdl[OKP_POSE_MAX_POINTS][3];  // the model row of every slot (zeros without one)
@@ -57,6 +63,7 @@ __global__ __launch_bounds__(OKP_REFINE_WIDE_MAX_VIEWS) void okp_refine_pose_vie
   __shared__ unsigned w_seen[OKP_WIDE_WAVES];     // before the loop: bit s - some lane of the wave observed slot s
   __shared__ int w_obs[OKP_WIDE_WAVES], w_skip[OKP_WIDE_WAVES];
   __shared__ int w_behind[OKP_WIDE_WAVES], w_inlier[OKP_WIDE_WAVES];          // per iterate
+  [[maybe_unused]] __shared__ double pri[PRIOR ? OKP_POSE_MAX_POINTS : 1][PRIOR ? OKP_REFINE_WIDE_MAX_VIEWS : 1];     // (PRIOR) [s][tid]: 1.0 without an observation
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nw = blockDim.x >> 6;
   const size_t oi = blockIdx.x;
   const int b = (int)(oi / P.max_obj), o = (int)(oi - (size_t)b * P.max_obj);
@@ -111,6 +118,14 @@ __global__ __launch_bounds__(OKP_REFINE_WIDE_MAX_VIEWS) void okp_refine_pose_vie
       }
       bad = bad || ((u != u) != (v != v)) || fabs(u) == inf || fabs(v) == inf;
       const bool mine = ((rows >> s) & 1u) && finite64(u) && finite64(v);
+      if constexpr (PRIOR) {
+        double a = 1.0;
+        if (mine) {                               // (a prior is read, and judged, only where there is an observation)
+          a = P.prior[(oi * S + s) * V + tid];
+          bad = bad || !(a > 0.0 && a < inf);
+        }
+        pri[s][tid] = a;
+      }
       const unsigned long long who = __ballot(mine);
       n_obs_w += __popcll(who);
       if (who != 0ull) seen_w |= 1u << s;
@@ -148,12 +163,19 @@ __global__ __launch_bounds__(OKP_REFINE_WIDE_MAX_VIEWS) void okp_refine_pose_vie
 #pragma unroll
           for (int q = 0; q < 6; ++q) { j[0][q] = 0.0; j[1][q] = 0.0; }
         }
+        [[maybe_unused]] double a = 1.0;
+        if constexpr (PRIOR) a = pri[s][tid];     // (1.0 for a lane without the observation: its terms are zeros)
         if constexpr (ROBUST) {
-          const double sq = e[0] * e[0] + e[1] * e[1];           // (0 for a lane without the observation: an inlier that adds nothing)
+          double sq = e[0] * e[0] + e[1] * e[1];                 // (0 for a lane without the observation: an inlier that adds nothing)
+          if constexpr (PRIOR) sq = a * sq;                      // the whitened residual: the Huber rule is applied to it
           const bool inlier = sq <= c2;
-          const double w = huber_weight(sq, c, c2);
+          double w = huber_weight(sq, c, c2);
           const double rho = inlier ? sq : two_c * sqrt(sq) - c2;
           inlier_w += __popcll(__ballot(mine && inlier));
+          if constexpr (PRIOR) {                                 // the terms' weight is a w_h (the weight OUTPUT stays w_h); the prior is read
+            __asm__ volatile("" ::: "memory");                   // again, not held over the square root and the division: three registers
+            w = pri[s][tid] * w;                                 // that this instance does not have (tests/test_refine_weighted_args.py holds the build's report to no scratch)
+          }
           int idx = 0;
 #pragma unroll
           for (int r = 0; r < 6; ++r) {           // (w j of one row at a time: the products of the one-wave kernel, fewer live registers)
@@ -164,6 +186,16 @@ __global__ __launch_bounds__(OKP_REFINE_WIDE_MAX_VIEWS) void okp_refine_pose_vie
           }
           acc[27] += rho;
           acc[28] += sq;
+        } else if constexpr (PRIOR) {             // a j in the place of the first j of every product: 1.0 gives the bits of the plain instance
+          int idx = 0;
+#pragma unroll
+          for (int r = 0; r < 6; ++r) {
+            const double aj0 = a * j[0][r], aj1 = a * j[1][r];
+#pragma unroll
+            for (int q = r; q < 6; ++q) { acc[idx] += aj0 * j[0][q] + aj1 * j[1][q]; ++idx; }
+            acc[21 + r] += aj0 * e[0] + aj1 * e[1];
+          }
+          acc[27] += a * (e[0] * e[0] + e[1] * e[1]);
         } else {
           int idx = 0;
 #pragma unroll
@@ -223,7 +255,9 @@ __global__ __launch_bounds__(OKP_REFINE_WIDE_MAX_VIEWS) void okp_refine_pose_vie
           double w = nan;
           if (ok && ((seen >> s) & 1u)) {
             const ViewTerm T = view_term(R, t, rv, tv, kx, ky, mdl[s][0], mdl[s][1], mdl[s][2], ou[s], ov[s]);
-            w = huber_weight(T.e0 * T.e0 + T.e1 * T.e1, c, c2);
+            double sq = T.e0 * T.e0 + T.e1 * T.e1;
+            if constexpr (PRIOR) sq = pri[s][tid] * sq;
+            w = huber_weight(sq, c, c2);
           }
           wrow[(size_t)s * V] = w;
         }
@@ -269,20 +303,51 @@ __global__ __launch_bounds__(OKP_REFINE_WIDE_MAX_VIEWS) void okp_refine_pose_vie
 
 }  // namespace
 
-extern "C" int okp_refine_pose_views_wide(const double* obs, const double* views, int32_t views_each, const double* pose, const int32_t* assignment,
-                                          const int32_t* n_obj, const double* model, double sigma_px, double huber_px, int32_t iters, double damping, int32_t B,
-                                          int32_t max_obj, int32_t S, int32_t V, double* pose_out, double* fit, int32_t* n_obs, int32_t* n_inlier, double* weight,
-                                          double* information, int32_t* status, void* stream) {
+// okp_refine_pose_views_wide (prior = null) and, for okp_refine_pose_views_weighted beyond one wave of views, its PRIOR instances
+static int wide_launch(const char* fn, const char* what, bool weighted, const double* obs, const double* prior, const double* views, int32_t views_each,
+                       const double* pose, const int32_t* assignment, const int32_t* n_obj, const double* model, double sigma_px, double huber_px, int32_t iters,
+                       double damping, int32_t B, int32_t max_obj, int32_t S, int32_t V, double* pose_out, double* fit, int32_t* n_obs, int32_t* n_inlier,
+                       double* weight, double* information, int32_t* status, void* stream) {
   ViewsParams v;
-  const int rc = refine_views_params("okp_refine_pose_views_wide", obs, views, pose, assignment, n_obj, model, sigma_px, &huber_px, true, &views_each, iters, damping, B,
+  const int rc = refine_views_params(fn, obs, views, pose, assignment, n_obj, model, sigma_px, &huber_px, true, &views_each, iters, damping, B,
                                      max_obj, S, V, OKP_REFINE_WIDE_MAX_VIEWS, pose_out, fit, n_obs, n_inlier, weight, information, status, v);
   if (rc) return rc;
+  if (weighted && !prior) { okp_set_error("%s: null prior", fn); return OKP_EINVAL; }
   WideParams p = {};
   p.obs = v.obs; p.views = v.views; p.pose = v.pose; p.assignment = v.assignment; p.n_obj = v.n_obj; p.model = v.model;
   p.max_obj = v.max_obj; p.S = v.S; p.V = v.V; p.iters = v.iters; p.each = v.each; p.sigma_px = v.sigma_px; p.damping = v.damping; p.c = v.c; p.c2 = v.c2;
   p.pose_out = v.pose_out; p.fit = v.fit; p.n_obs = v.n_obs; p.n_inlier = v.n_inlier; p.weight = v.weight; p.information = v.information; p.status = v.status;
+  p.prior = prior;
   const dim3 grid((unsigned)((size_t)B * max_obj)), block(64u * (unsigned)((V + 63) / 64));
-  if (huber_px > 0.0) hipLaunchKernelGGL(okp_refine_pose_views_wide_kernel<true>, grid, block, 0, (hipStream_t)stream, p);
-  else hipLaunchKernelGGL(okp_refine_pose_views_wide_kernel<false>, grid, block, 0, (hipStream_t)stream, p);
-  return okp_check_hip(hipGetLastError(), "okp_refine_pose_views_wide launch");
+  const hipStream_t st = (hipStream_t)stream;
+  if (weighted && huber_px > 0.0) hipLaunchKernelGGL((okp_refine_pose_views_wide_kernel<true, true>), grid, block, 0, st, p);
+  else if (weighted) hipLaunchKernelGGL((okp_refine_pose_views_wide_kernel<false, true>), grid, block, 0, st, p);
+  else if (huber_px > 0.0) hipLaunchKernelGGL((okp_refine_pose_views_wide_kernel<true, false>), grid, block, 0, st, p);
+  else hipLaunchKernelGGL((okp_refine_pose_views_wide_kernel<false, false>), grid, block, 0, st, p);
+  return okp_check_hip(hipGetLastError(), what);
+}
+
+extern "C" int okp_refine_pose_views_wide(const double* obs, const double* views, int32_t views_each, const double* pose, const int32_t* assignment,
+                                          const int32_t* n_obj, const double* model, double sigma_px, double huber_px, int32_t iters, double damping, int32_t B,
+                                          int32_t max_obj, int32_t S, int32_t V, double* pose_out, double* fit, int32_t* n_obs, int32_t* n_inlier, double* weight,
+                                          double* information, int32_t* status, void* stream) {
+  return wide_launch("okp_refine_pose_views_wide", "okp_refine_pose_views_wide launch", false, obs, nullptr, views, views_each, pose, assignment, n_obj, model, sigma_px,
+                     huber_px, iters, damping, B, max_obj, S, V, pose_out, fit, n_obs, n_inlier, weight, information, status, stream);
+}
+
+// okp_refine_pose_views_weighted on the wide kernel's PRIOR instances whatever V is: with all priors 1.0 the bits of okp_refine_pose_views_wide
+extern "C" int okp_refine_pose_views_weighted_wide(const double* obs, const double* prior, const double* views, int32_t views_each, const double* pose,
+                                                   const int32_t* assignment, const int32_t* n_obj, const double* model, double sigma_px, double huber_px, int32_t iters,
+                                                   double damping, int32_t B, int32_t max_obj, int32_t S, int32_t V, double* pose_out, double* fit, int32_t* n_obs,
+                                                   int32_t* n_inlier, double* weight, double* information, int32_t* status, void* stream) {
+  return wide_launch("okp_refine_pose_views_weighted_wide", "okp_refine_pose_views_weighted_wide launch", true, obs, prior, views, views_each, pose, assignment, n_obj, model,
+                     sigma_px, huber_px, iters, damping, B, max_obj, S, V, pose_out, fit, n_obs, n_inlier, weight, information, status, stream);
+}
+
+int okp_refine_views_weighted_wide(const char* fn, const double* obs, const double* prior, const double* views, int32_t views_each, const double* pose,
+                                   const int32_t* assignment, const int32_t* n_obj, const double* model, double sigma_px, double huber_px, int32_t iters,
+                                   double damping, int32_t B, int32_t max_obj, int32_t S, int32_t V, double* pose_out, double* fit, int32_t* n_obs,
+                                   int32_t* n_inlier, double* weight, double* information, int32_t* status, void* stream) {
+  return wide_launch(fn, "okp_refine_pose_views_weighted launch", true, obs, prior, views, views_each, pose, assignment, n_obj, model, sigma_px, huber_px, iters,
+                     damping, B, max_obj, S, V, pose_out, fit, n_obs, n_inlier, weight, information, status, stream);
 }

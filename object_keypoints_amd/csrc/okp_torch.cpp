@@ -907,6 +907,144 @@ void refine_pose_views_wide(const Tensor& obs, const Tensor& views, int64_t view
            "okp_refine_pose_views_wide");
 }
 
+// ---- the views refinements weighted by the peaks' confidences (include/okp.h: okp_refine_pose_views_weighted and its three producers) ----
+
+// rig_bearings with conf_ref / conf_floor -> obs [cap_f,S,2P,2] and prior [cap_f,S,2P] float64
+void rig_bearings_weighted(const Tensor& table, const Tensor& count, const Tensor& xyc, const Tensor& match, const Tensor& member, const Tensor& object,
+                           const Tensor& n_fused, at::IntArrayRef type_count, double conf_ref, double conf_floor, const Tensor& obs, const Tensor& prior, int64_t stream) {
+  const int64_t P = stereo_tick_pairs(count, xyc);
+  const int32_t n_table = stereo_table_size(table);
+  check_dev(match, at::kInt, "match"); check_dev(member, at::kInt, "member"); check_dev(object, at::kInt, "object"); check_dev(n_fused, at::kInt, "n_fused");
+  check_dev(obs, at::kDouble, "obs"); check_dev(prior, at::kDouble, "prior");
+  const int64_t K = xyc.size(1), cap = xyc.size(2);
+  TORCH_CHECK(object.dim() == 2 && object.size(0) == K, "okp: object is [K,cap_f] int32 (rig_fuse)");
+  const int64_t cap_f = object.size(1);
+  int64_t S = 1;
+  for (auto c : type_count) S += c;
+  TORCH_CHECK((int64_t)type_count.size() == K - 1, "okp: type_count has K-1 entries");
+  TORCH_CHECK(match.numel() == P * K * cap && member.numel() == P * K * cap && n_fused.numel() == K && obs.numel() == cap_f * S * 2 * P * 2 &&
+              prior.numel() == cap_f * S * 2 * P,
+              "okp: rig_bearings_weighted buffers are match and member [P,K,cap], n_fused [K] int32, obs [cap_f,S,2P,2] and prior [cap_f,S,2P] float64");
+  std::vector<int32_t> tc(type_count.begin(), type_count.end());
+  tc.push_back(0);                                  // (K = 1: a non-null pointer for the entry point to refuse K with)
+  check_rc(okp_rig_bearings_weighted(count.data_ptr<int32_t>(), xyc.data_ptr<float>(), match.data_ptr<int32_t>(), member.data_ptr<int32_t>(), object.data_ptr<int32_t>(),
+                                     n_fused.data_ptr<int32_t>(), reinterpret_cast<const okp_stereo_pair*>(table.data_ptr()), n_table, (int32_t)P, (int32_t)K, (int32_t)cap,
+                                     (int32_t)cap_f, tc.data(), conf_ref, conf_floor, obs.data_ptr<double>(), prior.data_ptr<double>(), sp(stream)),
+           "okp_rig_bearings_weighted");
+}
+
+// refine_pose_views_wide's arguments and prior [B,max_obj,S,V]
+void refine_views_weighted(bool wide, const Tensor& obs, const Tensor& prior, const Tensor& views, int64_t views_each, const Tensor& pose, const Tensor& assignment,
+                           const Tensor& n_obj, const Tensor& model, double sigma_px, double huber_px, int64_t iters, double damping, const Tensor& pose_out,
+                           const Tensor& fit, const Tensor& n_obs, const optional<Tensor>& n_inlier, const optional<Tensor>& weight, const Tensor& information,
+                           const Tensor& status, int64_t stream) {
+  check_dev(obs, at::kDouble, "obs"); check_dev(prior, at::kDouble, "prior"); check_dev(views, at::kDouble, "views"); check_dev(pose, at::kDouble, "pose");
+  check_dev(assignment, at::kInt, "assignment"); check_dev(n_obj, at::kInt, "n_obj"); check_dev(model, at::kDouble, "model"); check_dev(pose_out, at::kDouble, "pose_out");
+  check_dev(fit, at::kDouble, "fit"); check_dev(n_obs, at::kInt, "n_obs"); check_dev(information, at::kDouble, "information"); check_dev(status, at::kInt, "status");
+  if (n_inlier.has_value()) check_dev(*n_inlier, at::kInt, "n_inlier");
+  if (weight.has_value()) check_dev(*weight, at::kDouble, "weight");
+  TORCH_CHECK(obs.dim() == 5 && obs.size(4) == 2, "okp: obs is [B,max_obj,S,V,2] float64");
+  const int64_t B = obs.size(0), max_obj = obs.size(1), S = obs.size(2), V = obs.size(3);
+  const bool robust = huber_px > 0.0;
+  TORCH_CHECK(prior.numel() == B * max_obj * S * V, "okp: prior is [B,max_obj,S,V] float64, one value per entry of obs");
+  TORCH_CHECK(views_each >= INT32_MIN && views_each <= INT32_MAX, "okp: views_each does not fit an int32");
+  TORCH_CHECK((views_each != 0 && views_each != 1) || views.numel() == (views_each == 1 ? B * max_obj : 1) * V * 14,      // (any other value: the entry point refuses it)
+              "okp: refine_pose_views_weighted takes views [V,14] (views_each = 0) or [B,max_obj,V,14] (views_each = 1)");
+  TORCH_CHECK(pose.numel() == B * max_obj * 12 && assignment.numel() == B * max_obj * S && n_obj.numel() == B && model.numel() == S * 3,
+              "okp: refine_pose_views_weighted inputs are pose [B,max_obj,12], assignment [B,max_obj,S], n_obj [B] and model [S,3]");
+  TORCH_CHECK(pose_out.numel() == B * max_obj * 12 && fit.numel() == B * max_obj * (robust ? 4 : 2) && n_obs.numel() == B * max_obj &&
+              information.numel() == B * max_obj * 36 && status.numel() == B * max_obj,
+              "okp: refine_pose_views_weighted outputs are pose_out [B,max_obj,12], fit [B,max_obj,2] ([B,max_obj,4] with huber_px > 0), n_obs [B,max_obj], "
+              "information [B,max_obj,36] and status [B,max_obj]");
+  TORCH_CHECK((!n_inlier.has_value() || n_inlier->numel() == B * max_obj) && (!weight.has_value() || weight->numel() == B * max_obj * S * V),
+              "okp: refine_pose_views_weighted writes n_inlier [B,max_obj] and weight [B,max_obj,S,V] when huber_px > 0");
+  TORCH_CHECK(iters >= INT32_MIN && iters <= INT32_MAX, "okp: iters does not fit an int32");
+  TORCH_CHECK(B <= INT32_MAX && max_obj <= INT32_MAX && S <= INT32_MAX && V <= INT32_MAX, "okp: obs is too large");
+  check_rc((wide ? okp_refine_pose_views_weighted_wide : okp_refine_pose_views_weighted)(obs.data_ptr<double>(), prior.data_ptr<double>(), views.data_ptr<double>(), (int32_t)views_each, pose.data_ptr<double>(),
+                                          assignment.data_ptr<int32_t>(), n_obj.data_ptr<int32_t>(), model.data_ptr<double>(), sigma_px, huber_px, (int32_t)iters, damping,
+                                          (int32_t)B, (int32_t)max_obj, (int32_t)S, (int32_t)V, pose_out.data_ptr<double>(), fit.data_ptr<double>(), n_obs.data_ptr<int32_t>(),
+                                          n_inlier.has_value() ? n_inlier->data_ptr<int32_t>() : nullptr, weight.has_value() ? weight->data_ptr<double>() : nullptr,
+                                          information.data_ptr<double>(), status.data_ptr<int32_t>(), sp(stream)),
+           wide ? "okp_refine_pose_views_weighted_wide" : "okp_refine_pose_views_weighted");
+}
+
+void refine_pose_views_weighted(const Tensor& obs, const Tensor& prior, const Tensor& views, int64_t views_each, const Tensor& pose, const Tensor& assignment,
+                                const Tensor& n_obj, const Tensor& model, double sigma_px, double huber_px, int64_t iters, double damping, const Tensor& pose_out,
+                                const Tensor& fit, const Tensor& n_obs, const optional<Tensor>& n_inlier, const optional<Tensor>& weight, const Tensor& information,
+                                const Tensor& status, int64_t stream) {
+  refine_views_weighted(false, obs, prior, views, views_each, pose, assignment, n_obj, model, sigma_px, huber_px, iters, damping, pose_out, fit, n_obs, n_inlier, weight,
+                        information, status, stream);
+}
+
+// the same on the wide kernel's instance whatever V is (okp_refine_pose_views_weighted_wide)
+void refine_pose_views_weighted_wide(const Tensor& obs, const Tensor& prior, const Tensor& views, int64_t views_each, const Tensor& pose, const Tensor& assignment,
+                                     const Tensor& n_obj, const Tensor& model, double sigma_px, double huber_px, int64_t iters, double damping, const Tensor& pose_out,
+                                     const Tensor& fit, const Tensor& n_obs, const optional<Tensor>& n_inlier, const optional<Tensor>& weight, const Tensor& information,
+                                     const Tensor& status, int64_t stream) {
+  refine_views_weighted(true, obs, prior, views, views_each, pose, assignment, n_obj, model, sigma_px, huber_px, iters, damping, pose_out, fit, n_obs, n_inlier, weight,
+                        information, status, stream);
+}
+
+// window_push with conf_ref / conf_floor and the state win_prior [B,T,S,W]
+void window_push_weighted(at::ArrayRef<double> camera, const Tensor& tab, const Tensor& assignment, const Tensor& status, const Tensor& meas_of, const Tensor& track_i,
+                          const Tensor& track_f, const Tensor& track_pose, const Tensor& T_WC, int64_t min_views, double max_speed, double conf_ref, double conf_floor,
+                          const Tensor& win_obs, const Tensor& win_prior, const Tensor& win_views, const Tensor& win_i, const Tensor& n_views, const Tensor& start,
+                          int64_t stream) {
+  check_dev(tab, at::kDouble, "tab"); check_dev(assignment, at::kInt, "assignment"); check_dev(status, at::kInt, "status"); check_dev(meas_of, at::kInt, "meas_of");
+  check_dev(track_i, at::kInt, "track_i"); check_dev(track_f, at::kDouble, "track_f"); check_dev(track_pose, at::kDouble, "track_pose"); check_dev(T_WC, at::kDouble, "T_WC");
+  check_dev(win_obs, at::kDouble, "win_obs"); check_dev(win_prior, at::kDouble, "win_prior"); check_dev(win_views, at::kDouble, "win_views"); check_dev(win_i, at::kInt, "win_i");
+  check_dev(n_views, at::kInt, "n_views"); check_dev(start, at::kDouble, "start");
+  TORCH_CHECK(tab.dim() == 4 && tab.size(3) == 4, "okp: tab is [B,max_obj,S,4] float64");
+  TORCH_CHECK(win_obs.dim() == 5 && win_obs.size(4) == 2, "okp: win_obs is [B,T,S,W,2] float64");
+  const int64_t B = tab.size(0), max_obj = tab.size(1), S = tab.size(2), T = win_obs.size(1), W = win_obs.size(3);
+  TORCH_CHECK(win_obs.size(0) == B && win_obs.size(2) == S && win_prior.numel() == B * T * S * W && win_views.numel() == B * T * W * 14 && win_i.numel() == B * T * 4,
+              "okp: the weighted window state is win_obs [B,T,S,W,2], win_prior [B,T,S,W], win_views [B,T,W,14] and win_i [B,T,4] for the table's B and S");
+  TORCH_CHECK(assignment.numel() == B * max_obj * S && status.numel() == B * max_obj && meas_of.numel() == B * T && track_i.numel() == B * T * 4 &&
+              track_f.numel() == B * T * 16 && track_pose.numel() == B * T * 12 && T_WC.numel() == B * 12,
+              "okp: window_push_weighted inputs are assignment [B,max_obj,S], status [B,max_obj], meas_of [B,T], track_i [B,T,4], track_f [B,T,16], track_pose [B,T,12] and T_WC [B,12]");
+  TORCH_CHECK(n_views.numel() == B * T && start.numel() == B * T * 12, "okp: window_push_weighted outputs are n_views [B,T] and start [B,T,12]");
+  TORCH_CHECK(min_views >= INT32_MIN && min_views <= INT32_MAX, "okp: min_views does not fit an int32");
+  TORCH_CHECK(B <= INT32_MAX && max_obj <= INT32_MAX && S <= INT32_MAX && T <= INT32_MAX && W <= INT32_MAX, "okp: tab or win_obs is too large");
+  const okp_camera cam = camera_of(camera);
+  check_rc(okp_window_push_weighted(tab.data_ptr<double>(), assignment.data_ptr<int32_t>(), status.data_ptr<int32_t>(), meas_of.data_ptr<int32_t>(), track_i.data_ptr<int32_t>(),
+                                    track_f.data_ptr<double>(), track_pose.data_ptr<double>(), T_WC.data_ptr<double>(), &cam, (int32_t)B, (int32_t)max_obj, (int32_t)S, (int32_t)T,
+                                    (int32_t)W, (int32_t)min_views, max_speed, conf_ref, conf_floor, win_obs.data_ptr<double>(), win_prior.data_ptr<double>(),
+                                    win_views.data_ptr<double>(), win_i.data_ptr<int32_t>(), n_views.data_ptr<int32_t>(), start.data_ptr<double>(), sp(stream)),
+           "okp_window_push_weighted");
+}
+
+// window_push_views with the tick's prior [B,max_obj,S,V] and the state win_prior [B,T,S,W*V]
+void window_push_views_weighted(const Tensor& obs, const Tensor& prior, const Tensor& assignment, const Tensor& status, const Tensor& meas_of, const Tensor& track_i,
+                                const Tensor& track_f, const Tensor& track_pose, const Tensor& T_WB, const Tensor& views, int64_t ticks, int64_t min_views, double max_speed,
+                                const Tensor& win_obs, const Tensor& win_prior, const Tensor& win_views, const Tensor& win_i, const Tensor& n_views, const Tensor& start,
+                                int64_t stream) {
+  check_dev(obs, at::kDouble, "obs"); check_dev(prior, at::kDouble, "prior"); check_dev(assignment, at::kInt, "assignment"); check_dev(status, at::kInt, "status");
+  check_dev(meas_of, at::kInt, "meas_of"); check_dev(track_i, at::kInt, "track_i"); check_dev(track_f, at::kDouble, "track_f"); check_dev(track_pose, at::kDouble, "track_pose");
+  check_dev(T_WB, at::kDouble, "T_WB"); check_dev(views, at::kDouble, "views"); check_dev(win_obs, at::kDouble, "win_obs"); check_dev(win_prior, at::kDouble, "win_prior");
+  check_dev(win_views, at::kDouble, "win_views"); check_dev(win_i, at::kInt, "win_i"); check_dev(n_views, at::kInt, "n_views"); check_dev(start, at::kDouble, "start");
+  TORCH_CHECK(obs.dim() == 5 && obs.size(4) == 2, "okp: obs is [B,max_obj,S,V,2] float64");
+  TORCH_CHECK(win_obs.dim() == 5 && win_obs.size(4) == 2, "okp: win_obs is [B,T,S,W*V,2] float64");
+  const int64_t B = obs.size(0), max_obj = obs.size(1), S = obs.size(2), V = obs.size(3), T = win_obs.size(1), W = ticks;
+  TORCH_CHECK(W >= INT32_MIN && W <= INT32_MAX && min_views >= INT32_MIN && min_views <= INT32_MAX, "okp: ticks or min_views does not fit an int32");
+  TORCH_CHECK(B <= INT32_MAX && max_obj <= INT32_MAX && S <= INT32_MAX && T <= INT32_MAX && V <= INT32_MAX, "okp: obs or win_obs is too large");
+  TORCH_CHECK(prior.numel() == B * max_obj * S * V, "okp: prior is [B,max_obj,S,V] float64, one value per entry of obs");
+  TORCH_CHECK(W < 1 || V < 1 || (win_obs.size(0) == B && win_obs.size(2) == S && win_obs.size(3) == W * V && win_prior.numel() == B * T * S * W * V &&
+                                 win_views.numel() == B * T * W * V * 14 && win_i.numel() == B * T * 4),
+              "okp: the weighted window state is win_obs [B,T,S,W*V,2], win_prior [B,T,S,W*V], win_views [B,T,W*V,14] and win_i [B,T,4] for the bearings' B, S and V and "
+              "W = ticks");                        // (W, V < 1: the entry point refuses)
+  TORCH_CHECK(assignment.numel() == B * max_obj * S && status.numel() == B * max_obj && meas_of.numel() == B * T && track_i.numel() == B * T * 4 &&
+              track_f.numel() == B * T * 16 && track_pose.numel() == B * T * 12 && T_WB.numel() == B * 12 && views.numel() == V * 14,
+              "okp: window_push_views_weighted inputs are assignment [B,max_obj,S], status [B,max_obj], meas_of [B,T], track_i [B,T,4], track_f [B,T,16], "
+              "track_pose [B,T,12], T_WB [B,12] and views [V,14]");
+  TORCH_CHECK(n_views.numel() == B * T && start.numel() == B * T * 12, "okp: window_push_views_weighted outputs are n_views [B,T] and start [B,T,12]");
+  check_rc(okp_window_push_views_weighted(obs.data_ptr<double>(), prior.data_ptr<double>(), assignment.data_ptr<int32_t>(), status.data_ptr<int32_t>(),
+                                          meas_of.data_ptr<int32_t>(), track_i.data_ptr<int32_t>(), track_f.data_ptr<double>(), track_pose.data_ptr<double>(),
+                                          T_WB.data_ptr<double>(), views.data_ptr<double>(), (int32_t)B, (int32_t)max_obj, (int32_t)S, (int32_t)T, (int32_t)W, (int32_t)V,
+                                          (int32_t)min_views, max_speed, win_obs.data_ptr<double>(), win_prior.data_ptr<double>(), win_views.data_ptr<double>(),
+                                          win_i.data_ptr<int32_t>(), n_views.data_ptr<int32_t>(), start.data_ptr<double>(), sp(stream)),
+           "okp_window_push_views_weighted");
+}
+
 void lift_peaks(at::ArrayRef<double> camera, const Tensor& count, const Tensor& xyc, const Tensor& depth, int64_t max_x, int64_t max_y, const Tensor& out, int64_t stream) {
   TORCH_CHECK(xyc.is_cuda() && xyc.dim() == 4 && xyc.scalar_type() == at::kFloat && depth.is_cuda() && depth.scalar_type() == at::kFloat && depth.dim() == 4 && depth.is_contiguous() &&
               depth.size(0) == xyc.size(0) && depth.size(1) == xyc.size(1) && count.scalar_type() == at::kInt && out.scalar_type() == at::kDouble &&
@@ -1091,6 +1229,20 @@ TORCH_LIBRARY(okp, m) {
   m.def("refine_pose_views_wide(Tensor obs, Tensor views, int views_each, Tensor pose, Tensor assignment, Tensor n_obj, Tensor model, float sigma_px, float huber_px, "
         "int iters, float damping, Tensor(a!) pose_out, Tensor(b!) fit, Tensor(c!) n_obs, Tensor(d!)? n_inlier, Tensor(e!)? weight, Tensor(f!) information, "
         "Tensor(g!) status, int stream) -> ()", refine_pose_views_wide);
+  m.def("rig_bearings_weighted(Tensor table, Tensor count, Tensor xyc, Tensor match, Tensor member, Tensor object, Tensor n_fused, int[] type_count, float conf_ref, "
+        "float conf_floor, Tensor(a!) obs, Tensor(b!) prior, int stream) -> ()", rig_bearings_weighted);
+  m.def("refine_pose_views_weighted(Tensor obs, Tensor prior, Tensor views, int views_each, Tensor pose, Tensor assignment, Tensor n_obj, Tensor model, float sigma_px, "
+        "float huber_px, int iters, float damping, Tensor(a!) pose_out, Tensor(b!) fit, Tensor(c!) n_obs, Tensor(d!)? n_inlier, Tensor(e!)? weight, "
+        "Tensor(f!) information, Tensor(g!) status, int stream) -> ()", refine_pose_views_weighted);
+  m.def("refine_pose_views_weighted_wide(Tensor obs, Tensor prior, Tensor views, int views_each, Tensor pose, Tensor assignment, Tensor n_obj, Tensor model, float sigma_px, "
+        "float huber_px, int iters, float damping, Tensor(a!) pose_out, Tensor(b!) fit, Tensor(c!) n_obs, Tensor(d!)? n_inlier, Tensor(e!)? weight, "
+        "Tensor(f!) information, Tensor(g!) status, int stream) -> ()", refine_pose_views_weighted_wide);
+  m.def("window_push_weighted(float[] camera, Tensor tab, Tensor assignment, Tensor status, Tensor meas_of, Tensor track_i, Tensor track_f, Tensor track_pose, Tensor T_WC, "
+        "int min_views, float max_speed, float conf_ref, float conf_floor, Tensor(a!) win_obs, Tensor(b!) win_prior, Tensor(c!) win_views, Tensor(d!) win_i, "
+        "Tensor(e!) n_views, Tensor(f!) start, int stream) -> ()", window_push_weighted);
+  m.def("window_push_views_weighted(Tensor obs, Tensor prior, Tensor assignment, Tensor status, Tensor meas_of, Tensor track_i, Tensor track_f, Tensor track_pose, "
+        "Tensor T_WB, Tensor views, int ticks, int min_views, float max_speed, Tensor(a!) win_obs, Tensor(b!) win_prior, Tensor(c!) win_views, Tensor(d!) win_i, "
+        "Tensor(e!) n_views, Tensor(f!) start, int stream) -> ()", window_push_views_weighted);
   m.def("refine_assignments(float[] camera, Tensor tab, Tensor pose, Tensor assignment, Tensor n_obj, Tensor model, int[] type_count, float sigma_px, float sigma_z, int iters, "
         "float damping, Tensor(a!) pose_out, Tensor(b!) fit, Tensor(c!) information, Tensor(d!) status, Tensor(e!) assignment_out, Tensor(f!) hypothesis, Tensor(g!) cost, "
         "int stream) -> ()", refine_assignments);

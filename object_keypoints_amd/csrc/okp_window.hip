@@ -22,10 +22,15 @@ struct WindowParams {
   double fx, fy, max_speed2;
   int32_t max_obj, S, T, W, min_views;
   double* win_obs; double* win_views; int32_t* win_i; int32_t* n_views; double* start;
+  double* win_prior; double conf_ref, conf_floor;                 // the PRIOR instance's (okp_window_push_weighted); last, so the other offsets stay
 };
 
+// PRIOR: the ring of priors next to the ring of bearings (okp_window_push_weighted): an entry of win_prior is written wherever its entry of
+// win_obs is - the mapped confidence of the table row with a bearing, NaN with (NaN, NaN); the plain instance is the code it was
+template <bool PRIOR>
 __global__ __launch_bounds__(64) void okp_window_push_kernel(const WindowParams P) {
   __shared__ double row[OKP_POSE_MAX_POINTS][2];                  // the new column: the bearing of every model row, or NaN
+  [[maybe_unused]] __shared__ double prow[OKP_POSE_MAX_POINTS];   // (PRIOR) and its prior
   __shared__ double view[14];
   const int lane = threadIdx.x;
   const size_t bi = blockIdx.x;                                   // b * T + i
@@ -56,19 +61,29 @@ __global__ __launch_bounds__(64) void okp_window_push_kernel(const WindowParams 
   }
 
   if (push) {                                                     // (wave-uniform)
-    if (lane < OKP_POSE_MAX_POINTS) { row[lane][0] = nan; row[lane][1] = nan; }
+    if (lane < OKP_POSE_MAX_POINTS) {
+      row[lane][0] = nan; row[lane][1] = nan;
+      if constexpr (PRIOR) prow[lane] = nan;
+    }
     int a = -1;
     double u = nan, v = nan;
+    [[maybe_unused]] double pa = nan;
     if (lane < S) {
       const size_t slot = (b * P.max_obj + o) * S + lane;
       const double* p = P.tab + slot * 4;
       const double X = p[0], Y = p[1], Z = p[2], c = p[3];
       const int as = P.assignment[slot];
-      if (as >= 0 && as < S && finite64(X) && finite64(Y) && finite64(Z) && finite64(c) && Z != 0.0) { a = as; u = X / Z; v = Y / Z; }
+      if (as >= 0 && as < S && finite64(X) && finite64(Y) && finite64(Z) && finite64(c) && Z != 0.0) {
+        a = as; u = X / Z; v = Y / Z;
+        if constexpr (PRIOR) pa = c >= P.conf_ref ? 1.0 : ((c > P.conf_floor ? c : P.conf_floor) / P.conf_ref);
+      }
     }
     __syncthreads();
     for (int s = 0; s < S; ++s) {                                 // ascending slots: a later slot with the same model row wins
-      if (lane == s && a >= 0) { row[a][0] = u; row[a][1] = v; }
+      if (lane == s && a >= 0) {
+        row[a][0] = u; row[a][1] = v;
+        if constexpr (PRIOR) prow[a] = pa;
+      }
       __syncthreads();
     }
     if (lane < 14) {                                              // camera-from-world: [R^T | R^T (-t)], then fx, fy
@@ -91,8 +106,13 @@ __global__ __launch_bounds__(64) void okp_window_push_kernel(const WindowParams 
   double* obs = P.win_obs + bi * S * W * 2;
   for (int e = lane; e < S * W; e += 64) {
     const int r = e / W, c = e - r * W;
-    if (push && c == head) { obs[2 * e] = row[r][0]; obs[2 * e + 1] = row[r][1]; }
-    else if (clear) { obs[2 * e] = nan; obs[2 * e + 1] = nan; }
+    if (push && c == head) {
+      obs[2 * e] = row[r][0]; obs[2 * e + 1] = row[r][1];
+      if constexpr (PRIOR) P.win_prior[bi * S * W + e] = prow[r];
+    } else if (clear) {
+      obs[2 * e] = nan; obs[2 * e + 1] = nan;
+      if constexpr (PRIOR) P.win_prior[bi * S * W + e] = nan;
+    }
   }
   double* vw = P.win_views + bi * W * 14;
   for (int e = lane; e < W * 14; e += 64) {
@@ -112,11 +132,12 @@ __global__ __launch_bounds__(64) void okp_window_push_kernel(const WindowParams 
 
 }  // namespace
 
-extern "C" int okp_window_push(const double* tab, const int32_t* assignment, const int32_t* status, const int32_t* meas_of, const int32_t* track_i,
-                               const double* track_f, const double* track_pose, const double* T_WC, const okp_camera* cam, int32_t B, int32_t max_obj,
-                               int32_t S, int32_t T, int32_t W, int32_t min_views, double max_speed, double* win_obs, double* win_views,
-                               int32_t* win_i, int32_t* n_views, double* start, void* stream) {
-  const char* fn = "okp_window_push";
+// okp_window_push and okp_window_push_weighted: one kernel, the second instance also keeps the ring of priors
+static int window_push_launch(const char* fn, const char* what, const double* tab, const int32_t* assignment, const int32_t* status, const int32_t* meas_of,
+                              const int32_t* track_i, const double* track_f, const double* track_pose, const double* T_WC, const okp_camera* cam, int32_t B,
+                              int32_t max_obj, int32_t S, int32_t T, int32_t W, int32_t min_views, double max_speed, bool weighted, double conf_ref,
+                              double conf_floor, double* win_obs, double* win_prior, double* win_views, int32_t* win_i, int32_t* n_views, double* start,
+                              void* stream) {
   if (B < 1) { okp_set_error("%s: B = %d; at least one stream", fn, B); return OKP_EINVAL; }
   if (max_obj < 1) { okp_set_error("%s: max_obj = %d; a stream holds at least one object", fn, max_obj); return OKP_EINVAL; }
   if (S < 1 || S > OKP_POSE_MAX_POINTS) { okp_set_error("%s: S = %d outside [1, %d] model points", fn, S, OKP_POSE_MAX_POINTS); return OKP_EINVAL; }
@@ -130,18 +151,46 @@ extern "C" int okp_window_push(const double* tab, const int32_t* assignment, con
     okp_set_error("%s: cam fx = %g, fy = %g must be positive and finite", fn, (double)cam->fx, (double)cam->fy);
     return OKP_EINVAL;
   }
+  if (weighted && !(conf_ref > 0.0 && conf_ref < __builtin_inf())) {
+    okp_set_error("%s: conf_ref = %g must be positive and finite (the confidence from which a key point has the full weight)", fn, conf_ref);
+    return OKP_EINVAL;
+  }
+  if (weighted && !(conf_floor > 0.0 && conf_floor <= conf_ref)) {
+    okp_set_error("%s: conf_floor = %g outside (0, conf_ref = %g]", fn, conf_floor, conf_ref);
+    return OKP_EINVAL;
+  }
   const struct { const void* ptr; const char* name; } required[] = {
       {tab, "tab"}, {assignment, "assignment"}, {status, "status"}, {meas_of, "meas_of"}, {track_i, "track_i"}, {track_f, "track_f"},
       {track_pose, "track_pose"}, {T_WC, "T_WC"}, {win_obs, "win_obs"}, {win_views, "win_views"}, {win_i, "win_i"}, {n_views, "n_views"},
       {start, "start"}};
   for (const auto& r : required)
     if (!r.ptr) { okp_set_error("%s: null %s", fn, r.name); return OKP_EINVAL; }
+  if (weighted && !win_prior) { okp_set_error("%s: null win_prior", fn); return OKP_EINVAL; }
   WindowParams p = {};
   p.tab = tab; p.assignment = assignment; p.status = status; p.meas_of = meas_of; p.track_i = track_i; p.track_f = track_f;
   p.track_pose = track_pose; p.T_WC = T_WC;
   p.fx = cam->fx; p.fy = cam->fy; p.max_speed2 = max_speed * max_speed;
   p.max_obj = max_obj; p.S = S; p.T = T; p.W = W; p.min_views = min_views;
   p.win_obs = win_obs; p.win_views = win_views; p.win_i = win_i; p.n_views = n_views; p.start = start;
-  hipLaunchKernelGGL(okp_window_push_kernel, dim3((unsigned)((size_t)B * T)), dim3(64), 0, (hipStream_t)stream, p);
-  return okp_check_hip(hipGetLastError(), "okp_window_push launch");
+  p.win_prior = win_prior; p.conf_ref = conf_ref; p.conf_floor = conf_floor;
+  if (weighted) hipLaunchKernelGGL(okp_window_push_kernel<true>, dim3((unsigned)((size_t)B * T)), dim3(64), 0, (hipStream_t)stream, p);
+  else hipLaunchKernelGGL(okp_window_push_kernel<false>, dim3((unsigned)((size_t)B * T)), dim3(64), 0, (hipStream_t)stream, p);
+  return okp_check_hip(hipGetLastError(), what);
+}
+
+extern "C" int okp_window_push(const double* tab, const int32_t* assignment, const int32_t* status, const int32_t* meas_of, const int32_t* track_i,
+                               const double* track_f, const double* track_pose, const double* T_WC, const okp_camera* cam, int32_t B, int32_t max_obj,
+                               int32_t S, int32_t T, int32_t W, int32_t min_views, double max_speed, double* win_obs, double* win_views,
+                               int32_t* win_i, int32_t* n_views, double* start, void* stream) {
+  return window_push_launch("okp_window_push", "okp_window_push launch", tab, assignment, status, meas_of, track_i, track_f, track_pose, T_WC, cam, B, max_obj, S, T,
+                            W, min_views, max_speed, false, 0.0, 0.0, win_obs, nullptr, win_views, win_i, n_views, start, stream);
+}
+
+extern "C" int okp_window_push_weighted(const double* tab, const int32_t* assignment, const int32_t* status, const int32_t* meas_of, const int32_t* track_i,
+                                        const double* track_f, const double* track_pose, const double* T_WC, const okp_camera* cam, int32_t B,
+                                        int32_t max_obj, int32_t S, int32_t T, int32_t W, int32_t min_views, double max_speed, double conf_ref,
+                                        double conf_floor, double* win_obs, double* win_prior, double* win_views, int32_t* win_i, int32_t* n_views,
+                                        double* start, void* stream) {
+  return window_push_launch("okp_window_push_weighted", "okp_window_push_weighted launch", tab, assignment, status, meas_of, track_i, track_f, track_pose, T_WC, cam,
+                            B, max_obj, S, T, W, min_views, max_speed, true, conf_ref, conf_floor, win_obs, win_prior, win_views, win_i, n_views, start, stream);
 }

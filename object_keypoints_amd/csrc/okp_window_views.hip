@@ -26,8 +26,12 @@ struct WindowViewsParams {
   double max_speed2;
   int32_t max_obj, S, T, W, V, min_views;
   double* win_obs; double* win_views; int32_t* win_i; int32_t* n_views; double* start;
+  const double* prior; double* win_prior;                         // the PRIOR instance's (okp_window_push_views_weighted); last, so the other offsets stay
 };
 
+// PRIOR: the ring of priors next to the ring of bearings (okp_window_push_views_weighted): an entry of win_prior is written wherever its entry
+// of win_obs is - the table's prior bit for bit with a copied bearing, NaN with (NaN, NaN); the plain instance is the code it was
+template <bool PRIOR>
 __global__ __launch_bounds__(OKP_WINDOW_VIEWS_THREADS) void okp_window_push_views_kernel(const WindowViewsParams P) {
   __shared__ int32_t slot_of[OKP_POSE_MAX_POINTS];                // the table slot whose bearings model row r takes, or -1
   const int tid = threadIdx.x;
@@ -78,7 +82,15 @@ __global__ __launch_bounds__(OKP_WINDOW_VIEWS_THREADS) void okp_window_push_view
       double x = nan, y = nan;
       if (src >= 0) { x = tab[((size_t)src * V + v) * 2]; y = tab[((size_t)src * V + v) * 2 + 1]; }
       ring[2 * (size_t)e] = x; ring[2 * (size_t)e + 1] = y;
-    } else if (clear) { ring[2 * (size_t)e] = nan; ring[2 * (size_t)e + 1] = nan; }
+      if constexpr (PRIOR) {
+        unsigned long long bits = __builtin_bit_cast(unsigned long long, nan);
+        if (src >= 0) bits = reinterpret_cast<const unsigned long long*>(P.prior)[((b * P.max_obj + (size_t)o) * S + src) * V + v];
+        reinterpret_cast<unsigned long long*>(P.win_prior)[bi * (size_t)S * WV + e] = bits;
+      }
+    } else if (clear) {
+      ring[2 * (size_t)e] = nan; ring[2 * (size_t)e + 1] = nan;
+      if constexpr (PRIOR) P.win_prior[bi * (size_t)S * WV + e] = nan;
+    }
   }
   double* vw = P.win_views + bi * (size_t)WV * 14;
   for (int e = tid; e < WV * 14; e += OKP_WINDOW_VIEWS_THREADS) {
@@ -112,11 +124,12 @@ __global__ __launch_bounds__(OKP_WINDOW_VIEWS_THREADS) void okp_window_push_view
 
 }  // namespace
 
-extern "C" int okp_window_push_views(const double* obs, const int32_t* assignment, const int32_t* status, const int32_t* meas_of, const int32_t* track_i,
-                                     const double* track_f, const double* track_pose, const double* T_WB, const double* views, int32_t B, int32_t max_obj,
-                                     int32_t S, int32_t T, int32_t W, int32_t V, int32_t min_views, double max_speed, double* win_obs, double* win_views,
-                                     int32_t* win_i, int32_t* n_views, double* start, void* stream) {
-  const char* fn = "okp_window_push_views";
+// okp_window_push_views and okp_window_push_views_weighted: one kernel, the second instance also keeps the ring of priors
+static int window_push_views_launch(const char* fn, const char* what, const double* obs, const double* prior, bool weighted, const int32_t* assignment,
+                                    const int32_t* status, const int32_t* meas_of, const int32_t* track_i, const double* track_f, const double* track_pose,
+                                    const double* T_WB, const double* views, int32_t B, int32_t max_obj, int32_t S, int32_t T, int32_t W, int32_t V,
+                                    int32_t min_views, double max_speed, double* win_obs, double* win_prior, double* win_views, int32_t* win_i, int32_t* n_views,
+                                    double* start, void* stream) {
   if (B < 1) { okp_set_error("%s: B = %d; at least one stream", fn, B); return OKP_EINVAL; }
   if (max_obj < 1) { okp_set_error("%s: max_obj = %d; a stream holds at least one object", fn, max_obj); return OKP_EINVAL; }
   if (S < 1 || S > OKP_POSE_MAX_POINTS) { okp_set_error("%s: S = %d outside [1, %d] model points", fn, S, OKP_POSE_MAX_POINTS); return OKP_EINVAL; }
@@ -136,12 +149,35 @@ extern "C" int okp_window_push_views(const double* obs, const int32_t* assignmen
       {n_views, "n_views"}, {start, "start"}};
   for (const auto& r : required)
     if (!r.ptr) { okp_set_error("%s: null %s", fn, r.name); return OKP_EINVAL; }
+  if (weighted && !prior) { okp_set_error("%s: null prior", fn); return OKP_EINVAL; }
+  if (weighted && !win_prior) { okp_set_error("%s: null win_prior", fn); return OKP_EINVAL; }
   WindowViewsParams p = {};
   p.obs = obs; p.assignment = assignment; p.status = status; p.meas_of = meas_of; p.track_i = track_i; p.track_f = track_f;
   p.track_pose = track_pose; p.T_WB = T_WB; p.views = views;
   p.max_speed2 = max_speed * max_speed;
   p.max_obj = max_obj; p.S = S; p.T = T; p.W = W; p.V = V; p.min_views = min_views;
   p.win_obs = win_obs; p.win_views = win_views; p.win_i = win_i; p.n_views = n_views; p.start = start;
-  hipLaunchKernelGGL(okp_window_push_views_kernel, dim3((unsigned)((size_t)B * T)), dim3(OKP_WINDOW_VIEWS_THREADS), 0, (hipStream_t)stream, p);
-  return okp_check_hip(hipGetLastError(), "okp_window_push_views launch");
+  p.prior = prior; p.win_prior = win_prior;
+  const dim3 grid((unsigned)((size_t)B * T)), block(OKP_WINDOW_VIEWS_THREADS);
+  if (weighted) hipLaunchKernelGGL(okp_window_push_views_kernel<true>, grid, block, 0, (hipStream_t)stream, p);
+  else hipLaunchKernelGGL(okp_window_push_views_kernel<false>, grid, block, 0, (hipStream_t)stream, p);
+  return okp_check_hip(hipGetLastError(), what);
+}
+
+extern "C" int okp_window_push_views(const double* obs, const int32_t* assignment, const int32_t* status, const int32_t* meas_of, const int32_t* track_i,
+                                     const double* track_f, const double* track_pose, const double* T_WB, const double* views, int32_t B, int32_t max_obj,
+                                     int32_t S, int32_t T, int32_t W, int32_t V, int32_t min_views, double max_speed, double* win_obs, double* win_views,
+                                     int32_t* win_i, int32_t* n_views, double* start, void* stream) {
+  return window_push_views_launch("okp_window_push_views", "okp_window_push_views launch", obs, nullptr, false, assignment, status, meas_of, track_i, track_f,
+                                  track_pose, T_WB, views, B, max_obj, S, T, W, V, min_views, max_speed, win_obs, nullptr, win_views, win_i, n_views, start, stream);
+}
+
+extern "C" int okp_window_push_views_weighted(const double* obs, const double* prior, const int32_t* assignment, const int32_t* status, const int32_t* meas_of,
+                                              const int32_t* track_i, const double* track_f, const double* track_pose, const double* T_WB, const double* views,
+                                              int32_t B, int32_t max_obj, int32_t S, int32_t T, int32_t W, int32_t V, int32_t min_views, double max_speed,
+                                              double* win_obs, double* win_prior, double* win_views, int32_t* win_i, int32_t* n_views, double* start,
+                                              void* stream) {
+  return window_push_views_launch("okp_window_push_views_weighted", "okp_window_push_views_weighted launch", obs, prior, true, assignment, status, meas_of, track_i,
+                                  track_f, track_pose, T_WB, views, B, max_obj, S, T, W, V, min_views, max_speed, win_obs, win_prior, win_views, win_i, n_views, start,
+                                  stream);
 }

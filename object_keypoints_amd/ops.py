@@ -1420,6 +1420,40 @@ REFINE_NONE = 16                                                                
 REFINE_MAX_HYPOTHESES = 24                                                       # include/okp.h OKP_REFINE_MAX_HYPOTHESES
 
 
+class ConfidenceWeights:
+    """The model that turns a peak's confidence into the prior of its bearing in a refinement against views (include/okp.h, "Weighting the
+    views refinements by the peaks' confidences"), validated here - an OkpError names the field:
+        ref    the confidence from which a bearing has the full weight 1.0 (positive, finite)
+        floor  the confidence below which the weight does not fall any further, in (0, ref]: the least prior is floor / ref
+    prior = 1.0 for c >= ref, otherwise max(c, floor) / ref: a bearing's sigma is sigma_px / sqrt(prior).  A stated model, not a measured
+    one.  A RefineConfig or a WindowConfig takes it as confidence=..."""
+
+    def __init__(self, ref, floor):
+        def number(name, v):
+            if isinstance(v, (bool, np.bool_)):
+                raise OkpError(f"ConfidenceWeights: {name} = {v!r} is not a number")
+            try:
+                return float(v)
+            except (TypeError, ValueError):
+                raise OkpError(f"ConfidenceWeights: {name} = {v!r} is not a number") from None
+
+        self.ref, self.floor = number("ref", ref), number("floor", floor)
+        if not (self.ref > 0.0 and np.isfinite(self.ref)):
+            raise OkpError(f"ConfidenceWeights: ref = {ref!r} must be positive and finite (a peak's confidence)")
+        if not 0.0 < self.floor <= self.ref:
+            raise OkpError(f"ConfidenceWeights: floor = {floor!r} must lie in (0, ref = {self.ref}]")
+
+    def __repr__(self):
+        return f"ConfidenceWeights(ref={self.ref}, floor={self.floor})"
+
+
+def _confidence(owner, v):
+    """confidence of a RefineConfig / WindowConfig: None, or a ConfidenceWeights."""
+    if v is not None and not isinstance(v, ConfidenceWeights):
+        raise OkpError(f"{owner}: confidence = {v!r} must be an ops.ConfidenceWeights (None: uniform weights)")
+    return v
+
+
 class RefineConfig:
     """The parameters of the pose refinement (okp_refine_pose), validated here - an OkpError names the field:
         sigma_px  map pixels: the standard deviation of a key point's pixel position (positive, finite)
@@ -1432,9 +1466,11 @@ class RefineConfig:
     damping only: its cost has no depth term, so sigma_z is not used, and it does not resolve assignments (a rig pipeline refuses
     resolve_assignment=True).
         huber_px  (keyword, default None) map pixels, positive and finite: refine_pose_views / refine_pose_views_each then run under a Huber
-                  loss with this threshold (okp_refine_pose_views_robust).  The single-camera refinement does not offer it."""
+                  loss with this threshold (okp_refine_pose_views_robust).  The single-camera refinement does not offer it.
+        confidence  (keyword, default None) a ConfidenceWeights: StereoStreamPipeline(refine=...) then weights every bearing by its peak's
+                  confidence (rig_bearings_weighted, refine_pose_views_weighted).  The single-camera refinement does not offer it."""
 
-    def __init__(self, sigma_px=0.25, sigma_z=0.05, iters=6, damping=1e-9, *, resolve_assignment=False, huber_px=None):
+    def __init__(self, sigma_px=0.25, sigma_z=0.05, iters=6, damping=1e-9, *, resolve_assignment=False, huber_px=None, confidence=None):
         def number(name, v):
             if isinstance(v, bool):
                 raise OkpError(f"RefineConfig: {name} = {v!r} is not a number")
@@ -1457,10 +1493,12 @@ class RefineConfig:
             raise OkpError(f"RefineConfig: resolve_assignment = {resolve_assignment!r} must be True or False")
         self.resolve_assignment = bool(resolve_assignment)
         self.huber_px = _huber_px("RefineConfig", huber_px)
+        self.confidence = _confidence("RefineConfig", confidence)
 
     def __repr__(self):
         flag = ", resolve_assignment=True" if self.resolve_assignment else ""
         flag += f", huber_px={self.huber_px}" if self.huber_px is not None else ""
+        flag += f", confidence={self.confidence}" if self.confidence is not None else ""
         return f"RefineConfig(sigma_px={self.sigma_px}, sigma_z={self.sigma_z}, iters={self.iters}, damping={self.damping}{flag})"
 
 
@@ -1485,6 +1523,9 @@ def _refine_inputs(tab, pose, n_obj, model, cam, cfg):
         raise OkpError("cfg must be an ops.RefineConfig")
     if cfg.huber_px is not None:                 # (not ignored quietly: okp_refine_pose and okp_refine_assignments have no robust form)
         raise OkpNotOffered("cfg.huber_px: not offered for the single-camera refinement (refine_pose_views and refine_pose_views_each take it)")
+    if cfg.confidence is not None:               # (nor a weighted one)
+        raise OkpNotOffered("cfg.confidence: not offered for the single-camera refinement (refine_pose_views_weighted takes it: "
+                            "StereoStreamPipeline(refine=..., rig_window=...) and BatchedKeypointPipeline(window=...))")
     if not isinstance(cam, _lib.okp_camera):
         raise OkpError(f"cam must be an okp_camera (make_camera), not {type(cam).__name__}")
     try:
@@ -1613,12 +1654,8 @@ def rig_views(stereo_cameras, rig_poses):
     return torch.from_numpy(check_views(out))
 
 
-def rig_bearings(table, count, xyc, match, fused, type_count):
-    """The bearings of a fused tick's objects in every camera of the rig (okp_rig_bearings, specified in include/okp.h): table - the rig's
-    calibration table on the device (stereo_rig; one entry serves every pair) -, count [2P,K] int32 and xyc [2P,K,cap,3] fp32 (peak_nms),
-    match [P,K,cap] int32 (stereo_match_rig), fused: rig_fuse()'s dict ("member", "object" and "n_fused" are read), type_count: the K-1 counts
-    -> obs [1, cap_f, S, 2P, 2] float64 (device): the undistorted normalised image coordinates of slot s of object o in camera v (2p: the left
-    camera of pair p), (NaN, NaN) where the camera did not see it.  Every word is written.  One launch, no host sync."""
+def _rig_bearings_inputs(table, count, xyc, match, fused, type_count):
+    """The argument checks rig_bearings and rig_bearings_weighted share -> (the launch's tensors and type counts, cap_f, s, n_pairs, dev)."""
     n_pairs, k, cap = _tick_pairs(count, xyc)
     n_table = _rig_table(table)
     tc, s = _pose_type_count(type_count, "type_count")
@@ -1645,11 +1682,34 @@ def rig_bearings(table, count, xyc, match, fused, type_count):
         raise OkpError(f"n_fused must be int32 [{k}] on the peaks' device (rig_fuse)")
     if table.device != dev:
         raise OkpError(f"table is on {table.device}, the peaks on {dev}")
-    cap_f = int(obj.shape[1])
+    args = (table, count.contiguous(), xyc.contiguous(), match.contiguous(), member.contiguous(), obj.contiguous(), n_fused.contiguous(), tc)
+    return args, int(obj.shape[1]), s, n_pairs, dev
+
+
+def rig_bearings(table, count, xyc, match, fused, type_count):
+    """The bearings of a fused tick's objects in every camera of the rig (okp_rig_bearings, specified in include/okp.h): table - the rig's
+    calibration table on the device (stereo_rig; one entry serves every pair) -, count [2P,K] int32 and xyc [2P,K,cap,3] fp32 (peak_nms),
+    match [P,K,cap] int32 (stereo_match_rig), fused: rig_fuse()'s dict ("member", "object" and "n_fused" are read), type_count: the K-1 counts
+    -> obs [1, cap_f, S, 2P, 2] float64 (device): the undistorted normalised image coordinates of slot s of object o in camera v (2p: the left
+    camera of pair p), (NaN, NaN) where the camera did not see it.  Every word is written.  One launch, no host sync."""
+    args, cap_f, s, n_pairs, dev = _rig_bearings_inputs(table, count, xyc, match, fused, type_count)
     obs = torch.empty((1, cap_f, s, 2 * n_pairs, 2), dtype=torch.float64, device=dev)
-    _dispatch(_ops().rig_bearings, table, count.contiguous(), xyc.contiguous(), match.contiguous(), member.contiguous(), obj.contiguous(), n_fused.contiguous(), tc, obs,
-              stream_int())
+    _dispatch(_ops().rig_bearings, *args, obs, stream_int())
     return obs
+
+
+def rig_bearings_weighted(table, count, xyc, match, fused, type_count, confidence):
+    """rig_bearings with the prior of every bearing (okp_rig_bearings_weighted): the same arguments and confidence, a ConfidenceWeights
+    -> (obs [1, cap_f, S, 2P, 2] float64, the bits of rig_bearings; prior [1, cap_f, S, 2P] float64: 1.0 for a peak whose confidence
+    xyc[..., 2] is at least confidence.ref, otherwise max(c, confidence.floor) / confidence.ref, NaN where obs is (NaN, NaN)).  Every word is
+    written.  One launch, no host sync."""
+    if not isinstance(confidence, ConfidenceWeights):
+        raise OkpError("confidence must be an ops.ConfidenceWeights")
+    args, cap_f, s, n_pairs, dev = _rig_bearings_inputs(table, count, xyc, match, fused, type_count)
+    obs = torch.empty((1, cap_f, s, 2 * n_pairs, 2), dtype=torch.float64, device=dev)
+    prior = torch.empty((1, cap_f, s, 2 * n_pairs), dtype=torch.float64, device=dev)
+    _dispatch(_ops().rig_bearings_weighted, *args, confidence.ref, confidence.floor, obs, prior, stream_int())
+    return obs, prior
 
 
 def refine_pose_views(obs, views, pose, n_obj, model, cfg):
@@ -1678,7 +1738,7 @@ def refine_pose_views_each(obs, views, pose, n_obj, model, cfg):
     return _refine_views(True, obs, views, pose, n_obj, model, cfg)
 
 
-def _views_inputs(each, obs, views, pose, n_obj, model, cfg, cfg_types, cfg_text, max_views, obs_from, views_from):
+def _views_inputs(each, obs, views, pose, n_obj, model, cfg, cfg_types, cfg_text, max_views, obs_from, views_from, prior=None):
     """The argument checks every refinement against views shares -> (fitted, assignment, b, max_obj, s, v, dev).  cfg_types / cfg_text: the
     config classes accepted and their names in the message; max_views: the entry point's limit on V; obs_from / views_from: where the message
     says obs and a shared views table come from."""
@@ -1686,6 +1746,9 @@ def _views_inputs(each, obs, views, pose, n_obj, model, cfg, cfg_types, cfg_text
         raise OkpError(f"cfg must be {cfg_text}")
     if not isinstance(each, (bool, np.bool_)):
         raise OkpError(f"each = {each!r} must be True (one views table per object) or False (one for all)")
+    if (prior is None) != (getattr(cfg, "confidence", None) is None):      # (never weighted, or uniform, quietly)
+        raise OkpNotOffered("cfg.confidence: refine_pose_views_weighted takes it, with the bearings' priors; refine_pose_views, refine_pose_views_each and "
+                            "refine_pose_views_wide have no priors and take a config without it")
     try:
         fitted, assignment = pose["pose"], pose["assignment"]
     except (TypeError, KeyError, IndexError):
@@ -1709,6 +1772,11 @@ def _views_inputs(each, obs, views, pose, n_obj, model, cfg, cfg_types, cfg_text
         raise OkpError(f"n_obj must be int32 [{b}] on the bearings' device: the objects of each frame")
     if model.dtype != torch.float64 or tuple(model.shape) != (s, 3) or model.device != dev:
         raise OkpError(f"model must be float64 [{s},3] on the bearings' device (object_model)")
+    if prior is not None:
+        require_cuda(prior, "prior")
+        if prior.dtype != torch.float64 or tuple(prior.shape) != (b, max_obj, s, v) or prior.device != dev:
+            raise OkpError(f"prior must be float64 [{b},{max_obj},{s},{v}] on the bearings' device: one value for each bearing of obs (rig_bearings_weighted, or "
+                           "the win_prior of a window's state)")
     return fitted, assignment, b, max_obj, s, v, dev
 
 
@@ -1752,9 +1820,12 @@ class WindowConfig:
                    (positive; inf: never)
         sigma_px, iters, damping   as in RefineConfig (there is no depth term)
         huber_px   (keyword, default None) map pixels, positive and finite: the refinement of the ring then runs under a Huber loss with this
-                   threshold (okp_refine_pose_views_robust, views_each = 1)."""
+                   threshold (okp_refine_pose_views_robust, views_each = 1).
+        confidence (keyword, default None) a ConfidenceWeights: the window then keeps a ring of priors next to its ring of bearings
+                   (okp_window_push_weighted / okp_window_push_views_weighted) and its refinement weights every bearing by its prior
+                   (okp_refine_pose_views_weighted)."""
 
-    def __init__(self, ticks, min_views=2, max_speed=float("inf"), sigma_px=0.25, iters=6, damping=1e-9, *, huber_px=None):
+    def __init__(self, ticks, min_views=2, max_speed=float("inf"), sigma_px=0.25, iters=6, damping=1e-9, *, huber_px=None, confidence=None):
         def number(name, v):
             if isinstance(v, bool):
                 raise OkpError(f"WindowConfig: {name} = {v!r} is not a number")
@@ -1779,18 +1850,21 @@ class WindowConfig:
             raise OkpError(f"WindowConfig: damping = {damping!r} must be finite and not negative")
         self.iters = integer("iters", iters, 1, REFINE_MAX_ITERS)
         self.huber_px = _huber_px("WindowConfig", huber_px)
+        self.confidence = _confidence("WindowConfig", confidence)
 
     def __repr__(self):
         flag = f", huber_px={self.huber_px}" if self.huber_px is not None else ""
+        flag += f", confidence={self.confidence}" if self.confidence is not None else ""
         return (f"WindowConfig(ticks={self.ticks}, min_views={self.min_views}, max_speed={self.max_speed}, sigma_px={self.sigma_px}, iters={self.iters}, "
                 f"damping={self.damping}{flag})")
 
 
-def window_state(B, max_tracks, S, ticks, device):
+def window_state(B, max_tracks, S, ticks, device, prior=False):
     """An empty window of B streams x max_tracks slots x S model rows x ticks columns: {"win_obs" [B,T,S,W,2] float64, all NaN, "win_views"
     [B,T,W,14] float64 and "win_i" [B,T,4] int32 (owner id, head, filled, one spare), zeros} on `device` - window_push() steps it in place -
     plus what the refinement of the window reads next to it on every call: "win_assignment" [B,T,S] int32, the identity (ring rows are model
-    rows), and "win_n" [B] int32 filled with T (every slot is an "object"; free ones arrive with a NaN pose)."""
+    rows), and "win_n" [B] int32 filled with T (every slot is an "object"; free ones arrive with a NaN pose).  prior=True (a WindowConfig with
+    confidence): also "win_prior" [B,T,S,W] float64, all NaN, the ring of the bearings' priors."""
     B, T, S, W = int(B), int(max_tracks), int(S), int(ticks)
     if B < 1 or not 1 <= T <= TRACK_MAX_TRACKS or not 1 <= S <= POSE_MAX_POINTS or not 1 <= W <= REFINE_MAX_VIEWS:
         raise OkpError(f"window_state: B = {B} streams (at least 1) of max_tracks = {T} slots (1 .. {TRACK_MAX_TRACKS}), S = {S} model rows (1 .. {POSE_MAX_POINTS}), "
@@ -1798,10 +1872,13 @@ def window_state(B, max_tracks, S, ticks, device):
     device = torch.device(device)
     if device.type != "cuda":
         raise OkpError("window_state: the window's state lives in device memory: the HIP path has no CPU fallback")
-    return {"win_obs": torch.full((B, T, S, W, 2), float("nan"), dtype=torch.float64, device=device),
-            "win_views": torch.zeros((B, T, W, 14), dtype=torch.float64, device=device), "win_i": torch.zeros((B, T, 4), dtype=torch.int32, device=device),
-            "win_assignment": torch.arange(S, dtype=torch.int32, device=device).repeat(B, T, 1).contiguous(),
-            "win_n": torch.full((B,), T, dtype=torch.int32, device=device)}
+    state = {"win_obs": torch.full((B, T, S, W, 2), float("nan"), dtype=torch.float64, device=device),
+             "win_views": torch.zeros((B, T, W, 14), dtype=torch.float64, device=device), "win_i": torch.zeros((B, T, 4), dtype=torch.int32, device=device),
+             "win_assignment": torch.arange(S, dtype=torch.int32, device=device).repeat(B, T, 1).contiguous(),
+             "win_n": torch.full((B,), T, dtype=torch.int32, device=device)}
+    if prior:
+        state["win_prior"] = torch.full((B, T, S, W), float("nan"), dtype=torch.float64, device=device)
+    return state
 
 
 def window_push(state, tab, assignment, status, track, T_WC, cam, cfg):
@@ -1812,7 +1889,9 @@ def window_push(state, tab, assignment, status, track, T_WC, cam, cfg):
     T_WC [B,12] float64 (device), this tick's camera poses; cam: the okp_camera the table was lifted through (only fx and fy are read);
     cfg: a WindowConfig
     -> {"n_views" [B,T] int32 (filled columns), "start" [B,T,12] float64 (the track pose bit for bit from cfg.min_views columns on, otherwise
-        NaN)}.  One launch, no host sync."""
+        NaN)}.  One launch, no host sync.  With cfg.confidence set the launch is okp_window_push_weighted: state (window_state(..., prior=True))
+    also holds "win_prior" [B,T,S,W], which gets the prior of every bearing pushed - from the fourth value of its table row - and NaN wherever
+    win_obs gets (NaN, NaN)."""
     if not isinstance(cfg, WindowConfig):
         raise OkpError("cfg must be an ops.WindowConfig")
     if not isinstance(cam, _lib.okp_camera):
@@ -1851,22 +1930,41 @@ def window_push(state, tab, assignment, status, track, T_WC, cam, cfg):
                                   ("win_i", win_i, torch.int32, (b, t, 4))):
         if x.dtype != dtype or tuple(x.shape) != shape or x.device != dev or not x.is_contiguous():
             raise OkpError(f"state[{name!r}] must be a contiguous {dtype} tensor {list(shape)} on the table's device: window_state({b}, {t}, {s}, cfg.ticks = {w}, device)")
+    win_prior = _win_prior(state, cfg, (b, t, s, w), dev, f"window_state({b}, {t}, {s}, cfg.ticks = {w}, device, prior=True)")
     n_views = torch.empty((b, t), dtype=torch.int32, device=dev)
     start = torch.empty((b, t, 12), dtype=torch.float64, device=dev)
-    _dispatch(_ops().window_push, _cam_list(cam), tab.contiguous(), assignment.contiguous(), status.contiguous(), meas_of.contiguous(), track_i.contiguous(),
-              track_f.contiguous(), track_pose.contiguous(), T_WC.contiguous(), cfg.min_views, cfg.max_speed, win_obs, win_views, win_i, n_views, start, stream_int())
+    inputs = (_cam_list(cam), tab.contiguous(), assignment.contiguous(), status.contiguous(), meas_of.contiguous(), track_i.contiguous(), track_f.contiguous(),
+              track_pose.contiguous(), T_WC.contiguous(), cfg.min_views, cfg.max_speed)
+    if win_prior is not None:
+        _dispatch(_ops().window_push_weighted, *inputs, cfg.confidence.ref, cfg.confidence.floor, win_obs, win_prior, win_views, win_i, n_views, start, stream_int())
+    else:
+        _dispatch(_ops().window_push, *inputs, win_obs, win_views, win_i, n_views, start, stream_int())
     return {"n_views": n_views, "start": start}
+
+
+def _win_prior(state, cfg, shape, dev, made_by):
+    """state["win_prior"] of a window whose config has confidence set, checked; None without the keyword."""
+    if cfg.confidence is None:
+        return None
+    x = state.get("win_prior") if isinstance(state, dict) else None
+    if x is None:
+        raise OkpError(f"state has no \"win_prior\": cfg.confidence is set, so the window keeps a ring of priors: {made_by}")
+    require_cuda(x, "win_prior")
+    if x.dtype != torch.float64 or tuple(x.shape) != shape or x.device != dev or not x.is_contiguous():
+        raise OkpError(f"state['win_prior'] must be a contiguous {torch.float64} tensor {list(shape)} on the window's device: {made_by}")
+    return x
 
 
 # ---- a rig's tracked objects refined against a sliding window of ticks x cameras (okp_window_push_views, okp_refine_pose_views_wide) ----------------
 REFINE_WIDE_MAX_VIEWS = 512                                                      # include/okp.h OKP_REFINE_WIDE_MAX_VIEWS
 
 
-def window_views_state(B, max_tracks, S, ticks, n_views, device):
+def window_views_state(B, max_tracks, S, ticks, n_views, device, prior=False):
     """An empty window of B streams x max_tracks slots x S model rows x ticks columns of n_views cameras each: {"win_obs" [B,T,S,W*V,2]
     float64, all NaN, "win_views" [B,T,W*V,14] float64 and "win_i" [B,T,4] int32 (owner id, head, filled, one spare), zeros} on `device` -
     window_push_views() steps it in place - plus what the refinement of the window reads next to it on every call: "win_assignment" [B,T,S]
-    int32, the identity, and "win_n" [B] int32 filled with T."""
+    int32, the identity, and "win_n" [B] int32 filled with T.  prior=True (a WindowConfig with confidence): also "win_prior" [B,T,S,W*V] float64,
+    all NaN, the ring of the bearings' priors."""
     B, T, S, W, V = int(B), int(max_tracks), int(S), int(ticks), int(n_views)
     if B < 1 or not 1 <= T <= TRACK_MAX_TRACKS or not 1 <= S <= POSE_MAX_POINTS or not 1 <= W <= REFINE_MAX_VIEWS or not 1 <= V <= 2 * RIG_MAX_PAIRS:
         raise OkpError(f"window_views_state: B = {B} streams (at least 1) of max_tracks = {T} slots (1 .. {TRACK_MAX_TRACKS}), S = {S} model rows (1 .. {POSE_MAX_POINTS}), "
@@ -1876,13 +1974,16 @@ def window_views_state(B, max_tracks, S, ticks, n_views, device):
     device = torch.device(device)
     if device.type != "cuda":
         raise OkpError("window_views_state: the window's state lives in device memory: the HIP path has no CPU fallback")
-    return {"win_obs": torch.full((B, T, S, W * V, 2), float("nan"), dtype=torch.float64, device=device),
-            "win_views": torch.zeros((B, T, W * V, 14), dtype=torch.float64, device=device), "win_i": torch.zeros((B, T, 4), dtype=torch.int32, device=device),
-            "win_assignment": torch.arange(S, dtype=torch.int32, device=device).repeat(B, T, 1).contiguous(),
-            "win_n": torch.full((B,), T, dtype=torch.int32, device=device)}
+    state = {"win_obs": torch.full((B, T, S, W * V, 2), float("nan"), dtype=torch.float64, device=device),
+             "win_views": torch.zeros((B, T, W * V, 14), dtype=torch.float64, device=device), "win_i": torch.zeros((B, T, 4), dtype=torch.int32, device=device),
+             "win_assignment": torch.arange(S, dtype=torch.int32, device=device).repeat(B, T, 1).contiguous(),
+             "win_n": torch.full((B,), T, dtype=torch.int32, device=device)}
+    if prior:
+        state["win_prior"] = torch.full((B, T, S, W * V), float("nan"), dtype=torch.float64, device=device)
+    return state
 
 
-def window_push_views(state, obs, assignment, status, track, T_WB, views, cfg):
+def window_push_views(state, obs, assignment, status, track, T_WB, views, cfg, prior=None):
     """One tick of a rig's sliding window (okp_window_push_views; the ring, its resets and the push are specified in include/okp.h).  state:
     window_views_state(...), stepped in place; obs [B,max_obj,S,V,2] float64: the tick's bearings by table slot (rig_bearings; a rig has
     B = 1); assignment [B,max_obj,S] int32 and status [B,max_obj] int32, the pose stage's; track: the dict of this tick's track_objects()
@@ -1890,9 +1991,13 @@ def window_push_views(state, obs, assignment, status, track, T_WB, views, cfg):
     rig pose; views [V,14] float64 (device): rig_views(...) moved to the device; cfg: a WindowConfig, whose ticks x V may not exceed
     REFINE_WIDE_MAX_VIEWS
     -> {"n_views" [B,T] int32 (filled columns: ticks), "start" [B,T,12] float64 (the track pose bit for bit from cfg.min_views columns on,
-        otherwise NaN)}.  One launch, no host sync."""
+        otherwise NaN)}.  One launch, no host sync.  With cfg.confidence set the launch is okp_window_push_views_weighted: prior
+    [B,max_obj,S,V] float64 (rig_bearings_weighted's) is required and state (window_views_state(..., prior=True)) also holds "win_prior"
+    [B,T,S,W*V], into which the prior rows are copied alongside the bearing rows."""
     if not isinstance(cfg, WindowConfig):
         raise OkpError("cfg must be an ops.WindowConfig")
+    if (prior is None) != (cfg.confidence is None):
+        raise OkpError("prior: the bearings' priors (rig_bearings_weighted) go with a WindowConfig whose confidence is set, and only with one")
     try:
         meas_of, track_i, track_f, track_pose = track["meas_of"], track["track_i"], track["track_f"], track["track_pose"]
     except (TypeError, KeyError, IndexError):
@@ -1930,10 +2035,19 @@ def window_push_views(state, obs, assignment, status, track, T_WB, views, cfg):
         if x.dtype != dtype or tuple(x.shape) != shape or x.device != dev or not x.is_contiguous():
             raise OkpError(f"state[{name!r}] must be a contiguous {dtype} tensor {list(shape)} on the bearings' device: "
                            f"window_views_state({b}, {t}, {s}, cfg.ticks = {w}, {v}, device)")
+    win_prior = _win_prior(state, cfg, (b, t, s, w * v), dev, f"window_views_state({b}, {t}, {s}, cfg.ticks = {w}, {v}, device, prior=True)")
+    if prior is not None:
+        require_cuda(prior, "prior")
+        if prior.dtype != torch.float64 or tuple(prior.shape) != (b, max_obj, s, v) or prior.device != dev:
+            raise OkpError(f"prior must be float64 [{b},{max_obj},{s},{v}] on the bearings' device: one value for each bearing of obs (rig_bearings_weighted)")
     n_views = torch.empty((b, t), dtype=torch.int32, device=dev)
     start = torch.empty((b, t, 12), dtype=torch.float64, device=dev)
-    _dispatch(_ops().window_push_views, obs.contiguous(), assignment.contiguous(), status.contiguous(), meas_of.contiguous(), track_i.contiguous(), track_f.contiguous(),
-              track_pose.contiguous(), T_WB.contiguous(), views.contiguous(), w, cfg.min_views, cfg.max_speed, win_obs, win_views, win_i, n_views, start, stream_int())
+    inputs = (assignment.contiguous(), status.contiguous(), meas_of.contiguous(), track_i.contiguous(), track_f.contiguous(), track_pose.contiguous(),
+              T_WB.contiguous(), views.contiguous(), w, cfg.min_views, cfg.max_speed)
+    if win_prior is not None:
+        _dispatch(_ops().window_push_views_weighted, obs.contiguous(), prior.contiguous(), *inputs, win_obs, win_prior, win_views, win_i, n_views, start, stream_int())
+    else:
+        _dispatch(_ops().window_push_views, obs.contiguous(), *inputs, win_obs, win_views, win_i, n_views, start, stream_int())
     return {"n_views": n_views, "start": start}
 
 
@@ -1951,6 +2065,30 @@ def refine_pose_views_wide(obs, views, pose, n_obj, model, cfg, each=False):
     _dispatch(_ops().refine_pose_views_wide, obs.contiguous(), views.contiguous(), 1 if each else 0, fitted.contiguous(), assignment.contiguous(),
               n_obj.reshape(b).contiguous(), model.contiguous(), cfg.sigma_px, huber_px if huber_px is not None else 0.0, cfg.iters, cfg.damping, out["pose"], out["fit"],
               out["n_obs"], out.get("n_inlier"), out.get("weight"), out["information"], out["status"], stream_int())
+    return out
+
+
+def refine_pose_views_weighted(obs, prior, views, pose, n_obj, model, cfg, each=False, wide=False):
+    """refine_pose_views_wide with a prior for every bearing (okp_refine_pose_views_weighted; the weighted cost is specified in
+    include/okp.h): prior [B,max_obj,S,V] float64 (device) scales the squared residual of bearing (s, v) - rig_bearings_weighted's, or the
+    "win_prior" of a window's state; only the priors of observations are read, and one that is NaN, infinite or not positive makes its object
+    REFINE_SKIPPED.  cfg: a RefineConfig or a WindowConfig WITH confidence set (its ref and floor were used where the priors were made; here
+    it says that the weighted path is meant); huber_px selects the Huber cost on the whitened residuals, and "weight" stays the Huber weight
+    alone.  The other arguments and the returned dict are refine_pose_views_wide's, V up to REFINE_WIDE_MAX_VIEWS.  With every prior 1.0 the
+    result has the bits of the unweighted refinement of the same shape: refine_pose_views / refine_pose_views_each up to REFINE_MAX_VIEWS views,
+    refine_pose_views_wide above.  wide=True (okp_refine_pose_views_weighted_wide) runs the wide kernel's instance whatever V is - the bits of
+    refine_pose_views_wide for every V, which up to 32 views are not those of the one-wave kernels: a rig's window refines its ring with it.
+    One launch, no host sync."""
+    if not isinstance(wide, (bool, np.bool_)):
+        raise OkpError(f"wide = {wide!r} must be True (the wide kernel whatever V is) or False")
+    fitted, assignment, b, max_obj, s, v, dev = _views_inputs(
+        each, obs, views, pose, n_obj, model, cfg, (RefineConfig, WindowConfig), "an ops.RefineConfig or an ops.WindowConfig", REFINE_WIDE_MAX_VIEWS,
+        "rig_bearings_weighted, or the win_obs of a window's state", "", prior=prior)
+    huber_px = getattr(cfg, "huber_px", None)
+    out = _views_outputs(b, max_obj, s, v, dev, huber_px is not None)
+    _dispatch(_ops().refine_pose_views_weighted_wide if wide else _ops().refine_pose_views_weighted, obs.contiguous(), prior.contiguous(), views.contiguous(), 1 if each else 0, fitted.contiguous(),
+              assignment.contiguous(), n_obj.reshape(b).contiguous(), model.contiguous(), cfg.sigma_px, huber_px if huber_px is not None else 0.0, cfg.iters,
+              cfg.damping, out["pose"], out["fit"], out["n_obs"], out.get("n_inlier"), out.get("weight"), out["information"], out["status"], stream_int())
     return out
 
 

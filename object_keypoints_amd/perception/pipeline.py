@@ -590,6 +590,8 @@ def _pose_fields(pose, n, refine=None):
             fields.update(refine_n_obs=refine["n_obs"][n])
         if "n_inlier" in refine:                 # under a Huber loss (RefineConfig.huber_px): "refine_fit" is [max_obj,4], "refine_weight" [max_obj,S,V]
             fields.update(refine_n_inlier=refine["n_inlier"][n], refine_weight=refine["weight"][n])
+        if "prior" in refine:                    # weighted by the peaks' confidences (RefineConfig.confidence): "refine_prior" [max_obj,S,V]
+            fields.update(refine_prior=refine["prior"][n])
         if "hypothesis" in refine:
             fields.update(refine_assignment=refine["assignment"][n], refine_hypothesis=refine["hypothesis"][n], refine_cost=refine["cost"][n])
     return fields
@@ -605,6 +607,8 @@ def _track_fields(track, n, window=None):
         fields["window_pose_C"] = window["pose_C" if "pose_C" in window else "pose_B"][n]       # (a rig's window: the rig frame, [T,S,W*V] weights)
         if "n_inlier" in window:                 # under a Huber loss (WindowConfig.huber_px): "window_fit" is [T,4], "window_weight" [T,S,W]
             fields.update(window_n_inlier=window["n_inlier"][n], window_weight=window["weight"][n])
+        if "prior" in window:                    # weighted by the confidences (WindowConfig.confidence): "window_prior" [T,S,W] ([T,S,W*V] for a rig)
+            fields.update(window_prior=window["prior"][n])
     return fields
 
 
@@ -635,7 +639,17 @@ def _window_entries(rec, slot, key='T_CO_window', cameras=None):
         if cameras is not None:
             outliers = [(s, v // cameras, v % cameras) for s, v in outliers]
         entries.update(window_inliers=int(rec["window_n_inlier"][slot]), window_robust_rmse=(float(fit[2]), float(fit[3])), window_outliers=outliers)
+    if "window_prior" in rec:                # WindowConfig.confidence: 'window_priors', indexed as 'window_outliers' is, with the prior as the last value
+        priors = _priors(rec["window_prior"][slot])
+        if cameras is not None:
+            priors = [(s, v // cameras, v % cameras, a) for s, v, a in priors]
+        entries.update(window_priors=priors)
     return entries
+
+
+def _priors(prior):
+    """The (row, column, prior) entries of one object's table of priors [S,V] that hold one: the bearings it has (NaN: no bearing)."""
+    return [(int(s), int(v), float(prior[s, v])) for s, v in zip(*np.nonzero(~np.isnan(prior)))]
 
 
 def _outliers(weight):
@@ -674,6 +688,8 @@ def _rig_refine_entries(rec, o, T_BO):
                'pose_information': rec["information"][o].reshape(6, 6).copy(), 'refine_status': int(rec["refine_status"][o])}
     if "refine_n_inlier" in rec:
         entries.update(refine_inliers=int(rec["refine_n_inlier"][o]), robust_rmse=(float(fit[o, 2]), float(fit[o, 3])), refine_outliers=_outliers(rec["refine_weight"][o]))
+    if "refine_prior" in rec:                # RefineConfig.confidence: 'refine_priors', (table slot, camera, prior) of every bearing the object has
+        entries.update(refine_priors=_priors(rec["refine_prior"][o]))
     return entries
 
 
@@ -781,20 +797,30 @@ class _Window:
     def state(self, device, streams, rows):
         st = self.states.get((device, streams))
         if st is None:
-            st = self.states[(device, streams)] = ops.window_state(streams, self.max_tracks, rows, self.cfg.ticks, device)
+            st = self.states[(device, streams)] = ops.window_state(streams, self.max_tracks, rows, self.cfg.ticks, device, **self._prior())
         return st
+
+    def _prior(self):
+        """The keyword that gives the state its ring of priors - only under cfg.confidence: without it the call is the one it was."""
+        return {"prior": True} if self.cfg.confidence is not None else {}
 
     def step(self, tab, assignment, status, track, T_WC, cam, model):
         """ops.window_push on the state of the table's device and streams, ops.refine_pose_views_each on that state from the pushed start, and
         the refined poses back in the camera frame -> the entries of the step's "window" dict."""
         st = self.state(tab.device, int(tab.shape[0]), int(tab.shape[2]))
         pushed = ops.window_push(st, tab, assignment, status, track, T_WC, cam, self.cfg)
-        refined = ops.refine_pose_views_each(st["win_obs"], st["win_views"], {"pose": pushed["start"], "assignment": st["win_assignment"]}, st["win_n"], model, self.cfg)
+        start = {"pose": pushed["start"], "assignment": st["win_assignment"]}
+        if self.cfg.confidence is not None:      # the push kept the ring of priors: the weighted refinement, one launch as well
+            refined = ops.refine_pose_views_weighted(st["win_obs"], st["win_prior"], st["win_views"], start, st["win_n"], model, self.cfg, each=True)
+        else:
+            refined = ops.refine_pose_views_each(st["win_obs"], st["win_views"], start, st["win_n"], model, self.cfg)
         pose_C = ops.change_frame(T_WC, poses=refined["pose"], inverse=True)["poses"]
         out = {"pose": refined["pose"], "fit": refined["fit"], "n_obs": refined["n_obs"], "n_views": pushed["n_views"], "information": refined["information"],
                "status": refined["status"], "pose_C": pose_C, "win_obs": st["win_obs"], "win_views": st["win_views"], "win_i": st["win_i"]}
         if "n_inlier" in refined:                # cfg.huber_px: the refinement was okp_refine_pose_views_robust
             out.update(n_inlier=refined["n_inlier"], weight=refined["weight"])
+        if "win_prior" in st:                    # cfg.confidence: the ring of priors, a state tensor like win_obs
+            out.update(prior=st["win_prior"])
         return out
 
     def reset(self):
@@ -802,6 +828,8 @@ class _Window:
             st["win_obs"].fill_(float("nan"))
             st["win_views"].zero_()
             st["win_i"].zero_()
+            if "win_prior" in st:
+                st["win_prior"].fill_(float("nan"))
 
 
 class _RigWindow(_Window):
@@ -815,21 +843,26 @@ class _RigWindow(_Window):
     def state(self, device, streams, rows):
         st = self.states.get((device, streams))
         if st is None:
-            st = self.states[(device, streams)] = ops.window_views_state(streams, self.max_tracks, rows, self.cfg.ticks, self.cameras, device)
+            st = self.states[(device, streams)] = ops.window_views_state(streams, self.max_tracks, rows, self.cfg.ticks, self.cameras, device, **self._prior())
         return st
 
-    def step(self, obs, assignment, status, track, T_WB, views, model):
+    def step(self, obs, assignment, status, track, T_WB, views, model, prior=None):
         """ops.window_push_views on the state of the bearings' device and streams, ops.refine_pose_views_wide on that state from the pushed
         start, and the refined poses back in the rig frame -> the entries of the tick's "window" dict."""
         st = self.state(obs.device, int(obs.shape[0]), int(obs.shape[2]))
-        pushed = ops.window_push_views(st, obs, assignment, status, track, T_WB, views, self.cfg)
-        refined = ops.refine_pose_views_wide(st["win_obs"], st["win_views"], {"pose": pushed["start"], "assignment": st["win_assignment"]}, st["win_n"], model, self.cfg,
-                                             each=True)
+        pushed = ops.window_push_views(st, obs, assignment, status, track, T_WB, views, self.cfg, **({"prior": prior} if prior is not None else {}))
+        start = {"pose": pushed["start"], "assignment": st["win_assignment"]}
+        if self.cfg.confidence is not None:      # the push kept the ring of priors: the weighted refinement, one launch as well
+            refined = ops.refine_pose_views_weighted(st["win_obs"], st["win_prior"], st["win_views"], start, st["win_n"], model, self.cfg, each=True, wide=True)
+        else:
+            refined = ops.refine_pose_views_wide(st["win_obs"], st["win_views"], start, st["win_n"], model, self.cfg, each=True)
         pose_B = ops.change_frame(T_WB, poses=refined["pose"], inverse=True)["poses"]
         out = {"pose": refined["pose"], "fit": refined["fit"], "n_obs": refined["n_obs"], "n_views": pushed["n_views"], "information": refined["information"],
                "status": refined["status"], "pose_B": pose_B, "tick_obs": obs, "win_obs": st["win_obs"], "win_views": st["win_views"], "win_i": st["win_i"]}
         if "n_inlier" in refined:                # cfg.huber_px: the Huber instance
             out.update(n_inlier=refined["n_inlier"], weight=refined["weight"])
+        if "win_prior" in st:                    # cfg.confidence: the ring of priors, and the tick's
+            out.update(prior=st["win_prior"], tick_prior=prior)
         return out
 
 
@@ -917,20 +950,29 @@ class _ObjectStage:
         self.window = None
         if window is not None:
             self.window = _RigWindow(window, track.max_tracks, rig_cameras) if rig_cameras else _Window(window, track.max_tracks)
+        # a rig's one launch of the bearings serves the refinement and the window: the priors it writes follow one ConfidenceWeights
+        given = [c for c in (getattr(refine, "confidence", None), getattr(window, "confidence", None) if rig_cameras else None) if c is not None]
+        if len(given) == 2 and (given[0].ref, given[0].floor) != (given[1].ref, given[1].floor):
+            raise OkpError(f"refine has confidence = {given[0]} and rig_window confidence = {given[1]}: the tick's bearings are collected, and their priors "
+                           "formed, in one launch for both, so the two must agree")
+        self.bearings_confidence = given[0] if given else None
 
     def run(self, tab, n_obj, points, overflow, frame_pose, cam=None, rig=None):
         """The stage behind a step: tab = the object point table (None without a model), n_obj, points (what the world frame shows besides the
         objects) and overflow = the step's own; frame_pose: the checked per-step pose, or None; cam: the camera of a refined table; rig: what
         a refined rig tick observes with - {"table", "count", "xyc", "match", "fused", "views"}
         -> the entries the step's dict gains, in order: "pose", "refine", "world", "track", "window"."""
-        out, fed, obs = {}, None, None
+        out, fed, obs, prior = {}, None, None, None
         if self.model.host is not None:
             model = self.model(tab.device)
             fed = out["pose"] = dict(ops.object_pose(tab, n_obj, model, self.type_count, self.max_rmse), tab=tab)
             if self.refine is not None:
                 if rig is not None:
-                    obs = ops.rig_bearings(rig["table"], rig["count"], rig["xyc"], rig["match"], rig["fused"], self.type_count)
-                    out["refine"] = dict(ops.refine_pose_views(obs, rig["views"], fed, n_obj, model, self.refine), obs=obs)
+                    obs, prior = self._bearings(rig)
+                    if self.refine.confidence is not None:
+                        out["refine"] = dict(ops.refine_pose_views_weighted(obs, prior, rig["views"], fed, n_obj, model, self.refine), obs=obs, prior=prior)
+                    else:
+                        out["refine"] = dict(ops.refine_pose_views(obs, rig["views"], fed, n_obj, model, self.refine), obs=obs)
                 elif self.refine.resolve_assignment:
                     out["refine"] = ops.refine_assignments(tab, fed, n_obj, model, self.type_count, cam, self.refine)
                 else:
@@ -949,12 +991,20 @@ class _ObjectStage:
                 out["track"]["track_pose_C"] = ops.change_frame(frame_pose, poses=out["track"]["track_pose"], inverse=True)["poses"]
         if isinstance(self.window, _RigWindow):
             if obs is None:                      # (no refinement: the one launch of the bearings is the window's)
-                obs = ops.rig_bearings(rig["table"], rig["count"], rig["xyc"], rig["match"], rig["fused"], self.type_count)
-            out["window"] = self.window.step(obs, out["pose"]["assignment"], out["pose"]["status"], out["track"], frame_pose, rig["views"], model)
+                obs, prior = self._bearings(rig)
+            weighted = {"prior": prior} if self.window.cfg.confidence is not None else {}
+            out["window"] = self.window.step(obs, out["pose"]["assignment"], out["pose"]["status"], out["track"], frame_pose, rig["views"], model, **weighted)
         elif self.window is not None:
             resolved = out.get("refine", {}).get("assignment")       # the refined assignment where resolve_assignment produced one
             out["window"] = self.window.step(tab, resolved if resolved is not None else out["pose"]["assignment"], out["pose"]["status"], out["track"], frame_pose, cam, model)
         return out
+
+    def _bearings(self, rig):
+        """The one launch that collects a rig tick's bearings -> (obs, prior): okp_rig_bearings_weighted where the refinement or the window
+        weights them by the peaks' confidences, otherwise okp_rig_bearings and no priors."""
+        if self.bearings_confidence is None:
+            return ops.rig_bearings(rig["table"], rig["count"], rig["xyc"], rig["match"], rig["fused"], self.type_count), None
+        return ops.rig_bearings_weighted(rig["table"], rig["count"], rig["xyc"], rig["match"], rig["fused"], self.type_count, self.bearings_confidence)
 
     def reset_tracks(self):
         if self.tracker is None:
@@ -977,7 +1027,7 @@ class _ObjectStage:
         if "track" in static_out:
             step._track_state = [static_out["track"][k] for k in ("track_f", "track_i", "next_id")]
             if "window" in static_out:
-                step._window_state = [static_out["window"][k] for k in ("win_obs", "win_views", "win_i")]
+                step._window_state = [static_out["window"][k] for k in ("win_obs", "win_views", "win_i", "prior") if k in static_out["window"]]
             self.reset_tracks()
 
 
@@ -1108,6 +1158,9 @@ class BatchedKeypointPipeline(_ObjectStagePipeline):
         if isinstance(refine, ops.RefineConfig) and refine.huber_px is not None:
             raise OkpNotOffered("refine with huber_px: not offered for one camera (five points against six unknowns and a depth prior leave a Huber loss "
                                 "nothing to vote with); window=ops.WindowConfig(..., huber_px=...) and a rig's refine take it")
+        if isinstance(refine, ops.RefineConfig) and refine.confidence is not None:
+            raise OkpNotOffered("refine with confidence: not offered for one camera (the single-camera refinement has no weighted form); "
+                                "window=ops.WindowConfig(..., confidence=...) and StereoStreamPipeline's refine and rig_window take it")
         self.max_objects = max_objects
         self.max_per_type = max_per_type
         self.config = keypoint_config
@@ -1739,6 +1792,10 @@ class StereoStreamPipeline(_ObjectStagePipeline):
                 if key in out:
                     whole[key] = out[key]
             return whole
+        for name, cfg in (("refine", self.refine), ("rig_window", self.rig_window)):
+            if cfg is not None and cfg.confidence is not None:
+                raise OkpNotOffered(f"tick_sharded with {name} and its confidence under a process group: not offered (the weighted refinement reads every "
+                                    "pair's peaks); tick_device and capture_device of a pipeline built with refine / rig_window take the keyword")
         if self.refine is not None:
             raise OkpError("tick_sharded with refine under a process group: the refinement reads every pair's peaks and matches, and the gathered "
                            "payload holds the other ranks' 3D points only")
