@@ -47,6 +47,7 @@ extern "C" {
                                     refining every assignment);
                                     okp_rig_bearings, okp_refine_pose_views, OKP_REFINE_MAX_VIEWS (a rig's object poses refined against every
                                     camera's bearings);
+                                    okp_refine_assignments_views (a rig's interchangeable key points resolved against every camera's bearings);
                                     okp_window_push, okp_refine_pose_views_each (tracked objects refined against a sliding window of ticks'
                                     bearings);
                                     okp_refine_pose_views_robust (those two refinements under a Huber loss);
@@ -853,7 +854,7 @@ int okp_refine_pose(const double* tab_dev, const double* pose_dev, const int32_t
  * Limits.  Uniform weights.  An exactly symmetric model gives equal costs by construction: the lowest index wins and cost[1] ~ cost[0]
  * tells the reader so.  With a quarter of a map pixel of pixel noise on top of 3 % depth noise about one valve in eleven still ends on a
  * wrong assignment (23 of 256 in the specification).  The objects of a rig have their own refinement, okp_refine_pose_views; their
- * assignments are not resolved.
+ * assignments are resolved by okp_refine_assignments_views, not here.
  * Refused on the host before any launch (OKP_EINVAL, the message names the argument): everything okp_refine_pose refuses, K outside
  * [2, 16], a type_count below 1, S > OKP_POSE_MAX_POINTS, prod c_k! > OKP_REFINE_MAX_HYPOTHESES, pose_out overlapping pose,
  * assignment_out overlapping assignment.
@@ -939,7 +940,8 @@ int okp_refine_assignments(const double* tab_dev, const double* pose_dev, const 
  *   order and one butterfly adds the lanes (tests/test_gpu_refine_views.py: 1e-9 on R and t against a NumPy evaluation).  pose_out must not
  *   overlap pose.
  * Limits.  Uniform weights over the observations: the peaks' confidences are not used unless the weighted entry points are called
- * (okp_rig_bearings_weighted, okp_refine_pose_views_weighted, below).  The assignment is okp_object_pose's, as it is.
+ * (okp_rig_bearings_weighted, okp_refine_pose_views_weighted, below).  The assignment is okp_object_pose's, as it is:
+ * okp_refine_assignments_views (below) resolves it against the same bearings first.
  * Refused on the host before any launch (OKP_EINVAL, the message names the argument): a null pointer, B or max_obj < 1, S outside
  * [1, OKP_POSE_MAX_POINTS], V outside [1, OKP_REFINE_MAX_VIEWS], iters outside [1, OKP_REFINE_MAX_ITERS], sigma_px not positive and finite,
  * damping negative or not finite, pose_out overlapping pose.
@@ -961,6 +963,52 @@ int okp_refine_pose_views_each(const double* obs_dev, const double* views_dev, c
                                const int32_t* n_obj_dev, const double* model_dev, double sigma_px, int32_t iters, double damping, int32_t B,
                                int32_t max_obj, int32_t S, int32_t V, double* pose_out_dev, double* fit_dev, int32_t* n_obs_dev,
                                double* information_dev, int32_t* status_dev, void* stream);
+/* okp_refine_assignments_views (csrc/okp_refine_assign_views.hip): a rig's interchangeable key points resolved against every camera's
+ * bearings.  okp_object_pose picks a rig object's assignment by a rigid fit to fused points, and okp_refine_pose_views keeps it as it is: a
+ * wrong pick leaves a pose 120 degrees off for a valve, polished, with a good rmse over the key points it got right.  This entry point is to
+ * okp_refine_pose_views what okp_refine_assignments is to okp_refine_pose: it refines EVERY assignment, each from its own rigid fit to the
+ * table's points, against the bearings of all V views, and keeps the one of least final cost.  The contract is stated in terms of those two;
+ * there is no reference implementation (tests/refine_assign_views_spec.py restates it in NumPy).
+ * One launch, one workgroup of four waves per object - wave w runs the hypotheses w, w + 4, ... over ceil(H / 4) rounds, its lanes split over
+ * the views and the slots as okp_refine_pose_views' are; one barrier, after the last round -, fp64, no atomics, no host wait, capturable; the
+ * same bits on every run.
+ * Inputs: obs [B][max_obj][S][V][2] and views [V][14] as okp_refine_pose_views takes them; tab [B][max_obj][S][4] (okp_rig_object_points: the
+ *   fused points the pose was fitted to), pose, assignment, n_obj, model, type_count HOST [K-1] and K as okp_refine_assignments takes them,
+ *   S = 1 + sum(type_count); sigma_px, iters, damping, B, max_obj, V on the host.  pose and assignment are the fallback, not the start.
+ * Per object o < min(n_obj[b], max_obj):
+ *   1. Precheck; it does not depend on the hypothesis.  A slot is FILLED when its four values of tab are finite (okp_refine_assignments'
+ *      rule).  An OBSERVATION is a filled entry (s, v) of obs whose slot s is filled; n_obs counts them - the same number under every
+ *      hypothesis, which makes the costs comparable - and is written for every live object.  Bearings of a slot that is not filled are never
+ *      used.  OKP_REFINE_SKIPPED when one of the 12 values of the input pose is not finite, when one of the object's S x V entries of obs has
+ *      exactly one NaN half or an infinite half (okp_refine_pose_views' rule, on every entry), or when fewer than 3 filled slots have at least
+ *      one observation.
+ *   2. Hypotheses: okp_refine_assignments, step 2, on the filled mask - the enumeration of okp_object_pose, step 1 -, so a hypothesis index
+ *      means the same in all three stages.  H <= prod_k c_k! <= OKP_REFINE_MAX_HYPOTHESES.
+ *   3. Per hypothesis: the degeneracy rule of okp_refine_assignments, step 3 (the per-hypothesis status OKP_REFINE_SINGULAR).  The start is the
+ *      uniform-weight rigid fit of the matched model rows to the filled points of tab; how the minimum is found is not part of the contract.
+ *      Then exactly `iters` steps of okp_refine_pose_views with the hypothesis' rows as the assignment - the same cost, step, Cholesky pivot
+ *      rule and C(w), the same OKP_REFINE_BEHIND / OKP_REFINE_SINGULAR / OKP_REFINE_REJECTED, the slack 1e-12 x n_obs - and the evaluation at
+ *      the final iterate, J_final.  No depth term, no Huber weight, no priors.
+ *   4. Selection: okp_refine_assignments, step 4 - the least J_final among the hypotheses of status 0, the lowest index on exactly equal
+ *      cost; the runner-up likewise among the rest.
+ *   5. Outputs, all written by every call: pose_out [..][12], fit [..][2] (the rmse in map pixels at the winner's own start and at its final
+ *      iterate) and information [..][36] as okp_refine_pose_views defines them, for the winner; n_obs [..] int32; assignment_out [..][S],
+ *      hypothesis [..][2] and cost [..][2] as okp_refine_assignments defines them; status 0, OKP_REFINE_SKIPPED or OKP_REFINE_NONE (every
+ *      hypothesis ended out).  For ANY non-zero status pose_out and assignment_out are the inputs bit for bit, fit, information and cost are
+ *      NaN, hypothesis is -1.  Objects from n_obj[b] on: NaN, -1, n_obs 0, OKP_REFINE_SKIPPED; their rows are not read.
+ *   The order of the sums is not part of the contract (tests/test_gpu_refine_assign_views.py: 1e-9 on R, t, fit and cost).
+ * Limits.  The selection is under the plain, uniform cost: a gross outlier among the bearings can mislead it before a Huber loss acts
+ * (a pipeline runs the robust or weighted refinement AFTER it, from its pose and assignment).  With one or two pairs some valves stay wrong
+ * (README: the accuracy statement).  An exactly symmetric model gives equal costs: the lowest index wins and cost[1] ~ cost[0] says so.  At
+ * most OKP_REFINE_MAX_HYPOTHESES hypotheses.
+ * Refused on the host before any launch (OKP_EINVAL, the message names the argument): everything okp_refine_pose_views refuses, with V in
+ * [1, OKP_REFINE_MAX_VIEWS]; everything okp_refine_assignments refuses about type_count, K, S and the number of hypotheses; pose_out
+ * overlapping pose, assignment_out overlapping assignment. */
+int okp_refine_assignments_views(const double* obs_dev, const double* views_dev, const double* tab_dev, const double* pose_dev,
+                                 const int32_t* assignment_dev, const int32_t* n_obj_dev, const double* model_dev,
+                                 const int32_t* type_count /* HOST [K-1] */, int32_t K, double sigma_px, int32_t iters, double damping, int32_t B,
+                                 int32_t max_obj, int32_t V, double* pose_out_dev, double* fit_dev, int32_t* n_obs_dev, double* information_dev,
+                                 int32_t* status_dev, int32_t* assignment_out_dev, int32_t* hypothesis_dev, double* cost_dev, void* stream);
 /* okp_refine_pose_views_robust: okp_refine_pose_views under a Huber loss, by iteratively reweighted least squares.  A rig of four pairs has
  * 40 bearings for 6 unknowns and a window of 16 ticks 80: a false peak, a key point grouped to the wrong object, a wrong stereo match or a
  * stale camera pose is one gross error among them, and in plain least squares it pulls the pose by its full residual.  Here its pull is

@@ -395,6 +395,17 @@ def refine_pose_views_each(obs, views, pose, assignment, n_obj, model, sigma_px,
                                                      information.data_ptr(), status.data_ptr(), stream), "okp_refine_pose_views_each")
 
 
+# ---- a rig's interchangeable key points resolved against every camera's bearings (csrc/okp_refine_assign_views.hip) ----------------------------------
+def refine_assignments_views(obs, views, tab, pose, assignment, n_obj, model, type_count, sigma_px, iters, damping, pose_out, fit, n_obs, information, status,
+                             assignment_out, hypothesis, cost, stream):
+    b, max_obj, _, v, _ = obs.shape
+    _lib.check(_lib.lib().okp_refine_assignments_views(obs.data_ptr(), views.data_ptr(), tab.data_ptr(), pose.data_ptr(), assignment.data_ptr(), n_obj.data_ptr(),
+                                                       model.data_ptr(), _int32s(type_count), len(type_count) + 1, sigma_px, iters, damping, b, max_obj, v,
+                                                       pose_out.data_ptr(), fit.data_ptr(), n_obs.data_ptr(), information.data_ptr(), status.data_ptr(),
+                                                       assignment_out.data_ptr(), hypothesis.data_ptr(), cost.data_ptr(), stream),
+               "okp_refine_assignments_views")
+
+
 def refine_pose_views_robust(obs, views, views_each, pose, assignment, n_obj, model, sigma_px, huber_px, iters, damping, pose_out, fit, n_obs, n_inlier, weight,
                              information, status, stream):
     b, max_obj, s, v, _ = obs.shape

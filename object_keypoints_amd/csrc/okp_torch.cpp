@@ -789,6 +789,39 @@ void refine_pose_views_each(const Tensor& obs, const Tensor& views, const Tensor
   refine_views(true, obs, views, pose, assignment, n_obj, model, sigma_px, iters, damping, pose_out, fit, n_obs, information, status, stream);
 }
 
+// A rig's interchangeable key points resolved against every camera's bearings (csrc/okp_refine_assign_views.hip): refine_pose_views' obs and views,
+// refine_assignments' tab, pose, assignment, n_obj, model and type_count -> the winner's pose_out, fit [B,max_obj,2], n_obs, information, status,
+// assignment_out [B,max_obj,S], hypothesis and cost [B,max_obj,2]
+void refine_assignments_views(const Tensor& obs, const Tensor& views, const Tensor& tab, const Tensor& pose, const Tensor& assignment, const Tensor& n_obj,
+                              const Tensor& model, at::IntArrayRef type_count, double sigma_px, int64_t iters, double damping, const Tensor& pose_out, const Tensor& fit,
+                              const Tensor& n_obs, const Tensor& information, const Tensor& status, const Tensor& assignment_out, const Tensor& hypothesis,
+                              const Tensor& cost, int64_t stream) {
+  check_dev(obs, at::kDouble, "obs"); check_dev(views, at::kDouble, "views"); check_dev(tab, at::kDouble, "tab"); check_dev(pose, at::kDouble, "pose");
+  check_dev(assignment, at::kInt, "assignment"); check_dev(n_obj, at::kInt, "n_obj"); check_dev(model, at::kDouble, "model"); check_dev(pose_out, at::kDouble, "pose_out");
+  check_dev(fit, at::kDouble, "fit"); check_dev(n_obs, at::kInt, "n_obs"); check_dev(information, at::kDouble, "information"); check_dev(status, at::kInt, "status");
+  check_dev(assignment_out, at::kInt, "assignment_out"); check_dev(hypothesis, at::kInt, "hypothesis"); check_dev(cost, at::kDouble, "cost");
+  TORCH_CHECK(obs.dim() == 5 && obs.size(4) == 2, "okp: obs is [B,max_obj,S,V,2] float64");
+  const int64_t B = obs.size(0), max_obj = obs.size(1), S = obs.size(2), V = obs.size(3);
+  int64_t want = 1;
+  for (auto c : type_count) want += c;
+  TORCH_CHECK(want == S && model.numel() == S * 3, "okp: obs has S = 1 + sum(type_count) slots and model is [S,3] float64");
+  TORCH_CHECK(views.numel() == V * 14 && tab.numel() == B * max_obj * S * 4 && pose.numel() == B * max_obj * 12 && assignment.numel() == B * max_obj * S && n_obj.numel() == B,
+              "okp: refine_assignments_views inputs are views [V,14], tab [B,max_obj,S,4], pose [B,max_obj,12], assignment [B,max_obj,S], n_obj [B] and model [S,3]");
+  TORCH_CHECK(pose_out.numel() == B * max_obj * 12 && fit.numel() == B * max_obj * 2 && n_obs.numel() == B * max_obj && information.numel() == B * max_obj * 36 &&
+              status.numel() == B * max_obj && assignment_out.numel() == B * max_obj * S && hypothesis.numel() == B * max_obj * 2 && cost.numel() == B * max_obj * 2,
+              "okp: refine_assignments_views outputs are pose_out [B,max_obj,12], fit [B,max_obj,2], n_obs [B,max_obj], information [B,max_obj,36], status [B,max_obj], "
+              "assignment_out [B,max_obj,S], hypothesis and cost [B,max_obj,2]");
+  TORCH_CHECK(iters >= INT32_MIN && iters <= INT32_MAX, "okp: iters does not fit an int32");
+  TORCH_CHECK(B <= INT32_MAX && max_obj <= INT32_MAX && V <= INT32_MAX, "okp: obs is too large");
+  std::vector<int32_t> tc(type_count.begin(), type_count.end());
+  tc.push_back(0);
+  check_rc(okp_refine_assignments_views(obs.data_ptr<double>(), views.data_ptr<double>(), tab.data_ptr<double>(), pose.data_ptr<double>(), assignment.data_ptr<int32_t>(),
+                                        n_obj.data_ptr<int32_t>(), model.data_ptr<double>(), tc.data(), (int32_t)type_count.size() + 1, sigma_px, (int32_t)iters, damping,
+                                        (int32_t)B, (int32_t)max_obj, (int32_t)V, pose_out.data_ptr<double>(), fit.data_ptr<double>(), n_obs.data_ptr<int32_t>(),
+                                        information.data_ptr<double>(), status.data_ptr<int32_t>(), assignment_out.data_ptr<int32_t>(), hypothesis.data_ptr<int32_t>(),
+                                        cost.data_ptr<double>(), sp(stream)), "okp_refine_assignments_views");
+}
+
 // The two under a Huber loss (okp_refine_pose_views_robust): views [V,14] (views_each = 0) or [B,max_obj,V,14] (1); fit is [B,max_obj,4], and
 // n_inlier [B,max_obj] and weight [B,max_obj,S,V] are written next to the plain outputs
 void refine_pose_views_robust(const Tensor& obs, const Tensor& views, int64_t views_each, const Tensor& pose, const Tensor& assignment, const Tensor& n_obj,
@@ -1246,6 +1279,9 @@ TORCH_LIBRARY(okp, m) {
   m.def("refine_assignments(float[] camera, Tensor tab, Tensor pose, Tensor assignment, Tensor n_obj, Tensor model, int[] type_count, float sigma_px, float sigma_z, int iters, "
         "float damping, Tensor(a!) pose_out, Tensor(b!) fit, Tensor(c!) information, Tensor(d!) status, Tensor(e!) assignment_out, Tensor(f!) hypothesis, Tensor(g!) cost, "
         "int stream) -> ()", refine_assignments);
+  m.def("refine_assignments_views(Tensor obs, Tensor views, Tensor tab, Tensor pose, Tensor assignment, Tensor n_obj, Tensor model, int[] type_count, float sigma_px, "
+        "int iters, float damping, Tensor(a!) pose_out, Tensor(b!) fit, Tensor(c!) n_obs, Tensor(d!) information, Tensor(e!) status, Tensor(f!) assignment_out, "
+        "Tensor(g!) hypothesis, Tensor(h!) cost, int stream) -> ()", refine_assignments_views);
   m.def("rig_fuse(Tensor points, Tensor poses, int[] type_count, float merge_radius, float object_radius, Tensor(a!) fused, Tensor(b!) n_fused, Tensor(c!) views, "
         "Tensor(d!) object, Tensor(e!) member, Tensor(f!) n_obj, Tensor(g!) overflow, int stream, Tensor? overflow_in=None) -> ()", rig_fuse);
   m.def("project_labels(float[] camera, Tensor world_points, Tensor T_WC, float scale, float crop_x, float crop_y, Tensor(a!) labels, int stream) -> ()", project_labels);

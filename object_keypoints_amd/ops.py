@@ -1468,9 +1468,13 @@ class RefineConfig:
         huber_px  (keyword, default None) map pixels, positive and finite: refine_pose_views / refine_pose_views_each then run under a Huber
                   loss with this threshold (okp_refine_pose_views_robust).  The single-camera refinement does not offer it.
         confidence  (keyword, default None) a ConfidenceWeights: StereoStreamPipeline(refine=...) then weights every bearing by its peak's
-                  confidence (rig_bearings_weighted, refine_pose_views_weighted).  The single-camera refinement does not offer it."""
+                  confidence (rig_bearings_weighted, refine_pose_views_weighted).  The single-camera refinement does not offer it.
+        resolve_views  (keyword, default False) StereoStreamPipeline(refine=...) then resolves a rig's interchangeable key points first: every
+                  assignment refined against the bearings of all 2P cameras, each from its own rigid fit, the one of least final cost kept
+                  (refine_assignments_views); with huber_px or confidence the configured refinement follows from its pose and assignment.
+                  A rig's keyword: one camera has resolve_assignment."""
 
-    def __init__(self, sigma_px=0.25, sigma_z=0.05, iters=6, damping=1e-9, *, resolve_assignment=False, huber_px=None, confidence=None):
+    def __init__(self, sigma_px=0.25, sigma_z=0.05, iters=6, damping=1e-9, *, resolve_assignment=False, huber_px=None, confidence=None, resolve_views=False):
         def number(name, v):
             if isinstance(v, bool):
                 raise OkpError(f"RefineConfig: {name} = {v!r} is not a number")
@@ -1494,11 +1498,15 @@ class RefineConfig:
         self.resolve_assignment = bool(resolve_assignment)
         self.huber_px = _huber_px("RefineConfig", huber_px)
         self.confidence = _confidence("RefineConfig", confidence)
+        if not isinstance(resolve_views, (bool, np.bool_)):
+            raise OkpError(f"RefineConfig: resolve_views = {resolve_views!r} must be True or False")
+        self.resolve_views = bool(resolve_views)
 
     def __repr__(self):
         flag = ", resolve_assignment=True" if self.resolve_assignment else ""
         flag += f", huber_px={self.huber_px}" if self.huber_px is not None else ""
         flag += f", confidence={self.confidence}" if self.confidence is not None else ""
+        flag += ", resolve_views=True" if self.resolve_views else ""
         return f"RefineConfig(sigma_px={self.sigma_px}, sigma_z={self.sigma_z}, iters={self.iters}, damping={self.damping}{flag})"
 
 
@@ -1517,6 +1525,10 @@ def _huber_px(owner, v):
     return h
 
 
+_RESOLVE_VIEWS_ELSEWHERE = ("cfg.resolve_views: not offered here - it is a rig's keyword (StereoStreamPipeline(refine=...), refine_assignments_views); one "
+                            "camera's interchangeable key points are resolved by resolve_assignment=True")
+
+
 def _refine_inputs(tab, pose, n_obj, model, cam, cfg):
     """The argument checks refine_pose and refine_assignments share -> (fitted, assignment, b, max_obj, s, dev)."""
     if not isinstance(cfg, RefineConfig):
@@ -1526,6 +1538,8 @@ def _refine_inputs(tab, pose, n_obj, model, cam, cfg):
     if cfg.confidence is not None:               # (nor a weighted one)
         raise OkpNotOffered("cfg.confidence: not offered for the single-camera refinement (refine_pose_views_weighted takes it: "
                             "StereoStreamPipeline(refine=..., rig_window=...) and BatchedKeypointPipeline(window=...))")
+    if cfg.resolve_views:
+        raise OkpNotOffered(_RESOLVE_VIEWS_ELSEWHERE)
     if not isinstance(cam, _lib.okp_camera):
         raise OkpError(f"cam must be an okp_camera (make_camera), not {type(cam).__name__}")
     try:
@@ -1749,6 +1763,8 @@ def _views_inputs(each, obs, views, pose, n_obj, model, cfg, cfg_types, cfg_text
     if (prior is None) != (getattr(cfg, "confidence", None) is None):      # (never weighted, or uniform, quietly)
         raise OkpNotOffered("cfg.confidence: refine_pose_views_weighted takes it, with the bearings' priors; refine_pose_views, refine_pose_views_each and "
                             "refine_pose_views_wide have no priors and take a config without it")
+    if getattr(cfg, "resolve_views", False):     # (never dropped quietly: these refine ONE assignment)
+        raise OkpNotOffered(_RESOLVE_VIEWS_ELSEWHERE)
     try:
         fitted, assignment = pose["pose"], pose["assignment"]
     except (TypeError, KeyError, IndexError):
@@ -1807,6 +1823,48 @@ def _refine_views(each, obs, views, pose, n_obj, model, cfg):
         _dispatch(B.refine_pose_views_each if each else B.refine_pose_views, obs.contiguous(), views.contiguous(), fitted.contiguous(), assignment.contiguous(),
                   n_obj.reshape(b).contiguous(), model.contiguous(), cfg.sigma_px, cfg.iters, cfg.damping, out["pose"], out["fit"], out["n_obs"], out["information"],
                   out["status"], stream_int())
+    return out
+
+
+def without_resolve_views(cfg):
+    """A RefineConfig with every field of cfg but resolve_views: what the refinement that follows the resolver is called with."""
+    return RefineConfig(cfg.sigma_px, cfg.sigma_z, cfg.iters, cfg.damping, resolve_assignment=cfg.resolve_assignment, huber_px=cfg.huber_px, confidence=cfg.confidence)
+
+
+def refine_assignments_views(obs, views, tab, pose, n_obj, model, type_count, cfg):
+    """Every assignment of every object's interchangeable key points refined against its bearings in all views, each from its own rigid fit to
+    the table's points, and the one of least final cost kept (okp_refine_assignments_views; precheck, hypotheses, selection and outputs are
+    specified in include/okp.h).  obs, views, pose, n_obj and model as refine_pose_views takes them; tab [B,max_obj,S,4] float64 (device;
+    rig_object_points: the points the pose was fitted to) and type_count, the K-1 counts of object_pose, as refine_assignments takes them;
+    pose (object_pose()'s dict) is the fallback, not the start.  cfg: a RefineConfig, of which sigma_px, iters and damping are read; one that
+    carries huber_px or confidence is refused (OkpNotOffered): the selection is under the plain uniform cost, and a pipeline runs the robust or
+    weighted refinement after it.
+    -> refine_pose_views' "pose", "fit" [B,max_obj,2], "n_obs", "information" and "status" (0, REFINE_SKIPPED or REFINE_NONE) of the winner,
+        and refine_assignments' "assignment" [B,max_obj,S] int32, "hypothesis" [B,max_obj,2] int32 and "cost" [B,max_obj,2] float64.  Where the
+        status is not 0, "pose" and "assignment" are the inputs bit for bit.  One launch, no host sync."""
+    if not isinstance(cfg, RefineConfig):
+        raise OkpError("cfg must be an ops.RefineConfig")
+    if cfg.huber_px is not None:
+        raise OkpNotOffered("cfg.huber_px: not offered for refine_assignments_views (the assignments are compared under the plain uniform cost; run "
+                            "refine_pose_views with huber_px from its pose and assignment)")
+    if cfg.confidence is not None:
+        raise OkpNotOffered("cfg.confidence: not offered for refine_assignments_views (the assignments are compared under the plain uniform cost; run "
+                            "refine_pose_views_weighted from its pose and assignment)")
+    fitted, assignment, b, max_obj, s, v, dev = _views_inputs(False, obs, views, pose, n_obj, model, without_resolve_views(cfg), RefineConfig, "an ops.RefineConfig",
+                                                              REFINE_MAX_VIEWS, "rig_bearings", " (rig_views)")
+    require_cuda(tab, "tab")
+    if tab.dtype != torch.float64 or tuple(tab.shape) != (b, max_obj, s, 4) or tab.device != dev:
+        raise OkpError(f"tab must be float64 [{b},{max_obj},{s},4] on the bearings' device (rig_object_points)")
+    tc, want = _pose_type_count(type_count, "type_count")
+    if want != s:
+        raise OkpError(f"obs has {s} slots per object, type_count gives S = 1 + sum(type_count) = {want}")
+    check_refine_hypotheses(tc)
+    out = _views_outputs(b, max_obj, s, v, dev, False)
+    out.update(assignment=torch.empty((b, max_obj, s), dtype=torch.int32, device=dev), hypothesis=torch.empty((b, max_obj, 2), dtype=torch.int32, device=dev),
+               cost=torch.empty((b, max_obj, 2), dtype=torch.float64, device=dev))
+    _dispatch(_ops().refine_assignments_views, obs.contiguous(), views.contiguous(), tab.contiguous(), fitted.contiguous(), assignment.contiguous(),
+              n_obj.reshape(b).contiguous(), model.contiguous(), tc, cfg.sigma_px, cfg.iters, cfg.damping, out["pose"], out["fit"], out["n_obs"], out["information"],
+              out["status"], out["assignment"], out["hypothesis"], out["cost"], stream_int())
     return out
 
 

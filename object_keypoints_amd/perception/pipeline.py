@@ -594,6 +594,8 @@ def _pose_fields(pose, n, refine=None):
             fields.update(refine_prior=refine["prior"][n])
         if "hypothesis" in refine:
             fields.update(refine_assignment=refine["assignment"][n], refine_hypothesis=refine["hypothesis"][n], refine_cost=refine["cost"][n])
+        if "resolve_status" in refine:           # a rig's resolve_views: the resolver's own status next to the refinement's
+            fields.update(resolve_status=refine["resolve_status"][n])
     return fields
 
 
@@ -690,6 +692,9 @@ def _rig_refine_entries(rec, o, T_BO):
         entries.update(refine_inliers=int(rec["refine_n_inlier"][o]), robust_rmse=(float(fit[o, 2]), float(fit[o, 3])), refine_outliers=_outliers(rec["refine_weight"][o]))
     if "refine_prior" in rec:                # RefineConfig.confidence: 'refine_priors', (table slot, camera, prior) of every bearing the object has
         entries.update(refine_priors=_priors(rec["refine_prior"][o]))
+    if "refine_hypothesis" in rec:           # resolve_views: the winning assignment (model row per slot), (winner, runner-up) indices and costs, the resolver's status
+        entries.update(assignment_refined=rec["refine_assignment"][o].copy(), refine_hypothesis=tuple(int(h) for h in rec["refine_hypothesis"][o]),
+                       refine_cost=tuple(float(c) for c in rec["refine_cost"][o]), resolve_status=int(rec["resolve_status"][o]))
     return entries
 
 
@@ -936,9 +941,12 @@ class _ObjectStage:
                 raise OkpError("refine must be an ops.RefineConfig")
             if points_3d is None:
                 raise OkpError("refine without points_3d: the refinement starts from the pose of the object model")
-            if refine.resolve_assignment:
+            if refine.resolve_assignment or refine.resolve_views:
                 ops.check_refine_hypotheses(type_count)
         self.refine = refine
+        # a rig's resolve_views: the resolver reads sigma_px, iters and damping; the configured refinement that follows it is called without the keyword
+        self.resolver = ops.RefineConfig(refine.sigma_px, refine.sigma_z, refine.iters, refine.damping) if getattr(refine, "resolve_views", False) else None
+        self.refine_after = ops.without_resolve_views(refine) if self.resolver is not None else refine
         if window is not None:
             name, pose = ("rig_window", "rig_pose") if rig_cameras else ("window", "camera_pose")      # (a rig's keyword: its ring holds rig_cameras views per tick)
             if not isinstance(window, ops.WindowConfig):
@@ -969,10 +977,18 @@ class _ObjectStage:
             if self.refine is not None:
                 if rig is not None:
                     obs, prior = self._bearings(rig)
+                    start, resolved = fed, None
+                    if self.resolver is not None:                # every assignment against all cameras' bearings: the pose and assignment of the least cost
+                        resolved = ops.refine_assignments_views(obs, rig["views"], tab, fed, n_obj, model, self.type_count, self.resolver)
+                        start = dict(fed, pose=resolved["pose"], assignment=resolved["assignment"])      # (the fit's where the resolver's status is not 0)
                     if self.refine.confidence is not None:
-                        out["refine"] = dict(ops.refine_pose_views_weighted(obs, prior, rig["views"], fed, n_obj, model, self.refine), obs=obs, prior=prior)
-                    else:
-                        out["refine"] = dict(ops.refine_pose_views(obs, rig["views"], fed, n_obj, model, self.refine), obs=obs)
+                        out["refine"] = dict(ops.refine_pose_views_weighted(obs, prior, rig["views"], start, n_obj, model, self.refine_after), obs=obs, prior=prior)
+                    elif resolved is None or self.refine.huber_px is not None:
+                        out["refine"] = dict(ops.refine_pose_views(obs, rig["views"], start, n_obj, model, self.refine_after), obs=obs)
+                    else:                                        # neither a Huber loss nor priors: the resolver is the whole refinement
+                        out["refine"] = dict(resolved, obs=obs)
+                    if resolved is not None:
+                        out["refine"].update(assignment=resolved["assignment"], hypothesis=resolved["hypothesis"], cost=resolved["cost"], resolve_status=resolved["status"])
                 elif self.refine.resolve_assignment:
                     out["refine"] = ops.refine_assignments(tab, fed, n_obj, model, self.type_count, cam, self.refine)
                 else:
@@ -993,7 +1009,9 @@ class _ObjectStage:
             if obs is None:                      # (no refinement: the one launch of the bearings is the window's)
                 obs, prior = self._bearings(rig)
             weighted = {"prior": prior} if self.window.cfg.confidence is not None else {}
-            out["window"] = self.window.step(obs, out["pose"]["assignment"], out["pose"]["status"], out["track"], frame_pose, rig["views"], model, **weighted)
+            resolved = out.get("refine", {}).get("assignment")       # the resolved assignment where resolve_views produced one
+            out["window"] = self.window.step(obs, resolved if resolved is not None else out["pose"]["assignment"], out["pose"]["status"], out["track"], frame_pose,
+                                             rig["views"], model, **weighted)
         elif self.window is not None:
             resolved = out.get("refine", {}).get("assignment")       # the refined assignment where resolve_assignment produced one
             out["window"] = self.window.step(tab, resolved if resolved is not None else out["pose"]["assignment"], out["pose"]["status"], out["track"], frame_pose, cam, model)
@@ -1161,6 +1179,9 @@ class BatchedKeypointPipeline(_ObjectStagePipeline):
         if isinstance(refine, ops.RefineConfig) and refine.confidence is not None:
             raise OkpNotOffered("refine with confidence: not offered for one camera (the single-camera refinement has no weighted form); "
                                 "window=ops.WindowConfig(..., confidence=...) and StereoStreamPipeline's refine and rig_window take it")
+        if isinstance(refine, ops.RefineConfig) and refine.resolve_views:
+            raise OkpNotOffered("refine with resolve_views=True: not offered for one camera (it resolves a rig's key points against every camera's bearings: "
+                                "StereoStreamPipeline's refine takes it); resolve_assignment=True resolves one camera's")
         self.max_objects = max_objects
         self.max_per_type = max_per_type
         self.config = keypoint_config
@@ -1509,7 +1530,8 @@ class StereoStreamPipeline(_ObjectStagePipeline):
                  fuse_capacity=None, points_3d=None, max_rmse=None, track=None, world_frame=False, refine=None, rig_window=None):
         self.net = net
         if isinstance(refine, ops.RefineConfig) and refine.resolve_assignment:
-            raise OkpNotOffered("refine with resolve_assignment=True: not offered for a rig (its refinement keeps the assignment of the fit)")
+            raise OkpNotOffered("refine with resolve_assignment=True: not offered for a rig (its refinement keeps the assignment of the fit; "
+                                "resolve_views=True resolves a rig's key points against every camera's bearings)")
         if world_frame and rig_poses is None:
             raise OkpError("world_frame without rig_poses, merge_radius and object_radius: the fused tick is what has one frame to pose")
         self.rig = None if hasattr(stereo_camera, "left_camera") else list(stereo_camera)       # one StereoCamera, or a sequence of them
