@@ -55,7 +55,8 @@ extern "C" {
                                     against a sliding window of ticks x cameras);
                                     okp_refine_pose_views_weighted, okp_rig_bearings_weighted, okp_window_push_weighted,
                                     okp_window_push_views_weighted, okp_refine_pose_views_weighted_wide (those refinements weighted by the
-                                    peaks' confidences) */
+                                    peaks' confidences);
+                                    okp_score_objects, OKP_SCORE_* (key-point and pose accuracy of labelled scenes, tabulated on the device) */
 
 /* OKP_F16: IEEE half activations / weights, fp32 accumulate (BASELINE configs[4]).
  * OKP_F32X3 (okp_conv plans only): fp32 activations, weights and results like OKP_F32 - every tensor argument of such a plan is an
@@ -1313,6 +1314,104 @@ int okp_keypoint_loss(const float* const* p_heat_dev, const float* const* p_dept
                       int32_t max_obj, const int32_t* type_count, const float* t_heat_dev, const float* t_depth_dev,
                       const float* t_centers_dev, double depth_weight, double center_weight, double* partial_dev, double* terms_dev,
                       int32_t* mask_count_dev, double* out_dev, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * Accuracy of labelled scenes (csrc/okp_score.hip): a step's object table and up to four sets of poses against labelled truth, tabulated
+ * in an append-only log in device memory that lives across steps and graph replays.  The key-point part is the reference's Results.add
+ * (scripts/eval_model.py:129-232); the pose errors and the detection counters have no reference counterpart: the specification is this
+ * comment (tests/score_spec.py restates it in NumPy).
+ *
+ * okp_score_objects: two launches (one wave per frame; one workgroup that appends), fp64 with no contraction, no floating-point atomics,
+ * no host wait, capturable; the same bits on every run.
+ * Inputs in device memory:
+ *   tab [B][max_obj][S][4] fp64      the object point table of okp_object_points / okp_rig_object_points, rows (X, Y, Z, confidence)
+ *   n_obj [B] int32                  clamped to [0, max_obj]
+ *   truth [B][G][S][4] fp64          the labelled key points in the table's frame, row 0 the centre; the fourth value is never read, so
+ *                                    okp_change_frame's output can be passed as it is
+ *   n_truth [B] int32                clamped to [0, G]
+ *   cam (HOST, may be NULL: a rig's table, no view test) with the host scalars size_x, size_y: the camera's image_size in the order the
+ *                                    camera holds it, the bounds of the projected u and v
+ *   P <= OKP_SCORE_MAX_POSES pose sets, given as HOST arrays of P entries: set_pose[p] device [B][set_rows[p]][12] fp64 rows [R | t];
+ *                                    set_index[p] device int32 [B][max_obj], the row of set p that belongs to detection o (a tracker's
+ *                                    track_of), or NULL: row o, which requires set_rows[p] == max_obj.  With P == 0 the three may be NULL
+ *   with P > 0: truth_pose [B][G][12] fp64, the labelled objects' poses in the table's frame, and model [S][3] fp64
+ * Host scalars: match_radius (metres, positive; +infinity is the reference's behaviour: no gate), max_range (positive; the reference's 2.0,
+ *   eval_model.py:169).  match_radius^2 is formed once on the host.
+ * Per frame b and detection o < min(n_obj[b], max_obj), in this order:
+ *   1. Centre.  If the four values of tab[b][o][0] are not all finite: count no_centre, match = -1, stop.
+ *   2. Match (eval_model.py:152-153).  d2(g) = dx*dx + dy*dy between the centre's (X, Y) and truth[b][g][0]'s.  g ascends from 0 over
+ *      g < n_truth[b] with best = +infinity; g is taken, and best = d2(g), when d2(g) < best: the least distance wins, on equal distance
+ *      the lowest g, and a NaN or infinite distance is never taken.  With none taken, or best > match_radius^2: count unmatched,
+ *      match = -2, stop.  Otherwise g* is the g taken last.
+ *   3. View (:157-161), only with cam.  A truth row (X, Y, Z) is IN VIEW when Z > 0 and 0 < u < size_x and 0 < v < size_y, (u, v) =
+ *      cam's projection of the row in raw pixels, computed with the arithmetic of okp_project_labels (one device function serves both;
+ *      it is compiled with that kernel's contraction, so a projection within rounding of a border is decided by the device's bits).
+ *      The Z > 0 clause is ours: the reference divides regardless.  Without cam every row is in view.  If truth[b][g*][0] is not in
+ *      view: count out_of_view, match = -3, stop.  Otherwise match = g*, count detections, and g* is DETECTED in this frame.
+ *   4. Slots s = 0 .. S-1 of the detection (:165-183; the centre slot is scored too, as the reference scores it):
+ *      confidence not finite: the slot is absent (the reference's None group or shorter group): count absent, nothing else.
+ *      confidence finite, X, Y, Z not all finite or not all < max_range: count points and missing (not lifted, or beyond range).
+ *      otherwise d2(j) = (dx*dx + dy*dy) + dz*dz to row j of truth object g*; j ascends over j < S with best = +infinity and is taken
+ *      when d2(j) < best (lowest j on equal distance; a NaN row is never taken); j* is the j taken last.  With none taken, or with
+ *      cam and row j* not in view: count truth_hidden, nothing else.  Else count points and emit one key-point record:
+ *      err = sqrt(d2(j*)), err_xy = sqrt(dx*dx + dy*dy) of that row, id (step, b, o, s).
+ *   5. Poses, where P > 0: every detection that reached step 4 emits one pose record, id (step, b, o, g*), with OKP_SCORE_MAX_POSES
+ *      triples (rotation error in degrees, centre error, model rmse; metres).  The triple of set p is all NaN when p >= P, the selected
+ *      row (set_index[p][b][o], or o) is outside [0, set_rows[p]), any of its 12 values is not finite, or any of truth_pose[b][g*]'s is
+ *      not.  Else, with [R | t] the set's row, [Rg | tg] the truth's, m_i the model's rows:
+ *        Q = Rg^T R: Q[a][c] = (Rg[0][a]*R[0][c] + Rg[1][a]*R[1][c]) + Rg[2][a]*R[2][c];  w = (Q21-Q12, Q02-Q20, Q10-Q01),
+ *        s = sqrt((w0*w0 + w1*w1) + w2*w2), theta = atan2(s/2, (((Q00 + Q11) + Q22) - 1)/2) - step 4 of okp_track_objects -, rotation =
+ *        theta * (180/pi).  There is no symmetry allowance: a pose 120 degrees off on a nearly symmetric object reads 120.
+ *        p_i = ((R[r][0]*m_i0 + R[r][1]*m_i1) + R[r][2]*m_i2) + t[r] (okp_change_frame's association), q_i likewise from the truth,
+ *        e_i = (d0*d0 + d1*d1) + d2*d2 with d = p_i - q_i;  centre = sqrt(e_0);  rmse = sqrt(((e_0 + e_1) + ... + e_{S-1}) / S).
+ *   6. Per frame: truth_visible += the objects g < n_truth[b] whose row 0 is in view (all of them without cam); truth_detected += those
+ *      of them detected in step 3.
+ * State, in device memory, updated in place; all zeros is a valid empty log:
+ *   kp_err [cap_kp][2] fp64          err, err_xy of each key-point record (metres)
+ *   kp_id [cap_kp][4] int32          step, frame, detection, slot
+ *   pose_err [cap_pose][OKP_SCORE_MAX_POSES][3] fp64   rotation (degrees), centre, rmse (metres) per set
+ *   pose_id [cap_pose][4] int32      step, frame, detection, truth object
+ *   counts [16] int64 at the indices OKP_SCORE_*: calls (the `step` of the next call's ids), frames, detections, no_centre, unmatched,
+ *                                    out_of_view, points, missing, absent, truth_hidden, truth_visible, truth_detected, key-point
+ *                                    records in the log, pose records in the log, the overflow word; index 15 is spare and stays 0
+ * Records are appended in (b, o, s) order behind those of earlier calls, from the two cursors in counts.  A record that does not fit is
+ * dropped and so are all after it (the cursor stays at the capacity); every other counter still counts it, and bit OKP_SCORE_OVERFLOW of
+ * the overflow word is raised, for either log.
+ * Per-call outputs, written by every call: match [B][max_obj] int32 (g*, -1, -2, -3 as above, -4 for o >= n_obj[b]) and
+ * nearest [B][max_obj][S] int32 (j* wherever step 4 took one, else -1).
+ * Scratch, written by every call and of no meaning between calls: stage_f [B][max_obj][2 S + 3 OKP_SCORE_MAX_POSES] fp64 and
+ * stage_i [B][16 + 2 max_obj] int32 (the first kernel's fixed-position records and per-frame counters).
+ * Limits.  The table says what the reference's says: without a match_radius a false detection is scored against its nearest label; the
+ * rig path (cam NULL) has no view test.  Labels are taken as finite; the kernel cannot refuse a device table.
+ * Refused on the host before any launch (OKP_EINVAL, the message names the argument): B outside [1, 2^20], max_obj or G outside [1, 64], S
+ * outside [1, OKP_POSE_MAX_POINTS], cap_kp or cap_pose < 1, P outside [0, OKP_SCORE_MAX_POSES], an unknown camera model, size_x or size_y not
+ * positive (with cam), match_radius or max_range not positive (NaN included), a set without index whose rows differ from max_obj, a
+ * set with no rows, a null required pointer.
+ * ---------------------------------------------------------------------------------- */
+#define OKP_SCORE_MAX_POSES 4
+#define OKP_SCORE_OVERFLOW 1
+#define OKP_SCORE_CALLS 0
+#define OKP_SCORE_FRAMES 1
+#define OKP_SCORE_DETECTIONS 2
+#define OKP_SCORE_NO_CENTRE 3
+#define OKP_SCORE_UNMATCHED 4
+#define OKP_SCORE_OUT_OF_VIEW 5
+#define OKP_SCORE_POINTS 6
+#define OKP_SCORE_MISSING 7
+#define OKP_SCORE_ABSENT 8
+#define OKP_SCORE_TRUTH_HIDDEN 9
+#define OKP_SCORE_TRUTH_VISIBLE 10
+#define OKP_SCORE_TRUTH_DETECTED 11
+#define OKP_SCORE_KP_WRITTEN 12
+#define OKP_SCORE_POSE_WRITTEN 13
+#define OKP_SCORE_OVERFLOW_WORD 14
+int okp_score_objects(const double* tab_dev, const int32_t* n_obj_dev, const double* truth_dev, const int32_t* n_truth_dev, int32_t B,
+                      int32_t max_obj, int32_t G, int32_t S, const okp_camera* cam, double size_x, double size_y,
+                      const double* const* set_pose_dev /* HOST [P] */, const int32_t* const* set_index_dev /* HOST [P] */,
+                      const int32_t* set_rows /* HOST [P] */, int32_t P, const double* truth_pose_dev, const double* model_dev,
+                      double match_radius, double max_range, double* kp_err_dev, int32_t* kp_id_dev, int32_t cap_kp, double* pose_err_dev,
+                      int32_t* pose_id_dev, int32_t cap_pose, int64_t* counts_dev, int32_t* match_dev, int32_t* nearest_dev,
+                      double* stage_f_dev, int32_t* stage_i_dev, void* stream);
 
 #ifdef __cplusplus
 }

@@ -507,3 +507,19 @@ def keypoint_loss(p_heat, p_depth, p_centers, n_first, n_total, labels, n_obj, t
     _lib.check(_lib.lib().okp_keypoint_loss(ptrs[0], ptrs[1], ptrs[2], s, n_first, p_heat[0].shape[0], n_total, k, _ptr(labels), _ptr(n_obj) if labels is not None else None,
                                             max_obj, _int32s(type_count), _ptr(t_heat), _ptr(t_depth), _ptr(t_centers), depth_weight, center_weight,
                                             partial.data_ptr(), terms.data_ptr(), mask_count.data_ptr(), out.data_ptr(), stream), "okp_keypoint_loss")
+
+
+def score_objects(tab, n_obj, truth, n_truth, camera, size_x, size_y, set_pose, set_index, truth_pose, model, match_radius, max_range, kp_err, kp_id,
+                  pose_err, pose_id, counts, match, nearest, stage_f, stage_i, stream):
+    b, max_obj, s, _ = tab.shape
+    p = len(set_pose)
+    if len(set_index) != p:
+        raise OkpError(f"okp: score_objects takes one set_index entry (a tensor or None) per pose set: {len(set_index)} for {p}")
+    poses = (ctypes.c_void_p * p)(*[t.data_ptr() for t in set_pose]) if p else None
+    index = (ctypes.c_void_p * p)(*[_ptr(t) for t in set_index]) if p else None
+    rows = _int32s([t.shape[1] for t in set_pose]) if p else None
+    _lib.check(_lib.lib().okp_score_objects(tab.data_ptr(), n_obj.data_ptr(), truth.data_ptr(), n_truth.data_ptr(), b, max_obj, truth.shape[1], s,
+                                            _camera(camera) if len(camera) else None, size_x, size_y, poses, index, rows, p, _ptr(truth_pose), _ptr(model),
+                                            match_radius, max_range, kp_err.data_ptr(), kp_id.data_ptr(), kp_err.shape[0], pose_err.data_ptr(),
+                                            pose_id.data_ptr(), pose_err.shape[0], counts.data_ptr(), match.data_ptr(), nearest.data_ptr(),
+                                            stage_f.data_ptr(), stage_i.data_ptr(), stream), "okp_score_objects")

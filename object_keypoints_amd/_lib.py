@@ -163,6 +163,9 @@ SIGNATURES = [
     ("okp_render_targets", c_int, [c_void_p, c_void_p, c_int32, c_int32, POINTER(c_int32), c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     ("okp_keypoint_loss", c_int, [POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p), c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p,
                                   c_int32, POINTER(c_int32), c_void_p, c_void_p, c_void_p, c_double, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    ("okp_score_objects", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, POINTER(okp_camera), c_double, c_double,
+                                  POINTER(c_void_p), POINTER(c_void_p), POINTER(c_int32), c_int32, c_void_p, c_void_p, c_double, c_double, c_void_p, c_void_p,
+                                  c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
 ]
 
 _lib = None

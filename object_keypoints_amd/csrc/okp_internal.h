@@ -351,6 +351,30 @@ static __device__ __forceinline__ void okp_undistort_point(const okp_camera& cam
   else okp_fisheye_undistort_point(cam, x, y, xu, yu);
 }
 
+// camera.project of a camera-frame point (perception/utils/camera_utils.py:93-118 as restated by the product's host FisheyeCamera /
+// RadTanPinholeCamera.project) -> raw pixels.  The arithmetic of okp_project_labels, which okp_score_objects' view test shares; it divides
+// by Z whatever its sign, as the reference does: a caller that cares tests Z itself.
+static __device__ __forceinline__ void okp_project_point(const okp_camera& cam, double X, double Y, double Z, double& px, double& py) {
+  const double a = X / Z, b = Y / Z;
+  double u, v;
+  if (cam.model == OKP_CAM_RADTAN) {
+    const double k1 = cam.d[0], k2 = cam.d[1], p1 = cam.d[2], p2 = cam.d[3];
+    const double r2 = a * a + b * b;
+    const double radial = 1 + k1 * r2 + k2 * r2 * r2;
+    u = a * radial + 2 * p1 * a * b + p2 * (r2 + 2 * a * a);
+    v = b * radial + p1 * (r2 + 2 * b * b) + 2 * p2 * a * b;
+  } else {
+    const double r = sqrt(a * a + b * b);
+    const double theta = atan(r);
+    const double t2 = theta * theta;
+    const double theta_d = theta * (1 + cam.d[0] * t2 + cam.d[1] * t2 * t2 + cam.d[2] * t2 * t2 * t2 + cam.d[3] * t2 * t2 * t2 * t2);
+    const double sc = r > 1e-8 ? theta_d / r : 1.0;
+    u = a * sc; v = b * sc;
+  }
+  px = cam.fx * u + cam.cx;
+  py = cam.fy * v + cam.cy;
+}
+
 // The lifting of one pixel position to a camera-frame point, the arithmetic of DetectionToPoint.__call__ (perception/pipeline.py:164-171) that
 // okp_unproject_depth, okp_lift_peaks and okp_object_points share (one body: their results agree bit for bit): undistort (P = K) -> the
 // undistorted point rounded to fp32 (cv2 returns the dtype it was given, and the reference passes float32 peaks) -> round half to even, clip

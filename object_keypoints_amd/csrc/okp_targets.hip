@@ -244,25 +244,11 @@ __global__ void okp_project_labels_kernel(okp_camera cam, const double* __restri
     const double ti = -(r0 * T[3] + r1 * T[7] + r2 * T[11]);
     X[i] = (r0 * w[0] + r1 * w[1] + r2 * w[2]) + ti;
   }
-  const double a = X[0] / X[2], b = X[1] / X[2];
-  double u, v;
-  if (cam.model == OKP_CAM_RADTAN) {
-    const double k1 = cam.d[0], k2 = cam.d[1], p1 = cam.d[2], p2 = cam.d[3];
-    const double r2 = a * a + b * b;
-    const double radial = 1 + k1 * r2 + k2 * r2 * r2;
-    u = a * radial + 2 * p1 * a * b + p2 * (r2 + 2 * a * a);
-    v = b * radial + p1 * (r2 + 2 * b * b) + 2 * p2 * a * b;
-  } else {
-    const double r = sqrt(a * a + b * b);
-    const double theta = atan(r);
-    const double t2 = theta * theta;
-    const double theta_d = theta * (1 + cam.d[0] * t2 + cam.d[1] * t2 * t2 + cam.d[2] * t2 * t2 * t2 + cam.d[3] * t2 * t2 * t2 * t2);
-    const double sc = r > 1e-8 ? theta_d / r : 1.0;
-    u = a * sc; v = b * sc;
-  }
+  double px, py;
+  okp_project_point(cam, X[0], X[1], X[2], px, py);
   double* out = labels + (size_t)idx * 3;
-  out[0] = (cam.fx * u + cam.cx) * scale - crop_x;
-  out[1] = (cam.fy * v + cam.cy) * scale - crop_y;
+  out[0] = px * scale - crop_x;
+  out[1] = py * scale - crop_y;
   out[2] = X[2];
 }
 

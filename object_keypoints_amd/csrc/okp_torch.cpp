@@ -1180,6 +1180,67 @@ void keypoint_loss(at::TensorList p_heat, at::TensorList p_depth, at::TensorList
                              mask_count.data_ptr<int32_t>(), out.data_ptr<double>(), sp(stream)), "okp_keypoint_loss");
 }
 
+// ---- accuracy of labelled scenes (csrc/okp_score.hip) ------------------------------------------------------------------------------
+// camera: the 9 numbers of camera_of, or an empty list for no camera (a rig's table: no view test)
+void score_objects(const Tensor& tab, const Tensor& n_obj, const Tensor& truth, const Tensor& n_truth, at::ArrayRef<double> camera, double size_x, double size_y,
+                   at::TensorList set_pose, const c10::List<optional<Tensor>>& set_index, const optional<Tensor>& truth_pose, const optional<Tensor>& model,
+                   double match_radius, double max_range, const Tensor& kp_err, const Tensor& kp_id, const Tensor& pose_err, const Tensor& pose_id,
+                   const Tensor& counts, const Tensor& match, const Tensor& nearest, const Tensor& stage_f, const Tensor& stage_i, int64_t stream) {
+  check_dev(tab, at::kDouble, "tab"); check_dev(n_obj, at::kInt, "n_obj"); check_dev(truth, at::kDouble, "truth"); check_dev(n_truth, at::kInt, "n_truth");
+  TORCH_CHECK(tab.dim() == 4 && tab.size(3) == 4, "okp: tab is [B,max_obj,S,4]");
+  const int64_t B = tab.size(0), max_obj = tab.size(1), S = tab.size(2);
+  TORCH_CHECK(truth.dim() == 4 && truth.size(0) == B && truth.size(2) == S && truth.size(3) == 4, "okp: truth is [B,G,S,4]");
+  const int64_t G = truth.size(1);
+  TORCH_CHECK(n_obj.numel() == B && n_truth.numel() == B, "okp: n_obj and n_truth are [B]");
+  check_dev(kp_err, at::kDouble, "kp_err"); check_dev(kp_id, at::kInt, "kp_id"); check_dev(pose_err, at::kDouble, "pose_err"); check_dev(pose_id, at::kInt, "pose_id");
+  check_dev(counts, at::kLong, "counts"); check_dev(match, at::kInt, "match"); check_dev(nearest, at::kInt, "nearest");
+  check_dev(stage_f, at::kDouble, "stage_f"); check_dev(stage_i, at::kInt, "stage_i");
+  TORCH_CHECK(kp_err.dim() == 2 && kp_err.size(1) == 2 && kp_id.dim() == 2 && kp_id.size(0) == kp_err.size(0) && kp_id.size(1) == 4,
+              "okp: the key-point log is kp_err [cap_kp,2] and kp_id [cap_kp,4]");
+  TORCH_CHECK(pose_err.dim() == 3 && pose_err.size(1) == OKP_SCORE_MAX_POSES && pose_err.size(2) == 3 && pose_id.dim() == 2 && pose_id.size(0) == pose_err.size(0) &&
+              pose_id.size(1) == 4, "okp: the pose log is pose_err [cap_pose,4,3] and pose_id [cap_pose,4]");
+  TORCH_CHECK(counts.numel() == 16, "okp: counts is [16] int64");
+  TORCH_CHECK(match.numel() == B * max_obj && nearest.numel() == B * max_obj * S, "okp: match is [B,max_obj] and nearest [B,max_obj,S]");
+  TORCH_CHECK(stage_f.numel() == B * max_obj * (2 * S + 3 * OKP_SCORE_MAX_POSES) && stage_i.numel() == B * (16 + 2 * max_obj),
+              "okp: the scratch is stage_f [B,max_obj,2 S + 12] and stage_i [B,16 + 2 max_obj]");
+  const int64_t P = (int64_t)set_pose.size();
+  TORCH_CHECK((int64_t)set_index.size() == P, "okp: score_objects takes one set_index entry (a tensor or None) per pose set");
+  TORCH_CHECK(P <= OKP_SCORE_MAX_POSES, "okp: at most ", OKP_SCORE_MAX_POSES, " pose sets");
+  std::vector<const double*> poses;
+  std::vector<const int32_t*> index;
+  std::vector<int32_t> rows;
+  for (int64_t p = 0; p < P; ++p) {
+    check_dev(set_pose[p], at::kDouble, "set_pose");
+    TORCH_CHECK(set_pose[p].dim() == 3 && set_pose[p].size(0) == B && set_pose[p].size(2) == 12, "okp: set_pose[", p, "] is [B,rows,12]");
+    poses.push_back(set_pose[p].data_ptr<double>());
+    rows.push_back((int32_t)set_pose[p].size(1));
+    const optional<Tensor> ix = set_index.get(p);
+    if (ix.has_value()) {
+      check_dev(*ix, at::kInt, "set_index");
+      TORCH_CHECK(ix->numel() == B * max_obj, "okp: set_index[", p, "] is [B,max_obj]");
+      index.push_back(ix->data_ptr<int32_t>());
+    } else {
+      index.push_back(nullptr);
+    }
+  }
+  const double* tp = nullptr; const double* md = nullptr;
+  if (P > 0) {
+    TORCH_CHECK(truth_pose.has_value() && model.has_value(), "okp: pose sets take truth_pose [B,G,12] and model [S,3]");
+    check_dev(*truth_pose, at::kDouble, "truth_pose"); check_dev(*model, at::kDouble, "model");
+    TORCH_CHECK(truth_pose->numel() == B * G * 12 && model->numel() == S * 3, "okp: pose sets take truth_pose [B,G,12] and model [S,3]");
+    tp = truth_pose->data_ptr<double>(); md = model->data_ptr<double>();
+  }
+  okp_camera cam{};
+  const bool has_cam = camera.size() != 0;
+  if (has_cam) cam = camera_of(camera);
+  check_rc(okp_score_objects(tab.data_ptr<double>(), n_obj.data_ptr<int32_t>(), truth.data_ptr<double>(), n_truth.data_ptr<int32_t>(), (int32_t)B, (int32_t)max_obj,
+                             (int32_t)G, (int32_t)S, has_cam ? &cam : nullptr, size_x, size_y, P ? poses.data() : nullptr, P ? index.data() : nullptr,
+                             P ? rows.data() : nullptr, (int32_t)P, tp, md, match_radius, max_range, kp_err.data_ptr<double>(), kp_id.data_ptr<int32_t>(),
+                             (int32_t)kp_err.size(0), pose_err.data_ptr<double>(), pose_id.data_ptr<int32_t>(), (int32_t)pose_err.size(0),
+                             counts.data_ptr<int64_t>(), match.data_ptr<int32_t>(), nearest.data_ptr<int32_t>(), stage_f.data_ptr<double>(),
+                             stage_i.data_ptr<int32_t>(), sp(stream)), "okp_score_objects");
+}
+
 }  // namespace
 
 TORCH_LIBRARY(okp, m) {
@@ -1289,4 +1350,7 @@ TORCH_LIBRARY(okp, m) {
   m.def("keypoint_loss(Tensor[] p_heat, Tensor[] p_depth, Tensor[] p_centers, int n_first, int n_total, Tensor? labels, Tensor? n_obj, int[] type_count, "
         "Tensor? t_heat, Tensor? t_depth, Tensor? t_centers, float depth_weight, float center_weight, Tensor(a!) partial, Tensor(b!) terms, Tensor(c!) mask_count, "
         "Tensor(d!) out, int stream) -> ()", keypoint_loss);
+  m.def("score_objects(Tensor tab, Tensor n_obj, Tensor truth, Tensor n_truth, float[] camera, float size_x, float size_y, Tensor[] set_pose, Tensor?[] set_index, "
+        "Tensor? truth_pose, Tensor? model, float match_radius, float max_range, Tensor(a!) kp_err, Tensor(b!) kp_id, Tensor(c!) pose_err, Tensor(d!) pose_id, "
+        "Tensor(e!) counts, Tensor(f!) match, Tensor(g!) nearest, Tensor(h!) stage_f, Tensor(i!) stage_i, int stream) -> ()", score_objects);
 }

@@ -2332,3 +2332,174 @@ def keypoint_loss(p_heatmaps, p_depth, p_centers, type_count, labels=None, n_obj
     COUNTERS["launches"] += 2 if first + n == total else 1
     return {"loss": out[0], "heat": out[1:1 + s], "depth": out[1 + s:1 + 2 * s], "center": out[1 + 2 * s:], "terms": terms, "mask_count": mask_count,
             "partial": partial, "out": out}
+
+
+# ---- key-point and pose accuracy of labelled scenes (okp_score_objects, csrc/okp_score.hip; the specification is include/okp.h) --------------
+SCORE_MAX_POSES = 4          # include/okp.h OKP_SCORE_MAX_POSES
+SCORE_MAX_OBJECTS = 64       # detections and labelled objects per frame
+SCORE_OVERFLOW = 1           # bit of counts[SCORE_OVERFLOW_WORD]: a record did not fit one of the logs and was dropped
+(SCORE_CALLS, SCORE_FRAMES, SCORE_DETECTIONS, SCORE_NO_CENTRE, SCORE_UNMATCHED, SCORE_OUT_OF_VIEW, SCORE_POINTS, SCORE_MISSING, SCORE_ABSENT,
+ SCORE_TRUTH_HIDDEN, SCORE_TRUTH_VISIBLE, SCORE_TRUTH_DETECTED, SCORE_KP_WRITTEN, SCORE_POSE_WRITTEN, SCORE_OVERFLOW_WORD) = range(15)
+SCORE_COUNTERS = ("calls", "frames", "detections", "no_centre", "unmatched", "out_of_view", "points", "missing", "absent", "truth_hidden",
+                  "truth_visible", "truth_detected", "kp_written", "pose_written", "overflow")      # the name of counts[i]
+
+
+class ScoreConfig:
+    """score_objects' two host scalars: match_radius (metres; a detection farther than this from every labelled centre in x/y is unmatched;
+    infinity, the default, is the reference's behaviour: no gate) and max_range (a lifted coordinate at or beyond it counts as missing; 2.0 is
+    the reference's value).  Both positive; an OkpError names the field."""
+
+    def __init__(self, match_radius=float("inf"), max_range=2.0):
+        for name, v in (("match_radius", match_radius), ("max_range", max_range)):
+            try:
+                v = float(v)
+            except (TypeError, ValueError):
+                raise OkpError(f"ScoreConfig: {name} = {v!r} is not a number") from None
+            if not v > 0.0:
+                raise OkpError(f"ScoreConfig: {name} = {v!r} must be positive")
+            setattr(self, name, v)
+
+    def __repr__(self):
+        return f"ScoreConfig(match_radius={self.match_radius}, max_range={self.max_range})"
+
+
+def score_log(capacity_points, capacity_poses, device):
+    """An empty accuracy log on `device`, all zeros: {"kp_err" [capacity_points,2] float64 (err, err_xy in metres), "kp_id" [capacity_points,4]
+    int32 (step, frame, detection, slot), "pose_err" [capacity_poses,4,3] float64 (rotation in degrees, centre error, model rmse per pose set),
+    "pose_id" [capacity_poses,4] int32 (step, frame, detection, truth object), "counts" [16] int64 (SCORE_COUNTERS)}.  score_objects() appends
+    to it in place.  The five are views of one allocation, "buffer" (uint8), in that order: one copy of it brings the whole log to the host
+    (score_log_host), and zeroing it empties the log."""
+    cap_kp, cap_pose = int(capacity_points), int(capacity_poses)
+    if cap_kp < 1 or cap_pose < 1 or cap_kp >= 2 ** 31 or cap_pose >= 2 ** 31:
+        raise OkpError(f"score_log: capacity_points = {capacity_points}, capacity_poses = {capacity_poses}: at least one record each")
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise OkpError("score_log: the log lives in device memory: the HIP path has no CPU fallback")
+    layout = _score_layout(cap_kp, cap_pose)
+    buffer = torch.zeros((layout[-1][2],), dtype=torch.uint8, device=device)
+    log = {name: buffer[start:end].view(dtype).view(shape) for name, start, end, dtype, shape in layout[:-1]}
+    log["buffer"] = buffer
+    return log
+
+
+def _score_layout(cap_kp, cap_pose):
+    """[(name, first byte, end byte, dtype, shape)] of a log's tensors inside its buffer (every start a multiple of 8), then ("buffer", 0, bytes)."""
+    out, at = [], 0
+    for name, dtype, shape in (("kp_err", torch.float64, (cap_kp, 2)), ("pose_err", torch.float64, (cap_pose, SCORE_MAX_POSES, 3)), ("counts", torch.int64, (16,)),
+                               ("kp_id", torch.int32, (cap_kp, 4)), ("pose_id", torch.int32, (cap_pose, 4))):
+        size = int(np.prod(shape)) * (4 if dtype == torch.int32 else 8)
+        out.append((name, at, at + size, dtype, shape))
+        at += size
+    return out + [("buffer", 0, at)]
+
+
+def score_log_host(log):
+    """The log on the host in ONE device -> host copy: {"kp_err", "kp_id", "pose_err", "pose_id", "counts"} as NumPy arrays."""
+    try:
+        buffer, cap_kp, cap_pose = log["buffer"], int(log["kp_err"].shape[0]), int(log["pose_err"].shape[0])
+    except (TypeError, KeyError):
+        raise OkpError("log must be the dict of ops.score_log") from None
+    host = buffer.cpu().numpy()
+    np_types = {torch.float64: np.float64, torch.int64: np.int64, torch.int32: np.int32}
+    return {name: host[start:end].view(np_types[dtype]).reshape(shape) for name, start, end, dtype, shape in _score_layout(cap_kp, cap_pose)[:-1]}
+
+
+def score_objects(tab, n_obj, truth, n_truth, log, config, cam=None, size=None, pose_sets=(), truth_pose=None, model=None):
+    """One step's object table, and up to SCORE_MAX_POSES sets of poses, against labelled truth (okp_score_objects; matching, the view test,
+    the slots, the pose errors and the log's order are specified in include/okp.h).
+        tab [B,max_obj,S,4] float64, n_obj int32 [B]: object_points / rig_object_points' table; truth [B,G,S,4] (or [...,3]) float64: the
+        labelled key points in the table's frame, row 0 the centre; n_truth int32 [B]
+        log: score_log(...), appended to in place; config: a ScoreConfig
+        cam: an okp_camera with size = the camera's image_size (the bounds of the projected u and v) for the reference's view test, or None
+        (a rig's table: everything counts as in view)
+        pose_sets: up to four entries `pose` or `(pose, index)`: pose [B,rows,12] float64; index int32 [B,max_obj], the row of detection o (a
+        tracker's track_of), or None: row o, and rows == max_obj.  With sets come truth_pose [B,G,12] (the labels' poses in the table's frame)
+        and model [S,3], both float64
+    -> {"match" [B,max_obj] int32 (the labelled object of each detection; -1 no centre, -2 unmatched, -3 out of view, -4 not a detection),
+        "nearest" [B,max_obj,S] int32 (the truth row each slot was scored against, or -1)}: views of scratch that the log keeps and the next
+    call with these shapes overwrites.  Two launches, no host sync, no allocation after the first call with these shapes."""
+    if not isinstance(config, ScoreConfig):
+        raise OkpError("config must be an ops.ScoreConfig")
+    for name, t in (("tab", tab), ("n_obj", n_obj), ("truth", truth), ("n_truth", n_truth)):
+        require_cuda(t, name)
+    if tab.dtype != torch.float64 or tab.dim() != 4 or tab.shape[3] != 4:
+        raise OkpError("tab must be float64 [B,max_obj,S,4] (object_points / rig_object_points)")
+    b, max_obj, s = (int(v) for v in tab.shape[:3])
+    dev = tab.device
+    if b < 1 or not 1 <= max_obj <= SCORE_MAX_OBJECTS or not 1 <= s <= POSE_MAX_POINTS:
+        raise OkpError(f"tab [{b},{max_obj},{s},4]: at least one frame, at most {SCORE_MAX_OBJECTS} objects per frame and {POSE_MAX_POINTS} rows per object")
+    if truth.dtype != torch.float64 or truth.dim() != 4 or truth.shape[0] != b or truth.shape[2] != s or truth.shape[3] not in (3, 4) or truth.device != dev:
+        raise OkpError(f"truth must be float64 [{b},G,{s},4] (or [...,3]) on the table's device: the labelled key points in the table's frame")
+    g = int(truth.shape[1])
+    if not 1 <= g <= SCORE_MAX_OBJECTS:
+        raise OkpError(f"truth holds G = {g} labelled objects per frame: 1 to {SCORE_MAX_OBJECTS}")
+    if truth.shape[3] == 3:
+        truth = torch.nn.functional.pad(truth, (0, 1))
+    for name, t in (("n_obj", n_obj), ("n_truth", n_truth)):
+        if t.dtype != torch.int32 or t.numel() != b or t.device != dev:
+            raise OkpError(f"{name} must be int32 [{b}] on the table's device")
+    try:
+        state = [log[k] for k in ("kp_err", "kp_id", "pose_err", "pose_id", "counts")]
+    except (TypeError, KeyError):
+        raise OkpError("log must be the dict of ops.score_log") from None
+    cap_kp, cap_pose = int(state[0].shape[0]), int(state[2].shape[0])
+    for name, x, dtype, shape in (("kp_err", state[0], torch.float64, (cap_kp, 2)), ("kp_id", state[1], torch.int32, (cap_kp, 4)),
+                                  ("pose_err", state[2], torch.float64, (cap_pose, SCORE_MAX_POSES, 3)), ("pose_id", state[3], torch.int32, (cap_pose, 4)),
+                                  ("counts", state[4], torch.int64, (16,))):
+        require_cuda(x, f"log[{name!r}]")
+        if x.dtype != dtype or tuple(x.shape) != shape or x.device != dev or not x.is_contiguous() or x.numel() == 0:
+            raise OkpError(f"log[{name!r}] must be a contiguous {dtype} tensor {list(shape)} on the table's device: score_log(...)")
+    if cam is None:
+        if size is not None:
+            raise OkpError("size goes with cam: without a camera there is no view test")
+        camera, size_x, size_y = [], 0.0, 0.0
+    else:
+        if not isinstance(cam, _lib.okp_camera):
+            raise OkpError(f"cam must be an okp_camera (make_camera) or None, not {type(cam).__name__}")
+        if cam.model not in (_lib.CAM_EQUIDISTANT, _lib.CAM_RADTAN):
+            raise OkpError(f"cam: unknown camera model {cam.model}")
+        try:
+            size_x, size_y = (float(v) for v in size)
+        except (TypeError, ValueError):
+            raise OkpError("size must be the camera's image_size, two numbers") from None
+        if not (size_x > 0.0 and size_y > 0.0):
+            raise OkpError(f"size = {size!r} must be positive")
+        camera = _cam_list(cam)
+    poses, index = [], []
+    if len(pose_sets) > SCORE_MAX_POSES:
+        raise OkpError(f"pose_sets has {len(pose_sets)} sets: at most {SCORE_MAX_POSES}")
+    for p, entry in enumerate(pose_sets):
+        pose, ix = entry if isinstance(entry, (tuple, list)) else (entry, None)
+        require_cuda(pose, f"pose_sets[{p}]")
+        if pose.dtype != torch.float64 or pose.dim() != 3 or pose.shape[0] != b or pose.shape[2] != 12 or pose.shape[1] < 1 or pose.device != dev:
+            raise OkpError(f"pose_sets[{p}] must be float64 [{b},rows,12] on the table's device")
+        if ix is None:
+            if pose.shape[1] != max_obj:
+                raise OkpError(f"pose_sets[{p}] has {pose.shape[1]} rows per frame and no index: row o is detection o's, so max_obj = {max_obj} rows")
+        else:
+            require_cuda(ix, f"pose_sets[{p}]'s index")
+            if ix.dtype != torch.int32 or tuple(ix.shape) != (b, max_obj) or ix.device != dev:
+                raise OkpError(f"pose_sets[{p}]'s index must be int32 [{b},{max_obj}] on the table's device (a tracker's track_of)")
+            ix = ix.contiguous()
+        poses.append(pose.contiguous())
+        index.append(ix)
+    if poses:
+        for name, t, shape in (("truth_pose", truth_pose, (b, g, 12)), ("model", model, (s, 3))):
+            require_cuda(t, name)
+            if t.dtype != torch.float64 or tuple(t.shape) != shape or t.device != dev:
+                raise OkpError(f"{name} must be float64 {list(shape)} on the table's device")
+        truth_pose, model = truth_pose.contiguous(), model.contiguous()
+    else:
+        truth_pose = model = None
+    work = log.setdefault("_work", {})
+    key = (b, max_obj, s)
+    if key not in work:
+        ints = torch.empty((b * max_obj + b * max_obj * s + b * (16 + 2 * max_obj),), dtype=torch.int32, device=dev)
+        work[key] = (ints[:b * max_obj].view(b, max_obj), ints[b * max_obj:b * max_obj * (1 + s)].view(b, max_obj, s), ints[b * max_obj * (1 + s):],
+                     torch.empty((b, max_obj, 2 * s + 3 * SCORE_MAX_POSES), dtype=torch.float64, device=dev))
+    match, nearest, stage_i, stage_f = work[key]
+    _dispatch(_ops().score_objects, tab.contiguous(), n_obj.reshape(b).contiguous(), truth.contiguous(), n_truth.reshape(b).contiguous(), camera, size_x, size_y,
+              poses, index, truth_pose, model, config.match_radius, config.max_range, state[0], state[1], state[2], state[3], state[4], match, nearest,
+              stage_f, stage_i, stream_int())
+    COUNTERS["launches"] += 2
+    return {"match": match, "nearest": nearest}

@@ -34,6 +34,10 @@ class SceneTargets:
         self.device = device
         self._world_dev = None
 
+    def truth_points(self):
+        """world_points as [n_objects, nk, 3], row 0 of every object its centre: what perception.evaluation.DeviceResults takes."""
+        return self.world_points.reshape(self.n_objects, self.n_keypoints, 3).copy()
+
     def labels(self, T_WC):
         """Camera poses T_WC [N,4,4] (NumPy or tensor) -> {"points": [N, n_objects * nk, 3] fp64, "n_obj": [N] int32} on the device."""
         dev = torch.device(self.device if self.device is not None else "cuda")
