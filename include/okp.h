@@ -56,6 +56,8 @@ extern "C" {
                                     okp_refine_pose_views_weighted, okp_rig_bearings_weighted, okp_window_push_weighted,
                                     okp_window_push_views_weighted, okp_refine_pose_views_weighted_wide (those refinements weighted by the
                                     peaks' confidences);
+                                    okp_window_push_timed, okp_window_push_views_timed, okp_refine_motion_views (the window refinement of a
+                                    moving object: a ring that knows how old its columns are, a pose and a linear velocity);
                                     okp_score_objects, OKP_SCORE_* (key-point and pose accuracy of labelled scenes, tabulated on the device) */
 
 /* OKP_F16: IEEE half activations / weights, fp32 accumulate (BASELINE configs[4]).
@@ -1262,6 +1264,93 @@ int okp_window_push_views_weighted(const double* obs_dev, const double* prior_de
                                    int32_t B, int32_t max_obj, int32_t S, int32_t T, int32_t W, int32_t V, int32_t min_views,
                                    double max_speed, double* win_obs_dev, double* win_prior_dev /* [B][T][S][W*V] */,
                                    double* win_views_dev, int32_t* win_i_dev, int32_t* n_views_dev, double* start_dev, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * The window refinement of a MOVING object: a constant-velocity model (csrc/okp_window.hip, csrc/okp_window_views.hip,
+ * csrc/okp_refine_motion.hip).  The windows above assume a static object: when the tracker follows a part on a conveyor or a tool in a hand
+ * they either empty the ring (max_speed) or average the bearings of an object that was somewhere else.  Here the ring knows how old its
+ * columns are and the refinement solves for the pose at "now" and a linear velocity, nine unknowns.  Opt-in: entry points of their own next
+ * to the plain ones, which keep their signatures, their kernel instances and their bits.  There is no reference implementation: the
+ * specification is this comment (tests/refine_motion_spec.py restates it in NumPy).
+ *
+ * okp_window_push_timed: okp_window_push - the same kernel, a second instance - with one more state tensor next to win_obs,
+ *   win_age [B][T][W] int32       the age of ring column w in TICKS; the empty state is zeros
+ * and one more output, start_velocity [B][T][3] fp64.  Per slot, inside okp_window_push's order of steps:
+ *   - wherever that contract says "empty the ring", every age of the slot also becomes 0;
+ *   - after step 3, for every slot with id != 0, whether or not a push follows, every age becomes min(age + 1, 2^30);
+ *   - a push (step 4) then sets the age of the column it writes to 0.
+ *   So a column pushed this tick has age 0, after a coasting tick - the track was not measured, nothing is pushed - the newest column has
+ *   age 1, and the ages of a free slot are 0.  Column index is not age; win_age is.
+ *   start_velocity[b][i] = track_f[b][i][3..5] copied bit for bit where start[b][i] is the track pose (filled >= min_views), NaN where start
+ *   is NaN.  Written by every call.
+ *   Everything else is okp_window_push's, word for word: win_obs, win_views, win_i, n_views, start, the refusals; this instance leaves the
+ *   same bits as the plain one in every tensor they share.  Also refused: a null win_age or start_velocity.
+ * okp_window_push_views_timed: okp_window_push_views in the same way, with win_age [B][T][W*V] int32 - the V entries c V .. c V + V - 1 of
+ *   ring column c are equal - and start_velocity [B][T][3].
+ * Both agree with tests/refine_motion_spec.py BIT FOR BIT.
+ *
+ * okp_refine_motion_views: one launch, one wave per object, a sibling of okp_refine_pose_views_each's kernel with the same lanes; fp64, no
+ * atomics, no host wait, no scratch memory, capturable; the same bits on every run.
+ * Inputs, in device memory: obs [B][max_obj][S][V][2] fp64 and views [B][max_obj][V][14] fp64, ALWAYS one table per object, as
+ *   okp_refine_pose_views_each takes them; age [B][max_obj][V] int32, the age of view v in ticks; pose [B][max_obj][12] fp64 (the pose at
+ *   age 0) and velocity [B][max_obj][3] fp64 (table's frame, metres per second), the start; assignment, n_obj and model as there.
+ * Host arguments: sigma_px, dt (seconds per tick, positive and finite), horizon (int32 in [1, 2^30] ticks), iters, damping, B, max_obj, S,
+ *   V in [1, OKP_REFINE_MAX_VIEWS].
+ * Per object o < min(n_obj[b], max_obj).  The observations are the filled entries (s, v) of the slots with a model row, as in
+ *   okp_refine_pose_views, whose age[v] lies in [0, horizon]; n_obs counts them.  An entry of an older view, or of one with a negative age,
+ *   contributes nothing, exactly like an empty entry; q_z <= 0 counts for observations only.
+ *   Model.  The unknowns are (w, d, nu): the pose [R | t] at age 0 and the linear velocity nu in the table's frame.  With
+ *     tau_v = -((double)age[v] * dt)   the point of model row a in view v is   X = R m_a + (t + tau_v * nu);
+ *     q, e_u, e_v, a and b = R_v^T a are those of okp_refine_pose_views at that X, J = sum over the observations of (e_u^2 + e_v^2).  A
+ *     Jacobian row is (p x b, b, tau_v * b) with p = R m_a.  The update is R <- C(w) R, t <- t + d, nu <- nu + x[6..8] for the solution x.
+ *   Solve.  (H + mu diag H) x = -g by Cholesky, lower triangle, column by column, with okp_refine_pose's pivot rule at 9 x 9: a pivot that is
+ *     <= 1e-12 x its diagonal entry of H, or not finite, gives OKP_REFINE_SINGULAR.  Exactly `iters` steps, then one final evaluation.
+ *   One age.  When all observations share ONE age - one filled column, or a horizon that leaves one: a ring of ages 1, 2, 3 after a
+ *     coasting tick under horizon = 1 - the bearings say nothing about a velocity.  With age 0 the velocity block of H is exactly zero; with
+ *     a non-zero age H is rank-deficient only up to rounding and, under a damping mu > 0, its seventh pivot is of the order of mu x H_cc,
+ *     which the pivot rule does not see.  So this is decided on the ages, whatever the damping: fewer than two DISTINCT ages among the
+ *     observations give OKP_REFINE_SINGULAR before the first iterate.  min_views >= 2 on the ring does not ensure two ages inside a horizon.
+ *   Status, the same four words in the same order of evaluation:
+ *     OKP_REFINE_SKIPPED   one of the 12 pose values or the 3 velocity values is not finite; one of the object's S x V entries - whatever
+ *                          its view's age - has exactly one NaN half, or an infinite half; or fewer than 3 slots have a model row and an
+ *                          observation inside the horizon
+ *     OKP_REFINE_SINGULAR  then, still before the first iterate: the observations have fewer than two distinct ages (above)
+ *     OKP_REFINE_BEHIND, OKP_REFINE_SINGULAR (a pivot)    as in okp_refine_pose_views, iterate by iterate
+ *     OKP_REFINE_REJECTED  J_final not finite, or J_final > J_initial + 1e-12 x n_obs
+ *   Outputs, all written by every call:
+ *     pose_out [B][max_obj][12], velocity_out [B][max_obj][3]   the final iterate; for ANY non-zero status the inputs copied bit for bit
+ *     fit [B][max_obj][2]                 the reprojection rmse in map pixels before and after; NaN for a non-zero status
+ *     n_obs [B][max_obj] int32            the observations, for every live object whatever its status
+ *     information [B][max_obj][81] fp64   the undamped H at the final iterate, row-major 9 x 9, exactly symmetric, parameter order
+ *                                         (w, d, nu); NaN for a non-zero status
+ *     status [B][max_obj] int32
+ *   Objects from n_obj[b] on: NaN pose_out, velocity_out, fit and information, n_obs 0, status OKP_REFINE_SKIPPED.
+ *   The order of the sums is not part of the contract: a lane (one view, so one tau) adds the 6-unknown sums over its slots in ascending
+ *   order and forms the velocity's rows as tau and tau^2 times them, then one butterfly adds the lanes
+ *   (tests/test_gpu_refine_motion.py: 1e-9 on R and t, and on nu x (the largest age x dt), against a NumPy evaluation).
+ * Limits.  The velocity is LINEAR only: the orientation is taken as constant over the window, which is the tracker's own model, and an
+ * object that rotates biases the result.  Constant velocity is assumed over `horizon` ticks and no further.  No Huber loss and no
+ * confidence weights yet.  At most OKP_REFINE_MAX_VIEWS views: a rig of P pairs has 2 P x W of them.  On a STATIC object the centre is
+ * worse than the static window's - the price of three more unknowns.  The camera poses are taken as exact.
+ * Refused on the host before any launch (OKP_EINVAL, the message names the argument): everything okp_refine_pose_views_each refuses, dt
+ * not positive and finite, horizon outside [1, 2^30], a null age, velocity or velocity_out, velocity_out overlapping velocity.
+ * ---------------------------------------------------------------------------------- */
+int okp_window_push_timed(const double* tab_dev, const int32_t* assignment_dev, const int32_t* status_dev, const int32_t* meas_of_dev,
+                          const int32_t* track_i_dev, const double* track_f_dev, const double* track_pose_dev, const double* T_WC_dev,
+                          const okp_camera* cam, int32_t B, int32_t max_obj, int32_t S, int32_t T, int32_t W, int32_t min_views, double max_speed,
+                          double* win_obs_dev, int32_t* win_age_dev /* [B][T][W] */, double* win_views_dev, int32_t* win_i_dev,
+                          int32_t* n_views_dev, double* start_dev, double* start_velocity_dev /* [B][T][3] */, void* stream);
+int okp_window_push_views_timed(const double* obs_dev, const int32_t* assignment_dev, const int32_t* status_dev, const int32_t* meas_of_dev,
+                                const int32_t* track_i_dev, const double* track_f_dev, const double* track_pose_dev, const double* T_WB_dev,
+                                const double* views_dev, int32_t B, int32_t max_obj, int32_t S, int32_t T, int32_t W, int32_t V,
+                                int32_t min_views, double max_speed, double* win_obs_dev, int32_t* win_age_dev /* [B][T][W*V] */,
+                                double* win_views_dev, int32_t* win_i_dev, int32_t* n_views_dev, double* start_dev,
+                                double* start_velocity_dev /* [B][T][3] */, void* stream);
+int okp_refine_motion_views(const double* obs_dev, const double* views_dev /* [B][max_obj][V][14] */, const int32_t* age_dev /* [B][max_obj][V] */,
+                            const double* pose_dev, const double* velocity_dev /* [B][max_obj][3] */, const int32_t* assignment_dev,
+                            const int32_t* n_obj_dev, const double* model_dev, double sigma_px, double dt, int32_t horizon, int32_t iters,
+                            double damping, int32_t B, int32_t max_obj, int32_t S, int32_t V, double* pose_out_dev, double* velocity_out_dev,
+                            double* fit_dev, int32_t* n_obs_dev, double* information_dev /* [B][max_obj][81] */, int32_t* status_dev, void* stream);
 
 /* Undistort only (FisheyeCamera.undistort, camera_utils.py:75-81 / RadTanPinholeCamera.undistort, :57-62, by cam->model):
  * xy [m][2] fp32 -> out [m][2] fp64.  okp_fisheye_undistort is the same entry point under its round-1 name. */

@@ -487,6 +487,34 @@ def window_push_views_weighted(obs, prior, assignment, status, meas_of, track_i,
                "okp_window_push_views_weighted")
 
 
+# ---- the window refinement of a moving object (csrc/okp_refine_motion.hip): win_age [B,T,W] / [B,T,W*V] int32, a pose and a velocity -------------------
+def window_push_timed(camera, tab, assignment, status, meas_of, track_i, track_f, track_pose, T_WC, min_views, max_speed, win_obs, win_age, win_views, win_i, n_views,
+                      start, start_velocity, stream):
+    b, max_obj, s, _ = tab.shape
+    _lib.check(_lib.lib().okp_window_push_timed(tab.data_ptr(), assignment.data_ptr(), status.data_ptr(), meas_of.data_ptr(), track_i.data_ptr(), track_f.data_ptr(),
+                                                track_pose.data_ptr(), T_WC.data_ptr(), _camera(camera), b, max_obj, s, win_obs.shape[1], win_obs.shape[3], min_views,
+                                                max_speed, win_obs.data_ptr(), win_age.data_ptr(), win_views.data_ptr(), win_i.data_ptr(), n_views.data_ptr(),
+                                                start.data_ptr(), start_velocity.data_ptr(), stream), "okp_window_push_timed")
+
+
+def window_push_views_timed(obs, assignment, status, meas_of, track_i, track_f, track_pose, T_WB, views, ticks, min_views, max_speed, win_obs, win_age, win_views,
+                            win_i, n_views, start, start_velocity, stream):
+    b, max_obj, s, v, _ = obs.shape
+    _lib.check(_lib.lib().okp_window_push_views_timed(obs.data_ptr(), assignment.data_ptr(), status.data_ptr(), meas_of.data_ptr(), track_i.data_ptr(),
+                                                      track_f.data_ptr(), track_pose.data_ptr(), T_WB.data_ptr(), views.data_ptr(), b, max_obj, s, win_obs.shape[1],
+                                                      ticks, v, min_views, max_speed, win_obs.data_ptr(), win_age.data_ptr(), win_views.data_ptr(), win_i.data_ptr(),
+                                                      n_views.data_ptr(), start.data_ptr(), start_velocity.data_ptr(), stream), "okp_window_push_views_timed")
+
+
+def refine_motion_views(obs, views, age, pose, velocity, assignment, n_obj, model, sigma_px, dt, horizon, iters, damping, pose_out, velocity_out, fit, n_obs,
+                        information, status, stream):
+    b, max_obj, s, v, _ = obs.shape
+    _lib.check(_lib.lib().okp_refine_motion_views(obs.data_ptr(), views.data_ptr(), age.data_ptr(), pose.data_ptr(), velocity.data_ptr(), assignment.data_ptr(),
+                                                  n_obj.data_ptr(), model.data_ptr(), sigma_px, dt, horizon, iters, damping, b, max_obj, s, v, pose_out.data_ptr(),
+                                                  velocity_out.data_ptr(), fit.data_ptr(), n_obs.data_ptr(), information.data_ptr(), status.data_ptr(), stream),
+               "okp_refine_motion_views")
+
+
 # ---- scoring labelled scenes -----------------------------------------------------------------------------------------------------------------
 def project_labels(camera, world_points, T_WC, scale, crop_x, crop_y, labels, stream):
     _lib.check(_lib.lib().okp_project_labels(_camera(camera), world_points.data_ptr(), world_points.shape[0], T_WC.data_ptr(), T_WC.shape[0], scale, crop_x, crop_y,

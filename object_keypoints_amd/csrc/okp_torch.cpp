@@ -1078,6 +1078,92 @@ void window_push_views_weighted(const Tensor& obs, const Tensor& prior, const Te
            "okp_window_push_views_weighted");
 }
 
+// window_push with the state win_age [B,T,W] int32 and the output start_velocity [B,T,3] (the window of a moving object)
+void window_push_timed(at::ArrayRef<double> camera, const Tensor& tab, const Tensor& assignment, const Tensor& status, const Tensor& meas_of, const Tensor& track_i,
+                       const Tensor& track_f, const Tensor& track_pose, const Tensor& T_WC, int64_t min_views, double max_speed, const Tensor& win_obs,
+                       const Tensor& win_age, const Tensor& win_views, const Tensor& win_i, const Tensor& n_views, const Tensor& start, const Tensor& start_velocity,
+                       int64_t stream) {
+  check_dev(tab, at::kDouble, "tab"); check_dev(assignment, at::kInt, "assignment"); check_dev(status, at::kInt, "status"); check_dev(meas_of, at::kInt, "meas_of");
+  check_dev(track_i, at::kInt, "track_i"); check_dev(track_f, at::kDouble, "track_f"); check_dev(track_pose, at::kDouble, "track_pose"); check_dev(T_WC, at::kDouble, "T_WC");
+  check_dev(win_obs, at::kDouble, "win_obs"); check_dev(win_age, at::kInt, "win_age"); check_dev(win_views, at::kDouble, "win_views"); check_dev(win_i, at::kInt, "win_i");
+  check_dev(n_views, at::kInt, "n_views"); check_dev(start, at::kDouble, "start"); check_dev(start_velocity, at::kDouble, "start_velocity");
+  TORCH_CHECK(tab.dim() == 4 && tab.size(3) == 4, "okp: tab is [B,max_obj,S,4] float64");
+  TORCH_CHECK(win_obs.dim() == 5 && win_obs.size(4) == 2, "okp: win_obs is [B,T,S,W,2] float64");
+  const int64_t B = tab.size(0), max_obj = tab.size(1), S = tab.size(2), T = win_obs.size(1), W = win_obs.size(3);
+  TORCH_CHECK(win_obs.size(0) == B && win_obs.size(2) == S && win_age.numel() == B * T * W && win_views.numel() == B * T * W * 14 && win_i.numel() == B * T * 4,
+              "okp: the timed window state is win_obs [B,T,S,W,2], win_age [B,T,W], win_views [B,T,W,14] and win_i [B,T,4] for the table's B and S");
+  TORCH_CHECK(assignment.numel() == B * max_obj * S && status.numel() == B * max_obj && meas_of.numel() == B * T && track_i.numel() == B * T * 4 &&
+              track_f.numel() == B * T * 16 && track_pose.numel() == B * T * 12 && T_WC.numel() == B * 12,
+              "okp: window_push_timed inputs are assignment [B,max_obj,S], status [B,max_obj], meas_of [B,T], track_i [B,T,4], track_f [B,T,16], track_pose [B,T,12] and T_WC [B,12]");
+  TORCH_CHECK(n_views.numel() == B * T && start.numel() == B * T * 12 && start_velocity.numel() == B * T * 3,
+              "okp: window_push_timed outputs are n_views [B,T], start [B,T,12] and start_velocity [B,T,3]");
+  TORCH_CHECK(min_views >= INT32_MIN && min_views <= INT32_MAX, "okp: min_views does not fit an int32");
+  TORCH_CHECK(B <= INT32_MAX && max_obj <= INT32_MAX && S <= INT32_MAX && T <= INT32_MAX && W <= INT32_MAX, "okp: tab or win_obs is too large");
+  const okp_camera cam = camera_of(camera);
+  check_rc(okp_window_push_timed(tab.data_ptr<double>(), assignment.data_ptr<int32_t>(), status.data_ptr<int32_t>(), meas_of.data_ptr<int32_t>(), track_i.data_ptr<int32_t>(),
+                                 track_f.data_ptr<double>(), track_pose.data_ptr<double>(), T_WC.data_ptr<double>(), &cam, (int32_t)B, (int32_t)max_obj, (int32_t)S, (int32_t)T,
+                                 (int32_t)W, (int32_t)min_views, max_speed, win_obs.data_ptr<double>(), win_age.data_ptr<int32_t>(), win_views.data_ptr<double>(),
+                                 win_i.data_ptr<int32_t>(), n_views.data_ptr<int32_t>(), start.data_ptr<double>(), start_velocity.data_ptr<double>(), sp(stream)),
+           "okp_window_push_timed");
+}
+
+// window_push_views with the state win_age [B,T,W*V] int32 and the output start_velocity [B,T,3]
+void window_push_views_timed(const Tensor& obs, const Tensor& assignment, const Tensor& status, const Tensor& meas_of, const Tensor& track_i, const Tensor& track_f,
+                             const Tensor& track_pose, const Tensor& T_WB, const Tensor& views, int64_t ticks, int64_t min_views, double max_speed, const Tensor& win_obs,
+                             const Tensor& win_age, const Tensor& win_views, const Tensor& win_i, const Tensor& n_views, const Tensor& start, const Tensor& start_velocity,
+                             int64_t stream) {
+  check_dev(obs, at::kDouble, "obs"); check_dev(assignment, at::kInt, "assignment"); check_dev(status, at::kInt, "status"); check_dev(meas_of, at::kInt, "meas_of");
+  check_dev(track_i, at::kInt, "track_i"); check_dev(track_f, at::kDouble, "track_f"); check_dev(track_pose, at::kDouble, "track_pose"); check_dev(T_WB, at::kDouble, "T_WB");
+  check_dev(views, at::kDouble, "views"); check_dev(win_obs, at::kDouble, "win_obs"); check_dev(win_age, at::kInt, "win_age"); check_dev(win_views, at::kDouble, "win_views");
+  check_dev(win_i, at::kInt, "win_i"); check_dev(n_views, at::kInt, "n_views"); check_dev(start, at::kDouble, "start"); check_dev(start_velocity, at::kDouble, "start_velocity");
+  TORCH_CHECK(obs.dim() == 5 && obs.size(4) == 2, "okp: obs is [B,max_obj,S,V,2] float64");
+  TORCH_CHECK(win_obs.dim() == 5 && win_obs.size(4) == 2, "okp: win_obs is [B,T,S,W*V,2] float64");
+  const int64_t B = obs.size(0), max_obj = obs.size(1), S = obs.size(2), V = obs.size(3), T = win_obs.size(1), W = ticks;
+  TORCH_CHECK(W >= INT32_MIN && W <= INT32_MAX && min_views >= INT32_MIN && min_views <= INT32_MAX, "okp: ticks or min_views does not fit an int32");
+  TORCH_CHECK(B <= INT32_MAX && max_obj <= INT32_MAX && S <= INT32_MAX && T <= INT32_MAX && V <= INT32_MAX, "okp: obs or win_obs is too large");
+  TORCH_CHECK(W < 1 || V < 1 || (win_obs.size(0) == B && win_obs.size(2) == S && win_obs.size(3) == W * V && win_age.numel() == B * T * W * V &&
+                                 win_views.numel() == B * T * W * V * 14 && win_i.numel() == B * T * 4),
+              "okp: the timed window state is win_obs [B,T,S,W*V,2], win_age [B,T,W*V], win_views [B,T,W*V,14] and win_i [B,T,4] for the bearings' B, S and V and W = ticks");
+  TORCH_CHECK(assignment.numel() == B * max_obj * S && status.numel() == B * max_obj && meas_of.numel() == B * T && track_i.numel() == B * T * 4 &&
+              track_f.numel() == B * T * 16 && track_pose.numel() == B * T * 12 && T_WB.numel() == B * 12 && views.numel() == V * 14,
+              "okp: window_push_views_timed inputs are assignment [B,max_obj,S], status [B,max_obj], meas_of [B,T], track_i [B,T,4], track_f [B,T,16], track_pose [B,T,12], "
+              "T_WB [B,12] and views [V,14]");
+  TORCH_CHECK(n_views.numel() == B * T && start.numel() == B * T * 12 && start_velocity.numel() == B * T * 3,
+              "okp: window_push_views_timed outputs are n_views [B,T], start [B,T,12] and start_velocity [B,T,3]");
+  check_rc(okp_window_push_views_timed(obs.data_ptr<double>(), assignment.data_ptr<int32_t>(), status.data_ptr<int32_t>(), meas_of.data_ptr<int32_t>(),
+                                       track_i.data_ptr<int32_t>(), track_f.data_ptr<double>(), track_pose.data_ptr<double>(), T_WB.data_ptr<double>(), views.data_ptr<double>(),
+                                       (int32_t)B, (int32_t)max_obj, (int32_t)S, (int32_t)T, (int32_t)W, (int32_t)V, (int32_t)min_views, max_speed, win_obs.data_ptr<double>(),
+                                       win_age.data_ptr<int32_t>(), win_views.data_ptr<double>(), win_i.data_ptr<int32_t>(), n_views.data_ptr<int32_t>(),
+                                       start.data_ptr<double>(), start_velocity.data_ptr<double>(), sp(stream)), "okp_window_push_views_timed");
+}
+
+// The window refinement of a moving object (csrc/okp_refine_motion.hip): refine_pose_views_each's obs and views [B,max_obj,V,14] with age [B,max_obj,V] int32, a pose
+// and a velocity [B,max_obj,3] -> pose_out, velocity_out, fit [B,max_obj,2], n_obs, information [B,max_obj,81] and status
+void refine_motion_views(const Tensor& obs, const Tensor& views, const Tensor& age, const Tensor& pose, const Tensor& velocity, const Tensor& assignment, const Tensor& n_obj,
+                         const Tensor& model, double sigma_px, double dt, int64_t horizon, int64_t iters, double damping, const Tensor& pose_out, const Tensor& velocity_out,
+                         const Tensor& fit, const Tensor& n_obs, const Tensor& information, const Tensor& status, int64_t stream) {
+  check_dev(obs, at::kDouble, "obs"); check_dev(views, at::kDouble, "views"); check_dev(age, at::kInt, "age"); check_dev(pose, at::kDouble, "pose");
+  check_dev(velocity, at::kDouble, "velocity"); check_dev(assignment, at::kInt, "assignment"); check_dev(n_obj, at::kInt, "n_obj"); check_dev(model, at::kDouble, "model");
+  check_dev(pose_out, at::kDouble, "pose_out"); check_dev(velocity_out, at::kDouble, "velocity_out"); check_dev(fit, at::kDouble, "fit"); check_dev(n_obs, at::kInt, "n_obs");
+  check_dev(information, at::kDouble, "information"); check_dev(status, at::kInt, "status");
+  TORCH_CHECK(obs.dim() == 5 && obs.size(4) == 2, "okp: obs is [B,max_obj,S,V,2] float64");
+  const int64_t B = obs.size(0), max_obj = obs.size(1), S = obs.size(2), V = obs.size(3);
+  TORCH_CHECK(views.numel() == B * max_obj * V * 14 && age.numel() == B * max_obj * V && pose.numel() == B * max_obj * 12 && velocity.numel() == B * max_obj * 3 &&
+              assignment.numel() == B * max_obj * S && n_obj.numel() == B && model.numel() == S * 3,
+              "okp: refine_motion_views inputs are views [B,max_obj,V,14], age [B,max_obj,V], pose [B,max_obj,12], velocity [B,max_obj,3], assignment [B,max_obj,S], "
+              "n_obj [B] and model [S,3]");
+  TORCH_CHECK(pose_out.numel() == B * max_obj * 12 && velocity_out.numel() == B * max_obj * 3 && fit.numel() == B * max_obj * 2 && n_obs.numel() == B * max_obj &&
+              information.numel() == B * max_obj * 81 && status.numel() == B * max_obj,
+              "okp: refine_motion_views outputs are pose_out [B,max_obj,12], velocity_out [B,max_obj,3], fit [B,max_obj,2], n_obs [B,max_obj], information [B,max_obj,81] "
+              "and status [B,max_obj]");
+  TORCH_CHECK(iters >= INT32_MIN && iters <= INT32_MAX && horizon >= INT32_MIN && horizon <= INT32_MAX, "okp: iters or horizon does not fit an int32");
+  TORCH_CHECK(B <= INT32_MAX && max_obj <= INT32_MAX && S <= INT32_MAX && V <= INT32_MAX, "okp: obs is too large");
+  check_rc(okp_refine_motion_views(obs.data_ptr<double>(), views.data_ptr<double>(), age.data_ptr<int32_t>(), pose.data_ptr<double>(), velocity.data_ptr<double>(),
+                                   assignment.data_ptr<int32_t>(), n_obj.data_ptr<int32_t>(), model.data_ptr<double>(), sigma_px, dt, (int32_t)horizon, (int32_t)iters, damping,
+                                   (int32_t)B, (int32_t)max_obj, (int32_t)S, (int32_t)V, pose_out.data_ptr<double>(), velocity_out.data_ptr<double>(), fit.data_ptr<double>(),
+                                   n_obs.data_ptr<int32_t>(), information.data_ptr<double>(), status.data_ptr<int32_t>(), sp(stream)), "okp_refine_motion_views");
+}
+
 void lift_peaks(at::ArrayRef<double> camera, const Tensor& count, const Tensor& xyc, const Tensor& depth, int64_t max_x, int64_t max_y, const Tensor& out, int64_t stream) {
   TORCH_CHECK(xyc.is_cuda() && xyc.dim() == 4 && xyc.scalar_type() == at::kFloat && depth.is_cuda() && depth.scalar_type() == at::kFloat && depth.dim() == 4 && depth.is_contiguous() &&
               depth.size(0) == xyc.size(0) && depth.size(1) == xyc.size(1) && count.scalar_type() == at::kInt && out.scalar_type() == at::kDouble &&
@@ -1337,6 +1423,15 @@ TORCH_LIBRARY(okp, m) {
   m.def("window_push_views_weighted(Tensor obs, Tensor prior, Tensor assignment, Tensor status, Tensor meas_of, Tensor track_i, Tensor track_f, Tensor track_pose, "
         "Tensor T_WB, Tensor views, int ticks, int min_views, float max_speed, Tensor(a!) win_obs, Tensor(b!) win_prior, Tensor(c!) win_views, Tensor(d!) win_i, "
         "Tensor(e!) n_views, Tensor(f!) start, int stream) -> ()", window_push_views_weighted);
+  m.def("window_push_timed(float[] camera, Tensor tab, Tensor assignment, Tensor status, Tensor meas_of, Tensor track_i, Tensor track_f, Tensor track_pose, Tensor T_WC, "
+        "int min_views, float max_speed, Tensor(a!) win_obs, Tensor(b!) win_age, Tensor(c!) win_views, Tensor(d!) win_i, Tensor(e!) n_views, Tensor(f!) start, "
+        "Tensor(g!) start_velocity, int stream) -> ()", window_push_timed);
+  m.def("window_push_views_timed(Tensor obs, Tensor assignment, Tensor status, Tensor meas_of, Tensor track_i, Tensor track_f, Tensor track_pose, Tensor T_WB, "
+        "Tensor views, int ticks, int min_views, float max_speed, Tensor(a!) win_obs, Tensor(b!) win_age, Tensor(c!) win_views, Tensor(d!) win_i, Tensor(e!) n_views, "
+        "Tensor(f!) start, Tensor(g!) start_velocity, int stream) -> ()", window_push_views_timed);
+  m.def("refine_motion_views(Tensor obs, Tensor views, Tensor age, Tensor pose, Tensor velocity, Tensor assignment, Tensor n_obj, Tensor model, float sigma_px, float dt, "
+        "int horizon, int iters, float damping, Tensor(a!) pose_out, Tensor(b!) velocity_out, Tensor(c!) fit, Tensor(d!) n_obs, Tensor(e!) information, "
+        "Tensor(f!) status, int stream) -> ()", refine_motion_views);
   m.def("refine_assignments(float[] camera, Tensor tab, Tensor pose, Tensor assignment, Tensor n_obj, Tensor model, int[] type_count, float sigma_px, float sigma_z, int iters, "
         "float damping, Tensor(a!) pose_out, Tensor(b!) fit, Tensor(c!) information, Tensor(d!) status, Tensor(e!) assignment_out, Tensor(f!) hypothesis, Tensor(g!) cost, "
         "int stream) -> ()", refine_assignments);

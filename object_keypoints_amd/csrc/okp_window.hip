@@ -23,12 +23,17 @@ struct WindowParams {
   int32_t max_obj, S, T, W, min_views;
   double* win_obs; double* win_views; int32_t* win_i; int32_t* n_views; double* start;
   double* win_prior; double conf_ref, conf_floor;                 // the PRIOR instance's (okp_window_push_weighted); last, so the other offsets stay
+  int32_t* win_age; double* start_velocity;                       // (every instance's kernel arguments grow by these 16 bytes) the TIMED instance's (okp_window_push_timed); after those, for the same reason
 };
 
 // PRIOR: the ring of priors next to the ring of bearings (okp_window_push_weighted): an entry of win_prior is written wherever its entry of
 // win_obs is - the mapped confidence of the table row with a bearing, NaN with (NaN, NaN); the plain instance is the code it was
-template <bool PRIOR>
-__global__ __launch_bounds__(64) void okp_window_push_kernel(const WindowParams P) {
+// TIMED: the ring knows how old its columns are (okp_window_push_timed): win_age counts the ticks since a column was pushed - a coasting tick
+// pushes nothing, so the column index is not the age - and the track's velocity goes out next to the start; under `if constexpr`, so the
+// instances without it are the code they were.  The body of the kernels below: okp_window_push_kernel<PRIOR> keeps its name and its two
+// instances, the TIMED instance is a kernel of its own name
+template <bool PRIOR, bool TIMED>
+__device__ __forceinline__ void window_push_body(const WindowParams& P) {
   __shared__ double row[OKP_POSE_MAX_POINTS][2];                  // the new column: the bearing of every model row, or NaN
   [[maybe_unused]] __shared__ double prow[OKP_POSE_MAX_POINTS];   // (PRIOR) and its prior
   __shared__ double view[14];
@@ -120,6 +125,13 @@ __global__ __launch_bounds__(64) void okp_window_push_kernel(const WindowParams 
     if (push && c == head) vw[e] = view[k];
     else if (clear) vw[e] = 0.0;
   }
+  if constexpr (TIMED) {                                          // a pushed column is 0 ticks old, a free slot's are 0, every other one a tick older
+    int32_t* ages = P.win_age + bi * W;
+    for (int c = lane; c < W; c += 64) {
+      const int32_t old = clear ? 0 : ages[c];
+      ages[c] = (push && c == head) || id == 0 ? 0 : (old < (1 << 30) ? old + 1 : (1 << 30));
+    }
+  }
   if (push) { head = head + 1 == W ? 0 : head + 1; filled = filled < W ? filled + 1 : W; }
 
   if (lane == 0) { wi[0] = owner; wi[1] = head; wi[2] = filled; wi[3] = 0; P.n_views[bi] = filled; }
@@ -128,16 +140,29 @@ __global__ __launch_bounds__(64) void okp_window_push_kernel(const WindowParams 
     if (filled >= P.min_views) reinterpret_cast<unsigned long long*>(P.start)[bi * 12 + lane] = bits;
     else P.start[bi * 12 + lane] = nan;
   }
+  if constexpr (TIMED) {
+    if (lane < 3) {                                               // the start of the velocity: the track's, bit for bit, wherever the start is the track pose
+      const unsigned long long bits = reinterpret_cast<const unsigned long long*>(P.track_f)[bi * 16 + 3 + lane];
+      if (filled >= P.min_views) reinterpret_cast<unsigned long long*>(P.start_velocity)[bi * 3 + lane] = bits;
+      else P.start_velocity[bi * 3 + lane] = nan;
+    }
+  }
 }
+
+template <bool PRIOR>
+__global__ __launch_bounds__(64) void okp_window_push_kernel(const WindowParams P) { window_push_body<PRIOR, false>(P); }
+
+__global__ __launch_bounds__(64) void okp_window_push_timed_kernel(const WindowParams P) { window_push_body<false, true>(P); }
 
 }  // namespace
 
-// okp_window_push and okp_window_push_weighted: one kernel, the second instance also keeps the ring of priors
+// okp_window_push, okp_window_push_weighted and okp_window_push_timed: one kernel; the second instance also keeps the ring of priors, the third
+// the ages of the columns
 static int window_push_launch(const char* fn, const char* what, const double* tab, const int32_t* assignment, const int32_t* status, const int32_t* meas_of,
                               const int32_t* track_i, const double* track_f, const double* track_pose, const double* T_WC, const okp_camera* cam, int32_t B,
                               int32_t max_obj, int32_t S, int32_t T, int32_t W, int32_t min_views, double max_speed, bool weighted, double conf_ref,
                               double conf_floor, double* win_obs, double* win_prior, double* win_views, int32_t* win_i, int32_t* n_views, double* start,
-                              void* stream) {
+                              void* stream, bool timed = false, int32_t* win_age = nullptr, double* start_velocity = nullptr) {
   if (B < 1) { okp_set_error("%s: B = %d; at least one stream", fn, B); return OKP_EINVAL; }
   if (max_obj < 1) { okp_set_error("%s: max_obj = %d; a stream holds at least one object", fn, max_obj); return OKP_EINVAL; }
   if (S < 1 || S > OKP_POSE_MAX_POINTS) { okp_set_error("%s: S = %d outside [1, %d] model points", fn, S, OKP_POSE_MAX_POINTS); return OKP_EINVAL; }
@@ -166,6 +191,8 @@ static int window_push_launch(const char* fn, const char* what, const double* ta
   for (const auto& r : required)
     if (!r.ptr) { okp_set_error("%s: null %s", fn, r.name); return OKP_EINVAL; }
   if (weighted && !win_prior) { okp_set_error("%s: null win_prior", fn); return OKP_EINVAL; }
+  if (timed && !win_age) { okp_set_error("%s: null win_age", fn); return OKP_EINVAL; }
+  if (timed && !start_velocity) { okp_set_error("%s: null start_velocity", fn); return OKP_EINVAL; }
   WindowParams p = {};
   p.tab = tab; p.assignment = assignment; p.status = status; p.meas_of = meas_of; p.track_i = track_i; p.track_f = track_f;
   p.track_pose = track_pose; p.T_WC = T_WC;
@@ -173,7 +200,9 @@ static int window_push_launch(const char* fn, const char* what, const double* ta
   p.max_obj = max_obj; p.S = S; p.T = T; p.W = W; p.min_views = min_views;
   p.win_obs = win_obs; p.win_views = win_views; p.win_i = win_i; p.n_views = n_views; p.start = start;
   p.win_prior = win_prior; p.conf_ref = conf_ref; p.conf_floor = conf_floor;
-  if (weighted) hipLaunchKernelGGL(okp_window_push_kernel<true>, dim3((unsigned)((size_t)B * T)), dim3(64), 0, (hipStream_t)stream, p);
+  p.win_age = win_age; p.start_velocity = start_velocity;
+  if (timed) hipLaunchKernelGGL(okp_window_push_timed_kernel, dim3((unsigned)((size_t)B * T)), dim3(64), 0, (hipStream_t)stream, p);
+  else if (weighted) hipLaunchKernelGGL(okp_window_push_kernel<true>, dim3((unsigned)((size_t)B * T)), dim3(64), 0, (hipStream_t)stream, p);
   else hipLaunchKernelGGL(okp_window_push_kernel<false>, dim3((unsigned)((size_t)B * T)), dim3(64), 0, (hipStream_t)stream, p);
   return okp_check_hip(hipGetLastError(), what);
 }
@@ -193,4 +222,13 @@ extern "C" int okp_window_push_weighted(const double* tab, const int32_t* assign
                                         double* start, void* stream) {
   return window_push_launch("okp_window_push_weighted", "okp_window_push_weighted launch", tab, assignment, status, meas_of, track_i, track_f, track_pose, T_WC, cam,
                             B, max_obj, S, T, W, min_views, max_speed, true, conf_ref, conf_floor, win_obs, win_prior, win_views, win_i, n_views, start, stream);
+}
+
+extern "C" int okp_window_push_timed(const double* tab, const int32_t* assignment, const int32_t* status, const int32_t* meas_of, const int32_t* track_i,
+                                     const double* track_f, const double* track_pose, const double* T_WC, const okp_camera* cam, int32_t B, int32_t max_obj,
+                                     int32_t S, int32_t T, int32_t W, int32_t min_views, double max_speed, double* win_obs, int32_t* win_age, double* win_views,
+                                     int32_t* win_i, int32_t* n_views, double* start, double* start_velocity, void* stream) {
+  return window_push_launch("okp_window_push_timed", "okp_window_push_timed launch", tab, assignment, status, meas_of, track_i, track_f, track_pose, T_WC, cam, B,
+                            max_obj, S, T, W, min_views, max_speed, false, 0.0, 0.0, win_obs, nullptr, win_views, win_i, n_views, start, stream, true, win_age,
+                            start_velocity);
 }

@@ -27,12 +27,17 @@ struct WindowViewsParams {
   int32_t max_obj, S, T, W, V, min_views;
   double* win_obs; double* win_views; int32_t* win_i; int32_t* n_views; double* start;
   const double* prior; double* win_prior;                         // the PRIOR instance's (okp_window_push_views_weighted); last, so the other offsets stay
+  int32_t* win_age; double* start_velocity;                       // (every instance's kernel arguments grow by these 16 bytes) the TIMED instance's (okp_window_push_views_timed); after those, for the same reason
 };
 
 // PRIOR: the ring of priors next to the ring of bearings (okp_window_push_views_weighted): an entry of win_prior is written wherever its entry
 // of win_obs is - the table's prior bit for bit with a copied bearing, NaN with (NaN, NaN); the plain instance is the code it was
-template <bool PRIOR>
-__global__ __launch_bounds__(OKP_WINDOW_VIEWS_THREADS) void okp_window_push_views_kernel(const WindowViewsParams P) {
+// TIMED: the ring knows how old its columns are (okp_window_push_views_timed): win_age holds, for every view of the ring, the ticks since its
+// column was pushed, and the track's velocity goes out next to the start; under `if constexpr`, so the instances without it are the code
+// they were.  The body of the kernels below: okp_window_push_views_kernel<PRIOR> keeps its name and its two instances, the TIMED instance
+// is a kernel of its own name
+template <bool PRIOR, bool TIMED>
+__device__ __forceinline__ void window_push_views_body(const WindowViewsParams& P) {
   __shared__ int32_t slot_of[OKP_POSE_MAX_POINTS];                // the table slot whose bearings model row r takes, or -1
   const int tid = threadIdx.x;
   const size_t bi = blockIdx.x;                                   // b * T + i
@@ -112,6 +117,13 @@ __global__ __launch_bounds__(OKP_WINDOW_VIEWS_THREADS) void okp_window_push_view
       vw[e] = x;
     } else if (clear) vw[e] = 0.0;
   }
+  if constexpr (TIMED) {                                          // a pushed column is 0 ticks old, a free slot's are 0, every other one a tick older
+    int32_t* ages = P.win_age + bi * (size_t)WV;
+    for (int cv = tid; cv < WV; cv += OKP_WINDOW_VIEWS_THREADS) {
+      const int32_t old = clear ? 0 : ages[cv];
+      ages[cv] = (push && cv / V == head) || id == 0 ? 0 : (old < (1 << 30) ? old + 1 : (1 << 30));
+    }
+  }
   if (push) { head = head + 1 == W ? 0 : head + 1; filled = filled < W ? filled + 1 : W; }
 
   if (tid == 0) { wi[0] = owner; wi[1] = head; wi[2] = filled; wi[3] = 0; P.n_views[bi] = filled; }
@@ -120,16 +132,29 @@ __global__ __launch_bounds__(OKP_WINDOW_VIEWS_THREADS) void okp_window_push_view
     if (filled >= P.min_views) reinterpret_cast<unsigned long long*>(P.start)[bi * 12 + tid] = bits;
     else P.start[bi * 12 + tid] = nan;
   }
+  if constexpr (TIMED) {
+    if (tid < 3) {                                                // the start of the velocity: the track's, bit for bit, wherever the start is the track pose
+      const unsigned long long bits = reinterpret_cast<const unsigned long long*>(P.track_f)[bi * 16 + 3 + tid];
+      if (filled >= P.min_views) reinterpret_cast<unsigned long long*>(P.start_velocity)[bi * 3 + tid] = bits;
+      else P.start_velocity[bi * 3 + tid] = nan;
+    }
+  }
 }
+
+template <bool PRIOR>
+__global__ __launch_bounds__(OKP_WINDOW_VIEWS_THREADS) void okp_window_push_views_kernel(const WindowViewsParams P) { window_push_views_body<PRIOR, false>(P); }
+
+__global__ __launch_bounds__(OKP_WINDOW_VIEWS_THREADS) void okp_window_push_views_timed_kernel(const WindowViewsParams P) { window_push_views_body<false, true>(P); }
 
 }  // namespace
 
-// okp_window_push_views and okp_window_push_views_weighted: one kernel, the second instance also keeps the ring of priors
+// okp_window_push_views, okp_window_push_views_weighted and okp_window_push_views_timed: one kernel; the second instance also keeps the ring of
+// priors, the third the ages of the columns
 static int window_push_views_launch(const char* fn, const char* what, const double* obs, const double* prior, bool weighted, const int32_t* assignment,
                                     const int32_t* status, const int32_t* meas_of, const int32_t* track_i, const double* track_f, const double* track_pose,
                                     const double* T_WB, const double* views, int32_t B, int32_t max_obj, int32_t S, int32_t T, int32_t W, int32_t V,
                                     int32_t min_views, double max_speed, double* win_obs, double* win_prior, double* win_views, int32_t* win_i, int32_t* n_views,
-                                    double* start, void* stream) {
+                                    double* start, void* stream, bool timed = false, int32_t* win_age = nullptr, double* start_velocity = nullptr) {
   if (B < 1) { okp_set_error("%s: B = %d; at least one stream", fn, B); return OKP_EINVAL; }
   if (max_obj < 1) { okp_set_error("%s: max_obj = %d; a stream holds at least one object", fn, max_obj); return OKP_EINVAL; }
   if (S < 1 || S > OKP_POSE_MAX_POINTS) { okp_set_error("%s: S = %d outside [1, %d] model points", fn, S, OKP_POSE_MAX_POINTS); return OKP_EINVAL; }
@@ -151,6 +176,8 @@ static int window_push_views_launch(const char* fn, const char* what, const doub
     if (!r.ptr) { okp_set_error("%s: null %s", fn, r.name); return OKP_EINVAL; }
   if (weighted && !prior) { okp_set_error("%s: null prior", fn); return OKP_EINVAL; }
   if (weighted && !win_prior) { okp_set_error("%s: null win_prior", fn); return OKP_EINVAL; }
+  if (timed && !win_age) { okp_set_error("%s: null win_age", fn); return OKP_EINVAL; }
+  if (timed && !start_velocity) { okp_set_error("%s: null start_velocity", fn); return OKP_EINVAL; }
   WindowViewsParams p = {};
   p.obs = obs; p.assignment = assignment; p.status = status; p.meas_of = meas_of; p.track_i = track_i; p.track_f = track_f;
   p.track_pose = track_pose; p.T_WB = T_WB; p.views = views;
@@ -158,8 +185,10 @@ static int window_push_views_launch(const char* fn, const char* what, const doub
   p.max_obj = max_obj; p.S = S; p.T = T; p.W = W; p.V = V; p.min_views = min_views;
   p.win_obs = win_obs; p.win_views = win_views; p.win_i = win_i; p.n_views = n_views; p.start = start;
   p.prior = prior; p.win_prior = win_prior;
+  p.win_age = win_age; p.start_velocity = start_velocity;
   const dim3 grid((unsigned)((size_t)B * T)), block(OKP_WINDOW_VIEWS_THREADS);
-  if (weighted) hipLaunchKernelGGL(okp_window_push_views_kernel<true>, grid, block, 0, (hipStream_t)stream, p);
+  if (timed) hipLaunchKernelGGL(okp_window_push_views_timed_kernel, grid, block, 0, (hipStream_t)stream, p);
+  else if (weighted) hipLaunchKernelGGL(okp_window_push_views_kernel<true>, grid, block, 0, (hipStream_t)stream, p);
   else hipLaunchKernelGGL(okp_window_push_views_kernel<false>, grid, block, 0, (hipStream_t)stream, p);
   return okp_check_hip(hipGetLastError(), what);
 }
@@ -180,4 +209,14 @@ extern "C" int okp_window_push_views_weighted(const double* obs, const double* p
   return window_push_views_launch("okp_window_push_views_weighted", "okp_window_push_views_weighted launch", obs, prior, true, assignment, status, meas_of, track_i,
                                   track_f, track_pose, T_WB, views, B, max_obj, S, T, W, V, min_views, max_speed, win_obs, win_prior, win_views, win_i, n_views, start,
                                   stream);
+}
+
+extern "C" int okp_window_push_views_timed(const double* obs, const int32_t* assignment, const int32_t* status, const int32_t* meas_of, const int32_t* track_i,
+                                           const double* track_f, const double* track_pose, const double* T_WB, const double* views, int32_t B,
+                                           int32_t max_obj, int32_t S, int32_t T, int32_t W, int32_t V, int32_t min_views, double max_speed, double* win_obs,
+                                           int32_t* win_age, double* win_views, int32_t* win_i, int32_t* n_views, double* start, double* start_velocity,
+                                           void* stream) {
+  return window_push_views_launch("okp_window_push_views_timed", "okp_window_push_views_timed launch", obs, nullptr, false, assignment, status, meas_of, track_i,
+                                  track_f, track_pose, T_WB, views, B, max_obj, S, T, W, V, min_views, max_speed, win_obs, nullptr, win_views, win_i, n_views, start,
+                                  stream, true, win_age, start_velocity);
 }

@@ -1752,7 +1752,7 @@ def refine_pose_views_each(obs, views, pose, n_obj, model, cfg):
     return _refine_views(True, obs, views, pose, n_obj, model, cfg)
 
 
-def _views_inputs(each, obs, views, pose, n_obj, model, cfg, cfg_types, cfg_text, max_views, obs_from, views_from, prior=None):
+def _views_inputs(each, obs, views, pose, n_obj, model, cfg, cfg_types, cfg_text, max_views, obs_from, views_from, prior=None, motion=False):
     """The argument checks every refinement against views shares -> (fitted, assignment, b, max_obj, s, v, dev).  cfg_types / cfg_text: the
     config classes accepted and their names in the message; max_views: the entry point's limit on V; obs_from / views_from: where the message
     says obs and a shared views table come from."""
@@ -1765,6 +1765,9 @@ def _views_inputs(each, obs, views, pose, n_obj, model, cfg, cfg_types, cfg_text
                             "refine_pose_views_wide have no priors and take a config without it")
     if getattr(cfg, "resolve_views", False):     # (never dropped quietly: these refine ONE assignment)
         raise OkpNotOffered(_RESOLVE_VIEWS_ELSEWHERE)
+    if getattr(cfg, "motion", None) is not None and not motion:      # (nor a moving object refined as a static one)
+        raise OkpNotOffered("cfg.motion: refine_motion_views takes it, with the ages of the views and a start velocity; the refinements of a static object "
+                            "take a config without it")
     try:
         fitted, assignment = pose["pose"], pose["assignment"]
     except (TypeError, KeyError, IndexError):
@@ -1881,9 +1884,19 @@ class WindowConfig:
                    threshold (okp_refine_pose_views_robust, views_each = 1).
         confidence (keyword, default None) a ConfidenceWeights: the window then keeps a ring of priors next to its ring of bearings
                    (okp_window_push_weighted / okp_window_push_views_weighted) and its refinement weights every bearing by its prior
-                   (okp_refine_pose_views_weighted)."""
+                   (okp_refine_pose_views_weighted).
+        motion     (keyword, default None) "constant_velocity": the window of a MOVING object.  The ring then knows how old its columns are
+                   (okp_window_push_timed / okp_window_push_views_timed) and its refinement solves for the pose at the newest tick and a
+                   linear velocity in the world frame, nine unknowns (okp_refine_motion_views).  Needs min_views >= 2 - one column has one
+                   age, and a velocity cannot be seen from it - and is not offered together with huber_px or confidence yet.  The
+                   orientation is taken as constant over the window; on a static object the centre is worse than the static window's.
+        horizon    (keyword, default None) with motion: an integer number of ticks, at least 1; columns older than this are left out of the
+                   refinement - constant velocity is assumed over the horizon and no further.  None: 2^30, every column counts."""
 
-    def __init__(self, ticks, min_views=2, max_speed=float("inf"), sigma_px=0.25, iters=6, damping=1e-9, *, huber_px=None, confidence=None):
+    MOTIONS = ("constant_velocity",)
+    MAX_HORIZON = 1 << 30
+
+    def __init__(self, ticks, min_views=2, max_speed=float("inf"), sigma_px=0.25, iters=6, damping=1e-9, *, huber_px=None, confidence=None, motion=None, horizon=None):
         def number(name, v):
             if isinstance(v, bool):
                 raise OkpError(f"WindowConfig: {name} = {v!r} is not a number")
@@ -1909,20 +1922,35 @@ class WindowConfig:
         self.iters = integer("iters", iters, 1, REFINE_MAX_ITERS)
         self.huber_px = _huber_px("WindowConfig", huber_px)
         self.confidence = _confidence("WindowConfig", confidence)
+        if motion is not None and (not isinstance(motion, str) or motion not in self.MOTIONS):
+            raise OkpError(f"WindowConfig: motion = {motion!r} must be one of {list(self.MOTIONS)} (None: a static object)")
+        self.motion = motion
+        if horizon is not None and motion is None:
+            raise OkpError(f"WindowConfig: horizon = {horizon!r} without motion: the static window has no notion of a column's age")
+        self.horizon = integer("horizon", horizon, 1, self.MAX_HORIZON) if horizon is not None else (self.MAX_HORIZON if motion is not None else None)
+        if motion is not None:
+            if self.min_views < 2:
+                raise OkpError(f"WindowConfig: motion = {motion!r} with min_views = {self.min_views}: a velocity needs columns of two ages, min_views >= 2")
+            if self.huber_px is not None:
+                raise OkpNotOffered("WindowConfig: huber_px together with motion is not offered yet (a follow-up: the Huber loss on the nine-unknown refinement)")
+            if self.confidence is not None:
+                raise OkpNotOffered("WindowConfig: confidence together with motion is not offered yet (a follow-up: the priors on the nine-unknown refinement)")
 
     def __repr__(self):
         flag = f", huber_px={self.huber_px}" if self.huber_px is not None else ""
         flag += f", confidence={self.confidence}" if self.confidence is not None else ""
+        flag += f", motion={self.motion!r}, horizon={self.horizon}" if self.motion is not None else ""
         return (f"WindowConfig(ticks={self.ticks}, min_views={self.min_views}, max_speed={self.max_speed}, sigma_px={self.sigma_px}, iters={self.iters}, "
                 f"damping={self.damping}{flag})")
 
 
-def window_state(B, max_tracks, S, ticks, device, prior=False):
+def window_state(B, max_tracks, S, ticks, device, prior=False, timed=False):
     """An empty window of B streams x max_tracks slots x S model rows x ticks columns: {"win_obs" [B,T,S,W,2] float64, all NaN, "win_views"
     [B,T,W,14] float64 and "win_i" [B,T,4] int32 (owner id, head, filled, one spare), zeros} on `device` - window_push() steps it in place -
     plus what the refinement of the window reads next to it on every call: "win_assignment" [B,T,S] int32, the identity (ring rows are model
     rows), and "win_n" [B] int32 filled with T (every slot is an "object"; free ones arrive with a NaN pose).  prior=True (a WindowConfig with
-    confidence): also "win_prior" [B,T,S,W] float64, all NaN, the ring of the bearings' priors."""
+    confidence): also "win_prior" [B,T,S,W] float64, all NaN, the ring of the bearings' priors.  timed=True (a WindowConfig with motion): also
+    "win_age" [B,T,W] int32, zeros, the age of every column in ticks."""
     B, T, S, W = int(B), int(max_tracks), int(S), int(ticks)
     if B < 1 or not 1 <= T <= TRACK_MAX_TRACKS or not 1 <= S <= POSE_MAX_POINTS or not 1 <= W <= REFINE_MAX_VIEWS:
         raise OkpError(f"window_state: B = {B} streams (at least 1) of max_tracks = {T} slots (1 .. {TRACK_MAX_TRACKS}), S = {S} model rows (1 .. {POSE_MAX_POINTS}), "
@@ -1936,6 +1964,8 @@ def window_state(B, max_tracks, S, ticks, device, prior=False):
              "win_n": torch.full((B,), T, dtype=torch.int32, device=device)}
     if prior:
         state["win_prior"] = torch.full((B, T, S, W), float("nan"), dtype=torch.float64, device=device)
+    if timed:
+        state["win_age"] = torch.zeros((B, T, W), dtype=torch.int32, device=device)
     return state
 
 
@@ -1949,7 +1979,9 @@ def window_push(state, tab, assignment, status, track, T_WC, cam, cfg):
     -> {"n_views" [B,T] int32 (filled columns), "start" [B,T,12] float64 (the track pose bit for bit from cfg.min_views columns on, otherwise
         NaN)}.  One launch, no host sync.  With cfg.confidence set the launch is okp_window_push_weighted: state (window_state(..., prior=True))
     also holds "win_prior" [B,T,S,W], which gets the prior of every bearing pushed - from the fourth value of its table row - and NaN wherever
-    win_obs gets (NaN, NaN)."""
+    win_obs gets (NaN, NaN).  With cfg.motion set the launch is okp_window_push_timed: state (window_state(..., timed=True)) also holds "win_age"
+    [B,T,W] int32, stepped in place, and the dict gains "start_velocity" [B,T,3] float64 (the track's velocity bit for bit where "start" is the
+    track pose, otherwise NaN)."""
     if not isinstance(cfg, WindowConfig):
         raise OkpError("cfg must be an ops.WindowConfig")
     if not isinstance(cam, _lib.okp_camera):
@@ -1989,10 +2021,15 @@ def window_push(state, tab, assignment, status, track, T_WC, cam, cfg):
         if x.dtype != dtype or tuple(x.shape) != shape or x.device != dev or not x.is_contiguous():
             raise OkpError(f"state[{name!r}] must be a contiguous {dtype} tensor {list(shape)} on the table's device: window_state({b}, {t}, {s}, cfg.ticks = {w}, device)")
     win_prior = _win_prior(state, cfg, (b, t, s, w), dev, f"window_state({b}, {t}, {s}, cfg.ticks = {w}, device, prior=True)")
+    win_age = _win_age(state, cfg, (b, t, w), dev, f"window_state({b}, {t}, {s}, cfg.ticks = {w}, device, timed=True)")
     n_views = torch.empty((b, t), dtype=torch.int32, device=dev)
     start = torch.empty((b, t, 12), dtype=torch.float64, device=dev)
     inputs = (_cam_list(cam), tab.contiguous(), assignment.contiguous(), status.contiguous(), meas_of.contiguous(), track_i.contiguous(), track_f.contiguous(),
               track_pose.contiguous(), T_WC.contiguous(), cfg.min_views, cfg.max_speed)
+    if win_age is not None:
+        start_velocity = torch.empty((b, t, 3), dtype=torch.float64, device=dev)
+        _dispatch(_ops().window_push_timed, *inputs, win_obs, win_age, win_views, win_i, n_views, start, start_velocity, stream_int())
+        return {"n_views": n_views, "start": start, "start_velocity": start_velocity}
     if win_prior is not None:
         _dispatch(_ops().window_push_weighted, *inputs, cfg.confidence.ref, cfg.confidence.floor, win_obs, win_prior, win_views, win_i, n_views, start, stream_int())
     else:
@@ -2013,16 +2050,30 @@ def _win_prior(state, cfg, shape, dev, made_by):
     return x
 
 
+def _win_age(state, cfg, shape, dev, made_by):
+    """state["win_age"] of a window whose config has motion set, checked; None without the keyword."""
+    if getattr(cfg, "motion", None) is None:
+        return None
+    x = state.get("win_age") if isinstance(state, dict) else None
+    if x is None:
+        raise OkpError(f"state has no \"win_age\": cfg.motion is set, so the window keeps the age of its columns: {made_by}")
+    require_cuda(x, "win_age")
+    if x.dtype != torch.int32 or tuple(x.shape) != shape or x.device != dev or not x.is_contiguous():
+        raise OkpError(f"state['win_age'] must be a contiguous {torch.int32} tensor {list(shape)} on the window's device: {made_by}")
+    return x
+
+
 # ---- a rig's tracked objects refined against a sliding window of ticks x cameras (okp_window_push_views, okp_refine_pose_views_wide) ----------------
 REFINE_WIDE_MAX_VIEWS = 512                                                      # include/okp.h OKP_REFINE_WIDE_MAX_VIEWS
 
 
-def window_views_state(B, max_tracks, S, ticks, n_views, device, prior=False):
+def window_views_state(B, max_tracks, S, ticks, n_views, device, prior=False, timed=False):
     """An empty window of B streams x max_tracks slots x S model rows x ticks columns of n_views cameras each: {"win_obs" [B,T,S,W*V,2]
     float64, all NaN, "win_views" [B,T,W*V,14] float64 and "win_i" [B,T,4] int32 (owner id, head, filled, one spare), zeros} on `device` -
     window_push_views() steps it in place - plus what the refinement of the window reads next to it on every call: "win_assignment" [B,T,S]
     int32, the identity, and "win_n" [B] int32 filled with T.  prior=True (a WindowConfig with confidence): also "win_prior" [B,T,S,W*V] float64,
-    all NaN, the ring of the bearings' priors."""
+    all NaN, the ring of the bearings' priors.  timed=True (a WindowConfig with motion): also "win_age" [B,T,W*V] int32, zeros, the age in ticks
+    of every view's column."""
     B, T, S, W, V = int(B), int(max_tracks), int(S), int(ticks), int(n_views)
     if B < 1 or not 1 <= T <= TRACK_MAX_TRACKS or not 1 <= S <= POSE_MAX_POINTS or not 1 <= W <= REFINE_MAX_VIEWS or not 1 <= V <= 2 * RIG_MAX_PAIRS:
         raise OkpError(f"window_views_state: B = {B} streams (at least 1) of max_tracks = {T} slots (1 .. {TRACK_MAX_TRACKS}), S = {S} model rows (1 .. {POSE_MAX_POINTS}), "
@@ -2038,6 +2089,8 @@ def window_views_state(B, max_tracks, S, ticks, n_views, device, prior=False):
              "win_n": torch.full((B,), T, dtype=torch.int32, device=device)}
     if prior:
         state["win_prior"] = torch.full((B, T, S, W * V), float("nan"), dtype=torch.float64, device=device)
+    if timed:
+        state["win_age"] = torch.zeros((B, T, W * V), dtype=torch.int32, device=device)
     return state
 
 
@@ -2051,7 +2104,9 @@ def window_push_views(state, obs, assignment, status, track, T_WB, views, cfg, p
     -> {"n_views" [B,T] int32 (filled columns: ticks), "start" [B,T,12] float64 (the track pose bit for bit from cfg.min_views columns on,
         otherwise NaN)}.  One launch, no host sync.  With cfg.confidence set the launch is okp_window_push_views_weighted: prior
     [B,max_obj,S,V] float64 (rig_bearings_weighted's) is required and state (window_views_state(..., prior=True)) also holds "win_prior"
-    [B,T,S,W*V], into which the prior rows are copied alongside the bearing rows."""
+    [B,T,S,W*V], into which the prior rows are copied alongside the bearing rows.  With cfg.motion set the launch is okp_window_push_views_timed:
+    state (window_views_state(..., timed=True)) also holds "win_age" [B,T,W*V] int32, stepped in place, and the dict gains "start_velocity"
+    [B,T,3] float64."""
     if not isinstance(cfg, WindowConfig):
         raise OkpError("cfg must be an ops.WindowConfig")
     if (prior is None) != (cfg.confidence is None):
@@ -2094,6 +2149,7 @@ def window_push_views(state, obs, assignment, status, track, T_WB, views, cfg, p
             raise OkpError(f"state[{name!r}] must be a contiguous {dtype} tensor {list(shape)} on the bearings' device: "
                            f"window_views_state({b}, {t}, {s}, cfg.ticks = {w}, {v}, device)")
     win_prior = _win_prior(state, cfg, (b, t, s, w * v), dev, f"window_views_state({b}, {t}, {s}, cfg.ticks = {w}, {v}, device, prior=True)")
+    win_age = _win_age(state, cfg, (b, t, w * v), dev, f"window_views_state({b}, {t}, {s}, cfg.ticks = {w}, {v}, device, timed=True)")
     if prior is not None:
         require_cuda(prior, "prior")
         if prior.dtype != torch.float64 or tuple(prior.shape) != (b, max_obj, s, v) or prior.device != dev:
@@ -2102,6 +2158,10 @@ def window_push_views(state, obs, assignment, status, track, T_WB, views, cfg, p
     start = torch.empty((b, t, 12), dtype=torch.float64, device=dev)
     inputs = (assignment.contiguous(), status.contiguous(), meas_of.contiguous(), track_i.contiguous(), track_f.contiguous(), track_pose.contiguous(),
               T_WB.contiguous(), views.contiguous(), w, cfg.min_views, cfg.max_speed)
+    if win_age is not None:
+        start_velocity = torch.empty((b, t, 3), dtype=torch.float64, device=dev)
+        _dispatch(_ops().window_push_views_timed, obs.contiguous(), *inputs, win_obs, win_age, win_views, win_i, n_views, start, start_velocity, stream_int())
+        return {"n_views": n_views, "start": start, "start_velocity": start_velocity}
     if win_prior is not None:
         _dispatch(_ops().window_push_views_weighted, obs.contiguous(), prior.contiguous(), *inputs, win_obs, win_prior, win_views, win_i, n_views, start, stream_int())
     else:
@@ -2147,6 +2207,46 @@ def refine_pose_views_weighted(obs, prior, views, pose, n_obj, model, cfg, each=
     _dispatch(_ops().refine_pose_views_weighted_wide if wide else _ops().refine_pose_views_weighted, obs.contiguous(), prior.contiguous(), views.contiguous(), 1 if each else 0, fitted.contiguous(),
               assignment.contiguous(), n_obj.reshape(b).contiguous(), model.contiguous(), cfg.sigma_px, huber_px if huber_px is not None else 0.0, cfg.iters,
               cfg.damping, out["pose"], out["fit"], out["n_obs"], out.get("n_inlier"), out.get("weight"), out["information"], out["status"], stream_int())
+    return out
+
+
+def refine_motion_views(obs, views, age, start, n_obj, model, cfg, dt):
+    """The window refinement of a MOVING object (okp_refine_motion_views; the model, the solve, the statuses and the outputs are specified in
+    include/okp.h): every object's pose at age 0 and its linear velocity in the table's frame, nine unknowns, against bearings whose views
+    carry an age.  obs [B,max_obj,S,V,2] float64 and views [B,max_obj,V,14] float64 (device), one table per object, as refine_pose_views_each
+    takes them - the "win_obs" and "win_views" of a window's state -; age [B,max_obj,V] int32 (device), the age of every view in ticks - its
+    "win_age"; start: a dict with "pose" [B,max_obj,12] float64, "velocity" [B,max_obj,3] float64 (metres per second) and "assignment"
+    [B,max_obj,S] int32; n_obj int32 [B]; model [S,3] float64; cfg: a WindowConfig with motion set (sigma_px, iters, damping and horizon are
+    read); dt: seconds per tick, positive and finite
+    -> {"pose" [B,max_obj,12] and "velocity" [B,max_obj,3] float64 (the inputs bit for bit where the status is not 0), "fit" [B,max_obj,2]
+        float64, "n_obs" [B,max_obj] int32 (bearings inside the horizon), "information" [B,max_obj,81] float64 (H at the result, 9 x 9 over
+        (rotation, translation, velocity); NaN where the status is not 0), "status" [B,max_obj] int32}.  One launch, no host sync."""
+    if not isinstance(cfg, WindowConfig) or cfg.motion is None:
+        raise OkpError("cfg must be an ops.WindowConfig with motion set (motion=\"constant_velocity\")")
+    if isinstance(dt, (bool, np.bool_)):
+        raise OkpError(f"dt = {dt!r} is not a number (seconds per tick)")
+    try:
+        step = float(dt)
+    except (TypeError, ValueError):
+        raise OkpError(f"dt = {dt!r} is not a number (seconds per tick)") from None
+    if not (step > 0.0 and np.isfinite(step)):
+        raise OkpError(f"dt = {dt!r} must be positive and finite (seconds per tick)")
+    try:
+        velocity = start["velocity"]
+    except (TypeError, KeyError, IndexError):
+        raise OkpError("start must be a dict with \"pose\", \"velocity\" and \"assignment\" (a timed window_push's start and start_velocity)") from None
+    fitted, assignment, b, max_obj, s, v, dev = _views_inputs(True, obs, views, start, n_obj, model, cfg, WindowConfig, "an ops.WindowConfig with motion set",
+                                                              REFINE_MAX_VIEWS, "the win_obs of a timed window's state", "", motion=True)
+    for name, x, dtype, shape in (("age", age, torch.int32, (b, max_obj, v)), ("velocity", velocity, torch.float64, (b, max_obj, 3))):
+        require_cuda(x, name)
+        if x.dtype != dtype or tuple(x.shape) != shape or x.device != dev:
+            raise OkpError(f"{name} must be a {dtype} tensor {list(shape)} on the bearings' device")
+    out = {"pose": torch.empty((b, max_obj, 12), dtype=torch.float64, device=dev), "velocity": torch.empty((b, max_obj, 3), dtype=torch.float64, device=dev),
+           "fit": torch.empty((b, max_obj, 2), dtype=torch.float64, device=dev), "n_obs": torch.empty((b, max_obj), dtype=torch.int32, device=dev),
+           "information": torch.empty((b, max_obj, 81), dtype=torch.float64, device=dev), "status": torch.empty((b, max_obj), dtype=torch.int32, device=dev)}
+    _dispatch(_ops().refine_motion_views, obs.contiguous(), views.contiguous(), age.contiguous(), fitted.contiguous(), velocity.contiguous(), assignment.contiguous(),
+              n_obj.reshape(b).contiguous(), model.contiguous(), cfg.sigma_px, step, cfg.horizon, cfg.iters, cfg.damping, out["pose"], out["velocity"], out["fit"],
+              out["n_obs"], out["information"], out["status"], stream_int())
     return out
 
 

@@ -611,6 +611,8 @@ def _track_fields(track, n, window=None):
             fields.update(window_n_inlier=window["n_inlier"][n], window_weight=window["weight"][n])
         if "prior" in window:                    # weighted by the confidences (WindowConfig.confidence): "window_prior" [T,S,W] ([T,S,W*V] for a rig)
             fields.update(window_prior=window["prior"][n])
+        if "velocity" in window:                 # a moving object (WindowConfig.motion): "window_velocity" [T,3], and "window_information" is [T,81]
+            fields.update(window_velocity=window["velocity"][n])
     return fields
 
 
@@ -635,7 +637,10 @@ def _window_entries(rec, slot, key='T_CO_window', cameras=None):
     fit = rec["window_fit"][slot]
     entries = {'T_WO_window': _track_transform(rec["window_pose"][slot]) if ok else None, key: _track_transform(rec["window_pose_C"][slot]) if ok else None,
                'window_views': int(rec["window_n_views"][slot]), 'window_rmse': (float(fit[0]), float(fit[1])),
-               'window_information': rec["window_information"][slot].reshape(6, 6).copy(), 'window_status': int(rec["window_status"][slot])}
+               'window_information': rec["window_information"][slot].reshape(*((9, 9) if "window_velocity" in rec else (6, 6))).copy(),
+               'window_status': int(rec["window_status"][slot])}
+    if "window_velocity" in rec:             # WindowConfig.motion: the object's linear velocity in the world frame, metres per second; the information is 9 x 9
+        entries.update(window_velocity=rec["window_velocity"][slot].copy() if ok else None)
     if "window_n_inlier" in rec:
         outliers = _outliers(rec["window_weight"][slot])
         if cameras is not None:
@@ -796,8 +801,8 @@ class _Window:
     """The device state of a pipeline's sliding window, one ops.window_state per (device, streams), created on first use and kept for the
     pipeline's life like the tracker's: captured steps hold these very tensors, so reset() empties them in place."""
 
-    def __init__(self, cfg, max_tracks):
-        self.cfg, self.max_tracks, self.states = cfg, max_tracks, {}
+    def __init__(self, cfg, max_tracks, dt=None):
+        self.cfg, self.max_tracks, self.states, self.dt = cfg, max_tracks, {}, dt      # dt: the tracker's seconds per tick, what an age is counted in
 
     def state(self, device, streams, rows):
         st = self.states.get((device, streams))
@@ -806,14 +811,27 @@ class _Window:
         return st
 
     def _prior(self):
-        """The keyword that gives the state its ring of priors - only under cfg.confidence: without it the call is the one it was."""
-        return {"prior": True} if self.cfg.confidence is not None else {}
+        """The keyword that gives the state its ring of priors - only under cfg.confidence - or the ages of its columns - only under cfg.motion:
+        without either the call is the one it was."""
+        return {"prior": True} if self.cfg.confidence is not None else {"timed": True} if self.cfg.motion is not None else {}
+
+    def _moving(self, st, pushed, model, T, pose_key):
+        """cfg.motion: ops.refine_motion_views on the timed state from the pushed start and start velocity, and the refined poses back in the
+        frame of T -> the entries of the step's "window" dict: "velocity" and "win_age" more, "information" [.., 81]."""
+        start = {"pose": pushed["start"], "velocity": pushed["start_velocity"], "assignment": st["win_assignment"]}
+        refined = ops.refine_motion_views(st["win_obs"], st["win_views"], st["win_age"], start, st["win_n"], model, self.cfg, self.dt)
+        local = ops.change_frame(T, poses=refined["pose"], inverse=True)["poses"]
+        return {"pose": refined["pose"], "fit": refined["fit"], "n_obs": refined["n_obs"], "n_views": pushed["n_views"], "information": refined["information"],
+                "status": refined["status"], pose_key: local, "velocity": refined["velocity"], "win_obs": st["win_obs"], "win_views": st["win_views"],
+                "win_i": st["win_i"], "win_age": st["win_age"]}
 
     def step(self, tab, assignment, status, track, T_WC, cam, model):
         """ops.window_push on the state of the table's device and streams, ops.refine_pose_views_each on that state from the pushed start, and
         the refined poses back in the camera frame -> the entries of the step's "window" dict."""
         st = self.state(tab.device, int(tab.shape[0]), int(tab.shape[2]))
         pushed = ops.window_push(st, tab, assignment, status, track, T_WC, cam, self.cfg)
+        if self.cfg.motion is not None:
+            return self._moving(st, pushed, model, T_WC, "pose_C")
         start = {"pose": pushed["start"], "assignment": st["win_assignment"]}
         if self.cfg.confidence is not None:      # the push kept the ring of priors: the weighted refinement, one launch as well
             refined = ops.refine_pose_views_weighted(st["win_obs"], st["win_prior"], st["win_views"], start, st["win_n"], model, self.cfg, each=True)
@@ -835,14 +853,16 @@ class _Window:
             st["win_i"].zero_()
             if "win_prior" in st:
                 st["win_prior"].fill_(float("nan"))
+            if "win_age" in st:
+                st["win_age"].zero_()
 
 
 class _RigWindow(_Window):
     """_Window for a rig: a ring column holds the tick's bearings in all `cameras` cameras (ops.window_views_state, ops.window_push_views) and
     the refinement is the one beyond one wave (ops.refine_pose_views_wide, a views table per track)."""
 
-    def __init__(self, cfg, max_tracks, cameras):
-        super().__init__(cfg, max_tracks)
+    def __init__(self, cfg, max_tracks, cameras, dt=None):
+        super().__init__(cfg, max_tracks, dt)
         self.cameras = cameras
 
     def state(self, device, streams, rows):
@@ -856,6 +876,10 @@ class _RigWindow(_Window):
         start, and the refined poses back in the rig frame -> the entries of the tick's "window" dict."""
         st = self.state(obs.device, int(obs.shape[0]), int(obs.shape[2]))
         pushed = ops.window_push_views(st, obs, assignment, status, track, T_WB, views, self.cfg, **({"prior": prior} if prior is not None else {}))
+        if self.cfg.motion is not None:
+            out = self._moving(st, pushed, model, T_WB, "pose_B")
+            out["tick_obs"] = obs
+            return out
         start = {"pose": pushed["start"], "assignment": st["win_assignment"]}
         if self.cfg.confidence is not None:      # the push kept the ring of priors: the weighted refinement, one launch as well
             refined = ops.refine_pose_views_weighted(st["win_obs"], st["win_prior"], st["win_views"], start, st["win_n"], model, self.cfg, each=True, wide=True)
@@ -957,7 +981,11 @@ class _ObjectStage:
                     raise OkpError(f"{name} without {why}")
         self.window = None
         if window is not None:
-            self.window = _RigWindow(window, track.max_tracks, rig_cameras) if rig_cameras else _Window(window, track.max_tracks)
+            if window.motion is not None and rig_cameras * window.ticks > ops.REFINE_MAX_VIEWS:
+                raise OkpNotOffered(f"{name}: motion with 2 x {rig_cameras // 2} pairs x {window.ticks} ticks = {rig_cameras * window.ticks} views exceeds the "
+                                        f"{ops.REFINE_MAX_VIEWS} of okp_refine_motion_views (the wide motion kernel is a follow-up)")
+            moving = {"dt": track.dt} if window.motion is not None else {}
+            self.window = _RigWindow(window, track.max_tracks, rig_cameras, **moving) if rig_cameras else _Window(window, track.max_tracks, **moving)
         # a rig's one launch of the bearings serves the refinement and the window: the priors it writes follow one ConfidenceWeights
         given = [c for c in (getattr(refine, "confidence", None), getattr(window, "confidence", None) if rig_cameras else None) if c is not None]
         if len(given) == 2 and (given[0].ref, given[0].floor) != (given[1].ref, given[1].floor):
@@ -1045,7 +1073,7 @@ class _ObjectStage:
         if "track" in static_out:
             step._track_state = [static_out["track"][k] for k in ("track_f", "track_i", "next_id")]
             if "window" in static_out:
-                step._window_state = [static_out["window"][k] for k in ("win_obs", "win_views", "win_i", "prior") if k in static_out["window"]]
+                step._window_state = [static_out["window"][k] for k in ("win_obs", "win_views", "win_i", "prior", "win_age") if k in static_out["window"]]
             self.reset_tracks()
 
 
