@@ -58,7 +58,8 @@ extern "C" {
                                     peaks' confidences);
                                     okp_window_push_timed, okp_window_push_views_timed, okp_refine_motion_views (the window refinement of a
                                     moving object: a ring that knows how old its columns are, a pose and a linear velocity);
-                                    okp_score_objects, OKP_SCORE_* (key-point and pose accuracy of labelled scenes, tabulated on the device) */
+                                    okp_score_objects, OKP_SCORE_* (key-point and pose accuracy of labelled scenes, tabulated on the device);
+                                    okp_preprocess_raw8, OKP_CFA_* (8-bit Bayer mosaics and mono8 camera frames straight into the network) */
 
 /* OKP_F16: IEEE half activations / weights, fp32 accumulate (BASELINE configs[4]).
  * OKP_F32X3 (okp_conv plans only): fp32 activations, weights and results like OKP_F32 - every tensor argument of such a plan is an
@@ -315,6 +316,31 @@ int okp_preprocess_yuv420(int dtype, const uint8_t* frames_dev, int32_t n, int32
                           int32_t layout, int32_t matrix, int32_t full_range, int32_t resized_h, int32_t resized_w,
                           int32_t crop_y, int32_t crop_x, int32_t h, int32_t w, const float* mean3, const float* std3,
                           void* out_dev, int32_t out_w, void* stream);
+
+/* The same pre-processing from what a machine-vision camera delivers: an 8-bit Bayer mosaic or mono8, one byte per pixel (the
+ * reference has the host demosaic such frames: scripts/encode_bag.py, imgmsg_to_cv2(..., desired_encoding='rgb8')).  A frame is
+ * src_h rows of src_w samples M[y][x], rows src_pitch >= src_w bytes apart, frames src_frame_stride >= (src_h-1)*src_pitch + src_w
+ * bytes apart; the bytes between src_w and the pitch are never read.
+ * `cfa` names the colours of pixels (0,0), (0,1), (1,0), (1,1) (the sensor_msgs convention):
+ *   OKP_CFA_RGGB  R G / G B     OKP_CFA_BGGR  B G / G R     OKP_CFA_GRBG  G R / B G     OKP_CFA_GBRG  G B / R G
+ * and the colour of (y, x) is that of (y & 1, x & 1); Bayer frames have even src_h >= 2 and src_w >= 2.  A view that starts at an
+ * odd row or column of a larger mosaic has another pattern: the caller names it.
+ * A neighbour outside the frame is the mirror image without repeating the edge sample (index -1 -> 1, src_h -> src_h-2; columns
+ * alike), which keeps the neighbour's parity, so it is a sample of the colour the rule expects.
+ * Bilinear demosaic in integers, round half up (no clamp needed):
+ *   own colour                      M[y][x]
+ *   at an R or B site               G = (N + S + W + E + 2) >> 2;  the opposite colour = (NW + NE + SW + SE + 2) >> 2
+ *   at a G site                     the colour of its row's other sites = (W + E + 1) >> 1;  of its column's = (N + S + 1) >> 1
+ *   OKP_CFA_MONO                    R = G = B = M[y][x]; any src_h, src_w >= 1
+ * Each tap of the bilinear resize demosaics its own sample: the output equals okp_preprocess_u8 of the demosaiced frames, bit for
+ * bit; halo and fourth channel are zero.  Limits: bilinear only (no edge-directed demosaic); 8 bits only (no 10- or 12-bit packed
+ * mosaics); no white balance, gamma or colour matrix (a sensor's raw colours are not the sRGB the weights were trained on); parity
+ * with OpenCV's cvtColor(COLOR_Bayer*), whose pattern names differ from sensor_msgs', and with camera drivers' debayer is not
+ * pinned. */
+enum { OKP_CFA_RGGB = 0, OKP_CFA_BGGR = 1, OKP_CFA_GRBG = 2, OKP_CFA_GBRG = 3, OKP_CFA_MONO = 4 };
+int okp_preprocess_raw8(int dtype, const uint8_t* frames_dev, int32_t n, int32_t src_h, int32_t src_w, int32_t src_pitch,
+                        int64_t src_frame_stride, int32_t cfa, int32_t resized_h, int32_t resized_w, int32_t crop_y, int32_t crop_x,
+                        int32_t h, int32_t w, const float* mean3, const float* std3, void* out_dev, int32_t out_w, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * The 7x7 / stride-2 / pad-3 stem convolution 3 -> 128 + folded BatchNorm + ReLU in bf16 as its own kernel

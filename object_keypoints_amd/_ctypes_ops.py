@@ -244,6 +244,14 @@ def preprocess_yuv420(frames, layout, matrix, full_range, resized_h, resized_w, 
                "okp_preprocess_yuv420")
 
 
+def preprocess_raw8(frames, cfa, resized_h, resized_w, crop_y, crop_x, h, w, mean, std, out, stream):
+    n, sh, sw = frames.shape
+    pitch = frames.stride(1) if sh > 1 else sw
+    frame_stride = frames.stride(0) if n > 1 else sh * pitch
+    _lib.check(_lib.lib().okp_preprocess_raw8(_okp_dtype(out.dtype), frames.data_ptr(), n, sh, sw, pitch, frame_stride, cfa, resized_h, resized_w, crop_y, crop_x, h, w,
+                                              _floats3(mean), _floats3(std), out.data_ptr(), out.shape[2], stream), "okp_preprocess_raw8")
+
+
 # ---- peaks, geometry, grouping -------------------------------------------------------------------------------------------------------------
 def peak_nms(heat, cap, count, yx, xyc, stream):
     n, k, h, w = heat.shape

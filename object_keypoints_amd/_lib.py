@@ -15,6 +15,7 @@ OKP_ABI = 7
 CAM_EQUIDISTANT, CAM_RADTAN = 0, 1
 YUV_I420, YUV_NV12 = 0, 1
 YUV_BT601, YUV_BT709 = 0, 1
+CFA_RGGB, CFA_BGGR, CFA_GRBG, CFA_GBRG, CFA_MONO = 0, 1, 2, 3, 4
 ACT_NONE, ACT_RELU, ACT_SIGMOID = 0, 1, 2
 HEAD_MAX_OUT = 32
 
@@ -93,6 +94,8 @@ SIGNATURES = [
                                   POINTER(c_float), POINTER(c_float), c_void_p, c_int32, c_void_p]),
     ("okp_preprocess_yuv420", c_int, [c_int, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
                                       c_int32, c_int32, c_int32, POINTER(c_float), POINTER(c_float), c_void_p, c_int32, c_void_p]),
+    ("okp_preprocess_raw8", c_int, [c_int, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32,
+                                    c_int32, c_int32, POINTER(c_float), POINTER(c_float), c_void_p, c_int32, c_void_p]),
     ("okp_stem_create", c_void_p, [POINTER(c_float), POINTER(c_float)]),
     ("okp_stem_create_dtype", c_void_p, [c_int, POINTER(c_float), POINTER(c_float)]),
     ("okp_stem_destroy", None, [c_void_p]),

@@ -358,6 +358,89 @@ __global__ __launch_bounds__(256) void okp_preprocess_yuv420_kernel(const uint8_
   }
 }
 
+// ---- the same pre-processing from an 8-bit Bayer mosaic or mono8 (one byte per pixel) ----------------------------------------------------
+// Specification: include/okp.h, okp_preprocess_raw8.  The R site of the 2x2 cell sits at parity (ry, rx); with py = (y ^ ry) & 1,
+// px = (x ^ rx) & 1 a site is R (0,0), B (1,1), G in an R row (0,1) or G in a B row (1,0).  A thread's four taps are (sy0, sx0) and
+// its right, lower and lower-right neighbours; where resize_coeff clamped s1 to s0 the second tap's weight is 0, so the neighbour may
+// stand in for it.  The taps and their neighbours are the 4 x 4 block of rows sy0-1 .. sy0+2, columns sx0-1 .. sx0+2, each index
+// mirrored into the frame (-1 -> 1, size -> size-2); an index two past the edge belongs only to a weight-0 tap's neighbourhood and is
+// clamped so that the load stays inside the frame.  The block is read once; every tap forms all five candidates and selects by parity.
+struct RawParams {
+  int32_t pitch, ry, rx;
+  size_t frame_stride;
+};
+
+__device__ __forceinline__ int mirror_index(int i, int size) {
+  i = i < 0 ? -i : i;
+  i = i >= size ? 2 * size - 2 - i : i;
+  return i < 0 ? 0 : i;
+}
+
+template <typename T, bool MONO>
+__global__ __launch_bounds__(256) void okp_preprocess_raw8_kernel(const uint8_t* __restrict__ in, int N, ResizeParams rp, RawParams bp,
+                                                                   T* __restrict__ out, int OHt, int OWt) {
+  const long total = (long)N * OHt * OWt;
+  for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
+    const int x = (int)(idx % OWt);
+    const long t = idx / OWt;
+    const int y = (int)(t % OHt);
+    const int n = (int)(t / OHt);
+    const int cy = y - 3, cx = x - 3;               // position inside the cropped frame
+    float v[3] = {0.f, 0.f, 0.f};
+    if (cy >= 0 && cy < rp.H && cx >= 0 && cx < rp.W) {
+      int sy0, sy1, b0, b1, sx0, sx1, a0, a1;
+      resize_coeff(cy + rp.cropY, rp.scaleY, rp.srcH, sy0, sy1, b0, b1);
+      resize_coeff(cx + rp.cropX, rp.scaleX, rp.srcW, sx0, sx1, a0, a1);
+      const uint8_t* f = in + (size_t)n * bp.frame_stride;
+      if constexpr (MONO) {
+        const uint8_t* r0 = f + (size_t)sy0 * bp.pitch;
+        const uint8_t* r1 = f + (size_t)sy1 * bp.pitch;
+        const int h0 = (int)r0[sx0] * a0 + (int)r0[sx1] * a1;
+        const int h1 = (int)r1[sx0] * a0 + (int)r1[sx1] * a1;
+        const int u = resize_vertical(h0, h1, b0, b1);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) v[c] = normalise_u8(u, rp.np, c);
+      } else {
+        int m[4][4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const uint8_t* row = f + (size_t)mirror_index(sy0 - 1 + r, rp.srcH) * bp.pitch;
+#pragma unroll
+          for (int c = 0; c < 4; ++c) m[r][c] = (int)row[mirror_index(sx0 - 1 + c, rp.srcW)];
+        }
+        const int py0 = (sy0 ^ bp.ry) & 1, px0 = (sx0 ^ bp.rx) & 1;
+        int p[2][2][3];
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+          for (int j = 0; j < 2; ++j) {
+            const int r = 1 + i, c = 1 + j;
+            const int py = py0 ^ i, px = px0 ^ j;
+            const int own = m[r][c];
+            const int cross = (m[r - 1][c] + m[r + 1][c] + m[r][c - 1] + m[r][c + 1] + 2) >> 2;
+            const int diag = (m[r - 1][c - 1] + m[r - 1][c + 1] + m[r + 1][c - 1] + m[r + 1][c + 1] + 2) >> 2;
+            const int horiz = (m[r][c - 1] + m[r][c + 1] + 1) >> 1;
+            const int vert = (m[r - 1][c] + m[r + 1][c] + 1) >> 1;
+            const bool green = py != px;
+            const int rowc = green ? horiz : own;       // the colour of this row's non-green sites: R in an R row (py == 0), B in a B row
+            const int colc = green ? vert : diag;       // the colour of the neighbouring rows' non-green sites
+            p[i][j][0] = py ? colc : rowc;
+            p[i][j][1] = green ? own : cross;
+            p[i][j][2] = py ? rowc : colc;
+          }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          const int h0 = p[0][0][c] * a0 + p[0][1][c] * a1;
+          const int h1 = p[1][0][c] * a0 + p[1][1][c] * a1;
+          v[c] = normalise_u8(resize_vertical(h0, h1, b0, b1), rp.np, c);
+        }
+      }
+    }
+    T* o = out + idx * 4;
+    o[0] = (T)v[0]; o[1] = (T)v[1]; o[2] = (T)v[2]; o[3] = (T)0.f;
+  }
+}
+
 struct HeadParams {
   const void* src; int32_t src_ps;
   int32_t N, HW, n_out;
@@ -630,6 +713,55 @@ extern "C" int okp_preprocess_yuv420(int dtype, const uint8_t* frames, int32_t n
   else if (dtype == OKP_F16) launch_yuv420<_Float16>(layout, grid, (hipStream_t)stream, frames, n, rp, yp, out, h + 6, out_w);
   else launch_yuv420<float>(layout, grid, (hipStream_t)stream, frames, n, rp, yp, out, h + 6, out_w);
   return okp_check_hip(hipGetLastError(), "okp_preprocess_yuv420 launch");
+}
+
+namespace {
+template <typename T>
+void launch_raw8(bool mono, int grid, hipStream_t stream, const uint8_t* frames, int n, const ResizeParams& rp, const RawParams& bp, void* out,
+                 int OHt, int OWt) {
+  if (mono) hipLaunchKernelGGL((okp_preprocess_raw8_kernel<T, true>), dim3(grid), dim3(256), 0, stream, frames, n, rp, bp, (T*)out, OHt, OWt);
+  else hipLaunchKernelGGL((okp_preprocess_raw8_kernel<T, false>), dim3(grid), dim3(256), 0, stream, frames, n, rp, bp, (T*)out, OHt, OWt);
+}
+}  // namespace
+
+extern "C" int okp_preprocess_raw8(int dtype, const uint8_t* frames, int32_t n, int32_t src_h, int32_t src_w, int32_t src_pitch,
+                                   int64_t src_frame_stride, int32_t cfa, int32_t resized_h, int32_t resized_w, int32_t crop_y, int32_t crop_x,
+                                   int32_t h, int32_t w, const float* mean3, const float* std3, void* out, int32_t out_w, void* stream) {
+  if (!frames || !out || !mean3 || !std3) { okp_set_error("okp_preprocess_raw8: null argument"); return OKP_EINVAL; }
+  if (dtype != OKP_F32 && !okp_is16(dtype)) { okp_set_error("okp_preprocess_raw8: bad dtype %d", dtype); return OKP_EINVAL; }
+  if (cfa < OKP_CFA_RGGB || cfa > OKP_CFA_MONO) { okp_set_error("okp_preprocess_raw8: unknown cfa %d", cfa); return OKP_EINVAL; }
+  const bool mono = cfa == OKP_CFA_MONO;
+  if (n < 1 || src_h < 1 || src_w < 1) { okp_set_error("okp_preprocess_raw8: %d frames of %dx%d", n, src_h, src_w); return OKP_EINVAL; }
+  if (!mono && (src_h < 2 || src_w < 2 || (src_h & 1) || (src_w & 1))) {
+    okp_set_error("okp_preprocess_raw8: %d frames of %dx%d: Bayer frames have an even height and width", n, src_h, src_w);
+    return OKP_EINVAL;
+  }
+  if (src_pitch < src_w) { okp_set_error("okp_preprocess_raw8: pitch %d is below the width %d", src_pitch, src_w); return OKP_EINVAL; }
+  const int64_t frame_span = (int64_t)(src_h - 1) * src_pitch + src_w;
+  if (src_frame_stride < frame_span) {
+    okp_set_error("okp_preprocess_raw8: frame stride %lld is below (src_h-1)*pitch + src_w = %lld", (long long)src_frame_stride, (long long)frame_span);
+    return OKP_EINVAL;
+  }
+  if (resized_h < 1 || resized_w < 1 || h < 1 || w < 1 || crop_y < 0 || crop_x < 0 || crop_y + h > resized_h || crop_x + w > resized_w) {
+    okp_set_error("okp_preprocess_raw8: crop %dx%d at (%d,%d) does not fit the resized frame %dx%d", h, w, crop_y, crop_x, resized_h, resized_w);
+    return OKP_EINVAL;
+  }
+  if (out_w < w + 6) { okp_set_error("okp_preprocess_raw8: out_w %d < w+6", out_w); return OKP_EINVAL; }
+  ResizeParams rp;
+  rp.srcH = src_h; rp.srcW = src_w; rp.rsH = resized_h; rp.rsW = resized_w; rp.cropY = crop_y; rp.cropX = crop_x; rp.H = h; rp.W = w;
+  rp.scaleY = 1.0 / ((double)resized_h / (double)src_h);
+  rp.scaleX = 1.0 / ((double)resized_w / (double)src_w);
+  for (int c = 0; c < 3; ++c) { rp.np.mean[c] = mean3[c]; rp.np.stdv[c] = std3[c]; }
+  RawParams bp;
+  bp.pitch = src_pitch; bp.frame_stride = (size_t)src_frame_stride;
+  bp.ry = (cfa == OKP_CFA_BGGR || cfa == OKP_CFA_GBRG) ? 1 : 0;       // the parity of the R site's row and column
+  bp.rx = (cfa == OKP_CFA_BGGR || cfa == OKP_CFA_GRBG) ? 1 : 0;
+  const long total = (long)n * (h + 6) * out_w;
+  const int grid = grid_for(total, 256);
+  if (dtype == OKP_BF16) launch_raw8<__bf16>(mono, grid, (hipStream_t)stream, frames, n, rp, bp, out, h + 6, out_w);
+  else if (dtype == OKP_F16) launch_raw8<_Float16>(mono, grid, (hipStream_t)stream, frames, n, rp, bp, out, h + 6, out_w);
+  else launch_raw8<float>(mono, grid, (hipStream_t)stream, frames, n, rp, bp, out, h + 6, out_w);
+  return okp_check_hip(hipGetLastError(), "okp_preprocess_raw8 launch");
 }
 
 extern "C" int okp_head_out_forward(int dtype, const okp_head_out_args* a, void* stream) {

@@ -389,6 +389,27 @@ void preprocess_yuv420(const Tensor& frames, int64_t layout, int64_t matrix, boo
            "okp_preprocess_yuv420");
 }
 
+// frames: uint8 [N, H, W] with stride(2) == 1, pitch = stride(1), frames stride(0) bytes apart (a view [..., :W] of pitched camera buffers
+// needs no copy); the stride of a dimension of size 1 says nothing and is replaced by the packed one
+void preprocess_raw8(const Tensor& frames, int64_t cfa, int64_t resized_h, int64_t resized_w, int64_t crop_y, int64_t crop_x, int64_t h, int64_t w,
+                     at::ArrayRef<double> mean, at::ArrayRef<double> std_, const Tensor& out, int64_t stream) {
+  TORCH_CHECK(frames.is_cuda(), "okp: frames must be a device tensor: the HIP path has no CPU fallback");
+  TORCH_CHECK(frames.scalar_type() == at::kByte && frames.dim() == 3 && frames.size(0) >= 1 && frames.size(1) >= 1 && frames.size(2) >= 1 &&
+              (frames.size(2) == 1 || frames.stride(2) == 1), "okp: frames must be uint8 [N, H, W] with unit inner stride");
+  const int64_t n = frames.size(0), sh = frames.size(1), sw = frames.size(2);
+  const int64_t pitch = sh > 1 ? frames.stride(1) : sw;
+  const int64_t frame_stride = n > 1 ? frames.stride(0) : sh * pitch;
+  TORCH_CHECK(pitch >= sw && pitch <= INT32_MAX && frame_stride >= (sh - 1) * pitch + sw, "okp: frames must have pitch (stride(1)) >= W and lie "
+              "stride(0) >= (H-1) * pitch + W bytes apart");
+  TORCH_CHECK(out.is_cuda() && out.dim() == 4 && out.is_contiguous() && out.size(0) == n && out.size(1) == h + 6 && out.size(3) == 4,
+              "okp: frames [N,H,W] uint8 -> out [N,h+6,wp,4]");
+  float m[3], sd[3]; three(mean, m, "mean"); three(std_, sd, "std");
+  check_rc(okp_preprocess_raw8(dtype_of(out), frames.data_ptr<uint8_t>(), (int32_t)n, (int32_t)sh, (int32_t)sw, (int32_t)pitch, frame_stride, (int32_t)cfa,
+                               (int32_t)resized_h, (int32_t)resized_w, (int32_t)crop_y, (int32_t)crop_x, (int32_t)h, (int32_t)w, m, sd, out.data_ptr(),
+                               (int32_t)out.size(2), sp(stream)),
+           "okp_preprocess_raw8");
+}
+
 inline int32_t* flag_ptr(const optional<Tensor>& f) {
   if (!f.has_value()) return nullptr;
   TORCH_CHECK(f->is_cuda() && f->scalar_type() == at::kInt && f->numel() >= 1, "okp: range_flag is an int32 device tensor");
@@ -1361,6 +1382,8 @@ TORCH_LIBRARY(okp, m) {
   m.def("preprocess_u8(Tensor frames, int resized_h, int resized_w, int crop_y, int crop_x, int h, int w, float[] mean, float[] std, Tensor(a!) out, int stream) -> ()", preprocess_u8);
   m.def("preprocess_yuv420(Tensor frames, int layout, int matrix, bool full_range, int resized_h, int resized_w, int crop_y, int crop_x, int h, int w, "
         "float[] mean, float[] std, Tensor(a!) out, int stream) -> ()", preprocess_yuv420);
+  m.def("preprocess_raw8(Tensor frames, int cfa, int resized_h, int resized_w, int crop_y, int crop_x, int h, int w, float[] mean, float[] std, "
+        "Tensor(a!) out, int stream) -> ()", preprocess_raw8);
   m.def("cast(Tensor src, Tensor(a!) dst, int stream, Tensor(b!)? range_flag=None) -> ()", cast);
   m.def("add_f16_f32(Tensor a, Tensor b, Tensor(a!) out, int act, int stream, Tensor(b!)? range_flag=None) -> ()", add_f16_f32);
   m.def("dwconv3x3_forward(Tensor src, int src_c0, int c, int conv_stride, Tensor w, Tensor bias, Tensor? res, int res_c0, Tensor(a!) out, int out_c0, int act, int stream) -> ()", dwconv3x3_forward);

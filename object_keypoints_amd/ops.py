@@ -717,6 +717,75 @@ def preprocess_yuv420(frames, dtype, fmt, size=511, mean=RGB_MEAN, std=RGB_STD):
     return _packed(out, size, size)
 
 
+_CFA_PATTERNS = {"rggb": _lib.CFA_RGGB, "bggr": _lib.CFA_BGGR, "grbg": _lib.CFA_GRBG, "gbrg": _lib.CFA_GBRG}
+
+
+@dataclasses.dataclass(frozen=True)
+class BayerFormat:
+    """An 8-bit Bayer mosaic, one byte per pixel (include/okp.h, okp_preprocess_raw8): `pattern` names the colours of pixels (0,0), (0,1),
+    (1,0), (1,1) as sensor_msgs does ("rggb", "bggr", "grbg", "gbrg": bayer_rggb8 and its siblings).  Frames are [N, H, W] uint8 with even
+    H and W.  A view that starts at an odd row or column of a larger mosaic has another pattern (an odd column of "rggb" is "grbg", an odd
+    row "gbrg", both "bggr"): that is the caller's to name.  Bilinear demosaic only; no white balance, gamma or colour matrix."""
+    pattern: str = "rggb"
+
+    def __post_init__(self):
+        if not isinstance(self.pattern, str) or self.pattern not in _CFA_PATTERNS:
+            raise OkpError(f"unknown Bayer pattern {self.pattern!r}: 'rggb', 'bggr', 'grbg' or 'gbrg'")
+
+
+@dataclasses.dataclass(frozen=True)
+class Mono8Format:
+    """mono8 camera frames [N, H, W] uint8, any H, W >= 1: R = G = B = the sample (include/okp.h, okp_preprocess_raw8)."""
+
+
+def check_raw8_frames(frames, fmt):
+    """Shape, dtype and stride checks of Bayer / mono8 frames (no device work) -> (n, H, W, pitch, frame_stride), both strides in bytes.
+    pitch = stride(1) >= W and frame_stride = stride(0) >= (H-1) * pitch + W: a view buf[..., :W] of pitched buffers is taken as it is."""
+    if not isinstance(fmt, (BayerFormat, Mono8Format)):
+        raise OkpError(f"fmt must be a BayerFormat or a Mono8Format, not {type(fmt).__name__}")
+    if not isinstance(frames, torch.Tensor):
+        raise OkpError("frames must be a uint8 tensor [N, H, W]")
+    if frames.dtype != torch.uint8:
+        raise OkpError(f"raw camera frames are uint8, not {frames.dtype}")
+    if frames.dim() != 3:
+        raise OkpError(f"raw camera frames are [N, H, W] (3-D), not {frames.dim()}-D: RGB frames [N,H,W,3] go through preprocess_u8")
+    n, h, w = frames.shape
+    if n < 1 or h < 1 or w < 1:
+        raise OkpError(f"raw camera frames of shape {tuple(frames.shape)}: at least one frame of at least one sample")
+    if isinstance(fmt, BayerFormat) and (h % 2 or w % 2):
+        raise OkpError(f"Bayer frames of {h}x{w}: the height and width must be even")
+    if w > 1 and frames.stride(2) != 1:
+        raise OkpError(f"raw camera frames need a unit inner stride (stride(2) = {frames.stride(2)})")
+    pitch = frames.stride(1) if h > 1 else w              # (the stride of a dimension of size 1 says nothing)
+    if pitch < w:
+        raise OkpError(f"pitch (stride(1)) = {pitch} is below the width {w}")
+    span = (h - 1) * pitch + w
+    frame_stride = frames.stride(0) if n > 1 else h * pitch
+    if frame_stride < span:
+        raise OkpError(f"frames must be at least (H-1) * pitch + W = {span} bytes apart, not stride(0) = {frame_stride}")
+    if frames.untyped_storage().nbytes() < frames.storage_offset() + (n - 1) * frame_stride + span:
+        raise OkpError("the frames' storage ends before the last frame's last sample")
+    return n, h, w, pitch, frame_stride
+
+
+def preprocess_raw8(frames, dtype, fmt, size=511, mean=RGB_MEAN, std=RGB_STD):
+    """Raw camera frames uint8 [N, H, W] (device; a Bayer mosaic or mono8 as `fmt`, a BayerFormat or Mono8Format; pitch = stride(1) and
+    frame stride = stride(0), so a view [..., :W] of pitched buffers is taken as it is) -> the packed stem input that preprocess_u8 makes
+    of the same frames demosaiced to RGB, bit for bit (okp_preprocess_raw8: demosaic, resize, centre crop and normalisation in one kernel)."""
+    n, sh, sw, pitch, frame_stride = check_raw8_frames(frames, fmt)
+    rh, rw = smallest_max_size(sh, sw, size) if size >= 1 else (0, 0)
+    if size < 1 or rh < size or rw < size:
+        raise OkpError(f"the {size}x{size} crop does not fit the resized frame {rh}x{rw}")
+    okp_dtype(dtype)
+    require_cuda(frames, "frames")
+    cy, cx = (rh - size) // 2, (rw - size) // 2
+    cfa = _CFA_PATTERNS[fmt.pattern] if isinstance(fmt, BayerFormat) else _lib.CFA_MONO
+    wp = stem_packed_width(size)
+    out = torch.empty((n, size + 6, wp, 4), dtype=dtype, device=frames.device)
+    _dispatch(_ops().preprocess_raw8, frames, cfa, rh, rw, cy, cx, size, size, _f32_list(mean), _f32_list(std), out, stream_int())
+    return _packed(out, size, size)
+
+
 def head_out(src, outputs, w_dev, bias_dev):
     """outputs: list of (in_c_off, act, out_tensor[N,Cx,H,W] fp32, channel index)."""
     _refuse_pairs(src)

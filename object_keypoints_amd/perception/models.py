@@ -105,6 +105,9 @@ class KeypointNet(_HipModule):
         self.raw_frame_size = 511
         # ops.YUV420Format: a 3-D uint8 tensor [N, 3H/2, W] is taken as 4:2:0 decoder output (NV12 / I420) and converted to RGB on the
         # device by the same pre-processing kernel (ops.preprocess_yuv420, to raw_frame_size); None = 4:2:0 frames are refused.
+        # ops.BayerFormat / ops.Mono8Format: a 3-D uint8 tensor [N, H, W] is taken as a camera's 8-bit Bayer mosaic / mono8 frames and
+        # demosaiced on the device likewise (ops.preprocess_raw8).  A 3-D tensor is dispatched by the type of frame_format; a view that
+        # starts at an odd row or column of a larger mosaic has another pattern, which is the caller's to name.
         # 4-D uint8 frames are RGB either way.
         self.frame_format = frame_format
         # Split-product configurations halve fp32 values into fp16: a value beyond +-65504 has no halves (inf, -inf -> NaN products, which the
@@ -250,9 +253,10 @@ class KeypointNet(_HipModule):
         # split-product configuration: the last stack's `cnv` has one reader, the heads - in pair format where its 3x3 convolution can write
         # that, the three heads are one launch (ops.heads_fused; _run_heads_ looks at Act.pairs)
         cnv_pairs = bool(ops.FUSE_HEADS_X3 and self.mfma_split and self.features == 128)      # (the mixed configuration's heads are three-term plans too)
-        if x.dtype == torch.uint8 and x.dim() == 3:      # 4:2:0 [N,3H/2,W]: colour conversion fused into the pre-processing kernel too
+        if x.dtype == torch.uint8 and x.dim() == 3:      # 4:2:0 [N,3H/2,W], or a Bayer mosaic / mono8 [N,H,W]: colour conversion fused into the pre-processing kernel too
             self._frame_hw(x)
-            return self.backbone(ops.preprocess_yuv420(x, self.compute_dtype, self.frame_format, size=self.raw_frame_size), cnv_pairs=cnv_pairs)
+            raw = ops.preprocess_raw8 if isinstance(self.frame_format, (ops.BayerFormat, ops.Mono8Format)) else ops.preprocess_yuv420
+            return self.backbone(raw(x, self.compute_dtype, self.frame_format, size=self.raw_frame_size), cnv_pairs=cnv_pairs)
         if x.dtype == torch.uint8:      # raw RGB [N,H,W,3]: normalisation (and resize + centre crop) fused into the packing kernel
             if self.raw_frame_size is not None and tuple(x.shape[1:3]) != (self.raw_frame_size, self.raw_frame_size):
                 return self.backbone(ops.preprocess_u8(x, self.compute_dtype, size=self.raw_frame_size), cnv_pairs=cnv_pairs)
@@ -275,6 +279,8 @@ class KeypointNet(_HipModule):
             if self.frame_format is None:
                 raise OkpError("a 3-D uint8 tensor is 4:2:0 (YUV) frames [N, 3H/2, W]: set frame_format (ops.YUV420Format) to take them; "
                                "RGB frames are [N, H, W, 3]")
+            if self.raw_frame_size is None and isinstance(self.frame_format, (ops.BayerFormat, ops.Mono8Format)):
+                raise OkpError("Bayer and mono8 frames are resized and cropped to raw_frame_size: it cannot be None with frame_format set")
             if self.raw_frame_size is None:
                 raise OkpError("4:2:0 frames are resized and cropped to raw_frame_size: it cannot be None with frame_format set")
             return self.raw_frame_size, self.raw_frame_size

@@ -198,8 +198,9 @@ def load_keypoint_net(model, compute_dtype=torch.float32, device=None, audit_fra
     range (KeypointNet.on_overflow): raise OkpError, re-run the pass with the exact float32 kernels, or leave the flag to the caller.
     range_guard (KeypointNet.range_guard): True runs a torch.float16 network under the same guard (on_overflow then applies to it); None
     keeps each configuration's default (a KeypointNet passed in keeps its own).
-    frame_format (KeypointNet.frame_format, an ops.YUV420Format): take 3-D uint8 tensors as 4:2:0 decoder output (NV12 / I420); None
-    keeps a KeypointNet's own (a new one refuses them)."""
+    frame_format (KeypointNet.frame_format): an ops.YUV420Format takes 3-D uint8 tensors as 4:2:0 decoder output (NV12 / I420); an
+    ops.BayerFormat or ops.Mono8Format takes them as a camera's 8-bit Bayer mosaic / mono8 frames [N, H, W]; None keeps a KeypointNet's
+    own (a new one refuses them)."""
     device = device or _device()
     if on_overflow not in ("raise", "float32", "defer"):
         raise OkpError("on_overflow is 'raise', 'float32' or 'defer'")
@@ -263,7 +264,8 @@ class InferenceComponent:
         """on_overflow (split-product compute dtypes only): the reference's fp32 model returns numbers for any input; the drop-in does too -
         a pass whose activations leave the fp16 range is re-run with the exact float32 kernels ("float32", with a RuntimeWarning the first
         time) - unless the caller prefers an OkpError ("raise").  range_guard=True extends that to torch.float16 (KeypointNet.range_guard).
-        frame_format (an ops.YUV420Format): frames may be 4:2:0 decoder output [N, 3H/2, W] uint8 (KeypointNet.frame_format)."""
+        frame_format (KeypointNet.frame_format): an ops.YUV420Format - frames may be 4:2:0 decoder output [N, 3H/2, W] uint8; an
+        ops.BayerFormat or ops.Mono8Format - frames may be 8-bit Bayer mosaics / mono8 frames [N, H, W] uint8."""
         if not cuda:
             raise OkpError("InferenceComponent(cuda=False): this build has no CPU path (the CPU restatement is oracle/, test-only)")
         self.cuda = cuda
@@ -455,6 +457,8 @@ class ObjectKeypointPipeline:
 
 class LearnedKeypointTrackingPipeline(ObjectKeypointPipeline):
     def __init__(self, model, cuda=True, *args, **kwargs):
+        """Keywords of its own, handed to InferenceComponent: compute_dtype, on_overflow, range_guard and frame_format (an ops.YUV420Format,
+        ops.BayerFormat or ops.Mono8Format: the frames of __call__ may then be 4:2:0 [N, 3H/2, W] or Bayer / mono8 [N, H, W] uint8)."""
         compute_dtype = kwargs.pop("compute_dtype", torch.float32)
         on_overflow = kwargs.pop("on_overflow", "float32")
         range_guard = kwargs.pop("range_guard", None)
@@ -1163,6 +1167,8 @@ class BatchedKeypointPipeline(_ObjectStagePipeline):
     `points` is the fixed-capacity payload that is all-gathered across ranks (object_keypoints_amd.distributed).
     objects(...) groups one frame's peaks exactly as ObjectKeypointPipeline does, reusing the lifted points (surplus votes of a
     multi-instance type reduced by the device k-means of okp_group_objects).
+    `frames` are whatever the network takes: fp32 NCHW crops, raw RGB uint8 [N,H,W,3] or, with the network's frame_format set, 4:2:0
+    decoder output [N,3H/2,W] or 8-bit Bayer mosaics / mono8 frames [N,H,W] (KeypointNet.frame_format); eager and captured steps alike.
 
     Pose, refinement, world frame and tracking (all optional) end the device step, inside a captured step too: _ObjectStage describes the
     launches and the keys "pose", "refine", "world" and "track" they add to the step's dict, in the CAMERA frame of each frame.  Here:
@@ -1401,7 +1407,8 @@ class SceneScorer:
 
     score(frames, labels) -> {"loss" [], "heat" [S], "depth" [S], "center" [S] (the reference's 4-tuple, perception/loss.py:48, fp64),
     "terms" [N,S,3] fp64 per-frame sums, "mask_count" [N,K] int32, "range_overflow" 0-d int32 (non-zero: a guarded configuration left
-    the fp16 range in this pass - the score is not to be trusted; always 0 for float32 / bfloat16)}.  labels: SceneTargets.labels."""
+    the fp16 range in this pass - the score is not to be trusted; always 0 for float32 / bfloat16)}.  labels: SceneTargets.labels.
+    frames: whatever net.forward takes, 4:2:0, Bayer and mono8 frames of a network with a frame_format (KeypointNet.frame_format) included."""
 
     def __init__(self, net, keypoint_config, depth_weight=10.0, center_weight=1.0):
         from .loss import KeypointLoss
@@ -1447,7 +1454,9 @@ class HostFrameFeed:
     """Host -> HBM upload of camera frames on a COPY stream, double-buffered, so that the frames of tick t + 1 cross PCIe while tick t is
     computed (the reference feeds its model from a DataLoader on the host, one frame per call: scripts/eval_model.py:274-293; raw frames
     are 1280 x 720 uint8, perception/datasets/video.py:83-100).  Frames come as a pinned host tensor of the shape / dtype given at
-    construction (pin_memory() once, reuse it: the copy is only asynchronous from pinned memory).
+    construction (pin_memory() once, reuse it: the copy is only asynchronous from pinned memory): RGB [n, H, W, 3], 4:2:0 decoder output
+    [n, 3H/2, W], or a camera's 8-bit Bayer mosaic / mono8 frames [n, H, W] - a third of the RGB bytes - for a network whose
+    frame_format names them.
 
         feed = HostFrameFeed(host.shape, host.dtype)
         slot = feed.submit(host)                 # async H2D on the copy stream into the next free device buffer
@@ -1498,7 +1507,9 @@ class StereoStreamPipeline(_ObjectStagePipeline):
     tick(frames) -> list over pairs of {type k: (n_k, 3) float64 points in the left camera frame}, plus timing-free device work:
     three small device -> host copies per tick (peaks, undistorted peaks, 3D points).
     `frames`: fp32 NCHW crops [2P, 3, 511, 511] in HBM, or raw camera frames uint8 [2P, H, W, 3] (resized, cropped and normalised on the
-    device, okp_preprocess_u8).  Host-fed operation: stream(host_ticks) uploads the raw frames of tick t + 1 on a copy stream while tick t
+    device, okp_preprocess_u8), or - for a network whose frame_format names them - 4:2:0 decoder output [2P, 3H/2, W] or the cameras' 8-bit
+    Bayer mosaics / mono8 frames [2P, H, W] (okp_preprocess_yuv420, okp_preprocess_raw8); tick, tick_device, capture_device and stream take
+    all of them.  Host-fed operation: stream(host_ticks) uploads the raw frames of tick t + 1 on a copy stream while tick t
     is computed (HostFrameFeed) and yields the same results, bit for bit, as tick() on resident frames.
 
     stereo_camera: one StereoCamera, used for every pair of a tick of any size, or a RIG - a sequence of P StereoCameras, each pair
@@ -1654,8 +1665,8 @@ class StereoStreamPipeline(_ObjectStagePipeline):
         return self._graph
 
     def stream(self, host_ticks, heat_override=None, use_graph=False):
-        """host_ticks: an iterable of pinned host tensors, one per tick (all of one shape / dtype: raw uint8 [2P, H, W, 3] frames or fp32
-        [2P, 3, 511, 511] crops).  Generator of tick() results; the upload of the next tick overlaps the current one."""
+        """host_ticks: an iterable of pinned host tensors, one per tick (all of one shape / dtype: raw uint8 [2P, H, W, 3] frames, fp32
+        [2P, 3, 511, 511] crops or, with the network's frame_format set, 4:2:0 [2P, 3H/2, W] or Bayer / mono8 [2P, H, W] frames).  Generator of tick() results; the upload of the next tick overlaps the current one."""
         it = iter(host_ticks)
         try:
             first = next(it)
