@@ -424,21 +424,32 @@ def refine_pose_views_robust(obs, views, views_each, pose, assignment, n_obj, mo
 
 
 # ---- a sliding window of ticks' bearings per track (csrc/okp_window.hip): win_obs [B,T,S,W,2], win_views [B,T,W,14], win_i [B,T,4] ------------------
-def window_push(camera, tab, assignment, status, meas_of, track_i, track_f, track_pose, T_WC, min_views, max_speed, win_obs, win_views, win_i, n_views, start, stream):
+def _window_push(symbol, camera, tab, inputs, min_views, max_speed, extra, win_obs, ring, win_views, win_i, n_views, start, outputs, stream):
+    """The three single-camera pushes: `extra` are the scalars after max_speed, `ring` the state tensor after win_obs, `outputs` the ones after start."""
     b, max_obj, s, _ = tab.shape
-    _lib.check(_lib.lib().okp_window_push(tab.data_ptr(), assignment.data_ptr(), status.data_ptr(), meas_of.data_ptr(), track_i.data_ptr(), track_f.data_ptr(),
-                                          track_pose.data_ptr(), T_WC.data_ptr(), _camera(camera), b, max_obj, s, win_obs.shape[1], win_obs.shape[3], min_views, max_speed,
-                                          win_obs.data_ptr(), win_views.data_ptr(), win_i.data_ptr(), n_views.data_ptr(), start.data_ptr(), stream), "okp_window_push")
+    _lib.check(getattr(_lib.lib(), symbol)(tab.data_ptr(), *(t.data_ptr() for t in inputs), _camera(camera), b, max_obj, s, win_obs.shape[1], win_obs.shape[3], min_views,
+                                           max_speed, *extra, win_obs.data_ptr(), *(t.data_ptr() for t in ring), win_views.data_ptr(), win_i.data_ptr(), n_views.data_ptr(),
+                                           start.data_ptr(), *(t.data_ptr() for t in outputs), stream), symbol)
+
+
+def window_push(camera, tab, assignment, status, meas_of, track_i, track_f, track_pose, T_WC, min_views, max_speed, win_obs, win_views, win_i, n_views, start, stream):
+    _window_push("okp_window_push", camera, tab, (assignment, status, meas_of, track_i, track_f, track_pose, T_WC), min_views, max_speed, (), win_obs, (), win_views, win_i,
+                 n_views, start, (), stream)
 
 
 # ---- the sliding window of a rig (csrc/okp_window_views.hip, csrc/okp_refine_views_wide.hip): win_obs [B,T,S,W*V,2], win_views [B,T,W*V,14] --------
+def _window_push_views(symbol, obs, inputs, ticks, min_views, max_speed, win_obs, ring, win_views, win_i, n_views, start, outputs, stream):
+    """The three pushes of a rig: `inputs` are the tensors after obs (the weighted push's begin with the prior), `ring` and `outputs` as in _window_push."""
+    b, max_obj, s, v, _ = obs.shape
+    _lib.check(getattr(_lib.lib(), symbol)(obs.data_ptr(), *(t.data_ptr() for t in inputs), b, max_obj, s, win_obs.shape[1], ticks, v, min_views, max_speed,
+                                           win_obs.data_ptr(), *(t.data_ptr() for t in ring), win_views.data_ptr(), win_i.data_ptr(), n_views.data_ptr(), start.data_ptr(),
+                                           *(t.data_ptr() for t in outputs), stream), symbol)
+
+
 def window_push_views(obs, assignment, status, meas_of, track_i, track_f, track_pose, T_WB, views, ticks, min_views, max_speed, win_obs, win_views, win_i, n_views,
                       start, stream):
-    b, max_obj, s, v, _ = obs.shape
-    _lib.check(_lib.lib().okp_window_push_views(obs.data_ptr(), assignment.data_ptr(), status.data_ptr(), meas_of.data_ptr(), track_i.data_ptr(), track_f.data_ptr(),
-                                                track_pose.data_ptr(), T_WB.data_ptr(), views.data_ptr(), b, max_obj, s, win_obs.shape[1], ticks, v, min_views, max_speed,
-                                                win_obs.data_ptr(), win_views.data_ptr(), win_i.data_ptr(), n_views.data_ptr(), start.data_ptr(), stream),
-               "okp_window_push_views")
+    _window_push_views("okp_window_push_views", obs, (assignment, status, meas_of, track_i, track_f, track_pose, T_WB, views), ticks, min_views, max_speed, win_obs, (),
+                       win_views, win_i, n_views, start, (), stream)
 
 
 def refine_pose_views_wide(obs, views, views_each, pose, assignment, n_obj, model, sigma_px, huber_px, iters, damping, pose_out, fit, n_obs, n_inlier, weight,
@@ -478,40 +489,27 @@ def refine_pose_views_weighted_wide(obs, prior, views, views_each, pose, assignm
 
 def window_push_weighted(camera, tab, assignment, status, meas_of, track_i, track_f, track_pose, T_WC, min_views, max_speed, conf_ref, conf_floor, win_obs,
                          win_prior, win_views, win_i, n_views, start, stream):
-    b, max_obj, s, _ = tab.shape
-    _lib.check(_lib.lib().okp_window_push_weighted(tab.data_ptr(), assignment.data_ptr(), status.data_ptr(), meas_of.data_ptr(), track_i.data_ptr(),
-                                                   track_f.data_ptr(), track_pose.data_ptr(), T_WC.data_ptr(), _camera(camera), b, max_obj, s, win_obs.shape[1],
-                                                   win_obs.shape[3], min_views, max_speed, conf_ref, conf_floor, win_obs.data_ptr(), win_prior.data_ptr(),
-                                                   win_views.data_ptr(), win_i.data_ptr(), n_views.data_ptr(), start.data_ptr(), stream), "okp_window_push_weighted")
+    _window_push("okp_window_push_weighted", camera, tab, (assignment, status, meas_of, track_i, track_f, track_pose, T_WC), min_views, max_speed, (conf_ref, conf_floor),
+                 win_obs, (win_prior,), win_views, win_i, n_views, start, (), stream)
 
 
 def window_push_views_weighted(obs, prior, assignment, status, meas_of, track_i, track_f, track_pose, T_WB, views, ticks, min_views, max_speed, win_obs,
                                win_prior, win_views, win_i, n_views, start, stream):
-    b, max_obj, s, v, _ = obs.shape
-    _lib.check(_lib.lib().okp_window_push_views_weighted(obs.data_ptr(), prior.data_ptr(), assignment.data_ptr(), status.data_ptr(), meas_of.data_ptr(),
-                                                         track_i.data_ptr(), track_f.data_ptr(), track_pose.data_ptr(), T_WB.data_ptr(), views.data_ptr(), b, max_obj,
-                                                         s, win_obs.shape[1], ticks, v, min_views, max_speed, win_obs.data_ptr(), win_prior.data_ptr(),
-                                                         win_views.data_ptr(), win_i.data_ptr(), n_views.data_ptr(), start.data_ptr(), stream),
-               "okp_window_push_views_weighted")
+    _window_push_views("okp_window_push_views_weighted", obs, (prior, assignment, status, meas_of, track_i, track_f, track_pose, T_WB, views), ticks, min_views, max_speed,
+                       win_obs, (win_prior,), win_views, win_i, n_views, start, (), stream)
 
 
 # ---- the window refinement of a moving object (csrc/okp_refine_motion.hip): win_age [B,T,W] / [B,T,W*V] int32, a pose and a velocity -------------------
 def window_push_timed(camera, tab, assignment, status, meas_of, track_i, track_f, track_pose, T_WC, min_views, max_speed, win_obs, win_age, win_views, win_i, n_views,
                       start, start_velocity, stream):
-    b, max_obj, s, _ = tab.shape
-    _lib.check(_lib.lib().okp_window_push_timed(tab.data_ptr(), assignment.data_ptr(), status.data_ptr(), meas_of.data_ptr(), track_i.data_ptr(), track_f.data_ptr(),
-                                                track_pose.data_ptr(), T_WC.data_ptr(), _camera(camera), b, max_obj, s, win_obs.shape[1], win_obs.shape[3], min_views,
-                                                max_speed, win_obs.data_ptr(), win_age.data_ptr(), win_views.data_ptr(), win_i.data_ptr(), n_views.data_ptr(),
-                                                start.data_ptr(), start_velocity.data_ptr(), stream), "okp_window_push_timed")
+    _window_push("okp_window_push_timed", camera, tab, (assignment, status, meas_of, track_i, track_f, track_pose, T_WC), min_views, max_speed, (), win_obs, (win_age,),
+                 win_views, win_i, n_views, start, (start_velocity,), stream)
 
 
 def window_push_views_timed(obs, assignment, status, meas_of, track_i, track_f, track_pose, T_WB, views, ticks, min_views, max_speed, win_obs, win_age, win_views,
                             win_i, n_views, start, start_velocity, stream):
-    b, max_obj, s, v, _ = obs.shape
-    _lib.check(_lib.lib().okp_window_push_views_timed(obs.data_ptr(), assignment.data_ptr(), status.data_ptr(), meas_of.data_ptr(), track_i.data_ptr(),
-                                                      track_f.data_ptr(), track_pose.data_ptr(), T_WB.data_ptr(), views.data_ptr(), b, max_obj, s, win_obs.shape[1],
-                                                      ticks, v, min_views, max_speed, win_obs.data_ptr(), win_age.data_ptr(), win_views.data_ptr(), win_i.data_ptr(),
-                                                      n_views.data_ptr(), start.data_ptr(), start_velocity.data_ptr(), stream), "okp_window_push_views_timed")
+    _window_push_views("okp_window_push_views_timed", obs, (assignment, status, meas_of, track_i, track_f, track_pose, T_WB, views), ticks, min_views, max_speed, win_obs,
+                       (win_age,), win_views, win_i, n_views, start, (start_velocity,), stream)
 
 
 def refine_motion_views(obs, views, age, pose, velocity, assignment, n_obj, model, sigma_px, dt, horizon, iters, damping, pose_out, velocity_out, fit, n_obs,

@@ -38,7 +38,8 @@ def _sources():
 
 def _deps():
     return [os.path.join(REPO, "include", "okp.h"), os.path.join(CSRC, "okp_internal.h"),
-            os.path.join(CSRC, "okp_igemm_kernel.h"), os.path.join(CSRC, "okp_pose_math.h"), os.path.abspath(__file__)]
+            os.path.join(CSRC, "okp_igemm_kernel.h"), os.path.join(CSRC, "okp_pose_math.h"), os.path.join(CSRC, "okp_window_ring.h"),
+            os.path.abspath(__file__)]
 
 
 def _stale(target, deps):

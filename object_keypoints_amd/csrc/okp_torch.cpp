@@ -873,57 +873,117 @@ void refine_pose_views_robust(const Tensor& obs, const Tensor& views, int64_t vi
 }
 
 // A sliding window of ticks' bearings per track slot (csrc/okp_window.hip): the camera-frame table, the assignment and status the tracker's tick had, the tracker's
-// meas_of / track_i / track_f / track_pose and T_WC -> the state win_obs [B,T,S,W,2], win_views [B,T,W,14], win_i [B,T,4] stepped in place, n_views [B,T], start [B,T,12]
-void window_push(at::ArrayRef<double> camera, const Tensor& tab, const Tensor& assignment, const Tensor& status, const Tensor& meas_of, const Tensor& track_i,
-                 const Tensor& track_f, const Tensor& track_pose, const Tensor& T_WC, int64_t min_views, double max_speed, const Tensor& win_obs, const Tensor& win_views,
-                 const Tensor& win_i, const Tensor& n_views, const Tensor& start, int64_t stream) {
+// meas_of / track_i / track_f / track_pose and T_WC -> the state win_obs [B,T,S,W,2], win_views [B,T,W,14], win_i [B,T,4] stepped in place, n_views [B,T], start [B,T,12].
+// The three pushes of the family behind one body; `op` is the registered name, for the messages.  win_prior [B,T,S,W] (with conf_ref / conf_floor) makes it
+// window_push_weighted, win_age [B,T,W] int32 and start_velocity [B,T,3] window_push_timed (null: the push has none; pointers, so that a call copies no tensor handle)
+void window_push_any(const char* op, at::ArrayRef<double> camera, const Tensor& tab, const Tensor& assignment, const Tensor& status, const Tensor& meas_of,
+                     const Tensor& track_i, const Tensor& track_f, const Tensor& track_pose, const Tensor& T_WC, int64_t min_views, double max_speed, double conf_ref,
+                     double conf_floor, const Tensor& win_obs, const Tensor* win_prior, const Tensor* win_age, const Tensor& win_views, const Tensor& win_i,
+                     const Tensor& n_views, const Tensor& start, const Tensor* start_velocity, int64_t stream) {
   check_dev(tab, at::kDouble, "tab"); check_dev(assignment, at::kInt, "assignment"); check_dev(status, at::kInt, "status"); check_dev(meas_of, at::kInt, "meas_of");
   check_dev(track_i, at::kInt, "track_i"); check_dev(track_f, at::kDouble, "track_f"); check_dev(track_pose, at::kDouble, "track_pose"); check_dev(T_WC, at::kDouble, "T_WC");
-  check_dev(win_obs, at::kDouble, "win_obs"); check_dev(win_views, at::kDouble, "win_views"); check_dev(win_i, at::kInt, "win_i"); check_dev(n_views, at::kInt, "n_views");
-  check_dev(start, at::kDouble, "start");
+  check_dev(win_obs, at::kDouble, "win_obs");
+  if (win_prior) check_dev(*win_prior, at::kDouble, "win_prior");
+  if (win_age) check_dev(*win_age, at::kInt, "win_age");
+  check_dev(win_views, at::kDouble, "win_views"); check_dev(win_i, at::kInt, "win_i"); check_dev(n_views, at::kInt, "n_views"); check_dev(start, at::kDouble, "start");
+  if (start_velocity) check_dev(*start_velocity, at::kDouble, "start_velocity");
   TORCH_CHECK(tab.dim() == 4 && tab.size(3) == 4, "okp: tab is [B,max_obj,S,4] float64");
   TORCH_CHECK(win_obs.dim() == 5 && win_obs.size(4) == 2, "okp: win_obs is [B,T,S,W,2] float64");
   const int64_t B = tab.size(0), max_obj = tab.size(1), S = tab.size(2), T = win_obs.size(1), W = win_obs.size(3);
-  TORCH_CHECK(win_obs.size(0) == B && win_obs.size(2) == S && win_views.numel() == B * T * W * 14 && win_i.numel() == B * T * 4,
-              "okp: the window state is win_obs [B,T,S,W,2], win_views [B,T,W,14] and win_i [B,T,4] for the table's B and S");
+  TORCH_CHECK(win_obs.size(0) == B && win_obs.size(2) == S && (!win_prior || win_prior->numel() == B * T * S * W) && (!win_age || win_age->numel() == B * T * W) &&
+              win_views.numel() == B * T * W * 14 && win_i.numel() == B * T * 4,
+              "okp: the ", win_prior ? "weighted " : win_age ? "timed " : "", "window state is win_obs [B,T,S,W,2], ", win_prior ? "win_prior [B,T,S,W], " : win_age ? "win_age [B,T,W], " : "",
+              "win_views [B,T,W,14] and win_i [B,T,4] for the table's B and S");
   TORCH_CHECK(assignment.numel() == B * max_obj * S && status.numel() == B * max_obj && meas_of.numel() == B * T && track_i.numel() == B * T * 4 &&
               track_f.numel() == B * T * 16 && track_pose.numel() == B * T * 12 && T_WC.numel() == B * 12,
-              "okp: window_push inputs are assignment [B,max_obj,S], status [B,max_obj], meas_of [B,T], track_i [B,T,4], track_f [B,T,16], track_pose [B,T,12] and T_WC [B,12]");
-  TORCH_CHECK(n_views.numel() == B * T && start.numel() == B * T * 12, "okp: window_push outputs are n_views [B,T] and start [B,T,12]");
+              "okp: ", op, " inputs are assignment [B,max_obj,S], status [B,max_obj], meas_of [B,T], track_i [B,T,4], track_f [B,T,16], track_pose [B,T,12] and T_WC [B,12]");
+  TORCH_CHECK(n_views.numel() == B * T && start.numel() == B * T * 12 && (!start_velocity || start_velocity->numel() == B * T * 3),
+              "okp: ", op, " outputs are n_views [B,T]", start_velocity ? ", start [B,T,12] and start_velocity [B,T,3]" : " and start [B,T,12]");
   TORCH_CHECK(min_views >= INT32_MIN && min_views <= INT32_MAX, "okp: min_views does not fit an int32");
   TORCH_CHECK(B <= INT32_MAX && max_obj <= INT32_MAX && S <= INT32_MAX && T <= INT32_MAX && W <= INT32_MAX, "okp: tab or win_obs is too large");
   const okp_camera cam = camera_of(camera);
-  check_rc(okp_window_push(tab.data_ptr<double>(), assignment.data_ptr<int32_t>(), status.data_ptr<int32_t>(), meas_of.data_ptr<int32_t>(), track_i.data_ptr<int32_t>(),
-                           track_f.data_ptr<double>(), track_pose.data_ptr<double>(), T_WC.data_ptr<double>(), &cam, (int32_t)B, (int32_t)max_obj, (int32_t)S, (int32_t)T,
-                           (int32_t)W, (int32_t)min_views, max_speed, win_obs.data_ptr<double>(), win_views.data_ptr<double>(), win_i.data_ptr<int32_t>(),
-                           n_views.data_ptr<int32_t>(), start.data_ptr<double>(), sp(stream)), "okp_window_push");
+  const double* tab_p = tab.data_ptr<double>(); const int32_t* as_p = assignment.data_ptr<int32_t>(); const int32_t* st_p = status.data_ptr<int32_t>();
+  const int32_t* meas_p = meas_of.data_ptr<int32_t>(); const int32_t* ti_p = track_i.data_ptr<int32_t>(); const double* tf_p = track_f.data_ptr<double>();
+  const double* tp_p = track_pose.data_ptr<double>(); const double* T_p = T_WC.data_ptr<double>();
+  double* obs_p = win_obs.data_ptr<double>(); double* views_p = win_views.data_ptr<double>(); int32_t* wi_p = win_i.data_ptr<int32_t>();
+  int32_t* nv_p = n_views.data_ptr<int32_t>(); double* start_p = start.data_ptr<double>();
+  if (win_age)
+    check_rc(okp_window_push_timed(tab_p, as_p, st_p, meas_p, ti_p, tf_p, tp_p, T_p, &cam, (int32_t)B, (int32_t)max_obj, (int32_t)S, (int32_t)T, (int32_t)W, (int32_t)min_views,
+                                   max_speed, obs_p, win_age->data_ptr<int32_t>(), views_p, wi_p, nv_p, start_p, start_velocity->data_ptr<double>(), sp(stream)),
+             "okp_window_push_timed");
+  else if (win_prior)
+    check_rc(okp_window_push_weighted(tab_p, as_p, st_p, meas_p, ti_p, tf_p, tp_p, T_p, &cam, (int32_t)B, (int32_t)max_obj, (int32_t)S, (int32_t)T, (int32_t)W,
+                                      (int32_t)min_views, max_speed, conf_ref, conf_floor, obs_p, win_prior->data_ptr<double>(), views_p, wi_p, nv_p, start_p, sp(stream)),
+             "okp_window_push_weighted");
+  else
+    check_rc(okp_window_push(tab_p, as_p, st_p, meas_p, ti_p, tf_p, tp_p, T_p, &cam, (int32_t)B, (int32_t)max_obj, (int32_t)S, (int32_t)T, (int32_t)W, (int32_t)min_views,
+                             max_speed, obs_p, views_p, wi_p, nv_p, start_p, sp(stream)), "okp_window_push");
+}
+
+void window_push(at::ArrayRef<double> camera, const Tensor& tab, const Tensor& assignment, const Tensor& status, const Tensor& meas_of, const Tensor& track_i,
+                 const Tensor& track_f, const Tensor& track_pose, const Tensor& T_WC, int64_t min_views, double max_speed, const Tensor& win_obs, const Tensor& win_views,
+                 const Tensor& win_i, const Tensor& n_views, const Tensor& start, int64_t stream) {
+  window_push_any("window_push", camera, tab, assignment, status, meas_of, track_i, track_f, track_pose, T_WC, min_views, max_speed, 0.0, 0.0, win_obs, nullptr, nullptr,
+                  win_views, win_i, n_views, start, nullptr, stream);
 }
 
 // The sliding window of a rig (csrc/okp_window_views.hip): the tick's bearings obs [B,max_obj,S,V,2] by table slot, what window_push takes of the pose stage and the
-// tracker, T_WB [B,12] and views [V,14] -> the state win_obs [B,T,S,W*V,2], win_views [B,T,W*V,14], win_i [B,T,4] stepped in place, n_views [B,T], start [B,T,12]
-void window_push_views(const Tensor& obs, const Tensor& assignment, const Tensor& status, const Tensor& meas_of, const Tensor& track_i, const Tensor& track_f,
-                       const Tensor& track_pose, const Tensor& T_WB, const Tensor& views, int64_t ticks, int64_t min_views, double max_speed, const Tensor& win_obs,
-                       const Tensor& win_views, const Tensor& win_i, const Tensor& n_views, const Tensor& start, int64_t stream) {
-  check_dev(obs, at::kDouble, "obs"); check_dev(assignment, at::kInt, "assignment"); check_dev(status, at::kInt, "status"); check_dev(meas_of, at::kInt, "meas_of");
-  check_dev(track_i, at::kInt, "track_i"); check_dev(track_f, at::kDouble, "track_f"); check_dev(track_pose, at::kDouble, "track_pose"); check_dev(T_WB, at::kDouble, "T_WB");
-  check_dev(views, at::kDouble, "views"); check_dev(win_obs, at::kDouble, "win_obs"); check_dev(win_views, at::kDouble, "win_views"); check_dev(win_i, at::kInt, "win_i");
-  check_dev(n_views, at::kInt, "n_views"); check_dev(start, at::kDouble, "start");
+// tracker, T_WB [B,12] and views [V,14] -> the state win_obs [B,T,S,W*V,2], win_views [B,T,W*V,14], win_i [B,T,4] stepped in place, n_views [B,T], start [B,T,12].
+// The three pushes of the family behind one body, as window_push_any: the tick's prior [B,max_obj,S,V] and win_prior [B,T,S,W*V] make it window_push_views_weighted,
+// win_age [B,T,W*V] int32 and start_velocity [B,T,3] window_push_views_timed
+void window_push_views_any(const char* op, const Tensor& obs, const Tensor* prior, const Tensor& assignment, const Tensor& status, const Tensor& meas_of,
+                           const Tensor& track_i, const Tensor& track_f, const Tensor& track_pose, const Tensor& T_WB, const Tensor& views, int64_t ticks, int64_t min_views,
+                           double max_speed, const Tensor& win_obs, const Tensor* win_prior, const Tensor* win_age, const Tensor& win_views, const Tensor& win_i,
+                           const Tensor& n_views, const Tensor& start, const Tensor* start_velocity, int64_t stream) {
+  check_dev(obs, at::kDouble, "obs");
+  if (prior) check_dev(*prior, at::kDouble, "prior");
+  check_dev(assignment, at::kInt, "assignment"); check_dev(status, at::kInt, "status"); check_dev(meas_of, at::kInt, "meas_of"); check_dev(track_i, at::kInt, "track_i");
+  check_dev(track_f, at::kDouble, "track_f"); check_dev(track_pose, at::kDouble, "track_pose"); check_dev(T_WB, at::kDouble, "T_WB"); check_dev(views, at::kDouble, "views");
+  check_dev(win_obs, at::kDouble, "win_obs");
+  if (win_prior) check_dev(*win_prior, at::kDouble, "win_prior");
+  if (win_age) check_dev(*win_age, at::kInt, "win_age");
+  check_dev(win_views, at::kDouble, "win_views"); check_dev(win_i, at::kInt, "win_i"); check_dev(n_views, at::kInt, "n_views"); check_dev(start, at::kDouble, "start");
+  if (start_velocity) check_dev(*start_velocity, at::kDouble, "start_velocity");
   TORCH_CHECK(obs.dim() == 5 && obs.size(4) == 2, "okp: obs is [B,max_obj,S,V,2] float64");
   TORCH_CHECK(win_obs.dim() == 5 && win_obs.size(4) == 2, "okp: win_obs is [B,T,S,W*V,2] float64");
   const int64_t B = obs.size(0), max_obj = obs.size(1), S = obs.size(2), V = obs.size(3), T = win_obs.size(1), W = ticks;
   TORCH_CHECK(W >= INT32_MIN && W <= INT32_MAX && min_views >= INT32_MIN && min_views <= INT32_MAX, "okp: ticks or min_views does not fit an int32");
   TORCH_CHECK(B <= INT32_MAX && max_obj <= INT32_MAX && S <= INT32_MAX && T <= INT32_MAX && V <= INT32_MAX, "okp: obs or win_obs is too large");
-  TORCH_CHECK(W < 1 || V < 1 || (win_obs.size(0) == B && win_obs.size(2) == S && win_obs.size(3) == W * V && win_views.numel() == B * T * W * V * 14 && win_i.numel() == B * T * 4),
-              "okp: the window state is win_obs [B,T,S,W*V,2], win_views [B,T,W*V,14] and win_i [B,T,4] for the bearings' B, S and V and W = ticks");       // (W, V < 1: the entry point refuses)
+  TORCH_CHECK(!prior || prior->numel() == B * max_obj * S * V, "okp: prior is [B,max_obj,S,V] float64, one value per entry of obs");
+  TORCH_CHECK(W < 1 || V < 1 || (win_obs.size(0) == B && win_obs.size(2) == S && win_obs.size(3) == W * V && (!win_prior || win_prior->numel() == B * T * S * W * V) &&
+                                 (!win_age || win_age->numel() == B * T * W * V) && win_views.numel() == B * T * W * V * 14 && win_i.numel() == B * T * 4),
+              "okp: the ", win_prior ? "weighted " : win_age ? "timed " : "", "window state is win_obs [B,T,S,W*V,2], ",
+              win_prior ? "win_prior [B,T,S,W*V], " : win_age ? "win_age [B,T,W*V], " : "",
+              "win_views [B,T,W*V,14] and win_i [B,T,4] for the bearings' B, S and V and W = ticks");        // (W, V < 1: the entry point refuses)
   TORCH_CHECK(assignment.numel() == B * max_obj * S && status.numel() == B * max_obj && meas_of.numel() == B * T && track_i.numel() == B * T * 4 &&
               track_f.numel() == B * T * 16 && track_pose.numel() == B * T * 12 && T_WB.numel() == B * 12 && views.numel() == V * 14,
-              "okp: window_push_views inputs are assignment [B,max_obj,S], status [B,max_obj], meas_of [B,T], track_i [B,T,4], track_f [B,T,16], track_pose [B,T,12], "
+              "okp: ", op, " inputs are assignment [B,max_obj,S], status [B,max_obj], meas_of [B,T], track_i [B,T,4], track_f [B,T,16], track_pose [B,T,12], "
               "T_WB [B,12] and views [V,14]");
-  TORCH_CHECK(n_views.numel() == B * T && start.numel() == B * T * 12, "okp: window_push_views outputs are n_views [B,T] and start [B,T,12]");
-  check_rc(okp_window_push_views(obs.data_ptr<double>(), assignment.data_ptr<int32_t>(), status.data_ptr<int32_t>(), meas_of.data_ptr<int32_t>(), track_i.data_ptr<int32_t>(),
-                                 track_f.data_ptr<double>(), track_pose.data_ptr<double>(), T_WB.data_ptr<double>(), views.data_ptr<double>(), (int32_t)B, (int32_t)max_obj,
-                                 (int32_t)S, (int32_t)T, (int32_t)W, (int32_t)V, (int32_t)min_views, max_speed, win_obs.data_ptr<double>(), win_views.data_ptr<double>(),
-                                 win_i.data_ptr<int32_t>(), n_views.data_ptr<int32_t>(), start.data_ptr<double>(), sp(stream)), "okp_window_push_views");
+  TORCH_CHECK(n_views.numel() == B * T && start.numel() == B * T * 12 && (!start_velocity || start_velocity->numel() == B * T * 3),
+              "okp: ", op, " outputs are n_views [B,T]", start_velocity ? ", start [B,T,12] and start_velocity [B,T,3]" : " and start [B,T,12]");
+  const double* obs_p = obs.data_ptr<double>(); const int32_t* as_p = assignment.data_ptr<int32_t>(); const int32_t* st_p = status.data_ptr<int32_t>();
+  const int32_t* meas_p = meas_of.data_ptr<int32_t>(); const int32_t* ti_p = track_i.data_ptr<int32_t>(); const double* tf_p = track_f.data_ptr<double>();
+  const double* tp_p = track_pose.data_ptr<double>(); const double* T_p = T_WB.data_ptr<double>(); const double* v_p = views.data_ptr<double>();
+  double* ring_p = win_obs.data_ptr<double>(); double* views_p = win_views.data_ptr<double>(); int32_t* wi_p = win_i.data_ptr<int32_t>();
+  int32_t* nv_p = n_views.data_ptr<int32_t>(); double* start_p = start.data_ptr<double>();
+  if (win_age)
+    check_rc(okp_window_push_views_timed(obs_p, as_p, st_p, meas_p, ti_p, tf_p, tp_p, T_p, v_p, (int32_t)B, (int32_t)max_obj, (int32_t)S, (int32_t)T, (int32_t)W, (int32_t)V,
+                                         (int32_t)min_views, max_speed, ring_p, win_age->data_ptr<int32_t>(), views_p, wi_p, nv_p, start_p,
+                                         start_velocity->data_ptr<double>(), sp(stream)), "okp_window_push_views_timed");
+  else if (win_prior)
+    check_rc(okp_window_push_views_weighted(obs_p, prior->data_ptr<double>(), as_p, st_p, meas_p, ti_p, tf_p, tp_p, T_p, v_p, (int32_t)B, (int32_t)max_obj, (int32_t)S,
+                                            (int32_t)T, (int32_t)W, (int32_t)V, (int32_t)min_views, max_speed, ring_p, win_prior->data_ptr<double>(), views_p, wi_p, nv_p,
+                                            start_p, sp(stream)), "okp_window_push_views_weighted");
+  else
+    check_rc(okp_window_push_views(obs_p, as_p, st_p, meas_p, ti_p, tf_p, tp_p, T_p, v_p, (int32_t)B, (int32_t)max_obj, (int32_t)S, (int32_t)T, (int32_t)W, (int32_t)V,
+                                   (int32_t)min_views, max_speed, ring_p, views_p, wi_p, nv_p, start_p, sp(stream)), "okp_window_push_views");
+}
+
+void window_push_views(const Tensor& obs, const Tensor& assignment, const Tensor& status, const Tensor& meas_of, const Tensor& track_i, const Tensor& track_f,
+                       const Tensor& track_pose, const Tensor& T_WB, const Tensor& views, int64_t ticks, int64_t min_views, double max_speed, const Tensor& win_obs,
+                       const Tensor& win_views, const Tensor& win_i, const Tensor& n_views, const Tensor& start, int64_t stream) {
+  window_push_views_any("window_push_views", obs, nullptr, assignment, status, meas_of, track_i, track_f, track_pose, T_WB, views, ticks, min_views, max_speed, win_obs,
+                        nullptr, nullptr, win_views, win_i, n_views, start, nullptr, stream);
 }
 
 // The views refinement beyond one wave (csrc/okp_refine_views_wide.hip): refine_pose_views_robust's arguments with V up to 512; huber_px = 0 is the plain cost:
@@ -1044,27 +1104,8 @@ void window_push_weighted(at::ArrayRef<double> camera, const Tensor& tab, const 
                           const Tensor& track_f, const Tensor& track_pose, const Tensor& T_WC, int64_t min_views, double max_speed, double conf_ref, double conf_floor,
                           const Tensor& win_obs, const Tensor& win_prior, const Tensor& win_views, const Tensor& win_i, const Tensor& n_views, const Tensor& start,
                           int64_t stream) {
-  check_dev(tab, at::kDouble, "tab"); check_dev(assignment, at::kInt, "assignment"); check_dev(status, at::kInt, "status"); check_dev(meas_of, at::kInt, "meas_of");
-  check_dev(track_i, at::kInt, "track_i"); check_dev(track_f, at::kDouble, "track_f"); check_dev(track_pose, at::kDouble, "track_pose"); check_dev(T_WC, at::kDouble, "T_WC");
-  check_dev(win_obs, at::kDouble, "win_obs"); check_dev(win_prior, at::kDouble, "win_prior"); check_dev(win_views, at::kDouble, "win_views"); check_dev(win_i, at::kInt, "win_i");
-  check_dev(n_views, at::kInt, "n_views"); check_dev(start, at::kDouble, "start");
-  TORCH_CHECK(tab.dim() == 4 && tab.size(3) == 4, "okp: tab is [B,max_obj,S,4] float64");
-  TORCH_CHECK(win_obs.dim() == 5 && win_obs.size(4) == 2, "okp: win_obs is [B,T,S,W,2] float64");
-  const int64_t B = tab.size(0), max_obj = tab.size(1), S = tab.size(2), T = win_obs.size(1), W = win_obs.size(3);
-  TORCH_CHECK(win_obs.size(0) == B && win_obs.size(2) == S && win_prior.numel() == B * T * S * W && win_views.numel() == B * T * W * 14 && win_i.numel() == B * T * 4,
-              "okp: the weighted window state is win_obs [B,T,S,W,2], win_prior [B,T,S,W], win_views [B,T,W,14] and win_i [B,T,4] for the table's B and S");
-  TORCH_CHECK(assignment.numel() == B * max_obj * S && status.numel() == B * max_obj && meas_of.numel() == B * T && track_i.numel() == B * T * 4 &&
-              track_f.numel() == B * T * 16 && track_pose.numel() == B * T * 12 && T_WC.numel() == B * 12,
-              "okp: window_push_weighted inputs are assignment [B,max_obj,S], status [B,max_obj], meas_of [B,T], track_i [B,T,4], track_f [B,T,16], track_pose [B,T,12] and T_WC [B,12]");
-  TORCH_CHECK(n_views.numel() == B * T && start.numel() == B * T * 12, "okp: window_push_weighted outputs are n_views [B,T] and start [B,T,12]");
-  TORCH_CHECK(min_views >= INT32_MIN && min_views <= INT32_MAX, "okp: min_views does not fit an int32");
-  TORCH_CHECK(B <= INT32_MAX && max_obj <= INT32_MAX && S <= INT32_MAX && T <= INT32_MAX && W <= INT32_MAX, "okp: tab or win_obs is too large");
-  const okp_camera cam = camera_of(camera);
-  check_rc(okp_window_push_weighted(tab.data_ptr<double>(), assignment.data_ptr<int32_t>(), status.data_ptr<int32_t>(), meas_of.data_ptr<int32_t>(), track_i.data_ptr<int32_t>(),
-                                    track_f.data_ptr<double>(), track_pose.data_ptr<double>(), T_WC.data_ptr<double>(), &cam, (int32_t)B, (int32_t)max_obj, (int32_t)S, (int32_t)T,
-                                    (int32_t)W, (int32_t)min_views, max_speed, conf_ref, conf_floor, win_obs.data_ptr<double>(), win_prior.data_ptr<double>(),
-                                    win_views.data_ptr<double>(), win_i.data_ptr<int32_t>(), n_views.data_ptr<int32_t>(), start.data_ptr<double>(), sp(stream)),
-           "okp_window_push_weighted");
+  window_push_any("window_push_weighted", camera, tab, assignment, status, meas_of, track_i, track_f, track_pose, T_WC, min_views, max_speed, conf_ref, conf_floor, win_obs,
+                  &win_prior, nullptr, win_views, win_i, n_views, start, nullptr, stream);
 }
 
 // window_push_views with the tick's prior [B,max_obj,S,V] and the state win_prior [B,T,S,W*V]
@@ -1072,31 +1113,8 @@ void window_push_views_weighted(const Tensor& obs, const Tensor& prior, const Te
                                 const Tensor& track_f, const Tensor& track_pose, const Tensor& T_WB, const Tensor& views, int64_t ticks, int64_t min_views, double max_speed,
                                 const Tensor& win_obs, const Tensor& win_prior, const Tensor& win_views, const Tensor& win_i, const Tensor& n_views, const Tensor& start,
                                 int64_t stream) {
-  check_dev(obs, at::kDouble, "obs"); check_dev(prior, at::kDouble, "prior"); check_dev(assignment, at::kInt, "assignment"); check_dev(status, at::kInt, "status");
-  check_dev(meas_of, at::kInt, "meas_of"); check_dev(track_i, at::kInt, "track_i"); check_dev(track_f, at::kDouble, "track_f"); check_dev(track_pose, at::kDouble, "track_pose");
-  check_dev(T_WB, at::kDouble, "T_WB"); check_dev(views, at::kDouble, "views"); check_dev(win_obs, at::kDouble, "win_obs"); check_dev(win_prior, at::kDouble, "win_prior");
-  check_dev(win_views, at::kDouble, "win_views"); check_dev(win_i, at::kInt, "win_i"); check_dev(n_views, at::kInt, "n_views"); check_dev(start, at::kDouble, "start");
-  TORCH_CHECK(obs.dim() == 5 && obs.size(4) == 2, "okp: obs is [B,max_obj,S,V,2] float64");
-  TORCH_CHECK(win_obs.dim() == 5 && win_obs.size(4) == 2, "okp: win_obs is [B,T,S,W*V,2] float64");
-  const int64_t B = obs.size(0), max_obj = obs.size(1), S = obs.size(2), V = obs.size(3), T = win_obs.size(1), W = ticks;
-  TORCH_CHECK(W >= INT32_MIN && W <= INT32_MAX && min_views >= INT32_MIN && min_views <= INT32_MAX, "okp: ticks or min_views does not fit an int32");
-  TORCH_CHECK(B <= INT32_MAX && max_obj <= INT32_MAX && S <= INT32_MAX && T <= INT32_MAX && V <= INT32_MAX, "okp: obs or win_obs is too large");
-  TORCH_CHECK(prior.numel() == B * max_obj * S * V, "okp: prior is [B,max_obj,S,V] float64, one value per entry of obs");
-  TORCH_CHECK(W < 1 || V < 1 || (win_obs.size(0) == B && win_obs.size(2) == S && win_obs.size(3) == W * V && win_prior.numel() == B * T * S * W * V &&
-                                 win_views.numel() == B * T * W * V * 14 && win_i.numel() == B * T * 4),
-              "okp: the weighted window state is win_obs [B,T,S,W*V,2], win_prior [B,T,S,W*V], win_views [B,T,W*V,14] and win_i [B,T,4] for the bearings' B, S and V and "
-              "W = ticks");                        // (W, V < 1: the entry point refuses)
-  TORCH_CHECK(assignment.numel() == B * max_obj * S && status.numel() == B * max_obj && meas_of.numel() == B * T && track_i.numel() == B * T * 4 &&
-              track_f.numel() == B * T * 16 && track_pose.numel() == B * T * 12 && T_WB.numel() == B * 12 && views.numel() == V * 14,
-              "okp: window_push_views_weighted inputs are assignment [B,max_obj,S], status [B,max_obj], meas_of [B,T], track_i [B,T,4], track_f [B,T,16], "
-              "track_pose [B,T,12], T_WB [B,12] and views [V,14]");
-  TORCH_CHECK(n_views.numel() == B * T && start.numel() == B * T * 12, "okp: window_push_views_weighted outputs are n_views [B,T] and start [B,T,12]");
-  check_rc(okp_window_push_views_weighted(obs.data_ptr<double>(), prior.data_ptr<double>(), assignment.data_ptr<int32_t>(), status.data_ptr<int32_t>(),
-                                          meas_of.data_ptr<int32_t>(), track_i.data_ptr<int32_t>(), track_f.data_ptr<double>(), track_pose.data_ptr<double>(),
-                                          T_WB.data_ptr<double>(), views.data_ptr<double>(), (int32_t)B, (int32_t)max_obj, (int32_t)S, (int32_t)T, (int32_t)W, (int32_t)V,
-                                          (int32_t)min_views, max_speed, win_obs.data_ptr<double>(), win_prior.data_ptr<double>(), win_views.data_ptr<double>(),
-                                          win_i.data_ptr<int32_t>(), n_views.data_ptr<int32_t>(), start.data_ptr<double>(), sp(stream)),
-           "okp_window_push_views_weighted");
+  window_push_views_any("window_push_views_weighted", obs, &prior, assignment, status, meas_of, track_i, track_f, track_pose, T_WB, views, ticks, min_views, max_speed,
+                        win_obs, &win_prior, nullptr, win_views, win_i, n_views, start, nullptr, stream);
 }
 
 // window_push with the state win_age [B,T,W] int32 and the output start_velocity [B,T,3] (the window of a moving object)
@@ -1104,28 +1122,8 @@ void window_push_timed(at::ArrayRef<double> camera, const Tensor& tab, const Ten
                        const Tensor& track_f, const Tensor& track_pose, const Tensor& T_WC, int64_t min_views, double max_speed, const Tensor& win_obs,
                        const Tensor& win_age, const Tensor& win_views, const Tensor& win_i, const Tensor& n_views, const Tensor& start, const Tensor& start_velocity,
                        int64_t stream) {
-  check_dev(tab, at::kDouble, "tab"); check_dev(assignment, at::kInt, "assignment"); check_dev(status, at::kInt, "status"); check_dev(meas_of, at::kInt, "meas_of");
-  check_dev(track_i, at::kInt, "track_i"); check_dev(track_f, at::kDouble, "track_f"); check_dev(track_pose, at::kDouble, "track_pose"); check_dev(T_WC, at::kDouble, "T_WC");
-  check_dev(win_obs, at::kDouble, "win_obs"); check_dev(win_age, at::kInt, "win_age"); check_dev(win_views, at::kDouble, "win_views"); check_dev(win_i, at::kInt, "win_i");
-  check_dev(n_views, at::kInt, "n_views"); check_dev(start, at::kDouble, "start"); check_dev(start_velocity, at::kDouble, "start_velocity");
-  TORCH_CHECK(tab.dim() == 4 && tab.size(3) == 4, "okp: tab is [B,max_obj,S,4] float64");
-  TORCH_CHECK(win_obs.dim() == 5 && win_obs.size(4) == 2, "okp: win_obs is [B,T,S,W,2] float64");
-  const int64_t B = tab.size(0), max_obj = tab.size(1), S = tab.size(2), T = win_obs.size(1), W = win_obs.size(3);
-  TORCH_CHECK(win_obs.size(0) == B && win_obs.size(2) == S && win_age.numel() == B * T * W && win_views.numel() == B * T * W * 14 && win_i.numel() == B * T * 4,
-              "okp: the timed window state is win_obs [B,T,S,W,2], win_age [B,T,W], win_views [B,T,W,14] and win_i [B,T,4] for the table's B and S");
-  TORCH_CHECK(assignment.numel() == B * max_obj * S && status.numel() == B * max_obj && meas_of.numel() == B * T && track_i.numel() == B * T * 4 &&
-              track_f.numel() == B * T * 16 && track_pose.numel() == B * T * 12 && T_WC.numel() == B * 12,
-              "okp: window_push_timed inputs are assignment [B,max_obj,S], status [B,max_obj], meas_of [B,T], track_i [B,T,4], track_f [B,T,16], track_pose [B,T,12] and T_WC [B,12]");
-  TORCH_CHECK(n_views.numel() == B * T && start.numel() == B * T * 12 && start_velocity.numel() == B * T * 3,
-              "okp: window_push_timed outputs are n_views [B,T], start [B,T,12] and start_velocity [B,T,3]");
-  TORCH_CHECK(min_views >= INT32_MIN && min_views <= INT32_MAX, "okp: min_views does not fit an int32");
-  TORCH_CHECK(B <= INT32_MAX && max_obj <= INT32_MAX && S <= INT32_MAX && T <= INT32_MAX && W <= INT32_MAX, "okp: tab or win_obs is too large");
-  const okp_camera cam = camera_of(camera);
-  check_rc(okp_window_push_timed(tab.data_ptr<double>(), assignment.data_ptr<int32_t>(), status.data_ptr<int32_t>(), meas_of.data_ptr<int32_t>(), track_i.data_ptr<int32_t>(),
-                                 track_f.data_ptr<double>(), track_pose.data_ptr<double>(), T_WC.data_ptr<double>(), &cam, (int32_t)B, (int32_t)max_obj, (int32_t)S, (int32_t)T,
-                                 (int32_t)W, (int32_t)min_views, max_speed, win_obs.data_ptr<double>(), win_age.data_ptr<int32_t>(), win_views.data_ptr<double>(),
-                                 win_i.data_ptr<int32_t>(), n_views.data_ptr<int32_t>(), start.data_ptr<double>(), start_velocity.data_ptr<double>(), sp(stream)),
-           "okp_window_push_timed");
+  window_push_any("window_push_timed", camera, tab, assignment, status, meas_of, track_i, track_f, track_pose, T_WC, min_views, max_speed, 0.0, 0.0, win_obs, nullptr,
+                  &win_age, win_views, win_i, n_views, start, &start_velocity, stream);
 }
 
 // window_push_views with the state win_age [B,T,W*V] int32 and the output start_velocity [B,T,3]
@@ -1133,29 +1131,8 @@ void window_push_views_timed(const Tensor& obs, const Tensor& assignment, const 
                              const Tensor& track_pose, const Tensor& T_WB, const Tensor& views, int64_t ticks, int64_t min_views, double max_speed, const Tensor& win_obs,
                              const Tensor& win_age, const Tensor& win_views, const Tensor& win_i, const Tensor& n_views, const Tensor& start, const Tensor& start_velocity,
                              int64_t stream) {
-  check_dev(obs, at::kDouble, "obs"); check_dev(assignment, at::kInt, "assignment"); check_dev(status, at::kInt, "status"); check_dev(meas_of, at::kInt, "meas_of");
-  check_dev(track_i, at::kInt, "track_i"); check_dev(track_f, at::kDouble, "track_f"); check_dev(track_pose, at::kDouble, "track_pose"); check_dev(T_WB, at::kDouble, "T_WB");
-  check_dev(views, at::kDouble, "views"); check_dev(win_obs, at::kDouble, "win_obs"); check_dev(win_age, at::kInt, "win_age"); check_dev(win_views, at::kDouble, "win_views");
-  check_dev(win_i, at::kInt, "win_i"); check_dev(n_views, at::kInt, "n_views"); check_dev(start, at::kDouble, "start"); check_dev(start_velocity, at::kDouble, "start_velocity");
-  TORCH_CHECK(obs.dim() == 5 && obs.size(4) == 2, "okp: obs is [B,max_obj,S,V,2] float64");
-  TORCH_CHECK(win_obs.dim() == 5 && win_obs.size(4) == 2, "okp: win_obs is [B,T,S,W*V,2] float64");
-  const int64_t B = obs.size(0), max_obj = obs.size(1), S = obs.size(2), V = obs.size(3), T = win_obs.size(1), W = ticks;
-  TORCH_CHECK(W >= INT32_MIN && W <= INT32_MAX && min_views >= INT32_MIN && min_views <= INT32_MAX, "okp: ticks or min_views does not fit an int32");
-  TORCH_CHECK(B <= INT32_MAX && max_obj <= INT32_MAX && S <= INT32_MAX && T <= INT32_MAX && V <= INT32_MAX, "okp: obs or win_obs is too large");
-  TORCH_CHECK(W < 1 || V < 1 || (win_obs.size(0) == B && win_obs.size(2) == S && win_obs.size(3) == W * V && win_age.numel() == B * T * W * V &&
-                                 win_views.numel() == B * T * W * V * 14 && win_i.numel() == B * T * 4),
-              "okp: the timed window state is win_obs [B,T,S,W*V,2], win_age [B,T,W*V], win_views [B,T,W*V,14] and win_i [B,T,4] for the bearings' B, S and V and W = ticks");
-  TORCH_CHECK(assignment.numel() == B * max_obj * S && status.numel() == B * max_obj && meas_of.numel() == B * T && track_i.numel() == B * T * 4 &&
-              track_f.numel() == B * T * 16 && track_pose.numel() == B * T * 12 && T_WB.numel() == B * 12 && views.numel() == V * 14,
-              "okp: window_push_views_timed inputs are assignment [B,max_obj,S], status [B,max_obj], meas_of [B,T], track_i [B,T,4], track_f [B,T,16], track_pose [B,T,12], "
-              "T_WB [B,12] and views [V,14]");
-  TORCH_CHECK(n_views.numel() == B * T && start.numel() == B * T * 12 && start_velocity.numel() == B * T * 3,
-              "okp: window_push_views_timed outputs are n_views [B,T], start [B,T,12] and start_velocity [B,T,3]");
-  check_rc(okp_window_push_views_timed(obs.data_ptr<double>(), assignment.data_ptr<int32_t>(), status.data_ptr<int32_t>(), meas_of.data_ptr<int32_t>(),
-                                       track_i.data_ptr<int32_t>(), track_f.data_ptr<double>(), track_pose.data_ptr<double>(), T_WB.data_ptr<double>(), views.data_ptr<double>(),
-                                       (int32_t)B, (int32_t)max_obj, (int32_t)S, (int32_t)T, (int32_t)W, (int32_t)V, (int32_t)min_views, max_speed, win_obs.data_ptr<double>(),
-                                       win_age.data_ptr<int32_t>(), win_views.data_ptr<double>(), win_i.data_ptr<int32_t>(), n_views.data_ptr<int32_t>(),
-                                       start.data_ptr<double>(), start_velocity.data_ptr<double>(), sp(stream)), "okp_window_push_views_timed");
+  window_push_views_any("window_push_views_timed", obs, nullptr, assignment, status, meas_of, track_i, track_f, track_pose, T_WB, views, ticks, min_views, max_speed,
+                        win_obs, nullptr, &win_age, win_views, win_i, n_views, start, &start_velocity, stream);
 }
 
 // The window refinement of a moving object (csrc/okp_refine_motion.hip): refine_pose_views_each's obs and views [B,max_obj,V,14] with age [B,max_obj,V] int32, a pose

@@ -10,7 +10,7 @@
 //                            the ring: an element is the new column's, or NaN / 0 when the ring is emptied, or left alone - so no word is
 //                            written twice.  Rings are a few KiB: the launch is latency-bound.
 // fp64, no atomics, no host wait, contraction off; the same bits on every run and as tests/window_spec.py.
-#include "okp_pose_math.h"           // finite64
+#include "okp_window_ring.h"         // the ring's step, ages and finish; the scalar refusals
 
 #pragma clang fp contract(off)
 
@@ -44,26 +44,10 @@ __device__ __forceinline__ void window_push_body(const WindowParams& P) {
   const double nan = __builtin_nan("");
   int32_t* wi = P.win_i + bi * 4;
 
-  // 1 - 3: whose ring this is, and whether it is emptied (wave-uniform: every lane reads the same words)
-  const int id = P.track_i[bi * 4];
-  int owner = wi[0], head = wi[1], filled = wi[2];
-  bool clear = false, push = false;
-  int o = -1;
-  if (id == 0) {
-    clear = true; owner = 0; head = 0; filled = 0;
-  } else {
-    if (id != owner || head < 0 || head >= W || filled < 0 || filled > W) { clear = true; owner = id; head = 0; filled = 0; }
-    const double* f = P.track_f + bi * 16;
-    const double vx = f[3], vy = f[4], vz = f[5];
-    if ((vx * vx + vy * vy) + vz * vz > P.max_speed2) { clear = true; head = 0; filled = 0; }
-    // 4: is there a column to push
-    o = P.meas_of[bi];
-    if (o >= 0 && o < P.max_obj && P.status[b * P.max_obj + o] == 0) {
-      push = true;
-#pragma unroll
-      for (int k = 0; k < 12; ++k) push = push && finite64(P.T_WC[b * 12 + k]);
-    }
-  }
+  // 1 - 4: whose ring this is, whether it is emptied, whether there is a column to push (wave-uniform: every lane reads the same words)
+  const RingStep step = ring_step(P.track_i, wi, P.track_f, P.meas_of, P.status, P.T_WC, bi, b, P.max_obj, W, P.max_speed2);
+  const bool clear = step.clear, push = step.push;
+  const int o = step.o, head = step.head;
 
   if (push) {                                                     // (wave-uniform)
     if (lane < OKP_POSE_MAX_POINTS) {
@@ -125,28 +109,8 @@ __device__ __forceinline__ void window_push_body(const WindowParams& P) {
     if (push && c == head) vw[e] = view[k];
     else if (clear) vw[e] = 0.0;
   }
-  if constexpr (TIMED) {                                          // a pushed column is 0 ticks old, a free slot's are 0, every other one a tick older
-    int32_t* ages = P.win_age + bi * W;
-    for (int c = lane; c < W; c += 64) {
-      const int32_t old = clear ? 0 : ages[c];
-      ages[c] = (push && c == head) || id == 0 ? 0 : (old < (1 << 30) ? old + 1 : (1 << 30));
-    }
-  }
-  if (push) { head = head + 1 == W ? 0 : head + 1; filled = filled < W ? filled + 1 : W; }
-
-  if (lane == 0) { wi[0] = owner; wi[1] = head; wi[2] = filled; wi[3] = 0; P.n_views[bi] = filled; }
-  if (lane < 12) {                                                // the start of the refinement: the track pose bit for bit, or NaN
-    const unsigned long long bits = reinterpret_cast<const unsigned long long*>(P.track_pose)[bi * 12 + lane];
-    if (filled >= P.min_views) reinterpret_cast<unsigned long long*>(P.start)[bi * 12 + lane] = bits;
-    else P.start[bi * 12 + lane] = nan;
-  }
-  if constexpr (TIMED) {
-    if (lane < 3) {                                               // the start of the velocity: the track's, bit for bit, wherever the start is the track pose
-      const unsigned long long bits = reinterpret_cast<const unsigned long long*>(P.track_f)[bi * 16 + 3 + lane];
-      if (filled >= P.min_views) reinterpret_cast<unsigned long long*>(P.start_velocity)[bi * 3 + lane] = bits;
-      else P.start_velocity[bi * 3 + lane] = nan;
-    }
-  }
+  if constexpr (TIMED) ring_age(P.win_age + bi * W, lane, 64, W, 1, step);
+  ring_finish<TIMED>(step, lane, bi, W, P.min_views, wi, P.n_views, P.track_pose, P.start, P.track_f, P.start_velocity);
 }
 
 template <bool PRIOR>
@@ -163,14 +127,7 @@ static int window_push_launch(const char* fn, const char* what, const double* ta
                               int32_t max_obj, int32_t S, int32_t T, int32_t W, int32_t min_views, double max_speed, bool weighted, double conf_ref,
                               double conf_floor, double* win_obs, double* win_prior, double* win_views, int32_t* win_i, int32_t* n_views, double* start,
                               void* stream, bool timed = false, int32_t* win_age = nullptr, double* start_velocity = nullptr) {
-  if (B < 1) { okp_set_error("%s: B = %d; at least one stream", fn, B); return OKP_EINVAL; }
-  if (max_obj < 1) { okp_set_error("%s: max_obj = %d; a stream holds at least one object", fn, max_obj); return OKP_EINVAL; }
-  if (S < 1 || S > OKP_POSE_MAX_POINTS) { okp_set_error("%s: S = %d outside [1, %d] model points", fn, S, OKP_POSE_MAX_POINTS); return OKP_EINVAL; }
-  if (T < 1 || T > OKP_TRACK_MAX_TRACKS) { okp_set_error("%s: T = %d outside [1, %d] track slots", fn, T, OKP_TRACK_MAX_TRACKS); return OKP_EINVAL; }
-  if (W < 1 || W > OKP_REFINE_MAX_VIEWS) { okp_set_error("%s: W = %d outside [1, %d] ticks", fn, W, OKP_REFINE_MAX_VIEWS); return OKP_EINVAL; }
-  if (min_views < 1 || min_views > W) { okp_set_error("%s: min_views = %d outside [1, W = %d]", fn, min_views, W); return OKP_EINVAL; }
-  if (!(max_speed > 0.0)) { okp_set_error("%s: max_speed = %g must be positive (metres per second; +inf: never reset)", fn, max_speed); return OKP_EINVAL; }
-  if ((long long)B * T > 0x7fffffffll) { okp_set_error("%s: B * T = %lld track slots do not fit one launch", fn, (long long)B * T); return OKP_EINVAL; }
+  if (int rc = window_scalars(fn, B, max_obj, S, T, W, nullptr, min_views, max_speed)) return rc;
   if (!cam) { okp_set_error("%s: null cam", fn); return OKP_EINVAL; }
   if (!(cam->fx > 0.0 && cam->fx < __builtin_inf() && cam->fy > 0.0 && cam->fy < __builtin_inf())) {
     okp_set_error("%s: cam fx = %g, fy = %g must be positive and finite", fn, (double)cam->fx, (double)cam->fy);
@@ -184,12 +141,11 @@ static int window_push_launch(const char* fn, const char* what, const double* ta
     okp_set_error("%s: conf_floor = %g outside (0, conf_ref = %g]", fn, conf_floor, conf_ref);
     return OKP_EINVAL;
   }
-  const struct { const void* ptr; const char* name; } required[] = {
+  const NamedArg required[] = {
       {tab, "tab"}, {assignment, "assignment"}, {status, "status"}, {meas_of, "meas_of"}, {track_i, "track_i"}, {track_f, "track_f"},
       {track_pose, "track_pose"}, {T_WC, "T_WC"}, {win_obs, "win_obs"}, {win_views, "win_views"}, {win_i, "win_i"}, {n_views, "n_views"},
       {start, "start"}};
-  for (const auto& r : required)
-    if (!r.ptr) { okp_set_error("%s: null %s", fn, r.name); return OKP_EINVAL; }
+  if (int rc = require_args(fn, required)) return rc;
   if (weighted && !win_prior) { okp_set_error("%s: null win_prior", fn); return OKP_EINVAL; }
   if (timed && !win_age) { okp_set_error("%s: null win_age", fn); return OKP_EINVAL; }
   if (timed && !start_velocity) { okp_set_error("%s: null start_velocity", fn); return OKP_EINVAL; }

@@ -2020,21 +2020,29 @@ def window_state(B, max_tracks, S, ticks, device, prior=False, timed=False):
     rows), and "win_n" [B] int32 filled with T (every slot is an "object"; free ones arrive with a NaN pose).  prior=True (a WindowConfig with
     confidence): also "win_prior" [B,T,S,W] float64, all NaN, the ring of the bearings' priors.  timed=True (a WindowConfig with motion): also
     "win_age" [B,T,W] int32, zeros, the age of every column in ticks."""
-    B, T, S, W = int(B), int(max_tracks), int(S), int(ticks)
-    if B < 1 or not 1 <= T <= TRACK_MAX_TRACKS or not 1 <= S <= POSE_MAX_POINTS or not 1 <= W <= REFINE_MAX_VIEWS:
-        raise OkpError(f"window_state: B = {B} streams (at least 1) of max_tracks = {T} slots (1 .. {TRACK_MAX_TRACKS}), S = {S} model rows (1 .. {POSE_MAX_POINTS}), "
-                       f"ticks = {W} (1 .. {REFINE_MAX_VIEWS})")
+    return _window_state("window_state", B, max_tracks, S, ticks, None, device, prior, timed)
+
+
+def _window_state(fn, B, max_tracks, S, ticks, n_views, device, prior, timed):
+    """window_state (n_views = None: a column is one view) and window_views_state (a column is n_views views) behind one constructor."""
+    B, T, S, W, V = int(B), int(max_tracks), int(S), int(ticks), None if n_views is None else int(n_views)
+    if B < 1 or not 1 <= T <= TRACK_MAX_TRACKS or not 1 <= S <= POSE_MAX_POINTS or not 1 <= W <= REFINE_MAX_VIEWS or not (V is None or 1 <= V <= 2 * RIG_MAX_PAIRS):
+        raise OkpError(f"{fn}: B = {B} streams (at least 1) of max_tracks = {T} slots (1 .. {TRACK_MAX_TRACKS}), S = {S} model rows (1 .. {POSE_MAX_POINTS}), "
+                       f"ticks = {W} (1 .. {REFINE_MAX_VIEWS})" + ("" if V is None else f", n_views = {V} cameras (1 .. {2 * RIG_MAX_PAIRS})"))
+    if V is not None and W * V > REFINE_WIDE_MAX_VIEWS:
+        raise OkpError(f"{fn}: ticks x n_views = {W} x {V} = {W * V} views exceed the {REFINE_WIDE_MAX_VIEWS} of okp_refine_pose_views_wide")
     device = torch.device(device)
     if device.type != "cuda":
-        raise OkpError("window_state: the window's state lives in device memory: the HIP path has no CPU fallback")
-    state = {"win_obs": torch.full((B, T, S, W, 2), float("nan"), dtype=torch.float64, device=device),
-             "win_views": torch.zeros((B, T, W, 14), dtype=torch.float64, device=device), "win_i": torch.zeros((B, T, 4), dtype=torch.int32, device=device),
+        raise OkpError(f"{fn}: the window's state lives in device memory: the HIP path has no CPU fallback")
+    WV = W if V is None else W * V
+    state = {"win_obs": torch.full((B, T, S, WV, 2), float("nan"), dtype=torch.float64, device=device),
+             "win_views": torch.zeros((B, T, WV, 14), dtype=torch.float64, device=device), "win_i": torch.zeros((B, T, 4), dtype=torch.int32, device=device),
              "win_assignment": torch.arange(S, dtype=torch.int32, device=device).repeat(B, T, 1).contiguous(),
              "win_n": torch.full((B,), T, dtype=torch.int32, device=device)}
     if prior:
-        state["win_prior"] = torch.full((B, T, S, W), float("nan"), dtype=torch.float64, device=device)
+        state["win_prior"] = torch.full((B, T, S, WV), float("nan"), dtype=torch.float64, device=device)
     if timed:
-        state["win_age"] = torch.zeros((B, T, W), dtype=torch.int32, device=device)
+        state["win_age"] = torch.zeros((B, T, WV), dtype=torch.int32, device=device)
     return state
 
 
@@ -2055,6 +2063,15 @@ def window_push(state, tab, assignment, status, track, T_WC, cam, cfg):
         raise OkpError("cfg must be an ops.WindowConfig")
     if not isinstance(cam, _lib.okp_camera):
         raise OkpError(f"cam must be an okp_camera (make_camera), not {type(cam).__name__}")
+    return _window_push("window_push", state, "tab", tab, assignment, status, track, "T_WC", T_WC, cfg, cam=cam)
+
+
+def _window_push(op, state, table_name, table, assignment, status, track, pose_name, frame_pose, cfg, cam=None, views=None, prior=None):
+    """window_push (table: tab, with cam) and window_push_views (table: obs, with views [V,14] and, under cfg.confidence, prior) from the track dict
+    on: the same unpacking, the same walk over the tensors, the same three launches by what the state holds."""
+    rig = op == "window_push_views"
+    what, maker = ("the bearings", "window_views_state") if rig else ("the table", "window_state")
+    noun = what + ("'" if rig else "'s")
     try:
         meas_of, track_i, track_f, track_pose = track["meas_of"], track["track_i"], track["track_f"], track["track_pose"]
     except (TypeError, KeyError, IndexError):
@@ -2062,73 +2079,81 @@ def window_push(state, tab, assignment, status, track, T_WC, cam, cfg):
     try:
         win_obs, win_views, win_i = state["win_obs"], state["win_views"], state["win_i"]
     except (TypeError, KeyError, IndexError):
-        raise OkpError("state must be the dict of ops.window_state") from None
-    for name, t in (("tab", tab), ("assignment", assignment), ("status", status), ("meas_of", meas_of), ("track_i", track_i), ("track_f", track_f),
-                    ("track_pose", track_pose), ("T_WC", T_WC), ("win_obs", win_obs), ("win_views", win_views), ("win_i", win_i)):
+        raise OkpError(f"state must be the dict of ops.{maker}") from None
+    for name, t in ((table_name, table), ("assignment", assignment), ("status", status), ("meas_of", meas_of), ("track_i", track_i), ("track_f", track_f),
+                    ("track_pose", track_pose), (pose_name, frame_pose), *((("views", views),) if rig else ()), ("win_obs", win_obs), ("win_views", win_views),
+                    ("win_i", win_i)):
         require_cuda(t, name)
-    if tab.dtype != torch.float64 or tab.dim() != 4 or tab.shape[3] != 4:
-        raise OkpError("tab must be float64 [B,max_obj,S,4] (object_points)")
-    b, max_obj, s = (int(v) for v in tab.shape[:3])
-    dev = tab.device
-    if not 1 <= s <= POSE_MAX_POINTS:
-        raise OkpError(f"tab [{b},{max_obj},{s},4]: at most {POSE_MAX_POINTS} model points")
+    w = cfg.ticks
+    if rig:
+        if table.dtype != torch.float64 or table.dim() != 5 or table.shape[4] != 2:
+            raise OkpError("obs must be float64 [B,max_obj,S,V,2] (rig_bearings)")
+        b, max_obj, s, v = (int(x) for x in table.shape[:4])
+        if not 1 <= s <= POSE_MAX_POINTS or not 1 <= v <= 2 * RIG_MAX_PAIRS:
+            raise OkpError(f"obs [{b},{max_obj},{s},{v},2]: at most {POSE_MAX_POINTS} model points and {2 * RIG_MAX_PAIRS} cameras")
+        if w * v > REFINE_WIDE_MAX_VIEWS:
+            raise OkpError(f"cfg.ticks x V = {w} x {v} = {w * v} views exceed the {REFINE_WIDE_MAX_VIEWS} of okp_refine_pose_views_wide")
+    else:
+        if table.dtype != torch.float64 or table.dim() != 4 or table.shape[3] != 4:
+            raise OkpError("tab must be float64 [B,max_obj,S,4] (object_points)")
+        b, max_obj, s = (int(x) for x in table.shape[:3])
+        if not 1 <= s <= POSE_MAX_POINTS:
+            raise OkpError(f"tab [{b},{max_obj},{s},4]: at most {POSE_MAX_POINTS} model points")
+        v = 1
+    dev = table.device
     if assignment.dtype != torch.int32 or tuple(assignment.shape) != (b, max_obj, s) or status.dtype != torch.int32 or tuple(status.shape) != (b, max_obj) or \
             assignment.device != dev or status.device != dev:
-        raise OkpError(f"assignment must be int32 [{b},{max_obj},{s}] and status int32 [{b},{max_obj}] on the table's device (object_pose)")
+        raise OkpError(f"assignment must be int32 [{b},{max_obj},{s}] and status int32 [{b},{max_obj}] on {noun} device (object_pose)")
     if track_i.dtype != torch.int32 or track_i.dim() != 3 or track_i.shape[0] != b or track_i.shape[2] != 4 or not 1 <= track_i.shape[1] <= TRACK_MAX_TRACKS:
         raise OkpError(f"track_i must be int32 [{b},T,4] with T in [1, {TRACK_MAX_TRACKS}] (track_state)")
     t = int(track_i.shape[1])
-    w = cfg.ticks
     for name, x, dtype, shape in (("meas_of", meas_of, torch.int32, (b, t)), ("track_f", track_f, torch.float64, (b, t, 16)), ("track_pose", track_pose, torch.float64, (b, t, 12)),
-                                  ("T_WC", T_WC, torch.float64, (b, 12))):
+                                  (pose_name, frame_pose, torch.float64, (b, 12)), *((("views", views, torch.float64, (v, 14)),) if rig else ())):
         if x.dtype != dtype or tuple(x.shape) != shape or x.device != dev:
-            raise OkpError(f"{name} must be a {dtype} tensor {list(shape)} on the table's device")
+            raise OkpError(f"{name} must be a {dtype} tensor {list(shape)} on {noun} device")
     if track_i.device != dev:
-        raise OkpError(f"track_i is on {track_i.device}, the table on {dev}")
-    for name, x, dtype, shape in (("win_obs", win_obs, torch.float64, (b, t, s, w, 2)), ("win_views", win_views, torch.float64, (b, t, w, 14)),
+        raise OkpError(f"track_i is on {track_i.device}, {what} on {dev}")
+    made = f"{maker}({b}, {t}, {s}, cfg.ticks = {w}, " + (f"{v}, " if rig else "") + "device"
+    for name, x, dtype, shape in (("win_obs", win_obs, torch.float64, (b, t, s, w * v, 2)), ("win_views", win_views, torch.float64, (b, t, w * v, 14)),
                                   ("win_i", win_i, torch.int32, (b, t, 4))):
         if x.dtype != dtype or tuple(x.shape) != shape or x.device != dev or not x.is_contiguous():
-            raise OkpError(f"state[{name!r}] must be a contiguous {dtype} tensor {list(shape)} on the table's device: window_state({b}, {t}, {s}, cfg.ticks = {w}, device)")
-    win_prior = _win_prior(state, cfg, (b, t, s, w), dev, f"window_state({b}, {t}, {s}, cfg.ticks = {w}, device, prior=True)")
-    win_age = _win_age(state, cfg, (b, t, w), dev, f"window_state({b}, {t}, {s}, cfg.ticks = {w}, device, timed=True)")
+            raise OkpError(f"state[{name!r}] must be a contiguous {dtype} tensor {list(shape)} on {noun} device: {made})")
+    win_prior = _win_ring(state, "win_prior", cfg.confidence is not None, "cfg.confidence is set, so the window keeps a ring of priors", torch.float64, (b, t, s, w * v), dev,
+                          f"{made}, prior=True)")
+    win_age = _win_ring(state, "win_age", getattr(cfg, "motion", None) is not None, "cfg.motion is set, so the window keeps the age of its columns", torch.int32,
+                        (b, t, w * v), dev, f"{made}, timed=True)")
+    if prior is not None:
+        require_cuda(prior, "prior")
+        if prior.dtype != torch.float64 or tuple(prior.shape) != (b, max_obj, s, v) or prior.device != dev:
+            raise OkpError(f"prior must be float64 [{b},{max_obj},{s},{v}] on the bearings' device: one value for each bearing of obs (rig_bearings_weighted)")
     n_views = torch.empty((b, t), dtype=torch.int32, device=dev)
     start = torch.empty((b, t, 12), dtype=torch.float64, device=dev)
-    inputs = (_cam_list(cam), tab.contiguous(), assignment.contiguous(), status.contiguous(), meas_of.contiguous(), track_i.contiguous(), track_f.contiguous(),
-              track_pose.contiguous(), T_WC.contiguous(), cfg.min_views, cfg.max_speed)
+    inputs = (*((table.contiguous(),) if rig else (_cam_list(cam), table.contiguous())), *((prior.contiguous(),) if prior is not None else ()), assignment.contiguous(),
+              status.contiguous(), meas_of.contiguous(), track_i.contiguous(), track_f.contiguous(), track_pose.contiguous(), frame_pose.contiguous(),
+              *((views.contiguous(), w) if rig else ()), cfg.min_views, cfg.max_speed)
     if win_age is not None:
         start_velocity = torch.empty((b, t, 3), dtype=torch.float64, device=dev)
-        _dispatch(_ops().window_push_timed, *inputs, win_obs, win_age, win_views, win_i, n_views, start, start_velocity, stream_int())
+        _dispatch(getattr(_ops(), op + "_timed"), *inputs, win_obs, win_age, win_views, win_i, n_views, start, start_velocity, stream_int())
         return {"n_views": n_views, "start": start, "start_velocity": start_velocity}
     if win_prior is not None:
-        _dispatch(_ops().window_push_weighted, *inputs, cfg.confidence.ref, cfg.confidence.floor, win_obs, win_prior, win_views, win_i, n_views, start, stream_int())
+        _dispatch(getattr(_ops(), op + "_weighted"), *inputs, *((cfg.confidence.ref, cfg.confidence.floor) if not rig else ()), win_obs, win_prior, win_views, win_i, n_views,
+                  start, stream_int())
     else:
-        _dispatch(_ops().window_push, *inputs, win_obs, win_views, win_i, n_views, start, stream_int())
+        _dispatch(getattr(_ops(), op), *inputs, win_obs, win_views, win_i, n_views, start, stream_int())
     return {"n_views": n_views, "start": start}
 
 
-def _win_prior(state, cfg, shape, dev, made_by):
-    """state["win_prior"] of a window whose config has confidence set, checked; None without the keyword."""
-    if cfg.confidence is None:
+def _win_ring(state, key, wanted, why, dtype, shape, dev, made_by):
+    """state["win_prior"] of a window whose config has confidence set, state["win_age"] of one whose config has motion set, checked; None when the
+    config does not want it."""
+    if not wanted:
         return None
-    x = state.get("win_prior") if isinstance(state, dict) else None
+    x = state.get(key) if isinstance(state, dict) else None
     if x is None:
-        raise OkpError(f"state has no \"win_prior\": cfg.confidence is set, so the window keeps a ring of priors: {made_by}")
-    require_cuda(x, "win_prior")
-    if x.dtype != torch.float64 or tuple(x.shape) != shape or x.device != dev or not x.is_contiguous():
-        raise OkpError(f"state['win_prior'] must be a contiguous {torch.float64} tensor {list(shape)} on the window's device: {made_by}")
-    return x
-
-
-def _win_age(state, cfg, shape, dev, made_by):
-    """state["win_age"] of a window whose config has motion set, checked; None without the keyword."""
-    if getattr(cfg, "motion", None) is None:
-        return None
-    x = state.get("win_age") if isinstance(state, dict) else None
-    if x is None:
-        raise OkpError(f"state has no \"win_age\": cfg.motion is set, so the window keeps the age of its columns: {made_by}")
-    require_cuda(x, "win_age")
-    if x.dtype != torch.int32 or tuple(x.shape) != shape or x.device != dev or not x.is_contiguous():
-        raise OkpError(f"state['win_age'] must be a contiguous {torch.int32} tensor {list(shape)} on the window's device: {made_by}")
+        raise OkpError(f"state has no \"{key}\": {why}: {made_by}")
+    require_cuda(x, key)
+    if x.dtype != dtype or tuple(x.shape) != shape or x.device != dev or not x.is_contiguous():
+        raise OkpError(f"state[{key!r}] must be a contiguous {dtype} tensor {list(shape)} on the window's device: {made_by}")
     return x
 
 
@@ -2143,24 +2168,7 @@ def window_views_state(B, max_tracks, S, ticks, n_views, device, prior=False, ti
     int32, the identity, and "win_n" [B] int32 filled with T.  prior=True (a WindowConfig with confidence): also "win_prior" [B,T,S,W*V] float64,
     all NaN, the ring of the bearings' priors.  timed=True (a WindowConfig with motion): also "win_age" [B,T,W*V] int32, zeros, the age in ticks
     of every view's column."""
-    B, T, S, W, V = int(B), int(max_tracks), int(S), int(ticks), int(n_views)
-    if B < 1 or not 1 <= T <= TRACK_MAX_TRACKS or not 1 <= S <= POSE_MAX_POINTS or not 1 <= W <= REFINE_MAX_VIEWS or not 1 <= V <= 2 * RIG_MAX_PAIRS:
-        raise OkpError(f"window_views_state: B = {B} streams (at least 1) of max_tracks = {T} slots (1 .. {TRACK_MAX_TRACKS}), S = {S} model rows (1 .. {POSE_MAX_POINTS}), "
-                       f"ticks = {W} (1 .. {REFINE_MAX_VIEWS}), n_views = {V} cameras (1 .. {2 * RIG_MAX_PAIRS})")
-    if W * V > REFINE_WIDE_MAX_VIEWS:
-        raise OkpError(f"window_views_state: ticks x n_views = {W} x {V} = {W * V} views exceed the {REFINE_WIDE_MAX_VIEWS} of okp_refine_pose_views_wide")
-    device = torch.device(device)
-    if device.type != "cuda":
-        raise OkpError("window_views_state: the window's state lives in device memory: the HIP path has no CPU fallback")
-    state = {"win_obs": torch.full((B, T, S, W * V, 2), float("nan"), dtype=torch.float64, device=device),
-             "win_views": torch.zeros((B, T, W * V, 14), dtype=torch.float64, device=device), "win_i": torch.zeros((B, T, 4), dtype=torch.int32, device=device),
-             "win_assignment": torch.arange(S, dtype=torch.int32, device=device).repeat(B, T, 1).contiguous(),
-             "win_n": torch.full((B,), T, dtype=torch.int32, device=device)}
-    if prior:
-        state["win_prior"] = torch.full((B, T, S, W * V), float("nan"), dtype=torch.float64, device=device)
-    if timed:
-        state["win_age"] = torch.zeros((B, T, W * V), dtype=torch.int32, device=device)
-    return state
+    return _window_state("window_views_state", B, max_tracks, S, ticks, n_views, device, prior, timed)
 
 
 def window_push_views(state, obs, assignment, status, track, T_WB, views, cfg, prior=None):
@@ -2180,62 +2188,7 @@ def window_push_views(state, obs, assignment, status, track, T_WB, views, cfg, p
         raise OkpError("cfg must be an ops.WindowConfig")
     if (prior is None) != (cfg.confidence is None):
         raise OkpError("prior: the bearings' priors (rig_bearings_weighted) go with a WindowConfig whose confidence is set, and only with one")
-    try:
-        meas_of, track_i, track_f, track_pose = track["meas_of"], track["track_i"], track["track_f"], track["track_pose"]
-    except (TypeError, KeyError, IndexError):
-        raise OkpError("track must be the dict of ops.track_objects with the tracker's state (its \"meas_of\", \"track_i\", \"track_f\" and \"track_pose\")") from None
-    try:
-        win_obs, win_views, win_i = state["win_obs"], state["win_views"], state["win_i"]
-    except (TypeError, KeyError, IndexError):
-        raise OkpError("state must be the dict of ops.window_views_state") from None
-    for name, t in (("obs", obs), ("assignment", assignment), ("status", status), ("meas_of", meas_of), ("track_i", track_i), ("track_f", track_f),
-                    ("track_pose", track_pose), ("T_WB", T_WB), ("views", views), ("win_obs", win_obs), ("win_views", win_views), ("win_i", win_i)):
-        require_cuda(t, name)
-    if obs.dtype != torch.float64 or obs.dim() != 5 or obs.shape[4] != 2:
-        raise OkpError("obs must be float64 [B,max_obj,S,V,2] (rig_bearings)")
-    b, max_obj, s, v = (int(x) for x in obs.shape[:4])
-    dev = obs.device
-    w = cfg.ticks
-    if not 1 <= s <= POSE_MAX_POINTS or not 1 <= v <= 2 * RIG_MAX_PAIRS:
-        raise OkpError(f"obs [{b},{max_obj},{s},{v},2]: at most {POSE_MAX_POINTS} model points and {2 * RIG_MAX_PAIRS} cameras")
-    if w * v > REFINE_WIDE_MAX_VIEWS:
-        raise OkpError(f"cfg.ticks x V = {w} x {v} = {w * v} views exceed the {REFINE_WIDE_MAX_VIEWS} of okp_refine_pose_views_wide")
-    if assignment.dtype != torch.int32 or tuple(assignment.shape) != (b, max_obj, s) or status.dtype != torch.int32 or tuple(status.shape) != (b, max_obj) or \
-            assignment.device != dev or status.device != dev:
-        raise OkpError(f"assignment must be int32 [{b},{max_obj},{s}] and status int32 [{b},{max_obj}] on the bearings' device (object_pose)")
-    if track_i.dtype != torch.int32 or track_i.dim() != 3 or track_i.shape[0] != b or track_i.shape[2] != 4 or not 1 <= track_i.shape[1] <= TRACK_MAX_TRACKS:
-        raise OkpError(f"track_i must be int32 [{b},T,4] with T in [1, {TRACK_MAX_TRACKS}] (track_state)")
-    t = int(track_i.shape[1])
-    for name, x, dtype, shape in (("meas_of", meas_of, torch.int32, (b, t)), ("track_f", track_f, torch.float64, (b, t, 16)), ("track_pose", track_pose, torch.float64, (b, t, 12)),
-                                  ("T_WB", T_WB, torch.float64, (b, 12)), ("views", views, torch.float64, (v, 14))):
-        if x.dtype != dtype or tuple(x.shape) != shape or x.device != dev:
-            raise OkpError(f"{name} must be a {dtype} tensor {list(shape)} on the bearings' device")
-    if track_i.device != dev:
-        raise OkpError(f"track_i is on {track_i.device}, the bearings on {dev}")
-    for name, x, dtype, shape in (("win_obs", win_obs, torch.float64, (b, t, s, w * v, 2)), ("win_views", win_views, torch.float64, (b, t, w * v, 14)),
-                                  ("win_i", win_i, torch.int32, (b, t, 4))):
-        if x.dtype != dtype or tuple(x.shape) != shape or x.device != dev or not x.is_contiguous():
-            raise OkpError(f"state[{name!r}] must be a contiguous {dtype} tensor {list(shape)} on the bearings' device: "
-                           f"window_views_state({b}, {t}, {s}, cfg.ticks = {w}, {v}, device)")
-    win_prior = _win_prior(state, cfg, (b, t, s, w * v), dev, f"window_views_state({b}, {t}, {s}, cfg.ticks = {w}, {v}, device, prior=True)")
-    win_age = _win_age(state, cfg, (b, t, w * v), dev, f"window_views_state({b}, {t}, {s}, cfg.ticks = {w}, {v}, device, timed=True)")
-    if prior is not None:
-        require_cuda(prior, "prior")
-        if prior.dtype != torch.float64 or tuple(prior.shape) != (b, max_obj, s, v) or prior.device != dev:
-            raise OkpError(f"prior must be float64 [{b},{max_obj},{s},{v}] on the bearings' device: one value for each bearing of obs (rig_bearings_weighted)")
-    n_views = torch.empty((b, t), dtype=torch.int32, device=dev)
-    start = torch.empty((b, t, 12), dtype=torch.float64, device=dev)
-    inputs = (assignment.contiguous(), status.contiguous(), meas_of.contiguous(), track_i.contiguous(), track_f.contiguous(), track_pose.contiguous(),
-              T_WB.contiguous(), views.contiguous(), w, cfg.min_views, cfg.max_speed)
-    if win_age is not None:
-        start_velocity = torch.empty((b, t, 3), dtype=torch.float64, device=dev)
-        _dispatch(_ops().window_push_views_timed, obs.contiguous(), *inputs, win_obs, win_age, win_views, win_i, n_views, start, start_velocity, stream_int())
-        return {"n_views": n_views, "start": start, "start_velocity": start_velocity}
-    if win_prior is not None:
-        _dispatch(_ops().window_push_views_weighted, obs.contiguous(), prior.contiguous(), *inputs, win_obs, win_prior, win_views, win_i, n_views, start, stream_int())
-    else:
-        _dispatch(_ops().window_push_views, obs.contiguous(), *inputs, win_obs, win_views, win_i, n_views, start, stream_int())
-    return {"n_views": n_views, "start": start}
+    return _window_push("window_push_views", state, "obs", obs, assignment, status, track, "T_WB", T_WB, cfg, views=views, prior=prior)
 
 
 def refine_pose_views_wide(obs, views, pose, n_obj, model, cfg, each=False):

@@ -829,6 +829,18 @@ class _Window:
                 "status": refined["status"], pose_key: local, "velocity": refined["velocity"], "win_obs": st["win_obs"], "win_views": st["win_views"],
                 "win_i": st["win_i"], "win_age": st["win_age"]}
 
+    def _static(self, st, pushed, refined, T, pose_key, **tick):
+        """The entries of the step's "window" dict for a static object, from the state, the pushed dict and the refined dict: the refined poses
+        also back in the frame of T, under pose_key; `tick`: what a rig's tick puts right after them (its "tick_obs")."""
+        local = ops.change_frame(T, poses=refined["pose"], inverse=True)["poses"]
+        out = {"pose": refined["pose"], "fit": refined["fit"], "n_obs": refined["n_obs"], "n_views": pushed["n_views"], "information": refined["information"],
+               "status": refined["status"], pose_key: local, **tick, "win_obs": st["win_obs"], "win_views": st["win_views"], "win_i": st["win_i"]}
+        if "n_inlier" in refined:                # cfg.huber_px: the refinement was the Huber instance
+            out.update(n_inlier=refined["n_inlier"], weight=refined["weight"])
+        if "win_prior" in st:                    # cfg.confidence: the ring of priors, a state tensor like win_obs
+            out.update(prior=st["win_prior"])
+        return out
+
     def step(self, tab, assignment, status, track, T_WC, cam, model):
         """ops.window_push on the state of the table's device and streams, ops.refine_pose_views_each on that state from the pushed start, and
         the refined poses back in the camera frame -> the entries of the step's "window" dict."""
@@ -841,14 +853,7 @@ class _Window:
             refined = ops.refine_pose_views_weighted(st["win_obs"], st["win_prior"], st["win_views"], start, st["win_n"], model, self.cfg, each=True)
         else:
             refined = ops.refine_pose_views_each(st["win_obs"], st["win_views"], start, st["win_n"], model, self.cfg)
-        pose_C = ops.change_frame(T_WC, poses=refined["pose"], inverse=True)["poses"]
-        out = {"pose": refined["pose"], "fit": refined["fit"], "n_obs": refined["n_obs"], "n_views": pushed["n_views"], "information": refined["information"],
-               "status": refined["status"], "pose_C": pose_C, "win_obs": st["win_obs"], "win_views": st["win_views"], "win_i": st["win_i"]}
-        if "n_inlier" in refined:                # cfg.huber_px: the refinement was okp_refine_pose_views_robust
-            out.update(n_inlier=refined["n_inlier"], weight=refined["weight"])
-        if "win_prior" in st:                    # cfg.confidence: the ring of priors, a state tensor like win_obs
-            out.update(prior=st["win_prior"])
-        return out
+        return self._static(st, pushed, refined, T_WC, "pose_C")
 
     def reset(self):
         for st in self.states.values():
@@ -889,13 +894,9 @@ class _RigWindow(_Window):
             refined = ops.refine_pose_views_weighted(st["win_obs"], st["win_prior"], st["win_views"], start, st["win_n"], model, self.cfg, each=True, wide=True)
         else:
             refined = ops.refine_pose_views_wide(st["win_obs"], st["win_views"], start, st["win_n"], model, self.cfg, each=True)
-        pose_B = ops.change_frame(T_WB, poses=refined["pose"], inverse=True)["poses"]
-        out = {"pose": refined["pose"], "fit": refined["fit"], "n_obs": refined["n_obs"], "n_views": pushed["n_views"], "information": refined["information"],
-               "status": refined["status"], "pose_B": pose_B, "tick_obs": obs, "win_obs": st["win_obs"], "win_views": st["win_views"], "win_i": st["win_i"]}
-        if "n_inlier" in refined:                # cfg.huber_px: the Huber instance
-            out.update(n_inlier=refined["n_inlier"], weight=refined["weight"])
-        if "win_prior" in st:                    # cfg.confidence: the ring of priors, and the tick's
-            out.update(prior=st["win_prior"], tick_prior=prior)
+        out = self._static(st, pushed, refined, T_WB, "pose_B", tick_obs=obs)
+        if "win_prior" in st:                    # cfg.confidence: next to the ring of priors, the tick's
+            out.update(tick_prior=prior)
         return out
 
 

@@ -303,3 +303,135 @@ def test_six_ticks_of_a_moving_camera_eager_and_captured():
     torch.cuda.synchronize()
     for k, v in _snap(out).items():
         assert np.array_equal(v.view(np.uint8), eager[0][k].view(np.uint8)), k
+
+
+# ---- the three pushes of a family through both bindings (shared with tests/test_gpu_window_views.py) --------------------------------------------
+
+TINY = dict(max_obj=2, T=2, S=2, W=2, V=2)       # the smallest shapes at which the head wraps, c == head with V > 1 and a later slot replaces a row all occur
+KINDS = ("", "_weighted", "_timed")
+RING = {"": (), "_weighted": ("win_prior",), "_timed": ("win_age",)}
+WIN_I = {0: [[1, 1, 1], [1, 0, 2], [1, 0, 2], [1, 1, 1], [2, 1, 1], [0, 0, 0]],      # slot 0: fill, wrap the head, coast, speed reset, owner change, freed
+         1: [[7, 1, 1], [7, 0, 2], [7, 1, 2], [7, 0, 2], [7, 1, 2], [7, 0, 2]]}      # slot 1: pushed on every tick
+
+
+def six_ticks(B, rig, seed=21):
+    """Six ticks at the TINY shape.  Slot 0: a fill, a push that wraps the head, a coasting tick (not measured), a speed reset (with a push), an owner
+    change, a freed slot.  Slot 1: track 7, pushed on every tick by object 1, whose two table slots both take model row 0 - the later one replaces
+    the row.  max_speed is 0.5 -> per tick the inputs of the family's pushes (rig: obs, prior, T_WB; otherwise tab, T_WC)."""
+    rng = np.random.default_rng(seed)
+    max_obj, T, S, V = TINY["max_obj"], TINY["T"], TINY["S"], TINY["V"]
+    ticks = []
+    for id0, meas0, speed0 in ((1, 0, 0.1), (1, 0, 0.1), (1, -1, 0.1), (1, 0, 1.0), (2, 0, 0.1), (0, -1, 0.0)):
+        track_i = rng.integers(0, 9, size=(B, T, 4)).astype(np.int32)
+        track_i[:, 0, 0], track_i[:, 1, 0] = id0, 7
+        track_f = rng.normal(size=(B, T, 16))
+        v = rng.normal(size=(B, T, 3))
+        track_f[..., 3:6] = v / np.linalg.norm(v, axis=2, keepdims=True) * np.array([speed0, 0.2])[None, :, None]
+        track_pose = np.stack([[wc.rigid(rng) for _ in range(T)] for _ in range(B)])
+        if id0 == 0:
+            track_f[:, 0], track_pose[:, 0] = 0.0, np.nan
+        d = dict(assignment=np.tile(np.array([[0, 1], [0, 0]], dtype=np.int32), (B, 1, 1)), status=np.zeros((B, max_obj), dtype=np.int32),
+                 meas_of=np.tile(np.array([meas0, 1], dtype=np.int32), (B, 1)), track_i=track_i, track_f=track_f, track_pose=track_pose)
+        frame = np.stack([wc.rigid(rng) for _ in range(B)])
+        if rig:
+            d.update(obs=rng.uniform(-0.3, 0.3, size=(B, max_obj, S, V, 2)), prior=rng.uniform(0.3, 1.0, size=(B, max_obj, S, V)), T_WB=frame)
+            d["obs"][:, 0, 1, 1] = np.nan                                     # a camera that does not see a key point
+        else:
+            tab = np.concatenate([rng.uniform(-0.3, 0.3, size=(B, max_obj, S, 2)), rng.uniform(0.5, 1.5, size=(B, max_obj, S, 1)), rng.uniform(0.3, 1.0, size=(B, max_obj, S, 1))], axis=3)
+            d.update(tab=tab, T_WC=frame)
+        ticks.append(d)
+    return ticks
+
+
+def push_args(kind, rig, d, state, out, views=None):
+    """The positional arguments of a binding's window_push{_views}{kind} (without the stream) from a tick's device tensors, a state and the outputs."""
+    tail = (state["win_obs"], *(state[k] for k in RING[kind]), state["win_views"], state["win_i"], out["n_views"], out["start"], *((out["start_velocity"],) if kind == "_timed" else ()))
+    track = (d["assignment"], d["status"], d["meas_of"], d["track_i"], d["track_f"], d["track_pose"])
+    if rig:
+        return (d["obs"], *((d["prior"],) if kind == "_weighted" else ()), *track, d["T_WB"], views, TINY["W"], 2, 0.5, *tail)
+    return ([62.0, 63.0, 32.0, 32.0, 0.0, 0.0, 0.0, 0.0, 0.0], d["tab"], *track, d["T_WC"], 2, 0.5, *((0.8, 0.4) if kind == "_weighted" else ()), *tail)
+
+
+def fresh(B, kind, rig):
+    """An empty state of the kind's and outputs filled with what no push leaves."""
+    from object_keypoints_amd import ops
+    T, S, W, V = TINY["T"], TINY["S"], TINY["W"], TINY["V"]
+    kw = dict(prior=kind == "_weighted", timed=kind == "_timed")
+    state = ops.window_views_state(B, T, S, W, V, "cuda", **kw) if rig else ops.window_state(B, T, S, W, "cuda", **kw)
+    out = {"n_views": torch.full((B, T), 77, dtype=torch.int32, device="cuda"), "start": torch.full((B, T, 12), 7.0, dtype=torch.float64, device="cuda"),
+           "start_velocity": torch.full((B, T, 3), 7.0, dtype=torch.float64, device="cuda")}
+    return state, out
+
+
+def run_six_ticks(binding, kind, B, rig, views=None):
+    """-> per tick {name: host array} of the state tensors and the outputs the push of this kind writes."""
+    state, out = fresh(B, kind, rig)
+    fn = getattr(binding, ("window_push_views" if rig else "window_push") + kind)
+    written = STATE + RING[kind], ("n_views", "start") + (("start_velocity",) if kind == "_timed" else ())
+    snaps = []
+    for tick in six_ticks(B, rig):
+        fn(*push_args(kind, rig, {k: _dev(v) for k, v in tick.items()}, state, out, views), torch.cuda.current_stream().cuda_stream)
+        torch.cuda.synchronize()
+        snaps.append({**{k: state[k].cpu().numpy().copy() for k in written[0]}, **{k: out[k].cpu().numpy().copy() for k in written[1]}})
+    return snaps
+
+
+def check_six_ticks(B, rig, views=None):
+    """Each of the family's three pushes through the dispatcher and through _ctypes_ops, from the same empty state: the same bits in every state tensor
+    and output after every tick; the ring went through the events the ticks were written for; and the ring of bearings, the views, the control
+    words, n_views and start of the weighted and the timed push are the plain push's."""
+    from object_keypoints_amd import _ctypes_ops, _lib
+    assert _lib.torch_ops() is not None
+    plain = None
+    for kind in KINDS:
+        a, b = run_six_ticks(_lib.torch_ops(), kind, B, rig, views), run_six_ticks(_ctypes_ops, kind, B, rig, views)
+        for t, (x, y) in enumerate(zip(a, b)):
+            assert list(x) == list(y)
+            for k in x:
+                assert x[k].dtype == y[k].dtype and np.array_equal(x[k].view(np.uint8), y[k].view(np.uint8)), (kind, t, k)
+            for slot, want in WIN_I.items():
+                assert x["win_i"][:, slot, :3].tolist() == [want[t]] * B, (kind, t, slot, x["win_i"].tolist())
+            assert x["n_views"].tolist() == x["win_i"][..., 2].tolist()
+            assert np.array_equal(np.isfinite(x["start"]).all(axis=2), (x["win_i"][..., 2] >= 2) & (x["win_i"][..., 0] != 0))
+            if kind == "_timed":
+                assert np.array_equal(np.isfinite(x["start_velocity"]).all(axis=2), np.isfinite(x["start"]).all(axis=2))
+        plain = a if plain is None else plain
+        for t, (x, p) in enumerate(zip(a, plain)):
+            for k in p:
+                assert np.array_equal(x[k].view(np.uint8), p[k].view(np.uint8)), (kind, t, k)
+    return plain
+
+
+@pytest.mark.parametrize("B", (1, 2))
+def test_the_three_pushes_give_the_same_bits_through_both_bindings(B):
+    last = check_six_ticks(B, rig=False)[-1]
+    assert np.isnan(last["win_obs"][:, 0]).all() and not np.isnan(last["win_obs"][:, 1, 0]).any() and np.isnan(last["win_obs"][:, 1, 1]).all()   # slot 1: both table slots went to row 0
+
+
+def state_sentences(rig):
+    """(kind, state tensor, the sentence of the shim that names the state) for every state tensor of every push of the family."""
+    wv = "W*V" if rig else "W"
+    tail = "for the bearings' B, S and V and W = ticks" if rig else "for the table's B and S"
+    text = {"": f"okp: the window state is win_obs [B,T,S,{wv},2], win_views [B,T,{wv},14] and win_i [B,T,4] {tail}",
+            "_weighted": f"okp: the weighted window state is win_obs [B,T,S,{wv},2], win_prior [B,T,S,{wv}], win_views [B,T,{wv},14] and win_i [B,T,4] {tail}",
+            "_timed": f"okp: the timed window state is win_obs [B,T,S,{wv},2], win_age [B,T,{wv}], win_views [B,T,{wv},14] and win_i [B,T,4] {tail}"}
+    return [(kind, name, text[kind]) for kind in KINDS for name in STATE + RING[kind]]
+
+
+def check_the_shim_names_the_state(rig, views=None):
+    """Every op of the family with each of its state tensors one row too long: the dispatcher shim refuses with the sentence that names that state."""
+    import re
+    from object_keypoints_amd import _lib
+    T = _lib.torch_ops()
+    d = {k: _dev(v) for k, v in six_ticks(1, rig)[0].items()}
+    for kind, name, sentence in state_sentences(rig):
+        state, out = fresh(1, kind, rig)
+        x = state[name]
+        state[name] = torch.zeros((x.shape[0], x.shape[1], x.shape[2] + 1) + tuple(x.shape[3:]), dtype=x.dtype, device="cuda")
+        with pytest.raises(RuntimeError, match=re.escape(sentence)):
+            getattr(T, ("window_push_views" if rig else "window_push") + kind)(*push_args(kind, rig, d, state, out, views), torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+
+
+def test_the_shim_names_the_state_it_refuses():
+    check_the_shim_names_the_state(rig=False)

@@ -442,3 +442,19 @@ def test_the_rig_window_under_a_huber_loss_and_next_to_a_refinement():
     live = pipe.rig_tracks(out)
     assert live and all({"window_inliers", "window_robust_rmse", "window_outliers"} <= set(tr) for tr in live)
     assert all(len(entry) == 3 and 0 <= entry[1] < W and 0 <= entry[2] < 2 * PAIRS for tr in live for entry in tr["window_outliers"])
+
+
+# ---- the three pushes of the family through both bindings, and the shim's own refusals (the helpers of tests/test_gpu_window.py) -------------------
+
+def test_the_three_pushes_give_the_same_bits_through_both_bindings():
+    import test_gpu_window as tw
+    last = tw.check_six_ticks(1, rig=True, views=_dev(wvc.vc.views_of(tw.TINY["V"], seed=5)))[-1]
+    V = tw.TINY["V"]
+    ring = last["win_obs"].reshape(1, 2, 2, 2, V, 2)                       # [B,T,S,W,V,2]
+    assert np.isnan(ring[:, 0]).all() and not np.isnan(ring[:, 1, 0]).any() and np.isnan(ring[:, 1, 1]).all()     # slot 1: both table slots went to row 0
+    assert (last["win_views"][:, 1, :, 12] != 0).all()                     # every view of both columns has its focal length
+
+
+def test_the_shim_names_the_state_it_refuses():
+    import test_gpu_window as tw
+    tw.check_the_shim_names_the_state(rig=True, views=_dev(wvc.vc.views_of(tw.TINY["V"], seed=5)))

@@ -50,8 +50,9 @@ def test_header_ctypes_table_and_op_registry_agree_on_the_names():
     for name, mark in zip(("win_obs", "win_views", "win_i", "n_views", "start"), "abcde"):
         assert f"Tensor({mark}!) {name}" in schema, (name, schema)
     assert (spec.MAX_VIEWS, spec.MAX_TRACKS, spec.MAX_POINTS) == (ops.REFINE_MAX_VIEWS, ops.TRACK_MAX_TRACKS, ops.POSE_MAX_POINTS)
-    source = open(os.path.join(REPO, "object_keypoints_amd", "csrc", "okp_window.hip")).read()
-    assert "#pragma clang fp contract(off)" in source and "atomic" not in re.sub(r"//.*", "", source)
+    for name in ("okp_window.hip", "okp_window_ring.h"):                # the kernel and what it shares with the rig's (the ring's step, ages and finish)
+        source = open(os.path.join(REPO, "object_keypoints_amd", "csrc", name)).read()
+        assert "#pragma clang fp contract(off)" in source and "atomic" not in re.sub(r"//.*", "", source), name
     flat = " ".join(text.replace("\n *", " ").split())
     for word in ("WHATEVER its row holds", "Static objects only", "No robust loss", "uniform weights", "camera poses goes straight into the result", "BASELINE"):
         assert word in flat, word

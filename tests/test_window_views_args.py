@@ -53,9 +53,9 @@ def test_header_ctypes_table_and_op_registry_agree_on_the_names():
     schema = str(T.window_push_views.default._schema)
     for name, mark in zip(("win_obs", "win_views", "win_i", "n_views", "start"), "abcde"):
         assert f"Tensor({mark}!) {name}" in schema, (name, schema)
-    for source in ("okp_window_views.hip", "okp_refine_views_wide.hip"):
+    for source in ("okp_window_views.hip", "okp_window_ring.h", "okp_refine_views_wide.hip"):
         code = open(os.path.join(REPO, "object_keypoints_amd", "csrc", source)).read()
-        assert "#pragma clang fp contract(off)" in code and "atomic" not in re.sub(r"//.*", "", code)
+        assert "#pragma clang fp contract(off)" in code and "atomic" not in re.sub(r"//.*", "", code), source
     flat = " ".join(text.replace("\n *", " ").split())
     for word in ("BIT FOR BIT those of okp_refine_pose_views", "whatever its row holds", "counted once however many waves see them", "static objects only",
                  "replaces the WHOLE row", "TICKS, not views"):
