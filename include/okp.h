@@ -59,7 +59,9 @@ extern "C" {
                                     okp_window_push_timed, okp_window_push_views_timed, okp_refine_motion_views (the window refinement of a
                                     moving object: a ring that knows how old its columns are, a pose and a linear velocity);
                                     okp_score_objects, OKP_SCORE_* (key-point and pose accuracy of labelled scenes, tabulated on the device);
-                                    okp_preprocess_raw8, OKP_CFA_* (8-bit Bayer mosaics and mono8 camera frames straight into the network) */
+                                    okp_preprocess_raw8, OKP_CFA_* (8-bit Bayer mosaics and mono8 camera frames straight into the network);
+                                    okp_preprocess_raw8_color (those frames colour-corrected in the same launch: black level, white balance,
+                                    colour matrix, tone curve) */
 
 /* OKP_F16: IEEE half activations / weights, fp32 accumulate (BASELINE configs[4]).
  * OKP_F32X3 (okp_conv plans only): fp32 activations, weights and results like OKP_F32 - every tensor argument of such a plan is an
@@ -334,13 +336,37 @@ int okp_preprocess_yuv420(int dtype, const uint8_t* frames_dev, int32_t n, int32
  *   OKP_CFA_MONO                    R = G = B = M[y][x]; any src_h, src_w >= 1
  * Each tap of the bilinear resize demosaics its own sample: the output equals okp_preprocess_u8 of the demosaiced frames, bit for
  * bit; halo and fourth channel are zero.  Limits: bilinear only (no edge-directed demosaic); 8 bits only (no 10- or 12-bit packed
- * mosaics); no white balance, gamma or colour matrix (a sensor's raw colours are not the sRGB the weights were trained on); parity
- * with OpenCV's cvtColor(COLOR_Bayer*), whose pattern names differ from sensor_msgs', and with camera drivers' debayer is not
+ * mosaics); no white balance, gamma or colour matrix here (a sensor's raw colours are not the sRGB the weights were trained on:
+ * okp_preprocess_raw8_color below corrects them in the same launch); parity with OpenCV's cvtColor(COLOR_Bayer*), whose pattern names differ from sensor_msgs', and with camera drivers' debayer is not
  * pinned. */
 enum { OKP_CFA_RGGB = 0, OKP_CFA_BGGR = 1, OKP_CFA_GRBG = 2, OKP_CFA_GBRG = 3, OKP_CFA_MONO = 4 };
 int okp_preprocess_raw8(int dtype, const uint8_t* frames_dev, int32_t n, int32_t src_h, int32_t src_w, int32_t src_pitch,
                         int64_t src_frame_stride, int32_t cfa, int32_t resized_h, int32_t resized_w, int32_t crop_y, int32_t crop_x,
                         int32_t h, int32_t w, const float* mean3, const float* std3, void* out_dev, int32_t out_w, void* stream);
+
+/* okp_preprocess_raw8 with a colour correction in the same launch: a sensor delivers linear samples on a black pedestal, in its own
+ * primaries and with a green cast; the weights were trained on sRGB.  The specification is ours, in integers (no reference counterpart;
+ * in NumPy: tests/color_spec.py).  Per source frame, in this order:
+ *   1. black level and white balance, on the mosaic: a sample s at a site of colour c (R, G or B by `cfa`) becomes
+ *        min(255, (max(s - black, 0) * G_c + 2048) >> 12)      black in [0, 254]; G_c = gain3_q12[c] in [0, 65535], gain_c * 4096 rounded.
+ *      OKP_CFA_MONO: the sample is replicated to R = G = B first, then each channel takes its own G_c.
+ *   2. the demosaic of okp_preprocess_raw8 on the balanced mosaic: mirrored borders, the five candidates, round half up.
+ *   3. colour matrix, row-major M = matrix9_q12, every M_ij in [-65535, 65535] (m_ij * 4096 rounded; every term stays below 2^31):
+ *        out_i = clamp8((M_i0 * R + M_i1 * G + M_i2 * B + 2048) >> 12)     the shift is arithmetic (floor) on the signed sum;
+ *        clamp8 saturates to [0, 255].
+ *   4. tone curve, one table of 256 bytes for all three channels: out = curve256[out].
+ * Resize, crop, normalisation and packing follow as in okp_preprocess_u8; each tap of the bilinear resize corrects its own sample, so
+ * the output equals okp_preprocess_u8 of the corrected frames, bit for bit, for every dtype.  black 0, gains 4096, the identity
+ * matrix (4096 on the diagonal) and curve256[v] = v give okp_preprocess_raw8's bits.
+ * gain3_q12, matrix9_q12 and curve256 are HOST arrays, read before the call returns: the values travel in the kernel's arguments
+ * (the kernel stages the table into LDS), so a captured graph owns them and the caller manages no device buffer.
+ * Limits: 8-bit mosaics only; one curve for the three channels; no lens shading; no estimation of the gains (no auto white balance:
+ * the numbers are the camera's calibration, the caller's to supply); RGB and 4:2:0 input are not corrected; parity with a camera
+ * vendor's image pipeline or with OpenCV is not pinned. */
+int okp_preprocess_raw8_color(int dtype, const uint8_t* frames_dev, int32_t n, int32_t src_h, int32_t src_w, int32_t src_pitch,
+                              int64_t src_frame_stride, int32_t cfa, int32_t resized_h, int32_t resized_w, int32_t crop_y, int32_t crop_x,
+                              int32_t h, int32_t w, const float* mean3, const float* std3, void* out_dev, int32_t out_w, int32_t black,
+                              const int32_t* gain3_q12, const int32_t* matrix9_q12, const uint8_t* curve256, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * The 7x7 / stride-2 / pad-3 stem convolution 3 -> 128 + folded BatchNorm + ReLU in bf16 as its own kernel

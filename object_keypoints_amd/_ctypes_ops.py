@@ -252,6 +252,20 @@ def preprocess_raw8(frames, cfa, resized_h, resized_w, crop_y, crop_x, h, w, mea
                                               _floats3(mean), _floats3(std), out.data_ptr(), out.shape[2], stream), "okp_preprocess_raw8")
 
 
+def preprocess_raw8_color(frames, cfa, resized_h, resized_w, crop_y, crop_x, h, w, mean, std, out, black, gains, matrix, curve, stream):
+    n, sh, sw = frames.shape
+    pitch = frames.stride(1) if sh > 1 else sw
+    frame_stride = frames.stride(0) if n > 1 else sh * pitch
+    if len(gains) != 3 or len(matrix) != 9 or len(curve) != 256:
+        raise _lib.OkpError("okp: gains are 3, matrix 9 and curve 256 integers")
+    if any(not 0 <= int(v) <= 255 for v in curve):
+        raise _lib.OkpError("okp: curve holds bytes (0 .. 255)")
+    table = (ctypes.c_uint8 * 256).from_buffer_copy(bytes(curve))
+    _lib.check(_lib.lib().okp_preprocess_raw8_color(_okp_dtype(out.dtype), frames.data_ptr(), n, sh, sw, pitch, frame_stride, cfa, resized_h, resized_w, crop_y,
+                                                    crop_x, h, w, _floats3(mean), _floats3(std), out.data_ptr(), out.shape[2], black, _int32s(gains),
+                                                    _int32s(matrix), table, stream), "okp_preprocess_raw8_color")
+
+
 # ---- peaks, geometry, grouping -------------------------------------------------------------------------------------------------------------
 def peak_nms(heat, cap, count, yx, xyc, stream):
     n, k, h, w = heat.shape

@@ -96,6 +96,9 @@ SIGNATURES = [
                                       c_int32, c_int32, c_int32, POINTER(c_float), POINTER(c_float), c_void_p, c_int32, c_void_p]),
     ("okp_preprocess_raw8", c_int, [c_int, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32,
                                     c_int32, c_int32, POINTER(c_float), POINTER(c_float), c_void_p, c_int32, c_void_p]),
+    ("okp_preprocess_raw8_color", c_int, [c_int, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32,
+                                          c_int32, c_int32, POINTER(c_float), POINTER(c_float), c_void_p, c_int32, c_int32, POINTER(c_int32),
+                                          POINTER(c_int32), POINTER(ctypes.c_uint8), c_void_p]),
     ("okp_stem_create", c_void_p, [POINTER(c_float), POINTER(c_float)]),
     ("okp_stem_create_dtype", c_void_p, [c_int, POINTER(c_float), POINTER(c_float)]),
     ("okp_stem_destroy", None, [c_void_p]),

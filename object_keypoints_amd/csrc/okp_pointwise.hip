@@ -441,6 +441,128 @@ __global__ __launch_bounds__(256) void okp_preprocess_raw8_kernel(const uint8_t*
   }
 }
 
+// ---- the raw path with a colour correction (a kernel of its own: the instances above keep their code) ------------------------------------
+// Specification: include/okp.h, okp_preprocess_raw8_color.  Black level and white balance act on the 4 x 4 block as it is loaded (the
+// gain of a site follows from its parity, as its colour does), the demosaic above runs on the balanced block, and each of the four taps
+// goes through the matrix and the tone curve before the resize weighs it.  The curve travels in the kernel's arguments; a workgroup
+// stages it into LDS once.  Every product here has a factor of at most 8 bits and one of at most 17 with its sign, so the 24-bit
+// multiply (full rate, where the 32-bit one is quarter rate) is exact.
+struct ColorParams {
+  int32_t gain[3];            // Q12, [0, 65535]
+  int32_t bias[3];            // 2048 - black * gain: see balance_u8
+  int32_t m[9];               // Q12, row-major, [-65535, 65535]
+  uint32_t curve[64];         // the 256 bytes of the tone curve, little-endian words
+};
+
+// a * b + c on the low 24 bits of a and b, signed.  Spelled out: left to itself the compiler turns the products it cannot fold into an
+// addition back into 32-bit multiplies.
+__device__ __forceinline__ int mad24(int a, int b, int c) {
+  int r;
+  asm("v_mad_i32_i24 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
+  return r;
+}
+
+// min(255, (max(s - black, 0) * gain + 2048) >> 12) as clamp8((s * gain + bias) >> 12) with bias = 2048 - black * gain: at or above the
+// black level the sum is the specification's; below it the sum is under 2048, its floor shift at most 0, and the clamp gives the 0 the
+// specification gives.  |s * gain| and |bias| stay below 2^25.
+__device__ __forceinline__ int balance_u8(int s, int gain, int bias) {
+  const int u = mad24(s, gain, bias) >> 12;
+  return u < 0 ? 0 : (u > 255 ? 255 : u);
+}
+
+// one tap: colour matrix (arithmetic shift on the signed sum, saturated to 8 bits), then the curve
+__device__ __forceinline__ void matrix_curve(const ColorParams& cp, const uint8_t* lut, const int (&in)[3], int (&out)[3]) {
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    int u = mad24(cp.m[3 * i + 2], in[2], mad24(cp.m[3 * i + 1], in[1], mad24(cp.m[3 * i], in[0], 2048))) >> 12;
+    u = u < 0 ? 0 : (u > 255 ? 255 : u);
+    out[i] = (int)lut[u];
+  }
+}
+
+template <typename T, bool MONO>
+__global__ __launch_bounds__(256) void okp_preprocess_raw8_color_kernel(const uint8_t* __restrict__ in, int N, ResizeParams rp, RawParams bp,
+                                                                         ColorParams cp, T* __restrict__ out, int OHt, int OWt) {
+  __shared__ uint32_t lut32[64];
+  if (threadIdx.x < 64) lut32[threadIdx.x] = cp.curve[threadIdx.x];
+  __syncthreads();
+  const uint8_t* lut = (const uint8_t*)lut32;
+  const long total = (long)N * OHt * OWt;
+  for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
+    const int x = (int)(idx % OWt);
+    const long t = idx / OWt;
+    const int y = (int)(t % OHt);
+    const int n = (int)(t / OHt);
+    const int cy = y - 3, cx = x - 3;               // position inside the cropped frame
+    float v[3] = {0.f, 0.f, 0.f};
+    if (cy >= 0 && cy < rp.H && cx >= 0 && cx < rp.W) {
+      int sy0, sy1, b0, b1, sx0, sx1, a0, a1;
+      resize_coeff(cy + rp.cropY, rp.scaleY, rp.srcH, sy0, sy1, b0, b1);
+      resize_coeff(cx + rp.cropX, rp.scaleX, rp.srcW, sx0, sx1, a0, a1);
+      const uint8_t* f = in + (size_t)n * bp.frame_stride;
+      int q[2][2][3];                                 // the four taps, corrected
+      if constexpr (MONO) {
+        const uint8_t* r0 = f + (size_t)sy0 * bp.pitch;
+        const uint8_t* r1 = f + (size_t)sy1 * bp.pitch;
+        const int s[2][2] = {{(int)r0[sx0], (int)r0[sx1]}, {(int)r1[sx0], (int)r1[sx1]}};
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+          for (int j = 0; j < 2; ++j) {
+            int p[3];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) p[c] = balance_u8(s[i][j], cp.gain[c], cp.bias[c]);
+            matrix_curve(cp, lut, p, q[i][j]);
+          }
+      } else {
+        const int py0 = (sy0 ^ bp.ry) & 1, px0 = (sx0 ^ bp.rx) & 1;
+        // the gain of a site of parity (py0 ^ i, px0 ^ j): R at (0,0), B at (1,1), G elsewhere; block row r has i = (r ^ 1) & 1
+        int g[2][2], k[2][2];
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+          for (int j = 0; j < 2; ++j) {
+            const int py = py0 ^ i, px = px0 ^ j;
+            g[i][j] = py != px ? cp.gain[1] : (py ? cp.gain[2] : cp.gain[0]);
+            k[i][j] = py != px ? cp.bias[1] : (py ? cp.bias[2] : cp.bias[0]);
+          }
+        int m[4][4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const uint8_t* row = f + (size_t)mirror_index(sy0 - 1 + r, rp.srcH) * bp.pitch;
+#pragma unroll
+          for (int c = 0; c < 4; ++c) m[r][c] = balance_u8((int)row[mirror_index(sx0 - 1 + c, rp.srcW)], g[(r ^ 1) & 1][(c ^ 1) & 1], k[(r ^ 1) & 1][(c ^ 1) & 1]);
+        }
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+          for (int j = 0; j < 2; ++j) {
+            const int r = 1 + i, c = 1 + j;
+            const int py = py0 ^ i, px = px0 ^ j;
+            const int own = m[r][c];
+            const int cross = (m[r - 1][c] + m[r + 1][c] + m[r][c - 1] + m[r][c + 1] + 2) >> 2;
+            const int diag = (m[r - 1][c - 1] + m[r - 1][c + 1] + m[r + 1][c - 1] + m[r + 1][c + 1] + 2) >> 2;
+            const int horiz = (m[r][c - 1] + m[r][c + 1] + 1) >> 1;
+            const int vert = (m[r - 1][c] + m[r + 1][c] + 1) >> 1;
+            const bool green = py != px;
+            const int rowc = green ? horiz : own;       // the colour of this row's non-green sites: R in an R row (py == 0), B in a B row
+            const int colc = green ? vert : diag;       // the colour of the neighbouring rows' non-green sites
+            const int p[3] = {py ? colc : rowc, green ? own : cross, py ? rowc : colc};
+            matrix_curve(cp, lut, p, q[i][j]);
+          }
+      }
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const int h0 = __mul24(q[0][0][c], a0) + __mul24(q[0][1][c], a1);      // (weights within [0, 2048])
+        const int h1 = __mul24(q[1][0][c], a0) + __mul24(q[1][1][c], a1);
+        v[c] = normalise_u8(resize_vertical(h0, h1, b0, b1), rp.np, c);
+      }
+    }
+    T* o = out + idx * 4;
+    o[0] = (T)v[0]; o[1] = (T)v[1]; o[2] = (T)v[2]; o[3] = (T)0.f;
+  }
+}
+
 struct HeadParams {
   const void* src; int32_t src_ps;
   int32_t N, HW, n_out;
@@ -722,46 +844,103 @@ void launch_raw8(bool mono, int grid, hipStream_t stream, const uint8_t* frames,
   if (mono) hipLaunchKernelGGL((okp_preprocess_raw8_kernel<T, true>), dim3(grid), dim3(256), 0, stream, frames, n, rp, bp, (T*)out, OHt, OWt);
   else hipLaunchKernelGGL((okp_preprocess_raw8_kernel<T, false>), dim3(grid), dim3(256), 0, stream, frames, n, rp, bp, (T*)out, OHt, OWt);
 }
+template <typename T>
+void launch_raw8_color(bool mono, int grid, hipStream_t stream, const uint8_t* frames, int n, const ResizeParams& rp, const RawParams& bp,
+                       const ColorParams& cp, void* out, int OHt, int OWt) {
+  if (mono) hipLaunchKernelGGL((okp_preprocess_raw8_color_kernel<T, true>), dim3(grid), dim3(256), 0, stream, frames, n, rp, bp, cp, (T*)out, OHt, OWt);
+  else hipLaunchKernelGGL((okp_preprocess_raw8_color_kernel<T, false>), dim3(grid), dim3(256), 0, stream, frames, n, rp, bp, cp, (T*)out, OHt, OWt);
+}
+
+// the argument checks okp_preprocess_raw8 and okp_preprocess_raw8_color share (`fn` names the entry point in the message), and the
+// kernel parameters that follow from the arguments
+int raw8_args(const char* fn, int dtype, const uint8_t* frames, int32_t n, int32_t src_h, int32_t src_w, int32_t src_pitch, int64_t src_frame_stride,
+              int32_t cfa, int32_t resized_h, int32_t resized_w, int32_t crop_y, int32_t crop_x, int32_t h, int32_t w, const float* mean3,
+              const float* std3, const void* out, int32_t out_w, ResizeParams& rp, RawParams& bp) {
+  if (!frames || !out || !mean3 || !std3) { okp_set_error("%s: null argument", fn); return OKP_EINVAL; }
+  if (dtype != OKP_F32 && !okp_is16(dtype)) { okp_set_error("%s: bad dtype %d", fn, dtype); return OKP_EINVAL; }
+  if (cfa < OKP_CFA_RGGB || cfa > OKP_CFA_MONO) { okp_set_error("%s: unknown cfa %d", fn, cfa); return OKP_EINVAL; }
+  const bool mono = cfa == OKP_CFA_MONO;
+  if (n < 1 || src_h < 1 || src_w < 1) { okp_set_error("%s: %d frames of %dx%d", fn, n, src_h, src_w); return OKP_EINVAL; }
+  if (!mono && (src_h < 2 || src_w < 2 || (src_h & 1) || (src_w & 1))) {
+    okp_set_error("%s: %d frames of %dx%d: Bayer frames have an even height and width", fn, n, src_h, src_w);
+    return OKP_EINVAL;
+  }
+  if (src_pitch < src_w) { okp_set_error("%s: pitch %d is below the width %d", fn, src_pitch, src_w); return OKP_EINVAL; }
+  const int64_t frame_span = (int64_t)(src_h - 1) * src_pitch + src_w;
+  if (src_frame_stride < frame_span) {
+    okp_set_error("%s: frame stride %lld is below (src_h-1)*pitch + src_w = %lld", fn, (long long)src_frame_stride, (long long)frame_span);
+    return OKP_EINVAL;
+  }
+  if (resized_h < 1 || resized_w < 1 || h < 1 || w < 1 || crop_y < 0 || crop_x < 0 || crop_y + h > resized_h || crop_x + w > resized_w) {
+    okp_set_error("%s: crop %dx%d at (%d,%d) does not fit the resized frame %dx%d", fn, h, w, crop_y, crop_x, resized_h, resized_w);
+    return OKP_EINVAL;
+  }
+  if (out_w < w + 6) { okp_set_error("%s: out_w %d < w+6", fn, out_w); return OKP_EINVAL; }
+  rp.srcH = src_h; rp.srcW = src_w; rp.rsH = resized_h; rp.rsW = resized_w; rp.cropY = crop_y; rp.cropX = crop_x; rp.H = h; rp.W = w;
+  rp.scaleY = 1.0 / ((double)resized_h / (double)src_h);
+  rp.scaleX = 1.0 / ((double)resized_w / (double)src_w);
+  for (int c = 0; c < 3; ++c) { rp.np.mean[c] = mean3[c]; rp.np.stdv[c] = std3[c]; }
+  bp.pitch = src_pitch; bp.frame_stride = (size_t)src_frame_stride;
+  bp.ry = (cfa == OKP_CFA_BGGR || cfa == OKP_CFA_GBRG) ? 1 : 0;       // the parity of the R site's row and column
+  bp.rx = (cfa == OKP_CFA_BGGR || cfa == OKP_CFA_GRBG) ? 1 : 0;
+  return OKP_OK;
+}
 }  // namespace
 
 extern "C" int okp_preprocess_raw8(int dtype, const uint8_t* frames, int32_t n, int32_t src_h, int32_t src_w, int32_t src_pitch,
                                    int64_t src_frame_stride, int32_t cfa, int32_t resized_h, int32_t resized_w, int32_t crop_y, int32_t crop_x,
                                    int32_t h, int32_t w, const float* mean3, const float* std3, void* out, int32_t out_w, void* stream) {
-  if (!frames || !out || !mean3 || !std3) { okp_set_error("okp_preprocess_raw8: null argument"); return OKP_EINVAL; }
-  if (dtype != OKP_F32 && !okp_is16(dtype)) { okp_set_error("okp_preprocess_raw8: bad dtype %d", dtype); return OKP_EINVAL; }
-  if (cfa < OKP_CFA_RGGB || cfa > OKP_CFA_MONO) { okp_set_error("okp_preprocess_raw8: unknown cfa %d", cfa); return OKP_EINVAL; }
-  const bool mono = cfa == OKP_CFA_MONO;
-  if (n < 1 || src_h < 1 || src_w < 1) { okp_set_error("okp_preprocess_raw8: %d frames of %dx%d", n, src_h, src_w); return OKP_EINVAL; }
-  if (!mono && (src_h < 2 || src_w < 2 || (src_h & 1) || (src_w & 1))) {
-    okp_set_error("okp_preprocess_raw8: %d frames of %dx%d: Bayer frames have an even height and width", n, src_h, src_w);
-    return OKP_EINVAL;
-  }
-  if (src_pitch < src_w) { okp_set_error("okp_preprocess_raw8: pitch %d is below the width %d", src_pitch, src_w); return OKP_EINVAL; }
-  const int64_t frame_span = (int64_t)(src_h - 1) * src_pitch + src_w;
-  if (src_frame_stride < frame_span) {
-    okp_set_error("okp_preprocess_raw8: frame stride %lld is below (src_h-1)*pitch + src_w = %lld", (long long)src_frame_stride, (long long)frame_span);
-    return OKP_EINVAL;
-  }
-  if (resized_h < 1 || resized_w < 1 || h < 1 || w < 1 || crop_y < 0 || crop_x < 0 || crop_y + h > resized_h || crop_x + w > resized_w) {
-    okp_set_error("okp_preprocess_raw8: crop %dx%d at (%d,%d) does not fit the resized frame %dx%d", h, w, crop_y, crop_x, resized_h, resized_w);
-    return OKP_EINVAL;
-  }
-  if (out_w < w + 6) { okp_set_error("okp_preprocess_raw8: out_w %d < w+6", out_w); return OKP_EINVAL; }
   ResizeParams rp;
-  rp.srcH = src_h; rp.srcW = src_w; rp.rsH = resized_h; rp.rsW = resized_w; rp.cropY = crop_y; rp.cropX = crop_x; rp.H = h; rp.W = w;
-  rp.scaleY = 1.0 / ((double)resized_h / (double)src_h);
-  rp.scaleX = 1.0 / ((double)resized_w / (double)src_w);
-  for (int c = 0; c < 3; ++c) { rp.np.mean[c] = mean3[c]; rp.np.stdv[c] = std3[c]; }
   RawParams bp;
-  bp.pitch = src_pitch; bp.frame_stride = (size_t)src_frame_stride;
-  bp.ry = (cfa == OKP_CFA_BGGR || cfa == OKP_CFA_GBRG) ? 1 : 0;       // the parity of the R site's row and column
-  bp.rx = (cfa == OKP_CFA_BGGR || cfa == OKP_CFA_GRBG) ? 1 : 0;
+  const int rc = raw8_args("okp_preprocess_raw8", dtype, frames, n, src_h, src_w, src_pitch, src_frame_stride, cfa, resized_h, resized_w, crop_y, crop_x,
+                           h, w, mean3, std3, out, out_w, rp, bp);
+  if (rc != OKP_OK) return rc;
+  const bool mono = cfa == OKP_CFA_MONO;
   const long total = (long)n * (h + 6) * out_w;
   const int grid = grid_for(total, 256);
   if (dtype == OKP_BF16) launch_raw8<__bf16>(mono, grid, (hipStream_t)stream, frames, n, rp, bp, out, h + 6, out_w);
   else if (dtype == OKP_F16) launch_raw8<_Float16>(mono, grid, (hipStream_t)stream, frames, n, rp, bp, out, h + 6, out_w);
   else launch_raw8<float>(mono, grid, (hipStream_t)stream, frames, n, rp, bp, out, h + 6, out_w);
   return okp_check_hip(hipGetLastError(), "okp_preprocess_raw8 launch");
+}
+
+extern "C" int okp_preprocess_raw8_color(int dtype, const uint8_t* frames, int32_t n, int32_t src_h, int32_t src_w, int32_t src_pitch,
+                                         int64_t src_frame_stride, int32_t cfa, int32_t resized_h, int32_t resized_w, int32_t crop_y,
+                                         int32_t crop_x, int32_t h, int32_t w, const float* mean3, const float* std3, void* out, int32_t out_w,
+                                         int32_t black, const int32_t* gain3_q12, const int32_t* matrix9_q12, const uint8_t* curve256,
+                                         void* stream) {
+  static const char* fn = "okp_preprocess_raw8_color";
+  if (!gain3_q12) { okp_set_error("%s: null argument gain3_q12", fn); return OKP_EINVAL; }
+  if (!matrix9_q12) { okp_set_error("%s: null argument matrix9_q12", fn); return OKP_EINVAL; }
+  if (!curve256) { okp_set_error("%s: null argument curve256", fn); return OKP_EINVAL; }
+  ResizeParams rp;
+  RawParams bp;
+  const int rc = raw8_args(fn, dtype, frames, n, src_h, src_w, src_pitch, src_frame_stride, cfa, resized_h, resized_w, crop_y, crop_x, h, w, mean3,
+                           std3, out, out_w, rp, bp);
+  if (rc != OKP_OK) return rc;
+  if (black < 0 || black > 254) { okp_set_error("%s: black %d is outside [0, 254]", fn, black); return OKP_EINVAL; }
+  ColorParams cp;
+  for (int c = 0; c < 3; ++c) {
+    if (gain3_q12[c] < 0 || gain3_q12[c] > 65535) { okp_set_error("%s: gain3_q12[%d] = %d is outside [0, 65535]", fn, c, gain3_q12[c]); return OKP_EINVAL; }
+    cp.gain[c] = gain3_q12[c];
+    cp.bias[c] = 2048 - black * gain3_q12[c];
+  }
+  for (int i = 0; i < 9; ++i) {
+    if (matrix9_q12[i] < -65535 || matrix9_q12[i] > 65535) {
+      okp_set_error("%s: matrix9_q12[%d] = %d is outside [-65535, 65535]", fn, i, matrix9_q12[i]);
+      return OKP_EINVAL;
+    }
+    cp.m[i] = matrix9_q12[i];
+  }
+  for (int i = 0; i < 64; ++i)
+    cp.curve[i] = (uint32_t)curve256[4 * i] | (uint32_t)curve256[4 * i + 1] << 8 | (uint32_t)curve256[4 * i + 2] << 16 | (uint32_t)curve256[4 * i + 3] << 24;
+  const bool mono = cfa == OKP_CFA_MONO;
+  const long total = (long)n * (h + 6) * out_w;
+  const int grid = grid_for(total, 256);
+  if (dtype == OKP_BF16) launch_raw8_color<__bf16>(mono, grid, (hipStream_t)stream, frames, n, rp, bp, cp, out, h + 6, out_w);
+  else if (dtype == OKP_F16) launch_raw8_color<_Float16>(mono, grid, (hipStream_t)stream, frames, n, rp, bp, cp, out, h + 6, out_w);
+  else launch_raw8_color<float>(mono, grid, (hipStream_t)stream, frames, n, rp, bp, cp, out, h + 6, out_w);
+  return okp_check_hip(hipGetLastError(), "okp_preprocess_raw8_color launch");
 }
 
 extern "C" int okp_head_out_forward(int dtype, const okp_head_out_args* a, void* stream) {

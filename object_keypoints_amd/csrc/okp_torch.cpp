@@ -17,6 +17,8 @@
 #include <cstring>
 #include <torch/library.h>
 
+#include <algorithm>
+#include <climits>
 #include <tuple>
 #include <vector>
 
@@ -391,23 +393,53 @@ void preprocess_yuv420(const Tensor& frames, int64_t layout, int64_t matrix, boo
 
 // frames: uint8 [N, H, W] with stride(2) == 1, pitch = stride(1), frames stride(0) bytes apart (a view [..., :W] of pitched camera buffers
 // needs no copy); the stride of a dimension of size 1 says nothing and is replaced by the packed one
-void preprocess_raw8(const Tensor& frames, int64_t cfa, int64_t resized_h, int64_t resized_w, int64_t crop_y, int64_t crop_x, int64_t h, int64_t w,
-                     at::ArrayRef<double> mean, at::ArrayRef<double> std_, const Tensor& out, int64_t stream) {
+struct Raw8Geometry { int64_t n, sh, sw, pitch, frame_stride; };
+inline Raw8Geometry raw8_geometry(const Tensor& frames, const Tensor& out, int64_t h) {
   TORCH_CHECK(frames.is_cuda(), "okp: frames must be a device tensor: the HIP path has no CPU fallback");
   TORCH_CHECK(frames.scalar_type() == at::kByte && frames.dim() == 3 && frames.size(0) >= 1 && frames.size(1) >= 1 && frames.size(2) >= 1 &&
               (frames.size(2) == 1 || frames.stride(2) == 1), "okp: frames must be uint8 [N, H, W] with unit inner stride");
-  const int64_t n = frames.size(0), sh = frames.size(1), sw = frames.size(2);
-  const int64_t pitch = sh > 1 ? frames.stride(1) : sw;
-  const int64_t frame_stride = n > 1 ? frames.stride(0) : sh * pitch;
-  TORCH_CHECK(pitch >= sw && pitch <= INT32_MAX && frame_stride >= (sh - 1) * pitch + sw, "okp: frames must have pitch (stride(1)) >= W and lie "
+  Raw8Geometry g;
+  g.n = frames.size(0); g.sh = frames.size(1); g.sw = frames.size(2);
+  g.pitch = g.sh > 1 ? frames.stride(1) : g.sw;
+  g.frame_stride = g.n > 1 ? frames.stride(0) : g.sh * g.pitch;
+  TORCH_CHECK(g.pitch >= g.sw && g.pitch <= INT32_MAX && g.frame_stride >= (g.sh - 1) * g.pitch + g.sw, "okp: frames must have pitch (stride(1)) >= W and lie "
               "stride(0) >= (H-1) * pitch + W bytes apart");
-  TORCH_CHECK(out.is_cuda() && out.dim() == 4 && out.is_contiguous() && out.size(0) == n && out.size(1) == h + 6 && out.size(3) == 4,
+  TORCH_CHECK(out.is_cuda() && out.dim() == 4 && out.is_contiguous() && out.size(0) == g.n && out.size(1) == h + 6 && out.size(3) == 4,
               "okp: frames [N,H,W] uint8 -> out [N,h+6,wp,4]");
+  return g;
+}
+
+void preprocess_raw8(const Tensor& frames, int64_t cfa, int64_t resized_h, int64_t resized_w, int64_t crop_y, int64_t crop_x, int64_t h, int64_t w,
+                     at::ArrayRef<double> mean, at::ArrayRef<double> std_, const Tensor& out, int64_t stream) {
+  const Raw8Geometry g = raw8_geometry(frames, out, h);
   float m[3], sd[3]; three(mean, m, "mean"); three(std_, sd, "std");
-  check_rc(okp_preprocess_raw8(dtype_of(out), frames.data_ptr<uint8_t>(), (int32_t)n, (int32_t)sh, (int32_t)sw, (int32_t)pitch, frame_stride, (int32_t)cfa,
-                               (int32_t)resized_h, (int32_t)resized_w, (int32_t)crop_y, (int32_t)crop_x, (int32_t)h, (int32_t)w, m, sd, out.data_ptr(),
-                               (int32_t)out.size(2), sp(stream)),
+  check_rc(okp_preprocess_raw8(dtype_of(out), frames.data_ptr<uint8_t>(), (int32_t)g.n, (int32_t)g.sh, (int32_t)g.sw, (int32_t)g.pitch, g.frame_stride,
+                               (int32_t)cfa, (int32_t)resized_h, (int32_t)resized_w, (int32_t)crop_y, (int32_t)crop_x, (int32_t)h, (int32_t)w, m, sd,
+                               out.data_ptr(), (int32_t)out.size(2), sp(stream)),
            "okp_preprocess_raw8");
+}
+
+// the same with a colour correction (include/okp.h, okp_preprocess_raw8_color): the Q12 gains and matrix and the 256 bytes of the tone
+// curve come as int[], as mean and std come as float[]; their ranges are the entry point's to check, a byte's is checked here
+void preprocess_raw8_color(const Tensor& frames, int64_t cfa, int64_t resized_h, int64_t resized_w, int64_t crop_y, int64_t crop_x, int64_t h,
+                           int64_t w, at::ArrayRef<double> mean, at::ArrayRef<double> std_, const Tensor& out, int64_t black, at::IntArrayRef gains,
+                           at::IntArrayRef matrix, at::IntArrayRef curve, int64_t stream) {
+  const Raw8Geometry g = raw8_geometry(frames, out, h);
+  float m[3], sd[3]; three(mean, m, "mean"); three(std_, sd, "std");
+  TORCH_CHECK(gains.size() == 3 && matrix.size() == 9 && curve.size() == 256, "okp: gains are 3, matrix 9 and curve 256 integers");
+  int32_t g3[3], m9[9];
+  uint8_t table[256];
+  for (int i = 0; i < 3; ++i) g3[i] = (int32_t)std::min<int64_t>(std::max<int64_t>(gains[i], INT32_MIN), INT32_MAX);
+  for (int i = 0; i < 9; ++i) m9[i] = (int32_t)std::min<int64_t>(std::max<int64_t>(matrix[i], INT32_MIN), INT32_MAX);
+  for (int i = 0; i < 256; ++i) {
+    TORCH_CHECK(curve[i] >= 0 && curve[i] <= 255, "okp: curve holds bytes (0 .. 255)");
+    table[i] = (uint8_t)curve[i];
+  }
+  const int32_t black32 = (int32_t)std::min<int64_t>(std::max<int64_t>(black, INT32_MIN), INT32_MAX);
+  check_rc(okp_preprocess_raw8_color(dtype_of(out), frames.data_ptr<uint8_t>(), (int32_t)g.n, (int32_t)g.sh, (int32_t)g.sw, (int32_t)g.pitch,
+                                     g.frame_stride, (int32_t)cfa, (int32_t)resized_h, (int32_t)resized_w, (int32_t)crop_y, (int32_t)crop_x, (int32_t)h,
+                                     (int32_t)w, m, sd, out.data_ptr(), (int32_t)out.size(2), black32, g3, m9, table, sp(stream)),
+           "okp_preprocess_raw8_color");
 }
 
 inline int32_t* flag_ptr(const optional<Tensor>& f) {
@@ -1361,6 +1393,8 @@ TORCH_LIBRARY(okp, m) {
         "float[] mean, float[] std, Tensor(a!) out, int stream) -> ()", preprocess_yuv420);
   m.def("preprocess_raw8(Tensor frames, int cfa, int resized_h, int resized_w, int crop_y, int crop_x, int h, int w, float[] mean, float[] std, "
         "Tensor(a!) out, int stream) -> ()", preprocess_raw8);
+  m.def("preprocess_raw8_color(Tensor frames, int cfa, int resized_h, int resized_w, int crop_y, int crop_x, int h, int w, float[] mean, float[] std, "
+        "Tensor(a!) out, int black, int[] gains, int[] matrix, int[] curve, int stream) -> ()", preprocess_raw8_color);
   m.def("cast(Tensor src, Tensor(a!) dst, int stream, Tensor(b!)? range_flag=None) -> ()", cast);
   m.def("add_f16_f32(Tensor a, Tensor b, Tensor(a!) out, int act, int stream, Tensor(b!)? range_flag=None) -> ()", add_f16_f32);
   m.def("dwconv3x3_forward(Tensor src, int src_c0, int c, int conv_stride, Tensor w, Tensor bias, Tensor? res, int res_c0, Tensor(a!) out, int out_c0, int act, int stream) -> ()", dwconv3x3_forward);

@@ -8,6 +8,8 @@ Every wrapper checks its arguments and makes ONE call, `_dispatch(_ops().<entry 
 """
 import ctypes
 import dataclasses
+import functools
+import math
 import os
 
 import numpy as np
@@ -720,22 +722,115 @@ def preprocess_yuv420(frames, dtype, fmt, size=511, mean=RGB_MEAN, std=RGB_STD):
 _CFA_PATTERNS = {"rggb": _lib.CFA_RGGB, "bggr": _lib.CFA_BGGR, "grbg": _lib.CFA_GRBG, "gbrg": _lib.CFA_GBRG}
 
 
+def _number(x):
+    return isinstance(x, (int, float, np.integer, np.floating)) and not isinstance(x, (bool, np.bool_)) and math.isfinite(x)
+
+
+@functools.lru_cache(maxsize=None)
+def _tone_curve(gamma):
+    """The 256 bytes of a tone curve: floor(255 * f(v / 255) + 0.5) with f the identity (None), the sRGB transfer curve ("srgb") or
+    x ** (1 / gamma)."""
+    if gamma is None:
+        return tuple(range(256))
+    if gamma == "srgb":
+        f = lambda x: 12.92 * x if x <= 0.0031308 else 1.055 * math.pow(x, 1.0 / 2.4) - 0.055
+    else:
+        f = lambda x: math.pow(x, 1.0 / gamma)
+    return tuple(min(255, max(0, int(math.floor(255.0 * f(v / 255.0) + 0.5)))) for v in range(256))
+
+
+def _q12(x):
+    """A gain or matrix coefficient as the kernel takes it: x * 4096 rounded (Python's round), held to the 16 bits of |x| < 16."""
+    return max(-65535, min(65535, int(round(float(x) * 4096.0))))
+
+
+@dataclasses.dataclass(frozen=True)
+class ColorCorrection:
+    """The colour correction of raw camera frames, run inside the pre-processing launch (include/okp.h, okp_preprocess_raw8_color; in
+    NumPy: tests/color_spec.py), in this order: `black_level` (an integer in [0, 254]) is subtracted from every sample and the result
+    multiplied by the white-balance gain of its colour (`gains`: R, G, B in [0, 16)) on the mosaic; the demosaic; `matrix` (3 x 3, the
+    sensor's RGB -> the RGB the weights were trained on, |m| < 16; None = identity); and a tone curve, `gamma`: None (identity), "srgb"
+    (the sRGB transfer curve) or a positive number g (x ** (1 / g)).  All of it is integer arithmetic on Q12 roundings of these numbers
+    (gains_q12, matrix_q12) and one table of 256 bytes (curve).  The numbers are a camera's calibration: nothing here estimates them.
+    ColorCorrection() changes no sample, yet it is a correction: frames whose format carries it take the correcting kernel."""
+    black_level: int = 0
+    gains: tuple = (1.0, 1.0, 1.0)
+    matrix: tuple = None
+    gamma: object = None
+
+    def __post_init__(self):
+        b = self.black_level
+        if isinstance(b, (bool, np.bool_)) or not isinstance(b, (int, np.integer)) or not 0 <= b <= 254:
+            raise OkpError(f"black_level is an integer in [0, 254], not {b!r}")
+        object.__setattr__(self, "black_level", int(b))
+        try:
+            gains = tuple(self.gains)
+        except TypeError:
+            gains = ()
+        if len(gains) != 3 or not all(_number(g) and 0 <= g < 16 for g in gains):
+            raise OkpError(f"gains are three finite numbers in [0, 16) (R, G, B), not {self.gains!r}")
+        object.__setattr__(self, "gains", tuple(float(g) for g in gains))
+        if self.matrix is not None:
+            try:
+                rows = tuple(tuple(r) for r in self.matrix)
+            except TypeError:
+                rows = ()
+            if len(rows) != 3 or any(len(r) != 3 for r in rows) or not all(_number(m) and abs(m) < 16 for r in rows for m in r):
+                raise OkpError(f"matrix is None or 3 x 3 finite numbers with |m| < 16, not {self.matrix!r}")
+            object.__setattr__(self, "matrix", tuple(tuple(float(m) for m in r) for r in rows))
+        g = self.gamma
+        if g is not None and not (isinstance(g, str) and g == "srgb"):
+            if isinstance(g, str) or not _number(g) or not g > 0:
+                raise OkpError(f"gamma is None, 'srgb' or a positive finite number, not {g!r}")
+            object.__setattr__(self, "gamma", float(g))
+
+    @property
+    def gains_q12(self):
+        """(G_R, G_G, G_B): round(gain * 4096), each in [0, 65535]."""
+        return tuple(_q12(g) for g in self.gains)
+
+    @property
+    def matrix_q12(self):
+        """The nine coefficients round(m * 4096), row-major, each in [-65535, 65535]."""
+        rows = self.matrix if self.matrix is not None else ((1.0, 0.0, 0.0), (0.0, 1.0, 0.0), (0.0, 0.0, 1.0))
+        return tuple(_q12(m) for r in rows for m in r)
+
+    @property
+    def curve(self):
+        """The tone curve: 256 integers in [0, 255]."""
+        return _tone_curve(self.gamma)
+
+
+def _check_color(color):
+    if color is not None and not isinstance(color, ColorCorrection):
+        raise OkpError(f"color is None or a ColorCorrection, not {type(color).__name__}")
+
+
 @dataclasses.dataclass(frozen=True)
 class BayerFormat:
     """An 8-bit Bayer mosaic, one byte per pixel (include/okp.h, okp_preprocess_raw8): `pattern` names the colours of pixels (0,0), (0,1),
     (1,0), (1,1) as sensor_msgs does ("rggb", "bggr", "grbg", "gbrg": bayer_rggb8 and its siblings).  Frames are [N, H, W] uint8 with even
     H and W.  A view that starts at an odd row or column of a larger mosaic has another pattern (an odd column of "rggb" is "grbg", an odd
-    row "gbrg", both "bggr"): that is the caller's to name.  Bilinear demosaic only; no white balance, gamma or colour matrix."""
+    row "gbrg", both "bggr"): that is the caller's to name.  Bilinear demosaic only.  `color`: None - the sensor's raw colours go to the
+    network as they are - or a ColorCorrection (black level, white balance, colour matrix, tone curve) applied in the same launch
+    (okp_preprocess_raw8_color)."""
     pattern: str = "rggb"
+    color: object = None
 
     def __post_init__(self):
         if not isinstance(self.pattern, str) or self.pattern not in _CFA_PATTERNS:
             raise OkpError(f"unknown Bayer pattern {self.pattern!r}: 'rggb', 'bggr', 'grbg' or 'gbrg'")
+        _check_color(self.color)
 
 
 @dataclasses.dataclass(frozen=True)
 class Mono8Format:
-    """mono8 camera frames [N, H, W] uint8, any H, W >= 1: R = G = B = the sample (include/okp.h, okp_preprocess_raw8)."""
+    """mono8 camera frames [N, H, W] uint8, any H, W >= 1: R = G = B = the sample (include/okp.h, okp_preprocess_raw8).  `color`: None or
+    a ColorCorrection; the replicated sample takes each channel's gain, then the matrix and the curve (okp_preprocess_raw8_color)."""
+    color: object = None
+
+    def __post_init__(self):
+        _check_color(self.color)
 
 
 def check_raw8_frames(frames, fmt):
@@ -771,7 +866,9 @@ def check_raw8_frames(frames, fmt):
 def preprocess_raw8(frames, dtype, fmt, size=511, mean=RGB_MEAN, std=RGB_STD):
     """Raw camera frames uint8 [N, H, W] (device; a Bayer mosaic or mono8 as `fmt`, a BayerFormat or Mono8Format; pitch = stride(1) and
     frame stride = stride(0), so a view [..., :W] of pitched buffers is taken as it is) -> the packed stem input that preprocess_u8 makes
-    of the same frames demosaiced to RGB, bit for bit (okp_preprocess_raw8: demosaic, resize, centre crop and normalisation in one kernel)."""
+    of the same frames demosaiced to RGB, bit for bit (okp_preprocess_raw8: demosaic, resize, centre crop and normalisation in one kernel).
+    With fmt.color (a ColorCorrection) the frames are colour-corrected in that launch too (okp_preprocess_raw8_color): the result is what
+    preprocess_u8 makes of the corrected RGB frames, bit for bit."""
     n, sh, sw, pitch, frame_stride = check_raw8_frames(frames, fmt)
     rh, rw = smallest_max_size(sh, sw, size) if size >= 1 else (0, 0)
     if size < 1 or rh < size or rw < size:
@@ -782,7 +879,12 @@ def preprocess_raw8(frames, dtype, fmt, size=511, mean=RGB_MEAN, std=RGB_STD):
     cfa = _CFA_PATTERNS[fmt.pattern] if isinstance(fmt, BayerFormat) else _lib.CFA_MONO
     wp = stem_packed_width(size)
     out = torch.empty((n, size + 6, wp, 4), dtype=dtype, device=frames.device)
-    _dispatch(_ops().preprocess_raw8, frames, cfa, rh, rw, cy, cx, size, size, _f32_list(mean), _f32_list(std), out, stream_int())
+    color = fmt.color
+    if color is None:
+        _dispatch(_ops().preprocess_raw8, frames, cfa, rh, rw, cy, cx, size, size, _f32_list(mean), _f32_list(std), out, stream_int())
+    else:
+        _dispatch(_ops().preprocess_raw8_color, frames, cfa, rh, rw, cy, cx, size, size, _f32_list(mean), _f32_list(std), out, color.black_level,
+                  list(color.gains_q12), list(color.matrix_q12), list(color.curve), stream_int())
     return _packed(out, size, size)
 
 

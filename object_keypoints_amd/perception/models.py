@@ -107,7 +107,8 @@ class KeypointNet(_HipModule):
         # device by the same pre-processing kernel (ops.preprocess_yuv420, to raw_frame_size); None = 4:2:0 frames are refused.
         # ops.BayerFormat / ops.Mono8Format: a 3-D uint8 tensor [N, H, W] is taken as a camera's 8-bit Bayer mosaic / mono8 frames and
         # demosaiced on the device likewise (ops.preprocess_raw8).  A 3-D tensor is dispatched by the type of frame_format; a view that
-        # starts at an odd row or column of a larger mosaic has another pattern, which is the caller's to name.
+        # starts at an odd row or column of a larger mosaic has another pattern, which is the caller's to name.  A format's `color` (an
+        # ops.ColorCorrection) travels with it: the same launch then corrects the sensor's colours (okp_preprocess_raw8_color).
         # 4-D uint8 frames are RGB either way.
         self.frame_format = frame_format
         # Split-product configurations halve fp32 values into fp16: a value beyond +-65504 has no halves (inf, -inf -> NaN products, which the
