@@ -39,7 +39,7 @@ def _sources():
 def _deps():
     return [os.path.join(REPO, "include", "okp.h"), os.path.join(CSRC, "okp_internal.h"),
             os.path.join(CSRC, "okp_igemm_kernel.h"), os.path.join(CSRC, "okp_pose_math.h"), os.path.join(CSRC, "okp_window_ring.h"),
-            os.path.abspath(__file__)]
+            os.path.join(CSRC, "okp_stamps.h"), os.path.abspath(__file__)]
 
 
 def _stale(target, deps):
@@ -49,10 +49,13 @@ def _stale(target, deps):
     return any(os.path.getmtime(d) > t for d in deps)
 
 
-def _parse_resources(stderr):
-    """-Rpass-analysis=kernel-resource-usage remarks -> {kernel symbol: {"vgprs", "agprs", "scratch", "vgpr_spill", "sgpr_spill"}}."""
+RESOURCE_KEYS = {"VGPRs": "vgprs", "AGPRs": "agprs", "ScratchSize [bytes/lane]": "scratch", "VGPRs Spill": "vgpr_spill", "SGPRs Spill": "sgpr_spill"}
+
+
+def _parse_resources(stderr, keys=RESOURCE_KEYS):
+    """-Rpass-analysis=kernel-resource-usage remarks -> {kernel symbol: {"vgprs", "agprs", "scratch", "vgpr_spill", "sgpr_spill"}}
+    (keys: remark name -> name in the result; scripts/kernel_resources.py asks for LDS and occupancy as well)."""
     out, cur = {}, None
-    keys = {"VGPRs": "vgprs", "AGPRs": "agprs", "ScratchSize [bytes/lane]": "scratch", "VGPRs Spill": "vgpr_spill", "SGPRs Spill": "sgpr_spill"}
     for line in stderr.splitlines():
         m = re.search(r"remark: .*?Function Name: (\S+)", line)
         if m:

@@ -27,23 +27,20 @@
 //    3 x 6 window), weights in registers for the duration of the phase.
 #include <cstdio>
 #include <cstring>
-
 #include <cstdlib>
 
 #include "okp_internal.h"
-
-// Timing ablations (wrong results, right timing; experiment builds only): OKP_F2_ABL_NOSTORE drops every output store, OKP_F2_ABL_NOX the
-// x requests of every tile but a workgroup's first, OKP_F2_ABL_NOSKIP the skip values, OKP_F2_ABL_NODW the depth-wise branch's MFMAs and reads,
-// OKP_F2_ABL_NOWEIGHTS the weight stream.
-#ifdef OKP_F2_ABL_NOSTORE
-#define F2_STORE_(v, rs, off) do { if ((off) == 0x7ffffff0u) __builtin_amdgcn_raw_buffer_store_b128(v, rs, (int)(off), 0, 0); } while (0)
+// Debug build (okp_stamps.h): stamps at the phase boundaries of a workgroup's SECOND tile (slots 0..4) and around the whole kernel (5..7)
+#ifdef OKP_FIRE_STAMPS
+#include "okp_stamps.h"
 #else
-#define F2_STORE_(v, rs, off) __builtin_amdgcn_raw_buffer_store_b128(v, rs, (int)(off), 0, 0)
+#define OKP_FIRE_STAMP(cond, nw, i) do {} while (0)
 #endif
+
 // every output store; the range-guarded instances (G) fold what they store into range_h (pixels outside the map - offset kInvalid - are not stored)
 #define F2_STORE(v, rs, off) do { \
     if constexpr (G) { if ((uint32_t)(off) < kInvalid) range_h = okp_range_max_h8(range_h, v); } \
-    F2_STORE_(v, rs, off); } while (0)
+    __builtin_amdgcn_raw_buffer_store_b128(v, rs, (int)(off), 0, 0); } while (0)
 
 
 namespace {
@@ -60,19 +57,12 @@ constexpr int MAXIH = 6;                         // interior rows per tile (dept
 // blocks instead of eight) divide the 64-, 32- and 16-row maps and give the 512 resident workgroups a whole number of tiles at 64 x 64 (8 each; 5-row
 // tiles: 6.5) - measured level at 32 x 32 and 16 x 16 and 5 % slower at 64 x 64 (profiles/r06t_ab_fire2_fixed_geometry.txt): the per-tile fixed
 // cost (eight k-step barriers, the phase changes) outweighs the even split
-#ifndef OKP_F2_DIH
-#define OKP_F2_DIH 5
-#endif
-constexpr int kDwmIH = OKP_F2_DIH;
-static_assert(kDwmIH >= 1 && kDwmIH <= 5, "DWM tile: (rows + 2) x 18 squeeze pixels <= SP");
+constexpr int kDwmIH = 5;
+static_assert((kDwmIH + 2) * 18 <= SP, "DWM tile: (rows + 2) x 18 squeeze pixels <= SP");
 // bytes per ring stage.  +64: a depth-wise thread takes its skip values from FOUR stages of one ring row (RING_SKIP: stage = channel group / 4);
 // with stages a multiple of 256 bytes apart those four 64-byte pieces sit in the same banks (4-way conflict), 64 bytes further each they cover
 // the 64 banks once
-#ifdef OKP_F2_NO_REMAP
-constexpr int XST = SP * 64;
-#else
 constexpr int XST = SP * 64 + 64;
-#endif
 
 template <int MID> struct FireLds {
   static constexpr int OFF_S = 0;                         // [128][MID x 2 B] squeeze tile, 16-B chunks XOR-swizzled by the row
@@ -121,17 +111,6 @@ __device__ __forceinline__ void wait_vm(int n) {   // s_waitcnt vmcnt(n) for a w
   }
 }
 
-#ifdef OKP_FIRE_STAMPS
-// Debug build (OKP_EXTRA_CFLAGS=-DOKP_FIRE_STAMPS, printed with OKP_FIRE_STAMPS_PRINT=1; scripts/probe_fire2.py): shader-clock stamps of every
-// wave at the phase boundaries of its workgroup's SECOND tile, workgroups 0..15: [wg][wave 8][8] u32.  OKP_FIRE_NOSKIP=1: timing ablation
-// without the skip requests (wrong results).
-#define F2_STAMP_ANY(i) do { if (lane == 0 && blockIdx.x < 16) { uint64_t t_; asm volatile("s_memtime %0\n s_waitcnt lgkmcnt(0)" : "=s"(t_) :: "memory"); p.dbg[(blockIdx.x * 8 + w) * 8 + (i)] = (uint32_t)t_; } } while (0)
-#define F2_STAMP(i) do { if (second && lane == 0 && blockIdx.x < 16) { uint64_t t_; asm volatile("s_memtime %0\n s_waitcnt lgkmcnt(0)" : "=s"(t_) :: "memory"); p.dbg[(blockIdx.x * 8 + w) * 8 + (i)] = (uint32_t)t_; } } while (0)
-#else
-#define F2_STAMP(i) do {} while (0)
-#define F2_STAMP_ANY(i) do {} while (0)
-#endif
-
 // DWM: the depth-wise branch on the MATRIX pipe (stride 1, interior tiles 16 pixels wide).  The kernel is bound by vector-ALU issue
 // (1 880 VALU instructions per wave and tile beside 176 MFMAs; the depth-wise block alone: 216 packed FMAs + 264 unpacking shifts / masks +
 // the epilogue = 716), while the matrix pipe idles three quarters of the time.  A depth-wise 3x3 is, per tap, a DIAGONAL 32 x 32 matrix
@@ -162,51 +141,20 @@ __global__ __launch_bounds__(MID * 2, MID == 128 ? 2 : 1) void okp_fire2_kernel(
   constexpr int HALF = MID;
   constexpr int KS1 = CIN / 32;                    // squeeze k-steps
   constexpr int KS2 = MID / 32;                    // expand k-steps
-  // Squeeze weights: streamed from L2 in fragment order for every instance (three rotating register sets, or the LDS ring below).  The
-  // CIN = 256 instances kept them RESIDENT until round 5 (64 registers per lane for the whole kernel; -DOKP_F2_RESIDENT_W1 builds that
-  // form): streaming them frees 40 registers, which the depth-wise phase uses to keep DWB squeeze-row reads in flight before their
-  // FMAs - and the kernel no longer sits on 255 registers (the fp16 and stride-2 instances spilled two).  Same bits out; 64 x 64 alone
-  // 89 -> 87 us, 32 x 32 31.9 -> 30.9, bf16 step -0.6 % (profiles/r05u_ab_fire2_batch.txt).
-#ifdef OKP_F2_RESIDENT_W1
-  constexpr bool RES = CIN <= 256;
-  constexpr int DWB = 1;
-#else
-  constexpr bool RES = false;
-#ifdef OKP_F2_RESIDENT_WA
-  constexpr int DWB = (CIN == 256 && MID == 128) ? OKP_F2_RESIDENT_WA : 1;
-#else
+  // Squeeze weights: streamed from L2 in fragment order for every instance (three rotating register sets, or the LDS ring below).  Kept
+  // resident, the CIN = 256 instances sat on 255 registers; streaming frees 40 of them, which the depth-wise phase uses to keep DWB squeeze-row
+  // reads in flight before their FMAs: same bits out, bf16 step -0.6 % (profiles/r05u_ab_fire2_batch.txt).
   constexpr int DWB = (CIN == 256 && MID == 128) ? 4 : 1;   // (the other instances have no registers to spare: batching spills there)
-#endif
-#endif
-  // Wider inputs stream the squeeze weights.  With >= 192 squeeze channels (one workgroup per CU, LDS to spare) they go through a
+  // With >= 192 squeeze channels (one workgroup per CU, LDS to spare) the squeeze weights go through a
   // per-wave LDS ring of DW k-steps filled by LDS-DMA (fragment order: 1 KiB per instruction, read back by the lane that needs it -
   // no barrier, no registers): DW - 1 steps in flight cover the 2-3 us a weight load takes to return under load (hot or cold in L2
   // alike), where the three register sets of the 128-channel instance (two workgroups per CU, no LDS left) cover 2 steps.
-  // Expand weights: per tile they were requested behind the squeeze GEMM and waited for in front of the expand GEMM - a weight load takes
-  // 2-3 us to return under load, most of the expand phase's 5.3 k clocks (profiles/r05g_fire2_stamps.txt: 48 MFMAs = 768 clocks of pipe).
-  // OKP_F2_RESIDENT_WA: the 256 -> 128 instance keeps them in registers for the whole kernel (32 per lane) and gives the depth-wise phase
-  // smaller read batches in exchange.
-  // (-DOKP_F2_RESWA=1: the matrix-pipe depth-wise 256 -> 128 instance only; 64 x 64 alone 66.5 -> 64.6 us, 32 x 32 and the step level:
-  //  profiles/r06t_ab_fire2_prologue_pack.txt; the stride-2 instance loses 7 % with resident expand weights)
-#ifndef OKP_F2_RESWA
-#define OKP_F2_RESWA 0
-#endif
-#ifdef OKP_F2_RESIDENT_WA
-  constexpr bool RESWA = CIN == 256 && MID == 128;
-#else
-  constexpr bool RESWA = OKP_F2_RESWA && DWM && CIN == 256 && MID == 128;
-#endif
-  constexpr bool WRING = !RES && MID >= 192;
-  // PIPE (-DOKP_F2_PIPE=1, an experiment that stays in the source): the squeeze k-loop software-pipelined by one step - behind barrier ks come the
-  // requests, the fragment reads of step ks and THEN the MFMAs of step ks - 1, which cover the reads' latency (two fragment sets, four rotating
-  // weight sets; 234 registers).  Left alone hipcc sinks a step's MFMAs below the next barrier too, but feeds them from two fragment registers
-  // (ds_read x 2 -> s_waitcnt -> 4 MFMAs, four times per step).  Measured level to 1.5 % SLOWER (64 x 64 alone 69.9 -> 71.1 us,
-  // profiles/r06t_ab_fire2_pipeline_resident_wa.txt): the k-loop does not wait for its fragment reads - the other workgroup of the CU fills the gaps.
-#ifndef OKP_F2_PIPE
-#define OKP_F2_PIPE 0
-#endif
-  constexpr bool PIPE = OKP_F2_PIPE && DWM && CIN == 256 && MID == 128 && !RES && !WRING;
-  constexpr int NWS = PIPE ? 4 : 3;                // rotating squeeze-weight sets
+  // Expand weights: re-fetched per tile, requested behind the squeeze GEMM and waited for in front of the expand GEMM.  Resident for the whole
+  // kernel (32 registers per lane) they were level at the step and cost the stride-2 instance 7 %
+  // (profiles/r06t_ab_fire2_prologue_pack.txt, profiles/r06t_ab_fire2_pipeline_resident_wa.txt).
+  // The squeeze k-loop is left to hipcc's schedule: software-pipelined by one step by hand it measured level to 1.5 % slower - the k-loop does
+  // not wait for its fragment reads, the other workgroup of the CU fills the gaps (profiles/r06t_ab_fire2_pipeline_resident_wa.txt).
+  constexpr bool WRING = MID >= 192;
   constexpr int DW = !WRING ? 0 : MID == 192 ? 5 : 3;
   constexpr int SWM = ((MID / 8) % 16 == 0) ? 15 : 7;   // swizzle key bits (chunks per row must be a multiple of key range)
   constexpr int CG = MID / 8;                      // 8-channel groups of the depth-wise branch; NT / CG = 16 column slots
@@ -228,7 +176,7 @@ __global__ __launch_bounds__(MID * 2, MID == 128 ? 2 : 1) void okp_fire2_kernel(
   const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.x), 0, (int)p.x_bytes, 0x00020000);
   const __amdgpu_buffer_rsrc_t rs_o = __builtin_amdgcn_make_buffer_rsrc(p.out, 0, (int)p.out_bytes, 0x00020000);
 
-  // ---- once per workgroup: resident squeeze weights, depth-wise constants -> LDS -----------------------------
+  // ---- once per workgroup: lane constants of both GEMMs and of the ring ----------------------------------------
   // B fragment (column = channel c, k-step ks, k-group q) = 16 bytes at [slice ks/2][row c][64 (ks&1) + 16 q]
   const int chq = 32 * w + 8 * q;                           // this lane's eight channels chq .. chq + 7 (block b, register r: chq + 4 b + r) in both GEMMs
   // weights in fragment order [wave][block b][k-step][lane][16 B] (okp_ensure_frags): one load = 1 KiB contiguous per
@@ -236,9 +184,6 @@ __global__ __launch_bounds__(MID * 2, MID == 128 ? 2 : 1) void okp_fire2_kernel(
   const __amdgpu_buffer_rsrc_t rs_w1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.w1), 0, NW * 2 * KS1 * 1024, 0x00020000);
   const uint32_t w1_voff = (uint32_t)lane * 16u;
   auto load_w1 = [&](int ks, u32x4 (&dst)[2]) {
-#ifdef OKP_F2_ABL_NOWEIGHTS        // timing ablation (wrong results): every k-step multiplies with the weights of k-step 0, requested once per tile
-    if (ks != 0) { dst[0] = u32x4{0x3c003c00u, 0u, 0u, 0u}; dst[1] = dst[0]; return; }
-#endif
     // (buffer loads: ONE lane offset register + a scalar offset per fragment; as global loads every fragment beyond the 4 KiB immediate range
     //  had its own 64-bit pointer pair, kept in registers across the whole k-loop - a dozen pairs)
 #pragma unroll
@@ -253,27 +198,17 @@ __global__ __launch_bounds__(MID * 2, MID == 128 ? 2 : 1) void okp_fire2_kernel(
                                                  (int)(((uint32_t)(w * 2 + b) * KS1 + (uint32_t)ks) * 1024u + (uint32_t)lane * 16u), 0, 0, 0);
     }
   };
-  auto first_weights = [&](u32x4 (&f)[RES ? KS1 : NWS][2]) {    // what a tile needs before its k-loop starts
+  auto first_weights = [&](u32x4 (&f)[3][2]) {                // what a tile needs before its k-loop starts
     if constexpr (WRING) {
 #pragma unroll
       for (int ks = 0; ks < DW; ++ks) issue_w(ks);
-    } else if constexpr (!RES) {
+    } else {
       load_w1(0, f[0]); load_w1(1, f[1]);
     }
   };
-  u32x4 w1f[RES ? KS1 : NWS][2];                              // resident: all k-steps; streamed: three (PIPE: four) rotating sets
-  if constexpr (RES) {
-#pragma unroll
-    for (int ks = 0; ks < KS1; ++ks) load_w1(ks, w1f[ks]);
-  }
+  u32x4 w1f[3][2];                                            // three rotating sets (the instances without the LDS ring)
   const u32x4* const wa_lane = static_cast<const u32x4*>(p.wa) + (size_t)w * 2 * KS2 * 64 + lane;
-  u32x4 waf[2][KS2];                                          // expand weights: resident (RESWA) or re-fetched per tile
-  if constexpr (RESWA) {
-#pragma unroll
-    for (int b = 0; b < 2; ++b)
-#pragma unroll
-      for (int ks = 0; ks < KS2; ++ks) waf[b][ks] = wa_lane[(size_t)(b * KS2 + ks) * 64];
-  }
+  u32x4 waf[2][KS2];                                          // expand weights: re-fetched per tile
   const f32x4 b1v0 = *reinterpret_cast<const f32x4*>(p.b1 + chq), b1v1 = *reinterpret_cast<const f32x4*>(p.b1 + chq + 4);
   const f32x4 bav0 = *reinterpret_cast<const f32x4*>(p.ba + chq), bav1 = *reinterpret_cast<const f32x4*>(p.ba + chq + 4);
   // interior pixel block pb, row l16 -> squeeze-tile row (constant over tiles: depends on the tile geometry only)
@@ -341,13 +276,7 @@ __global__ __launch_bounds__(MID * 2, MID == 128 ? 2 : 1) void okp_fire2_kernel(
       }
     }
   };
-#ifdef OKP_F2_ABL_NOX
-  bool abl_started = false;
-#endif
   auto issue_x = [&](int ks, int stage) {
-#ifdef OKP_F2_ABL_NOX
-    if (abl_started) return;
-#endif
 #pragma unroll
     for (int i = 0; i < NDM; ++i)
       if (UNI || i < nd)
@@ -357,7 +286,7 @@ __global__ __launch_bounds__(MID * 2, MID == 128 ? 2 : 1) void okp_fire2_kernel(
 
   int tile = blockIdx.x;
   if (tile >= p.n_tiles) return;
-  F2_STAMP_ANY(5);
+  OKP_FIRE_STAMP(true, 8, 5);
   // the first tile's requests go out BEFORE the per-workgroup constants are fetched: both are cold reads (2-3 us each right behind a launch, when
   // every workgroup asks at once), and one behind the other they cost every launch that time twice - 30 launches per network pass
   tile_setup(tile);
@@ -395,7 +324,7 @@ __global__ __launch_bounds__(MID * 2, MID == 128 ? 2 : 1) void okp_fire2_kernel(
   }
 
   __syncthreads();
-  F2_STAMP_ANY(6);
+  OKP_FIRE_STAMP(true, 8, 6);
 
   uint32_t range_h = 0u;                           // G: largest |fp16| bits this thread stored, over all its tiles (okp_range_max_h2)
   for (; tile < p.n_tiles; tile += gridDim.x) {
@@ -404,7 +333,7 @@ __global__ __launch_bounds__(MID * 2, MID == 128 ? 2 : 1) void okp_fire2_kernel(
 #ifdef OKP_FIRE_STAMPS
     const bool second = tile == (int)(blockIdx.x + gridDim.x);
 #endif
-    F2_STAMP(0);
+    OKP_FIRE_STAMP(second, 8, 0);
     // opaque copies: the per-(block, register) pixel arithmetic below is tile-invariant, and hoisting ~100 such
     // values out of the tile loop costs more registers than recomputing them (a multiply-high each)
     int qt = q, tidt = tid;
@@ -414,13 +343,9 @@ __global__ __launch_bounds__(MID * 2, MID == 128 ? 2 : 1) void okp_fire2_kernel(
     // row and half of the next, whose swizzle keys (row & 15) differ in the high chunk bits one time in four: 2-way conflicts, 23 % of the
     // kernel's LDS cycles (SQ_LDS_BANK_CONFLICT, profiles/r05v_sq_counters.json).  With 16 channel groups (MID = 128) the lanes of a hardware
     // group are given ONE row: lane l of a half-wave belongs to group parity(l bits 2, 3, 4), and (l & 3) | ((l >> 1) & 12) numbers its lanes.
-#ifdef OKP_F2_NO_REMAP
-    const int dw_cg = tidt % CG, dw_slot = tidt / CG;
-#else
     const int dw_l = tidt & 31;
     const int dw_cg = CG == 16 ? ((dw_l & 3) | ((dw_l >> 1) & 12)) : tidt % CG;
     const int dw_slot = CG == 16 ? 4 * (tidt >> 6) + 2 * ((tidt >> 5) & 1) + (((dw_l >> 2) ^ (dw_l >> 3) ^ (dw_l >> 4)) & 1) : tidt / CG;
-#endif
     // phase 2b residuals of column `ix` (thread = 8-channel group cg, column slot): one 16-byte load per output row
     auto load_col_residuals = [&](int ix, u32x4 (&rr)[MAXIH], uint32_t (&oo)[MAXIH]) {
       const int cg = dw_cg;
@@ -458,39 +383,11 @@ __global__ __launch_bounds__(MID * 2, MID == 128 ? 2 : 1) void okp_fire2_kernel(
       acc[pb][0] = b1v0;
       acc[pb][1] = b1v1;
     }
-    if constexpr (PIPE) {
-      // at the top of step ks >= 3 the queue holds, behind x(ks): w(ks), x(ks + 1), w(ks + 1), x(ks + 2) - all of them may stay in flight
-      // (the register loads of the weights are waited for by the compiler where their MFMAs are)
-      u32x4 a[2][NSB];
-#pragma unroll
-      for (int ks = 0; ks <= KS1; ++ks) {
-        if (ks < KS1) {
-          if (ks == 0) wait_vm(0);
-          else if (ks >= 3) wait_vm(2 + (ks + 1 < KS1 ? nd + 2 : 0) + (ks + 2 < KS1 ? nd : 0));
-          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-          __builtin_amdgcn_s_barrier();
-          if (ks + 2 < KS1) load_w1(ks + 2, w1f[(ks + 2) % NWS]);
-          if (ks + NST - 1 < KS1) issue_x(ks + NST - 1, (ks + NST - 1) % NST);
-          const char* st = smem + OFF_X + (ks % NST) * XST + xfrag_off;
-#pragma unroll
-          for (int pb = 0; pb < NSB; ++pb) a[ks & 1][pb] = *reinterpret_cast<const u32x4*>(st + pb * 1024);
-          __builtin_amdgcn_sched_barrier(0);
-        }
-        if (ks > 0) {
-#pragma unroll
-          for (int pb = 0; pb < NSB; ++pb)
-#pragma unroll
-            for (int b = 0; b < 2; ++b)
-              acc[pb][b] = H16<T>::mfma16(w1f[(ks - 1) % NWS][b], a[(ks - 1) & 1][pb], acc[pb][b]);
-          __builtin_amdgcn_sched_barrier(0);
-        }
-      }
-    } else
 #pragma unroll
     for (int ks = 0; ks < KS1; ++ks) {
       // ks == 0: everything older (the previous tile's stores, the prefetched steps and weight sets) must be done,
       // because loads and stores share the counter.  Later: ring steps ks+1, ks+2 may stay in flight (nd LDS-DMA each)
-      // and, when the squeeze weights are streamed, the weight set of step ks+1 issued between them.
+      // and the weight set of step ks+1 issued between them.
       // WAR on the ring: the barrier below frees stage (ks-1) % NST for the LDS-DMA issued right behind it, so every
       // wave's fragment reads of step ks-1 must have RETURNED before it arrives: the explicit lgkmcnt(0).  The k-loop is
       // fully unrolled and s_barrier orders memory operations only: without that wait hipcc sinks step ks-1's MFMAs - and
@@ -506,12 +403,12 @@ __global__ __launch_bounds__(MID * 2, MID == 128 ? 2 : 1) void okp_fire2_kernel(
         auto nw = [](int j) { return j >= 1 && j - 1 + DW < KS1 ? 2 : 0; };
         auto nx = [](int j) { return j >= 0 && j + NST - 1 < KS1 ? 1 : 0; };
         wait_vm((DW >= 4 ? nw(ks - 2) : 0) + nw(ks - 1) + (nx(ks - 2) + nx(ks - 1)) * nd);
-      } else if (ks >= (RES ? NST - 1 : 2))
-        wait_vm((ks + 1 < KS1 ? nd + (RES ? 0 : 2) : 0) + (ks + 2 < KS1 ? nd : 0));
+      } else if (ks >= 2)
+        wait_vm((ks + 1 < KS1 ? nd + 2 : 0) + (ks + 2 < KS1 ? nd : 0));
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_s_barrier();
       if constexpr (WRING) { if (ks >= 1 && ks - 1 + DW < KS1) issue_w(ks - 1 + DW); }
-      else if constexpr (!RES) { if (ks + 2 < KS1) load_w1(ks + 2, w1f[(ks + 2) % 3]); }
+      else if (ks + 2 < KS1) load_w1(ks + 2, w1f[(ks + 2) % 3]);
       if (ks + NST - 1 < KS1) issue_x(ks + NST - 1, (ks + NST - 1) % NST);
       const char* st = smem + OFF_X + (ks % NST) * XST + xfrag_off;
       u32x4 a[NSB], wr[2] = {};
@@ -521,31 +418,18 @@ __global__ __launch_bounds__(MID * 2, MID == 128 ? 2 : 1) void okp_fire2_kernel(
       }
 #pragma unroll
       for (int pb = 0; pb < NSB; ++pb) a[pb] = *reinterpret_cast<const u32x4*>(st + pb * 1024);
-#ifdef OKP_F2_PIN_READS
-      __builtin_amdgcn_sched_barrier(0);       // every fragment read of the step in flight before its first MFMA (hipcc otherwise issues them two at a time)
-#endif
 #pragma unroll
       for (int pb = 0; pb < NSB; ++pb)
 #pragma unroll
         for (int b = 0; b < 2; ++b)
-          acc[pb][b] = H16<T>::mfma16(WRING ? wr[b] : w1f[RES ? ks : ks % 3][b], a[pb], acc[pb][b]);
+          acc[pb][b] = H16<T>::mfma16(WRING ? wr[b] : w1f[ks % 3][b], a[pb], acc[pb][b]);
     }
-    F2_STAMP(1);
-#ifdef OKP_F2_ABL_NOX
-    abl_started = true;
-#endif
+    OKP_FIRE_STAMP(second, 8, 1);
     // expand weights for this tile (dead after phase 2a): issue now, consumed after the barrier
-    if constexpr (!RESWA) {
 #pragma unroll
-      for (int b = 0; b < 2; ++b)
+    for (int b = 0; b < 2; ++b)
 #pragma unroll
-        for (int ks = 0; ks < KS2; ++ks) {
-#ifdef OKP_F2_ABL_NOWEIGHTS
-          if (b + ks != 0) { waf[b][ks] = u32x4{0x3c003c00u, 0u, 0u, 0u}; continue; }
-#endif
-          waf[b][ks] = wa_lane[(size_t)(b * KS2 + ks) * 64];
-        }
-    }
+      for (int ks = 0; ks < KS2; ++ks) waf[b][ks] = wa_lane[(size_t)(b * KS2 + ks) * 64];
     // s -> LDS (zero outside the frame: the reference zero-pads the squeeze output)
     {
       const uint32_t* mk = reinterpret_cast<const uint32_t*>(smem + OFF_MASK);
@@ -569,7 +453,7 @@ __global__ __launch_bounds__(MID * 2, MID == 128 ? 2 : 1) void okp_fire2_kernel(
       }
     }
     __syncthreads();
-    F2_STAMP(2);
+    OKP_FIRE_STAMP(second, 8, 2);
     // ---- phase 2a: y_a = relu(Wa s + ba (+x)) on the interior pixels, whole lines straight to HBM --------------
     uint32_t dwm_o[DIH];                                    // DWM: output offset of this lane's pixel (row iy, column l16), channels chq ..
     uint32_t d2_o[D2B];                                     // DWM2: the same for (block pb, lane)
@@ -710,7 +594,7 @@ __global__ __launch_bounds__(MID * 2, MID == 128 ? 2 : 1) void okp_fire2_kernel(
       }
     }
     asm volatile("" ::: "memory");             // keep the stores here (the scheduler otherwise sinks them below phase 2b)
-    F2_STAMP(3);
+    OKP_FIRE_STAMP(second, 8, 3);
 
     // ---- phase 2b: y_b = relu(dw3x3(s) + bd (+x)) from the LDS squeeze tile -------------------------------------
     if constexpr (DWM2) {
@@ -806,7 +690,6 @@ __global__ __launch_bounds__(MID * 2, MID == 128 ? 2 : 1) void okp_fire2_kernel(
       const uint32_t m_lo = (l16t & 2) ? 0u : am, m_hi = (l16t & 2) ? am : 0u;
       const uint32_t wt_lane = (uint32_t)OFF_WD + (uint32_t)(chq + (l16t & 3)) * 4u;
       const uint32_t cx = (uint32_t)(4 * w) + (uint32_t)qt;
-#ifndef OKP_F2_ABL_NODW
       // (all DIH + 2 squeeze rows are walked whatever the tile's height: rows beyond it hold stale - finite or not, it does not matter -
       //  values of the LDS tile, and the accumulator rows they feed are never stored; no branch, so the reads run ahead of the MFMAs)
       u32x4 a0[3], a1[3];                                     // A operands of the three dy taps of a column position: block 0 {lo, hi, 0, 0}, block 1 {0, 0, lo, hi}
@@ -839,7 +722,6 @@ __global__ __launch_bounds__(MID * 2, MID == 128 ? 2 : 1) void okp_fire2_kernel(
           }
         }
       }
-#endif
 #pragma unroll
       for (int iy = 0; iy < DIH; ++iy) {
         const u32x4 o = relu_add_pack8<T>(acd[iy][0], acd[iy][1], rr2[iy]);
@@ -957,11 +839,11 @@ __global__ __launch_bounds__(MID * 2, MID == 128 ? 2 : 1) void okp_fire2_kernel(
         }
       }
     }
-    F2_STAMP(4);
+    OKP_FIRE_STAMP(second, 8, 4);
     // no barrier here: phase 2 does not read what the next tile's phase 1 writes before its own barriers
   }
   if constexpr (G) okp_raise_range_flag(p.range_flag, okp_range_exceeded_h2(range_h));
-  F2_STAMP_ANY(7);
+  OKP_FIRE_STAMP(true, 8, 7);
 }
 
 }  // namespace
@@ -1039,15 +921,11 @@ static int launch_fire2_t(OkpFire2Params p, int cin, int mid, int stride, hipStr
   const int resident = 256 * (mid == 128 ? 2 : 1);
   const dim3 grid((unsigned)(p.n_tiles < resident ? p.n_tiles : resident)), block((unsigned)(2 * mid));
 #ifdef OKP_FIRE_STAMPS
-  static uint32_t* dbg = nullptr;
-  if (!dbg) (void)hipMalloc((void**)&dbg, 16 * 8 * 8 * 4);
-  (void)hipMemsetAsync(dbg, 0, 16 * 8 * 8 * 4, stream);
-  p.dbg = dbg;
-  struct Print { OkpFire2Params p; int mid; hipStream_t stream; uint32_t* dbg; ~Print() {
-    if (!getenv("OKP_FIRE_STAMPS_PRINT")) return;
-    (void)hipStreamSynchronize(stream);
-    uint32_t h[16 * 8 * 8];
-    (void)hipMemcpy(h, dbg, sizeof(h), hipMemcpyDeviceToHost);
+  static OkpFireStamps stamps;
+  p.dbg = stamps.reset(stream);
+  struct Print { OkpFire2Params p; int mid; hipStream_t stream; ~Print() {      // (behind the launch below)
+    uint32_t h[OkpFireStamps::kWords];
+    if (!stamps.fetch(h, stream)) return;
     const int nw = mid / 32;
     printf("fire2 stamps (tile %d x %d interior, %d tiles, %d waves): clocks per wave of the second tile: squeeze GEMM (ring) | s -> LDS + barrier | expand GEMM + stores | depth-wise branch (+ next tile's requests)\n", p.IH, p.IW, p.n_tiles, nw);
     double sum[4] = {0, 0, 0, 0}; int cnt = 0;
@@ -1064,7 +942,7 @@ static int launch_fire2_t(OkpFire2Params p, int cin, int mid, int stride, hipStr
     for (int wg = 0; wg < 16; ++wg)
       for (int w = 0; w < nw; ++w) { const uint32_t* a = &h[(wg * 8 + w) * 8]; if (!a[7]) continue; pro += a[6] - a[5]; all += a[7] - a[5]; ++c2; }
     if (c2) printf("whole kernel: prologue (first requests + constants -> LDS + barrier) %.0f clocks, entry to exit %.0f clocks\n", pro / c2, all / c2);
-  } } print_at_exit{p, mid, stream, dbg};
+  } } print_at_exit{p, mid, stream};
 #endif
   bool launched = true;
   if (stride == 1 && dwm) {
@@ -1159,9 +1037,6 @@ extern "C" int okp_fire_forward(const okp_conv* squeeze, const okp_conv* expand,
     q.x = a->x.data; q.x_bytes = (uint32_t)a->x.bytes; q.H = a->x.h; q.W = a->x.w; q.x_ps = a->x.pix_stride;
     q.out = a->out.data; q.out_bytes = (uint32_t)a->out.bytes; q.Ho = ho; q.Wo = wo; q.out_ps = a->out.pix_stride;
     q.N = a->n; q.skip = a->skip;
-#if defined(OKP_FIRE_STAMPS) || defined(OKP_F2_ABL_NOSKIP)
-    if (getenv("OKP_FIRE_NOSKIP")) q.skip = 0;       // timing ablation of the debug build (wrong results): no skip values are requested
-#endif
     if (int e = okp_ensure_frags(squeeze, (hipStream_t)stream)) return e;
     if (int e = okp_ensure_frags(expand, (hipStream_t)stream)) return e;
     q.w1 = squeeze->fragT_dev; q.w1_cout_pad = squeeze->cout_pad; q.b1 = squeeze->bias_dev;

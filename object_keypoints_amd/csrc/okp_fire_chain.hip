@@ -22,6 +22,13 @@
 #include <type_traits>
 
 #include "okp_internal.h"
+// Debug build (okp_stamps.h): stamps at the phase boundaries of the chain's SECOND chain module (slots 0..4), and at kernel entry / before the
+// first chain module / exit (5..7)
+#ifdef OKP_FIRE_STAMPS
+#include "okp_stamps.h"
+#else
+#define OKP_FIRE_STAMP(cond, nw, i) do {} while (0)
+#endif
 
 namespace {
 
@@ -63,14 +70,6 @@ struct ChainCfg {
 template <int KEY>
 __device__ __forceinline__ uint32_t xoff(int row, int chunk, int rowbytes) { return (uint32_t)row * rowbytes + (uint32_t)((chunk ^ (row & KEY)) << 4); }
 
-#ifdef OKP_FIRE_STAMPS
-// Debug build (OKP_EXTRA_CFLAGS=-DOKP_FIRE_STAMPS, printed with OKP_FIRE_STAMPS_PRINT=1): shader-clock stamps of every wave of workgroups 0..15 at the
-// phase boundaries of the chain's SECOND chain module, and at kernel entry / before the first chain module / exit: [wg][wave 8][8] u32
-#define FC_STAMP(cond, i) do { if ((cond) && lane == 0 && blockIdx.x < 16) { uint64_t t_; asm volatile("s_memtime %0\n s_waitcnt lgkmcnt(0)" : "=s"(t_) :: "memory"); p.dbg[(blockIdx.x * 8 + w) * 8 + (i)] = (uint32_t)t_; } } while (0)
-#else
-#define FC_STAMP(cond, i) do {} while (0)
-#endif
-
 // G: the range-guarded fp16 instantiation (okp_internal.h: OKP_F16 range guard) - every module's squeeze tile and output, inside the chain as
 // well as at its end, is checked to be finite where it is written to LDS
 template <typename T, int CIN, int PXB, bool EE, bool G = false>
@@ -96,7 +95,7 @@ __global__ __launch_bounds__((ChainCfg<CIN, PXB, EE>::NT)) void okp_fire_chain_k
   const int l16 = lane & 15, q = lane >> 4;
   const int n = blockIdx.x;
   const int HW = p.H * p.W;
-  FC_STAMP(true, 5);
+  OKP_FIRE_STAMP(true, 8, 5);
   const int ch0 = 32 * w + 2 * l16;                    // this lane's channel pair in both GEMMs
 
   // frame -> LDS (buffer 0), squeeze tile cleared once: its halo stays zero for the whole chain.
@@ -199,9 +198,7 @@ __global__ __launch_bounds__((ChainCfg<CIN, PXB, EE>::NT)) void okp_fire_chain_k
         const u32x4 f0 = wf[ks % PF][0], f1 = wf[ks % PF][1];
         if (ks + PF < EKS1) { wf[ks % PF][0] = frag(w1_lane, EKS1, ks + PF, 0); wf[ks % PF][1] = frag(w1_lane, EKS1, ks + PF, 1); }
         else { wf[ks % PF][0] = frag(wa_lane, KS2, ks + PF - EKS1, 0); wf[ks % PF][1] = frag(wa_lane, KS2, ks + PF - EKS1, 1); }   // expand step ks - 4 -> slot (ks - 4 + 4) % 8
-#ifndef OKP_CHAIN_NO_PIN
         __builtin_amdgcn_sched_barrier(0);     // the refill is REQUESTED here, PF steps ahead of its use (hipcc otherwise sinks the loads down to their MFMAs)
-#endif
 #pragma unroll
         for (int pb = 0; pb < 4; ++pb) {
           acc0[pb] = H16<T>::mfma16(a[pb], f0, acc0[pb]);
@@ -237,9 +234,7 @@ __global__ __launch_bounds__((ChainCfg<CIN, PXB, EE>::NT)) void okp_fire_chain_k
         const u32x4 f0 = wf[(e + 4) % PF][0], f1 = wf[(e + 4) % PF][1];
         // the slot is free: the first chain module's squeeze step with that slot ((e + 4) % 8; the chain ring keeps step k in slot k % 8)
         wf[(e + 4) % PF][0] = frag(w1_next, KS1, (e + 4) % PF, 0); wf[(e + 4) % PF][1] = frag(w1_next, KS1, (e + 4) % PF, 1);
-#ifndef OKP_CHAIN_NO_PIN
         __builtin_amdgcn_sched_barrier(0);     // the refill is REQUESTED here, PF steps ahead of its use (hipcc otherwise sinks the loads down to their MFMAs)
-#endif
         acc0 = H16<T>::mfma16(a, f0, acc0);
         acc1 = H16<T>::mfma16(a, f1, acc1);
       }
@@ -285,13 +280,13 @@ __global__ __launch_bounds__((ChainCfg<CIN, PXB, EE>::NT)) void okp_fire_chain_k
   }
 
   const int m_first = EE ? 1 : 0, m_end = EE ? p.n_modules - 1 : p.n_modules;      // the chain modules proper
-  FC_STAMP(true, 6);
+  OKP_FIRE_STAMP(true, 8, 6);
   for (int m = m_first; m < m_end; ++m) {
     const OkpFireChainModule mod = p.mod[m];
 #ifdef OKP_FIRE_STAMPS
     const bool second = m == m_first + 1;
 #endif
-    FC_STAMP(second, 0);
+    OKP_FIRE_STAMP(second, 8, 0);
     const float* cst = reinterpret_cast<const float*>(smem + C::OFF_C + (m & 1) * C::CONST_BYTES);   // [9][MID] depth-wise weights
     const float* cbd = cst + C::WD_BYTES / 4;              // then bd, b1, ba
     const float* cb1 = cbd + C::B_BYTES / 4;
@@ -321,9 +316,7 @@ __global__ __launch_bounds__((ChainCfg<CIN, PXB, EE>::NT)) void okp_fire_chain_k
         const u32x4 f0 = wf[ks % PF][0], f1 = wf[ks % PF][1];
         if (ks + PF < KS1) { wf[ks % PF][0] = frag(w1_lane, KS1, ks + PF, 0); wf[ks % PF][1] = frag(w1_lane, KS1, ks + PF, 1); }
         else { wf[ks % PF][0] = frag(wa_lane, KS2, ks + PF - KS1, 0); wf[ks % PF][1] = frag(wa_lane, KS2, ks + PF - KS1, 1); }   // expand step ks + PF - KS1
-#ifndef OKP_CHAIN_NO_PIN
         __builtin_amdgcn_sched_barrier(0);     // the refill is REQUESTED here, PF steps ahead of its use (hipcc otherwise sinks the loads down to their MFMAs)
-#endif
 #pragma unroll
         for (int pb = 0; pb < PXB; ++pb) {
           acc0[pb] = H16<T>::mfma16(a[pb], f0, acc0[pb]);
@@ -345,9 +338,9 @@ __global__ __launch_bounds__((ChainCfg<CIN, PXB, EE>::NT)) void okp_fire_chain_k
           }
         }
     }
-    FC_STAMP(second, 1);
+    OKP_FIRE_STAMP(second, 8, 1);
     __syncthreads();
-    FC_STAMP(second, 2);
+    OKP_FIRE_STAMP(second, 8, 2);
 
     // ---- expand: y[:, :MID] = relu(Wa s + ba + x[:, :MID]) -> next activation buffer ----------------------------------
     {
@@ -367,9 +360,7 @@ __global__ __launch_bounds__((ChainCfg<CIN, PXB, EE>::NT)) void okp_fire_chain_k
         for (int pb = 0; pb < PXB; ++pb) a[pb] = *reinterpret_cast<const u32x4*>(smem + C::OFF_S + xoff<SK>(arow[pb], 4 * ks + q, SROW));
         const u32x4 f0 = wf[ks % PF][0], f1 = wf[ks % PF][1];
         if (more) { wf[ks % PF][0] = frag(w1_next, KS1, ks, 0); wf[ks % PF][1] = frag(w1_next, KS1, ks, 1); }      // the next module's squeeze step ks
-#ifndef OKP_CHAIN_NO_PIN
         __builtin_amdgcn_sched_barrier(0);     // the refill is REQUESTED here, PF steps ahead of its use (hipcc otherwise sinks the loads down to their MFMAs)
-#endif
 #pragma unroll
         for (int pb = 0; pb < PXB; ++pb) {
           acc0[pb] = H16<T>::mfma16(a[pb], f0, acc0[pb]);
@@ -392,7 +383,7 @@ __global__ __launch_bounds__((ChainCfg<CIN, PXB, EE>::NT)) void okp_fire_chain_k
         }
     }
 
-    FC_STAMP(second, 3);
+    OKP_FIRE_STAMP(second, 8, 3);
     // ---- depth-wise: y[:, MID:] = relu(dw3x3(s) + bd + x[:, MID:]) -----------------------------------------------------
     // thread = (8-channel group cg, pixel slot); NT / (MID / 8) = 16 pixel slots per pass
     // The NPX / 16 pixels of a thread are worked TOGETHER, tap by tap: a tap's weights are read from LDS once for all of them (pixel by pixel
@@ -448,11 +439,11 @@ __global__ __launch_bounds__((ChainCfg<CIN, PXB, EE>::NT)) void okp_fire_chain_k
     } else {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
-    FC_STAMP(second, 4);
+    OKP_FIRE_STAMP(second, 8, 4);
     __syncthreads();
     cur ^= 1;
   }
-  FC_STAMP(true, 7);
+  OKP_FIRE_STAMP(true, 8, 7);
 
   // ---- EE: exit module (the last one): 512 -> 192 -> 384, no skip; waves 0..5 own its 192 squeeze / expand channels ----------------
   if constexpr (EE) {
@@ -476,9 +467,7 @@ __global__ __launch_bounds__((ChainCfg<CIN, PXB, EE>::NT)) void okp_fire_chain_k
         const u32x4 f0 = wf[ks % PF][0], f1 = wf[ks % PF][1];
         if (ks + PF < KS1) { wf[ks % PF][0] = frag(w1_lane, KS1, ks + PF, 0); wf[ks % PF][1] = frag(w1_lane, KS1, ks + PF, 1); }
         else if (ks + PF - KS1 < XKS2) { wf[ks % PF][0] = frag(wa_lane, XKS2, ks + PF - KS1, 0); wf[ks % PF][1] = frag(wa_lane, XKS2, ks + PF - KS1, 1); }
-#ifndef OKP_CHAIN_NO_PIN
         __builtin_amdgcn_sched_barrier(0);     // the refill is REQUESTED here, PF steps ahead of its use (hipcc otherwise sinks the loads down to their MFMAs)
-#endif
         acc0 = H16<T>::mfma16(a, f0, acc0);
         acc1 = H16<T>::mfma16(a, f1, acc1);
       }
@@ -565,12 +554,10 @@ int okp_ensure_frags(const okp_conv* plan, hipStream_t) {
 
 
 #ifdef OKP_FIRE_STAMPS
-static uint32_t* g_chain_dbg = nullptr;
+static OkpFireStamps g_chain_stamps;
 static void chain_stamps_print(const char* what, int nw, hipStream_t stream) {
-  if (!getenv("OKP_FIRE_STAMPS_PRINT")) return;
-  (void)hipStreamSynchronize(stream);
-  uint32_t h[16 * 8 * 8];
-  (void)hipMemcpy(h, g_chain_dbg, sizeof(h), hipMemcpyDeviceToHost);
+  uint32_t h[OkpFireStamps::kWords];
+  if (!g_chain_stamps.fetch(h, stream)) return;
   double sum[5] = {0, 0, 0, 0, 0}, pro = 0, all = 0; int cnt = 0;
   for (int wg = 0; wg < 16; ++wg)
     for (int w = 0; w < nw; ++w) {
@@ -596,9 +583,7 @@ extern "C" int okp_fire_chain_forward(int32_t n_modules, okp_conv* const* squeez
   OkpFireChainParams p;
   std::memset(&p, 0, sizeof(p));
 #ifdef OKP_FIRE_STAMPS
-  if (!g_chain_dbg) (void)hipMalloc((void**)&g_chain_dbg, 16 * 8 * 8 * 4);
-  (void)hipMemsetAsync(g_chain_dbg, 0, 16 * 8 * 8 * 4, (hipStream_t)stream);
-  p.dbg = g_chain_dbg;
+  p.dbg = g_chain_stamps.reset((hipStream_t)stream);
 #endif
   // EE form: module 0 is the stride-2 entry module 384 -> 256 -> 512 (x is the twice larger map), the last one the exit module
   // 512 -> 192 -> 384, at least one fire(512, 512) in between - the whole innermost hourglass level in one launch

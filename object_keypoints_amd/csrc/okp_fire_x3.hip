@@ -29,6 +29,12 @@
 #include <cstdlib>
 
 #include "okp_igemm_kernel.h"
+// Debug build (okp_stamps.h): stamps at the phase boundaries of a workgroup's SECOND tile (steady state), slots 0..6
+#ifdef OKP_FIRE_STAMPS
+#include "okp_stamps.h"
+#else
+#define OKP_FIRE_STAMP(cond, nw, i) do {} while (0)
+#endif
 
 namespace {
 
@@ -37,9 +43,6 @@ constexpr int SP = 128;                          // squeeze-tile rows in LDS
 constexpr int PBI = 6;                           // interior pixel blocks of 16 (IP <= 96)
 constexpr int NST = 4;                           // x ring stages
 constexpr int MAXIH = 5;                         // interior rows per tile (5 x 16 tiles on every map of the network; a sixth row cost the depth-wise phase 9 registers)
-#ifndef OKP_FX3_DWB
-#define OKP_FX3_DWB 4
-#endif
 constexpr int KS1 = CIN / 32, KS2 = MID / 32;    // k-steps of the squeeze / expand GEMM
 constexpr int NW = 8, NT = 64 * NW;
 constexpr int XST = SP * 128;                    // bytes per ring stage (128 pixels x 32 fp32)
@@ -56,14 +59,6 @@ static_assert(LDS_TOTAL <= 160 * 1024, "LDS");
 // swizzle key of ring row r (128-byte rows, 16-row fragments whose lane k-group q reads chunk 2q / 2q + 1): by (r >> 1) & 7, conflict-free
 // for the ds_read_b128 lane groups of gfx950 (MI355X_MICROARCH.md, LDS; searched against them)
 __device__ __forceinline__ uint32_t ring_key(int row) { return (0x54541010u >> (4 * ((row >> 1) & 7))) & 7u; }
-
-#ifdef OKP_FIRE_STAMPS
-// Debug build (OKP_EXTRA_CFLAGS=-DOKP_FIRE_STAMPS, printed with OKP_FIRE_STAMPS_PRINT=1): shader-clock stamps of every wave at the phase
-// boundaries of its workgroup's SECOND tile (steady state), workgroups 0..15: [wg][wave][8] u32
-#define FX3_STAMP(i) do { if (second && lane == 0 && blockIdx.x < 16) { uint64_t t_; asm volatile("s_memtime %0\n s_waitcnt lgkmcnt(0)" : "=s"(t_) :: "memory"); p.dbg[(blockIdx.x * NW + w) * 8 + (i)] = (uint32_t)t_; } } while (0)
-#else
-#define FX3_STAMP(i) do {} while (0)
-#endif
 
 // STR = 2 (round 6, last): the stride-2 module 256 -> 128 -> 256 WITHOUT skip (64 x 64 -> 32 x 32: until now a squeeze launch plus the fused tail -
 // the fp32 squeeze tensor, 134 MB per 64 frames, written and read back).  The squeeze tile is the input pixels under a tile of OH2 x 8 output
@@ -193,7 +188,7 @@ __global__ __launch_bounds__(NT) void okp_fire_x3_kernel(const OkpFire2Params p)
 #ifdef OKP_FIRE_STAMPS
     const bool second = tile == (int)(blockIdx.x + gridDim.x);
 #endif
-    FX3_STAMP(0);
+    OKP_FIRE_STAMP(second, NW, 0);
     int qt = q, tidt = tid, l16t = l16;                      // opaque copies: keeps tile-invariant address arithmetic out of registers
     asm volatile("" : "+v"(qt), "+v"(tidt), "+v"(l16t));
 
@@ -211,7 +206,7 @@ __global__ __launch_bounds__(NT) void okp_fire_x3_kernel(const OkpFire2Params p)
     } else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     static_assert(OH == 5 || OH == 3, "the counted waits above name OH");
     __builtin_amdgcn_s_barrier();                            // stages 0 .. 2 have landed (every wave's part)
-    FX3_STAMP(1);
+    OKP_FIRE_STAMP(second, NW, 1);
     split_stage(0);
 #pragma unroll
     for (int ks = 0; ks < KS1; ++ks) {
@@ -257,7 +252,7 @@ __global__ __launch_bounds__(NT) void okp_fire_x3_kernel(const OkpFire2Params p)
 #undef OKP_FX3_BLOCK
       __builtin_amdgcn_sched_barrier(0);
     }
-    FX3_STAMP(2);
+    OKP_FIRE_STAMP(second, NW, 2);
     // expand weights for this tile (dead after phase 2a): requested now, consumed behind the barrier
     u32x4 wah[KS2], wal[KS2];
 #pragma unroll
@@ -291,7 +286,7 @@ __global__ __launch_bounds__(NT) void okp_fire_x3_kernel(const OkpFire2Params p)
       okp_raise_range_flag(p.range_flag, okp_range_exceeded(range_m));
     }
     __syncthreads();
-    FX3_STAMP(3);
+    OKP_FIRE_STAMP(second, NW, 3);
 
     // ---- phase 2a: y_a = relu(Wa s + ba + x[:, :128]) on the interior pixels, 16 bytes per lane straight to HBM --------------------
     // One block of 16 pixels per iteration (not unrolled: 24 blocks of reads + MFMAs in one basic block made hipcc hoist every LDS read
@@ -354,7 +349,7 @@ __global__ __launch_bounds__(NT) void okp_fire_x3_kernel(const OkpFire2Params p)
       }
       okp_raise_range_flag(p.range_flag, okp_range_exceeded(range_m2));
     }
-    FX3_STAMP(4);
+    OKP_FIRE_STAMP(second, NW, 4);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __syncthreads();                                         // every wave's reads of the [hi | lo] tile have returned: the ring is free
     {
@@ -366,7 +361,7 @@ __global__ __launch_bounds__(NT) void okp_fire_x3_kernel(const OkpFire2Params p)
       }
     }
 
-    FX3_STAMP(5);
+    OKP_FIRE_STAMP(second, NW, 5);
     // ---- phase 2b: y_b = relu(dw3x3(s) + bd + x[:, 128:]) from the fp32 squeeze tile -------------------------------------
     // thread = (4-channel group cg, column slot): it walks DOWN its column, each squeeze row feeding the three output rows that see it
     // as tap row 2, 1, 0; the nine taps' weights come from LDS per column position.
@@ -405,7 +400,7 @@ __global__ __launch_bounds__(NT) void okp_fire_x3_kernel(const OkpFire2Params p)
           // basic block of its own - ds_read -> s_waitcnt -> 12 FMAs, 21 LDS latencies one behind the other per column, most of this phase's
           // 9-10 k clocks.  Rows beyond the tile are read too (clamped into the tile): they feed only accumulator rows that are never stored
           // - and that the range maximum below leaves out.
-          constexpr int BT = OKP_FX3_DWB;                      // rows per batch (registers: 4 per row)
+          constexpr int BT = 4;                                // rows per batch (registers: 4 per row)
 #pragma unroll
           for (int s0 = 0; s0 < NSR; s0 += BT) {
             f32x4 sv[BT];
@@ -446,7 +441,7 @@ __global__ __launch_bounds__(NT) void okp_fire_x3_kernel(const OkpFire2Params p)
       }
       okp_raise_range_flag(p.range_flag, okp_range_exceeded(range_m3));
     }
-    FX3_STAMP(6);
+    OKP_FIRE_STAMP(second, NW, 6);
     // no barrier here: the next tile's phase 1 starts with one (behind its vmcnt(0)), and nothing of this phase is overwritten before it
   }
 }
@@ -479,18 +474,15 @@ int okp_launch_fire_x3(OkpFire2Params p, int stride, hipStream_t stream) {
   p.div_iw = okp_fastdiv((uint32_t)p.IW);
   const dim3 grid((unsigned)(p.n_tiles < 256 ? p.n_tiles : 256)), block((unsigned)NT);
 #ifdef OKP_FIRE_STAMPS
-  static uint32_t* dbg = nullptr;
-  if (!dbg) (void)hipMalloc((void**)&dbg, 16 * NW * 8 * 4);
-  (void)hipMemsetAsync(dbg, 0, 16 * NW * 8 * 4, stream);
-  p.dbg = dbg;
+  static_assert(NW == 8, "okp_stamps.h: [wg 16][wave 8][slot 8]");
+  static OkpFireStamps stamps;
+  p.dbg = stamps.reset(stream);
 #endif
   if (stride == 1) hipLaunchKernelGGL(okp_fire_x3_kernel<1>, grid, block, 0, stream, p);
   else hipLaunchKernelGGL(okp_fire_x3_kernel<2>, grid, block, 0, stream, p);
 #ifdef OKP_FIRE_STAMPS
-  if (getenv("OKP_FIRE_STAMPS_PRINT")) {
-    (void)hipStreamSynchronize(stream);
-    uint32_t h[16 * NW * 8];
-    (void)hipMemcpy(h, dbg, sizeof(h), hipMemcpyDeviceToHost);
+  uint32_t h[OkpFireStamps::kWords];
+  if (stamps.fetch(h, stream)) {
     printf("fire_x3 stamps (tile %d x %d interior, %d tiles): clocks per wave of the second tile: wait for the ring + older stores | squeeze GEMM (8 k-steps) | s -> LDS | expand GEMM + stores | barrier + next tile's requests | depth-wise branch\n", p.IH, p.IW, p.n_tiles);
     double sum[6] = {0, 0, 0, 0, 0, 0};
     for (int wg = 0; wg < 16; ++wg)

@@ -211,11 +211,7 @@ __global__ __launch_bounds__(512) void okp_igemm_patch_kernel(const OkpPatchPara
       const uint32_t w3 = (uint32_t)__builtin_amdgcn_readfirstlane((int)sv[3]);
       const int dxo = (w3 >> 8) & 0xff;                            // column offset of this step's tap inside the patch
       const bool more = t + 1 < t1;
-#ifdef OKP_PATCH_ABL_NOPATCH                    // timing ablation (wrong results): no patch but the first of a tile is ever requested
-      const bool next_patch = false; (void)nx_k0; (void)nx_k1; (void)nx_geom; (void)nx_c0b;
-#else
       const bool next_patch = nx_k1 > nx_k0 && (int)(w3 >> 24) + 1 < t1;   // the next group still belongs to this class
-#endif
 
       // my part of step t's weights (and of its patch) has landed, and my fragment reads of step t-1 have returned (the
       // barrier frees their stage / patch buffer for the next LDS-DMA)

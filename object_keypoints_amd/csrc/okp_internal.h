@@ -94,13 +94,8 @@ static __device__ __forceinline__ void okp_split4(const f32x4& x, u32x2& hi, u32
 // the stem reads, and what okp_cast / okp_add_f16_f32 make of fp16 tensors for a split-product consumer (the mixed configuration).  (The
 // patch-resident kernel keeps the exact per-value form as a lane mask in scalar registers: free there, where a maximum in a vector register
 // cost 1.4 %; the fire module and the stem are the other way round - 5-7 % with the mask, nothing measurable with the maximum.)
-#ifdef OKP_NO_RANGE_GUARD      // experiment build: what the guard costs (A/B against the committed kernels)
-static __device__ __forceinline__ bool okp_unsplittable(float) { return false; }
-static __device__ __forceinline__ float okp_range_max(float m, float) { return m; }
-#else
 static __device__ __forceinline__ bool okp_unsplittable(float v) { return !(__builtin_fabsf(v) <= 65504.f); }     // (true for NaN)
 static __device__ __forceinline__ float okp_range_max(float m, float v) { return __builtin_fmaxf(m, __builtin_fabsf(v)); }
-#endif
 static __device__ __forceinline__ bool okp_range_exceeded(float m) { return !(m <= 65504.f); }
 
 // OKP_F16 range guard (the `bool G` instantiations of the 16-bit kernels, chosen where an OKP_F16 plan has a flag): every value a float16
@@ -111,13 +106,9 @@ static __device__ __forceinline__ bool okp_range_exceeded(float m) { return !(m 
 // v_pk_max_u16 per dword): |h| >= 0x7c00 is inf or NaN, exact.  Where it still holds the fp32 value it uses okp_range_max (|v| <= 65504).
 // The unguarded fp16 and all bf16 instantiations compile none of it (if constexpr).
 typedef unsigned short okp_u16x2 __attribute__((ext_vector_type(2)));
-#ifdef OKP_NO_RANGE_GUARD
-static __device__ __forceinline__ uint32_t okp_range_max_h2(uint32_t m, uint32_t) { return m; }
-#else
 static __device__ __forceinline__ uint32_t okp_range_max_h2(uint32_t m, uint32_t w) {
   return __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(okp_u16x2, m), __builtin_bit_cast(okp_u16x2, w & 0x7fff7fffu)));
 }
-#endif
 static __device__ __forceinline__ uint32_t okp_range_max_h8(uint32_t m, const u32x4& w) {
 #pragma unroll
   for (int i = 0; i < 4; ++i) m = okp_range_max_h2(m, w[i]);

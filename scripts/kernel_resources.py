@@ -1,20 +1,15 @@
-"""Compile csrc/okp_igemm.hip (or the file given) with -Rpass-analysis=kernel-resource-usage and print a table."""
-import re, subprocess, sys, os
+"""Compile csrc/okp_igemm.hip (or the file given) with the build's flags and resource remarks and print a table."""
+import re, subprocess, sys, os, tempfile
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+from object_keypoints_amd.build import AGPR_FILES, CFLAGS, HIPCC, RESOURCE_KEYS, RESOURCE_REMARKS, VGPR_FORM, _parse_resources  # noqa: E402
 src = sys.argv[1] if len(sys.argv) > 1 else os.path.join(REPO, "object_keypoints_amd/csrc/okp_igemm.hip")
-form = [] if src.endswith("_w4.hip") else ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]
-cmd = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950"] + form + [
-       "-I" + os.path.join(REPO, "include"), "-I" + os.path.join(REPO, "object_keypoints_amd/csrc"), "-c", src, "-o", "/tmp/_kres.o",
-       "-Rpass-analysis=kernel-resource-usage"] + os.environ.get("OKP_EXTRA_CFLAGS", "").split()      # (the build's experiment switches)
-out = subprocess.run(cmd, capture_output=True, text=True).stderr
-cur = None
-rows = {}
-for line in out.splitlines():
-    m = re.search(r"Function Name: (\S+)", line)
-    if m: cur = m.group(1); rows[cur] = {}; continue
-    m = re.search(r"remark:\s+(\w[\w \[\]/]*?):\s+(\d+)", line)
-    if m and cur: rows[cur][m.group(1).strip()] = int(m.group(2))
+form = [] if os.path.basename(src) in AGPR_FILES else VGPR_FORM
+with tempfile.TemporaryDirectory() as tmp:
+    cmd = [HIPCC] + CFLAGS + form + RESOURCE_REMARKS + os.environ.get("OKP_EXTRA_CFLAGS", "").split() + ["-c", src, "-o", os.path.join(tmp, "_kres.o")]
+    out = subprocess.run(cmd, capture_output=True, text=True).stderr
+rows = _parse_resources(out, dict(RESOURCE_KEYS, **{"LDS Size [bytes/block]": "lds", "Occupancy [waves/SIMD]": "occ"}))
 for k, v in rows.items():
     if "DF16b" in k or "okp_fire" in k or len(sys.argv) > 2:
         name = re.sub(r"_ZN12_GLOBAL__N_116okp_igemm_kernelI|EEv14OkpIgemmParams", "", k)
-        print(f"{name:48s} VGPR {v.get('VGPRs', -1):4d} AGPR {v.get('AGPRs', -1):4d} spill {v.get('VGPRs Spill', -1):3d} scratch {v.get('ScratchSize [bytes/lane]', -1):4d} LDS {v.get('LDS Size [bytes/block]', -1):7d} occ {v.get('Occupancy [waves/SIMD]', -1)}")
+        print(f"{name:48s} VGPR {v.get('vgprs', -1):4d} AGPR {v.get('agprs', -1):4d} spill {v.get('vgpr_spill', -1):3d} scratch {v.get('scratch', -1):4d} LDS {v.get('lds', -1):7d} occ {v.get('occ', -1)}")

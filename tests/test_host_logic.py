@@ -773,3 +773,19 @@ def test_header_is_plain_c_and_a_c_program_links_against_the_library(tmp_path):
     import ctypes
     mirrors = (_lib.okp_conv_args, _lib.okp_fire_args, _lib.okp_head_out_args, _lib.okp_camera, _lib.okp_tap, _lib.okp_tensor)
     assert version == declared == _lib.OKP_ABI and sizes == [ctypes.sizeof(m) for m in mirrors]      # the ctypes mirrors of the structs have the C layout
+
+
+def test_kernel_sources_test_only_the_listed_macros():
+    """The kernels carry no experiment builds: every macro a csrc file tests with #if / #ifdef / #ifndef / #elif is the device-compile
+    macro, one of the two stamp (in-kernel instrument) switches, or a header guard.  A new compile-time switch has to be added here on purpose."""
+    allowed = {"__HIP_DEVICE_COMPILE__", "OKP_FIRE_STAMPS", "OKP_PATCH_STAMPS"}
+    csrc = os.path.join(REPO, "object_keypoints_amd", "csrc")
+    tested, guards = set(), set()
+    for name in sorted(os.listdir(csrc)):
+        text = open(os.path.join(csrc, name)).read().replace("\\\n", " ")
+        guards |= set(re.findall(r"^[ \t]*#[ \t]*ifndef[ \t]+(\w+)[ \t]*\n[ \t]*#[ \t]*define[ \t]+\1\b", text, flags=re.M))
+        for cond in re.findall(r"^[ \t]*#[ \t]*(?:if|ifdef|ifndef|elif)\b(.*)$", text, flags=re.M):
+            cond = re.sub(r"//.*|/\*.*?\*/", "", cond)
+            tested |= set(re.findall(r"\b[A-Za-z_]\w*\b", cond)) - {"defined"}
+    assert guards and all(g.endswith("_H") for g in guards), guards
+    assert tested == allowed | guards, f"unlisted: {sorted(tested - allowed - guards)}, gone: {sorted((allowed | guards) - tested)}"
