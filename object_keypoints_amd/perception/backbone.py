@@ -514,6 +514,7 @@ class hg_module(nn.Module):
         main = torch.cuda.current_stream()
         skey, side = self._side_stream(x.t.device)
         ops.stream_wait(side, main)                     # x is ready on the side stream
+        # (every edge and lifetime below is checked by tests/test_gpu_stream_order.py: a happens-before audit of one recorded pass)
         # Tensor lifetimes across the two streams WITHOUT Tensor.record_stream (the caching allocator answers a recorded use with an
         # event record on the using stream when the tensor dies - a marker packet in the MAIN queue right behind every merge, 6-8 us of
         # delay for the kernel after it, eight times per step):

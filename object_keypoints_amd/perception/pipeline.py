@@ -1464,12 +1464,19 @@ class HostFrameFeed:
         frames = feed.acquire(slot)              # the compute stream waits for that copy (device-side wait, no host sync)
         ...                                      # launches that read `frames`
         feed.release(slot)                       # the buffer may be overwritten once the work enqueued so far has run
+
+    The ordering of the copy stream against the compute stream (ready / done, release before overwrite, the buffers' first use) is
+    checked by tests/test_gpu_stream_order.py.
     """
 
     def __init__(self, shape, dtype=torch.uint8, device=None, depth=2):
         self.device = device or _device()
         self.buffers = [torch.empty(tuple(shape), dtype=dtype, device=self.device) for _ in range(depth)]
         self.copy_stream = torch.cuda.Stream(device=self.device)
+        # The buffers come from the CURRENT stream's pool: the allocator may hand out a block whose previous owner's kernels are still in
+        # that stream's queue, safe for work enqueued on that stream only.  Their first writer is the copy stream, which therefore starts
+        # behind the current stream, once (found by the stream-order audit: the first upload into each slot was unordered against it).
+        self.copy_stream.wait_stream(torch.cuda.current_stream(self.device))
         self.ready = [torch.cuda.Event() for _ in range(depth)]
         self.done = [None] * depth
         self.next = 0
