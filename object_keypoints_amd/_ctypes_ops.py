@@ -396,25 +396,45 @@ def refine_assignments(camera, tab, pose, assignment, n_obj, model, type_count, 
 
 
 # ---- a rig's poses refined against every camera's bearings (csrc/okp_refine_views.hip): obs [B,max_obj,S,V,2], views [V,14] ----------------------
-def rig_bearings(table, count, xyc, match, member, object, n_fused, type_count, obs, stream):
+def _rig_bearings(symbol, table, count, xyc, match, member, object, n_fused, type_count, extra, outputs, stream):
+    """The two collectors: `extra` are the scalars after type_count, `outputs` obs and what follows it."""
     n, k, cap, _ = xyc.shape
-    _lib.check(_lib.lib().okp_rig_bearings(count.data_ptr(), xyc.data_ptr(), match.data_ptr(), member.data_ptr(), object.data_ptr(), n_fused.data_ptr(),
-                                           table.data_ptr(), table.shape[0], n // 2, k, cap, object.shape[1], _int32s(type_count, max(1, k - 1)), obs.data_ptr(), stream),
-               "okp_rig_bearings")
+    _lib.check(getattr(_lib.lib(), symbol)(count.data_ptr(), xyc.data_ptr(), match.data_ptr(), member.data_ptr(), object.data_ptr(), n_fused.data_ptr(), table.data_ptr(),
+                                           table.shape[0], n // 2, k, cap, object.shape[1], _int32s(type_count, max(1, k - 1)), *extra,
+                                           *(t.data_ptr() for t in outputs), stream), symbol)
+
+
+def rig_bearings(table, count, xyc, match, member, object, n_fused, type_count, obs, stream):
+    _rig_bearings("okp_rig_bearings", table, count, xyc, match, member, object, n_fused, type_count, (), (obs,), stream)
+
+
+def _refine_views(symbol, obs, prior, views, views_each, pose, assignment, n_obj, model, sigma_px, huber_px, iters, damping, pose_out, fit, n_obs, n_inlier, weight,
+                  information, status, stream):
+    """The six refinements against views, three argument lists: views_each None - the two entry points without it, huber_px, n_inlier and weight;
+    prior None - the ones without priors.  Positional throughout: a launch costs the host no spliced tuple."""
+    b, max_obj, s, v, _ = obs.shape
+    fn = getattr(_lib.lib(), symbol)
+    if views_each is None:
+        rc = fn(obs.data_ptr(), views.data_ptr(), pose.data_ptr(), assignment.data_ptr(), n_obj.data_ptr(), model.data_ptr(), sigma_px, iters, damping, b, max_obj, s, v,
+                pose_out.data_ptr(), fit.data_ptr(), n_obs.data_ptr(), information.data_ptr(), status.data_ptr(), stream)
+    elif prior is None:
+        rc = fn(obs.data_ptr(), views.data_ptr(), views_each, pose.data_ptr(), assignment.data_ptr(), n_obj.data_ptr(), model.data_ptr(), sigma_px, huber_px, iters, damping,
+                b, max_obj, s, v, pose_out.data_ptr(), fit.data_ptr(), n_obs.data_ptr(), _ptr(n_inlier), _ptr(weight), information.data_ptr(), status.data_ptr(), stream)
+    else:
+        rc = fn(obs.data_ptr(), prior.data_ptr(), views.data_ptr(), views_each, pose.data_ptr(), assignment.data_ptr(), n_obj.data_ptr(), model.data_ptr(), sigma_px, huber_px,
+                iters, damping, b, max_obj, s, v, pose_out.data_ptr(), fit.data_ptr(), n_obs.data_ptr(), _ptr(n_inlier), _ptr(weight), information.data_ptr(),
+                status.data_ptr(), stream)
+    _lib.check(rc, symbol)
 
 
 def refine_pose_views(obs, views, pose, assignment, n_obj, model, sigma_px, iters, damping, pose_out, fit, n_obs, information, status, stream):
-    b, max_obj, s, v, _ = obs.shape
-    _lib.check(_lib.lib().okp_refine_pose_views(obs.data_ptr(), views.data_ptr(), pose.data_ptr(), assignment.data_ptr(), n_obj.data_ptr(), model.data_ptr(), sigma_px,
-                                                iters, damping, b, max_obj, s, v, pose_out.data_ptr(), fit.data_ptr(), n_obs.data_ptr(), information.data_ptr(),
-                                                status.data_ptr(), stream), "okp_refine_pose_views")
+    _refine_views("okp_refine_pose_views", obs, None, views, None, pose, assignment, n_obj, model, sigma_px, None, iters, damping, pose_out, fit, n_obs, None, None,
+                  information, status, stream)
 
 
 def refine_pose_views_each(obs, views, pose, assignment, n_obj, model, sigma_px, iters, damping, pose_out, fit, n_obs, information, status, stream):
-    b, max_obj, s, v, _ = obs.shape
-    _lib.check(_lib.lib().okp_refine_pose_views_each(obs.data_ptr(), views.data_ptr(), pose.data_ptr(), assignment.data_ptr(), n_obj.data_ptr(), model.data_ptr(),
-                                                     sigma_px, iters, damping, b, max_obj, s, v, pose_out.data_ptr(), fit.data_ptr(), n_obs.data_ptr(),
-                                                     information.data_ptr(), status.data_ptr(), stream), "okp_refine_pose_views_each")
+    _refine_views("okp_refine_pose_views_each", obs, None, views, None, pose, assignment, n_obj, model, sigma_px, None, iters, damping, pose_out, fit, n_obs, None, None,
+                  information, status, stream)
 
 
 # ---- a rig's interchangeable key points resolved against every camera's bearings (csrc/okp_refine_assign_views.hip) ----------------------------------
@@ -430,11 +450,8 @@ def refine_assignments_views(obs, views, tab, pose, assignment, n_obj, model, ty
 
 def refine_pose_views_robust(obs, views, views_each, pose, assignment, n_obj, model, sigma_px, huber_px, iters, damping, pose_out, fit, n_obs, n_inlier, weight,
                              information, status, stream):
-    b, max_obj, s, v, _ = obs.shape
-    _lib.check(_lib.lib().okp_refine_pose_views_robust(obs.data_ptr(), views.data_ptr(), views_each, pose.data_ptr(), assignment.data_ptr(), n_obj.data_ptr(),
-                                                       model.data_ptr(), sigma_px, huber_px, iters, damping, b, max_obj, s, v, pose_out.data_ptr(), fit.data_ptr(),
-                                                       n_obs.data_ptr(), n_inlier.data_ptr(), weight.data_ptr(), information.data_ptr(), status.data_ptr(), stream),
-               "okp_refine_pose_views_robust")
+    _refine_views("okp_refine_pose_views_robust", obs, None, views, views_each, pose, assignment, n_obj, model, sigma_px, huber_px, iters, damping, pose_out, fit, n_obs,
+                  n_inlier, weight, information, status, stream)
 
 
 # ---- a sliding window of ticks' bearings per track (csrc/okp_window.hip): win_obs [B,T,S,W,2], win_views [B,T,W,14], win_i [B,T,4] ------------------
@@ -468,37 +485,25 @@ def window_push_views(obs, assignment, status, meas_of, track_i, track_f, track_
 
 def refine_pose_views_wide(obs, views, views_each, pose, assignment, n_obj, model, sigma_px, huber_px, iters, damping, pose_out, fit, n_obs, n_inlier, weight,
                            information, status, stream):
-    b, max_obj, s, v, _ = obs.shape
-    _lib.check(_lib.lib().okp_refine_pose_views_wide(obs.data_ptr(), views.data_ptr(), views_each, pose.data_ptr(), assignment.data_ptr(), n_obj.data_ptr(),
-                                                     model.data_ptr(), sigma_px, huber_px, iters, damping, b, max_obj, s, v, pose_out.data_ptr(), fit.data_ptr(),
-                                                     n_obs.data_ptr(), _ptr(n_inlier), _ptr(weight), information.data_ptr(), status.data_ptr(), stream),
-               "okp_refine_pose_views_wide")
+    _refine_views("okp_refine_pose_views_wide", obs, None, views, views_each, pose, assignment, n_obj, model, sigma_px, huber_px, iters, damping, pose_out, fit, n_obs,
+                  n_inlier, weight, information, status, stream)
 
 
 # ---- the views refinements weighted by the peaks' confidences: prior [B,max_obj,S,V], win_prior [B,T,S,W] / [B,T,S,W*V] -----------------------------
 def rig_bearings_weighted(table, count, xyc, match, member, object, n_fused, type_count, conf_ref, conf_floor, obs, prior, stream):
-    n, k, cap, _ = xyc.shape
-    _lib.check(_lib.lib().okp_rig_bearings_weighted(count.data_ptr(), xyc.data_ptr(), match.data_ptr(), member.data_ptr(), object.data_ptr(), n_fused.data_ptr(),
-                                                    table.data_ptr(), table.shape[0], n // 2, k, cap, object.shape[1], _int32s(type_count, max(1, k - 1)), conf_ref,
-                                                    conf_floor, obs.data_ptr(), prior.data_ptr(), stream), "okp_rig_bearings_weighted")
+    _rig_bearings("okp_rig_bearings_weighted", table, count, xyc, match, member, object, n_fused, type_count, (conf_ref, conf_floor), (obs, prior), stream)
 
 
 def refine_pose_views_weighted(obs, prior, views, views_each, pose, assignment, n_obj, model, sigma_px, huber_px, iters, damping, pose_out, fit, n_obs, n_inlier,
                                weight, information, status, stream):
-    b, max_obj, s, v, _ = obs.shape
-    _lib.check(_lib.lib().okp_refine_pose_views_weighted(obs.data_ptr(), prior.data_ptr(), views.data_ptr(), views_each, pose.data_ptr(), assignment.data_ptr(),
-                                                         n_obj.data_ptr(), model.data_ptr(), sigma_px, huber_px, iters, damping, b, max_obj, s, v, pose_out.data_ptr(),
-                                                         fit.data_ptr(), n_obs.data_ptr(), _ptr(n_inlier), _ptr(weight), information.data_ptr(), status.data_ptr(),
-                                                         stream), "okp_refine_pose_views_weighted")
+    _refine_views("okp_refine_pose_views_weighted", obs, prior, views, views_each, pose, assignment, n_obj, model, sigma_px, huber_px, iters, damping, pose_out, fit, n_obs,
+                  n_inlier, weight, information, status, stream)
 
 
 def refine_pose_views_weighted_wide(obs, prior, views, views_each, pose, assignment, n_obj, model, sigma_px, huber_px, iters, damping, pose_out, fit, n_obs, n_inlier,
                                     weight, information, status, stream):
-    b, max_obj, s, v, _ = obs.shape
-    _lib.check(_lib.lib().okp_refine_pose_views_weighted_wide(obs.data_ptr(), prior.data_ptr(), views.data_ptr(), views_each, pose.data_ptr(), assignment.data_ptr(),
-                                                              n_obj.data_ptr(), model.data_ptr(), sigma_px, huber_px, iters, damping, b, max_obj, s, v, pose_out.data_ptr(),
-                                                              fit.data_ptr(), n_obs.data_ptr(), _ptr(n_inlier), _ptr(weight), information.data_ptr(), status.data_ptr(),
-                                                              stream), "okp_refine_pose_views_weighted_wide")
+    _refine_views("okp_refine_pose_views_weighted_wide", obs, prior, views, views_each, pose, assignment, n_obj, model, sigma_px, huber_px, iters, damping, pose_out, fit,
+                  n_obs, n_inlier, weight, information, status, stream)
 
 
 def window_push_weighted(camera, tab, assignment, status, meas_of, track_i, track_f, track_pose, T_WC, min_views, max_speed, conf_ref, conf_floor, win_obs,

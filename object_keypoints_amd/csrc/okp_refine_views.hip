@@ -26,7 +26,7 @@
 //                                  further template flag: the two plain instances stay the code they are.  Two bodies, because a merged
 //                                  one, or bodies built from more shared blocks than csrc/okp_pose_math.h's pose load (plain kernel) and
 //                                  `information` writer (both), changed the instances' instructions and their time (docs/EXPERIMENTS.md);
-//                                  the launch parameters and the argument checks of all four entry points are shared (refine_views_params).
+//                                  the launch parameters, the argument checks and the launcher of the four entry points of this file are shared.
 //   PRIOR instances (okp_refine_pose_views_weighted, okp_rig_bearings_weighted; contract in include/okp.h): a template flag on the two
 //                                  refinement kernels - the lane keeps the priors of its observations in registers, 1.0 where it has none,
 //                                  and the factor scales the first j of every product (plain) or the Huber weight, so with all priors
@@ -523,35 +523,41 @@ extern "C" int okp_rig_bearings_weighted(const int32_t* count, const float* xyc,
                              K, cap, cap_f, type_count, true, conf_ref, conf_floor, obs, prior, stream);
 }
 
-// the four one-wave entry points: plain or Huber (huber_px), one views table for every object or one per object
-static int refine_views_launch(const char* fn, const char* what, const double* obs, const double* views, const int32_t* views_each, bool each, const double* pose,
-                               const int32_t* assignment, const int32_t* n_obj, const double* model, double sigma_px, const double* huber_px, int32_t iters,
-                               double damping, int32_t B, int32_t max_obj, int32_t S, int32_t V, double* pose_out, double* fit, int32_t* n_obs, int32_t* n_inlier,
-                               double* weight, double* information, int32_t* status, void* stream) {
+// The four one-wave entry points behind one launcher: plain or Huber, one views table for every object or one per object, with priors or without.
+// huber_px and views_each are null for the entry points that have none; weighted: okp_refine_pose_views_weighted's - prior is required, V may
+// be refused only beyond the wide limit (above one wave the entry point has handed off already) and huber_px = 0 selects the plain cost
+static int refine_views_launch(const char* fn, const char* what, bool weighted, const double* obs, const double* prior, const double* views, const int32_t* views_each,
+                               bool each, const double* pose, const int32_t* assignment, const int32_t* n_obj, const double* model, double sigma_px, const double* huber_px,
+                               int32_t iters, double damping, int32_t B, int32_t max_obj, int32_t S, int32_t V, double* pose_out, double* fit, int32_t* n_obs,
+                               int32_t* n_inlier, double* weight, double* information, int32_t* status, void* stream) {
   ViewsParams p;
-  const int rc = refine_views_params(fn, obs, views, pose, assignment, n_obj, model, sigma_px, huber_px, false, views_each, iters, damping, B, max_obj, S, V,
-                                     OKP_REFINE_MAX_VIEWS, pose_out, fit, n_obs, n_inlier, weight, information, status, p);
+  const int rc = refine_views_params(fn, obs, views, pose, assignment, n_obj, model, sigma_px, huber_px, weighted, views_each, iters, damping, B, max_obj, S, V,
+                                     weighted ? OKP_REFINE_WIDE_MAX_VIEWS : OKP_REFINE_MAX_VIEWS, pose_out, fit, n_obs, n_inlier, weight, information, status, p);
   if (rc) return rc;
-  const dim3 grid((unsigned)((size_t)B * max_obj)), block(64);
-  const hipStream_t st = (hipStream_t)stream;
-  if (!huber_px && each) hipLaunchKernelGGL((okp_refine_pose_views_kernel<true, false>), grid, block, 0, st, p);
-  else if (!huber_px) hipLaunchKernelGGL((okp_refine_pose_views_kernel<false, false>), grid, block, 0, st, p);
-  else if (each) hipLaunchKernelGGL((okp_refine_pose_views_robust_kernel<true, false>), grid, block, 0, st, p);
-  else hipLaunchKernelGGL((okp_refine_pose_views_robust_kernel<false, false>), grid, block, 0, st, p);
+  if (weighted && !prior) { okp_set_error("%s: null prior", fn); return OKP_EINVAL; }
+  p.prior = prior;
+  using Kernel = void (*)(const ViewsParams);
+  static const Kernel instance[2][2][2] = {          // [PRIOR][Huber][!EACH]: named in the order the file has always emitted them, so its device code stays the same bytes
+      {{okp_refine_pose_views_kernel<true, false>, okp_refine_pose_views_kernel<false, false>},
+       {okp_refine_pose_views_robust_kernel<true, false>, okp_refine_pose_views_robust_kernel<false, false>}},
+      {{okp_refine_pose_views_kernel<true, true>, okp_refine_pose_views_kernel<false, true>},
+       {okp_refine_pose_views_robust_kernel<true, true>, okp_refine_pose_views_robust_kernel<false, true>}}};
+  const bool robust = huber_px && *huber_px > 0.0;                // (an entry point that does not take 0 as the plain cost has refused it)
+  hipLaunchKernelGGL(instance[weighted][robust][!each], dim3((unsigned)((size_t)B * max_obj)), dim3(64), 0, (hipStream_t)stream, p);
   return okp_check_hip(hipGetLastError(), what);
 }
 
 extern "C" int okp_refine_pose_views(const double* obs, const double* views, const double* pose, const int32_t* assignment, const int32_t* n_obj,
                                      const double* model, double sigma_px, int32_t iters, double damping, int32_t B, int32_t max_obj, int32_t S,
                                      int32_t V, double* pose_out, double* fit, int32_t* n_obs, double* information, int32_t* status, void* stream) {
-  return refine_views_launch("okp_refine_pose_views", "okp_refine_pose_views launch", obs, views, nullptr, false, pose, assignment, n_obj, model, sigma_px, nullptr,
+  return refine_views_launch("okp_refine_pose_views", "okp_refine_pose_views launch", false, obs, nullptr, views, nullptr, false, pose, assignment, n_obj, model, sigma_px, nullptr,
                              iters, damping, B, max_obj, S, V, pose_out, fit, n_obs, nullptr, nullptr, information, status, stream);
 }
 
 extern "C" int okp_refine_pose_views_each(const double* obs, const double* views, const double* pose, const int32_t* assignment, const int32_t* n_obj,
                                           const double* model, double sigma_px, int32_t iters, double damping, int32_t B, int32_t max_obj, int32_t S,
                                           int32_t V, double* pose_out, double* fit, int32_t* n_obs, double* information, int32_t* status, void* stream) {
-  return refine_views_launch("okp_refine_pose_views_each", "okp_refine_pose_views_each launch", obs, views, nullptr, true, pose, assignment, n_obj, model, sigma_px,
+  return refine_views_launch("okp_refine_pose_views_each", "okp_refine_pose_views_each launch", false, obs, nullptr, views, nullptr, true, pose, assignment, n_obj, model, sigma_px,
                              nullptr, iters, damping, B, max_obj, S, V, pose_out, fit, n_obs, nullptr, nullptr, information, status, stream);
 }
 
@@ -559,7 +565,7 @@ extern "C" int okp_refine_pose_views_robust(const double* obs, const double* vie
                                             const int32_t* n_obj, const double* model, double sigma_px, double huber_px, int32_t iters, double damping, int32_t B,
                                             int32_t max_obj, int32_t S, int32_t V, double* pose_out, double* fit, int32_t* n_obs, int32_t* n_inlier, double* weight,
                                             double* information, int32_t* status, void* stream) {
-  return refine_views_launch("okp_refine_pose_views_robust", "okp_refine_pose_views_robust launch", obs, views, &views_each, views_each != 0, pose, assignment, n_obj,
+  return refine_views_launch("okp_refine_pose_views_robust", "okp_refine_pose_views_robust launch", false, obs, nullptr, views, &views_each, views_each != 0, pose, assignment, n_obj,
                              model, sigma_px, &huber_px, iters, damping, B, max_obj, S, V, pose_out, fit, n_obs, n_inlier, weight, information, status, stream);
 }
 
@@ -572,18 +578,6 @@ extern "C" int okp_refine_pose_views_weighted(const double* obs, const double* p
   if (V > OKP_REFINE_MAX_VIEWS)
     return okp_refine_views_weighted_wide(fn, obs, prior, views, views_each, pose, assignment, n_obj, model, sigma_px, huber_px, iters, damping, B, max_obj, S, V,
                                           pose_out, fit, n_obs, n_inlier, weight, information, status, stream);
-  ViewsParams p;
-  const int rc = refine_views_params(fn, obs, views, pose, assignment, n_obj, model, sigma_px, &huber_px, true, &views_each, iters, damping, B, max_obj, S, V,
-                                     OKP_REFINE_WIDE_MAX_VIEWS, pose_out, fit, n_obs, n_inlier, weight, information, status, p);
-  if (rc) return rc;
-  if (!prior) { okp_set_error("%s: null prior", fn); return OKP_EINVAL; }
-  p.prior = prior;
-  const dim3 grid((unsigned)((size_t)B * max_obj)), block(64);
-  const hipStream_t st = (hipStream_t)stream;
-  const bool robust = huber_px > 0.0, each = views_each != 0;
-  if (!robust && each) hipLaunchKernelGGL((okp_refine_pose_views_kernel<true, true>), grid, block, 0, st, p);
-  else if (!robust) hipLaunchKernelGGL((okp_refine_pose_views_kernel<false, true>), grid, block, 0, st, p);
-  else if (each) hipLaunchKernelGGL((okp_refine_pose_views_robust_kernel<true, true>), grid, block, 0, st, p);
-  else hipLaunchKernelGGL((okp_refine_pose_views_robust_kernel<false, true>), grid, block, 0, st, p);
-  return okp_check_hip(hipGetLastError(), "okp_refine_pose_views_weighted launch");
+  return refine_views_launch(fn, "okp_refine_pose_views_weighted launch", true, obs, prior, views, &views_each, views_each != 0, pose, assignment, n_obj, model, sigma_px,
+                             &huber_px, iters, damping, B, max_obj, S, V, pose_out, fit, n_obs, n_inlier, weight, information, status, stream);
 }

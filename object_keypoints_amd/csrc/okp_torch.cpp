@@ -783,63 +783,160 @@ void refine_assignments(at::ArrayRef<double> camera, const Tensor& tab, const Te
 
 // A rig's poses refined against every camera's bearings (csrc/okp_refine_views.hip).  rig_bearings: the fused tick's count / xyc / match / member /
 // object / n_fused and the calibration table -> obs [cap_f,S,2P,2] float64; refine_pose_views: obs [B,max_obj,S,V,2], views [V,14] and the pose
-// stage's pose / assignment / n_obj and the model -> pose_out [B,max_obj,12], fit [B,max_obj,2], n_obs [B,max_obj], information [B,max_obj,36], status
-void rig_bearings(const Tensor& table, const Tensor& count, const Tensor& xyc, const Tensor& match, const Tensor& member, const Tensor& object, const Tensor& n_fused,
-                  at::IntArrayRef type_count, const Tensor& obs, int64_t stream) {
+// stage's pose / assignment / n_obj and the model -> pose_out [B,max_obj,12], fit [B,max_obj,2], n_obs [B,max_obj], information [B,max_obj,36], status.
+// The two collectors behind one body: prior [cap_f,S,2P] (with conf_ref / conf_floor) makes it rig_bearings_weighted (null: rig_bearings; a pointer, as in
+// window_push_any, so that a call copies no tensor handle)
+void rig_bearings_any(const char* op, const Tensor& table, const Tensor& count, const Tensor& xyc, const Tensor& match, const Tensor& member, const Tensor& object,
+                      const Tensor& n_fused, at::IntArrayRef type_count, double conf_ref, double conf_floor, const Tensor& obs, const Tensor* prior, int64_t stream) {
   const int64_t P = stereo_tick_pairs(count, xyc);
   const int32_t n_table = stereo_table_size(table);
   check_dev(match, at::kInt, "match"); check_dev(member, at::kInt, "member"); check_dev(object, at::kInt, "object"); check_dev(n_fused, at::kInt, "n_fused");
   check_dev(obs, at::kDouble, "obs");
+  if (prior) check_dev(*prior, at::kDouble, "prior");
   const int64_t K = xyc.size(1), cap = xyc.size(2);
   TORCH_CHECK(object.dim() == 2 && object.size(0) == K, "okp: object is [K,cap_f] int32 (rig_fuse)");
   const int64_t cap_f = object.size(1);
   int64_t S = 1;
   for (auto c : type_count) S += c;
   TORCH_CHECK((int64_t)type_count.size() == K - 1, "okp: type_count has K-1 entries");
-  TORCH_CHECK(match.numel() == P * K * cap && member.numel() == P * K * cap && n_fused.numel() == K && obs.numel() == cap_f * S * 2 * P * 2,
-              "okp: rig_bearings buffers are match and member [P,K,cap], n_fused [K] int32 and obs [cap_f,S,2P,2] float64");
+  TORCH_CHECK(match.numel() == P * K * cap && member.numel() == P * K * cap && n_fused.numel() == K && obs.numel() == cap_f * S * 2 * P * 2 &&
+              (!prior || prior->numel() == cap_f * S * 2 * P),
+              "okp: ", op, " buffers are match and member [P,K,cap], n_fused [K] int32", prior ? ", obs [cap_f,S,2P,2] and prior [cap_f,S,2P] float64" : " and obs [cap_f,S,2P,2] float64");
   std::vector<int32_t> tc(type_count.begin(), type_count.end());
   tc.push_back(0);                                  // (K = 1: a non-null pointer for the entry point to refuse K with)
-  check_rc(okp_rig_bearings(count.data_ptr<int32_t>(), xyc.data_ptr<float>(), match.data_ptr<int32_t>(), member.data_ptr<int32_t>(), object.data_ptr<int32_t>(),
-                            n_fused.data_ptr<int32_t>(), reinterpret_cast<const okp_stereo_pair*>(table.data_ptr()), n_table, (int32_t)P, (int32_t)K, (int32_t)cap,
-                            (int32_t)cap_f, tc.data(), obs.data_ptr<double>(), sp(stream)), "okp_rig_bearings");
+  const okp_stereo_pair* table_p = reinterpret_cast<const okp_stereo_pair*>(table.data_ptr());
+  if (prior)
+    check_rc(okp_rig_bearings_weighted(count.data_ptr<int32_t>(), xyc.data_ptr<float>(), match.data_ptr<int32_t>(), member.data_ptr<int32_t>(), object.data_ptr<int32_t>(),
+                                       n_fused.data_ptr<int32_t>(), table_p, n_table, (int32_t)P, (int32_t)K, (int32_t)cap, (int32_t)cap_f, tc.data(), conf_ref, conf_floor,
+                                       obs.data_ptr<double>(), prior->data_ptr<double>(), sp(stream)), "okp_rig_bearings_weighted");
+  else
+    check_rc(okp_rig_bearings(count.data_ptr<int32_t>(), xyc.data_ptr<float>(), match.data_ptr<int32_t>(), member.data_ptr<int32_t>(), object.data_ptr<int32_t>(),
+                              n_fused.data_ptr<int32_t>(), table_p, n_table, (int32_t)P, (int32_t)K, (int32_t)cap, (int32_t)cap_f, tc.data(), obs.data_ptr<double>(),
+                              sp(stream)), "okp_rig_bearings");
 }
 
-// each = false: views [V,14], one table for every object (okp_refine_pose_views); each = true: views [B,max_obj,V,14] (okp_refine_pose_views_each)
-void refine_views(bool each, const Tensor& obs, const Tensor& views, const Tensor& pose, const Tensor& assignment, const Tensor& n_obj, const Tensor& model, double sigma_px,
-                  int64_t iters, double damping, const Tensor& pose_out, const Tensor& fit, const Tensor& n_obs, const Tensor& information, const Tensor& status,
-                  int64_t stream) {
-  check_dev(obs, at::kDouble, "obs"); check_dev(views, at::kDouble, "views"); check_dev(pose, at::kDouble, "pose"); check_dev(assignment, at::kInt, "assignment");
-  check_dev(n_obj, at::kInt, "n_obj"); check_dev(model, at::kDouble, "model"); check_dev(pose_out, at::kDouble, "pose_out"); check_dev(fit, at::kDouble, "fit");
-  check_dev(n_obs, at::kInt, "n_obs"); check_dev(information, at::kDouble, "information"); check_dev(status, at::kInt, "status");
+void rig_bearings(const Tensor& table, const Tensor& count, const Tensor& xyc, const Tensor& match, const Tensor& member, const Tensor& object, const Tensor& n_fused,
+                  at::IntArrayRef type_count, const Tensor& obs, int64_t stream) {
+  rig_bearings_any("rig_bearings", table, count, xyc, match, member, object, n_fused, type_count, 0.0, 0.0, obs, nullptr, stream);
+}
+
+// rig_bearings with conf_ref / conf_floor -> obs [cap_f,S,2P,2] and prior [cap_f,S,2P] float64
+void rig_bearings_weighted(const Tensor& table, const Tensor& count, const Tensor& xyc, const Tensor& match, const Tensor& member, const Tensor& object,
+                           const Tensor& n_fused, at::IntArrayRef type_count, double conf_ref, double conf_floor, const Tensor& obs, const Tensor& prior, int64_t stream) {
+  rig_bearings_any("rig_bearings_weighted", table, count, xyc, match, member, object, n_fused, type_count, conf_ref, conf_floor, obs, &prior, stream);
+}
+
+// what every op that takes a table of bearings begins with: obs is [B,max_obj,S,V,2]
+struct ViewsDims { int64_t B, max_obj, S, V; };
+inline ViewsDims views_dims(const Tensor& obs) {
   TORCH_CHECK(obs.dim() == 5 && obs.size(4) == 2, "okp: obs is [B,max_obj,S,V,2] float64");
-  const int64_t B = obs.size(0), max_obj = obs.size(1), S = obs.size(2), V = obs.size(3);
-  TORCH_CHECK(views.numel() == (each ? B * max_obj : 1) * V * 14, each ? "okp: refine_pose_views_each takes views [B,max_obj,V,14]: one table per object" :
-                                                                           "okp: refine_pose_views inputs are views [V,14], pose [B,max_obj,12], assignment [B,max_obj,S], n_obj [B] and model [S,3]");
+  return {obs.size(0), obs.size(1), obs.size(2), obs.size(3)};
+}
+
+// The six refinements against views behind one body.  What differs between them is their form: kViewsPlain has no Huber loss, and its wrappers set views_each: 0 for
+// refine_pose_views (views [V,14], one table for every object), 1 for refine_pose_views_each ([B,max_obj,V,14]); kViewsRobust (refine_pose_views_robust) has
+// views_each, a positive huber_px, fit [B,max_obj,4] and n_inlier [B,max_obj] and weight [B,max_obj,S,V] next to the plain outputs; kViewsWide
+// (refine_pose_views_wide, V up to 512, and with prior [B,max_obj,S,V] the two weighted ops) takes huber_px = 0 as the plain cost: fit is then [B,max_obj,2] and
+// n_inlier and weight may be None.  `op` is the name the sentences use (refine_pose_views_weighted_wide speaks as refine_pose_views_weighted), `wide` selects that
+// entry point under a prior; prior, n_inlier and weight are pointers (null: the op has none), so that a call copies no tensor handle
+enum ViewsForm { kViewsPlain, kViewsRobust, kViewsWide };
+void refine_views_any(const char* op, ViewsForm form, bool wide, const Tensor& obs, const Tensor* prior, const Tensor& views,
+                      int64_t views_each, const Tensor& pose, const Tensor& assignment, const Tensor& n_obj, const Tensor& model, double sigma_px, double huber_px,
+                      int64_t iters, double damping, const Tensor& pose_out, const Tensor& fit, const Tensor& n_obs, const Tensor* n_inlier, const Tensor* weight,
+                      const Tensor& information, const Tensor& status, int64_t stream) {
+  const bool plain = form == kViewsPlain, each = views_each == 1, robust = form == kViewsRobust || huber_px > 0.0;
+  check_dev(obs, at::kDouble, "obs");
+  if (prior) check_dev(*prior, at::kDouble, "prior");
+  check_dev(views, at::kDouble, "views"); check_dev(pose, at::kDouble, "pose"); check_dev(assignment, at::kInt, "assignment"); check_dev(n_obj, at::kInt, "n_obj");
+  check_dev(model, at::kDouble, "model"); check_dev(pose_out, at::kDouble, "pose_out"); check_dev(fit, at::kDouble, "fit"); check_dev(n_obs, at::kInt, "n_obs");
+  if (form == kViewsRobust) { check_dev(*n_inlier, at::kInt, "n_inlier"); check_dev(*weight, at::kDouble, "weight"); }
+  check_dev(information, at::kDouble, "information"); check_dev(status, at::kInt, "status");
+  if (form == kViewsWide && n_inlier) check_dev(*n_inlier, at::kInt, "n_inlier");
+  if (form == kViewsWide && weight) check_dev(*weight, at::kDouble, "weight");
+  const auto [B, max_obj, S, V] = views_dims(obs);
+  TORCH_CHECK(!prior || prior->numel() == B * max_obj * S * V, "okp: prior is [B,max_obj,S,V] float64, one value per entry of obs");
+  TORCH_CHECK(views_each >= INT32_MIN && views_each <= INT32_MAX, "okp: views_each does not fit an int32");
+  TORCH_CHECK((views_each != 0 && views_each != 1) || views.numel() == (views_each == 1 ? B * max_obj : 1) * V * 14,      // (any other value: the entry point refuses it)
+              "okp: ", op, !plain ? " takes views [V,14] (views_each = 0) or [B,max_obj,V,14] (views_each = 1)" : each ? " takes views [B,max_obj,V,14]: one table per object" :
+              " inputs are views [V,14], pose [B,max_obj,12], assignment [B,max_obj,S], n_obj [B] and model [S,3]");
   TORCH_CHECK(pose.numel() == B * max_obj * 12 && assignment.numel() == B * max_obj * S && n_obj.numel() == B && model.numel() == S * 3,
-              "okp: refine_pose_views inputs are views [V,14], pose [B,max_obj,12], assignment [B,max_obj,S], n_obj [B] and model [S,3]");
-  TORCH_CHECK(pose_out.numel() == B * max_obj * 12 && fit.numel() == B * max_obj * 2 && n_obs.numel() == B * max_obj && information.numel() == B * max_obj * 36 &&
+              "okp: ", plain ? "refine_pose_views inputs are views [V,14], " : op, plain ? "" : " inputs are ", "pose [B,max_obj,12], assignment [B,max_obj,S], n_obj [B] and model [S,3]");
+  TORCH_CHECK(pose_out.numel() == B * max_obj * 12 && fit.numel() == B * max_obj * (robust ? 4 : 2) && n_obs.numel() == B * max_obj &&
+              (form != kViewsRobust || (n_inlier->numel() == B * max_obj && weight->numel() == B * max_obj * S * V)) && information.numel() == B * max_obj * 36 &&
               status.numel() == B * max_obj,
-              "okp: refine_pose_views outputs are pose_out [B,max_obj,12], fit [B,max_obj,2], n_obs [B,max_obj], information [B,max_obj,36] and status [B,max_obj]");
+              "okp: ", plain ? "refine_pose_views" : op, " outputs are pose_out [B,max_obj,12], fit [B,max_obj,", plain ? "2]" : form == kViewsRobust ? "4]" : "2] ([B,max_obj,4] with huber_px > 0)",
+              form == kViewsRobust ? ", n_obs and n_inlier [B,max_obj], weight [B,max_obj,S,V]," : ", n_obs [B,max_obj],", " information [B,max_obj,36] and status [B,max_obj]");
+  TORCH_CHECK(form != kViewsWide || ((!n_inlier || n_inlier->numel() == B * max_obj) && (!weight || weight->numel() == B * max_obj * S * V)),
+              "okp: ", op, " writes n_inlier [B,max_obj] and weight [B,max_obj,S,V] when huber_px > 0");
   TORCH_CHECK(iters >= INT32_MIN && iters <= INT32_MAX, "okp: iters does not fit an int32");
   TORCH_CHECK(B <= INT32_MAX && max_obj <= INT32_MAX && S <= INT32_MAX && V <= INT32_MAX, "okp: obs is too large");
-  check_rc((each ? okp_refine_pose_views_each : okp_refine_pose_views)(
-               obs.data_ptr<double>(), views.data_ptr<double>(), pose.data_ptr<double>(), assignment.data_ptr<int32_t>(), n_obj.data_ptr<int32_t>(),
-               model.data_ptr<double>(), sigma_px, (int32_t)iters, damping, (int32_t)B, (int32_t)max_obj, (int32_t)S, (int32_t)V,
-               pose_out.data_ptr<double>(), fit.data_ptr<double>(), n_obs.data_ptr<int32_t>(), information.data_ptr<double>(),
-               status.data_ptr<int32_t>(), sp(stream)), each ? "okp_refine_pose_views_each" : "okp_refine_pose_views");
+  const double* obs_p = obs.data_ptr<double>(); const double* views_p = views.data_ptr<double>(); const double* pose_p = pose.data_ptr<double>();
+  const int32_t* as_p = assignment.data_ptr<int32_t>(); const int32_t* no_p = n_obj.data_ptr<int32_t>(); const double* model_p = model.data_ptr<double>();
+  double* out_p = pose_out.data_ptr<double>(); double* fit_p = fit.data_ptr<double>(); int32_t* nobs_p = n_obs.data_ptr<int32_t>();
+  int32_t* ni_p = n_inlier ? n_inlier->data_ptr<int32_t>() : nullptr; double* w_p = weight ? weight->data_ptr<double>() : nullptr;
+  double* info_p = information.data_ptr<double>(); int32_t* st_p = status.data_ptr<int32_t>();
+  if (plain)
+    check_rc((each ? okp_refine_pose_views_each : okp_refine_pose_views)(obs_p, views_p, pose_p, as_p, no_p, model_p, sigma_px, (int32_t)iters, damping, (int32_t)B,
+                                                                         (int32_t)max_obj, (int32_t)S, (int32_t)V, out_p, fit_p, nobs_p, info_p, st_p, sp(stream)),
+             each ? "okp_refine_pose_views_each" : "okp_refine_pose_views");
+  else if (!prior)
+    check_rc((form == kViewsRobust ? okp_refine_pose_views_robust : okp_refine_pose_views_wide)(
+                 obs_p, views_p, (int32_t)views_each, pose_p, as_p, no_p, model_p, sigma_px, huber_px, (int32_t)iters, damping, (int32_t)B, (int32_t)max_obj, (int32_t)S,
+                 (int32_t)V, out_p, fit_p, nobs_p, ni_p, w_p, info_p, st_p, sp(stream)), form == kViewsRobust ? "okp_refine_pose_views_robust" : "okp_refine_pose_views_wide");
+  else
+    check_rc((wide ? okp_refine_pose_views_weighted_wide : okp_refine_pose_views_weighted)(
+                 obs_p, prior->data_ptr<double>(), views_p, (int32_t)views_each, pose_p, as_p, no_p, model_p, sigma_px, huber_px, (int32_t)iters, damping, (int32_t)B,
+                 (int32_t)max_obj, (int32_t)S, (int32_t)V, out_p, fit_p, nobs_p, ni_p, w_p, info_p, st_p, sp(stream)),
+             wide ? "okp_refine_pose_views_weighted_wide" : "okp_refine_pose_views_weighted");
 }
 
 void refine_pose_views(const Tensor& obs, const Tensor& views, const Tensor& pose, const Tensor& assignment, const Tensor& n_obj, const Tensor& model, double sigma_px,
                        int64_t iters, double damping, const Tensor& pose_out, const Tensor& fit, const Tensor& n_obs, const Tensor& information, const Tensor& status,
                        int64_t stream) {
-  refine_views(false, obs, views, pose, assignment, n_obj, model, sigma_px, iters, damping, pose_out, fit, n_obs, information, status, stream);
+  refine_views_any("refine_pose_views", kViewsPlain, false, obs, nullptr, views, 0, pose, assignment, n_obj, model, sigma_px, 0.0, iters,
+                   damping, pose_out, fit, n_obs, nullptr, nullptr, information, status, stream);
 }
 
 void refine_pose_views_each(const Tensor& obs, const Tensor& views, const Tensor& pose, const Tensor& assignment, const Tensor& n_obj, const Tensor& model, double sigma_px,
                             int64_t iters, double damping, const Tensor& pose_out, const Tensor& fit, const Tensor& n_obs, const Tensor& information, const Tensor& status,
                             int64_t stream) {
-  refine_views(true, obs, views, pose, assignment, n_obj, model, sigma_px, iters, damping, pose_out, fit, n_obs, information, status, stream);
+  refine_views_any("refine_pose_views_each", kViewsPlain, false, obs, nullptr, views, 1, pose, assignment, n_obj, model, sigma_px, 0.0,
+                   iters, damping, pose_out, fit, n_obs, nullptr, nullptr, information, status, stream);
+}
+
+void refine_pose_views_robust(const Tensor& obs, const Tensor& views, int64_t views_each, const Tensor& pose, const Tensor& assignment, const Tensor& n_obj,
+                              const Tensor& model, double sigma_px, double huber_px, int64_t iters, double damping, const Tensor& pose_out, const Tensor& fit,
+                              const Tensor& n_obs, const Tensor& n_inlier, const Tensor& weight, const Tensor& information, const Tensor& status, int64_t stream) {
+  refine_views_any("refine_pose_views_robust", kViewsRobust, false, obs, nullptr, views, views_each, pose, assignment, n_obj, model,
+                   sigma_px, huber_px, iters, damping, pose_out, fit, n_obs, &n_inlier, &weight, information, status, stream);
+}
+
+inline const Tensor* ptr_of(const optional<Tensor>& t) { return t.has_value() ? &*t : nullptr; }
+
+void refine_pose_views_wide(const Tensor& obs, const Tensor& views, int64_t views_each, const Tensor& pose, const Tensor& assignment, const Tensor& n_obj,
+                            const Tensor& model, double sigma_px, double huber_px, int64_t iters, double damping, const Tensor& pose_out, const Tensor& fit,
+                            const Tensor& n_obs, const optional<Tensor>& n_inlier, const optional<Tensor>& weight, const Tensor& information, const Tensor& status,
+                            int64_t stream) {
+  refine_views_any("refine_pose_views_wide", kViewsWide, false, obs, nullptr, views, views_each, pose, assignment, n_obj, model, sigma_px,
+                   huber_px, iters, damping, pose_out, fit, n_obs, ptr_of(n_inlier), ptr_of(weight), information, status, stream);
+}
+
+// refine_pose_views_wide's arguments and prior [B,max_obj,S,V] (include/okp.h: okp_refine_pose_views_weighted)
+void refine_pose_views_weighted(const Tensor& obs, const Tensor& prior, const Tensor& views, int64_t views_each, const Tensor& pose, const Tensor& assignment,
+                                const Tensor& n_obj, const Tensor& model, double sigma_px, double huber_px, int64_t iters, double damping, const Tensor& pose_out,
+                                const Tensor& fit, const Tensor& n_obs, const optional<Tensor>& n_inlier, const optional<Tensor>& weight, const Tensor& information,
+                                const Tensor& status, int64_t stream) {
+  refine_views_any("refine_pose_views_weighted", kViewsWide, false, obs, &prior, views, views_each, pose, assignment, n_obj, model,
+                   sigma_px, huber_px, iters, damping, pose_out, fit, n_obs, ptr_of(n_inlier), ptr_of(weight), information, status, stream);
+}
+
+// the same on the wide kernel's instance whatever V is (okp_refine_pose_views_weighted_wide)
+void refine_pose_views_weighted_wide(const Tensor& obs, const Tensor& prior, const Tensor& views, int64_t views_each, const Tensor& pose, const Tensor& assignment,
+                                     const Tensor& n_obj, const Tensor& model, double sigma_px, double huber_px, int64_t iters, double damping, const Tensor& pose_out,
+                                     const Tensor& fit, const Tensor& n_obs, const optional<Tensor>& n_inlier, const optional<Tensor>& weight, const Tensor& information,
+                                     const Tensor& status, int64_t stream) {
+  refine_views_any("refine_pose_views_weighted", kViewsWide, true, obs, &prior, views, views_each, pose, assignment, n_obj, model,
+                   sigma_px, huber_px, iters, damping, pose_out, fit, n_obs, ptr_of(n_inlier), ptr_of(weight), information, status, stream);
 }
 
 // A rig's interchangeable key points resolved against every camera's bearings (csrc/okp_refine_assign_views.hip): refine_pose_views' obs and views,
@@ -853,8 +950,7 @@ void refine_assignments_views(const Tensor& obs, const Tensor& views, const Tens
   check_dev(assignment, at::kInt, "assignment"); check_dev(n_obj, at::kInt, "n_obj"); check_dev(model, at::kDouble, "model"); check_dev(pose_out, at::kDouble, "pose_out");
   check_dev(fit, at::kDouble, "fit"); check_dev(n_obs, at::kInt, "n_obs"); check_dev(information, at::kDouble, "information"); check_dev(status, at::kInt, "status");
   check_dev(assignment_out, at::kInt, "assignment_out"); check_dev(hypothesis, at::kInt, "hypothesis"); check_dev(cost, at::kDouble, "cost");
-  TORCH_CHECK(obs.dim() == 5 && obs.size(4) == 2, "okp: obs is [B,max_obj,S,V,2] float64");
-  const int64_t B = obs.size(0), max_obj = obs.size(1), S = obs.size(2), V = obs.size(3);
+  const auto [B, max_obj, S, V] = views_dims(obs);
   int64_t want = 1;
   for (auto c : type_count) want += c;
   TORCH_CHECK(want == S && model.numel() == S * 3, "okp: obs has S = 1 + sum(type_count) slots and model is [S,3] float64");
@@ -873,35 +969,6 @@ void refine_assignments_views(const Tensor& obs, const Tensor& views, const Tens
                                         (int32_t)B, (int32_t)max_obj, (int32_t)V, pose_out.data_ptr<double>(), fit.data_ptr<double>(), n_obs.data_ptr<int32_t>(),
                                         information.data_ptr<double>(), status.data_ptr<int32_t>(), assignment_out.data_ptr<int32_t>(), hypothesis.data_ptr<int32_t>(),
                                         cost.data_ptr<double>(), sp(stream)), "okp_refine_assignments_views");
-}
-
-// The two under a Huber loss (okp_refine_pose_views_robust): views [V,14] (views_each = 0) or [B,max_obj,V,14] (1); fit is [B,max_obj,4], and
-// n_inlier [B,max_obj] and weight [B,max_obj,S,V] are written next to the plain outputs
-void refine_pose_views_robust(const Tensor& obs, const Tensor& views, int64_t views_each, const Tensor& pose, const Tensor& assignment, const Tensor& n_obj,
-                              const Tensor& model, double sigma_px, double huber_px, int64_t iters, double damping, const Tensor& pose_out, const Tensor& fit,
-                              const Tensor& n_obs, const Tensor& n_inlier, const Tensor& weight, const Tensor& information, const Tensor& status, int64_t stream) {
-  check_dev(obs, at::kDouble, "obs"); check_dev(views, at::kDouble, "views"); check_dev(pose, at::kDouble, "pose"); check_dev(assignment, at::kInt, "assignment");
-  check_dev(n_obj, at::kInt, "n_obj"); check_dev(model, at::kDouble, "model"); check_dev(pose_out, at::kDouble, "pose_out"); check_dev(fit, at::kDouble, "fit");
-  check_dev(n_obs, at::kInt, "n_obs"); check_dev(n_inlier, at::kInt, "n_inlier"); check_dev(weight, at::kDouble, "weight");
-  check_dev(information, at::kDouble, "information"); check_dev(status, at::kInt, "status");
-  TORCH_CHECK(obs.dim() == 5 && obs.size(4) == 2, "okp: obs is [B,max_obj,S,V,2] float64");
-  const int64_t B = obs.size(0), max_obj = obs.size(1), S = obs.size(2), V = obs.size(3);
-  TORCH_CHECK(views_each >= INT32_MIN && views_each <= INT32_MAX, "okp: views_each does not fit an int32");
-  TORCH_CHECK((views_each != 0 && views_each != 1) || views.numel() == (views_each == 1 ? B * max_obj : 1) * V * 14,      // (any other value: the entry point refuses it)
-              "okp: refine_pose_views_robust takes views [V,14] (views_each = 0) or [B,max_obj,V,14] (views_each = 1)");
-  TORCH_CHECK(pose.numel() == B * max_obj * 12 && assignment.numel() == B * max_obj * S && n_obj.numel() == B && model.numel() == S * 3,
-              "okp: refine_pose_views_robust inputs are pose [B,max_obj,12], assignment [B,max_obj,S], n_obj [B] and model [S,3]");
-  TORCH_CHECK(pose_out.numel() == B * max_obj * 12 && fit.numel() == B * max_obj * 4 && n_obs.numel() == B * max_obj && n_inlier.numel() == B * max_obj &&
-              weight.numel() == B * max_obj * S * V && information.numel() == B * max_obj * 36 && status.numel() == B * max_obj,
-              "okp: refine_pose_views_robust outputs are pose_out [B,max_obj,12], fit [B,max_obj,4], n_obs and n_inlier [B,max_obj], weight [B,max_obj,S,V], "
-              "information [B,max_obj,36] and status [B,max_obj]");
-  TORCH_CHECK(iters >= INT32_MIN && iters <= INT32_MAX, "okp: iters does not fit an int32");
-  TORCH_CHECK(B <= INT32_MAX && max_obj <= INT32_MAX && S <= INT32_MAX && V <= INT32_MAX, "okp: obs is too large");
-  check_rc(okp_refine_pose_views_robust(obs.data_ptr<double>(), views.data_ptr<double>(), (int32_t)views_each, pose.data_ptr<double>(), assignment.data_ptr<int32_t>(),
-                                        n_obj.data_ptr<int32_t>(), model.data_ptr<double>(), sigma_px, huber_px, (int32_t)iters, damping, (int32_t)B, (int32_t)max_obj,
-                                        (int32_t)S, (int32_t)V, pose_out.data_ptr<double>(), fit.data_ptr<double>(), n_obs.data_ptr<int32_t>(),
-                                        n_inlier.data_ptr<int32_t>(), weight.data_ptr<double>(), information.data_ptr<double>(), status.data_ptr<int32_t>(), sp(stream)),
-           "okp_refine_pose_views_robust");
 }
 
 // A sliding window of ticks' bearings per track slot (csrc/okp_window.hip): the camera-frame table, the assignment and status the tracker's tick had, the tracker's
@@ -1018,119 +1085,6 @@ void window_push_views(const Tensor& obs, const Tensor& assignment, const Tensor
                         nullptr, nullptr, win_views, win_i, n_views, start, nullptr, stream);
 }
 
-// The views refinement beyond one wave (csrc/okp_refine_views_wide.hip): refine_pose_views_robust's arguments with V up to 512; huber_px = 0 is the plain cost:
-// fit is then [B,max_obj,2] and n_inlier and weight may be None
-void refine_pose_views_wide(const Tensor& obs, const Tensor& views, int64_t views_each, const Tensor& pose, const Tensor& assignment, const Tensor& n_obj,
-                            const Tensor& model, double sigma_px, double huber_px, int64_t iters, double damping, const Tensor& pose_out, const Tensor& fit,
-                            const Tensor& n_obs, const optional<Tensor>& n_inlier, const optional<Tensor>& weight, const Tensor& information, const Tensor& status,
-                            int64_t stream) {
-  check_dev(obs, at::kDouble, "obs"); check_dev(views, at::kDouble, "views"); check_dev(pose, at::kDouble, "pose"); check_dev(assignment, at::kInt, "assignment");
-  check_dev(n_obj, at::kInt, "n_obj"); check_dev(model, at::kDouble, "model"); check_dev(pose_out, at::kDouble, "pose_out"); check_dev(fit, at::kDouble, "fit");
-  check_dev(n_obs, at::kInt, "n_obs"); check_dev(information, at::kDouble, "information"); check_dev(status, at::kInt, "status");
-  if (n_inlier.has_value()) check_dev(*n_inlier, at::kInt, "n_inlier");
-  if (weight.has_value()) check_dev(*weight, at::kDouble, "weight");
-  TORCH_CHECK(obs.dim() == 5 && obs.size(4) == 2, "okp: obs is [B,max_obj,S,V,2] float64");
-  const int64_t B = obs.size(0), max_obj = obs.size(1), S = obs.size(2), V = obs.size(3);
-  const bool robust = huber_px > 0.0;
-  TORCH_CHECK(views_each >= INT32_MIN && views_each <= INT32_MAX, "okp: views_each does not fit an int32");
-  TORCH_CHECK((views_each != 0 && views_each != 1) || views.numel() == (views_each == 1 ? B * max_obj : 1) * V * 14,      // (any other value: the entry point refuses it)
-              "okp: refine_pose_views_wide takes views [V,14] (views_each = 0) or [B,max_obj,V,14] (views_each = 1)");
-  TORCH_CHECK(pose.numel() == B * max_obj * 12 && assignment.numel() == B * max_obj * S && n_obj.numel() == B && model.numel() == S * 3,
-              "okp: refine_pose_views_wide inputs are pose [B,max_obj,12], assignment [B,max_obj,S], n_obj [B] and model [S,3]");
-  TORCH_CHECK(pose_out.numel() == B * max_obj * 12 && fit.numel() == B * max_obj * (robust ? 4 : 2) && n_obs.numel() == B * max_obj &&
-              information.numel() == B * max_obj * 36 && status.numel() == B * max_obj,
-              "okp: refine_pose_views_wide outputs are pose_out [B,max_obj,12], fit [B,max_obj,2] ([B,max_obj,4] with huber_px > 0), n_obs [B,max_obj], "
-              "information [B,max_obj,36] and status [B,max_obj]");
-  TORCH_CHECK((!n_inlier.has_value() || n_inlier->numel() == B * max_obj) && (!weight.has_value() || weight->numel() == B * max_obj * S * V),
-              "okp: refine_pose_views_wide writes n_inlier [B,max_obj] and weight [B,max_obj,S,V] when huber_px > 0");
-  TORCH_CHECK(iters >= INT32_MIN && iters <= INT32_MAX, "okp: iters does not fit an int32");
-  TORCH_CHECK(B <= INT32_MAX && max_obj <= INT32_MAX && S <= INT32_MAX && V <= INT32_MAX, "okp: obs is too large");
-  check_rc(okp_refine_pose_views_wide(obs.data_ptr<double>(), views.data_ptr<double>(), (int32_t)views_each, pose.data_ptr<double>(), assignment.data_ptr<int32_t>(),
-                                      n_obj.data_ptr<int32_t>(), model.data_ptr<double>(), sigma_px, huber_px, (int32_t)iters, damping, (int32_t)B, (int32_t)max_obj,
-                                      (int32_t)S, (int32_t)V, pose_out.data_ptr<double>(), fit.data_ptr<double>(), n_obs.data_ptr<int32_t>(),
-                                      n_inlier.has_value() ? n_inlier->data_ptr<int32_t>() : nullptr, weight.has_value() ? weight->data_ptr<double>() : nullptr,
-                                      information.data_ptr<double>(), status.data_ptr<int32_t>(), sp(stream)),
-           "okp_refine_pose_views_wide");
-}
-
-// ---- the views refinements weighted by the peaks' confidences (include/okp.h: okp_refine_pose_views_weighted and its three producers) ----
-
-// rig_bearings with conf_ref / conf_floor -> obs [cap_f,S,2P,2] and prior [cap_f,S,2P] float64
-void rig_bearings_weighted(const Tensor& table, const Tensor& count, const Tensor& xyc, const Tensor& match, const Tensor& member, const Tensor& object,
-                           const Tensor& n_fused, at::IntArrayRef type_count, double conf_ref, double conf_floor, const Tensor& obs, const Tensor& prior, int64_t stream) {
-  const int64_t P = stereo_tick_pairs(count, xyc);
-  const int32_t n_table = stereo_table_size(table);
-  check_dev(match, at::kInt, "match"); check_dev(member, at::kInt, "member"); check_dev(object, at::kInt, "object"); check_dev(n_fused, at::kInt, "n_fused");
-  check_dev(obs, at::kDouble, "obs"); check_dev(prior, at::kDouble, "prior");
-  const int64_t K = xyc.size(1), cap = xyc.size(2);
-  TORCH_CHECK(object.dim() == 2 && object.size(0) == K, "okp: object is [K,cap_f] int32 (rig_fuse)");
-  const int64_t cap_f = object.size(1);
-  int64_t S = 1;
-  for (auto c : type_count) S += c;
-  TORCH_CHECK((int64_t)type_count.size() == K - 1, "okp: type_count has K-1 entries");
-  TORCH_CHECK(match.numel() == P * K * cap && member.numel() == P * K * cap && n_fused.numel() == K && obs.numel() == cap_f * S * 2 * P * 2 &&
-              prior.numel() == cap_f * S * 2 * P,
-              "okp: rig_bearings_weighted buffers are match and member [P,K,cap], n_fused [K] int32, obs [cap_f,S,2P,2] and prior [cap_f,S,2P] float64");
-  std::vector<int32_t> tc(type_count.begin(), type_count.end());
-  tc.push_back(0);                                  // (K = 1: a non-null pointer for the entry point to refuse K with)
-  check_rc(okp_rig_bearings_weighted(count.data_ptr<int32_t>(), xyc.data_ptr<float>(), match.data_ptr<int32_t>(), member.data_ptr<int32_t>(), object.data_ptr<int32_t>(),
-                                     n_fused.data_ptr<int32_t>(), reinterpret_cast<const okp_stereo_pair*>(table.data_ptr()), n_table, (int32_t)P, (int32_t)K, (int32_t)cap,
-                                     (int32_t)cap_f, tc.data(), conf_ref, conf_floor, obs.data_ptr<double>(), prior.data_ptr<double>(), sp(stream)),
-           "okp_rig_bearings_weighted");
-}
-
-// refine_pose_views_wide's arguments and prior [B,max_obj,S,V]
-void refine_views_weighted(bool wide, const Tensor& obs, const Tensor& prior, const Tensor& views, int64_t views_each, const Tensor& pose, const Tensor& assignment,
-                           const Tensor& n_obj, const Tensor& model, double sigma_px, double huber_px, int64_t iters, double damping, const Tensor& pose_out,
-                           const Tensor& fit, const Tensor& n_obs, const optional<Tensor>& n_inlier, const optional<Tensor>& weight, const Tensor& information,
-                           const Tensor& status, int64_t stream) {
-  check_dev(obs, at::kDouble, "obs"); check_dev(prior, at::kDouble, "prior"); check_dev(views, at::kDouble, "views"); check_dev(pose, at::kDouble, "pose");
-  check_dev(assignment, at::kInt, "assignment"); check_dev(n_obj, at::kInt, "n_obj"); check_dev(model, at::kDouble, "model"); check_dev(pose_out, at::kDouble, "pose_out");
-  check_dev(fit, at::kDouble, "fit"); check_dev(n_obs, at::kInt, "n_obs"); check_dev(information, at::kDouble, "information"); check_dev(status, at::kInt, "status");
-  if (n_inlier.has_value()) check_dev(*n_inlier, at::kInt, "n_inlier");
-  if (weight.has_value()) check_dev(*weight, at::kDouble, "weight");
-  TORCH_CHECK(obs.dim() == 5 && obs.size(4) == 2, "okp: obs is [B,max_obj,S,V,2] float64");
-  const int64_t B = obs.size(0), max_obj = obs.size(1), S = obs.size(2), V = obs.size(3);
-  const bool robust = huber_px > 0.0;
-  TORCH_CHECK(prior.numel() == B * max_obj * S * V, "okp: prior is [B,max_obj,S,V] float64, one value per entry of obs");
-  TORCH_CHECK(views_each >= INT32_MIN && views_each <= INT32_MAX, "okp: views_each does not fit an int32");
-  TORCH_CHECK((views_each != 0 && views_each != 1) || views.numel() == (views_each == 1 ? B * max_obj : 1) * V * 14,      // (any other value: the entry point refuses it)
-              "okp: refine_pose_views_weighted takes views [V,14] (views_each = 0) or [B,max_obj,V,14] (views_each = 1)");
-  TORCH_CHECK(pose.numel() == B * max_obj * 12 && assignment.numel() == B * max_obj * S && n_obj.numel() == B && model.numel() == S * 3,
-              "okp: refine_pose_views_weighted inputs are pose [B,max_obj,12], assignment [B,max_obj,S], n_obj [B] and model [S,3]");
-  TORCH_CHECK(pose_out.numel() == B * max_obj * 12 && fit.numel() == B * max_obj * (robust ? 4 : 2) && n_obs.numel() == B * max_obj &&
-              information.numel() == B * max_obj * 36 && status.numel() == B * max_obj,
-              "okp: refine_pose_views_weighted outputs are pose_out [B,max_obj,12], fit [B,max_obj,2] ([B,max_obj,4] with huber_px > 0), n_obs [B,max_obj], "
-              "information [B,max_obj,36] and status [B,max_obj]");
-  TORCH_CHECK((!n_inlier.has_value() || n_inlier->numel() == B * max_obj) && (!weight.has_value() || weight->numel() == B * max_obj * S * V),
-              "okp: refine_pose_views_weighted writes n_inlier [B,max_obj] and weight [B,max_obj,S,V] when huber_px > 0");
-  TORCH_CHECK(iters >= INT32_MIN && iters <= INT32_MAX, "okp: iters does not fit an int32");
-  TORCH_CHECK(B <= INT32_MAX && max_obj <= INT32_MAX && S <= INT32_MAX && V <= INT32_MAX, "okp: obs is too large");
-  check_rc((wide ? okp_refine_pose_views_weighted_wide : okp_refine_pose_views_weighted)(obs.data_ptr<double>(), prior.data_ptr<double>(), views.data_ptr<double>(), (int32_t)views_each, pose.data_ptr<double>(),
-                                          assignment.data_ptr<int32_t>(), n_obj.data_ptr<int32_t>(), model.data_ptr<double>(), sigma_px, huber_px, (int32_t)iters, damping,
-                                          (int32_t)B, (int32_t)max_obj, (int32_t)S, (int32_t)V, pose_out.data_ptr<double>(), fit.data_ptr<double>(), n_obs.data_ptr<int32_t>(),
-                                          n_inlier.has_value() ? n_inlier->data_ptr<int32_t>() : nullptr, weight.has_value() ? weight->data_ptr<double>() : nullptr,
-                                          information.data_ptr<double>(), status.data_ptr<int32_t>(), sp(stream)),
-           wide ? "okp_refine_pose_views_weighted_wide" : "okp_refine_pose_views_weighted");
-}
-
-void refine_pose_views_weighted(const Tensor& obs, const Tensor& prior, const Tensor& views, int64_t views_each, const Tensor& pose, const Tensor& assignment,
-                                const Tensor& n_obj, const Tensor& model, double sigma_px, double huber_px, int64_t iters, double damping, const Tensor& pose_out,
-                                const Tensor& fit, const Tensor& n_obs, const optional<Tensor>& n_inlier, const optional<Tensor>& weight, const Tensor& information,
-                                const Tensor& status, int64_t stream) {
-  refine_views_weighted(false, obs, prior, views, views_each, pose, assignment, n_obj, model, sigma_px, huber_px, iters, damping, pose_out, fit, n_obs, n_inlier, weight,
-                        information, status, stream);
-}
-
-// the same on the wide kernel's instance whatever V is (okp_refine_pose_views_weighted_wide)
-void refine_pose_views_weighted_wide(const Tensor& obs, const Tensor& prior, const Tensor& views, int64_t views_each, const Tensor& pose, const Tensor& assignment,
-                                     const Tensor& n_obj, const Tensor& model, double sigma_px, double huber_px, int64_t iters, double damping, const Tensor& pose_out,
-                                     const Tensor& fit, const Tensor& n_obs, const optional<Tensor>& n_inlier, const optional<Tensor>& weight, const Tensor& information,
-                                     const Tensor& status, int64_t stream) {
-  refine_views_weighted(true, obs, prior, views, views_each, pose, assignment, n_obj, model, sigma_px, huber_px, iters, damping, pose_out, fit, n_obs, n_inlier, weight,
-                        information, status, stream);
-}
-
 // window_push with conf_ref / conf_floor and the state win_prior [B,T,S,W]
 void window_push_weighted(at::ArrayRef<double> camera, const Tensor& tab, const Tensor& assignment, const Tensor& status, const Tensor& meas_of, const Tensor& track_i,
                           const Tensor& track_f, const Tensor& track_pose, const Tensor& T_WC, int64_t min_views, double max_speed, double conf_ref, double conf_floor,
@@ -1176,8 +1130,7 @@ void refine_motion_views(const Tensor& obs, const Tensor& views, const Tensor& a
   check_dev(velocity, at::kDouble, "velocity"); check_dev(assignment, at::kInt, "assignment"); check_dev(n_obj, at::kInt, "n_obj"); check_dev(model, at::kDouble, "model");
   check_dev(pose_out, at::kDouble, "pose_out"); check_dev(velocity_out, at::kDouble, "velocity_out"); check_dev(fit, at::kDouble, "fit"); check_dev(n_obs, at::kInt, "n_obs");
   check_dev(information, at::kDouble, "information"); check_dev(status, at::kInt, "status");
-  TORCH_CHECK(obs.dim() == 5 && obs.size(4) == 2, "okp: obs is [B,max_obj,S,V,2] float64");
-  const int64_t B = obs.size(0), max_obj = obs.size(1), S = obs.size(2), V = obs.size(3);
+  const auto [B, max_obj, S, V] = views_dims(obs);
   TORCH_CHECK(views.numel() == B * max_obj * V * 14 && age.numel() == B * max_obj * V && pose.numel() == B * max_obj * 12 && velocity.numel() == B * max_obj * 3 &&
               assignment.numel() == B * max_obj * S && n_obj.numel() == B && model.numel() == S * 3,
               "okp: refine_motion_views inputs are views [B,max_obj,V,14], age [B,max_obj,V], pose [B,max_obj,12], velocity [B,max_obj,3], assignment [B,max_obj,S], "

@@ -1877,10 +1877,7 @@ def rig_bearings(table, count, xyc, match, fused, type_count):
     match [P,K,cap] int32 (stereo_match_rig), fused: rig_fuse()'s dict ("member", "object" and "n_fused" are read), type_count: the K-1 counts
     -> obs [1, cap_f, S, 2P, 2] float64 (device): the undistorted normalised image coordinates of slot s of object o in camera v (2p: the left
     camera of pair p), (NaN, NaN) where the camera did not see it.  Every word is written.  One launch, no host sync."""
-    args, cap_f, s, n_pairs, dev = _rig_bearings_inputs(table, count, xyc, match, fused, type_count)
-    obs = torch.empty((1, cap_f, s, 2 * n_pairs, 2), dtype=torch.float64, device=dev)
-    _dispatch(_ops().rig_bearings, *args, obs, stream_int())
-    return obs
+    return _rig_bearings(table, count, xyc, match, fused, type_count, None)[0]
 
 
 def rig_bearings_weighted(table, count, xyc, match, fused, type_count, confidence):
@@ -1890,8 +1887,16 @@ def rig_bearings_weighted(table, count, xyc, match, fused, type_count, confidenc
     written.  One launch, no host sync."""
     if not isinstance(confidence, ConfidenceWeights):
         raise OkpError("confidence must be an ops.ConfidenceWeights")
+    return _rig_bearings(table, count, xyc, match, fused, type_count, confidence)
+
+
+def _rig_bearings(table, count, xyc, match, fused, type_count, confidence):
+    """The body behind rig_bearings (confidence None) and rig_bearings_weighted: the shared checks, the outputs, one launch -> (obs, prior or None)."""
     args, cap_f, s, n_pairs, dev = _rig_bearings_inputs(table, count, xyc, match, fused, type_count)
     obs = torch.empty((1, cap_f, s, 2 * n_pairs, 2), dtype=torch.float64, device=dev)
+    if confidence is None:
+        _dispatch(_ops().rig_bearings, *args, obs, stream_int())
+        return obs, None
     prior = torch.empty((1, cap_f, s, 2 * n_pairs), dtype=torch.float64, device=dev)
     _dispatch(_ops().rig_bearings_weighted, *args, confidence.ref, confidence.floor, obs, prior, stream_int())
     return obs, prior
@@ -1911,7 +1916,7 @@ def refine_pose_views(obs, views, pose, n_obj, model, cfg):
     pixels - and the dict has the same keys with "fit" as [B,max_obj,4] (the two values above, then the rmse of the robust cost before and
     after), plus "n_inlier" [B,max_obj] int32 (bearings inside the threshold at the refined pose) and "weight" [B,max_obj,S,V] float64 (the
     weight of every bearing there: exactly 1.0 for an inlier, NaN where there is no observation or the status is not 0)."""
-    return _refine_views(False, obs, views, pose, n_obj, model, cfg)
+    return _refine_views("one wave", False, obs, None, views, pose, n_obj, model, cfg)
 
 
 def refine_pose_views_each(obs, views, pose, n_obj, model, cfg):
@@ -1920,7 +1925,7 @@ def refine_pose_views_each(obs, views, pose, n_obj, model, cfg):
     RefineConfig or a WindowConfig (sigma_px, iters and damping are read).  A view none of whose entries is filled contributes nothing,
     whatever its row holds.  With one table replicated per object the result has the bits of refine_pose_views.  One launch, no host sync.
     cfg.huber_px selects the Huber sibling as it does there (views_each = 1)."""
-    return _refine_views(True, obs, views, pose, n_obj, model, cfg)
+    return _refine_views("one wave", True, obs, None, views, pose, n_obj, model, cfg)
 
 
 def _views_inputs(each, obs, views, pose, n_obj, model, cfg, cfg_types, cfg_text, max_views, obs_from, views_from, prior=None, motion=False):
@@ -1982,20 +1987,34 @@ def _views_outputs(b, max_obj, s, v, dev, robust):
     return out
 
 
-def _refine_views(each, obs, views, pose, n_obj, model, cfg):
-    fitted, assignment, b, max_obj, s, v, dev = _views_inputs(
-        each, obs, views, pose, n_obj, model, cfg, (RefineConfig, WindowConfig) if each else RefineConfig,
-        "an ops.RefineConfig" + (" or an ops.WindowConfig" if each else ""), REFINE_MAX_VIEWS, "rig_bearings", " (rig_views)")
+def _refine_views(kind, each, obs, prior, views, pose, n_obj, model, cfg, wide=False):
+    """The body behind the four refinements against views: the shared checks, the dict, one launch (of three forms of argument list).  kind: "one wave" (refine_pose_views and
+    refine_pose_views_each: up to REFINE_MAX_VIEWS views, and the entry point without views_each unless cfg.huber_px asks for the Huber one),
+    "wide" (refine_pose_views_wide) or "weighted" (refine_pose_views_weighted: the prior, and `wide` for the wide kernel's instance)."""
+    if kind == "one wave":
+        fitted, assignment, b, max_obj, s, v, dev = _views_inputs(
+            each, obs, views, pose, n_obj, model, cfg, (RefineConfig, WindowConfig) if each else RefineConfig,
+            "an ops.RefineConfig or an ops.WindowConfig" if each else "an ops.RefineConfig", REFINE_MAX_VIEWS, "rig_bearings", " (rig_views)")
+    else:
+        fitted, assignment, b, max_obj, s, v, dev = _views_inputs(
+            each, obs, views, pose, n_obj, model, cfg, (RefineConfig, WindowConfig), "an ops.RefineConfig or an ops.WindowConfig", REFINE_WIDE_MAX_VIEWS,
+            "rig_bearings_weighted, or the win_obs of a window's state" if kind == "weighted" else "rig_bearings, or the win_obs of window_views_state", "", prior)
     B = _ops()
     huber_px = getattr(cfg, "huber_px", None)
     out = _views_outputs(b, max_obj, s, v, dev, huber_px is not None)
-    if huber_px is not None:                     # the Huber instance: one launch, the plain keys (fit with four values) and the two it adds
-        _dispatch(B.refine_pose_views_robust, obs.contiguous(), views.contiguous(), 1 if each else 0, fitted.contiguous(), assignment.contiguous(),
-                  n_obj.reshape(b).contiguous(), model.contiguous(), cfg.sigma_px, huber_px, cfg.iters, cfg.damping, out["pose"], out["fit"], out["n_obs"], out["n_inlier"],
-                  out["weight"], out["information"], out["status"], stream_int())
+    obs, views, fitted, assignment, n_obj, model = obs.contiguous(), views.contiguous(), fitted.contiguous(), assignment.contiguous(), n_obj.reshape(b).contiguous(), model.contiguous()
+    if kind == "one wave" and huber_px is None:  # the two entry points without views_each, a threshold, n_inlier and weight
+        _dispatch(B.refine_pose_views_each if each else B.refine_pose_views, obs, views, fitted, assignment, n_obj, model, cfg.sigma_px, cfg.iters, cfg.damping,
+                  out["pose"], out["fit"], out["n_obs"], out["information"], out["status"], stream_int())
+        return out
+    views_each, threshold = 1 if each else 0, huber_px if huber_px is not None else 0.0          # (beyond one wave 0 is the plain cost, which writes neither n_inlier nor weight)
+    if kind == "weighted":
+        _dispatch(B.refine_pose_views_weighted_wide if wide else B.refine_pose_views_weighted, obs, prior.contiguous(), views, views_each, fitted, assignment, n_obj, model,
+                  cfg.sigma_px, threshold, cfg.iters, cfg.damping, out["pose"], out["fit"], out["n_obs"], out.get("n_inlier"), out.get("weight"), out["information"],
+                  out["status"], stream_int())
     else:
-        _dispatch(B.refine_pose_views_each if each else B.refine_pose_views, obs.contiguous(), views.contiguous(), fitted.contiguous(), assignment.contiguous(),
-                  n_obj.reshape(b).contiguous(), model.contiguous(), cfg.sigma_px, cfg.iters, cfg.damping, out["pose"], out["fit"], out["n_obs"], out["information"],
+        _dispatch(B.refine_pose_views_robust if kind == "one wave" else B.refine_pose_views_wide, obs, views, views_each, fitted, assignment, n_obj, model,
+                  cfg.sigma_px, threshold, cfg.iters, cfg.damping, out["pose"], out["fit"], out["n_obs"], out.get("n_inlier"), out.get("weight"), out["information"],
                   out["status"], stream_int())
     return out
 
@@ -2299,15 +2318,7 @@ def refine_pose_views_wide(obs, views, pose, n_obj, model, cfg, each=False):
     the statuses and the returned dict are theirs; cfg: a RefineConfig or a WindowConfig, whose huber_px selects the Huber instance as it
     does there ("fit" with four values, "n_inlier", "weight").  For 32 < V <= 64 the result has the bits of those entry points.  One launch,
     no host sync."""
-    fitted, assignment, b, max_obj, s, v, dev = _views_inputs(
-        each, obs, views, pose, n_obj, model, cfg, (RefineConfig, WindowConfig), "an ops.RefineConfig or an ops.WindowConfig", REFINE_WIDE_MAX_VIEWS,
-        "rig_bearings, or the win_obs of window_views_state", "")
-    huber_px = getattr(cfg, "huber_px", None)
-    out = _views_outputs(b, max_obj, s, v, dev, huber_px is not None)
-    _dispatch(_ops().refine_pose_views_wide, obs.contiguous(), views.contiguous(), 1 if each else 0, fitted.contiguous(), assignment.contiguous(),
-              n_obj.reshape(b).contiguous(), model.contiguous(), cfg.sigma_px, huber_px if huber_px is not None else 0.0, cfg.iters, cfg.damping, out["pose"], out["fit"],
-              out["n_obs"], out.get("n_inlier"), out.get("weight"), out["information"], out["status"], stream_int())
-    return out
+    return _refine_views("wide", each, obs, None, views, pose, n_obj, model, cfg)
 
 
 def refine_pose_views_weighted(obs, prior, views, pose, n_obj, model, cfg, each=False, wide=False):
@@ -2323,15 +2334,7 @@ def refine_pose_views_weighted(obs, prior, views, pose, n_obj, model, cfg, each=
     One launch, no host sync."""
     if not isinstance(wide, (bool, np.bool_)):
         raise OkpError(f"wide = {wide!r} must be True (the wide kernel whatever V is) or False")
-    fitted, assignment, b, max_obj, s, v, dev = _views_inputs(
-        each, obs, views, pose, n_obj, model, cfg, (RefineConfig, WindowConfig), "an ops.RefineConfig or an ops.WindowConfig", REFINE_WIDE_MAX_VIEWS,
-        "rig_bearings_weighted, or the win_obs of a window's state", "", prior=prior)
-    huber_px = getattr(cfg, "huber_px", None)
-    out = _views_outputs(b, max_obj, s, v, dev, huber_px is not None)
-    _dispatch(_ops().refine_pose_views_weighted_wide if wide else _ops().refine_pose_views_weighted, obs.contiguous(), prior.contiguous(), views.contiguous(), 1 if each else 0, fitted.contiguous(),
-              assignment.contiguous(), n_obj.reshape(b).contiguous(), model.contiguous(), cfg.sigma_px, huber_px if huber_px is not None else 0.0, cfg.iters,
-              cfg.damping, out["pose"], out["fit"], out["n_obs"], out.get("n_inlier"), out.get("weight"), out["information"], out["status"], stream_int())
-    return out
+    return _refine_views("weighted", each, obs, prior, views, pose, n_obj, model, cfg, wide)
 
 
 def refine_motion_views(obs, views, age, start, n_obj, model, cfg, dt):

@@ -801,6 +801,16 @@ class _Tracker:
                 t.zero_()
 
 
+def _refine_static(cfg, each, wide, obs, prior, views, start, n_obj, model):
+    """The one launch that refines static objects against views under cfg -> its dict: with cfg.confidence the weighted refinement, on the bearings'
+    priors (a push under it kept the ring of them); otherwise the plain one of the same shape (each: a views table per object; wide: beyond one wave)."""
+    if cfg.confidence is not None:
+        return ops.refine_pose_views_weighted(obs, prior, views, start, n_obj, model, cfg, each=each, wide=wide)
+    if wide:
+        return ops.refine_pose_views_wide(obs, views, start, n_obj, model, cfg, each=each)
+    return (ops.refine_pose_views_each if each else ops.refine_pose_views)(obs, views, start, n_obj, model, cfg)
+
+
 class _Window:
     """The device state of a pipeline's sliding window, one ops.window_state per (device, streams), created on first use and kept for the
     pipeline's life like the tracker's: captured steps hold these very tensors, so reset() empties them in place."""
@@ -849,10 +859,7 @@ class _Window:
         if self.cfg.motion is not None:
             return self._moving(st, pushed, model, T_WC, "pose_C")
         start = {"pose": pushed["start"], "assignment": st["win_assignment"]}
-        if self.cfg.confidence is not None:      # the push kept the ring of priors: the weighted refinement, one launch as well
-            refined = ops.refine_pose_views_weighted(st["win_obs"], st["win_prior"], st["win_views"], start, st["win_n"], model, self.cfg, each=True)
-        else:
-            refined = ops.refine_pose_views_each(st["win_obs"], st["win_views"], start, st["win_n"], model, self.cfg)
+        refined = _refine_static(self.cfg, True, False, st["win_obs"], st.get("win_prior"), st["win_views"], start, st["win_n"], model)
         return self._static(st, pushed, refined, T_WC, "pose_C")
 
     def reset(self):
@@ -890,10 +897,7 @@ class _RigWindow(_Window):
             out["tick_obs"] = obs
             return out
         start = {"pose": pushed["start"], "assignment": st["win_assignment"]}
-        if self.cfg.confidence is not None:      # the push kept the ring of priors: the weighted refinement, one launch as well
-            refined = ops.refine_pose_views_weighted(st["win_obs"], st["win_prior"], st["win_views"], start, st["win_n"], model, self.cfg, each=True, wide=True)
-        else:
-            refined = ops.refine_pose_views_wide(st["win_obs"], st["win_views"], start, st["win_n"], model, self.cfg, each=True)
+        refined = _refine_static(self.cfg, True, True, st["win_obs"], st.get("win_prior"), st["win_views"], start, st["win_n"], model)
         out = self._static(st, pushed, refined, T_WB, "pose_B", tick_obs=obs)
         if "win_prior" in st:                    # cfg.confidence: next to the ring of priors, the tick's
             out.update(tick_prior=prior)
@@ -1014,10 +1018,11 @@ class _ObjectStage:
                     if self.resolver is not None:                # every assignment against all cameras' bearings: the pose and assignment of the least cost
                         resolved = ops.refine_assignments_views(obs, rig["views"], tab, fed, n_obj, model, self.type_count, self.resolver)
                         start = dict(fed, pose=resolved["pose"], assignment=resolved["assignment"])      # (the fit's where the resolver's status is not 0)
-                    if self.refine.confidence is not None:
-                        out["refine"] = dict(ops.refine_pose_views_weighted(obs, prior, rig["views"], start, n_obj, model, self.refine_after), obs=obs, prior=prior)
-                    elif resolved is None or self.refine.huber_px is not None:
-                        out["refine"] = dict(ops.refine_pose_views(obs, rig["views"], start, n_obj, model, self.refine_after), obs=obs)
+                    weighted = self.refine.confidence is not None
+                    if weighted or resolved is None or self.refine.huber_px is not None:
+                        out["refine"] = dict(_refine_static(self.refine_after, False, False, obs, prior, rig["views"], start, n_obj, model), obs=obs)
+                        if weighted:
+                            out["refine"]["prior"] = prior
                     else:                                        # neither a Huber loss nor priors: the resolver is the whole refinement
                         out["refine"] = dict(resolved, obs=obs)
                     if resolved is not None:

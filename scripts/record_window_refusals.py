@@ -16,6 +16,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 sys.path.insert(0, os.path.join(REPO, "tests"))
 
+import refusal_record                                                    # noqa: E402
 import window_refusal_cases as cases                                     # noqa: E402
 
 
@@ -29,7 +30,7 @@ def main():
     c = [cases.run_c(L, case) for case in cases.c_cases()]
     o = [cases.run_ops(case) for case in cases.ops_cases()]
     with open(args.out, "w") as f:
-        f.write(cases.dumps(cases.pack(c, o)))
+        f.write(refusal_record.dumps(refusal_record.pack(cases.c_cases(), cases.ops_cases(), c, o)))
     print(f"{args.out}: {len(c)} C cases, {len(o)} ops cases, {os.path.getsize(args.out)} bytes")
 
 

@@ -67,12 +67,12 @@ def _cfg(params, confidence=True):
     return ops.RefineConfig(**kw)
 
 
-def _weighted(case, prior=None):
+def _weighted(case, prior=None, wide=False):
     from object_keypoints_amd import ops
     d = {k: _dev(case[k]) for k in INPUTS}
     p = _dev(case["prior"]) if prior is None else prior
     out = ops.refine_pose_views_weighted(d["obs"], p, d["views"], {"pose": d["pose"], "assignment": d["assignment"]}, d["n_obj"], d["model"], _cfg(case["params"]),
-                                         each=case["views"].ndim == 4)
+                                         each=case["views"].ndim == 4, wide=wide)
     torch.cuda.synchronize()
     return out
 
@@ -135,6 +135,15 @@ def test_runs_and_bindings_give_the_same_bits(monkeypatch):
             b = _weighted(case)
         assert ops.COUNTERS["ctypes_launches"] == before + 1
         _same_bits(b, a, (case["name"], "ctypes"))
+    for case in (by["b3_obj64_n_0_5_64_huber"], by["each_b3_obj64_free_slots_plain"]):              # wide=True: okp_refine_pose_views_weighted_wide, at the same shapes
+        a = _weighted(case, wide=True)
+        _same_bits(_weighted(case, wide=True), a, (case["name"], "wide"))
+        before = ops.COUNTERS["ctypes_launches"]
+        with monkeypatch.context() as m:
+            m.setattr(_lib, "torch_ops", lambda: None)
+            b = _weighted(case, wide=True)
+        assert ops.COUNTERS["ctypes_launches"] == before + 1
+        _same_bits(b, a, (case["name"], "wide", "ctypes"))
 
 
 # ---- all priors 1.0: the bits of the unweighted entry points, on their own cases ------------------------------------------------------------------

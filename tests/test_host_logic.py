@@ -378,6 +378,8 @@ def test_ctypes_adapter_speaks_the_dispatcher_signatures():
     adapter = {n: f for n, f in vars(_ctypes_ops).items() if inspect.isfunction(f) and f.__module__ == _ctypes_ops.__name__ and not n.startswith("_")}
     called = set(re.findall(r"\b(?:_ops\(\)|B)\.([a-z0-9_]+)", inspect.getsource(ops)))
     assert len(called) >= 38 and {"conv_forward", "conv_create", "stem_set_range_flag", "keypoint_loss", "rig_fuse"} <= called, sorted(called)
+    assert {"rig_bearings", "rig_bearings_weighted", "refine_pose_views", "refine_pose_views_each", "refine_pose_views_robust", "refine_pose_views_wide",
+            "refine_pose_views_weighted", "refine_pose_views_weighted_wide"} <= called, sorted(called)      # the family behind one body: none dropped from this view
     assert called <= set(adapter), f"ops.py calls {sorted(called - set(adapter))}, which the ctypes adapter does not define"
     for name, fn in sorted(adapter.items()):
         assert hasattr(T, name), f"_ctypes_ops.{name} is not a schema of okp_torch.cpp"

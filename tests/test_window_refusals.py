@@ -7,11 +7,12 @@ cases.  Equality of code and text, case by case, no case left out.  No GPU neede
 import json
 import os
 
+import refusal_record
 import window_refusal_cases as cases
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 with open(os.path.join(REPO, "tests", "golden", "window_push_refusals.json")) as f:
-    C, OPS = cases.unpack(json.load(f))              # [(case, [rc, text])], [(case, text)]: the file holds the answers, the module the cases (tied by a digest)
+    C, OPS = refusal_record.unpack(json.load(f), cases.c_cases(), cases.ops_cases())              # [(case, [rc, text])], [(case, text)]: the file holds the answers, the module the cases (tied by a digest)
 
 
 def test_the_record_holds_every_case_and_only_refusals():

@@ -12,7 +12,8 @@ tests/golden/window_push_refusals.json and tests/test_window_refusals.py replays
         do the same job for the pipelines); the launch itself is replaced by a stub that fails the case, so none can reach the device.
 
 A case is JSON: C cases {"fn", "set": {scalar: value}, "null": [pointer names]}; ops cases {"fn", "cfg", "faults": [[argument, kind], ..]} or
-{"fn", "args": [..]} for the state constructors.  nan and the infinities are written as strings.  No GPU needed."""
+{"fn", "args": [..]} for the state constructors.  nan and the infinities are written as strings.  The record itself - digest, pack, unpack,
+dumps - is tests/refusal_record.py's.  No GPU needed."""
 import ctypes
 import itertools
 
@@ -205,41 +206,3 @@ def run_ops(case):
     finally:
         ops._dispatch = real
     raise AssertionError(f"{case}: not refused")
-
-
-# ---- the record ---------------------------------------------------------------------------------------------------------------------------------
-
-def digest(cases):
-    """What ties a record to the list of cases it was made from: the cases are not in the file, their order is."""
-    import hashlib
-    import json
-    return hashlib.sha256(json.dumps(cases, sort_keys=True).encode()).hexdigest()
-
-
-def pack(c_results, ops_results):
-    """[[rc, text]] of c_cases() and [text] of ops_cases(), in their order -> the record: every distinct answer once (a C text without the
-    "<entry point>: " it begins with), and per case the index of its answer."""
-    c = [[rc, text[len(case["fn"]) + 2:]] for case, (rc, text) in zip(c_cases(), c_results) if text.startswith(case["fn"] + ": ")]
-    assert len(c) == len(c_results) == len(c_cases()) and len(ops_results) == len(ops_cases())
-    answers = sorted({(rc, text) for rc, text in c}) + sorted({(None, text) for text in ops_results}, key=lambda a: a[1])
-    index = {a: i for i, a in enumerate(answers)}
-    return {"c_cases": digest(c_cases()), "ops_cases": digest(ops_cases()), "answers": [list(a) for a in answers],
-            "c": [index[(rc, text)] for rc, text in c], "ops": [index[(None, text)] for text in ops_results]}
-
-
-def unpack(record):
-    """The record -> ([(case, [rc, text])] of the C cases, [(case, text)] of the ops cases); refuses a record made from another list of cases."""
-    c, o = c_cases(), ops_cases()
-    assert record["c_cases"] == digest(c) and record["ops_cases"] == digest(o), "the record was made from another list of cases: record again at the commit before the change"
-    assert len(record["c"]) == len(c) and len(record["ops"]) == len(o)
-    answer = record["answers"]
-    return ([(case, [answer[i][0], case["fn"] + ": " + answer[i][1]]) for case, i in zip(c, record["c"])],
-            [(case, answer[i][1]) for case, i in zip(o, record["ops"])])
-
-
-def dumps(record):
-    """The record as text: an answer per line, the indices forty to a line."""
-    import json
-    rows = lambda v: ",\n".join("  " + ", ".join(map(str, v[i:i + 40])) for i in range(0, len(v), 40))
-    return ('{"c_cases": "%s",\n"ops_cases": "%s",\n"answers": [\n' % (record["c_cases"], record["ops_cases"]) + ",\n".join("  " + json.dumps(a) for a in record["answers"])
-            + '\n],\n"c": [\n' + rows(record["c"]) + '\n],\n"ops": [\n' + rows(record["ops"]) + "\n]}\n")
